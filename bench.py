@@ -17,8 +17,11 @@ ranges, fused pruned lattice) -> backward -> bucketed RCCL gradient all-reduce (
 grad-norm clip 5.0 -> ScaledAdam step -> Eden step.  Weak scaling: per-GPU work is fixed.
 `--config C2` times the conformer-CTC step (12 layers, d=256, B=32) instead; the headline is C3.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the roofline / cpu_baseline
-objects).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and reports
+them (value, ms_per_step, config); `--full` adds the CPU baseline (oracle) and the roofline block
+(see DESIGN.md "Measurement" for the roofline / cpu_baseline objects), which cost runs of their own.
+`--dump-outputs DIR` writes the last timed step's loss, updated parameters and reduced gradient as .npy;
+that step is given the run's start state, so it has the same inputs in every run (StartState).
 """
 import argparse
 import json
@@ -548,6 +551,105 @@ def gemm_paths():
             "lt_own_calls": int(zk.lt_own_calls()), "aten_fallbacks": int(zk.LT_STATS["aten_fallbacks"])}
 
 
+_PLAIN = (bool, int, float, str, type(None))
+
+
+class StartState:
+    """The state a run's first step starts from: the same in every run with the same arguments
+    (host-side seeded initialisation, seeded batch).  --dump-outputs puts it back before the LAST timed
+    step, so that the step whose outputs are written has the same inputs in every run.  Without that, its
+    inputs are what the earlier steps trained, and that differs from run to run: the library's gradient
+    reductions use float atomics (summation order varies), and training on one repeated batch amplifies
+    that rounding until the loss itself differs (measured on C3: 6e-5 relative after 23 steps, 14.1
+    against 30.4 after 55).  The state: every parameter and buffer, every module's plain-valued attributes
+    (Whiten.prob, counters, the task's global_step), the optimizer and LR scheduler (fresh, as
+    Trainer.setup made them: neither has stepped yet) and the random streams."""
+
+    def __init__(self, task, device):
+        import torch
+        self.task, self.device = task, device
+        self.tensors = {k: v.detach().clone() for k, v in self._named_tensors()}
+        self.attrs = [(m, {k: v for k, v in vars(m).items() if isinstance(v, _PLAIN)})
+                      for m in task.modules()]
+        self.rng = (random.getstate(), np.random.get_state(), torch.get_rng_state(),
+                    torch.cuda.get_rng_state(device) if device.type == "cuda" else None)
+
+    def _named_tensors(self):
+        yield from self.task.named_parameters()
+        yield from (("buffer:" + k, v) for k, v in self.task.named_buffers())
+
+    def restore(self, trainer):
+        import torch
+        with torch.no_grad():
+            for k, v in self._named_tensors():                # in place: views of the flat store
+                v.copy_(self.tensors[k])
+        trainer.store.epoch += 1                              # the weights' bf16 pieces are rewritten
+        trainer.store.zero_grad()
+        for m, attrs in self.attrs:
+            m.__dict__.update(attrs)
+        old = trainer.optimizer
+        opt = self.task.configure_optimizers()
+        new = opt["optimizer"]
+        for k in ("pre_clip", "zero_grad_in_step"):           # Trainer.setup's wiring of the fused step
+            if hasattr(old, k):
+                setattr(new, k, getattr(old, k))
+        trainer.optimizer, trainer.scheduler = new, opt["lr_scheduler"]["scheduler"]
+        if hasattr(new, "_init"):
+            new._init()                                       # ScaledAdam's flat state, made at its first step
+        random.setstate(self.rng[0])
+        np.random.set_state(self.rng[1])
+        torch.set_rng_state(self.rng[2])
+        if self.rng[3] is not None:
+            torch.cuda.set_rng_state(self.rng[3], self.device)
+
+    @staticmethod
+    def keep_gradient(trainer):
+        """-> dict that receives 'grad', a copy of the reduced (and not yet clipped) flat gradient, when the
+        next optimizer step starts (the fused step zeroes the gradient as it applies it)."""
+        keep = {}
+        opt = trainer.optimizer
+        step = opt.step
+
+        def step_keeping_gradient(*a, **k):
+            keep["grad"] = trainer.store.flat_g.clone()
+            opt.step = step
+            return step(*a, **k)
+
+        opt.step = step_keeping_gradient
+        return keep
+
+
+def dump_outputs(outdir, loss, task, store, grad, cap_bytes=48 * 2**20, seed=20241218):
+    """What the last timed step computed, for comparing two builds output for output:
+      loss.npy    the loss Trainer.training_step returned (float64, shape (1,));
+      params.npy  the trainable parameters after the step's optimizer update, float32, flattened and
+                  concatenated in task.named_parameters() order;
+      grads.npy   the reduced gradient the update was made from, same order and indices.
+    When the two arrays together would exceed `cap_bytes`, both hold the same fixed sample of their
+    elements (sorted indices drawn by a generator seeded with `seed`).  -> (files written, bytes)."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    where = {id(p): (o, n) for p, o, n in zip(store.params, store.offsets, store.lengths)}
+    spans = [where[id(p)] for _, p in task.named_parameters() if id(p) in where]
+    total = sum(n for _, n in spans)
+    k = min(total, cap_bytes // 8)
+    idx = None
+    if k < total:
+        idx = np.sort(np.random.default_rng(seed).choice(total, k, replace=False))
+        idx = torch.from_numpy(idx).to(store.flat_p.device)
+
+    def gather(flat):
+        v = torch.cat([flat[o:o + n] for o, n in spans])
+        return (v if idx is None else v[idx]).to(torch.float32).cpu().numpy()
+
+    arrays = {"loss": np.asarray([float(loss)], np.float64), "params": gather(store.flat_p)}
+    if grad is not None:
+        arrays["grads"] = gather(grad)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return len(arrays), sum(a.nbytes for a in arrays.values())
+
+
 # ------------------------------------------------------------------ launcher
 def self_launch(args, argv):
     """--gpus N>1 outside a launcher: start N ranks in child processes (this parent never
@@ -625,6 +727,17 @@ def parse_args(argv=None):
                          "tools/gpu_pmc2.sh use it so that traffic and algorithmic bytes cover the "
                          "same launches)")
     ap.add_argument("--launcher-selftest", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baseline (oracle) and report the roofline block (entry "
+                         "point chosen in the last warm-up step, sampled inside the timed region, "
+                         "--profile-steps extra profiled steps); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (loss, parameters after the update, "
+                         "reduced gradient; a fixed seeded sample of the last two) as DIR/<name>.npy. "
+                         "That step starts from the run's start state (StartState: weights, module "
+                         "state, a fresh optimizer and scheduler, random streams), restored with the "
+                         "clock stopped; the step itself stays timed and includes one copy of the flat "
+                         "gradient; config.final_loss stays the loss after the trained steps")
     args = ap.parse_args(argv)
     # per-rank batch, labels per utterance, vocabulary, utterance seconds
     d = {"C3": (64, 50, 500, 10.0), "C2": (32, 40, 128, 10.0), "C4": (16, 60, 128, 10.0),
@@ -694,7 +807,7 @@ def main(argv=None):
     torch.manual_seed(1234)                                 # same init on every rank
     task = TaskFactory.get(cfg["task"]["type"])(cfg)        # parameters are created on the host
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         note("timing the CPU baseline (oracle) ...")
         try:
             if args.config == "C3":
@@ -724,6 +837,7 @@ def main(argv=None):
             dist.barrier()
         torch.cuda.synchronize()
 
+    start = StartState(task, device) if args.dump_outputs else None
     note("model + synthetic batch ready; warmup ...")
     loss = None
     want = args.roofline_kernel
@@ -731,11 +845,11 @@ def main(argv=None):
     for i in range(args.warmup):
         tw = time.perf_counter()
         last = i == args.warmup - 1
-        if last and want == "auto":
+        if args.full and last and want == "auto":
             _native.profile_begin("*")
         loss = trainer.training_step(batch, i)
         torch.cuda.synchronize()
-        if last and want == "auto":
+        if args.full and last and want == "auto":
             pw = _native.profile_end()
             cand = {k: v for k, v in pw.items() if v["algo_bytes"] > 0}
             want = max(cand, key=lambda k: cand[k]["total_ms"]) if cand else "s2t_relpos_attn_fwd"
@@ -743,7 +857,7 @@ def main(argv=None):
         note(f"warmup step {i}: {time.perf_counter() - tw:.3f} s, loss {float(loss):.4f}")
     if want == "auto":
         want = "s2t_relpos_attn_fwd"
-    if world > 1:                                           # every rank brackets the SAME entry
+    if args.full and world > 1:                             # every rank brackets the SAME entry
         names = sorted(_native.parse_header())
         t = torch.tensor([names.index(want)], device=device, dtype=torch.int64)
         dist.broadcast(t, src=0)
@@ -759,20 +873,35 @@ def main(argv=None):
         while want_launches % every == 0 or (every > 2 and every % 2 == 0):
             every += 1
     sync()
-    _native.profile_begin(want, every)
+    if args.full:
+        _native.profile_begin(want, every)
     t0 = time.perf_counter()
+    paused, kept, trained_loss = 0.0, {}, None
     for i in range(args.steps):
+        if start is not None and i == args.steps - 1:
+            # the dumped step gets the run's start state (the same inputs every run); the clock stops
+            # for the restore.  The step itself stays timed, with one copy of the flat gradient in it.
+            sync()
+            tp = time.perf_counter()
+            trained_loss = None if loss is None else float(loss)
+            start.restore(trainer)
+            kept = start.keep_gradient(trainer)
+            sync()
+            paused += time.perf_counter() - tp
         loss = trainer.training_step(batch, args.warmup + i)
     sync()
-    dt = time.perf_counter() - t0
-    prof_timed = _native.profile_end()
+    dt = time.perf_counter() - t0 - paused
+    prof_timed = _native.profile_end() if args.full else {}
     if world > 1:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    final_loss = float(loss)
+    final_loss = float(loss) if start is None else trained_loss   # the loss after K steps of training
+    if args.dump_outputs and rank == 0:                     # before the profiled steps move the weights
+        n_files, n_bytes = dump_outputs(args.dump_outputs, loss, task, trainer.store, kept.get("grad"))
+        note(f"wrote {n_files} arrays ({n_bytes / 2**20:.1f} MiB) to {args.dump_outputs}")
     prof_all = {}
-    if args.profile_steps > 0:                              # every rank: the step has collectives
+    if args.full and args.profile_steps > 0:                # every rank: the step has collectives
         _native.profile_begin("*")
         for i in range(args.profile_steps):
             trainer.training_step(batch, args.warmup + args.steps + i)
@@ -814,12 +943,16 @@ def main(argv=None):
                        "per_gpu_batch": args.batch, "global_batch": args.batch * world,
                        "utterance_seconds": args.seconds, "labels_per_utt": args.labels,
                        "parallelism": f"dp{world}", "final_loss": final_loss},
-            "roofline": roofline_report(prof_timed, prof_all, want, step_flops, ms, every),
-            "cpu_baseline": cpu if cpu is not None else {
+        }
+        if start is not None:
+            # the last timed step ran from the start state (--dump-outputs): its loss, not final_loss's
+            out["config"]["dumped_step_loss"] = float(loss)
+        if args.full:
+            out["roofline"] = roofline_report(prof_timed, prof_all, want, step_flops, ms, every)
+            out["cpu_baseline"] = cpu if cpu is not None else {
                 "value": None, "unit": "audio-seconds/sec", "cores": host_threads(), "kind": "port",
                 "sample": "not timed in this run (multi-rank or --no-cpu-baseline): the oracle "
-                          "step is timed on rank 0 of the N=1 run, see that line"},
-        }
+                          "step is timed on rank 0 of the N=1 run, see that line"}
         print(json.dumps(out), flush=True)
     if world > 1 or args.ddp_force:
         dist.destroy_process_group()

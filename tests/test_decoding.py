@@ -63,13 +63,12 @@ def test_ssl_metric_topk_host_logic():
     assert float(none["top_1_acc"]) == 0.0
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/sample_data/spm/tokenizer.model"),
-                    reason="reference sample_data not present")
-def test_subword_tokenizer_roundtrip_as_reference_test():
+def test_subword_tokenizer_roundtrip_as_reference_test(golden_dir):
     from speech2text_amd.dataset.utils import TokenizerSetup
+    spm = os.path.join(golden_dir, "reference_configs", "sample_data", "spm")   # the reference's sample_data/spm
     tok = TokenizerSetup({"type": "subword", "config": {
-        "spm_model": "/root/reference/sample_data/spm/tokenizer.model",
-        "spm_vocab": "/root/reference/sample_data/spm/tokenizer.vocab"}})
+        "spm_model": os.path.join(spm, "tokenizer.model"),
+        "spm_vocab": os.path.join(spm, "tokenizer.vocab")}})
     assert len(tok.labels) == 128                      # decoding_test.py uses (.., 128) logits
     for ref in ["abc", "aabc", "i love china", "bilibili is good"]:
         assert tok.decode(tok.encode(ref)) == ref

@@ -19,7 +19,7 @@ def test_bench_line_contract_and_roofline_rows(dev, cfg, arith):
     if arith:
         env["S2T_GEMM_ARITH"] = arith
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "3",
-                        "--warmup", "2", "--no-cpu-baseline", "--profile-steps", "1"],
+                        "--warmup", "2", "--full", "--no-cpu-baseline", "--profile-steps", "1"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -75,3 +75,38 @@ def test_bench_line_contract_and_roofline_rows(dev, cfg, arith):
         assert abs(rf["bf16_ceiling_tflops"] - 2500.0 / products) < 1e-6
         assert 0 < rf["algorithmic_bytes_min_per_launch"] <= rf["algorithmic_bytes_per_launch"]
     assert d["config"]["gemm_paths"]["aten_fallbacks"] == 0
+
+
+def test_plain_bench_line_and_dumped_outputs(dev, tmp_path):
+    """Without --full the line carries the headline only (no roofline / cpu_baseline blocks) and --steps sets
+    the timed steps.  --dump-outputs writes the last timed step's loss, updated parameters and reduced
+    gradient (a fixed sample, < 64 MB); that step runs from the start state, so two runs with the same
+    arguments write the same arrays up to the rounding of the gradient reductions' float atomics (measured:
+    <= 8e-7 of an array's largest magnitude), and a run with more trained steps writes the same too."""
+    import numpy as np
+    lines = {}
+    for tag, steps in (("a", 2), ("b", 2), ("c", 4)):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[tag] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    d = lines["a"]
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "audio-seconds/sec" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert "roofline" not in d and "cpu_baseline" not in d
+    assert np.isfinite(d["config"]["final_loss"])               # the loss after the trained steps
+    files = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert files == ["grads.npy", "loss.npy", "params.npy"]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 64e6
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float64 and loss.shape == (1,) and loss[0] == d["config"]["dumped_step_loss"]
+    ref = {f: np.load(tmp_path / "a" / f) for f in files}
+    for f in ("params.npy", "grads.npy"):
+        a = ref[f]
+        assert a.dtype == np.float32 and a.ndim == 1 and a.size > 10 ** 6 and np.isfinite(a).all(), f
+        assert np.abs(a).max() > 0, f
+    for tag in ("b", "c"):
+        for f in files:
+            a, b = ref[f].astype(np.float64), np.load(tmp_path / tag / f).astype(np.float64)
+            assert a.shape == b.shape, (tag, f)
+            assert np.abs(a - b).max() <= 5e-6 * np.abs(a).max(), (tag, f, np.abs(a - b).max(), np.abs(a).max())

@@ -1,6 +1,6 @@
 """CPU: optimizer param groups of every task cover each trainable parameter exactly once
-(reference ctc_task.py:201-213, rnnt_task.py:596-630), for the shipped YAMLs when the reference
-tree is present, and a multi-group ScaledAdam keeps ONE flat store whose groups are ranges."""
+(reference ctc_task.py:201-213, rnnt_task.py:596-630), for the shipped YAMLs (stored under
+tests/golden/reference_configs), and a multi-group ScaledAdam keeps ONE flat store whose groups are ranges."""
 import copy
 import glob
 import os
@@ -12,7 +12,9 @@ import yaml
 import bench
 from speech2text_amd.build_task import TaskFactory
 
-REF_CFG = "/root/reference/config/training"
+# the reference's config/training/*.yaml and the sample_data/spm tokenizer they name, in the same layout
+REF_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_configs", "config",
+                       "training")
 IN_SCOPE = {"CTC", "Rnnt", "CTC_Hybrid_Rnnt", "Pruned_Rnnt", "SSL"}
 
 
@@ -61,7 +63,6 @@ def test_ctc_task_seperate_lr_groups():
     assert [g["name"] for g in opt.param_groups] == ["encoder_lr", "decoder_lr"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference tree not present")
 def test_shipped_yamls_build_and_group_every_parameter(monkeypatch):
     # the YAMLs name their tokenizer files relative to the reference's root (its tests run from there)
     monkeypatch.chdir(os.path.dirname(os.path.dirname(REF_CFG)))
