@@ -1,9 +1,11 @@
 """GPU: every BASELINE.json configuration at its FULL size.
 
 C3 (zipformer YAML dims, 500 BPE, prune_range 5): 2 x 10 s against the oracle (features,
-encoder activations, simple / pruned loss within the north-star 1e-3, prune ranges), then the
-per-rank batch of 64 through size-independent properties (finite, lengths, ranges monotone and
-in bounds, loss decreasing under the real optimizer).  C2 (conformer-CTC, 12 layers, d = 256),
+encoder activations, simple / pruned loss within the north-star 1e-3, prune ranges); the bench's
+padded geometry against the oracle with eight utterances ragged: 64 x 10 s in evaluation mode
+(every utterance's losses), the bench's training step at 32 x 10 s and chunked at 16 x 10 s (loss,
+every gradient); then the per-rank batch of 64 through size-independent properties (finite, lengths,
+ranges monotone and in bounds, loss decreasing under the real optimizer).  C2 (conformer-CTC, 12 layers, d = 256),
 C4 (CTC_Hybrid_Rnnt, B = 16, U = 60) and C5 (BEST-RQ, 30 s, 8192 x 16 codebook, KL over 8193
 classes) likewise: a small-batch comparison with the oracle at full model size plus the full
 batch through properties.  The oracle for k2 / torchaudio / lhotse arithmetic is our restatement
@@ -14,6 +16,7 @@ import random
 import numpy as np
 import pytest
 import torch
+from torch.utils.checkpoint import checkpoint
 
 import bench
 from oracle import conformer as OC
@@ -192,6 +195,247 @@ def test_c3_yaml_dims_training_step_gradients_vs_oracle(dev, monkeypatch, rv, ch
         if e > worst:
             worst, worst_name = e, n
     assert worst <= 5e-3, (worst_name, worst)
+
+
+# The bench's geometry: bench.make_batch(0, B, 10.0, 50, 500) keeps its padded shape (998 frames, 50
+# labels), so every product runs in the bench's shape buckets; eight utterances spread over the batch
+# are shorter.  Their PCM lengths (6.25 ... 9.875 s) give encoder lengths 245 232 220 207 195 182 169
+# 154, one of every remainder modulo 8: partial last groups in every down / upsampling ratio.  Their
+# label lengths run from 50 down to 2, the last below prune_range 5 (the padding branch of the prune
+# ranges).
+_RAGGED_PCM = (158000, 150000, 142000, 134000, 126000, 118000, 109500, 100000)
+_RAGGED_LABELS = (50, 43, 36, 29, 22, 15, 8, 2)
+
+
+def _ragged_bench_batch(B, dev):
+    """-> (bench.make_batch(0, B, 10.0, 50, 500, dev) with the eight ragged utterances, their rows)."""
+    batch = bench.make_batch(0, B, 10.0, 50, 500, dev)
+    rows = [1 + k * (B - 2) // 7 for k in range(8)]
+    for b, n, s in zip(rows, _RAGGED_PCM, _RAGGED_LABELS):
+        batch["pcm_length"][b] = n
+        batch["label_length"][b] = s
+    return batch, rows
+
+
+def _oracle_c3_train_step(sd, cfg, feat, feat_len, lab, lab_len, rv, cs, lcc, recompute=True):
+    """The oracle's C3 training step on `sd` (CPU tensors, the trainable ones requiring grad):
+    oracle/zipformer.py + heads.py + k2_rnnt.py forward, 0.5 simple + 0.5 pruned loss, backward
+    (gradients land in sd[name].grad) -> loss.  With `recompute` the subsampling frontend and every
+    encoder layer keep only their inputs and run again in backward (torch.utils.checkpoint): the plain
+    graph of 64 x 10 s would hold ~26 GB of host memory.  The recomputation repeats the arithmetic --
+    the step's random decisions are the pinned `rv` and the feature masks drawn outside those pieces
+    -- so the gradients are the plain graph's bit for bit (measured at B = 4, plain and chunked)."""
+    def recomputed(fn):
+        return lambda *a: checkpoint(fn, *a, use_reentrant=False)
+
+    nt = torch.get_num_threads()
+    torch.set_num_threads(bench.host_threads())
+    try:
+        with pytest.MonkeyPatch.context() as mp:
+            if recompute:
+                mp.setattr(Z, "conv2d_subsampling", recomputed(Z.conv2d_subsampling))
+                mp.setattr(Z, "encoder_layer", recomputed(Z.encoder_layer))
+            enc_sd = {k[len("_encoder.encoder."):]: v for k, v in sd.items()
+                      if k.startswith("_encoder.encoder.")}
+            yo, ylo = Z.zipformer_forward(enc_sd, bench._zcfg(cfg["encoder"]["config"]), feat, feat_len,
+                                          Z.Ctl(True, lambda: rv, pos_dropout=0.0), cs, lcc)
+            po = H.stateless_predictor(sd, "_predictor.predictor.", lab, 5)
+            am, lm = H.joiner_projections(sd, "_joiner.", yo, po)
+            lo, bo, ro, so = K2.joiner_pruned(am, lm, lab, lab_len, ylo, 5)
+            pro = K2.rnnt_loss_pruned(lo, lab, ro, 0, bo)
+            ref = H.pruned_rnnt_task_loss(so, pro, 0.5, 0.5)
+            del yo, po, am, lm, lo
+            ref.backward()
+    finally:
+        torch.set_num_threads(nt)
+    return ref.detach()
+
+
+def _worst(err):
+    """err (B,) -> (worst value, its utterance)."""
+    b = int(torch.argmax(err))
+    return float(err[b]), b
+
+
+def test_c3_bench_geometry_eval_vs_oracle(dev):
+    """The B = 2 comparison above at the bench's geometry: 64 x 10 s padded, eight utterances ragged
+    (_ragged_bench_batch), so the six stacks run 31 680 / 15 872 / 7 936 / 3 968 / 7 936 / 15 872 rows --
+    GEMM plan buckets, batch-sized workspaces and grids that B = 2 never reaches.  The plans of this
+    geometry are timed first by one training step of a second task; the task's parameters live in a
+    FlatStore as the bench's do, so the plans' own kernels serve the products.  Features, encoder
+    lengths, the encoder output on each utterance's valid frames, prune ranges, and the simple and
+    pruned loss of EVERY utterance against the oracle: a batch mean dilutes one wrong utterance 64-fold."""
+    from speech2text_amd import flat
+    from speech2text_amd import kernels as K
+    from speech2text_amd import zip_kernels as zk
+    from speech2text_amd.build_task import TaskFactory
+    B = 64
+    cfg = bench.c3_config(500)
+    random.seed(1234)
+    torch.manual_seed(1234)
+    task = TaskFactory.get("Pruned_Rnnt")(cfg)
+    sd = _cpu_sd(task)
+    task.to(dev)
+    flat.get_store([p for p in task.parameters() if p.requires_grad])
+    batch, rows = _ragged_bench_batch(B, dev)
+    task.eval()
+    with torch.no_grad():
+        feat, feat_len = task.features(batch)
+    _warm_gemm_plans(cfg, {"feat": feat, "feat_length": feat_len, "label": batch["label"],
+                           "label_length": batch["label_length"]}, dev, 0.0)
+    bucket = zk._half_octave(B * 495)                        # stack 0: 495 frames x 64 utterances
+    assert bucket == 29 and any(k[1] == bucket for k in zk._PLANS), \
+        ("no GEMM plan in the 31 680-row bucket", sorted({k[1] for k in zk._PLANS}))
+    task.eval()
+    lab, lab_len = batch["label"].cpu(), batch["label_length"].cpu()
+    with torch.no_grad():
+        enc, enc_len = task._encoder(feat, feat_len)
+        pred, pred_len, _ = task._predictor(batch["label"], batch["label_length"],
+                                            task._predictor.init_state())
+        lattice, boundary, ranges, simple = task._joiner(enc, enc_len, pred, pred_len, batch["label"])
+        pruned = task._loss({"logits": lattice, "logits_length": enc_len, "targets": batch["label"],
+                             "targets_length": batch["label_length"], "boundary": boundary,
+                             "ranges": ranges})
+        # the same kernels, per utterance (the task reduces them with a mean)
+        sym = batch["label"].to(torch.int64).contiguous()
+        simple_u = K.rnnt_simple_loss(lattice.lm.float(), lattice.am.float(), sym, boundary, 0)[0].cpu()
+        pruned_u = K.rnnt_pruned_joiner_loss(lattice.am, lattice.lm, ranges, sym, boundary, 0,
+                                             lattice.activation).cpu()
+    assert _rel(simple_u.mean(), simple) <= 1e-6 and _rel(pruned_u.mean(), pruned) <= 1e-6
+    assert enc.shape == (B, 248, 256)
+    # ---- oracle on the same parameters and PCM
+    pcm = batch["pcm"].cpu().numpy()
+    n = batch["pcm_length"].cpu().numpy()
+    fo = [ofb.fbank(pcm[i, :n[i]] * 32768.0, 80, high_freq=-400.0) for i in range(B)]
+    frames = [f.shape[0] for f in fo]
+    assert frames == feat_len.cpu().tolist()
+    assert [frames[b] for b in rows] == [986, 936, 886, 836, 786, 736, 682, 623]
+    feat_err = torch.tensor([np.abs(feat[i, :frames[i]].cpu().numpy() - fo[i]).max() for i in range(B)])
+    x = torch.zeros(B, 998, 80)
+    for i in range(B):
+        x[i, :frames[i]] = torch.from_numpy(fo[i])
+    enc_sd = {k[len("_encoder.encoder."):]: v for k, v in sd.items() if k.startswith("_encoder.encoder.")}
+    nt = torch.get_num_threads()
+    torch.set_num_threads(bench.host_threads())
+    try:
+        with torch.no_grad():
+            yo, ylo = Z.zipformer_forward(enc_sd, bench._zcfg(cfg["encoder"]["config"]), x,
+                                          feat_len.cpu(), Z.Ctl(False), -1, -1)
+            po = H.stateless_predictor(sd, "_predictor.predictor.", lab, 5)
+            am, lm = H.joiner_projections(sd, "_joiner.", yo, po)
+            lo, bo, ro, so = K2.joiner_pruned(am, lm, lab, lab_len, ylo, 5)
+            so_u = K2.rnnt_loss_smoothed(lm.float(), am.float(), lab, 0, bo, reduction="none")[0]
+            pro_u = K2.rnnt_loss_pruned(lo, lab, ro, 0, bo, reduction="none")
+    finally:
+        torch.set_num_threads(nt)
+    el = ylo.tolist()
+    enc_err = torch.tensor([(enc[b, :el[b]].cpu() - yo[b, :el[b]]).abs().max().item()
+                            / max(1.0, yo[b, :el[b]].abs().max().item()) for b in range(B)])
+    simple_err = (simple_u - so_u).abs() / so_u.abs()
+    pruned_err = (pruned_u - pro_u).abs() / pro_u.abs()
+    same = (ranges.cpu() == ro).float().mean().item()
+    print(f"\n[c3 bench geometry eval, B = {B}] worst (error, utterance): features "
+          f"{_worst(feat_err)}, encoder {_worst(enc_err)} of max, simple {_worst(simple_err)}, pruned "
+          f"{_worst(pruned_err)} relative; batch means simple {_rel(simple, so_u.mean()):.2e} pruned "
+          f"{_rel(pruned, pro_u.mean()):.2e}; prune ranges {same:.4f} identical")
+    assert _worst(feat_err)[0] <= 5e-3, ("features", _worst(feat_err))
+    assert enc_len.cpu().tolist() == el and [el[b] for b in rows] == [245, 232, 220, 207, 195, 182, 169, 154]
+    assert _worst(enc_err)[0] <= 2e-3, ("encoder output, valid frames", _worst(enc_err))
+    assert _worst(simple_err)[0] <= 1e-3, ("simple loss of an utterance", _worst(simple_err))
+    assert _worst(pruned_err)[0] <= 1e-3, ("pruned loss of an utterance", _worst(pruned_err))
+    assert _rel(simple, so_u.mean()) <= 1e-3, (float(simple), float(so_u.mean()))
+    assert _rel(pruned, pro_u.mean()) <= 1e-3, (float(pruned), float(pro_u.mean()))
+    assert same >= 0.98, same                               # argmax ties can move a window by one
+
+
+@pytest.mark.parametrize("B,rv,chunk", [(32, 0.0, (-1, -1)), (16, 0.2, (32, 128))])
+def test_c3_bench_geometry_training_step_vs_oracle(dev, monkeypatch, B, rv, chunk):
+    """The training step as bench.main runs and times it -- Trainer.setup, bench.StartState, two warm
+    steps (the first times the GEMM plans of this geometry on the Python layer executor, the second runs
+    on the native one), StartState.restore, StartState.keep_gradient, one Trainer.training_step -- against
+    the oracle: the loss and the reduced flat gradient, parameter by parameter, at the B = 2 test's bounds.
+    The batch is the bench's padded one (_ragged_bench_batch), fed the way the B = 2 test feeds it:
+    features computed once in evaluation mode, feature masks drawn on the host, Python `random` pinned
+    (0.0: every Balancer / Whiten / limit_param_value and the score penalty fire), positional dropout off.
+    B = 32 runs 15 840 / 7 936 / 3 968 / 1 984 rows in stacks 0-3.  The oracle's host memory decides
+    that batch: with the frontend and the layers recomputed in backward (_oracle_c3_train_step) the
+    oracle half peaks at 8.9 GiB host RSS at B = 32 (158 s on 8 threads, measured without a GPU) and at
+    15.5 GiB at 64 -- over the 12 GB a test may hold on a shared host.  The second case is the YAML's
+    chunked training mode (chunk 32, left context 128 frames) at B = 16 (7 920 rows in stack 0): the
+    chunk-masked attention tiles and chunk-causal conv edges against padding; 4.7 GiB, 14 s."""
+    from speech2text_amd import rng, zip_native
+    from speech2text_amd.build_task import TaskFactory
+    from speech2text_amd.trainer import Trainer
+    monkeypatch.setattr(rng, "rand", lambda *s, device=None, dtype=torch.float32:
+                        torch.rand(*s, dtype=dtype).to(device))
+    cfg = bench.c3_config(500)
+    cs, lcf = chunk
+    cfg["encoder"]["config"]["chunk_size"] = [cs]
+    cfg["encoder"]["config"]["left_context_frames"] = [lcf]
+    lcc = -1 if cs < 0 else max(1, lcf // cs)
+    random.seed(1234)
+    np.random.seed(1234)
+    torch.manual_seed(1234)
+    task = TaskFactory.get("Pruned_Rnnt")(cfg)
+    pnames = {n for n, _ in task.named_parameters()}
+    sd = {k: v.detach().cpu().clone().requires_grad_(k in pnames and v.dtype.is_floating_point)
+          for k, v in task.state_dict().items()}
+    trainer = Trainer(**cfg["trainer"]).setup(task, dev)
+    batch, _ = _ragged_bench_batch(B, dev)
+    task.eval()
+    with torch.no_grad():
+        feat, feat_len = task.features(batch)
+    task.train()
+    for mod in task.modules():
+        if mod.__class__.__name__ == "CompactRelPositionalEncoding":
+            mod.dropout.p = 0.0
+    fb = {"feat": feat, "feat_length": feat_len, "label": batch["label"],
+          "label_length": batch["label_length"]}
+    monkeypatch.setattr(random, "random", lambda: rv)
+    torch.manual_seed(1234)
+    start = bench.StartState(task, dev)
+    for i in range(2):
+        trainer.training_step(fb, i)
+    torch.cuda.synchronize()
+    start.restore(trainer)
+    kept = start.keep_gradient(trainer)
+    host_rng = torch.get_rng_state()                         # the feature masks' generator
+    nat0 = list(zip_native.CALLS)
+    loss = trainer.training_step(fb, 2)
+    torch.cuda.synchronize()
+    moved = [zip_native.CALLS[0] - nat0[0], zip_native.CALLS[1] - nat0[1]]
+    assert moved == [12, 12], f"native executor served {moved} forward / backward layer calls of 12 / 12"
+    store = trainer.store
+    where = {id(p): (o, n) for p, o, n in zip(store.params, store.offsets, store.lengths)}
+    grads = {n: kept["grad"][where[id(p)][0]:sum(where[id(p)])].view_as(p).cpu()
+             for n, p in task.named_parameters()}
+    # ---- oracle, same parameters / features / decisions
+    torch.set_rng_state(host_rng)
+    ref = _oracle_c3_train_step(sd, cfg, feat.cpu(), feat_len.cpu(), batch["label"].cpu(),
+                                batch["label_length"].cpu(), rv, cs, lcc)
+    # The output downsample's bias is a softmax over 2 taps: its gradient is 0.25 (dw0 - dw1), the
+    # difference of the two taps' sums g * src over B x 248 x 256 terms.  At B = 32 the taps' sums are
+    # 4e4 - 9e4 times larger than that difference (measured: taps 131.24 / 131.26, bias gradient
+    # 3.3e-3), so ONE fp32 rounding of a tap sum moves the bias gradient by ~1e-3 of itself -- in the
+    # oracle as in the kernel, whose tap sums match a float64 sum of its own inputs to 7e-7 and whose
+    # float-atomic order alone moved that gradient by 3.4e-3 between two calls on identical inputs.
+    # That parameter gets 2e-2 (a few roundings of the taps); every other one the B = 2 test's 5e-3.
+    ill, ill_bound, ill_err = "_encoder.encoder.downsample_output.bias", 2e-2, 0.0
+    worst, worst_name = 0.0, None
+    for n, g in grads.items():
+        r = sd[n].grad
+        r = torch.zeros_like(sd[n]) if r is None else r
+        e = (g - r).abs().max().item() / (r.abs().max().item() + 1e-6)
+        if n == ill:
+            ill_err = e
+        elif e > worst:
+            worst, worst_name = e, n
+    print(f"\n[c3 bench geometry training step, B = {B}, rv {rv}, chunk {chunk}] loss {float(loss):.4f} "
+          f"oracle {float(ref):.4f} ({_rel(loss, ref):.2e} relative); worst gradient {worst:.2e} of its "
+          f"max at {worst_name}; {ill} {ill_err:.2e}")
+    assert _rel(loss, ref) <= 1e-3, (float(loss), float(ref))
+    assert worst <= 5e-3, (worst_name, worst)
+    assert ill_err <= ill_bound, (ill, ill_err)
 
 
 def test_c3_yaml_size_prune_ranges_bit_exact_given_the_oracles_gradients(dev):
