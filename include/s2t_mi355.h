@@ -388,16 +388,16 @@ int s2t_gemm_f32_tiled(int mode, const float* A, long lda, const float* B, long 
                        long ldr, int tile, void* stream);
 
 /* Arithmetic of the TN (weight-gradient) products, s2t_gemm_f32 mode 2 / s2t_gemm_tn_grouped /
- * s2t_gemm_xtx: 1 (default, or S2T_TN_X3=1) = both fp32 operands split exactly into three bf16
+ * s2t_gemm_xtx: 1 (default) = both fp32 operands split exactly into three bf16
  * pieces, six v_mfma_f32_32x32x16_bf16 products per 16-deep step, fp32 accumulation (fp32-level
  * error); 0 = v_mfma_f32_32x32x2_f32.  set >= 0 selects, set < 0 queries; returns the mode. */
 int s2t_tn_x3(int set);
-/* Kernel form of the bf16-split TN products (round 5): 1 (default, or S2T_TN_W=1) = wave-specialised
+/* Kernel form of the bf16-split TN products (round 5): 1 = wave-specialised
  * 128x128 / 128x192 / 192x128 tiles (producer waves load 16-byte runs and split, consumer waves run
  * the MFMAs; aligned non-symmetric problems: s2t_gemm_f32 mode 2, s2t_gemm_tn_grouped, and
  * s2t_conv3x3_gemm mode 2 with its implicit patch operand); 0 = the all-waves form (every wave splits
  * what it staged and multiplies it: 64x64 tiles under six products, 128x128 under three).  Same
- * arithmetic, different summation order.  With no setting (S2T_TN_W unset, or set == 2) the form
+ * arithmetic, different summation order.  With no setting (or set == 2) the form
  * follows the weight-gradient class's arithmetic (s2t_gemm_arith_of(2)): six products -> 1, three -> 0
  * (round 6: measured per step; the implicit-patch product stays on the W form).  set = 0 / 1
  * forces, set = 2 returns to automatic, set < 0 queries; returns the form now in effect. */
@@ -489,11 +489,11 @@ int s2t_linear_lt(int mode, const float* X, long ldx, const float* W, long ldw, 
                   const float* C, long ldc, float beta, float* D, long ldd, int M, int N, int K,
                   void* workspace, long ws_bytes, void* stream);
 /* plans made (one per exact shape, table capped) and buckets {mode, half-octave of M, N, K,
- * bias} whose candidates were timed (capped by S2T_LT_TUNE_MAX, default 192) so far. */
+ * bias} whose candidates were timed (capped at 192) so far. */
 int s2t_linear_lt_stats(int* plans, int* timed);
 /* s2t_linear_lt times OUR NT / NN kernel (s2t_gemm_f32, bf16x3 form, bias + residual epilogue) as one
- * more candidate of a bucket and keeps it where it beats the library's best by > 8 % twice
- * (S2T_LT_OWN=0 disables); launches it has served so far: */
+ * more candidate of a bucket and keeps it where it beats the library's best by > 8 % twice;
+ * launches it has served so far: */
 long s2t_linear_lt_own_calls(void);
 
 /* ---- fused glue of the zipformer layer (csrc/zip_glue.hip), rows of C channels, time-major.

@@ -958,51 +958,31 @@ __global__ __launch_bounds__(512) void gemm_tn_w_patch_kernel(GemmArgs g, int sh
 // Weight-gradient contractions on the bf16 matrix cores (three-way exact split, six products:
 // fp32-level error, tests/test_gpu_gemm.py) -- on by default: in the training step the TN GEMMs
 // share the CUs with the main stream's library GEMMs, and 2.3x fewer matrix-pipe cycles for the
-// same product took the C3 step from 47.8 to 46.6 ms (same box, 3 x 3 runs).  S2T_TN_X3=0: the
+// same product took the C3 step from 47.8 to 46.6 ms (same box, 3 x 3 runs).  s2t_tn_x3(0): the
 // f32 MFMA form.
-// the same arithmetic for the NT / NN products of s2t_gemm_f32 (default on; S2T_NN_X3=0: f32 MFMA)
-static int g_nn_x3 = -1;
-static bool nn_x3() {
-  if (g_nn_x3 < 0) { const char* e = getenv("S2T_NN_X3"); g_nn_x3 = e ? atoi(e) : 1; }
-  return g_nn_x3 == 1;
-}
+// the same arithmetic for the NT / NN products of s2t_gemm_f32 (default on; s2t_nn_x3(0): f32 MFMA)
+static int g_nn_x3 = 1;
+static bool nn_x3() { return g_nn_x3 == 1; }
 extern "C" int s2t_nn_x3(int set) {
   if (set >= 0) g_nn_x3 = set ? 1 : 0;
   return nn_x3() ? 1 : 0;
 }
-// S2T_TN_P3=0: the form that splits every fragment where it is read (A/B, tests)
-static bool tn_p3() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("S2T_TN_P3"); v = e ? atoi(e) : 1; }
-  return v == 1;
-}
-// S2T_TN_W=0: weight gradients on the 64 x 64 form instead of the wave-specialised "W" form;
-// S2T_TN_W_BLOCKS: workgroups a W launch aims at (one is resident per CU)
+// s2t_tn_w(0): weight gradients on the 64 x 64 form instead of the wave-specialised "W" form.
 // Round 6: with no setting the form follows the weight gradients' arithmetic -- six products: the W form
 // (round 5: 0.65 ms per step better than the all-waves form); three products: the all-waves form on
 // 128 x 128 tiles (the split and the MFMAs both shrank, the producer / consumer imbalance did not:
 // 33.80-33.90 against 33.33-33.46 ms per step, three pairs on one box).
-static int g_tn_w = -1;      // -1: not asked yet; 2: automatic; 0 / 1: forced (S2T_TN_W, s2t_tn_w)
-static bool tn_w_forced() {
-  if (g_tn_w < 0) { const char* e = getenv("S2T_TN_W"); g_tn_w = e ? (atoi(e) ? 1 : 0) : 2; }
-  return g_tn_w != 2;
-}
+static int g_tn_w = 2;       // 2: automatic; 0 / 1: forced (s2t_tn_w)
+static bool tn_w_forced() { return g_tn_w != 2; }
 static bool tn_w() { return tn_w_forced() ? g_tn_w == 1 : s2t_gemm_arith_of(2) != 2; }
 // the 3x3 convolution's implicit-patch weight gradient has no 128 x 128 all-waves instantiation: W unless forced off
 static bool tn_w_patch() { return tn_w_forced() ? g_tn_w == 1 : true; }
-static long tn_w_blocks() {
-  static long v = -1;
-  if (v < 0) { const char* e = getenv("S2T_TN_W_BLOCKS"); v = e ? atol(e) : 512; }
-  return v;
-}
+constexpr long TN_W_BLOCKS = 512;   // workgroups a W launch aims at (one is resident per CU)
 // tile shape of an (M x N) output on the W form and its tile counts
 static int tn_w_shape_of(int M, int N, int& tiles_m, int& tiles_n) {
   const auto waste = [](int n, int t) { return ((n + t - 1) / t) * t - n; };
-  static int wide = -1;      // S2T_TN_W_WIDE=0: 128 x 128 tiles only (96 KB of LDS instead of 120)
-  if (wide < 0) { const char* e = getenv("S2T_TN_W_WIDE"); wide = e ? atoi(e) : 1; }
   int shape = 0;
-  if (!wide) shape = 0;
-  else if (waste(N, 192) < waste(N, 128)) shape = 1;
+  if (waste(N, 192) < waste(N, 128)) shape = 1;
   else if (waste(M, 192) < waste(M, 128)) shape = 2;
   tiles_m = (M + (shape == 2 ? 191 : 127)) / (shape == 2 ? 192 : 128);
   tiles_n = (N + (shape == 1 ? 191 : 127)) / (shape == 1 ? 192 : 128);
@@ -1013,11 +993,8 @@ static bool tn_w_prepare(K kern) {      // the kernels take 120 KB of dynamic LD
   return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                              TNW_LDS) == hipSuccess;
 }
-static int g_tn_x3 = -1;
-static bool tn_x3() {
-  if (g_tn_x3 < 0) { const char* e = getenv("S2T_TN_X3"); g_tn_x3 = e ? atoi(e) : 1; }
-  return g_tn_x3 == 1;
-}
+static int g_tn_x3 = 1;
+static bool tn_x3() { return g_tn_x3 == 1; }
 
 template <int TM, int TN, int MODE, int PRO>
 int launch(GemmArgs& g, int splits, hipStream_t st) {
@@ -1028,19 +1005,23 @@ int launch(GemmArgs& g, int splits, hipStream_t st) {
   const int total = g.tiles_m * g.tiles_n;
   g.splits = splits;
   const int grid = MODE == MODE_TN ? 8 * total * ((splits + 7) / 8) : ((total + 7) / 8) * 8;
-  static const bool p2 = [] { const char* e = getenv("S2T_TN_P2"); return !e || atoi(e) != 0; }();
-  if constexpr (MODE == MODE_TN && TM == 2 && TN == 2) {
-    if (tn_x3() && tn_p3() && g.np == 2 && p2) {
-      hipLaunchKernelGGL((gemm_tn_p2_kernel<TM, TN, PRO>), dim3(grid), dim3(256), 0, st, g);
-      return (int)hipGetLastError();
+  if constexpr (MODE == MODE_TN) {      // split operands: once, at staging
+    if constexpr (TM == 2 && TN == 2) {
+      if (tn_x3() && g.np == 2) {
+        hipLaunchKernelGGL((gemm_tn_p2_kernel<TM, TN, PRO>), dim3(grid), dim3(256), 0, st, g);
+        return (int)hipGetLastError();
+      }
     }
+    if (tn_x3())
+      hipLaunchKernelGGL((gemm_kernel<TM, TN, MODE, PRO, true, false, true>), dim3(grid), dim3(256), 0, st, g);
+    else
+      hipLaunchKernelGGL((gemm_kernel<TM, TN, MODE, PRO>), dim3(grid), dim3(256), 0, st, g);
+  } else {
+    if (nn_x3())
+      hipLaunchKernelGGL((gemm_kernel<TM, TN, MODE, PRO, true>), dim3(grid), dim3(256), 0, st, g);
+    else
+      hipLaunchKernelGGL((gemm_kernel<TM, TN, MODE, PRO>), dim3(grid), dim3(256), 0, st, g);
   }
-  if (MODE == MODE_TN && tn_x3() && tn_p3())
-    hipLaunchKernelGGL((gemm_kernel<TM, TN, MODE, PRO, true, false, (MODE == MODE_TN)>), dim3(grid), dim3(256), 0, st, g);
-  else if (MODE == MODE_TN ? tn_x3() : nn_x3())
-    hipLaunchKernelGGL((gemm_kernel<TM, TN, MODE, PRO, true>), dim3(grid), dim3(256), 0, st, g);
-  else
-    hipLaunchKernelGGL((gemm_kernel<TM, TN, MODE, PRO>), dim3(grid), dim3(256), 0, st, g);
   return (int)hipGetLastError();
 }
 
@@ -1051,11 +1032,14 @@ int launch_p(GemmArgs& g, int pro, int splits, hipStream_t st) {
   return launch<TM, TN, MODE, ACT_SWOOSH_R>(g, splits, st);
 }
 
-// tile shapes: (2,2) 128x128, (2,3) 128x192, (2,1) 128x64, (1,2) 64x128, (1,1) 64x64
+// tile shapes: (2,2) 128x128, (2,3) 128x192, (2,1) 128x64, (1,2) 64x128, (1,1) 64x64; the TN rule
+// (dispatch) picks among (2,2), (1,2) and (1,1) only
 template <int MODE>
 int launch_t(GemmArgs& g, int tm, int tn, int pro, int splits, hipStream_t st) {
-  if (tm == 2 && tn == 3) return launch_p<2, 3, MODE>(g, pro, splits, st);
-  if (tm == 2 && tn == 1) return launch_p<2, 1, MODE>(g, pro, splits, st);
+  if constexpr (MODE != MODE_TN) {
+    if (tm == 2 && tn == 3) return launch_p<2, 3, MODE>(g, pro, splits, st);
+    if (tm == 2 && tn == 1) return launch_p<2, 1, MODE>(g, pro, splits, st);
+  }
   if (tm == 2) return launch_p<2, 2, MODE>(g, pro, splits, st);
   if (tn >= 2) return launch_p<1, 2, MODE>(g, pro, splits, st);
   return launch_p<1, 1, MODE>(g, pro, splits, st);
@@ -1083,7 +1067,6 @@ int dispatch(GemmArgs& g, hipStream_t st) {
     // the chip adds ~1.3 TB/s, so SMALL tiles win: 64x64 tiles at ~6 workgroups per CU moved the
     // C3 shapes from ~50 to ~75 TFLOP/s against 128x192 tiles at 2 per CU (tools/bench_tn.py);
     // 64x128 once the output is wide enough to give the slices enough tiles.
-    // S2T_TN_TILE ("11", "12", "21", "22", "23") / S2T_TN_BLOCKS override the choice for tuning.
     // Round 5: aligned, non-symmetric problems take the wave-specialised W form first (tn_w_body).
     // Alone on the chip it is SLOWER than the 64 x 64 form (10 C3 shapes: 700 against 535 us: one
     // workgroup per CU, 40 KB of loads in flight), inside the training step it is faster (same box:
@@ -1092,16 +1075,12 @@ int dispatch(GemmArgs& g, hipStream_t st) {
     // takes fewer of each per flop (bigger tiles, 16-byte loads, half the split work per product).
     // S2T_GEMM_DEBUG bits (timing ablations, results wrong): 1 no output adds, 2 no split/store,
     // 4 no MFMA, 8 no loads, 16 print the launch.
-    static int force = -1, user_blocks = -2;
-    if (force < 0) { const char* e = getenv("S2T_TN_TILE"); force = e ? atoi(e) : 0; }
-    if (user_blocks == -2) { const char* e = getenv("S2T_TN_BLOCKS"); user_blocks = e ? atoi(e) : -1; }
-    if (tn_w() && tn_x3() && tn_p3() && !g.sym_cg && force <= 0 && !((g.M | g.N | g.lda | g.ldb) & 3) &&
+    if (tn_w() && tn_x3() && !g.sym_cg && !((g.M | g.N | g.lda | g.ldb) & 3) &&
         !((reinterpret_cast<uintptr_t>(g.A) | reinterpret_cast<uintptr_t>(g.B)) & 15)) {
       const int shape = tn_w_shape_of(g.M, g.N, g.tiles_m, g.tiles_n);
       { static const int dbg = s2t_debug_env("S2T_GEMM_DEBUG"); g.debug = dbg; }
       const long tiles = (long)g.tiles_m * g.tiles_n;
-      const long target = user_blocks > 0 ? user_blocks : tn_w_blocks();
-      int splits = (int)((target + tiles - 1) / tiles);
+      int splits = (int)((TN_W_BLOCKS + tiles - 1) / tiles);
       splits = std::max(1, std::min(splits, (g.K + 2 * KR - 1) / (2 * KR)));
       int kper = (g.K + splits - 1) / splits;
       kper = ((kper + KR - 1) / KR) * KR;
@@ -1118,15 +1097,12 @@ int dispatch(GemmArgs& g, hipStream_t st) {
       else hipLaunchKernelGGL((gemm_tn_w_kernel<ACT_SWOOSH_R>), dim3(grid), dim3(512), lds, st, g, shape);
       return (int)hipGetLastError();
     }
-    // (no forced tile: 128 x 128 under the three-product arithmetic -- see tn_w_forced -- else 64 x 64 / 64 x 128)
-    const bool big = force <= 0 && !g.sym_cg && g.np == 2 && tn_x3() && tn_p3();
-    const int ttm = (force > 0 && !g.sym_cg) ? force / 10 : (big ? 2 : 1);
-    const int ttn = g.sym_cg ? 1 : (force > 0 ? force % 10 : (big ? 2 : (g.N >= 512 ? 2 : 1)));
+    // (128 x 128 under the three-product arithmetic -- see tn_w_forced -- else 64 x 64 / 64 x 128)
+    const bool big = !g.sym_cg && g.np == 2 && tn_x3();
+    const int ttm = big ? 2 : 1;
+    const int ttn = g.sym_cg ? 1 : (big ? 2 : (g.N >= 512 ? 2 : 1));
     const long tiles = (long)((g.M + 64 * ttm - 1) / (64 * ttm)) * ((g.N + 64 * ttn - 1) / (64 * ttn));
-    static int xtx_blocks = -2;   // S2T_XTX_BLOCKS: workgroup target of the symmetric x^T x
-    if (xtx_blocks == -2) { const char* e = getenv("S2T_XTX_BLOCKS"); xtx_blocks = e ? atoi(e) : -1; }
-    const int target = (g.sym_cg && xtx_blocks > 0) ? xtx_blocks
-                       : user_blocks > 0 ? user_blocks : (ttm * ttn == 1 ? 1536 : 768);
+    const int target = ttm * ttn == 1 ? 1536 : 768;
     int splits = (int)((target + tiles - 1) / tiles);
     const int maxs = (g.K + 2 * KR - 1) / (2 * KR);
     if (splits > maxs) splits = maxs;
@@ -1137,18 +1113,12 @@ int dispatch(GemmArgs& g, hipStream_t st) {
     splits = (g.K + kper - 1) / kper;
     return launch_t<MODE>(g, ttm, ttn, pro, splits, st);
   }
-  {
-    static int wide = -1;       // S2T_GEMM_WIDE_EP=0: the scalar epilogue
-    if (wide < 0) { const char* e = getenv("S2T_GEMM_WIDE_EP"); wide = e ? atoi(e) : 1; }
-    g.wide_ep = wide && !g.act_src && !g.accumulate && (g.N & 3) == 0 && (g.ldc & 3) == 0 &&
-                (reinterpret_cast<uintptr_t>(g.C) & 15) == 0 &&
-                (!g.bias || (reinterpret_cast<uintptr_t>(g.bias) & 15) == 0) &&
-                (!g.resid || ((g.ldr & 3) == 0 && (reinterpret_cast<uintptr_t>(g.resid) & 15) == 0));
-  }
-  static int nt_force = -1;     // S2T_NT_TILE = "tm tn" digits (11, 12, 21, 22, 23): tuning
-  if (nt_force < 0) { const char* e = getenv("S2T_NT_TILE"); nt_force = e ? atoi(e) : 0; }
+  // 16-byte epilogue where everything it touches is aligned, else the scalar one
+  g.wide_ep = !g.act_src && !g.accumulate && (g.N & 3) == 0 && (g.ldc & 3) == 0 &&
+              (reinterpret_cast<uintptr_t>(g.C) & 15) == 0 &&
+              (!g.bias || (reinterpret_cast<uintptr_t>(g.bias) & 15) == 0) &&
+              (!g.resid || ((g.ldr & 3) == 0 && (reinterpret_cast<uintptr_t>(g.resid) & 15) == 0));
   if (g.tile_force > 0) return launch_t<MODE>(g, g.tile_force / 10, g.tile_force % 10, pro, 1, st);
-  if (nt_force > 0) return launch_t<MODE>(g, nt_force / 10, nt_force % 10, pro, 1, st);
   if (tiles_big >= 384) return launch_t<MODE>(g, 2, tn_sel, pro, 1, st);
   if (tn_sel == 3) tn_sel = 2;
   return launch_t<MODE>(g, 1, tn_sel, pro, 1, st);
@@ -1204,8 +1174,6 @@ extern "C" int s2t_gemm_f32_sq(int mode, const float* A, long lda, const float* 
   if ((N & 3) || (ldc & 3) || (ld_other & 3) || (reinterpret_cast<uintptr_t>(C) & 15) ||
       (reinterpret_cast<uintptr_t>(other) & 15) || (bias && (reinterpret_cast<uintptr_t>(bias) & 15)))
     return -2;
-  static const bool wide_on = [] { const char* e = getenv("S2T_GEMM_WIDE_EP"); return !e || atoi(e) != 0; }();
-  if (!wide_on) return -2;
   GemmArgs g{A, lda, B, ldb, C, ldc, M, N, K, bias, nullptr, 0, nullptr, 0, 0, 0,
              0, nullptr, 0, 0, 0, 0, 0, 0, 1.f, 0};
   g.sq_other = other;
@@ -1319,13 +1287,12 @@ extern "C" int s2t_conv3x3_gemm(int mode, const float* x, int B, int H, int W, i
   // either way (37.64 / 37.66 ms, three pairs), so the shorter launch is kept.
   // Round 6: under the three-product arithmetic every size runs on the all-waves form below with the patch
   // operand (C3 33.24-33.42 -> 33.02-33.15 ms per step against the fragment-splitting 64 x 64 form, C2
-  // 19.30-19.42 -> 18.89-19.10 against the W form; S2T_CONV_W_P3=0: the round-5 forms)
-  static const int p3mode = [] { const char* e = getenv("S2T_CONV_W_P3"); return e ? atoi(e) : 1; }();
-  const bool allw = p3mode && tn_x3() && tn_p3();
-  if (!(allw && g.np == 2) && tn_w_patch() && tn_x3() && tn_p3() && CO >= 128 && K9 >= 1024) {
+  // 19.30-19.42 -> 18.89-19.10 against the W form)
+  const bool allw = tn_x3();
+  if (allw && g.np != 2 && tn_w_patch() && CO >= 128 && K9 >= 1024) {
     const int shape = tn_w_shape_of(g.M, g.N, g.tiles_m, g.tiles_n);
     const long tiles = (long)g.tiles_m * g.tiles_n;
-    int splits = (int)((tn_w_blocks() + tiles - 1) / tiles);
+    int splits = (int)((TN_W_BLOCKS + tiles - 1) / tiles);
     splits = std::max(1, std::min(splits, (g.K + 2 * KR - 1) / (2 * KR)));
     int kper = (g.K + splits - 1) / splits;
     kper = ((kper + KR - 1) / KR) * KR;
@@ -1398,27 +1365,13 @@ extern "C" int s2t_gemm_tn_grouped(int n, const S2tTnProblem* probs, void* strea
   // the chip on its own (the single-problem rule: ~1536 blocks each) made a 17-problem layer
   // launch write 22x its output.  The problems of a group run concurrently, so the GROUP has to
   // fill the chip: slices = the multiple of 8 (one residue per XCD, see gemm_body) that brings
-  // the group's total to ~S2T_TN_GROUP_BLOCKS blocks (default 6144 = 4 rounds of 6 per CU).
-  static long target = -1;
-  if (target < 0) {
-    const char* e = getenv("S2T_TN_GROUP_BLOCKS");
-    target = e ? atol(e) : 6144;
-    if (target < 8) target = 8;
-  }
-  // output tile (64 tmw) x (64 tnw): S2T_TN_GROUP_TILE = 11 | 12 | 22; unset: 22 under the three-product
-  // arithmetic (1536 workgroups per group unless S2T_TN_GROUP_BLOCKS says otherwise), else 11
-  static int gtile = -1;
-  static bool user_target = false;
-  if (gtile < 0) {
-    const char* e = getenv("S2T_TN_GROUP_TILE");
-    gtile = e ? atoi(e) : 0;
-    user_target = getenv("S2T_TN_GROUP_BLOCKS") != nullptr;
-  }
-  const int gt = gtile > 0 ? gtile : ((s2t_gemm_arith_of(2) == 2 && tn_x3() && tn_p3()) ? 22 : 11);
-  const int tmw = gt == 22 ? 2 : 1, tnw = (gt == 12 || gt == 22) ? 2 : 1;
-  const long gtarget = (gt == 22 && !user_target) ? 1536 : target;
-  const long qtarget = tn_w_blocks();
-  bool useq = tn_w() && tn_x3() && tn_p3();
+  // the group's total to ~6144 blocks (4 rounds of 6 per CU).
+  // output tile 64 tw x 64 tw: 128 x 128 under the three-product arithmetic (1536 workgroups per
+  // group), else 64 x 64
+  const int tw = (s2t_gemm_arith_of(2) == 2 && tn_x3()) ? 2 : 1;
+  const long gtarget = tw == 2 ? 1536 : 6144;
+  const long qtarget = TN_W_BLOCKS;
+  bool useq = tn_w() && tn_x3();
   for (int i = 0; i < n && useq; ++i) {
     const S2tTnProblem& s = probs[i];
     useq = !((s.M & 3) || (s.N & 3) || (s.lda & 3) || (s.ldb & 3) ||
@@ -1480,7 +1433,7 @@ extern "C" int s2t_gemm_tn_grouped(int n, const S2tTnProblem* probs, void* strea
           (reinterpret_cast<uintptr_t>(s.A) & 15) || (reinterpret_cast<uintptr_t>(s.B) & 15) ||
           s.lda > INT32_MAX || s.ldb > INT32_MAX || s.ldc > INT32_MAX)
         return -2;
-      total_tiles += (long)((s.M + 64 * tmw - 1) / (64 * tmw)) * ((s.N + 64 * tnw - 1) / (64 * tnw));
+      total_tiles += (long)((s.M + 64 * tw - 1) / (64 * tw)) * ((s.N + 64 * tw - 1) / (64 * tw));
     }
     int want = (int)((gtarget + total_tiles - 1) / total_tiles);
     want = std::max(8, ((want + 4) / 8) * 8);
@@ -1489,7 +1442,7 @@ extern "C" int s2t_gemm_tn_grouped(int n, const S2tTnProblem* probs, void* strea
       const S2tTnProblem& s = probs[base + i];
       TnProb& q = grp.p[i];
       q = TnProb{s.A, s.B, s.C, s.colsum, (int)s.lda, (int)s.ldb, (int)s.ldc, s.M, s.N, s.K,
-                 0, (s.M + 64 * tmw - 1) / (64 * tmw), (s.N + 64 * tnw - 1) / (64 * tnw), 0, s.alpha};
+                 0, (s.M + 64 * tw - 1) / (64 * tw), (s.N + 64 * tw - 1) / (64 * tw), 0, s.alpha};
       const long tiles = (long)q.tiles_m * q.tiles_n;
       const int maxs = (s.K + 2 * KR - 1) / (2 * KR);
       int splits = std::max(1, std::min(want, maxs));
@@ -1501,19 +1454,10 @@ extern "C" int s2t_gemm_tn_grouped(int n, const S2tTnProblem* probs, void* strea
       blocks += (unsigned)(8 * tiles * ((q.splits + 7) / 8));
     }
     grp.begin[grp.n] = blocks;
-    static const bool p2 = [] { const char* e = getenv("S2T_TN_P2"); return !e || atoi(e) != 0; }();
-    if (tn_x3() && tn_p3() && tmw == 2 && grp.np == 2 && p2)
+    if (tw == 2)                        // three products, operands split once at staging
       hipLaunchKernelGGL((gemm_tn_grouped_p2_kernel<2, 2>), dim3(blocks), dim3(256), 0, st, grp);
-    else if (tn_x3() && tn_p3() && tmw == 2)
-      hipLaunchKernelGGL((gemm_tn_grouped_kernel<true, 2, true, 2>), dim3(blocks), dim3(256), 0, st, grp);
-    else if (tn_x3() && tn_p3() && tnw == 2)
-      hipLaunchKernelGGL((gemm_tn_grouped_kernel<true, 2, true>), dim3(blocks), dim3(256), 0, st, grp);
-    else if (tn_x3() && tn_p3())
-      hipLaunchKernelGGL((gemm_tn_grouped_kernel<true, 1, true>), dim3(blocks), dim3(256), 0, st, grp);
-    else if (tn_x3() && tnw == 2)
-      hipLaunchKernelGGL((gemm_tn_grouped_kernel<true, 2>), dim3(blocks), dim3(256), 0, st, grp);
     else if (tn_x3())
-      hipLaunchKernelGGL((gemm_tn_grouped_kernel<true, 1>), dim3(blocks), dim3(256), 0, st, grp);
+      hipLaunchKernelGGL((gemm_tn_grouped_kernel<true, 1, true>), dim3(blocks), dim3(256), 0, st, grp);
     else
       hipLaunchKernelGGL((gemm_tn_grouped_kernel<false, 1>), dim3(blocks), dim3(256), 0, st, grp);
     if (hipGetLastError() != hipSuccess) return -3;

@@ -39,16 +39,7 @@ constexpr int MAX_CAND = 16;
 
 // Our own NT / NN MFMA kernel (gemm.hip, bf16x3 form) as one more candidate of the plan: same
 // product, bias and residual in its epilogue.  Usable when the residual weight is 0 or 1.
-bool own_enabled() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("S2T_LT_OWN"); v = e ? atoi(e) : 1; }
-  return v == 1;
-}
-float own_margin() {
-  static float v = -1.f;
-  if (v < 0.f) { const char* e = getenv("S2T_LT_OWN_MARGIN"); v = e ? (float)atof(e) : 0.97f; }
-  return v;
-}
+constexpr float OWN_MARGIN = 0.97f;   // ours replaces the library's best when it takes less than this share of its time
 int run_own(int mode, const float* X, long ldx, const float* W, long ldw, const float* bias,
             const float* C, long ldc, float beta, float* D, long ldd, int M, int N, int K, int tile,
             hipStream_t st) {
@@ -86,14 +77,7 @@ int g_tunings = 0;
 long g_own_calls = 0;
 constexpr size_t MAX_PLANS = 8192;
 
-int tune_budget() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("S2T_LT_TUNE_MAX");
-    v = e ? atoi(e) : 192;
-  }
-  return v;
-}
+constexpr int TUNE_BUDGET = 192;      // buckets timed per process; later ones take the heuristic's first choice
 
 int half_octave(int m) { return (int)std::floor(2.0 * std::log2((double)(m < 1 ? 1 : m))); }
 
@@ -149,15 +133,6 @@ int make_plan(Plan& p, int mode, int M, int N, int K, long ldx, long ldw, long l
   return 0;
 }
 
-bool tuning_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("S2T_LT_TUNE");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
 // Time every candidate the heuristic returned on the call's own operands (output into a scratch
 // buffer, so accumulating epilogues are not applied twice) and keep the fastest.  The library's
 // first choice is tuned for large square problems; on the tall, short-K shapes of this model
@@ -166,7 +141,7 @@ void tune(Plan& p, const float* X, const float* W, const float* C, float beta, l
           void* workspace, size_t ws_bytes, hipStream_t st, int mode, long ldx, long ldw,
           const float* bias, long ldc, long ldd, int M, int N, int K) {
   p.tuned = true;
-  if (p.ncand < 2 || !tuning_enabled()) return;
+  if (p.ncand < 2) return;
   // The candidates must be compared on an otherwise idle chip: the step's side streams (the
   // grouped weight-gradient GEMM, the Whiten statistics) run 400 us kernels beside the main
   // stream, and whichever candidate was timed under one of them lost -- at the conformer's
@@ -198,9 +173,7 @@ void tune(Plan& p, const float* X, const float* W, const float* C, float beta, l
   (void)time_cand(0);                      // clocks and caches up before anything is compared
   float best = 1e30f;
   int best_i = 0;
-  static int max_try = -1;
-  if (max_try < 0) { const char* e = getenv("S2T_LT_CANDIDATES"); max_try = e ? atoi(e) : 8; }
-  const int ntry = p.ncand < max_try ? p.ncand : max_try;
+  const int ntry = p.ncand < 8 ? p.ncand : 8;
   for (int i = 0; i < ntry; ++i) {
     // the better of two measurements: one pass picks a different kernel from run to run often
     // enough to move the step by a millisecond
@@ -227,7 +200,7 @@ void tune(Plan& p, const float* X, const float* W, const float* C, float beta, l
   p.algo = p.cand[best_i].algo;
   p.ws = p.cand[best_i].workspaceSize;
   // our kernel against the library's best: same operands, same epilogue, output into the scratch
-  if (own_enabled() && (beta == 0.f || beta == 1.f)) {
+  if (beta == 0.f || beta == 1.f) {
     auto time_own = [&](int tile) -> float {
       for (int rep = 0; rep < 5; ++rep) {
         if (rep == 1) (void)hipEventRecord(e0, st);
@@ -256,7 +229,7 @@ void tune(Plan& p, const float* X, const float* W, const float* C, float beta, l
     bool win = best_t != 0;
     for (int round = 0; round < 2 && win; ++round) {
       const float tl = time_cand(best_i), to = time_own(best_t);
-      win = to > 0.f && tl > 0.f && to < own_margin() * tl;
+      win = to > 0.f && tl > 0.f && to < OWN_MARGIN * tl;
     }
     p.own = win;
     p.own_tile = win ? best_t : 0;
@@ -329,7 +302,7 @@ extern "C" int s2t_linear_lt(int mode, const float* X, long ldx, const float* W,
           p.ws = p.cand[i].workspaceSize;
           break;
         }
-    } else if (g_tunings < tune_budget()) {
+    } else if (g_tunings < TUNE_BUDGET) {
       tune(p, X, W, C == D ? nullptr : C, C == D ? 0.f : beta, (long)M * ldd, workspace,
            (size_t)ws_bytes, (hipStream_t)stream, mode, ldx, ldw, bias, ldc, ldd, M, N, K);
       g_winner.emplace(bkey, Winner{p.algo, p.own, p.own_tile});

@@ -941,25 +941,17 @@ void launch_x3p(X3P& g, hipStream_t st) {
   g.tiles_m = (g.M + 64 * TM - 1) / (64 * TM);
   g.tiles_n = (g.N + 64 * TN - 1) / (64 * TN);
   const int total = g.tiles_m * g.tiles_n;
-  {
-    // persistent grid: S2T_X3P_WGS workgroups per CU (default: what registers / LDS admit, <= 3)
-    static int wgs = -1;
-    if (wgs < 0) { const char* e = getenv("S2T_X3P_WGS"); wgs = e ? atoi(e) : 0; }
-    const int per_cu = wgs > 0 ? wgs : g.wgs_per_cu > 0 ? g.wgs_per_cu : (TM * TN >= 4 ? 2 : TM * TN >= 2 ? 3 : 4);
-    const int cap = 256 * per_cu;
-    const int grid = std::min(((total + 7) / 8) * 8, cap);
-    if (g.bal_stats)
-      X3P_LAUNCH((x3p_db_kernel<TM, TN, true, NP>), grid, 256, 0);
-    else
-      X3P_LAUNCH((x3p_db_kernel<TM, TN, false, NP>), grid, 256, 0);
-  }
+  // persistent grid: the caller's workgroups per CU, else what registers / LDS admit (<= 4)
+  const int per_cu = g.wgs_per_cu > 0 ? g.wgs_per_cu : (TM * TN >= 4 ? 2 : TM * TN >= 2 ? 3 : 4);
+  const int grid = std::min(((total + 7) / 8) * 8, 256 * per_cu);
+  if (g.bal_stats)
+    X3P_LAUNCH((x3p_db_kernel<TM, TN, true, NP>), grid, 256, 0);
+  else
+    X3P_LAUNCH((x3p_db_kernel<TM, TN, false, NP>), grid, 256, 0);
 }
 
 // block tile from the shape: the widest tile that still gives the chip >= ~2 rounds of workgroups
 int pick_tile(int M, int N) {
-  static int force = -1;      // S2T_X3P_TILE = 11 | 12 | 21 | 22: tuning
-  if (force < 0) { const char* e = getenv("S2T_X3P_TILE"); force = e ? atoi(e) : 0; }
-  if (force > 0) return force;
   const long t22 = (long)((M + 127) / 128) * ((N + 127) / 128);
   if (t22 >= 768) return 22;
   const long t21 = (long)((M + 127) / 128) * ((N + 63) / 64);
@@ -1120,14 +1112,10 @@ int s2t_gemm_x3p(const float* A, long lda, const unsigned short* Bp, int N, int 
       g.op[k] = g_sq.other; g.ldop[k] = g_sq.ld; g.role[k++] = 4;
     }
   }
-  {
-    // S2T_X3P_PRIO: 0 = none; 1 = by the workgroup's slot on its CU (register-staged form; round 4);
-    // 2 (default, round 6) = every wave of these main-stream kernels above the side stream's kernels
-    // on the same CU (33.29 / 33.16 / 33.09 -> 33.07 / 33.17 / 32.92 ms per step, one box)
-    static int prio = -1;
-    if (prio < 0) { const char* e = getenv("S2T_X3P_PRIO"); prio = e ? atoi(e) : 2; }
-    g.prio = prio;
-  }
+  // every wave of these main-stream kernels above the side stream's kernels on the same CU (round 6:
+  // 33.29 / 33.16 / 33.09 -> 33.07 / 33.17 / 32.92 ms per step, one box; 1 = by the workgroup's slot
+  // on its CU, the round-4 rule of the register-staged form; 0 = none)
+  g.prio = 2;
   hipStream_t st = (hipStream_t)stream;
   ++g_x3p_calls;
   if (g_samp.every > 0 && !s2t_prof_start && (g_samp.count++ % g_samp.every) == 0) {

@@ -520,210 +520,8 @@ inline size_t attn_mfma_smem() {
                           8 * 32);
 }
 
-// ---------------------------------------------------------------- backward
-// dS_ij = W_ij (dW_ij - delta_i) on unmasked entries, delta_i = sum_j W_ij dW_ij.
-// bwd_q: workgroup = (64 rows, b, h): delta, dq_i = sum_j dS_ij k_j, dp_i = sum_j dS_ij pos[rel].
-//        thread = (row = tid/4, dgrp = tid%4) accumulates qd/4 dims of dq and one dim of dp.
-__global__ __launch_bounds__(256) void attn_bwd_q_kernel(AttnArgs a, const float* __restrict__ W,
-                                                         int delta_given,
-                                                         float* __restrict__ delta,
-                                                         float* __restrict__ dqkp) {
-  constexpr int JC = 64;   // key chunk
-  __shared__ float s_dS[ROWS][JC + 1];
-  __shared__ float s_K[JC][MAXQD + 1];
-  __shared__ float s_pos[MAXPD][JC + ROWS];
-  __shared__ float s_delta[ROWS];
-  __shared__ float s_dO[ROWS][MAXCD + 1];
-  __shared__ float s_Vc[JC][MAXCD + 1];
-  const float* dW = a.dW;
-  const int cd = pair_dims(a);
-  const int i0 = blockIdx.x * ROWS, b = blockIdx.y, h = blockIdx.z;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* Wb = W + ((long)h * a.B + b) * a.T * a.T;
-  const float* dWb = dW ? dW + ((long)h * a.B + b) * a.T * a.T : nullptr;
-  const float* dW0b = (a.dW0 && h == 0) ? a.dW0 + (long)b * a.T * a.T : nullptr;
-  if (delta_given) {
-    for (int r = threadIdx.x; r < ROWS; r += 256)
-      s_delta[r] = (i0 + r < a.T) ? delta[((long)h * a.B + b) * a.T + i0 + r] : 0.f;
-  } else {
-    // pass 0: delta for the 64 rows from the materialised dW (wave per row, coalesced)
-    for (int r = wave; r < ROWS; r += 4) {
-      const int i = i0 + r;
-      float acc = 0.f;
-      if (i < a.T)
-        for (int j = lane; j < a.T; j += 64) acc = fmaf(Wb[(long)i * a.T + j], dWb[(long)i * a.T + j], acc);
-      acc = wave_sum(acc);
-      if (lane == 0) {
-        s_delta[r] = acc;
-        if (i < a.T) delta[((long)h * a.B + b) * a.T + i] = acc;
-      }
-    }
-  }
-  if (cd) stage_pairs(a, a.pdO, b, h, i0, ROWS, s_dO);
-  __syncthreads();
-  const int row = tid >> 2, dg = tid & 3;
-  const int qd = a.qd, pd = a.pd;
-  const int dper = (qd + 3) / 4;   // dims of dq per thread (<= 8)
-  float accq[8];
-#pragma unroll
-  for (int d = 0; d < 8; ++d) accq[d] = 0.f;
-  float accp0 = 0.f, accp1 = 0.f;  // pos dims dg and dg+4
-  for (int j0 = 0; j0 < a.T; j0 += JC) {
-    __syncthreads();
-    if (cd) {
-      stage_pairs(a, a.pV, b, h, j0, JC, s_Vc);
-      __syncthreads();
-    }
-    // stage dS chunk (coalesced over j), K chunk, pos window
-    for (int idx = tid; idx < ROWS * JC; idx += 256) {
-      const int r = idx / JC, jj = idx % JC;
-      const int i = i0 + r, j = j0 + jj;
-      float v = 0.f;
-      if (i < a.T && j < a.T) {
-        const bool masked = (a.kpm && a.kpm[(long)b * a.T + j]) || (a.amask && a.amask[(long)i * a.T + j]);
-        if (!masked) {
-          const float w = Wb[(long)i * a.T + j];
-          float dw = dWb ? dWb[(long)i * a.T + j] : 0.f;
-          if (dW0b) dw += dW0b[(long)i * a.T + j];
-          for (int d = 0; d < cd; ++d) dw = fmaf(s_dO[r][d], s_Vc[jj][d], dw);
-          v = w * (dw - s_delta[r]);
-        }
-      }
-      s_dS[r][jj] = v;
-    }
-    for (int idx = tid; idx < JC * qd; idx += 256) {
-      const int jj = idx / qd, d = idx % qd;
-      s_K[jj][d] = (j0 + jj < a.T) ? k_row(a, j0 + jj, b, h)[d] : 0.f;
-    }
-    if (a.pos) {
-      const int base = (a.T - 1) - (i0 + ROWS - 1) + j0;
-      for (int idx = tid; idx < (JC + ROWS) * pd; idx += 256) {
-        const int w = idx / pd, d = idx % pd;
-        const int r = base + w;
-        s_pos[d][w] = (r >= 0 && r < 2 * a.T - 1) ? a.pos[(long)r * a.H * pd + h * pd + d] : 0.f;
-      }
-    }
-    __syncthreads();
-    for (int jj = 0; jj < JC; ++jj) {
-      const float ds = s_dS[row][jj];
-#pragma unroll
-      for (int d = 0; d < 8; ++d)
-        if (d < dper) accq[d] = fmaf(ds, s_K[jj][dg * dper + d], accq[d]);
-      if (a.pos) {
-        const int w = (ROWS - 1) - row + jj;
-        if (dg < pd) accp0 = fmaf(ds, s_pos[dg][w], accp0);
-        if (dg + 4 < pd) accp1 = fmaf(ds, s_pos[dg + 4][w], accp1);
-      }
-    }
-  }
-  const int i = i0 + row;
-  if (i < a.T) {
-    float* o = dqkp + ((long)i * a.B + b) * (a.H * (2 * qd + pd));
-    for (int d = 0; d < dper; ++d)
-      if (dg * dper + d < qd) o[h * qd + dg * dper + d] = accq[d];
-    if (dg < pd) o[2 * a.H * qd + h * pd + dg] = a.pos ? accp0 : 0.f;
-    if (dg + 4 < pd) o[2 * a.H * qd + h * pd + dg + 4] = a.pos ? accp1 : 0.f;
-  }
-}
-
-// bwd_k: workgroup = (64 keys, b, h): dk_j = sum_i dS_ij q_i ; dpos[rel] += sum dS_ij p_i
-__global__ __launch_bounds__(256) void attn_bwd_k_kernel(AttnArgs a, const float* __restrict__ W,
-                                                         const float* __restrict__ delta,
-                                                         float* __restrict__ dqkp,
-                                                         float* __restrict__ dpos) {
-  constexpr int IC = 64;   // query chunk
-  __shared__ float s_dS[IC][ROWS + 1];       // [i][j]
-  __shared__ float s_Q[IC][MAXQD + 1];
-  __shared__ float s_P[IC][MAXPD];
-  __shared__ float s_dOc[IC][MAXCD + 1];
-  __shared__ float s_Vk[ROWS][MAXCD + 1];
-  const float* dW = a.dW;
-  const int cd = pair_dims(a);
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  float* s_acc = reinterpret_cast<float*>(smem_raw);   // [pd][T + ROWS]: dpos for rel = j0 + u
-  const int j0 = blockIdx.x * ROWS, b = blockIdx.y, h = blockIdx.z;
-  const int tid = threadIdx.x;
-  const float* Wb = W + ((long)h * a.B + b) * a.T * a.T;
-  const float* dWb = dW ? dW + ((long)h * a.B + b) * a.T * a.T : nullptr;
-  const float* dW0b = (a.dW0 && h == 0) ? a.dW0 + (long)b * a.T * a.T : nullptr;
-  const float* dl = delta + ((long)h * a.B + b) * a.T;
-  if (cd) stage_pairs(a, a.pV, b, h, j0, ROWS, s_Vk);
-  const int col = tid >> 2, dg = tid & 3;
-  const int qd = a.qd, pd = a.pd;
-  const int dper = (qd + 3) / 4;
-  float acck[8];
-#pragma unroll
-  for (int d = 0; d < 8; ++d) acck[d] = 0.f;
-  const int accw = a.T + ROWS;
-  if (dpos)
-    for (int idx = tid; idx < accw * pd; idx += 256) s_acc[idx] = 0.f;
-  for (int i0 = 0; i0 < a.T; i0 += IC) {
-    __syncthreads();
-    if (cd) {
-      stage_pairs(a, a.pdO, b, h, i0, IC, s_dOc);
-      __syncthreads();
-    }
-    for (int idx = tid; idx < IC * ROWS; idx += 256) {
-      const int ii = idx / ROWS, jj = idx % ROWS;
-      const int i = i0 + ii, j = j0 + jj;
-      float v = 0.f;
-      if (i < a.T && j < a.T) {
-        const bool masked = (a.kpm && a.kpm[(long)b * a.T + j]) || (a.amask && a.amask[(long)i * a.T + j]);
-        if (!masked) {
-          float dw = dWb ? dWb[(long)i * a.T + j] : 0.f;
-          if (dW0b) dw += dW0b[(long)i * a.T + j];
-          for (int d = 0; d < cd; ++d) dw = fmaf(s_dOc[ii][d], s_Vk[jj][d], dw);
-          v = Wb[(long)i * a.T + j] * (dw - dl[i]);
-        }
-      }
-      s_dS[ii][jj] = v;
-    }
-    for (int idx = tid; idx < IC * qd; idx += 256) {
-      const int ii = idx / qd, d = idx % qd;
-      s_Q[ii][d] = (i0 + ii < a.T) ? q_row(a, i0 + ii, b, h)[d] : 0.f;
-    }
-    for (int idx = tid; idx < IC * pd; idx += 256) {
-      const int ii = idx / pd, d = idx % pd;
-      s_P[ii][d] = (i0 + ii < a.T) ? p_row(a, i0 + ii, b, h)[d] : 0.f;
-    }
-    __syncthreads();
-    for (int ii = 0; ii < IC; ++ii) {
-      const float ds = s_dS[ii][col];
-#pragma unroll
-      for (int d = 0; d < 8; ++d)
-        if (d < dper) acck[d] = fmaf(ds, s_Q[ii][dg * dper + d], acck[d]);
-    }
-    if (dpos) {
-      // diagonals of the chunk: w = (IC-1) - ii + jj in [0, IC+ROWS-2]; thread per (w, dim)
-      for (int idx = tid; idx < (IC + ROWS - 1) * pd; idx += 256) {
-        const int w = idx / pd, d = idx % pd;
-        float acc = 0.f;
-        const int ii_lo = max(0, (IC - 1) - w), ii_hi = min(IC - 1, (IC - 1) - w + ROWS - 1);
-        for (int ii = ii_lo; ii <= ii_hi; ++ii) acc = fmaf(s_dS[ii][w - (IC - 1) + ii], s_P[ii][d], acc);
-        // u = rel - j0 = (T-1) - (i0 + IC-1) + w ; one thread per (u,d): no LDS atomics needed
-        const int u = (a.T - 1) - (i0 + IC - 1) + w;
-        if (u >= 0 && u < accw) s_acc[d * accw + u] += acc;
-      }
-    }
-  }
-  if (dpos) {
-    __syncthreads();
-    for (int idx = tid; idx < accw * pd; idx += 256) {
-      const int d = idx / accw, u = idx % accw;
-      const int r = j0 + u;
-      const float v = s_acc[idx];
-      if (r < 2 * a.T - 1 && v != 0.f) atomicAdd(&dpos[(long)r * a.H * pd + h * pd + d], v);
-    }
-  }
-  const int j = j0 + col;
-  if (j < a.T) {
-    float* o = dqkp + ((long)j * a.B + b) * (a.H * (2 * qd + pd)) + a.H * qd + h * qd;
-    for (int d = 0; d < dper; ++d)
-      if (dg * dper + d < qd) o[dg * dper + d] = acck[d];
-  }
-}
-
 // ---------------------------------------------------------------- backward on the matrix cores
+// dS_ij = W_ij (dW_ij - delta_i) on unmasked entries, delta_i = sum_j W_ij dW_ij.
 // Per 32x32 score tile:  dW = dOcat . Vcat^T  (+ materialised terms),  dS = W o (dW - delta_i),
 //   dq += dS . K   and   dk += dS^T . Q   on v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate).
 // Accumulator layout of a 32x32 tile: column = lane&31, rows (r&3)+8(r>>2)+4(lane>>5) in the 16
@@ -839,83 +637,9 @@ __device__ __forceinline__ f32x16 ds_tile(const AttnArgs& a, const float* __rest
 
 constexpr int AM_MAXT = 512;      // sequences up to here get the bit-staged mask (8 KB of LDS)
 
-
-// dk: workgroup = (32 keys, b, h); the 4 waves split the query blocks and their partial
-// sums meet in LDS.
-template <int NS>
-__global__ __launch_bounds__(256, 2) void attn_bwd_k_mfma_kernel(AttnArgs a,
-                                                              const float* __restrict__ W,
-                                                              const float* __restrict__ delta,
-                                                              float* __restrict__ dqkp) {
-  constexpr int NSA = NS > 0 ? NS : 1;
-  __shared__ float s_red[4][32][33];   // first the per-wave dO_cat staging, then the dk partials
-  int tile_, slab_;
-  if (!slab_tile((a.T + 31) / 32, a.B * a.H, tile_, slab_)) return;
-  const int j0 = tile_ * 32, b = slab_ % a.B, h = slab_ / a.B;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lo = lane & 31, hi = lane >> 5;
-  const float* Wb = W + ((long)h * a.B + b) * a.T * a.T;
-  const float* dWb = a.dW ? a.dW + ((long)h * a.B + b) * a.T * a.T : nullptr;
-  const float* dW0b = (a.dW0 && h == 0) ? a.dW0 + (long)b * a.T * a.T : nullptr;
-  const float* dlb = delta + ((long)h * a.B + b) * a.T;
-  const int qd = a.qd;
-  float bf[NSA];   // V_cat[j0+lo][hi + 2s]
-#pragma unroll
-  for (int s = 0; s < NS; ++s) bf[s] = pair_elem(a, a.pV, j0 + lo, b, h, hi + 2 * s);
-  f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const int nib = (a.T + 31) / 32;
-  float wn[16];
-  if (wave < nib) load_tile16(Wb, a.T, wave * 32, j0, lo, hi, wn);
-  for (int ib = wave; ib < nib; ib += 4) {
-    const int i0 = ib * 32;
-    float af[NSA], qv[16];
-    f32x16 ndl;
-    if (NS > 0) {
-      // dO_cat rows of this query block: coalesced load -> wave-private LDS -> A fragments
-      constexpr int CDP = 2 * NSA;
-#pragma unroll 4
-      for (int q = 0; q < (32 * CDP + 63) / 64; ++q) {
-        const int idx = lane + 64 * q;
-        const int rr = idx / CDP, k = idx % CDP;
-        if (rr < 32) s_red[wave][rr][k] = pair_elem(a, a.pdO, i0 + rr, b, h, k);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int s = 0; s < NS; ++s) af[s] = s_red[wave][lo][hi + 2 * s];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-    }
-    const unsigned Dp = (unsigned)(a.H * (2 * qd + a.pd));
-    const unsigned qcol = (unsigned)b * Dp + (unsigned)(h * qd + min(lo, qd - 1));
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const unsigned i = (unsigned)min(i0 + acc_row(r, hi), a.T - 1);   // rows beyond T meet dS = 0
-      ndl[r] = -dlb[i];
-      const float q = a.qkp[i * ((unsigned)a.B * Dp) + qcol];
-      qv[r] = lo < qd ? q : 0.f;
-    }
-    f32x16 ds = ds_tile<NS>(a, dWb, dW0b, b, i0, j0, lo, hi, af, bf, wn, ndl);
-    if (ib + 4 < nib) load_tile16(Wb, a.T, i0 + 128, j0, lo, hi, wn);
-    // dk[j][d] += sum_i dS[i][j] q[i][d]: A = dS registers (k = query row), B[k][n = d]
-#pragma unroll
-    for (int s = 0; s < 16; ++s) z = __builtin_amdgcn_mfma_f32_32x32x2f32(ds[s], qv[s], z, 0, 0, 0);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < 16; ++r) s_red[wave][acc_row(r, hi)][lo] = z[r];
-  __syncthreads();
-  for (int idx = tid; idx < 32 * 32; idx += 256) {
-    const int jj = idx >> 5, d = idx & 31;
-    const int j = j0 + jj;
-    if (j < a.T && d < qd) {
-      const float v = s_red[0][jj][d] + s_red[1][jj][d] + s_red[2][jj][d] + s_red[3][jj][d];
-      dqkp[((long)j * a.B + b) * (a.H * (2 * qd + a.pd)) + a.H * qd + h * qd + d] = v;
-    }
-  }
-}
-
 // dk, shared-operand form: workgroup = (128 keys, b, h), one 32-key tile per wave, ALL waves walk
-// the same query blocks.  The kernel above is bound by the volume of L1 fills, not by the matrix
+// the same query blocks.  The earlier form (one 32-key tile per workgroup, the 4 waves splitting the
+// query blocks) was bound by the volume of L1 fills, not by the matrix
 // pipe (T = 495: 248 us against a 48 us MFMA floor; without its in-loop global loads 108 us, with
 // them prefetched a block ahead still 259 us): each of a slab's 16 key-tile workgroups re-reads the
 // query-side rows (q, dO_cat, delta -- 9 of the 13 KB a tile needs) for its own use.  Here those
@@ -1250,7 +974,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
 template <int NS>
 int launch_attn_bwd_mfma(const AttnArgs& a, const float* W, const float* delta, float* dqkp,
                          float* dpos, float* ws, hipStream_t st) {
-  const dim3 gq(slab_grid((a.T + 127) / 128, a.B * a.H)), gk(slab_grid((a.T + 31) / 32, a.B * a.H));
+  const dim3 gq(slab_grid((a.T + 127) / 128, a.B * a.H));
   if (a.pd <= 4)
     hipLaunchKernelGGL((attn_bwd_q_mfma_kernel<NS, 4>), gq, dim3(256), 0, st, a, W, delta, dqkp,
                        a.pos ? ws : nullptr);
@@ -1258,14 +982,8 @@ int launch_attn_bwd_mfma(const AttnArgs& a, const float* W, const float* delta, 
     hipLaunchKernelGGL((attn_bwd_q_mfma_kernel<NS, 8>), gq, dim3(256), 0, st, a, W, delta, dqkp,
                        a.pos ? ws : nullptr);
   S2T_CHECK_LAUNCH();
-  static const bool k_old = getenv("S2T_ATTN_BWD_K_OLD") != nullptr;   // one 32-key tile per workgroup
   const int nz = (a.pos && a.pd > 0) ? (2 * a.T - 1) * a.H * a.pd : 0;
-  if (k_old) {
-    if (nz && hipMemsetAsync(dpos, 0, sizeof(float) * (size_t)nz, st) != hipSuccess) return -3;
-    hipLaunchKernelGGL((attn_bwd_k_mfma_kernel<NS>), gk, dim3(256), 0, st, a, W, delta, dqkp);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_k3_mfma_kernel<NS>), gq, dim3(256), 0, st, a, W, delta, dqkp, dpos, nz);
-  }
+  hipLaunchKernelGGL((attn_bwd_k3_mfma_kernel<NS>), gq, dim3(256), 0, st, a, W, delta, dqkp, dpos, nz);
   S2T_CHECK_LAUNCH();
   if (a.pos && a.pd > 0) {
     const int n = (2 * a.T - 1) * a.pd;
@@ -1450,9 +1168,7 @@ extern "C" int s2t_attn_apply(const float* W, const float* v, int T, int B, int 
   if (T <= 0 || B <= 0 || H <= 0) return 0;
   if (dv <= 0 || dv > 16) return -1;
   dim3 grid((T + 127) / 128, B, H);
-  static int old = -1;
-  if (old < 0) { const char* e = getenv("S2T_ATTN_APPLY_OLD"); old = e ? atoi(e) : 0; }
-  const bool wide = !old && T >= 4 && T <= 16384 && (dv & 3) == 0 &&
+  const bool wide = T >= 4 && T <= 16384 && (dv & 3) == 0 &&
                     ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 &&
                     (reinterpret_cast<uintptr_t>(W) & 3) == 0;
   if (wide) {
@@ -1529,10 +1245,9 @@ extern "C" int s2t_relpos_attn_fwd_flag(const float* qkp, const float* pos,
     attr_done = true;
   }
   // MFMA path: whole key matrix of a (b,h) in LDS, scores of a 32-row strip in accumulators
-  static const bool no_mfma = getenv("S2T_ATTN_FWD_OLD") != nullptr;
   const bool aligned = ((reinterpret_cast<uintptr_t>(qkp) & 15) == 0) && (qd % 8 == 0) &&
                        ((H * (2 * qd + pd)) % 4 == 0) && ((H * qd) % 4 == 0);
-  if (!no_mfma && T <= 512 && pd <= 4 && aligned) {
+  if (T <= 512 && pd <= 4 && aligned) {
     const int v = (pos ? 1 : 0) + (amask ? 2 : 0);
     int rc;
     if (T > 256) rc = launch_fwd_mfma<8, 2>(v, a, W, st);
@@ -1556,8 +1271,8 @@ extern "C" int s2t_relpos_attn_fwd_flag(const float* qkp, const float* pos,
 // Gradient of W is given materialised (dW) and/or as factors (see AttnArgs): dW0 (B,T,T) for
 // head 0, and up to two (dO_c, V_c) pairs of (T,B,H*dv_c) tensors.  When any factor is used,
 // `delta_ws` must hold delta[h,b,i] = sum_j W dW on entry (delta_given = 1; for the pairs it is
-// sum_d dO_c * O_c, O_c = the apply's forward output).  dqkp (T,B,Dp) is fully written; dpos
-// (2T-1, H*pd) must be zeroed by the caller (accumulated) or NULL when pos was skipped.
+// sum_d dO_c * O_c, O_c = the apply's forward output).  dqkp (T,B,Dp) and dpos
+// (2T-1, H*pd) are fully written (dpos is cleared by the dk launch); dpos is NULL when pos was skipped.
 extern "C" long s2t_relpos_attn_bwd_workspace_floats(int T, int B, int H, int pd) {
   const long nj = (T + 31) / 32;
   return (long)B * H * nj * (nj + 1) * 32 * pd;
@@ -1575,33 +1290,17 @@ extern "C" int s2t_relpos_attn_bwd(const float* qkp, const float* pos, const uns
   if ((long)T * T >= (1L << 31) || (long)T * B * H * (2 * qd + pd) >= (1L << 31)) return -1;
   if (!dW && !delta_given) return -1;
   AttnArgs a{qkp, pos, kpm, amask, T, B, H, qd, pd, dW, dW0, {dO1, dO2}, {V1, V2}, {dv1, dv2}};
-  static const bool use_valu = getenv("S2T_ATTN_BWD_VALU") != nullptr;
-  if (!use_valu) {
-    hipStream_t st = (hipStream_t)stream;
-    if (pos && pd > 0 && !workspace) return -1;
-    if (!delta_given) {
-      const long rows = (long)H * B * T;
-      hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, W,
-                         dW, rows, T, delta_ws);
-      S2T_CHECK_LAUNCH();
-    }
-    const int cd = (dO1 ? dv1 : 0) + (dO2 ? dv2 : 0);
-    if (cd == 0) return launch_attn_bwd_mfma<0>(a, W, delta_ws, dqkp, dpos, workspace, st);
-    if (cd <= 12) return launch_attn_bwd_mfma<6>(a, W, delta_ws, dqkp, dpos, workspace, st);
-    if (cd <= 24) return launch_attn_bwd_mfma<12>(a, W, delta_ws, dqkp, dpos, workspace, st);
-    return launch_attn_bwd_mfma<16>(a, W, delta_ws, dqkp, dpos, workspace, st);
+  hipStream_t st = (hipStream_t)stream;
+  if (pos && pd > 0 && !workspace) return -1;
+  if (!delta_given) {
+    const long rows = (long)H * B * T;
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, W,
+                       dW, rows, T, delta_ws);
+    S2T_CHECK_LAUNCH();
   }
-  dim3 grid((T + ROWS - 1) / ROWS, B, H);
-  if (pos && pd > 0 &&
-      hipMemsetAsync(dpos, 0, sizeof(float) * (size_t)(2 * T - 1) * H * pd, (hipStream_t)stream) != hipSuccess)
-    return -3;
-  hipLaunchKernelGGL(attn_bwd_q_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, W, delta_given,
-                     delta_ws, dqkp);
-  S2T_CHECK_LAUNCH();
-  const size_t sm = pos ? sizeof(float) * (size_t)(T + ROWS) * pd : 0;
-  if (sm > 64 * 1024) return -1;
-  hipLaunchKernelGGL(attn_bwd_k_kernel, grid, dim3(256), sm, (hipStream_t)stream, a, W, delta_ws,
-                     dqkp, pos ? dpos : nullptr);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  const int cd = (dO1 ? dv1 : 0) + (dO2 ? dv2 : 0);
+  if (cd == 0) return launch_attn_bwd_mfma<0>(a, W, delta_ws, dqkp, dpos, workspace, st);
+  if (cd <= 12) return launch_attn_bwd_mfma<6>(a, W, delta_ws, dqkp, dpos, workspace, st);
+  if (cd <= 24) return launch_attn_bwd_mfma<12>(a, W, delta_ws, dqkp, dpos, workspace, st);
+  return launch_attn_bwd_mfma<16>(a, W, delta_ws, dqkp, dpos, workspace, st);
 }

@@ -46,9 +46,8 @@ struct ConvArgs {
   const float* wk;      // (C,K)
   const float* bk;      // (C) or null
   const float* scale;   // (2,C,K) or null
-  // t-tile of a workgroup = blockIdx.z + z_base, + z_jump from z_split on: a launch covers either the
-  // INTERIOR tiles [n_lo, n_hi) (no frame within K of a chunk edge: edge scale == 1, no edge arrays
-  // and no scaled-gradient tile in LDS -- 36 instead of 52 / 76 KB at K = 31) or the others
+  // t-tile of a workgroup = blockIdx.z + z_base, + z_jump from z_split on.  Every launch covers all
+  // tiles (0, 1 << 30, 0); the fields stay: without them 56 of these kernels allocate registers differently
   int z_base, z_split, z_jump;
   int nt;               // t-tiles in all (partial-sum slots of the weight kernel)
 };
@@ -796,16 +795,6 @@ size_t conv_smem(bool with_red, int tiles, bool edge) {
                           (with_red ? 256 : 0));
 }
 
-// t-tiles [n_lo, n_hi) are interior (single chunk: no frame of the tile or its halo within K of
-// either end of the sequence)
-inline void interior_tiles(int T, int K, int nt, int* n_lo, int* n_hi) {
-  int lo = 0, hi = nt;
-  while (lo < nt && lo * TT - K / 2 < K) ++lo;
-  while (hi > lo && (hi - 1) * TT + TT + K / 2 > T - K) --hi;
-  *n_lo = lo;
-  *n_hi = hi;
-}
-
 }  // namespace
 
 #define S2T_CONV_DISPATCH(K, BODY)  \
@@ -822,31 +811,19 @@ static int conv_args_ok(int T, int B, int C, int K, int chunk) {
   return T > 0 && B > 0 && C > 0 && (K & 1) && chunk > 0;
 }
 
-// One launch: the EDGE kernel over all tiles, or -- a plain depthwise Conv1d, nothing to scale -- the
-// lean one (EDGE = false: no edge arrays in LDS).
-struct ZSplit {
-  int nt, n_lo, n_hi;
-  ZSplit(int T, int K, bool gen, bool has_scale) {
-    nt = (T + TT - 1) / TT;
-    if (gen) { n_lo = n_hi = 0; }                    // everything through the EDGE kernel
-    else if (!has_scale) { n_lo = 0; n_hi = nt; }    // nothing to scale: everything interior
-    else if (getenv("S2T_CONV_SPLIT")) interior_tiles(T, K, nt, &n_lo, &n_hi);
-    else { n_lo = n_hi = 0; }
-    // (measured at the C3 shapes: the interior kernel alone over ALL tiles is 20-40 % faster than
-    // the edge kernel, but two launches -- each with its own tail -- are 30-45 % slower than one;
-    // the split is kept for experiments: S2T_CONV_SPLIT=1)
-  }
-  int n_int() const { return n_hi - n_lo; }
-  int n_edge() const { return nt - (n_hi - n_lo); }
-  void set_int(ConvArgs& a) const { a.z_base = n_lo; a.z_split = 1 << 30; a.z_jump = 0; a.nt = nt; }
-  void set_edge(ConvArgs& a) const { a.z_base = 0; a.z_split = n_lo; a.z_jump = n_hi - n_lo; a.nt = nt; }
+// One launch over all nt t-tiles: the EDGE kernel, or -- a plain depthwise Conv1d, nothing to scale --
+// the lean one (EDGE = false: no edge arrays in LDS).  (Measured at the C3 shapes: the lean kernel on
+// the interior tiles of a scaled conv plus the edge kernel on the rest is 30-45 % slower than one launch.)
+struct ConvTiles {
+  int nt;
+  bool edge;
+  ConvTiles(int T, bool gen, bool has_scale) : nt((T + TT - 1) / TT), edge(gen || has_scale) {}
 };
 
 // sub-block size of the chunked (GEN) kernels' masked-window form: min(chunk, FPT) when chunk is a
 // power of two (every chunk_size / downsampling pair of the YAMLs), 0 = the per-tap test
 static int conv_subblock(int chunk) {
-  static const bool on = [] { const char* e = getenv("S2T_CONV_SUBBLOCK"); return !e || atoi(e) != 0; }();
-  return (on && chunk >= 2 && (chunk & (chunk - 1)) == 0) ? std::min(chunk, FPT) : 0;
+  return (chunk >= 2 && (chunk & (chunk - 1)) == 0) ? std::min(chunk, FPT) : 0;
 }
 #define S2T_CONV_GEN_SB(SBSEL, LAUNCH) \
   switch (SBSEL) {                     \
@@ -866,17 +843,15 @@ static int zipconv_fwd_impl(const float* u, long ld, int gate_off, const unsigne
   ConvArgs a{u, ld, gate_off, mask, T, B, C, chunk, wc, bc, wk, bk, scale, 0, 1 << 30, 0, 0};
   hipStream_t st = (hipStream_t)stream;
   const bool gen = chunk < T;
-  const ZSplit z(T, K, gen, scale != nullptr);
+  const ConvTiles z(T, gen, scale != nullptr);
   const unsigned gx = (C + 63) / 64;
-  if (z.n_int() > 0) {
-    z.set_int(a);
-    S2T_CONV_DISPATCH(K, hipLaunchKernelGGL((zipconv_fwd_kernel<KK, false, false>), dim3(gx, B, z.n_int()),
+  a.nt = z.nt;
+  if (!z.edge) {
+    S2T_CONV_DISPATCH(K, hipLaunchKernelGGL((zipconv_fwd_kernel<KK, false, false>), dim3(gx, B, z.nt),
                                             dim3(256), conv_smem<KK>(false, 1, false), st, a, y, y2, act_off, act_c));
     S2T_CHECK_LAUNCH();
-  }
-  if (z.n_edge() > 0) {
-    z.set_edge(a);
-    const dim3 grid(gx, B, z.n_edge());
+  } else {
+    const dim3 grid(gx, B, z.nt);
     if (!gen) {
       S2T_CONV_DISPATCH(K, hipLaunchKernelGGL((zipconv_fwd_kernel<KK, false, true>), grid, dim3(256),
                                               conv_smem<KK>(false, 1, true), st, a, y, y2, act_off, act_c));
@@ -933,19 +908,17 @@ extern "C" long s2t_zipconv_bwd_workspace_floats(int T, int B, int C, int K) {
 }
 
 // the data-gradient kernels of a backward call on stream st
-static int zipconv_bwd_launch_data(ConvArgs a, int T, int B, int C, int K, bool gen, const ZSplit& z,
+static int zipconv_bwd_launch_data(ConvArgs a, int T, int B, int C, int K, bool gen, const ConvTiles& z,
                                    const float* dy, float* du, hipStream_t st) {
   const unsigned gx = (C + 63) / 64;
-  if (z.n_int() > 0) {
-    z.set_int(a);
+  a.nt = z.nt;
+  if (!z.edge) {
     S2T_CONV_DISPATCH(K, hipLaunchKernelGGL((zipconv_bwd_data_kernel<KK, false, false>),
-                                            dim3(gx, B, z.n_int()), dim3(256),
+                                            dim3(gx, B, z.nt), dim3(256),
                                             conv_smem<KK>(false, 1, false), st, a, dy, du));
     S2T_CHECK_LAUNCH();
-  }
-  if (z.n_edge() > 0) {
-    z.set_edge(a);
-    const dim3 grid(gx, B, z.n_edge());
+  } else {
+    const dim3 grid(gx, B, z.nt);
     if (!gen) {
       S2T_CONV_DISPATCH(K, hipLaunchKernelGGL((zipconv_bwd_data_kernel<KK, false, true>), grid, dim3(256),
                                               conv_smem<KK>(false, 1, true), st, a, dy, du));
@@ -961,7 +934,7 @@ static int zipconv_bwd_launch_data(ConvArgs a, int T, int B, int C, int K, bool 
 }
 
 // the parameter-gradient kernels (taps, biases, edge scales) + their reduction on stream st
-static int zipconv_bwd_launch_params(ConvArgs a, int T, int B, int C, int K, bool gen, const ZSplit& z,
+static int zipconv_bwd_launch_params(ConvArgs a, int T, int B, int C, int K, bool gen, const ConvTiles& z,
                                      const float* wc, const float* scale, const float* dy, float* dwc,
                                      float* dbc, float* dwk, float* dbk, float* dscale,
                                      float* workspace, hipStream_t st) {
@@ -976,16 +949,14 @@ static int zipconv_bwd_launch_params(ConvArgs a, int T, int B, int C, int K, boo
   if (BB > 16) BB = 16;
   const unsigned gy = (B + BB - 1) / BB;             // utterance groups
   float* const dsc = (scale && dscale) ? dscale : nullptr;
-  if (z.n_int() > 0) {
-    z.set_int(a);
-    S2T_CONV_DISPATCH(K, hipLaunchKernelGGL((zipconv_bwd_w_kernel<KK, false, false>), dim3(gx, gy, z.n_int()),
+  a.nt = z.nt;
+  if (!z.edge) {
+    S2T_CONV_DISPATCH(K, hipLaunchKernelGGL((zipconv_bwd_w_kernel<KK, false, false>), dim3(gx, gy, z.nt),
                                             dim3(256), conv_smem<KK>(true, 1, false), st, a, dy, BB,
                                             workspace, dsc));
     S2T_CHECK_LAUNCH();
-  }
-  if (z.n_edge() > 0) {
-    z.set_edge(a);
-    const dim3 gridw(gx, gy, z.n_edge());
+  } else {
+    const dim3 gridw(gx, gy, z.nt);
     if (!gen) {
       S2T_CONV_DISPATCH(K, hipLaunchKernelGGL((zipconv_bwd_w_kernel<KK, false, true>), gridw, dim3(256),
                                               conv_smem<KK>(true, 1, true), st, a, dy, BB, workspace, dsc));
@@ -1019,7 +990,7 @@ extern "C" int s2t_zipconv_bwd(const float* u, long ld, int gate_off, const unsi
   hipStream_t st = (hipStream_t)stream;
   ConvArgs a{u, ld, gate_off, mask, T, B, C, chunk, wc, nullptr, wk, bk, scale, 0, 1 << 30, 0, 0};
   const bool gen = chunk < T;
-  const ZSplit z(T, K, gen, scale != nullptr);
+  const ConvTiles z(T, gen, scale != nullptr);
   const unsigned gx = (C + 63) / 64;
   // (a one-kernel form of both gradients was built in round 3 and measured SLOWER -- 137 / 105 / 82 /
   // 49 us against 112 / 89 / 49 / 44 at T = 495 / 248 / 124 / 62: the union of the two bodies needs
@@ -1040,7 +1011,7 @@ extern "C" int s2t_zipconv_bwd_data(const float* u, long ld, int gate_off, const
   if (!conv_args_ok(T, B, C, K, chunk)) return -1;
   ConvArgs a{u, ld, gate_off, mask, T, B, C, chunk, wc, nullptr, wk, bk, scale, 0, 1 << 30, 0, 0};
   const bool gen = chunk < T;
-  const ZSplit z(T, K, gen, scale != nullptr);
+  const ConvTiles z(T, gen, scale != nullptr);
   return zipconv_bwd_launch_data(a, T, B, C, K, gen, z, dy, du, (hipStream_t)stream);
 }
 
@@ -1053,7 +1024,7 @@ extern "C" int s2t_zipconv_bwd_params(const float* u, long ld, int gate_off,
   if (!conv_args_ok(T, B, C, K, chunk)) return -1;
   ConvArgs a{u, ld, gate_off, mask, T, B, C, chunk, wc, nullptr, wk, bk, scale, 0, 1 << 30, 0, 0};
   const bool gen = chunk < T;
-  const ZSplit z(T, K, gen, scale != nullptr);
+  const ConvTiles z(T, gen, scale != nullptr);
   return zipconv_bwd_launch_params(a, T, B, C, K, gen, z, wc, scale, dy, dwc, dbc, dwk, dbk, dscale,
                                    workspace, (hipStream_t)stream);
 }

@@ -817,12 +817,11 @@ extern "C" int s2t_norm_bypass_bwd(const float* x, const float* bias, const floa
   if (rows <= 0) return 0;
   if (D <= 0 || D > 1024 || B <= 0) return -1;
   hipStream_t st = (hipStream_t)stream;
-  static const int form16 = [] { const char* e = getenv("S2T_NB_BWD16"); return e ? atoi(e) : 1; }();
   const uintptr_t al = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(bias) |
                        reinterpret_cast<uintptr_t>(orig) | reinterpret_cast<uintptr_t>(bypass_scale) |
                        reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(fm) |
                        reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(d_orig);
-  if (form16 && (D & 3) == 0 && (al & 15) == 0) {
+  if ((D & 3) == 0 && (al & 15) == 0) {
     constexpr unsigned cap16 = 512u;
     // workgroups: ~16 rows per wave (four trips of four; 8 below 8 192 rows), at most 512 -- measured at the C3 shapes
     // (tools/bench_atomics.py): more workgroups lengthen the atomics' tail, fewer starve the loads

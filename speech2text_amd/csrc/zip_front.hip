@@ -457,9 +457,7 @@ extern "C" int s2t_dwconv2d_nhwc_wgrad(const float* x, const float* dy, int N, i
   const int nparts = (W + RWO - 1) / RWO, nrr = (H + RRT - 1) / RRT;
   // (the workspace is sized for (H + 7) / 8 partial blocks per (n, c-tile): holds for W <= 98)
   constexpr int CPB = 256 / RCT;
-  static int ring = -1;      // S2T_DWCONV_WGRAD_RING=0: the roll kernel's MODE 2
-  if (ring < 0) { const char* e = getenv("S2T_DWCONV_WGRAD_RING"); ring = e ? atoi(e) : 1; }
-  if (KH == 7 && KW == 7 && ring) {
+  if (KH == 7 && KW == 7) {      // the ring form; else, or when its workspace bound fails: the roll kernel's MODE 2
     // rows per thread: the 2 workgroups per CU that fit (210 VGPRs) in ONE round where the map is
     // tall enough (each thread pays KH - 1 extra row steps, so not below 24 rows)
     const long per_row = (long)nparts * N * ((C + RCT - 1) / RCT);   // thread groups per row range

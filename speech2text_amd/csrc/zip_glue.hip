@@ -720,8 +720,7 @@ extern "C" int s2t_bypass_up_bwd(const float* orig, const float* src, const floa
   const uintptr_t al = reinterpret_cast<uintptr_t>(orig) | reinterpret_cast<uintptr_t>(src) |
                        reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(g) |
                        reinterpret_cast<uintptr_t>(d_orig) | reinterpret_cast<uintptr_t>(d_src);
-  static const bool form16 = [] { const char* e = getenv("S2T_BYPASS_UP_BWD16"); return !e || e[0] != '0'; }();
-  if (form16 && (C & 3) == 0 && C <= 1024 && (al & 15) == 0 && (up == 2 || up == 4 || up == 8)) {
+  if ((C & 3) == 0 && C <= 1024 && (al & 15) == 0 && (up == 2 || up == 4 || up == 8)) {
     const int C4 = C / 4;
     const long F = (long)B * C4, n = (long)Ts * F;
     // the grid's stride (256 x blocks) must be a multiple of C4: blocks in multiples of C4 / gcd(256, C4)

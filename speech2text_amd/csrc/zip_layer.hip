@@ -188,6 +188,10 @@ int fail(int rc, const char* what) {
 
 inline bool dec(const Ctx& c, int i) { return c.c.dec[i] != 0; }
 
+// arithmetic class of the Whiten penalty product: statistics (3) on the three-launch form, data
+// gradient (1) on the pre-split-weight kernel (zip_kernels._WHITEN_PG_CLS / _WHITEN_PG2_CLS)
+constexpr int WHITEN_PG_CLS = 3, WHITEN_PG2_CLS = 1;
+
 // ---- streams
 int fork_side(Ctx& c) {              // side stream ordered after the work enqueued so far on the main one
   RUN(s2t_stream_order((void*)c.st, (void*)c.side));
@@ -199,20 +203,11 @@ int fork_side(Ctx& c) {              // side stream ordered after the work enque
 // every one of them at a fork).  Nothing on the main stream waits for the side stream's work inside a
 // pass -- forward's statistics are read by backward, backward's parameter gradients by the optimizer -- so
 // the side-stream launches of a pass are collected and leave behind ONE fork at its end (their operands
-// live in the pass's workspace, which the caller keeps until the join).  S2T_SIDE_DEFER=0: a fork per site.
-// (bits: 1 forward's statistics, 2 backward's parameter gradients, 4 backward's implied event waits)
-int defer_bits() {
-  static const int bits = [] { const char* e = getenv("S2T_SIDE_DEFER"); return e ? atoi(e) : 7; }();
-  return bits;
-}
+// live in the pass's workspace, which the caller keeps until the join).
 template <class F>
-int side_run(Ctx& c, int bit, F&& f) {   // f(): launches on c.side, ordered after the main stream's work so far
-  if (defer_bits() & bit) {
-    c.later.emplace_back(std::forward<F>(f));
-    return 0;
-  }
-  TRY(fork_side(c));
-  return f();
+int side_run(Ctx& c, F&& f) {   // f(): launches on c.side, ordered after the main stream's work so far
+  c.later.emplace_back(std::forward<F>(f));
+  return 0;
 }
 int flush_side(Ctx& c) {
   if (c.later.empty()) return 0;
@@ -395,9 +390,8 @@ int whiten_stats(Ctx& c, WStat& s, const float* x, long ldx, long R, int C, int 
       RUN(s2t_whiten_prep(s.cov, s.mean, s.scal, s.G, s.cg, s.dcov, s.bias, s.sums, (void*)q));
       RUN(s2t_x3p_split(s.dcov, sc->tab, 1, sc->blocks, s.pieces, (void*)q));
       if (s.pg) {
-        static const int pg_cls = [] { const char* e = getenv("S2T_WHITEN_PG_CLS"); return e ? atoi(e) : 1; }();
-        const S2tGemmClass cls(pg_cls);
-        const bool two = s2t_gemm_arith_of(pg_cls) == 2;
+        const S2tGemmClass cls(WHITEN_PG2_CLS);
+        const bool two = s2t_gemm_arith_of(WHITEN_PG2_CLS) == 2;
         const int tile = c.c.x3p_tile ? c.c.x3p_tile : ((C & 127) == 0 ? (two ? 2212 : 312) : (two ? 2221 : 321));
         const int rc = s2t_gemm_x3p_sq(x, ldx, s.pieces, C, C, s.pg, C, (int)R, s.bias, nullptr, 0, s.sums, tile, (void*)q);
         if (rc != 0) return fail(rc, "s2t_gemm_x3p_sq(whiten, forward)");
@@ -408,7 +402,7 @@ int whiten_stats(Ctx& c, WStat& s, const float* x, long ldx, long R, int C, int 
     HIPRUN(hipEventRecord(s.ev, q));
     return 0;
   };
-  return on_side ? side_run(c, 1, launch) : launch();
+  return on_side ? side_run(c, launch) : launch();
 }
 
 // zip_kernels.whiten_backward: g (R,C) dense -> *out (g itself when the penalty is inactive)
@@ -440,12 +434,11 @@ int whiten_bwd(Ctx& c, int site, const S2tZlWh& w, WStat& s, const float* x, lon
     if (c.dry) return 0;
     // the penalty product is a data-gradient-like product (class D: two pieces by default -- measured:
     // every C3 gradient stays where the six-product step has it; it is the covariance x^T x
-    // that needs the six products); S2T_WHITEN_PG_CLS=3 files it under the statistics
-    static const int pg_cls = [] { const char* e = getenv("S2T_WHITEN_PG_CLS"); return e ? atoi(e) : 1; }();
-    const S2tGemmClass cls(pg_cls);
+    // that needs the six products)
+    const S2tGemmClass cls(WHITEN_PG2_CLS);
     // block tile by the output width (the plan table has no bucket for these C x C products): 128-wide
     // column tiles where C is a multiple of 128, 64-wide otherwise; the 32-deep LDS-DMA form with two pieces
-    const bool two = s2t_gemm_arith_of(pg_cls) == 2;
+    const bool two = s2t_gemm_arith_of(WHITEN_PG2_CLS) == 2;
     const int tile = c.c.x3p_tile ? c.c.x3p_tile : ((C & 127) == 0 ? (two ? 2212 : 312) : (two ? 2221 : 321));
     const int rc = s2t_gemm_x3p_sq(x, ldx, s.pieces, C, C, pg, C, (int)R, s.bias, g, C, s.sums, tile,
                                    (void*)c.st);
@@ -461,10 +454,8 @@ int whiten_bwd(Ctx& c, int site, const S2tZlWh& w, WStat& s, const float* x, lon
   float* o = c.ar.alloc(R * C);
   if (c.dry) return 0;
   RUN(s2t_whiten_dcov(s.cov, s.mean, s.scal, s.G, s.cg, dcov, bias, sums, (void*)c.st));
-  // the penalty's product x dcov: class S (statistics) -- S2T_WHITEN_PG_CLS=1 files it under the data
-  // gradients instead (experiment: which of the two statistics products needs the six-product form)
-  static const int pg_cls = [] { const char* e = getenv("S2T_WHITEN_PG_CLS"); return e ? atoi(e) : 3; }();
-  const S2tGemmClass cls(pg_cls);
+  // the penalty's product x dcov: class S (statistics)
+  const S2tGemmClass cls(WHITEN_PG_CLS);
   if (c.c.whiten_sq) {               // the two norms of (g, pg) from the product's own epilogue
     const int rc = s2t_gemm_f32_sq(1, x, ldx, dcov, C, pg, C, (int)R, C, C, bias, g, C, sums, (void*)c.st);
     if (rc == 0) {
@@ -529,7 +520,7 @@ int bal_stats_fwd(Ctx& c, int site, const float* x, long ldx, long R, int C, int
   c.s.bst[site] = st;
   if (c.dry) return 0;
   c.s.bal_fwd = 1;
-  return side_run(c, 1, [&c, st, x, ldx, R, C, coef]() -> int {
+  return side_run(c, [&c, st, x, ldx, R, C, coef]() -> int {
     HIPRUN(hipMemsetAsync(st, 0, 2048 * sizeof(float), c.side));
     RUN(s2t_balancer_stats(x, ldx, R, C, st, (void*)c.side));
     if (coef)                        // (the epilogue form's per-column coefficients, off the data-gradient chain too)
@@ -849,7 +840,7 @@ int conv_bwd(Ctx& c, int i, int d0, const float* x_in, const float* g, const flo
     RUN(s2t_zipconv_bwd_data(sv.u, 2 * D, D, c.c.k8, T, B, D, m.K, sv.chunk, m.wc, m.wk, m.bk, m.scale, dy, du,
                              (void*)c.st));
     if (!c.dry)
-      TRY(side_run(c, 2, [&c, &m, &sv, dy, ws, T, B, D]() -> int {
+      TRY(side_run(c, [&c, &m, &sv, dy, ws, T, B, D]() -> int {
         RUN(s2t_zipconv_bwd_params(sv.u, 2 * D, D, c.c.k8, T, B, D, m.K, sv.chunk, m.wc, m.wk, m.bk, m.scale, dy,
                                    m.gwc, m.gbc, m.gwk, m.gbk, m.gscale, ws, (void*)c.side));
         return 0;
@@ -928,7 +919,7 @@ int layer_bwd(Ctx& c, int phase) {
     // forward's Balancer statistics (side stream).  The side stream runs in order: once this stream has
     // waited for a LATER layer's event -- backward visits the layers in reverse -- the wait (a barrier packet
     // of its own) is implied
-    if (s.bal_fwd && !c.dry && !((defer_bits() & 4) && g_bal_waited_on == (void*)c.st && s.bal_seq <= g_bal_waited)) {
+    if (s.bal_fwd && !c.dry && !(g_bal_waited_on == (void*)c.st && s.bal_seq <= g_bal_waited)) {
       HIPRUN(hipStreamWaitEvent(c.st, s.bal_ev, 0));
       g_bal_waited_on = (void*)c.st;
       g_bal_waited = s.bal_seq;
@@ -1020,7 +1011,7 @@ int layer_bwd(Ctx& c, int phase) {
   }
   if (!c.dry && s.nprob > 0) {
     if (c.c.wgrad_side && c.side) {
-      TRY(side_run(c, 2, [&c, &s]() -> int {
+      TRY(side_run(c, [&c, &s]() -> int {
         RUN(s2t_gemm_tn_grouped(s.nprob, s.probs, (void*)c.side));
         return 0;
       }));

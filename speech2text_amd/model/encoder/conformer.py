@@ -15,7 +15,6 @@ and models whose parameters are not in a FlatStore, with the same kernels one op
 import dataclasses
 from typing import Tuple
 
-import os
 
 import torch
 import torch.nn as nn
@@ -80,24 +79,17 @@ class Subsampling(nn.Module):
             x = x.unsqueeze(1).contiguous(memory_format=torch.channels_last)
         for m in convs:
             if isinstance(m, nn.Conv2d):
-                own = os.environ.get("S2T_CONF_CONV2", "own")          # (read per call: own | gemm | lib)
                 plain = (x.is_cuda and tuple(m.kernel_size) == (3, 3) and tuple(m.padding) == (0, 0)
                          and tuple(m.dilation) == (1, 1) and m.groups == 1)
-                if own == "own" and plain and zk.conv3x3_s2_map_ok(x.permute(0, 2, 3, 1), m.weight, m.stride):
+                if plain and zk.conv3x3_s2_map_ok(x.permute(0, 2, 3, 1), m.weight, m.stride):
                     # the pre-split bf16x3 GEMM with implicit operands, forward and data gradient
                     # (zk._Conv3x3S2Map; weight gradient: the implicit-im2col TN kernel): no library
                     # convolution and no patch matrix on the default path
                     y = zk.conv3x3_s2_map(x.permute(0, 2, 3, 1), m.weight, m.bias)
                     x = y.permute(0, 3, 1, 2)
-                elif (own == "gemm" and plain and x.shape[1] % 4 == 0 and m.out_channels % 4 == 0):
-                    # S2T_CONF_CONV2=gemm: implicit-im2col MFMA GEMM on the channel-last map
-                    # (s2t_conv3x3_gemm, the kernel of the zipformer frontend) for the forward and
-                    # the weight gradient.  Measured (round 4, C2): 25.3 ms/step against 24.4 with
-                    # the library's NHWC implicit-GEMM kernels (127 TFLOP/s on this 178 GFLOP
-                    # product), so the library stays the default
-                    y = zk.conv3x3_nhwc(x.permute(0, 2, 3, 1), m.weight, m.bias, m.stride)
-                    x = y.permute(0, 3, 1, 2)
                 else:
+                    # (the zipformer frontend's implicit-im2col kernel here, round 4, C2: 25.3 ms/step
+                    # against 24.4 with the library)
                     x = F.conv2d(x, m.weight.contiguous(memory_format=torch.channels_last), m.bias,
                                  m.stride)
             else:

@@ -307,13 +307,10 @@ def _whiten_scratch(dev, C):
     return ent
 
 
-_STATS_SIDE = os.environ.get("S2T_WHITEN_STREAM", "1") == "1"
-
-
 def _stats_stream():
     """Side-stream handle for forward-pass statistics, ordered after the work enqueued so far on
     the current stream; None when disabled (then the statistics run on the current stream)."""
-    if not (_STATS_SIDE and _Side.enabled):
+    if not _Side.enabled:
         return None
     if _Side.handle is None:
         h = N.lib().s2t_side_stream()
@@ -380,7 +377,7 @@ class WhitenStats:
         # depend on x only -- taken now, on the statistics' stream
         self.pieces = None
         self.pg = None
-        ent = planes.adhoc_entry(C, C, 1, dev) if (_WHITEN_X3P == 2 and X3P["on"] and _tn_ok(xf) and C % 8 == 0
+        ent = planes.adhoc_entry(C, C, 1, dev) if (_WHITEN_X3P == 2 and _tn_ok(xf) and C % 8 == 0
                                                     and cg <= 1024 and n >= 4
                                                     and n * max(C, xf.stride(0)) * 4 < 0x7FFFFF00) else None
         if ent is not None:
@@ -431,18 +428,18 @@ class WhitenStats:
 # (round 6: 2 = dcov and its pieces taken in forward on the statistics' stream, backward = the penalty
 # product on the pre-split-weight kernel with the two norms in its epilogue + the combining pass; 0 = the
 # three-launch form on the NN kernel -- also what shapes outside the pre-split kernel's rules take)
-_WHITEN_X3P = int(os.environ.get("S2T_WHITEN_X3P", "2"))
+_WHITEN_X3P = 2
 # the norms of (g, x dcov) taken in the product's epilogue (s2t_gemm_f32_sq) instead of by a pass over both
-_WHITEN_SQ = os.environ.get("S2T_WHITEN_SQ", "1") == "1"
+_WHITEN_SQ = True
 # the penalty product x dcov itself in forward, on the statistics' stream (late round 6; parity-tested).  OFF:
 # measured 33.49 / 33.46 / 33.12 against 32.78 / 32.79 / 32.63 ms per step with the product in backward -- a
 # GEMM with a 48-64 KB / 130-200 register footprint on the side stream costs forward's own GEMMs more than
 # the 25 us per firing Whiten it takes off backward's chain
-_WHITEN_FWD_PG = os.environ.get("S2T_WHITEN_FWD_PG", "0") == "1"
+_WHITEN_FWD_PG = False
 
 
-_WHITEN_PG_CLS = int(os.environ.get("S2T_WHITEN_PG_CLS", "3"))   # class of the penalty product, three-launch form (csrc/zip_layer.hip whiten_bwd)
-_WHITEN_PG2_CLS = int(os.environ.get("S2T_WHITEN_PG_CLS", "1"))  # ... on the pre-split-weight kernel (round-6 form): data gradient
+_WHITEN_PG_CLS = 3    # class of the penalty product, three-launch form (csrc/zip_layer.hip whiten_bwd): statistics
+_WHITEN_PG2_CLS = 1   # ... on the pre-split-weight kernel (round-6 form): data gradient
 
 
 def whiten_backward(x, g, stats, limit, grad_scale):
@@ -582,9 +579,6 @@ def zipconv_forward(u, gate_off, m8, chunk, K, wc, bc, wk, bk, scale, act=None):
     return y
 
 
-_CONV_W_SIDE = os.environ.get("S2T_CONV_W_SIDE", "1") == "1"
-
-
 def zipconv_backward(u, gate_off, m8, chunk, K, wc, wk, bk, scale, dy, grads, side=True):
     """-> du (T,B,2C | C).  grads = (dwc, dbc, dwk, dbk, dscale) tensors the kernels ACCUMULATE the
     parameter gradients into (None where the parameter is absent).  side: the parameter-gradient
@@ -601,7 +595,7 @@ def zipconv_backward(u, gate_off, m8, chunk, K, wc, wk, bk, scale, dy, grads, si
     dwc, dbc, dwk, dbk, dsc = grads
     # the tap / bias / edge-scale gradients only feed the optimizer: side stream, as the weight-
     # gradient GEMMs (operands kept alive until the join)
-    wst = _side_launch_stream(u, dy, ws, m8, wc, wk, bk, scale) if (_CONV_W_SIDE and side) else None
+    wst = _side_launch_stream(u, dy, ws, m8, wc, wk, bk, scale) if side else None
     L = N.lib()
     gptr = (N.raw(dwc) if dwc is not None else None, N.raw(dbc) if dbc is not None else None,
             N.raw(dwk), N.raw(dbk) if dbk is not None else None,
@@ -1179,7 +1173,7 @@ class _Side:
     """Weight-gradient GEMMs of backward run on the library's side stream (streams.hip): they
     only feed the optimizer, so they overlap the data-gradient chain.  Operands are kept alive
     until the join, which autograd runs as an end-of-backward callback."""
-    enabled = os.environ.get("S2T_WGRAD_STREAM", "1") == "1"
+    enabled = True       # False once the library cannot give a side stream: everything on the current stream
     handle = None
     keep = []
     queued = False
@@ -1232,16 +1226,9 @@ def _side_launch_stream(*tensors):
 
 
 _EXT = {}
-_WGRAD_SIDE = os.environ.get("S2T_WGRAD_SIDE_MORE", "1") == "1"
 
 
-# which of the FRONTEND's parameter gradients fork to the side stream (bits: 1 = the 7x7 depthwise,
-# 2 = the 3x3 convs' implicit-im2col products, 4 = the 600 k-row Linears and the output Linear).  Its backward is a run of
-# HBM-bound passes over 300-900 MB maps: two of them at once share the same bandwidth.
-_FRONT_SIDE = int(os.environ.get("S2T_FRONT_W_SIDE", "7"))
-
-
-def side_param_grads(params, compute, keep=(), allow=True):
+def side_param_grads(params, compute, keep=()):
     """Parameter gradients that only feed the optimizer, off the data-gradient chain: when every
     parameter of `params` (None entries allowed) is a leaf whose `.grad` is a flat-store view and a
     backward pass is running, `compute()` -- the launches that produce the gradients, in the
@@ -1249,7 +1236,7 @@ def side_param_grads(params, compute, keep=(), allow=True):
     after the work enqueued so far), its results are added into the `.grad` views there, and a
     list of None is returned for autograd; operands in `keep` stay referenced until the join.
     Otherwise `compute()` runs on the current stream and its tensors are returned."""
-    ok = allow and _WGRAD_SIDE and _Side.enabled
+    ok = _Side.enabled
     if ok:
         for q in params:
             if q is None:
@@ -1309,7 +1296,7 @@ def wgrad_into(wparam, bparam, g2, a2, pro=0, notify=False):
     # gives back -- measured on the conformer step; the grouped per-layer launch below does fork,
     # and so do the few products big enough to matter: the frontend's 600 k-row maps)
     st = None
-    if _WGRAD_SIDE and (_FRONT_SIDE & 4) and 2.0 * g2.shape[0] * g2.shape[1] * a2.shape[1] >= 2.0e10:
+    if 2.0 * g2.shape[0] * g2.shape[1] * a2.shape[1] >= 2.0e10:
         st = _side_launch_stream(g2, a2)
     gemm_tn(g2, a2, wg, bg, pro, stream=st)
     if notify:
@@ -1317,9 +1304,6 @@ def wgrad_into(wparam, bparam, g2, a2, pro=0, notify=False):
         if bparam is not None:
             flat.grad_written(bparam)
     return True
-
-
-_BMM_OWN = os.environ.get("S2T_BMM_OWN", "1") == "1"
 
 
 def batched_matmul(mode, a, b, own_tn=False):
@@ -1343,7 +1327,7 @@ def batched_matmul(mode, a, b, own_tn=False):
     # W^T @ exp(lm): K = S + 1 = 51, one slice, no split) it needs no second pass; its tiles are ADDED
     # to the output, which therefore starts as zeros
     tn_ok = own_tn and mode == 2 and M % 4 == 0 and Nn % 4 == 0
-    if (_BMM_OWN and (mode != 2 or tn_ok) and (mode == 2 or K % 4 == 0) and (mode == 0 or Nn % 4 == 0)
+    if ((mode != 2 or tn_ok) and (mode == 2 or K % 4 == 0) and (mode == 0 or Nn % 4 == 0)
             and min(M, Nn, K) >= 4 and a.is_cuda and a.dtype is torch.float32 and b.dtype is torch.float32
             and a.is_contiguous() and b.is_contiguous() and n > 0):
         out = (torch.zeros if mode == 2 else torch.empty)((n, M, Nn), dtype=torch.float32, device=a.device)
@@ -1451,9 +1435,7 @@ def _rows(t):
 
 
 _ACTK = {None: 0, "swoosh_l": 1, "swoosh_r": 2, "add": 3}
-X3P = {"on": os.environ.get("S2T_X3P", "1") == "1", "calls": 0, "tile": 0,
-       "tune": os.environ.get("S2T_X3P_TUNE", "1") == "1",
-       "margin": float(os.environ.get("S2T_X3P_MARGIN", "0.97"))}
+X3P = {"calls": 0, "tile": 0, "margin": 0.97}
 
 
 def _vp(t):
@@ -1527,12 +1509,12 @@ _PLANS = {}          # shape bucket + epilogue -> ("lt", 0) | ("x3p", tile)
 _BASE = {}           # shape bucket -> (library ms, best own ms | None, its tile): timed once, on the plain product
 # tile / occupancy candidates timed per shape bucket: 100 w + tile = the register-staged form at w
 # workgroups per CU; 2000 + tile = the LDS-DMA form (weight pieces global -> LDS directly) at 3 / 4 /
-# 4 workgroups per CU (S2T_X3P_DMA=1 adds them: same-box A/B at C3 38.6 ms/step with and without)
-_X3P_TILES = (222, 321, 312, 411) + ((2022, 2021, 2012) if os.environ.get("S2T_X3P_DMA", "0") == "1" else ())
+# 4 workgroups per CU (not timed under the six-product arithmetic: same-box A/B at C3 38.6 ms/step
+# with and without)
+_X3P_TILES = (222, 321, 312, 411)
 # two-piece arithmetic (S2T_GEMM_ARITH=2): the same tiles of the register-staged form, the LDS-DMA form
 # at 16-deep stages (2000 +) and at 32-deep barrier intervals (2200 +)
-_X3P_TILES2 = tuple(int(t) for t in os.environ.get(
-    "S2T_X3P_TILES2", "222,321,312,411,2022,2021,2012,2222,2221,2212,2211").split(","))
+_X3P_TILES2 = (222, 321, 312, 411, 2022, 2021, 2012, 2222, 2221, 2212, 2211)
 PLAN_STATS = {"timed": 0}
 
 
@@ -1600,9 +1582,6 @@ def _time_call(fn, reps=4, groups=2):
     return best
 
 
-_BAL_EPI = os.environ.get("S2T_BAL_EPI", "1") == "1"
-
-
 def lt_matmul(mode, x2, w2, bias=None, resid2=None, act_src=None, act_kind=None, act2=None,
               resid_b=None, bal=None):
     """Forward / data-gradient product of a Linear with its elementwise neighbours:
@@ -1620,8 +1599,6 @@ def lt_matmul(mode, x2, w2, bias=None, resid2=None, act_src=None, act_kind=None,
     # (s2t_gemm_x3p_bal), or the two-pass s2t_balancer_bwd after the library product
     assert bal is None or (act_src is not None and bias is None and resid2 is None and act2 is None
                            and resid_b is None)
-    if bal is not None and not _BAL_EPI:           # (A/B switch: the separate two-pass update)
-        return balancer_backward(act_src, lt_matmul(mode, x2, w2), *bal, swoosh_l=(act_kind == "swoosh_l"))
 
     def lib():
         if bal is not None:
@@ -1640,7 +1617,7 @@ def lt_matmul(mode, x2, w2, bias=None, resid2=None, act_src=None, act_kind=None,
             return y, swoosh_forward(y, act2 == "swoosh_l")
         return y
 
-    pp = planes.pieces(w2, mode) if (X3P["on"] and x2.shape[0]) else None
+    pp = planes.pieces(w2, mode) if x2.shape[0] else None
     if pp is None:
         return lib()
     arith = N.lib().s2t_gemm_arith_of(mode)   # (read per call, per class of product: the buckets of the two arithmetics are apart)
@@ -1657,20 +1634,17 @@ def lt_matmul(mode, x2, w2, bias=None, resid2=None, act_src=None, act_kind=None,
         # separate passes of the library path would move.
         b = _BASE.get(base)
         if b is None:
-            if not X3P["tune"]:
-                b = (float("inf"), 0.0, 0)
-            else:
-                torch.cuda.synchronize()       # side streams idle: candidates are compared alone
-                t_lib = _time_call(lambda: _lt_matmul_lib(mode, x2, w2, bias, resid2))
-                t_own, tile = None, 0
-                for t in (_X3P_TILES2 if arith == 2 else _X3P_TILES):
-                    if x3p_matmul(mode, x2, w2, bias, resid2, tile=t) is None:
-                        break
-                    ms = _time_call(lambda: x3p_matmul(mode, x2, w2, bias, resid2, tile=t))
-                    if t_own is None or ms < t_own:
-                        t_own, tile = ms, t
-                b = (t_lib, t_own, tile)
-                PLAN_STATS["timed"] += 1
+            torch.cuda.synchronize()       # side streams idle: candidates are compared alone
+            t_lib = _time_call(lambda: _lt_matmul_lib(mode, x2, w2, bias, resid2))
+            t_own, tile = None, 0
+            for t in (_X3P_TILES2 if arith == 2 else _X3P_TILES):
+                if x3p_matmul(mode, x2, w2, bias, resid2, tile=t) is None:
+                    break
+                ms = _time_call(lambda: x3p_matmul(mode, x2, w2, bias, resid2, tile=t))
+                if t_own is None or ms < t_own:
+                    t_own, tile = ms, t
+            b = (t_lib, t_own, tile)
+            PLAN_STATS["timed"] += 1
             _BASE[base] = b
             # the native layer executor (csrc/zip_layer.hip) decides from the same numbers
             N.lib().s2t_zl_plan_put(base[0], base[1], base[2], base[3], float(b[0]),
@@ -1893,7 +1867,7 @@ class _LinearColPerm(torch.autograd.Function):
         def compute():
             dwp, db = linear_wgrad(g2, x2, bias is not None)
             return [dwp.view(-1, f, c).permute(0, 2, 1).reshape(weight.shape), db]
-        dw, db = side_param_grads((weight, bias), compute, keep=(g2, x2), allow=bool(_FRONT_SIDE & 4))
+        dw, db = side_param_grads((weight, bias), compute, keep=(g2, x2))
         return dx, dw, db, None, None
 
 
@@ -1956,9 +1930,6 @@ def _implicit_ok(x, Cout, sh=1, sw=1):
     return x.is_cuda and C % 4 == 0 and Cout % 4 == 0 and x.numel() < (1 << 31) and rows >= 4
 
 
-_CONV_MAP_FWD = os.environ.get("S2T_CONV_MAP_FWD", "1") == "1"
-
-
 class _Conv3x3Nhwc(torch.autograd.Function):
     """3x3 conv on channel-last (N,H,W,Cin) as an implicit-im2col GEMM: each patch row is 3
     contiguous runs of 3*Cin floats of x, which the MFMA kernel's operand loader addresses in
@@ -1977,7 +1948,7 @@ class _Conv3x3Nhwc(torch.autograd.Function):
         w2 = weight.permute(0, 2, 3, 1).reshape(Cout, 9 * C)                    # cout x (kh,kw,cin)
         ctx.implicit = _implicit_ok(x, Cout, sh, sw)
         pp = None
-        if ctx.implicit and _CONV_MAP_FWD and C % 16 == 0 and Cout % 16 == 0:
+        if ctx.implicit and C % 16 == 0 and Cout % 16 == 0:
             # forward on the pre-split bf16x3 GEMM with implicit operands (s2t_gemm_x3p_map: 150 TFLOP/s
             # on the conformer's 256 -> 256 product where the NT kernel below reaches ~ 90)
             pp = planes.adhoc_pieces(w2.detach().contiguous(), 0)
@@ -2014,13 +1985,12 @@ class _Conv3x3Nhwc(torch.autograd.Function):
         g = g if g.is_contiguous() else g.contiguous()
         if ctx.implicit:
             dweight, db = side_param_grads(
-                ctx.params, lambda: list(_conv3x3_wgrad_implicit(xc, g, sh, sw, has_bias)), keep=(xc, g),
-                allow=bool(_FRONT_SIDE & 2))
+                ctx.params, lambda: list(_conv3x3_wgrad_implicit(xc, g, sh, sw, has_bias)), keep=(xc, g))
         else:
             dwmat, db = linear_wgrad(g, xc, has_bias)                            # (Cout, 9C)
             dweight = dwmat.view(Cout, 3, 3, C).permute(0, 3, 1, 2)
         dx = None
-        if ctx.needs_input_grad[0] and ctx.implicit and _CONV_MAP_DGRAD and (sh, sw) == (1, 2) and Cout % 16 == 0 \
+        if ctx.needs_input_grad[0] and ctx.implicit and (sh, sw) == (1, 2) and Cout % 16 == 0 \
                 and C >= 16 and g.numel() * 5 < (1 << 31):
             dx = _conv3x3_s12_dgrad_map(g.view(B, Ho, Wo, Cout), weight.detach(), H, W)
         elif ctx.needs_input_grad[0] and ctx.implicit and 9 * C * Cout >= (1 << 18):
@@ -2044,8 +2014,7 @@ class _Conv3x3Nhwc(torch.autograd.Function):
         return dx, dweight, db, None, None
 
 
-_CONV_MAP_DGRAD = os.environ.get("S2T_CONV_MAP_DGRAD", "1") == "1"
-_CONV_MAP_DGRAD_TILE = int(os.environ.get("S2T_CONV_MAP_DGRAD_TILE", "221"))    # (128 x 64 block, 32-deep intervals)
+_CONV_MAP_DGRAD_TILE = 221    # (128 x 64 block, 32-deep intervals)
 
 
 _PAD_BUF = {}
@@ -2094,7 +2063,7 @@ class RowMap(ctypes.Structure):
                 ("sw", ctypes.c_long), ("base", ctypes.c_long)]
 
 
-_CONV_MAP_TILE = int(os.environ.get("S2T_CONV_MAP_TILE", "22"))
+_CONV_MAP_TILE = 22
 
 
 def _x3p_map(a, amap, seg, segoff, pp, ncols, out, ldc, cmap, c_elems, M, bias, tile=None):
@@ -2148,8 +2117,7 @@ class _Conv3x3S2Map(torch.autograd.Function):
         g = dy.contiguous().float()
         has_bias = ctx.params[1] is not None
         dweight, db = side_param_grads(
-            ctx.params, lambda: list(_conv3x3_wgrad_implicit(x, g.view(-1, Cout), 2, 2, has_bias)), keep=(x, g),
-            allow=bool(_FRONT_SIDE & 2))
+            ctx.params, lambda: list(_conv3x3_wgrad_implicit(x, g.view(-1, Cout), 2, 2, has_bias)), keep=(x, g))
         dx = None
         if ctx.needs_input_grad[0]:
             gp = F.pad(g, (0, 0, 1, 1, 1, 1))                                  # zero border: every tap in range
@@ -2348,7 +2316,7 @@ class _DwConv2dNhwc(torch.autograd.Function):
             N.check(L.s2t_dwconv2d_nhwc_fwd(N.fp(dy), N.fp(w), None, Nn, H, W, C, KH, KW, 1,
                                             N.fp(dx), N.stream()), "s2t_dwconv2d_nhwc_bwd_data")
         dw, db = side_param_grads(ctx.params, lambda: _dwconv_wgrad(x, dy, w, ctx.has_bias, ctx.wshape),
-                                  keep=(x, dy), allow=bool(_FRONT_SIDE & 1))
+                                  keep=(x, dy))
         return dx, dw, db
 
 
@@ -2386,7 +2354,7 @@ class _DwConv2dTap(torch.autograd.Function):
             N.check(L.s2t_dwconv2d_nhwc_fwd_add(N.fp(dy), N.fp(w), None, N.fp(gp), Nn, H, W, C, KH, KW,
                                                 1, N.fp(dx), N.stream()), "s2t_dwconv2d_nhwc_bwd_data")
         dw, db = side_param_grads(ctx.params, lambda: _dwconv_wgrad(x, dy, w, ctx.has_bias, ctx.wshape),
-                                  keep=(x, dy), allow=bool(_FRONT_SIDE & 1))
+                                  keep=(x, dy))
         return dx, dw, db
 
 

@@ -70,12 +70,9 @@ def _static_ok(layer):
         ok = (all(d % 4 == 0 for d in dims) and dv1 <= 16 and dv2 <= 16 and dv1 + dv2 <= 32
               and sa.dropout == 0.0 and layer.norm.channel_dim in (-1, 2))
         layer.__dict__["_zl_static"] = ok
-        if ok and _PIN_ATTRS:
+        if ok:
             _pin_attrs(layer)
     return ok
-
-
-_PIN_ATTRS = os.environ.get("S2T_PIN_ATTRS", "1") == "1"
 
 
 def _pin_attrs(root):
@@ -134,8 +131,7 @@ def _mask8(m):
 def _pen_ok(sa, T):
     """The score-limit flag comes from the MFMA attention kernel only (zip_attn.hip)."""
     H, qd, pd = sa.num_heads, sa.query_head_dim, sa.pos_head_dim
-    return (T <= 512 and pd <= 4 and qd % 8 == 0 and (H * (2 * qd + pd)) % 4 == 0
-            and "S2T_ATTN_FWD_OLD" not in os.environ)
+    return T <= 512 and pd <= 4 and qd % 8 == 0 and (H * (2 * qd + pd)) % 4 == 0
 
 
 def run(layer, src, pos_emb, chunk_size, attn_mask=None, key_padding_mask=None, feature_mask=None):

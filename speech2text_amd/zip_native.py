@@ -20,7 +20,6 @@ from . import planes
 from . import zip_kernels as zk
 
 ENABLED = os.environ.get("S2T_LAYER_NATIVE", "1") == "1"
-_BAL_FWD_SIDE = os.environ.get("S2T_BAL_FWD_SIDE", "1") == "1"   # Balancer column statistics in forward, side stream
 CALLS = [0, 0]           # forward / backward calls served natively (tests assert the path really ran)
 _F32 = torch.float32
 NDEC, NWHITEN = 32, 11
@@ -293,7 +292,7 @@ def _side_handle():
 
 def usable(layer, T, B):
     """Can the native executor serve this layer call?  (zip_layer.eligible has passed already.)"""
-    if not ENABLED or "S2T_ATTN_FWD_OLD" in os.environ:
+    if not ENABLED:
         return None
     # a profile of an entry point whose launches are only seen from the Python call sites ("*", or any
     # single entry that is not sampled inside the library) needs the Python executor
@@ -343,17 +342,17 @@ def _fill_call(L, T, B, D, chunk_size, x0, pos2, a8, k8, fm, dec, dev):
     c.nwh = len(cs)
     ws = zk._lt_workspace(dev)
     c.lt_ws, c.lt_ws_bytes = ws.data_ptr(), ws.numel()
-    c.x3p_on, c.x3p_tile, c.x3p_margin = int(zk.X3P["on"]), int(zk.X3P["tile"]), float(zk.X3P["margin"])
+    c.x3p_on, c.x3p_tile, c.x3p_margin = 1, int(zk.X3P["tile"]), float(zk.X3P["margin"])
     c.whiten_x3p = int(zk._WHITEN_X3P)
     side = zk._Side.enabled
-    c.conv_w_side = int(zk._CONV_W_SIDE and side)
+    c.conv_w_side = int(side)
     c.conv_fused = 0                      # (the one-kernel conv backward: removed in round 5)
-    c.stats_side = int(zk._STATS_SIDE and side)
+    c.stats_side = int(side)
     c.wgrad_side = int(side)
-    c.bmm_own = int(zk._BMM_OWN)
-    c.bal_epi = int(zk._BAL_EPI)
+    c.bmm_own = 1
+    c.bal_epi = 1
     c.whiten_sq = int(zk._WHITEN_SQ)
-    c.bal_fwd_side = int(_BAL_FWD_SIDE and side)
+    c.bal_fwd_side = int(side)       # Balancer column statistics in forward, side stream
     c.whiten_fwd_pg = int(zk._WHITEN_FWD_PG)
     return c
 

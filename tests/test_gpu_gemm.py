@@ -317,7 +317,7 @@ def test_tn_wave_specialised_form(dev, R, Nf, Mf, pro):
         assert L.s2t_tn_w(0) == 0
         dW2, db2 = run()
     finally:
-        L.s2t_tn_w(2)               # back to automatic (S2T_TN_W, or by the weight gradients' arithmetic)
+        L.s2t_tn_w(2)               # back to automatic (by the weight gradients' arithmetic)
     scale = ref.abs().max().item()
     for a, c in ((dW, db), (dW2, db2)):
         assert (a - ref).abs().max().item() / scale < _b(2e-6)

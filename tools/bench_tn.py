@@ -1,11 +1,12 @@
-"""GPU: the TN (weight-gradient) mode of s2t_gemm_f32 on the C3 shapes; tile / slice count come
-from S2T_TN_TILE / S2T_TN_BLOCKS (read once per process), so sweep them from the shell."""
+"""GPU: the TN (weight-gradient) mode of s2t_gemm_f32 on the C3 shapes; TN_W=0 | 1 forces the
+all-waves / the wave-specialised form through s2t_tn_w (tile and slice count follow the shape)."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+from speech2text_amd import _native as N  # noqa: E402
 from tools.bench_gemm import dev, gemm, timeit  # noqa: E402
 
 if os.environ.get("TN_SHAPES") == "sym":      # Whiten statistics: x^T x
@@ -16,8 +17,7 @@ else:
 SHAPES = SHAPES_ or [(31680, 192, 384), (31680, 192, 640), (31680, 512, 192), (31680, 192, 272),
           (31680, 192, 48), (15872, 256, 768), (15872, 960, 256), (15872, 256, 272),
           (7936, 256, 768), (3968, 768, 256)]
-tag = (f"W={os.environ.get('S2T_TN_W', '1')} tile={os.environ.get('S2T_TN_TILE', 'auto')} "
-       f"blocks={os.environ.get('S2T_TN_W_BLOCKS', os.environ.get('S2T_TN_BLOCKS', 'auto'))}")
+tag = f"W={N.lib().s2t_tn_w(int(os.environ.get('TN_W', '-1')))}"
 out = []
 tot = 0.0
 for (M, K, Nn) in SHAPES:

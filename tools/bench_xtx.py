@@ -1,4 +1,4 @@
-"""s2t_gemm_xtx (Whiten covariance) at the C3 shapes; S2T_TN_BLOCKS picks the slice count."""
+"""s2t_gemm_xtx (Whiten covariance) at the C3 shapes."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -5,7 +5,6 @@ import os
 import random
 import sys
 
-os.environ["S2T_WGRAD_STREAM"] = "0"
 import numpy as np
 import torch
 
@@ -13,6 +12,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import bench  # noqa: E402
 from speech2text_amd import _native as N  # noqa: E402
 from speech2text_amd import zip_kernels as zk  # noqa: E402
+
+zk._Side.enabled = False      # side stream off
 from speech2text_amd.build_task import TaskFactory  # noqa: E402
 from speech2text_amd.trainer import Trainer  # noqa: E402
 

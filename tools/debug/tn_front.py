@@ -1,5 +1,5 @@
 """GPU: the frontend's weight-gradient products (contraction over 601 920 / 31 680 rows) on the TN forms;
-run once per setting of S2T_TN_W / S2T_TN_BLOCKS / S2T_TN_TILE (read once per process)."""
+the form follows the arithmetic (s2t_tn_w forces it)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

@@ -25,7 +25,6 @@ for t in (22, 23, 21):
     for _ in range(iters):
         N.check(L.s2t_gemm_f32_tiled(0, N.fp(x), K, N.fp(W.detach()), K, N.fp(out), Nn, M, Nn, K, N.fp(b.detach()),
                                      None, 0, t, N.stream()), "tiled")
-os.environ["S2T_LT_OWN"] = "0"
 for _ in range(iters):
     zk._lt_matmul_lib(0, x, W.detach(), b.detach(), None)
 torch.cuda.synchronize()
