@@ -459,6 +459,29 @@ int s2t_rnnt_greedy_stateless(const float* am, const long* lengths, const float*
                               int D, int ctx, int act, int max_token_step, int max_out, int blank,
                               long* tokens, long* out_len, void* stream);
 
+/* ---- RNN-T beam search (model/decoding.py:295-425 RnntBeamDecoding), stateless predictor and a
+ * joiner without output projection; inputs as s2t_rnnt_greedy_stateless.  One launch per batch,
+ * one workgroup per utterance.  Per frame t < lengths[b] and live beam: lp = log_softmax(act(am[b,t]
+ * + lm[beam])); the cutoff_top_k best classes by (value descending, class ascending; a
+ * cutoff_top_k above V behaves as V) give one candidate each -- blank keeps the beam's tokens and
+ * predictor state, any other class appends it (at most one symbol per frame per beam) -- with
+ * score = beam score + lp in fp32; the beam_size best candidates by (score descending, parent beam
+ * position ascending, rank in the parent's top-k ascending) are kept, equal hypotheses are not
+ * merged.  Outputs are the best beam's after the last frame: tokens [B][T] and frames [B][T]
+ * (the frame at which each token was emitted), first out_len[b] valid; score [B].  A zero-length
+ * utterance gives no tokens and score 0.  workspace: s2t_rnnt_beam_workspace_bytes(B, T, V,
+ * beam_size) bytes of device memory (a pure host function), 256-byte aligned: the (parent, class)
+ * records the best beam is traced back through, and the beams' lm rows when they do not fit the
+ * LDS.  Returns -1 for shapes the fused search does not take: beam_size or min(cutoff_top_k, V)
+ * outside 1..16, V > 8192, ctx > 64, or 16 (E + D) + 128 ctx bytes above 60 KiB. */
+long s2t_rnnt_beam_workspace_bytes(int B, int T, int V, int beam_size);
+int s2t_rnnt_beam_stateless(const float* am, const long* lengths, const float* emb,
+                            const float* conv_w, const float* lin_w, const float* lin_b,
+                            const float* pre_w, const float* pre_b, int B, int T, int V, int E,
+                            int D, int ctx, int act, int blank, int beam_size, int cutoff_top_k,
+                            void* workspace, long* tokens, long* frames, long* out_len,
+                            float* score, void* stream);
+
 /* ---- batched on-device augmentation + collate next to the fbank kernel
  * (dataset/frontend/data_augmentation.py:13-56 AddNoise, :59-118 MixFeats, :150-196 SpecAugment;
  * dataset/utils.py:182-202 batch()).  Random decisions are made on the host as the reference

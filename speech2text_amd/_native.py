@@ -105,7 +105,7 @@ class _LibProxy:
 
     def __getattr__(self, name):
         raw = getattr(self._cdll, name)
-        if _Prof.target is None or name.endswith("_floats") or name.endswith("_elems") \
+        if _Prof.target is None or name.endswith(("_floats", "_elems", "_bytes")) \
                 or name in _NO_LAUNCH or (_Prof.target != "*" and _Prof.target != name) \
                 or (_Prof.target != "*" and name in KERNEL_TIMED):    # (sampled inside the library)
             fn = raw          # (a single-entry profile leaves every other entry point unwrapped)

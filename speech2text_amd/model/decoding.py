@@ -1,14 +1,18 @@
-"""Validation-time greedy decoding (mirror of the reference's model/decoding.py:19-82,
-157-177, 196-271): DecodingMethod / batch_search / reference_decoder / CtcGreedyDecoding /
-RnntGreedyDecoding with the same constructor arguments and `decode(hidden_states[1,T,D]) -> str`.
+"""Validation-time decoding (mirror of the reference's model/decoding.py:19-82, 157-177,
+196-271, 295-435): DecodingMethod / batch_search / reference_decoder / CtcGreedyDecoding /
+RnntGreedyDecoding / RnntBeamDecoding / DecodingFactory with the same constructor arguments and
+`decode(hidden_states[1,T,D]) -> str`.
 
 The reference decodes one utterance at a time with Python loops over frames (and, for RNN-T,
-predictor / joiner module calls per lattice move).  Here `batch_search` hands the WHOLE batch to
-one HIP launch (csrc/decode.hip): per-frame argmax + repeat/blank collapse for CTC; for RNN-T
-with the stateless predictor and a projection-free joiner the whole lattice walk runs on the
-device, one workgroup per utterance.  Other predictor / joiner combinations keep the
-module-by-module loop.  Beam / lexicon decoders are out of scope."""
+predictor / joiner module calls per lattice move, per beam for the beam search).  Here
+`batch_search` hands the WHOLE batch to one HIP launch: per-frame argmax + repeat/blank collapse
+for CTC (csrc/decode.hip); for RNN-T with the stateless predictor and a projection-free joiner the
+whole greedy lattice walk (csrc/decode.hip) and the whole beam search (csrc/decode_beam.hip) run
+on the device, one workgroup per utterance.  Other predictor / joiner combinations keep the
+module-by-module loop.  The lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder
+are not here."""
 import abc
+from enum import Enum, unique
 from typing import List
 
 import torch
@@ -146,3 +150,135 @@ class RnntGreedyDecoding(DecodingMethod):
                 pred_out, pred_state = self._predictor.streaming_step(cur, pred_state)
                 out.append(tok)
         return self._tokenizer.decode(torch.tensor(out, dtype=torch.int64))
+
+
+def rnnt_beam_tokens_from_am(am, lengths, predictor, joiner, beam_size=4, cutoff_top_k=4):
+    """Fused device beam search on a given am = joiner._enc_proj(encoder_out), (B,T,V) fp32.
+    -> (tokens (B,T) int64, frames (B,T) int64, out_len (B) int64, score (B) fp32): the best
+    beam's tokens, the frame at which each was emitted, their count and the beam's score.
+    Returns None when the kernel does not take the shape (rc -1: the caller runs the module
+    loop).  HIP: decode_beam.hip."""
+    if not am.is_cuda:
+        raise RuntimeError("the fused RNN-T beam search runs on the GPU only")
+    p = getattr(predictor, "predictor", predictor)
+    am = am.contiguous().float()
+    B, T, V = am.shape
+    dev = am.device
+    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+    tokens = torch.zeros((B, T), dtype=torch.int64, device=dev)
+    frames = torch.zeros((B, T), dtype=torch.int64, device=dev)
+    out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
+    score = torch.zeros((B,), dtype=torch.float32, device=dev)
+    if B == 0 or T == 0:
+        return tokens, frames, out_len, score
+    ws = torch.empty((max(1, N.lib().s2t_rnnt_beam_workspace_bytes(B, T, V, int(beam_size))),),
+                     dtype=torch.uint8, device=dev)
+    conv_w = p._conv.weight.reshape(p._embedding_dim, p._context_size).contiguous()
+    rc = N.lib().s2t_rnnt_beam_stateless(
+        N.fp(am), N.lp(lengths), N.fp(p._embedding.weight.contiguous()), N.fp(conv_w),
+        N.fp(p._output_linear.weight.contiguous()), N.fp(p._output_linear.bias.contiguous()),
+        N.fp(joiner._pre_proj.weight.contiguous()), N.fp(joiner._pre_proj.bias.contiguous()),
+        B, T, V, p._embedding_dim, p._output_dim, p._context_size,
+        0 if joiner._act_name == "relu" else 1, 0, int(beam_size), int(cutoff_top_k),
+        N.ptr(ws), N.lp(tokens), N.lp(frames), N.lp(out_len), N.fp(score), N.stream())
+    if rc == -1:
+        return None
+    N.check(rc, "s2t_rnnt_beam_stateless")
+    return tokens, frames, out_len, score
+
+
+class RnntBeamDecoding(DecodingMethod):
+    """Beam search of the RNN-T (reference :295-425): at most one symbol per frame per beam, the
+    `cutoff_top_k` best classes of every beam are expanded, the `beam_size` best candidates
+    survive, equal hypotheses are not merged.  The orders the reference leaves to its library are
+    fixed: top-k by (log-probability descending, class ascending), candidates by (score
+    descending, parent beam position ascending, rank in the parent's top-k ascending)."""
+
+    def __init__(self, tokenizer, predictor, joiner, beam_size=4, cutoff_top_k=4) -> None:
+        self._tokenizer = tokenizer
+        self._predictor = predictor
+        self._joiner = joiner
+        self._beam_size = beam_size
+        self._cutoff_top_k = cutoff_top_k
+        assert hasattr(self._predictor, "streaming_step") and hasattr(self._joiner, "streaming_step"), \
+            "Predictor and Joiner should impl streaming_step for decoding."
+
+    def _fusable(self):
+        from speech2text_amd.model.joiner.joiner import Joiner
+        from speech2text_amd.model.predictor.predictor import StatelessPredictor
+        p = getattr(self._predictor, "predictor", self._predictor)
+        return isinstance(p, StatelessPredictor) and isinstance(self._joiner, Joiner) \
+            and not self._joiner._use_out_project
+
+    def _module_loop(self, hidden_states):
+        """(1,T,D) -> (tokens, frames, score) of the best beam: the reference's loop (:350-425)
+        against init_state / streaming_step only, in plain torch on whatever device the inputs
+        live.  Scores are accumulated in fp32 on that device (beam score + log-probability)."""
+        dev = hidden_states.device
+        blk = torch.zeros((1, 1), dtype=torch.int64, device=dev)
+        pred_out, pred_state = self._predictor.streaming_step(blk, self._predictor.init_state())
+        beams = [((), (), pred_state, pred_out)]            # (tokens, frames, state, pred_out)
+        scores = torch.zeros((1,), dtype=torch.float32, device=dev)
+        for t in range(hidden_states.shape[1]):
+            log_probs = self._joiner.streaming_step(hidden_states[:, t:t + 1, :],
+                                                    torch.cat([b[3] for b in beams], dim=0)).float()
+            k = min(int(self._cutoff_top_k), log_probs.shape[-1])
+            vals, cls = torch.sort(log_probs, dim=-1, descending=True, stable=True)
+            cand = (scores.unsqueeze(1) + vals[:, :k]).flatten()      # index = parent * k + rank
+            scores, pick = torch.sort(cand, descending=True, stable=True)
+            scores, pick = scores[:self._beam_size], pick[:self._beam_size]
+            new_beams = []
+            for q, c in zip(pick.tolist(), cls[:, :k].flatten()[pick].tolist()):
+                tokens, frames, state, out = beams[q // k]
+                if c != 0:
+                    out, state = self._predictor.streaming_step(
+                        torch.full((1, 1), c, dtype=torch.int64, device=dev), state)
+                    tokens, frames = tokens + (c,), frames + (t,)
+                new_beams.append((tokens, frames, state, out))
+            beams = new_beams
+        return list(beams[0][0]), list(beams[0][1]), float(scores[0])
+
+    @torch.no_grad()
+    def beam_tokens(self, hidden_states, inputs_length, fused=True):
+        """(B,T,D) encoder output -> (tokens (B,T), frames (B,T), out_len (B), score (B)) of the
+        best beam per utterance.  The fused device search where the modules allow it (and `fused`
+        is left on), else the module loop per utterance."""
+        if fused and self._fusable() and hidden_states.is_cuda:
+            am = self._joiner._enc_proj(hidden_states)                # (B,T,V), one GEMM
+            out = rnnt_beam_tokens_from_am(am, inputs_length, self._predictor, self._joiner,
+                                           self._beam_size, self._cutoff_top_k)
+            if out is not None:
+                return out
+        B, T = hidden_states.shape[0], hidden_states.shape[1]
+        tokens = torch.zeros((B, T), dtype=torch.int64)
+        frames = torch.zeros((B, T), dtype=torch.int64)
+        out_len = torch.zeros((B,), dtype=torch.int64)
+        score = torch.zeros((B,), dtype=torch.float32)
+        for b in range(B):
+            n = max(0, min(int(inputs_length[b]), T))
+            tok, frm, score[b] = self._module_loop(hidden_states[b:b + 1, :n, :])
+            out_len[b] = len(tok)
+            tokens[b, :len(tok)] = torch.tensor(tok, dtype=torch.int64)
+            frames[b, :len(frm)] = torch.tensor(frm, dtype=torch.int64)
+        dev = hidden_states.device
+        return tokens.to(dev), frames.to(dev), out_len.to(dev), score.to(dev)
+
+    @torch.no_grad()
+    def decode_batch(self, hidden_states, inputs_length):
+        tokens, _, out_len, _ = self.beam_tokens(hidden_states, inputs_length)
+        return _to_texts(tokens, out_len, self._tokenizer)
+
+    @torch.no_grad()
+    def decode(self, hidden_states: torch.Tensor) -> str:
+        assert hidden_states.shape[0] == 1, "Support BatchSize = 1 only."
+        n = torch.tensor([hidden_states.shape[1]], dtype=torch.int64)
+        return self.decode_batch(hidden_states, n)[0]
+
+
+@unique
+class DecodingFactory(Enum):
+    """Decoding methods by the reference's names (:428-435), so that an inference YAML's
+    `decoding.type` / `decoding.config` resolves as there: DecodingFactory[type].value(**config)."""
+    ctc_greedy_decoding = CtcGreedyDecoding
+    rnnt_greedy_decoding = RnntGreedyDecoding
+    rnnt_beam_decoding = RnntBeamDecoding

@@ -5,8 +5,8 @@ from typing import List, Tuple
 
 import torch
 
-from speech2text_amd.model.decoding import (CtcGreedyDecoding, RnntGreedyDecoding, batch_search,
-                                            reference_decoder)
+from speech2text_amd.model.decoding import (CtcGreedyDecoding, RnntBeamDecoding, RnntGreedyDecoding,
+                                            batch_search, reference_decoder)
 
 
 def _levenshtein(a: List, b: List) -> int:
@@ -37,8 +37,13 @@ def word_error_rate(hypotheses: List[str], references: List[str], show_on_screen
 
 @dataclasses.dataclass
 class AsrMetricConfig:
+    """decode_method: "ctc_greedy_search" / "rnnt_greedy_search" as in the reference, and
+    "rnnt_beam_search" (a name of this project: the reference's AsrMetric knows the greedy
+    decoders only), which scores with RnntBeamDecoding(beam_size, cutoff_top_k)."""
     decode_method: str = "ctc_greedy_search"
     max_token_step: int = 5
+    beam_size: int = 4
+    cutoff_top_k: int = 4
 
 
 class AsrMetric(object):
@@ -50,6 +55,10 @@ class AsrMetric(object):
             self._decode_sess = RnntGreedyDecoding(tokenizer=tokenizer, predictor=predictor,
                                                    joiner=joiner,
                                                    max_token_step=config.max_token_step)
+        elif config.decode_method == "rnnt_beam_search":
+            self._decode_sess = RnntBeamDecoding(tokenizer=tokenizer, predictor=predictor,
+                                                 joiner=joiner, beam_size=config.beam_size,
+                                                 cutoff_top_k=config.cutoff_top_k)
         else:
             raise NotImplementedError(config.decode_method)
 

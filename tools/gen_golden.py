@@ -2,7 +2,7 @@
 
 Runs only in the build container (needs /root/reference).  Writes plain arrays
 (inputs, parameters, expected outputs) -- never reference source.  Usage:
-    python tools/gen_golden.py [fbank] [ctc] [bestrq] [zipformer] [losses] ...
+    python tools/gen_golden.py [fbank] [ctc] [bestrq] [zipformer] [losses] [rnnt_beam] ...
 """
 import os
 import sys
@@ -514,6 +514,132 @@ def gen_state_keys():
             out[f"{pre}.{k}"] = list(v.shape)
     json.dump(out, open(os.path.join(OUT, "state_keys_c3.json"), "w"), indent=0, sort_keys=True)
     print("state_keys", len(out))
+
+
+# (V, D, E, ctx, act, scale, enc_scale, Tmax, beam_size, cutoff_top_k, utterances drawn, seed)
+RNNT_BEAM_CONFIGS = [
+    (128, 256, 512, 5, "relu", 4.0, 1.0, 247, 4, 4, 48, 11),     # the C3 YAML's predictor / joiner
+    (40, 48, 32, 5, "relu", 3.0, 1.5, 60, 4, 4, 24, 12),
+    (40, 48, 32, 5, "tanh", 1.0, 1.0, 30, 4, 4, 48, 13),
+    (40, 48, 32, 2, "relu", 3.0, 1.5, 60, 8, 3, 24, 14),
+    (500, 64, 48, 5, "relu", 3.0, 1.5, 60, 16, 8, 24, 15),
+]
+RNNT_BEAM_KEEP = 8
+# arrays kept out of the main file so that every committed file stays below 1 MiB
+RNNT_BEAM_SIDE = {"c0_params": ("c0_emb", "c0_lin_w", "c0_pre_w"), "c0_am": ("c0_am_packed",),
+                  "c4": ("c4_am_packed", "c4_emb", "c4_pre_w", "c4_enc_w", "c4_enc")}
+
+
+def gen_rnnt_beam():
+    """tests/golden/rnnt_beam_ref*.npz: the reference's RnntBeamDecoding (fp32, its own
+    StatelessPredictor / Joiner modules) and the float64 restatement of tests/
+    rnnt_beam_restatement.py on random models.  Kept per configuration: the first 8 utterances on
+    which the reference's fp32 tokens equal the float64 tokens and whose decision margin is at
+    least 16 N, N = the largest |fp32 score - float64 score| of the configuration (the reference's
+    own fp32 noise; 16 = 2 scores x the 4 N the kernel is allowed on each x a safety factor 2)."""
+    import importlib.machinery
+    import types
+    import torch
+    ref_import.install_stubs()
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import rnnt_beam_restatement as R
+    for _ in range(12):                                      # stub whatever third-party wheel is absent
+        try:
+            from model.decoding import RnntBeamDecoding
+            break
+        except ModuleNotFoundError as e:
+            name = e.name
+            assert not os.path.exists(os.path.join("/root/reference", name.split(".")[0])), name
+            m = types.ModuleType(name)
+            m.__spec__ = importlib.machinery.ModuleSpec(name, None)
+            m.__path__ = []
+            m.__getattr__ = lambda attr, _n=name: type(attr, (), {})
+            sys.modules[name] = m
+    from model.joiner.joiner import Joiner, JoinerConfig
+    from model.predictor.stateless_predictor import StatelessPredictor, StatelessPredictorConfig
+
+    class Ids:                                               # tokenizer stand-in: ids pass through
+        def decode(self, t):
+            return t.tolist()
+
+    out = {"n_configs": np.array([len(RNNT_BEAM_CONFIGS)])}
+    for ci, (V, D, E, ctx, act, scale, enc_scale, Tmax, beam, topk, drawn, seed) in \
+            enumerate(RNNT_BEAM_CONFIGS):
+        torch.manual_seed(seed)
+        pred = StatelessPredictor(StatelessPredictorConfig(num_symbols=V, output_dim=D,
+                                                           symbol_embedding_dim=E, context_size=ctx))
+        join = Joiner(JoinerConfig(input_dim=D, output_dim=V, activation=act, prune_range=5,
+                                   use_out_project=False))
+        with torch.no_grad():
+            for p in list(pred.parameters()) + list(join.parameters()):
+                p.mul_(scale)
+            enc = torch.randn(drawn, Tmax, D) * enc_scale
+            lens = torch.randint(1, Tmax + 1, (drawn,))
+            lens[0] = Tmax
+            am = join._enc_proj(enc)                         # one batched fp32 product
+        params = {"emb": pred._embedding.weight, "conv_w": pred._conv.weight.reshape(E, ctx),
+                  "lin_w": pred._output_linear.weight, "lin_b": pred._output_linear.bias,
+                  "pre_w": join._pre_proj.weight, "pre_b": join._pre_proj.bias}
+        params = {k: v.detach().numpy().copy() for k, v in params.items()}
+        sess = RnntBeamDecoding(Ids(), pred, join, beam_size=beam, cutoff_top_k=topk)
+        rows = []
+        for b in range(drawn):
+            n = int(lens[b])
+            with torch.no_grad():
+                ref_tok = sess.decode(enc[b:b + 1, :n])
+            ref_score = float(sess._decoding_state.best_beam.score)
+            tok, score, frames, margin = R.beam_search(am[b, :n].numpy(), params, ctx, act, beam, topk)
+            rows.append((b, ref_tok, ref_score, tok, score, frames, margin))
+        agree = [r for r in rows if r[1] == r[3]]
+        noise = max(abs(r[2] - r[4]) for r in agree)
+        ok = [r for r in agree if r[6] >= 16 * noise]
+        keep = ok[:RNNT_BEAM_KEEP]
+        print(f"rnnt_beam c{ci}: drawn {drawn}, self-consistent {len(agree)}, pass 16N {len(ok)}, "
+              f"N {noise:.2e}, kept lengths {[int(lens[r[0]]) for r in keep]}, "
+              f"tokens {[len(r[3]) for r in keep]}")
+        assert len(keep) == RNNT_BEAM_KEEP, "draw more utterances"
+        assert 0 < sum(len(r[3]) for r in keep) < sum(int(lens[r[0]]) for r in keep), \
+            "kept set needs emitted tokens and blank frames"
+        if ci == 0:
+            assert any(int(lens[r[0]]) >= 200 for r in keep), "need one utterance with T >= 200"
+        idx = [r[0] for r in keep]
+        klens = lens[idx].numpy().astype(np.int64)
+        umax = max(len(r[3]) for r in keep)
+        tokens = np.zeros((RNNT_BEAM_KEEP, umax), dtype=np.int64)
+        frames = np.zeros((RNNT_BEAM_KEEP, umax), dtype=np.int64)
+        for i, r in enumerate(keep):
+            tokens[i, :len(r[3])] = r[3]
+            frames[i, :len(r[5])] = r[5]
+        pre = f"c{ci}_"
+        out[pre + "dims"] = np.array([V, D, E, ctx, 0 if act == "relu" else 1, Tmax, beam, topk],
+                                     dtype=np.int64)
+        out[pre + "scales"] = np.array([scale, enc_scale])
+        for k, v in params.items():
+            out[pre + k] = v
+        out[pre + "am_packed"] = np.concatenate([am[b, :int(lens[b])].numpy() for b in idx])
+        if ci > 0:                                           # (the C3-dims configuration: am only)
+            out[pre + "enc"] = enc[idx].numpy()
+            out[pre + "enc_w"] = join._enc_proj.weight.detach().numpy().copy()
+            out[pre + "enc_b"] = join._enc_proj.bias.detach().numpy().copy()
+        out[pre + "lengths"] = klens
+        out[pre + "tokens"] = tokens                         # the reference class's (= float64) tokens
+        out[pre + "tok_len"] = np.array([len(r[3]) for r in keep], dtype=np.int64)
+        out[pre + "frames"] = frames
+        out[pre + "score_f64"] = np.array([r[4] for r in keep])
+        out[pre + "score_ref_f32"] = np.array([r[2] for r in keep])
+        out[pre + "margin"] = np.array([r[6] for r in keep])
+        out[pre + "N"] = np.array([noise])
+    side = set()
+    for name, keys in RNNT_BEAM_SIDE.items():
+        np.savez_compressed(os.path.join(OUT, f"rnnt_beam_ref_{name}.npz"), **{k: out[k] for k in keys})
+        side.update(keys)
+    np.savez_compressed(os.path.join(OUT, "rnnt_beam_ref.npz"),
+                        **{k: v for k, v in out.items() if k not in side})
+    for f in sorted(os.listdir(OUT)):
+        if f.startswith("rnnt_beam_ref"):
+            size = os.path.getsize(os.path.join(OUT, f))
+            print(f, size)
+            assert size < 1 << 20, f
 
 
 if __name__ == "__main__":
