@@ -11,6 +11,8 @@
 //      scattered to classes in LDS, grad = (softmax - occupancy) * scale  (the product of
 //      CTCLoss' gradient and the log_softmax backward)
 // Logits stay batch-major (B,T,V); no transposed copy is ever made.
+// An utterance with no feasible alignment (nll = +inf) gets an all-zero gradient under either
+// zero_infinity; the flag only decides whether its reported loss is 0 or +inf.
 #include "common.h"
 #include "../../include/s2t_mi355.h"
 

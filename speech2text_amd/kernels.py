@@ -12,6 +12,8 @@ from . import _native as N
 
 _NEG_INF = float("-inf")
 CTC_MAX_LABELS = 1023     # == S2T_CTC_MAX_LABELS (include/s2t_mi355.h)
+RNNT_MAX_ROWS = 1024      # S+1 lattice rows: one thread each in one workgroup (csrc/rnnt.hip mi_*_kernel)
+RNNT_MAX_JOINER_DIM = 1024  # fused pruned joiner: 16 classes per lane of one wave (csrc/rnnt.hip)
 
 
 def _dev_check(*ts):
@@ -152,11 +154,19 @@ def _i64(t, dev):
     return t.to(device=dev, dtype=torch.int64).contiguous()
 
 
+def _check_lattice_rows(S):
+    if S + 1 > RNNT_MAX_ROWS:
+        raise ValueError(f"RNN-T lattice: {S} symbols + 1 rows exceed the kernel's limit of "
+                         f"{RNNT_MAX_ROWS} lattice rows per utterance (one thread per row in one "
+                         "workgroup, csrc/rnnt.hip)")
+
+
 def mutual_information(px, py, boundary, want_grads=True):
     """Raw recursion: returns (scores (B,), p, px_grad, py_grad) -- no autograd."""
     B, S, T1 = px.shape
     T = T1 - 1
     dev = px.device
+    _check_lattice_rows(S)
     p = torch.empty((B, S + 1, T + 1), dtype=torch.float32, device=dev)
     ans = torch.empty((B,), dtype=torch.float32, device=dev)
     L = N.lib()
@@ -184,6 +194,7 @@ class _SimpleRnntLoss(torch.autograd.Function):
         am = am.contiguous().float()
         B, T, C = am.shape
         S = lm.shape[1] - 1
+        _check_lattice_rows(S)
         dev = am.device
         L = N.lib()
         st = N.stream()
@@ -273,6 +284,11 @@ class _PrunedJoinerLoss(torch.autograd.Function):
         S = lm.shape[1] - 1
         R = ranges.shape[2]
         dev = am.device
+        _check_lattice_rows(S)
+        if C > RNNT_MAX_JOINER_DIM:
+            raise ValueError(f"fused pruned joiner: joiner dimension {C} exceeds the kernel's "
+                             f"limit of {RNNT_MAX_JOINER_DIM} (a row is held in one wave's "
+                             "registers, csrc/rnnt.hip); there is no fallback")
         L = N.lib()
         st = N.stream()
         px = torch.empty((B, S, T + 1), dtype=torch.float32, device=dev)
@@ -323,6 +339,7 @@ class _LatticeLoss(torch.autograd.Function):
         logits = logits.contiguous().float()
         B, T, R, V = logits.shape
         S = symbols.shape[1]
+        _check_lattice_rows(S)
         dev = logits.device
         px = torch.empty((B, S, T + 1), dtype=torch.float32, device=dev)
         py = torch.empty((B, S + 1, T), dtype=torch.float32, device=dev)
