@@ -436,9 +436,34 @@ class _LnLstm(torch.autograd.Function):
 
 def lnlstm(gx, p2g_weight, g_norm, c_norm, h0=None, c0=None):
     """gx (T,B,4H) -> (hs (T,B,H), h_T, c_T).  g_norm / c_norm: nn.LayerNorm modules, or
-    nn.Identity (no layer norm)."""
+    nn.Identity (no layer norm).  h0 / c0 are constants and h_T / c_T carry no gradient.  Hidden
+    widths outside the kernel's rule (H % 4 != 0, H > 1024) take the same recurrence composed from
+    torch's device ops."""
     if not gx.is_cuda:
         raise RuntimeError("speech2text_amd.lnlstm needs device tensors (HIP path only)")
+    if torch.is_grad_enabled() and any(s is not None and s.requires_grad for s in (h0, c0)):
+        raise RuntimeError("speech2text_amd.lnlstm treats h0 / c0 as constants (no gradient is "
+                           "formed for the initial state): detach them")
+    H = gx.shape[-1] // 4
+    if H % 4 or H > 1024:
+        # hidden widths the sequence kernel is not built for: the same recurrence from torch's
+        # device ops, autograd doing the backward
+        ln = isinstance(g_norm, torch.nn.LayerNorm)
+        h = gx.new_zeros(gx.shape[1], H) if h0 is None else h0.to(gx.dtype)
+        c = gx.new_zeros(gx.shape[1], H) if c0 is None else c0.to(gx.dtype)
+        outs = []
+        for g in gx.unbind(0):
+            g = g + torch.nn.functional.linear(h, p2g_weight)
+            if ln:
+                g = torch.nn.functional.layer_norm(g, (4 * H,), g_norm.weight, g_norm.bias, g_norm.eps)
+            i, f, z, o = g.chunk(4, dim=1)
+            c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(z)
+            if ln:
+                c = torch.nn.functional.layer_norm(c, (H,), c_norm.weight, c_norm.bias, c_norm.eps)
+            h = torch.sigmoid(o) * torch.tanh(c)
+            outs.append(h)
+        hs = torch.stack(outs, 0) if outs else gx.new_zeros(0, gx.shape[1], H)
+        return hs, h.detach(), c.detach()        # the final state is a constant, as on the kernel path
     if isinstance(g_norm, torch.nn.LayerNorm):
         return _LnLstm.apply(gx, p2g_weight, g_norm.weight, g_norm.bias, c_norm.weight,
                              c_norm.bias, g_norm.eps, h0, c0)

@@ -97,6 +97,16 @@ class RnntGreedyDecoding(DecodingMethod):
         p = getattr(self._predictor, "predictor", self._predictor)
         return isinstance(p, StatelessPredictor) and not self._joiner._use_out_project
 
+    def _fused(self):
+        """The fused device search serves these modules: fusable, and the kernel's rules hold (its
+        per-utterance vectors of E + D + V floats and the ctx-token state fit 60 KB of shared
+        memory, ctx <= 64 -- csrc/decode.hip).  Otherwise: the module-by-module lattice walk."""
+        if not self._fusable():
+            return False
+        p = getattr(self._predictor, "predictor", self._predictor)
+        need = 4 * (p._embedding_dim + p._output_dim + self._joiner._output_dim) + 4 * p._context_size
+        return need <= 60 * 1024 and p._context_size <= 64
+
     def greedy_tokens(self, hidden_states, inputs_length):
         """(B,T,D) encoder output -> (tokens (B,max_out), out_len (B)); fused device search."""
         p = getattr(self._predictor, "predictor", self._predictor)
@@ -120,17 +130,18 @@ class RnntGreedyDecoding(DecodingMethod):
 
     @torch.no_grad()
     def decode_batch(self, hidden_states, inputs_length):
-        if self._fusable():
+        if self._fused():
             return _to_texts(*self.greedy_tokens(hidden_states, inputs_length), self._tokenizer)
         return super().decode_batch(hidden_states, inputs_length)
 
     @torch.no_grad()
     def decode(self, hidden_states: torch.Tensor) -> str:
         assert hidden_states.shape[0] == 1, "Support BatchSize = 1 only."
-        if self._fusable():
+        if self._fused():
             n = torch.tensor([hidden_states.shape[1]], dtype=torch.int64)
             return self.decode_batch(hidden_states, n)[0]
-        # module-by-module lattice walk (reference :237-271) for LSTM predictors / out-projection
+        # module-by-module lattice walk (reference :237-271) for LSTM predictors / out-projection /
+        # vocabularies beyond the fused kernel's shared memory
         pred_state = self._predictor.init_state()
         T = hidden_states.shape[1]
         t = 0

@@ -289,8 +289,9 @@ def test_layer_executor_vs_oracle_c2_dims(dev):
 
 def test_shapes_outside_the_kernels_rules_use_torch_device_ops(dev):
     """Row lengths that are not multiples of 4 / head widths other than 16, 32, 64 / a BatchNorm
-    with momentum=None / an empty LSTM sequence: the wrappers fall back to torch's DEVICE kernels
-    (or handle the case) instead of failing with -2."""
+    with momentum=None / an empty LSTM sequence / an LSTM hidden width that is no multiple of 4 or
+    above 1024: the wrappers fall back to torch's DEVICE kernels (or handle the case) instead of
+    failing with -2.  (The LSTM's composed path is held to float64 in test_gpu_lstm_kernel.py.)"""
     from speech2text_amd import conf_kernels as ck
     torch.manual_seed(0)
     ln = torch.nn.LayerNorm(6).to(dev)
@@ -324,3 +325,10 @@ def test_shapes_outside_the_kernels_rules_use_torch_device_ops(dev):
     assert hs.shape[0] == 0
     torch.testing.assert_close(hT, h0)
     torch.testing.assert_close(cT, c0)
+    # hidden widths outside the sequence kernel's rule
+    for Hh in (6, 1028):
+        hs, hT, cT = ck.lnlstm(torch.randn(3, 2, 4 * Hh, device=dev),
+                               torch.randn(4 * Hh, Hh, device=dev) / Hh ** 0.5,
+                               torch.nn.Identity(), torch.nn.Identity())
+        assert hs.shape == (3, 2, Hh) and hs.is_cuda and torch.equal(hT, hs[-1])
+        assert cT.shape == (2, Hh) and torch.isfinite(hs).all()
