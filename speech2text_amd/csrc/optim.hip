@@ -114,7 +114,11 @@ __global__ __launch_bounds__(256) void scaled_adam_coef_kernel(CoefArgs A) {
     A.segstat[3 * (long)s + 1] = b;
     A.segstat[3 * (long)s + 2] = c;
   }
-  // ---- trainer clip: global gradient norm over EVERY tensor of the store
+  // ---- trainer clip: global gradient norm over EVERY tensor of the store.  A NaN norm leaves the
+  // factor at 1 (fminf drops the NaN operand; torch's clip_grad_norm_ would scale every gradient by
+  // NaN): without a threshold the finite elements step and the NaN stays in its own element, with one
+  // the group's factor below is 0 and the gradients are zeroed.  The host forms and
+  // tests/optim_f64.py state the same rule.
   float c = 1.f;
   if (A.clip_val > 0.f) {
     float t = 0.f;
@@ -282,7 +286,9 @@ __global__ __launch_bounds__(256) void scaled_adam_apply_kernel(
 // ---- Adam / AdamW on the flat buffers (torch.optim.Adam / AdamW semantics, amsgrad off):
 // the conformer configs (config/training/conformer_*.yaml `optimizer: type: "AdamW"`).
 // clip_coef: ONE workgroup folds the per-chunk sums of g^2 (seg_stats) in a fixed order and
-// writes min(1, clip / (norm + 1e-6)); adam_apply: one workgroup per chunk.
+// writes min(1, clip / (norm + 1e-6)), 1 for a NaN norm (fmin drops the NaN operand: the rule of the
+// ScaledAdam coefficient kernel above); adam_apply: one workgroup per chunk.  A dropped step (skip)
+// leaves parameters and moments alone; the host advances the step count all the same.
 __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict__ partial,
                                                         int nchunks, float clip_val,
                                                         float* __restrict__ out) {

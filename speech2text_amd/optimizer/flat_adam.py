@@ -8,7 +8,19 @@ grad-norm clip; with all parameters in one FlatStore (speech2text_amd.flat) a st
 launches (csrc/optim.hip): per-chunk sums of g^2, one workgroup that folds them into the clip
 factor, one fused update that also zeroes the gradients.  `state[p]` holds views of the flat
 moment buffers under torch's keys (`step`, `exp_avg`, `exp_avg_sq`), so checkpoints interchange.
-Parameters that are not in a FlatStore on the GPU (host-logic tests) take torch's own step.
+Parameters that are not in a FlatStore on the GPU (host-logic tests), and more than
+S2T_ADAM_MAX_GROUPS param groups, take torch's own step.
+
+Rules on top of torch's, the same on both paths (tests/optim_f64.py restates them,
+tests/test_optim_f64.py and tests/test_gpu_optim_kernels.py hold both paths to it):
+  * trainer clip (`pre_clip`): clip_grad_norm_'s factor min(1, clip / (norm + 1e-6)) with the norm
+    over every tensor of the store, the ones no group lists included; a NaN norm leaves the factor
+    at 1 (fmin on the device) where clip_grad_norm_ would multiply every gradient by NaN.
+  * dropped step (`skip_flag`): the step count, and with it the bias corrections, advances -- the
+    fused path cannot read the flag without a host sync, and ScaledAdam counts the same way --
+    parameters and moments stay, the gradients are cleared if `zero_grad_in_step`.
+  * a trainable tensor of the store that no group lists is never updated; its gradient is cleared
+    with the others.
 """
 import ctypes
 import math
@@ -38,6 +50,7 @@ class _FlatMixin:
         # (set by the trainer from the DP reducer's "step dropped on every rank" flag; no host sync)
         self.skip_flag = None
         self._flat = None
+        self._host_store = None       # the FlatStore of the parameters, if they have one (host path)
 
     def _flat_init(self):
         groups = [[p for p in g["params"] if p.requires_grad] for g in self.param_groups]
@@ -46,6 +59,7 @@ class _FlatMixin:
             st = store_of(allp)
         except RuntimeError:
             st = None
+        self._host_store = st
         if st is None or not st.flat_p.is_cuda or len(groups) > 8:
             self._flat = False
             return
@@ -88,17 +102,7 @@ class _FlatMixin:
         if self._flat is None:
             self._flat_init()
         if self._flat is False:
-            if self.skip_flag is not None and float(self.skip_flag) != 0.0:
-                if self.zero_grad_in_step:   # dropped step (ddp.py), host form: CPU tensors only
-                    self.zero_grad(set_to_none=False)
-                return None
-            if self.pre_clip:
-                params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
-                torch.nn.utils.clip_grad_norm_(params, self.pre_clip)
-            out = super().step(closure)
-            if self.zero_grad_in_step:
-                self.zero_grad(set_to_none=False)
-            return out
+            return self._host_step(closure)
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -136,6 +140,39 @@ class _FlatMixin:
         st.epoch += 1                      # parameters rewritten: weight pieces are stale
         f["step_t"].fill_(float(k))        # ONE shared host scalar: every state's "step" is this tensor
         return loss
+
+    def _host_step(self, closure):
+        """torch's own step under the rules of the fused path (module docstring)."""
+        st = self._host_store
+        everyone = st.params if st is not None else \
+            [p for g in self.param_groups for p in g["params"]]
+        if self.skip_flag is not None and float(self.skip_flag) != 0.0:
+            for g in self.param_groups:      # dropped step (ddp.py): only the count advances
+                for p in g["params"]:
+                    if p.grad is None:       # torch keeps no state for it either
+                        continue
+                    s = self.state[p]
+                    if len(s) == 0:          # torch's lazy state, as Adam._init_group makes it
+                        s["step"] = torch.tensor(0.0, dtype=torch.get_default_dtype())
+                        s["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                        s["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                        if g.get("amsgrad"):
+                            s["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    s["step"] += 1
+            out = None
+        else:
+            if self.pre_clip:
+                grads = [p.grad for p in everyone if p.grad is not None]
+                norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g) for g in grads]))
+                c = torch.nan_to_num(torch.clamp(self.pre_clip / (norm + 1.0e-6), max=1.0), nan=1.0)
+                for g in grads:
+                    g.mul_(c)
+            out = super().step(closure)
+        if self.zero_grad_in_step:
+            for p in everyone:
+                if p.grad is not None:
+                    p.grad.zero_()
+        return out
 
     def load_state_dict(self, sd):
         """torch's loader replaces the per-parameter tensors; copy them back into the flat moment

@@ -12,11 +12,37 @@ never waits for the device except when the clipping threshold is re-estimated (e
 `clipping_update_period` steps), to raise on a non-finite median as the reference does.
 
 CPU tensors (host-logic tests only) run the same arithmetic as torch ops on the same buffers.
+
+Rules on top of the reference's, the same on the device and in the host form
+(tests/optim_f64.py restates them independently, tests/test_optim_f64.py and
+tests/test_gpu_optim_kernels.py hold both forms to it):
+  * trainer clip (`pre_clip`): every gradient is scaled by min(1, clip / (norm + 1e-6)), the norm
+    taken over every tensor of the store.  A NaN norm leaves the factor at 1 (fminf on the device),
+    where torch's clip_grad_norm_ would multiply every gradient by NaN: while no clipping threshold
+    exists (step 0, `clipping_scale=None`) the finite elements take their step and the NaN stays in
+    its own element; with a threshold the group's factor is 0 and its gradients are zeroed, as in
+    the reference.  From the size update after a NaN has reached a parameter on, that tensor's rms is
+    NaN and the two forms part ways (fminf / fmaxf drop a NaN operand, torch.minimum / clamp keep
+    it); no test holds that regime.
+  * dropped step (`skip_flag`): the step count advances (bias corrections, LR schedule position),
+    parameters and moments stay, the (p . g) sample of the step is 0, the clipping window repeats
+    the previous norm, the gradients are cleared if `zero_grad_in_step`.
+  * non-finite median: `RuntimeError("Too many grads were not finite")`.  On the device the raise
+    comes after the coefficient kernels and before the update: the parameters, `delta`,
+    `exp_avg_sq`, the gradients and every group's step count are as before the call; the small
+    state of the step is written (`model_norms[k % period]`, `scale_grads[k % P]`, on a size-update
+    step `param_rms` and `scale_exp_avg_sq`, the non-finite threshold) and `istate[2]` stays set,
+    so every later threshold step raises again: the optimizer is to be rebuilt or reloaded, not
+    stepped on.  The host form raises from inside its loop over the groups, with the groups before
+    the raising one already stepped.
+  * `clipping_update_period` is 1..1024 (the coefficient kernel sorts the window in LDS).
 """
 import torch
 from torch.optim import Optimizer
 
 from speech2text_amd.flat import FlatStore, store_of
+
+MAX_CLIPPING_UPDATE_PERIOD = 1024
 
 
 class ScaledAdam(Optimizer):
@@ -40,6 +66,12 @@ class ScaledAdam(Optimizer):
                         size_update_period=size_update_period,
                         clipping_update_period=clipping_update_period)
         super().__init__(params, defaults)
+        for g in self.param_groups:
+            period = g["clipping_update_period"]
+            if not (isinstance(period, int) and 1 <= period <= MAX_CLIPPING_UPDATE_PERIOD):
+                raise ValueError(f"clipping_update_period must be an integer in 1.."
+                                 f"{MAX_CLIPPING_UPDATE_PERIOD} (the fused kernel sorts the window "
+                                 f"of norms in one workgroup's LDS), got {period!r}")
         self._gstate = None
         self.store = None
         self.pre_clip = None          # trainer's gradient_clip_val (norm), applied inside step()
@@ -108,11 +140,12 @@ class ScaledAdam(Optimizer):
         elif self.skip_flag is not None and float(self.skip_flag) != 0.0:
             # dropped step (ddp.py), host form (CPU tensors only).  As on the GPU path the step
             # count (bias correction, LR schedule position) advances, parameters and moments stay,
-            # and the clipping window repeats the previous norm.
-            for s in self._gstate:
+            # the (p . g) sample of the step is 0 and the clipping window repeats the previous norm.
+            for group, s in zip(self.param_groups, self._gstate):
                 k = s["step"]
-                mn = s.get("model_norms")
-                if mn is not None and k > 0:
+                s["scale_grads"][k % group["size_update_period"]] = 0.0
+                if group["clipping_scale"] is not None and k > 0:
+                    mn = s["model_norms"]
                     P = mn.numel()
                     mn[k % P] = mn[(k - 1) % P]
                 s["step"] = k + 1
@@ -185,6 +218,7 @@ class ScaledAdam(Optimizer):
         c = None
         if self.pre_clip:
             c = torch.clamp(self.pre_clip / (st.g().norm() + 1.0e-6), max=1.0)
+            c = torch.nan_to_num(c, nan=1.0)      # the device's fminf: a NaN norm clips nothing
         for group, s in zip(self.param_groups, self._gstate):
             h = self._host_scalars(group, s)
             k, beta1, beta2, P = h["k"], h["beta1"], h["beta2"], h["P"]
