@@ -712,6 +712,22 @@ int s2t_lnlstm_bwd(const float* wp, const float* g_gamma, const float* g_beta,
                    float* dgx, float* d_g_gamma, float* d_g_beta, float* d_c_gamma,
                    float* d_c_beta, void* stream);
 
+/* ---- LSTM layer of the RNN language model (reference model/lm/rnn_lm.py:40-45: torch.nn.LSTM, gate
+ * order i, f, g, o, no layer norm), ONE LAUNCH PER TIME STEP, ordered by the stream alone
+ * (csrc/lstm_step.hip): a workgroup owns 16 hidden units and 16 utterances, so the recurrent matrix
+ * is read once per step and batch tile, not once per utterance.  gx (T,B,4H) = x W_ih^T + b_ih +
+ * b_hh; whh = weight_hh (4H,H) for the forward, whh_t = its transpose (H,4H) for the backward;
+ * h0 / c0 (B,H) or NULL = zeros.  The forward writes hs (T,B,H), the final state hT / cT (B,H) and
+ * keeps the ACTIVATED gates (T,B,4H) and the cells (T,B,H); the backward takes dhs (T,B,H) and
+ * writes dgx (T,B,4H), the gradient w.r.t. the raw gates (weight gradients: TN GEMMs over its
+ * rows; bias gradients: its column sums); dc_ws (B,H) is scratch for the carried cell gradient.
+ * H % 4 == 0, H <= 1024 (else -2); all pointers 16-byte aligned. */
+int s2t_lstm_seq_fwd(const float* gx, const float* whh, const float* h0, const float* c0, int T,
+                     int B, int H, float* hs, float* gates, float* cells, float* hT, float* cT,
+                     void* stream);
+int s2t_lstm_seq_bwd(const float* whh_t, const float* c0, int T, int B, int H, const float* gates,
+                     const float* cells, const float* dhs, float* dgx, float* dc_ws, void* stream);
+
 /* ---- StatelessPredictor: embedding + depthwise context convolution in one pass
  * (reference model/predictor/stateless_predictor.py:27-105: nn.Embedding -> nn.Conv1d(D, D, K,
  * groups=D, bias=False) on the blank-left-padded labels).  tokens (B,L) int32 (values clamped to

@@ -11,6 +11,7 @@ import torch
 import yaml
 
 from speech2text_amd.task_factory.ctc_task import CtcTask
+from speech2text_amd.task_factory.nnlm_task import NnLmTask
 from speech2text_amd.task_factory.rnnt_task import CtcHybridRnnt, PrunedRnntTask, RnntTask
 from speech2text_amd.task_factory.ssl_task import SslTask
 from speech2text_amd.trainer import Trainer
@@ -19,11 +20,6 @@ from speech2text_amd.trainer import Trainer
 class CifTask:
     def __init__(self, config):
         raise NotImplementedError("task CIF is outside the accelerated path (SURVEY.md 2)")
-
-
-class NnlmTask:
-    def __init__(self, config):
-        raise NotImplementedError("task NNLM is outside the accelerated path (SURVEY.md 2)")
 
 
 @unique
@@ -35,7 +31,7 @@ class TaskFactory(Enum):
     Pruned_Rnnt = PrunedRnntTask
     SSL = SslTask
     CIF = CifTask
-    NNLM = NnlmTask
+    NNLM = NnLmTask
 
     @classmethod
     def get(cls, name):

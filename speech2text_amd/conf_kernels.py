@@ -470,6 +470,96 @@ def lnlstm(gx, p2g_weight, g_norm, c_norm, h0=None, c0=None):
     return _LnLstm.apply(gx, p2g_weight, None, None, None, None, 0.0, h0, c0)
 
 
+# ------------------------------------------------------------------ plain LSTM layer, step-launched
+class _LstmSeq(torch.autograd.Function):
+    """hs, hT, cT = torch.nn.LSTM's layer on gx (T,B,4H) = x W_ih^T + b_ih + b_hh, one launch per
+    time step with the recurrent matrix shared across the batch (csrc/lstm_step.hip).  Backward:
+    the reverse walk gives the gradient w.r.t. the raw gates; d weight_hh is a TN GEMM of it
+    against the shifted hidden states, as for _LnLstm."""
+
+    @staticmethod
+    def forward(ctx, gx, whh, h0, c0):
+        T, B, G = gx.shape
+        H = G // 4
+        dev = gx.device
+        gx = gx.contiguous().float()
+        wc = whh.detach().contiguous().float()
+        hs = torch.empty((T, B, H), dtype=_F32, device=dev)
+        gates = torch.empty((T, B, G), dtype=_F32, device=dev)
+        cells = torch.empty((T, B, H), dtype=_F32, device=dev)
+        h0c = None if h0 is None else h0.contiguous().float()
+        c0c = None if c0 is None else c0.contiguous().float()
+        if T == 0:                   # nothing to scan: the final state is the initial one
+            hT = torch.zeros((B, H), dtype=_F32, device=dev) if h0c is None else h0c.clone()
+            cT = torch.zeros((B, H), dtype=_F32, device=dev) if c0c is None else c0c.clone()
+        else:
+            hT = torch.empty((B, H), dtype=_F32, device=dev)
+            cT = torch.empty((B, H), dtype=_F32, device=dev)
+        N.check(N.lib().s2t_lstm_seq_fwd(N.fp(gx), N.fp(wc), N.fp(h0c), N.fp(c0c), T, B, H,
+                                         N.fp(hs), N.fp(gates), N.fp(cells), N.fp(hT), N.fp(cT),
+                                         N.stream()), "s2t_lstm_seq_fwd")
+        ctx.save_for_backward(whh, gates, cells, hs, h0c, c0c)
+        ctx.params = (whh,)
+        ctx.mark_non_differentiable(hT, cT)
+        return hs, hT, cT
+
+    @staticmethod
+    def backward(ctx, dhs, _dh, _dc):
+        from . import zip_kernels as zk
+        whh, gates, cells, hs, h0c, c0c = ctx.saved_tensors
+        (wparam,) = ctx.params
+        T, B, G = gates.shape
+        H = G // 4
+        dhs = dhs.contiguous().float()
+        dgx = torch.empty_like(gates)
+        dc_ws = torch.empty((B, H), dtype=_F32, device=gates.device)
+        wt = whh.detach().float().t().contiguous()
+        N.check(N.lib().s2t_lstm_seq_bwd(N.fp(wt), N.fp(c0c), T, B, H, N.fp(gates), N.fp(cells),
+                                         N.fp(dhs), N.fp(dgx), N.fp(dc_ws), N.stream()),
+                "s2t_lstm_seq_bwd")
+        dwhh = None
+        if ctx.needs_input_grad[1]:
+            # d weight_hh = sum_t dg_t^T h_{t-1}
+            hprev = torch.empty_like(hs)
+            hprev[1:] = hs[:-1]
+            if h0c is None:
+                hprev[0].zero_()
+            else:
+                hprev[0] = h0c
+            g2, a2 = dgx.view(T * B, G), hprev.view(T * B, H)
+            if not zk.wgrad_into(wparam, None, g2, a2):
+                dwhh, _ = zk.linear_wgrad(g2, a2, False)
+        return dgx, dwhh, None, None
+
+
+# Batches below this take the per-utterance sequence kernel (csrc/lstm.hip with NULL norms: one
+# launch for all T steps); from it on, the step-launched batch-tiled kernel.  Measured on the
+# MI355X at H = 512 (tools/bench_rnn_lm.py --sweep, profiles/rnn_lm_bench.json, DESIGN.md 3j): the
+# step kernel is the faster one at EVERY batch from 1 to 256, at T = 1 (score_step: 0.020 against
+# 0.054 ms) as at T = 117 (B = 1: 0.84 against 4.0 ms), so there is no crossover and nothing goes
+# to the per-utterance kernel.
+LSTM_STEP_MIN_BATCH = 1
+
+
+def lstm(gx, weight_hh, h0=None, c0=None):
+    """torch.nn.LSTM's recurrence of ONE layer and direction on gx (T,B,4H) = x W_ih^T + b_ih + b_hh
+    (gate order i, f, g, o) -> (hs (T,B,H), h_T, c_T).  h0 / c0 (B,H) are constants and h_T / c_T
+    carry no gradient (the contract of `lnlstm`).  B >= LSTM_STEP_MIN_BATCH (every batch, as
+    measured): the step-launched kernel of csrc/lstm_step.hip; smaller batches: the per-utterance
+    kernel of csrc/lstm.hip without norms; widths outside both kernels' rule (H % 4 != 0,
+    H > 1024): the recurrence composed from torch's device ops."""
+    if not gx.is_cuda:
+        raise RuntimeError("speech2text_amd.lstm needs device tensors (HIP path only)")
+    if torch.is_grad_enabled() and any(s is not None and s.requires_grad for s in (h0, c0)):
+        raise RuntimeError("speech2text_amd.lstm treats h0 / c0 as constants (no gradient is "
+                           "formed for the initial state): detach them")
+    H = gx.shape[-1] // 4
+    if H % 4 or H > 1024 or gx.shape[1] < LSTM_STEP_MIN_BATCH:
+        ident = torch.nn.Identity()
+        return lnlstm(gx, weight_hh, ident, ident, h0, c0)
+    return _LstmSeq.apply(gx, weight_hh, h0, c0)
+
+
 # ------------------------------------------------------------------ Subsampling: first conv + ReLU
 def conv1_relu_ok(conv, x):
     C = conv.out_channels

@@ -30,8 +30,12 @@ class TaskBase(nn.Module):
             self._tokenizer = TokenizerSetup(config["tokenizer"])
         self._metric_config = config.get("metric")
         self._metric = None
-        self._frontend = self._get_frontend(copy.deepcopy(config["dataset"]))
-        self._global_cmvn = GlobalCmvnLayer(config=self._dataset_config)
+        if "feat_type" in self._dataset_config:
+            self._frontend = self._get_frontend(copy.deepcopy(config["dataset"]))
+            self._global_cmvn = GlobalCmvnLayer(config=self._dataset_config)
+        else:       # a text task (NNLM): its dataset section describes no acoustic features
+            self._frontend = None
+            self._global_cmvn = None
         self.logged = {}
         self.current_epoch = 0
         self.global_step = 0

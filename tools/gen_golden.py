@@ -642,6 +642,57 @@ def gen_rnnt_beam():
             assert size < 1 << 20, f
 
 
+def gen_rnn_lm():
+    """The reference RnnLm (model/lm/rnn_lm.py) and its training loss (MaskedKLDivergence, label
+    smoothing 0.1, as task_factory/nnlm_task.py:118-134 calls them), run here on the CPU at a tiny
+    config -> rnn_lm_ref.npz; and the names / shapes of its state dict at the YAML config under the
+    task's `_nnlm.` prefix -> state_keys_nnlm.json."""
+    import json
+    import torch
+    import yaml
+    ref_import.install_stubs()
+    from model.lm.rnn_lm import RnnLm, RnnLmConfig
+    from model.loss.kl_divergence import MaskedKLDivergence, MaskedKLDivergenceConfig
+    torch.manual_seed(20241027)
+    V, E, L, B, T = 16, 8, 2, 4, 9
+    m = RnnLm(RnnLmConfig(num_symbols=V, symbol_embedding_dim=E, num_rnn_layer=L))
+    with torch.no_grad():            # the default init (|w| <= 0.35) leaves the gates near 0.5
+        for n, p in m.named_parameters():
+            if "_rnn_layer" in n:
+                p.mul_(3.0)
+    lens = torch.tensor([9, 7, 5, 2])
+    tokens = torch.randint(1, V, (B, T))
+    for b in range(B):
+        tokens[b, lens[b]:] = 0
+    out = {"sd." + k: v.detach().numpy().copy() for k, v in m.state_dict().items()}
+    out["tokens"], out["lengths"] = tokens.numpy(), lens.numpy()
+    logits, _ = m(tokens, lens)
+    out["logits"] = logits.detach().numpy()
+    out["score"] = m.score(tokens, lens).numpy()
+    st = m.init_states(B)
+    for i in range(2):
+        lp, st = m.score_step(tokens[:, i], st)
+        out[f"step{i}_log_probs"] = lp.numpy()
+        out[f"step{i}_h"], out[f"step{i}_c"] = st[0].numpy(), st[1].numpy()
+    loss_fn = MaskedKLDivergence(MaskedKLDivergenceConfig(num_classes=V, scale_factor=1.0,
+                                                          label_smoothing=0.1))
+    inp, lab, ll = tokens[:, :-1].long(), tokens[:, 1:].long(), (lens - 1).long()
+    lg, lg_len = m(inp, ll)
+    loss = loss_fn(logits=lg, ori_labels=lab, mask=lg_len)
+    loss.backward()
+    out["loss"] = loss.detach().numpy()
+    for k, p in m.named_parameters():
+        out["grad." + k] = p.grad.numpy().copy()
+    np.savez_compressed(os.path.join(OUT, "rnn_lm_ref.npz"), **out)
+    print("rnn_lm: loss", float(out["loss"]), "score", out["score"],
+          os.path.getsize(os.path.join(OUT, "rnn_lm_ref.npz")), "bytes")
+    cfg = yaml.safe_load(open("/root/reference/config/training/rnn_lm.yaml"))
+    big = RnnLm(RnnLmConfig(**cfg["nnlm"]))
+    keys = {"_nnlm." + k: list(v.shape) for k, v in big.state_dict().items()}
+    json.dump(keys, open(os.path.join(OUT, "state_keys_nnlm.json"), "w"), indent=0, sort_keys=True)
+    print("state_keys_nnlm", len(keys))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["fbank", "ctc", "bestrq", "zipformer", "scaledadam"]
