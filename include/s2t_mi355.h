@@ -890,7 +890,9 @@ int s2t_bmm_lt(int mode, const float* A, const float* B, float* C, int batch, in
  * them and passes them as `dec`; C++ only reads them.
  *   desc  : the layer's shapes, parameter / gradient addresses (views of the FlatStore), bf16 piece
  *           addresses of its weights (planes.py; NULL = library path) and module constants;
- *   call  : this call's shapes, inputs, masks, decisions, persistent scratch, switches;
+ *   call  : this call's shapes, inputs, masks, decisions, persistent scratch, and the switches the
+ *           caller still varies (Whiten forms, the plan's tile / margin, what runs on the side stream):
+ *           every field is read;
  *   state : s2t_zip_layer_state_bytes() bytes of HOST memory, written by fwd, read by bwd;
  *   ws    : device workspace, >= s2t_zip_layer_ws_floats(desc, call, backward) floats; the forward's
  *           must stay alive (and untouched) until the backward has been enqueued.
@@ -991,11 +993,10 @@ typedef struct S2tZipLayerCall {
   int nwh;
   void* lt_ws;
   long lt_ws_bytes;
-  int x3p_on, x3p_tile;
-  float x3p_margin;
+  int x3p_tile;                    /* tile code of the Whiten penalty product (s2t_gemm_x3p_sq; 0: from the shape) */
+  float x3p_margin;                /* s2t_zl_plan_choose's margin */
   int whiten_x3p;                  /* Whiten backward: 2 = dcov + its pieces in forward, product on the pre-split-weight kernel (round 6); 0 = the NN kernel, three launches */
-  int conv_w_side, conv_fused, stats_side, wgrad_side, bmm_own;
-  int bal_epi;                     /* hidden Balancers in the dgrad epilogue (s2t_gemm_x3p_bal) */
+  int conv_w_side, stats_side, wgrad_side;   /* conv parameter gradients / Whiten statistics / weight gradients on the side stream */
   int whiten_sq;                   /* Whiten's norms in the x dcov product's epilogue (s2t_gemm_f32_sq) */
   int bal_fwd_side;                /* firing Balancers' column statistics taken in forward on the side stream (round 6) */
   int whiten_fwd_pg;               /* Whiten's penalty product x dcov taken in forward on the statistics' stream (round 6) */
@@ -1015,6 +1016,21 @@ void* s2t_zip_layer_error(void);
 int s2t_zl_plan_put(int mode, int half_oct, int N, int K, double t_lib_ms, double t_own_ms, int tile);
 int s2t_zl_plan_clear(void);
 long s2t_zl_plan_count(void);
+/* THE plan rule: which kernel serves a product of `rows` rows in the bucket {mode as given to
+ * s2t_zl_plan_put, half-octave of rows, N, K} with the epilogue `epilogue_bits` (S2T_ZL_EPI_*).  1: our
+ * kernel, *tile = the bucket's tile; 0: the library; -1: the bucket has no timings yet.  With one
+ * elementwise pass over the (rows, cols) result costed at 4 us + 12 rows cols bytes at 3 TB/s:
+ *   library = t_lib (* margin when the epilogue is plain: bias / resid2 only)
+ *             + one pass per {act_src, act_src with resid2, resid_b, Swoosh act2, bal};
+ *   ours    = t_own + 4 rows cols bytes at 3 TB/s per {act_src, resid_b, any act2, bal};
+ * ours where it is strictly cheaper.  Launches nothing. */
+#define S2T_ZL_EPI_ACT_SRC 1
+#define S2T_ZL_EPI_RESID2 2
+#define S2T_ZL_EPI_RESID_B 4
+#define S2T_ZL_EPI_ACT2_SWOOSH 8
+#define S2T_ZL_EPI_ACT2_ADD 16
+#define S2T_ZL_EPI_BAL 32
+int s2t_zl_plan_choose(int mode, long rows, int N, int K, int epilogue_bits, float margin, int* tile);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,8 @@ There is no fallback: if the shared library is missing, or a tensor handed to a
 kernel is not a contiguous device tensor of the declared dtype, this raises.
 """
 import ctypes
+import functools
+import keyword
 import os
 import re
 
@@ -38,6 +40,57 @@ def parse_header(path=HEADER_PATH):
     return protos
 
 
+_FIELD_CT = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float,
+             "double": ctypes.c_double, "unsigned": ctypes.c_uint}
+_DECL = r"(\**)\s*(\w+)\s*(?:\[\s*(\w+)\s*\])?"
+
+
+def parse_abi(txt):
+    """-> ({S2T_NAME: int} for every plain-integer #define, {S2tName: ctypes.Structure class} for every
+    `typedef struct { ... } S2tName;`) of a header's text.  Pointers of any pointee are c_void_p, as in
+    the prototypes; a field named like a Python keyword gets a trailing underscore.  A field this does
+    not understand raises ValueError: a layout is never guessed."""
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    consts = {m.group(1): int(m.group(2))
+              for m in re.finditer(r"^[ \t]*#define[ \t]+(S2T_\w+)[ \t]+(\d+)[ \t]*$", txt, re.M)}
+    structs = {}
+    for m in re.finditer(r"\btypedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", txt):
+        sname, fields = m.group(2), []
+        for stmt in filter(None, (s.strip() for s in m.group(1).split(";"))):
+            first, *rest = stmt.split(",")
+            head = re.fullmatch(r"(?:const\s+)?(\w+(?:\s+\w+)*?)\b\s*" + _DECL, first.strip())
+            decls = [re.fullmatch(_DECL, r.strip()) for r in rest]
+            if head is None or None in decls:
+                raise ValueError(f"{sname}: cannot parse the field declaration {stmt!r}")
+            base = head.group(1)
+            for stars, name, dim in [head.groups()[1:]] + [d.groups() for d in decls]:
+                ct = ctypes.c_void_p if stars else _FIELD_CT.get(base) or structs.get(base)
+                if ct is None:
+                    raise ValueError(f"{sname}: unknown type {base!r} in {stmt!r}")
+                if dim is not None:
+                    if not dim.isdigit() and dim not in consts:
+                        raise ValueError(f"{sname}: undefined array dimension {dim!r} in {stmt!r}")
+                    ct = ct * (int(dim) if dim.isdigit() else consts[dim])
+                fields.append((name + "_" if keyword.iskeyword(name) else name, ct))
+        structs[sname] = type(sname, (ctypes.Structure,), {"_fields_": fields})
+    return consts, structs
+
+
+@functools.lru_cache(maxsize=None)
+def _abi():
+    return parse_abi(open(HEADER_PATH).read())
+
+
+def struct(name):
+    """The ctypes.Structure class of a struct of include/s2t_mi355.h, laid out from the header."""
+    return _abi()[1][name]
+
+
+def const(name):
+    """The value of a plain-integer #define of include/s2t_mi355.h."""
+    return _abi()[0][name]
+
+
 class _Prof:
     target = None        # None | "*" (every entry point) | one C entry-point name
     events = {}          # entry -> [(start, stop)] HIP events on the launch stream
@@ -49,7 +102,8 @@ class _Prof:
 
 _NO_LAUNCH = ("s2t_side_stream", "s2t_stream_order", "s2t_balancer_next_parity", "s2t_gemm_arith",
               "s2t_gemm_arith_of", "s2t_gemm_class_set", "s2t_gemm_arith_set",
-              "s2t_zip_layer_info", "s2t_zip_layer_error", "s2t_zip_layer_plans_missing", "s2t_zl_plan_put")   # stream plumbing, nothing to time
+              "s2t_zip_layer_info", "s2t_zip_layer_error", "s2t_zip_layer_plans_missing", "s2t_zl_plan_put",
+              "s2t_zl_plan_choose")   # stream plumbing, nothing to time
 SELF_NOTING = ("s2t_gemm_x3p",)   # entries whose call site calls profile_note() whenever a profile is active
 PROF = [False]   # True while profile_begin() is active: call sites write `N.PROF[0] and
                  # N.profile_note(...)` so that the note's arguments cost nothing on the training path

@@ -44,10 +44,7 @@ def ln_fwd(x2, y2, alpha, weight, bias, eps):
     return xsum, out, stats
 
 
-class LnFold(ctypes.Structure):
-    """Mirror of S2tLnFold (include/s2t_mi355.h)."""
-    _fields_ = [("partial", ctypes.c_void_p), ("rows", ctypes.c_long),
-                ("dgamma", ctypes.c_void_p), ("dbeta", ctypes.c_void_p)]
+LnFold = N.struct("S2tLnFold")
 
 
 def ln_bwd(x2, stats, weight, dy2, resid2, pend):

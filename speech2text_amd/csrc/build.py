@@ -29,6 +29,13 @@ def sources():
     return sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".hip"))
 
 
+def headers():
+    """What every object is stale against besides its own source: the public header each source
+    includes, and the private ones next to the sources."""
+    return [os.path.join(os.path.dirname(PKG), "include", "s2t_mi355.h")] + \
+        sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h"))
+
+
 def _stale(target, deps):
     if not os.path.exists(target):
         return True
@@ -38,7 +45,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     srcs = sources()
-    hdrs = [os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")]
+    hdrs = headers()
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     hipcc = _hipcc()

@@ -235,11 +235,32 @@ struct Epi {
 constexpr float kSwOff[3] = {0.f, 4.0f, 1.0f};
 constexpr float kSwC[3] = {0.f, 0.035f, 0.313261687f};
 
-int plan_missing(const Ctx& c, int mode, long R, const S2tZlLin& L) {
-  if (!c.c.x3p_on || R == 0) return 0;
+int plan_missing(int mode, long R, const S2tZlLin& L) {
+  if (R == 0) return 0;
   const unsigned short* pp = mode == 0 ? L.pf : L.pb;
   if (!pp) return 0;
   return g_plans.find(plan_key(plan_mode(mode), half_octave(R), L.N, L.K)) == g_plans.end();
+}
+
+// the plan rule (s2t_zl_plan_choose, include/s2t_mi355.h); `mode` as given to s2t_zl_plan_put
+int plan_choose(int mode, long R, int N, int K, int epi, float margin, int* tile) {
+  auto it = g_plans.find(plan_key(mode, half_octave(R), N, K));
+  if (it == g_plans.end()) return -1;
+  const Base& b = it->second;
+  if (b.t_own < 0.0) return 0;
+  const auto has = [epi](int bit) { return (epi & bit) != 0; };
+  const bool fused = epi & (S2T_ZL_EPI_ACT_SRC | S2T_ZL_EPI_RESID_B | S2T_ZL_EPI_ACT2_SWOOSH | S2T_ZL_EPI_ACT2_ADD);
+  const double rc = (double)R * ((mode & 1) == 0 ? N : K);
+  const double pass_ms = 4.0e-3 + 12.0 * rc / 3.0e9;    // one elementwise pass: 2 reads + 1 write at 3 TB/s
+  const int n_pass = has(S2T_ZL_EPI_ACT_SRC) + (has(S2T_ZL_EPI_ACT_SRC) && has(S2T_ZL_EPI_RESID2)) +
+                     has(S2T_ZL_EPI_RESID_B) + has(S2T_ZL_EPI_ACT2_SWOOSH) + has(S2T_ZL_EPI_BAL);
+  const int n_ops = has(S2T_ZL_EPI_ACT_SRC) + has(S2T_ZL_EPI_RESID_B) +
+                    (has(S2T_ZL_EPI_ACT2_SWOOSH) || has(S2T_ZL_EPI_ACT2_ADD)) + has(S2T_ZL_EPI_BAL);
+  const double cost_lt = b.t_lib * (fused ? 1.0 : (double)margin) + n_pass * pass_ms;
+  const double cost_own = b.t_own + n_ops * 4.0 * rc / 3.0e9;   // each extra operand / output: one more stream
+  if (!(cost_own < cost_lt)) return 0;
+  *tile = b.tile;
+  return 1;
 }
 
 int balancer_bwd(Ctx& c, const S2tZlBal& b, const float* x, long ldx, const float* g, long ldg, long R,
@@ -251,28 +272,16 @@ int lt_matmul(Ctx& c, int mode, const float* x, long ldx, long R, const S2tZlLin
   const int cols = mode == 0 ? L.N : L.K, inner = mode == 0 ? L.K : L.N;
   const long n = R * cols;
   const unsigned short* pp = mode == 0 ? L.pf : L.pb;
-  const bool fused = e.act_src || e.act2 || e.resid_b;
   bool own = false;
   int tile = 0;
-  if (c.c.x3p_on && R > 0 && pp) {
-    auto it = g_plans.find(plan_key(plan_mode(mode), half_octave(R), L.N, L.K));
-    if (it == g_plans.end()) {
-      if (!c.dry) return fail(-5, "lt_matmul: shape bucket not timed yet");
-      own = true;
-    } else if (it->second.t_own >= 0.0) {
-      const Base& b = it->second;
-      const double rc = (double)R * cols;
-      const double pass_ms = 4.0e-3 + 12.0 * rc / 3.0e9;
-      const int n_pass = (e.act_src != nullptr) + (e.act_src && e.resid2) + (e.resid_b != nullptr) +
-                         (e.act2 == 1 || e.act2 == 2) + (e.bal != nullptr);
-      const int n_ops = (e.act_src != nullptr) + (e.resid_b != nullptr) + (e.act2 != 0) + (e.bal != nullptr);
-      const double cost_lt = b.t_lib * (fused ? 1.0 : (double)c.c.x3p_margin) + n_pass * pass_ms;
-      const double cost_own = b.t_own + n_ops * 4.0 * rc / 3.0e9;
-      own = cost_own < cost_lt;
-      tile = b.tile;
-    }
+  if (R > 0 && pp) {
+    const int epi = (e.act_src ? S2T_ZL_EPI_ACT_SRC : 0) | (e.resid2 ? S2T_ZL_EPI_RESID2 : 0) |
+                    (e.resid_b ? S2T_ZL_EPI_RESID_B : 0) | (e.act2 == 1 || e.act2 == 2 ? S2T_ZL_EPI_ACT2_SWOOSH : 0) |
+                    (e.act2 == 3 ? S2T_ZL_EPI_ACT2_ADD : 0) | (e.bal ? S2T_ZL_EPI_BAL : 0);
+    const int choice = plan_choose(plan_mode(mode), R, L.N, L.K, epi, c.c.x3p_margin, &tile);
+    if (choice < 0 && !c.dry) return fail(-5, "lt_matmul: shape bucket not timed yet");
+    own = choice != 0;               // (a dry run over an untimed bucket sizes the workspace for our kernel)
   }
-  if (e.bal && !c.c.bal_epi) own = false;          // (A/B switch: plain product + the two-pass update)
   float* bstats = e.bal_stats ? e.bal_stats : ((e.bal && own) ? c.ar.alloc(4096) : nullptr);   // sums | squares | a | b
   if (own && !c.dry && e.bal) {
     if (cols <= 1024) {
@@ -329,7 +338,7 @@ int lt_matmul(Ctx& c, int mode, const float* x, long ldx, long R, const S2tZlLin
 int bmm(Ctx& c, int mode, const float* a, const float* b, float* out, int n, int M, int N, int K) {
   if (c.dry) return 0;
   const int mn = M < N ? (M < K ? M : K) : (N < K ? N : K);
-  if (c.c.bmm_own && mode != 2 && K % 4 == 0 && (mode == 0 || N % 4 == 0) && mn >= 4) {
+  if (mode != 2 && K % 4 == 0 && (mode == 0 || N % 4 == 0) && mn >= 4) {
     const long lda = K, sA = (long)M * K;
     const long ldb = mode == 0 ? K : N, sB = (long)N * K;
     const int rc = s2t_gemm_f32_batched(mode, a, lda, sA, b, ldb, sB, out, N, (long)M * N, M, N, K, n, (void*)c.st);
@@ -359,7 +368,7 @@ int whiten_stats(Ctx& c, WStat& s, const float* x, long ldx, long R, int C, int 
   // stream (they depend on x only): backward's chain is the penalty product on the pre-split-weight kernel
   // with the two norms in its epilogue, and the combining pass
   const S2tZlWhScratch* sc0 = wh_scratch(c, C);
-  const bool fused = c.c.whiten_x3p == 2 && c.c.x3p_on && C >= 16 && (C & 7) == 0 && s.cg <= 1024 &&
+  const bool fused = c.c.whiten_x3p == 2 && C >= 16 && (C & 7) == 0 && s.cg <= 1024 &&
                      R >= 4 && R * C * 4 < 0x7FFFFF00L && R * ldx * 4 < 0x7FFFFF00L && sc0 && sc0->tab;
   s.pieces = nullptr;
   if (fused) {
@@ -836,7 +845,7 @@ int conv_bwd(Ctx& c, int i, int d0, const float* x_in, const float* g, const flo
   float* du = c.ar.alloc(R * 2 * D);
   const long wsn = s2t_zipconv_bwd_workspace_floats(T, B, D, m.K);
   float* ws = c.ar.alloc(wsn);
-  if (c.c.conv_w_side && c.side && !c.c.conv_fused) {
+  if (c.c.conv_w_side && c.side) {
     RUN(s2t_zipconv_bwd_data(sv.u, 2 * D, D, c.c.k8, T, B, D, m.K, sv.chunk, m.wc, m.wk, m.bk, m.scale, dy, du,
                              (void*)c.st));
     if (!c.dry)
@@ -1041,6 +1050,11 @@ int s2t_zl_plan_clear(void) {
   return 0;
 }
 long s2t_zl_plan_count(void) { return (long)g_plans.size(); }
+int s2t_zl_plan_choose(int mode, long rows, int N, int K, int epilogue_bits, float margin, int* tile) {
+  if (!tile) return -1;
+  std::lock_guard<std::mutex> lock(g_mu);
+  return plan_choose(mode, rows, N, K, epilogue_bits, margin, tile);
+}
 
 // floats of workspace the forward (backward = 0) or backward (1) pass of this call may need: a dry
 // run of the same code with every decision of `call` as given (pass all ones for the bound) and
@@ -1061,11 +1075,6 @@ long s2t_zip_layer_ws_floats(const S2tZipLayerDesc* desc, const S2tZipLayerCall*
 // 0 = shapes timed (or not needed), 1 = some product of this call has no plan entry yet
 int s2t_zip_layer_plans_missing(const S2tZipLayerDesc* desc, int T, int B) {
   if (!desc) return -1;
-  S2tZipLayerCall call;
-  memset(&call, 0, sizeof(call));
-  call.x3p_on = 1;
-  State tmp;
-  Ctx c{*desc, call, tmp, Arena{nullptr, 0, 0}, nullptr, nullptr, true, (long)T * B};
   const long R = (long)T * B;
   const S2tZlLin* both[] = {&desc->attn_in,   &desc->ff[0].in, &desc->ff[0].out, &desc->ff[1].in, &desc->ff[1].out,
                             &desc->ff[2].in,  &desc->ff[2].out, &desc->na.in,    &desc->na.out,   &desc->sa[0].in,
@@ -1073,8 +1082,8 @@ int s2t_zip_layer_plans_missing(const S2tZipLayerDesc* desc, int T, int B) {
                             &desc->cv[1].in,  &desc->cv[1].out};
   std::lock_guard<std::mutex> lock(g_mu);
   for (const S2tZlLin* L : both)
-    if (plan_missing(c, 0, R, *L) || plan_missing(c, 1, R, *L)) return 1;
-  if (plan_missing(c, 0, 2 * T - 1, desc->attn_pos)) return 1;
+    if (plan_missing(0, R, *L) || plan_missing(1, R, *L)) return 1;
+  if (plan_missing(0, 2 * T - 1, desc->attn_pos)) return 1;
   return 0;
 }
 
@@ -1093,7 +1102,7 @@ int s2t_zip_layer_fwd(const S2tZipLayerDesc* desc, const S2tZipLayerCall* call, 
     Ctx dr{*desc, *call, tmp, Arena{nullptr, 0, 0}, nullptr, nullptr, true, c.R};
     if (layer_fwd(dr) != 0 || dr.ar.off > ws_floats) return fail(-4, "s2t_zip_layer_fwd: workspace too small");
   }
-  if (s2t_zip_layer_plans_missing(desc, call->T, call->B) == 1 && call->x3p_on)
+  if (s2t_zip_layer_plans_missing(desc, call->T, call->B) == 1)
     return fail(-5, "s2t_zip_layer_fwd: a product of this shape has not been timed yet");
   return layer_fwd(c);
 }

@@ -11,7 +11,7 @@ import torch
 from . import _native as N
 
 _NEG_INF = float("-inf")
-CTC_MAX_LABELS = 1023     # == S2T_CTC_MAX_LABELS (include/s2t_mi355.h)
+CTC_MAX_LABELS = N.const("S2T_CTC_MAX_LABELS")
 RNNT_MAX_ROWS = 1024      # S+1 lattice rows: one thread each in one workgroup (csrc/rnnt.hip mi_*_kernel)
 RNNT_MAX_JOINER_DIM = 1024  # fused pruned joiner: 16 classes per lane of one wave (csrc/rnnt.hip)
 

@@ -28,15 +28,10 @@ import math
 import torch
 from torch.optim import Adam, AdamW
 
+from speech2text_amd import _native as N
 from speech2text_amd.flat import store_of
 
-
-class _AdamGroup(ctypes.Structure):
-    """Mirror of S2tAdamGroup (include/s2t_mi355.h)."""
-    _fields_ = [("chunk_hi", ctypes.c_int), ("lr", ctypes.c_float), ("beta1", ctypes.c_float),
-                ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
-                ("weight_decay", ctypes.c_float), ("bias_correction1", ctypes.c_float),
-                ("sqrt_bias_correction2", ctypes.c_float), ("decoupled", ctypes.c_int)]
+_AdamGroup = N.struct("S2tAdamGroup")
 
 
 class _FlatMixin:
@@ -60,7 +55,7 @@ class _FlatMixin:
         except RuntimeError:
             st = None
         self._host_store = st
-        if st is None or not st.flat_p.is_cuda or len(groups) > 8:
+        if st is None or not st.flat_p.is_cuda or len(groups) > N.const("S2T_ADAM_MAX_GROUPS"):
             self._flat = False
             return
         for g in self.param_groups:
@@ -107,7 +102,6 @@ class _FlatMixin:
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        from speech2text_amd import _native as N
         f = self._flat
         st = f["store"]
         st.check_views()

@@ -20,9 +20,7 @@ import torch
 from . import _native as N
 from . import flat
 
-_DESC = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("N", "<i4"), ("K", "<i4"), ("ld", "<i4"),
-                  ("transposed", "<i4"), ("blk_begin", "<u4"), ("pad", "<i4")])
-assert _DESC.itemsize == 40
+_DESC = np.dtype(N.struct("S2tPlaneDesc"))
 
 SPLITS = [0]         # refresh launches so far (tests)
 

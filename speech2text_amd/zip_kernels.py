@@ -1358,12 +1358,7 @@ def batched_matmul(mode, a, b, own_tn=False):
     return torch.bmm(a.transpose(1, 2), b)
 
 
-class TnProblem(ctypes.Structure):
-    """Mirror of S2tTnProblem (include/s2t_mi355.h)."""
-    _fields_ = [("A", ctypes.c_void_p), ("lda", ctypes.c_long), ("B", ctypes.c_void_p),
-                ("ldb", ctypes.c_long), ("C", ctypes.c_void_p), ("ldc", ctypes.c_long),
-                ("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int),
-                ("colsum", ctypes.c_void_p), ("alpha", ctypes.c_float)]
+TnProblem = N.struct("S2tTnProblem")
 
 
 def wgrad_group(items):
@@ -1516,6 +1511,8 @@ _X3P_TILES = (222, 321, 312, 411)
 # at 16-deep stages (2000 +) and at 32-deep barrier intervals (2200 +)
 _X3P_TILES2 = (222, 321, 312, 411, 2022, 2021, 2012, 2222, 2221, 2212, 2211)
 PLAN_STATS = {"timed": 0}
+_EPI_ACT_SRC, _EPI_RESID2, _EPI_RESID_B, _EPI_ACT2_SWOOSH, _EPI_ACT2_ADD, _EPI_BAL = (
+    N.const("S2T_ZL_EPI_" + n) for n in ("ACT_SRC", "RESID2", "RESID_B", "ACT2_SWOOSH", "ACT2_ADD", "BAL"))
 
 
 CLS_F, CLS_D, CLS_W, CLS_S = 0, 1, 2, 3     # classes of product (include/s2t_mi355.h s2t_gemm_arith_of)
@@ -1649,18 +1646,17 @@ def lt_matmul(mode, x2, w2, bias=None, resid2=None, act_src=None, act_kind=None,
             # the native layer executor (csrc/zip_layer.hip) decides from the same numbers
             N.lib().s2t_zl_plan_put(base[0], base[1], base[2], base[3], float(b[0]),
                                     -1.0 if b[1] is None else float(b[1]), int(b[2]))
-        t_lib, t_own, tile = b
-        if t_own is None:
-            plan = ("lt", 0)
-        else:
-            rc = float(x2.shape[0]) * (w2.shape[0] if mode == 0 else w2.shape[1])
-            pass_ms = 4.0e-3 + 12.0 * rc / 3.0e9                 # one elementwise pass: 2 reads + 1 write at 3 TB/s
-            n_pass = ((act_src is not None) + (act_src is not None and resid2 is not None)
-                      + (resid_b is not None) + (act2 in ("swoosh_l", "swoosh_r")) + (bal is not None))
-            n_ops = (act_src is not None) + (resid_b is not None) + (act2 is not None) + (bal is not None)
-            cost_lt = t_lib * (1.0 if fused else X3P["margin"]) + n_pass * pass_ms
-            cost_own = t_own + n_ops * 4.0 * rc / 3.0e9          # each extra operand / output: one more stream
-            plan = ("x3p", tile) if cost_own < cost_lt else ("lt", 0)
+        t_lib, t_own = b[:2]
+        # the rule itself is the library's (s2t_zl_plan_choose): the native executor asks the same function
+        epi = ((act_src is not None) * _EPI_ACT_SRC | (resid2 is not None) * _EPI_RESID2
+               | (resid_b is not None) * _EPI_RESID_B | (act2 in ("swoosh_l", "swoosh_r")) * _EPI_ACT2_SWOOSH
+               | (act2 == "add") * _EPI_ACT2_ADD | (bal is not None) * _EPI_BAL)
+        tile = ctypes.c_int(0)
+        own = N.lib().s2t_zl_plan_choose(base[0], x2.shape[0], base[2], base[3], epi, float(X3P["margin"]),
+                                         ctypes.byref(tile))
+        if own < 0:
+            raise RuntimeError("s2t_zl_plan_choose: the bucket just timed has no entry")
+        plan = ("x3p", tile.value) if own else ("lt", 0)
         if os.environ.get("S2T_PLAN_DUMP"):
             print(f"[s2t plan] mode {mode} R {x2.shape[0]} N {w2.shape[0]} K {w2.shape[1]} "
                   f"bias {bias is not None} resid {resid2 is not None} fused {fused}: {plan} "
@@ -2057,10 +2053,7 @@ def _conv3x3_s12_dgrad_map(g, wd, H, W):
     return dx
 
 
-class RowMap(ctypes.Structure):
-    """Mirror of S2tRowMap (include/s2t_mi355.h): row r = (b, i, j) -> base + b sb + i sh + j sw floats."""
-    _fields_ = [("hw", ctypes.c_int), ("w", ctypes.c_int), ("sb", ctypes.c_long), ("sh", ctypes.c_long),
-                ("sw", ctypes.c_long), ("base", ctypes.c_long)]
+RowMap = N.struct("S2tRowMap")      # row r = (b, i, j) -> base + b sb + i sh + j sw floats
 
 
 _CONV_MAP_TILE = 22

@@ -211,11 +211,7 @@ def _balancer_bwd(mod, x, g, inplace=False, swoosh_l=None):
     return zk.balancer_backward(x, g, *mod.cfg(2), inplace=inplace, swoosh_l=swoosh_l)
 
 
-class _Commit(ctypes.Structure):
-    """Mirror of S2tCommit (include/s2t_mi355.h)."""
-    _fields_ = [("x", ctypes.c_void_p), ("d", ctypes.c_void_p), ("grad", ctypes.c_void_p),
-                ("lo", ctypes.c_float), ("hi", ctypes.c_float), ("limit", ctypes.c_int),
-                ("n", ctypes.c_long)]
+_Commit = N.struct("S2tCommit")
 
 
 def _commit(items):

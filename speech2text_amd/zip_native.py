@@ -22,76 +22,8 @@ from . import zip_kernels as zk
 ENABLED = os.environ.get("S2T_LAYER_NATIVE", "1") == "1"
 CALLS = [0, 0]           # forward / backward calls served natively (tests assert the path really ran)
 _F32 = torch.float32
-NDEC, NWHITEN = 32, 11
-
-c_fp = ctypes.c_void_p
-
-
-class Lin(ctypes.Structure):
-    _fields_ = [("w", c_fp), ("b", c_fp), ("gw", c_fp), ("gb", c_fp), ("pf", c_fp), ("pb", c_fp),
-                ("N", ctypes.c_int), ("K", ctypes.c_int)]
-
-
-class Bal(ctypes.Structure):
-    _fields_ = [("min_mean", ctypes.c_float), ("max_mean", ctypes.c_float), ("min_rms", ctypes.c_float),
-                ("max_rms", ctypes.c_float), ("grad_scale", ctypes.c_float)]
-
-
-class Wh(ctypes.Structure):
-    _fields_ = [("groups", ctypes.c_int), ("limit", ctypes.c_float), ("grad_scale", ctypes.c_float)]
-
-
-class Ff(ctypes.Structure):
-    _fields_ = [("in_", Lin), ("out", Lin), ("hidden", Bal), ("out_wh", Wh), ("post", Bal)]
-
-
-class Sa(ctypes.Structure):
-    _fields_ = [("in_", Lin), ("out", Lin), ("wh", Wh)]
-
-
-class Conv(ctypes.Structure):
-    _fields_ = [("in_", Lin), ("out", Lin), ("bal1", Bal), ("bal2", Bal), ("wh", Wh),
-                ("K", ctypes.c_int), ("causal", ctypes.c_int),
-                ("wc", c_fp), ("bc", c_fp), ("wk", c_fp), ("bk", c_fp), ("scale", c_fp),
-                ("gwc", c_fp), ("gbc", c_fp), ("gwk", c_fp), ("gbk", c_fp), ("gscale", c_fp)]
-
-
-class Na(ctypes.Structure):
-    _fields_ = [("in_", Lin), ("out", Lin), ("bal", Bal), ("wh1", Wh), ("wh2", Wh), ("post", Bal)]
-
-
-class Param(ctypes.Structure):
-    _fields_ = [("x", c_fp), ("grad", c_fp), ("lo", ctypes.c_float), ("hi", ctypes.c_float)]
-
-
-class Desc(ctypes.Structure):
-    """Mirror of S2tZipLayerDesc (include/s2t_mi355.h)."""
-    _fields_ = [("D", ctypes.c_int), ("H", ctypes.c_int), ("qd", ctypes.c_int), ("pd", ctypes.c_int),
-                ("pos_dim", ctypes.c_int),
-                ("attn_in", Lin), ("attn_pos", Lin), ("bal_keys", Bal), ("wh_keys", Wh),
-                ("ff", Ff * 3), ("na", Na), ("sa", Sa * 2), ("cv", Conv * 2),
-                ("byp_mid", Param), ("byp", Param), ("norm_bias", Param), ("norm_ls", Param),
-                ("bal1", Bal), ("bal2", Bal), ("wh_out", Wh)]
-
-
-class WhScratch(ctypes.Structure):
-    _fields_ = [("C", ctypes.c_int), ("acc", c_fp), ("ws", c_fp), ("tab", c_fp), ("buf", c_fp),
-                ("blocks", ctypes.c_int)]
-
-
-class Call(ctypes.Structure):
-    """Mirror of S2tZipLayerCall."""
-    _fields_ = [("T", ctypes.c_int), ("B", ctypes.c_int), ("chunk_size", ctypes.c_int),
-                ("x0", c_fp), ("pos", c_fp), ("k8", c_fp), ("a8", c_fp), ("fm", c_fp),
-                ("out", c_fp), ("g", c_fp), ("gx", c_fp),
-                ("dec", ctypes.c_int * NDEC),
-                ("bal_ws", c_fp), ("layer_acc", c_fp), ("wh", WhScratch * 8), ("nwh", ctypes.c_int),
-                ("lt_ws", c_fp), ("lt_ws_bytes", ctypes.c_long),
-                ("x3p_on", ctypes.c_int), ("x3p_tile", ctypes.c_int), ("x3p_margin", ctypes.c_float),
-                ("whiten_x3p", ctypes.c_int),
-                ("conv_w_side", ctypes.c_int), ("conv_fused", ctypes.c_int), ("stats_side", ctypes.c_int),
-                ("wgrad_side", ctypes.c_int), ("bmm_own", ctypes.c_int), ("bal_epi", ctypes.c_int),
-                ("whiten_sq", ctypes.c_int), ("bal_fwd_side", ctypes.c_int), ("whiten_fwd_pg", ctypes.c_int)]
+NDEC, NWHITEN = N.const("S2T_ZL_NDEC"), N.const("S2T_ZL_NWHITEN")
+Desc, Call = N.struct("S2tZipLayerDesc"), N.struct("S2tZipLayerCall")    # laid out from include/s2t_mi355.h
 
 
 def _dp(t):
@@ -342,15 +274,12 @@ def _fill_call(L, T, B, D, chunk_size, x0, pos2, a8, k8, fm, dec, dev):
     c.nwh = len(cs)
     ws = zk._lt_workspace(dev)
     c.lt_ws, c.lt_ws_bytes = ws.data_ptr(), ws.numel()
-    c.x3p_on, c.x3p_tile, c.x3p_margin = 1, int(zk.X3P["tile"]), float(zk.X3P["margin"])
+    c.x3p_tile, c.x3p_margin = int(zk.X3P["tile"]), float(zk.X3P["margin"])
     c.whiten_x3p = int(zk._WHITEN_X3P)
     side = zk._Side.enabled
     c.conv_w_side = int(side)
-    c.conv_fused = 0                      # (the one-kernel conv backward: removed in round 5)
     c.stats_side = int(side)
     c.wgrad_side = int(side)
-    c.bmm_own = 1
-    c.bal_epi = 1
     c.whiten_sq = int(zk._WHITEN_SQ)
     c.bal_fwd_side = int(side)       # Balancer column statistics in forward, side stream
     c.whiten_fwd_pg = int(zk._WHITEN_FWD_PG)
