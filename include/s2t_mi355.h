@@ -482,6 +482,76 @@ int s2t_rnnt_beam_stateless(const float* am, const long* lengths, const float* e
                             void* workspace, long* tokens, long* frames, long* out_len,
                             float* score, void* stream);
 
+/* ---- RNN-T greedy and beam search with the layer-norm LSTM predictor (model/decoding.py:196-425 over
+ * model/predictor/lstm_predictor.py:28-109 and model/joiner/joiner.py:186-207), joiner with or
+ * without output projection (csrc/decode_lstm.hip).  The search runs in LOCKSTEP over the batch: a
+ * "round" makes one lattice move for every live row (greedy: one row per utterance; beam: beam_size
+ * rows per utterance), as a handful of launches ordered by the stream alone.  Per round the rows
+ * that emitted a symbol take one predictor step -- LN(embedding[token]); per layer the raw gates
+ * x . x2g^T (+ bias) + h . p2g^T tiled over 16 rows x 16 gate rows, so that a weight matrix is read
+ * once per round and row tile, then g_norm, i / f / cell / o, c_norm and h per row; LN(linear(h)) and
+ * pre_proj give the row's lm vector (V) -- and every live row takes z = act(am[b, t_b] + lm[row]),
+ * through the two out-projection Linears when inner > 0, and decides on it.  A device-side count of
+ * the rows that emitted lets every launch of a round without one return at once.  A row's result
+ * does not depend on the rows that share its launch.  Blank is class 0; the initial state is zero
+ * state + one predictor step on blank.
+ * S2tRnntLstmDesc: the modules' shapes and parameter addresses.  layer_norm = 0: x2g has a bias and
+ * the four norm pointers of a layer are NULL; layer_norm = 1: x2g_b is NULL.  inner = 0: no
+ * output projection (out1_* / out2_* unused).  act: 0 relu, 1 tanh.
+ * Limits (else -1, before any launch): E, H <= S2T_RNNT_LSTM_MAX_HIDDEN and H % 4 == 0; layers <=
+ * S2T_RNNT_LSTM_MAX_LAYERS; V, D, inner <= S2T_RNNT_LSTM_MAX_VOCAB; beam_size and min(cutoff_top_k,
+ * V) in 1..S2T_RNNT_LSTM_MAX_BEAM. */
+#define S2T_RNNT_LSTM_MAX_HIDDEN 1024
+#define S2T_RNNT_LSTM_MAX_LAYERS 8
+#define S2T_RNNT_LSTM_MAX_VOCAB 8192
+#define S2T_RNNT_LSTM_MAX_BEAM 16
+typedef struct S2tLstmLayer {
+  const float* x2g_w;              /* (4H, E or H) */
+  const float* x2g_b;              /* (4H) or NULL */
+  const float* p2g_w;              /* (4H, H) */
+  const float *g_gamma, *g_beta;   /* (4H) or NULL */
+  const float *c_gamma, *c_beta;   /* (H) or NULL */
+} S2tLstmLayer;
+typedef struct S2tRnntLstmDesc {
+  int V, E, H, D, inner, num_layers, layer_norm, act;
+  float in_eps, lstm_eps, out_eps; /* input_layer_norm, g_norm / c_norm, output_layer_norm */
+  int pad_;
+  const float* emb;                /* (num_symbols, E) */
+  const float *in_gamma, *in_beta; /* (E) */
+  S2tLstmLayer layers[S2T_RNNT_LSTM_MAX_LAYERS];
+  const float *lin_w, *lin_b;      /* predictor linear (D, H), (D) */
+  const float *out_gamma, *out_beta;   /* (D) */
+  const float *pre_w, *pre_b;      /* joiner pre_proj (V, D), (V) */
+  const float *out1_w, *out1_b;    /* out-projection (inner, V), (inner) */
+  const float *out2_w, *out2_b;    /* (V, inner), (V) */
+} S2tRnntLstmDesc;
+/* bytes of device `workspace` (256-byte aligned) of the three calls below for R = B * max(1,
+ * beam_size) rows; a pure host function, 0 for a shape outside the limits. */
+long s2t_rnnt_lstm_workspace_bytes(const S2tRnntLstmDesc* desc, int B, int T, int beam_size);
+/* One predictor step for R rows.  Row r with emit[r] != 0 steps from the state of row parent[r]
+ * (parent NULL: r itself) of h_in / c_in [layers][R][H] on tokens[r] and writes its new state to
+ * h_out / c_out and its lm vector to lm_out [R][V]; a row with emit[r] == 0 receives the state and
+ * the lm_in row of parent[r] unchanged, bit for bit.  In and out buffers are either the same (then
+ * parent must be NULL) or disjoint. */
+int s2t_lstm_pred_step(const S2tRnntLstmDesc* desc, int R, const int* tokens, const int* emit,
+                       const int* parent, const float* h_in, const float* c_in, const float* lm_in,
+                       float* h_out, float* c_out, float* lm_out, void* workspace, void* stream);
+/* am [B][T][V] = enc_proj(encoder_out); tokens [B][max_out] with max_out = T (max_token_step + 1),
+ * zeroed by the caller; out_len [B].  Per row the reference's walk: blank, or more than
+ * max_token_step symbols on this frame, moves to the next frame; anything else is emitted and fed
+ * to the predictor.  Rounds are enqueued in blocks of 32 with ONE host read (a stream
+ * synchronisation) of the device's count of unfinished rows per block, at most T (max_token_step +
+ * 2) rounds; finished rows are inert. */
+int s2t_rnnt_greedy_lstm(const S2tRnntLstmDesc* desc, const float* am, const long* lengths, int B,
+                         int T, int max_token_step, void* workspace, long* tokens, long* out_len,
+                         void* stream);
+/* The search of s2t_rnnt_beam_stateless (same orders, same outputs) over this predictor and joiner:
+ * exactly T rounds, the survivors gather their LSTM state and lm row from their parent's row through
+ * two alternating state buffers; no host synchronisation. */
+int s2t_rnnt_beam_lstm(const S2tRnntLstmDesc* desc, const float* am, const long* lengths, int B,
+                       int T, int beam_size, int cutoff_top_k, void* workspace, long* tokens,
+                       long* frames, long* out_len, float* score, void* stream);
+
 /* ---- batched on-device augmentation + collate next to the fbank kernel
  * (dataset/frontend/data_augmentation.py:13-56 AddNoise, :59-118 MixFeats, :150-196 SpecAugment;
  * dataset/utils.py:182-202 batch()).  Random decisions are made on the host as the reference

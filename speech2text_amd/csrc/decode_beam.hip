@@ -21,6 +21,7 @@
 // After the last frame the best beam (position 0) is traced back through the records.
 // lm [beam_size][V] lives in LDS when it fits and in the workspace (L2 resident) when it does not.
 #include "common.h"
+#include "decode_common.h"
 
 namespace {
 
@@ -35,28 +36,7 @@ constexpr int kRegs = 8;           // classes per lane held in registers (V <= 5
 constexpr int kTraceFrames = 64;   // frames of records staged in LDS per trace-back step
 constexpr size_t kLdsBudget = 60 * 1024;
 
-struct Top {
-  float v;
-  int i;
-};
-__device__ __forceinline__ Top better(Top a, Top b) {   // first index wins ties
-  if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
-  return a;
-}
-__device__ __forceinline__ Top wave_top(Top a) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    Top b;
-    b.v = __shfl_xor(a.v, o, 64);
-    b.i = __shfl_xor(a.i, o, 64);
-    a = better(a, b);
-  }
-  return a;
-}
-// (v, i) comes strictly after (pv, pi) in the order (value descending, index ascending)
-__device__ __forceinline__ bool after(float v, int i, float pv, int pi) {
-  return v < pv || (v == pv && i > pi);
-}
+using namespace s2t_dec;           // Top, better, wave_top, after, activate (decode_common.h)
 
 struct BeamArgs {
   const float* am;        // [B][T][V]  = enc_proj(encoder_out), bias included
@@ -75,10 +55,6 @@ struct BeamArgs {
   long* out_len;          // [B]
   float* score;           // [B]
 };
-
-__device__ __forceinline__ float activate(float v, int act) {
-  return act == 0 ? fmaxf(v, 0.f) : tanhf(v);
-}
 
 // y[g][r] = w[r] . x[g] + bias[r] for the ng <= kGroup vectors x[g] (LDS, [g][cols]): a wave per
 // row, kRows rows in flight per wave so that their loads overlap (the walk is latency-bound: one

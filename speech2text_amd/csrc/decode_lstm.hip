@@ -1,0 +1,731 @@
+// RNN-T greedy and beam search (reference model/decoding.py:196-271 RnntGreedyDecoding, :295-425
+// RnntBeamDecoding) with the layer-norm LSTM predictor (model/predictor/lstm_predictor.py:28-109 ->
+// torchaudio _Predictor / _CustomLSTM) and the joiner with or without output projection
+// (model/joiner/joiner.py:186-207), for gfx950, float32 throughout.
+//
+// The reference walks one utterance and one lattice move at a time, a few dozen launches per move.
+// Here the search runs in LOCKSTEP over the batch.  A "round" is one lattice move of every live row
+// (greedy: a row per utterance; beam: beam_size rows per utterance):
+//   joint     a workgroup per row: z = act(am[b, t_b] + lm[row]) (through the two out-projection
+//             Linears when there are any) and the row's decision -- greedy: arg-max, first index on
+//             ties, and the reference's bookkeeping; beam: log-softmax, the cutoff_top_k best classes,
+//             then (a workgroup per utterance) candidate ranking, selection and trace-back records
+//             in the orders of csrc/decode_beam.hip.  Rows that emitted are counted on the device.
+//   predictor for the rows that emitted: LN(embedding[token]); per layer the raw gates
+//             x . x2g^T (+ bias) + h . p2g^T as (16 rows x 16 gate rows) tiles -- a weight matrix is
+//             read once per round and row tile, not once per row -- then g_norm, i / f / cell / o,
+//             c_norm, h per row; LN(linear(h_last)); pre_proj -> the row's lm vector.
+// Launches are ordered by the stream alone (csrc/lstm_step.hip): no grid-wide barrier, no cooperative
+// launch, no flag.  Every predictor launch reads the round's count first and returns on zero, so a
+// round in which no row emitted costs its launches and nothing else.  Greedy rounds are enqueued in
+// blocks of 32 with one host read of the "rows still live" counter per block; a beam search is
+// exactly T rounds (at most one symbol per frame per beam) and never synchronises.
+//
+// A row's arithmetic does not depend on the rows that share its launch: tiles sit at fixed row
+// positions, every (row, output) sum is taken per lane over k = lane, lane + 64, ... and folded by the
+// same butterfly, and rows beyond R read clamped addresses and are never stored.
+#include "common.h"
+#include "decode_common.h"
+#include "../../include/s2t_mi355.h"
+
+namespace {
+
+using namespace s2t_dec;           // Top, better, wave_top, after, activate
+
+constexpr int kTileRows = 16;      // rows of a tile
+constexpr int kTileOuts = 4;       // outputs of a wave: 4 x 16 sums, one per lane after the fold
+constexpr int kTileWaves = 4;      // waves of a tile workgroup: 16 outputs
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kMaxBeam = S2T_RNNT_LSTM_MAX_BEAM;
+constexpr int kMaxCand = kMaxBeam * kMaxBeam;
+constexpr int kRoundBlock = 32;    // greedy rounds between two host reads of the live counter
+static_assert(kMaxCand <= kThreads, "a thread per candidate");
+static_assert(kMaxBeam <= 16, "a record keeps the parent position in 4 bits");
+
+__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
+
+// ------------------------------------------------------------------ tiled products
+// One butterfly step over lane bit HALF: the two lanes split the sums between them (the upper lane
+// keeps the upper half), so after the steps 32, 16, ..., 1 lane l holds the complete sum number l.
+// The pairs added are wave_sum's, whatever the number of the sum.
+template <int HALF>
+__device__ __forceinline__ void fold_step(float (&v)[64]) {
+  const bool up = (threadIdx.x & HALF) != 0;
+#pragma unroll
+  for (int i = 0; i < HALF; ++i) {
+    const float keep = up ? v[i + HALF] : v[i], send = up ? v[i] : v[i + HALF];
+    v[i] = keep + __shfl_xor(send, HALF, 64);
+  }
+}
+
+// acc[j * 16 + r] += sum_k w[n0 + j][k] x[rows[r]][k]: a lane takes k = lane, lane + 64, ...; loads
+// are unconditional on clamped addresses, a k beyond K multiplies by a zeroed weight.
+__device__ __forceinline__ void tile_accumulate(float (&acc)[64], const float* __restrict__ x, long ld,
+                                                const int* rows, const float* __restrict__ w, int K,
+                                                int n0, int N) {
+  const int lane = threadIdx.x & 63;
+  const float* wr[kTileOuts];
+#pragma unroll
+  for (int j = 0; j < kTileOuts; ++j) wr[j] = w + (long)min(n0 + j, N - 1) * K;
+  const float* xr[kTileRows];
+#pragma unroll
+  for (int r = 0; r < kTileRows; ++r) xr[r] = x + (long)rows[r] * ld;
+  for (int k0 = 0; k0 < K; k0 += 64) {
+    const int k = k0 + lane, kk = min(k, K - 1);
+    float wv[kTileOuts], xv[kTileRows];
+#pragma unroll
+    for (int j = 0; j < kTileOuts; ++j) wv[j] = wr[j][kk];
+#pragma unroll
+    for (int r = 0; r < kTileRows; ++r) xv[r] = xr[r][kk];
+#pragma unroll
+    for (int j = 0; j < kTileOuts; ++j) {
+      const float wj = k < K ? wv[j] : 0.f;
+#pragma unroll
+      for (int r = 0; r < kTileRows; ++r) acc[j * kTileRows + r] = fmaf(wj, xv[r], acc[j * kTileRows + r]);
+    }
+  }
+}
+
+struct TileArgs {
+  const float* x1;      // [R][ld1], row r
+  long ld1;
+  const float* w1;      // [N][K1]
+  int K1;
+  const float* x2;      // [R][ld2], row parent[r] (parent NULL: r), or NULL
+  long ld2;
+  const float* w2;      // [N][K2]
+  int K2;
+  const float* bias;    // [N] or NULL
+  int N, R;
+  const int* emit;      // [R]
+  const int* parent;    // [R] or NULL
+  const int* count;     // rows that emit this round
+  float* y;             // [R][ldy], written for emitting rows
+  long ldy;
+};
+
+// grid (ceil(N / 16), ceil(R / 16)): y[r][n] = x1[r] . w1[n] + x2[parent r] . w2[n] + bias[n]
+__global__ __launch_bounds__(64 * kTileWaves) void tile_linear_kernel(TileArgs a) {
+  if (*a.count == 0) return;
+  __shared__ int s_rows[2][kTileRows];
+  __shared__ int s_any;
+  const int tid = threadIdx.x, row0 = blockIdx.y * kTileRows;
+  if (tid < kTileRows) {
+    const int r = min(row0 + tid, a.R - 1);
+    s_rows[0][tid] = r;
+    s_rows[1][tid] = a.parent ? a.parent[r] : r;
+  }
+  if (tid == 64) {
+    int any = 0;
+    for (int r = row0; r < min(row0 + kTileRows, a.R); ++r) any |= a.emit[r];
+    s_any = any;
+  }
+  __syncthreads();
+  if (!s_any) return;
+  const int n0 = (blockIdx.x * kTileWaves + (tid >> 6)) * kTileOuts;
+  if (n0 >= a.N) return;                                   // (no barrier below)
+  float acc[64];
+#pragma unroll
+  for (int i = 0; i < 64; ++i) acc[i] = 0.f;
+  tile_accumulate(acc, a.x1, a.ld1, s_rows[0], a.w1, a.K1, n0, a.N);
+  if (a.x2) tile_accumulate(acc, a.x2, a.ld2, s_rows[1], a.w2, a.K2, n0, a.N);
+  fold_step<32>(acc);
+  fold_step<16>(acc);
+  fold_step<8>(acc);
+  fold_step<4>(acc);
+  fold_step<2>(acc);
+  fold_step<1>(acc);
+  const int lane = tid & 63, n = n0 + (lane >> 4), row = row0 + (lane & 15);
+  if (n < a.N && row < a.R && a.emit[row]) a.y[row * a.ldy + n] = acc[0] + (a.bias ? a.bias[n] : 0.f);
+}
+
+// ------------------------------------------------------------------ per-row kernels of a predictor step
+// LayerNorm of the n values v[0..n) (LDS) in place, two passes; ends with a barrier.
+__device__ __forceinline__ void layer_norm_lds(float* v, int n, const float* __restrict__ gamma,
+                                               const float* __restrict__ beta, float eps, float* scratch) {
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += kThreads) s += v[i];
+  const float mean = block_sum(s, scratch) / n;
+  float q = 0.f;
+  for (int i = threadIdx.x; i < n; i += kThreads) {
+    const float d = v[i] - mean;
+    q = fmaf(d, d, q);
+  }
+  const float rstd = 1.f / sqrtf(block_sum(q, scratch) / n + eps);
+  for (int i = threadIdx.x; i < n; i += kThreads) v[i] = (v[i] - mean) * rstd * gamma[i] + beta[i];
+  __syncthreads();
+}
+
+struct RowLnArgs {
+  const float* in;      // rows of ld floats: row index[r] (index NULL: r)
+  long ld;
+  const int* index;
+  const float *gamma, *beta;
+  float eps;
+  int n, R;
+  const int* emit;
+  const int* count;
+  int inplace;          // the state buffers are updated in place: nothing to do without an emission
+  float* out;           // [R][n]
+  // rows that do not emit receive copy_src[parent r] (n_copy floats) in copy_dst[r] (not inplace)
+  const float* copy_src;
+  float* copy_dst;
+  int n_copy;
+  const int* parent;
+};
+
+// grid R: out[r] = LN(in[index r]) for the rows that emit
+__global__ __launch_bounds__(kThreads) void row_ln_kernel(RowLnArgs a) {
+  extern __shared__ float sm[];
+  __shared__ float scratch[kWaves];
+  if (a.inplace && *a.count == 0) return;
+  const int row = blockIdx.x, tid = threadIdx.x;
+  if (!a.emit[row]) {
+    if (!a.inplace && a.copy_src) {
+      const float* s = a.copy_src + (long)(a.parent ? a.parent[row] : row) * a.n_copy;
+      float* d = a.copy_dst + (long)row * a.n_copy;
+      for (int i = tid; i < a.n_copy; i += kThreads) d[i] = s[i];
+    }
+    return;
+  }
+  const float* x = a.in + (long)(a.index ? a.index[row] : row) * a.ld;
+  for (int i = tid; i < a.n; i += kThreads) sm[i] = x[i];
+  __syncthreads();
+  layer_norm_lds(sm, a.n, a.gamma, a.beta, a.eps, scratch);
+  for (int i = tid; i < a.n; i += kThreads) a.out[(long)row * a.n + i] = sm[i];
+}
+
+struct CellArgs {
+  const float* raw;     // [R][4H] raw gates of the rows that emit
+  const float *g_gamma, *g_beta, *c_gamma, *c_beta;   // NULL: no layer norm
+  float eps;
+  int H, R;
+  const int* emit;
+  const int* parent;
+  const int* count;
+  int inplace;
+  const float *h_src, *c_src;   // [R][H] of this layer
+  float *h_dst, *c_dst;
+};
+
+// grid R: g_norm, i / f / cell / o, c_norm, h of one layer; a row that does not emit takes its
+// parent's state as it is
+__global__ __launch_bounds__(kThreads) void cell_kernel(CellArgs a) {
+  extern __shared__ float sm[];                            // [4H] gates, [H] cell
+  __shared__ float scratch[kWaves];
+  if (a.inplace && *a.count == 0) return;
+  const int row = blockIdx.x, tid = threadIdx.x, H = a.H;
+  const long src = a.parent ? a.parent[row] : row;
+  if (!a.emit[row]) {
+    if (!a.inplace)
+      for (int i = tid; i < H; i += kThreads) {
+        a.h_dst[(long)row * H + i] = a.h_src[src * H + i];
+        a.c_dst[(long)row * H + i] = a.c_src[src * H + i];
+      }
+    return;
+  }
+  float* g = sm;
+  float* c = sm + 4 * H;
+  for (int i = tid; i < 4 * H; i += kThreads) g[i] = a.raw[(long)row * 4 * H + i];
+  __syncthreads();
+  if (a.g_gamma) layer_norm_lds(g, 4 * H, a.g_gamma, a.g_beta, a.eps, scratch);
+  for (int j = tid; j < H; j += kThreads)
+    c[j] = sigm(g[H + j]) * a.c_src[src * H + j] + sigm(g[j]) * tanhf(g[2 * H + j]);
+  __syncthreads();
+  if (a.c_gamma) layer_norm_lds(c, H, a.c_gamma, a.c_beta, a.eps, scratch);
+  for (int j = tid; j < H; j += kThreads) {
+    a.c_dst[(long)row * H + j] = c[j];
+    a.h_dst[(long)row * H + j] = sigm(g[3 * H + j]) * tanhf(c[j]);
+  }
+}
+
+// ------------------------------------------------------------------ workspace
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct Workspace {
+  float *h[2], *c[2], *lm[2];   // state [layers][R][H] twice, lm [R][V] twice
+  float *x, *raw, *lin, *dvec;  // LN(embedding) [R][E], raw gates [R][4H], linear(h) [R][D], its LN
+  float *z, *mid, *logit;       // joint: act(am + lm) [R][V], [R][inner], out-projection [R][V]
+  float* cscore;                // beam: candidates [B][kMaxCand]
+  float* score;                 // beam: [R]
+  int *ccls, *blen, *nb, *rec;  // beam: candidate classes, tokens per beam [R], live beams [B], records [B][T][beam]
+  int *emit, *token, *parent;   // [R]
+  int *t, *nts, *done;          // greedy: [R]
+  int* counts;                  // [0], [1]: rows that emit, by round parity; [2]: R; [3]: rows still live
+  size_t bytes;
+};
+
+Workspace carve(const S2tRnntLstmDesc& d, int B, int T, int beam, void* base) {
+  const size_t R = (size_t)B * (beam > 0 ? beam : 1), L = d.num_layers;
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* q = p + off;
+    off += align256(bytes);
+    return q;
+  };
+  auto f = [&](size_t n) { return reinterpret_cast<float*>(take(4 * n)); };
+  auto i = [&](size_t n) { return reinterpret_cast<int*>(take(4 * n)); };
+  Workspace w;
+  for (int s = 0; s < 2; ++s) {
+    w.h[s] = f(L * R * d.H);
+    w.c[s] = f(L * R * d.H);
+    w.lm[s] = f(R * d.V);
+  }
+  w.x = f(R * d.E);
+  w.raw = f(R * 4 * d.H);
+  w.lin = f(R * d.D);
+  w.dvec = f(R * d.D);
+  w.z = f(R * d.V);
+  w.mid = f(R * (d.inner > 0 ? d.inner : 1));
+  w.logit = f(R * d.V);
+  w.cscore = f((size_t)B * kMaxCand);
+  w.score = f(R);
+  w.ccls = i((size_t)B * kMaxCand);
+  w.blen = i(R);
+  w.nb = i(B);
+  w.rec = i(beam > 0 ? (size_t)B * T * beam : 1);
+  w.emit = i(R);
+  w.token = i(R);
+  w.parent = i(R);
+  w.t = i(R);
+  w.nts = i(R);
+  w.done = i(R);
+  w.counts = i(4);
+  w.bytes = off;
+  return w;
+}
+
+bool desc_ok(const S2tRnntLstmDesc* d) {
+  return d && d->V >= 1 && d->V <= S2T_RNNT_LSTM_MAX_VOCAB && d->D >= 1 && d->D <= S2T_RNNT_LSTM_MAX_VOCAB &&
+         d->inner >= 0 && d->inner <= S2T_RNNT_LSTM_MAX_VOCAB && d->E >= 1 &&
+         d->E <= S2T_RNNT_LSTM_MAX_HIDDEN && d->H >= 4 && d->H <= S2T_RNNT_LSTM_MAX_HIDDEN && d->H % 4 == 0 &&
+         d->num_layers >= 1 && d->num_layers <= S2T_RNNT_LSTM_MAX_LAYERS && d->act >= 0 && d->act <= 1;
+}
+
+// ------------------------------------------------------------------ one predictor step, enqueued
+// In place (src == dst, parent NULL) or from buffer `src` to buffer `dst`.
+void enqueue_pred_step(const S2tRnntLstmDesc& d, int R, const int* tokens, const int* emit,
+                       const int* parent, const int* count, const float* h_src, const float* c_src,
+                       const float* lm_src, float* h_dst, float* c_dst, float* lm_dst,
+                       const Workspace& w, hipStream_t st) {
+  const int inplace = h_src == h_dst;
+  const int row_tiles = (R + kTileRows - 1) / kTileRows;
+  constexpr int kOuts = kTileWaves * kTileOuts;
+  const size_t LRH = (size_t)R * d.H;
+  {
+    RowLnArgs a{d.emb, d.E, tokens, d.in_gamma, d.in_beta, d.in_eps, d.E, R, emit, count, inplace, w.x,
+                nullptr, nullptr, 0, parent};
+    hipLaunchKernelGGL(row_ln_kernel, dim3(R), dim3(kThreads), sizeof(float) * d.E, st, a);
+  }
+  for (int l = 0; l < d.num_layers; ++l) {
+    const S2tLstmLayer& p = d.layers[l];
+    const float* x = l ? h_dst + (l - 1) * LRH : w.x;
+    const int K = l ? d.H : d.E;
+    TileArgs t{x, K, p.x2g_w, K, h_src + l * LRH, d.H, p.p2g_w, d.H, p.x2g_b, 4 * d.H, R, emit, parent,
+               count, w.raw, 4L * d.H};
+    hipLaunchKernelGGL(tile_linear_kernel, dim3((4 * d.H + kOuts - 1) / kOuts, row_tiles),
+                       dim3(64 * kTileWaves), 0, st, t);
+    CellArgs c{w.raw, p.g_gamma, p.g_beta, p.c_gamma, p.c_beta, d.lstm_eps, d.H, R, emit, parent, count,
+               inplace, h_src + l * LRH, c_src + l * LRH, h_dst + l * LRH, c_dst + l * LRH};
+    hipLaunchKernelGGL(cell_kernel, dim3(R), dim3(kThreads), sizeof(float) * 5 * d.H, st, c);
+  }
+  {
+    TileArgs t{h_dst + (d.num_layers - 1) * LRH, d.H, d.lin_w, d.H, nullptr, 0, nullptr, 0, d.lin_b, d.D, R,
+               emit, nullptr, count, w.lin, d.D};
+    hipLaunchKernelGGL(tile_linear_kernel, dim3((d.D + kOuts - 1) / kOuts, row_tiles),
+                       dim3(64 * kTileWaves), 0, st, t);
+    RowLnArgs a{w.lin, d.D, nullptr, d.out_gamma, d.out_beta, d.out_eps, d.D, R, emit, count, inplace,
+                w.dvec, lm_src, lm_dst, d.V, parent};
+    hipLaunchKernelGGL(row_ln_kernel, dim3(R), dim3(kThreads), sizeof(float) * d.D, st, a);
+    TileArgs u{w.dvec, d.D, d.pre_w, d.D, nullptr, 0, nullptr, 0, d.pre_b, d.V, R, emit, nullptr, count,
+               lm_dst, d.V};
+    hipLaunchKernelGGL(tile_linear_kernel, dim3((d.V + kOuts - 1) / kOuts, row_tiles),
+                       dim3(64 * kTileWaves), 0, st, u);
+  }
+}
+
+__global__ void count_kernel(const int* emit, int R, int* count) {
+  __shared__ int s;
+  if (threadIdx.x == 0) s = 0;
+  __syncthreads();
+  int n = 0;
+  for (int r = threadIdx.x; r < R; r += blockDim.x) n += emit[r] != 0;
+  if (n) atomicAdd(&s, n);
+  __syncthreads();
+  if (threadIdx.x == 0) *count = s;
+}
+
+// ------------------------------------------------------------------ joint
+struct JointArgs {
+  const float* am;      // [B][T][V]
+  int T, V, inner, act;
+  const float *out1_w, *out1_b, *out2_w, *out2_b;
+  float *z, *mid, *logit;   // [R][V], [R][inner], [R][V]
+};
+
+// The joiner's output for one row, before the log-softmax: returns the row's V logits (global
+// memory, visible to the whole workgroup).  y[r] = w[r] . x + b[r] by a wave per r, a lane over
+// c = lane, lane + 64, ..., then wave_sum.
+__device__ __forceinline__ void gemv_wave(const float* __restrict__ w, const float* __restrict__ b,
+                                          const float* x, int rows, int cols, float* y) {
+  const int lane = threadIdx.x & 63;
+  for (int r = threadIdx.x >> 6; r < rows; r += kWaves) {
+    const float* wr = w + (long)r * cols;
+    float s = 0.f;
+    for (int c = lane; c < cols; c += 64) s = fmaf(wr[c], x[c], s);
+    s = wave_sum(s);
+    if (lane == 0) y[r] = s + b[r];
+  }
+}
+
+__device__ const float* joint_logits(const JointArgs& a, int row, int b, int t, const float* lm_row) {
+  const float* amt = a.am + ((long)b * a.T + t) * a.V;
+  float* z = a.z + (long)row * a.V;
+  for (int c = threadIdx.x; c < a.V; c += kThreads) z[c] = activate(amt[c] + lm_row[c], a.act);
+  __syncthreads();
+  if (a.inner <= 0) return z;
+  float* mid = a.mid + (long)row * a.inner;
+  float* out = a.logit + (long)row * a.V;
+  gemv_wave(a.out1_w, a.out1_b, z, a.inner, a.V, mid);
+  __syncthreads();
+  gemv_wave(a.out2_w, a.out2_b, mid, a.V, a.inner, out);
+  __syncthreads();
+  return out;
+}
+
+// the best (value descending, class ascending) of the classes this thread is given, over the
+// workgroup; every thread gets it.  Ends with a barrier.
+__device__ __forceinline__ Top block_top(Top mine, Top* s_top) {
+  mine = wave_top(mine);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_top[threadIdx.x >> 6] = mine;
+  __syncthreads();
+  Top best = s_top[0];
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) best = better(best, s_top[w]);
+  return best;
+}
+
+// ------------------------------------------------------------------ greedy
+struct GreedyArgs {
+  JointArgs j;
+  const long* lengths;
+  const float* lm;      // [B][V]
+  int max_token_step, max_out, parity;
+  int *t, *nts, *done, *emit, *token, *counts;
+  long* tokens;         // [B][max_out]
+  long* out_len;        // [B]
+};
+
+__global__ void greedy_init_kernel(const long* lengths, int B, int T, int* t, int* nts, int* done, int* emit,
+                                   int* token, int* counts, long* out_len) {
+  __shared__ int live;
+  if (threadIdx.x == 0) live = 0;
+  __syncthreads();
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const long n = lengths[b];
+    t[b] = 0;
+    nts[b] = 0;
+    done[b] = n <= 0;
+    emit[b] = 1;                                           // the first predictor step: blank, from zero state
+    token[b] = 0;
+    out_len[b] = 0;
+    if (n > 0) atomicAdd(&live, 1);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    counts[0] = 0;
+    counts[1] = 0;
+    counts[2] = B;
+    counts[3] = live;
+  }
+}
+
+// grid B: one lattice move of every live utterance (reference model/decoding.py:244-268)
+__global__ __launch_bounds__(kThreads) void greedy_joint_kernel(GreedyArgs a) {
+  __shared__ Top s_top[kWaves];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (b == 0 && tid == 0) a.counts[a.parity ^ 1] = 0;      // the next round's count
+  if (a.done[b]) {
+    if (tid == 0) a.emit[b] = 0;
+    return;
+  }
+  const int t = a.t[b], V = a.j.V;
+  const float* lg = joint_logits(a.j, b, b, t, a.lm + (long)b * V);
+  Top best{S2T_NEG_INF, V};
+  for (int c = tid; c < V; c += kThreads) best = better(best, Top{lg[c], c});
+  best = block_top(best, s_top);
+  if (tid == 0) {
+    const int tok = best.i < V ? best.i : 0;               // (only a NaN row leaves no class)
+    const int nts = a.nts[b];
+    if (tok == 0 || nts > a.max_token_step) {
+      long Tb = a.lengths[b];
+      if (Tb > a.j.T) Tb = a.j.T;
+      a.t[b] = t + 1;
+      a.nts[b] = 0;
+      a.emit[b] = 0;
+      if (t + 1 >= Tb) {
+        a.done[b] = 1;
+        atomicSub(&a.counts[3], 1);
+      }
+    } else {
+      const long n = a.out_len[b];
+      if (n < a.max_out) a.tokens[(long)b * a.max_out + n] = tok;
+      a.out_len[b] = n + 1;
+      a.nts[b] = nts + 1;
+      a.emit[b] = 1;
+      a.token[b] = tok;
+      atomicAdd(&a.counts[a.parity], 1);
+    }
+  }
+}
+
+// ------------------------------------------------------------------ beam
+struct BeamArgs {
+  JointArgs j;
+  const long* lengths;
+  const float* lm;      // [R][V], the buffer the round reads
+  int t, B, beam, topk, parity;
+  float *cscore, *score;
+  int *ccls, *blen, *nb, *rec, *emit, *token, *parent, *counts;
+};
+
+__global__ void beam_init_kernel(int B, int beam, float* score, int* blen, int* nb, int* emit, int* token,
+                                 int* counts) {
+  const int R = B * beam;
+  for (int r = threadIdx.x; r < R; r += blockDim.x) {
+    score[r] = 0.f;
+    blen[r] = 0;
+    emit[r] = 1;
+    token[r] = 0;
+  }
+  for (int b = threadIdx.x; b < B; b += blockDim.x) nb[b] = 1;
+  if (threadIdx.x == 0) {
+    counts[0] = 0;
+    counts[1] = 0;
+    counts[2] = R;
+    counts[3] = 0;
+  }
+}
+
+__device__ __forceinline__ long clamped_len(const long* lengths, int b, int T) {
+  const long n = lengths[b];
+  return n < 0 ? 0 : (n > T ? T : n);
+}
+
+// grid B * beam: the cutoff_top_k best classes of a live beam by (logit descending, class ascending)
+// -- log-softmax is monotone, the order is taken on the logits -- as candidates (beam score +
+// log-probability, class)
+__global__ __launch_bounds__(kThreads) void beam_expand_kernel(BeamArgs a) {
+  __shared__ Top s_top[kWaves];
+  __shared__ float scratch[kWaves];
+  const int row = blockIdx.x, b = row / a.beam, i = row - b * a.beam, tid = threadIdx.x;
+  if (a.t >= clamped_len(a.lengths, b, a.j.T) || i >= a.nb[b]) return;
+  const int V = a.j.V, K = min(a.topk, V);
+  const float* lg = joint_logits(a.j, row, b, a.t, a.lm + (long)row * V);
+  const float base = a.score[row];
+  float pv = 0.f, zmax = 0.f, lse = 0.f;
+  int pi = -1;
+  for (int r = 0; r < K; ++r) {
+    Top best{S2T_NEG_INF, V};
+    for (int c = tid; c < V; c += kThreads)
+      if (r == 0 || after(lg[c], c, pv, pi)) best = better(best, Top{lg[c], c});
+    best = block_top(best, s_top);
+    pv = best.v;
+    pi = best.i;
+    if (r == 0) {                                          // log-softmax as max, then log sum exp
+      zmax = pv;
+      float s = 0.f;
+      for (int c = tid; c < V; c += kThreads) s += expf(lg[c] - zmax);
+      lse = logf(block_sum(s, scratch));
+    }
+    if (tid == 0) {
+      const bool ok = pi < V;                              // (only a NaN input leaves a round empty)
+      a.cscore[b * kMaxCand + i * K + r] = ok ? base + ((pv - zmax) - lse) : S2T_NEG_INF;
+      a.ccls[b * kMaxCand + i * K + r] = ok ? pi : 0;
+    }
+  }
+}
+
+// grid B: rank the candidates of an utterance (score descending, then parent position, then rank
+// in the parent's top-k: the candidate index), keep the beam_size best as the new beams, one
+// (parent, class) record each; the rows' parent / emit / token for the predictor step.
+__global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
+  __shared__ float s_cscore[kMaxCand], s_score[kMaxBeam];
+  __shared__ int s_ccls[kMaxCand], s_pick[kMaxBeam], s_len[kMaxBeam];
+  const int b = blockIdx.x, tid = threadIdx.x, BS = a.beam, row0 = b * BS;
+  if (b == 0 && tid == 0) a.counts[a.parity ^ 1] = 0;
+  if (a.t >= clamped_len(a.lengths, b, a.j.T)) {           // finished: the rows keep what they have
+    if (tid < BS) {
+      a.emit[row0 + tid] = 0;
+      a.parent[row0 + tid] = row0 + tid;
+    }
+    return;
+  }
+  const int nb = a.nb[b], K = min(a.topk, a.j.V), nc = nb * K, nnb = min(nc, BS);
+  if (tid < nc) {
+    s_cscore[tid] = a.cscore[b * kMaxCand + tid];
+    s_ccls[tid] = a.ccls[b * kMaxCand + tid];
+  }
+  if (tid < nb) s_len[tid] = a.blen[row0 + tid];
+  __syncthreads();
+  if (tid < nc) {
+    const float mine = s_cscore[tid];
+    int rank = 0;
+    for (int q = 0; q < nc; ++q) {
+      const float o = s_cscore[q];
+      rank += (o > mine || (o == mine && q < tid)) ? 1 : 0;
+    }
+    if (rank < nnb) s_pick[rank] = tid;
+  }
+  __syncthreads();
+  if (tid < BS) {
+    const int row = row0 + tid;
+    if (tid < nnb) {
+      const int q = s_pick[tid], parent = q / K, cls = s_ccls[q];
+      a.score[row] = s_cscore[q];
+      a.blen[row] = s_len[parent] + (cls != 0 ? 1 : 0);
+      a.rec[((long)b * a.j.T + a.t) * BS + tid] = parent | (cls << 4);
+      a.parent[row] = row0 + parent;
+      a.emit[row] = cls != 0;
+      a.token[row] = cls;
+      if (cls != 0) atomicAdd(&a.counts[a.parity], 1);
+    } else {
+      a.parent[row] = row;
+      a.emit[row] = 0;
+    }
+  }
+  if (tid == 0) a.nb[b] = nnb;
+}
+
+// grid B: the best beam is position 0; its (parent, class) records traced back
+__global__ void beam_trace_kernel(const long* lengths, int T, int beam, const int* rec, const int* blen,
+                                  const float* score, long* tokens, long* frames, long* out_len,
+                                  float* out_score) {
+  const int b = blockIdx.x;
+  if (threadIdx.x != 0) return;
+  const long Tb = clamped_len(lengths, b, T);
+  if (Tb == 0) {                                           // no frames: no tokens, score 0
+    out_len[b] = 0;
+    out_score[b] = 0.f;
+    return;
+  }
+  int left = blen[b * beam], pos = 0;
+  out_len[b] = left;
+  out_score[b] = score[b * beam];
+  for (long t = Tb - 1; t >= 0 && left > 0; --t) {
+    const int r = rec[((long)b * T + t) * beam + pos];
+    const int cls = r >> 4;
+    pos = r & 15;
+    if (cls != 0) {
+      --left;
+      tokens[(long)b * T + left] = cls;
+      frames[(long)b * T + left] = t;
+    }
+  }
+}
+
+JointArgs joint_args(const S2tRnntLstmDesc& d, const float* am, int T, const Workspace& w) {
+  return JointArgs{am, T, d.V, d.inner, d.act, d.out1_w, d.out1_b, d.out2_w, d.out2_b, w.z, w.mid, w.logit};
+}
+
+}  // namespace
+
+extern "C" {
+
+long s2t_rnnt_lstm_workspace_bytes(const S2tRnntLstmDesc* desc, int B, int T, int beam_size) {
+  if (!desc_ok(desc) || B <= 0 || T < 0 || beam_size < 0 || beam_size > kMaxBeam) return 0;
+  return (long)carve(*desc, B, T, beam_size, nullptr).bytes;
+}
+
+int s2t_lstm_pred_step(const S2tRnntLstmDesc* desc, int R, const int* tokens, const int* emit,
+                       const int* parent, const float* h_in, const float* c_in, const float* lm_in,
+                       float* h_out, float* c_out, float* lm_out, void* workspace, void* stream) {
+  if (R <= 0) return 0;
+  if (!desc_ok(desc) || !workspace) return -1;
+  const bool same = h_in == h_out;
+  if (same != (c_in == c_out) || same != (lm_in == lm_out) || (same && parent)) return -1;
+  const Workspace w = carve(*desc, R, 0, 0, workspace);
+  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, emit, R, w.counts);
+  enqueue_pred_step(*desc, R, tokens, emit, parent, w.counts, h_in, c_in, lm_in, h_out, c_out, lm_out, w,
+                    (hipStream_t)stream);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_rnnt_greedy_lstm(const S2tRnntLstmDesc* desc, const float* am, const long* lengths, int B,
+                         int T, int max_token_step, void* workspace, long* tokens, long* out_len,
+                         void* stream) {
+  if (B <= 0) return 0;
+  if (!desc_ok(desc) || T <= 0 || max_token_step < 0 || !workspace) return -1;
+  const S2tRnntLstmDesc& d = *desc;
+  hipStream_t st = (hipStream_t)stream;
+  const Workspace w = carve(d, B, T, 0, workspace);
+  const size_t state = sizeof(float) * (size_t)d.num_layers * B * d.H;
+  hipError_t e = hipMemsetAsync(w.h[0], 0, state, st);
+  if (e == hipSuccess) e = hipMemsetAsync(w.c[0], 0, state, st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(greedy_init_kernel, dim3(1), dim3(kThreads), 0, st, lengths, B, T, w.t, w.nts, w.done,
+                     w.emit, w.token, w.counts, out_len);
+  enqueue_pred_step(d, B, w.token, w.emit, nullptr, w.counts + 2, w.h[0], w.c[0], w.lm[0], w.h[0], w.c[0],
+                    w.lm[0], w, st);
+  const long max_rounds = (long)T * (max_token_step + 2);
+  GreedyArgs g{joint_args(d, am, T, w), lengths, w.lm[0], max_token_step, T * (max_token_step + 1), 0,
+               w.t, w.nts, w.done, w.emit, w.token, w.counts, tokens, out_len};
+  for (long r = 0; r < max_rounds;) {
+    for (int q = 0; q < kRoundBlock && r < max_rounds; ++q, ++r) {
+      g.parity = (int)(r & 1);
+      hipLaunchKernelGGL(greedy_joint_kernel, dim3(B), dim3(kThreads), 0, st, g);
+      enqueue_pred_step(d, B, w.token, w.emit, nullptr, w.counts + g.parity, w.h[0], w.c[0], w.lm[0],
+                        w.h[0], w.c[0], w.lm[0], w, st);
+    }
+    S2T_CHECK_LAUNCH();
+    int live = 0;                                          // the one host read of the block
+    e = hipMemcpyAsync(&live, w.counts + 3, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return (int)e;
+    if (live <= 0) break;
+  }
+  return 0;
+}
+
+int s2t_rnnt_beam_lstm(const S2tRnntLstmDesc* desc, const float* am, const long* lengths, int B,
+                       int T, int beam_size, int cutoff_top_k, void* workspace, long* tokens,
+                       long* frames, long* out_len, float* score, void* stream) {
+  if (B <= 0) return 0;
+  if (!desc_ok(desc) || T <= 0 || beam_size < 1 || beam_size > kMaxBeam || cutoff_top_k < 1 ||
+      (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam || !workspace)
+    return -1;
+  const S2tRnntLstmDesc& d = *desc;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = B * beam_size;
+  const Workspace w = carve(d, B, T, beam_size, workspace);
+  const size_t state = sizeof(float) * (size_t)d.num_layers * R * d.H;
+  hipError_t e = hipMemsetAsync(w.h[0], 0, state, st);
+  if (e == hipSuccess) e = hipMemsetAsync(w.c[0], 0, state, st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(beam_init_kernel, dim3(1), dim3(kThreads), 0, st, B, beam_size, w.score, w.blen, w.nb,
+                     w.emit, w.token, w.counts);
+  enqueue_pred_step(d, R, w.token, w.emit, nullptr, w.counts + 2, w.h[0], w.c[0], w.lm[0], w.h[0], w.c[0],
+                    w.lm[0], w, st);
+  BeamArgs a{joint_args(d, am, T, w), lengths, w.lm[0], 0, B, beam_size, cutoff_top_k, 0, w.cscore, w.score,
+             w.ccls, w.blen, w.nb, w.rec, w.emit, w.token, w.parent, w.counts};
+  for (int t = 0; t < T; ++t) {
+    const int cur = t & 1, nxt = cur ^ 1;
+    a.t = t;
+    a.parity = cur;
+    a.lm = w.lm[cur];
+    hipLaunchKernelGGL(beam_expand_kernel, dim3(R), dim3(kThreads), 0, st, a);
+    hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(kThreads), 0, st, a);
+    enqueue_pred_step(d, R, w.token, w.emit, w.parent, w.counts + cur, w.h[cur], w.c[cur], w.lm[cur],
+                      w.h[nxt], w.c[nxt], w.lm[nxt], w, st);
+  }
+  hipLaunchKernelGGL(beam_trace_kernel, dim3(B), dim3(64), 0, st, lengths, T, beam_size, w.rec, w.blen,
+                     w.score, tokens, frames, out_len, score);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"

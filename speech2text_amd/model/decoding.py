@@ -8,9 +8,13 @@ predictor / joiner module calls per lattice move, per beam for the beam search).
 `batch_search` hands the WHOLE batch to one HIP launch: per-frame argmax + repeat/blank collapse
 for CTC (csrc/decode.hip); for RNN-T with the stateless predictor and a projection-free joiner the
 whole greedy lattice walk (csrc/decode.hip) and the whole beam search (csrc/decode_beam.hip) run
-on the device, one workgroup per utterance.  Other predictor / joiner combinations keep the
-module-by-module loop.  The lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder
-are not here."""
+on the device, one workgroup per utterance.  With the LSTM predictor (joiner with or without
+output projection: every LSTM YAML of the reference) both searches run on the device in lockstep
+over the batch (csrc/decode_lstm.hip): per round one lattice move of every live row, a predictor
+step for the rows that emitted, no host synchronisation per move.  Other predictor / joiner
+combinations (the stateless predictor with an out-projection joiner, foreign classes, shapes a
+kernel refuses) keep the module-by-module loop.  The lexicon CTC beam decoder (it wraps
+flashlight) and the CIF decoder are not here."""
 import abc
 from enum import Enum, unique
 from typing import List
@@ -83,6 +87,131 @@ class CtcGreedyDecoding(DecodingMethod):
         return self.decode_batch(hidden_states, n)[0]
 
 
+def _is_lstm_pair(predictor, joiner):
+    """The modules csrc/decode_lstm.hip serves: LstmPredictor + Joiner (any out-projection)."""
+    from speech2text_amd.model.joiner.joiner import Joiner
+    from speech2text_amd.model.predictor.lstm_predictor import LstmPredictor
+    return isinstance(getattr(predictor, "predictor", predictor), LstmPredictor) and isinstance(joiner, Joiner)
+
+
+def rnnt_lstm_desc(predictor, joiner):
+    """-> (S2tRnntLstmDesc of the two modules' fp32 device parameters, the tensors it points to:
+    keep them alive while the descriptor is in use)."""
+    import ctypes
+    p = getattr(predictor, "predictor", predictor)._predictor
+    keep = []
+
+    def a(t):
+        if t is None:
+            return None
+        t = t.detach().contiguous().float()
+        keep.append(t)
+        return N.fp(t)
+
+    d = N.struct("S2tRnntLstmDesc")()
+    layers = list(p.lstm_layers)
+    if len(layers) > N.const("S2T_RNNT_LSTM_MAX_LAYERS") or p.embedding.num_embeddings < joiner._output_dim:
+        return None, keep                                  # (every class must have an embedding row)
+    ln = isinstance(layers[0].g_norm, torch.nn.LayerNorm)
+    d.V, d.E, d.H, d.D = joiner._output_dim, p.embedding.embedding_dim, layers[0].hidden_dim, \
+        p.linear.out_features
+    d.inner = joiner._inner_dim if joiner._use_out_project else 0
+    d.num_layers, d.layer_norm, d.act = len(layers), int(ln), 0 if joiner._act_name == "relu" else 1
+    d.in_eps, d.out_eps = p.input_layer_norm.eps, p.output_layer_norm.eps
+    d.lstm_eps = layers[0].g_norm.eps if ln else 0.0
+    d.emb, d.in_gamma, d.in_beta = a(p.embedding.weight), a(p.input_layer_norm.weight), \
+        a(p.input_layer_norm.bias)
+    for i, m in enumerate(layers):
+        L = d.layers[i]
+        L.x2g_w, L.x2g_b, L.p2g_w = a(m.x2g.weight), a(m.x2g.bias), a(m.p2g.weight)
+        if ln:
+            L.g_gamma, L.g_beta, L.c_gamma, L.c_beta = a(m.g_norm.weight), a(m.g_norm.bias), \
+                a(m.c_norm.weight), a(m.c_norm.bias)
+    d.lin_w, d.lin_b = a(p.linear.weight), a(p.linear.bias)
+    d.out_gamma, d.out_beta = a(p.output_layer_norm.weight), a(p.output_layer_norm.bias)
+    d.pre_w, d.pre_b = a(joiner._pre_proj.weight), a(joiner._pre_proj.bias)
+    if joiner._use_out_project:
+        o1, o2 = joiner._out_projection[0], joiner._out_projection[1]
+        d.out1_w, d.out1_b, d.out2_w, d.out2_b = a(o1.weight), a(o1.bias), a(o2.weight), a(o2.bias)
+    keep.append(d)
+    return ctypes.byref(d), keep
+
+
+def _lstm_workspace(desc, B, T, beam, dev):
+    n = N.lib().s2t_rnnt_lstm_workspace_bytes(desc, B, T, beam) if desc is not None else 0
+    return None if n <= 0 else torch.empty((n,), dtype=torch.uint8, device=dev)
+
+
+def rnnt_greedy_lstm_tokens_from_am(am, lengths, predictor, joiner, max_token_step=10):
+    """Lockstep device greedy search on a given am = joiner._enc_proj(encoder_out), (B,T,V) fp32, LSTM
+    predictor.  -> (tokens (B, T (max_token_step + 1)) int64, out_len (B) int64), or None when the
+    kernels do not take the shape (the caller runs the module loop).  HIP: decode_lstm.hip."""
+    if not am.is_cuda:
+        raise RuntimeError("the device RNN-T greedy search runs on the GPU only")
+    am = am.contiguous().float()
+    B, T, V = am.shape
+    dev = am.device
+    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+    tokens = torch.zeros((B, T * (int(max_token_step) + 1)), dtype=torch.int64, device=dev)
+    out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
+    if B == 0 or T == 0:
+        return tokens, out_len
+    desc, keep = rnnt_lstm_desc(predictor, joiner)
+    ws = _lstm_workspace(desc, B, T, 0, dev)
+    if ws is None or max_token_step < 0:
+        return None
+    rc = N.lib().s2t_rnnt_greedy_lstm(desc, N.fp(am), N.lp(lengths), B, T, int(max_token_step),
+                                      N.ptr(ws), N.lp(tokens), N.lp(out_len), N.stream())
+    if rc == -1:
+        return None
+    N.check(rc, "s2t_rnnt_greedy_lstm")
+    return tokens, out_len
+
+
+def rnnt_beam_lstm_tokens_from_am(am, lengths, predictor, joiner, beam_size=4, cutoff_top_k=4):
+    """rnnt_beam_tokens_from_am for the LSTM predictor (joiner with or without out-projection):
+    same outputs, or None when the kernels do not take the shape.  HIP: decode_lstm.hip."""
+    if not am.is_cuda:
+        raise RuntimeError("the device RNN-T beam search runs on the GPU only")
+    am = am.contiguous().float()
+    B, T, V = am.shape
+    dev = am.device
+    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+    tokens = torch.zeros((B, T), dtype=torch.int64, device=dev)
+    frames = torch.zeros((B, T), dtype=torch.int64, device=dev)
+    out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
+    score = torch.zeros((B,), dtype=torch.float32, device=dev)
+    if B == 0 or T == 0:
+        return tokens, frames, out_len, score
+    desc, keep = rnnt_lstm_desc(predictor, joiner)
+    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
+    if not 1 <= beam_size <= N.const("S2T_RNNT_LSTM_MAX_BEAM"):
+        return None
+    ws = _lstm_workspace(desc, B, T, beam_size, dev)
+    if ws is None:
+        return None
+    rc = N.lib().s2t_rnnt_beam_lstm(desc, N.fp(am), N.lp(lengths), B, T, beam_size, cutoff_top_k,
+                                    N.ptr(ws), N.lp(tokens), N.lp(frames), N.lp(out_len), N.fp(score),
+                                    N.stream())
+    if rc == -1:
+        return None
+    N.check(rc, "s2t_rnnt_beam_lstm")
+    return tokens, frames, out_len, score
+
+
+def _am_per_utterance(joiner, hidden_states, inputs_length):
+    """am (B,T,V) = enc_proj(encoder_out), formed utterance by utterance on the frames an utterance
+    has: the product decode() forms for the same utterance alone, so that a batched search and a
+    per-utterance one see the same bits.  -> (am, lengths clamped to [0, T])."""
+    B, T = hidden_states.shape[0], hidden_states.shape[1]
+    lens = [max(0, min(int(n), T)) for n in inputs_length.tolist()]
+    am = torch.zeros((B, T, joiner._output_dim), dtype=torch.float32, device=hidden_states.device)
+    for b, n in enumerate(lens):
+        if n:
+            am[b, :n] = joiner._enc_proj(hidden_states[b:b + 1, :n, :])[0].float()
+    return am, torch.tensor(lens, dtype=torch.int64)
+
+
 class RnntGreedyDecoding(DecodingMethod):
     def __init__(self, tokenizer, predictor, joiner, max_token_step=10):
         self._tokenizer = tokenizer
@@ -128,20 +257,40 @@ class RnntGreedyDecoding(DecodingMethod):
             "s2t_rnnt_greedy_stateless")
         return tokens, out_len
 
+    def _lstm_search(self):
+        """The lockstep device search of csrc/decode_lstm.hip serves these modules."""
+        return _is_lstm_pair(self._predictor, self._joiner)
+
+    def greedy_tokens_lstm(self, hidden_states, inputs_length):
+        """(B,T,D) encoder output -> (tokens (B,max_out), out_len (B)) by the lockstep device
+        search, or None when the kernels refuse the shape."""
+        am, lens = _am_per_utterance(self._joiner, hidden_states, inputs_length)
+        return rnnt_greedy_lstm_tokens_from_am(am, lens, self._predictor, self._joiner,
+                                               self._max_token_step)
+
     @torch.no_grad()
     def decode_batch(self, hidden_states, inputs_length):
         if self._fused():
             return _to_texts(*self.greedy_tokens(hidden_states, inputs_length), self._tokenizer)
+        if self._lstm_search() and hidden_states.is_cuda:
+            out = self.greedy_tokens_lstm(hidden_states, inputs_length)
+            if out is not None:
+                return _to_texts(*out, self._tokenizer)
+            return [self._module_loop(hidden_states[i:i + 1, :int(inputs_length[i]), :])
+                    for i in range(hidden_states.shape[0])]
         return super().decode_batch(hidden_states, inputs_length)
 
     @torch.no_grad()
     def decode(self, hidden_states: torch.Tensor) -> str:
         assert hidden_states.shape[0] == 1, "Support BatchSize = 1 only."
-        if self._fused():
+        if self._fused() or (self._lstm_search() and hidden_states.is_cuda):
             n = torch.tensor([hidden_states.shape[1]], dtype=torch.int64)
             return self.decode_batch(hidden_states, n)[0]
-        # module-by-module lattice walk (reference :237-271) for LSTM predictors / out-projection /
-        # vocabularies beyond the fused kernel's shared memory
+        return self._module_loop(hidden_states)
+
+    def _module_loop(self, hidden_states: torch.Tensor) -> str:
+        """module-by-module lattice walk (reference :237-271) for the combinations no device search
+        serves, and for the shapes one refuses"""
         pred_state = self._predictor.init_state()
         T = hidden_states.shape[1]
         t = 0
@@ -221,6 +370,10 @@ class RnntBeamDecoding(DecodingMethod):
         return isinstance(p, StatelessPredictor) and isinstance(self._joiner, Joiner) \
             and not self._joiner._use_out_project
 
+    def _lstm_search(self):
+        """The lockstep device search of csrc/decode_lstm.hip serves these modules."""
+        return _is_lstm_pair(self._predictor, self._joiner)
+
     def _module_loop(self, hidden_states):
         """(1,T,D) -> (tokens, frames, score) of the best beam: the reference's loop (:350-425)
         against init_state / streaming_step only, in plain torch on whatever device the inputs
@@ -258,6 +411,12 @@ class RnntBeamDecoding(DecodingMethod):
             am = self._joiner._enc_proj(hidden_states)                # (B,T,V), one GEMM
             out = rnnt_beam_tokens_from_am(am, inputs_length, self._predictor, self._joiner,
                                            self._beam_size, self._cutoff_top_k)
+            if out is not None:
+                return out
+        if fused and self._lstm_search() and hidden_states.is_cuda:
+            am, lens = _am_per_utterance(self._joiner, hidden_states, inputs_length)
+            out = rnnt_beam_lstm_tokens_from_am(am, lens, self._predictor, self._joiner,
+                                                self._beam_size, self._cutoff_top_k)
             if out is not None:
                 return out
         B, T = hidden_states.shape[0], hidden_states.shape[1]

@@ -530,23 +530,15 @@ RNNT_BEAM_SIDE = {"c0_params": ("c0_emb", "c0_lin_w", "c0_pre_w"), "c0_am": ("c0
                   "c4": ("c4_am_packed", "c4_emb", "c4_pre_w", "c4_enc_w", "c4_enc")}
 
 
-def gen_rnnt_beam():
-    """tests/golden/rnnt_beam_ref*.npz: the reference's RnntBeamDecoding (fp32, its own
-    StatelessPredictor / Joiner modules) and the float64 restatement of tests/
-    rnnt_beam_restatement.py on random models.  Kept per configuration: the first 8 utterances on
-    which the reference's fp32 tokens equal the float64 tokens and whose decision margin is at
-    least 16 N, N = the largest |fp32 score - float64 score| of the configuration (the reference's
-    own fp32 noise; 16 = 2 scores x the 4 N the kernel is allowed on each x a safety factor 2)."""
+def _ref_decoding():
+    """The reference's model.decoding module, with whatever third-party wheel it imports and this
+    machine lacks stubbed."""
+    import importlib
     import importlib.machinery
     import types
-    import torch
-    ref_import.install_stubs()
-    sys.path.insert(0, os.path.join(REPO, "tests"))
-    import rnnt_beam_restatement as R
-    for _ in range(12):                                      # stub whatever third-party wheel is absent
+    for _ in range(12):
         try:
-            from model.decoding import RnntBeamDecoding
-            break
+            return importlib.import_module("model.decoding")
         except ModuleNotFoundError as e:
             name = e.name
             assert not os.path.exists(os.path.join("/root/reference", name.split(".")[0])), name
@@ -555,6 +547,21 @@ def gen_rnnt_beam():
             m.__path__ = []
             m.__getattr__ = lambda attr, _n=name: type(attr, (), {})
             sys.modules[name] = m
+    raise RuntimeError("model.decoding does not import")
+
+
+def gen_rnnt_beam():
+    """tests/golden/rnnt_beam_ref*.npz: the reference's RnntBeamDecoding (fp32, its own
+    StatelessPredictor / Joiner modules) and the float64 restatement of tests/
+    rnnt_beam_restatement.py on random models.  Kept per configuration: the first 8 utterances on
+    which the reference's fp32 tokens equal the float64 tokens and whose decision margin is at
+    least 16 N, N = the largest |fp32 score - float64 score| of the configuration (the reference's
+    own fp32 noise; 16 = 2 scores x the 4 N the kernel is allowed on each x a safety factor 2)."""
+    import torch
+    ref_import.install_stubs()
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import rnnt_beam_restatement as R
+    RnntBeamDecoding = _ref_decoding().RnntBeamDecoding
     from model.joiner.joiner import Joiner, JoinerConfig
     from model.predictor.stateless_predictor import StatelessPredictor, StatelessPredictorConfig
 
@@ -640,6 +647,102 @@ def gen_rnnt_beam():
             size = os.path.getsize(os.path.join(OUT, f))
             print(f, size)
             assert size < 1 << 20, f
+
+
+RNNT_LSTM_CONFIGS = [   # (model of tests/rnnt_lstm_search_cases.py, seed, Tmax, max_token_step, beam, topk, drawn)
+    ("h20", 11, 12, 1, 4, 4, 40),
+    ("h20_v11", 12, 10, 0, 16, 20, 40),
+    ("h48", 13, 8, 10, 4, 4, 60),
+]
+RNNT_LSTM_KEEP = 8
+
+
+def gen_rnnt_lstm_search():
+    """tests/golden/rnnt_lstm_search_ref.npz: the reference's own RnntGreedyDecoding and
+    RnntBeamDecoding loops (fp32) over the plain-torch stand-ins of tests/rnnt_lstm_search_f64.py
+    (the reference's LstmPredictor wraps torchaudio, which is absent: the predictor's own parity
+    stays unpinned, what is pinned are the two search loops), next to the float64 restatement.
+    Kept per configuration and search: the first 8 utterances on which the reference's fp32 tokens
+    equal the float64 tokens and which float64 decides by at least 1e-3."""
+    import torch
+    ref_import.install_stubs()
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import rnnt_lstm_search_cases as C
+    import rnnt_lstm_search_f64 as S
+    D = _ref_decoding()
+
+    class Ids:                                               # tokenizer stand-in: ids pass through
+        def decode(self, t):
+            return t.tolist()
+
+    def flat(w):
+        out = {k: v.numpy() for k, v in w.items() if isinstance(v, torch.Tensor)}
+        for i, p in enumerate(w["layers"]):
+            out.update({f"l{i}_{k}": v.numpy() for k, v in p.items()})
+        return out
+
+    out = {"n_configs": np.array([len(RNNT_LSTM_CONFIGS)])}
+    for ci, (model, seed, Tmax, mts, beam, topk, drawn) in enumerate(RNNT_LSTM_CONFIGS):
+        m = C.MODELS[model]
+        w = C.weights(model, seed)
+        g = torch.Generator().manual_seed(seed)
+        am = m["scale"] * torch.randn(drawn, Tmax, m["V"], generator=g)
+        spread = (2 * np.log(m["V"])) ** 0.5
+        if m["inner"]:
+            w["o2_b"][0] += spread * m["oscale"] * 0.8 * m["scale"]
+        else:
+            am[:, :, 0] += 0.5 * spread * m["scale"]
+        lens = torch.randint(1, Tmax + 1, (drawn,), generator=g)
+        lens[0] = Tmax
+        w64 = S.cast(w, torch.float64)
+        pred, join = S.PlainPredictor(w), S.PlainJoiner(w, m["act"])
+        gsess = D.RnntGreedyDecoding(Ids(), pred, join, max_token_step=mts)
+        bsess = D.RnntBeamDecoding(Ids(), pred, join, beam_size=beam, cutoff_top_k=topk)
+        pre = f"c{ci}_"
+        for kind in ("greedy", "beam"):
+            rows = []
+            for b in range(drawn):
+                a = am[b:b + 1, :int(lens[b])]
+                with torch.no_grad():
+                    if kind == "greedy":
+                        ref_tok, ref_score = gsess.decode(a), 0.0
+                        tok, margin, _ = S.greedy(a[0], w64, m["act"], mts)
+                        score, frames = 0.0, []
+                    else:
+                        ref_tok = bsess.decode(a)
+                        ref_score = float(bsess._decoding_state.best_beam.score)
+                        tok, score, frames, margin = S.beam_search(a[0], w64, m["act"], beam, topk)
+                if ref_tok == tok and margin >= S.MARGIN:
+                    rows.append((b, tok, frames, score, ref_score, margin))
+            keep = rows[:RNNT_LSTM_KEEP]
+            print(f"rnnt_lstm_search c{ci} {model} {kind}: drawn {drawn}, agree and decided {len(rows)}, "
+                  f"lengths {[int(lens[r[0]]) for r in keep]}, tokens {[len(r[1]) for r in keep]}")
+            assert len(keep) == RNNT_LSTM_KEEP, "draw more utterances"
+            assert 0 < sum(len(r[1]) for r in keep), "the kept set needs emitted tokens"
+            umax = max(1, max(len(r[1]) for r in keep))
+            tokens = np.zeros((RNNT_LSTM_KEEP, umax), dtype=np.int64)
+            frames = np.zeros((RNNT_LSTM_KEEP, umax), dtype=np.int64)
+            for i, r in enumerate(keep):
+                tokens[i, :len(r[1])] = r[1]
+                frames[i, :len(r[2])] = r[2]
+            k = pre + kind + "_"
+            out[k + "am_packed"] = np.concatenate([am[r[0], :int(lens[r[0]])].numpy() for r in keep])
+            out[k + "lengths"] = np.array([int(lens[r[0]]) for r in keep], dtype=np.int64)
+            out[k + "tokens"] = tokens                       # the reference class's (= float64) tokens
+            out[k + "tok_len"] = np.array([len(r[1]) for r in keep], dtype=np.int64)
+            out[k + "margin"] = np.array([r[5] for r in keep])
+            if kind == "beam":
+                out[k + "frames"] = frames
+                out[k + "score_f64"] = np.array([r[3] for r in keep])
+                out[k + "score_ref_f32"] = np.array([r[4] for r in keep])
+        out[pre + "model"] = np.array([model])
+        out[pre + "settings"] = np.array([seed, Tmax, mts, beam, topk], dtype=np.int64)
+        for key, v in flat(w).items():
+            out[pre + "w_" + key] = v
+    path = os.path.join(OUT, "rnnt_lstm_search_ref.npz")
+    np.savez_compressed(path, **out)
+    print("rnnt_lstm_search_ref.npz", os.path.getsize(path))
+    assert os.path.getsize(path) < 1 << 20
 
 
 def gen_rnn_lm():
