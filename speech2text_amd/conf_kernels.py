@@ -28,6 +28,12 @@ def _rows(x):
     return x2
 
 
+def _aligned(t):
+    """`t` (contiguous) at a 16-byte address: a view into a larger buffer may start anywhere, the
+    float4 passes cannot.  Element indices, and with them the dropout hash's mask, are unchanged."""
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 # ------------------------------------------------------------------ raw launches
 def ln_fwd(x2, y2, alpha, weight, bias, eps):
     """-> (xsum | None, out, stats).  y2 given: the input is x2 + alpha * y2 (also returned)."""
@@ -229,9 +235,9 @@ def layer_norm(x, ln):
     if not x.is_cuda:
         raise RuntimeError("speech2text_amd.layer_norm needs device tensors (HIP path only)")
     C = x.shape[-1]
-    if C % 4 or C > 1024 or x.dtype != _F32 or ln.weight is None:
-        # outside the kernel's rules (row length a multiple of 4, <= 1024, affine): torch's device
-        # kernel -- still the GPU, never a host path
+    if C % 4 or C > 1024 or x.dtype != _F32 or ln.weight is None or ln.bias is None:
+        # outside the kernel's rules (row length a multiple of 4, <= 1024, affine with a bias):
+        # torch's device kernel -- still the GPU, never a host path
         return torch.nn.functional.layer_norm(x, (C,), ln.weight, ln.bias, ln.eps)
     return _LayerNorm.apply(x, ln.weight, ln.bias, ln.eps)
 
@@ -310,13 +316,12 @@ class _Dropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p, seed):
         ctx.cfg = (p, seed)
-        x2 = x.contiguous()
-        return dropout_add(None, x2.view(-1), 1.0, p, seed).view(x.shape)
+        return dropout_add(None, _aligned(x.contiguous()).view(-1), 1.0, p, seed).view(x.shape)
 
     @staticmethod
     def backward(ctx, g):
         p, seed = ctx.cfg
-        g2 = g.contiguous().float()
+        g2 = _aligned(g.contiguous().float())
         return dropout_add(None, g2.view(-1), 1.0, p, seed).view(g.shape), None, None
 
 
