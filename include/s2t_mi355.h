@@ -482,6 +482,61 @@ int s2t_rnnt_beam_stateless(const float* am, const long* lengths, const float* e
                             void* workspace, long* tokens, long* frames, long* out_len,
                             float* score, void* stream);
 
+/* ---- chunk-carried (streaming) RNN-T search: the two searches above fed their frames in pieces
+ * (csrc/decode_stream.hip).  Same predictor / joiner parameters, same orders, same limits; the walks
+ * are the device functions the whole-utterance kernels run (csrc/decode_search.h), so for ANY cut of
+ * [0, L) into chunks -- one frame each, different per row -- tokens, frames, out_len and score after
+ * the last chunk are those of the whole-utterance call on the concatenated am with lengths = L, bit
+ * for bit, and after every chunk those of the prefix fed so far.  No call synchronises with the
+ * host: all of them can be captured into a graph.
+ * state: ONE caller-owned device buffer of s2t_rnnt_stream_state_bytes(B, V, ctx, beam_size,
+ * max_tokens) bytes (a pure host function; beam_size 0 = the greedy state; a multiple of 256; 0 for
+ * B <= 0 or a shape outside the limits: V in 1..8192, ctx in 1..64, beam_size in 0..16, max_tokens
+ * >= 1), a row per stream.  Its size does not depend on how many chunks or frames a stream sees.
+ * A greedy row holds the predictor state and its lm vector; a beam row holds per beam the score,
+ * length, predictor state and lm vector (persisted: a chunk starts without a pass over the
+ * predictor's weights), the (parent, class) records of the current chunk's frames only, and two
+ * alternating buffers [beam_size][max_tokens] of token and frame histories (int32).
+ * s2t_rnnt_stream_reset: a kernel on `stream` that makes every row b with rows[b] != 0 (rows NULL:
+ * every row) the empty hypothesis: one beam, score 0, no tokens, predictor state = ctx blanks, frame
+ * counter 0, overflow 0.  Other rows are not touched: a slot can end one stream and start another
+ * while its neighbours go on.  The caller's output arrays are not reset's to write: they show the
+ * new stream from its first chunk with chunk_len > 0 on.
+ * A chunk call advances row b over the first min(chunk_len[b], Tc) frames of am [B][Tc][V] from the
+ * carried state and stores the state back; Tc <= 256.  chunk_len[b] <= 0 leaves row b's state AND
+ * outputs exactly as they were (an idle stream is not a zero-length utterance).  Outputs are the
+ * result for the whole stream since its reset:
+ * s2t_rnnt_greedy_stateless_chunk: tokens [B][max_tokens] is appended to, so a stream must be given
+ *   the same array on every call; out_len [B].  When max_tokens tokens are out the row is inert
+ *   until reset (the whole-utterance kernel ends its walk there too) and overflow[b] = 1: later
+ *   symbols, if any, are lost.
+ * s2t_rnnt_beam_stateless_chunk: the best beam's tokens [B][max_tokens], the frames [B][max_tokens]
+ *   at which they were emitted counted from the reset (not from the chunk's start), out_len [B],
+ *   score [B], all rewritten by every call with chunk_len > 0.  stable_len [B]: the length of the
+ *   longest common prefix of all live beams' token sequences; every later result starts with these
+ *   tokens, so it never decreases and a client may print them; with one live beam it is out_len.
+ *   A beam that would pass max_tokens keeps its first max_tokens tokens while the search goes on
+ *   with exact scores and predictor states: out_len saturates, and overflow[b] = 1 from the first
+ *   chunk after which a live beam is longer than max_tokens until reset.
+ * Return 0; -1 before any launch (outputs untouched) for Tc outside 1..256, state NULL, max_tokens
+ * < 1, or what the whole-utterance call refuses; B <= 0 returns 0. */
+long s2t_rnnt_stream_state_bytes(int B, int V, int ctx, int beam_size, int max_tokens);
+int s2t_rnnt_stream_reset(void* state, const int* rows, int B, int V, int ctx, int beam_size,
+                          int max_tokens, int blank, void* stream);
+int s2t_rnnt_greedy_stateless_chunk(const float* am, const long* chunk_len, const float* emb,
+                                    const float* conv_w, const float* lin_w, const float* lin_b,
+                                    const float* pre_w, const float* pre_b, int B, int Tc, int V,
+                                    int E, int D, int ctx, int act, int max_token_step,
+                                    int max_tokens, int blank, void* state, long* tokens,
+                                    long* out_len, int* overflow, void* stream);
+int s2t_rnnt_beam_stateless_chunk(const float* am, const long* chunk_len, const float* emb,
+                                  const float* conv_w, const float* lin_w, const float* lin_b,
+                                  const float* pre_w, const float* pre_b, int B, int Tc, int V, int E,
+                                  int D, int ctx, int act, int blank, int beam_size,
+                                  int cutoff_top_k, int max_tokens, void* state, long* tokens,
+                                  long* frames, long* out_len, float* score, long* stable_len,
+                                  int* overflow, void* stream);
+
 /* ---- RNN-T greedy and beam search with the layer-norm LSTM predictor (model/decoding.py:196-425 over
  * model/predictor/lstm_predictor.py:28-109 and model/joiner/joiner.py:186-207), joiner with or
  * without output projection (csrc/decode_lstm.hip).  The search runs in LOCKSTEP over the batch: a

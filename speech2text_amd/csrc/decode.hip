@@ -11,6 +11,7 @@
 // `ctx` tokens, so the language-side vector lm = pre_proj(linear(conv(embed(state)))) is
 // recomputed (two wave-per-row GEMVs) only when a symbol is emitted.
 #include "common.h"
+#include "decode_search.h"
 
 namespace {
 
@@ -78,80 +79,23 @@ struct RnntGreedyArgs {
   long* out_len;          // [B]
 };
 
-// y[r] = w[r] . x + b[r], one wave per row, x in LDS
-__device__ __forceinline__ void gemv_rows(const float* __restrict__ w, const float* __restrict__ bias,
-                                          const float* __restrict__ x, int rows, int cols,
-                                          float* __restrict__ y) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int r = wave; r < rows; r += 4) {
-    const float* wr = w + (long)r * cols;
-    float acc = 0.f;
-    for (int c = lane; c < cols; c += 64) acc = fmaf(wr[c], x[c], acc);
-    acc = wave_sum(acc);
-    if (lane == 0) y[r] = acc + (bias ? bias[r] : 0.f);
-  }
-}
-
 __global__ __launch_bounds__(256) void rnnt_greedy_kernel(RnntGreedyArgs a) {
   extern __shared__ float sm[];
   float* e = sm;                       // [E]   conv(embed(state))
   float* hvec = e + a.E;               // [D]
   float* lm = hvec + a.D;              // [V]
   int* state = reinterpret_cast<int*>(lm + a.V);   // [ctx] most recent last
-  __shared__ ArgMax s_red[4];
-  __shared__ int s_tok;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ s2t_dec::GreedyShared s_walk;
+  const int b = blockIdx.x, tid = threadIdx.x;
   long Tb = a.lengths[b];
   if (Tb > a.T) Tb = a.T;
   for (int k = tid; k < a.ctx; k += 256) state[k] = a.blank;   // init_state + blank start token
   __syncthreads();
-  const float* amb = a.am + (long)b * a.T * a.V;
   long n = 0;
-  int t = 0, nts = 0;
   bool need_lm = true;
-  while (t < Tb) {
-    if (need_lm) {
-      for (int c = tid; c < a.E; c += 256) {
-        float acc = 0.f;
-        for (int k = 0; k < a.ctx; ++k) acc = fmaf(a.conv_w[c * a.ctx + k], a.emb[(long)state[k] * a.E + c], acc);
-        e[c] = acc;
-      }
-      __syncthreads();
-      gemv_rows(a.lin_w, a.lin_b, e, a.D, a.E, hvec);
-      __syncthreads();
-      gemv_rows(a.pre_w, a.pre_b, hvec, a.V, a.D, lm);
-      __syncthreads();
-      need_lm = false;
-    }
-    ArgMax best{S2T_NEG_INF, a.V};
-    for (int c = tid; c < a.V; c += 256) {
-      float v = amb[(long)t * a.V + c] + lm[c];
-      v = a.act == 0 ? fmaxf(v, 0.f) : tanhf(v);
-      best = better(best, ArgMax{v, c});
-    }
-    best = wave_argmax(best);
-    if (lane == 0) s_red[wave] = best;
-    __syncthreads();
-    if (tid == 0) s_tok = better(better(s_red[0], s_red[1]), better(s_red[2], s_red[3])).i;
-    __syncthreads();
-    const int tok = s_tok;
-    if (tok == a.blank || nts > a.max_token_step) {
-      ++t;
-      nts = 0;
-    } else {
-      ++nts;
-      if (tid == 0 && n < a.max_out) a.tokens[(long)b * a.max_out + n] = tok;
-      ++n;
-      __syncthreads();
-      if (tid == 0) {
-        for (int k = 0; k + 1 < a.ctx; ++k) state[k] = state[k + 1];
-        state[a.ctx - 1] = tok;
-      }
-      need_lm = true;
-      if (n >= a.max_out) break;                     // output buffer full (uniform exit)
-    }
-    __syncthreads();
-  }
+  // the walk itself is shared with the chunk-carried kernel (decode_search.h)
+  s2t_dec::greedy_walk(a, s_walk, a.am + (long)b * a.T * a.V, Tb, state, e, hvec, lm, need_lm, n,
+                       a.tokens + (long)b * a.max_out, a.max_out);
   if (tid == 0) a.out_len[b] = n < a.max_out ? n : a.max_out;
 }
 

@@ -1,4 +1,4 @@
-// Device functions shared by the RNN-T search kernels (csrc/decode_beam.hip, csrc/decode_lstm.hip):
+// Device functions shared by the RNN-T search kernels (csrc/decode_search.h, csrc/decode_lstm.hip):
 // the (value descending, index ascending) order every arg-max / top-k of the searches is taken in,
 // and the joiner's activation.
 #pragma once

@@ -445,6 +445,109 @@ class RnntBeamDecoding(DecodingMethod):
         return self.decode_batch(hidden_states, n)[0]
 
 
+class RnntStreamingSearch:
+    """Chunk-carried RNN-T search on the device (csrc/decode_stream.hip): the fused greedy / beam
+    search of the stateless predictor and a projection-free joiner, fed `am = joiner._enc_proj(
+    encoder_out)` a chunk at a time.  However the frames are cut, the result after a chunk is the
+    whole-utterance search's on the frames fed so far, bit for bit (the kernels share their walk).
+
+    Owns the state buffer (one row per stream, size independent of the stream's length) and fixed
+    output tensors; `step` returns views of them, and makes no host synchronisation, so a step can
+    be captured into a graph.  There is no module-loop fallback: a predictor / joiner pair or a
+    shape the fused search does not take is an error at construction."""
+
+    def __init__(self, predictor, joiner, batch_size=1, method="greedy", max_token_step=5,
+                 beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None):
+        from speech2text_amd.model.joiner.joiner import Joiner
+        from speech2text_amd.model.predictor.predictor import StatelessPredictor
+        if method not in ("greedy", "beam"):
+            raise ValueError(f"method must be 'greedy' or 'beam', got {method!r}")
+        p = getattr(predictor, "predictor", predictor)
+        if not isinstance(p, StatelessPredictor):
+            raise ValueError("the chunk-carried search takes the stateless predictor only, got "
+                             f"{type(p).__name__} (the LSTM-predictor search is whole-utterance)")
+        if not isinstance(joiner, Joiner) or joiner._use_out_project:
+            raise ValueError("the chunk-carried search takes a Joiner without output projection")
+        dev = torch.device("cuda") if device is None else torch.device(device)
+        if dev.type != "cuda" or p._embedding.weight.device.type != "cuda":
+            raise RuntimeError("the chunk-carried search runs on the GPU only: modules and device must be cuda")
+        self.method, self.batch_size, self.max_tokens = method, int(batch_size), int(max_tokens)
+        self.max_token_step = int(max_token_step)
+        self.beam_size = int(beam_size) if method == "beam" else 0
+        self.cutoff_top_k = int(cutoff_top_k)
+        self.V, self.E, self.D, self.ctx = joiner._output_dim, p._embedding_dim, p._output_dim, p._context_size
+        self._act = 0 if joiner._act_name == "relu" else 1
+        B, V, E, D, ctx = self.batch_size, self.V, self.E, self.D, self.ctx
+        n = N.lib().s2t_rnnt_stream_state_bytes(B, V, ctx, self.beam_size, self.max_tokens) if B > 0 else 0
+        if method == "beam":
+            ok = 1 <= self.beam_size <= 16 and 1 <= min(self.cutoff_top_k, V) <= 16 \
+                and 16 * (E + D) + 128 * ctx <= 60 * 1024
+        else:
+            ok = self.max_token_step >= 0 and 4 * (E + D + V + ctx) <= 60 * 1024
+        if n <= 0 or not ok or p._embedding.num_embeddings < V:
+            raise ValueError(f"the chunk-carried {method} search does not take this shape: B {B} V {V} "
+                             f"E {E} D {D} ctx {ctx} beam {self.beam_size} top-k {self.cutoff_top_k} "
+                             f"max_tokens {self.max_tokens} (limits: include/s2t_mi355.h)")
+        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        self._w = [f32(p._embedding.weight), f32(p._conv.weight.reshape(E, ctx)),
+                   f32(p._output_linear.weight), f32(p._output_linear.bias),
+                   f32(joiner._pre_proj.weight), f32(joiner._pre_proj.bias)]
+        self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        self.tokens = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
+        self.frames = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
+        self.out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
+        self.score = torch.zeros((B,), dtype=torch.float32, device=dev)
+        self.stable_len = torch.zeros((B,), dtype=torch.int64, device=dev)
+        self.overflow = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self._full = {}                                    # Tc -> chunk_len of a whole chunk
+        self.reset()
+
+    def reset(self, rows=None):
+        """Rows (indices, or None for all) become the empty hypothesis; their outputs read zero
+        until their next chunk.  The others are not touched."""
+        B = self.batch_size
+        mask = None
+        if rows is not None:
+            mask = torch.zeros((B,), dtype=torch.int32)
+            mask[torch.as_tensor(rows, dtype=torch.int64)] = 1
+            mask = mask.to(self.state.device)
+        N.check(N.lib().s2t_rnnt_stream_reset(N.ptr(self.state), N.ip(mask), B, self.V, self.ctx,
+                                              self.beam_size, self.max_tokens, 0, N.stream()),
+                "s2t_rnnt_stream_reset")
+        for t in (self.tokens, self.frames, self.out_len, self.score, self.stable_len, self.overflow):
+            if mask is None:
+                t.zero_()
+            else:
+                t.masked_fill_(mask.bool().reshape(-1, *[1] * (t.dim() - 1)), 0)
+
+    def step(self, am_chunk, chunk_len=None):
+        """am_chunk (B, Tc, V) fp32 on the device, Tc <= 256; chunk_len (B) int64 on the device
+        (None: Tc frames for every row; 0 leaves a row as it is).  -> greedy (tokens, out_len),
+        beam (tokens, frames, out_len, score, stable_len): views of the fixed output tensors."""
+        B, V = self.batch_size, self.V
+        if am_chunk.dim() != 3 or am_chunk.shape[0] != B or am_chunk.shape[2] != V \
+                or not 1 <= am_chunk.shape[1] <= 256:
+            raise ValueError(f"expected am of shape ({B}, 1..256, {V}), got {tuple(am_chunk.shape)}")
+        Tc = am_chunk.shape[1]
+        if chunk_len is None:
+            chunk_len = self._full.get(Tc)
+            if chunk_len is None:
+                chunk_len = self._full[Tc] = torch.full((B,), Tc, dtype=torch.int64, device=self.state.device)
+        w = [N.fp(t) for t in self._w]
+        if self.method == "greedy":
+            N.check(N.lib().s2t_rnnt_greedy_stateless_chunk(
+                N.fp(am_chunk), N.lp(chunk_len), *w, B, Tc, V, self.E, self.D, self.ctx, self._act,
+                self.max_token_step, self.max_tokens, 0, N.ptr(self.state), N.lp(self.tokens),
+                N.lp(self.out_len), N.ip(self.overflow), N.stream()), "s2t_rnnt_greedy_stateless_chunk")
+            return self.tokens, self.out_len
+        N.check(N.lib().s2t_rnnt_beam_stateless_chunk(
+            N.fp(am_chunk), N.lp(chunk_len), *w, B, Tc, V, self.E, self.D, self.ctx, self._act, 0,
+            self.beam_size, self.cutoff_top_k, self.max_tokens, N.ptr(self.state), N.lp(self.tokens),
+            N.lp(self.frames), N.lp(self.out_len), N.fp(self.score), N.lp(self.stable_len),
+            N.ip(self.overflow), N.stream()), "s2t_rnnt_beam_stateless_chunk")
+        return self.tokens, self.frames, self.out_len, self.score, self.stable_len
+
+
 @unique
 class DecodingFactory(Enum):
     """Decoding methods by the reference's names (:428-435), so that an inference YAML's

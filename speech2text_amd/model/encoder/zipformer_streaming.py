@@ -276,3 +276,143 @@ class StreamingSession:
         self.x.copy_(x)
         self.graph.replay()
         return self.out
+
+
+def _state_batch_dim(i: int, n_states: int) -> int:
+    """The batch dimension of states[i] (get_init_states): 1 for the four attention caches of a
+    layer, 0 for its two conv caches, the ConvNeXt pad and processed_lens."""
+    return 1 if i < n_states - 2 and i % 6 < 4 else 0
+
+
+class StreamingRecognizer:
+    """Features in, text out, a chunk at a time: CMVN -> `streaming_step` -> `joiner._enc_proj` -> the
+    chunk-carried RNN-T search (model/decoding.py RnntStreamingSearch) -> the encoder-state update,
+    captured once and replayed as ONE hipGraph per chunk, in the style of StreamingSession.
+
+    Fixed buffers: the features `x` (B, 2*chunk+13, F), `chunk_len` (B) -- how many of the chunk's
+    chunk//2 encoder frames are valid per row; 0 leaves a row's hypothesis as it is --, the encoder
+    states, the search state and its outputs.  `step` is a copy-in plus one replay and returns views:
+    consume or clone them before the next step.  The search takes the stateless predictor and a
+    joiner without output projection only (an error otherwise: there is no module-loop fallback)."""
+
+    def __init__(self, encoder, predictor, joiner, tokenizer, cmvn=None, batch_size: int = 1,
+                 method: str = "greedy", max_token_step: int = 5, beam_size: int = 4,
+                 cutoff_top_k: int = 4, max_tokens: int = 1024, device=None, warmup: int = 2):
+        from speech2text_amd.model.decoding import RnntStreamingSearch
+        model = getattr(encoder, "encoder", encoder)
+        if model.training or getattr(predictor, "training", False) or getattr(joiner, "training", False):
+            raise RuntimeError("StreamingRecognizer is an inference path: call .eval() first")
+        device = torch.device("cuda") if device is None else torch.device(device)
+        if device.type != "cuda" or next(model.parameters()).device.type != "cuda":
+            raise RuntimeError("StreamingRecognizer runs on the HIP kernels: model and device must be cuda")
+        chunk = model.chunk_size[0]
+        if chunk <= 0 or chunk % 2 or model.left_context_frames[0] < 0:
+            raise ValueError("streaming needs a causal model with an even chunk_size > 0 and "
+                             "left_context_frames >= 0")
+        if model._for_ctc:
+            raise ValueError("StreamingRecognizer searches the encoder output: build the encoder with for_ctc=False")
+        self.model, self.joiner, self.tokenizer = model, joiner, tokenizer
+        self.batch_size, self.chunk, self.Tc = batch_size, chunk, chunk // 2
+        self.frames = 2 * chunk + 13
+        self.search = RnntStreamingSearch(predictor, joiner, batch_size, method, max_token_step,
+                                          beam_size, cutoff_top_k, max_tokens, device)
+        self.x = torch.zeros(batch_size, self.frames, model._feature_dim, device=device)
+        self.chunk_len = torch.full((batch_size,), self.Tc, dtype=torch.int64, device=device)
+        self.states = get_init_states(model, batch_size, device)
+        mean = getattr(cmvn, "global_mean", None)
+        istd = getattr(cmvn, "global_istd", None)
+        self._cmvn = None if mean is None or istd is None else \
+            (mean.detach().to(device).float(), istd.detach().to(device).float())
+
+        def chain(states):
+            x = self.x if self._cmvn is None else (self.x - self._cmvn[0]) * self._cmvn[1]
+            enc, new = streaming_step(model, x, states)
+            am = joiner._enc_proj(enc).float().contiguous()
+            return am, self.search.step(am, self.chunk_len), new
+
+        side = torch.cuda.Stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side), torch.no_grad():
+            st = [s.clone() for s in self.states]
+            for _ in range(warmup):
+                _, _, st = chain(st)
+            self.search.reset()
+        torch.cuda.current_stream(device).wait_stream(side)
+        torch.cuda.synchronize(device)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=side), torch.no_grad():
+            self.am, self.outputs, new = chain(self.states)
+            for dst, src in zip(self.states, new):
+                dst.copy_(src)
+
+    def reset(self, rows=None):
+        """Rows (indices, or None for all) start a new stream: empty hypothesis, zero encoder states."""
+        self.search.reset(rows)
+        if rows is None:
+            for s in self.states:
+                s.zero_()
+            return
+        idx = torch.as_tensor(rows, dtype=torch.int64).to(self.x.device)
+        for i, s in enumerate(self.states):
+            s.index_fill_(_state_batch_dim(i, len(self.states)), idx, 0)
+
+    @torch.no_grad()
+    def step(self, x: Tensor, chunk_len=None):
+        """x (B, 2*chunk+13, F); chunk_len (B) valid encoder frames of this chunk per row, 0..chunk//2
+        (None: all).  -> greedy (tokens, out_len, am), beam (tokens, frames, out_len, score,
+        stable_len, am); am (B, chunk//2, V) is the chunk's joiner input."""
+        if tuple(x.shape) != tuple(self.x.shape):
+            raise ValueError(f"expected input of shape {tuple(self.x.shape)}, got {tuple(x.shape)}")
+        self.x.copy_(x)
+        if chunk_len is None:
+            self.chunk_len.fill_(self.Tc)
+        else:
+            self.chunk_len.copy_(torch.as_tensor(chunk_len, dtype=torch.int64))
+        self.graph.replay()
+        return (*self.outputs, self.am)
+
+    def _texts(self, lens: Tensor) -> List[str]:
+        both = torch.cat([self.search.tokens, lens.unsqueeze(1)], dim=1).cpu()      # one host read
+        return [self.tokenizer.decode(both[b, :int(both[b, -1])]) for b in range(both.shape[0])]
+
+    def texts(self) -> List[str]:
+        """The current best hypothesis of every row."""
+        return self._texts(self.search.out_len)
+
+    def stable_texts(self) -> List[str]:
+        """The part of every row's hypothesis that can no longer change (beam: the prefix all live
+        beams share; greedy: everything)."""
+        return self._texts(self.search.stable_len if self.search.method == "beam" else self.search.out_len)
+
+    def num_output_frames(self, feat_lens: Tensor) -> Tensor:
+        """Encoder frames of feat_lens feature frames: the encoder's own arithmetic, (n - 7) // 2
+        through the subsampling and (n + 1) // 2 through the output downsampling."""
+        n = torch.as_tensor(feat_lens, dtype=torch.int64).cpu()
+        return (((n - 7) // 2 + 1) // 2).clamp(min=0)
+
+    def recognize(self, feats: Tensor, feat_lens: Tensor) -> List[str]:
+        """Whole utterances (B, T, F) through the stream from a reset: right-padded with log(1e-10)
+        (as simulated_streaming_forward pads; the value is the padding's AFTER the CMVN), cut into
+        2*chunk-strided windows; row b has clamp(n_out[b] - k * chunk//2, 0, chunk//2) valid frames in
+        chunk k, so a row that ended idles while longer ones go on.  -> the texts."""
+        import math
+        if feats.dim() != 3 or feats.shape[0] != self.batch_size or feats.shape[2] != self.x.shape[2]:
+            raise ValueError(f"expected feats of shape ({self.batch_size}, T, {self.x.shape[2]}), "
+                             f"got {tuple(feats.shape)}")
+        n_out = self.num_output_frames(feat_lens)
+        K = max(1, -(-int(n_out.max()) // self.Tc))
+        need = 2 * self.chunk * (K - 1) + self.frames
+        feats = feats.to(self.x.device).float()
+        pad = torch.full((feats.shape[2],), math.log(1e-10), device=feats.device)
+        if self._cmvn is not None:
+            pad = pad / self._cmvn[1] + self._cmvn[0]
+        T = feats.shape[1]
+        lens = torch.as_tensor(feat_lens, dtype=torch.int64).to(feats.device).clamp(max=T)
+        buf = pad.expand(feats.shape[0], max(need, T), -1).clone()
+        valid = torch.arange(T, device=feats.device).unsqueeze(0) < lens.unsqueeze(1)
+        buf[:, :T] = torch.where(valid.unsqueeze(-1), feats, buf[:, :T])
+        self.reset()
+        for k in range(K):
+            cl = (n_out - k * self.Tc).clamp(0, self.Tc)
+            self.step(buf[:, 2 * self.chunk * k:2 * self.chunk * k + self.frames], cl)
+        return self.texts()

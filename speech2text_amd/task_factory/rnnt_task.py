@@ -194,3 +194,26 @@ class PrunedRnntTask(BaseRnntTask):
                 "val_loss/pruned_loss": pruned_loss, "val_loss/ctc_loss": ctc_loss, "wer": wer}
         self.log_dict(info, sync_dist=True, prog_bar=True, logger=True)
         return info
+
+    def streaming_recognizer(self, batch_size=1, method=None, **kw):
+        """A StreamingRecognizer (model/encoder/zipformer_streaming.py) over this task's encoder,
+        predictor, joiner, tokenizer and global CMVN: features in, text out, a chunk at a time.
+        method ("greedy" | "beam"), max_token_step, beam_size and cutoff_top_k come from the task's
+        `metric:` section when not given.  The task must be on the GPU and in eval mode; its decoder
+        must be the identity (the search reads the encoder output through joiner._enc_proj)."""
+        from speech2text_amd.model.decoder.decoder import Identity
+        from speech2text_amd.model.encoder.zipformer_streaming import StreamingRecognizer
+        from speech2text_amd.model.utils import AsrMetricConfig
+        if self._tokenizer is None:
+            raise RuntimeError("streaming_recognizer needs the YAML's `tokenizer:` section")
+        if not isinstance(self._decoder.decoder, Identity):
+            raise NotImplementedError("streaming_recognizer serves the Identity decoder only")
+        cfg = AsrMetricConfig(**(self._metric_config or {}))
+        if method is None:
+            method = {"rnnt_beam_search": "beam", "rnnt_greedy_search": "greedy"}.get(cfg.decode_method)
+            if method is None:
+                raise ValueError(f"metric decode_method {cfg.decode_method!r} names no RNN-T search: pass method=")
+        for k in ("max_token_step", "beam_size", "cutoff_top_k"):
+            kw.setdefault(k, getattr(cfg, k))
+        return StreamingRecognizer(self._encoder, self._predictor, self._joiner, self._tokenizer,
+                                   cmvn=self._global_cmvn, batch_size=batch_size, method=method, **kw)
