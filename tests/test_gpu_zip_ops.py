@@ -601,7 +601,10 @@ def N_lib():
 
 
 def _balancer_ref64(x, g, min_mean, max_mean, min_rms, max_rms, grad_scale, swoosh):
-    """reference model/layer/scaling.py:741-789 in closed form (as zk.balancer_backward's torch path), fp64."""
+    """reference model/layer/scaling.py:741-789 in closed form (as zk.balancer_backward's torch path), fp64.
+    Right on live channels only: where a variance is at the 1e-20 clamp it multiplies by 1 / (std var)
+    what autograd sees as a constant.  tests/test_zip_f64.py pins the autograd restatement
+    (tests/zip_f64.py balancer_bwd_ref, the yardstick below) to it on live channels."""
     x, g = x.double(), g.double()
     if swoosh is not None:
         g = g * (torch.sigmoid(x - (4.0 if swoosh else 1.0)) - 0.08)
@@ -624,19 +627,21 @@ def _balancer_ref64(x, g, min_mean, max_mean, min_rms, max_rms, grad_scale, swoo
 @pytest.mark.parametrize("swoosh", [None, True])
 def test_balancer_backward_vs_fp64_closed_form(dev, rows, C, swoosh):
     """s2t_balancer_bwd (reference model/layer/scaling.py:741-789 in closed form; two passes: column
-    statistics, fused update) against the fp64 closed form: channels on both sides of every clamp
+    statistics, fused update) against the reference's own statement in fp64 (autograd through the loss
+    inside backward, tests/zip_f64.py balancer_bwd_ref): channels on both sides of every clamp
     (|mean| / std <= 8: the fp32 statistics' var = E[x^2] - mean^2 keeps four digits), row counts that
     leave ragged tails, channel counts that are no multiple of 64, few channels (C = 4 ... 32 contiguous:
     the flat 16-byte form the frontend's first convolutions take), operands at addresses that are no
     multiple of 16 bytes, a row-strided slice of a wider tensor, with and without the Swoosh derivative
     in front."""
     from speech2text_amd import zip_kernels as zk
+    import zip_f64 as ZF
     g0 = torch.Generator().manual_seed(rows + C)
     x = (torch.randn(rows, C, generator=g0) * torch.logspace(-0.7, 1.0, C) + torch.linspace(-1.5, 1.5, C)).to(dev)
     g = torch.randn(rows, C, generator=g0).to(dev)
     cfg = (-0.05, 0.6, 0.3, 4.0, 0.04)
     out = zk.balancer_backward(x, g, *cfg, 1, swoosh_l=swoosh)
-    ref = _balancer_ref64(x, g, *cfg, swoosh)
+    ref = ZF.balancer_bwd_ref(x.double(), g.double(), *cfg, swoosh=swoosh)
     scale = ref.abs().max().item()
     upd = (out.double() - ref).abs().max().item()
     size = (ref - (g.double() * ((torch.sigmoid(x.double() - 4.0) - 0.08) if swoosh else 1.0))).abs().max().item()
