@@ -607,6 +607,67 @@ int s2t_rnnt_beam_lstm(const S2tRnntLstmDesc* desc, const float* am, const long*
                        int T, int beam_size, int cutoff_top_k, void* workspace, long* tokens,
                        long* frames, long* out_len, float* score, void* stream);
 
+/* ---- chunk-carried (streaming) RNN-T search with the LSTM predictor: the two searches above fed
+ * their frames in pieces (csrc/decode_lstm.hip).  A round's launches ARE the whole-utterance calls'
+ * (one text, the same arguments), and a row's arithmetic does not depend on the rows that share its
+ * launch, so for ANY cut of [0, L) into chunks -- one frame each, different per row, idle calls in
+ * between -- tokens, frames, out_len and score after the last chunk are those of the whole-utterance
+ * call on the concatenated am with lengths = L, bit for bit, and after every chunk those of the
+ * prefix fed so far.  Descriptor and limits as above; Tc in 1..256; max_tokens >= 1.
+ * state: ONE caller-owned device buffer of s2t_rnnt_lstm_stream_state_bytes(desc, B, beam_size,
+ * max_tokens) bytes (beam_size 0 = the greedy state; a multiple of 256), whose size does not depend
+ * on how many chunks or frames a stream sees.  It holds, for R = B * max(1, beam_size) rows, the
+ * LSTM state [layers][R][H] (h and c), the lm vectors [R][V] and per utterance the frames seen since
+ * the reset; greedy adds the count of symbols since the reset; beam adds score and length per beam,
+ * the live-beam count, overflow, stable_len, and two alternating buffers [beam_size][max_tokens] of
+ * token and frame histories (int32) with the index of the one in use.
+ * workspace: s2t_rnnt_lstm_stream_workspace_bytes(desc, B, Tc, beam_size) bytes of scratch, 256-byte
+ * aligned, which calls on one stream may share (one sized for Tc = 256 serves every call): the
+ * per-round vectors, the candidates, the emit / token / parent rows and the counters, the (parent,
+ * class) records [B][Tc][beam_size] of the current chunk only, and for beam the second of the two
+ * alternating state copies.  The LIVE copy is always the state buffer's: frame 0 of a chunk reads
+ * it, and after an odd Tc one launch copies the survivors home, so the launches of a call depend on
+ * its arguments alone.  Both size functions are pure host functions and return 0 for a shape
+ * outside the limits.
+ * s2t_rnnt_lstm_stream_reset: makes every row b with rows[b] != 0 (rows NULL: every row) the empty
+ * hypothesis by the launches the whole-utterance calls start with -- zero (h, c), one predictor step
+ * on blank giving lm, one live beam of score 0, frame counter 0, overflow 0.  Other rows keep their
+ * state bit for bit.  The caller's output arrays are not reset's to write.
+ * A chunk call advances row b over the first min(chunk_len[b], Tc) frames of am [B][Tc][V].
+ * chunk_len[b] <= 0 leaves row b's hypothesis AND the caller's outputs for it as they were; a
+ * finished or idle row never reads am.  Outputs are the result for the whole stream since its reset:
+ * s2t_rnnt_greedy_lstm_chunk: tokens [B][max_tokens] is appended to, so a stream must be given the
+ *   same array on every call; out_len [B].  A symbol past max_tokens is dropped, out_len saturates
+ *   and overflow[b] = 1 -- and the walk GOES ON (the predictor takes the dropped symbol, later
+ *   frames are walked), as s2t_rnnt_greedy_lstm never ends a walk early either.  This differs from
+ *   s2t_rnnt_greedy_stateless_chunk, whose full row is inert until reset.  host_poll = 0 enqueues
+ *   all Tc (max_token_step + 2) rounds and never synchronises; host_poll = 1 enqueues blocks of 32
+ *   rounds with one host read of the live counter each, as s2t_rnnt_greedy_lstm does.  Finished rows
+ *   are inert, so both give the same bits.
+ * s2t_rnnt_beam_lstm_chunk: the best beam's tokens and frames [B][max_tokens] (frames counted from
+ *   the reset), out_len, score, stable_len (the longest common prefix of the live beams' token
+ *   sequences; it never decreases) and overflow, as s2t_rnnt_beam_stateless_chunk: a beam past
+ *   max_tokens keeps its first max_tokens tokens, scores and states stay exact.
+ * s2t_rnnt_beam_lstm_chunk, the reset, and the greedy call with host_poll = 0 make no host
+ * synchronisation and no cooperative launch, and leave nothing behind that depends on host memory:
+ * they can be captured into a graph and replayed.
+ * Return 0; -1 before any launch (outputs untouched) for Tc outside 1..256, state or workspace NULL,
+ * max_tokens < 1, or what the whole-utterance call refuses; B <= 0 returns 0. */
+long s2t_rnnt_lstm_stream_state_bytes(const S2tRnntLstmDesc* desc, int B, int beam_size,
+                                      int max_tokens);
+long s2t_rnnt_lstm_stream_workspace_bytes(const S2tRnntLstmDesc* desc, int B, int Tc, int beam_size);
+int s2t_rnnt_lstm_stream_reset(const S2tRnntLstmDesc* desc, void* state, const int* rows, int B,
+                               int beam_size, int max_tokens, void* workspace, void* stream);
+int s2t_rnnt_greedy_lstm_chunk(const S2tRnntLstmDesc* desc, const float* am, const long* chunk_len,
+                               int B, int Tc, int max_token_step, int max_tokens, int host_poll,
+                               void* state, void* workspace, long* tokens, long* out_len,
+                               int* overflow, void* stream);
+int s2t_rnnt_beam_lstm_chunk(const S2tRnntLstmDesc* desc, const float* am, const long* chunk_len,
+                             int B, int Tc, int beam_size, int cutoff_top_k, int max_tokens,
+                             void* state, void* workspace, long* tokens, long* frames,
+                             long* out_len, float* score, long* stable_len, int* overflow,
+                             void* stream);
+
 /* ---- batched on-device augmentation + collate next to the fbank kernel
  * (dataset/frontend/data_augmentation.py:13-56 AddNoise, :59-118 MixFeats, :150-196 SpecAugment;
  * dataset/utils.py:182-202 batch()).  Random decisions are made on the host as the reference

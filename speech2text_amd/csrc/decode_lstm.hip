@@ -21,6 +21,10 @@
 // blocks of 32 with one host read of the "rows still live" counter per block; a beam search is
 // exactly T rounds (at most one symbol per frame per beam) and never synchronises.
 //
+// The same rounds also run a chunk at a time on caller-owned state (s2t_rnnt_*_lstm_chunk, at the
+// end of this file): the whole-utterance calls and the chunk calls enqueue them through the same
+// host functions.
+//
 // A row's arithmetic does not depend on the rows that share its launch: tiles sit at fixed row
 // positions, every (row, output) sum is taken per lane over k = lane, lane + 64, ... and folded by the
 // same butterfly, and rows beyond R read clamped addresses and are never stored.
@@ -256,7 +260,9 @@ struct Workspace {
   size_t bytes;
 };
 
-Workspace carve(const S2tRnntLstmDesc& d, int B, int T, int beam, void* base) {
+// n_state: how many copies of (h, c, lm) the workspace holds -- two for a whole-utterance search; a
+// chunk call keeps the live copy in the caller's state buffer (beam: one here, greedy: none)
+Workspace carve(const S2tRnntLstmDesc& d, int B, int T, int beam, void* base, int n_state = 2) {
   const size_t R = (size_t)B * (beam > 0 ? beam : 1), L = d.num_layers;
   char* p = static_cast<char*>(base);
   size_t off = 0;
@@ -269,9 +275,9 @@ Workspace carve(const S2tRnntLstmDesc& d, int B, int T, int beam, void* base) {
   auto i = [&](size_t n) { return reinterpret_cast<int*>(take(4 * n)); };
   Workspace w;
   for (int s = 0; s < 2; ++s) {
-    w.h[s] = f(L * R * d.H);
-    w.c[s] = f(L * R * d.H);
-    w.lm[s] = f(R * d.V);
+    w.h[s] = s < n_state ? f(L * R * d.H) : nullptr;
+    w.c[s] = s < n_state ? f(L * R * d.H) : nullptr;
+    w.lm[s] = s < n_state ? f(R * d.V) : nullptr;
   }
   w.x = f(R * d.E);
   w.raw = f(R * 4 * d.H);
@@ -631,6 +637,286 @@ JointArgs joint_args(const S2tRnntLstmDesc& d, const float* am, int T, const Wor
   return JointArgs{am, T, d.V, d.inner, d.act, d.out1_w, d.out1_b, d.out2_w, d.out2_b, w.z, w.mid, w.logit};
 }
 
+// The rounds of a greedy search on the state (h, c, lm), in place: a joint launch and a predictor
+// step each.  host_poll: blocks of kRoundBlock rounds with one host read of the "rows still live"
+// counter per block; else every round is enqueued (finished rows are inert: the same bits).
+int greedy_rounds(const S2tRnntLstmDesc& d, int B, GreedyArgs g, float* h, float* c, float* lm,
+                  const Workspace& w, long max_rounds, int host_poll, hipStream_t st) {
+  for (long r = 0; r < max_rounds;) {
+    for (int q = 0; (q < kRoundBlock || !host_poll) && r < max_rounds; ++q, ++r) {
+      g.parity = (int)(r & 1);
+      hipLaunchKernelGGL(greedy_joint_kernel, dim3(B), dim3(kThreads), 0, st, g);
+      enqueue_pred_step(d, B, w.token, w.emit, nullptr, w.counts + g.parity, h, c, lm, h, c, lm, w, st);
+    }
+    S2T_CHECK_LAUNCH();
+    if (!host_poll) continue;
+    int live = 0;                                          // the one host read of the block
+    hipError_t e = hipMemcpyAsync(&live, w.counts + 3, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return (int)e;
+    if (live <= 0) break;
+  }
+  return 0;
+}
+
+struct StateBuf {
+  float *h, *c, *lm;    // [layers][R][H], [layers][R][H], [R][V]
+};
+
+// The T rounds of a beam search: frame t reads buf[t & 1] and leaves the survivors in buf[~t & 1].
+void beam_rounds(const S2tRnntLstmDesc& d, BeamArgs a, const StateBuf (&buf)[2], const Workspace& w, int T,
+                 hipStream_t st) {
+  const int R = a.B * a.beam;
+  for (int t = 0; t < T; ++t) {
+    const int cur = t & 1, nxt = cur ^ 1;
+    a.t = t;
+    a.parity = cur;
+    a.lm = buf[cur].lm;
+    hipLaunchKernelGGL(beam_expand_kernel, dim3(R), dim3(kThreads), 0, st, a);
+    hipLaunchKernelGGL(beam_select_kernel, dim3(a.B), dim3(kThreads), 0, st, a);
+    enqueue_pred_step(d, R, w.token, w.emit, w.parent, w.counts + cur, buf[cur].h, buf[cur].c, buf[cur].lm,
+                      buf[nxt].h, buf[nxt].c, buf[nxt].lm, w, st);
+  }
+}
+
+// ------------------------------------------------------------------ chunk-carried search
+// The searches above fed their frames in pieces.  A round's launches are the ones above, on the
+// same arguments; what follows only says where the state lives between two calls and turns a
+// chunk's records into histories.  The caller's state buffer holds (h, c, lm) in the layout the
+// round kernels work on ([layers][R][H], [R][V] over all rows of the batch), so a greedy chunk steps
+// it in place and nothing is loaded or stored.  A beam chunk alternates between the state buffer
+// (frame 0 reads it) and one copy in the workspace; after an odd number of rounds the live copy is
+// the workspace's and one launch copies it home, so the launches of a call depend on Tc alone and
+// nothing between two calls depends on host memory.
+constexpr int kMaxChunk = 256;     // frames per chunk call
+constexpr int kStreamHdr = 4;      // ints per row: frames since reset, overflow, history buffer in use, stable_len
+
+struct StreamState {
+  float *h, *c, *lm;
+  float* score;                    // beam: [R]
+  int *blen, *nb;                  // beam: tokens per beam [R] (not clamped), live beams [B]
+  long* n;                         // greedy: symbols since the reset [B] (not clamped)
+  int* hdr;                        // [B][kStreamHdr]
+  int *htok, *hfrm;                // beam: [B][2][beam][max_tokens]
+  size_t bytes;
+};
+
+StreamState carve_state(const S2tRnntLstmDesc& d, int B, int beam, int max_tokens, void* base) {
+  const size_t R = (size_t)B * (beam > 0 ? beam : 1), L = d.num_layers;
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* q = p + off;
+    off += align256(bytes);
+    return q;
+  };
+  StreamState s{};
+  s.h = reinterpret_cast<float*>(take(4 * L * R * d.H));
+  s.c = reinterpret_cast<float*>(take(4 * L * R * d.H));
+  s.lm = reinterpret_cast<float*>(take(4 * R * d.V));
+  s.hdr = reinterpret_cast<int*>(take(4 * (size_t)B * kStreamHdr));
+  if (beam > 0) {
+    s.score = reinterpret_cast<float*>(take(4 * R));
+    s.blen = reinterpret_cast<int*>(take(4 * R));
+    s.nb = reinterpret_cast<int*>(take(4 * (size_t)B));
+    s.htok = reinterpret_cast<int*>(take(4 * 2 * R * max_tokens));
+    s.hfrm = reinterpret_cast<int*>(take(4 * 2 * R * max_tokens));
+  } else {
+    s.n = reinterpret_cast<long*>(take(8 * (size_t)B));
+  }
+  s.bytes = off;
+  return s;
+}
+
+bool stream_ok(const S2tRnntLstmDesc* d, int beam, int max_tokens) {
+  return desc_ok(d) && beam >= 0 && beam <= kMaxBeam && max_tokens >= 1;
+}
+
+struct ResetArgs {
+  const int* rows;      // [B] or NULL
+  int beam, BS, layers, H;   // BS = max(1, beam) rows per utterance
+  float *h, *c, *score;
+  int *blen, *nb, *hdr;
+  long* n;
+  int *emit, *token;    // [R]: the rows that take the first predictor step, on blank
+};
+
+// grid B: a row the mask names becomes the empty hypothesis -- zero (h, c), one live beam of score
+// 0, no tokens, frame 0, no overflow -- and is marked for the predictor step on blank that follows;
+// the other rows are marked idle and keep every bit.
+__global__ __launch_bounds__(kThreads) void stream_reset_kernel(ResetArgs a) {
+  const int b = blockIdx.x, tid = threadIdx.x, BS = a.BS, row0 = b * BS;
+  const long R = (long)gridDim.x * BS;
+  const int on = !a.rows || a.rows[b] != 0;
+  if (tid < BS) {
+    a.emit[row0 + tid] = on;
+    a.token[row0 + tid] = 0;
+  }
+  if (!on) return;
+  for (int l = 0; l < a.layers; ++l)
+    for (int x = tid; x < BS * a.H; x += kThreads) {
+      a.h[(l * R + row0) * a.H + x] = 0.f;
+      a.c[(l * R + row0) * a.H + x] = 0.f;
+    }
+  if (a.beam > 0 && tid < BS) {
+    a.score[row0 + tid] = 0.f;
+    a.blen[row0 + tid] = 0;
+  }
+  if (tid < kStreamHdr) a.hdr[b * kStreamHdr + tid] = 0;
+  if (tid == 0) {
+    if (a.beam > 0) a.nb[b] = 1;
+    else a.n[b] = 0;
+  }
+}
+
+// greedy_init_kernel for a chunk: every row with frames in this chunk is live at its frame 0; no
+// row emits (the carried lm is current: a chunk ends right after a frame advance)
+__global__ void greedy_chunk_init_kernel(const long* chunk_len, int B, int* t, int* nts, int* done, int* emit,
+                                         int* token, int* counts) {
+  __shared__ int live;
+  if (threadIdx.x == 0) live = 0;
+  __syncthreads();
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const long n = chunk_len[b];
+    t[b] = 0;
+    nts[b] = 0;
+    done[b] = n <= 0;
+    emit[b] = 0;
+    token[b] = 0;
+    if (n > 0) atomicAdd(&live, 1);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    counts[0] = 0;
+    counts[1] = 0;
+    counts[2] = B;
+    counts[3] = live;
+  }
+}
+
+__global__ void greedy_chunk_end_kernel(const long* chunk_len, int B, int Tc, int max_tokens, const long* n,
+                                        int* hdr, long* out_len, int* overflow) {
+  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
+    const long Tb = clamped_len(chunk_len, b, Tc);
+    if (Tb <= 0) continue;                                 // an idle stream: state and outputs stay
+    const long nn = n[b];
+    const int ovf = nn > max_tokens ? 1 : 0;               // a symbol was dropped
+    hdr[b * kStreamHdr] += (int)Tb;
+    hdr[b * kStreamHdr + 1] = ovf;
+    out_len[b] = ovf ? max_tokens : nn;
+    overflow[b] = ovf;
+  }
+}
+
+__global__ void beam_chunk_init_kernel(int* counts, int R) {
+  if (threadIdx.x < 4) counts[threadIdx.x] = threadIdx.x == 2 ? R : 0;
+}
+
+__global__ __launch_bounds__(kThreads) void state_copy_kernel(const float* __restrict__ h_src,
+                                                              const float* __restrict__ c_src,
+                                                              const float* __restrict__ lm_src, float* h,
+                                                              float* c, float* lm, long n_state, long n_lm) {
+  const long step = (long)gridDim.x * kThreads;
+  for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n_state; i += step) {
+    h[i] = h_src[i];
+    c[i] = c_src[i];
+  }
+  for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n_lm; i += step) lm[i] = lm_src[i];
+}
+
+struct BeamEndArgs {
+  const long* chunk_len;
+  int Tc, beam, max_tokens;
+  const int *rec, *blen, *nb;   // records [B][Tc][beam] of this chunk; lengths and live beams after it
+  const float* score;
+  int *hdr, *htok, *hfrm;
+  long *tokens, *frames, *out_len;   // [B][max_tokens] twice, [B]
+  float* out_score;
+  long* stable_len;
+  int* overflow;
+};
+
+// grid B, the scheme of csrc/decode_stream.hip: a lane per surviving beam walks the chunk's records
+// back to the beam's ancestor position at chunk start, writing the chunk's emissions to the tail of
+// the beam's new history on the way; a wave per beam copies the ancestor's old history in front of
+// them.  The two history buffers swap roles per chunk (the index is the row's, on the device).
+__global__ __launch_bounds__(kThreads) void beam_chunk_end_kernel(BeamEndArgs a) {
+  __shared__ int s_anc[kMaxBeam], s_base[kMaxBeam], s_len[kMaxBeam];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Tb = (int)clamped_len(a.chunk_len, b, a.Tc);
+  if (Tb <= 0) return;                                     // an idle stream: state and outputs stay
+  const int BS = a.beam, MT = a.max_tokens, row0 = b * BS, nb = a.nb[b];
+  int* hdr = a.hdr + b * kStreamHdr;
+  const int f0 = hdr[0], ovf0 = hdr[1], hcur = hdr[2];
+  const int* otok = a.htok + ((long)b * 2 + hcur) * BS * MT;
+  const int* ofrm = a.hfrm + ((long)b * 2 + hcur) * BS * MT;
+  int* ntok = a.htok + ((long)b * 2 + (hcur ^ 1)) * BS * MT;
+  int* nfrm = a.hfrm + ((long)b * 2 + (hcur ^ 1)) * BS * MT;
+  if (tid < nb) {
+    int pos = tid, left = a.blen[row0 + tid];
+    s_len[tid] = left;
+    for (int t = Tb - 1; t >= 0; --t) {
+      const int r = a.rec[((long)b * a.Tc + t) * BS + pos];
+      const int cls = r >> 4;
+      pos = r & 15;
+      if (cls != 0) {
+        --left;
+        if (left < MT) {
+          ntok[(long)tid * MT + left] = cls;
+          nfrm[(long)tid * MT + left] = f0 + t;
+        }
+      }
+    }
+    s_anc[tid] = pos;                                      // position at chunk start
+    s_base[tid] = left;                                    // = that beam's length there
+  }
+  __syncthreads();
+  for (int i = wave; i < nb; i += kWaves) {
+    const int anc = s_anc[i], m = min(s_base[i], MT);
+    for (int p = lane; p < m; p += 64) {
+      ntok[(long)i * MT + p] = otok[(long)anc * MT + p];
+      nfrm[(long)i * MT + p] = ofrm[(long)anc * MT + p];
+    }
+  }
+  __syncthreads();
+  // outputs: the best beam (position 0), and the prefix all live beams share
+  const int n0 = s_len[0], m0 = min(n0, MT);
+  for (int p = tid; p < m0; p += kThreads) {
+    a.tokens[(long)b * MT + p] = ntok[p];
+    a.frames[(long)b * MT + p] = nfrm[p];
+  }
+  if (wave == 0) {
+    int shortest = m0, longest = n0;
+    for (int i = 1; i < nb; ++i) {
+      shortest = min(shortest, s_len[i]);
+      longest = max(longest, s_len[i]);
+    }
+    int stable = shortest;                                 // first position where two beams differ
+    for (int p = lane; p < shortest; p += 64) {
+      const int t0 = ntok[p];
+      bool same = true;
+      for (int i = 1; i < nb; ++i) same = same && ntok[(long)i * MT + p] == t0;
+      if (!same) {
+        stable = p;
+        break;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) stable = min(stable, __shfl_xor(stable, o, 64));
+    if (lane == 0) {
+      const int ovf = (ovf0 || longest > MT) ? 1 : 0;
+      a.out_len[b] = m0;
+      a.out_score[b] = a.score[row0];
+      a.stable_len[b] = stable;
+      a.overflow[b] = ovf;
+      hdr[0] = f0 + Tb;
+      hdr[1] = ovf;
+      hdr[2] = hcur ^ 1;
+      hdr[3] = stable;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -671,24 +957,9 @@ int s2t_rnnt_greedy_lstm(const S2tRnntLstmDesc* desc, const float* am, const lon
                      w.emit, w.token, w.counts, out_len);
   enqueue_pred_step(d, B, w.token, w.emit, nullptr, w.counts + 2, w.h[0], w.c[0], w.lm[0], w.h[0], w.c[0],
                     w.lm[0], w, st);
-  const long max_rounds = (long)T * (max_token_step + 2);
   GreedyArgs g{joint_args(d, am, T, w), lengths, w.lm[0], max_token_step, T * (max_token_step + 1), 0,
                w.t, w.nts, w.done, w.emit, w.token, w.counts, tokens, out_len};
-  for (long r = 0; r < max_rounds;) {
-    for (int q = 0; q < kRoundBlock && r < max_rounds; ++q, ++r) {
-      g.parity = (int)(r & 1);
-      hipLaunchKernelGGL(greedy_joint_kernel, dim3(B), dim3(kThreads), 0, st, g);
-      enqueue_pred_step(d, B, w.token, w.emit, nullptr, w.counts + g.parity, w.h[0], w.c[0], w.lm[0],
-                        w.h[0], w.c[0], w.lm[0], w, st);
-    }
-    S2T_CHECK_LAUNCH();
-    int live = 0;                                          // the one host read of the block
-    e = hipMemcpyAsync(&live, w.counts + 3, sizeof(int), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return (int)e;
-    if (live <= 0) break;
-  }
-  return 0;
+  return greedy_rounds(d, B, g, w.h[0], w.c[0], w.lm[0], w, (long)T * (max_token_step + 2), 1, st);
 }
 
 int s2t_rnnt_beam_lstm(const S2tRnntLstmDesc* desc, const float* am, const long* lengths, int B,
@@ -712,18 +983,93 @@ int s2t_rnnt_beam_lstm(const S2tRnntLstmDesc* desc, const float* am, const long*
                     w.lm[0], w, st);
   BeamArgs a{joint_args(d, am, T, w), lengths, w.lm[0], 0, B, beam_size, cutoff_top_k, 0, w.cscore, w.score,
              w.ccls, w.blen, w.nb, w.rec, w.emit, w.token, w.parent, w.counts};
-  for (int t = 0; t < T; ++t) {
-    const int cur = t & 1, nxt = cur ^ 1;
-    a.t = t;
-    a.parity = cur;
-    a.lm = w.lm[cur];
-    hipLaunchKernelGGL(beam_expand_kernel, dim3(R), dim3(kThreads), 0, st, a);
-    hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(kThreads), 0, st, a);
-    enqueue_pred_step(d, R, w.token, w.emit, w.parent, w.counts + cur, w.h[cur], w.c[cur], w.lm[cur],
-                      w.h[nxt], w.c[nxt], w.lm[nxt], w, st);
-  }
+  const StateBuf buf[2] = {{w.h[0], w.c[0], w.lm[0]}, {w.h[1], w.c[1], w.lm[1]}};
+  beam_rounds(d, a, buf, w, T, st);
   hipLaunchKernelGGL(beam_trace_kernel, dim3(B), dim3(64), 0, st, lengths, T, beam_size, w.rec, w.blen,
                      w.score, tokens, frames, out_len, score);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+long s2t_rnnt_lstm_stream_state_bytes(const S2tRnntLstmDesc* desc, int B, int beam_size, int max_tokens) {
+  if (B <= 0 || !stream_ok(desc, beam_size, max_tokens)) return 0;
+  return (long)carve_state(*desc, B, beam_size, max_tokens, nullptr).bytes;
+}
+
+long s2t_rnnt_lstm_stream_workspace_bytes(const S2tRnntLstmDesc* desc, int B, int Tc, int beam_size) {
+  if (!desc_ok(desc) || B <= 0 || Tc < 1 || Tc > kMaxChunk || beam_size < 0 || beam_size > kMaxBeam) return 0;
+  return (long)carve(*desc, B, Tc, beam_size, nullptr, beam_size > 0 ? 1 : 0).bytes;
+}
+
+int s2t_rnnt_lstm_stream_reset(const S2tRnntLstmDesc* desc, void* state, const int* rows, int B,
+                               int beam_size, int max_tokens, void* workspace, void* stream) {
+  if (B <= 0) return 0;
+  if (!stream_ok(desc, beam_size, max_tokens) || !state || !workspace) return -1;
+  const S2tRnntLstmDesc& d = *desc;
+  hipStream_t st = (hipStream_t)stream;
+  const int BS = beam_size > 0 ? beam_size : 1, R = B * BS;
+  const StreamState s = carve_state(d, B, beam_size, max_tokens, state);
+  const Workspace w = carve(d, B, 1, beam_size, workspace, beam_size > 0 ? 1 : 0);
+  ResetArgs a{rows, beam_size, BS, d.num_layers, d.H, s.h, s.c, s.score, s.blen, s.nb, s.hdr, s.n, w.emit, w.token};
+  hipLaunchKernelGGL(stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, st, w.emit, R, w.counts + 2);
+  enqueue_pred_step(d, R, w.token, w.emit, nullptr, w.counts + 2, s.h, s.c, s.lm, s.h, s.c, s.lm, w, st);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_rnnt_greedy_lstm_chunk(const S2tRnntLstmDesc* desc, const float* am, const long* chunk_len, int B,
+                               int Tc, int max_token_step, int max_tokens, int host_poll, void* state,
+                               void* workspace, long* tokens, long* out_len, int* overflow, void* stream) {
+  if (B <= 0) return 0;
+  if (!stream_ok(desc, 0, max_tokens) || Tc < 1 || Tc > kMaxChunk || max_token_step < 0 || !state || !workspace)
+    return -1;
+  const S2tRnntLstmDesc& d = *desc;
+  hipStream_t st = (hipStream_t)stream;
+  const StreamState s = carve_state(d, B, 0, max_tokens, state);
+  const Workspace w = carve(d, B, Tc, 0, workspace, 0);
+  hipLaunchKernelGGL(greedy_chunk_init_kernel, dim3(1), dim3(kThreads), 0, st, chunk_len, B, w.t, w.nts, w.done,
+                     w.emit, w.token, w.counts);
+  // the walk's own counter of symbols is the state's: it appends to the caller's tokens at the
+  // stream's length and goes on counting past max_tokens
+  GreedyArgs g{joint_args(d, am, Tc, w), chunk_len, s.lm, max_token_step, max_tokens, 0,
+               w.t, w.nts, w.done, w.emit, w.token, w.counts, tokens, s.n};
+  const int rc = greedy_rounds(d, B, g, s.h, s.c, s.lm, w, (long)Tc * (max_token_step + 2), host_poll, st);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(greedy_chunk_end_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
+                     chunk_len, B, Tc, max_tokens, s.n, s.hdr, out_len, overflow);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_rnnt_beam_lstm_chunk(const S2tRnntLstmDesc* desc, const float* am, const long* chunk_len, int B,
+                             int Tc, int beam_size, int cutoff_top_k, int max_tokens, void* state,
+                             void* workspace, long* tokens, long* frames, long* out_len, float* score,
+                             long* stable_len, int* overflow, void* stream) {
+  if (B <= 0) return 0;
+  if (!stream_ok(desc, beam_size, max_tokens) || beam_size < 1 || Tc < 1 || Tc > kMaxChunk ||
+      cutoff_top_k < 1 || (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam || !state || !workspace)
+    return -1;
+  const S2tRnntLstmDesc& d = *desc;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = B * beam_size;
+  const StreamState s = carve_state(d, B, beam_size, max_tokens, state);
+  const Workspace w = carve(d, B, Tc, beam_size, workspace, 1);
+  hipLaunchKernelGGL(beam_chunk_init_kernel, dim3(1), dim3(64), 0, st, w.counts, R);
+  BeamArgs a{joint_args(d, am, Tc, w), chunk_len, s.lm, 0, B, beam_size, cutoff_top_k, 0, w.cscore, s.score,
+             w.ccls, s.blen, s.nb, w.rec, w.emit, w.token, w.parent, w.counts};
+  const StateBuf buf[2] = {{s.h, s.c, s.lm}, {w.h[0], w.c[0], w.lm[0]}};
+  beam_rounds(d, a, buf, w, Tc, st);
+  if (Tc & 1) {                                            // the live copy goes home
+    const long n_state = (long)d.num_layers * R * d.H, n_lm = (long)R * d.V;
+    const long need = ((n_state > n_lm ? n_state : n_lm) + kThreads - 1) / kThreads;
+    const int blocks = (int)(need < 1024 ? need : 1024);
+    hipLaunchKernelGGL(state_copy_kernel, dim3(blocks), dim3(kThreads), 0, st, w.h[0], w.c[0], w.lm[0], s.h, s.c,
+                       s.lm, n_state, n_lm);
+  }
+  BeamEndArgs e{chunk_len, Tc, beam_size, max_tokens, w.rec, s.blen, s.nb, s.score, s.hdr, s.htok, s.hfrm,
+                tokens, frames, out_len, score, stable_len, overflow};
+  hipLaunchKernelGGL(beam_chunk_end_kernel, dim3(B), dim3(kThreads), 0, st, e);
   S2T_CHECK_LAUNCH();
   return 0;
 }

@@ -11,7 +11,9 @@ whole greedy lattice walk (csrc/decode.hip) and the whole beam search (csrc/deco
 on the device, one workgroup per utterance.  With the LSTM predictor (joiner with or without
 output projection: every LSTM YAML of the reference) both searches run on the device in lockstep
 over the batch (csrc/decode_lstm.hip): per round one lattice move of every live row, a predictor
-step for the rows that emitted, no host synchronisation per move.  Other predictor / joiner
+step for the rows that emitted, no host synchronisation per move.  Both families are also carried
+across chunks of a stream (RnntStreamingSearch, csrc/decode_stream.hip; RnntLstmStreamingSearch,
+csrc/decode_lstm.hip; rnnt_streaming_search picks the class).  Other predictor / joiner
 combinations (the stateless predictor with an out-projection joiner, foreign classes, shapes a
 kernel refuses) keep the module-by-module loop.  The lexicon CTC beam decoder (it wraps
 flashlight) and the CIF decoder are not here."""
@@ -464,8 +466,9 @@ class RnntStreamingSearch:
             raise ValueError(f"method must be 'greedy' or 'beam', got {method!r}")
         p = getattr(predictor, "predictor", predictor)
         if not isinstance(p, StatelessPredictor):
-            raise ValueError("the chunk-carried search takes the stateless predictor only, got "
-                             f"{type(p).__name__} (the LSTM-predictor search is whole-utterance)")
+            raise ValueError("RnntStreamingSearch takes the stateless predictor only, got "
+                             f"{type(p).__name__} (the LSTM predictor is carried across chunks by "
+                             "RnntLstmStreamingSearch; rnnt_streaming_search picks the class)")
         if not isinstance(joiner, Joiner) or joiner._use_out_project:
             raise ValueError("the chunk-carried search takes a Joiner without output projection")
         dev = torch.device("cuda") if device is None else torch.device(device)
@@ -546,6 +549,123 @@ class RnntStreamingSearch:
             N.lp(self.frames), N.lp(self.out_len), N.fp(self.score), N.lp(self.stable_len),
             N.ip(self.overflow), N.stream()), "s2t_rnnt_beam_stateless_chunk")
         return self.tokens, self.frames, self.out_len, self.score, self.stable_len
+
+
+class RnntLstmStreamingSearch:
+    """RnntStreamingSearch for the LSTM predictor and a Joiner with or without output projection
+    (csrc/decode_lstm.hip, s2t_rnnt_*_lstm_chunk): the lockstep device searches fed `am` a chunk at
+    a time.  A round's launches are the whole-utterance calls' own, so however the frames are cut
+    the result after a chunk is rnnt_greedy_lstm_tokens_from_am / rnnt_beam_lstm_tokens_from_am on
+    the frames fed so far, bit for bit.
+
+    Same surface: `state`, `tokens`, `frames`, `out_len`, `score`, `stable_len`, `overflow`,
+    `reset(rows)`, `step(am_chunk, chunk_len)` returning views without a host synchronisation.
+    `capturable=True` (the default) enqueues every greedy round, so a step can be captured into a
+    graph; `capturable=False` lets the greedy step read the device's live counter every 32 rounds
+    and stop early (the same bits; a beam step never synchronises either way).  Greedy past
+    `max_tokens` drops symbols and sets `overflow` but goes on walking, as the whole-utterance LSTM
+    search does.  There is no module-loop fallback: other modules or a shape the kernels refuse are
+    an error at construction."""
+
+    def __init__(self, predictor, joiner, batch_size=1, method="greedy", max_token_step=5,
+                 beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None, capturable=True):
+        if method not in ("greedy", "beam"):
+            raise ValueError(f"method must be 'greedy' or 'beam', got {method!r}")
+        if not _is_lstm_pair(predictor, joiner):
+            raise ValueError("RnntLstmStreamingSearch takes LstmPredictor + Joiner, got "
+                             f"{type(getattr(predictor, 'predictor', predictor)).__name__} + "
+                             f"{type(joiner).__name__} (the stateless predictor: RnntStreamingSearch)")
+        dev = torch.device("cuda") if device is None else torch.device(device)
+        if dev.type != "cuda" or joiner._pre_proj.weight.device.type != "cuda" or \
+                next(predictor.parameters()).device.type != "cuda":
+            raise RuntimeError("the chunk-carried search runs on the GPU only: modules and device must be cuda")
+        self.method, self.batch_size, self.max_tokens = method, int(batch_size), int(max_tokens)
+        self.max_token_step = int(max_token_step)
+        self.beam_size = int(beam_size) if method == "beam" else 0
+        self.cutoff_top_k = int(cutoff_top_k)
+        self.capturable = bool(capturable)
+        self.V = joiner._output_dim
+        B, V = self.batch_size, self.V
+        self._desc, self._keep = rnnt_lstm_desc(predictor, joiner)
+        lib = N.lib()
+        n = ws = 0
+        if self._desc is not None and B > 0:
+            n = lib.s2t_rnnt_lstm_stream_state_bytes(self._desc, B, self.beam_size, self.max_tokens)
+            ws = lib.s2t_rnnt_lstm_stream_workspace_bytes(self._desc, B, 256, self.beam_size)
+        if method == "beam":
+            ok = 1 <= self.beam_size <= N.const("S2T_RNNT_LSTM_MAX_BEAM") and \
+                1 <= min(self.cutoff_top_k, V) <= N.const("S2T_RNNT_LSTM_MAX_BEAM")
+        else:
+            ok = self.max_token_step >= 0
+        if n <= 0 or ws <= 0 or not ok:
+            raise ValueError(f"the chunk-carried LSTM {method} search does not take this shape: B {B} V {V} "
+                             f"beam {self.beam_size} top-k {self.cutoff_top_k} max_token_step "
+                             f"{self.max_token_step} max_tokens {self.max_tokens} (limits: include/s2t_mi355.h)")
+        self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        self._ws = torch.zeros((ws,), dtype=torch.uint8, device=dev)
+        self.tokens = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
+        self.frames = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
+        self.out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
+        self.score = torch.zeros((B,), dtype=torch.float32, device=dev)
+        self.stable_len = torch.zeros((B,), dtype=torch.int64, device=dev)
+        self.overflow = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self._full = {}                                    # Tc -> chunk_len of a whole chunk
+        self.reset()
+
+    def reset(self, rows=None):
+        """Rows (indices, or None for all) become the empty hypothesis (zero LSTM state, one predictor
+        step on blank); their outputs read zero until their next chunk.  The others are not touched."""
+        B = self.batch_size
+        mask = None
+        if rows is not None:
+            mask = torch.zeros((B,), dtype=torch.int32)
+            mask[torch.as_tensor(rows, dtype=torch.int64)] = 1
+            mask = mask.to(self.state.device)
+        N.check(N.lib().s2t_rnnt_lstm_stream_reset(self._desc, N.ptr(self.state), N.ip(mask), B, self.beam_size,
+                                                   self.max_tokens, N.ptr(self._ws), N.stream()),
+                "s2t_rnnt_lstm_stream_reset")
+        for t in (self.tokens, self.frames, self.out_len, self.score, self.stable_len, self.overflow):
+            if mask is None:
+                t.zero_()
+            else:
+                t.masked_fill_(mask.bool().reshape(-1, *[1] * (t.dim() - 1)), 0)
+
+    def step(self, am_chunk, chunk_len=None):
+        """am_chunk (B, Tc, V) fp32 on the device, Tc <= 256; chunk_len (B) int64 on the device
+        (None: Tc frames for every row; 0 leaves a row as it is).  -> greedy (tokens, out_len),
+        beam (tokens, frames, out_len, score, stable_len): views of the fixed output tensors."""
+        B, V = self.batch_size, self.V
+        if am_chunk.dim() != 3 or am_chunk.shape[0] != B or am_chunk.shape[2] != V \
+                or not 1 <= am_chunk.shape[1] <= 256:
+            raise ValueError(f"expected am of shape ({B}, 1..256, {V}), got {tuple(am_chunk.shape)}")
+        Tc = am_chunk.shape[1]
+        if chunk_len is None:
+            chunk_len = self._full.get(Tc)
+            if chunk_len is None:
+                chunk_len = self._full[Tc] = torch.full((B,), Tc, dtype=torch.int64, device=self.state.device)
+        if self.method == "greedy":
+            N.check(N.lib().s2t_rnnt_greedy_lstm_chunk(
+                self._desc, N.fp(am_chunk), N.lp(chunk_len), B, Tc, self.max_token_step, self.max_tokens,
+                0 if self.capturable else 1, N.ptr(self.state), N.ptr(self._ws), N.lp(self.tokens),
+                N.lp(self.out_len), N.ip(self.overflow), N.stream()), "s2t_rnnt_greedy_lstm_chunk")
+            return self.tokens, self.out_len
+        N.check(N.lib().s2t_rnnt_beam_lstm_chunk(
+            self._desc, N.fp(am_chunk), N.lp(chunk_len), B, Tc, self.beam_size, self.cutoff_top_k,
+            self.max_tokens, N.ptr(self.state), N.ptr(self._ws), N.lp(self.tokens), N.lp(self.frames),
+            N.lp(self.out_len), N.fp(self.score), N.lp(self.stable_len), N.ip(self.overflow), N.stream()),
+            "s2t_rnnt_beam_lstm_chunk")
+        return self.tokens, self.frames, self.out_len, self.score, self.stable_len
+
+
+def rnnt_streaming_search(predictor, joiner, batch_size=1, method="greedy", max_token_step=5, beam_size=4,
+                          cutoff_top_k=4, max_tokens=1024, device=None, **kw):
+    """The chunk-carried search that serves the pair: RnntLstmStreamingSearch for LstmPredictor +
+    Joiner (kw: capturable), RnntStreamingSearch otherwise (which raises for what it does not take)."""
+    if _is_lstm_pair(predictor, joiner):
+        return RnntLstmStreamingSearch(predictor, joiner, batch_size, method, max_token_step, beam_size,
+                                       cutoff_top_k, max_tokens, device, **kw)
+    return RnntStreamingSearch(predictor, joiner, batch_size, method, max_token_step, beam_size,
+                               cutoff_top_k, max_tokens, device, **kw)
 
 
 @unique

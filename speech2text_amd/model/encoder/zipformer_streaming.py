@@ -286,19 +286,21 @@ def _state_batch_dim(i: int, n_states: int) -> int:
 
 class StreamingRecognizer:
     """Features in, text out, a chunk at a time: CMVN -> `streaming_step` -> `joiner._enc_proj` -> the
-    chunk-carried RNN-T search (model/decoding.py RnntStreamingSearch) -> the encoder-state update,
+    chunk-carried RNN-T search (model/decoding.py rnnt_streaming_search) -> the encoder-state update,
     captured once and replayed as ONE hipGraph per chunk, in the style of StreamingSession.
 
     Fixed buffers: the features `x` (B, 2*chunk+13, F), `chunk_len` (B) -- how many of the chunk's
     chunk//2 encoder frames are valid per row; 0 leaves a row's hypothesis as it is --, the encoder
     states, the search state and its outputs.  `step` is a copy-in plus one replay and returns views:
-    consume or clone them before the next step.  The search takes the stateless predictor and a
-    joiner without output projection only (an error otherwise: there is no module-loop fallback)."""
+    consume or clone them before the next step.  The search is RnntStreamingSearch for the stateless
+    predictor and a joiner without output projection, RnntLstmStreamingSearch (capturable: every
+    greedy round enqueued) for the LSTM predictor and a joiner with or without one; any other pair
+    is an error: there is no module-loop fallback."""
 
     def __init__(self, encoder, predictor, joiner, tokenizer, cmvn=None, batch_size: int = 1,
                  method: str = "greedy", max_token_step: int = 5, beam_size: int = 4,
                  cutoff_top_k: int = 4, max_tokens: int = 1024, device=None, warmup: int = 2):
-        from speech2text_amd.model.decoding import RnntStreamingSearch
+        from speech2text_amd.model.decoding import rnnt_streaming_search
         model = getattr(encoder, "encoder", encoder)
         if model.training or getattr(predictor, "training", False) or getattr(joiner, "training", False):
             raise RuntimeError("StreamingRecognizer is an inference path: call .eval() first")
@@ -314,8 +316,8 @@ class StreamingRecognizer:
         self.model, self.joiner, self.tokenizer = model, joiner, tokenizer
         self.batch_size, self.chunk, self.Tc = batch_size, chunk, chunk // 2
         self.frames = 2 * chunk + 13
-        self.search = RnntStreamingSearch(predictor, joiner, batch_size, method, max_token_step,
-                                          beam_size, cutoff_top_k, max_tokens, device)
+        self.search = rnnt_streaming_search(predictor, joiner, batch_size, method, max_token_step,
+                                            beam_size, cutoff_top_k, max_tokens, device)
         self.x = torch.zeros(batch_size, self.frames, model._feature_dim, device=device)
         self.chunk_len = torch.full((batch_size,), self.Tc, dtype=torch.int64, device=device)
         self.states = get_init_states(model, batch_size, device)

@@ -200,7 +200,9 @@ class PrunedRnntTask(BaseRnntTask):
         predictor, joiner, tokenizer and global CMVN: features in, text out, a chunk at a time.
         method ("greedy" | "beam"), max_token_step, beam_size and cutoff_top_k come from the task's
         `metric:` section when not given.  The task must be on the GPU and in eval mode; its decoder
-        must be the identity (the search reads the encoder output through joiner._enc_proj)."""
+        must be the identity (the search reads the encoder output through joiner._enc_proj).  The
+        search is the one that serves the task's predictor (model/decoding.py rnnt_streaming_search):
+        stateless with a projection-free joiner, or `predictor.model: Lstm` with either joiner."""
         from speech2text_amd.model.decoder.decoder import Identity
         from speech2text_amd.model.encoder.zipformer_streaming import StreamingRecognizer
         from speech2text_amd.model.utils import AsrMetricConfig
