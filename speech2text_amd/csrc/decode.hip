@@ -9,7 +9,8 @@
 // reference runs a Python loop of predictor / joiner module calls per lattice move; here one
 // workgroup per utterance walks its lattice on the device.  The predictor state is the last
 // `ctx` tokens, so the language-side vector lm = pre_proj(linear(conv(embed(state)))) is
-// recomputed (two wave-per-row GEMVs) only when a symbol is emitted.
+// recomputed (two wave-per-row GEMVs) only when a symbol is emitted.  The walk is decode_search.h's
+// greedy_walk (decode_stream.hip runs it a chunk at a time); the beam searches' records: decode_records.h.
 #include "common.h"
 #include "decode_search.h"
 

@@ -18,7 +18,8 @@
 //      up to 4 beams per pass over the weights (the arithmetic per beam is the greedy kernel's:
 //      with beam_size = cutoff_top_k = 1 the walk is s2t_rnnt_greedy_stateless at
 //      max_token_step = 0, bit for bit).
-// After the last frame the best beam (position 0) is traced back through the records.
+// After the last frame the best beam (position 0) is traced back through the records
+// (decode_records.h trace_best, which also holds the record, the ranking of B and the limits).
 // lm [beam_size][V] lives in LDS when it fits and in the workspace (L2 resident) when it does not.
 #include "common.h"
 #include "decode_search.h"
@@ -26,7 +27,8 @@
 namespace {
 
 using namespace s2t_dec;           // Top, better, wave_top, after, activate (decode_common.h); the
-                                   // constants, BeamShared, recompute_lm, beam_walk (decode_search.h)
+                                   // constants, BeamShared, recompute_lm, beam_walk (decode_search.h);
+                                   // clamped_len, trace_best, align256 (decode_records.h)
 
 struct BeamArgs {
   const float* am;        // [B][T][V]  = enc_proj(encoder_out), bias included
@@ -38,7 +40,7 @@ struct BeamArgs {
   const float* pre_w;     // [V][D]
   const float* pre_b;     // [V]
   int T, V, E, D, ctx, act, blank, beam, topk, lm_in_lds;
-  int* records;           // [B][T][beam]  parent position | class << 4
+  int* records;           // [B][T][beam]  pack_record(parent, class)
   float* lm_spill;        // [B][beam][V]  (used when lm does not fit the LDS)
   long* tokens;           // [B][T]
   long* frames;           // [B][T]
@@ -58,9 +60,7 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_kernel(BeamArgs a) {
   int* state = reinterpret_cast<int*>(h + kGroup * a.D);   // [2][kMaxBeam][ctx], most recent last
   float* lm = a.lm_in_lds ? reinterpret_cast<float*>(state + 2 * kMaxBeam * a.ctx)
                           : a.lm_spill + (long)b * BS * V;  // [beam][V]
-  long Tb = a.lengths[b];
-  if (Tb > a.T) Tb = a.T;
-  if (Tb < 0) Tb = 0;
+  const int Tb = (int)clamped_len(a.lengths, b, a.T);
   if (Tb == 0) {                                           // no frames: no tokens, score 0
     if (tid == 0) {
       a.out_len[b] = 0;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_kernel(BeamArgs a) {
   recompute_lm(a, s.emit, 1, state, s.slot[0], e, h, lm);
   int nb = 1, cur = 0;
   // phases A-D per frame: shared with the chunk-carried kernel (decode_search.h)
-  beam_walk<CACHE>(a, s, amb, (int)Tb, nb, cur, e, h, state, lm,
+  beam_walk<CACHE>(a, s, amb, Tb, nb, cur, e, h, state, lm,
                    [&](int t, int pos, int r) { rec[(long)t * BS + pos] = r; });
 
   // ---- the best beam is position 0: trace its (parent, class) records back
@@ -92,30 +92,10 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_kernel(BeamArgs a) {
     a.out_len[b] = n;
     a.score[b] = s.score[cur][0];
   }
-  int pos = 0, left = n;                                   // tokens still to be found
-  for (int tend = (int)Tb; tend > 0 && left > 0; tend -= kTraceFrames) {
-    const int t0 = max(0, tend - kTraceFrames);
-    for (int x = tid; x < (tend - t0) * BS; x += kThreads) s.trace[x] = rec[(long)t0 * BS + x];
-    __syncthreads();
-    if (tid == 0) {
-      for (int t = tend - 1; t >= t0; --t) {
-        const int r = s.trace[(t - t0) * BS + pos];
-        const int cls = r >> 4;
-        pos = r & 15;
-        if (cls != a.blank) {
-          --left;
-          a.tokens[(long)b * a.T + left] = cls;
-          a.frames[(long)b * a.T + left] = t;
-        }
-      }
-      s.nemit = left;
-    }
-    __syncthreads();
-    left = s.nemit;                                        // every thread leaves with thread 0
-  }
+  trace_best<kThreads>(rec, Tb, BS, a.blank, n, s.trace, &s.nemit, a.tokens + (long)b * a.T,
+                       a.frames + (long)b * a.T);
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 size_t records_bytes(int B, int T, int beam) { return align256(sizeof(int) * (size_t)B * T * beam); }
 
 }  // namespace

@@ -1,6 +1,7 @@
 // Device functions shared by the RNN-T search kernels (csrc/decode_search.h, csrc/decode_lstm.hip):
 // the (value descending, index ascending) order every arg-max / top-k of the searches is taken in,
-// and the joiner's activation.
+// and the joiner's activation.  The searches' bookkeeping -- limits, (parent, class) records, candidate
+// ranking, trace-back, chunk histories -- is csrc/decode_records.h.
 #pragma once
 #include "common.h"
 

@@ -10,7 +10,8 @@
 //             Linears when there are any) and the row's decision -- greedy: arg-max, first index on
 //             ties, and the reference's bookkeeping; beam: log-softmax, the cutoff_top_k best classes,
 //             then (a workgroup per utterance) candidate ranking, selection and trace-back records
-//             in the orders of csrc/decode_beam.hip.  Rows that emitted are counted on the device.
+//             in the orders of csrc/decode_beam.hip, by the functions both share
+//             (csrc/decode_records.h).  Rows that emitted are counted on the device.
 //   predictor for the rows that emitted: LN(embedding[token]); per layer the raw gates
 //             x . x2g^T (+ bias) + h . p2g^T as (16 rows x 16 gate rows) tiles -- a weight matrix is
 //             read once per round and row tile, not once per row -- then g_norm, i / f / cell / o,
@@ -23,29 +24,30 @@
 //
 // The same rounds also run a chunk at a time on caller-owned state (s2t_rnnt_*_lstm_chunk, at the
 // end of this file): the whole-utterance calls and the chunk calls enqueue them through the same
-// host functions.
+// host functions.  A beam chunk's records become histories and outputs by decode_records.h
+// chunk_histories, the scheme csrc/decode_stream.hip keeps written out.
 //
 // A row's arithmetic does not depend on the rows that share its launch: tiles sit at fixed row
 // positions, every (row, output) sum is taken per lane over k = lane, lane + 64, ... and folded by the
 // same butterfly, and rows beyond R read clamped addresses and are never stored.
 #include "common.h"
 #include "decode_common.h"
+#include "decode_records.h"
 #include "../../include/s2t_mi355.h"
 
 namespace {
 
-using namespace s2t_dec;           // Top, better, wave_top, after, activate
+using namespace s2t_dec;           // decode_common.h: Top, better, wave_top, after, activate; decode_records.h:
+                                   // the limits, the record, rank_candidates, trace_best, chunk_histories
 
 constexpr int kTileRows = 16;      // rows of a tile
 constexpr int kTileOuts = 4;       // outputs of a wave: 4 x 16 sums, one per lane after the fold
 constexpr int kTileWaves = 4;      // waves of a tile workgroup: 16 outputs
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxBeam = S2T_RNNT_LSTM_MAX_BEAM;
-constexpr int kMaxCand = kMaxBeam * kMaxBeam;
 constexpr int kRoundBlock = 32;    // greedy rounds between two host reads of the live counter
 static_assert(kMaxCand <= kThreads, "a thread per candidate");
-static_assert(kMaxBeam <= 16, "a record keeps the parent position in 4 bits");
+static_assert(S2T_RNNT_LSTM_MAX_BEAM == s2t_dec::kMaxBeam, "the header's limit is the kernels'");
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -245,8 +247,6 @@ __global__ __launch_bounds__(kThreads) void cell_kernel(CellArgs a) {
 }
 
 // ------------------------------------------------------------------ workspace
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Workspace {
   float *h[2], *c[2], *lm[2];   // state [layers][R][H] twice, lm [R][V] twice
   float *x, *raw, *lin, *dvec;  // LN(embedding) [R][E], raw gates [R][4H], linear(h) [R][D], its LN
@@ -516,11 +516,6 @@ __global__ void beam_init_kernel(int B, int beam, float* score, int* blen, int* 
   }
 }
 
-__device__ __forceinline__ long clamped_len(const long* lengths, int b, int T) {
-  const long n = lengths[b];
-  return n < 0 ? 0 : (n > T ? T : n);
-}
-
 // grid B * beam: the cutoff_top_k best classes of a live beam by (logit descending, class ascending)
 // -- log-softmax is monotone, the order is taken on the logits -- as candidates (beam score +
 // log-probability, class)
@@ -559,7 +554,7 @@ __global__ __launch_bounds__(kThreads) void beam_expand_kernel(BeamArgs a) {
 // in the parent's top-k: the candidate index), keep the beam_size best as the new beams, one
 // (parent, class) record each; the rows' parent / emit / token for the predictor step.
 __global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
-  __shared__ float s_cscore[kMaxCand], s_score[kMaxBeam];
+  __shared__ float s_cscore[kMaxCand];
   __shared__ int s_ccls[kMaxCand], s_pick[kMaxBeam], s_len[kMaxBeam];
   const int b = blockIdx.x, tid = threadIdx.x, BS = a.beam, row0 = b * BS;
   if (b == 0 && tid == 0) a.counts[a.parity ^ 1] = 0;
@@ -577,15 +572,7 @@ __global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
   }
   if (tid < nb) s_len[tid] = a.blen[row0 + tid];
   __syncthreads();
-  if (tid < nc) {
-    const float mine = s_cscore[tid];
-    int rank = 0;
-    for (int q = 0; q < nc; ++q) {
-      const float o = s_cscore[q];
-      rank += (o > mine || (o == mine && q < tid)) ? 1 : 0;
-    }
-    if (rank < nnb) s_pick[rank] = tid;
-  }
+  rank_candidates(s_cscore, nc, nnb, s_pick);
   __syncthreads();
   if (tid < BS) {
     const int row = row0 + tid;
@@ -593,7 +580,7 @@ __global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
       const int q = s_pick[tid], parent = q / K, cls = s_ccls[q];
       a.score[row] = s_cscore[q];
       a.blen[row] = s_len[parent] + (cls != 0 ? 1 : 0);
-      a.rec[((long)b * a.j.T + a.t) * BS + tid] = parent | (cls << 4);
+      a.rec[((long)b * a.j.T + a.t) * BS + tid] = pack_record(parent, cls);
       a.parent[row] = row0 + parent;
       a.emit[row] = cls != 0;
       a.token[row] = cls;
@@ -607,30 +594,18 @@ __global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
 }
 
 // grid B: the best beam is position 0; its (parent, class) records traced back
-__global__ void beam_trace_kernel(const long* lengths, int T, int beam, const int* rec, const int* blen,
-                                  const float* score, long* tokens, long* frames, long* out_len,
-                                  float* out_score) {
+__global__ __launch_bounds__(64) void beam_trace_kernel(const long* lengths, int T, int beam, const int* rec,
+                                                        const int* blen, const float* score, long* tokens,
+                                                        long* frames, long* out_len, float* out_score) {
+  __shared__ int s_trace[kTraceFrames * kMaxBeam], s_left;
   const int b = blockIdx.x;
-  if (threadIdx.x != 0) return;
-  const long Tb = clamped_len(lengths, b, T);
-  if (Tb == 0) {                                           // no frames: no tokens, score 0
-    out_len[b] = 0;
-    out_score[b] = 0.f;
-    return;
+  const int Tb = (int)clamped_len(lengths, b, T), n = Tb ? blen[b * beam] : 0;
+  if (threadIdx.x == 0) {                                  // no frames: no tokens, score 0
+    out_len[b] = n;
+    out_score[b] = Tb ? score[b * beam] : 0.f;
   }
-  int left = blen[b * beam], pos = 0;
-  out_len[b] = left;
-  out_score[b] = score[b * beam];
-  for (long t = Tb - 1; t >= 0 && left > 0; --t) {
-    const int r = rec[((long)b * T + t) * beam + pos];
-    const int cls = r >> 4;
-    pos = r & 15;
-    if (cls != 0) {
-      --left;
-      tokens[(long)b * T + left] = cls;
-      frames[(long)b * T + left] = t;
-    }
-  }
+  trace_best<64>(rec + (long)b * T * beam, Tb, beam, 0, n, s_trace, &s_left, tokens + (long)b * T,
+                 frames + (long)b * T);
 }
 
 JointArgs joint_args(const S2tRnntLstmDesc& d, const float* am, int T, const Workspace& w) {
@@ -688,7 +663,6 @@ void beam_rounds(const S2tRnntLstmDesc& d, BeamArgs a, const StateBuf (&buf)[2],
 // (frame 0 reads it) and one copy in the workspace; after an odd number of rounds the live copy is
 // the workspace's and one launch copies it home, so the launches of a call depend on Tc alone and
 // nothing between two calls depends on host memory.
-constexpr int kMaxChunk = 256;     // frames per chunk call
 constexpr int kStreamHdr = 4;      // ints per row: frames since reset, overflow, history buffer in use, stable_len
 
 struct StreamState {
@@ -836,85 +810,36 @@ struct BeamEndArgs {
   int* overflow;
 };
 
-// grid B, the scheme of csrc/decode_stream.hip: a lane per surviving beam walks the chunk's records
-// back to the beam's ancestor position at chunk start, writing the chunk's emissions to the tail of
-// the beam's new history on the way; a wave per beam copies the ancestor's old history in front of
-// them.  The two history buffers swap roles per chunk (the index is the row's, on the device).
+// grid B: the chunk's records become the beams' new histories and the row's outputs
+// (decode_records.h chunk_histories, the scheme of csrc/decode_stream.hip).  The two history
+// buffers swap roles per chunk (the index is the row's, on the device).
 __global__ __launch_bounds__(kThreads) void beam_chunk_end_kernel(BeamEndArgs a) {
-  __shared__ int s_anc[kMaxBeam], s_base[kMaxBeam], s_len[kMaxBeam];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int s_trace[kTraceFrames * kMaxBeam], s_anc[kMaxBeam], s_base[kMaxBeam], s_len[kMaxBeam];
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int Tb = (int)clamped_len(a.chunk_len, b, a.Tc);
-  if (Tb <= 0) return;                                     // an idle stream: state and outputs stay
+  if (Tb == 0) return;                                     // an idle stream: state and outputs stay
   const int BS = a.beam, MT = a.max_tokens, row0 = b * BS, nb = a.nb[b];
   int* hdr = a.hdr + b * kStreamHdr;
   const int f0 = hdr[0], ovf0 = hdr[1], hcur = hdr[2];
-  const int* otok = a.htok + ((long)b * 2 + hcur) * BS * MT;
-  const int* ofrm = a.hfrm + ((long)b * 2 + hcur) * BS * MT;
-  int* ntok = a.htok + ((long)b * 2 + (hcur ^ 1)) * BS * MT;
-  int* nfrm = a.hfrm + ((long)b * 2 + (hcur ^ 1)) * BS * MT;
-  if (tid < nb) {
-    int pos = tid, left = a.blen[row0 + tid];
-    s_len[tid] = left;
-    for (int t = Tb - 1; t >= 0; --t) {
-      const int r = a.rec[((long)b * a.Tc + t) * BS + pos];
-      const int cls = r >> 4;
-      pos = r & 15;
-      if (cls != 0) {
-        --left;
-        if (left < MT) {
-          ntok[(long)tid * MT + left] = cls;
-          nfrm[(long)tid * MT + left] = f0 + t;
-        }
-      }
-    }
-    s_anc[tid] = pos;                                      // position at chunk start
-    s_base[tid] = left;                                    // = that beam's length there
-  }
-  __syncthreads();
-  for (int i = wave; i < nb; i += kWaves) {
-    const int anc = s_anc[i], m = min(s_base[i], MT);
-    for (int p = lane; p < m; p += 64) {
-      ntok[(long)i * MT + p] = otok[(long)anc * MT + p];
-      nfrm[(long)i * MT + p] = ofrm[(long)anc * MT + p];
-    }
-  }
-  __syncthreads();
-  // outputs: the best beam (position 0), and the prefix all live beams share
-  const int n0 = s_len[0], m0 = min(n0, MT);
-  for (int p = tid; p < m0; p += kThreads) {
-    a.tokens[(long)b * MT + p] = ntok[p];
-    a.frames[(long)b * MT + p] = nfrm[p];
-  }
-  if (wave == 0) {
-    int shortest = m0, longest = n0;
-    for (int i = 1; i < nb; ++i) {
-      shortest = min(shortest, s_len[i]);
-      longest = max(longest, s_len[i]);
-    }
-    int stable = shortest;                                 // first position where two beams differ
-    for (int p = lane; p < shortest; p += 64) {
-      const int t0 = ntok[p];
-      bool same = true;
-      for (int i = 1; i < nb; ++i) same = same && ntok[(long)i * MT + p] == t0;
-      if (!same) {
-        stable = p;
-        break;
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) stable = min(stable, __shfl_xor(stable, o, 64));
-    if (lane == 0) {
-      const int ovf = (ovf0 || longest > MT) ? 1 : 0;
-      a.out_len[b] = m0;
-      a.out_score[b] = a.score[row0];
-      a.stable_len[b] = stable;
-      a.overflow[b] = ovf;
-      hdr[0] = f0 + Tb;
-      hdr[1] = ovf;
-      hdr[2] = hcur ^ 1;
-      hdr[3] = stable;
-    }
-  }
+  int* htok = a.htok + (long)b * 2 * BS * MT;
+  int* hfrm = a.hfrm + (long)b * 2 * BS * MT;
+  if (tid < nb) s_len[tid] = a.blen[row0 + tid];           // (read first by the thread that wrote it)
+  chunk_histories<kThreads>(
+      tid, tid & 63, tid >> 6,
+      ChunkHistoryArgs{Tb, nb, BS, MT, 0, f0, ovf0, a.rec + (long)b * a.Tc * BS, s_len, htok + (long)hcur * BS * MT,
+                       hfrm + (long)hcur * BS * MT, htok + (long)(hcur ^ 1) * BS * MT,
+                       hfrm + (long)(hcur ^ 1) * BS * MT, a.tokens + (long)b * MT, a.frames + (long)b * MT,
+                       s_trace, s_anc, s_base},
+      [&](int out_len, int stable, int ovf) {
+        a.out_len[b] = out_len;
+        a.out_score[b] = a.score[row0];
+        a.stable_len[b] = stable;
+        a.overflow[b] = ovf;
+        hdr[0] = f0 + Tb;
+        hdr[1] = ovf;
+        hdr[2] = hcur ^ 1;
+        hdr[3] = stable;
+      });
 }
 
 }  // namespace

@@ -6,10 +6,12 @@
 //                (256 threads): lm recompute after an emission, arg-max, emit or advance.
 //   beam_walk    phases A-D of s2t_rnnt_beam_stateless (see decode_beam.hip) over frames [0, Tb) of
 //                one row (8 waves); the (parent, class) record of every kept beam goes to a functor.
-// Both take the search state by reference and leave it as the next frame needs it.
+// Both take the search state by reference and leave it as the next frame needs it.  The limits,
+// the record and candidate ranking are decode_records.h's.
 #pragma once
 #include "common.h"
 #include "decode_common.h"
+#include "decode_records.h"
 
 namespace s2t_dec {
 
@@ -95,15 +97,12 @@ __device__ __forceinline__ bool greedy_walk(const A& a, GreedyShared& s, const f
 }
 
 // ------------------------------------------------------------------------------------ beam
-constexpr int kMaxBeam = 16;       // beams, and classes kept per beam
-constexpr int kMaxCand = kMaxBeam * kMaxBeam;
 constexpr int kGroup = 4;          // beams per pass over the predictor weights
 constexpr int kRows = 4;           // weight rows in flight per wave in that pass ...
 constexpr int kCols = 4;           // ... and 64-column steps of each row loaded before they are used
 constexpr int kWaves = 8;          // waves per workgroup
 constexpr int kThreads = 64 * kWaves;
 constexpr int kRegs = 8;           // classes per lane held in registers (V <= 512)
-constexpr int kTraceFrames = 64;   // frames of records staged in LDS per trace-back step
 constexpr size_t kLdsBudget = 60 * 1024;
 
 struct BeamShared {
@@ -248,9 +247,9 @@ __device__ void recompute_lm(const A& a, const int* __restrict__ list, int n,
 }
 
 // Frames [0, Tb) of amb [Tb][V], Tb >= 1, from the nb beams of buffer `cur` (s.score / s.slot / s.len
-// [cur], state [cur], their lm rows): phases A-D per frame.  rec(t, position, parent | class << 4) is
-// called by the lane of every kept beam.  On return nb and cur name the beams after the last
-// frame, best first.  CACHE: V <= 64 kRegs, the frame's am is held in registers and the next
+// [cur], state [cur], their lm rows): phases A-D per frame.  rec(t, position, pack_record(parent,
+// class)) is called by the lane of every kept beam.  On return nb and cur name the beams after the
+// last frame, best first.  CACHE: V <= 64 kRegs, the frame's am is held in registers and the next
 // frame's is fetched a frame ahead.  A: recompute_lm's fields and a.act, a.blank, a.beam, a.topk.
 template <bool CACHE, typename A, typename Rec>
 __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float* __restrict__ amb,
@@ -326,15 +325,7 @@ __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float
     __syncthreads();
     // ---- B: rank the candidates, keep the beam_size best
     const int nc = nb * K, nnb = min(nc, BS), nxt = cur ^ 1;
-    if (tid < nc) {
-      const float mine = s.cscore[tid];
-      int rank = 0;
-      for (int q = 0; q < nc; ++q) {
-        const float o = s.cscore[q];
-        rank += (o > mine || (o == mine && q < tid)) ? 1 : 0;
-      }
-      if (rank < nnb) s.pick[rank] = tid;
-    }
+    rank_candidates(s.cscore, nc, nnb, s.pick);
     __syncthreads();
     // ---- C: the new beams (wave 0, a lane per beam)
     if (wave == 0) {
@@ -346,7 +337,7 @@ __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float
         cls = s.ccls[q];
         s.score[nxt][lane] = s.cscore[q];
         s.len[nxt][lane] = s.len[cur][parent] + (cls != a.blank ? 1 : 0);
-        rec(t, lane, parent | (cls << 4));
+        rec(t, lane, pack_record(parent, cls));
         const int* so = state + (cur * kMaxBeam + parent) * a.ctx;
         int* sn = state + (nxt * kMaxBeam + lane) * a.ctx;
         if (cls == a.blank) {

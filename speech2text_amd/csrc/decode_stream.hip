@@ -20,6 +20,9 @@
 // to the beam's ancestor position at chunk start, writing the chunk's emissions to the tail of the
 // beam's new history on the way; a wave per beam then copies the ancestor's history in front of
 // them.  The two history buffers swap roles per chunk, so a history is never copied onto itself.
+// This is the text of decode_records.h chunk_histories (the LSTM chunk end calls that), kept written
+// out here, with the chunk length clamped by hand: through the shared function, in every form tried,
+// the chunk search measured 1.6-2.4 % slower (profiles/decode_records_resources.txt).
 #include "common.h"
 #include "decode_search.h"
 
@@ -27,10 +30,7 @@ namespace {
 
 using namespace s2t_dec;
 
-constexpr int kMaxChunk = 256;     // frames per chunk call
 constexpr int kHdr = 64;           // bytes of a row's header, and of each [16] array after it
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Layout {                    // byte offsets inside a row of state
   long pstate, lm, rec, htok, hfrm, stride;
@@ -109,10 +109,9 @@ __global__ __launch_bounds__(kGreedyThreads) void rnnt_greedy_chunk_kernel(Greed
   int* hdr = reinterpret_cast<int*>(row);
   int* g_state = reinterpret_cast<int*>(row + a.o_pstate);
   float* g_lm = reinterpret_cast<float*>(row + a.o_lm);
-  long Tb = a.chunk_len[b];
-  if (Tb > a.Tc) Tb = a.Tc;
+  const long Tb = clamped_len(a.chunk_len, b, a.Tc);
   const int n0 = hdr[0], f0 = hdr[1], inert = hdr[2], lm_valid = hdr[3];
-  if (Tb <= 0 || inert) return;        // an idle stream, or a full one: state and outputs stay
+  if (Tb == 0 || inert) return;        // an idle stream, or a full one: state and outputs stay
   for (int k = tid; k < a.ctx; k += kGreedyThreads) state[k] = g_state[k];
   if (lm_valid)
     for (int c = tid; c < a.V; c += kGreedyThreads) lm[c] = g_lm[c];
@@ -177,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamChunkArgs
   int* g_slot = reinterpret_cast<int*>(row + 3 * kHdr);
   int* g_state = reinterpret_cast<int*>(row + a.l.pstate);
   float* g_lm = reinterpret_cast<float*>(row + a.l.lm);
-  int* rec = reinterpret_cast<int*>(row + a.l.rec);        // [Tc][beam]  parent position | class << 4
+  int* rec = reinterpret_cast<int*>(row + a.l.rec);        // [Tc][beam]  pack_record(parent, class)
   int* htok = reinterpret_cast<int*>(row + a.l.htok);      // [2][beam][max_tokens]
   int* hfrm = reinterpret_cast<int*>(row + a.l.hfrm);
 
@@ -227,8 +226,8 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamChunkArgs
     if (tracer) {
       for (int t = tend - 1; t >= t0; --t) {
         const int r = s.trace[(t - t0) * BS + pos];
-        const int cls = r >> 4;
-        pos = r & 15;
+        const int cls = record_class(r);
+        pos = record_parent(r);
         if (cls != a.blank) {
           --left;
           if (left < MT) {

@@ -144,6 +144,12 @@ def _lstm_workspace(desc, B, T, beam, dev):
     return None if n <= 0 else torch.empty((n,), dtype=torch.uint8, device=dev)
 
 
+def _beam_outputs(B, T, dev):
+    """Zeroed outputs of a whole-utterance beam search: tokens, frames (B,T), out_len (B) int64, score (B) fp32."""
+    return (torch.zeros((B, T), dtype=torch.int64, device=dev), torch.zeros((B, T), dtype=torch.int64, device=dev),
+            torch.zeros((B,), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.float32, device=dev))
+
+
 def rnnt_greedy_lstm_tokens_from_am(am, lengths, predictor, joiner, max_token_step=10):
     """Lockstep device greedy search on a given am = joiner._enc_proj(encoder_out), (B,T,V) fp32, LSTM
     predictor.  -> (tokens (B, T (max_token_step + 1)) int64, out_len (B) int64), or None when the
@@ -179,12 +185,9 @@ def rnnt_beam_lstm_tokens_from_am(am, lengths, predictor, joiner, beam_size=4, c
     B, T, V = am.shape
     dev = am.device
     lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
-    tokens = torch.zeros((B, T), dtype=torch.int64, device=dev)
-    frames = torch.zeros((B, T), dtype=torch.int64, device=dev)
-    out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
-    score = torch.zeros((B,), dtype=torch.float32, device=dev)
+    tokens, frames, out_len, score = out = _beam_outputs(B, T, dev)
     if B == 0 or T == 0:
-        return tokens, frames, out_len, score
+        return out
     desc, keep = rnnt_lstm_desc(predictor, joiner)
     beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
     if not 1 <= beam_size <= N.const("S2T_RNNT_LSTM_MAX_BEAM"):
@@ -327,12 +330,9 @@ def rnnt_beam_tokens_from_am(am, lengths, predictor, joiner, beam_size=4, cutoff
     B, T, V = am.shape
     dev = am.device
     lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
-    tokens = torch.zeros((B, T), dtype=torch.int64, device=dev)
-    frames = torch.zeros((B, T), dtype=torch.int64, device=dev)
-    out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
-    score = torch.zeros((B,), dtype=torch.float32, device=dev)
+    tokens, frames, out_len, score = out = _beam_outputs(B, T, dev)
     if B == 0 or T == 0:
-        return tokens, frames, out_len, score
+        return out
     ws = torch.empty((max(1, N.lib().s2t_rnnt_beam_workspace_bytes(B, T, V, int(beam_size))),),
                      dtype=torch.uint8, device=dev)
     conv_w = p._conv.weight.reshape(p._embedding_dim, p._context_size).contiguous()
@@ -447,55 +447,27 @@ class RnntBeamDecoding(DecodingMethod):
         return self.decode_batch(hidden_states, n)[0]
 
 
-class RnntStreamingSearch:
-    """Chunk-carried RNN-T search on the device (csrc/decode_stream.hip): the fused greedy / beam
-    search of the stateless predictor and a projection-free joiner, fed `am = joiner._enc_proj(
-    encoder_out)` a chunk at a time.  However the frames are cut, the result after a chunk is the
-    whole-utterance search's on the frames fed so far, bit for bit (the kernels share their walk).
-
-    Owns the state buffer (one row per stream, size independent of the stream's length) and fixed
-    output tensors; `step` returns views of them, and makes no host synchronisation, so a step can
-    be captured into a graph.  There is no module-loop fallback: a predictor / joiner pair or a
-    shape the fused search does not take is an error at construction."""
+class _ChunkCarriedSearch:
+    """What the two chunk-carried searches share: the settings, the fixed output tensors, `reset`
+    and `step` around the library calls.  A subclass says which modules it takes (`_check_modules`),
+    which shapes, and where its state lives (`_allocate`), and makes the calls (`_reset_state`,
+    `_chunk`)."""
 
     def __init__(self, predictor, joiner, batch_size=1, method="greedy", max_token_step=5,
                  beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None):
-        from speech2text_amd.model.joiner.joiner import Joiner
-        from speech2text_amd.model.predictor.predictor import StatelessPredictor
         if method not in ("greedy", "beam"):
             raise ValueError(f"method must be 'greedy' or 'beam', got {method!r}")
-        p = getattr(predictor, "predictor", predictor)
-        if not isinstance(p, StatelessPredictor):
-            raise ValueError("RnntStreamingSearch takes the stateless predictor only, got "
-                             f"{type(p).__name__} (the LSTM predictor is carried across chunks by "
-                             "RnntLstmStreamingSearch; rnnt_streaming_search picks the class)")
-        if not isinstance(joiner, Joiner) or joiner._use_out_project:
-            raise ValueError("the chunk-carried search takes a Joiner without output projection")
+        on_gpu = self._check_modules(predictor, joiner)
         dev = torch.device("cuda") if device is None else torch.device(device)
-        if dev.type != "cuda" or p._embedding.weight.device.type != "cuda":
+        if dev.type != "cuda" or any(t.device.type != "cuda" for t in on_gpu):
             raise RuntimeError("the chunk-carried search runs on the GPU only: modules and device must be cuda")
         self.method, self.batch_size, self.max_tokens = method, int(batch_size), int(max_tokens)
         self.max_token_step = int(max_token_step)
         self.beam_size = int(beam_size) if method == "beam" else 0
         self.cutoff_top_k = int(cutoff_top_k)
-        self.V, self.E, self.D, self.ctx = joiner._output_dim, p._embedding_dim, p._output_dim, p._context_size
-        self._act = 0 if joiner._act_name == "relu" else 1
-        B, V, E, D, ctx = self.batch_size, self.V, self.E, self.D, self.ctx
-        n = N.lib().s2t_rnnt_stream_state_bytes(B, V, ctx, self.beam_size, self.max_tokens) if B > 0 else 0
-        if method == "beam":
-            ok = 1 <= self.beam_size <= 16 and 1 <= min(self.cutoff_top_k, V) <= 16 \
-                and 16 * (E + D) + 128 * ctx <= 60 * 1024
-        else:
-            ok = self.max_token_step >= 0 and 4 * (E + D + V + ctx) <= 60 * 1024
-        if n <= 0 or not ok or p._embedding.num_embeddings < V:
-            raise ValueError(f"the chunk-carried {method} search does not take this shape: B {B} V {V} "
-                             f"E {E} D {D} ctx {ctx} beam {self.beam_size} top-k {self.cutoff_top_k} "
-                             f"max_tokens {self.max_tokens} (limits: include/s2t_mi355.h)")
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        self._w = [f32(p._embedding.weight), f32(p._conv.weight.reshape(E, ctx)),
-                   f32(p._output_linear.weight), f32(p._output_linear.bias),
-                   f32(joiner._pre_proj.weight), f32(joiner._pre_proj.bias)]
-        self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        self.V = joiner._output_dim
+        self._allocate(predictor, joiner, dev)             # raises for a shape the kernels refuse
+        B = self.batch_size
         self.tokens = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
         self.frames = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
         self.out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
@@ -508,15 +480,12 @@ class RnntStreamingSearch:
     def reset(self, rows=None):
         """Rows (indices, or None for all) become the empty hypothesis; their outputs read zero
         until their next chunk.  The others are not touched."""
-        B = self.batch_size
         mask = None
         if rows is not None:
-            mask = torch.zeros((B,), dtype=torch.int32)
+            mask = torch.zeros((self.batch_size,), dtype=torch.int32)
             mask[torch.as_tensor(rows, dtype=torch.int64)] = 1
             mask = mask.to(self.state.device)
-        N.check(N.lib().s2t_rnnt_stream_reset(N.ptr(self.state), N.ip(mask), B, self.V, self.ctx,
-                                              self.beam_size, self.max_tokens, 0, N.stream()),
-                "s2t_rnnt_stream_reset")
+        self._reset_state(mask)
         for t in (self.tokens, self.frames, self.out_len, self.score, self.stable_len, self.overflow):
             if mask is None:
                 t.zero_()
@@ -536,22 +505,78 @@ class RnntStreamingSearch:
             chunk_len = self._full.get(Tc)
             if chunk_len is None:
                 chunk_len = self._full[Tc] = torch.full((B,), Tc, dtype=torch.int64, device=self.state.device)
+        self._chunk(am_chunk, chunk_len, Tc)
+        if self.method == "greedy":
+            return self.tokens, self.out_len
+        return self.tokens, self.frames, self.out_len, self.score, self.stable_len
+
+
+class RnntStreamingSearch(_ChunkCarriedSearch):
+    """Chunk-carried RNN-T search on the device (csrc/decode_stream.hip): the fused greedy / beam
+    search of the stateless predictor and a projection-free joiner, fed `am = joiner._enc_proj(
+    encoder_out)` a chunk at a time.  However the frames are cut, the result after a chunk is the
+    whole-utterance search's on the frames fed so far, bit for bit (the kernels share their walk).
+
+    Owns the state buffer (one row per stream, size independent of the stream's length) and fixed
+    output tensors; `step` returns views of them, and makes no host synchronisation, so a step can
+    be captured into a graph.  There is no module-loop fallback: a predictor / joiner pair or a
+    shape the fused search does not take is an error at construction."""
+
+    def _check_modules(self, predictor, joiner):
+        from speech2text_amd.model.joiner.joiner import Joiner
+        from speech2text_amd.model.predictor.predictor import StatelessPredictor
+        p = getattr(predictor, "predictor", predictor)
+        if not isinstance(p, StatelessPredictor):
+            raise ValueError("RnntStreamingSearch takes the stateless predictor only, got "
+                             f"{type(p).__name__} (the LSTM predictor is carried across chunks by "
+                             "RnntLstmStreamingSearch; rnnt_streaming_search picks the class)")
+        if not isinstance(joiner, Joiner) or joiner._use_out_project:
+            raise ValueError("the chunk-carried search takes a Joiner without output projection")
+        return [p._embedding.weight]
+
+    def _allocate(self, predictor, joiner, dev):
+        p = getattr(predictor, "predictor", predictor)
+        self.E, self.D, self.ctx = p._embedding_dim, p._output_dim, p._context_size
+        self._act = 0 if joiner._act_name == "relu" else 1
+        B, V, E, D, ctx = self.batch_size, self.V, self.E, self.D, self.ctx
+        n = N.lib().s2t_rnnt_stream_state_bytes(B, V, ctx, self.beam_size, self.max_tokens) if B > 0 else 0
+        if self.method == "beam":
+            ok = 1 <= self.beam_size <= 16 and 1 <= min(self.cutoff_top_k, V) <= 16 \
+                and 16 * (E + D) + 128 * ctx <= 60 * 1024
+        else:
+            ok = self.max_token_step >= 0 and 4 * (E + D + V + ctx) <= 60 * 1024
+        if n <= 0 or not ok or p._embedding.num_embeddings < V:
+            raise ValueError(f"the chunk-carried {self.method} search does not take this shape: B {B} V {V} "
+                             f"E {E} D {D} ctx {ctx} beam {self.beam_size} top-k {self.cutoff_top_k} "
+                             f"max_tokens {self.max_tokens} (limits: include/s2t_mi355.h)")
+        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        self._w = [f32(p._embedding.weight), f32(p._conv.weight.reshape(E, ctx)),
+                   f32(p._output_linear.weight), f32(p._output_linear.bias),
+                   f32(joiner._pre_proj.weight), f32(joiner._pre_proj.bias)]
+        self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
+
+    def _reset_state(self, mask):
+        N.check(N.lib().s2t_rnnt_stream_reset(N.ptr(self.state), N.ip(mask), self.batch_size, self.V, self.ctx,
+                                              self.beam_size, self.max_tokens, 0, N.stream()),
+                "s2t_rnnt_stream_reset")
+
+    def _chunk(self, am_chunk, chunk_len, Tc):
+        B, V = self.batch_size, self.V
         w = [N.fp(t) for t in self._w]
         if self.method == "greedy":
             N.check(N.lib().s2t_rnnt_greedy_stateless_chunk(
                 N.fp(am_chunk), N.lp(chunk_len), *w, B, Tc, V, self.E, self.D, self.ctx, self._act,
                 self.max_token_step, self.max_tokens, 0, N.ptr(self.state), N.lp(self.tokens),
                 N.lp(self.out_len), N.ip(self.overflow), N.stream()), "s2t_rnnt_greedy_stateless_chunk")
-            return self.tokens, self.out_len
+            return
         N.check(N.lib().s2t_rnnt_beam_stateless_chunk(
             N.fp(am_chunk), N.lp(chunk_len), *w, B, Tc, V, self.E, self.D, self.ctx, self._act, 0,
             self.beam_size, self.cutoff_top_k, self.max_tokens, N.ptr(self.state), N.lp(self.tokens),
             N.lp(self.frames), N.lp(self.out_len), N.fp(self.score), N.lp(self.stable_len),
             N.ip(self.overflow), N.stream()), "s2t_rnnt_beam_stateless_chunk")
-        return self.tokens, self.frames, self.out_len, self.score, self.stable_len
 
 
-class RnntLstmStreamingSearch:
+class RnntLstmStreamingSearch(_ChunkCarriedSearch):
     """RnntStreamingSearch for the LSTM predictor and a Joiner with or without output projection
     (csrc/decode_lstm.hip, s2t_rnnt_*_lstm_chunk): the lockstep device searches fed `am` a chunk at
     a time.  A round's launches are the whole-utterance calls' own, so however the frames are cut
@@ -559,7 +584,8 @@ class RnntLstmStreamingSearch:
     the frames fed so far, bit for bit.
 
     Same surface: `state`, `tokens`, `frames`, `out_len`, `score`, `stable_len`, `overflow`,
-    `reset(rows)`, `step(am_chunk, chunk_len)` returning views without a host synchronisation.
+    `reset(rows)` (zero LSTM state, one predictor step on blank), `step(am_chunk, chunk_len)`
+    returning views without a host synchronisation.
     `capturable=True` (the default) enqueues every greedy round, so a step can be captured into a
     graph; `capturable=False` lets the greedy step read the device's live counter every 32 rounds
     and stop early (the same bits; a beam step never synchronises either way).  Greedy past
@@ -569,22 +595,18 @@ class RnntLstmStreamingSearch:
 
     def __init__(self, predictor, joiner, batch_size=1, method="greedy", max_token_step=5,
                  beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None, capturable=True):
-        if method not in ("greedy", "beam"):
-            raise ValueError(f"method must be 'greedy' or 'beam', got {method!r}")
+        self.capturable = bool(capturable)
+        super().__init__(predictor, joiner, batch_size, method, max_token_step, beam_size, cutoff_top_k,
+                         max_tokens, device)
+
+    def _check_modules(self, predictor, joiner):
         if not _is_lstm_pair(predictor, joiner):
             raise ValueError("RnntLstmStreamingSearch takes LstmPredictor + Joiner, got "
                              f"{type(getattr(predictor, 'predictor', predictor)).__name__} + "
                              f"{type(joiner).__name__} (the stateless predictor: RnntStreamingSearch)")
-        dev = torch.device("cuda") if device is None else torch.device(device)
-        if dev.type != "cuda" or joiner._pre_proj.weight.device.type != "cuda" or \
-                next(predictor.parameters()).device.type != "cuda":
-            raise RuntimeError("the chunk-carried search runs on the GPU only: modules and device must be cuda")
-        self.method, self.batch_size, self.max_tokens = method, int(batch_size), int(max_tokens)
-        self.max_token_step = int(max_token_step)
-        self.beam_size = int(beam_size) if method == "beam" else 0
-        self.cutoff_top_k = int(cutoff_top_k)
-        self.capturable = bool(capturable)
-        self.V = joiner._output_dim
+        return [joiner._pre_proj.weight, next(predictor.parameters())]
+
+    def _allocate(self, predictor, joiner, dev):
         B, V = self.batch_size, self.V
         self._desc, self._keep = rnnt_lstm_desc(predictor, joiner)
         lib = N.lib()
@@ -592,69 +614,36 @@ class RnntLstmStreamingSearch:
         if self._desc is not None and B > 0:
             n = lib.s2t_rnnt_lstm_stream_state_bytes(self._desc, B, self.beam_size, self.max_tokens)
             ws = lib.s2t_rnnt_lstm_stream_workspace_bytes(self._desc, B, 256, self.beam_size)
-        if method == "beam":
+        if self.method == "beam":
             ok = 1 <= self.beam_size <= N.const("S2T_RNNT_LSTM_MAX_BEAM") and \
                 1 <= min(self.cutoff_top_k, V) <= N.const("S2T_RNNT_LSTM_MAX_BEAM")
         else:
             ok = self.max_token_step >= 0
         if n <= 0 or ws <= 0 or not ok:
-            raise ValueError(f"the chunk-carried LSTM {method} search does not take this shape: B {B} V {V} "
+            raise ValueError(f"the chunk-carried LSTM {self.method} search does not take this shape: B {B} V {V} "
                              f"beam {self.beam_size} top-k {self.cutoff_top_k} max_token_step "
                              f"{self.max_token_step} max_tokens {self.max_tokens} (limits: include/s2t_mi355.h)")
         self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
         self._ws = torch.zeros((ws,), dtype=torch.uint8, device=dev)
-        self.tokens = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
-        self.frames = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
-        self.out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
-        self.score = torch.zeros((B,), dtype=torch.float32, device=dev)
-        self.stable_len = torch.zeros((B,), dtype=torch.int64, device=dev)
-        self.overflow = torch.zeros((B,), dtype=torch.int32, device=dev)
-        self._full = {}                                    # Tc -> chunk_len of a whole chunk
-        self.reset()
 
-    def reset(self, rows=None):
-        """Rows (indices, or None for all) become the empty hypothesis (zero LSTM state, one predictor
-        step on blank); their outputs read zero until their next chunk.  The others are not touched."""
-        B = self.batch_size
-        mask = None
-        if rows is not None:
-            mask = torch.zeros((B,), dtype=torch.int32)
-            mask[torch.as_tensor(rows, dtype=torch.int64)] = 1
-            mask = mask.to(self.state.device)
-        N.check(N.lib().s2t_rnnt_lstm_stream_reset(self._desc, N.ptr(self.state), N.ip(mask), B, self.beam_size,
-                                                   self.max_tokens, N.ptr(self._ws), N.stream()),
+    def _reset_state(self, mask):
+        N.check(N.lib().s2t_rnnt_lstm_stream_reset(self._desc, N.ptr(self.state), N.ip(mask), self.batch_size,
+                                                   self.beam_size, self.max_tokens, N.ptr(self._ws), N.stream()),
                 "s2t_rnnt_lstm_stream_reset")
-        for t in (self.tokens, self.frames, self.out_len, self.score, self.stable_len, self.overflow):
-            if mask is None:
-                t.zero_()
-            else:
-                t.masked_fill_(mask.bool().reshape(-1, *[1] * (t.dim() - 1)), 0)
 
-    def step(self, am_chunk, chunk_len=None):
-        """am_chunk (B, Tc, V) fp32 on the device, Tc <= 256; chunk_len (B) int64 on the device
-        (None: Tc frames for every row; 0 leaves a row as it is).  -> greedy (tokens, out_len),
-        beam (tokens, frames, out_len, score, stable_len): views of the fixed output tensors."""
-        B, V = self.batch_size, self.V
-        if am_chunk.dim() != 3 or am_chunk.shape[0] != B or am_chunk.shape[2] != V \
-                or not 1 <= am_chunk.shape[1] <= 256:
-            raise ValueError(f"expected am of shape ({B}, 1..256, {V}), got {tuple(am_chunk.shape)}")
-        Tc = am_chunk.shape[1]
-        if chunk_len is None:
-            chunk_len = self._full.get(Tc)
-            if chunk_len is None:
-                chunk_len = self._full[Tc] = torch.full((B,), Tc, dtype=torch.int64, device=self.state.device)
+    def _chunk(self, am_chunk, chunk_len, Tc):
+        B = self.batch_size
         if self.method == "greedy":
             N.check(N.lib().s2t_rnnt_greedy_lstm_chunk(
                 self._desc, N.fp(am_chunk), N.lp(chunk_len), B, Tc, self.max_token_step, self.max_tokens,
                 0 if self.capturable else 1, N.ptr(self.state), N.ptr(self._ws), N.lp(self.tokens),
                 N.lp(self.out_len), N.ip(self.overflow), N.stream()), "s2t_rnnt_greedy_lstm_chunk")
-            return self.tokens, self.out_len
+            return
         N.check(N.lib().s2t_rnnt_beam_lstm_chunk(
             self._desc, N.fp(am_chunk), N.lp(chunk_len), B, Tc, self.beam_size, self.cutoff_top_k,
             self.max_tokens, N.ptr(self.state), N.ptr(self._ws), N.lp(self.tokens), N.lp(self.frames),
             N.lp(self.out_len), N.fp(self.score), N.lp(self.stable_len), N.ip(self.overflow), N.stream()),
             "s2t_rnnt_beam_lstm_chunk")
-        return self.tokens, self.frames, self.out_len, self.score, self.stable_len
 
 
 def rnnt_streaming_search(predictor, joiner, batch_size=1, method="greedy", max_token_step=5, beam_size=4,

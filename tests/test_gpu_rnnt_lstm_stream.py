@@ -131,6 +131,28 @@ def test_beam_chunks_equal_the_whole_utterance_search(dev, name, partition):
     assert int(search.overflow.sum()) == 0
 
 
+@pytest.mark.parametrize("name", list(SC.LONG_CASES))
+def test_long_chunks_cross_the_trace_blocks(dev, name):
+    """90-frame rows: the whole-utterance trace-back and the chunk end both stage their records in
+    blocks of 64 frames.  The whole-utterance call gives the float64 tokens and frames; the stream
+    fed one 90-frame chunk, 70 + 20 frames and 7-frame chunks equals it bit for bit, with the same
+    stable_len after the last chunk."""
+    c, p, j, am, lens, ref = _case(dev, name)
+    want = _one_shot(dev, name)
+    for b, (tok, _, frm, _) in enumerate(ref):
+        n = int(want[2][b])
+        assert want[0][b, :n].tolist() == tok and want[1][b, :n].tolist() == frm, b
+    stable = []
+    for step in (90, 70, 7):
+        search = _stream(dev, name)
+        got, off = SS._feed(search, am, SS._regular(_lens(name), step))
+        assert off.tolist() == _lens(name).tolist()
+        SS._same_rows(got, want)
+        assert int(search.overflow.sum()) == 0
+        stable.append(got[4].tolist())
+    assert stable[0] == stable[1] == stable[2], stable
+
+
 # ------------------------------------------------------------------------------------ 3. prefix answer
 @functools.lru_cache(maxsize=None)
 def _run7(dev, name):

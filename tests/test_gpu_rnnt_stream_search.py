@@ -401,6 +401,30 @@ def test_degenerate_beam_chunks_equal_greedy_chunks(dev, golden_dir):
             assert torch.equal(bm[0][b, :int(g[1][b])], g[0][b, :int(g[1][b])]), b
 
 
+def test_long_chunks_cross_the_trace_blocks(dev, golden_dir):
+    """Chunks of more than 64 frames: the chunk end stages its records in 64-frame blocks, as the
+    whole-utterance trace-back does.  Rows 0-7 of the seeded 64 x 90 input at beam 4 / top-k 4: a
+    chunk per row, 70 + the rest, and 7-frame chunks equal the whole-utterance search bit for bit and
+    end with the same stable_len.  Row 0 (90 frames: the blocks [26, 90) and [0, 26)) emits on both
+    sides of both block edges; tests/test_rnnt_beam.py asserts the same of the float64 restatement."""
+    c = TB._fixture(golden_dir)[0]
+    am, lens = TB._long_input(c)
+    assert int(lens[0]) == 90
+    want = TB._search(c, am, lens, dev, beam=4, topk=4)
+    frames0 = want[1][0, :int(want[2][0])].tolist()
+    assert min(frames0) < 26 and max(frames0) >= 64, frames0
+    modules = TB._modules(c, dev)
+    stable = []
+    for step in (90, 70, 7):
+        search = _stream(c, dev, 8, beam=4, topk=4, max_tokens=90, modules=modules)
+        got, off = _feed(search, am.to(dev), _regular(lens, step))
+        assert off.tolist() == lens.tolist()
+        _same_rows(got, want)
+        assert int(search.overflow.sum()) == 0
+        stable.append(got[4].tolist())
+    assert stable[0] == stable[1] == stable[2], stable
+
+
 # ------------------------------------------------------------------------------------ recogniser
 def _tiny_stream_encoder(golden_dir, dev):
     from speech2text_amd.model.encoder.zipformer import Zipformer2, Zipformer2Config

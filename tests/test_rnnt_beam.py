@@ -121,6 +121,27 @@ def test_factory_and_metric_config():
         AsrMetric(_tokenizer(40), AsrMetricConfig(decode_method="ctc_lexicon_beam_search"))
 
 
+def _long_input(c):
+    """Rows 0-7 of the seeded 64 x 90 input of test_degenerate_beam_equals_the_greedy_kernel (row 0 has
+    90 frames): longer than one 64-frame block of the staged trace-back (csrc/decode_records.h)."""
+    g = torch.Generator().manual_seed(17)
+    am = torch.randn(64, 90, c["V"], generator=g) * 3.0
+    lens = torch.randint(1, 91, (64,), generator=g)
+    lens[0] = 90
+    return am[:8].contiguous(), lens[:8].numpy()
+
+
+def test_long_input_emits_on_both_sides_of_the_trace_blocks(golden_dir):
+    """What tests/test_gpu_rnnt_stream_search.py::test_long_chunks_cross_the_trace_blocks relies on, by
+    the float64 restatement: at beam 4 / top-k 4 the best beam of row 0 (90 frames: blocks [26, 90)
+    and [0, 26)) has a token at a frame < 26 and one at a frame >= 64."""
+    c = _fixture(golden_dir)[0]
+    am, lens = _long_input(c)
+    assert int(lens[0]) == 90
+    _, _, frames, _ = R.beam_search(am[0].numpy(), _params(c), c["ctx"], c["act"], 4, 4)
+    assert min(frames) < 26 and max(frames) >= 64, frames
+
+
 def _fixture_free_config(V=40, D=48, E=32, ctx=3, act="relu", seed=5, scale=1.0):
     g = np.random.default_rng(seed)
     c = {"V": V, "D": D, "E": E, "ctx": ctx, "act": act}

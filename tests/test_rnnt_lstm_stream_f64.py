@@ -1,6 +1,7 @@
 """CPU: the chunked float64 restatement of tests/rnnt_lstm_stream_f64.py is the whole-utterance
 restatement of tests/rnnt_lstm_search_f64.py however the frames are cut, and the two longer beam
-cases of tests/rnnt_lstm_stream_cases.py are what the GPU file takes them for."""
+cases and the two 90-frame cases of tests/rnnt_lstm_stream_cases.py are what the GPU file takes them
+for."""
 import pytest
 import torch
 
@@ -75,3 +76,21 @@ def test_the_longer_cases_are_decided_and_not_trivial(name):
         boundaries += sum(0 < s < n for s, n in zip(got[4], best7))
     print(f"{name}: 0 < common prefix < best length on {between} of {frames} frames")
     assert between > frames // 4 and boundaries > 0
+
+
+@pytest.mark.parametrize("name", list(SC.LONG_CASES))
+def test_the_long_cases_cross_the_trace_blocks(name):
+    """Rows of 90, 0 and 90 (93 clamped) frames; margin >= 1e-3 on every utterance; float32 gives
+    float64's tokens and frames; the best beam of row 0 has a token at a frame < 26 and one at a
+    frame >= 64, the edges of the 64-frame blocks a 90-frame trace-back is staged in."""
+    c = SC.CASES[name]
+    lens = SC.make(name)[3].tolist()
+    assert SC.lengths(name) == [90, 0, 90] and lens[2] == 93
+    ref, f32 = SC.reference(name), SC.evaluate(name, torch.float32)
+    for b, (r, q) in enumerate(zip(ref, f32)):
+        print(f"{name} row {b}: {len(r[0])} tokens, first frame {r[2][:1]}, margin {r[3]:.2e}")
+        assert r[3] >= S.MARGIN, (name, b, r[3])
+        assert q[0] == r[0] and q[2] == r[2], (name, b)
+    assert ref[1][0] == [] and ref[1][1] == 0.0
+    frames = ref[0][2]
+    assert min(frames) < 26 and max(frames) >= 64, (name, frames)
