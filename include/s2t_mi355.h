@@ -59,6 +59,42 @@ int s2t_rnnt_simple_bwd(const float* am_probs, const float* lm_probs, const floa
                         const float* G_lm, const float* dpx, const float* dpy,
                         const float* gscale, const long* symbols, int B, int S, int T, int C,
                         int blank, float* d_am, float* d_lm, int accumulate, void* stream);
+/* k2.rnnt_loss_smoothed with lm_only_scale = lam and/or am_only_scale = mu non-zero (both >= 0,
+ * lam + mu < 1; alpha = 1 - lam - mu).  With both 0 the three entry points above are the whole
+ * path and none of these is called.  am_probs / lm_probs / am_max / lm_max are s2t_rnnt_row_exp's,
+ * nrm their product, as above.
+ *   stats: lm_sum [B][S+1] = sum_c lm_probs (so Ll = log lm_sum + lm_max, q = lm_probs / lm_sum).
+ *     With mu != 0 also the unigram u [C] = mean of q over ALL B (S+1) rows, padded ones included
+ *     (+ the smallest normal float, as k2), log_u [C], and am_dot [B][T] = sum_c am_probs u (so
+ *     La = log am_dot + am_max); u is reduced column-parallel over slabs of
+ *     S2T_RNNT_SMOOTH_LM_SLAB rows into u_part [ceil(B (S+1) / slab)][C], then in one final pass.
+ *     With mu == 0 u, log_u, am_dot and u_part are not touched and may be NULL.
+ *   pxpy: px / py = alpha (joint) + lam (lm only) + mu (am only) log-probs at the symbol / at the
+ *     blank, written in one pass (column T of px and column T_b stay -inf); a scale that is exactly
+ *     0 drops its term.
+ *   bwd: what s2t_rnnt_simple_bwd does, from the same G_am / G_lm (products of s2t_rnnt_simple_w's
+ *     W, which the row kernels scale by alpha), with the lm-only / am-only softmax terms and, for
+ *     mu != 0, the gradient through u: the am rows' share of d loss / d log u is reduced over
+ *     slabs of S2T_RNNT_SMOOTH_AM_SLAB rows into dlogu_part [ceil(B T / slab)][C], summed into
+ *     v [C] = dlogu / (u B (S+1)), and fed to every lm row.  With mu == 0 dlogu_part and v may be
+ *     NULL.  C may be at most S2T_RNNT_SMOOTH_MAX_C (two rows per wave in LDS); wider returns -1. */
+#define S2T_RNNT_SMOOTH_LM_SLAB 64
+#define S2T_RNNT_SMOOTH_AM_SLAB 32
+#define S2T_RNNT_SMOOTH_MAX_C 2048
+int s2t_rnnt_smooth_stats(const float* am_probs, const float* lm_probs, int B, int S, int T, int C,
+                          float mu, float* lm_sum, float* u_part, float* u, float* log_u,
+                          float* am_dot, void* stream);
+int s2t_rnnt_smooth_pxpy(const float* am, const float* lm, const float* am_max,
+                         const float* lm_max, const float* nrm, const float* lm_sum,
+                         const float* am_dot, const float* log_u, const long* symbols,
+                         const long* boundary, int B, int S, int T, int C, int blank, float lam,
+                         float mu, float* px, float* py, void* stream);
+int s2t_rnnt_smooth_bwd(const float* am_probs, const float* lm_probs, const float* G_am,
+                        const float* G_lm, const float* dpx, const float* dpy,
+                        const float* gscale, const long* symbols, const float* lm_sum,
+                        const float* am_dot, const float* u, int B, int S, int T, int C, int blank,
+                        float lam, float mu, float* dlogu_part, float* v, float* d_am, float* d_lm,
+                        void* stream);
 int s2t_mutual_info_fwd(const float* px, const float* py, const long* boundary, int B, int S,
                         int T, float* p, float* ans, void* stream);
 int s2t_mutual_info_bwd(const float* px, const float* py, const long* boundary, const float* p,

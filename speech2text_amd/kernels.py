@@ -183,18 +183,42 @@ def mutual_information(px, py, boundary, want_grads=True):
     return ans, p, gx, gy
 
 
+RNNT_SMOOTH_MAX_C = N.const("S2T_RNNT_SMOOTH_MAX_C")
+_SMOOTH_LM_SLAB = N.const("S2T_RNNT_SMOOTH_LM_SLAB")
+_SMOOTH_AM_SLAB = N.const("S2T_RNNT_SMOOTH_AM_SLAB")
+
+
+def check_smoothing_scales(lm_only_scale, am_only_scale):
+    """k2.rnnt_loss_smoothed's weights: the joint term keeps alpha = 1 - lm_only - am_only, which
+    must stay positive (with alpha <= 0 the -inf columns of px turn into NaN)."""
+    lam, mu = float(lm_only_scale), float(am_only_scale)
+    if not (lam >= 0.0 and mu >= 0.0 and lam + mu < 1.0):
+        raise ValueError(f"smoothed RNN-T loss: lm_only_scale={lm_only_scale} and am_only_scale="
+                         f"{am_only_scale} must be >= 0 with a sum below 1")
+    return lam, mu
+
+
 class _SimpleRnntLoss(torch.autograd.Function):
-    """k2.rnnt_loss_smoothed(lm, am, symbols, blank, lm_only_scale=0, am_only_scale=0,
-    boundary, reduction='none', return_grad=True) -> (neg scores (B,), px_grad, py_grad)."""
+    """k2.rnnt_loss_smoothed(lm, am, symbols, blank, lm_only_scale, am_only_scale, boundary,
+    reduction='none', return_grad=True) -> (neg scores (B,), px_grad, py_grad).  With both scales
+    0 the launches are those of the unsmoothed path; a non-zero scale adds csrc/rnnt_smooth.hip's
+    row statistics and swaps the px/py pass and the two backward row kernels for their smoothed
+    forms.  With am_only_scale != 0 the utterances of a batch are coupled through the batch's
+    unigram u (the mean of softmax(lm) over all B (S+1) rows, padded ones included)."""
 
     @staticmethod
-    def forward(ctx, lm, am, symbols, boundary, blank):
+    def forward(ctx, lm, am, symbols, boundary, blank, lam, mu):
         _dev_check(lm, am)
         lm = lm.contiguous().float()
         am = am.contiguous().float()
         B, T, C = am.shape
         S = lm.shape[1] - 1
         _check_lattice_rows(S)
+        smooth = lam != 0.0 or mu != 0.0
+        if smooth and C > RNNT_SMOOTH_MAX_C:
+            raise ValueError(f"smoothed RNN-T loss: joiner dimension {C} exceeds the kernel's "
+                             f"limit of {RNNT_SMOOTH_MAX_C} (two rows per wave are held in LDS, "
+                             "csrc/rnnt_smooth.hip); there is no fallback")
         dev = am.device
         L = N.lib()
         st = N.stream()
@@ -214,20 +238,49 @@ class _SimpleRnntLoss(torch.autograd.Function):
             nrm = zk.batched_matmul(0, lm_p, am_p)                       # (B,S+1,T)
         px = torch.empty((B, S, T + 1), dtype=torch.float32, device=dev)
         py = torch.empty((B, S + 1, T), dtype=torch.float32, device=dev)
-        # (two gathered operands per lattice arc -- am / lm at the arc's symbol or at blank -- the normaliser once)
-        N.PROF[0] and N.profile_note("s2t_rnnt_simple_pxpy", 4.0 * (3 * px.numel() + 3 * py.numel() + nrm.numel()))
-        N.check(L.s2t_rnnt_simple_pxpy(N.fp(am), N.fp(lm), N.fp(am_max), N.fp(lm_max),
-                                       N.fp(nrm), N.lp(symbols), N.lp(boundary), B, S, T, C,
-                                       int(blank), N.fp(px), N.fp(py), st), "simple_pxpy")
+        lm_sum = u = am_dot = None
+        if not smooth:
+            # (two gathered operands per lattice arc -- am / lm at the arc's symbol or at blank -- the normaliser once)
+            N.PROF[0] and N.profile_note("s2t_rnnt_simple_pxpy", 4.0 * (3 * px.numel() + 3 * py.numel() + nrm.numel()))
+            N.check(L.s2t_rnnt_simple_pxpy(N.fp(am), N.fp(lm), N.fp(am_max), N.fp(lm_max),
+                                           N.fp(nrm), N.lp(symbols), N.lp(boundary), B, S, T, C,
+                                           int(blank), N.fp(px), N.fp(py), st), "simple_pxpy")
+        else:
+            lm_sum = torch.empty((B, S + 1), dtype=torch.float32, device=dev)
+            u_part = log_u = None
+            stats_bytes = 4.0 * (lm_p.numel() + lm_sum.numel())
+            if mu != 0.0:
+                parts = (B * (S + 1) + _SMOOTH_LM_SLAB - 1) // _SMOOTH_LM_SLAB
+                u_part = torch.empty((parts, C), dtype=torch.float32, device=dev)
+                u = torch.empty((C,), dtype=torch.float32, device=dev)
+                log_u = torch.empty((C,), dtype=torch.float32, device=dev)
+                am_dot = torch.empty((B, T), dtype=torch.float32, device=dev)
+                # lm_probs once more for the column sums, the partials out and in, am_probs once
+                stats_bytes += 4.0 * (lm_p.numel() + lm_sum.numel() + 2 * u_part.numel() + 3 * C
+                                      + am_p.numel() + am_dot.numel())
+            N.PROF[0] and N.profile_note("s2t_rnnt_smooth_stats", stats_bytes)
+            N.check(L.s2t_rnnt_smooth_stats(N.fp(am_p), N.fp(lm_p), B, S, T, C, mu, N.fp(lm_sum),
+                                            N.fp(u_part), N.fp(u), N.fp(log_u), N.fp(am_dot), st),
+                    "smooth_stats")
+            # simple_pxpy's traffic, the row scalars and (mu) log u at the arc's class on top
+            N.PROF[0] and N.profile_note("s2t_rnnt_smooth_pxpy",
+                                         4.0 * ((3 + (mu != 0.0)) * (px.numel() + py.numel()) + nrm.numel()
+                                                + lm_sum.numel() + (B * T if mu != 0.0 else 0)))
+            N.check(L.s2t_rnnt_smooth_pxpy(N.fp(am), N.fp(lm), N.fp(am_max), N.fp(lm_max),
+                                           N.fp(nrm), N.fp(lm_sum), N.fp(am_dot), N.fp(log_u),
+                                           N.lp(symbols), N.lp(boundary), B, S, T, C, int(blank),
+                                           lam, mu, N.fp(px), N.fp(py), st), "smooth_pxpy")
         ans, _, gx, gy = mutual_information(px, py, boundary)
-        ctx.save_for_backward(am_p, lm_p, nrm, gx, gy, symbols)
+        extra = () if not smooth else (lm_sum,) if mu == 0.0 else (lm_sum, u, am_dot)
+        ctx.save_for_backward(am_p, lm_p, nrm, gx, gy, symbols, *extra)
         ctx.blank = int(blank)
+        ctx.lam, ctx.mu = lam, mu
         ctx.mark_non_differentiable(gx, gy)
         return -ans, gx, gy
 
     @staticmethod
     def backward(ctx, g_loss, _gx, _gy):
-        am_p, lm_p, nrm, gx, gy, symbols = ctx.saved_tensors
+        am_p, lm_p, nrm, gx, gy, symbols = ctx.saved_tensors[:6]
         B, T, C = am_p.shape
         S = lm_p.shape[1] - 1
         L = N.lib()
@@ -243,16 +296,36 @@ class _SimpleRnntLoss(torch.autograd.Function):
             G_lm = zk.batched_matmul(1, W, am_p)                  # W @ exp(am):   (B,S+1,C)
         d_am = torch.empty_like(am_p)
         d_lm = torch.empty_like(lm_p)
-        N.PROF[0] and N.profile_note("s2t_rnnt_simple_bwd", 12.0 * (am_p.numel() + lm_p.numel())
-                                     + 4.0 * (gx.numel() + gy.numel()))
-        N.check(L.s2t_rnnt_simple_bwd(N.fp(am_p), N.fp(lm_p), N.fp(G_am), N.fp(G_lm), N.fp(gx),
-                                      N.fp(gy), N.fp(gscale), N.lp(symbols), B, S, T, C,
-                                      ctx.blank, N.fp(d_am), N.fp(d_lm), 0, st), "simple_bwd")
-        return d_lm, d_am, None, None, None
+        if ctx.lam == 0.0 and ctx.mu == 0.0:
+            N.PROF[0] and N.profile_note("s2t_rnnt_simple_bwd", 12.0 * (am_p.numel() + lm_p.numel())
+                                         + 4.0 * (gx.numel() + gy.numel()))
+            N.check(L.s2t_rnnt_simple_bwd(N.fp(am_p), N.fp(lm_p), N.fp(G_am), N.fp(G_lm), N.fp(gx),
+                                          N.fp(gy), N.fp(gscale), N.lp(symbols), B, S, T, C,
+                                          ctx.blank, N.fp(d_am), N.fp(d_lm), 0, st), "simple_bwd")
+            return d_lm, d_am, None, None, None, None, None
+        lm_sum = ctx.saved_tensors[6]
+        u = am_dot = dlogu_part = v = None
+        extra = 0
+        if ctx.mu != 0.0:
+            u, am_dot = ctx.saved_tensors[7:9]
+            parts = (B * T + _SMOOTH_AM_SLAB - 1) // _SMOOTH_AM_SLAB
+            dlogu_part = torch.empty((parts, C), dtype=torch.float32, device=am_p.device)
+            v = torch.empty((C,), dtype=torch.float32, device=am_p.device)
+            # the partials out and in, lm_probs once more for q.v, the gradients once more for colsum
+            extra = 2 * dlogu_part.numel() + lm_p.numel() + gx.numel() + 3 * C + B * T
+        N.PROF[0] and N.profile_note("s2t_rnnt_smooth_bwd", 12.0 * (am_p.numel() + lm_p.numel())
+                                     + 4.0 * (gx.numel() + gy.numel() + lm_sum.numel() + extra))
+        N.check(L.s2t_rnnt_smooth_bwd(N.fp(am_p), N.fp(lm_p), N.fp(G_am), N.fp(G_lm), N.fp(gx),
+                                      N.fp(gy), N.fp(gscale), N.lp(symbols), N.fp(lm_sum),
+                                      N.fp(am_dot), N.fp(u), B, S, T, C, ctx.blank, ctx.lam, ctx.mu,
+                                      N.fp(dlogu_part), N.fp(v), N.fp(d_am), N.fp(d_lm), st),
+                "smooth_bwd")
+        return d_lm, d_am, None, None, None, None, None
 
 
-def rnnt_simple_loss(lm, am, symbols, boundary, blank=0):
-    return _SimpleRnntLoss.apply(lm, am, symbols, boundary, blank)
+def rnnt_simple_loss(lm, am, symbols, boundary, blank=0, lm_only_scale=0.0, am_only_scale=0.0):
+    lam, mu = check_smoothing_scales(lm_only_scale, am_only_scale)
+    return _SimpleRnntLoss.apply(lm, am, symbols, boundary, blank, lam, mu)
 
 
 def rnnt_prune_ranges(px_grad, py_grad, boundary, s_range):

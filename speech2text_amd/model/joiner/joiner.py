@@ -73,9 +73,7 @@ class Joiner(nn.Module):
         self._prune_range = config.prune_range
         self._lm_scale = config.lm_scale
         self._am_scale = config.am_scale
-        if self._lm_scale != 0.0 or self._am_scale != 0.0:
-            raise NotImplementedError("lm_scale/am_scale != 0 (smoothed simple loss) is not on "
-                                      "the accelerated path; every shipped YAML uses 0.0")
+        K.check_smoothing_scales(self._lm_scale, self._am_scale)
 
     @property
     def prune_range(self) -> int:
@@ -95,8 +93,11 @@ class Joiner(nn.Module):
             dev = am.device
             boundary = K.make_boundary(target_lengths, encoder_out_lengths, dev)
             sym = target.to(device=dev, dtype=torch.int64).contiguous()
+            # reference joiner.py:100-106: k2.rnnt_loss_smoothed with the YAML's lm_scale / am_scale;
+            # the ranges below and both returns (with and without use_out_project) follow from it
             neg_scores, px_grad, py_grad = K.rnnt_simple_loss(lm.float(), am.float(), sym,
-                                                              boundary, self.blank_token)
+                                                              boundary, self.blank_token,
+                                                              self._lm_scale, self._am_scale)
             simple_loss = neg_scores.mean()
             ranges = K.rnnt_prune_ranges(px_grad, py_grad, boundary, self.prune_range)
             lattice = PrunedLattice(am, lm, ranges, self._act_name)
