@@ -15,10 +15,13 @@
 //   px [B][S][T+1]   log-prob of emitting symbol s at frame t   (col T = -inf)
 //   py [B][S+1][T]   log-prob of blank at (s,t)
 //   p  [B][S+1][T+1] forward scores of the recursion
+// rnnt_type "modified" / "constrained" (k2.rnnt_loss_pruned): px [B][S][T], a symbol arc advances a
+// frame too, and the recursion walks the frames instead (mi_mod_*_kernel below).
 // The recursion is a wavefront over anti-diagonals: lane/thread = s, one
 // workgroup per utterance, neighbour exchange through LDS (or DPP shuffles
 // when S+1 <= 64), the next diagonal's px/py prefetched ahead of the barrier.
 #include "common.h"
+#include "../../include/s2t_mi355.h"
 
 namespace {
 
@@ -306,6 +309,140 @@ __global__ void mi_bwd_kernel(const float* __restrict__ px, const float* __restr
 #undef MI_FETCH
 }
 
+// ------------------------------------ modified-topology recursion (column walk)
+// rnnt_type "modified" / "constrained" (k2: px.shape[2] == T): the symbol arc advances a frame too,
+//   p[s][t] = logadd(p[s-1][t-1] + px[s-1][t-1], p[s][t-1] + py[s][t-1]),   px [B][S][T],
+// so column t depends on column t-1 only.  Thread = row s walks the frames: T_b steps instead of the
+// S_b + T_b anti-diagonals, one LDS exchange (the row below) and one barrier per step.  Operands are
+// requested MI_PD frames ahead through raw buffer accesses on straight-line code, as above.
+__global__ void mi_mod_fwd_kernel(const float* __restrict__ px, const float* __restrict__ py,
+                                  const long* __restrict__ boundary, int S, int T,
+                                  float* __restrict__ p, float* __restrict__ ans) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float* ex = reinterpret_cast<float*>(smem_raw);  // [2][blockDim.x + 1]
+  const int b = blockIdx.x, s = threadIdx.x, nt = blockDim.x;
+  const int Sb = (int)boundary[b * 4 + 2], Tb = (int)boundary[b * 4 + 3];
+  const __amdgpu_buffer_rsrc_t rpx = mi_rsrc(px + (long)b * S * T, (long)S * T);
+  const __amdgpu_buffer_rsrc_t rpy = mi_rsrc(py + (long)b * (S + 1) * T, (long)(S + 1) * T);
+  const __amdgpu_buffer_rsrc_t rp = mi_rsrc(p + (long)b * (S + 1) * (T + 1), (long)(S + 1) * (T + 1));
+  const bool act = s <= Sb;
+  float own = (s == 0) ? 0.f : S2T_NEG_INF;  // p[s][t-1]; column 0 holds the start state only
+  mi_store(rp, act ? (unsigned)(s * (T + 1)) * 4u : MI_OOB, own);
+  ex[s] = act ? own : S2T_NEG_INF;
+  ex[nt + 1 + s] = S2T_NEG_INF;
+  if (s == 0) {
+    ex[nt] = S2T_NEG_INF;
+    ex[2 * nt + 1] = S2T_NEG_INF;
+  }
+  __syncthreads();
+  // operands of frame t: px[s-1][t-1], py[s][t-1]
+  float rx[MI_PD], ry[MI_PD];
+#define MI_FETCH(TT, X, Y)                                                                   \
+  {                                                                                          \
+    const int t1_ = (TT);                                                                    \
+    const bool in_ = act && t1_ >= 1 && t1_ <= Tb;                                           \
+    X = mi_load(rpx, (in_ && s > 0) ? (unsigned)((s - 1) * T + t1_ - 1) * 4u : MI_OOB);      \
+    Y = mi_load(rpy, in_ ? (unsigned)(s * T + t1_ - 1) * 4u : MI_OOB);                       \
+  }
+#pragma unroll
+  for (int u = 0; u < MI_PD; ++u) MI_FETCH(1 + u, rx[u], ry[u])
+  int cur = 1;
+  // whole groups of MI_PD frames: the ones past T_b fall through as no-ops
+  for (int t0 = 1; t0 <= Tb; t0 += MI_PD) {
+#pragma unroll
+    for (int u = 0; u < MI_PD; ++u) {
+      const int t = t0 + u;
+      const float vx = rx[u], vy = ry[u];
+      MI_FETCH(t + MI_PD, rx[u], ry[u])
+      const bool in = act && t <= Tb;
+      const float up = (s > 0) ? ex[(cur ^ 1) * (nt + 1) + (s > 0 ? s - 1 : 0)] + vx : S2T_NEG_INF;
+      const float left = own + vy;
+      const float val = in ? log_add_comp(up, left) : S2T_NEG_INF;
+      mi_store(rp, in ? (unsigned)(s * (T + 1) + t) * 4u : MI_OOB, val);
+      own = in ? val : own;
+      ex[cur * (nt + 1) + s] = val;
+      __syncthreads();
+      cur ^= 1;
+    }
+  }
+#undef MI_FETCH
+  if (s == Sb) ans[b] = own;
+}
+
+// px_grad [B][S][T], py_grad [B][S+1][T] (pre-zeroed): the occupation of every arc, walking the
+// frames back from T_b - 1; the row above (s+1 at t+1) comes through LDS.
+__global__ void mi_mod_bwd_kernel(const float* __restrict__ px, const float* __restrict__ py,
+                                  const long* __restrict__ boundary, const float* __restrict__ p,
+                                  const float* __restrict__ ans_grad, int S, int T,
+                                  float* __restrict__ px_grad, float* __restrict__ py_grad) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float* exg = reinterpret_cast<float*>(smem_raw);  // [2][nt+1] p_grad
+  const int b = blockIdx.x, s = threadIdx.x, nt = blockDim.x;
+  float* exp_ = exg + 2 * (nt + 1);                 // [2][nt+1] p
+  const int Sb = (int)boundary[b * 4 + 2], Tb = (int)boundary[b * 4 + 3];
+  const __amdgpu_buffer_rsrc_t rpx = mi_rsrc(px + (long)b * S * T, (long)S * T);
+  const __amdgpu_buffer_rsrc_t rpy = mi_rsrc(py + (long)b * (S + 1) * T, (long)(S + 1) * T);
+  const __amdgpu_buffer_rsrc_t rp = mi_rsrc(p + (long)b * (S + 1) * (T + 1), (long)(S + 1) * (T + 1));
+  const __amdgpu_buffer_rsrc_t rgx = mi_rsrc(px_grad + (long)b * S * T, (long)S * T);
+  const __amdgpu_buffer_rsrc_t rgy = mi_rsrc(py_grad + (long)b * (S + 1) * T, (long)(S + 1) * T);
+  for (int i = s; i < 2 * (nt + 1); i += nt) {
+    exg[i] = 0.f;
+    exp_[i] = S2T_NEG_INF;
+  }
+  __syncthreads();
+  const bool act = s <= Sb;
+  const float ag = ans_grad ? ans_grad[b] : 1.f;
+  // column T_b: the final state holds all the gradient
+  float own_g = (s == Sb) ? ag : 0.f;                                       // p_grad[s][t+1]
+  float own_p = mi_load(rp, act ? (unsigned)(s * (T + 1) + Tb) * 4u : MI_OOB);  // p[s][t+1]
+  own_p = act ? own_p : S2T_NEG_INF;
+  exg[s] = own_g;
+  exp_[s] = own_p;
+  __syncthreads();
+  int cur = 1;
+  // operands of frame t: p, px, py at (s, t)
+  float rp_[MI_PD], rx[MI_PD], ry[MI_PD];
+#define MI_FETCH(TT, VP, VX, VY)                                                             \
+  {                                                                                          \
+    const int t1_ = (TT);                                                                    \
+    const bool in_ = act && t1_ >= 0 && t1_ < Tb;                                            \
+    VP = mi_load(rp, in_ ? (unsigned)(s * (T + 1) + t1_) * 4u : MI_OOB);                     \
+    VX = mi_load(rpx, (in_ && s < Sb) ? (unsigned)(s * T + t1_) * 4u : MI_OOB);              \
+    VY = mi_load(rpy, in_ ? (unsigned)(s * T + t1_) * 4u : MI_OOB);                          \
+  }
+#pragma unroll
+  for (int u = 0; u < MI_PD; ++u) MI_FETCH(Tb - 1 - u, rp_[u], rx[u], ry[u])
+  for (int t0 = Tb - 1; t0 >= 0; t0 -= MI_PD) {
+#pragma unroll
+    for (int u = 0; u < MI_PD; ++u) {
+      const int t = t0 - u;
+      const float vp = rp_[u], vx = rx[u], vy = ry[u];
+      MI_FETCH(t - MI_PD, rp_[u], rx[u], ry[u])
+      const bool in = act && t >= 0;
+      const float pd = exp_[(cur ^ 1) * (nt + 1) + s + 1];  // p[s+1][t+1]
+      const float gd = exg[(cur ^ 1) * (nt + 1) + s + 1];   // p_grad[s+1][t+1]
+      float xg = 0.f, yg = 0.f;
+      if (in && s < Sb && pd != S2T_NEG_INF && gd != 0.f) {
+        const float e = __expf(vp + vx - pd);
+        xg = (e == e) ? gd * e : 0.f;
+      }
+      if (in && own_p != S2T_NEG_INF && own_g != 0.f) {
+        const float e = __expf(vp + vy - own_p);
+        yg = (e == e) ? own_g * e : 0.f;
+      }
+      mi_store(rgx, (in && s < Sb) ? (unsigned)(s * T + t) * 4u : MI_OOB, xg);
+      mi_store(rgy, in ? (unsigned)(s * T + t) * 4u : MI_OOB, yg);
+      own_g = in ? xg + yg : own_g;
+      own_p = in ? vp : own_p;
+      exg[cur * (nt + 1) + s] = in ? xg + yg : 0.f;
+      exp_[cur * (nt + 1) + s] = in ? vp : S2T_NEG_INF;
+      __syncthreads();
+      cur ^= 1;
+    }
+  }
+#undef MI_FETCH
+}
+
 // ------------------------------------------------------------ prune ranges
 // v[t] <- min(v[t], v[t+1], ..., v[T-1]) for a 256-thread workgroup; v in LDS, cm = 256 longs of
 // LDS scratch.  Every thread owns a contiguous chunk; the chunk minima are combined by a
@@ -388,6 +525,18 @@ __global__ __launch_bounds__(256) void prune_ranges_kernel(
 }
 
 // ----------------------------------------------------- fused pruned joiner
+// Lattice type of the px / py builders and their backwards: a compile-time parameter, so that K_REG
+// (regular, no delay penalty) stays the code the default path has always run.  K_REGPEN is regular
+// with a delay penalty (forward builders only: the penalty is a constant with no gradient).
+//   modified:    px [B][S][T], no column T / T_b fix (the symbol arc advances a frame)
+//   constrained: modified, then px[s][t] += py[s+1][t]; -inf where row s+1 is outside the frame's band
+//   penalty:     px[s][t] += pen * ((T_b - 1) / 2 - t)
+constexpr int K_REG = S2T_RNNT_REGULAR, K_MOD = S2T_RNNT_MODIFIED, K_CON = S2T_RNNT_CONSTRAINED,
+              K_REGPEN = 3;
+__device__ __forceinline__ float delay_term(float pen, long Tb, int t) {
+  return pen * (0.5f * (float)(Tb - 1) - (float)t);
+}
+
 __device__ __forceinline__ float act_fwd(float x, int act) {
   return act == 0 ? fmaxf(x, 0.f) : tanhf(x);
 }
@@ -398,11 +547,13 @@ __device__ __forceinline__ float act_deriv(float pre, float out, int act) {
 // One wave per (b,t): for each of the R pruned rows compute
 // row = act(am[b,t,:] + lm[b,s,:]), Z = logsumexp(row), px~, py~ -> px,py.
 // px/py must be pre-filled with -inf.  lse [B][T][R] saved for backward.
-template <int MAXC_PER_LANE>
+// constrained: the symbol entry of band row i waits one turn of the loop for the blank log-prob of
+// row i+1; the band's top row is never completed and keeps its -inf.
+template <int MAXC_PER_LANE, int TYPE>
 __global__ __launch_bounds__(256) void pruned_fwd_kernel(
     const float* __restrict__ am, const float* __restrict__ lm, const long* __restrict__ ranges,
     const long* __restrict__ symbols, const long* __restrict__ boundary, int B, int S, int T,
-    int C, int R, int blank, int act, float* __restrict__ px, float* __restrict__ py,
+    int C, int R, int blank, int act, float pen, float* __restrict__ px, float* __restrict__ py,
     float* __restrict__ lse) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -410,6 +561,10 @@ __global__ __launch_bounds__(256) void pruned_fwd_kernel(
   const int b = (int)(row / T), t = (int)(row % T);
   const int S1 = S + 1;
   const long Tb = boundary[b * 4 + 3];
+  constexpr bool kMod = TYPE == K_MOD || TYPE == K_CON;
+  const int TX = kMod ? T : T + 1;
+  float pen_t = 0.f, pend = 0.f;
+  if constexpr (TYPE != K_REG) pen_t = delay_term(pen, Tb, t);
   float a[MAXC_PER_LANE];
   const float* amr = am + row * C;
 #pragma unroll
@@ -441,18 +596,29 @@ __global__ __launch_bounds__(256) void pruned_fwd_kernel(
     if (lane == 0) {
       const float vb = act_fwd(amr[blank] + lmr[blank], act);
       py[((long)b * S1 + s) * T + t] = vb - z;
-      if (s < S) {
+      if constexpr (TYPE == K_CON) {
+        if (i > 0) px[((long)b * S + s - 1) * TX + t] = pend + (vb - z) + pen_t;
+        if (s < S) {
+          const long y = symbols[(long)b * S + s];
+          pend = act_fwd(amr[y] + lmr[y], act) - z;
+        }
+      } else if (s < S) {
         const long y = symbols[(long)b * S + s];
         float vy = act_fwd(amr[y] + lmr[y], act) - z;
-        if (t == Tb) vy = S2T_NEG_INF;
-        px[((long)b * S + s) * (T + 1) + t] = vy;
+        if constexpr (!kMod)
+          if (t == Tb) vy = S2T_NEG_INF;
+        if constexpr (TYPE != K_REG) vy += pen_t;
+        px[((long)b * S + s) * TX + t] = vy;
       }
     }
   }
 }
 
 // d_am[b,t,:] = sum_i act'(.) * ( dpx*(1[y]-P) + dpy*(1[blank]-P) ); wave per (b,t)
-template <int MAXC_PER_LANE>
+// constrained: the blank of band row i > 0 also carries dpx of the row below (px[s-1] holds py[s]).
+// Outside regular a node whose two gradients are zero is skipped: frames past T_b and rows past S_b
+// are such nodes (the recursion's backward leaves them zero) and their inputs are never read.
+template <int MAXC_PER_LANE, int TYPE>
 __global__ __launch_bounds__(256) void pruned_dam_kernel(
     const float* __restrict__ am, const float* __restrict__ lm, const long* __restrict__ ranges,
     const long* __restrict__ symbols, const float* __restrict__ lse,
@@ -464,6 +630,7 @@ __global__ __launch_bounds__(256) void pruned_dam_kernel(
   if (row >= (long)B * T) return;
   const int b = (int)(row / T), t = (int)(row % T);
   const int S1 = S + 1;
+  const int TX = TYPE == K_REG ? T + 1 : T;
   const float g = gscale[b];
   float a[MAXC_PER_LANE], acc[MAXC_PER_LANE];
   const float* amr = am + row * C;
@@ -479,8 +646,12 @@ __global__ __launch_bounds__(256) void pruned_dam_kernel(
     if (s > S) break;
     const float* lmr = lm + ((long)b * S1 + s) * C;
     const float z = lse[row * R + i];
-    const float gy = dpy[((long)b * S1 + s) * T + t] * g;
-    const float gx = (s < S) ? dpx[((long)b * S + s) * (T + 1) + t] * g : 0.f;
+    float gy = dpy[((long)b * S1 + s) * T + t] * g;
+    const float gx = (s < S) ? dpx[((long)b * S + s) * TX + t] * g : 0.f;
+    if constexpr (TYPE == K_CON)
+      if (i > 0) gy += dpx[((long)b * S + s - 1) * TX + t] * g;
+    if constexpr (TYPE != K_REG)
+      if (gx == 0.f && gy == 0.f) continue;
     const long y = (s < S) ? symbols[(long)b * S + s] : -1;
     const float gt = gx + gy;
 #pragma unroll
@@ -512,7 +683,7 @@ __global__ __launch_bounds__(256) void pruned_dam_kernel(
 // d_am pass over the same nodes).  The waves of the workgroup stride the range and add up
 // through LDS.
 constexpr int DLM_W = 8;
-template <int MAXC_PER_LANE>
+template <int MAXC_PER_LANE, int TYPE>
 __global__ __launch_bounds__(64 * DLM_W) void pruned_dlm_kernel(
     const float* __restrict__ am, const float* __restrict__ lm, const long* __restrict__ ranges,
     const long* __restrict__ symbols, const float* __restrict__ lse,
@@ -521,6 +692,7 @@ __global__ __launch_bounds__(64 * DLM_W) void pruned_dlm_kernel(
     int accumulate) {
   __shared__ float s_acc[DLM_W][64 * MAXC_PER_LANE];
   const int S1 = S + 1;
+  const int TX = TYPE == K_REG ? T + 1 : T;
   const long row = blockIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = (int)(row / S1), s = (int)(row % S1);
@@ -553,8 +725,12 @@ __global__ __launch_bounds__(64 * DLM_W) void pruned_dlm_kernel(
     const int i = s - (int)rb[(long)t * R];
     const float* amr = am + ((long)b * T + t) * C;
     const float z = lse[((long)b * T + t) * R + i];
-    const float gy = dpy[((long)b * S1 + s) * T + t] * g;
-    const float gx = (s < S) ? dpx[((long)b * S + s) * (T + 1) + t] * g : 0.f;
+    float gy = dpy[((long)b * S1 + s) * T + t] * g;
+    const float gx = (s < S) ? dpx[((long)b * S + s) * TX + t] * g : 0.f;
+    if constexpr (TYPE == K_CON)
+      if (i > 0) gy += dpx[((long)b * S + s - 1) * TX + t] * g;
+    if constexpr (TYPE != K_REG)
+      if (gx == 0.f && gy == 0.f) continue;
     const float gt = gx + gy;
 #pragma unroll
     for (int j = 0; j < MAXC_PER_LANE; ++j) {
@@ -584,11 +760,26 @@ __global__ __launch_bounds__(64 * DLM_W) void pruned_dlm_kernel(
 // ------------------------------------------------- materialised lattice rows
 // logits [B][T][U1][V] (full, U1 = S+1) or pruned [B][T][R][V] with ranges.
 // One wave per lattice node: Z = logsumexp; writes px/py (pre-filled -inf).
+// constrained: the node of band row i needs the blank log-prob of row i+1, another wave's node; its
+// wave takes that node's Z as well (a second pass over V classes, in this instantiation only).
+__device__ __forceinline__ float node_lse(const float* __restrict__ x, int V, int lane) {
+  float m = S2T_NEG_INF;
+  for (int c = lane; c < V; c += 64) m = fmaxf(m, x[c]);
+  m = wave_max(m);
+  float sum = 0.f;
+  for (int c = lane; c < V; c += 64) sum += expf(x[c] - m);
+  sum = wave_sum(sum);
+  return m + logf(sum);
+}
+
+template <int TYPE>
 __global__ __launch_bounds__(256) void lattice_fwd_kernel(
     const float* __restrict__ logits, const long* __restrict__ ranges,
     const long* __restrict__ symbols, const long* __restrict__ boundary, int B, int S, int T,
-    int V, int R, int blank, float* __restrict__ px, float* __restrict__ py,
+    int V, int R, int blank, float pen, float* __restrict__ px, float* __restrict__ py,
     float* __restrict__ lse) {
+  constexpr bool kMod = TYPE == K_MOD || TYPE == K_CON;
+  const int TX = kMod ? T : T + 1;
   const long node = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int S1 = S + 1;
@@ -606,18 +797,31 @@ __global__ __launch_bounds__(256) void lattice_fwd_kernel(
   for (int c = lane; c < V; c += 64) sum += expf(x[c] - m);
   sum = wave_sum(sum);
   const float z = m + logf(sum);
+  float zn = 0.f;
+  bool next = false;   // constrained: row s+1 is inside this frame's band
+  if constexpr (TYPE == K_CON) {
+    next = i + 1 < R && s < S;
+    if (next) zn = node_lse(x + V, V, lane);
+  }
   if (lane == 0) {
     lse[node] = z;
     const long Tb = boundary[b * 4 + 3];
     py[((long)b * S1 + s) * T + t] = x[blank] - z;
-    if (s < S) {
+    if constexpr (TYPE == K_CON) {
+      if (next)
+        px[((long)b * S + s) * TX + t] =
+            x[symbols[(long)b * S + s]] - z + (x[V + blank] - zn) + delay_term(pen, Tb, t);
+    } else if (s < S) {
       float v = x[symbols[(long)b * S + s]] - z;
-      if (t == Tb) v = S2T_NEG_INF;
-      px[((long)b * S + s) * (T + 1) + t] = v;
+      if constexpr (!kMod)
+        if (t == Tb) v = S2T_NEG_INF;
+      if constexpr (TYPE != K_REG) v += delay_term(pen, Tb, t);
+      px[((long)b * S + s) * TX + t] = v;
     }
   }
 }
 
+template <int TYPE>
 __global__ __launch_bounds__(256) void lattice_bwd_kernel(
     const float* __restrict__ logits, const long* __restrict__ ranges,
     const long* __restrict__ symbols, const float* __restrict__ lse,
@@ -636,11 +840,19 @@ __global__ __launch_bounds__(256) void lattice_bwd_kernel(
     for (int c = lane; c < V; c += 64) o[c] = 0.f;
     return;
   }
+  const int TX = TYPE == K_REG ? T + 1 : T;
   const float g = gscale[b];
   const float* x = logits + node * V;
+  float gy = dpy[((long)b * S1 + s) * T + t] * g;
+  const float gx = (s < S) ? dpx[((long)b * S + s) * TX + t] * g : 0.f;
+  if constexpr (TYPE == K_CON)
+    if (i > 0) gy += dpx[((long)b * S + s - 1) * TX + t] * g;
+  if constexpr (TYPE != K_REG)
+    if (gx == 0.f && gy == 0.f) {   // frames past T_b, rows past S_b: inputs not read
+      for (int c = lane; c < V; c += 64) o[c] = 0.f;
+      return;
+    }
   const float z = lse[node];
-  const float gy = dpy[((long)b * S1 + s) * T + t] * g;
-  const float gx = (s < S) ? dpx[((long)b * S + s) * (T + 1) + t] * g : 0.f;
   const long y = (s < S) ? symbols[(long)b * S + s] : -1;
   const float gt = gx + gy;
   for (int c = lane; c < V; c += 64) {
@@ -768,56 +980,116 @@ extern "C" int s2t_rnnt_prune_ranges(const float* px_grad, const float* py_grad,
   return 0;
 }
 
-#define S2T_DISPATCH_C(KERNEL, ...)                                                         \
+// KERNEL<classes per lane, TY> by joiner width; `rows` and `st` are the caller's
+#define S2T_DISPATCH_C(KERNEL, TY, ...)                                                     \
   do {                                                                                      \
     const unsigned nb__ = (unsigned)((rows + 3) / 4);                                       \
     if (C <= 128)                                                                           \
-      hipLaunchKernelGGL(KERNEL<2>, dim3(nb__), dim3(256), 0, st, __VA_ARGS__);             \
+      hipLaunchKernelGGL((KERNEL<2, TY>), dim3(nb__), dim3(256), 0, st, __VA_ARGS__);       \
     else if (C <= 256)                                                                      \
-      hipLaunchKernelGGL(KERNEL<4>, dim3(nb__), dim3(256), 0, st, __VA_ARGS__);             \
+      hipLaunchKernelGGL((KERNEL<4, TY>), dim3(nb__), dim3(256), 0, st, __VA_ARGS__);       \
     else if (C <= 512)                                                                      \
-      hipLaunchKernelGGL(KERNEL<8>, dim3(nb__), dim3(256), 0, st, __VA_ARGS__);             \
+      hipLaunchKernelGGL((KERNEL<8, TY>), dim3(nb__), dim3(256), 0, st, __VA_ARGS__);       \
     else if (C <= 1024)                                                                     \
-      hipLaunchKernelGGL(KERNEL<16>, dim3(nb__), dim3(256), 0, st, __VA_ARGS__);            \
+      hipLaunchKernelGGL((KERNEL<16, TY>), dim3(nb__), dim3(256), 0, st, __VA_ARGS__);      \
     else                                                                                    \
       return -1;                                                                            \
   } while (0)
+
+namespace {
+// the forward builders' instantiation: K_REG only without a penalty; -1 for an unknown type or a
+// negative penalty
+inline int fwd_kind(int rnnt_type, float delay_penalty) {
+  if (!(delay_penalty >= 0.f)) return -1;
+  if (rnnt_type == S2T_RNNT_REGULAR) return delay_penalty > 0.f ? K_REGPEN : K_REG;
+  if (rnnt_type == S2T_RNNT_MODIFIED) return K_MOD;
+  if (rnnt_type == S2T_RNNT_CONSTRAINED) return K_CON;
+  return -1;
+}
+inline int px_cols(int rnnt_type, int T) { return rnnt_type == S2T_RNNT_REGULAR ? T + 1 : T; }
+}  // namespace
+
+extern "C" int s2t_mutual_info_mod_fwd(const float* px, const float* py, const long* boundary,
+                                       int B, int S, int T, float* p, float* ans, void* stream) {
+  if (B <= 0) return 0;
+  if (S < 0 || T < 0 || S + 1 > 1024) return -1;
+  const int nt = mi_threads(S);
+  hipLaunchKernelGGL(mi_mod_fwd_kernel, dim3(B), dim3(nt), sizeof(float) * 2 * (nt + 1),
+                     (hipStream_t)stream, px, py, boundary, S, T, p, ans);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int s2t_mutual_info_mod_bwd(const float* px, const float* py, const long* boundary,
+                                       const float* p, const float* ans_grad, int B, int S, int T,
+                                       float* px_grad, float* py_grad, void* stream) {
+  if (B <= 0) return 0;
+  if (S < 0 || T < 0 || S + 1 > 1024) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipSuccess;
+  if (S > 0 && T > 0) e = hipMemsetAsync(px_grad, 0, sizeof(float) * (size_t)B * S * T, st);
+  if (e != hipSuccess) return (int)e;
+  if (T > 0) e = hipMemsetAsync(py_grad, 0, sizeof(float) * (size_t)B * (S + 1) * T, st);
+  if (e != hipSuccess) return (int)e;
+  const int nt = mi_threads(S);
+  hipLaunchKernelGGL(mi_mod_bwd_kernel, dim3(B), dim3(nt), sizeof(float) * 4 * (nt + 1), st, px, py,
+                     boundary, p, ans_grad, S, T, px_grad, py_grad);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int s2t_rnnt_pruned_fwd_typed(const float* am, const float* lm, const long* ranges,
+                                         const long* symbols, const long* boundary, int B, int S,
+                                         int T, int C, int R, int blank, int act, int rnnt_type,
+                                         float delay_penalty, float* px, float* py, float* lse,
+                                         void* stream) {
+  const int kind = fwd_kind(rnnt_type, delay_penalty);
+  if (kind < 0) return -1;
+  if (B <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = s2t_fill_f32(px, (long)B * S * px_cols(rnnt_type, T), S2T_NEG_INF, stream);
+  if (rc) return rc;
+  rc = s2t_fill_f32(py, (long)B * (S + 1) * T, S2T_NEG_INF, stream);
+  if (rc) return rc;
+  const long rows = (long)B * T;
+#define S2T_PFWD(TY)                                                                              \
+  S2T_DISPATCH_C(pruned_fwd_kernel, TY, am, lm, ranges, symbols, boundary, B, S, T, C, R, blank, \
+                 act, delay_penalty, px, py, lse)
+  if (kind == K_REG) S2T_PFWD(K_REG);
+  else if (kind == K_MOD) S2T_PFWD(K_MOD);
+  else if (kind == K_CON) S2T_PFWD(K_CON);
+  else S2T_PFWD(K_REGPEN);
+#undef S2T_PFWD
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
 
 extern "C" int s2t_rnnt_pruned_fwd(const float* am, const float* lm, const long* ranges,
                                    const long* symbols, const long* boundary, int B, int S, int T,
                                    int C, int R, int blank, int act, float* px, float* py,
                                    float* lse, void* stream) {
-  if (B <= 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = s2t_fill_f32(px, (long)B * S * (T + 1), S2T_NEG_INF, stream);
-  if (rc) return rc;
-  rc = s2t_fill_f32(py, (long)B * (S + 1) * T, S2T_NEG_INF, stream);
-  if (rc) return rc;
-  const long rows = (long)B * T;
-  S2T_DISPATCH_C(pruned_fwd_kernel, am, lm, ranges, symbols, boundary, B, S, T, C, R, blank, act,
-                 px, py, lse);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  return s2t_rnnt_pruned_fwd_typed(am, lm, ranges, symbols, boundary, B, S, T, C, R, blank, act,
+                                   S2T_RNNT_REGULAR, 0.f, px, py, lse, stream);
 }
 
-extern "C" int s2t_rnnt_pruned_bwd(const float* am, const float* lm, const long* ranges,
-                                   const long* symbols, const float* lse, const float* dpx,
-                                   const float* dpy, const float* gscale, int B, int S, int T,
-                                   int C, int R, int blank, int act, float* d_am, float* d_lm,
-                                   int accumulate, void* stream) {
-  if (B <= 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
+namespace {
+template <int TYPE>
+int pruned_bwd_launch(const float* am, const float* lm, const long* ranges, const long* symbols,
+                      const float* lse, const float* dpx, const float* dpy, const float* gscale,
+                      int B, int S, int T, int C, int R, int blank, int act, float* d_am,
+                      float* d_lm, int accumulate, hipStream_t st) {
   {
     const long rows = (long)B * T;
-    S2T_DISPATCH_C(pruned_dam_kernel, am, lm, ranges, symbols, lse, dpx, dpy, gscale, B, S, T, C,
-                   R, blank, act, d_am, accumulate);
+    S2T_DISPATCH_C(pruned_dam_kernel, TYPE, am, lm, ranges, symbols, lse, dpx, dpy, gscale, B, S,
+                   T, C, R, blank, act, d_am, accumulate);
     S2T_CHECK_LAUNCH();
   }
   {
     const unsigned nb = (unsigned)((long)B * (S + 1));      // one DLM_W-wave workgroup per (b, s)
-#define S2T_DLM(MC)                                                                              \
-  hipLaunchKernelGGL(pruned_dlm_kernel<MC>, dim3(nb), dim3(64 * DLM_W), 0, st, am, lm, ranges, \
-                     symbols, lse, dpx, dpy, gscale, B, S, T, C, R, blank, act, d_lm, accumulate)
+#define S2T_DLM(MC)                                                                            \
+  hipLaunchKernelGGL((pruned_dlm_kernel<MC, TYPE>), dim3(nb), dim3(64 * DLM_W), 0, st, am, lm, \
+                     ranges, symbols, lse, dpx, dpy, gscale, B, S, T, C, R, blank, act, d_lm,  \
+                     accumulate)
     if (C <= 128) S2T_DLM(2);
     else if (C <= 256) S2T_DLM(4);
     else if (C <= 512) S2T_DLM(8);
@@ -828,19 +1100,87 @@ extern "C" int s2t_rnnt_pruned_bwd(const float* am, const float* lm, const long*
   }
   return 0;
 }
+}  // namespace
 
-extern "C" int s2t_rnnt_lattice_fwd(const float* logits, const long* ranges, const long* symbols,
-                                    const long* boundary, int B, int S, int T, int V, int R,
-                                    int blank, float* px, float* py, float* lse, void* stream) {
+extern "C" int s2t_rnnt_pruned_bwd_typed(const float* am, const float* lm, const long* ranges,
+                                         const long* symbols, const float* lse, const float* dpx,
+                                         const float* dpy, const float* gscale, int B, int S, int T,
+                                         int C, int R, int blank, int act, int rnnt_type,
+                                         float* d_am, float* d_lm, int accumulate, void* stream) {
+  if (rnnt_type != S2T_RNNT_REGULAR && rnnt_type != S2T_RNNT_MODIFIED &&
+      rnnt_type != S2T_RNNT_CONSTRAINED)
+    return -1;
   if (B <= 0) return 0;
-  int rc = s2t_fill_f32(px, (long)B * S * (T + 1), S2T_NEG_INF, stream);
+  hipStream_t st = (hipStream_t)stream;
+#define S2T_PBWD(TY)                                                                             \
+  pruned_bwd_launch<TY>(am, lm, ranges, symbols, lse, dpx, dpy, gscale, B, S, T, C, R, blank,   \
+                        act, d_am, d_lm, accumulate, st)
+  if (rnnt_type == S2T_RNNT_MODIFIED) return S2T_PBWD(K_MOD);
+  if (rnnt_type == S2T_RNNT_CONSTRAINED) return S2T_PBWD(K_CON);
+  return S2T_PBWD(K_REG);
+#undef S2T_PBWD
+}
+
+extern "C" int s2t_rnnt_pruned_bwd(const float* am, const float* lm, const long* ranges,
+                                   const long* symbols, const float* lse, const float* dpx,
+                                   const float* dpy, const float* gscale, int B, int S, int T,
+                                   int C, int R, int blank, int act, float* d_am, float* d_lm,
+                                   int accumulate, void* stream) {
+  return s2t_rnnt_pruned_bwd_typed(am, lm, ranges, symbols, lse, dpx, dpy, gscale, B, S, T, C, R,
+                                   blank, act, S2T_RNNT_REGULAR, d_am, d_lm, accumulate, stream);
+}
+
+extern "C" int s2t_rnnt_lattice_fwd_typed(const float* logits, const long* ranges,
+                                          const long* symbols, const long* boundary, int B, int S,
+                                          int T, int V, int R, int blank, int rnnt_type,
+                                          float delay_penalty, float* px, float* py, float* lse,
+                                          void* stream) {
+  const int kind = fwd_kind(rnnt_type, delay_penalty);
+  if (kind < 0) return -1;
+  if (B <= 0) return 0;
+  int rc = s2t_fill_f32(px, (long)B * S * px_cols(rnnt_type, T), S2T_NEG_INF, stream);
   if (rc) return rc;
   rc = s2t_fill_f32(py, (long)B * (S + 1) * T, S2T_NEG_INF, stream);
   if (rc) return rc;
   const long nodes = (long)B * T * R;
-  hipLaunchKernelGGL(lattice_fwd_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0,
-                     (hipStream_t)stream, logits, ranges, symbols, boundary, B, S, T, V, R, blank,
-                     px, py, lse);
+#define S2T_LFWD(TY)                                                                            \
+  hipLaunchKernelGGL(lattice_fwd_kernel<TY>, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0,  \
+                     (hipStream_t)stream, logits, ranges, symbols, boundary, B, S, T, V, R,    \
+                     blank, delay_penalty, px, py, lse)
+  if (kind == K_REG) S2T_LFWD(K_REG);
+  else if (kind == K_MOD) S2T_LFWD(K_MOD);
+  else if (kind == K_CON) S2T_LFWD(K_CON);
+  else S2T_LFWD(K_REGPEN);
+#undef S2T_LFWD
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int s2t_rnnt_lattice_fwd(const float* logits, const long* ranges, const long* symbols,
+                                    const long* boundary, int B, int S, int T, int V, int R,
+                                    int blank, float* px, float* py, float* lse, void* stream) {
+  return s2t_rnnt_lattice_fwd_typed(logits, ranges, symbols, boundary, B, S, T, V, R, blank,
+                                    S2T_RNNT_REGULAR, 0.f, px, py, lse, stream);
+}
+
+extern "C" int s2t_rnnt_lattice_bwd_typed(const float* logits, const long* ranges,
+                                          const long* symbols, const float* lse, const float* dpx,
+                                          const float* dpy, const float* gscale, int B, int S,
+                                          int T, int V, int R, int blank, int rnnt_type,
+                                          float* d_logits, void* stream) {
+  if (rnnt_type != S2T_RNNT_REGULAR && rnnt_type != S2T_RNNT_MODIFIED &&
+      rnnt_type != S2T_RNNT_CONSTRAINED)
+    return -1;
+  if (B <= 0) return 0;
+  const long nodes = (long)B * T * R;
+#define S2T_LBWD(TY)                                                                            \
+  hipLaunchKernelGGL(lattice_bwd_kernel<TY>, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0,  \
+                     (hipStream_t)stream, logits, ranges, symbols, lse, dpx, dpy, gscale, B, S, \
+                     T, V, R, blank, d_logits)
+  if (rnnt_type == S2T_RNNT_MODIFIED) S2T_LBWD(K_MOD);
+  else if (rnnt_type == S2T_RNNT_CONSTRAINED) S2T_LBWD(K_CON);
+  else S2T_LBWD(K_REG);
+#undef S2T_LBWD
   S2T_CHECK_LAUNCH();
   return 0;
 }
@@ -849,11 +1189,6 @@ extern "C" int s2t_rnnt_lattice_bwd(const float* logits, const long* ranges, con
                                     const float* lse, const float* dpx, const float* dpy,
                                     const float* gscale, int B, int S, int T, int V, int R,
                                     int blank, float* d_logits, void* stream) {
-  if (B <= 0) return 0;
-  const long nodes = (long)B * T * R;
-  hipLaunchKernelGGL(lattice_bwd_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0,
-                     (hipStream_t)stream, logits, ranges, symbols, lse, dpx, dpy, gscale, B, S, T,
-                     V, R, blank, d_logits);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  return s2t_rnnt_lattice_bwd_typed(logits, ranges, symbols, lse, dpx, dpy, gscale, B, S, T, V, R,
+                                    blank, S2T_RNNT_REGULAR, d_logits, stream);
 }

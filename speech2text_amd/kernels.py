@@ -161,12 +161,39 @@ def _check_lattice_rows(S):
                          "workgroup, csrc/rnnt.hip)")
 
 
+def _mutual_information_modified(px, py, boundary, want_grads):
+    """px (B,S,T): the modified topology's column walk (csrc/rnnt.hip mi_mod_*_kernel)."""
+    B, S, T = px.shape
+    dev = px.device
+    p = torch.empty((B, S + 1, T + 1), dtype=torch.float32, device=dev)
+    ans = torch.empty((B,), dtype=torch.float32, device=dev)
+    L = N.lib()
+    N.PROF[0] and N.profile_note("s2t_mutual_info_mod_fwd", 4.0 * (px.numel() + py.numel() + p.numel()))
+    N.check(L.s2t_mutual_info_mod_fwd(N.fp(px), N.fp(py), N.lp(boundary), B, S, T, N.fp(p),
+                                      N.fp(ans), N.stream()), "s2t_mutual_info_mod_fwd")
+    if not want_grads:
+        return ans, p, None, None
+    gx = torch.empty_like(px)
+    gy = torch.empty_like(py)
+    N.PROF[0] and N.profile_note("s2t_mutual_info_mod_bwd", 4.0 * (2 * px.numel() + 2 * py.numel() + p.numel()))
+    N.check(L.s2t_mutual_info_mod_bwd(N.fp(px), N.fp(py), N.lp(boundary), N.fp(p), None, B, S, T,
+                                      N.fp(gx), N.fp(gy), N.stream()), "s2t_mutual_info_mod_bwd")
+    return ans, p, gx, gy
+
+
 def mutual_information(px, py, boundary, want_grads=True):
-    """Raw recursion: returns (scores (B,), p, px_grad, py_grad) -- no autograd."""
+    """Raw recursion: returns (scores (B,), p, px_grad, py_grad) -- no autograd.  As in k2 the
+    topology follows from the shapes: px (B,S,T+1) is the regular lattice, px (B,S,T) -- as many
+    columns as py -- the modified one, in which a symbol arc advances a frame too."""
     B, S, T1 = px.shape
+    _check_lattice_rows(S)
+    if py.shape != (B, S + 1, T1) and py.shape != (B, S + 1, T1 - 1):
+        raise ValueError(f"mutual_information: px {tuple(px.shape)} and py {tuple(py.shape)} are "
+                         "neither a regular (B,S,T+1)/(B,S+1,T) nor a modified (B,S,T)/(B,S+1,T) pair")
+    if T1 == py.shape[2]:
+        return _mutual_information_modified(px, py, boundary, want_grads)
     T = T1 - 1
     dev = px.device
-    _check_lattice_rows(S)
     p = torch.empty((B, S + 1, T + 1), dtype=torch.float32, device=dev)
     ans = torch.empty((B,), dtype=torch.float32, device=dev)
     L = N.lib()
@@ -342,6 +369,19 @@ def rnnt_prune_ranges(px_grad, py_grad, boundary, s_range):
 
 
 _ACT = {"relu": 0, "tanh": 1}
+RNNT_TYPES = {"regular": N.const("S2T_RNNT_REGULAR"), "modified": N.const("S2T_RNNT_MODIFIED"),
+              "constrained": N.const("S2T_RNNT_CONSTRAINED")}
+
+
+def check_rnnt_type(rnnt_type, delay_penalty):
+    """k2.rnnt_loss_pruned's rnnt_type and delay_penalty -> (type constant, penalty as float)."""
+    if rnnt_type not in RNNT_TYPES:
+        raise ValueError(f"rnnt_type {rnnt_type!r} is not one of 'regular', 'modified', 'constrained'")
+    pen = float(delay_penalty)
+    if not pen >= 0.0:
+        raise ValueError(f"delay_penalty {delay_penalty} is negative: k2 silently ignores such a "
+                         "value (it applies the penalty only when it is > 0); it must be >= 0")
+    return RNNT_TYPES[rnnt_type], pen
 
 
 class _PrunedJoinerLoss(torch.autograd.Function):
@@ -349,7 +389,7 @@ class _PrunedJoinerLoss(torch.autograd.Function):
     of the lattice logits[b,t,i,:] = act(am[b,t,:] + lm[b,ranges[b,t,0]+i,:])."""
 
     @staticmethod
-    def forward(ctx, am, lm, ranges, symbols, boundary, blank, act):
+    def forward(ctx, am, lm, ranges, symbols, boundary, blank, act, ty, pen):
         _dev_check(am, lm)
         am = am.contiguous().float()
         lm = lm.contiguous().float()
@@ -364,18 +404,29 @@ class _PrunedJoinerLoss(torch.autograd.Function):
                              "registers, csrc/rnnt.hip); there is no fallback")
         L = N.lib()
         st = N.stream()
-        px = torch.empty((B, S, T + 1), dtype=torch.float32, device=dev)
+        # the default setting stays on the untyped entry point: the same launches either way, and
+        # the step's profile keeps the entry names its recorded runs are compared by
+        plain = ty == RNNT_TYPES["regular"] and pen == 0.0
+        px = torch.empty((B, S, T + 1 if ty == RNNT_TYPES["regular"] else T), dtype=torch.float32,
+                         device=dev)
         py = torch.empty((B, S + 1, T), dtype=torch.float32, device=dev)
         lse = torch.empty((B, T, R), dtype=torch.float32, device=dev)
-        N.PROF[0] and N.profile_note("s2t_rnnt_pruned_fwd",
-                       4.0 * (am.numel() + lm.numel() + px.numel() + py.numel() + lse.numel())
-                       + 8.0 * ranges.numel())
-        N.check(L.s2t_rnnt_pruned_fwd(N.fp(am), N.fp(lm), N.lp(ranges), N.lp(symbols),
-                                      N.lp(boundary), B, S, T, C, R, int(blank), _ACT[act],
-                                      N.fp(px), N.fp(py), N.fp(lse), st), "pruned_fwd")
+        nbytes = 4.0 * (am.numel() + lm.numel() + px.numel() + py.numel() + lse.numel()) \
+            + 8.0 * ranges.numel()
+        if plain:
+            N.PROF[0] and N.profile_note("s2t_rnnt_pruned_fwd", nbytes)
+            N.check(L.s2t_rnnt_pruned_fwd(N.fp(am), N.fp(lm), N.lp(ranges), N.lp(symbols),
+                                          N.lp(boundary), B, S, T, C, R, int(blank), _ACT[act],
+                                          N.fp(px), N.fp(py), N.fp(lse), st), "pruned_fwd")
+        else:
+            N.PROF[0] and N.profile_note("s2t_rnnt_pruned_fwd_typed", nbytes)
+            N.check(L.s2t_rnnt_pruned_fwd_typed(N.fp(am), N.fp(lm), N.lp(ranges), N.lp(symbols),
+                                                N.lp(boundary), B, S, T, C, R, int(blank),
+                                                _ACT[act], ty, pen, N.fp(px), N.fp(py), N.fp(lse),
+                                                st), "pruned_fwd_typed")
         ans, _, gx, gy = mutual_information(px, py, boundary)
         ctx.save_for_backward(am, lm, ranges, symbols, lse, gx, gy)
-        ctx.blank, ctx.act = int(blank), _ACT[act]
+        ctx.blank, ctx.act, ctx.ty, ctx.plain = int(blank), _ACT[act], ty, plain
         return -ans
 
     @staticmethod
@@ -389,41 +440,72 @@ class _PrunedJoinerLoss(torch.autograd.Function):
         d_lm = torch.empty_like(lm)
         # the (B,T,R,C) pruned logits are recomputed, never stored: the algorithmic traffic is the
         # operands and their gradients; the recomputation costs 2 B T R C flops of VALU per pass
-        N.PROF[0] and N.profile_note("s2t_rnnt_pruned_bwd",
-                       4.0 * (2 * am.numel() + 2 * lm.numel() + lse.numel() + gx.numel() + gy.numel())
-                       + 8.0 * ranges.numel(), 4.0 * B * T * R * C)
-        N.check(N.lib().s2t_rnnt_pruned_bwd(N.fp(am), N.fp(lm), N.lp(ranges), N.lp(symbols),
-                                            N.fp(lse), N.fp(gx), N.fp(gy), N.fp(gscale), B, S, T,
-                                            C, R, ctx.blank, ctx.act, N.fp(d_am), N.fp(d_lm), 0,
-                                            N.stream()), "pruned_bwd")
-        return d_am, d_lm, None, None, None, None, None
+        nbytes = 4.0 * (2 * am.numel() + 2 * lm.numel() + lse.numel() + gx.numel() + gy.numel()) \
+            + 8.0 * ranges.numel()
+        if ctx.plain:
+            N.PROF[0] and N.profile_note("s2t_rnnt_pruned_bwd", nbytes, 4.0 * B * T * R * C)
+            N.check(N.lib().s2t_rnnt_pruned_bwd(N.fp(am), N.fp(lm), N.lp(ranges), N.lp(symbols),
+                                                N.fp(lse), N.fp(gx), N.fp(gy), N.fp(gscale), B, S,
+                                                T, C, R, ctx.blank, ctx.act, N.fp(d_am),
+                                                N.fp(d_lm), 0, N.stream()), "pruned_bwd")
+        else:
+            N.PROF[0] and N.profile_note("s2t_rnnt_pruned_bwd_typed", nbytes, 4.0 * B * T * R * C)
+            N.check(N.lib().s2t_rnnt_pruned_bwd_typed(N.fp(am), N.fp(lm), N.lp(ranges),
+                                                      N.lp(symbols), N.fp(lse), N.fp(gx), N.fp(gy),
+                                                      N.fp(gscale), B, S, T, C, R, ctx.blank,
+                                                      ctx.act, ctx.ty, N.fp(d_am), N.fp(d_lm), 0,
+                                                      N.stream()), "pruned_bwd_typed")
+        return d_am, d_lm, None, None, None, None, None, None, None
 
 
-def rnnt_pruned_joiner_loss(am, lm, ranges, symbols, boundary, blank=0, activation="relu"):
-    return _PrunedJoinerLoss.apply(am, lm, ranges, symbols, boundary, blank, activation)
+def _full_ranges(B, T, S, dev):
+    """ranges of the full lattice: every frame's band is all S+1 rows."""
+    return torch.arange(S + 1, dtype=torch.int64, device=dev).expand(B, T, S + 1).contiguous()
+
+
+def rnnt_pruned_joiner_loss(am, lm, ranges, symbols, boundary, blank=0, activation="relu",
+                            rnnt_type="regular", delay_penalty=0.0):
+    """k2.rnnt_loss_pruned(reduction='none') on the fused joiner's lattice.  rnnt_type 'modified' /
+    'constrained' emit at most one symbol per frame; delay_penalty >= 0 pushes symbols to earlier
+    frames.  ranges None is the full lattice: every row in every frame."""
+    ty, pen = check_rnnt_type(rnnt_type, delay_penalty)
+    if ranges is None:
+        ranges = _full_ranges(am.shape[0], am.shape[1], lm.shape[1] - 1, am.device)
+    return _PrunedJoinerLoss.apply(am, lm, ranges, symbols, boundary, blank, activation, ty, pen)
 
 
 class _LatticeLoss(torch.autograd.Function):
     """Materialised lattice: logits (B,T,R,V); ranges None => full lattice (R = S+1)."""
 
     @staticmethod
-    def forward(ctx, logits, ranges, symbols, boundary, blank):
+    def forward(ctx, logits, ranges, symbols, boundary, blank, ty, pen):
         _dev_check(logits)
         logits = logits.contiguous().float()
         B, T, R, V = logits.shape
         S = symbols.shape[1]
         _check_lattice_rows(S)
         dev = logits.device
-        px = torch.empty((B, S, T + 1), dtype=torch.float32, device=dev)
+        plain = ty == RNNT_TYPES["regular"] and pen == 0.0
+        px = torch.empty((B, S, T + 1 if ty == RNNT_TYPES["regular"] else T), dtype=torch.float32,
+                         device=dev)
         py = torch.empty((B, S + 1, T), dtype=torch.float32, device=dev)
         lse = torch.empty((B, T, R), dtype=torch.float32, device=dev)
-        N.check(N.lib().s2t_rnnt_lattice_fwd(N.fp(logits), N.lp(ranges), N.lp(symbols),
-                                             N.lp(boundary), B, S, T, V, R, int(blank), N.fp(px),
-                                             N.fp(py), N.fp(lse), N.stream()), "lattice_fwd")
+        if plain:
+            N.check(N.lib().s2t_rnnt_lattice_fwd(N.fp(logits), N.lp(ranges), N.lp(symbols),
+                                                 N.lp(boundary), B, S, T, V, R, int(blank),
+                                                 N.fp(px), N.fp(py), N.fp(lse), N.stream()),
+                    "lattice_fwd")
+        else:
+            N.PROF[0] and N.profile_note("s2t_rnnt_lattice_fwd_typed",
+                           4.0 * (logits.numel() + px.numel() + py.numel() + lse.numel()))
+            N.check(N.lib().s2t_rnnt_lattice_fwd_typed(N.fp(logits), N.lp(ranges), N.lp(symbols),
+                                                       N.lp(boundary), B, S, T, V, R, int(blank),
+                                                       ty, pen, N.fp(px), N.fp(py), N.fp(lse),
+                                                       N.stream()), "lattice_fwd_typed")
         ans, _, gx, gy = mutual_information(px, py, boundary)
         ctx.save_for_backward(logits, symbols, lse, gx, gy)
         ctx.ranges = ranges
-        ctx.blank = int(blank)
+        ctx.blank, ctx.ty, ctx.plain = int(blank), ty, plain
         return -ans
 
     @staticmethod
@@ -433,15 +515,28 @@ class _LatticeLoss(torch.autograd.Function):
         S = symbols.shape[1]
         gscale = (-g).contiguous().float()
         d = torch.empty_like(logits)
-        N.check(N.lib().s2t_rnnt_lattice_bwd(N.fp(logits), N.lp(ctx.ranges), N.lp(symbols),
-                                             N.fp(lse), N.fp(gx), N.fp(gy), N.fp(gscale), B, S, T,
-                                             V, R, ctx.blank, N.fp(d), N.stream()),
-                "lattice_bwd")
-        return d, None, None, None, None
+        if ctx.plain:
+            N.check(N.lib().s2t_rnnt_lattice_bwd(N.fp(logits), N.lp(ctx.ranges), N.lp(symbols),
+                                                 N.fp(lse), N.fp(gx), N.fp(gy), N.fp(gscale), B, S,
+                                                 T, V, R, ctx.blank, N.fp(d), N.stream()),
+                    "lattice_bwd")
+        else:
+            N.PROF[0] and N.profile_note("s2t_rnnt_lattice_bwd_typed",
+                           4.0 * (2 * logits.numel() + lse.numel() + gx.numel() + gy.numel()))
+            N.check(N.lib().s2t_rnnt_lattice_bwd_typed(N.fp(logits), N.lp(ctx.ranges),
+                                                       N.lp(symbols), N.fp(lse), N.fp(gx),
+                                                       N.fp(gy), N.fp(gscale), B, S, T, V, R,
+                                                       ctx.blank, ctx.ty, N.fp(d), N.stream()),
+                    "lattice_bwd_typed")
+        return d, None, None, None, None, None, None
 
 
-def rnnt_lattice_loss(logits, ranges, symbols, boundary, blank=0):
-    return _LatticeLoss.apply(logits, ranges, symbols, boundary, blank)
+def rnnt_lattice_loss(logits, ranges, symbols, boundary, blank=0, rnnt_type="regular",
+                      delay_penalty=0.0):
+    """Materialised lattice under k2.rnnt_loss_pruned's rnnt_type / delay_penalty; ranges None is
+    the full lattice (R = S+1) for every type."""
+    ty, pen = check_rnnt_type(rnnt_type, delay_penalty)
+    return _LatticeLoss.apply(logits, ranges, symbols, boundary, blank, ty, pen)
 
 
 def make_boundary(target_lengths, frame_lengths, device):

@@ -75,9 +75,9 @@ class PrunedRnntLossConfig:
 class PrunedRnntLoss(nn.Module):
     def __init__(self, config: PrunedRnntLossConfig) -> None:
         super().__init__()
-        if config.rnnt_type != "regular" or config.delay_penalty != 0.0:
-            raise NotImplementedError("only rnnt_type='regular', delay_penalty=0 (all shipped "
-                                      "YAMLs) are on the accelerated path")
+        K.check_rnnt_type(config.rnnt_type, config.delay_penalty)     # ValueError on either
+        self._rnnt_type = config.rnnt_type
+        self._delay_penalty = float(config.delay_penalty)
         self._termination_symbol = config.termination_symbol
         self._reduction = config.reduction
 
@@ -85,9 +85,11 @@ class PrunedRnntLoss(nn.Module):
         sym = targets.to(device=ranges.device, dtype=torch.int64).contiguous()
         if isinstance(logits, PrunedLattice):
             per = K.rnnt_pruned_joiner_loss(logits.am, logits.lm, ranges, sym, boundary,
-                                            self._termination_symbol, logits.activation)
+                                            self._termination_symbol, logits.activation,
+                                            self._rnnt_type, self._delay_penalty)
         else:
-            per = K.rnnt_lattice_loss(logits, ranges, sym, boundary, self._termination_symbol)
+            per = K.rnnt_lattice_loss(logits, ranges, sym, boundary, self._termination_symbol,
+                                      self._rnnt_type, self._delay_penalty)
         return _reduce(per, self._reduction)
 
 
