@@ -95,66 +95,46 @@ int s2t_rnnt_smooth_bwd(const float* am_probs, const float* lm_probs, const floa
                         const float* am_dot, const float* u, int B, int S, int T, int C, int blank,
                         float lam, float mu, float* dlogu_part, float* v, float* d_am, float* d_lm,
                         void* stream);
-int s2t_mutual_info_fwd(const float* px, const float* py, const long* boundary, int B, int S,
-                        int T, float* p, float* ans, void* stream);
-int s2t_mutual_info_bwd(const float* px, const float* py, const long* boundary, const float* p,
-                        const float* ans_grad, int B, int S, int T, float* px_grad,
-                        float* py_grad, void* stream);
-int s2t_rnnt_prune_ranges(const float* px_grad, const float* py_grad, const long* boundary, int B,
-                          int S, int T, int s_range, long* ranges, void* stream);
-/* The recursion of k2's rnnt_type "modified" / "constrained" (k2 selects it by px.shape[2] == T): the
- * symbol arc advances a frame too, p[s][t] = logadd(p[s-1][t-1] + px[s-1][t-1], p[s][t-1] +
- * py[s][t-1]); px [B][S][T], px_grad [B][S][T], everything else as s2t_mutual_info_fwd / _bwd (p
- * [B][S+1][T+1], the same limit of 1024 lattice rows).  An utterance without a path (S_b > T_b, or a
- * band that one symbol per frame cannot follow) scores -inf and has zero gradients. */
-int s2t_mutual_info_mod_fwd(const float* px, const float* py, const long* boundary, int B, int S,
-                            int T, float* p, float* ans, void* stream);
-int s2t_mutual_info_mod_bwd(const float* px, const float* py, const long* boundary, const float* p,
-                            const float* ans_grad, int B, int S, int T, float* px_grad,
-                            float* py_grad, void* stream);
-/* k2.rnnt_loss_pruned's rnnt_type, for the _typed entry points below.  REGULAR: px [B][S][T+1], columns
- * T and T_b -inf.  MODIFIED: px [B][S][T], no such fix.  CONSTRAINED: MODIFIED, then px[b][s][t] +=
- * py[b][s+1][t] (-inf where row s+1 is outside frame t's band).  delay_penalty >= 0 (any type): px[b][s][t]
- * += delay_penalty * ((T_b - 1) / 2 - t), a constant without a gradient, so the _bwd_typed entry points
- * take the type only; their dpx is [B][S][T+1] or [B][S][T] as px.  An unknown type or a negative penalty
- * returns -1.  The untyped entry points are REGULAR with penalty 0. */
+/* k2.rnnt_loss_pruned's rnnt_type: an argument of the recursion and of both lattice builders.
+ * REGULAR: px [B][S][T+1], columns T and T_b -inf.  MODIFIED: px [B][S][T], no such fix.  CONSTRAINED:
+ * MODIFIED, then px[b][s][t] += py[b][s+1][t] (-inf where row s+1 is outside frame t's band).
+ * delay_penalty >= 0 (any type): px[b][s][t] += delay_penalty * ((T_b - 1) / 2 - t), a constant without
+ * a gradient, so the _bwd entry points take the type only; their dpx is [B][S][T+1] or [B][S][T] as px.
+ * An unknown type or a negative penalty returns -1 before anything is launched. */
 #define S2T_RNNT_REGULAR 0
 #define S2T_RNNT_MODIFIED 1
 #define S2T_RNNT_CONSTRAINED 2
+/* The recursion.  REGULAR walks the anti-diagonals of px [B][S][T+1]; MODIFIED and CONSTRAINED (k2
+ * selects it by px.shape[2] == T) walk the frames, as the symbol arc advances a frame too: p[s][t] =
+ * logadd(p[s-1][t-1] + px[s-1][t-1], p[s][t-1] + py[s][t-1]), px and px_grad [B][S][T].  Either way
+ * py [B][S+1][T], p [B][S+1][T+1], at most 1024 lattice rows.  An utterance without a path (modified:
+ * S_b > T_b, or a band that one symbol per frame cannot follow) scores -inf and has zero gradients. */
+int s2t_mutual_info_fwd(const float* px, const float* py, const long* boundary, int B, int S,
+                        int T, int rnnt_type, float* p, float* ans, void* stream);
+int s2t_mutual_info_bwd(const float* px, const float* py, const long* boundary, const float* p,
+                        const float* ans_grad, int B, int S, int T, int rnnt_type, float* px_grad,
+                        float* py_grad, void* stream);
+int s2t_rnnt_prune_ranges(const float* px_grad, const float* py_grad, const long* boundary, int B,
+                          int S, int T, int s_range, long* ranges, void* stream);
 /* fused joiner: logits[b,t,i,:] = act(am[b,t,:] + lm[b,ranges[b,t,0]+i,:]) is
  * never materialised; act: 0 = relu, 1 = tanh.  lse [B][T][R]. */
 int s2t_rnnt_pruned_fwd(const float* am, const float* lm, const long* ranges,
                         const long* symbols, const long* boundary, int B, int S, int T, int C,
-                        int R, int blank, int act, float* px, float* py, float* lse, void* stream);
+                        int R, int blank, int act, int rnnt_type, float delay_penalty, float* px,
+                        float* py, float* lse, void* stream);
 int s2t_rnnt_pruned_bwd(const float* am, const float* lm, const long* ranges,
                         const long* symbols, const float* lse, const float* dpx, const float* dpy,
                         const float* gscale, int B, int S, int T, int C, int R, int blank, int act,
-                        float* d_am, float* d_lm, int accumulate, void* stream);
-int s2t_rnnt_pruned_fwd_typed(const float* am, const float* lm, const long* ranges,
-                              const long* symbols, const long* boundary, int B, int S, int T, int C,
-                              int R, int blank, int act, int rnnt_type, float delay_penalty,
-                              float* px, float* py, float* lse, void* stream);
-int s2t_rnnt_pruned_bwd_typed(const float* am, const float* lm, const long* ranges,
-                              const long* symbols, const float* lse, const float* dpx,
-                              const float* dpy, const float* gscale, int B, int S, int T, int C,
-                              int R, int blank, int act, int rnnt_type, float* d_am, float* d_lm,
-                              int accumulate, void* stream);
+                        int rnnt_type, float* d_am, float* d_lm, int accumulate, void* stream);
 /* materialised lattice: logits [B][T][R][V]; ranges NULL => full lattice, R = S+1 */
 int s2t_rnnt_lattice_fwd(const float* logits, const long* ranges, const long* symbols,
                          const long* boundary, int B, int S, int T, int V, int R, int blank,
-                         float* px, float* py, float* lse, void* stream);
+                         int rnnt_type, float delay_penalty, float* px, float* py, float* lse,
+                         void* stream);
 int s2t_rnnt_lattice_bwd(const float* logits, const long* ranges, const long* symbols,
                          const float* lse, const float* dpx, const float* dpy,
                          const float* gscale, int B, int S, int T, int V, int R, int blank,
-                         float* d_logits, void* stream);
-int s2t_rnnt_lattice_fwd_typed(const float* logits, const long* ranges, const long* symbols,
-                               const long* boundary, int B, int S, int T, int V, int R, int blank,
-                               int rnnt_type, float delay_penalty, float* px, float* py,
-                               float* lse, void* stream);
-int s2t_rnnt_lattice_bwd_typed(const float* logits, const long* ranges, const long* symbols,
-                               const float* lse, const float* dpx, const float* dpy,
-                               const float* gscale, int B, int S, int T, int V, int R, int blank,
-                               int rnnt_type, float* d_logits, void* stream);
+                         int rnnt_type, float* d_logits, void* stream);
 
 
 /* ---- zipformer streaming ops (model/layer/scaling.py: Swoosh :1340-1509, BiasNorm

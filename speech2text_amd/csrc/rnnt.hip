@@ -23,6 +23,8 @@
 #include "common.h"
 #include "../../include/s2t_mi355.h"
 
+#include <type_traits>
+
 namespace {
 
 // ---------------------------------------------------------------- row exp
@@ -869,9 +871,19 @@ __global__ void fill_kernel(float* __restrict__ p, long n, float v) {
   for (; i < n; i += stride) p[i] = v;
 }
 
-inline int mi_threads(int S) {
-  int nt = ((S + 1 + 63) / 64) * 64;
-  return nt;
+inline bool known_type(int rnnt_type) {
+  return rnnt_type == S2T_RNNT_REGULAR || rnnt_type == S2T_RNNT_MODIFIED ||
+         rnnt_type == S2T_RNNT_CONSTRAINED;
+}
+inline int px_cols(int rnnt_type, int T) { return rnnt_type == S2T_RNNT_REGULAR ? T + 1 : T; }
+
+// threads of the recursion's workgroup: one per lattice row, in whole waves.  0: an empty batch, -1:
+// refused (an unknown type before anything else, as in every entry point that takes one)
+inline int mi_threads(int rnnt_type, int B, int S, int T) {
+  if (!known_type(rnnt_type)) return -1;
+  if (B <= 0) return 0;
+  if (S < 0 || T < 0 || S + 1 > 1024) return -1;
+  return ((S + 1 + 63) / 64) * 64;
 }
 
 }  // namespace
@@ -942,29 +954,31 @@ extern "C" int s2t_rnnt_simple_bwd(const float* am_probs, const float* lm_probs,
 }
 
 extern "C" int s2t_mutual_info_fwd(const float* px, const float* py, const long* boundary, int B,
-                                   int S, int T, float* p, float* ans, void* stream) {
-  if (B <= 0) return 0;
-  if (S < 0 || T < 0 || S + 1 > 1024) return -1;
-  const int nt = mi_threads(S);
-  hipLaunchKernelGGL(mi_fwd_kernel, dim3(B), dim3(nt), sizeof(float) * 2 * (nt + 1),
-                     (hipStream_t)stream, px, py, boundary, S, T, p, ans);
+                                   int S, int T, int rnnt_type, float* p, float* ans,
+                                   void* stream) {
+  const int nt = mi_threads(rnnt_type, B, S, T);
+  if (nt <= 0) return nt;
+  hipLaunchKernelGGL(rnnt_type == S2T_RNNT_REGULAR ? mi_fwd_kernel : mi_mod_fwd_kernel, dim3(B),
+                     dim3(nt), sizeof(float) * 2 * (nt + 1), (hipStream_t)stream, px, py, boundary,
+                     S, T, p, ans);
   S2T_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int s2t_mutual_info_bwd(const float* px, const float* py, const long* boundary,
                                    const float* p, const float* ans_grad, int B, int S, int T,
-                                   float* px_grad, float* py_grad, void* stream) {
-  if (B <= 0) return 0;
-  if (S < 0 || T < 0 || S + 1 > 1024) return -1;
+                                   int rnnt_type, float* px_grad, float* py_grad, void* stream) {
+  const int nt = mi_threads(rnnt_type, B, S, T);
+  if (nt <= 0) return nt;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(px_grad, 0, sizeof(float) * (size_t)B * S * (T + 1), st);
+  const size_t nx = (size_t)B * S * px_cols(rnnt_type, T), ny = (size_t)B * (S + 1) * T;
+  hipError_t e = nx ? hipMemsetAsync(px_grad, 0, sizeof(float) * nx, st) : hipSuccess;
   if (e != hipSuccess) return (int)e;
-  e = hipMemsetAsync(py_grad, 0, sizeof(float) * (size_t)B * (S + 1) * T, st);
+  e = ny ? hipMemsetAsync(py_grad, 0, sizeof(float) * ny, st) : hipSuccess;
   if (e != hipSuccess) return (int)e;
-  const int nt = mi_threads(S);
-  hipLaunchKernelGGL(mi_bwd_kernel, dim3(B), dim3(nt), sizeof(float) * 4 * (nt + 1), st, px, py,
-                     boundary, p, ans_grad, S, T, px_grad, py_grad);
+  hipLaunchKernelGGL(rnnt_type == S2T_RNNT_REGULAR ? mi_bwd_kernel : mi_mod_bwd_kernel, dim3(B),
+                     dim3(nt), sizeof(float) * 4 * (nt + 1), st, px, py, boundary, p, ans_grad, S, T,
+                     px_grad, py_grad);
   S2T_CHECK_LAUNCH();
   return 0;
 }
@@ -980,207 +994,112 @@ extern "C" int s2t_rnnt_prune_ranges(const float* px_grad, const float* py_grad,
   return 0;
 }
 
-// KERNEL<classes per lane, TY> by joiner width; `rows` and `st` are the caller's
-#define S2T_DISPATCH_C(KERNEL, TY, ...)                                                     \
-  do {                                                                                      \
-    const unsigned nb__ = (unsigned)((rows + 3) / 4);                                       \
-    if (C <= 128)                                                                           \
-      hipLaunchKernelGGL((KERNEL<2, TY>), dim3(nb__), dim3(256), 0, st, __VA_ARGS__);       \
-    else if (C <= 256)                                                                      \
-      hipLaunchKernelGGL((KERNEL<4, TY>), dim3(nb__), dim3(256), 0, st, __VA_ARGS__);       \
-    else if (C <= 512)                                                                      \
-      hipLaunchKernelGGL((KERNEL<8, TY>), dim3(nb__), dim3(256), 0, st, __VA_ARGS__);       \
-    else if (C <= 1024)                                                                     \
-      hipLaunchKernelGGL((KERNEL<16, TY>), dim3(nb__), dim3(256), 0, st, __VA_ARGS__);      \
-    else                                                                                    \
-      return -1;                                                                            \
-  } while (0)
-
 namespace {
-// the forward builders' instantiation: K_REG only without a penalty; -1 for an unknown type or a
-// negative penalty
-inline int fwd_kind(int rnnt_type, float delay_penalty) {
-  if (!(delay_penalty >= 0.f)) return -1;
-  if (rnnt_type == S2T_RNNT_REGULAR) return delay_penalty > 0.f ? K_REGPEN : K_REG;
-  if (rnnt_type == S2T_RNNT_MODIFIED) return K_MOD;
-  if (rnnt_type == S2T_RNNT_CONSTRAINED) return K_CON;
+// A runtime kind or joiner width becomes the template argument here and nowhere else: f is a generic
+// lambda that takes it as a std::integral_constant.  -1 for a value without an instantiation.
+template <int V>
+using Const = std::integral_constant<int, V>;
+
+// the backward kernels take the type only (WITH_PEN false: no K_REGPEN instantiation of them)
+template <bool WITH_PEN, class F>
+int with_kind(int kind, F f) {
+  if (kind == K_REG) return f(Const<K_REG>{});
+  if (kind == K_MOD) return f(Const<K_MOD>{});
+  if (kind == K_CON) return f(Const<K_CON>{});
+  if constexpr (WITH_PEN)
+    if (kind == K_REGPEN) return f(Const<K_REGPEN>{});
   return -1;
 }
-inline int px_cols(int rnnt_type, int T) { return rnnt_type == S2T_RNNT_REGULAR ? T + 1 : T; }
+
+// classes per lane of the fused joiner's kernels: a row of C classes in one wave's registers
+template <class F>
+int with_width(int C, F f) {
+  if (C <= 128) return f(Const<2>{});
+  if (C <= 256) return f(Const<4>{});
+  if (C <= 512) return f(Const<8>{});
+  if (C <= 1024) return f(Const<16>{});
+  return -1;
+}
+
+// the forward builders' instantiation: K_REG only without a penalty; -1 for an unknown type or a
+// negative (or NaN) penalty
+inline int fwd_kind(int rnnt_type, float delay_penalty) {
+  if (!(delay_penalty >= 0.f) || !known_type(rnnt_type)) return -1;
+  return rnnt_type == S2T_RNNT_REGULAR && delay_penalty > 0.f ? K_REGPEN : rnnt_type;
+}
+
+// px and py start at -inf: the builders write only the cells inside each frame's band
+inline int fill_pxpy(float* px, float* py, int B, int S, int T, int rnnt_type, void* stream) {
+  const int rc = s2t_fill_f32(px, (long)B * S * px_cols(rnnt_type, T), S2T_NEG_INF, stream);
+  return rc ? rc : s2t_fill_f32(py, (long)B * (S + 1) * T, S2T_NEG_INF, stream);
+}
 }  // namespace
-
-extern "C" int s2t_mutual_info_mod_fwd(const float* px, const float* py, const long* boundary,
-                                       int B, int S, int T, float* p, float* ans, void* stream) {
-  if (B <= 0) return 0;
-  if (S < 0 || T < 0 || S + 1 > 1024) return -1;
-  const int nt = mi_threads(S);
-  hipLaunchKernelGGL(mi_mod_fwd_kernel, dim3(B), dim3(nt), sizeof(float) * 2 * (nt + 1),
-                     (hipStream_t)stream, px, py, boundary, S, T, p, ans);
-  S2T_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int s2t_mutual_info_mod_bwd(const float* px, const float* py, const long* boundary,
-                                       const float* p, const float* ans_grad, int B, int S, int T,
-                                       float* px_grad, float* py_grad, void* stream) {
-  if (B <= 0) return 0;
-  if (S < 0 || T < 0 || S + 1 > 1024) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  if (S > 0 && T > 0) e = hipMemsetAsync(px_grad, 0, sizeof(float) * (size_t)B * S * T, st);
-  if (e != hipSuccess) return (int)e;
-  if (T > 0) e = hipMemsetAsync(py_grad, 0, sizeof(float) * (size_t)B * (S + 1) * T, st);
-  if (e != hipSuccess) return (int)e;
-  const int nt = mi_threads(S);
-  hipLaunchKernelGGL(mi_mod_bwd_kernel, dim3(B), dim3(nt), sizeof(float) * 4 * (nt + 1), st, px, py,
-                     boundary, p, ans_grad, S, T, px_grad, py_grad);
-  S2T_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int s2t_rnnt_pruned_fwd_typed(const float* am, const float* lm, const long* ranges,
-                                         const long* symbols, const long* boundary, int B, int S,
-                                         int T, int C, int R, int blank, int act, int rnnt_type,
-                                         float delay_penalty, float* px, float* py, float* lse,
-                                         void* stream) {
-  const int kind = fwd_kind(rnnt_type, delay_penalty);
-  if (kind < 0) return -1;
-  if (B <= 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = s2t_fill_f32(px, (long)B * S * px_cols(rnnt_type, T), S2T_NEG_INF, stream);
-  if (rc) return rc;
-  rc = s2t_fill_f32(py, (long)B * (S + 1) * T, S2T_NEG_INF, stream);
-  if (rc) return rc;
-  const long rows = (long)B * T;
-#define S2T_PFWD(TY)                                                                              \
-  S2T_DISPATCH_C(pruned_fwd_kernel, TY, am, lm, ranges, symbols, boundary, B, S, T, C, R, blank, \
-                 act, delay_penalty, px, py, lse)
-  if (kind == K_REG) S2T_PFWD(K_REG);
-  else if (kind == K_MOD) S2T_PFWD(K_MOD);
-  else if (kind == K_CON) S2T_PFWD(K_CON);
-  else S2T_PFWD(K_REGPEN);
-#undef S2T_PFWD
-  S2T_CHECK_LAUNCH();
-  return 0;
-}
 
 extern "C" int s2t_rnnt_pruned_fwd(const float* am, const float* lm, const long* ranges,
                                    const long* symbols, const long* boundary, int B, int S, int T,
-                                   int C, int R, int blank, int act, float* px, float* py,
-                                   float* lse, void* stream) {
-  return s2t_rnnt_pruned_fwd_typed(am, lm, ranges, symbols, boundary, B, S, T, C, R, blank, act,
-                                   S2T_RNNT_REGULAR, 0.f, px, py, lse, stream);
-}
-
-namespace {
-template <int TYPE>
-int pruned_bwd_launch(const float* am, const float* lm, const long* ranges, const long* symbols,
-                      const float* lse, const float* dpx, const float* dpy, const float* gscale,
-                      int B, int S, int T, int C, int R, int blank, int act, float* d_am,
-                      float* d_lm, int accumulate, hipStream_t st) {
-  {
-    const long rows = (long)B * T;
-    S2T_DISPATCH_C(pruned_dam_kernel, TYPE, am, lm, ranges, symbols, lse, dpx, dpy, gscale, B, S,
-                   T, C, R, blank, act, d_am, accumulate);
-    S2T_CHECK_LAUNCH();
-  }
-  {
-    const unsigned nb = (unsigned)((long)B * (S + 1));      // one DLM_W-wave workgroup per (b, s)
-#define S2T_DLM(MC)                                                                            \
-  hipLaunchKernelGGL((pruned_dlm_kernel<MC, TYPE>), dim3(nb), dim3(64 * DLM_W), 0, st, am, lm, \
-                     ranges, symbols, lse, dpx, dpy, gscale, B, S, T, C, R, blank, act, d_lm,  \
-                     accumulate)
-    if (C <= 128) S2T_DLM(2);
-    else if (C <= 256) S2T_DLM(4);
-    else if (C <= 512) S2T_DLM(8);
-    else if (C <= 1024) S2T_DLM(16);
-    else return -1;
-#undef S2T_DLM
-    S2T_CHECK_LAUNCH();
-  }
-  return 0;
-}
-}  // namespace
-
-extern "C" int s2t_rnnt_pruned_bwd_typed(const float* am, const float* lm, const long* ranges,
-                                         const long* symbols, const float* lse, const float* dpx,
-                                         const float* dpy, const float* gscale, int B, int S, int T,
-                                         int C, int R, int blank, int act, int rnnt_type,
-                                         float* d_am, float* d_lm, int accumulate, void* stream) {
-  if (rnnt_type != S2T_RNNT_REGULAR && rnnt_type != S2T_RNNT_MODIFIED &&
-      rnnt_type != S2T_RNNT_CONSTRAINED)
-    return -1;
+                                   int C, int R, int blank, int act, int rnnt_type,
+                                   float delay_penalty, float* px, float* py, float* lse,
+                                   void* stream) {
+  const int kind = fwd_kind(rnnt_type, delay_penalty);
+  if (kind < 0) return -1;
   if (B <= 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-#define S2T_PBWD(TY)                                                                             \
-  pruned_bwd_launch<TY>(am, lm, ranges, symbols, lse, dpx, dpy, gscale, B, S, T, C, R, blank,   \
-                        act, d_am, d_lm, accumulate, st)
-  if (rnnt_type == S2T_RNNT_MODIFIED) return S2T_PBWD(K_MOD);
-  if (rnnt_type == S2T_RNNT_CONSTRAINED) return S2T_PBWD(K_CON);
-  return S2T_PBWD(K_REG);
-#undef S2T_PBWD
+  int rc = fill_pxpy(px, py, B, S, T, rnnt_type, stream);
+  if (rc) return rc;
+  const unsigned nb = (unsigned)(((long)B * T + 3) / 4);      // one wave per (b, t)
+  rc = with_kind<true>(kind, [&](auto ty) {
+    return with_width(C, [&](auto mc) {
+      hipLaunchKernelGGL((pruned_fwd_kernel<mc(), ty()>), dim3(nb), dim3(256), 0,
+                         (hipStream_t)stream, am, lm, ranges, symbols, boundary, B, S, T, C, R,
+                         blank, act, delay_penalty, px, py, lse);
+      return 0;
+    });
+  });
+  if (rc) return rc;
+  S2T_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int s2t_rnnt_pruned_bwd(const float* am, const float* lm, const long* ranges,
                                    const long* symbols, const float* lse, const float* dpx,
                                    const float* dpy, const float* gscale, int B, int S, int T,
-                                   int C, int R, int blank, int act, float* d_am, float* d_lm,
-                                   int accumulate, void* stream) {
-  return s2t_rnnt_pruned_bwd_typed(am, lm, ranges, symbols, lse, dpx, dpy, gscale, B, S, T, C, R,
-                                   blank, act, S2T_RNNT_REGULAR, d_am, d_lm, accumulate, stream);
-}
-
-extern "C" int s2t_rnnt_lattice_fwd_typed(const float* logits, const long* ranges,
-                                          const long* symbols, const long* boundary, int B, int S,
-                                          int T, int V, int R, int blank, int rnnt_type,
-                                          float delay_penalty, float* px, float* py, float* lse,
-                                          void* stream) {
-  const int kind = fwd_kind(rnnt_type, delay_penalty);
-  if (kind < 0) return -1;
+                                   int C, int R, int blank, int act, int rnnt_type, float* d_am,
+                                   float* d_lm, int accumulate, void* stream) {
+  if (!known_type(rnnt_type)) return -1;
   if (B <= 0) return 0;
-  int rc = s2t_fill_f32(px, (long)B * S * px_cols(rnnt_type, T), S2T_NEG_INF, stream);
-  if (rc) return rc;
-  rc = s2t_fill_f32(py, (long)B * (S + 1) * T, S2T_NEG_INF, stream);
-  if (rc) return rc;
-  const long nodes = (long)B * T * R;
-#define S2T_LFWD(TY)                                                                            \
-  hipLaunchKernelGGL(lattice_fwd_kernel<TY>, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0,  \
-                     (hipStream_t)stream, logits, ranges, symbols, boundary, B, S, T, V, R,    \
-                     blank, delay_penalty, px, py, lse)
-  if (kind == K_REG) S2T_LFWD(K_REG);
-  else if (kind == K_MOD) S2T_LFWD(K_MOD);
-  else if (kind == K_CON) S2T_LFWD(K_CON);
-  else S2T_LFWD(K_REGPEN);
-#undef S2T_LFWD
-  S2T_CHECK_LAUNCH();
-  return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned nb_am = (unsigned)(((long)B * T + 3) / 4);   // one wave per (b, t)
+  const unsigned nb_lm = (unsigned)((long)B * (S + 1));       // one DLM_W-wave workgroup per (b, s)
+  return with_kind<false>(rnnt_type, [&](auto ty) {
+    return with_width(C, [&](auto mc) {
+      hipLaunchKernelGGL((pruned_dam_kernel<mc(), ty()>), dim3(nb_am), dim3(256), 0, st, am, lm,
+                         ranges, symbols, lse, dpx, dpy, gscale, B, S, T, C, R, blank, act, d_am,
+                         accumulate);
+      S2T_CHECK_LAUNCH();
+      hipLaunchKernelGGL((pruned_dlm_kernel<mc(), ty()>), dim3(nb_lm), dim3(64 * DLM_W), 0, st, am,
+                         lm, ranges, symbols, lse, dpx, dpy, gscale, B, S, T, C, R, blank, act,
+                         d_lm, accumulate);
+      S2T_CHECK_LAUNCH();
+      return 0;
+    });
+  });
 }
 
 extern "C" int s2t_rnnt_lattice_fwd(const float* logits, const long* ranges, const long* symbols,
                                     const long* boundary, int B, int S, int T, int V, int R,
-                                    int blank, float* px, float* py, float* lse, void* stream) {
-  return s2t_rnnt_lattice_fwd_typed(logits, ranges, symbols, boundary, B, S, T, V, R, blank,
-                                    S2T_RNNT_REGULAR, 0.f, px, py, lse, stream);
-}
-
-extern "C" int s2t_rnnt_lattice_bwd_typed(const float* logits, const long* ranges,
-                                          const long* symbols, const float* lse, const float* dpx,
-                                          const float* dpy, const float* gscale, int B, int S,
-                                          int T, int V, int R, int blank, int rnnt_type,
-                                          float* d_logits, void* stream) {
-  if (rnnt_type != S2T_RNNT_REGULAR && rnnt_type != S2T_RNNT_MODIFIED &&
-      rnnt_type != S2T_RNNT_CONSTRAINED)
-    return -1;
+                                    int blank, int rnnt_type, float delay_penalty, float* px,
+                                    float* py, float* lse, void* stream) {
+  const int kind = fwd_kind(rnnt_type, delay_penalty);
+  if (kind < 0) return -1;
   if (B <= 0) return 0;
-  const long nodes = (long)B * T * R;
-#define S2T_LBWD(TY)                                                                            \
-  hipLaunchKernelGGL(lattice_bwd_kernel<TY>, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0,  \
-                     (hipStream_t)stream, logits, ranges, symbols, lse, dpx, dpy, gscale, B, S, \
-                     T, V, R, blank, d_logits)
-  if (rnnt_type == S2T_RNNT_MODIFIED) S2T_LBWD(K_MOD);
-  else if (rnnt_type == S2T_RNNT_CONSTRAINED) S2T_LBWD(K_CON);
-  else S2T_LBWD(K_REG);
-#undef S2T_LBWD
+  const int rc = fill_pxpy(px, py, B, S, T, rnnt_type, stream);
+  if (rc) return rc;
+  const unsigned nb = (unsigned)(((long)B * T * R + 3) / 4);  // one wave per lattice node
+  with_kind<true>(kind, [&](auto ty) {
+    hipLaunchKernelGGL(lattice_fwd_kernel<ty()>, dim3(nb), dim3(256), 0, (hipStream_t)stream,
+                       logits, ranges, symbols, boundary, B, S, T, V, R, blank, delay_penalty, px,
+                       py, lse);
+    return 0;
+  });
   S2T_CHECK_LAUNCH();
   return 0;
 }
@@ -1188,7 +1107,16 @@ extern "C" int s2t_rnnt_lattice_bwd_typed(const float* logits, const long* range
 extern "C" int s2t_rnnt_lattice_bwd(const float* logits, const long* ranges, const long* symbols,
                                     const float* lse, const float* dpx, const float* dpy,
                                     const float* gscale, int B, int S, int T, int V, int R,
-                                    int blank, float* d_logits, void* stream) {
-  return s2t_rnnt_lattice_bwd_typed(logits, ranges, symbols, lse, dpx, dpy, gscale, B, S, T, V, R,
-                                    blank, S2T_RNNT_REGULAR, d_logits, stream);
+                                    int blank, int rnnt_type, float* d_logits, void* stream) {
+  if (!known_type(rnnt_type)) return -1;
+  if (B <= 0) return 0;
+  const unsigned nb = (unsigned)(((long)B * T * R + 3) / 4);  // one wave per lattice node
+  with_kind<false>(rnnt_type, [&](auto ty) {
+    hipLaunchKernelGGL(lattice_bwd_kernel<ty()>, dim3(nb), dim3(256), 0, (hipStream_t)stream,
+                       logits, ranges, symbols, lse, dpx, dpy, gscale, B, S, T, V, R, blank,
+                       d_logits);
+    return 0;
+  });
+  S2T_CHECK_LAUNCH();
+  return 0;
 }

@@ -161,26 +161,6 @@ def _check_lattice_rows(S):
                          "workgroup, csrc/rnnt.hip)")
 
 
-def _mutual_information_modified(px, py, boundary, want_grads):
-    """px (B,S,T): the modified topology's column walk (csrc/rnnt.hip mi_mod_*_kernel)."""
-    B, S, T = px.shape
-    dev = px.device
-    p = torch.empty((B, S + 1, T + 1), dtype=torch.float32, device=dev)
-    ans = torch.empty((B,), dtype=torch.float32, device=dev)
-    L = N.lib()
-    N.PROF[0] and N.profile_note("s2t_mutual_info_mod_fwd", 4.0 * (px.numel() + py.numel() + p.numel()))
-    N.check(L.s2t_mutual_info_mod_fwd(N.fp(px), N.fp(py), N.lp(boundary), B, S, T, N.fp(p),
-                                      N.fp(ans), N.stream()), "s2t_mutual_info_mod_fwd")
-    if not want_grads:
-        return ans, p, None, None
-    gx = torch.empty_like(px)
-    gy = torch.empty_like(py)
-    N.PROF[0] and N.profile_note("s2t_mutual_info_mod_bwd", 4.0 * (2 * px.numel() + 2 * py.numel() + p.numel()))
-    N.check(L.s2t_mutual_info_mod_bwd(N.fp(px), N.fp(py), N.lp(boundary), N.fp(p), None, B, S, T,
-                                      N.fp(gx), N.fp(gy), N.stream()), "s2t_mutual_info_mod_bwd")
-    return ans, p, gx, gy
-
-
 def mutual_information(px, py, boundary, want_grads=True):
     """Raw recursion: returns (scores (B,), p, px_grad, py_grad) -- no autograd.  As in k2 the
     topology follows from the shapes: px (B,S,T+1) is the regular lattice, px (B,S,T) -- as many
@@ -190,22 +170,21 @@ def mutual_information(px, py, boundary, want_grads=True):
     if py.shape != (B, S + 1, T1) and py.shape != (B, S + 1, T1 - 1):
         raise ValueError(f"mutual_information: px {tuple(px.shape)} and py {tuple(py.shape)} are "
                          "neither a regular (B,S,T+1)/(B,S+1,T) nor a modified (B,S,T)/(B,S+1,T) pair")
-    if T1 == py.shape[2]:
-        return _mutual_information_modified(px, py, boundary, want_grads)
-    T = T1 - 1
+    T = py.shape[2]
+    ty = RNNT_TYPES["modified" if T1 == T else "regular"]
     dev = px.device
     p = torch.empty((B, S + 1, T + 1), dtype=torch.float32, device=dev)
     ans = torch.empty((B,), dtype=torch.float32, device=dev)
     L = N.lib()
     N.PROF[0] and N.profile_note("s2t_mutual_info_fwd", 4.0 * (px.numel() + py.numel() + p.numel()))
-    N.check(L.s2t_mutual_info_fwd(N.fp(px), N.fp(py), N.lp(boundary), B, S, T, N.fp(p),
+    N.check(L.s2t_mutual_info_fwd(N.fp(px), N.fp(py), N.lp(boundary), B, S, T, ty, N.fp(p),
                                   N.fp(ans), N.stream()), "s2t_mutual_info_fwd")
     if not want_grads:
         return ans, p, None, None
     gx = torch.empty_like(px)
     gy = torch.empty_like(py)
     N.PROF[0] and N.profile_note("s2t_mutual_info_bwd", 4.0 * (2 * px.numel() + 2 * py.numel() + p.numel()))
-    N.check(L.s2t_mutual_info_bwd(N.fp(px), N.fp(py), N.lp(boundary), N.fp(p), None, B, S, T,
+    N.check(L.s2t_mutual_info_bwd(N.fp(px), N.fp(py), N.lp(boundary), N.fp(p), None, B, S, T, ty,
                                   N.fp(gx), N.fp(gy), N.stream()), "s2t_mutual_info_bwd")
     return ans, p, gx, gy
 
@@ -384,6 +363,14 @@ def check_rnnt_type(rnnt_type, delay_penalty):
     return RNNT_TYPES[rnnt_type], pen
 
 
+def _lattice_buffers(B, S, T, R, ty, dev):
+    """What either lattice builder writes: px (B,S,T+1) on the regular lattice and (B,S,T) on the
+    two others, py (B,S+1,T), lse (B,T,R)."""
+    TX = T + 1 if ty == RNNT_TYPES["regular"] else T
+    return [torch.empty(shape, dtype=torch.float32, device=dev)
+            for shape in ((B, S, TX), (B, S + 1, T), (B, T, R))]
+
+
 class _PrunedJoinerLoss(torch.autograd.Function):
     """Fused Joiner tail + k2.rnnt_loss_pruned(reduction='none'): per-utterance neg score
     of the lattice logits[b,t,i,:] = act(am[b,t,:] + lm[b,ranges[b,t,0]+i,:])."""
@@ -396,37 +383,22 @@ class _PrunedJoinerLoss(torch.autograd.Function):
         B, T, C = am.shape
         S = lm.shape[1] - 1
         R = ranges.shape[2]
-        dev = am.device
         _check_lattice_rows(S)
         if C > RNNT_MAX_JOINER_DIM:
             raise ValueError(f"fused pruned joiner: joiner dimension {C} exceeds the kernel's "
                              f"limit of {RNNT_MAX_JOINER_DIM} (a row is held in one wave's "
                              "registers, csrc/rnnt.hip); there is no fallback")
-        L = N.lib()
-        st = N.stream()
-        # the default setting stays on the untyped entry point: the same launches either way, and
-        # the step's profile keeps the entry names its recorded runs are compared by
-        plain = ty == RNNT_TYPES["regular"] and pen == 0.0
-        px = torch.empty((B, S, T + 1 if ty == RNNT_TYPES["regular"] else T), dtype=torch.float32,
-                         device=dev)
-        py = torch.empty((B, S + 1, T), dtype=torch.float32, device=dev)
-        lse = torch.empty((B, T, R), dtype=torch.float32, device=dev)
-        nbytes = 4.0 * (am.numel() + lm.numel() + px.numel() + py.numel() + lse.numel()) \
-            + 8.0 * ranges.numel()
-        if plain:
-            N.PROF[0] and N.profile_note("s2t_rnnt_pruned_fwd", nbytes)
-            N.check(L.s2t_rnnt_pruned_fwd(N.fp(am), N.fp(lm), N.lp(ranges), N.lp(symbols),
-                                          N.lp(boundary), B, S, T, C, R, int(blank), _ACT[act],
-                                          N.fp(px), N.fp(py), N.fp(lse), st), "pruned_fwd")
-        else:
-            N.PROF[0] and N.profile_note("s2t_rnnt_pruned_fwd_typed", nbytes)
-            N.check(L.s2t_rnnt_pruned_fwd_typed(N.fp(am), N.fp(lm), N.lp(ranges), N.lp(symbols),
-                                                N.lp(boundary), B, S, T, C, R, int(blank),
-                                                _ACT[act], ty, pen, N.fp(px), N.fp(py), N.fp(lse),
-                                                st), "pruned_fwd_typed")
+        px, py, lse = _lattice_buffers(B, S, T, R, ty, am.device)
+        N.PROF[0] and N.profile_note("s2t_rnnt_pruned_fwd",
+                                     4.0 * (am.numel() + lm.numel() + px.numel() + py.numel() + lse.numel())
+                                     + 8.0 * ranges.numel())
+        N.check(N.lib().s2t_rnnt_pruned_fwd(N.fp(am), N.fp(lm), N.lp(ranges), N.lp(symbols),
+                                            N.lp(boundary), B, S, T, C, R, int(blank), _ACT[act], ty,
+                                            pen, N.fp(px), N.fp(py), N.fp(lse), N.stream()),
+                "pruned_fwd")
         ans, _, gx, gy = mutual_information(px, py, boundary)
         ctx.save_for_backward(am, lm, ranges, symbols, lse, gx, gy)
-        ctx.blank, ctx.act, ctx.ty, ctx.plain = int(blank), _ACT[act], ty, plain
+        ctx.blank, ctx.act, ctx.ty = int(blank), _ACT[act], ty
         return -ans
 
     @staticmethod
@@ -440,21 +412,13 @@ class _PrunedJoinerLoss(torch.autograd.Function):
         d_lm = torch.empty_like(lm)
         # the (B,T,R,C) pruned logits are recomputed, never stored: the algorithmic traffic is the
         # operands and their gradients; the recomputation costs 2 B T R C flops of VALU per pass
-        nbytes = 4.0 * (2 * am.numel() + 2 * lm.numel() + lse.numel() + gx.numel() + gy.numel()) \
-            + 8.0 * ranges.numel()
-        if ctx.plain:
-            N.PROF[0] and N.profile_note("s2t_rnnt_pruned_bwd", nbytes, 4.0 * B * T * R * C)
-            N.check(N.lib().s2t_rnnt_pruned_bwd(N.fp(am), N.fp(lm), N.lp(ranges), N.lp(symbols),
-                                                N.fp(lse), N.fp(gx), N.fp(gy), N.fp(gscale), B, S,
-                                                T, C, R, ctx.blank, ctx.act, N.fp(d_am),
-                                                N.fp(d_lm), 0, N.stream()), "pruned_bwd")
-        else:
-            N.PROF[0] and N.profile_note("s2t_rnnt_pruned_bwd_typed", nbytes, 4.0 * B * T * R * C)
-            N.check(N.lib().s2t_rnnt_pruned_bwd_typed(N.fp(am), N.fp(lm), N.lp(ranges),
-                                                      N.lp(symbols), N.fp(lse), N.fp(gx), N.fp(gy),
-                                                      N.fp(gscale), B, S, T, C, R, ctx.blank,
-                                                      ctx.act, ctx.ty, N.fp(d_am), N.fp(d_lm), 0,
-                                                      N.stream()), "pruned_bwd_typed")
+        N.PROF[0] and N.profile_note("s2t_rnnt_pruned_bwd",
+                                     4.0 * (2 * am.numel() + 2 * lm.numel() + lse.numel() + gx.numel() + gy.numel())
+                                     + 8.0 * ranges.numel(), 4.0 * B * T * R * C)
+        N.check(N.lib().s2t_rnnt_pruned_bwd(N.fp(am), N.fp(lm), N.lp(ranges), N.lp(symbols),
+                                            N.fp(lse), N.fp(gx), N.fp(gy), N.fp(gscale), B, S, T, C,
+                                            R, ctx.blank, ctx.act, ctx.ty, N.fp(d_am), N.fp(d_lm), 0,
+                                            N.stream()), "pruned_bwd")
         return d_am, d_lm, None, None, None, None, None, None, None
 
 
@@ -484,28 +448,17 @@ class _LatticeLoss(torch.autograd.Function):
         B, T, R, V = logits.shape
         S = symbols.shape[1]
         _check_lattice_rows(S)
-        dev = logits.device
-        plain = ty == RNNT_TYPES["regular"] and pen == 0.0
-        px = torch.empty((B, S, T + 1 if ty == RNNT_TYPES["regular"] else T), dtype=torch.float32,
-                         device=dev)
-        py = torch.empty((B, S + 1, T), dtype=torch.float32, device=dev)
-        lse = torch.empty((B, T, R), dtype=torch.float32, device=dev)
-        if plain:
-            N.check(N.lib().s2t_rnnt_lattice_fwd(N.fp(logits), N.lp(ranges), N.lp(symbols),
-                                                 N.lp(boundary), B, S, T, V, R, int(blank),
-                                                 N.fp(px), N.fp(py), N.fp(lse), N.stream()),
-                    "lattice_fwd")
-        else:
-            N.PROF[0] and N.profile_note("s2t_rnnt_lattice_fwd_typed",
-                           4.0 * (logits.numel() + px.numel() + py.numel() + lse.numel()))
-            N.check(N.lib().s2t_rnnt_lattice_fwd_typed(N.fp(logits), N.lp(ranges), N.lp(symbols),
-                                                       N.lp(boundary), B, S, T, V, R, int(blank),
-                                                       ty, pen, N.fp(px), N.fp(py), N.fp(lse),
-                                                       N.stream()), "lattice_fwd_typed")
+        px, py, lse = _lattice_buffers(B, S, T, R, ty, logits.device)
+        N.PROF[0] and N.profile_note("s2t_rnnt_lattice_fwd",
+                                     4.0 * (logits.numel() + px.numel() + py.numel() + lse.numel()))
+        N.check(N.lib().s2t_rnnt_lattice_fwd(N.fp(logits), N.lp(ranges), N.lp(symbols),
+                                             N.lp(boundary), B, S, T, V, R, int(blank), ty, pen,
+                                             N.fp(px), N.fp(py), N.fp(lse), N.stream()),
+                "lattice_fwd")
         ans, _, gx, gy = mutual_information(px, py, boundary)
         ctx.save_for_backward(logits, symbols, lse, gx, gy)
         ctx.ranges = ranges
-        ctx.blank, ctx.ty, ctx.plain = int(blank), ty, plain
+        ctx.blank, ctx.ty = int(blank), ty
         return -ans
 
     @staticmethod
@@ -515,19 +468,12 @@ class _LatticeLoss(torch.autograd.Function):
         S = symbols.shape[1]
         gscale = (-g).contiguous().float()
         d = torch.empty_like(logits)
-        if ctx.plain:
-            N.check(N.lib().s2t_rnnt_lattice_bwd(N.fp(logits), N.lp(ctx.ranges), N.lp(symbols),
-                                                 N.fp(lse), N.fp(gx), N.fp(gy), N.fp(gscale), B, S,
-                                                 T, V, R, ctx.blank, N.fp(d), N.stream()),
-                    "lattice_bwd")
-        else:
-            N.PROF[0] and N.profile_note("s2t_rnnt_lattice_bwd_typed",
-                           4.0 * (2 * logits.numel() + lse.numel() + gx.numel() + gy.numel()))
-            N.check(N.lib().s2t_rnnt_lattice_bwd_typed(N.fp(logits), N.lp(ctx.ranges),
-                                                       N.lp(symbols), N.fp(lse), N.fp(gx),
-                                                       N.fp(gy), N.fp(gscale), B, S, T, V, R,
-                                                       ctx.blank, ctx.ty, N.fp(d), N.stream()),
-                    "lattice_bwd_typed")
+        N.PROF[0] and N.profile_note("s2t_rnnt_lattice_bwd",
+                                     4.0 * (2 * logits.numel() + lse.numel() + gx.numel() + gy.numel()))
+        N.check(N.lib().s2t_rnnt_lattice_bwd(N.fp(logits), N.lp(ctx.ranges), N.lp(symbols),
+                                             N.fp(lse), N.fp(gx), N.fp(gy), N.fp(gscale), B, S, T, V,
+                                             R, ctx.blank, ctx.ty, N.fp(d), N.stream()),
+                "lattice_bwd")
         return d, None, None, None, None, None, None
 
 

@@ -220,10 +220,13 @@ def test_infeasible_utterance_inside_a_feasible_batch(dev, rnnt_type):
         assert float(per[2].detach()) == float("inf")
 
 
-# ------------------------------------------------------------------ regular parity with the untyped ABI
-def test_regular_through_the_typed_entry_points_is_bit_identical(dev):
-    """s2t_rnnt_{pruned,lattice}_{fwd,bwd}_typed(REGULAR, 0) against the untyped entry points at the
-    C3 bench geometry (the materialised lattice on its first 8 utterances): same bits."""
+# ------------------------------------------------------------------ the defaults through the C ABI
+def test_default_wrappers_equal_the_entry_points_at_regular_without_penalty(dev):
+    """rnnt_pruned_joiner_loss / rnnt_lattice_loss under their defaults against a direct call of
+    s2t_rnnt_{pruned,lattice}_{fwd,bwd} with (S2T_RNNT_REGULAR, 0.0) at the C3 bench geometry (the
+    materialised lattice on its first 8 utterances): same bits in the loss, d_am, d_lm and d_logits,
+    which pins the place of the type and the penalty among the arguments the binding passes through
+    the header-parsed ABI.  Then what the library itself refuses before it launches anything."""
     from speech2text_amd import _native as N
     k = _kern()
     c = LC.bench_case()
@@ -233,60 +236,73 @@ def test_regular_through_the_typed_entry_points_is_bit_identical(dev):
     _, gx, gy = k.rnnt_simple_loss(lm, am, sym, bnd, 0)
     rg = k.rnnt_prune_ranges(gx, gy, bnd, R)
     lib, st, REG = N.lib(), N.stream(), k.RNNT_TYPES["regular"]
-    gscale = (-LC.weights(B)).float().to(dev)
+    w = LC.weights(B).float().to(dev)
+    gscale = -w
 
     def new(*shape):
         return torch.full(shape, 7.0, device=dev)
 
-    def fused(typed):
-        px, py, lse = new(B, S, T + 1), new(B, S + 1, T), new(B, T, R)
-        head = (N.fp(am), N.fp(lm), N.lp(rg), N.lp(sym), N.lp(bnd), B, S, T, C, R, 0, 0)
-        if typed:
-            N.check(lib.s2t_rnnt_pruned_fwd_typed(*head, REG, 0.0, N.fp(px), N.fp(py), N.fp(lse), st), "fwd")
-        else:
-            N.check(lib.s2t_rnnt_pruned_fwd(*head, N.fp(px), N.fp(py), N.fp(lse), st), "fwd")
-        _, _, dx, dy = k.mutual_information(px, py, bnd)
-        d_am, d_lm = new(B, T, C), new(B, S + 1, C)
-        head = (N.fp(am), N.fp(lm), N.lp(rg), N.lp(sym), N.fp(lse), N.fp(dx), N.fp(dy), N.fp(gscale),
-                B, S, T, C, R, 0, 0)
-        if typed:
-            N.check(lib.s2t_rnnt_pruned_bwd_typed(*head, REG, N.fp(d_am), N.fp(d_lm), 0, st), "bwd")
-        else:
-            N.check(lib.s2t_rnnt_pruned_bwd(*head, N.fp(d_am), N.fp(d_lm), 0, st), "bwd")
-        return px, py, lse, d_am, d_lm
+    def wrapped(fn, leaves, *rest):
+        leaves = [x.clone().requires_grad_(True) for x in leaves]
+        per = fn(*leaves, *rest)
+        return (per.detach(),) + torch.autograd.grad(per, leaves, grad_outputs=w[:per.shape[0]])
 
-    for a, b in zip(fused(False), fused(True)):
+    px, py, lse = new(B, S, T + 1), new(B, S + 1, T), new(B, T, R)
+    N.check(lib.s2t_rnnt_pruned_fwd(N.fp(am), N.fp(lm), N.lp(rg), N.lp(sym), N.lp(bnd), B, S, T, C, R, 0, 0,
+                                    REG, 0.0, N.fp(px), N.fp(py), N.fp(lse), st), "fwd")
+    ans, _, dx, dy = k.mutual_information(px, py, bnd)
+    d_am, d_lm = new(B, T, C), new(B, S + 1, C)
+    N.check(lib.s2t_rnnt_pruned_bwd(N.fp(am), N.fp(lm), N.lp(rg), N.lp(sym), N.fp(lse), N.fp(dx), N.fp(dy),
+                                    N.fp(gscale), B, S, T, C, R, 0, 0, REG, N.fp(d_am), N.fp(d_lm), 0, st), "bwd")
+    for a, b in zip(wrapped(k.rnnt_pruned_joiner_loss, (am, lm), rg, sym, bnd), (-ans, d_am, d_lm)):
         assert torch.equal(a, b)
 
     Bs = 8
     from speech2text_amd.model.joiner.joiner import PrunedLattice
     logits = PrunedLattice(am[:Bs], lm[:Bs], rg[:Bs].contiguous(), "relu").materialize().contiguous()
     rgs, syms, bnds = rg[:Bs].contiguous(), sym[:Bs].contiguous(), bnd[:Bs].contiguous()
-
-    def lattice(typed):
-        px, py, lse = new(Bs, S, T + 1), new(Bs, S + 1, T), new(Bs, T, R)
-        head = (N.fp(logits), N.lp(rgs), N.lp(syms), N.lp(bnds), Bs, S, T, C, R, 0)
-        if typed:
-            N.check(lib.s2t_rnnt_lattice_fwd_typed(*head, REG, 0.0, N.fp(px), N.fp(py), N.fp(lse), st), "fwd")
-        else:
-            N.check(lib.s2t_rnnt_lattice_fwd(*head, N.fp(px), N.fp(py), N.fp(lse), st), "fwd")
-        _, _, dx, dy = k.mutual_information(px, py, bnds)
-        d = new(Bs, T, R, C)
-        head = (N.fp(logits), N.lp(rgs), N.lp(syms), N.fp(lse), N.fp(dx), N.fp(dy), N.fp(gscale), Bs, S, T,
-                C, R, 0)
-        if typed:
-            N.check(lib.s2t_rnnt_lattice_bwd_typed(*head, REG, N.fp(d), st), "bwd")
-        else:
-            N.check(lib.s2t_rnnt_lattice_bwd(*head, N.fp(d), st), "bwd")
-        return px, py, lse, d
-
-    for a, b in zip(lattice(False), lattice(True)):
+    px, py, lse = new(Bs, S, T + 1), new(Bs, S + 1, T), new(Bs, T, R)
+    N.check(lib.s2t_rnnt_lattice_fwd(N.fp(logits), N.lp(rgs), N.lp(syms), N.lp(bnds), Bs, S, T, C, R, 0, REG, 0.0,
+                                     N.fp(px), N.fp(py), N.fp(lse), st), "fwd")
+    ans, _, dx, dy = k.mutual_information(px, py, bnds)
+    d = new(Bs, T, R, C)
+    N.check(lib.s2t_rnnt_lattice_bwd(N.fp(logits), N.lp(rgs), N.lp(syms), N.fp(lse), N.fp(dx), N.fp(dy),
+                                     N.fp(gscale), Bs, S, T, C, R, 0, REG, N.fp(d), st), "bwd")
+    for a, b in zip(wrapped(k.rnnt_lattice_loss, (logits,), rgs, syms, bnds), (-ans, d)):
         assert torch.equal(a, b)
-    # an unknown type and a negative penalty are refused by the library itself
-    px, py, lse = new(B, S, T + 1), new(B, S + 1, T), new(B, T, R)
-    head = (N.fp(am), N.fp(lm), N.lp(rg), N.lp(sym), N.lp(bnd), B, S, T, C, R, 0, 0)
-    assert lib.s2t_rnnt_pruned_fwd_typed(*head, 3, 0.0, N.fp(px), N.fp(py), N.fp(lse), st) == -1
-    assert lib.s2t_rnnt_pruned_fwd_typed(*head, REG, -0.5, N.fp(px), N.fp(py), N.fp(lse), st) == -1
+
+    # an unknown type on all six entry points, a negative or NaN penalty on the two forwards: -1 from the
+    # library itself, and every output buffer still holds what it held
+    B, S, T, C, R = 1, 2, 3, 8, 2
+    am, lm, logits, gscale = new(B, T, C), new(B, S + 1, C), new(B, T, R, C), new(B)
+    rg = torch.zeros(B, T, R, dtype=torch.int64, device=dev)
+    sym = torch.ones(B, S, dtype=torch.int64, device=dev)
+    bnd = k.make_boundary(torch.tensor([S]), torch.tensor([T]), dev)
+    px, py, lse, p, ans = new(B, S, T + 1), new(B, S + 1, T), new(B, T, R), new(B, S + 1, T + 1), new(B)
+    dx, dy, d_am, d_lm, d = new(B, S, T + 1), new(B, S + 1, T), new(B, T, C), new(B, S + 1, C), new(B, T, R, C)
+    forwards = (
+        lambda ty, pen: lib.s2t_rnnt_pruned_fwd(N.fp(am), N.fp(lm), N.lp(rg), N.lp(sym), N.lp(bnd), B, S, T, C, R,
+                                                0, 0, ty, pen, N.fp(px), N.fp(py), N.fp(lse), st),
+        lambda ty, pen: lib.s2t_rnnt_lattice_fwd(N.fp(logits), N.lp(rg), N.lp(sym), N.lp(bnd), B, S, T, C, R, 0,
+                                                 ty, pen, N.fp(px), N.fp(py), N.fp(lse), st))
+    typed_only = (
+        lambda ty: lib.s2t_rnnt_pruned_bwd(N.fp(am), N.fp(lm), N.lp(rg), N.lp(sym), N.fp(lse), N.fp(px), N.fp(py),
+                                           N.fp(gscale), B, S, T, C, R, 0, 0, ty, N.fp(d_am), N.fp(d_lm), 0, st),
+        lambda ty: lib.s2t_rnnt_lattice_bwd(N.fp(logits), N.lp(rg), N.lp(sym), N.fp(lse), N.fp(px), N.fp(py),
+                                            N.fp(gscale), B, S, T, C, R, 0, ty, N.fp(d), st),
+        lambda ty: lib.s2t_mutual_info_fwd(N.fp(px), N.fp(py), N.lp(bnd), B, S, T, ty, N.fp(p), N.fp(ans), st),
+        lambda ty: lib.s2t_mutual_info_bwd(N.fp(px), N.fp(py), N.lp(bnd), N.fp(p), None, B, S, T, ty, N.fp(dx),
+                                           N.fp(dy), st))
+    for ty in (3, -1):
+        for call in forwards:
+            assert call(ty, 0.0) == -1
+        for call in typed_only:
+            assert call(ty) == -1
+    for pen in (-0.5, float("nan")):
+        for call in forwards:
+            assert call(REG, pen) == -1
+    for out in (px, py, lse, p, ans, dx, dy, d_am, d_lm, d):
+        assert (out == 7.0).all()
 
 
 # ------------------------------------------------------------------ the chain

@@ -35,9 +35,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
-LOSS_ENTRIES = ("s2t_mutual_info_fwd", "s2t_mutual_info_bwd", "s2t_mutual_info_mod_fwd",
-                "s2t_mutual_info_mod_bwd", "s2t_rnnt_pruned_fwd", "s2t_rnnt_pruned_bwd",
-                "s2t_rnnt_pruned_fwd_typed", "s2t_rnnt_pruned_bwd_typed")
+LOSS_ENTRIES = ("s2t_mutual_info_fwd", "s2t_mutual_info_bwd", "s2t_rnnt_pruned_fwd",
+                "s2t_rnnt_pruned_bwd")
 
 
 def run(setting, args, device):

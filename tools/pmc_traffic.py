@@ -45,7 +45,10 @@ KERNELS = [
     ("attn_delta_pairs_kernel", "s2t_attn_delta_pairs", True),
     ("whiten_apply_kernel", "s2t_whiten_apply", True), ("sumsq2_kernel", "s2t_whiten_apply", False),
     ("mi_fwd_kernel", "s2t_mutual_info_fwd", True), ("mi_bwd_kernel", "s2t_mutual_info_bwd", True),
-    ("pruned_fwd", "s2t_rnnt_pruned_fwd", True), ("pruned_bwd", "s2t_rnnt_pruned_bwd", True),
+    ("mi_mod_fwd_kernel", "s2t_mutual_info_fwd", True), ("mi_mod_bwd_kernel", "s2t_mutual_info_bwd", True),
+    ("pruned_fwd", "s2t_rnnt_pruned_fwd", True), ("pruned_dam_kernel", "s2t_rnnt_pruned_bwd", True),
+    ("pruned_dlm_kernel", "s2t_rnnt_pruned_bwd", False),
+    ("lattice_fwd_kernel", "s2t_rnnt_lattice_fwd", True), ("lattice_bwd_kernel", "s2t_rnnt_lattice_bwd", True),
     ("simple_pxpy", "s2t_rnnt_simple_pxpy", True), ("simple_bwd", "s2t_rnnt_simple_bwd", True),
     ("row_exp", "s2t_rnnt_row_exp", True),
     ("ctc_alpha_beta_kernel", "s2t_ctc_loss_fwd_bwd", True), ("ctc_lse_gather_kernel", "s2t_ctc_loss_fwd_bwd", False),
