@@ -659,6 +659,49 @@ int s2t_rnnt_beam_lstm(const S2tRnntLstmDesc* desc, const float* am, const long*
                        int T, int beam_size, int cutoff_top_k, void* workspace, long* tokens,
                        long* frames, long* out_len, float* score, void* stream);
 
+/* ---- RNN-LM shallow fusion in the beam search above (csrc/decode_lstm.hip).  Every live beam also
+ * carries the state (h, c) of an RNN language model (model/lm/rnn_lm.py: Embedding -> LSTM stack
+ * without layer norm -> Linear), the row q[V] = log_softmax(logits(h_last)) of the next token given
+ * the beam's tokens, and the running sum lm_sum of the q it was extended by.  The cutoff_top_k classes
+ * of a beam are chosen as above (the LM does not enter the cut); the candidate of class c scores
+ * score + lp + (c != blank ? lm_weight * q[c] : 0) and sums lm_sum + (c != blank ? q[c] : 0); ranking,
+ * selection and records are unchanged.  A kept beam that emitted c steps the LM on c from its
+ * parent's LM state in the same round as the predictor, by the same tiled products; a beam that took
+ * blank copies its parent's LM state, q and lm_sum bit for bit.  lm_start_token < 0: zero LM state,
+ * q = 0 (the first token of a hypothesis carries no LM term, as RnnLm.score scores a sequence);
+ * lm_start_token = s in [0, V): the LM is first stepped on s from zero state.  With lm_weight = 0
+ * tokens, frames, out_len and score are s2t_rnnt_beam_lstm's bit for bit.
+ * S2tRnnLmDesc: layers[l].x2g_w = weight_ih_l (4H, E or H), x2g_b = bias_ih_l + bias_hh_l (4H),
+ * p2g_w = weight_hh_l (4H, H), the four norm pointers NULL; gate order i, f, g, o.
+ * Limits (else -1 / size 0, before any launch and without following a pointer): lm.V == desc.V; E, H
+ * <= S2T_RNNT_LSTM_MAX_HIDDEN and H % 4 == 0; 1 <= num_layers <= S2T_RNNT_LSTM_MAX_LAYERS;
+ * lm_start_token < V; lm_weight finite; and the limits of s2t_rnnt_beam_lstm. */
+typedef struct S2tRnnLmDesc {
+  int V, E, H, num_layers;
+  const float* emb;                /* (V, E) */
+  S2tLstmLayer layers[S2T_RNNT_LSTM_MAX_LAYERS];
+  const float *out_w, *out_b;      /* logits layer (V, H), (V) */
+} S2tRnnLmDesc;
+/* bytes of device `workspace` of s2t_rnn_lm_step for R rows; 0 outside the limits. */
+long s2t_rnn_lm_step_workspace_bytes(const S2tRnnLmDesc* lm, int R);
+/* One LM step for R rows, masked and gathered as s2t_lstm_pred_step: row r with emit[r] != 0 steps
+ * from the state of row parent[r] (NULL: r) of h_in / c_in [layers][R][H] on tokens[r] and writes its
+ * new state and q_out[r] = log_softmax(logits) [R][V]; a row with emit[r] == 0 receives the state and
+ * the q_in row of parent[r] bit for bit.  In and out buffers are either the same (then parent must be
+ * NULL) or disjoint. */
+int s2t_rnn_lm_step(const S2tRnnLmDesc* lm, int R, const int* tokens, const int* emit,
+                    const int* parent, const float* h_in, const float* c_in, const float* q_in,
+                    float* h_out, float* c_out, float* q_out, void* workspace, void* stream);
+long s2t_rnnt_beam_lstm_lm_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B,
+                                           int T, int beam_size);
+/* s2t_rnnt_beam_lstm with the LM term; lm_score [B]: the best beam's unweighted lm_sum, so that
+ * score = (RNN-T path score) + lm_weight * lm_score.  An utterance without frames: no tokens, score 0,
+ * lm_score 0.  Exactly T rounds, no host synchronisation. */
+int s2t_rnnt_beam_lstm_lm(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, const float* am,
+                          const long* lengths, int B, int T, int beam_size, int cutoff_top_k,
+                          float lm_weight, int lm_start_token, void* workspace, long* tokens,
+                          long* frames, long* out_len, float* score, float* lm_score, void* stream);
+
 /* ---- chunk-carried (streaming) RNN-T search with the LSTM predictor: the two searches above fed
  * their frames in pieces (csrc/decode_lstm.hip).  A round's launches ARE the whole-utterance calls'
  * (one text, the same arguments), and a row's arithmetic does not depend on the rows that share its

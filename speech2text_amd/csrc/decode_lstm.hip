@@ -27,6 +27,12 @@
 // host functions.  A beam chunk's records become histories and outputs by decode_records.h
 // chunk_histories, the scheme csrc/decode_stream.hip keeps written out.
 //
+// RNN-LM shallow fusion (s2t_rnnt_beam_lstm_lm): a second recurrent model rides the beam rounds.  Every
+// row also carries the LM's (h, c), q = log_softmax(logits(h_last)) [V] and the sum of the q it was
+// extended by; a candidate of class c != blank scores lm_weight * q[c] more; the rows that emitted
+// step the LM after the predictor, on the same emit / parent / token / count, by the same tiled
+// products and cell kernel (no layer norm) and a log-softmax row kernel.
+//
 // A row's arithmetic does not depend on the rows that share its launch: tiles sit at fixed row
 // positions, every (row, output) sum is taken per lane over k = lane, lane + 64, ... and folded by the
 // same butterfly, and rows beyond R read clamped addresses and are never stored.
@@ -363,6 +369,133 @@ __global__ void count_kernel(const int* emit, int R, int* count) {
   if (threadIdx.x == 0) *count = s;
 }
 
+// ------------------------------------------------------------------ one RNN-LM step, enqueued
+// The language model of model/lm/rnn_lm.py: Embedding -> LSTM stack (no layer norm, bias b_ih + b_hh
+// on the raw gates) -> Linear -> log-softmax.  Masked and gathered like the predictor's step, on the
+// same tiled products and cell kernel.
+struct LmWorkspace {
+  float *h[2], *c[2], *q[2];    // state [layers][R][H] twice, log-probabilities [R][V] twice
+  float *x, *raw, *logit;       // embedding rows [R][E], raw gates [R][4H], logits [R][V]
+  float *cq, *lm_sum;           // beam: the candidates' q [B][kMaxCand], the rows' sums [R]
+  int *tok, *counts;            // the start token [R]; the step on its own: its count
+  size_t bytes;
+};
+
+// n_state copies of (h, c, q): two for a search, none for the step on its own (the caller's buffers)
+LmWorkspace carve_lm(const S2tRnnLmDesc& d, int B, int beam, void* base, int n_state) {
+  const size_t R = (size_t)B * (beam > 0 ? beam : 1), L = d.num_layers;
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto f = [&](size_t n) {
+    char* q = p + off;
+    off += align256(4 * n);
+    return reinterpret_cast<float*>(q);
+  };
+  LmWorkspace w;
+  for (int s = 0; s < 2; ++s) {
+    w.h[s] = s < n_state ? f(L * R * d.H) : nullptr;
+    w.c[s] = s < n_state ? f(L * R * d.H) : nullptr;
+    w.q[s] = s < n_state ? f(R * d.V) : nullptr;
+  }
+  w.x = f(R * d.E);
+  w.raw = f(R * 4 * d.H);
+  w.logit = f(R * d.V);
+  w.cq = f(beam > 0 ? (size_t)B * kMaxCand : 1);
+  w.lm_sum = f(R);
+  w.tok = reinterpret_cast<int*>(f(R));
+  w.counts = reinterpret_cast<int*>(f(4));
+  w.bytes = off;
+  return w;
+}
+
+bool lm_ok(const S2tRnnLmDesc* d) {
+  return d && d->V >= 1 && d->V <= S2T_RNNT_LSTM_MAX_VOCAB && d->E >= 1 && d->E <= S2T_RNNT_LSTM_MAX_HIDDEN &&
+         d->H >= 4 && d->H <= S2T_RNNT_LSTM_MAX_HIDDEN && d->H % 4 == 0 && d->num_layers >= 1 &&
+         d->num_layers <= S2T_RNNT_LSTM_MAX_LAYERS;
+}
+
+// grid R: x[r] = emb[tokens[r]] for the rows that emit
+__global__ __launch_bounds__(kThreads) void lm_embed_kernel(const float* __restrict__ emb, int V, int E,
+                                                            const int* tokens, const int* emit,
+                                                            const int* count, float* x) {
+  if (*count == 0) return;
+  const int row = blockIdx.x;
+  if (!emit[row]) return;
+  const float* e = emb + (long)min(max(tokens[row], 0), V - 1) * E;
+  for (int i = threadIdx.x; i < E; i += kThreads) x[(long)row * E + i] = e[i];
+}
+
+struct LogSoftmaxArgs {
+  const float* logit;   // [R][V] of the rows that emit
+  int V;
+  const int* emit;
+  const int* parent;
+  const int* count;
+  int inplace;
+  const float* q_src;   // [R][V]
+  float* q_dst;
+};
+
+// grid R: q[r] = log_softmax(logit[r]) as max, then log sum exp (beam_expand_kernel's form); a row that
+// does not emit takes its parent's q as it is
+__global__ __launch_bounds__(kThreads) void lm_log_softmax_kernel(LogSoftmaxArgs a) {
+  __shared__ float scratch[kWaves];
+  if (a.inplace && *a.count == 0) return;
+  const int row = blockIdx.x, tid = threadIdx.x, V = a.V;
+  float* q = a.q_dst + (long)row * V;
+  if (!a.emit[row]) {
+    if (!a.inplace) {
+      const float* s = a.q_src + (long)(a.parent ? a.parent[row] : row) * V;
+      for (int i = tid; i < V; i += kThreads) q[i] = s[i];
+    }
+    return;
+  }
+  const float* lg = a.logit + (long)row * V;
+  float m = S2T_NEG_INF;
+  for (int c = tid; c < V; c += kThreads) m = fmaxf(m, lg[c]);
+  const float zmax = block_max(m, scratch);
+  float s = 0.f;
+  for (int c = tid; c < V; c += kThreads) s += expf(lg[c] - zmax);
+  const float lse = logf(block_sum(s, scratch));
+  for (int c = tid; c < V; c += kThreads) q[c] = (lg[c] - zmax) - lse;
+}
+
+// In place (src == dst, parent NULL) or from buffer `src` to buffer `dst`.
+void enqueue_lm_step(const S2tRnnLmDesc& d, int R, const int* tokens, const int* emit, const int* parent,
+                     const int* count, const float* h_src, const float* c_src, const float* q_src,
+                     float* h_dst, float* c_dst, float* q_dst, const LmWorkspace& w, hipStream_t st) {
+  const int inplace = h_src == h_dst;
+  const int row_tiles = (R + kTileRows - 1) / kTileRows;
+  constexpr int kOuts = kTileWaves * kTileOuts;
+  const size_t LRH = (size_t)R * d.H;
+  hipLaunchKernelGGL(lm_embed_kernel, dim3(R), dim3(kThreads), 0, st, d.emb, d.V, d.E, tokens, emit, count, w.x);
+  for (int l = 0; l < d.num_layers; ++l) {
+    const S2tLstmLayer& p = d.layers[l];
+    const float* x = l ? h_dst + (l - 1) * LRH : w.x;
+    const int K = l ? d.H : d.E;
+    TileArgs t{x, K, p.x2g_w, K, h_src + l * LRH, d.H, p.p2g_w, d.H, p.x2g_b, 4 * d.H, R, emit, parent,
+               count, w.raw, 4L * d.H};
+    hipLaunchKernelGGL(tile_linear_kernel, dim3((4 * d.H + kOuts - 1) / kOuts, row_tiles),
+                       dim3(64 * kTileWaves), 0, st, t);
+    CellArgs c{w.raw, nullptr, nullptr, nullptr, nullptr, 0.f, d.H, R, emit, parent, count,
+               inplace, h_src + l * LRH, c_src + l * LRH, h_dst + l * LRH, c_dst + l * LRH};
+    hipLaunchKernelGGL(cell_kernel, dim3(R), dim3(kThreads), sizeof(float) * 5 * d.H, st, c);
+  }
+  TileArgs t{h_dst + (d.num_layers - 1) * LRH, d.H, d.out_w, d.H, nullptr, 0, nullptr, 0, d.out_b, d.V, R,
+             emit, nullptr, count, w.logit, d.V};
+  hipLaunchKernelGGL(tile_linear_kernel, dim3((d.V + kOuts - 1) / kOuts, row_tiles), dim3(64 * kTileWaves), 0,
+                     st, t);
+  LogSoftmaxArgs a{w.logit, d.V, emit, parent, count, inplace, q_src, q_dst};
+  hipLaunchKernelGGL(lm_log_softmax_kernel, dim3(R), dim3(kThreads), 0, st, a);
+}
+
+__global__ void lm_start_kernel(int R, int token, int* tok, float* lm_sum) {
+  for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < R; r += gridDim.x * blockDim.x) {
+    tok[r] = token;
+    lm_sum[r] = 0.f;
+  }
+}
+
 // ------------------------------------------------------------------ joint
 struct JointArgs {
   const float* am;      // [B][T][V]
@@ -496,6 +629,11 @@ struct BeamArgs {
   int t, B, beam, topk, parity;
   float *cscore, *score;
   int *ccls, *blen, *nb, *rec, *emit, *token, *parent, *counts;
+  // shallow fusion (q NULL: none): the LM's log-probabilities [R][V] of the buffer the round reads,
+  // the weight, the candidates' own q [B][kMaxCand] and the rows' unweighted sums [R]
+  const float* q;
+  float lm_weight;
+  float *cq, *lm_sum;
 };
 
 __global__ void beam_init_kernel(int B, int beam, float* score, int* blen, int* nb, int* emit, int* token,
@@ -527,6 +665,7 @@ __global__ __launch_bounds__(kThreads) void beam_expand_kernel(BeamArgs a) {
   const int V = a.j.V, K = min(a.topk, V);
   const float* lg = joint_logits(a.j, row, b, a.t, a.lm + (long)row * V);
   const float base = a.score[row];
+  const float* q = a.q ? a.q + (long)row * V : nullptr;
   float pv = 0.f, zmax = 0.f, lse = 0.f;
   int pi = -1;
   for (int r = 0; r < K; ++r) {
@@ -544,7 +683,13 @@ __global__ __launch_bounds__(kThreads) void beam_expand_kernel(BeamArgs a) {
     }
     if (tid == 0) {
       const bool ok = pi < V;                              // (only a NaN input leaves a round empty)
-      a.cscore[b * kMaxCand + i * K + r] = ok ? base + ((pv - zmax) - lse) : S2T_NEG_INF;
+      float sc = base + ((pv - zmax) - lse);
+      if (q) {                                             // blank carries no LM term
+        const float qv = ok && pi != 0 ? q[pi] : 0.f;
+        sc = __fadd_rn(sc, __fmul_rn(a.lm_weight, qv));
+        a.cq[b * kMaxCand + i * K + r] = qv;
+      }
+      a.cscore[b * kMaxCand + i * K + r] = ok ? sc : S2T_NEG_INF;
       a.ccls[b * kMaxCand + i * K + r] = ok ? pi : 0;
     }
   }
@@ -554,7 +699,7 @@ __global__ __launch_bounds__(kThreads) void beam_expand_kernel(BeamArgs a) {
 // in the parent's top-k: the candidate index), keep the beam_size best as the new beams, one
 // (parent, class) record each; the rows' parent / emit / token for the predictor step.
 __global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
-  __shared__ float s_cscore[kMaxCand];
+  __shared__ float s_cscore[kMaxCand], s_lmsum[kMaxBeam];
   __shared__ int s_ccls[kMaxCand], s_pick[kMaxBeam], s_len[kMaxBeam];
   const int b = blockIdx.x, tid = threadIdx.x, BS = a.beam, row0 = b * BS;
   if (b == 0 && tid == 0) a.counts[a.parity ^ 1] = 0;
@@ -570,7 +715,10 @@ __global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
     s_cscore[tid] = a.cscore[b * kMaxCand + tid];
     s_ccls[tid] = a.ccls[b * kMaxCand + tid];
   }
-  if (tid < nb) s_len[tid] = a.blen[row0 + tid];
+  if (tid < nb) {                                          // the rows of an utterance read each other's
+    s_len[tid] = a.blen[row0 + tid];
+    if (a.q) s_lmsum[tid] = a.lm_sum[row0 + tid];
+  }
   __syncthreads();
   rank_candidates(s_cscore, nc, nnb, s_pick);
   __syncthreads();
@@ -580,6 +728,7 @@ __global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
       const int q = s_pick[tid], parent = q / K, cls = s_ccls[q];
       a.score[row] = s_cscore[q];
       a.blen[row] = s_len[parent] + (cls != 0 ? 1 : 0);
+      if (a.q) a.lm_sum[row] = cls != 0 ? s_lmsum[parent] + a.cq[b * kMaxCand + q] : s_lmsum[parent];
       a.rec[((long)b * a.j.T + a.t) * BS + tid] = pack_record(parent, cls);
       a.parent[row] = row0 + parent;
       a.emit[row] = cls != 0;
@@ -596,13 +745,15 @@ __global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
 // grid B: the best beam is position 0; its (parent, class) records traced back
 __global__ __launch_bounds__(64) void beam_trace_kernel(const long* lengths, int T, int beam, const int* rec,
                                                         const int* blen, const float* score, long* tokens,
-                                                        long* frames, long* out_len, float* out_score) {
+                                                        long* frames, long* out_len, float* out_score,
+                                                        const float* lm_sum, float* out_lm) {
   __shared__ int s_trace[kTraceFrames * kMaxBeam], s_left;
   const int b = blockIdx.x;
   const int Tb = (int)clamped_len(lengths, b, T), n = Tb ? blen[b * beam] : 0;
   if (threadIdx.x == 0) {                                  // no frames: no tokens, score 0
     out_len[b] = n;
     out_score[b] = Tb ? score[b * beam] : 0.f;
+    if (out_lm) out_lm[b] = Tb ? lm_sum[b * beam] : 0.f;
   }
   trace_best<64>(rec + (long)b * T * beam, Tb, beam, 0, n, s_trace, &s_left, tokens + (long)b * T,
                  frames + (long)b * T);
@@ -639,18 +790,24 @@ struct StateBuf {
 };
 
 // The T rounds of a beam search: frame t reads buf[t & 1] and leaves the survivors in buf[~t & 1].
+// With an LM (shallow fusion) its step follows the predictor's on the same emit / parent / token / count,
+// from its buffer cur to nxt.
 void beam_rounds(const S2tRnntLstmDesc& d, BeamArgs a, const StateBuf (&buf)[2], const Workspace& w, int T,
-                 hipStream_t st) {
+                 hipStream_t st, const S2tRnnLmDesc* lm = nullptr, const LmWorkspace* lw = nullptr) {
   const int R = a.B * a.beam;
   for (int t = 0; t < T; ++t) {
     const int cur = t & 1, nxt = cur ^ 1;
     a.t = t;
     a.parity = cur;
     a.lm = buf[cur].lm;
+    if (lm) a.q = lw->q[cur];
     hipLaunchKernelGGL(beam_expand_kernel, dim3(R), dim3(kThreads), 0, st, a);
     hipLaunchKernelGGL(beam_select_kernel, dim3(a.B), dim3(kThreads), 0, st, a);
     enqueue_pred_step(d, R, w.token, w.emit, w.parent, w.counts + cur, buf[cur].h, buf[cur].c, buf[cur].lm,
                       buf[nxt].h, buf[nxt].c, buf[nxt].lm, w, st);
+    if (lm)
+      enqueue_lm_step(*lm, R, w.token, w.emit, w.parent, w.counts + cur, lw->h[cur], lw->c[cur], lw->q[cur],
+                      lw->h[nxt], lw->c[nxt], lw->q[nxt], *lw, st);
   }
 }
 
@@ -907,11 +1064,81 @@ int s2t_rnnt_beam_lstm(const S2tRnntLstmDesc* desc, const float* am, const long*
   enqueue_pred_step(d, R, w.token, w.emit, nullptr, w.counts + 2, w.h[0], w.c[0], w.lm[0], w.h[0], w.c[0],
                     w.lm[0], w, st);
   BeamArgs a{joint_args(d, am, T, w), lengths, w.lm[0], 0, B, beam_size, cutoff_top_k, 0, w.cscore, w.score,
-             w.ccls, w.blen, w.nb, w.rec, w.emit, w.token, w.parent, w.counts};
+             w.ccls, w.blen, w.nb, w.rec, w.emit, w.token, w.parent, w.counts, nullptr, 0.f, nullptr, nullptr};
   const StateBuf buf[2] = {{w.h[0], w.c[0], w.lm[0]}, {w.h[1], w.c[1], w.lm[1]}};
   beam_rounds(d, a, buf, w, T, st);
   hipLaunchKernelGGL(beam_trace_kernel, dim3(B), dim3(64), 0, st, lengths, T, beam_size, w.rec, w.blen,
-                     w.score, tokens, frames, out_len, score);
+                     w.score, tokens, frames, out_len, score, (const float*)nullptr, (float*)nullptr);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+long s2t_rnn_lm_step_workspace_bytes(const S2tRnnLmDesc* lm, int R) {
+  if (!lm_ok(lm) || R <= 0) return 0;
+  return (long)carve_lm(*lm, R, 0, nullptr, 0).bytes;
+}
+
+int s2t_rnn_lm_step(const S2tRnnLmDesc* lm, int R, const int* tokens, const int* emit, const int* parent,
+                    const float* h_in, const float* c_in, const float* q_in, float* h_out, float* c_out,
+                    float* q_out, void* workspace, void* stream) {
+  if (R <= 0) return 0;
+  if (!lm_ok(lm) || !workspace) return -1;
+  const bool same = h_in == h_out;
+  if (same != (c_in == c_out) || same != (q_in == q_out) || (same && parent)) return -1;
+  const LmWorkspace w = carve_lm(*lm, R, 0, workspace, 0);
+  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, emit, R, w.counts);
+  enqueue_lm_step(*lm, R, tokens, emit, parent, w.counts, h_in, c_in, q_in, h_out, c_out, q_out, w,
+                  (hipStream_t)stream);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+long s2t_rnnt_beam_lstm_lm_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B, int T,
+                                           int beam_size) {
+  if (!desc_ok(desc) || !lm_ok(lm) || lm->V != desc->V || B <= 0 || T < 0 || beam_size < 1 ||
+      beam_size > kMaxBeam)
+    return 0;
+  return (long)(carve(*desc, B, T, beam_size, nullptr).bytes + carve_lm(*lm, B, beam_size, nullptr, 2).bytes);
+}
+
+int s2t_rnnt_beam_lstm_lm(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, const float* am,
+                          const long* lengths, int B, int T, int beam_size, int cutoff_top_k, float lm_weight,
+                          int lm_start_token, void* workspace, long* tokens, long* frames, long* out_len,
+                          float* score, float* lm_score, void* stream) {
+  if (B <= 0) return 0;
+  if (!desc_ok(desc) || !lm_ok(lm) || lm->V != desc->V || T <= 0 || beam_size < 1 || beam_size > kMaxBeam ||
+      cutoff_top_k < 1 || (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam ||
+      lm_start_token >= desc->V || !__builtin_isfinite(lm_weight) || !workspace)
+    return -1;
+  const S2tRnntLstmDesc& d = *desc;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = B * beam_size;
+  const Workspace w = carve(d, B, T, beam_size, workspace);
+  const LmWorkspace lw = carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 2);
+  const size_t state = sizeof(float) * (size_t)d.num_layers * R * d.H;
+  const size_t lm_state = sizeof(float) * (size_t)lm->num_layers * R * lm->H;
+  hipError_t e = hipMemsetAsync(w.h[0], 0, state, st);
+  if (e == hipSuccess) e = hipMemsetAsync(w.c[0], 0, state, st);
+  if (e == hipSuccess) e = hipMemsetAsync(lw.h[0], 0, lm_state, st);
+  if (e == hipSuccess) e = hipMemsetAsync(lw.c[0], 0, lm_state, st);
+  if (e == hipSuccess) e = hipMemsetAsync(lw.q[0], 0, sizeof(float) * (size_t)R * d.V, st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(beam_init_kernel, dim3(1), dim3(kThreads), 0, st, B, beam_size, w.score, w.blen, w.nb,
+                     w.emit, w.token, w.counts);
+  hipLaunchKernelGGL(lm_start_kernel, dim3((R + kThreads - 1) / kThreads), dim3(kThreads), 0, st, R,
+                     lm_start_token, lw.tok, lw.lm_sum);
+  enqueue_pred_step(d, R, w.token, w.emit, nullptr, w.counts + 2, w.h[0], w.c[0], w.lm[0], w.h[0], w.c[0],
+                    w.lm[0], w, st);
+  if (lm_start_token >= 0)                                 // the LM's first step, as the predictor's on blank
+    enqueue_lm_step(*lm, R, lw.tok, w.emit, nullptr, w.counts + 2, lw.h[0], lw.c[0], lw.q[0], lw.h[0], lw.c[0],
+                    lw.q[0], lw, st);
+  BeamArgs a{joint_args(d, am, T, w), lengths, w.lm[0], 0, B, beam_size, cutoff_top_k, 0, w.cscore, w.score,
+             w.ccls, w.blen, w.nb, w.rec, w.emit, w.token, w.parent, w.counts, lw.q[0], lm_weight, lw.cq,
+             lw.lm_sum};
+  const StateBuf buf[2] = {{w.h[0], w.c[0], w.lm[0]}, {w.h[1], w.c[1], w.lm[1]}};
+  beam_rounds(d, a, buf, w, T, st, lm, &lw);
+  hipLaunchKernelGGL(beam_trace_kernel, dim3(B), dim3(64), 0, st, lengths, T, beam_size, w.rec, w.blen,
+                     w.score, tokens, frames, out_len, score, (const float*)lw.lm_sum, lm_score);
   S2T_CHECK_LAUNCH();
   return 0;
 }
@@ -982,7 +1209,7 @@ int s2t_rnnt_beam_lstm_chunk(const S2tRnntLstmDesc* desc, const float* am, const
   const Workspace w = carve(d, B, Tc, beam_size, workspace, 1);
   hipLaunchKernelGGL(beam_chunk_init_kernel, dim3(1), dim3(64), 0, st, w.counts, R);
   BeamArgs a{joint_args(d, am, Tc, w), chunk_len, s.lm, 0, B, beam_size, cutoff_top_k, 0, w.cscore, s.score,
-             w.ccls, s.blen, s.nb, w.rec, w.emit, w.token, w.parent, w.counts};
+             w.ccls, s.blen, s.nb, w.rec, w.emit, w.token, w.parent, w.counts, nullptr, 0.f, nullptr, nullptr};
   const StateBuf buf[2] = {{s.h, s.c, s.lm}, {w.h[0], w.c[0], w.lm[0]}};
   beam_rounds(d, a, buf, w, Tc, st);
   if (Tc & 1) {                                            // the live copy goes home

@@ -15,8 +15,10 @@ step for the rows that emitted, no host synchronisation per move.  Both families
 across chunks of a stream (RnntStreamingSearch, csrc/decode_stream.hip; RnntLstmStreamingSearch,
 csrc/decode_lstm.hip; rnnt_streaming_search picks the class).  Other predictor / joiner
 combinations (the stateless predictor with an out-projection joiner, foreign classes, shapes a
-kernel refuses) keep the module-by-module loop.  The lexicon CTC beam decoder (it wraps
-flashlight) and the CIF decoder are not here."""
+kernel refuses) keep the module-by-module loop.  RnntBeamDecoding takes an RNN language model
+for shallow fusion (`lm=`, `lm_weight=`): with the LSTM predictor the LM is stepped inside the
+lockstep device search (s2t_rnnt_beam_lstm_lm), everything else runs `_module_loop_lm`.  The
+lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are not here."""
 import abc
 from enum import Enum, unique
 from typing import List
@@ -204,6 +206,70 @@ def rnnt_beam_lstm_tokens_from_am(am, lengths, predictor, joiner, beam_size=4, c
     return tokens, frames, out_len, score
 
 
+def rnn_lm_desc(lm):
+    """-> (S2tRnnLmDesc of an RnnLm's fp32 device parameters, the tensors it points to: keep them
+    alive while the descriptor is in use).  A layer's two biases are summed once into a kept tensor."""
+    import ctypes
+    keep = []
+
+    def a(t):
+        t = t.detach().contiguous().float()
+        keep.append(t)
+        return N.fp(t)
+
+    st = lm._rnn_layer
+    if st.num_layers > N.const("S2T_RNNT_LSTM_MAX_LAYERS"):
+        return None, keep
+    d = N.struct("S2tRnnLmDesc")()
+    d.V, d.E, d.H, d.num_layers = lm._num_symbols, st.input_size, st.hidden_size, st.num_layers
+    d.emb = a(lm._embedding.weight)
+    for k in range(st.num_layers):
+        L = d.layers[k]
+        L.x2g_w, L.p2g_w = a(getattr(st, f"weight_ih_l{k}")), a(getattr(st, f"weight_hh_l{k}"))
+        L.x2g_b = a(getattr(st, f"bias_ih_l{k}").detach().float() + getattr(st, f"bias_hh_l{k}").detach().float())
+    d.out_w, d.out_b = a(lm._logits_layer.weight), a(lm._logits_layer.bias)
+    keep.append(d)
+    return ctypes.byref(d), keep
+
+
+def rnnt_beam_lstm_lm_tokens_from_am(am, lengths, predictor, joiner, lm, lm_weight, beam_size=4, cutoff_top_k=4,
+                                     lm_start_token=None):
+    """rnnt_beam_lstm_tokens_from_am with RNN-LM shallow fusion: a candidate of class c != blank scores
+    lm_weight * log p_lm(c | the beam's tokens) more.  lm_start_token None: the LM starts from zero
+    state and the first token carries no LM term (RnnLm.score's convention); a token: the LM is first
+    stepped on it.  -> (tokens, frames, out_len, score, lm_score (B) fp32: the best beam's unweighted
+    LM sum), or None when the kernels do not take the shape.  HIP: decode_lstm.hip."""
+    if not am.is_cuda:
+        raise RuntimeError("the device RNN-T beam search runs on the GPU only")
+    am = am.contiguous().float()
+    B, T, V = am.shape
+    dev = am.device
+    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+    out = _beam_outputs(B, T, dev) + (torch.zeros((B,), dtype=torch.float32, device=dev),)
+    if B == 0 or T == 0:
+        return out
+    desc, keep = rnnt_lstm_desc(predictor, joiner)
+    lm_desc, lm_keep = rnn_lm_desc(lm)
+    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
+    start = -1 if lm_start_token is None else int(lm_start_token)
+    if lm_start_token is not None and start < 0:
+        raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
+    if desc is None or lm_desc is None or not 1 <= beam_size <= N.const("S2T_RNNT_LSTM_MAX_BEAM"):
+        return None
+    n = N.lib().s2t_rnnt_beam_lstm_lm_workspace_bytes(desc, lm_desc, B, T, beam_size)
+    if n <= 0:
+        return None
+    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+    tokens, frames, out_len, score, lm_score = out
+    rc = N.lib().s2t_rnnt_beam_lstm_lm(desc, lm_desc, N.fp(am), N.lp(lengths), B, T, beam_size, cutoff_top_k,
+                                       float(lm_weight), start, N.ptr(ws), N.lp(tokens), N.lp(frames),
+                                       N.lp(out_len), N.fp(score), N.fp(lm_score), N.stream())
+    if rc == -1:
+        return None
+    N.check(rc, "s2t_rnnt_beam_lstm_lm")
+    return out
+
+
 def _am_per_utterance(joiner, hidden_states, inputs_length):
     """am (B,T,V) = enc_proj(encoder_out), formed utterance by utterance on the frames an utterance
     has: the product decode() forms for the same utterance alone, so that a batched search and a
@@ -354,14 +420,28 @@ class RnntBeamDecoding(DecodingMethod):
     `cutoff_top_k` best classes of every beam are expanded, the `beam_size` best candidates
     survive, equal hypotheses are not merged.  The orders the reference leaves to its library are
     fixed: top-k by (log-probability descending, class ascending), candidates by (score
-    descending, parent beam position ascending, rank in the parent's top-k ascending)."""
+    descending, parent beam position ascending, rank in the parent's top-k ascending).
 
-    def __init__(self, tokenizer, predictor, joiner, beam_size=4, cutoff_top_k=4) -> None:
+    With `lm` (an RnnLm, or anything with init_states / score_step) the search is shallow-fused: the
+    candidate of class c != blank scores `lm_weight * log p_lm(c | the beam's tokens)` more, the cut
+    to `cutoff_top_k` classes is still the RNN-T's own, blank carries no LM term.  `lm_start_token`
+    None: the LM starts from zero state and a hypothesis' first token carries no LM term (how
+    RnnLm.score scores a sequence); a token id: the LM is first stepped on it.  The LSTM predictor
+    runs the fused device search (csrc/decode_lstm.hip); everything else `_module_loop_lm`.
+    `beam_tokens` then returns a fifth tensor, the best beam's unweighted LM sum."""
+
+    def __init__(self, tokenizer, predictor, joiner, beam_size=4, cutoff_top_k=4, lm=None, lm_weight=0.0,
+                 lm_start_token=None) -> None:
         self._tokenizer = tokenizer
         self._predictor = predictor
         self._joiner = joiner
         self._beam_size = beam_size
         self._cutoff_top_k = cutoff_top_k
+        self._lm = lm
+        self._lm_weight = float(lm_weight)
+        self._lm_start_token = None if lm_start_token is None else int(lm_start_token)
+        if self._lm_start_token is not None and self._lm_start_token < 0:
+            raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
         assert hasattr(self._predictor, "streaming_step") and hasattr(self._joiner, "streaming_step"), \
             "Predictor and Joiner should impl streaming_step for decoding."
 
@@ -404,11 +484,66 @@ class RnntBeamDecoding(DecodingMethod):
             beams = new_beams
         return list(beams[0][0]), list(beams[0][1]), float(scores[0])
 
+    def _module_loop_lm(self, hidden_states):
+        """_module_loop with the LM term -> (tokens, frames, score, lm_score) of the best beam, over
+        predictor.streaming_step, joiner.streaming_step and lm.score_step.  Scores are accumulated
+        on the inputs' device in fp32 (fp64 where the modules compute in it) as (beam score +
+        log-probability) + lm_weight * q, the order of the device search."""
+        dev = hidden_states.device
+        lm, weight = self._lm, self._lm_weight
+        blk = torch.zeros((1, 1), dtype=torch.int64, device=dev)
+        pred_out, pred_state = self._predictor.streaming_step(blk, self._predictor.init_state())
+        lm_state, q = lm.init_states(1), None              # q None: all zeros (no start token)
+        if self._lm_start_token is not None:
+            q, lm_state = lm.score_step(torch.full((1,), self._lm_start_token, dtype=torch.int64, device=dev),
+                                        lm_state)
+        beams = [((), (), pred_state, pred_out, lm_state, q)]   # (tokens, frames, state, pred_out, LM state, q (1,V))
+        scores = lm_sums = None
+        for t in range(hidden_states.shape[1]):
+            log_probs = self._joiner.streaming_step(hidden_states[:, t:t + 1, :],
+                                                    torch.cat([b[3] for b in beams], dim=0))
+            log_probs = log_probs.to(torch.promote_types(log_probs.dtype, torch.float32))
+            if scores is None:
+                scores, lm_sums = log_probs.new_zeros(1), log_probs.new_zeros(1)
+            k = min(int(self._cutoff_top_k), log_probs.shape[-1])
+            vals, cls = torch.sort(log_probs, dim=-1, descending=True, stable=True)
+            vals, cls = vals[:, :k], cls[:, :k]
+            qs = torch.cat([torch.zeros_like(log_probs[:1]) if b[5] is None else b[5].to(log_probs.dtype)
+                            for b in beams], dim=0)
+            qv = torch.where(cls != 0, qs.gather(1, cls), torch.zeros_like(vals))   # blank: no LM term
+            cand = ((scores.unsqueeze(1) + vals) + weight * qv).flatten()   # index = parent * k + rank
+            cand_lm = (lm_sums.unsqueeze(1) + qv).flatten()
+            scores, pick = torch.sort(cand, descending=True, stable=True)
+            scores, pick = scores[:self._beam_size], pick[:self._beam_size]
+            lm_sums = cand_lm[pick]
+            new_beams = []
+            for p, c in zip(pick.tolist(), cls.flatten()[pick].tolist()):
+                tokens, frames, state, out, lm_state, q = beams[p // k]
+                if c != 0:
+                    tok = torch.full((1, 1), c, dtype=torch.int64, device=dev)
+                    out, state = self._predictor.streaming_step(tok, state)
+                    q, lm_state = lm.score_step(tok.reshape(1), lm_state)
+                    tokens, frames = tokens + (c,), frames + (t,)
+                new_beams.append((tokens, frames, state, out, lm_state, q))
+            beams = new_beams
+        if scores is None:
+            return [], [], 0.0, 0.0
+        return list(beams[0][0]), list(beams[0][1]), float(scores[0]), float(lm_sums[0])
+
+    def _lm_to(self, dev):
+        """The LM follows the inputs to their device on first use (the task does not own it)."""
+        if isinstance(self._lm, torch.nn.Module):
+            p = next(self._lm.parameters(), None)
+            if p is not None and p.device != dev:
+                self._lm.to(dev)
+
     @torch.no_grad()
     def beam_tokens(self, hidden_states, inputs_length, fused=True):
         """(B,T,D) encoder output -> (tokens (B,T), frames (B,T), out_len (B), score (B)) of the
-        best beam per utterance.  The fused device search where the modules allow it (and `fused`
-        is left on), else the module loop per utterance."""
+        best beam per utterance, and with an LM its lm_score (B).  The fused device search where the
+        modules allow it (and `fused` is left on), else the module loop per utterance."""
+        if self._lm is not None:
+            return self._beam_tokens_lm(hidden_states, inputs_length, fused)
         if fused and self._fusable() and hidden_states.is_cuda:
             am = self._joiner._enc_proj(hidden_states)                # (B,T,V), one GEMM
             out = rnnt_beam_tokens_from_am(am, inputs_length, self._predictor, self._joiner,
@@ -435,10 +570,35 @@ class RnntBeamDecoding(DecodingMethod):
         dev = hidden_states.device
         return tokens.to(dev), frames.to(dev), out_len.to(dev), score.to(dev)
 
+    def _beam_tokens_lm(self, hidden_states, inputs_length, fused):
+        from speech2text_amd.model.lm.rnn_lm import RnnLm
+        dev = hidden_states.device
+        self._lm_to(dev)
+        if fused and self._lstm_search() and isinstance(self._lm, RnnLm) and hidden_states.is_cuda:
+            am, lens = _am_per_utterance(self._joiner, hidden_states, inputs_length)
+            out = rnnt_beam_lstm_lm_tokens_from_am(am, lens, self._predictor, self._joiner, self._lm,
+                                                   self._lm_weight, self._beam_size, self._cutoff_top_k,
+                                                   self._lm_start_token)
+            if out is not None:
+                return out
+        B, T = hidden_states.shape[0], hidden_states.shape[1]
+        tokens = torch.zeros((B, T), dtype=torch.int64)
+        frames = torch.zeros((B, T), dtype=torch.int64)
+        out_len = torch.zeros((B,), dtype=torch.int64)
+        score = torch.zeros((B,), dtype=torch.float32)
+        lm_score = torch.zeros((B,), dtype=torch.float32)
+        for b in range(B):
+            n = max(0, min(int(inputs_length[b]), T))
+            tok, frm, score[b], lm_score[b] = self._module_loop_lm(hidden_states[b:b + 1, :n, :])
+            out_len[b] = len(tok)
+            tokens[b, :len(tok)] = torch.tensor(tok, dtype=torch.int64)
+            frames[b, :len(frm)] = torch.tensor(frm, dtype=torch.int64)
+        return tokens.to(dev), frames.to(dev), out_len.to(dev), score.to(dev), lm_score.to(dev)
+
     @torch.no_grad()
     def decode_batch(self, hidden_states, inputs_length):
-        tokens, _, out_len, _ = self.beam_tokens(hidden_states, inputs_length)
-        return _to_texts(tokens, out_len, self._tokenizer)
+        out = self.beam_tokens(hidden_states, inputs_length)
+        return _to_texts(out[0], out[2], self._tokenizer)
 
     @torch.no_grad()
     def decode(self, hidden_states: torch.Tensor) -> str:

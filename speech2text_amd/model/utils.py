@@ -1,7 +1,7 @@
 """Metrics for evaluation (mirror of the reference's model/utils.py:23-136): word / character
 error rate over decoded texts and the AsrMetric callable the tasks' validation_step uses."""
 import dataclasses
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -39,16 +39,20 @@ def word_error_rate(hypotheses: List[str], references: List[str], show_on_screen
 class AsrMetricConfig:
     """decode_method: "ctc_greedy_search" / "rnnt_greedy_search" as in the reference, and
     "rnnt_beam_search" (a name of this project: the reference's AsrMetric knows the greedy
-    decoders only), which scores with RnntBeamDecoding(beam_size, cutoff_top_k)."""
+    decoders only), which scores with RnntBeamDecoding(beam_size, cutoff_top_k); given a language
+    model (AsrMetric's `lm`) it is shallow-fused with lm_weight / lm_start_token."""
     decode_method: str = "ctc_greedy_search"
     max_token_step: int = 5
     beam_size: int = 4
     cutoff_top_k: int = 4
+    lm_weight: float = 0.0
+    lm_start_token: Optional[int] = None
 
 
 class AsrMetric(object):
-    def __init__(self, tokenizer, config: AsrMetricConfig, predictor=None, joiner=None):
+    def __init__(self, tokenizer, config: AsrMetricConfig, predictor=None, joiner=None, lm=None):
         self._tokenizer = tokenizer
+        self._lm = lm                  # held here, not by the task: no parameter of the task
         if config.decode_method == "ctc_greedy_search":
             self._decode_sess = CtcGreedyDecoding(tokenizer=tokenizer)
         elif config.decode_method == "rnnt_greedy_search":
@@ -58,7 +62,9 @@ class AsrMetric(object):
         elif config.decode_method == "rnnt_beam_search":
             self._decode_sess = RnntBeamDecoding(tokenizer=tokenizer, predictor=predictor,
                                                  joiner=joiner, beam_size=config.beam_size,
-                                                 cutoff_top_k=config.cutoff_top_k)
+                                                 cutoff_top_k=config.cutoff_top_k, lm=lm,
+                                                 lm_weight=config.lm_weight,
+                                                 lm_start_token=config.lm_start_token)
         else:
             raise NotImplementedError(config.decode_method)
 

@@ -29,6 +29,12 @@ class TaskBase(nn.Module):
             from speech2text_amd.dataset.utils import TokenizerSetup
             self._tokenizer = TokenizerSetup(config["tokenizer"])
         self._metric_config = config.get("metric")
+        self._metric_lm_config = None
+        if self._metric_config is not None and "lm" in self._metric_config:
+            # metric: {lm: {config: {<RnnLmConfig>}, checkpoint: <path|null>}}: the language model the
+            # RNN-T beam search is shallow-fused with; the rest is AsrMetricConfig's
+            self._metric_config = dict(self._metric_config)
+            self._metric_lm_config = self._metric_config.pop("lm")
         self._metric = None
         if "feat_type" in self._dataset_config:
             self._frontend = self._get_frontend(copy.deepcopy(config["dataset"]))
@@ -70,7 +76,25 @@ class TaskBase(nn.Module):
             return None
         from speech2text_amd.model.utils import AsrMetric, AsrMetricConfig
         return AsrMetric(tokenizer=self._tokenizer, config=AsrMetricConfig(**self._metric_config),
-                         predictor=predictor, joiner=joiner)
+                         predictor=predictor, joiner=joiner, lm=self._metric_lm())
+
+    def _metric_lm(self):
+        """The frozen RnnLm of `metric.lm`, or None: built from `lm.config`, loaded from the `_nnlm.*`
+        keys of a checkpoint the NNLM task wrote when `lm.checkpoint` names one.  The caller hands it
+        to the metric object; it is never an attribute of the task, so the task's state_dict(),
+        parameters() and optimizer groups do not know it.  It follows the inputs to their device on
+        first use (model/decoding.py)."""
+        if not self._metric_lm_config:
+            return None
+        from speech2text_amd.model.lm.rnn_lm import RnnLm, RnnLmConfig
+        with torch.random.fork_rng(devices=[]):            # its init draws nothing from the task's stream
+            lm = RnnLm(config=RnnLmConfig(**(self._metric_lm_config.get("config") or {})))
+        path = self._metric_lm_config.get("checkpoint")
+        if path:
+            sd = torch.load(path, map_location="cpu", weights_only=False)["state_dict"]
+            lm.load_state_dict({k[len("_nnlm."):]: v for k, v in sd.items() if k.startswith("_nnlm.")},
+                               strict=True)
+        return lm.eval().requires_grad_(False)
 
     def _wer(self, hidden_states, lengths, labels):
         if self._metric is None:

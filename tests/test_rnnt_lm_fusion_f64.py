@@ -1,0 +1,209 @@
+"""CPU: the yardstick of the RNN-T beam search with RNN-LM shallow fusion (csrc/decode_lstm.hip
+s2t_rnnt_beam_lstm_lm) and the Python surface around it.
+
+tests/rnnt_lm_fusion_f64.py is rnnt_lstm_search_f64.beam_search plus one term: with lm_weight 0 it must
+return that search's floats; its lm_score must be rnn_lm_f64.score_ref of the hypothesis and its score
+the plain RNN-T score of the path plus lm_weight x lm_score.  Then the conditions every case of
+tests/rnnt_lm_fusion_cases.py must meet, with no exclusions (margins, float32 on the same path, the
+LM changes at least one hypothesis where beam > 1), the recorded float32 costs to a factor 4, the
+project's module loop over plain stand-ins, and a task's state_dict / parameters with and without
+`metric.lm`.
+"""
+import copy
+
+import pytest
+import torch
+
+import rnnt_lm_fusion_cases as L
+import rnnt_lm_fusion_f64 as F
+import rnnt_lstm_search_cases as C
+import rnnt_lstm_search_f64 as S
+
+
+class _Ids:
+    def decode(self, t):
+        return [int(x) for x in t]
+
+
+# ------------------------------------------------------------------ 1. lm_weight 0 is the un-fused search
+@pytest.mark.parametrize("name", list(C.BEAM_CASES))
+def test_weight_zero_is_the_unfused_search(name):
+    c = C.BEAM_CASES[name]
+    V = C.MODELS[c["model"]]["V"]
+    lm = {63: "lm20", 11: "lm20_v11", 65: "lm48", 128: "lm64"}[V]
+    w, act, am, lens = C.make(name)
+    w, sd = S.cast(w, torch.float64), L.cast(L.lm_weights(lm, 7), torch.float64)
+    ref = C.reference(name)
+    for b in range(c["B"]):
+        a = am[b, :C.clamp(lens[b], c["T"])]
+        for start in (None, V - 1):
+            tokens, score, lm_score, frames, margin = F.beam_search_lm(a, w, act, c["beam"], c["topk"], sd, 0.0, start)
+            assert (tokens, score, frames, margin) == ref[b], (name, b, start)     # equal floats
+            assert lm_score == pytest.approx(F.lm_score_ref(sd, tokens, start), abs=1e-9)
+
+
+# ------------------------------------------------------------------ 2. what lm_score and score are
+@pytest.mark.parametrize("name", list(L.CASES))
+def test_lm_score_and_score_identities(name):
+    c = L.CASES[name]
+    w, act, am, lens, sd = L.make(name)
+    w, sd = S.cast(w, torch.float64), L.cast(sd, torch.float64)
+    for b, (tokens, score, lm_score, frames, _) in enumerate(L.reference(name)):
+        assert lm_score == pytest.approx(F.lm_score_ref(sd, tokens, c["start"]), abs=1e-9), (name, b)
+        path = F.path_score(am[b, :C.clamp(lens[b], am.shape[1])], w, act, tokens, frames)
+        assert score - c["weight"] * lm_score == pytest.approx(path, abs=1e-9), (name, b)
+        assert len(tokens) == len(frames) and frames == sorted(set(frames))
+
+
+def test_start_token_is_a_step_from_zero_state():
+    """With a start token s the first token is scored given [s]; without, it carries no LM term."""
+    sd = L.cast(L.lm_weights("lm20", 3), torch.float64)
+    assert F.lm_score_ref(sd, [5], None) == 0.0 and F.lm_score_ref(sd, [], 62) == 0.0
+    q, _ = F.lm_start(sd, 62)
+    assert F.lm_score_ref(sd, [5], 62) == pytest.approx(float(q[5]), abs=1e-12)
+    q0, st = F.lm_start(sd, None)
+    assert float(q0.abs().max()) == 0.0 and float(st[0].abs().max()) == 0.0
+
+
+# ------------------------------------------------------------------ 3. the cases' conditions and costs
+@pytest.mark.parametrize("name", list(L.CASES))
+def test_every_utterance_of_the_case_is_decided(name):
+    c = L.CASES[name]
+    ref, f32, plain = L.reference(name), L.evaluate(name, torch.float32), L.unfused(name)
+    _, _, am, lens, _ = L.make(name)
+    assert len(ref) == am.shape[0]
+    for b, (r, s) in enumerate(zip(ref, f32)):
+        print(f"{name} utterance {b}: length {C.clamp(lens[b], am.shape[1])} tokens {r[0]} (un-fused {plain[b][0]}) "
+              f"lm_score {r[2]:.4f} margin {r[4]:.3e}")
+        assert r[4] >= S.MARGIN, f"{name} utterance {b}: float64 decides a node by {r[4]:.2e} only"
+        assert s[0] == r[0] and s[3] == r[3], f"{name} utterance {b}: float32 walks another path"
+    assert sum(len(r[0]) for r in ref) > 0
+    changed = [b for b, (r, p) in enumerate(zip(ref, plain)) if r[0] != p[0]]
+    print(f"{name}: the LM changes utterances {changed}")
+    if c["beam"] > 1:
+        assert changed, f"{name}: a search that dropped the LM term would pass"
+    else:
+        assert not changed and any(r[2] != 0.0 for r in ref)
+    if am.shape[0] > 1:
+        assert int(lens[1]) == 0 and ref[1][:4] == ([], 0.0, 0.0, [])
+    if am.shape[0] > 2:
+        assert int(lens[2]) > am.shape[1]
+
+
+def test_cases_cover_what_the_issue_names():
+    ms = {c["lm"]: L.LM_MODELS[c["lm"]] for c in L.CASES.values()}
+    assert set(ms) == set(L.LM_MODELS)
+    assert {(m["H"], m["L"], m["V"]) for m in ms.values()} == {(20, 1, 63), (20, 1, 11), (48, 2, 65), (64, 3, 128),
+                                                              (64, 3, 65), (512, 3, 128)}
+    assert {c["weight"] for c in L.CASES.values()} == {0.3, 0.5}
+    starts = [(c["start"], L.LM_MODELS[c["lm"]]["V"]) for c in L.CASES.values() if c["start"] is not None]
+    assert starts == [(127, 128)]
+    assert any(c["beam"] == c["topk"] == 1 for c in L.CASES.values())
+    Bs = {C.CASES[c["base"]]["B"] for c in L.CASES.values()}
+    assert Bs >= {17, 33} and C.CASES[L.CASES[L.B33]["base"]]["B"] == 33
+    assert set(L.CASES) == set(L.FUSED_COST) and set(L.STEP_MODELS) == set(L.LM_STEP_COST)
+    for lm, pred in L.STEP_MODELS.items():
+        assert L.LM_MODELS[lm]["V"] == C.MODELS[pred]["V"]
+
+
+@pytest.mark.parametrize("model", list(L.STEP_MODELS))
+def test_fp32_cost_of_the_lm_step(model):
+    fig = L.step_fp32_figure(model)
+    print(f"fp32 cost of five chained LM steps, {model}: {fig:.3e}")
+    rec = L.LM_STEP_COST[model]
+    assert fig <= 4 * rec and rec <= 4 * fig, (fig, rec)
+
+
+@pytest.mark.parametrize("name", list(L.CASES))
+def test_fp32_cost_of_the_fused_scores(name):
+    fig = L.fused_fp32_figure(name)
+    print(f"fp32 cost of score / lm_score, {name}: {fig:.3e}")
+    rec = L.FUSED_COST[name]
+    assert fig <= 4 * rec and rec <= 4 * fig, (fig, rec)
+
+
+# ------------------------------------------------------------------ 4. the module loop over stand-ins
+@pytest.mark.parametrize("name", ["f_h20_beam1_k1", "f_h48_b17_beam4", "f_h64_beam16_k4_start"])
+def test_module_loop_lm_on_plain_torch_stand_ins(name):
+    from speech2text_amd.model.decoding import RnntBeamDecoding
+    c = L.CASES[name]
+    w, act, am, lens, sd = L.make(name)
+    w, sd = S.cast(w, torch.float64), L.cast(sd, torch.float64)
+    dec = RnntBeamDecoding(_Ids(), S.PlainPredictor(w), S.PlainJoiner(w, act), beam_size=c["beam"],
+                           cutoff_top_k=c["topk"], lm=F.PlainLm(sd), lm_weight=c["weight"], lm_start_token=c["start"])
+    assert not dec._fusable() and not dec._lstm_search()
+    ref = L.reference(name)
+    tokens, frames, out_len, score, lm_score = dec.beam_tokens(am.double(), lens)
+    for b, (tok, sc, lms, frm, _) in enumerate(ref):
+        n = int(out_len[b])
+        assert tokens[b, :n].tolist() == tok and frames[b, :n].tolist() == frm, (name, b)
+        assert float(score[b]) == pytest.approx(sc, rel=1e-6, abs=1e-6)
+        assert float(lm_score[b]) == pytest.approx(lms, rel=1e-6, abs=1e-6)
+        a = am[b:b + 1, :C.clamp(lens[b], am.shape[1])].double()
+        got = dec._module_loop_lm(a)                       # float64 throughout: the restatement's floats
+        assert got[0] == tok and got[1] == frm
+        assert got[2] == pytest.approx(sc, abs=1e-9) and got[3] == pytest.approx(lms, abs=1e-9)
+    assert dec.decode_batch(am.double(), lens) == [r[0] for r in ref]
+
+
+def test_without_an_lm_the_class_is_what_it_was():
+    from speech2text_amd.model.decoding import RnntBeamDecoding
+    from speech2text_amd.model.utils import AsrMetricConfig
+    w, act, am, lens = C.make("b_h20_beam1_k1")
+    dec = RnntBeamDecoding(_Ids(), S.PlainPredictor(w), S.PlainJoiner(w, act), beam_size=2, cutoff_top_k=2)
+    assert dec._lm is None and len(dec.beam_tokens(am, lens)) == 4
+    assert (AsrMetricConfig().lm_weight, AsrMetricConfig().lm_start_token) == (0.0, None)
+    with pytest.raises(ValueError):
+        RnntBeamDecoding(_Ids(), S.PlainPredictor(w), S.PlainJoiner(w, act), lm=object(), lm_start_token=-2)
+
+
+# ------------------------------------------------------------------ 5. the task does not own the LM
+def _rnnt_cfg():
+    from test_gpu_conformer_tasks import _CONF, _base_cfg
+    from test_gpu_validation import _TOK, _V
+    cfg = _base_cfg()
+    cfg.update({"task": {"type": "Rnnt"}, "tokenizer": _TOK, "encoder": _CONF,
+                "decoder": {"model": "Identity", "config": {"dummy": -1}},
+                "predictor": {"model": "Lstm", "config": {"num_symbols": _V, "output_dim": 64,
+                                                          "symbol_embedding_dim": 32, "num_lstm_layers": 2,
+                                                          "lstm_hidden_dim": 48, "lstm_layer_norm": True,
+                                                          "lstm_layer_norm_epsilon": 1e-3, "lstm_dropout": 0.1}},
+                "joiner": {"input_dim": 64, "output_dim": _V, "inner_dim": 48, "activation": "tanh",
+                           "prune_range": -1},
+                "metric": {"decode_method": "rnnt_beam_search", "beam_size": 3, "cutoff_top_k": 3},
+                "loss": {"model": "Rnnt", "config": {"blank_label": 0, "reduction": "mean"}}})
+    return cfg, _V
+
+
+def test_task_with_metric_lm_has_the_same_state_and_parameters(tmp_path):
+    from speech2text_amd.build_task import TaskFactory
+    from speech2text_amd.model.lm.rnn_lm import RnnLm, RnnLmConfig
+    cfg, V = _rnnt_cfg()
+    lm_cfg = {"num_symbols": V, "symbol_embedding_dim": 16, "num_rnn_layer": 2}
+    torch.manual_seed(11)
+    trained = RnnLm(RnnLmConfig(**lm_cfg))
+    path = str(tmp_path / "nnlm.chkpt")                    # the layout checkpoint.py writes for the NNLM task
+    torch.save({"state_dict": {"_nnlm." + k: v for k, v in trained.state_dict().items()}}, path)
+    cfg2 = copy.deepcopy(cfg)
+    cfg2["metric"].update({"lm_weight": 0.3, "lm": {"config": lm_cfg, "checkpoint": path}})
+    torch.manual_seed(0)
+    plain = TaskFactory.get("Rnnt")(cfg)
+    torch.manual_seed(0)
+    fused = TaskFactory.get("Rnnt")(cfg2)
+    assert list(plain.state_dict()) == list(fused.state_dict())
+    assert [n for n, _ in plain.named_parameters()] == [n for n, _ in fused.named_parameters()]
+    for a, b in zip(plain.parameters(), fused.parameters()):
+        assert torch.equal(a, b)                           # building the LM draws nothing from the task's stream
+    assert not any("nnlm" in n or "_lm" in n or n.startswith("_metric") for n in fused.state_dict())
+    sess = fused._metric._decode_sess
+    assert isinstance(sess._lm, RnnLm) and sess._lm is fused._metric._lm and plain._metric._decode_sess._lm is None
+    assert (sess._lm_weight, sess._lm_start_token) == (0.3, None)
+    assert not sess._lm.training and not any(p.requires_grad for p in sess._lm.parameters())
+    for k, v in trained.state_dict().items():
+        assert torch.equal(sess._lm.state_dict()[k], v)
+    groups = fused.configure_optimizers()["optimizer"].param_groups
+    ids = {id(p) for g in groups for p in g["params"]}
+    assert ids == {id(p) for p in fused.parameters()} and not ids & {id(p) for p in sess._lm.parameters()}
+    cfg3 = copy.deepcopy(cfg2)
+    cfg3["metric"]["lm"]["checkpoint"] = None              # no checkpoint: the LM as built
+    assert isinstance(TaskFactory.get("Rnnt")(cfg3)._metric._decode_sess._lm, RnnLm)
