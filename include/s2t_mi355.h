@@ -702,6 +702,51 @@ int s2t_rnnt_beam_lstm_lm(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, c
                           float lm_weight, int lm_start_token, void* workspace, long* tokens,
                           long* frames, long* out_len, float* score, float* lm_score, void* stream);
 
+/* ---- The fused search above over the STATELESS predictor (model/predictor/predictor.py: Embedding ->
+ * depthwise Conv1d over the last ctx tokens, no bias -> Linear) and the joiner with or without output
+ * projection (csrc/decode_lstm.hip).  Same lockstep rounds, same joint, candidates, ranking, records
+ * and LM step; a row's predictor state is int ctx[ctx], its last ctx tokens, most recent last, ctx
+ * blanks at the start.  A predictor step is three launches: one row kernel (gather of the parent's
+ * context, shift, x[r][e] = sum_k conv_w[e][k] emb[ctx[k]][e] in the order k = 0, 1, ..., and the
+ * masked copy of context and lm row), then the tiled products lin and pre_proj.
+ * S2tRnntStatelessDesc: emb (V, E), conv_w (E, ctx), lin_w (D, E), lin_b (D), pre_w (V, D), pre_b (V),
+ * out1_w (inner, V), out1_b, out2_w (V, inner), out2_b (unused when inner == 0); act: 0 relu, 1 tanh;
+ * blank is class 0.
+ * Limits (else -1 / size 0, before any launch and without following a pointer): 1 <= V, D <=
+ * S2T_RNNT_LSTM_MAX_VOCAB; 0 <= inner <= S2T_RNNT_LSTM_MAX_VOCAB; 1 <= E <= S2T_RNNT_LSTM_MAX_HIDDEN;
+ * 1 <= ctx <= S2T_RNNT_STATELESS_MAX_CONTEXT (the limit of s2t_rnnt_beam_stateless); act in {0, 1}. */
+#define S2T_RNNT_STATELESS_MAX_CONTEXT 64
+typedef struct S2tRnntStatelessDesc {
+  int V, E, D, ctx, inner, act;
+  const float* emb;                /* (V, E) */
+  const float* conv_w;             /* (E, ctx) */
+  const float *lin_w, *lin_b;      /* predictor linear (D, E), (D) */
+  const float *pre_w, *pre_b;      /* joiner pre_proj (V, D), (V) */
+  const float *out1_w, *out1_b;    /* out-projection (inner, V), (inner) */
+  const float *out2_w, *out2_b;    /* (V, inner), (V) */
+} S2tRnntStatelessDesc;
+/* bytes of device `workspace` of s2t_stateless_pred_step for R rows; 0 outside the limits. */
+long s2t_stateless_pred_step_workspace_bytes(const S2tRnntStatelessDesc* desc, int R);
+/* One predictor step for R rows, masked and gathered as s2t_lstm_pred_step: row r with emit[r] != 0
+ * takes the context of row parent[r] (parent NULL: r itself) of ctx_in [R][ctx], shifts tokens[r] in
+ * (clamped to [0, V)), writes it to ctx_out and lm_out[r] = pre_proj(linear(x[r])) [R][V]; a row with
+ * emit[r] == 0 receives the context and the lm_in row of parent[r] bit for bit.  In and out buffers
+ * are either the same (then parent must be NULL) or disjoint. */
+int s2t_stateless_pred_step(const S2tRnntStatelessDesc* desc, int R, const int* tokens, const int* emit,
+                            const int* parent, const int* ctx_in, const float* lm_in, int* ctx_out,
+                            float* lm_out, void* workspace, void* stream);
+long s2t_rnnt_beam_stateless_lm_workspace_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm,
+                                                int B, int T, int beam_size);
+/* s2t_rnnt_beam_lstm_lm over this predictor: same arguments, same outputs, same refusals (lm required,
+ * lm.V == desc.V, lm_weight finite, lm_start_token < V, beam_size and min(cutoff_top_k, V) in
+ * 1..S2T_RNNT_LSTM_MAX_BEAM).  Exactly T rounds, no host synchronisation.  With lm_weight = 0 and inner
+ * == 0 tokens and frames are s2t_rnnt_beam_stateless's and score is within rounding of it (that
+ * kernel orders the predictor's sums differently). */
+int s2t_rnnt_beam_stateless_lm(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, const float* am,
+                               const long* lengths, int B, int T, int beam_size, int cutoff_top_k,
+                               float lm_weight, int lm_start_token, void* workspace, long* tokens,
+                               long* frames, long* out_len, float* score, float* lm_score, void* stream);
+
 /* ---- chunk-carried (streaming) RNN-T search with the LSTM predictor: the two searches above fed
  * their frames in pieces (csrc/decode_lstm.hip).  A round's launches ARE the whole-utterance calls'
  * (one text, the same arguments), and a row's arithmetic does not depend on the rows that share its

@@ -33,6 +33,10 @@
 // step the LM after the predictor, on the same emit / parent / token / count, by the same tiled
 // products and cell kernel (no layer norm) and a log-softmax row kernel.
 //
+// The same fused search over the stateless predictor (s2t_rnnt_beam_stateless_lm): the rounds, the joint,
+// the LM step and the records are the ones above; a row's predictor state is its last ctx tokens and
+// its step is one row kernel (gather, shift, depthwise window sum) and two tiled products.
+//
 // A row's arithmetic does not depend on the rows that share its launch: tiles sit at fixed row
 // positions, every (row, output) sum is taken per lane over k = lane, lane + 64, ... and folded by the
 // same butterfly, and rows beyond R read clamped addresses and are never stored.
@@ -792,23 +796,155 @@ struct StateBuf {
 // The T rounds of a beam search: frame t reads buf[t & 1] and leaves the survivors in buf[~t & 1].
 // With an LM (shallow fusion) its step follows the predictor's on the same emit / parent / token / count,
 // from its buffer cur to nxt.
-void beam_rounds(const S2tRnntLstmDesc& d, BeamArgs a, const StateBuf (&buf)[2], const Workspace& w, int T,
-                 hipStream_t st, const S2tRnnLmDesc* lm = nullptr, const LmWorkspace* lw = nullptr) {
+// pred_step(cur, nxt) enqueues the predictor's step on a.token / a.emit / a.parent / a.counts + cur from
+// its buffer cur to nxt; lm_rows are the two buffers' lm vectors.
+template <typename PredStep>
+void beam_rounds_over(BeamArgs a, float* const (&lm_rows)[2], PredStep pred_step, int T, hipStream_t st,
+                      const S2tRnnLmDesc* lm, const LmWorkspace* lw) {
   const int R = a.B * a.beam;
   for (int t = 0; t < T; ++t) {
     const int cur = t & 1, nxt = cur ^ 1;
     a.t = t;
     a.parity = cur;
-    a.lm = buf[cur].lm;
+    a.lm = lm_rows[cur];
     if (lm) a.q = lw->q[cur];
     hipLaunchKernelGGL(beam_expand_kernel, dim3(R), dim3(kThreads), 0, st, a);
     hipLaunchKernelGGL(beam_select_kernel, dim3(a.B), dim3(kThreads), 0, st, a);
-    enqueue_pred_step(d, R, w.token, w.emit, w.parent, w.counts + cur, buf[cur].h, buf[cur].c, buf[cur].lm,
-                      buf[nxt].h, buf[nxt].c, buf[nxt].lm, w, st);
+    pred_step(cur, nxt);
     if (lm)
-      enqueue_lm_step(*lm, R, w.token, w.emit, w.parent, w.counts + cur, lw->h[cur], lw->c[cur], lw->q[cur],
+      enqueue_lm_step(*lm, R, a.token, a.emit, a.parent, a.counts + cur, lw->h[cur], lw->c[cur], lw->q[cur],
                       lw->h[nxt], lw->c[nxt], lw->q[nxt], *lw, st);
   }
+}
+
+void beam_rounds(const S2tRnntLstmDesc& d, BeamArgs a, const StateBuf (&buf)[2], const Workspace& w, int T,
+                 hipStream_t st, const S2tRnnLmDesc* lm = nullptr, const LmWorkspace* lw = nullptr) {
+  const int R = a.B * a.beam;
+  float* const lm_rows[2] = {buf[0].lm, buf[1].lm};
+  beam_rounds_over(
+      a, lm_rows,
+      [&](int cur, int nxt) {
+        enqueue_pred_step(d, R, w.token, w.emit, w.parent, w.counts + cur, buf[cur].h, buf[cur].c, buf[cur].lm,
+                          buf[nxt].h, buf[nxt].c, buf[nxt].lm, w, st);
+      },
+      T, st, lm, lw);
+}
+
+// ------------------------------------------------------------------ the stateless predictor in the row layout
+// model/predictor/predictor.py StatelessPredictor: Embedding -> depthwise Conv1d over the last ctx tokens
+// (no bias) -> Linear.  A row's state is its ctx tokens, most recent last.  A step is the row kernel
+// below and two tiled products (lin, pre_proj).
+struct StatelessRowArgs {
+  const float* emb;     // [V][E]
+  const float* conv_w;  // [E][ctx]
+  int V, E, ctx;
+  const int *tokens, *emit, *parent, *count;
+  int inplace;
+  const int* ctx_src;   // [R][ctx]
+  int* ctx_dst;
+  const float* lm_src;  // [R][V]
+  float* lm_dst;
+  float* x;             // [R][E], written for emitting rows
+};
+
+// grid R: a row that emits takes its parent's context, shifts its token in and sums the depthwise
+// window, x[e] = sum_k conv_w[e][k] emb[ctx[k]][e] over k = 0, 1, ... (csrc/decode_search.h's order); a row
+// that does not takes its parent's context and lm row as they are
+__global__ __launch_bounds__(kThreads) void stateless_row_kernel(StatelessRowArgs a) {
+  __shared__ int s_ctx[S2T_RNNT_STATELESS_MAX_CONTEXT];
+  if (a.inplace && *a.count == 0) return;
+  const int row = blockIdx.x, tid = threadIdx.x, n = a.ctx;
+  const long src = a.parent ? a.parent[row] : row;
+  if (!a.emit[row]) {
+    if (!a.inplace) {
+      for (int k = tid; k < n; k += kThreads) a.ctx_dst[(long)row * n + k] = a.ctx_src[src * n + k];
+      for (int i = tid; i < a.V; i += kThreads) a.lm_dst[(long)row * a.V + i] = a.lm_src[src * a.V + i];
+    }
+    return;
+  }
+  if (tid < n) s_ctx[tid] = tid + 1 < n ? a.ctx_src[src * n + tid + 1] : a.tokens[row];
+  __syncthreads();                                         // (in place: the row is read before it is written)
+  if (tid < n) {
+    s_ctx[tid] = min(max(s_ctx[tid], 0), a.V - 1);
+    a.ctx_dst[(long)row * n + tid] = s_ctx[tid];
+  }
+  __syncthreads();
+  for (int e = tid; e < a.E; e += kThreads) {
+    float acc = 0.f;
+    for (int k = 0; k < n; ++k) acc = fmaf(a.conv_w[e * n + k], a.emb[(long)s_ctx[k] * a.E + e], acc);
+    a.x[(long)row * a.E + e] = acc;
+  }
+}
+
+struct StatelessWorkspace {
+  int* ctx[2];                  // state [R][ctx] twice
+  float* lm[2];                 // lm [R][V] twice
+  float *x, *lin;               // the depthwise sums [R][E], linear(x) [R][D]
+  float *z, *mid, *logit;       // joint, as Workspace
+  float *cscore, *score;        // beam, as Workspace
+  int *ccls, *blen, *nb, *rec, *emit, *token, *parent, *counts;
+  size_t bytes;
+};
+
+// n_state copies of (ctx, lm): two for a search, none for the step on its own (the caller's buffers)
+StatelessWorkspace carve_stateless(const S2tRnntStatelessDesc& d, int B, int T, int beam, void* base, int n_state) {
+  const size_t R = (size_t)B * (beam > 0 ? beam : 1);
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* q = p + off;
+    off += align256(bytes);
+    return q;
+  };
+  auto f = [&](size_t n) { return reinterpret_cast<float*>(take(4 * n)); };
+  auto i = [&](size_t n) { return reinterpret_cast<int*>(take(4 * n)); };
+  StatelessWorkspace w;
+  for (int s = 0; s < 2; ++s) {
+    w.ctx[s] = s < n_state ? i(R * d.ctx) : nullptr;
+    w.lm[s] = s < n_state ? f(R * d.V) : nullptr;
+  }
+  w.x = f(R * d.E);
+  w.lin = f(R * d.D);
+  const bool search = beam > 0;
+  w.z = f(search ? R * d.V : 1);
+  w.mid = f(search && d.inner > 0 ? R * d.inner : 1);
+  w.logit = f(search ? R * d.V : 1);
+  w.cscore = f(search ? (size_t)B * kMaxCand : 1);
+  w.score = f(R);
+  w.ccls = i(search ? (size_t)B * kMaxCand : 1);
+  w.blen = i(R);
+  w.nb = i(B);
+  w.rec = i(search ? (size_t)B * T * beam : 1);
+  w.emit = i(R);
+  w.token = i(R);
+  w.parent = i(R);
+  w.counts = i(4);
+  w.bytes = off;
+  return w;
+}
+
+bool stateless_ok(const S2tRnntStatelessDesc* d) {
+  return d && d->V >= 1 && d->V <= S2T_RNNT_LSTM_MAX_VOCAB && d->D >= 1 && d->D <= S2T_RNNT_LSTM_MAX_VOCAB &&
+         d->inner >= 0 && d->inner <= S2T_RNNT_LSTM_MAX_VOCAB && d->E >= 1 && d->E <= S2T_RNNT_LSTM_MAX_HIDDEN &&
+         d->ctx >= 1 && d->ctx <= S2T_RNNT_STATELESS_MAX_CONTEXT && d->act >= 0 && d->act <= 1;
+}
+
+// In place (src == dst, parent NULL) or from buffer `src` to buffer `dst`.
+void enqueue_stateless_step(const S2tRnntStatelessDesc& d, int R, const int* tokens, const int* emit,
+                            const int* parent, const int* count, const int* ctx_src, const float* lm_src,
+                            int* ctx_dst, float* lm_dst, const StatelessWorkspace& w, hipStream_t st) {
+  const int row_tiles = (R + kTileRows - 1) / kTileRows;
+  constexpr int kOuts = kTileWaves * kTileOuts;
+  StatelessRowArgs a{d.emb, d.conv_w, d.V, d.E, d.ctx, tokens, emit, parent, count, ctx_src == ctx_dst,
+                     ctx_src, ctx_dst, lm_src, lm_dst, w.x};
+  hipLaunchKernelGGL(stateless_row_kernel, dim3(R), dim3(kThreads), 0, st, a);
+  TileArgs t{w.x, d.E, d.lin_w, d.E, nullptr, 0, nullptr, 0, d.lin_b, d.D, R, emit, nullptr, count, w.lin, d.D};
+  hipLaunchKernelGGL(tile_linear_kernel, dim3((d.D + kOuts - 1) / kOuts, row_tiles), dim3(64 * kTileWaves), 0,
+                     st, t);
+  TileArgs u{w.lin, d.D, d.pre_w, d.D, nullptr, 0, nullptr, 0, d.pre_b, d.V, R, emit, nullptr, count, lm_dst,
+             d.V};
+  hipLaunchKernelGGL(tile_linear_kernel, dim3((d.V + kOuts - 1) / kOuts, row_tiles), dim3(64 * kTileWaves), 0,
+                     st, u);
 }
 
 // ------------------------------------------------------------------ chunk-carried search
@@ -1137,6 +1273,81 @@ int s2t_rnnt_beam_lstm_lm(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, c
              lw.lm_sum};
   const StateBuf buf[2] = {{w.h[0], w.c[0], w.lm[0]}, {w.h[1], w.c[1], w.lm[1]}};
   beam_rounds(d, a, buf, w, T, st, lm, &lw);
+  hipLaunchKernelGGL(beam_trace_kernel, dim3(B), dim3(64), 0, st, lengths, T, beam_size, w.rec, w.blen,
+                     w.score, tokens, frames, out_len, score, (const float*)lw.lm_sum, lm_score);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+long s2t_stateless_pred_step_workspace_bytes(const S2tRnntStatelessDesc* desc, int R) {
+  if (!stateless_ok(desc) || R <= 0) return 0;
+  return (long)carve_stateless(*desc, R, 0, 0, nullptr, 0).bytes;
+}
+
+int s2t_stateless_pred_step(const S2tRnntStatelessDesc* desc, int R, const int* tokens, const int* emit,
+                            const int* parent, const int* ctx_in, const float* lm_in, int* ctx_out,
+                            float* lm_out, void* workspace, void* stream) {
+  if (R <= 0) return 0;
+  if (!stateless_ok(desc) || !workspace) return -1;
+  const bool same = ctx_in == ctx_out;
+  if (same != (lm_in == lm_out) || (same && parent)) return -1;
+  const StatelessWorkspace w = carve_stateless(*desc, R, 0, 0, workspace, 0);
+  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, emit, R, w.counts);
+  enqueue_stateless_step(*desc, R, tokens, emit, parent, w.counts, ctx_in, lm_in, ctx_out, lm_out, w,
+                         (hipStream_t)stream);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+long s2t_rnnt_beam_stateless_lm_workspace_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, int B,
+                                                int T, int beam_size) {
+  if (!stateless_ok(desc) || !lm_ok(lm) || lm->V != desc->V || B <= 0 || T < 0 || beam_size < 1 ||
+      beam_size > kMaxBeam)
+    return 0;
+  return (long)(carve_stateless(*desc, B, T, beam_size, nullptr, 2).bytes +
+                carve_lm(*lm, B, beam_size, nullptr, 2).bytes);
+}
+
+int s2t_rnnt_beam_stateless_lm(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, const float* am,
+                               const long* lengths, int B, int T, int beam_size, int cutoff_top_k,
+                               float lm_weight, int lm_start_token, void* workspace, long* tokens,
+                               long* frames, long* out_len, float* score, float* lm_score, void* stream) {
+  if (B <= 0) return 0;
+  if (!stateless_ok(desc) || !lm_ok(lm) || lm->V != desc->V || T <= 0 || beam_size < 1 ||
+      beam_size > kMaxBeam || cutoff_top_k < 1 || (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam ||
+      lm_start_token >= desc->V || !__builtin_isfinite(lm_weight) || !workspace)
+    return -1;
+  const S2tRnntStatelessDesc& d = *desc;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = B * beam_size;
+  const StatelessWorkspace w = carve_stateless(d, B, T, beam_size, workspace, 2);
+  const LmWorkspace lw = carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 2);
+  const size_t lm_state = sizeof(float) * (size_t)lm->num_layers * R * lm->H;
+  hipError_t e = hipMemsetAsync(w.ctx[0], 0, sizeof(int) * (size_t)R * d.ctx, st);   // ctx blanks
+  if (e == hipSuccess) e = hipMemsetAsync(lw.h[0], 0, lm_state, st);
+  if (e == hipSuccess) e = hipMemsetAsync(lw.c[0], 0, lm_state, st);
+  if (e == hipSuccess) e = hipMemsetAsync(lw.q[0], 0, sizeof(float) * (size_t)R * d.V, st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(beam_init_kernel, dim3(1), dim3(kThreads), 0, st, B, beam_size, w.score, w.blen, w.nb,
+                     w.emit, w.token, w.counts);
+  hipLaunchKernelGGL(lm_start_kernel, dim3((R + kThreads - 1) / kThreads), dim3(kThreads), 0, st, R,
+                     lm_start_token, lw.tok, lw.lm_sum);
+  enqueue_stateless_step(d, R, w.token, w.emit, nullptr, w.counts + 2, w.ctx[0], w.lm[0], w.ctx[0], w.lm[0], w,
+                         st);
+  if (lm_start_token >= 0)                                 // the LM's first step, as the predictor's on blank
+    enqueue_lm_step(*lm, R, lw.tok, w.emit, nullptr, w.counts + 2, lw.h[0], lw.c[0], lw.q[0], lw.h[0], lw.c[0],
+                    lw.q[0], lw, st);
+  BeamArgs a{JointArgs{am, T, d.V, d.inner, d.act, d.out1_w, d.out1_b, d.out2_w, d.out2_b, w.z, w.mid, w.logit},
+             lengths, w.lm[0], 0, B, beam_size, cutoff_top_k, 0, w.cscore, w.score, w.ccls, w.blen, w.nb, w.rec,
+             w.emit, w.token, w.parent, w.counts, lw.q[0], lm_weight, lw.cq, lw.lm_sum};
+  float* const lm_rows[2] = {w.lm[0], w.lm[1]};
+  beam_rounds_over(
+      a, lm_rows,
+      [&](int cur, int nxt) {
+        enqueue_stateless_step(d, R, w.token, w.emit, w.parent, w.counts + cur, w.ctx[cur], w.lm[cur], w.ctx[nxt],
+                               w.lm[nxt], w, st);
+      },
+      T, st, lm, &lw);
   hipLaunchKernelGGL(beam_trace_kernel, dim3(B), dim3(64), 0, st, lengths, T, beam_size, w.rec, w.blen,
                      w.score, tokens, frames, out_len, score, (const float*)lw.lm_sum, lm_score);
   S2T_CHECK_LAUNCH();

@@ -16,8 +16,9 @@ across chunks of a stream (RnntStreamingSearch, csrc/decode_stream.hip; RnntLstm
 csrc/decode_lstm.hip; rnnt_streaming_search picks the class).  Other predictor / joiner
 combinations (the stateless predictor with an out-projection joiner, foreign classes, shapes a
 kernel refuses) keep the module-by-module loop.  RnntBeamDecoding takes an RNN language model
-for shallow fusion (`lm=`, `lm_weight=`): with the LSTM predictor the LM is stepped inside the
-lockstep device search (s2t_rnnt_beam_lstm_lm), everything else runs `_module_loop_lm`.  The
+for shallow fusion (`lm=`, `lm_weight=`): with the LSTM predictor and with the stateless predictor
+(joiner with or without output projection) the LM is stepped inside the lockstep device search
+(s2t_rnnt_beam_lstm_lm, s2t_rnnt_beam_stateless_lm), everything else runs `_module_loop_lm`.  The
 lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are not here."""
 import abc
 from enum import Enum, unique
@@ -270,6 +271,83 @@ def rnnt_beam_lstm_lm_tokens_from_am(am, lengths, predictor, joiner, lm, lm_weig
     return out
 
 
+def _is_stateless_pair(predictor, joiner):
+    """The modules s2t_rnnt_beam_stateless_lm serves: StatelessPredictor + Joiner (any out-projection)."""
+    from speech2text_amd.model.joiner.joiner import Joiner
+    from speech2text_amd.model.predictor.predictor import StatelessPredictor
+    return isinstance(getattr(predictor, "predictor", predictor), StatelessPredictor) and isinstance(joiner, Joiner)
+
+
+def rnnt_stateless_desc(predictor, joiner):
+    """rnnt_lstm_desc for the stateless predictor -> (S2tRnntStatelessDesc of the two modules' fp32
+    parameters, the tensors it points to: keep them alive while the descriptor is in use), or
+    (None, []) for anything that is not StatelessPredictor + Joiner."""
+    import ctypes
+    keep = []
+    if not _is_stateless_pair(predictor, joiner):
+        return None, keep
+    p = getattr(predictor, "predictor", predictor)
+
+    def a(t):
+        t = t.detach().contiguous().float()
+        keep.append(t)
+        return t.data_ptr()
+
+    if p._embedding.num_embeddings < joiner._output_dim:   # (every class must have an embedding row)
+        return None, keep
+    d = N.struct("S2tRnntStatelessDesc")()
+    d.V, d.E, d.D, d.ctx = joiner._output_dim, p._embedding_dim, p._output_dim, p._context_size
+    d.inner = joiner._inner_dim if joiner._use_out_project else 0
+    d.act = 0 if joiner._act_name == "relu" else 1
+    d.emb, d.conv_w = a(p._embedding.weight), a(p._conv.weight.reshape(p._embedding_dim, p._context_size))
+    d.lin_w, d.lin_b = a(p._output_linear.weight), a(p._output_linear.bias)
+    d.pre_w, d.pre_b = a(joiner._pre_proj.weight), a(joiner._pre_proj.bias)
+    if joiner._use_out_project:
+        o1, o2 = joiner._out_projection[0], joiner._out_projection[1]
+        d.out1_w, d.out1_b, d.out2_w, d.out2_b = a(o1.weight), a(o1.bias), a(o2.weight), a(o2.bias)
+    keep.append(d)
+    return ctypes.byref(d), keep
+
+
+def rnnt_beam_stateless_lm_tokens_from_am(am, lengths, predictor, joiner, lm, lm_weight, beam_size=4,
+                                          cutoff_top_k=4, lm_start_token=None):
+    """rnnt_beam_lstm_lm_tokens_from_am for the stateless predictor (joiner with or without
+    out-projection): the same lockstep rounds, LM step and outputs, the predictor step being one row
+    kernel and two tiled products.  -> (tokens, frames, out_len, score, lm_score), or None when the
+    kernels do not take the modules or the shape.  HIP: decode_lstm.hip."""
+    if not am.is_cuda:
+        raise RuntimeError("the device RNN-T beam search runs on the GPU only")
+    am = am.contiguous().float()
+    B, T, V = am.shape
+    dev = am.device
+    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+    out = _beam_outputs(B, T, dev) + (torch.zeros((B,), dtype=torch.float32, device=dev),)
+    if B == 0 or T == 0:
+        return out
+    start = -1 if lm_start_token is None else int(lm_start_token)
+    if lm_start_token is not None and start < 0:
+        raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
+    desc, keep = rnnt_stateless_desc(predictor, joiner)
+    lm_desc, lm_keep = rnn_lm_desc(lm)
+    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
+    if desc is None or lm_desc is None or not 1 <= beam_size <= N.const("S2T_RNNT_LSTM_MAX_BEAM"):
+        return None
+    if any(not t.is_cuda for t in keep[:-1]):
+        raise RuntimeError("the device RNN-T beam search runs on the GPU only: the modules are not on it")
+    n = N.lib().s2t_rnnt_beam_stateless_lm_workspace_bytes(desc, lm_desc, B, T, beam_size)
+    if n <= 0:
+        return None
+    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+    tokens, frames, out_len, score, lm_score = out
+    rc = N.lib().s2t_rnnt_beam_stateless_lm(desc, lm_desc, N.fp(am), N.lp(lengths), B, T, beam_size, cutoff_top_k,
+                                            float(lm_weight), start, N.ptr(ws), N.lp(tokens), N.lp(frames),
+                                            N.lp(out_len), N.fp(score), N.fp(lm_score), N.stream())
+    if rc == -1:
+        return None
+    N.check(rc, "s2t_rnnt_beam_stateless_lm")
+    return out
+
+
 def _am_per_utterance(joiner, hidden_states, inputs_length):
     """am (B,T,V) = enc_proj(encoder_out), formed utterance by utterance on the frames an utterance
     has: the product decode() forms for the same utterance alone, so that a batched search and a
@@ -426,8 +504,9 @@ class RnntBeamDecoding(DecodingMethod):
     candidate of class c != blank scores `lm_weight * log p_lm(c | the beam's tokens)` more, the cut
     to `cutoff_top_k` classes is still the RNN-T's own, blank carries no LM term.  `lm_start_token`
     None: the LM starts from zero state and a hypothesis' first token carries no LM term (how
-    RnnLm.score scores a sequence); a token id: the LM is first stepped on it.  The LSTM predictor
-    runs the fused device search (csrc/decode_lstm.hip); everything else `_module_loop_lm`.
+    RnnLm.score scores a sequence); a token id: the LM is first stepped on it.  The LSTM predictor and
+    the stateless predictor (with the project's Joiner and an RnnLm) run the fused device search
+    (csrc/decode_lstm.hip); everything else, and a shape the kernels refuse, `_module_loop_lm`.
     `beam_tokens` then returns a fifth tensor, the best beam's unweighted LM sum."""
 
     def __init__(self, tokenizer, predictor, joiner, beam_size=4, cutoff_top_k=4, lm=None, lm_weight=0.0,
@@ -579,6 +658,14 @@ class RnntBeamDecoding(DecodingMethod):
             out = rnnt_beam_lstm_lm_tokens_from_am(am, lens, self._predictor, self._joiner, self._lm,
                                                    self._lm_weight, self._beam_size, self._cutoff_top_k,
                                                    self._lm_start_token)
+            if out is not None:
+                return out
+        if fused and _is_stateless_pair(self._predictor, self._joiner) and isinstance(self._lm, RnnLm) \
+                and hidden_states.is_cuda:
+            am, lens = _am_per_utterance(self._joiner, hidden_states, inputs_length)
+            out = rnnt_beam_stateless_lm_tokens_from_am(am, lens, self._predictor, self._joiner, self._lm,
+                                                        self._lm_weight, self._beam_size, self._cutoff_top_k,
+                                                        self._lm_start_token)
             if out is not None:
                 return out
         B, T = hidden_states.shape[0], hidden_states.shape[1]
