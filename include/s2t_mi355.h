@@ -808,6 +808,69 @@ int s2t_rnnt_beam_lstm_chunk(const S2tRnntLstmDesc* desc, const float* am, const
                              long* out_len, float* score, long* stable_len, int* overflow,
                              void* stream);
 
+/* ---- chunk-carried (streaming) RNN-T beam search with RNN-LM shallow fusion: s2t_rnnt_beam_lstm_lm and
+ * s2t_rnnt_beam_stateless_lm fed their frames in pieces (csrc/decode_lstm.hip).  The contract of the block
+ * above, word for word, extended by the LM: a round's launches ARE the fused whole-utterance calls'
+ * (chunk_len where those take lengths, Tc where they take T, the carried buffers where they take their
+ * workspace's), so for ANY cut of [0, L) into chunks tokens, frames, out_len, score and lm_score after
+ * the last chunk are those of the fused call on the concatenated am with lengths = L, bit for bit, and
+ * after every chunk those of the prefix fed so far.  lm_score [B]: the best beam's unweighted lm_sum.
+ * Beam only (the greedy searches take no LM); lm is required.  The stateless family takes inner == 0
+ * and inner > 0: it is the only chunk-carried search of the out-projection joiner with that predictor.
+ * state: ONE caller-owned buffer of *_lm_stream_state_bytes(desc, lm, B, beam_size, max_tokens) bytes (a
+ * multiple of 256, independent of the chunks or frames seen), every array 256-byte aligned.  LSTM
+ * family: the state of s2t_rnnt_lstm_stream_state_bytes (same layout), then the LM's h, c
+ * [lm.layers][R][lm.H], q [R][V] and lm_sum [R], R = B * beam_size.  Stateless family: ctx [R][ctx]
+ * (int32) and lm [R][V] in place of the LSTM (h, c, lm), the same per-utterance and per-beam records,
+ * then the same LM arrays.  lm_sum is updated in place by the rounds' select launch.
+ * workspace: *_lm_stream_workspace_bytes(desc, lm, B, Tc, beam_size) bytes of scratch (one sized for Tc =
+ * 256 serves every call and the reset), holding the second copy of the predictor's and the LM's
+ * state.  The LIVE copy is always the state buffer's: frame 0 of a chunk reads it, and after an odd Tc
+ * ONE launch copies every survivor home (predictor state and lm rows, the LM's h, c, q, the stateless
+ * ctx), so the launches of a call depend on its arguments alone.
+ * *_lm_stream_reset: for every row b with rows[b] != 0 (rows NULL: every row): zero predictor state (LSTM
+ * (h, c); ctx blanks), zero LM (h, c), q = 0, lm_sum = 0, one live beam of score 0, frame counter 0,
+ * overflow 0, then the fused call's own first predictor step on blank and, with lm_start_token >= 0, its
+ * own first LM step on that token, both masked by rows.  Other rows keep every bit, LM state included.
+ * The caller's output arrays are not reset's to write.  The same lm_start_token convention as
+ * s2t_rnnt_beam_lstm_lm (< 0: none).
+ * *_lm_chunk: outputs as s2t_rnnt_beam_lstm_chunk plus lm_score.  chunk_len[b] <= 0 leaves row b's
+ * hypothesis, its LM state and the caller's outputs for it as they were; a finished or idle row never
+ * reads am.  Past max_tokens a beam keeps its first max_tokens tokens and overflow[b] = 1; score,
+ * lm_score and all states stay exact.  With lm_weight = 0 the LSTM family's tokens, frames, out_len,
+ * score, stable_len and overflow are s2t_rnnt_beam_lstm_chunk's bit for bit.
+ * No host synchronisation, no cooperative launch, no memset, nothing left behind that depends on host
+ * memory: reset and chunk call can be captured into a graph and replayed.
+ * Return 0; -1 before any launch (outputs untouched, no pointer followed) for Tc outside 1..256, state,
+ * workspace or lm NULL, max_tokens < 1, lm_start_token >= V, lm_weight not finite, lm.V != desc.V, or
+ * what the fused whole-utterance call refuses; B <= 0 returns 0.  The size functions are pure host
+ * functions and return 0 outside the limits. */
+long s2t_rnnt_lstm_lm_stream_state_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B,
+                                         int beam_size, int max_tokens);
+long s2t_rnnt_lstm_lm_stream_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B,
+                                             int Tc, int beam_size);
+int s2t_rnnt_lstm_lm_stream_reset(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int lm_start_token,
+                                  void* state, const int* rows, int B, int beam_size, int max_tokens,
+                                  void* workspace, void* stream);
+int s2t_rnnt_beam_lstm_lm_chunk(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, const float* am,
+                                const long* chunk_len, int B, int Tc, int beam_size, int cutoff_top_k,
+                                float lm_weight, int max_tokens, void* state, void* workspace,
+                                long* tokens, long* frames, long* out_len, float* score, float* lm_score,
+                                long* stable_len, int* overflow, void* stream);
+long s2t_rnnt_stateless_lm_stream_state_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm,
+                                              int B, int beam_size, int max_tokens);
+long s2t_rnnt_stateless_lm_stream_workspace_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm,
+                                                  int B, int Tc, int beam_size);
+int s2t_rnnt_stateless_lm_stream_reset(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm,
+                                       int lm_start_token, void* state, const int* rows, int B,
+                                       int beam_size, int max_tokens, void* workspace, void* stream);
+int s2t_rnnt_beam_stateless_lm_chunk(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm,
+                                     const float* am, const long* chunk_len, int B, int Tc, int beam_size,
+                                     int cutoff_top_k, float lm_weight, int max_tokens, void* state,
+                                     void* workspace, long* tokens, long* frames, long* out_len,
+                                     float* score, float* lm_score, long* stable_len, int* overflow,
+                                     void* stream);
+
 /* ---- batched on-device augmentation + collate next to the fbank kernel
  * (dataset/frontend/data_augmentation.py:13-56 AddNoise, :59-118 MixFeats, :150-196 SpecAugment;
  * dataset/utils.py:182-202 batch()).  Random decisions are made on the host as the reference

@@ -37,6 +37,10 @@
 // the LM step and the records are the ones above; a row's predictor state is its last ctx tokens and
 // its step is one row kernel (gather, shift, depthwise window sum) and two tiled products.
 //
+// Both fused searches also run a chunk at a time (s2t_rnnt_beam_lstm_lm_chunk,
+// s2t_rnnt_beam_stateless_lm_chunk): the same rounds through the same host functions, the LM's (h, c), q
+// and lm_sum carried in the caller's state buffer behind the predictor's.
+//
 // A row's arithmetic does not depend on the rows that share its launch: tiles sit at fixed row
 // positions, every (row, output) sum is taken per lane over k = lane, lane + 64, ... and folded by the
 // same butterfly, and rows beyond R read clamped addresses and are never stored.
@@ -1101,6 +1105,8 @@ struct BeamEndArgs {
   float* out_score;
   long* stable_len;
   int* overflow;
+  const float* lm_sum;  // shallow fusion: the rows' unweighted LM sums [R] after the chunk, or NULL
+  float* out_lm;        // [B]
 };
 
 // grid B: the chunk's records become the beams' new histories and the row's outputs
@@ -1126,6 +1132,7 @@ __global__ __launch_bounds__(kThreads) void beam_chunk_end_kernel(BeamEndArgs a)
       [&](int out_len, int stable, int ovf) {
         a.out_len[b] = out_len;
         a.out_score[b] = a.score[row0];
+        if (a.out_lm) a.out_lm[b] = a.lm_sum[row0];
         a.stable_len[b] = stable;
         a.overflow[b] = ovf;
         hdr[0] = f0 + Tb;
@@ -1133,6 +1140,138 @@ __global__ __launch_bounds__(kThreads) void beam_chunk_end_kernel(BeamEndArgs a)
         hdr[2] = hcur ^ 1;
         hdr[3] = stable;
       });
+}
+
+// ------------------------------------------------------------------ chunk-carried search with the RNN-LM
+// The fused searches (s2t_rnnt_beam_lstm_lm, s2t_rnnt_beam_stateless_lm) fed their frames in pieces: the
+// rounds are beam_rounds_over with the LM, on carried buffers.  Behind the predictor's stream state the
+// caller's buffer holds the LM's live (h, c, q) and lm_sum; the workspace holds the second copy of (h, c,
+// q), and after an odd Tc ONE launch copies every survivor home, the predictor's and the LM's.
+struct LmStreamState {
+  float *h, *c, *q;                // [layers][R][H] twice, [R][V]
+  float* lm_sum;                   // [R]
+  size_t bytes;
+};
+
+LmStreamState carve_lm_state(const S2tRnnLmDesc& d, int B, int beam, void* base) {
+  const size_t R = (size_t)B * beam, L = d.num_layers;
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto f = [&](size_t n) {
+    char* q = p + off;
+    off += align256(4 * n);
+    return reinterpret_cast<float*>(q);
+  };
+  LmStreamState s{};
+  s.h = f(L * R * d.H);
+  s.c = f(L * R * d.H);
+  s.q = f(R * d.V);
+  s.lm_sum = f(R);
+  s.bytes = off;
+  return s;
+}
+
+// the stateless predictor's stream state: StreamState with the context in place of (h, c)
+struct StatelessStreamState {
+  int* ctx;                        // [R][ctx]
+  float *lm, *score;               // [R][V], [R]
+  int *blen, *nb, *hdr;            // [R], [B], [B][kStreamHdr]
+  int *htok, *hfrm;                // [B][2][beam][max_tokens]
+  size_t bytes;
+};
+
+StatelessStreamState carve_stateless_state(const S2tRnntStatelessDesc& d, int B, int beam, int max_tokens,
+                                           void* base) {
+  const size_t R = (size_t)B * beam;
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* q = p + off;
+    off += align256(bytes);
+    return q;
+  };
+  StatelessStreamState s{};
+  s.ctx = reinterpret_cast<int*>(take(4 * R * d.ctx));
+  s.lm = reinterpret_cast<float*>(take(4 * R * d.V));
+  s.hdr = reinterpret_cast<int*>(take(4 * (size_t)B * kStreamHdr));
+  s.score = reinterpret_cast<float*>(take(4 * R));
+  s.blen = reinterpret_cast<int*>(take(4 * R));
+  s.nb = reinterpret_cast<int*>(take(4 * (size_t)B));
+  s.htok = reinterpret_cast<int*>(take(4 * 2 * R * max_tokens));
+  s.hfrm = reinterpret_cast<int*>(take(4 * 2 * R * max_tokens));
+  s.bytes = off;
+  return s;
+}
+
+// pred_ok, V: the predictor descriptor's check and vocabulary
+bool lm_stream_ok(bool pred_ok, int V, const S2tRnnLmDesc* lm, int beam, int max_tokens) {
+  return pred_ok && lm_ok(lm) && lm->V == V && beam >= 1 && beam <= kMaxBeam && max_tokens >= 1;
+}
+
+// The LM workspace a chunk's rounds work on: buffer 0 is the state's (the live copy, frame 0 reads it),
+// buffer 1 the workspace's one copy; lm_sum is the state's, updated in place.
+LmWorkspace live_lm(LmWorkspace w, const LmStreamState& s) {
+  w.h[1] = w.h[0];
+  w.c[1] = w.c[0];
+  w.q[1] = w.q[0];
+  w.h[0] = s.h;
+  w.c[0] = s.c;
+  w.q[0] = s.q;
+  w.lm_sum = s.lm_sum;
+  return w;
+}
+
+struct LmResetArgs {
+  const int* rows;      // [B] or NULL
+  int BS, layers, H, V, nctx, start;   // nctx: the stateless predictor's context (0: none)
+  float *h, *c, *q, *lm_sum;
+  int* tok;             // [R]: the token of the LM's first step
+  int* ctx;             // [R][nctx] or NULL
+};
+
+// grid B, after stream_reset_kernel: a row the mask names gets zero LM (h, c), q = 0, lm_sum = 0 and
+// (stateless predictor) a context of blanks; the other rows keep every bit.  Every row's start token
+// is written (lm_start_kernel's tok), the step that follows is masked by emit.
+__global__ __launch_bounds__(kThreads) void lm_stream_reset_kernel(LmResetArgs a) {
+  const int b = blockIdx.x, tid = threadIdx.x, BS = a.BS, row0 = b * BS;
+  const long R = (long)gridDim.x * BS;
+  if (tid < BS) a.tok[row0 + tid] = a.start;
+  if (a.rows && a.rows[b] == 0) return;
+  for (int l = 0; l < a.layers; ++l)
+    for (int x = tid; x < BS * a.H; x += kThreads) {
+      a.h[(l * R + row0) * a.H + x] = 0.f;
+      a.c[(l * R + row0) * a.H + x] = 0.f;
+    }
+  for (long x = tid; x < (long)BS * a.V; x += kThreads) a.q[(long)row0 * a.V + x] = 0.f;
+  if (tid < BS) a.lm_sum[row0 + tid] = 0.f;
+  if (a.ctx)
+    for (int x = tid; x < BS * a.nctx; x += kThreads) a.ctx[(long)row0 * a.nctx + x] = 0;
+}
+
+constexpr int kCopyParts = 6;
+
+struct CopyHomeArgs {
+  const void* src[kCopyParts];
+  void* dst[kCopyParts];
+  long n[kCopyParts];              // 4-byte words (float or int); 0: unused
+};
+
+// state_copy_kernel for the fused searches: the predictor's survivors and the LM's in one launch
+__global__ __launch_bounds__(kThreads) void state_copy_parts_kernel(CopyHomeArgs a) {
+  const long step = (long)gridDim.x * kThreads, i0 = (long)blockIdx.x * kThreads + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kCopyParts; ++k) {
+    const unsigned* __restrict__ s = static_cast<const unsigned*>(a.src[k]);
+    unsigned* d = static_cast<unsigned*>(a.dst[k]);
+    for (long i = i0; i < a.n[k]; i += step) d[i] = s[i];
+  }
+}
+
+void enqueue_copy_home(const CopyHomeArgs& c, hipStream_t st) {
+  long most = 1;
+  for (int k = 0; k < kCopyParts; ++k) most = c.n[k] > most ? c.n[k] : most;
+  const long need = (most + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(state_copy_parts_kernel, dim3((int)(need < 1024 ? need : 1024)), dim3(kThreads), 0, st, c);
 }
 
 }  // namespace
@@ -1431,7 +1570,175 @@ int s2t_rnnt_beam_lstm_chunk(const S2tRnntLstmDesc* desc, const float* am, const
                        s.lm, n_state, n_lm);
   }
   BeamEndArgs e{chunk_len, Tc, beam_size, max_tokens, w.rec, s.blen, s.nb, s.score, s.hdr, s.htok, s.hfrm,
-                tokens, frames, out_len, score, stable_len, overflow};
+                tokens, frames, out_len, score, stable_len, overflow, nullptr, nullptr};
+  hipLaunchKernelGGL(beam_chunk_end_kernel, dim3(B), dim3(kThreads), 0, st, e);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+long s2t_rnnt_lstm_lm_stream_state_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B,
+                                         int beam_size, int max_tokens) {
+  if (B <= 0 || !lm_stream_ok(desc_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens)) return 0;
+  return (long)(carve_state(*desc, B, beam_size, max_tokens, nullptr).bytes +
+                carve_lm_state(*lm, B, beam_size, nullptr).bytes);
+}
+
+long s2t_rnnt_lstm_lm_stream_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B, int Tc,
+                                             int beam_size) {
+  if (B <= 0 || Tc < 1 || Tc > kMaxChunk || !lm_stream_ok(desc_ok(desc), desc ? desc->V : 0, lm, beam_size, 1))
+    return 0;
+  return (long)(carve(*desc, B, Tc, beam_size, nullptr, 1).bytes + carve_lm(*lm, B, beam_size, nullptr, 1).bytes);
+}
+
+int s2t_rnnt_lstm_lm_stream_reset(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int lm_start_token,
+                                  void* state, const int* rows, int B, int beam_size, int max_tokens,
+                                  void* workspace, void* stream) {
+  if (B <= 0) return 0;
+  if (!lm_stream_ok(desc_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens) || lm_start_token >= desc->V ||
+      !state || !workspace)
+    return -1;
+  const S2tRnntLstmDesc& d = *desc;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = B * beam_size;
+  const StreamState s = carve_state(d, B, beam_size, max_tokens, state);
+  const LmStreamState ls = carve_lm_state(*lm, B, beam_size, static_cast<char*>(state) + s.bytes);
+  const Workspace w = carve(d, B, 1, beam_size, workspace, 1);
+  const LmWorkspace lw = carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 1);
+  ResetArgs a{rows, beam_size, beam_size, d.num_layers, d.H, s.h, s.c, s.score, s.blen, s.nb, s.hdr, s.n, w.emit,
+              w.token};
+  hipLaunchKernelGGL(stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, a);
+  LmResetArgs la{rows, beam_size, lm->num_layers, lm->H, d.V, 0, lm_start_token, ls.h, ls.c, ls.q, ls.lm_sum,
+                 lw.tok, nullptr};
+  hipLaunchKernelGGL(lm_stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, la);
+  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, st, w.emit, R, w.counts + 2);
+  enqueue_pred_step(d, R, w.token, w.emit, nullptr, w.counts + 2, s.h, s.c, s.lm, s.h, s.c, s.lm, w, st);
+  if (lm_start_token >= 0)                                 // the LM's first step, as the predictor's on blank
+    enqueue_lm_step(*lm, R, lw.tok, w.emit, nullptr, w.counts + 2, ls.h, ls.c, ls.q, ls.h, ls.c, ls.q, lw, st);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_rnnt_beam_lstm_lm_chunk(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, const float* am,
+                                const long* chunk_len, int B, int Tc, int beam_size, int cutoff_top_k,
+                                float lm_weight, int max_tokens, void* state, void* workspace, long* tokens,
+                                long* frames, long* out_len, float* score, float* lm_score, long* stable_len,
+                                int* overflow, void* stream) {
+  if (B <= 0) return 0;
+  if (!lm_stream_ok(desc_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens) || Tc < 1 || Tc > kMaxChunk ||
+      cutoff_top_k < 1 || (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam ||
+      !__builtin_isfinite(lm_weight) || !state || !workspace)
+    return -1;
+  const S2tRnntLstmDesc& d = *desc;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = B * beam_size;
+  const StreamState s = carve_state(d, B, beam_size, max_tokens, state);
+  const LmStreamState ls = carve_lm_state(*lm, B, beam_size, static_cast<char*>(state) + s.bytes);
+  const Workspace w = carve(d, B, Tc, beam_size, workspace, 1);
+  const LmWorkspace lw = live_lm(carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 1), ls);
+  hipLaunchKernelGGL(beam_chunk_init_kernel, dim3(1), dim3(64), 0, st, w.counts, R);
+  BeamArgs a{joint_args(d, am, Tc, w), chunk_len, s.lm, 0, B, beam_size, cutoff_top_k, 0, w.cscore, s.score,
+             w.ccls, s.blen, s.nb, w.rec, w.emit, w.token, w.parent, w.counts, lw.q[0], lm_weight, lw.cq,
+             lw.lm_sum};
+  const StateBuf buf[2] = {{s.h, s.c, s.lm}, {w.h[0], w.c[0], w.lm[0]}};
+  beam_rounds(d, a, buf, w, Tc, st, lm, &lw);
+  if (Tc & 1) {                                            // the live copies go home
+    const long n_state = (long)d.num_layers * R * d.H, n_lm = (long)R * d.V;
+    const long n_lstate = (long)lm->num_layers * R * lm->H;
+    const CopyHomeArgs c{{w.h[0], w.c[0], w.lm[0], lw.h[1], lw.c[1], lw.q[1]},
+                         {s.h, s.c, s.lm, lw.h[0], lw.c[0], lw.q[0]},
+                         {n_state, n_state, n_lm, n_lstate, n_lstate, n_lm}};
+    enqueue_copy_home(c, st);
+  }
+  BeamEndArgs e{chunk_len, Tc, beam_size, max_tokens, w.rec, s.blen, s.nb, s.score, s.hdr, s.htok, s.hfrm,
+                tokens, frames, out_len, score, stable_len, overflow, lw.lm_sum, lm_score};
+  hipLaunchKernelGGL(beam_chunk_end_kernel, dim3(B), dim3(kThreads), 0, st, e);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+long s2t_rnnt_stateless_lm_stream_state_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, int B,
+                                              int beam_size, int max_tokens) {
+  if (B <= 0 || !lm_stream_ok(stateless_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens)) return 0;
+  return (long)(carve_stateless_state(*desc, B, beam_size, max_tokens, nullptr).bytes +
+                carve_lm_state(*lm, B, beam_size, nullptr).bytes);
+}
+
+long s2t_rnnt_stateless_lm_stream_workspace_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, int B,
+                                                  int Tc, int beam_size) {
+  if (B <= 0 || Tc < 1 || Tc > kMaxChunk || !lm_stream_ok(stateless_ok(desc), desc ? desc->V : 0, lm, beam_size, 1))
+    return 0;
+  return (long)(carve_stateless(*desc, B, Tc, beam_size, nullptr, 1).bytes +
+                carve_lm(*lm, B, beam_size, nullptr, 1).bytes);
+}
+
+int s2t_rnnt_stateless_lm_stream_reset(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm,
+                                       int lm_start_token, void* state, const int* rows, int B, int beam_size,
+                                       int max_tokens, void* workspace, void* stream) {
+  if (B <= 0) return 0;
+  if (!lm_stream_ok(stateless_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens) ||
+      lm_start_token >= desc->V || !state || !workspace)
+    return -1;
+  const S2tRnntStatelessDesc& d = *desc;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = B * beam_size;
+  const StatelessStreamState s = carve_stateless_state(d, B, beam_size, max_tokens, state);
+  const LmStreamState ls = carve_lm_state(*lm, B, beam_size, static_cast<char*>(state) + s.bytes);
+  const StatelessWorkspace w = carve_stateless(d, B, 1, beam_size, workspace, 1);
+  const LmWorkspace lw = carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 1);
+  // (no LSTM layers: the predictor's state is the context, which the LM's reset blanks)
+  ResetArgs a{rows, beam_size, beam_size, 0, 0, nullptr, nullptr, s.score, s.blen, s.nb, s.hdr, nullptr, w.emit,
+              w.token};
+  hipLaunchKernelGGL(stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, a);
+  LmResetArgs la{rows, beam_size, lm->num_layers, lm->H, d.V, d.ctx, lm_start_token, ls.h, ls.c, ls.q, ls.lm_sum,
+                 lw.tok, s.ctx};
+  hipLaunchKernelGGL(lm_stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, la);
+  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, st, w.emit, R, w.counts + 2);
+  enqueue_stateless_step(d, R, w.token, w.emit, nullptr, w.counts + 2, s.ctx, s.lm, s.ctx, s.lm, w, st);
+  if (lm_start_token >= 0)                                 // the LM's first step, as the predictor's on blank
+    enqueue_lm_step(*lm, R, lw.tok, w.emit, nullptr, w.counts + 2, ls.h, ls.c, ls.q, ls.h, ls.c, ls.q, lw, st);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_rnnt_beam_stateless_lm_chunk(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, const float* am,
+                                     const long* chunk_len, int B, int Tc, int beam_size, int cutoff_top_k,
+                                     float lm_weight, int max_tokens, void* state, void* workspace,
+                                     long* tokens, long* frames, long* out_len, float* score, float* lm_score,
+                                     long* stable_len, int* overflow, void* stream) {
+  if (B <= 0) return 0;
+  if (!lm_stream_ok(stateless_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens) || Tc < 1 ||
+      Tc > kMaxChunk || cutoff_top_k < 1 || (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam ||
+      !__builtin_isfinite(lm_weight) || !state || !workspace)
+    return -1;
+  const S2tRnntStatelessDesc& d = *desc;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = B * beam_size;
+  const StatelessStreamState s = carve_stateless_state(d, B, beam_size, max_tokens, state);
+  const LmStreamState ls = carve_lm_state(*lm, B, beam_size, static_cast<char*>(state) + s.bytes);
+  const StatelessWorkspace w = carve_stateless(d, B, Tc, beam_size, workspace, 1);
+  const LmWorkspace lw = live_lm(carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 1), ls);
+  hipLaunchKernelGGL(beam_chunk_init_kernel, dim3(1), dim3(64), 0, st, w.counts, R);
+  BeamArgs a{JointArgs{am, Tc, d.V, d.inner, d.act, d.out1_w, d.out1_b, d.out2_w, d.out2_b, w.z, w.mid, w.logit},
+             chunk_len, s.lm, 0, B, beam_size, cutoff_top_k, 0, w.cscore, s.score, w.ccls, s.blen, s.nb, w.rec,
+             w.emit, w.token, w.parent, w.counts, lw.q[0], lm_weight, lw.cq, lw.lm_sum};
+  int* const ctx[2] = {s.ctx, w.ctx[0]};
+  float* const lm_rows[2] = {s.lm, w.lm[0]};
+  beam_rounds_over(
+      a, lm_rows,
+      [&](int cur, int nxt) {
+        enqueue_stateless_step(d, R, w.token, w.emit, w.parent, w.counts + cur, ctx[cur], lm_rows[cur], ctx[nxt],
+                               lm_rows[nxt], w, st);
+      },
+      Tc, st, lm, &lw);
+  if (Tc & 1) {                                            // the live copies go home
+    const long n_ctx = (long)R * d.ctx, n_lm = (long)R * d.V, n_lstate = (long)lm->num_layers * R * lm->H;
+    const CopyHomeArgs c{{w.ctx[0], w.lm[0], lw.h[1], lw.c[1], lw.q[1], nullptr},
+                         {s.ctx, s.lm, lw.h[0], lw.c[0], lw.q[0], nullptr},
+                         {n_ctx, n_lm, n_lstate, n_lstate, n_lm, 0}};
+    enqueue_copy_home(c, st);
+  }
+  BeamEndArgs e{chunk_len, Tc, beam_size, max_tokens, w.rec, s.blen, s.nb, s.score, s.hdr, s.htok, s.hfrm,
+                tokens, frames, out_len, score, stable_len, overflow, lw.lm_sum, lm_score};
   hipLaunchKernelGGL(beam_chunk_end_kernel, dim3(B), dim3(kThreads), 0, st, e);
   S2T_CHECK_LAUNCH();
   return 0;

@@ -18,7 +18,9 @@ combinations (the stateless predictor with an out-projection joiner, foreign cla
 kernel refuses) keep the module-by-module loop.  RnntBeamDecoding takes an RNN language model
 for shallow fusion (`lm=`, `lm_weight=`): with the LSTM predictor and with the stateless predictor
 (joiner with or without output projection) the LM is stepped inside the lockstep device search
-(s2t_rnnt_beam_lstm_lm, s2t_rnnt_beam_stateless_lm), everything else runs `_module_loop_lm`.  The
+(s2t_rnnt_beam_lstm_lm, s2t_rnnt_beam_stateless_lm), everything else runs `_module_loop_lm`; the
+chunk-carried beam searches take the same LM (RnntLstmStreamingSearch with `lm=`,
+RnntStatelessLmStreamingSearch; s2t_rnnt_beam_lstm_lm_chunk, s2t_rnnt_beam_stateless_lm_chunk).  The
 lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are not here."""
 import abc
 from enum import Enum, unique
@@ -694,6 +696,25 @@ class RnntBeamDecoding(DecodingMethod):
         return self.decode_batch(hidden_states, n)[0]
 
 
+def _stream_lm_arguments(lm, lm_weight, lm_start_token, method):
+    """The LM arguments of a chunk-carried search, checked -> (lm, lm_weight, the C start token)."""
+    import math
+    if lm is None:
+        return None, 0.0, -1
+    from speech2text_amd.model.lm.rnn_lm import RnnLm
+    if method == "greedy":
+        raise ValueError("the greedy searches take no language model: use method='beam' or lm=None")
+    if not isinstance(lm, RnnLm):
+        raise ValueError(f"the chunk-carried search is fused with an RnnLm only, got {type(lm).__name__} "
+                         "(there is no module-loop fallback here)")
+    start = -1 if lm_start_token is None else int(lm_start_token)
+    if lm_start_token is not None and start < 0:
+        raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
+    if not math.isfinite(float(lm_weight)):
+        raise ValueError(f"lm_weight must be finite, got {lm_weight!r}")
+    return lm, float(lm_weight), start
+
+
 class _ChunkCarriedSearch:
     """What the two chunk-carried searches share: the settings, the fixed output tensors, `reset`
     and `step` around the library calls.  A subclass says which modules it takes (`_check_modules`),
@@ -733,7 +754,10 @@ class _ChunkCarriedSearch:
             mask[torch.as_tensor(rows, dtype=torch.int64)] = 1
             mask = mask.to(self.state.device)
         self._reset_state(mask)
-        for t in (self.tokens, self.frames, self.out_len, self.score, self.stable_len, self.overflow):
+        outs = [self.tokens, self.frames, self.out_len, self.score, self.stable_len, self.overflow]
+        if getattr(self, "lm_score", None) is not None:    # (the searches with a language model)
+            outs.append(self.lm_score)
+        for t in outs:
             if mask is None:
                 t.zero_()
             else:
@@ -838,11 +862,24 @@ class RnntLstmStreamingSearch(_ChunkCarriedSearch):
     and stop early (the same bits; a beam step never synchronises either way).  Greedy past
     `max_tokens` drops symbols and sets `overflow` but goes on walking, as the whole-utterance LSTM
     search does.  There is no module-loop fallback: other modules or a shape the kernels refuse are
-    an error at construction."""
+    an error at construction.
+
+    `lm` (an RnnLm) with `method="beam"`: RNN-LM shallow fusion carried across chunks
+    (s2t_rnnt_beam_lstm_lm_chunk): the state buffer also holds the LM's (h, c), q and lm_sum per beam,
+    the result after a chunk is rnnt_beam_lstm_lm_tokens_from_am on the frames fed so far, bit for
+    bit, and `lm_score` (B, fp32) beside `score` is the best beam's unweighted LM sum (`step` returns
+    the same five views; `reset(rows)` zeroes it for those rows and resets their LM state, stepping
+    the LM on `lm_start_token` when one is given).  `lm` None: the object and its calls are exactly
+    those without the argument.  `method="greedy"` with an `lm`, an `lm` that is not an RnnLm, or an
+    LM shape outside the limits is a ValueError: the greedy searches take no LM and there is no
+    module-loop fallback here."""
 
     def __init__(self, predictor, joiner, batch_size=1, method="greedy", max_token_step=5,
-                 beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None, capturable=True):
+                 beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None, capturable=True, lm=None,
+                 lm_weight=0.0, lm_start_token=None):
         self.capturable = bool(capturable)
+        self.lm_score = None
+        self._lm, self._lm_weight, self._lm_start = _stream_lm_arguments(lm, lm_weight, lm_start_token, method)
         super().__init__(predictor, joiner, batch_size, method, max_token_step, beam_size, cutoff_top_k,
                          max_tokens, device)
 
@@ -851,14 +888,22 @@ class RnntLstmStreamingSearch(_ChunkCarriedSearch):
             raise ValueError("RnntLstmStreamingSearch takes LstmPredictor + Joiner, got "
                              f"{type(getattr(predictor, 'predictor', predictor)).__name__} + "
                              f"{type(joiner).__name__} (the stateless predictor: RnntStreamingSearch)")
-        return [joiner._pre_proj.weight, next(predictor.parameters())]
+        return [joiner._pre_proj.weight, next(predictor.parameters())] + \
+            ([] if self._lm is None else [self._lm._embedding.weight])
 
     def _allocate(self, predictor, joiner, dev):
         B, V = self.batch_size, self.V
         self._desc, self._keep = rnnt_lstm_desc(predictor, joiner)
         lib = N.lib()
         n = ws = 0
-        if self._desc is not None and B > 0:
+        self._lm_desc = None
+        if self._lm is not None:
+            self._lm_desc, self._lm_keep = rnn_lm_desc(self._lm)
+            if self._desc is not None and self._lm_desc is not None and B > 0 and self._lm_start < V:
+                n = lib.s2t_rnnt_lstm_lm_stream_state_bytes(self._desc, self._lm_desc, B, self.beam_size,
+                                                            self.max_tokens)
+                ws = lib.s2t_rnnt_lstm_lm_stream_workspace_bytes(self._desc, self._lm_desc, B, 256, self.beam_size)
+        elif self._desc is not None and B > 0:
             n = lib.s2t_rnnt_lstm_stream_state_bytes(self._desc, B, self.beam_size, self.max_tokens)
             ws = lib.s2t_rnnt_lstm_stream_workspace_bytes(self._desc, B, 256, self.beam_size)
         if self.method == "beam":
@@ -869,11 +914,20 @@ class RnntLstmStreamingSearch(_ChunkCarriedSearch):
         if n <= 0 or ws <= 0 or not ok:
             raise ValueError(f"the chunk-carried LSTM {self.method} search does not take this shape: B {B} V {V} "
                              f"beam {self.beam_size} top-k {self.cutoff_top_k} max_token_step "
-                             f"{self.max_token_step} max_tokens {self.max_tokens} (limits: include/s2t_mi355.h)")
+                             f"{self.max_token_step} max_tokens {self.max_tokens}"
+                             + ("" if self._lm is None else f", with an LM of V {self._lm._num_symbols} "
+                                f"start token {self._lm_start}") + " (limits: include/s2t_mi355.h)")
         self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
         self._ws = torch.zeros((ws,), dtype=torch.uint8, device=dev)
+        if self._lm is not None:
+            self.lm_score = torch.zeros((B,), dtype=torch.float32, device=dev)
 
     def _reset_state(self, mask):
+        if self._lm is not None:
+            N.check(N.lib().s2t_rnnt_lstm_lm_stream_reset(
+                self._desc, self._lm_desc, self._lm_start, N.ptr(self.state), N.ip(mask), self.batch_size,
+                self.beam_size, self.max_tokens, N.ptr(self._ws), N.stream()), "s2t_rnnt_lstm_lm_stream_reset")
+            return
         N.check(N.lib().s2t_rnnt_lstm_stream_reset(self._desc, N.ptr(self.state), N.ip(mask), self.batch_size,
                                                    self.beam_size, self.max_tokens, N.ptr(self._ws), N.stream()),
                 "s2t_rnnt_lstm_stream_reset")
@@ -886,6 +940,13 @@ class RnntLstmStreamingSearch(_ChunkCarriedSearch):
                 0 if self.capturable else 1, N.ptr(self.state), N.ptr(self._ws), N.lp(self.tokens),
                 N.lp(self.out_len), N.ip(self.overflow), N.stream()), "s2t_rnnt_greedy_lstm_chunk")
             return
+        if self._lm is not None:
+            N.check(N.lib().s2t_rnnt_beam_lstm_lm_chunk(
+                self._desc, self._lm_desc, N.fp(am_chunk), N.lp(chunk_len), B, Tc, self.beam_size,
+                self.cutoff_top_k, self._lm_weight, self.max_tokens, N.ptr(self.state), N.ptr(self._ws),
+                N.lp(self.tokens), N.lp(self.frames), N.lp(self.out_len), N.fp(self.score), N.fp(self.lm_score),
+                N.lp(self.stable_len), N.ip(self.overflow), N.stream()), "s2t_rnnt_beam_lstm_lm_chunk")
+            return
         N.check(N.lib().s2t_rnnt_beam_lstm_chunk(
             self._desc, N.fp(am_chunk), N.lp(chunk_len), B, Tc, self.beam_size, self.cutoff_top_k,
             self.max_tokens, N.ptr(self.state), N.ptr(self._ws), N.lp(self.tokens), N.lp(self.frames),
@@ -893,13 +954,86 @@ class RnntLstmStreamingSearch(_ChunkCarriedSearch):
             "s2t_rnnt_beam_lstm_chunk")
 
 
+class RnntStatelessLmStreamingSearch(_ChunkCarriedSearch):
+    """The chunk-carried beam search of StatelessPredictor + Joiner (with or without output projection)
+    + RnnLm on the lockstep rounds of csrc/decode_lstm.hip (s2t_rnnt_beam_stateless_lm_chunk): however
+    the frames are cut, the result after a chunk is rnnt_beam_stateless_lm_tokens_from_am on the frames
+    fed so far, bit for bit.  This is the ONLY chunk-carried search of the stateless predictor with an
+    out-projection joiner, and it needs an LM: the lockstep rounds over this predictor exist as the
+    fused search alone (without an LM and without out-projection: RnntStreamingSearch, on the
+    one-workgroup kernels).
+
+    Same surface as RnntLstmStreamingSearch with an `lm`: `state`, `tokens`, `frames`, `out_len`,
+    `score`, `lm_score`, `stable_len`, `overflow`, `reset(rows)`, `step(am_chunk, chunk_len)` returning
+    the five beam views without a host synchronisation, so a step can be captured into a graph.  Beam
+    only.  Other modules, `method="greedy"`, a missing or foreign `lm`, or a shape the kernels refuse
+    are a ValueError at construction; modules off the GPU a RuntimeError.  No module-loop fallback."""
+
+    def __init__(self, predictor, joiner, batch_size=1, method="beam", max_token_step=5, beam_size=4,
+                 cutoff_top_k=4, max_tokens=1024, device=None, lm=None, lm_weight=0.0, lm_start_token=None):
+        if lm is None:
+            raise ValueError("RnntStatelessLmStreamingSearch needs an lm (without one: RnntStreamingSearch)")
+        self.lm_score = None
+        self._lm, self._lm_weight, self._lm_start = _stream_lm_arguments(lm, lm_weight, lm_start_token, method)
+        super().__init__(predictor, joiner, batch_size, method, max_token_step, beam_size, cutoff_top_k,
+                         max_tokens, device)
+
+    def _check_modules(self, predictor, joiner):
+        if not _is_stateless_pair(predictor, joiner):
+            raise ValueError("RnntStatelessLmStreamingSearch takes StatelessPredictor + Joiner, got "
+                             f"{type(getattr(predictor, 'predictor', predictor)).__name__} + "
+                             f"{type(joiner).__name__} (the LSTM predictor: RnntLstmStreamingSearch)")
+        return [joiner._pre_proj.weight, getattr(predictor, "predictor", predictor)._embedding.weight,
+                self._lm._embedding.weight]
+
+    def _allocate(self, predictor, joiner, dev):
+        B, V = self.batch_size, self.V
+        self._desc, self._keep = rnnt_stateless_desc(predictor, joiner)
+        self._lm_desc, self._lm_keep = rnn_lm_desc(self._lm)
+        lib = N.lib()
+        n = ws = 0
+        if self._desc is not None and self._lm_desc is not None and B > 0 and self._lm_start < V:
+            n = lib.s2t_rnnt_stateless_lm_stream_state_bytes(self._desc, self._lm_desc, B, self.beam_size,
+                                                             self.max_tokens)
+            ws = lib.s2t_rnnt_stateless_lm_stream_workspace_bytes(self._desc, self._lm_desc, B, 256, self.beam_size)
+        if n <= 0 or ws <= 0 or not 1 <= min(self.cutoff_top_k, V) <= N.const("S2T_RNNT_LSTM_MAX_BEAM"):
+            raise ValueError(f"the chunk-carried stateless beam search with an LM does not take this shape: B {B} "
+                             f"V {V} beam {self.beam_size} top-k {self.cutoff_top_k} max_tokens {self.max_tokens}, "
+                             f"LM V {self._lm._num_symbols} start token {self._lm_start} "
+                             "(limits: include/s2t_mi355.h)")
+        self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        self._ws = torch.zeros((ws,), dtype=torch.uint8, device=dev)
+        self.lm_score = torch.zeros((B,), dtype=torch.float32, device=dev)
+
+    def _reset_state(self, mask):
+        N.check(N.lib().s2t_rnnt_stateless_lm_stream_reset(
+            self._desc, self._lm_desc, self._lm_start, N.ptr(self.state), N.ip(mask), self.batch_size,
+            self.beam_size, self.max_tokens, N.ptr(self._ws), N.stream()), "s2t_rnnt_stateless_lm_stream_reset")
+
+    def _chunk(self, am_chunk, chunk_len, Tc):
+        N.check(N.lib().s2t_rnnt_beam_stateless_lm_chunk(
+            self._desc, self._lm_desc, N.fp(am_chunk), N.lp(chunk_len), self.batch_size, Tc, self.beam_size,
+            self.cutoff_top_k, self._lm_weight, self.max_tokens, N.ptr(self.state), N.ptr(self._ws),
+            N.lp(self.tokens), N.lp(self.frames), N.lp(self.out_len), N.fp(self.score), N.fp(self.lm_score),
+            N.lp(self.stable_len), N.ip(self.overflow), N.stream()), "s2t_rnnt_beam_stateless_lm_chunk")
+
+
 def rnnt_streaming_search(predictor, joiner, batch_size=1, method="greedy", max_token_step=5, beam_size=4,
-                          cutoff_top_k=4, max_tokens=1024, device=None, **kw):
+                          cutoff_top_k=4, max_tokens=1024, device=None, lm=None, lm_weight=0.0,
+                          lm_start_token=None, **kw):
     """The chunk-carried search that serves the pair: RnntLstmStreamingSearch for LstmPredictor +
-    Joiner (kw: capturable), RnntStreamingSearch otherwise (which raises for what it does not take)."""
+    Joiner (kw: capturable), with or without an `lm`; for the stateless predictor
+    RnntStatelessLmStreamingSearch with an `lm` (joiner with or without output projection) and
+    RnntStreamingSearch without one (which raises for what it does not take)."""
     if _is_lstm_pair(predictor, joiner):
+        if lm is not None:
+            kw.update(lm=lm, lm_weight=lm_weight, lm_start_token=lm_start_token)
         return RnntLstmStreamingSearch(predictor, joiner, batch_size, method, max_token_step, beam_size,
                                        cutoff_top_k, max_tokens, device, **kw)
+    if lm is not None:
+        return RnntStatelessLmStreamingSearch(predictor, joiner, batch_size, method, max_token_step, beam_size,
+                                              cutoff_top_k, max_tokens, device, lm=lm, lm_weight=lm_weight,
+                                              lm_start_token=lm_start_token, **kw)
     return RnntStreamingSearch(predictor, joiner, batch_size, method, max_token_step, beam_size,
                                cutoff_top_k, max_tokens, device, **kw)
 

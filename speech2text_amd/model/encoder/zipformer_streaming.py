@@ -295,11 +295,15 @@ class StreamingRecognizer:
     consume or clone them before the next step.  The search is RnntStreamingSearch for the stateless
     predictor and a joiner without output projection, RnntLstmStreamingSearch (capturable: every
     greedy round enqueued) for the LSTM predictor and a joiner with or without one; any other pair
-    is an error: there is no module-loop fallback."""
+    is an error: there is no module-loop fallback.  With `lm` (an RnnLm; beam only) the graph captures
+    the chunk call fused with the LM (`lm_weight`, `lm_start_token` as RnntBeamDecoding's): the LSTM
+    pair through RnntLstmStreamingSearch, the stateless predictor with either joiner through
+    RnntStatelessLmStreamingSearch; `search.lm_score` holds the best beams' unweighted LM sums."""
 
     def __init__(self, encoder, predictor, joiner, tokenizer, cmvn=None, batch_size: int = 1,
                  method: str = "greedy", max_token_step: int = 5, beam_size: int = 4,
-                 cutoff_top_k: int = 4, max_tokens: int = 1024, device=None, warmup: int = 2):
+                 cutoff_top_k: int = 4, max_tokens: int = 1024, device=None, warmup: int = 2,
+                 lm=None, lm_weight: float = 0.0, lm_start_token=None):
         from speech2text_amd.model.decoding import rnnt_streaming_search
         model = getattr(encoder, "encoder", encoder)
         if model.training or getattr(predictor, "training", False) or getattr(joiner, "training", False):
@@ -316,8 +320,11 @@ class StreamingRecognizer:
         self.model, self.joiner, self.tokenizer = model, joiner, tokenizer
         self.batch_size, self.chunk, self.Tc = batch_size, chunk, chunk // 2
         self.frames = 2 * chunk + 13
+        if lm is not None and hasattr(lm, "to"):           # (a frozen LM follows the model to its device)
+            lm = lm.to(device)
         self.search = rnnt_streaming_search(predictor, joiner, batch_size, method, max_token_step,
-                                            beam_size, cutoff_top_k, max_tokens, device)
+                                            beam_size, cutoff_top_k, max_tokens, device, lm=lm,
+                                            lm_weight=lm_weight, lm_start_token=lm_start_token)
         self.x = torch.zeros(batch_size, self.frames, model._feature_dim, device=device)
         self.chunk_len = torch.full((batch_size,), self.Tc, dtype=torch.int64, device=device)
         self.states = get_init_states(model, batch_size, device)

@@ -202,7 +202,10 @@ class PrunedRnntTask(BaseRnntTask):
         `metric:` section when not given.  The task must be on the GPU and in eval mode; its decoder
         must be the identity (the search reads the encoder output through joiner._enc_proj).  The
         search is the one that serves the task's predictor (model/decoding.py rnnt_streaming_search):
-        stateless with a projection-free joiner, or `predictor.model: Lstm` with either joiner."""
+        stateless with a projection-free joiner, or `predictor.model: Lstm` with either joiner.  With
+        `metric.lm` and the beam method the search is shallow-fused with that LM (`metric.lm_weight`,
+        `metric.lm_start_token`), as the validation search is; the stateless predictor then takes
+        either joiner."""
         from speech2text_amd.model.decoder.decoder import Identity
         from speech2text_amd.model.encoder.zipformer_streaming import StreamingRecognizer
         from speech2text_amd.model.utils import AsrMetricConfig
@@ -217,5 +220,11 @@ class PrunedRnntTask(BaseRnntTask):
                 raise ValueError(f"metric decode_method {cfg.decode_method!r} names no RNN-T search: pass method=")
         for k in ("max_token_step", "beam_size", "cutoff_top_k"):
             kw.setdefault(k, getattr(cfg, k))
+        if method == "beam" and "lm" not in kw:            # the LM the validation search is fused with
+            lm = self._metric_lm()
+            if lm is not None:
+                kw["lm"] = lm
+                kw.setdefault("lm_weight", cfg.lm_weight)
+                kw.setdefault("lm_start_token", cfg.lm_start_token)
         return StreamingRecognizer(self._encoder, self._predictor, self._joiner, self._tokenizer,
                                    cmvn=self._global_cmvn, batch_size=batch_size, method=method, **kw)

@@ -1,0 +1,623 @@
+"""GPU: the chunk-carried RNN-T beam search with RNN-LM shallow fusion (csrc/decode_lstm.hip
+s2t_rnnt_beam_lstm_lm_chunk, s2t_rnnt_beam_stateless_lm_chunk and their reset / size functions;
+model/decoding.py RnntLstmStreamingSearch with an `lm`, RnntStatelessLmStreamingSearch), the
+StreamingRecognizer graph around it and PrunedRnntTask.streaming_recognizer with `metric.lm`.
+
+The yardstick is exact: however [0, L) is cut into chunks, tokens, frames, out_len, score and lm_score
+are those of the one-shot fused device calls (rnnt_beam_lstm_lm_tokens_from_am /
+rnnt_beam_stateless_lm_tokens_from_am, themselves held to the float64 restatement by
+tests/test_gpu_rnnt_lm_fusion.py and tests/test_gpu_rnnt_stateless_lm.py) on the concatenated am, bit for
+bit -- torch.equal, no tolerance -- and the tokens and frames are the float64 restatement's
+(tests/rnnt_lm_stream_cases.py: no exclusions).  `stable_len` is held to the float64 chunked
+restatement of tests/rnnt_lm_stream_f64.py on every utterance of the four 40-frame cases."""
+import copy
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import rnnt_lm_stream_cases as K
+import rnnt_lstm_stream_cases as SC
+import test_gpu_rnnt_lm_fusion as GF
+import test_gpu_rnnt_lstm_search as LS
+import test_gpu_rnnt_lstm_stream as LT
+import test_gpu_rnnt_stateless_lm as GS
+import test_gpu_rnnt_stream_search as SS
+import test_rnnt_beam as TB
+
+pytestmark = pytest.mark.gpu
+
+_plan = LT._plan
+
+
+# ------------------------------------------------------------------------------------ helpers
+@functools.lru_cache(maxsize=None)
+def _case(dev, name):
+    """(predictor, joiner, LM, am and lengths on the device), built once per case."""
+    w, act, am, lens, sd = K.make(name)
+    c = K.CASES[name]
+    if K.is_lstm(name):
+        p, j = LS._modules(dev, w, SC.CASES[c["base"]]["model"])
+    else:
+        p, j = GS._modules(dev, w, c)
+    return p, j, GF._lm_module(dev, sd), am.to(dev), lens.to(dev)
+
+
+def _lens(name):
+    return np.asarray(K.lengths(name), dtype=np.int64)
+
+
+def _fused(dev, name, am, lens, **kw):
+    """The one-shot fused device search of the case's family at the case's settings."""
+    from speech2text_amd.model.decoding import rnnt_beam_lstm_lm_tokens_from_am, rnnt_beam_stateless_lm_tokens_from_am
+    p, j, lm = _case(dev, name)[:3]
+    beam, topk, weight, start, _ = K.settings(name)
+    args = dict(lm_weight=weight, beam_size=beam, cutoff_top_k=topk, lm_start_token=start)
+    args.update(kw)
+    fn = rnnt_beam_lstm_lm_tokens_from_am if K.is_lstm(name) else rnnt_beam_stateless_lm_tokens_from_am
+    out = fn(am, torch.as_tensor(lens), p, j, lm, **args)
+    assert out is not None
+    return [x.cpu() for x in out]
+
+
+@functools.lru_cache(maxsize=None)
+def _one_shot(dev, name):
+    """The one-shot fused search on a case: computed once, shared, left unchanged."""
+    return _fused(dev, name, *_case(dev, name)[3:5])
+
+
+def _stream(dev, name, B=None, max_tokens=None, **kw):
+    from speech2text_amd.model.decoding import RnntLstmStreamingSearch, RnntStatelessLmStreamingSearch
+    p, j, lm, am, _ = _case(dev, name)
+    beam, topk, weight, start, T = K.settings(name)
+    args = dict(beam_size=beam, cutoff_top_k=topk, max_tokens=T if max_tokens is None else max_tokens, device=dev,
+                lm=lm, lm_weight=weight, lm_start_token=start)
+    args.update(kw)
+    cls = RnntLstmStreamingSearch if K.is_lstm(name) else RnntStatelessLmStreamingSearch
+    return cls(p, j, am.shape[0] if B is None else B, "beam", **args)
+
+
+def _same(got, lm_score, want, rows=None):
+    """SS._same_rows on tokens / frames / out_len / score, torch.equal on lm_score."""
+    SS._same_rows(got, want, rows)
+    rows = range(len(lm_score)) if rows is None else rows
+    for b in rows:
+        assert torch.equal(lm_score[b], want[4][b]), (b, float(lm_score[b]), float(want[4][b]))
+
+
+def _feed(search, am, plan, snap=None, off=None):
+    """SS._feed; the snapshots and the result carry lm_score as a sixth tensor."""
+    wrap = None if snap is None else (lambda o, out: snap(o, out + [search.lm_score.cpu().clone()]))
+    got, off = SS._feed(search, am, plan, snap=wrap, off=off)
+    return got + [search.lm_score.cpu().clone()], off
+
+
+# ------------------------------------------------------------------------------------ 1. any cut
+@pytest.mark.parametrize("partition", K.PARTITIONS)
+@pytest.mark.parametrize("name", list(K.CASES))
+def test_chunks_equal_the_one_shot_fused_search(dev, name, partition):
+    """Both families; B 33 and B 17 cross the 16-row tile; "irregular": per-row sizes 0..16 with one call
+    that idles every row."""
+    am = _case(dev, name)[3]
+    want, ref = _one_shot(dev, name), K.reference(name)
+    search = _stream(dev, name)
+    got, off = _feed(search, am, _plan(_lens(name), partition, len(name)))
+    assert off.tolist() == _lens(name).tolist()
+    _same(got, got[5], want)
+    for b, (tok, _, _, frm, _) in enumerate(ref):
+        n = int(got[2][b])
+        assert got[0][b, :n].tolist() == tok and got[1][b, :n].tolist() == frm, b   # the float64 restatement's
+    assert int(search.overflow.sum()) == 0
+
+
+# ------------------------------------------------------------------------------------ 2. prefix answer
+@functools.lru_cache(maxsize=None)
+def _run7(dev, name):
+    """The 7-frame partition of a case with the outputs after every chunk."""
+    snaps = []
+    _feed(_stream(dev, name), _case(dev, name)[3], SS._regular(_lens(name), 7),
+          snap=lambda off, out: snaps.append((off, out)))
+    return snaps
+
+
+@pytest.mark.parametrize("name", K.STREAM_CASES + ["f_yaml"])
+def test_every_chunk_gives_the_prefix_answer(dev, name):
+    am = _case(dev, name)[3]
+    snaps = _run7(dev, name)
+    assert len(snaps) >= 2
+    for off, out in snaps:
+        _same(out, out[5], _fused(dev, name, am, off))
+
+
+# ------------------------------------------------------------------------------------ 3. 90 frames
+@pytest.mark.parametrize("name", K.LONG_CASES)
+def test_long_chunks_cross_the_trace_blocks(dev, name):
+    """90-frame rows: the one-shot trace-back and the chunk end both stage their records in blocks of 64
+    frames; the best beams emit on both sides of both block edges."""
+    am = _case(dev, name)[3]
+    want = _one_shot(dev, name)
+    for b, (tok, _, _, frm, _) in enumerate(K.reference(name)):
+        n = int(want[2][b])
+        assert want[0][b, :n].tolist() == tok and want[1][b, :n].tolist() == frm, b
+    stable = []
+    for step in (16, 1):
+        search = _stream(dev, name)
+        got, off = _feed(search, am, SS._regular(_lens(name), step))
+        assert off.tolist() == _lens(name).tolist()
+        _same(got, got[5], want)
+        assert int(search.overflow.sum()) == 0
+        stable.append(got[4].tolist())
+    assert stable[0] == stable[1], stable
+
+
+# ------------------------------------------------------------------------------------ 4. stable_len
+@pytest.mark.parametrize("name", K.STREAM_CASES + ["f_h20_beam1_k1", "s_b1_ctx1_beam1_k1"])
+def test_stable_len(dev, name):
+    """stable_len never decreases; tokens[:stable_len] is a prefix of every later result; with one beam it
+    is out_len; on every utterance of the four 40-frame cases it is the float64 chunked restatement's
+    common-prefix length at every boundary of the 7-frame cut."""
+    snaps = _run7(dev, name)
+    lens = _lens(name)
+    for b in range(len(lens)):
+        n = int(lens[b])
+        mine = [(out[0][b], int(out[2][b]), int(out[4][b])) for _, out in snaps[:-(-n // 7)]]
+        stable = [m[2] for m in mine]
+        assert stable == sorted(stable) and (not mine or stable[-1] <= mine[-1][1]), b
+        for k, (tok, _, st) in enumerate(mine):
+            for tok2, n2, _ in mine[k:]:
+                assert n2 >= st and torch.equal(tok2[:st], tok[:st]), (b, k)
+        if name in K.STREAM_CASES:
+            assert stable == K.chunked(name, b, "7")[5], (b, stable, K.chunked(name, b, "7")[5])
+    if K.settings(name)[0] == 1:
+        assert all(torch.equal(out[4], out[2]) for _, out in snaps) and int(snaps[-1][1][2].sum()) > 0
+    else:
+        assert any(0 < int(out[4][b]) < int(out[2][b]) for _, out in snaps for b in range(len(lens)))
+
+
+# ------------------------------------------------------------------------------------ 5. rows, reset
+def _utterance_mask(dev, name, B, beam, max_tokens, nbytes, b):
+    """The bytes of the state buffer that belong to utterance b, by the layout include/s2t_mi355.h
+    documents: every array 256-byte aligned, [outer][R or B][elements] of 4 bytes."""
+    p, j, lm = _case(dev, name)[:3]
+    c, R = K.CASES[name], B * beam
+    V, hist = j._output_dim, 2 * beam * max_tokens
+    st = lm._rnn_layer
+    if K.is_lstm(name):
+        q = p.predictor._predictor
+        L, H = len(q.lstm_layers), q.lstm_layers[0].hidden_dim
+        arrays = [(L, R, H), (L, R, H), (1, R, V)]
+    else:
+        arrays = [(1, R, c["ctx"]), (1, R, V)]
+    arrays += [(1, B, 4), (1, R, 1), (1, R, 1), (1, B, 1), (1, B, hist), (1, B, hist),
+               (st.num_layers, R, st.hidden_size), (st.num_layers, R, st.hidden_size), (1, R, V), (1, R, 1)]
+    mask, off = torch.zeros(nbytes, dtype=torch.bool), 0
+    for outer, rows, n in arrays:
+        per = rows // B                                     # rows of one utterance
+        for o in range(outer):
+            lo = off + 4 * n * (o * rows + b * per)
+            mask[lo:lo + 4 * n * per] = True
+        off += -(-4 * outer * rows * n // 256) * 256
+    assert off == nbytes, (off, nbytes)                    # the documented layout is the whole buffer
+    return mask
+
+
+@pytest.mark.parametrize("start", [None, "token"])
+@pytest.mark.parametrize("name", ["fs_h64o_t40", "ss_inner_t40"])
+def test_rows_are_independent_and_reset_alone(dev, name, start):
+    """Rows 0..3 run utterance A; row 2 is reset midway by the row mask and fed utterance B.  The reset
+    changes no byte of the other rows' state; rows 0, 1, 3 end bit-identical, outputs and state bytes, to
+    a run without the reset; row 2 ends at B's one-shot answer.  With and without a start token: a reset
+    that forgot the LM's state, its q, lm_sum or its first step would end row 2 elsewhere."""
+    am_c = _case(dev, name)[3]
+    beam, V = K.settings(name)[0], am_c.shape[2]
+    kw = {} if start is None else dict(lm_start_token=V - 1)
+    lens = _lens(name)
+    want = _one_shot(dev, name) if start is None else _fused(dev, name, am_c, lens, **kw)
+    la, lb = int(lens[0]), int(lens[3])
+    assert lb > 0 and int(want[2][0]) > 0 and int(want[2][3]) > 0
+    am = torch.stack([am_c[0]] * 4)
+    plain_search = _stream(dev, name, B=4, **kw)
+    plain, _ = _feed(plain_search, am, SS._regular([la] * 4, 16))
+    _same(plain, plain[5], [x[[0, 0, 0, 0]] for x in want])
+
+    search = _stream(dev, name, B=4, **kw)
+    plan = SS._regular([la] * 4, 16)
+    half = len(plan) // 2
+    _, off = _feed(search, am, plan[:half])
+    assert int(search.out_len[2]) > 0 and float(search.lm_score[2]) != 0.0
+    before = search.state.cpu().clone()
+    search.reset([2])
+    torch.cuda.synchronize()
+    assert search.out_len.tolist()[2] == 0 and float(search.lm_score[2]) == 0.0 and int(search.out_len[1]) > 0
+    after = search.state.cpu()
+    mine = _utterance_mask(dev, name, 4, beam, search.max_tokens, after.numel(), 2)
+    assert torch.equal(after[~mine], before[~mine]) and not torch.equal(after[mine], before[mine])
+    am2 = am.clone()
+    am2[2] = am_c[3]
+    off[2] = 0
+    rest = [np.array([q[0], q[1], 0, q[3]]) for q in plan[half:]]
+    for k, cl in enumerate(SS._regular([lb], 16)):                     # B rides along from its frame 0
+        if k < len(rest):
+            rest[k][2] = cl[0]
+        else:
+            rest.append(np.array([0, 0, cl[0], 0]))
+    got, off = _feed(search, am2, rest, off=off)
+    assert off.tolist() == [la, la, lb, la]
+    for x, y in zip(got, plain):
+        assert torch.equal(x[[0, 1, 3]], y[[0, 1, 3]])
+    a, b = search.state.cpu(), plain_search.state.cpu()
+    for r in (0, 1, 3):
+        m = _utterance_mask(dev, name, 4, beam, search.max_tokens, a.numel(), r)
+        assert torch.equal(a[m], b[m]), r
+    _same([x[2:3] for x in got], got[5][2:3], [x[3:4] for x in want])
+    if start is None:
+        ref = K.reference(name)[3]
+        n = int(got[2][2])
+        assert got[0][2, :n].tolist() == ref[0] and got[1][2, :n].tolist() == ref[3]
+
+
+# ------------------------------------------------------------------------------------ 6. idle call
+@pytest.mark.parametrize("name", ["fs_h20_t40", "ss_t40"])
+def test_idle_call_changes_nothing(dev, name):
+    am = _case(dev, name)[3]
+    want = _one_shot(dev, name)
+    search = _stream(dev, name)
+    plan = SS._regular(_lens(name), 7)
+    _, off = _feed(search, am, plan[:3])
+    assert int(search.out_len.sum()) > 0 and float(search.lm_score.abs().sum()) > 0
+    outs = (search.state, search.tokens, search.frames, search.out_len, search.score, search.lm_score,
+            search.stable_len, search.overflow)
+    for Tc in (7, 16):                                                  # an odd and an even number of rounds
+        before = [x.clone() for x in outs]
+        search.step(am[:, :Tc].contiguous(), torch.zeros(am.shape[0], dtype=torch.int64, device=dev))
+        torch.cuda.synchronize()
+        for x, y in zip(outs, before):
+            assert torch.equal(x, y), Tc
+    got, off = _feed(search, am, plan[3:], off=off)
+    _same(got, got[5], want)
+
+
+# ------------------------------------------------------------------------------------ 7. capacity
+@pytest.mark.parametrize("name", ["fs_h64o_t40", "ss_inner_t40"])
+def test_capacity(dev, name):
+    """max_tokens = 3 on utterances with more than 3 tokens: the first 3 tokens, out_len 3, overflow 1;
+    the search itself went on exactly -- score and lm_score are the one-shot call's, bit for bit; reset
+    clears overflow."""
+    am = _case(dev, name)[3]
+    want = _one_shot(dev, name)
+    rows = [b for b in range(am.shape[0]) if int(want[2][b]) > 3]
+    assert len(rows) >= 2, (name, want[2].tolist())
+    search = _stream(dev, name, B=len(rows), max_tokens=3)
+    lens = _lens(name)[rows]
+    got, _ = _feed(search, am[rows].contiguous(), SS._regular(lens, 7))
+    assert got[2].tolist() == [3] * len(rows) and search.overflow.tolist() == [1] * len(rows)
+    assert torch.equal(got[0], want[0][rows, :3]) and torch.equal(got[1], want[1][rows, :3])
+    assert torch.equal(got[3], want[3][rows]) and torch.equal(got[5], want[4][rows])
+    assert int(got[4].max()) <= 3
+    search.reset()
+    torch.cuda.synchronize()
+    assert search.overflow.tolist() == [0] * len(rows) and search.out_len.tolist() == [0] * len(rows)
+    assert search.lm_score.tolist() == [0.0] * len(rows)
+    _feed(search, am[rows].contiguous(), SS._regular(lens, 1)[:1])
+    assert search.overflow.tolist() == [0] * len(rows)                  # one frame: at most one token
+
+
+# ------------------------------------------------------------------------------------ 8. odd and even Tc
+@pytest.mark.parametrize("name", K.STREAM_CASES)
+def test_alternating_odd_and_even_chunks(dev, name):
+    """Chunks of 3 and 4 frames in turn: the copy-home launch and its absence."""
+    am = _case(dev, name)[3]
+    lens = _lens(name)
+    plan, done = [], np.zeros_like(lens)
+    while (done < lens).any():
+        cl = np.clip(lens - done, 0, 3 if len(plan) % 2 == 0 else 4)
+        plan.append(cl)
+        done = done + cl
+    search = _stream(dev, name)
+    got, off = _feed(search, am, plan)
+    assert off.tolist() == lens.tolist() and {int(p.max()) for p in plan} >= {3, 4}
+    _same(got, got[5], _one_shot(dev, name))
+
+
+# ------------------------------------------------------------------------------------ 9. lm_weight == 0
+@pytest.mark.parametrize("name", list(K.LSTM_STREAM))
+def test_weight_zero_gives_the_bits_of_the_search_without_an_lm(dev, name):
+    from speech2text_amd.model.decoding import RnntLstmStreamingSearch
+    p, j, lm, am, _ = _case(dev, name)
+    beam, topk, _, _, T = K.settings(name)
+    plain = RnntLstmStreamingSearch(p, j, am.shape[0], "beam", beam_size=beam, cutoff_top_k=topk, max_tokens=T,
+                                    device=dev)
+    assert plain.lm_score is None
+    fused = _stream(dev, name, lm_weight=0.0)
+    a, b = [], []
+    plan = SS._regular(_lens(name), 7)
+    SS._feed(plain, am, plan, snap=lambda off, out: a.append(out + [plain.overflow.cpu().clone()]))
+    SS._feed(fused, am, plan, snap=lambda off, out: b.append(out + [fused.overflow.cpu().clone()]))
+    assert len(a) == len(b) == len(plan)
+    for x, y in zip(a, b):
+        for u, v in zip(x, y):                             # tokens, frames, out_len, score, stable_len, overflow
+            assert torch.equal(u, v)
+    assert float(fused.lm_score.abs().sum()) > 0           # (the LM still rides along)
+
+
+# ------------------------------------------------------------------------------------ 10. refusals
+@pytest.mark.parametrize("family", ["lstm", "stateless"])
+def test_refusals(dev, family):
+    """-1 before any launch, every output, the state and the workspace untouched."""
+    from speech2text_amd import _native as N
+    from speech2text_amd.model.decoding import rnn_lm_desc, rnnt_lstm_desc, rnnt_stateless_desc
+    lib = N.lib()
+    V, B, MT = 16, 2, 10
+    if family == "lstm":
+        p, j = LS._build(dev, **LS._TINY)
+        desc, keep = rnnt_lstm_desc(p, j)
+        bad, keep_bad = rnnt_lstm_desc(p, j)
+        keep_bad[-1].H = 1028
+    else:
+        p, j = GS._build(dev, V, 8, 8, 2, inner=8)
+        desc, keep = rnnt_stateless_desc(p, j)
+        bad, keep_bad = rnnt_stateless_desc(p, j)
+        keep_bad[-1].ctx = 65
+    lm = GF._lm_module(dev, V=V, H=8, layers=1)
+    lmd, lm_keep = rnn_lm_desc(lm)
+    bad_lm, bad_lm_keep = rnn_lm_desc(lm)
+    bad_lm_keep[-1].H = 1028
+    other_v, other_keep = rnn_lm_desc(GF._lm_module(dev, V=V + 1, H=8, layers=1))
+    fam = family
+    state_bytes = getattr(lib, f"s2t_rnnt_{fam}_lm_stream_state_bytes")
+    ws_bytes = getattr(lib, f"s2t_rnnt_{fam}_lm_stream_workspace_bytes")
+    reset_fn = getattr(lib, f"s2t_rnnt_{fam}_lm_stream_reset")
+    chunk_fn = getattr(lib, f"s2t_rnnt_beam_{fam}_lm_chunk")
+    assert state_bytes(desc, lmd, B, 16, MT) > state_bytes(desc, lmd, B, 1, MT) > 0
+    assert state_bytes(desc, lmd, B, 16, 2 * MT) > state_bytes(desc, lmd, B, 16, MT)
+    if family == "lstm":                                    # the LM's arrays come on top of the plain state
+        assert state_bytes(desc, lmd, B, 4, MT) > lib.s2t_rnnt_lstm_stream_state_bytes(desc, B, 4, MT)
+        assert ws_bytes(desc, lmd, B, 7, 4) > lib.s2t_rnnt_lstm_stream_workspace_bytes(desc, B, 7, 4)
+    for args in ((B, 17, MT), (B, 0, MT), (B, 4, 0), (0, 4, MT)):
+        assert state_bytes(desc, lmd, *args) == 0, args
+    for d, l in ((bad, lmd), (desc, bad_lm), (desc, other_v), (desc, None), (None, lmd)):
+        assert state_bytes(d, l, B, 4, MT) == 0 and ws_bytes(d, l, B, 4, 4) == 0
+    for args in ((B, 0, 4), (B, 257, 4), (B, 4, 17), (B, 4, 0), (0, 4, 4)):
+        assert ws_bytes(desc, lmd, *args) == 0, args
+    state = torch.zeros(state_bytes(desc, lmd, B, 16, MT), dtype=torch.uint8, device=dev)
+    ws = torch.zeros(ws_bytes(desc, lmd, B, 256, 16), dtype=torch.uint8, device=dev)
+    am, cl = torch.zeros(B, 257, V, device=dev), torch.ones(B, dtype=torch.int64, device=dev)
+    tok, frm = (torch.full((B, MT), 7, dtype=torch.int64, device=dev) for _ in range(2))
+    n_out, stable = (torch.full((B,), 7, dtype=torch.int64, device=dev) for _ in range(2))
+    score, lm_score = torch.full((B,), 7.0, device=dev), torch.full((B,), 7.0, device=dev)
+    ovf = torch.full((B,), 7, dtype=torch.int32, device=dev)
+
+    def chunk(d=desc, l=lmd, Tc=4, beam_size=4, topk=4, weight=0.3, mt=MT, st=state, w=ws, nb=B):
+        return chunk_fn(d, l, N.fp(am), N.lp(cl), nb, Tc, beam_size, topk, weight, mt, N.ptr(st), N.ptr(w),
+                        N.lp(tok), N.lp(frm), N.lp(n_out), N.fp(score), N.fp(lm_score), N.lp(stable), N.ip(ovf),
+                        N.stream())
+
+    def reset(d=desc, l=lmd, start=-1, beam_size=4, mt=MT, st=state, w=ws, nb=B):
+        return reset_fn(d, l, start, N.ptr(st), None, nb, beam_size, mt, N.ptr(w), N.stream())
+
+    for kw in (dict(Tc=0), dict(Tc=257), dict(st=None), dict(w=None), dict(l=None), dict(mt=0), dict(beam_size=0),
+               dict(beam_size=17), dict(topk=0), dict(weight=float("inf")), dict(weight=float("nan")),
+               dict(l=other_v), dict(l=bad_lm), dict(d=bad)):
+        assert chunk(**kw) == -1, kw
+    for kw in (dict(st=None), dict(w=None), dict(l=None), dict(mt=0), dict(beam_size=17), dict(beam_size=0),
+               dict(start=V), dict(l=other_v), dict(l=bad_lm), dict(d=bad)):
+        assert reset(**kw) == -1, kw
+    assert chunk(nb=0) == 0 and reset(nb=0) == 0
+    torch.cuda.synchronize()
+    for t in (tok, frm, n_out, stable, ovf):
+        assert bool((t == 7).all())
+    assert bool((score == 7.0).all()) and bool((lm_score == 7.0).all())
+    assert int(state.sum()) == 0 and int(ws.sum()) == 0
+
+
+def test_classes_refuse_what_the_kernels_do_not_take(dev):
+    from speech2text_amd.model.decoding import (RnntLstmStreamingSearch, RnntStatelessLmStreamingSearch,
+                                                RnntStreamingSearch, rnnt_streaming_search)
+    V = LS._TINY["V"]
+    p, j = LS._build(dev, **LS._TINY)
+    sp, sj = GS._build(dev, V, 8, 8, 2, inner=8)
+    sp0, sj0 = GS._build(dev, V, 8, 8, 2)
+    lm = GF._lm_module(dev, V=V, H=8, layers=1)
+    a = rnnt_streaming_search(p, j, 2, "beam", device=dev, lm=lm, lm_weight=0.3)
+    assert isinstance(a, RnntLstmStreamingSearch) and a.lm_score is not None and a.lm_score.shape == (2,)
+    assert rnnt_streaming_search(p, j, 2, "beam", device=dev).lm_score is None
+    for pair in ((sp, sj), (sp0, sj0)):                                 # with and without the out-projection
+        s = rnnt_streaming_search(*pair, 2, "beam", device=dev, lm=lm, lm_weight=0.3, lm_start_token=V - 1)
+        assert isinstance(s, RnntStatelessLmStreamingSearch) and s.lm_score.shape == (2,)
+        assert len(s.step(torch.zeros(2, 3, V, device=dev))) == 5
+    assert isinstance(rnnt_streaming_search(sp0, sj0, 2, "beam", device=dev), RnntStreamingSearch)
+    with pytest.raises(ValueError):                                     # the out-projection pair needs an LM
+        rnnt_streaming_search(sp, sj, 2, "beam", device=dev)
+    for cls, pair in ((RnntLstmStreamingSearch, (p, j)), (RnntStatelessLmStreamingSearch, (sp, sj))):
+        with pytest.raises(ValueError):
+            cls(*pair, 2, "greedy", device=dev, lm=lm)
+        with pytest.raises(ValueError):
+            cls(*pair, 2, "beam", beam_size=17, device=dev, lm=lm)
+        with pytest.raises(ValueError):
+            cls(*pair, 2, "beam", cutoff_top_k=0, device=dev, lm=lm)
+        with pytest.raises(ValueError):
+            cls(*pair, 2, "beam", max_tokens=0, device=dev, lm=lm)
+        with pytest.raises(ValueError):                                 # lm.V != V
+            cls(*pair, 2, "beam", device=dev, lm=GF._lm_module(dev, V=V + 1, H=8, layers=1))
+        with pytest.raises(ValueError):                                 # H just outside the limit
+            cls(*pair, 2, "beam", device=dev, lm=GF._lm_module(dev, V=V, H=1028, layers=1))
+        with pytest.raises(ValueError):                                 # layers just outside the limit
+            cls(*pair, 2, "beam", device=dev, lm=GF._lm_module(dev, V=V, H=8, layers=9))
+        with pytest.raises(ValueError):
+            cls(*pair, 2, "beam", device=dev, lm=lm, lm_start_token=V)
+        with pytest.raises(RuntimeError):                               # an LM off the GPU
+            cls(*pair, 2, "beam", device=dev, lm=GF._lm_module("cpu", V=V, H=8, layers=1))
+        with pytest.raises(ValueError):
+            cls(*pair, 2, "beam", device=dev, lm=lm).step(torch.zeros(2, 257, V, device=dev))
+    with pytest.raises(ValueError):
+        RnntLstmStreamingSearch(*LS._build(dev, **dict(LS._TINY, H=1028)), 2, "beam", device=dev, lm=lm)
+    with pytest.raises(ValueError):
+        RnntStatelessLmStreamingSearch(*GS._build(dev, V, 8, 8, 65), 2, "beam", device=dev, lm=lm)
+
+
+# ------------------------------------------------------------------------------------ 11. recogniser
+def _peaky_lm(dev, V, seed):
+    torch.manual_seed(seed)
+    lm = GF._lm_module(dev, V=V, H=16, layers=1)
+    with torch.no_grad():
+        lm._logits_layer.weight.mul_(16.0)
+    return lm
+
+
+def _stateless_out_projection_pair(dev, V, D, seed, blank):
+    """A stateless predictor and a joiner WITH output projection of fresh weights, times 3, blank lifted
+    behind the out-projection (LT._lstm_pair's construction)."""
+    from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
+    from speech2text_amd.model.predictor.predictor import Predictor
+    torch.manual_seed(seed)
+    pred = Predictor({"model": "Stateless", "config": {"num_symbols": V, "output_dim": D, "symbol_embedding_dim": 16,
+                                                       "context_size": 3}})
+    join = Joiner(JoinerConfig(input_dim=D, output_dim=V, inner_dim=32, activation="relu", use_out_project=True))
+    with torch.no_grad():
+        for q in list(pred.parameters()) + list(join.parameters()):
+            q.mul_(3.0)
+        join._out_projection[1].bias[0] += blank
+    return pred.to(dev).eval(), join.to(dev).eval()
+
+
+@pytest.mark.parametrize("family", ["lstm", "stateless_out_projection"])
+def test_recognizer_graph_equals_the_eager_composition(dev, golden_dir, family):
+    """StreamingRecognizer.step with an `lm` (one graph replay) against streaming_step -> _enc_proj -> the
+    search's step issued eagerly, over the fixture's 6 chunks, twice across reset(): am, the outputs and
+    lm_score bit for bit; the final result is the one-shot fused search's on the concatenation of the am
+    chunks the recogniser returned."""
+    from speech2text_amd.model.decoding import (RnntLstmStreamingSearch, RnntStatelessLmStreamingSearch,
+                                                rnnt_beam_lstm_lm_tokens_from_am,
+                                                rnnt_beam_stateless_lm_tokens_from_am)
+    from speech2text_amd.model.encoder.zipformer_streaming import StreamingRecognizer
+    g, m, chunk = SS._tiny_stream_encoder(golden_dir, dev)
+    V, D = 24, max(m.encoder_dim)
+    if family == "lstm":
+        pred, join = LT._lstm_pair(dev, V, D, 31, LT.RECOGNIZER_BLANK)
+        cls, one_shot = RnntLstmStreamingSearch, rnnt_beam_lstm_lm_tokens_from_am
+    else:
+        pred, join = _stateless_out_projection_pair(dev, V, D, 31, LT.RECOGNIZER_BLANK)
+        cls, one_shot = RnntStatelessLmStreamingSearch, rnnt_beam_stateless_lm_tokens_from_am
+    lm = _peaky_lm(dev, V, 32)
+    feats = torch.from_numpy(g["feats"]).to(dev)
+    B, T, Tc = feats.shape[0], 2 * chunk + 13, chunk // 2
+    kw = dict(method="beam", beam_size=4, cutoff_top_k=4, max_tokens=64, lm=lm, lm_weight=0.3, lm_start_token=V - 1)
+    rec = StreamingRecognizer(m, pred, join, TB._tokenizer(V), batch_size=B, device=dev, **kw)
+    assert isinstance(rec.search, cls) and rec.search.lm_score is not None
+    eager = cls(pred, join, B, device=dev, **kw)
+    for rep in range(2):
+        st = m.get_init_states(B, dev)
+        rec.reset()
+        eager.reset()
+        ams = []
+        for c in range(6):
+            x = feats[:, 2 * chunk * c:2 * chunk * c + T]
+            with torch.no_grad():
+                enc, st = m.streaming_step(x, st)
+                am = join._enc_proj(enc).float().contiguous()
+            want = eager.step(am)
+            got = rec.step(x)
+            assert torch.equal(got[-1], am), (rep, c)
+            for a, b in zip(got[:-1], want):
+                assert torch.equal(a, b), (rep, c)
+            assert torch.equal(rec.search.lm_score, eager.lm_score), (rep, c)
+            ams.append(got[-1].clone())
+        am_all = torch.cat(ams, dim=1)
+        n = int(rec.search.out_len.sum())
+        print(f"{family} rep {rep}: {n} tokens on {B * 6 * Tc} frames, lm_score {rec.search.lm_score.tolist()}")
+        assert n > 0 and int(rec.search.overflow.sum()) == 0
+        lens = torch.full((B,), 6 * Tc, dtype=torch.int64)
+        want = [x.cpu() for x in one_shot(am_all, lens, pred, join, lm, 0.3, 4, 4, V - 1)]
+        _same([x.cpu() for x in rec.outputs], rec.search.lm_score.cpu(), want)
+        plain = [x.cpu() for x in one_shot(am_all, lens, pred, join, lm, 0.0, 4, 4, V - 1)]
+        print(f"    lm_weight 0 would give out_len {plain[2].tolist()} against {want[2].tolist()}")
+        assert bool((rec.search.stable_len <= rec.search.out_len).all())
+
+
+def _task(dev, cfg):
+    from speech2text_amd.build_task import TaskFactory
+    torch.manual_seed(0)
+    task = TaskFactory.get("Pruned_Rnnt")(copy.deepcopy(cfg)).to(dev)
+    task.eval()
+    with torch.no_grad():
+        for q in list(task._predictor.parameters()) + list(task._joiner.parameters()):
+            q.mul_(3.0)
+        task._global_cmvn.global_mean.fill_(0.25)
+        task._global_cmvn.global_istd.fill_(0.5)
+    return task
+
+
+def test_task_streaming_recognizer_hands_over_the_metric_lm(dev, tmp_path):
+    """PrunedRnntTask.streaming_recognizer of a task with `metric.lm` (its checkpoint written by hand in the
+    NNLM task's keys): the search is fused with that LM at the metric's lm_weight, and what it decodes is
+    what the task's own validation search (its RnntBeamDecoding session's fused call) decodes from the
+    same am.  Greedy, or a task without `metric.lm`: today's object, and the same outputs as the search
+    built by hand without an LM."""
+    from speech2text_amd.model.decoding import RnntLstmStreamingSearch
+    from speech2text_amd.model.lm.rnn_lm import RnnLm, RnnLmConfig
+    V, chunk = 32, 8
+    cfg = TB._pruned_cfg(V)
+    cfg["encoder"]["config"].update({"chunk_size": [chunk], "left_context_frames": [16]})
+    cfg["predictor"] = {"model": "Lstm", "config": {
+        "num_symbols": V, "output_dim": 64, "symbol_embedding_dim": 32, "num_lstm_layers": 2,
+        "lstm_hidden_dim": 48, "lstm_layer_norm": True, "lstm_layer_norm_epsilon": 1e-3, "lstm_dropout": 0.0}}
+    lm_cfg = {"num_symbols": V, "symbol_embedding_dim": 24, "num_rnn_layer": 2}
+    torch.manual_seed(11)
+    lm = RnnLm(config=RnnLmConfig(**lm_cfg))
+    with torch.no_grad():
+        lm._logits_layer.weight.mul_(16.0)
+    path = str(tmp_path / "nnlm.ckpt")
+    torch.save({"state_dict": {"_nnlm." + k: v for k, v in lm.state_dict().items()}}, path)
+    plain_task = _task(dev, cfg)
+    cfg_lm = copy.deepcopy(cfg)
+    cfg_lm["metric"].update({"lm_weight": 0.4, "lm_start_token": V - 1, "lm": {"config": lm_cfg, "checkpoint": path}})
+    task = _task(dev, cfg_lm)
+    rec = task.streaming_recognizer(batch_size=2)
+    search = rec.search
+    assert isinstance(search, RnntLstmStreamingSearch) and search._lm is not None and search.lm_score is not None
+    assert (search.method, search.beam_size, search.cutoff_top_k, search._lm_weight, search._lm_start) == \
+        ("beam", 3, 2, 0.4, V - 1)
+    assert next(search._lm.parameters()).is_cuda and not any(k.startswith("_lm") for k in task.state_dict())
+    greedy = task.streaming_recognizer(batch_size=1, method="greedy").search
+    assert isinstance(greedy, RnntLstmStreamingSearch) and greedy._lm is None and greedy.lm_score is None
+
+    g = torch.Generator().manual_seed(5)
+    feats = (torch.randn(2, 150, 80, generator=g) * 2.0).to(dev)
+    K_, Tc, T = 9, chunk // 2, 2 * chunk + 13
+    buf = torch.zeros(2, 2 * chunk * (K_ - 1) + T, 80, device=dev)
+    buf[:, :150] = feats
+
+    def run(r):
+        r.reset()
+        ams, snaps = [], []
+        for k in range(K_):
+            out = r.step(buf[:, 2 * chunk * k:2 * chunk * k + T])
+            ams.append(out[-1].clone())
+            snaps.append([x.clone() for x in out[:-1]])
+        return torch.cat(ams, dim=1), snaps
+
+    am_all, snaps = run(rec)
+    sess = task._metric._decode_sess
+    sess._lm_to(dev)
+    assert (sess._lm_weight, sess._lm_start_token, sess._beam_size, sess._cutoff_top_k) == (0.4, V - 1, 3, 2)
+    from speech2text_amd.model.decoding import rnnt_beam_lstm_lm_tokens_from_am
+    lens = torch.full((2,), K_ * Tc, dtype=torch.int64)
+    want = [x.cpu() for x in rnnt_beam_lstm_lm_tokens_from_am(
+        am_all, lens, sess._predictor, sess._joiner, sess._lm, sess._lm_weight, sess._beam_size, sess._cutoff_top_k,
+        sess._lm_start_token)]
+    _same([x.cpu() for x in rec.outputs], search.lm_score.cpu(), want)
+    assert int(want[2].sum()) > 0
+    assert rec.texts() == [task._tokenizer.decode(want[0][b, :int(want[2][b])]) for b in range(2)]
+
+    # without metric.lm: today's object, and the outputs of the search built by hand without an LM
+    plain_rec = plain_task.streaming_recognizer(batch_size=2)
+    assert isinstance(plain_rec.search, RnntLstmStreamingSearch) and plain_rec.search._lm is None
+    assert plain_rec.search.lm_score is None
+    am_plain, plain_snaps = run(plain_rec)
+    by_hand = RnntLstmStreamingSearch(plain_task._predictor, plain_task._joiner, 2, "beam", beam_size=3,
+                                      cutoff_top_k=2, device=dev)
+    for k in range(K_):
+        out = by_hand.step(am_plain[:, k * Tc:(k + 1) * Tc].contiguous())
+        for a, b in zip(out, plain_snaps[k]):
+            assert torch.equal(a, b), k
