@@ -263,7 +263,7 @@ __global__ __launch_bounds__(256) void dwconv2d_roll_kernel(const float* __restr
       __syncthreads();
       s_red[r][c] = live ? (k < NV - 1 ? wv[MODE == 2 ? (k < NV - 1 ? k : 0) : 0] : bacc) : 0.f;
       __syncthreads();
-      if (r == 0) {
+      if (r == 0 && tile < (C + 63) / 64) {     // the workspace holds ceil(C / 64) tiles, not 2 ceil(C / 128)
         float t = 0.f;
 #pragma unroll
         for (int rr2 = 0; rr2 < 256 / RCT; ++rr2) t += s_red[rr2][c];
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256) void dwconv2d_wgrad_ring_kernel(const float* _
     __syncthreads();
     s_red[r][c] = live ? (k < NV - 1 ? wv[k < NV - 1 ? k : 0] : bacc) : 0.f;
     __syncthreads();
-    if (r == 0) {
+    if (r == 0 && tile < (C + 63) / 64) {       // the workspace holds ceil(C / 64) tiles, not 2 ceil(C / 128)
       float t = 0.f;
 #pragma unroll
       for (int rr2 = 0; rr2 < 256 / RCT; ++rr2) t += s_red[rr2][c];
