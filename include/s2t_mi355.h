@@ -747,6 +747,45 @@ int s2t_rnnt_beam_stateless_lm(const S2tRnntStatelessDesc* desc, const S2tRnnLmD
                                float lm_weight, int lm_start_token, void* workspace, long* tokens,
                                long* frames, long* out_len, float* score, float* lm_score, void* stream);
 
+/* ---- CTC prefix beam search, lexicon-free, equal prefixes merged exactly, with optional RNN-LM shallow
+ * fusion (csrc/decode_ctc.hip, csrc/decode_ctc.h).  logits [B][T][V], raw or already normalised; per
+ * utterance the frames t < min(lengths[b], T) are searched and no later frame is read.  A live prefix
+ * carries pb / pnb, the log-probabilities of its alignments that end in blank / in a non-blank; the
+ * search starts from the empty prefix (pb 0, pnb -inf).  Per frame: lp = log_softmax(logits[b][t]) in
+ * fp32; the k = min(cutoff_top_k, V) classes by (logit descending, class ascending) are chosen once
+ * for all prefixes (the LM does not enter this cut).  With s = logaddexp(pb, pnb) of prefix p, in beam
+ * order, class c in rank order: blank adds s + lp[c] to pb of p; c == last(p) adds pnb + lp[c] to pnb of
+ * p and pb + lp[c] to pnb of p + c; any other c adds s + lp[c] to pnb of p + c ("adds" is logaddexp; a term
+ * of -inf is skipped and makes no candidate).  Candidates with equal token sequences are ONE candidate
+ * whatever parents they came from: a per-utterance trie in the workspace gives every sequence ever
+ * kept one node id.  Candidates rank by total = logaddexp(pb, pnb) + lm_weight * lm_sum, descending,
+ * then first contributing parent, staying before extensions, class rank; the beam_size best survive.
+ * tokens [B][T] (zeroed by the caller; at most one token a frame), out_len [B], score [B] = logaddexp(pb,
+ * pnb) of the best prefix, the acoustic part alone.  No frames: no tokens, score 0.  beam_size =
+ * cutoff_top_k = 1 gives s2t_ctc_greedy's tokens.  s2t_ctc_prefix_beam is one launch, a workgroup per
+ * utterance.
+ * Limits (else -1 / size 0, before any launch and without following a pointer): beam_size and
+ * min(cutoff_top_k, V) in 1..S2T_RNNT_LSTM_MAX_BEAM; 1 <= V <= S2T_RNNT_LSTM_MAX_VOCAB; blank in [0, V);
+ * workspace not NULL.  B <= 0 returns 0. */
+long s2t_ctc_prefix_beam_workspace_bytes(int B, int T, int V, int beam_size);
+int s2t_ctc_prefix_beam(const float* logits, const long* lengths, int B, int T, int V, int blank,
+                        int beam_size, int cutoff_top_k, void* workspace, long* tokens, long* out_len,
+                        float* score, void* stream);
+/* The same search with the LM term: a live prefix also carries the LM state, q[V] = log_softmax(LM
+ * logits) of its next token and lm_sum; an extension p + c has lm_sum(p) + q_p[c], a candidate that is a
+ * live prefix keeps its own lm_sum, q and state bit for bit; a kept prefix that was not live steps the
+ * LM on its last token from its parent's state.  The LM starts as in s2t_rnnt_beam_lstm_lm
+ * (lm_start_token < 0: zero state, q = 0).  Exactly T lockstep rounds over the batch, each one search
+ * kernel and s2t_rnn_lm_step on B * beam_size rows, no host synchronisation.  lm_score [B] = the best
+ * prefix' lm_sum, so that its total is score + lm_weight * lm_score.  With lm_weight = 0 tokens, out_len
+ * and score are s2t_ctc_prefix_beam's bit for bit.  Refused as well: lm NULL or outside S2tRnnLmDesc's
+ * limits, lm.V != V, lm_start_token >= V, lm_weight not finite. */
+long s2t_ctc_prefix_beam_lm_workspace_bytes(const S2tRnnLmDesc* lm, int B, int T, int V, int beam_size);
+int s2t_ctc_prefix_beam_lm(const S2tRnnLmDesc* lm, const float* logits, const long* lengths, int B, int T,
+                           int V, int blank, int beam_size, int cutoff_top_k, float lm_weight,
+                           int lm_start_token, void* workspace, long* tokens, long* out_len, float* score,
+                           float* lm_score, void* stream);
+
 /* ---- chunk-carried (streaming) RNN-T search with the LSTM predictor: the two searches above fed
  * their frames in pieces (csrc/decode_lstm.hip).  A round's launches ARE the whole-utterance calls'
  * (one text, the same arguments), and a row's arithmetic does not depend on the rows that share its

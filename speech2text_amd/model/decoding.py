@@ -20,9 +20,13 @@ for shallow fusion (`lm=`, `lm_weight=`): with the LSTM predictor and with the s
 (joiner with or without output projection) the LM is stepped inside the lockstep device search
 (s2t_rnnt_beam_lstm_lm, s2t_rnnt_beam_stateless_lm), everything else runs `_module_loop_lm`; the
 chunk-carried beam searches take the same LM (RnntLstmStreamingSearch with `lm=`,
-RnntStatelessLmStreamingSearch; s2t_rnnt_beam_lstm_lm_chunk, s2t_rnnt_beam_stateless_lm_chunk).  The
-lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are not here."""
+RnntStatelessLmStreamingSearch; s2t_rnnt_beam_lstm_lm_chunk, s2t_rnnt_beam_stateless_lm_chunk).
+CtcPrefixBeamDecoding is a lexicon-free CTC prefix beam search with equal prefixes merged and the same
+optional RNN-LM term, on the device for the whole batch (csrc/decode_ctc.hip: s2t_ctc_prefix_beam,
+s2t_ctc_prefix_beam_lm).  The lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are
+not here."""
 import abc
+import math
 from enum import Enum, unique
 from typing import List
 
@@ -88,6 +92,224 @@ class CtcGreedyDecoding(DecodingMethod):
         assert hidden_states.shape[-1] == len(self._tokenizer.labels)
         return _to_texts(*ctc_greedy_tokens(hidden_states, inputs_length), self._tokenizer)
 
+    def decode(self, hidden_states: torch.Tensor) -> str:
+        assert hidden_states.shape[0] == 1, "Support BatchSize = 1 only."
+        n = torch.tensor([hidden_states.shape[1]], dtype=torch.int64)
+        return self.decode_batch(hidden_states, n)[0]
+
+
+def _ctc_prefix_arguments(logits, lengths):
+    if not logits.is_cuda:
+        raise RuntimeError("the device CTC prefix beam search runs on the GPU only")
+    logits = logits.contiguous().float()
+    B, T, _ = logits.shape
+    dev = logits.device
+    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+    out = (torch.zeros((B, T), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev),
+           torch.zeros((B,), dtype=torch.float32, device=dev))
+    return logits, lengths, out
+
+
+def ctc_prefix_beam_tokens(logits, lengths, beam_size=4, cutoff_top_k=4, blank=0):
+    """CTC prefix beam search with equal prefixes merged: (B,T,V) device logits (raw or normalised) ->
+    (tokens (B,T) int64, out_len (B) int64, score (B) fp32: log-probability of the best prefix summed
+    over its alignments), or None when the kernel does not take the shape.  HIP: decode_ctc.hip."""
+    logits, lengths, out = _ctc_prefix_arguments(logits, lengths)
+    B, T, V = logits.shape
+    if B == 0 or T == 0:
+        return out
+    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
+    n = N.lib().s2t_ctc_prefix_beam_workspace_bytes(B, T, V, beam_size)
+    if n <= 0:
+        return None
+    ws = torch.empty((n,), dtype=torch.uint8, device=logits.device)
+    tokens, out_len, score = out
+    rc = N.lib().s2t_ctc_prefix_beam(N.fp(logits), N.lp(lengths), B, T, V, int(blank), beam_size, cutoff_top_k,
+                                     N.ptr(ws), N.lp(tokens), N.lp(out_len), N.fp(score), N.stream())
+    if rc == -1:
+        return None
+    N.check(rc, "s2t_ctc_prefix_beam")
+    return out
+
+
+def ctc_prefix_beam_lm_tokens(logits, lengths, lm, lm_weight, beam_size=4, cutoff_top_k=4, blank=0,
+                              lm_start_token=None):
+    """ctc_prefix_beam_tokens with RNN-LM shallow fusion: prefixes rank by their log-probability plus
+    lm_weight * (the LM's log-probability of their tokens).  lm_start_token as in
+    rnnt_beam_lstm_lm_tokens_from_am.  -> (tokens, out_len, score (the acoustic part), lm_score (B) fp32:
+    the best prefix' unweighted LM sum), or None when the kernels do not take the shape."""
+    logits, lengths, out = _ctc_prefix_arguments(logits, lengths)
+    B, T, V = logits.shape
+    out = out + (torch.zeros((B,), dtype=torch.float32, device=logits.device),)
+    if B == 0 or T == 0:
+        return out
+    start = -1 if lm_start_token is None else int(lm_start_token)
+    if lm_start_token is not None and start < 0:
+        raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
+    lm_desc, lm_keep = rnn_lm_desc(lm)
+    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
+    if lm_desc is None:
+        return None
+    n = N.lib().s2t_ctc_prefix_beam_lm_workspace_bytes(lm_desc, B, T, V, beam_size)
+    if n <= 0:
+        return None
+    ws = torch.empty((n,), dtype=torch.uint8, device=logits.device)
+    tokens, out_len, score, lm_score = out
+    rc = N.lib().s2t_ctc_prefix_beam_lm(lm_desc, N.fp(logits), N.lp(lengths), B, T, V, int(blank), beam_size,
+                                        cutoff_top_k, float(lm_weight), start, N.ptr(ws), N.lp(tokens),
+                                        N.lp(out_len), N.fp(score), N.fp(lm_score), N.stream())
+    del lm_keep
+    if rc == -1:
+        return None
+    N.check(rc, "s2t_ctc_prefix_beam_lm")
+    return out
+
+
+def _logaddexp(a, b):
+    """Of two Python floats; -inf is the empty sum."""
+    if a == -math.inf:
+        return b
+    if b == -math.inf:
+        return a
+    hi, lo = (a, b) if a >= b else (b, a)
+    return hi + math.log1p(math.exp(lo - hi))
+
+
+class CtcPrefixBeamDecoding(DecodingMethod):
+    """Lexicon-free CTC prefix beam search (the reference's CTC beam decoder wraps a lexicon decoder of
+    a library that is not here; this one searches the model's own classes).  A live prefix carries
+    the log-probabilities of its alignments ending in blank and in a non-blank; per frame the
+    `cutoff_top_k` classes by (logit descending, class ascending) extend every prefix, candidates that
+    spell the same tokens are merged into one, the `beam_size` best survive.
+
+    With `lm` (an RnnLm, or anything with init_states / score_step) prefixes rank by their
+    log-probability plus `lm_weight` times the LM's log-probability of their tokens; `lm_start_token`
+    as in RnntBeamDecoding.  Device logits run the fused search (csrc/decode_ctc.hip; with an LM when it
+    is this project's RnnLm); CPU tensors, shapes the kernels refuse and foreign LMs run `_module_loop`.
+    `beam_tokens` returns (tokens, out_len, score) and with an LM a fourth tensor, the best prefix'
+    unweighted LM sum."""
+
+    def __init__(self, tokenizer, beam_size=4, cutoff_top_k=4, lm=None, lm_weight=0.0, lm_start_token=None) -> None:
+        self._tokenizer = tokenizer
+        self._beam_size = int(beam_size)
+        self._cutoff_top_k = int(cutoff_top_k)
+        self._lm = lm
+        self._lm_weight = float(lm_weight)
+        self._lm_start_token = None if lm_start_token is None else int(lm_start_token)
+        if self._lm_start_token is not None and self._lm_start_token < 0:
+            raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
+        if self._beam_size < 1 or self._cutoff_top_k < 1:
+            raise ValueError(f"beam_size and cutoff_top_k must be at least 1, got {beam_size!r}, {cutoff_top_k!r}")
+
+    def _module_loop(self, hidden_states, blank=0):
+        """(1,T,V) -> (tokens, score, lm_score) of the best prefix: the same search on the host.  The
+        log-softmax, the top-k and the LM run in torch on the inputs' device (in their dtype, fp32 at
+        least); the per-prefix recursion runs on Python floats keyed by token tuples."""
+        x = hidden_states[0]
+        x = x.to(torch.promote_types(x.dtype, torch.float32))
+        T, V = x.shape
+        dev = x.device
+        k = min(self._cutoff_top_k, V)
+        lm, weight = self._lm, self._lm_weight
+        info = {}                                          # live prefix -> (q as a list, LM state, lm_sum)
+        if lm is not None:
+            state, q = lm.init_states(1), [0.0] * V
+            if self._lm_start_token is not None:
+                qt, state = lm.score_step(torch.full((1,), self._lm_start_token, dtype=torch.int64, device=dev),
+                                          state)
+                q = qt[0].double().tolist()
+            info[()] = (q, state, 0.0)
+        beam = [((), 0.0, -math.inf)]
+        if T > 0:
+            order = torch.sort(x, dim=-1, descending=True, stable=True).indices[:, :k]
+            lps = torch.log_softmax(x, dim=-1).gather(1, order).double().tolist()
+            order = order.tolist()
+        for t in range(T):
+            live = {p for p, _, _ in beam}
+            cand = {}                                      # tokens -> [pb, pnb, key, parent prefix]
+            for i, (p, pb, pnb) in enumerate(beam):
+                s = _logaddexp(pb, pnb)
+                for r, (c, lp) in enumerate(zip(order[t], lps[t])):
+                    if c == blank:
+                        e = cand.setdefault(p, [-math.inf, -math.inf, (i, 0, 0)])
+                        e[0] = _logaddexp(e[0], s + lp)
+                        continue
+                    if p and c == p[-1]:
+                        if pnb + lp != -math.inf:
+                            e = cand.setdefault(p, [-math.inf, -math.inf, (i, 0, 0)])
+                            e[1] = _logaddexp(e[1], pnb + lp)
+                        v = pb + lp
+                    else:
+                        v = s + lp
+                    if v != -math.inf:
+                        e = cand.setdefault(p + (c,), [-math.inf, -math.inf, (i, 1, r)])
+                        e[1] = _logaddexp(e[1], v)
+            ranked = []
+            for tokens, (pb, pnb, key) in cand.items():
+                lm_sum = 0.0
+                if lm is not None:
+                    lm_sum = info[tokens][2] if tokens in live else info[tokens[:-1]][2] + info[tokens[:-1]][0][tokens[-1]]
+                ranked.append((-(_logaddexp(pb, pnb) + weight * lm_sum), key, tokens, pb, pnb, lm_sum))
+            ranked.sort(key=lambda e: e[:2])
+            ranked = ranked[:self._beam_size]
+            if lm is not None:
+                new_info = {}
+                for _, _, tokens, _, _, lm_sum in ranked:
+                    if tokens in live:
+                        new_info[tokens] = info[tokens]
+                    else:
+                        qt, state = lm.score_step(torch.full((1,), tokens[-1], dtype=torch.int64, device=dev),
+                                                  info[tokens[:-1]][1])
+                        new_info[tokens] = (qt[0].double().tolist(), state, lm_sum)
+                info = new_info
+            beam = [(e[2], e[3], e[4]) for e in ranked]
+        p, pb, pnb = beam[0]
+        return list(p), _logaddexp(pb, pnb), (info[p][2] if lm is not None else 0.0)
+
+    def _fused(self, hidden_states, inputs_length):
+        from speech2text_amd.model.lm.rnn_lm import RnnLm
+        if not hidden_states.is_cuda:
+            return None
+        if self._lm is None:
+            return ctc_prefix_beam_tokens(hidden_states, inputs_length, self._beam_size, self._cutoff_top_k)
+        if not isinstance(self._lm, RnnLm):
+            return None
+        return ctc_prefix_beam_lm_tokens(hidden_states, inputs_length, self._lm, self._lm_weight, self._beam_size,
+                                         self._cutoff_top_k, lm_start_token=self._lm_start_token)
+
+    @torch.no_grad()
+    def beam_tokens(self, hidden_states, inputs_length, fused=True):
+        """(B,T,V) logits -> (tokens (B,T), out_len (B), score (B)) of the best prefix per utterance, and
+        with an LM its lm_score (B).  The fused device search where it applies (and `fused` is left
+        on), else the host loop per utterance."""
+        dev = hidden_states.device
+        if isinstance(self._lm, torch.nn.Module):
+            p = next(self._lm.parameters(), None)
+            if p is not None and p.device != dev:
+                self._lm.to(dev)
+        if fused:
+            out = self._fused(hidden_states, inputs_length)
+            if out is not None:
+                return out
+        B, T = hidden_states.shape[0], hidden_states.shape[1]
+        tokens = torch.zeros((B, T), dtype=torch.int64)
+        out_len = torch.zeros((B,), dtype=torch.int64)
+        score = torch.zeros((B,), dtype=torch.float32)
+        lm_score = torch.zeros((B,), dtype=torch.float32)
+        for b in range(B):
+            n = max(0, min(int(inputs_length[b]), T))
+            tok, score[b], lm_score[b] = self._module_loop(hidden_states[b:b + 1, :n, :])
+            out_len[b] = len(tok)
+            tokens[b, :len(tok)] = torch.tensor(tok, dtype=torch.int64)
+        out = (tokens.to(dev), out_len.to(dev), score.to(dev))
+        return out + (lm_score.to(dev),) if self._lm is not None else out
+
+    @torch.no_grad()
+    def decode_batch(self, hidden_states, inputs_length):
+        out = self.beam_tokens(hidden_states, inputs_length)
+        return _to_texts(out[0], out[1], self._tokenizer)
+
+    @torch.no_grad()
     def decode(self, hidden_states: torch.Tensor) -> str:
         assert hidden_states.shape[0] == 1, "Support BatchSize = 1 only."
         n = torch.tensor([hidden_states.shape[1]], dtype=torch.int64)

@@ -5,8 +5,8 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from speech2text_amd.model.decoding import (CtcGreedyDecoding, RnntBeamDecoding, RnntGreedyDecoding,
-                                            batch_search, reference_decoder)
+from speech2text_amd.model.decoding import (CtcGreedyDecoding, CtcPrefixBeamDecoding, RnntBeamDecoding,
+                                            RnntGreedyDecoding, batch_search, reference_decoder)
 
 
 def _levenshtein(a: List, b: List) -> int:
@@ -40,7 +40,11 @@ class AsrMetricConfig:
     """decode_method: "ctc_greedy_search" / "rnnt_greedy_search" as in the reference, and
     "rnnt_beam_search" (a name of this project: the reference's AsrMetric knows the greedy
     decoders only), which scores with RnntBeamDecoding(beam_size, cutoff_top_k); given a language
-    model (AsrMetric's `lm`) it is shallow-fused with lm_weight / lm_start_token."""
+    model (AsrMetric's `lm`) it is shallow-fused with lm_weight / lm_start_token.
+    "ctc_prefix_beam_search" (also a name of this project: the reference's CTC beam decoder needs a
+    lexicon decoder of a library) scores a CTC head with CtcPrefixBeamDecoding(beam_size,
+    cutoff_top_k), lexicon-free and with equal prefixes merged; it takes the same `lm`, lm_weight and
+    lm_start_token."""
     decode_method: str = "ctc_greedy_search"
     max_token_step: int = 5
     beam_size: int = 4
@@ -65,6 +69,11 @@ class AsrMetric(object):
                                                  cutoff_top_k=config.cutoff_top_k, lm=lm,
                                                  lm_weight=config.lm_weight,
                                                  lm_start_token=config.lm_start_token)
+        elif config.decode_method == "ctc_prefix_beam_search":
+            self._decode_sess = CtcPrefixBeamDecoding(tokenizer=tokenizer, beam_size=config.beam_size,
+                                                      cutoff_top_k=config.cutoff_top_k, lm=lm,
+                                                      lm_weight=config.lm_weight,
+                                                      lm_start_token=config.lm_start_token)
         else:
             raise NotImplementedError(config.decode_method)
 
