@@ -786,6 +786,90 @@ int s2t_ctc_prefix_beam_lm(const S2tRnnLmDesc* lm, const float* logits, const lo
                            int lm_start_token, void* workspace, long* tokens, long* out_len, float* score,
                            float* lm_score, void* stream);
 
+/* ---- chunk-carried (streaming) CTC prefix beam search: the two searches above fed their frames in
+ * pieces (csrc/decode_ctc.hip).  logits [B][Tc][V], Tc in 1..256; row b advances over the first n =
+ * min(chunk_len[b], Tc) frames of the chunk and reads no later frame.  A frame is the one-shot entries'
+ * own device function (csrc/decode_ctc.h ctc_frame, ctc_finish; the LM family's round is their round
+ * kernel plus s2t_rnn_lm_step), no frame body is forked or restated, so:
+ * EQUALITY.  For ANY cut of [0, L) into chunks -- one frame each, different per row, idle calls in
+ * between -- while overflow[b] == 0, tokens[b][:out_len[b]], out_len, score and lm_score after the last
+ * chunk are those of the one-shot entry on the concatenated logits with lengths = L, bit for bit, and
+ * after every chunk those of the prefix fed so far.  Through the LM entry with lm_weight = 0 tokens,
+ * out_len, score, stable_len and overflow are the plain chunk entry's bit for bit.  beam_size =
+ * cutoff_top_k = 1 gives s2t_ctc_greedy's tokens of the frames fed so far.
+ * IDLE ROWS.  chunk_len[b] <= 0 leaves row b's state and all its outputs exactly as they were (in the LM
+ * family with one exception, the per-call arrays eff and emit / parent / token: they are scratch,
+ * rewritten for every row by every call -- eff by its begin kernel, the others by every round and every
+ * reset -- before anything reads them, and carry nothing from call to call).
+ * THE TRIE DOES NOT GROW WITH THE STREAM.  stable_len[b] is the length of the longest common prefix of
+ * all live prefixes, the depth of the lowest common ancestor of the live nodes.  Every later live
+ * prefix descends from a live one, so stable_len never decreases and tokens[b][:stable_len[b]] never
+ * change again; no sequence outside that ancestor's subtree can be live again; and a sequence that is
+ * not on a path from the ancestor to a live node gets from a fresh node what it got from its old one
+ * (node ids enter results only through "is p + c live"; rank keys are slots).  Hence every call that
+ * consumes frames ends by compacting the row's trie -- always, not when room is short: one code path,
+ * the same launches every replay: the ancestor becomes the root, only the union of the root-to-live
+ * paths survives, renumbered in ascending order of the old ids (parent id < child id still holds), the
+ * child lists filtered in their order; the ancestor's depth is kept per row as the committed depth;
+ * prefix lengths stay absolute.  The trace-back of a call walks from the best node to the root only and
+ * writes tokens[b][p] for p from the committed depth up; positions below it were written by earlier
+ * calls, so a stream must pass the SAME tokens array [B][max_tokens] on every call (as
+ * s2t_rnnt_greedy_stateless_chunk requires).  A call's cost follows the unstable region, not the
+ * stream.  Every walk (sibling list, path to the root, ancestor) carries a hop bound: a corrupt state
+ * ends in a wrong answer, never in a hang.
+ * OVERFLOW, bits of overflow[b].  Bit 1 (value 2), nodes: row b consumes its n frames if and only if
+ * kept + beam_size * n <= max_nodes, kept = the row's node count after its last compaction (1 after a
+ * reset); otherwise the call consumes none of them, sets bit 1 and the row is inert until reset, its
+ * state and outputs as they were: no write lands outside the node array.  Bit 0 (value 1), tokens: a
+ * best prefix longer than max_tokens keeps its first max_tokens tokens in the array, out_len and
+ * stable_len saturate there, the search goes on with exact scores.
+ * state: ONE caller-owned buffer of s2t_ctc_stream_state_bytes / s2t_ctc_lm_stream_state_bytes bytes (a
+ * multiple of 256, independent of the frames seen), every array 256-byte aligned, in this order, R = B *
+ * beam_size, M = B * max_nodes:
+ *   nodes   [M] x 16 B   the trie (int32 parent, token, first_child, next_sibling), a row's at b * max_nodes
+ *   stage   [M] x 16 B   where a compaction builds the surviving nodes before they are copied back
+ *   map     [M] int32    old node id -> new id, -1 dropped (scratch of a compaction)
+ *   pb, pnb, lm_sum [R] fp32;  node, last, len [R] int32     the live prefixes in beam order
+ *   nb, kept [B] int32   live prefixes; nodes after the last compaction
+ *   depth, ovf [B] int32 the committed depth; the overflow bits
+ *   eff     [B] int64    frames the current call consumes (scratch; the LM rounds' lengths)
+ *   LM family only: emit, parent, token [R] int32 (what s2t_rnn_lm_step is asked: scratch), h, c
+ *   [lm.layers][R][lm.H], q [R][V] fp32: the LIVE copy of the LM's state.
+ * workspace (LM family): s2t_ctc_prefix_beam_lm_chunk_workspace_bytes bytes of scratch, independent of
+ * Tc, serving every call and the reset: the second copy of h, c, q and s2t_rnn_lm_step's workspace.  The
+ * rounds alternate between the copies; the LM step after the chunk's last frame IS enqueued (the next
+ * chunk's first frame reads it; outputs do not depend on it), and after an odd Tc ONE launch copies the
+ * survivors home, so the launches of a call depend on its arguments alone.
+ * *_stream_reset: every row b with rows[b] != 0 (rows NULL: every row) becomes the empty prefix: root
+ * node only, pb 0, pnb -inf, committed depth 0, overflow 0; the LM family also zeroes the row's LM
+ * state and q and, with lm_start_token >= 0, makes the one-shot entry's own first LM step on that
+ * token, masked by rows.  Other rows keep every bit (but the scratch arrays named above).  The
+ * caller's outputs are not reset's to write.
+ * s2t_ctc_prefix_beam_chunk is ONE launch, a workgroup per utterance; s2t_ctc_prefix_beam_lm_chunk is a
+ * begin kernel (admission, the effective lengths), exactly Tc lockstep rounds, the copy home after an odd
+ * Tc and an end kernel (outputs, compaction).  No host synchronisation, no cooperative launch, no memset:
+ * reset and chunk calls can be captured into a graph and replayed.
+ * Return 0; -1 / size 0 before any launch (outputs untouched, no pointer followed) for Tc outside
+ * 1..256, state (or workspace, lm) NULL, max_tokens < 1, max_nodes outside 1..S2T_CTC_STREAM_MAX_NODES, and
+ * what the one-shot entries refuse; B <= 0 returns 0.  The size functions are pure host functions. */
+#define S2T_CTC_STREAM_MAX_NODES 1048576
+long s2t_ctc_stream_state_bytes(int B, int V, int beam_size, int max_nodes);
+int s2t_ctc_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
+                         void* stream);
+int s2t_ctc_prefix_beam_chunk(const float* logits, const long* chunk_len, int B, int Tc, int V, int blank,
+                              int beam_size, int cutoff_top_k, int max_tokens, int max_nodes, void* state,
+                              long* tokens, long* out_len, float* score, long* stable_len, int* overflow,
+                              void* stream);
+long s2t_ctc_lm_stream_state_bytes(const S2tRnnLmDesc* lm, int B, int V, int beam_size, int max_nodes);
+long s2t_ctc_prefix_beam_lm_chunk_workspace_bytes(const S2tRnnLmDesc* lm, int B, int V, int beam_size);
+int s2t_ctc_lm_stream_reset(const S2tRnnLmDesc* lm, int lm_start_token, void* state, const int* rows, int B,
+                            int V, int beam_size, int max_nodes, void* workspace, void* stream);
+int s2t_ctc_prefix_beam_lm_chunk(const S2tRnnLmDesc* lm, const float* logits, const long* chunk_len, int B,
+                                 int Tc, int V, int blank, int beam_size, int cutoff_top_k, float lm_weight,
+                                 int lm_start_token, int max_tokens, int max_nodes, void* state,
+                                 void* workspace, long* tokens, long* out_len, float* score, float* lm_score,
+                                 long* stable_len, int* overflow, void* stream);
+
 /* ---- chunk-carried (streaming) RNN-T search with the LSTM predictor: the two searches above fed
  * their frames in pieces (csrc/decode_lstm.hip).  A round's launches ARE the whole-utterance calls'
  * (one text, the same arguments), and a row's arithmetic does not depend on the rows that share its

@@ -239,18 +239,23 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
   __syncthreads();
 }
 
-// the best prefix (position 0): its tokens by a walk to the root, its acoustic score
+// the best prefix (position 0): its tokens by a walk to the root, its acoustic score.  tokens holds
+// max_tokens positions: a longer prefix keeps its first max_tokens tokens and out_len saturates there
+// (the whole-utterance entries pass T: a prefix has at most a token a frame).  The walk ends at the
+// root, whatever its depth (a chunk-carried trie's root is the committed prefix), after at most
+// max_hops nodes.
 __device__ __forceinline__ void ctc_finish(const CtcShared& s, const CtcNode* nodes, long* __restrict__ tokens,
-                                           long* out_len, float* score, float* lm_score) {
+                                           long* out_len, float* score, float* lm_score, int max_tokens,
+                                           int max_hops) {
   if (threadIdx.x == 0) {
     const int n = s.len[0];
-    *out_len = n;
+    *out_len = min(n, max_tokens);
     *score = log_add_precise(s.pb[0], s.pnb[0]);
     if (lm_score) *lm_score = s.lm_sum[0];
     int id = s.node[0];
-    for (int p = n - 1; p >= 0 && id > 0; --p) {
+    for (int p = n - 1, hop = 0; p >= 0 && id > 0 && hop < max_hops; --p, ++hop) {
       const CtcNode nd = nodes[id];
-      tokens[p] = nd.token;
+      if (p < max_tokens) tokens[p] = nd.token;
       id = nd.parent;
     }
   }

@@ -11,6 +11,10 @@
 //                            parent / token), then s2t_rnn_lm_step on B * beam_size rows through two
 //                            alternating state buffers.  The beam lives in the workspace between
 //                            rounds.  A row past its length passes its state through.
+//   s2t_ctc_prefix_beam_chunk, s2t_ctc_prefix_beam_lm_chunk
+//                            the two above fed their frames in pieces: beam and trie in a caller-owned
+//                            state, the same frame body and round kernel, and at the end of every call
+//                            a compaction of the trie to what the live prefixes can still reach.
 #include <hip/hip_runtime.h>
 
 #include "../../include/s2t_mi355.h"
@@ -48,7 +52,7 @@ __global__ __launch_bounds__(kCtcThreads) void ctc_prefix_kernel(CtcArgs a) {
   for (int t = 0; t < Tb; ++t)
     ctc_frame<false>(s, row, x + (long)t * a.V, a.V, K, a.beam, a.blank, nodes, a.max_nodes, 0.f, nullptr,
                      nullptr, nullptr, nullptr, 0);
-  ctc_finish(s, nodes, a.tokens + (long)b * a.T, a.out_len + b, a.score + b, nullptr);
+  ctc_finish(s, nodes, a.tokens + (long)b * a.T, a.out_len + b, a.score + b, nullptr, a.T, a.max_nodes);
 }
 
 // ------------------------------------------------------------------ the lockstep form
@@ -144,7 +148,7 @@ __global__ __launch_bounds__(64) void ctc_lm_finish_kernel(CtcLmArgs a) {
   load_beam(s, a.st, b, a.c.beam);
   __syncthreads();
   ctc_finish(s, a.c.nodes + (long)b * a.c.max_nodes, a.c.tokens + (long)b * a.c.T, a.c.out_len + b,
-             a.c.score + b, a.lm_score + b);
+             a.c.score + b, a.lm_score + b, a.c.T, a.c.max_nodes);
 }
 
 bool ctc_ok(int T, int V, int blank, int beam_size, int cutoff_top_k) {
@@ -194,6 +198,322 @@ CtcLmWorkspace carve_ctc_lm(const S2tRnnLmDesc& d, int B, int T, int beam, void*
   w.step = take((size_t)s2t_rnn_lm_step_workspace_bytes(&d, (int)R));
   w.bytes = off;
   return w;
+}
+
+// ------------------------------------------------------------------ the chunk-carried form
+// A stream's beam and trie live in a caller-owned state buffer between calls.  A call that consumes
+// frames ends by compacting the trie: the lowest common ancestor of the live nodes becomes the root,
+// only the union of the paths from it to the live nodes survives (renumbered in ascending order of
+// the old ids, so that parent id < child id still holds; the child lists filtered in their order),
+// and the ancestor's depth is kept as the committed depth.  Nothing outside that subtree can be live
+// again, and a sequence off those paths gets from a fresh node what it got from its old one: node
+// ids enter results only through "is p + c live".  st.nnodes is then `kept`, and a row consumes its n
+// frames only when kept + beam * n <= max_nodes: no node is ever written outside the array.
+struct CtcStream {
+  CtcNode *nodes, *stage;          // [B][max_nodes] the trie; where a compaction builds its successor
+  int* map;                        // [B][max_nodes] old node id -> new id, -1: dropped
+  CtcState st;                     // the beams; emit / parent / token with an LM only
+  int *depth, *ovf;                // [B] the committed depth; the overflow bits
+  long* eff;                       // [B] frames the current call consumes (the LM family's rounds read it)
+  float *h, *c, *q;                // the LM's live copy (LM family)
+  size_t bytes;
+};
+
+CtcStream carve_ctc_stream(const S2tRnnLmDesc* lm, int B, int V, int beam, int max_nodes, void* base) {
+  const size_t R = (size_t)B * beam, M = (size_t)B * max_nodes;
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t n) {
+    char* q = p + off;
+    off += align256(n);
+    return q;
+  };
+  auto f = [&](size_t n) { return reinterpret_cast<float*>(take(4 * n)); };
+  auto i = [&](size_t n) { return reinterpret_cast<int*>(take(4 * n)); };
+  CtcStream s{};
+  s.nodes = reinterpret_cast<CtcNode*>(take(sizeof(CtcNode) * M));
+  s.stage = reinterpret_cast<CtcNode*>(take(sizeof(CtcNode) * M));
+  s.map = i(M);
+  s.st = CtcState{f(R), f(R), f(R), i(R), i(R), i(R), i(B), i(B), nullptr, nullptr, nullptr};
+  s.depth = i(B);
+  s.ovf = i(B);
+  s.eff = reinterpret_cast<long*>(take(sizeof(long) * (size_t)B));
+  if (lm) {
+    s.st.emit = i(R);
+    s.st.parent = i(R);
+    s.st.token = i(R);
+    s.h = f((size_t)lm->num_layers * R * lm->H);
+    s.c = f((size_t)lm->num_layers * R * lm->H);
+    s.q = f(R * V);
+  }
+  s.bytes = off;
+  return s;
+}
+
+struct CtcLmStreamWorkspace {      // the second copy of the LM's state, the LM step's scratch
+  float *h, *c, *q;
+  void* step;
+  size_t bytes;
+};
+
+CtcLmStreamWorkspace carve_ctc_lm_stream_ws(const S2tRnnLmDesc& d, int B, int beam, void* base) {
+  const size_t R = (size_t)B * beam;
+  char* p = static_cast<char*>(base);
+  CtcLmStreamWorkspace w;
+  size_t off = 0;
+  auto f = [&](size_t n) {
+    char* q = p + off;
+    off += align256(4 * n);
+    return reinterpret_cast<float*>(q);
+  };
+  w.h = f((size_t)d.num_layers * R * d.H);
+  w.c = f((size_t)d.num_layers * R * d.H);
+  w.q = f(R * d.V);
+  w.step = p + off;
+  off += align256((size_t)s2t_rnn_lm_step_workspace_bytes(&d, (int)R));
+  w.bytes = off;
+  return w;
+}
+
+struct CtcStreamArgs {
+  CtcArgs c;                       // lengths: chunk_len, T: Tc, nodes: the state's, tokens [B][max_tokens]
+  CtcState st;
+  CtcNode* stage;
+  int *map, *depth, *ovf;
+  long* eff;
+  int max_tokens;
+  float* lm_score;                 // NULL: the plain family
+  long* stable_len;
+  int* overflow;
+};
+
+struct CtcCompact {
+  int anc, depth;                  // the live nodes' lowest common ancestor and its absolute depth
+  int part[kCtcWaves];
+};
+
+// frames row b consumes in this call: 0 for an idle row, an inert one, and one whose nodes do not fit
+// (which then becomes inert: bit 1)
+__device__ __forceinline__ int ctc_stream_admit(const CtcStreamArgs& a, int b) {
+  const int n = (int)clamped_len(a.c.lengths, b, a.c.T);
+  const int ovf = a.ovf[b];
+  const long need = (long)a.st.nnodes[b] + (long)a.c.beam * n;
+  __syncthreads();                                         // (every thread has read what thread 0 may write)
+  if (n <= 0 || (ovf & 2)) return 0;
+  if (need <= a.c.max_nodes) return n;
+  if (threadIdx.x == 0) {
+    a.ovf[b] = ovf | 2;
+    a.overflow[b] = ovf | 2;
+  }
+  return 0;
+}
+
+// After the last frame of a call, beam in s: the outputs, then the compaction.  All kCtcThreads
+// threads call it.  Every walk is bounded by the node count: a corrupt state ends in a wrong answer.
+__device__ __forceinline__ void ctc_stream_close(CtcShared& s, CtcCompact& k, const CtcStreamArgs& a, int b) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int M = a.c.max_nodes, nb = s.nb, nn = s.nnodes, BS = a.c.beam;
+  CtcNode* nodes = a.c.nodes + (long)b * M;
+  CtcNode* stage = a.stage + (long)b * M;
+  int* map = a.map + (long)b * M;
+  const int root_depth = a.depth[b];
+  // ---- the best prefix: positions from the committed depth up (below it earlier calls wrote them)
+  ctc_finish(s, nodes, a.c.tokens + (long)b * a.max_tokens, a.c.out_len + b, a.c.score + b,
+             a.lm_score ? a.lm_score + b : nullptr, a.max_tokens, nn);
+  for (int id = tid; id < nn; id += kCtcThreads) map[id] = -1;
+  // ---- the lowest common ancestor: a lane per live node, levelled to the shallowest, then up together
+  if (wave == 0) {
+    const int i = lane < nb ? lane : 0;
+    int id = s.node[i], d = s.len[i], dmin = d;
+    for (int o = 32; o; o >>= 1) dmin = min(dmin, __shfl_xor(dmin, o));
+    for (int hop = 0; d > dmin && id > 0 && hop < nn; ++hop, --d) id = nodes[id].parent;
+    bool same = false;
+    for (int hop = 0; hop <= nn; ++hop) {
+      same = __all(id == __shfl(id, 0)) != 0;
+      if (same) break;
+      if (id > 0) {
+        id = nodes[id].parent;
+        --d;
+      }
+    }
+    if (lane == 0) {
+      const bool ok = same && id >= 0 && id < nn;
+      k.anc = ok ? id : 0;
+      k.depth = ok ? d : root_depth;
+    }
+  }
+  __syncthreads();
+  const int anc = k.anc;
+  // ---- mark the paths from the live nodes to it
+  if (tid < nb) {
+    int id = s.node[tid];
+    for (int hop = 0; id > 0 && id < nn && id != anc && hop < nn; ++hop) {
+      map[id] = 1;
+      id = nodes[id].parent;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) map[anc] = 1;
+  __syncthreads();
+  // ---- new ids: the marked nodes counted in ascending order of the old ones
+  int kept = 0;
+  for (int base = 0; base < nn; base += kCtcThreads) {
+    const int id = base + tid;
+    const bool on = id < nn && map[id] == 1;
+    const unsigned long long m = __ballot(on);
+    if (lane == 0) k.part[wave] = __popcll(m);
+    __syncthreads();
+    int mine = kept + __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < kCtcWaves; ++w) {
+      if (w < wave) mine += k.part[w];
+      kept += k.part[w];
+    }
+    if (id < nn) map[id] = on ? mine : -1;
+    __syncthreads();
+  }
+  // ---- the surviving nodes, their child lists filtered in order, into the staging copy
+  for (int id = tid; id < nn; id += kCtcThreads) {
+    const int nid = map[id];
+    if (nid < 0) continue;
+    const CtcNode o = nodes[id];
+    CtcNode nw{-1, -1, -1, -1};
+    int ch = o.first_child;
+    for (int hop = 0; ch >= 0 && ch < nn && map[ch] < 0; ++hop) ch = hop < nn ? nodes[ch].next_sibling : -1;
+    nw.first_child = ch >= 0 && ch < nn ? map[ch] : -1;
+    if (id != anc) {
+      nw.parent = o.parent >= 0 && o.parent < nn ? map[o.parent] : -1;
+      nw.token = o.token;
+      int sb = o.next_sibling;
+      for (int hop = 0; sb >= 0 && sb < nn && map[sb] < 0; ++hop) sb = hop < nn ? nodes[sb].next_sibling : -1;
+      nw.next_sibling = sb >= 0 && sb < nn ? map[sb] : -1;
+    }
+    stage[nid] = nw;
+  }
+  __syncthreads();
+  for (int id = tid; id < kept; id += kCtcThreads) nodes[id] = stage[id];
+  // ---- the beam goes home under its new node ids
+  if (tid < nb) {
+    const int r = b * BS + tid, id = s.node[tid];
+    const int nid = id >= 0 && id < nn ? map[id] : -1;
+    a.st.pb[r] = s.pb[tid];
+    a.st.pnb[r] = s.pnb[tid];
+    a.st.lm_sum[r] = s.lm_sum[tid];
+    a.st.node[r] = nid < 0 ? 0 : nid;
+    a.st.last[r] = s.last[tid];
+    a.st.len[r] = s.len[tid];
+  }
+  if (tid == 0) {
+    const int ovf = a.ovf[b] | (s.len[0] > a.max_tokens ? 1 : 0);
+    a.st.nb[b] = nb;
+    a.st.nnodes[b] = kept;
+    a.depth[b] = k.depth;
+    a.ovf[b] = ovf;
+    a.overflow[b] = ovf;
+    a.stable_len[b] = min(k.depth, a.max_tokens);
+  }
+}
+
+// grid B: rows[b] != 0 (NULL: every row) becomes the empty prefix; with an LM its state is zeroed and
+// the first LM step is asked for on row 0 of exactly those utterances
+__global__ __launch_bounds__(kCtcThreads) void ctc_stream_reset_kernel(CtcStreamArgs a, const int* rows,
+                                                                       int lm_start_token, int layers, int H,
+                                                                       float* h, float* c, float* q) {
+  const int b = blockIdx.x, tid = threadIdx.x, BS = a.c.beam, r = b * BS + tid;
+  const long R = (long)gridDim.x * BS;
+  const bool on = !rows || rows[b] != 0;
+  if (a.st.emit && tid < BS) {
+    a.st.emit[r] = on && tid == 0;
+    a.st.parent[r] = r;
+    a.st.token[r] = lm_start_token < 0 ? 0 : lm_start_token;
+  }
+  if (!on) return;
+  if (tid < BS) {
+    a.st.pb[r] = tid == 0 ? 0.f : S2T_NEG_INF;
+    a.st.pnb[r] = S2T_NEG_INF;
+    a.st.lm_sum[r] = 0.f;
+    a.st.node[r] = 0;
+    a.st.last[r] = -1;
+    a.st.len[r] = 0;
+  }
+  if (tid == 0) {
+    a.st.nb[b] = 1;
+    a.st.nnodes[b] = 1;
+    a.depth[b] = 0;
+    a.ovf[b] = 0;
+    a.eff[b] = 0;
+    a.c.nodes[(long)b * a.c.max_nodes] = CtcNode{-1, -1, -1, -1};
+  }
+  if (!h) return;
+  for (int l = 0; l < layers; ++l)
+    for (int x = tid; x < BS * H; x += kCtcThreads) {
+      h[(l * R + (long)b * BS) * H + x] = 0.f;
+      c[(l * R + (long)b * BS) * H + x] = 0.f;
+    }
+  for (long x = tid; x < (long)BS * a.c.V; x += kCtcThreads) q[(long)b * BS * a.c.V + x] = 0.f;
+}
+
+// the plain family: ONE launch, a workgroup per utterance, like ctc_prefix_kernel
+__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_chunk_kernel(CtcStreamArgs a) {
+  extern __shared__ float row[];
+  __shared__ CtcShared s;
+  __shared__ CtcCompact k;
+  const int b = blockIdx.x;
+  const int n = ctc_stream_admit(a, b);
+  if (n == 0) return;
+  CtcNode* nodes = a.c.nodes + (long)b * a.c.max_nodes;
+  const float* x = a.c.logits + (long)b * a.c.T * a.c.V;
+  load_beam(s, a.st, b, a.c.beam);
+  __syncthreads();
+  const int K = min(a.c.topk, a.c.V);
+  for (int t = 0; t < n; ++t)
+    ctc_frame<false>(s, row, x + (long)t * a.c.V, a.c.V, K, a.c.beam, a.c.blank, nodes, a.c.max_nodes, 0.f, nullptr,
+                     nullptr, nullptr, nullptr, 0);
+  ctc_stream_close(s, k, a, b);
+}
+
+// the LM family: what the rounds read as lengths, before them ...
+__global__ __launch_bounds__(64) void ctc_stream_begin_kernel(CtcStreamArgs a) {
+  const int b = blockIdx.x;
+  const int n = ctc_stream_admit(a, b);
+  if (threadIdx.x == 0) a.eff[b] = n;
+}
+
+// ... and outputs and compaction after them
+__global__ __launch_bounds__(kCtcThreads) void ctc_stream_end_kernel(CtcStreamArgs a) {
+  __shared__ CtcShared s;
+  __shared__ CtcCompact k;
+  const int b = blockIdx.x;
+  if (a.eff[b] <= 0) return;
+  load_beam(s, a.st, b, a.c.beam);
+  __syncthreads();
+  ctc_stream_close(s, k, a, b);
+}
+
+// after an odd Tc the survivors' LM state is in the workspace's copy: one launch takes it home
+struct CtcCopyHomeArgs {
+  const float* src[3];
+  float* dst[3];
+  long n[3];
+};
+
+__global__ __launch_bounds__(kCtcThreads) void ctc_lm_copy_home_kernel(CtcCopyHomeArgs a) {
+  const long step = (long)gridDim.x * kCtcThreads, i0 = (long)blockIdx.x * kCtcThreads + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    for (long i = i0; i < a.n[k]; i += step) a.dst[k][i] = a.src[k][i];
+}
+
+bool ctc_stream_ok(int V, int beam_size, int max_nodes) {
+  return V >= 1 && V <= S2T_RNNT_LSTM_MAX_VOCAB && beam_size >= 1 && beam_size <= kMaxBeam && max_nodes >= 1 &&
+         max_nodes <= S2T_CTC_STREAM_MAX_NODES;
+}
+
+CtcStreamArgs stream_args(const CtcStream& s, const float* logits, const long* chunk_len, int Tc, int V, int blank,
+                          int beam_size, int cutoff_top_k, int max_tokens, int max_nodes, long* tokens,
+                          long* out_len, float* score, float* lm_score, long* stable_len, int* overflow) {
+  return CtcStreamArgs{{logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_nodes, s.nodes, tokens, out_len,
+                        score},
+                       s.st, s.stage, s.map, s.depth, s.ovf, s.eff, max_tokens, lm_score, stable_len, overflow};
 }
 
 }  // namespace
@@ -261,6 +581,111 @@ int s2t_ctc_prefix_beam_lm(const S2tRnnLmDesc* lm, const float* logits, const lo
     cur ^= 1;
   }
   hipLaunchKernelGGL(ctc_lm_finish_kernel, dim3(B), dim3(64), 0, st, a);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------ the chunk-carried entries
+long s2t_ctc_stream_state_bytes(int B, int V, int beam_size, int max_nodes) {
+  if (B <= 0 || !ctc_stream_ok(V, beam_size, max_nodes)) return 0;
+  return (long)carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, nullptr).bytes;
+}
+
+int s2t_ctc_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes, void* stream) {
+  if (B <= 0) return 0;
+  if (!ctc_stream_ok(V, beam_size, max_nodes) || !state) return -1;
+  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state);
+  const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
+                                      nullptr, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows, -1, 0, 0,
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_ctc_prefix_beam_chunk(const float* logits, const long* chunk_len, int B, int Tc, int V, int blank,
+                              int beam_size, int cutoff_top_k, int max_tokens, int max_nodes, void* state,
+                              long* tokens, long* out_len, float* score, long* stable_len, int* overflow,
+                              void* stream) {
+  if (B <= 0) return 0;
+  if (Tc < 1 || Tc > 256 || !ctc_ok(Tc, V, blank, beam_size, cutoff_top_k) || max_tokens < 1 ||
+      !ctc_stream_ok(V, beam_size, max_nodes) || !state)
+    return -1;
+  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state);
+  const CtcStreamArgs a = stream_args(s, logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_tokens,
+                                      max_nodes, tokens, out_len, score, nullptr, stable_len, overflow);
+  hipLaunchKernelGGL(ctc_prefix_chunk_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, (hipStream_t)stream, a);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+long s2t_ctc_lm_stream_state_bytes(const S2tRnnLmDesc* lm, int B, int V, int beam_size, int max_nodes) {
+  if (B <= 0 || !ctc_stream_ok(V, beam_size, max_nodes) || !lm_desc_ok(lm, V)) return 0;
+  return (long)carve_ctc_stream(lm, B, V, beam_size, max_nodes, nullptr).bytes;
+}
+
+long s2t_ctc_prefix_beam_lm_chunk_workspace_bytes(const S2tRnnLmDesc* lm, int B, int V, int beam_size) {
+  if (B <= 0 || !ctc_stream_ok(V, beam_size, 1) || !lm_desc_ok(lm, V)) return 0;
+  return (long)carve_ctc_lm_stream_ws(*lm, B, beam_size, nullptr).bytes;
+}
+
+int s2t_ctc_lm_stream_reset(const S2tRnnLmDesc* lm, int lm_start_token, void* state, const int* rows, int B, int V,
+                            int beam_size, int max_nodes, void* workspace, void* stream) {
+  if (B <= 0) return 0;
+  if (!ctc_stream_ok(V, beam_size, max_nodes) || !lm_desc_ok(lm, V) || lm_start_token >= V || !state || !workspace)
+    return -1;
+  const CtcStream s = carve_ctc_stream(lm, B, V, beam_size, max_nodes, state);
+  const CtcLmStreamWorkspace w = carve_ctc_lm_stream_ws(*lm, B, beam_size, workspace);
+  const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
+                                      nullptr, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows,
+                     lm_start_token, lm->num_layers, lm->H, s.h, s.c, s.q);
+  if (lm_start_token >= 0) {                               // the one-shot entry's own first step, masked by rows
+    const int rc = s2t_rnn_lm_step(lm, B * beam_size, s.st.token, s.st.emit, nullptr, s.h, s.c, s.q, s.h, s.c, s.q,
+                                   w.step, stream);
+    if (rc != 0) return rc;
+  }
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_ctc_prefix_beam_lm_chunk(const S2tRnnLmDesc* lm, const float* logits, const long* chunk_len, int B, int Tc,
+                                 int V, int blank, int beam_size, int cutoff_top_k, float lm_weight,
+                                 int lm_start_token, int max_tokens, int max_nodes, void* state, void* workspace,
+                                 long* tokens, long* out_len, float* score, float* lm_score, long* stable_len,
+                                 int* overflow, void* stream) {
+  if (B <= 0) return 0;
+  if (Tc < 1 || Tc > 256 || !ctc_ok(Tc, V, blank, beam_size, cutoff_top_k) || max_tokens < 1 ||
+      !ctc_stream_ok(V, beam_size, max_nodes) || !lm_desc_ok(lm, V) || lm_start_token >= V ||
+      !__builtin_isfinite(lm_weight) || !state || !workspace)
+    return -1;
+  hipStream_t st = (hipStream_t)stream;
+  const int R = B * beam_size;
+  const CtcStream s = carve_ctc_stream(lm, B, V, beam_size, max_nodes, state);
+  const CtcLmStreamWorkspace w = carve_ctc_lm_stream_ws(*lm, B, beam_size, workspace);
+  const CtcStreamArgs sa = stream_args(s, logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_tokens,
+                                       max_nodes, tokens, out_len, score, lm_score, stable_len, overflow);
+  hipLaunchKernelGGL(ctc_stream_begin_kernel, dim3(B), dim3(64), 0, st, sa);
+  CtcLmArgs a{sa.c, s.st, s.q, lm_weight, 0, lm_start_token, lm_score};
+  a.c.lengths = s.eff;                                     // the rounds walk the frames this call consumes
+  float *h[2] = {s.h, w.h}, *c[2] = {s.c, w.c}, *q[2] = {s.q, w.q};
+  int cur = 0;
+  for (int t = 0; t < Tc; ++t) {
+    a.t = t;
+    a.q = q[cur];
+    hipLaunchKernelGGL(ctc_prefix_round_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, st, a);
+    const int rc = s2t_rnn_lm_step(lm, R, s.st.token, s.st.emit, s.st.parent, h[cur], c[cur], q[cur], h[cur ^ 1],
+                                   c[cur ^ 1], q[cur ^ 1], w.step, stream);   // (also after the last frame: the
+    if (rc != 0) return rc;                                                   // next chunk's frame 0 reads it)
+    cur ^= 1;
+  }
+  if (cur) {
+    const long ns = (long)lm->num_layers * R * lm->H, nq = (long)R * V;
+    const CtcCopyHomeArgs cp{{w.h, w.c, w.q}, {s.h, s.c, s.q}, {ns, ns, nq}};
+    const long most = ns > nq ? ns : nq, need = (most + kCtcThreads - 1) / kCtcThreads;
+    hipLaunchKernelGGL(ctc_lm_copy_home_kernel, dim3((int)(need < 1024 ? need : 1024)), dim3(kCtcThreads), 0, st, cp);
+  }
+  hipLaunchKernelGGL(ctc_stream_end_kernel, dim3(B), dim3(kCtcThreads), 0, st, sa);
   S2T_CHECK_LAUNCH();
   return 0;
 }

@@ -23,8 +23,9 @@ chunk-carried beam searches take the same LM (RnntLstmStreamingSearch with `lm=`
 RnntStatelessLmStreamingSearch; s2t_rnnt_beam_lstm_lm_chunk, s2t_rnnt_beam_stateless_lm_chunk).
 CtcPrefixBeamDecoding is a lexicon-free CTC prefix beam search with equal prefixes merged and the same
 optional RNN-LM term, on the device for the whole batch (csrc/decode_ctc.hip: s2t_ctc_prefix_beam,
-s2t_ctc_prefix_beam_lm).  The lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are
-not here."""
+s2t_ctc_prefix_beam_lm); CtcStreamingSearch carries that search across chunks with a trie that does
+not grow with the stream (s2t_ctc_prefix_beam_chunk, s2t_ctc_prefix_beam_lm_chunk).  The lexicon CTC
+beam decoder (it wraps flashlight) and the CIF decoder are not here."""
 import abc
 import math
 from enum import Enum, unique
@@ -1258,6 +1259,128 @@ def rnnt_streaming_search(predictor, joiner, batch_size=1, method="greedy", max_
                                               lm_start_token=lm_start_token, **kw)
     return RnntStreamingSearch(predictor, joiner, batch_size, method, max_token_step, beam_size,
                                cutoff_top_k, max_tokens, device, **kw)
+
+
+class CtcStreamingSearch:
+    """Chunk-carried CTC prefix beam search on the device (csrc/decode_ctc.hip s2t_ctc_prefix_beam_chunk,
+    with an `lm` s2t_ctc_prefix_beam_lm_chunk): ctc_prefix_beam_tokens / ctc_prefix_beam_lm_tokens fed the
+    frames' scores (B, Tc, V) a chunk at a time.  The frame body is the whole-utterance entries' own, so
+    however the frames are cut the result after a chunk is theirs on the frames fed so far, bit for bit,
+    while `overflow` is 0.  The trie is compacted at the end of every chunk to the paths between the live
+    prefixes' common ancestor and the live prefixes, so the state's size (`max_nodes` nodes a stream)
+    and a chunk's cost do not grow with the stream; a row needs `kept + beam_size * n <= max_nodes` to
+    consume n frames, else `overflow` gets bit 1 (value 2) and the row is inert until `reset`.  A best
+    prefix past `max_tokens` keeps its first `max_tokens` tokens, bit 0 (value 1).
+
+    Owns the state buffer and the fixed output tensors `tokens` (B, max_tokens), `out_len`, `score`,
+    `stable_len` (`tokens[b, :stable_len[b]]` can no longer change), `overflow` and, with an `lm`,
+    `lm_score` (else None).  `step` makes no host synchronisation, so it can be captured into a graph.
+    `method="greedy"` is beam_size = cutoff_top_k = 1 through the same kernel (ctc_greedy_tokens' tokens)
+    and takes no LM.  A shape the entries refuse, an `lm` that is not an RnnLm, or greedy with an `lm` is
+    a ValueError at construction: there is no host-loop fallback."""
+
+    def __init__(self, num_classes, batch_size=1, method="beam", beam_size=4, cutoff_top_k=4, max_tokens=1024,
+                 max_nodes=4096, blank=0, device=None, lm=None, lm_weight=0.0, lm_start_token=None):
+        if method not in ("greedy", "beam"):
+            raise ValueError(f"method must be 'greedy' or 'beam', got {method!r}")
+        self._lm, self._lm_weight, self._lm_start = _stream_lm_arguments(lm, lm_weight, lm_start_token, method)
+        dev = torch.device("cuda") if device is None else torch.device(device)
+        if dev.type != "cuda" or (self._lm is not None and self._lm._embedding.weight.device.type != "cuda"):
+            raise RuntimeError("the chunk-carried search runs on the GPU only: the LM and device must be cuda")
+        self.method, self.batch_size, self.V = method, int(batch_size), int(num_classes)
+        self.beam_size = int(beam_size) if method == "beam" else 1
+        self.cutoff_top_k = int(cutoff_top_k) if method == "beam" else 1
+        self.max_tokens, self.max_nodes, self.blank = int(max_tokens), int(max_nodes), int(blank)
+        B, V, lib = self.batch_size, self.V, N.lib()
+        top = N.const("S2T_RNNT_LSTM_MAX_BEAM")
+        ok = B > 0 and 0 <= self.blank < V and self.max_tokens >= 1 and self.cutoff_top_k >= 1 \
+            and min(self.cutoff_top_k, V) <= top
+        n, ws = 0, 1
+        self._lm_desc = None
+        if ok and self._lm is not None:
+            self._lm_desc, self._lm_keep = rnn_lm_desc(self._lm)
+            if self._lm_desc is not None and self._lm_start < V:
+                n = lib.s2t_ctc_lm_stream_state_bytes(self._lm_desc, B, V, self.beam_size, self.max_nodes)
+                ws = lib.s2t_ctc_prefix_beam_lm_chunk_workspace_bytes(self._lm_desc, B, V, self.beam_size)
+        elif ok:
+            n = lib.s2t_ctc_stream_state_bytes(B, V, self.beam_size, self.max_nodes)
+        if n <= 0 or ws <= 0:
+            raise ValueError(f"the chunk-carried CTC {method} search does not take this shape: B {B} V {V} blank "
+                             f"{self.blank} beam {self.beam_size} top-k {self.cutoff_top_k} max_tokens "
+                             f"{self.max_tokens} max_nodes {self.max_nodes}"
+                             + ("" if self._lm is None else f", with an LM of V {self._lm._num_symbols} "
+                                f"start token {self._lm_start}") + " (limits: include/s2t_mi355.h)")
+        self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        self._ws = None if self._lm is None else torch.zeros((ws,), dtype=torch.uint8, device=dev)
+        self.tokens = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
+        self.out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
+        self.score = torch.zeros((B,), dtype=torch.float32, device=dev)
+        self.stable_len = torch.zeros((B,), dtype=torch.int64, device=dev)
+        self.overflow = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.lm_score = None if self._lm is None else torch.zeros((B,), dtype=torch.float32, device=dev)
+        self._full = {}                                    # Tc -> chunk_len of a whole chunk
+        self.reset()
+
+    def reset(self, rows=None):
+        """Rows become the empty prefix; their outputs read zero until their next chunk.  The others
+        are not touched.  rows: None for all; a list of row indices (the mask is then built on the
+        host and copied over: not for a graph capture); or a device mask, an int32 tensor (B) on the
+        search's device with 1 for the rows to reset, which is used as it is -- then, as with None,
+        reset enqueues kernels only and can be captured."""
+        mask = None
+        if isinstance(rows, torch.Tensor) and rows.is_cuda:
+            if rows.dtype != torch.int32 or tuple(rows.shape) != (self.batch_size,):
+                raise ValueError(f"a device mask is int32 of shape ({self.batch_size},), got {rows.dtype} "
+                                 f"{tuple(rows.shape)}")
+            mask = rows.contiguous()
+        elif rows is not None:
+            mask = torch.zeros((self.batch_size,), dtype=torch.int32)
+            mask[torch.as_tensor(rows, dtype=torch.int64)] = 1
+            mask = mask.to(self.state.device)
+        B, V = self.batch_size, self.V
+        if self._lm is not None:
+            N.check(N.lib().s2t_ctc_lm_stream_reset(self._lm_desc, self._lm_start, N.ptr(self.state), N.ip(mask), B, V,
+                                                    self.beam_size, self.max_nodes, N.ptr(self._ws), N.stream()),
+                    "s2t_ctc_lm_stream_reset")
+        else:
+            N.check(N.lib().s2t_ctc_stream_reset(N.ptr(self.state), N.ip(mask), B, V, self.beam_size, self.max_nodes,
+                                                 N.stream()), "s2t_ctc_stream_reset")
+        outs = [self.tokens, self.out_len, self.score, self.stable_len, self.overflow]
+        if self.lm_score is not None:
+            outs.append(self.lm_score)
+        for t in outs:
+            if mask is None:
+                t.zero_()
+            else:
+                t.masked_fill_(mask.bool().reshape(-1, *[1] * (t.dim() - 1)), 0)
+
+    def step(self, logits_chunk, chunk_len=None):
+        """logits_chunk (B, Tc, V) fp32 on the device, raw or normalised, Tc <= 256; chunk_len (B) int64
+        on the device (None: Tc frames for every row; 0 leaves a row as it is).  -> (tokens, out_len,
+        score, stable_len): views of the fixed output tensors."""
+        B, V = self.batch_size, self.V
+        if logits_chunk.dim() != 3 or logits_chunk.shape[0] != B or logits_chunk.shape[2] != V \
+                or not 1 <= logits_chunk.shape[1] <= 256:
+            raise ValueError(f"expected logits of shape ({B}, 1..256, {V}), got {tuple(logits_chunk.shape)}")
+        Tc = logits_chunk.shape[1]
+        if chunk_len is None:
+            chunk_len = self._full.get(Tc)
+            if chunk_len is None:
+                chunk_len = self._full[Tc] = torch.full((B,), Tc, dtype=torch.int64, device=self.state.device)
+        if self._lm is not None:
+            N.check(N.lib().s2t_ctc_prefix_beam_lm_chunk(
+                self._lm_desc, N.fp(logits_chunk), N.lp(chunk_len), B, Tc, V, self.blank, self.beam_size,
+                self.cutoff_top_k, self._lm_weight, self._lm_start, self.max_tokens, self.max_nodes,
+                N.ptr(self.state), N.ptr(self._ws), N.lp(self.tokens), N.lp(self.out_len), N.fp(self.score),
+                N.fp(self.lm_score), N.lp(self.stable_len), N.ip(self.overflow), N.stream()),
+                "s2t_ctc_prefix_beam_lm_chunk")
+        else:
+            N.check(N.lib().s2t_ctc_prefix_beam_chunk(
+                N.fp(logits_chunk), N.lp(chunk_len), B, Tc, V, self.blank, self.beam_size, self.cutoff_top_k,
+                self.max_tokens, self.max_nodes, N.ptr(self.state), N.lp(self.tokens), N.lp(self.out_len),
+                N.fp(self.score), N.lp(self.stable_len), N.ip(self.overflow), N.stream()),
+                "s2t_ctc_prefix_beam_chunk")
+        return self.tokens, self.out_len, self.score, self.stable_len
 
 
 @unique

@@ -305,26 +305,41 @@ class StreamingRecognizer:
                  cutoff_top_k: int = 4, max_tokens: int = 1024, device=None, warmup: int = 2,
                  lm=None, lm_weight: float = 0.0, lm_start_token=None):
         from speech2text_amd.model.decoding import rnnt_streaming_search
+        model, device, lm = self._check_model(encoder, (predictor, joiner), tokenizer, batch_size, device, lm)
+        if model._for_ctc:
+            raise ValueError("StreamingRecognizer searches the encoder output: build the encoder with for_ctc=False")
+        self.joiner = joiner
+        self.search = rnnt_streaming_search(predictor, joiner, batch_size, method, max_token_step,
+                                            beam_size, cutoff_top_k, max_tokens, device, lm=lm,
+                                            lm_weight=lm_weight, lm_start_token=lm_start_token)
+        self._capture(model, cmvn, device, warmup, lambda enc: joiner._enc_proj(enc).float().contiguous())
+
+    def _check_model(self, encoder, heads, tokenizer, batch_size, device, lm):
+        """What every recogniser asks of its encoder (eval mode, on the GPU, causal with an even chunk)
+        and of the modules behind it (eval mode); sets the model, tokenizer and chunk geometry ->
+        (model, device, the LM on that device)."""
+        name = type(self).__name__
         model = getattr(encoder, "encoder", encoder)
-        if model.training or getattr(predictor, "training", False) or getattr(joiner, "training", False):
-            raise RuntimeError("StreamingRecognizer is an inference path: call .eval() first")
+        if model.training or any(getattr(h, "training", False) for h in heads):
+            raise RuntimeError(f"{name} is an inference path: call .eval() first")
         device = torch.device("cuda") if device is None else torch.device(device)
         if device.type != "cuda" or next(model.parameters()).device.type != "cuda":
-            raise RuntimeError("StreamingRecognizer runs on the HIP kernels: model and device must be cuda")
+            raise RuntimeError(f"{name} runs on the HIP kernels: model and device must be cuda")
         chunk = model.chunk_size[0]
         if chunk <= 0 or chunk % 2 or model.left_context_frames[0] < 0:
             raise ValueError("streaming needs a causal model with an even chunk_size > 0 and "
                              "left_context_frames >= 0")
-        if model._for_ctc:
-            raise ValueError("StreamingRecognizer searches the encoder output: build the encoder with for_ctc=False")
-        self.model, self.joiner, self.tokenizer = model, joiner, tokenizer
+        self.model, self.tokenizer = model, tokenizer
         self.batch_size, self.chunk, self.Tc = batch_size, chunk, chunk // 2
         self.frames = 2 * chunk + 13
         if lm is not None and hasattr(lm, "to"):           # (a frozen LM follows the model to its device)
             lm = lm.to(device)
-        self.search = rnnt_streaming_search(predictor, joiner, batch_size, method, max_token_step,
-                                            beam_size, cutoff_top_k, max_tokens, device, lm=lm,
-                                            lm_weight=lm_weight, lm_start_token=lm_start_token)
+        return model, device, lm
+
+    def _capture(self, model, cmvn, device, warmup, scores):
+        """The fixed buffers, then CMVN -> streaming_step -> `scores` (encoder output -> what the search
+        reads) -> self.search.step -> the state update, warmed up and captured as one graph."""
+        batch_size = self.batch_size
         self.x = torch.zeros(batch_size, self.frames, model._feature_dim, device=device)
         self.chunk_len = torch.full((batch_size,), self.Tc, dtype=torch.int64, device=device)
         self.states = get_init_states(model, batch_size, device)
@@ -336,7 +351,7 @@ class StreamingRecognizer:
         def chain(states):
             x = self.x if self._cmvn is None else (self.x - self._cmvn[0]) * self._cmvn[1]
             enc, new = streaming_step(model, x, states)
-            am = joiner._enc_proj(enc).float().contiguous()
+            am = scores(enc)
             return am, self.search.step(am, self.chunk_len), new
 
         side = torch.cuda.Stream(device)
@@ -369,7 +384,8 @@ class StreamingRecognizer:
     def step(self, x: Tensor, chunk_len=None):
         """x (B, 2*chunk+13, F); chunk_len (B) valid encoder frames of this chunk per row, 0..chunk//2
         (None: all).  -> greedy (tokens, out_len, am), beam (tokens, frames, out_len, score,
-        stable_len, am); am (B, chunk//2, V) is the chunk's joiner input."""
+        stable_len, am); am (B, chunk//2, V) is the chunk's joiner input.  (CtcStreamingRecognizer:
+        (tokens, out_len, score, stable_len, scores), scores being what its search read.)"""
         if tuple(x.shape) != tuple(self.x.shape):
             raise ValueError(f"expected input of shape {tuple(self.x.shape)}, got {tuple(x.shape)}")
         self.x.copy_(x)
@@ -425,3 +441,39 @@ class StreamingRecognizer:
             cl = (n_out - k * self.Tc).clamp(0, self.Tc)
             self.step(buf[:, 2 * self.chunk * k:2 * self.chunk * k + self.frames], cl)
         return self.texts()
+
+
+class CtcStreamingRecognizer(StreamingRecognizer):
+    """StreamingRecognizer for a CTC model: CMVN -> `streaming_step` -> the CTC scores -> the chunk-carried
+    prefix beam search (model/decoding.py CtcStreamingSearch) -> the encoder-state update, captured once
+    and replayed as ONE hipGraph per chunk.  The encoder is either built with for_ctc=True (its own
+    projection; `streaming_step` returns log-softmax scores) or with for_ctc=False and `head`, the CTC
+    task's Projector in eval mode, whose raw logits the search normalises itself.
+
+    Same surface: `reset`, `step`, `texts`, `stable_texts`, `num_output_frames`, `recognize`, the fixed
+    buffers `x`, `chunk_len`, `states`, and `search` with its outputs.  `step` returns (tokens, out_len,
+    score, stable_len, scores), scores (B, chunk//2, V) being what the search read.  method "beam" or
+    "greedy" (beam_size = cutoff_top_k = 1); with `lm` (an RnnLm; beam only) the chunk call is fused with
+    it (`lm_weight`, `lm_start_token` as CtcPrefixBeamDecoding's) and `search.lm_score` holds the best
+    prefixes' unweighted LM sums.  `max_nodes`: trie nodes per stream (CtcStreamingSearch)."""
+
+    def __init__(self, encoder, tokenizer, head=None, cmvn=None, batch_size: int = 1, method: str = "beam",
+                 beam_size: int = 4, cutoff_top_k: int = 4, max_tokens: int = 1024, max_nodes: int = 4096,
+                 blank: int = 0, device=None, warmup: int = 2, lm=None, lm_weight: float = 0.0,
+                 lm_start_token=None):
+        from speech2text_amd.model.decoding import CtcStreamingSearch
+        model, device, lm = self._check_model(encoder, (head,), tokenizer, batch_size, device, lm)
+        if model._for_ctc == (head is not None):
+            raise ValueError("CtcStreamingRecognizer searches CTC scores: build the encoder with for_ctc=True and "
+                             "pass no head, or with for_ctc=False and pass the task's Projector as head")
+        if head is None:
+            num_classes = model._ctc_projection.out_features
+            scores = lambda enc: enc.float().contiguous()                                   # noqa: E731
+        else:
+            num_classes = head._fc.out_features
+            scores = lambda enc: head(enc, self.chunk_len)[0].float().contiguous()          # noqa: E731
+        self.head = head
+        self.search = CtcStreamingSearch(num_classes, batch_size, method, beam_size, cutoff_top_k, max_tokens,
+                                         max_nodes, blank, device, lm=lm, lm_weight=lm_weight,
+                                         lm_start_token=lm_start_token)
+        self._capture(model, cmvn, device, warmup, scores)

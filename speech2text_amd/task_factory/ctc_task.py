@@ -45,3 +45,37 @@ class CtcTask(TaskBase):
         wer = self._wer(F.log_softmax(dec, dim=-1), dec_len, batch["label"])
         self.log_dict({"val_loss": loss, "wer": wer}, sync_dist=True, prog_bar=True)
         return {"val_loss": loss, "wer": wer}
+
+    def streaming_recognizer(self, batch_size=1, method=None, **kw):
+        """A CtcStreamingRecognizer (model/encoder/zipformer_streaming.py) over this task's encoder, CTC
+        head, tokenizer and global CMVN: features in, text out, a chunk at a time.  method ("greedy" |
+        "beam") comes from the `metric:` section's decode_method when not given (ctc_greedy_search /
+        ctc_prefix_beam_search), beam_size and cutoff_top_k from there too, and with `metric.lm` and the
+        beam method the search is shallow-fused with that LM (`metric.lm_weight`,
+        `metric.lm_start_token`), as the validation search is.  The task must be on the GPU and in eval
+        mode; its head is the encoder's own projection (for_ctc, Identity decoder) or the Projector."""
+        from speech2text_amd.model.decoder.decoder import Identity, Projector
+        from speech2text_amd.model.encoder.zipformer_streaming import CtcStreamingRecognizer
+        from speech2text_amd.model.utils import AsrMetricConfig
+        if self._tokenizer is None:
+            raise RuntimeError("streaming_recognizer needs the YAML's `tokenizer:` section")
+        head = self._decoder.decoder
+        if isinstance(head, Identity):
+            head = None
+        elif not isinstance(head, Projector):
+            raise NotImplementedError("streaming_recognizer serves the Identity and Projector decoders only")
+        cfg = AsrMetricConfig(**(self._metric_config or {}))
+        if method is None:
+            method = {"ctc_prefix_beam_search": "beam", "ctc_greedy_search": "greedy"}.get(cfg.decode_method)
+            if method is None:
+                raise ValueError(f"metric decode_method {cfg.decode_method!r} names no CTC search: pass method=")
+        for k in ("beam_size", "cutoff_top_k"):
+            kw.setdefault(k, getattr(cfg, k))
+        if method == "beam" and "lm" not in kw:            # the LM the validation search is fused with
+            lm = self._metric_lm()
+            if lm is not None:
+                kw["lm"] = lm
+                kw.setdefault("lm_weight", cfg.lm_weight)
+                kw.setdefault("lm_start_token", cfg.lm_start_token)
+        return CtcStreamingRecognizer(self._encoder, self._tokenizer, head=head, cmvn=self._global_cmvn,
+                                      batch_size=batch_size, method=method, **kw)
