@@ -43,6 +43,51 @@ int s2t_ctc_loss_fwd_bwd(const float* logits, const long* targets, long tgt_stri
                          int blank, int zero_infinity, const float* grad_scale, float* workspace,
                          float* loss_per_utt, float* grad_logits, void* stream);
 
+/* ---- CTC forced alignment: the best path of a known transcript over the frames, and from it token
+ * times (csrc/ctc_align.hip).  logits [B][T][V] batch-major, raw or already log-probabilities; targets
+ * [B][tgt_stride].  THE STATEMENT, for utterance b:
+ *   Tb = clamp(lengths[b], 0, T), U = max(tgt_len[b], 0) (and at most Umax); states s = 0..2U;
+ *   label(s) = blank for even s, targets[b][s>>1] for odd s;
+ *   e[t][s] = logits[b][t][label(s)], gathered exactly (a label outside [0, V) gives -inf); frames at or
+ *   beyond Tb are never read;
+ *   v[0][0] = e[0][0], v[0][1] = e[0][1], -inf elsewhere; for t >= 1  v[t][s] = m + e[t][s] (one fp32
+ *   add), m = max(c0, c1, c2) with c0 = v[t-1][s], c1 = v[t-1][s-1] (s >= 1), c2 = v[t-1][s-2] (only odd
+ *   s >= 3 with label(s) != label(s-2)); the backpointer is the FIRST maximum in the order stay, step,
+ *   skip: k = 0, then k = 1 if c1 > c0, then k = 2 if c2 > max(c0, c1);
+ *   end state 2U, unless U > 0 and !(v[Tb-1][2U] > v[Tb-1][2U-1]): then 2U-1;
+ *   feasible (ok = 1) when Tb > 0 and the end value is above -inf, or when Tb == 0 and U == 0 (the empty
+ *   path, raw_score = score = 0); the path follows the backpointers from the end state.
+ * A per-frame constant does not move the best path, so the recursion runs on the raw logits: a max and
+ * one fp32 add per step, which a float32 restatement on the host repeats bit for bit, ties included.
+ * Outputs (the caller's buffers; every element is written, none needs zeroing):
+ *   path [B][T] int: the lattice state of every frame, -1 at t >= Tb and on infeasible rows;
+ *   tok_begin, tok_end [B][Umax] int: the first frame at state 2u+1 and one past the last, -1 for u >= U
+ *   and on infeasible rows;
+ *   tok_logp [B][Umax]: sum of e[t][2u+1] - lse[t] over the token's frames in frame order in fp32, lse[t]
+ *   the row's log-sum-exp; 0 where there is no token;
+ *   raw_score [B]: the end value v (-inf on infeasible rows); score [B] = raw_score - sum_t lse[t], the
+ *   path's log-probability, -inf on infeasible rows; ok [B] int.
+ * Three launches on `stream` (rows, recursion + backtrace, token outputs), no host synchronisation, no
+ * memset, no atomics, no cooperative launch: the call can be captured in a graph.
+ * s2t_ctc_align_form(T, Umax) names the kernel form that serves a shape: the lattice states per thread
+ * of the recursion (1, 2, 4, 8, 16: 128 threads x that many cover 2 Umax + 1), plus
+ * S2T_CTC_ALIGN_FORM_WORKSPACE when the 2-bit backpointers of T frames (16 bytes per 64 states and
+ * frame, and 2 bytes of path per frame) exceed S2T_CTC_ALIGN_LDS_BYTES of LDS: then they are kept a
+ * block of frames at a time, full blocks go to the workspace and are staged back for the backtrace;
+ * otherwise they never leave LDS.  -1 for T <= 0 or Umax outside 0..S2T_CTC_MAX_LABELS.
+ * s2t_ctc_align_workspace_bytes: 0 for a shape the entry refuses.  Both are pure host functions.
+ * Returns as s2t_ctc_loss_fwd_bwd: B <= 0 returns 0; -1 for T <= 0, V <= 0, Umax < 0, blank outside
+ * [0, V), tgt_stride < Umax, a NULL workspace or output; -4 for Umax > S2T_CTC_MAX_LABELS; every refusal
+ * before any launch and without following a pointer. */
+#define S2T_CTC_ALIGN_LDS_BYTES 40960
+#define S2T_CTC_ALIGN_FORM_WORKSPACE 256
+long s2t_ctc_align_workspace_bytes(int B, int T, int Umax);
+int s2t_ctc_align_form(int T, int Umax);
+int s2t_ctc_align(const float* logits, const long* lengths, const long* targets, long tgt_stride,
+                  const long* tgt_len, int B, int T, int V, int Umax, int blank, void* workspace,
+                  int* path, int* tok_begin, int* tok_end, float* tok_logp, float* raw_score,
+                  float* score, int* ok, void* stream);
+
 /* ---- RNN-T lattice.  k2 call sites: model/joiner/joiner.py:100-123,
  * model/loss/pruned_rnnt_loss.py:39-48; torchaudio: model/loss/rnnt_loss.py:42-44.
  * am [B][T][C], lm [B][S+1][C], symbols [B][S], boundary [B][4]=(0,0,S_b,T_b),

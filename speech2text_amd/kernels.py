@@ -3,6 +3,7 @@
 Everything here runs on the HIP stream torch considers current; torch is used for
 device memory and autograd plumbing only.  There is no CPU path: CPU tensors raise.
 """
+import collections
 import math
 
 import numpy as np
@@ -147,6 +148,65 @@ def ctc_loss(logits, targets, logits_length, targets_length, blank=0, reduction=
     """Fused log_softmax + CTC on batch-major logits (B,T,V)."""
     return _CtcLoss.apply(logits, targets, logits_length, targets_length, blank, reduction,
                           zero_infinity)
+
+
+CtcAlignment = collections.namedtuple(
+    "CtcAlignment", ["path", "tok_begin", "tok_end", "tok_logp", "raw_score", "score", "ok"])
+CTC_ALIGN_FORM_WORKSPACE = N.const("S2T_CTC_ALIGN_FORM_WORKSPACE")
+
+
+def _align_check(t, dtype, what):
+    if not t.is_cuda or t.dtype is not dtype or not t.is_contiguous():
+        raise RuntimeError(f"ctc_align: {what} must be a contiguous {dtype} device tensor, got "
+                           f"{t.dtype} on {t.device}{'' if t.is_contiguous() else ', not contiguous'}")
+
+
+def ctc_align(logits, lengths, targets, target_lengths, blank=0, out=None):
+    """CTC forced alignment (csrc/ctc_align.hip; the statement is in include/s2t_mi355.h): logits (B,T,V)
+    fp32, raw or log-probabilities, lengths (B) int64, targets (B,U) int64, target_lengths (B) int64,
+    all contiguous on the device -> CtcAlignment(path (B,T) int32, tok_begin / tok_end (B,U) int32,
+    tok_logp (B,U) fp32, raw_score / score (B) fp32, ok (B) int32).  `out`: an earlier result of the same
+    shapes to write into again (no allocation besides the workspace)."""
+    _align_check(logits, torch.float32, "logits")
+    _align_check(lengths, torch.int64, "lengths")
+    _align_check(targets, torch.int64, "targets")
+    _align_check(target_lengths, torch.int64, "target_lengths")
+    if logits.dim() != 3 or targets.dim() != 2 or targets.shape[0] != logits.shape[0] \
+            or lengths.shape != (logits.shape[0],) or target_lengths.shape != (logits.shape[0],):
+        raise ValueError(f"ctc_align: logits (B,T,V), lengths (B), targets (B,U), target_lengths (B) expected, got "
+                         f"{tuple(logits.shape)}, {tuple(lengths.shape)}, {tuple(targets.shape)}, "
+                         f"{tuple(target_lengths.shape)}")
+    B, T, V = logits.shape
+    U = targets.shape[1]
+    dev = logits.device
+    if U > CTC_MAX_LABELS:
+        raise ValueError(f"CTC: padded label width {U} exceeds the kernel's limit of "
+                         f"{CTC_MAX_LABELS} labels per utterance (2U+1 lattice states are "
+                         "held in one workgroup's LDS, csrc/ctc_align.hip)")
+    if not 0 <= int(blank) < V:
+        raise ValueError(f"ctc_align: blank {blank} is outside the {V} classes")
+    if out is None:
+        i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)      # noqa: E731
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)    # noqa: E731
+        out = CtcAlignment(i32(B, T), i32(B, U), i32(B, U), f32(B, U), f32(B), f32(B), i32(B))
+    if B == 0 or T == 0:
+        out.path.fill_(-1), out.tok_begin.fill_(-1), out.tok_end.fill_(-1), out.tok_logp.zero_()
+        empty = target_lengths <= 0                        # no frames: only the empty transcript has a path
+        out.ok.copy_(empty)
+        out.raw_score.copy_(torch.where(empty, 0.0, _NEG_INF))
+        out.score.copy_(out.raw_score)
+        return out
+    ws = torch.empty(N.lib().s2t_ctc_align_workspace_bytes(B, T, U), dtype=torch.uint8, device=dev)
+    # an empty tensor has no address: the entry takes none of these as NULL, and writes nothing at U = 0
+    tok = [t if U else ws for t in (out.tok_begin, out.tok_end, out.tok_logp)]
+    N.PROF[0] and N.profile_note("s2t_ctc_align", 4.0 * B * T * V + 12.0 * B * T * (2 * U + 1) + 4.0 * B * T)
+    rc = N.lib().s2t_ctc_align(N.fp(logits), N.lp(lengths), N.lp(targets) if U else N.ptr(ws),
+                               targets.stride(0) if U else 0, N.lp(target_lengths), B, T, V, U, int(blank),
+                               N.ptr(ws), N.ip(out.path),
+                               tok[0].data_ptr(), tok[1].data_ptr(), tok[2].data_ptr(), N.fp(out.raw_score),
+                               N.fp(out.score), N.ip(out.ok), N.stream())
+    N.check(rc, "s2t_ctc_align")
+    return out
 
 
 # =============================================================== RNN-T lattice

@@ -46,6 +46,19 @@ class CtcTask(TaskBase):
         self.log_dict({"val_loss": loss, "wer": wer}, sync_dist=True, prog_bar=True)
         return {"val_loss": loss, "wer": wer}
 
+    @torch.no_grad()
+    def align(self, batch, frame_seconds=None):
+        """Forced alignment of batch["label"] / batch["label_length"] against this task's own logits
+        (features -> encoder -> decoder -> model/alignment.py CtcForcedAligner): one Alignment per
+        utterance with token spans in frames of the head's output, words where the task has a tokenizer,
+        and seconds where frame_seconds (the duration of one output frame) is given."""
+        from speech2text_amd.model.alignment import CtcForcedAligner
+        feat, feat_len = self.features(batch)
+        enc, enc_len = self._encoder(feat, feat_len)
+        dec, dec_len = self._decoder(enc, enc_len)
+        aligner = CtcForcedAligner(self._tokenizer, blank=0, frame_seconds=frame_seconds)
+        return aligner.align(dec, dec_len, batch["label"].to(dec.device), batch["label_length"].to(dec.device))
+
     def streaming_recognizer(self, batch_size=1, method=None, **kw):
         """A CtcStreamingRecognizer (model/encoder/zipformer_streaming.py) over this task's encoder, CTC
         head, tokenizer and global CMVN: features in, text out, a chunk at a time.  method ("greedy" |
