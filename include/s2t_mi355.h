@@ -181,6 +181,50 @@ int s2t_rnnt_lattice_bwd(const float* logits, const long* ranges, const long* sy
                          const float* gscale, int B, int S, int T, int V, int R, int blank,
                          int rnnt_type, float* d_logits, void* stream);
 
+/* ---- RNN-T forced alignment: the best path of a known transcript over the lattice, and from it the
+ * frame each token is emitted at (csrc/rnnt_align.hip).  px, py and boundary are exactly the operands of
+ * s2t_mutual_info_fwd: px [B][S][T+1] for REGULAR and [B][S][T] for MODIFIED / CONSTRAINED, py
+ * [B][S+1][T], boundary [B][4] of which only entries 2 and 3 are read.  THE STATEMENT, for utterance b:
+ *   Sb = clamp(boundary[b][2], 0, S), Tb = clamp(boundary[b][3], 0, T); cells (s, t) with 0 <= s <= Sb,
+ *   0 <= t <= Tb; v[0][0] = 0; a candidate with no predecessor is -inf;
+ *   REGULAR: cl = v[s][t-1] + py[s][t-1] (t >= 1), cu = v[s-1][t] + px[s-1][t] (s >= 1);
+ *   MODIFIED and CONSTRAINED (one recursion, as in the loss: the constrained px already carries its
+ *   blank): the same cl, cu = v[s-1][t-1] + px[s-1][t-1] (s >= 1 and t >= 1);
+ *   each candidate is one fp32 add; v[s][t] = max(cl, cu); the backpointer is the FIRST maximum in the
+ *   order blank, symbol: "symbol" exactly when cu > cl;
+ *   score[b] = v[Sb][Tb], ok[b] = score > -inf: Sb == Tb == 0 is the empty path with score 0, MODIFIED
+ *   with Sb > Tb has no path;
+ *   following the backpointers from (Sb, Tb), the symbol arc into row s + 1 gives tok_frame[b][s]: the
+ *   frame t it is on for REGULAR, t - 1 otherwise; tok_logp[b][s] is the px value on that arc, gathered
+ *   exactly.
+ * There is no multiply and no normaliser in the recursion, so a float32 restatement on the host repeats
+ * every output bit for bit, ties included.  A cell outside s <= Sb, t <= Tb is never read.
+ * Outputs (the caller's buffers; every element is written, none needs zeroing): tok_frame [B][S] int and
+ * tok_logp [B][S]: -1 and 0 for s >= Sb and on rows without a path; score [B]: -inf on such rows; ok [B]
+ * int.
+ * One launch on `stream`: one workgroup per utterance and one thread per lattice row (at most 1024
+ * rows, the recursion's limit); no host synchronisation, no memset, no atomics, no cooperative launch:
+ * the call can be captured in a graph.
+ * s2t_rnnt_align_form(S, T, rnnt_type) names the kernel form that serves a shape: the waves per
+ * workgroup, ceil((S + 1) / 64), plus S2T_RNNT_ALIGN_FORM_WORKSPACE when the backpointers of all the
+ * steps (S + T + 1 anti-diagonals for REGULAR, T frames otherwise; 8 bytes per step and wave) exceed
+ * S2T_RNNT_ALIGN_LDS_BYTES of LDS: then they are kept a block of
+ * S2T_RNNT_ALIGN_LDS_BYTES / (8 ceil((S + 1) / 64)) steps at a time (rounded down to whole groups of 8
+ * steps, the recursion's look-ahead), full blocks go to the workspace and are staged back for the backtrace; otherwise they never leave LDS and the workspace may be NULL.  -1
+ * for a shape the entry refuses.  s2t_rnnt_align_workspace_bytes: 0 for the LDS form and for a shape the
+ * entry refuses.  Both are pure host functions.
+ * Returns: B <= 0 returns 0; -1 for T <= 0, S < 0, an unknown rnnt_type, (S + 1) (T + 1) floats beyond
+ * 2 GiB (an utterance's operands are addressed by 32-bit offsets), a NULL output, a NULL workspace in
+ * the workspace form; -4 for S + 1 > 1024; every refusal before any launch and without following a
+ * pointer. */
+#define S2T_RNNT_ALIGN_LDS_BYTES 40960
+#define S2T_RNNT_ALIGN_FORM_WORKSPACE 256
+long s2t_rnnt_align_workspace_bytes(int B, int S, int T, int rnnt_type);
+int s2t_rnnt_align_form(int S, int T, int rnnt_type);
+int s2t_rnnt_align(const float* px, const float* py, const long* boundary, int B, int S, int T,
+                   int rnnt_type, void* workspace, int* tok_frame, float* tok_logp, float* score,
+                   int* ok, void* stream);
+
 
 /* ---- zipformer streaming ops (model/layer/scaling.py: Swoosh :1340-1509, BiasNorm
  * :347-476, Balancer backward :741-789 in closed form). */

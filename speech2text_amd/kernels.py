@@ -545,6 +545,107 @@ def rnnt_lattice_loss(logits, ranges, symbols, boundary, blank=0, rnnt_type="reg
     return _LatticeLoss.apply(logits, ranges, symbols, boundary, blank, ty, pen)
 
 
+def rnnt_full_lattice(am, lm, symbols, boundary, blank=0, activation="relu", rnnt_type="regular",
+                      delay_penalty=0.0):
+    """(px, py) of the FULL lattice of the fused joiner act(am[b,t,:] + lm[b,s,:]), never materialised:
+    s2t_rnnt_pruned_fwd with zero ranges and a band of all S+1 rows.  am (B,T,C), lm (B,S+1,C) fp32,
+    symbols (B,S) and boundary (B,4) int64 on the device -> px (B,S,T+1) on the regular lattice and
+    (B,S,T) on the two others, py (B,S+1,T).  No autograd: the operands of mutual_information and of
+    rnnt_align."""
+    ty, pen = check_rnnt_type(rnnt_type, delay_penalty)
+    _dev_check(am, lm)
+    am = am.contiguous().float()
+    lm = lm.contiguous().float()
+    B, T, C = am.shape
+    S = lm.shape[1] - 1
+    _check_lattice_rows(S)
+    if C > RNNT_MAX_JOINER_DIM:
+        raise ValueError(f"fused pruned joiner: joiner dimension {C} exceeds the kernel's limit of "
+                         f"{RNNT_MAX_JOINER_DIM} (a row is held in one wave's registers, csrc/rnnt.hip); "
+                         "there is no fallback")
+    dev = am.device
+    px, py, lse = _lattice_buffers(B, S, T, S + 1, ty, dev)
+    ranges = torch.zeros((B, T, S + 1), dtype=torch.int64, device=dev)     # (only each frame's first is read)
+    N.PROF[0] and N.profile_note("s2t_rnnt_pruned_fwd",
+                                 4.0 * (am.numel() + lm.numel() + px.numel() + py.numel() + lse.numel())
+                                 + 8.0 * ranges.numel())
+    N.check(N.lib().s2t_rnnt_pruned_fwd(N.fp(am), N.fp(lm), N.lp(ranges), N.lp(_i64(symbols, dev)),
+                                        N.lp(_i64(boundary, dev)), B, S, T, C, S + 1, int(blank),
+                                        _ACT[activation], ty, pen, N.fp(px), N.fp(py), N.fp(lse), N.stream()),
+            "pruned_fwd")
+    return px, py
+
+
+def rnnt_logits_lattice(logits, symbols, boundary, blank=0, rnnt_type="regular", delay_penalty=0.0):
+    """(px, py) of the full lattice of materialised logits (B,T,S+1,V): s2t_rnnt_lattice_fwd with
+    ranges NULL.  No autograd."""
+    ty, pen = check_rnnt_type(rnnt_type, delay_penalty)
+    _dev_check(logits)
+    logits = logits.contiguous().float()
+    B, T, R, V = logits.shape
+    S = symbols.shape[1]
+    if R != S + 1:
+        raise ValueError(f"rnnt_logits_lattice: logits {tuple(logits.shape)} are not the full lattice of "
+                         f"{S} symbols (B,T,S+1,V)")
+    _check_lattice_rows(S)
+    dev = logits.device
+    px, py, lse = _lattice_buffers(B, S, T, R, ty, dev)
+    N.PROF[0] and N.profile_note("s2t_rnnt_lattice_fwd",
+                                 4.0 * (logits.numel() + px.numel() + py.numel() + lse.numel()))
+    N.check(N.lib().s2t_rnnt_lattice_fwd(N.fp(logits), None, N.lp(_i64(symbols, dev)),
+                                         N.lp(_i64(boundary, dev)), B, S, T, V, R, int(blank), ty, pen,
+                                         N.fp(px), N.fp(py), N.fp(lse), N.stream()), "lattice_fwd")
+    return px, py
+
+
+RnntAlignment = collections.namedtuple("RnntAlignment", ["tok_frame", "tok_logp", "score", "ok"])
+
+
+def rnnt_align(px, py, boundary, rnnt_type="regular", out=None):
+    """RNN-T forced alignment (csrc/rnnt_align.hip; the statement is in include/s2t_mi355.h): the
+    operands of mutual_information -- px (B,S,T+1) for the regular lattice, (B,S,T) for 'modified' /
+    'constrained', py (B,S+1,T) fp32, boundary (B,4) int64, contiguous on the device ->
+    RnntAlignment(tok_frame (B,S) int32: the frame each symbol is emitted at, tok_logp (B,S) fp32: the
+    log-probability on that arc, score (B) fp32: the best path's, ok (B) int32).  `out`: an earlier result
+    of the same shapes to write into again (no allocation besides the workspace, where one is needed)."""
+    if rnnt_type not in RNNT_TYPES:
+        raise ValueError(f"rnnt_type {rnnt_type!r} is not one of 'regular', 'modified', 'constrained'")
+    ty = RNNT_TYPES[rnnt_type]
+    for t, dtype, what in ((px, torch.float32, "px"), (py, torch.float32, "py"), (boundary, torch.int64, "boundary")):
+        if not t.is_cuda or t.dtype is not dtype or not t.is_contiguous():
+            raise RuntimeError(f"rnnt_align: {what} must be a contiguous {dtype} device tensor, got "
+                               f"{t.dtype} on {t.device}{'' if t.is_contiguous() else ', not contiguous'}")
+    if px.dim() != 3 or py.dim() != 3:
+        raise ValueError(f"rnnt_align: px (B,S,T+1 or T) and py (B,S+1,T) expected, got {tuple(px.shape)}, "
+                         f"{tuple(py.shape)}")
+    B, S, TX = px.shape
+    T = py.shape[2]
+    if py.shape != (B, S + 1, T) or TX != (T + 1 if rnnt_type == "regular" else T) or boundary.shape != (B, 4):
+        raise ValueError(f"rnnt_align: px {tuple(px.shape)}, py {tuple(py.shape)} and boundary "
+                         f"{tuple(boundary.shape)} are not the (B,S,{'T+1' if rnnt_type == 'regular' else 'T'}), "
+                         f"(B,S+1,T), (B,4) operands of the {rnnt_type} lattice")
+    _check_lattice_rows(S)
+    dev = px.device
+    if out is None:
+        out = RnntAlignment(torch.empty((B, S), dtype=torch.int32, device=dev),
+                            torch.empty((B, S), dtype=torch.float32, device=dev),
+                            torch.empty((B,), dtype=torch.float32, device=dev),
+                            torch.empty((B,), dtype=torch.int32, device=dev))
+    if B == 0:
+        return out
+    if T == 0:
+        raise ValueError("rnnt_align: py has no frames; the lattice needs at least one (s2t_rnnt_align refuses T <= 0)")
+    nbytes = N.lib().s2t_rnnt_align_workspace_bytes(B, S, T, ty)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    # an empty tensor has no address: the entry takes no output as NULL, and writes nothing there at S = 0
+    tok = [t if S else ws for t in (out.tok_frame, out.tok_logp)]
+    N.PROF[0] and N.profile_note("s2t_rnnt_align", 4.0 * (px.numel() + py.numel()) + 8.0 * B * S)
+    rc = N.lib().s2t_rnnt_align(px.data_ptr(), N.fp(py), N.lp(boundary), B, S, T, ty, N.ptr(ws),
+                                tok[0].data_ptr(), tok[1].data_ptr(), N.fp(out.score), N.ip(out.ok), N.stream())
+    N.check(rc, "s2t_rnnt_align")
+    return out
+
+
 def make_boundary(target_lengths, frame_lengths, device):
     B = target_lengths.shape[0]
     b = torch.zeros((B, 4), dtype=torch.int64, device=device)

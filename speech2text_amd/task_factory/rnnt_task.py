@@ -31,6 +31,31 @@ class BaseRnntTask(TaskBase):
                     {"params": self._joiner.parameters(), "name": "joiner_lr", "lr": c["joiner_lr"]}]
         return self.parameters()
 
+    # what the joiner's encoder projection takes in this task's training step: decoder_out, or
+    # encoder_out where the decoder is the CTC head (CtcHybridRnnt)
+    _JOINS_ENCODER_OUT = False
+
+    def _align_rnnt_type(self) -> str:
+        """The lattice this task trains on: regular unless the loss configuration says otherwise."""
+        return "regular"
+
+    @torch.no_grad()
+    def align(self, batch, frame_seconds=None):
+        """Forced alignment of batch["label"] / batch["label_length"] on the frames of this task's own
+        RNN-T (features -> encoder -> decoder, then model/alignment.py RnntForcedAligner over the predictor
+        and the joiner): one Alignment per utterance; every token is emitted at one frame (begin, end =
+        begin + 1), words where the task has a tokenizer, seconds where frame_seconds (the duration of one
+        joiner input frame) is given.  The lattice is the one the task's loss trains on; a delay penalty is
+        a training device and never enters."""
+        from speech2text_amd.model.alignment import RnntForcedAligner
+        feat, feat_len = self.features(batch)
+        enc, enc_len = self._encoder(feat, feat_len)
+        dec, dec_len = self._decoder(enc, enc_len)
+        x, n = (enc, enc_len) if self._JOINS_ENCODER_OUT else (dec, dec_len)
+        aligner = RnntForcedAligner(self._predictor, self._joiner, self._tokenizer, blank=self._joiner.blank_token,
+                                    frame_seconds=frame_seconds, rnnt_type=self._align_rnnt_type())
+        return aligner.align(x, n, batch["label"].to(x.device), batch["label_length"].to(x.device))
+
 
 class RnntTask(BaseRnntTask):
     def __init__(self, config) -> None:
@@ -69,6 +94,7 @@ class RnntTask(BaseRnntTask):
 
 class CtcHybridRnnt(BaseRnntTask):
     """Shared encoder, CTC head on decoder_out, RNN-T branch on encoder_out (reference :287-420)."""
+    _JOINS_ENCODER_OUT = True
 
     def __init__(self, config) -> None:
         super().__init__(config)
@@ -132,6 +158,9 @@ class PrunedRnntTask(BaseRnntTask):
         if self._enable_ctc:
             self._ctc_loss = Loss({"model": "CTC", "config": {**self._loss_config["ctc_config"]}})
             self._ctc_projector = Decoder(config["ctc_projector"])
+
+    def _align_rnnt_type(self) -> str:
+        return (self._loss_config.get("config") or {}).get("rnnt_type", "regular")
 
     def _optimizer_params(self):
         """reference rnnt_task.py:596-630: the CTC head is a fifth group when enable_ctc."""

@@ -1,0 +1,336 @@
+"""CPU: the conditions of tests/rnnt_align_cases.py on the restatement tests/rnnt_align_f64.py (float32 and
+float64 agree on ok and tok_frame on every utterance; every TIES case has a tied decision on a best path),
+the validity of every returned path, the best path against every path enumerated on small lattices and
+against the log-likelihood of the same operands, the host-side entries of csrc/rnnt_align.hip (sizes, forms,
+refusals: the library loads without a GPU), the aligner's host loop against the restatement and the
+aligner end to end on CPU modules with both tokenizers.
+"""
+import math
+import os
+
+import pytest
+import torch
+
+import lattice_types_f64 as LT
+import rnnt_align_cases as C
+import rnnt_align_f64 as A
+
+
+# ------------------------------------------------------------------ 1. the conditions
+@pytest.mark.parametrize("name", list(C.CASES))
+def test_float32_and_float64_restatements_agree(name):
+    ref, f32 = C.reference(name), C.restated(name)
+    assert len(ref) == len(f32) == C.CASES[name]["B"]
+    for b, (a, r) in enumerate(zip(f32, ref)):
+        assert a.ok == r.ok and a.tok_frame == r.tok_frame, (name, b)
+        assert a.ties == r.ties, (name, b)
+        assert a.tok_logp == r.tok_logp, (name, b)                       # gathered, never computed
+
+
+@pytest.mark.parametrize("name", C.TIES)
+def test_ties_cases_have_a_tied_decision_on_the_best_path(name):
+    ties = sum(r.ties for r in C.restated(name))
+    print(f"{name}: {ties} tied decisions on the best paths")
+    assert ties >= 1
+    for a, r in zip(C.restated(name), C.reference(name)):                # quantised: exact in both
+        assert a.score == r.score
+
+
+def test_cases_reach_what_they_are_for():
+    m, ref = C.make("s4_reg_inf_one_and_none"), C.reference("s4_reg_inf_one_and_none")
+    assert ref[0].ok and ref[0].tok_frame == [1, 1, 3, 5] and not ref[1].ok
+    ref = C.reference("s4_mod_inf_one_and_none")
+    assert ref[0].ok and ref[0].tok_frame == [0, 2, 3, 5] and not ref[1].ok
+    ref = C.reference("s3_t1_reg_all_at_frame0")                          # one frame: every token at frame 0
+    assert all(r.ok and r.tok_frame == [0, 0, 0] for r in ref)
+    assert not any(r.ok for r in C.reference("s2_t1_mod_infeasible"))
+    assert not any(r.ok for r in C.reference("s512_mod_infeasible"))
+    for name in ("s7_b17_mod_ragged", "s12_b33_con_ragged"):
+        m, ref = C.make(name), C.reference(name)
+        kinds = [C.CASES[name]["rows"][b % len(C.CASES[name]["rows"])] for b in range(m["B"])]
+        for b, k in enumerate(kinds):
+            sb, tb = m["sb"][b], m["tb"][b]
+            if k == "eq":                                                # Sb == Tb: the diagonal, a single path
+                assert sb == tb > 0 and ref[b].ok and ref[b].tok_frame == list(range(sb))
+            if k == "eq1":                                               # Sb == Tb + 1: none
+                assert sb == tb + 1 and not ref[b].ok
+            if k == "t0s0":                                              # the empty path
+                assert sb == tb == 0 and ref[b].ok and ref[b].score == 0.0 and ref[b].tok_frame == []
+            if k == "t0":
+                assert tb == 0 and sb > 0 and not ref[b].ok
+            if k == "above":
+                assert int(m["boundary"][b, 2]) > m["S"] and int(m["boundary"][b, 3]) > m["T"]
+            if k == "neg":
+                assert int(m["boundary"][b, 2]) < 0 and sb == 0 and tb == 0 and ref[b].ok
+    m, ref = C.make("s7_b17_reg_ragged"), C.reference("s7_b17_reg_ragged")
+    assert any(tb == 0 and sb > 0 for sb, tb in zip(m["sb"], m["tb"]))     # regular, no frames: px[.][0] is -inf
+    assert any(sb == 0 and tb > 0 and r.ok for sb, tb, r in zip(m["sb"], m["tb"], ref))
+    assert {c["B"] for c in C.CASES.values()} >= {1, 17, 33}
+    assert {c["S"] for c in C.CASES.values()} >= {0, 1, 63, 64, 127, 128, 255, 256, 511, 512, 1023}
+    assert {c["ty"] for c in C.CASES.values()} == set(LT.TYPES)
+    for name in C.CASES:                                                 # NaN wherever no cell is
+        m = C.make(name)
+        reg = m["ty"] == "regular"
+        for b in range(m["B"]):
+            sb, tb = m["sb"][b], m["tb"][b]
+            inside_x = m["px"][b, :sb, :tb + 1 if reg else tb]
+            assert not bool(torch.isnan(inside_x).any()) and not bool(torch.isnan(m["py"][b, :sb + 1, :tb]).any())
+            assert int(torch.isnan(m["px"][b]).sum()) == m["px"][b].numel() - inside_x.numel()
+            assert int(torch.isnan(m["py"][b]).sum()) == m["py"][b].numel() - (sb + 1) * tb
+
+
+# ------------------------------------------------------------------ 2. every path is a path
+@pytest.mark.parametrize("name", list(C.CASES))
+def test_paths_are_valid_and_score_what_they_say(name):
+    m = C.make(name)
+    reg = m["ty"] == "regular"
+    clamped = LT.make_boundary(m["sb"], m["tb"])
+    zero_nan = lambda x: torch.where(torch.isnan(x), 0.0, x.double())     # noqa: E731  (-inf stays -inf)
+    ll = LT.scores(zero_nan(m["px"]), zero_nan(m["py"]), clamped)
+    for b, r in enumerate(C.reference(name)):
+        sb, tb = m["sb"][b], m["tb"][b]
+        assert len(r.tok_frame) == sb and len(r.tok_logp) == sb
+        assert r.ok == bool(ll[b] > -math.inf), (name, b)                # a path for one is a path for the other
+        if not r.ok:
+            assert r.score == -math.inf and r.tok_frame == [-1] * sb and r.tok_logp == [0.0] * sb
+            continue
+        f = r.tok_frame
+        assert all(0 <= x < max(tb, 1) for x in f) and (tb > 0 or sb == 0), (name, b)    # within [0, Tb)
+        assert all(p <= q for p, q in zip(f, f[1:]))                     # non-decreasing
+        if not reg:
+            assert all(p < q for p, q in zip(f, f[1:])), (name, b)       # one token per frame
+        again = A.path_score(m["px"][b], m["py"][b], sb, tb, f, m["ty"])
+        assert abs(again - r.score) <= 1e-9 * max(1.0, abs(r.score)), (name, b)
+        assert r.tok_logp == [float(m["px"][b, s, f[s]]) for s in range(sb)]
+        assert r.score <= float(ll[b]) + 1e-9 * max(1.0, abs(float(ll[b]))), (name, b)   # one term of the sum
+
+
+@pytest.mark.parametrize("rnnt_type", LT.TYPES)
+def test_best_path_is_the_best_of_all_paths_on_small_lattices(rnnt_type):
+    g = torch.Generator().manual_seed(13)
+    reg = rnnt_type == "regular"
+    for S, T, Sb, Tb in ((0, 1, 0, 1), (1, 1, 1, 1), (2, 3, 2, 3), (4, 5, 4, 5), (4, 5, 3, 2), (3, 4, 3, 4),
+                         (4, 4, 4, 4), (4, 3, 4, 3), (3, 5, 0, 5), (2, 2, 2, 0)):
+        px = 2.0 * torch.randn(S, T + 1 if reg else T, generator=g, dtype=torch.float64) - 1.0
+        py = 2.0 * torch.randn(S + 1, T, generator=g, dtype=torch.float64) - 1.0
+        if reg:
+            px[:, Tb] = -math.inf
+        best = A.enumerate_best(px, py, Sb, Tb, rnnt_type)
+        r = A.align(px, py, Sb, Tb, rnnt_type)
+        assert r.ok == (best > -math.inf), (S, T, Sb, Tb)
+        if r.ok:
+            assert abs(r.score - best) < 1e-12, (S, T, Sb, Tb)
+            assert abs(A.path_score(px, py, Sb, Tb, r.tok_frame, rnnt_type) - best) < 1e-12
+
+
+# ------------------------------------------------------------------ 3. the host side of the entry
+def _lib():
+    from speech2text_amd import _native as N
+    return N, N.lib()
+
+
+def _ty(name):
+    from speech2text_amd import kernels
+    return kernels.RNNT_TYPES[name]
+
+
+def test_workspace_size_and_form_are_pure_host_functions():
+    N, lib = _lib()
+    budget, ws = N.const("S2T_RNNT_ALIGN_LDS_BYTES"), N.const("S2T_RNNT_ALIGN_FORM_WORKSPACE")
+    assert ws == C._WS and budget == 40960
+    assert set(C.FORMS) == set(C.CASES)
+    for name, want in C.FORMS.items():
+        m = C.make(name)
+        assert lib.s2t_rnnt_align_form(m["S"], m["T"], _ty(m["ty"])) == want, name
+        steps = m["S"] + m["T"] + 1 if m["ty"] == "regular" else m["T"]
+        waves = want & (ws - 1)
+        assert lib.s2t_rnnt_align_workspace_bytes(m["B"], m["S"], m["T"], _ty(m["ty"])) == \
+            (8 * m["B"] * steps * waves if want & ws else 0), name
+    assert {f & (ws - 1) for f in C.FORMS.values()} >= {1, 2, 3, 4, 5, 8, 9, 16}
+    assert {f & (ws - 1) for f in C.FORMS.values() if f & ws} >= {1, 3, 4, 16}
+    reg, mod, con = _ty("regular"), _ty("modified"), _ty("constrained")
+    for S in (0, 5, 63, 64, 255, 256, 1023):                              # the edge is where the header says
+        fb = budget // (8 * ((S + 1 + 63) // 64))
+        if fb - S - 1 >= 1:                                               # (1023 rows never fit on the regular lattice)
+            assert lib.s2t_rnnt_align_form(S, fb - S - 1, reg) & ws == 0
+        assert lib.s2t_rnnt_align_form(S, max(1, fb - S), reg) & ws == ws
+        for ty in (mod, con):
+            assert lib.s2t_rnnt_align_form(S, fb, ty) & ws == 0 and lib.s2t_rnnt_align_form(S, fb + 1, ty) & ws == ws
+    assert budget // 8 == 5120 and budget // (8 * 4) == 1280 and budget // (8 * 16) == 320
+    for args in ((5, 0, reg), (-1, 5, reg), (1024, 5, reg), (5, 5, 3), (5, 5, -1)):
+        assert lib.s2t_rnnt_align_form(*args) == -1, args
+        assert lib.s2t_rnnt_align_workspace_bytes(2, *args) == 0, args
+    assert lib.s2t_rnnt_align_workspace_bytes(0, 5, 6000, reg) == 0
+
+
+@pytest.mark.parametrize("change, code", [
+    (dict(B=0), 0), (dict(B=-1), 0), (dict(T=0), -1), (dict(T=-3), -1), (dict(S=-1), -1), (dict(ty=3), -1),
+    (dict(ty=-1), -1), (dict(null="tok_frame"), -1), (dict(null="tok_logp"), -1), (dict(null="score"), -1),
+    (dict(null="ok"), -1), (dict(T=6000, null="ws"), -1), (dict(S=1024), -4), (dict(S=1024, ty=1), -4),
+    (dict(S=1023, T=2 ** 20), -1)], ids=str)
+def test_refusals_come_before_any_launch_and_follow_no_pointer(change, code):
+    """Every data pointer is NULL or an address nothing is mapped at: a refusal that followed one, or
+    launched anything, would not return."""
+    _, lib = _lib()
+    bad = 8                                                  # never dereferenced
+    a = dict(B=2, S=4, T=5, ty=0)
+    a.update({k: v for k, v in change.items() if k != "null"})
+    out = {k: bad for k in ("ws", "tok_frame", "tok_logp", "score", "ok")}
+    if "null" in change:
+        out[change["null"]] = None
+    rc = lib.s2t_rnnt_align(bad, bad, bad, a["B"], a["S"], a["T"], a["ty"], out["ws"], out["tok_frame"], out["tok_logp"],
+                            out["score"], out["ok"], None)
+    assert rc == code
+
+
+def test_python_surface_refuses_host_tensors_and_unknown_types():
+    from speech2text_amd import kernels
+    px, py, bnd = torch.zeros(1, 2, 5), torch.zeros(1, 3, 4), torch.tensor([[0, 0, 2, 4]])
+    with pytest.raises(RuntimeError, match="device tensor"):
+        kernels.rnnt_align(px, py, bnd)
+    with pytest.raises(ValueError, match="rnnt_type"):
+        kernels.rnnt_align(px, py, bnd, rnnt_type="simple")
+    with pytest.raises(RuntimeError, match="GPU only"):
+        kernels.rnnt_full_lattice(torch.zeros(1, 4, 8), torch.zeros(1, 3, 8), torch.zeros(1, 2, dtype=torch.int64), bnd)
+
+
+# ------------------------------------------------------------------ 4. the aligner's host loop
+@pytest.mark.parametrize("name", ["s0_b17_mod_ragged", "s7_b17_reg_ragged", "s7_b17_mod_ragged", "s12_b33_con_ragged",
+                                  "s4_reg_inf_one_and_none", "s4_mod_inf_one_and_none", "ties_s6_b17_mod", "ties_s64_reg",
+                                  "s64_con", "s3_t1_reg_all_at_frame0"])
+def test_aligner_host_loop_is_the_restatement(name):
+    from speech2text_amd.model.alignment import RnntForcedAligner
+    m = C.make(name)
+    al = RnntForcedAligner(None, None, rnnt_type=m["ty"])
+    rows = al._rows(m["px"], m["py"], m["boundary"])                      # NaN outside the cells: never read
+    tf, lp, score, ok = C.dense(C.restated(name), m["S"])
+    assert torch.equal(rows.ok, ok) and torch.equal(rows.tok_frame, tf)
+    assert torch.equal(rows.tok_logp.double(), lp) and torch.equal(rows.score.double(), score)
+
+
+def test_module_loop_serves_lattices_beyond_the_kernels_rows():
+    from speech2text_amd.model.alignment import RnntForcedAligner
+    g = torch.Generator().manual_seed(2)
+    S, T = 1024, 3
+    px, py = torch.randn(S, T + 1, generator=g), torch.randn(S + 1, T, generator=g)
+    px[:, T] = -math.inf
+    r = RnntForcedAligner._module_loop(px, py, S, T, "regular")
+    want = A.align(px, py, S, T, "regular")
+    assert r.ok and r.tok_frame.tolist() == want.tok_frame and r.score == want.score
+
+
+# ------------------------------------------------------------------ 5. the aligner end to end on CPU modules
+class _TinyPredictor(torch.nn.Module):
+    """Called as the training step calls a predictor: (labels (B,S), lengths, state) -> ((B,S+1,D), ...)."""
+
+    def __init__(self, V, D):
+        super().__init__()
+        self.emb, self.lin = torch.nn.Embedding(V, 8), torch.nn.Linear(16, D)
+
+    def init_state(self):
+        return None
+
+    def forward(self, labels, lengths, state):
+        x = self.emb(torch.nn.functional.pad(labels, (2, 0)))            # two blanks of left context
+        return torch.tanh(self.lin(torch.cat([x[:, :-1], x[:, 1:]], dim=2))), lengths, None
+
+
+class _TinyJoiner(torch.nn.Module):
+    """Called as the training step calls a joiner without pruning: -> ((B,T,S+1,V) logits, None, None, None)."""
+
+    def __init__(self, V, D, use_out_project):
+        super().__init__()
+        self.enc, self.pre = torch.nn.Linear(D, V), torch.nn.Linear(D, V)
+        self.out = torch.nn.Linear(V, V) if use_out_project else torch.nn.Identity()
+
+    def forward(self, enc, lens, pred, tl, target=None):
+        return self.out(torch.relu(self.enc(enc).unsqueeze(2) + self.pre(pred).unsqueeze(1))), None, None, None
+
+
+def _pair(V, use_out_project, D=16, seed=0):
+    """Plain torch modules: this package's own Linear runs on the device only."""
+    torch.manual_seed(seed)
+    return _TinyPredictor(V, D).eval(), _TinyJoiner(V, D, use_out_project).eval()
+
+
+@pytest.mark.parametrize("rnnt_type", LT.TYPES)
+@pytest.mark.parametrize("use_out_project", [False, True])
+def test_aligner_end_to_end_is_the_best_path_of_the_modules_lattice(rnnt_type, use_out_project):
+    from speech2text_amd.model.alignment import RnntForcedAligner
+    V, D = 9, 16
+    pred, join = _pair(V, use_out_project)
+    g = torch.Generator().manual_seed(4)
+    enc = torch.randn(3, 7, D, generator=g)
+    lens, tl = torch.tensor([7, 5, 2]), torch.tensor([4, 0, 3])
+    targets = torch.randint(1, V - 1, (3, 4), generator=g)
+    al = RnntForcedAligner(pred, join, frame_seconds=0.04, rnnt_type=rnnt_type)
+    out = al.align(enc, lens, targets, tl)
+    with torch.no_grad():                                                # the lattice, by the modules' own forward
+        p = pred(targets, tl, pred.init_state())[0]
+        logits = join(enc, lens, p, tl)[0].double()
+    bnd = LT.make_boundary(tl, lens)
+    px, py = LT.typed_pxpy(logits, targets, None, bnd, 0, rnnt_type)
+    for b, a in enumerate(out):
+        sb, tb = int(tl[b]), int(lens[b])
+        want = A.align(px[b], py[b], sb, tb, rnnt_type)
+        assert a.ok == want.ok, (rnnt_type, b)
+        if not a.ok:
+            assert a.tokens == [] and a.words == [] and a.score == -math.inf
+            continue
+        f = [t.begin for t in a.tokens]
+        assert [t.token for t in a.tokens] == targets[b, :sb].tolist() and all(t.end == t.begin + 1 for t in a.tokens)
+        assert all(t.begin_s == t.begin * 0.04 and t.end_s == t.end * 0.04 and t.piece is None for t in a.tokens)
+        # the float32 path re-scored in float64 is the float64 optimum, up to what float32 can tell apart
+        again = A.path_score(px[b], py[b], sb, tb, f, rnnt_type)
+        assert again >= want.score - 2e-5 * max(1.0, abs(want.score)), (rnnt_type, b, again, want.score)
+        assert a.score == pytest.approx(want.score, rel=2e-5, abs=2e-5)
+    assert not out[2].ok if rnnt_type != "regular" else out[2].ok        # three tokens on two frames
+
+
+def test_align_text_gives_words_with_times_char_tokenizer():
+    from speech2text_amd.dataset.utils import CharTokenizer, CharTokenizerConfig
+    from speech2text_amd.model.alignment import RnntForcedAligner
+    tok = CharTokenizer(CharTokenizerConfig())
+    V = len(tok.labels) + 1                                              # (the predictor's start token)
+    pred, join = _pair(V, False)
+    g = torch.Generator().manual_seed(3)
+    enc = torch.randn(2, 30, 16, generator=g)
+    al = RnntForcedAligner(pred, join, tok, frame_seconds=0.04, rnnt_type="modified")
+    out = al.align_text(enc, torch.tensor([30, 4]), ["go to bed", "far too long for four frames"])
+    assert out[0].ok and [w.word for w in out[0].words] == ["go", "to", "bed"]
+    assert "".join(t.piece for t in out[0].tokens) == "go to bed"
+    w = out[0].words
+    assert all(a.end <= b.begin for a, b in zip(w, w[1:])) and w[0].begin >= 0 and w[-1].end <= 30
+    assert w[0].begin == out[0].tokens[0].begin and w[0].end == out[0].tokens[1].end     # "g", "o"
+    assert all(x.begin_s == x.begin * 0.04 and x.end_s == x.end * 0.04 for x in w)
+    assert not out[1].ok and out[1].tokens == [] and out[1].score == -math.inf
+    reg = RnntForcedAligner(pred, join, tok, rnnt_type="regular").align_text(enc, torch.tensor([30, 4]), ["go", "far too long"])
+    assert reg[1].ok and len(reg[1].tokens) == len("far too long")      # regular: tokens may share a frame
+    assert [t.begin for t in reg[1].tokens] == sorted(t.begin for t in reg[1].tokens)
+
+
+def test_align_words_with_a_subword_vocabulary(golden_dir):
+    from speech2text_amd.model.alignment import WORD_MARK, RnntForcedAligner
+    text = "the quick brown fox jumps"
+    root = os.path.join(golden_dir, "reference_configs", "sample_data", "spm")
+    try:
+        import sentencepiece  # noqa: F401
+        from speech2text_amd.dataset.utils import SubwordTokenizer, SubwordTokenizerConfig
+        tok = SubwordTokenizer(SubwordTokenizerConfig(os.path.join(root, "tokenizer.model"),
+                                                      os.path.join(root, "tokenizer.vocab")))
+    except ImportError:                                      # a stub with the same marks
+        class _Stub:
+            labels = ["<blank>", WORD_MARK + "the", WORD_MARK + "qu", "ick", WORD_MARK, "brown", WORD_MARK + "fox",
+                      WORD_MARK + "jump", "s"]
+
+            def encode(self, _):
+                return torch.arange(1, 9)
+        tok = _Stub()
+    V = len(tok.labels) + 1
+    pred, join = _pair(V, True, seed=1)
+    g = torch.Generator().manual_seed(6)
+    enc = torch.randn(1, 25, 16, generator=g)
+    out = RnntForcedAligner(pred, join, tok, frame_seconds=0.04).align_text(enc, torch.tensor([25]), [text])[0]
+    assert out.ok and [w.word for w in out.words] == text.split()
+    assert sum(w.logp for w in out.words) == pytest.approx(sum(t.logp for t in out.tokens), rel=1e-6)
+    assert out.words[0].begin == out.tokens[0].begin and out.words[-1].end == out.tokens[-1].end
