@@ -875,6 +875,51 @@ int s2t_ctc_prefix_beam_lm(const S2tRnnLmDesc* lm, const float* logits, const lo
                            int lm_start_token, void* workspace, long* tokens, long* out_len, float* score,
                            float* lm_score, void* stream);
 
+/* ---- Back-off n-gram language model over the model's own classes, and the CTC prefix beam search
+ * fused with it in ONE launch (csrc/ngram_lookup.h, csrc/ngram.hip, csrc/decode_ctc.hip; the host side
+ * and the ARPA reader are model/lm/ngram_lm.py).  The LM's state is one integer, a context node.
+ * Tables: ctx_begin [num_ctx + 1] (the arcs of context n are [ctx_begin[n], ctx_begin[n + 1])), ctx_fail
+ * [num_ctx] (the context with its oldest token dropped), ctx_backoff [num_ctx] (natural log), arc_token /
+ * arc_logp (natural log) / arc_next [num_arcs] (the longest suffix of context + token that is itself a
+ * context, precomputed on the host).  Context 0 is the root and is dense: exactly V arcs, arc c is class
+ * c.  The arcs of every other context are sorted by token, without duplicates.  The host validates the
+ * tables (NgramLm); the kernels trust them, and only clamp what they index with so that no table
+ * makes them read outside the arrays.
+ * THE SCORING STATEMENT, score(ctx, c) -> (logp, next):  acc = 0.f, n = ctx.  While n != 0: binary-search
+ * c among the arcs of n; found at arc a: return (acc + arc_logp[a], arc_next[a]); else acc += ctx_backoff[n],
+ * n = ctx_fail[n].  At the root return (acc + arc_logp[c], arc_next[c]).  fp32 adds in exactly this order;
+ * at most `order` hops (the loop is bounded by order whatever the tables hold, then the root answers).
+ * Limits (else -1 / size 0, before any launch and without following a device pointer): lm and each of
+ * its six pointers not NULL; 1 <= V <= S2T_RNNT_LSTM_MAX_VOCAB; order in 1..S2T_NGRAM_MAX_ORDER; num_ctx
+ * >= 1; num_arcs >= V. */
+#define S2T_NGRAM_MAX_ORDER 8
+typedef struct S2tNgramLmDesc {
+  int V, order, num_ctx, num_arcs;
+  const int *ctx_begin, *ctx_fail;
+  const float* ctx_backoff;
+  const int* arc_token;
+  const float* arc_logp;
+  const int* arc_next;
+} S2tNgramLmDesc;
+/* The statement for R independent rows in one launch: (logp[r], next[r]) = score(ctx[r], token[r]); a ctx
+ * outside [0, num_ctx) or a token outside [0, V) is clamped into it.  R <= 0 returns 0. */
+int s2t_ngram_score(const S2tNgramLmDesc* lm, int R, const int* ctx, const int* token, float* logp,
+                    int* next, void* stream);
+/* s2t_ctc_prefix_beam_lm's statement with two changes: q_p[c] is score(state_p, c).logp, and instead of an
+ * LM step a kept prefix that was not live takes the `next` its look-up returned.  A live prefix carries
+ * its context id; the empty prefix starts in start_ctx, so the first token is scored too; a candidate
+ * that lands on a live prefix keeps that prefix' lm_sum and state.  The look-up runs only for an
+ * extension that does not land on a live prefix.  There is no end-of-sentence term.  ONE launch, a
+ * workgroup per utterance, no host synchronisation (it can be captured in a graph); the workspace is
+ * the plain entry's (the tries).  lm_score [B] = the best prefix' lm_sum.  With lm_weight = 0 tokens,
+ * out_len and score are s2t_ctc_prefix_beam's bit for bit.  Refused (-1 / size 0): the plain entry's
+ * limits, the descriptor's limits above, lm.V != V, start_ctx outside [0, num_ctx), lm_weight not finite. */
+long s2t_ctc_prefix_beam_ngram_workspace_bytes(int B, int T, int V, int beam_size);
+int s2t_ctc_prefix_beam_ngram(const S2tNgramLmDesc* lm, const float* logits, const long* lengths, int B,
+                              int T, int V, int blank, int beam_size, int cutoff_top_k, float lm_weight,
+                              int start_ctx, void* workspace, long* tokens, long* out_len, float* score,
+                              float* lm_score, void* stream);
+
 /* ---- chunk-carried (streaming) CTC prefix beam search: the two searches above fed their frames in
  * pieces (csrc/decode_ctc.hip).  logits [B][Tc][V], Tc in 1..256; row b advances over the first n =
  * min(chunk_len[b], Tc) frames of the chunk and reads no later frame.  A frame is the one-shot entries'

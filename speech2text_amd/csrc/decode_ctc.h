@@ -15,10 +15,18 @@
 // the two-operand logaddexp (symmetric in its operands) leaves no summation order to choose.  Its
 // rank key is the smallest contributing slot: first contributing parent, staying before
 // extensions, class rank.
+//
+// The body stands once for three LM modes: none; RNN rows (q [beam][V] of the live prefixes, and emit /
+// parent / token for the LM step that follows the frame); n-gram (a live prefix also carries its
+// context id, the slot thread that would add q[i * V + c] runs the look-up of csrc/ngram_lookup.h instead
+// and records the `next` it returns beside clm, and a kept prefix that was not live takes that next:
+// nothing has to run between frames).  The n-gram mode's extra LDS is a struct of its own, so the
+// other modes' kernels keep the LDS and the arithmetic they had.
 #pragma once
 #include "common.h"
 #include "decode_common.h"
 #include "decode_records.h"
+#include "ngram_lookup.h"
 
 namespace s2t_dec {
 
@@ -26,6 +34,7 @@ constexpr int kCtcThreads = 256;
 constexpr int kCtcWaves = kCtcThreads / 64;
 constexpr int kCtcSlots = kMaxBeam * (kMaxBeam + 1);
 constexpr int kCtcNoKey = 0x7fffffff;
+constexpr int kCtcPlain = 0, kCtcRnn = 1, kCtcNgram = 2;   // the LM modes of ctc_frame
 
 struct alignas(16) CtcNode {
   int parent, token, first_child, next_sibling;
@@ -47,6 +56,12 @@ struct CtcShared {
   int par_node[kMaxBeam];          // node of a new prefix' parent
 };
 
+struct CtcNgramShared {            // the n-gram mode's part of the beam and of the candidates
+  NgramTables g;                   // (in LDS: ten scalar registers less to hold across the frame)
+  int state[kMaxBeam];             // a live prefix' context id
+  int cnext[kCtcSlots];            // the context a candidate is in when it is kept
+};
+
 // the empty prefix: pb = 0, pnb = -inf, the root node
 __device__ __forceinline__ void ctc_start(CtcShared& s, CtcNode* nodes) {
   if (threadIdx.x == 0) {
@@ -62,15 +77,17 @@ __device__ __forceinline__ void ctc_start(CtcShared& s, CtcNode* nodes) {
   }
 }
 
-// One frame x [V] (global) of one utterance; row: LDS [V].  LM: q [beam][V] are the rows of the live
+// One frame x [V] (global) of one utterance; row: LDS [V].  kCtcRnn: q [beam][V] are the rows of the live
 // prefixes (beam order); emit / parent / token [beam] receive what s2t_rnn_lm_step needs, parent as a
-// row of the whole batch (row0 + position).  All kCtcThreads threads call it; it begins and ends
-// with the beam in s consistent for every thread.
-template <bool LM>
+// row of the whole batch (row0 + position).  kCtcNgram: ng holds the tables and the context ids (else
+// NULL).  All kCtcThreads threads call it; it begins and ends with the beam in s (and ng) consistent
+// for every thread.
+template <int MODE>
 __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float* __restrict__ x, int V, int K,
                                           int BS, int blank, CtcNode* nodes, int max_nodes, float lm_weight,
                                           const float* __restrict__ q, int* emit, int* parent, int* token,
-                                          int row0) {
+                                          int row0, CtcNgramShared* ng = nullptr) {
+  constexpr bool LM = MODE != kCtcPlain;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nb = s.nb, K1 = K + 1, nc = nb * K1;
   // ---- the frame's log-softmax and its K classes, once for all prefixes
@@ -116,7 +133,8 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
     const float pb = s.pb[i], pnb = s.pnb[i], sc = log_add_precise(pb, pnb);
     const int last = s.last[i];
     float cpb = S2T_NEG_INF, cpnb = S2T_NEG_INF, clm = s.lm_sum[i];
-    int cnode = s.node[i], key = kCtcNoKey;
+    int cnode = s.node[i], key = kCtcNoKey, cnext = 0;
+    if (MODE == kCtcNgram) cnext = ng->state[i];
     if (j == 0) {
       for (int r = 0; r < K; ++r) {
         const int c = s.cls[r];
@@ -144,7 +162,12 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
         } else {
           cpnb = v;
           key = xs;
-          if (LM) clm += q[(long)i * V + c];
+          if (MODE == kCtcRnn) clm += q[(long)i * V + c];
+          if (MODE == kCtcNgram) {
+            const NgramHit h = ngram_score(ng->g, cnext, c);
+            clm += h.logp;
+            cnext = h.next;
+          }
         }
         cnode = id;
       }
@@ -154,6 +177,7 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
     s.clm[xs] = clm;
     s.cnode[xs] = cnode;
     s.ckey[xs] = key;
+    if (MODE == kCtcNgram) ng->cnext[xs] = cnext;
     s.ctot[xs] = LM ? cpnb + lm_weight * clm : cpnb;       // (an extension: pb = -inf; staying: below)
   }
   __syncthreads();
@@ -184,7 +208,7 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
   const int xs = tid < BS ? s.pick[tid] : -1;
   const bool kept = xs >= 0;
   float npb = 0.f, npnb = 0.f, nlm = 0.f;
-  int nnode = 0, nlast = 0, nlen = 0, npar = 0, src = tid, ext = 0;
+  int nnode = 0, nlast = 0, nlen = 0, npar = 0, src = tid, ext = 0, nstate = 0;
   if (kept) {
     src = xs / K1;
     const int j = xs - src * K1;
@@ -196,10 +220,11 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
     nlast = ext ? s.cls[j - 1] : s.last[src];
     nlen = s.len[src] + ext;
     npar = s.node[src];
+    if (MODE == kCtcNgram) nstate = ng->cnext[xs];
   }
   __syncthreads();
   if (s.pick[0] < 0) {                                     // no candidate at all (NaN input): the beam stays
-    if (LM && tid < BS) {
+    if (MODE == kCtcRnn && tid < BS) {
       emit[tid] = 0;
       parent[tid] = row0 + tid;
       token[tid] = 0;
@@ -214,8 +239,9 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
     s.last[tid] = nlast;
     s.len[tid] = nlen;
     s.par_node[tid] = npar;
+    if (MODE == kCtcNgram) ng->state[tid] = nstate;
   }
-  if (LM && tid < BS) {                                    // a prefix that was not live steps the LM
+  if (MODE == kCtcRnn && tid < BS) {                       // a prefix that was not live steps the LM
     emit[tid] = kept && ext;
     parent[tid] = row0 + src;
     token[tid] = kept && ext ? nlast : 0;

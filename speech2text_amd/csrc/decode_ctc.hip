@@ -11,6 +11,11 @@
 //                            parent / token), then s2t_rnn_lm_step on B * beam_size rows through two
 //                            alternating state buffers.  The beam lives in the workspace between
 //                            rounds.  A row past its length passes its state through.
+//   s2t_ctc_prefix_beam_ngram
+//                            the plain entry's one launch with a back-off n-gram LM: the frame body's
+//                            n-gram mode scores an extension by the look-up of csrc/ngram_lookup.h and a
+//                            kept prefix takes the context that look-up returned, so nothing runs
+//                            between frames.  The beam gains one int per prefix, in LDS.
 //   s2t_ctc_prefix_beam_chunk, s2t_ctc_prefix_beam_lm_chunk
 //                            the two above fed their frames in pieces: beam and trie in a caller-owned
 //                            state, the same frame body and round kernel, and at the end of every call
@@ -50,9 +55,40 @@ __global__ __launch_bounds__(kCtcThreads) void ctc_prefix_kernel(CtcArgs a) {
   __syncthreads();
   const int K = min(a.topk, a.V);
   for (int t = 0; t < Tb; ++t)
-    ctc_frame<false>(s, row, x + (long)t * a.V, a.V, K, a.beam, a.blank, nodes, a.max_nodes, 0.f, nullptr,
-                     nullptr, nullptr, nullptr, 0);
+    ctc_frame<kCtcPlain>(s, row, x + (long)t * a.V, a.V, K, a.beam, a.blank, nodes, a.max_nodes, 0.f, nullptr,
+                         nullptr, nullptr, nullptr, 0);
   ctc_finish(s, nodes, a.tokens + (long)b * a.T, a.out_len + b, a.score + b, nullptr, a.T, a.max_nodes);
+}
+
+// ------------------------------------------------------------------ the n-gram form: one launch
+struct CtcNgramArgs {
+  CtcArgs c;
+  NgramTables g;
+  float lm_weight;
+  int start_ctx;
+  float* lm_score;        // [B]
+};
+
+__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_ngram_kernel(CtcNgramArgs a) {
+  extern __shared__ float row[];
+  __shared__ CtcShared s;
+  __shared__ CtcNgramShared ng;
+  const int b = blockIdx.x;
+  const int Tb = (int)clamped_len(a.c.lengths, b, a.c.T);
+  CtcNode* nodes = a.c.nodes + (long)b * a.c.max_nodes;
+  const float* x = a.c.logits + (long)b * a.c.T * a.c.V;
+  ctc_start(s, nodes);
+  if (threadIdx.x == 0) {
+    ng.g = a.g;
+    ng.state[0] = a.start_ctx;
+  }
+  __syncthreads();
+  const int K = min(a.c.topk, a.c.V);
+  for (int t = 0; t < Tb; ++t)
+    ctc_frame<kCtcNgram>(s, row, x + (long)t * a.c.V, a.c.V, K, a.c.beam, a.c.blank, nodes, a.c.max_nodes,
+                         a.lm_weight, nullptr, nullptr, nullptr, nullptr, 0, &ng);
+  ctc_finish(s, nodes, a.c.tokens + (long)b * a.c.T, a.c.out_len + b, a.c.score + b, a.lm_score + b, a.c.T,
+             a.c.max_nodes);
 }
 
 // ------------------------------------------------------------------ the lockstep form
@@ -125,9 +161,9 @@ __global__ __launch_bounds__(kCtcThreads) void ctc_prefix_round_kernel(CtcLmArgs
   CtcNode* nodes = a.c.nodes + (long)b * a.c.max_nodes;
   load_beam(s, a.st, b, BS);
   __syncthreads();
-  ctc_frame<true>(s, row, a.c.logits + ((long)b * a.c.T + a.t) * a.c.V, a.c.V, min(a.c.topk, a.c.V), BS,
-                  a.c.blank, nodes, a.c.max_nodes, a.lm_weight, a.q + (long)b * BS * a.c.V, a.st.emit + b * BS,
-                  a.st.parent + b * BS, a.st.token + b * BS, b * BS);
+  ctc_frame<kCtcRnn>(s, row, a.c.logits + ((long)b * a.c.T + a.t) * a.c.V, a.c.V, min(a.c.topk, a.c.V), BS,
+                     a.c.blank, nodes, a.c.max_nodes, a.lm_weight, a.q + (long)b * BS * a.c.V, a.st.emit + b * BS,
+                     a.st.parent + b * BS, a.st.token + b * BS, b * BS);
   if (tid < s.nb) {
     a.st.pb[r] = s.pb[tid];
     a.st.pnb[r] = s.pnb[tid];
@@ -466,8 +502,8 @@ __global__ __launch_bounds__(kCtcThreads) void ctc_prefix_chunk_kernel(CtcStream
   __syncthreads();
   const int K = min(a.c.topk, a.c.V);
   for (int t = 0; t < n; ++t)
-    ctc_frame<false>(s, row, x + (long)t * a.c.V, a.c.V, K, a.c.beam, a.c.blank, nodes, a.c.max_nodes, 0.f, nullptr,
-                     nullptr, nullptr, nullptr, 0);
+    ctc_frame<kCtcPlain>(s, row, x + (long)t * a.c.V, a.c.V, K, a.c.beam, a.c.blank, nodes, a.c.max_nodes, 0.f,
+                         nullptr, nullptr, nullptr, nullptr, 0);
   ctc_stream_close(s, k, a, b);
 }
 
@@ -533,6 +569,26 @@ int s2t_ctc_prefix_beam(const float* logits, const long* lengths, int B, int T, 
   CtcArgs a{logits, lengths, T, V, blank, beam_size, cutoff_top_k, max_nodes_of(T, beam_size),
             static_cast<CtcNode*>(workspace), tokens, out_len, score};
   hipLaunchKernelGGL(ctc_prefix_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, (hipStream_t)stream, a);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+long s2t_ctc_prefix_beam_ngram_workspace_bytes(int B, int T, int V, int beam_size) {
+  return s2t_ctc_prefix_beam_workspace_bytes(B, T, V, beam_size);
+}
+
+int s2t_ctc_prefix_beam_ngram(const S2tNgramLmDesc* lm, const float* logits, const long* lengths, int B, int T,
+                              int V, int blank, int beam_size, int cutoff_top_k, float lm_weight, int start_ctx,
+                              void* workspace, long* tokens, long* out_len, float* score, float* lm_score,
+                              void* stream) {
+  if (B <= 0) return 0;
+  if (T <= 0 || !ctc_ok(T, V, blank, beam_size, cutoff_top_k) || !ngram_desc_ok(lm) || lm->V != V || start_ctx < 0 ||
+      start_ctx >= lm->num_ctx || !__builtin_isfinite(lm_weight) || !workspace)
+    return -1;
+  CtcNgramArgs a{{logits, lengths, T, V, blank, beam_size, cutoff_top_k, max_nodes_of(T, beam_size),
+                  static_cast<CtcNode*>(workspace), tokens, out_len, score},
+                 ngram_tables(*lm), lm_weight, start_ctx, lm_score};
+  hipLaunchKernelGGL(ctc_prefix_ngram_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, (hipStream_t)stream, a);
   S2T_CHECK_LAUNCH();
   return 0;
 }

@@ -23,9 +23,11 @@ chunk-carried beam searches take the same LM (RnntLstmStreamingSearch with `lm=`
 RnntStatelessLmStreamingSearch; s2t_rnnt_beam_lstm_lm_chunk, s2t_rnnt_beam_stateless_lm_chunk).
 CtcPrefixBeamDecoding is a lexicon-free CTC prefix beam search with equal prefixes merged and the same
 optional RNN-LM term, on the device for the whole batch (csrc/decode_ctc.hip: s2t_ctc_prefix_beam,
-s2t_ctc_prefix_beam_lm); CtcStreamingSearch carries that search across chunks with a trie that does
-not grow with the stream (s2t_ctc_prefix_beam_chunk, s2t_ctc_prefix_beam_lm_chunk).  The lexicon CTC
-beam decoder (it wraps flashlight) and the CIF decoder are not here."""
+s2t_ctc_prefix_beam_lm) and, in one launch again, a back-off n-gram over the model's classes
+(model/lm/ngram_lm.py NgramLm, s2t_ctc_prefix_beam_ngram); CtcStreamingSearch carries the plain and the
+RNN-LM search across chunks with a trie that does not grow with the stream (s2t_ctc_prefix_beam_chunk,
+s2t_ctc_prefix_beam_lm_chunk).  The lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are
+not here."""
 import abc
 import math
 from enum import Enum, unique
@@ -166,6 +168,37 @@ def ctc_prefix_beam_lm_tokens(logits, lengths, lm, lm_weight, beam_size=4, cutof
     return out
 
 
+def ctc_prefix_beam_ngram_tokens(logits, lengths, lm, lm_weight, beam_size=4, cutoff_top_k=4, blank=0):
+    """ctc_prefix_beam_tokens with back-off n-gram shallow fusion (lm: an NgramLm whose fp32 tables are on
+    the logits' device), in ONE launch: an extension is scored by the n-gram look-up inside the frame
+    body and a kept prefix carries the context that look-up returned.  The search starts in the LM's
+    own start context, so the first token is scored too.  -> (tokens, out_len, score (the acoustic
+    part), lm_score (B) fp32: the best prefix' unweighted LM sum), or None where the entry refuses.
+    HIP: decode_ctc.hip, ngram_lookup.h."""
+    logits, lengths, out = _ctc_prefix_arguments(logits, lengths)
+    B, T, V = logits.shape
+    out = out + (torch.zeros((B,), dtype=torch.float32, device=logits.device),)
+    if B == 0 or T == 0:
+        return out
+    if lm.device != logits.device:
+        raise RuntimeError(f"the n-gram tables are on {lm.device}, the logits on {logits.device}: NgramLm.to(device)")
+    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
+    n = N.lib().s2t_ctc_prefix_beam_ngram_workspace_bytes(B, T, V, beam_size)
+    if n <= 0:
+        return None
+    lm_desc, lm_keep = lm.desc()
+    ws = torch.empty((n,), dtype=torch.uint8, device=logits.device)
+    tokens, out_len, score, lm_score = out
+    rc = N.lib().s2t_ctc_prefix_beam_ngram(lm_desc, N.fp(logits), N.lp(lengths), B, T, V, int(blank), beam_size,
+                                           cutoff_top_k, float(lm_weight), int(lm.start_ctx), N.ptr(ws),
+                                           N.lp(tokens), N.lp(out_len), N.fp(score), N.fp(lm_score), N.stream())
+    del lm_keep
+    if rc == -1:
+        return None
+    N.check(rc, "s2t_ctc_prefix_beam_ngram")
+    return out
+
+
 def _logaddexp(a, b):
     """Of two Python floats; -inf is the empty sum."""
     if a == -math.inf:
@@ -176,6 +209,11 @@ def _logaddexp(a, b):
     return hi + math.log1p(math.exp(lo - hi))
 
 
+def _is_ngram(lm):
+    from speech2text_amd.model.lm.ngram_lm import NgramLm
+    return isinstance(lm, NgramLm)
+
+
 class CtcPrefixBeamDecoding(DecodingMethod):
     """Lexicon-free CTC prefix beam search (the reference's CTC beam decoder wraps a lexicon decoder of
     a library that is not here; this one searches the model's own classes).  A live prefix carries
@@ -183,10 +221,13 @@ class CtcPrefixBeamDecoding(DecodingMethod):
     `cutoff_top_k` classes by (logit descending, class ascending) extend every prefix, candidates that
     spell the same tokens are merged into one, the `beam_size` best survive.
 
-    With `lm` (an RnnLm, or anything with init_states / score_step) prefixes rank by their
+    With `lm` (an RnnLm, an NgramLm, or anything with init_states / score_step) prefixes rank by their
     log-probability plus `lm_weight` times the LM's log-probability of their tokens; `lm_start_token`
-    as in RnntBeamDecoding.  Device logits run the fused search (csrc/decode_ctc.hip; with an LM when it
-    is this project's RnnLm); CPU tensors, shapes the kernels refuse and foreign LMs run `_module_loop`.
+    as in RnntBeamDecoding.  An LM that has `start_scores` (NgramLm) scores the first token too, from
+    its own start state, and takes no `lm_start_token`.  Device logits run the fused search
+    (csrc/decode_ctc.hip; with an LM when it is this project's RnnLm, in lockstep rounds, or NgramLm, in
+    one launch, its tables following the logits to their device); CPU tensors, shapes the kernels
+    refuse and foreign LMs run `_module_loop`.
     `beam_tokens` returns (tokens, out_len, score) and with an LM a fourth tensor, the best prefix'
     unweighted LM sum."""
 
@@ -201,6 +242,8 @@ class CtcPrefixBeamDecoding(DecodingMethod):
             raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
         if self._beam_size < 1 or self._cutoff_top_k < 1:
             raise ValueError(f"beam_size and cutoff_top_k must be at least 1, got {beam_size!r}, {cutoff_top_k!r}")
+        if self._lm_start_token is not None and _is_ngram(lm):
+            raise ValueError("an NgramLm starts in its own <s> context: lm_start_token must be None")
 
     def _module_loop(self, hidden_states, blank=0):
         """(1,T,V) -> (tokens, score, lm_score) of the best prefix: the same search on the host.  The
@@ -215,7 +258,9 @@ class CtcPrefixBeamDecoding(DecodingMethod):
         info = {}                                          # live prefix -> (q as a list, LM state, lm_sum)
         if lm is not None:
             state, q = lm.init_states(1), [0.0] * V
-            if self._lm_start_token is not None:
+            if hasattr(lm, "start_scores"):                # (an n-gram scores the first token too)
+                q = lm.start_scores(state)[0].double().tolist()
+            elif self._lm_start_token is not None:
                 qt, state = lm.score_step(torch.full((1,), self._lm_start_token, dtype=torch.int64, device=dev),
                                           state)
                 q = qt[0].double().tolist()
@@ -273,6 +318,11 @@ class CtcPrefixBeamDecoding(DecodingMethod):
             return None
         if self._lm is None:
             return ctc_prefix_beam_tokens(hidden_states, inputs_length, self._beam_size, self._cutoff_top_k)
+        if _is_ngram(self._lm):
+            if self._lm.dtype != torch.float32:
+                return None
+            return ctc_prefix_beam_ngram_tokens(hidden_states, inputs_length, self._lm, self._lm_weight,
+                                                self._beam_size, self._cutoff_top_k)
         if not isinstance(self._lm, RnnLm):
             return None
         return ctc_prefix_beam_lm_tokens(hidden_states, inputs_length, self._lm, self._lm_weight, self._beam_size,
@@ -288,6 +338,8 @@ class CtcPrefixBeamDecoding(DecodingMethod):
             p = next(self._lm.parameters(), None)
             if p is not None and p.device != dev:
                 self._lm.to(dev)
+        elif _is_ngram(self._lm):
+            self._lm.to(dev)
         if fused:
             out = self._fused(hidden_states, inputs_length)
             if out is not None:
@@ -927,6 +979,9 @@ def _stream_lm_arguments(lm, lm_weight, lm_start_token, method):
     from speech2text_amd.model.lm.rnn_lm import RnnLm
     if method == "greedy":
         raise ValueError("the greedy searches take no language model: use method='beam' or lm=None")
+    if _is_ngram(lm):
+        raise ValueError("the chunk-carried searches are not fused with an NgramLm: the n-gram search is the "
+                         "whole-utterance CtcPrefixBeamDecoding only (pass an RnnLm, or lm=None)")
     if not isinstance(lm, RnnLm):
         raise ValueError(f"the chunk-carried search is fused with an RnnLm only, got {type(lm).__name__} "
                          "(there is no module-loop fallback here)")

@@ -32,7 +32,8 @@ class TaskBase(nn.Module):
         self._metric_lm_config = None
         if self._metric_config is not None and "lm" in self._metric_config:
             # metric: {lm: {config: {<RnnLmConfig>}, checkpoint: <path|null>}}: the language model the
-            # RNN-T beam search is shallow-fused with; the rest is AsrMetricConfig's
+            # beam searches are shallow-fused with, or {lm: {arpa: <path>, missing_logp: ..}}: a back-off
+            # n-gram over the tokenizer's pieces (CTC prefix beam search); the rest is AsrMetricConfig's
             self._metric_config = dict(self._metric_config)
             self._metric_lm_config = self._metric_config.pop("lm")
         self._metric = None
@@ -80,12 +81,22 @@ class TaskBase(nn.Module):
 
     def _metric_lm(self):
         """The frozen RnnLm of `metric.lm`, or None: built from `lm.config`, loaded from the `_nnlm.*`
-        keys of a checkpoint the NNLM task wrote when `lm.checkpoint` names one.  The caller hands it
+        keys of a checkpoint the NNLM task wrote when `lm.checkpoint` names one.  With `lm.arpa` instead
+        the NgramLm of that ARPA file over the task's tokenizer (`lm.missing_logp` for a class without
+        a unigram).  The caller hands it
         to the metric object; it is never an attribute of the task, so the task's state_dict(),
         parameters() and optimizer groups do not know it.  It follows the inputs to their device on
         first use (model/decoding.py)."""
         if not self._metric_lm_config:
             return None
+        if self._metric_lm_config.get("arpa"):
+            from speech2text_amd.model.lm.ngram_lm import NgramLm
+            if self._metric_lm_config.get("config") or self._metric_lm_config.get("checkpoint"):
+                raise ValueError("metric.lm names either an ARPA n-gram (arpa:) or an RNN LM (config:, checkpoint:)")
+            if self._tokenizer is None:
+                raise RuntimeError("metric.lm.arpa needs the YAML's `tokenizer:` section: its pieces are the words")
+            return NgramLm.from_arpa(self._metric_lm_config["arpa"], tokenizer=self._tokenizer,
+                                     missing_logp=self._metric_lm_config.get("missing_logp", -30.0))
         from speech2text_amd.model.lm.rnn_lm import RnnLm, RnnLmConfig
         with torch.random.fork_rng(devices=[]):            # its init draws nothing from the task's stream
             lm = RnnLm(config=RnnLmConfig(**(self._metric_lm_config.get("config") or {})))

@@ -86,6 +86,10 @@ class CtcTask(TaskBase):
             kw.setdefault(k, getattr(cfg, k))
         if method == "beam" and "lm" not in kw:            # the LM the validation search is fused with
             lm = self._metric_lm()
+            from speech2text_amd.model.lm.ngram_lm import NgramLm
+            if isinstance(lm, NgramLm):
+                raise ValueError("metric.lm names an ARPA n-gram: the chunk-carried CTC search is not fused with "
+                                 "it (pass lm=None or an RnnLm to stream without it)")
             if lm is not None:
                 kw["lm"] = lm
                 kw.setdefault("lm_weight", cfg.lm_weight)
