@@ -325,7 +325,9 @@ long s2t_zipconv_bwd_workspace_floats(int T, int B, int C, int K);
  * (dO_c, V_c) pairs (T,B,H*dv_c) whose outer products are contracted on the fly, so the
  * consumers' (H,B,T,T) gradients are never written; with factors, delta_ws (H,B,T) must hold
  * sum_j W*dW on entry (delta_given=1).  dqkp (T,B,Dp) and dpos fully written (dpos is cleared
- * by the entry point before the partial sums are added; the caller need not zero it). */
+ * by the entry point before the partial sums are added; the caller need not zero it).
+ * pd == 0 means "no position term" in forward and backward alike: `pos` is then ignored even when
+ * it is not NULL (the forward treats it as NULL, the backward writes neither dpos nor workspace). */
 int s2t_relpos_attn_fwd(const float* qkp, const float* pos, const unsigned char* kpm,
                         const unsigned char* amask, int T, int B, int H, int qd, int pd, float* W,
                         void* stream);

@@ -1234,6 +1234,10 @@ extern "C" int s2t_relpos_attn_fwd_flag(const float* qkp, const float* pos,
                                         float pen_limit, float* pen_flag, void* stream) {
   if (T <= 0 || B <= 0 || H <= 0) return 0;
   if (qd <= 0 || qd > MAXQD || pd < 0 || pd > MAXPD) return -1;
+  // pd == 0: there are no p columns, so the position term is skipped whatever `pos` is (as the
+  // backward's `pos && pd > 0`).  Staging a window for it would divide by pd (general kernel) or
+  // read p_row(...)[0], one float past the last row of qkp (MFMA kernel).
+  if (pd == 0) pos = nullptr;
   AttnArgs a{qkp, pos, kpm, amask, T, B, H, qd, pd, nullptr, nullptr, {nullptr, nullptr},
              {nullptr, nullptr}, {0, 0}, pen_limit, pen_flag};
   hipStream_t st = (hipStream_t)stream;

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+import zipattn_f64 as ZR
 from oracle import zipformer as Z
 
 pytestmark = pytest.mark.gpu
@@ -245,21 +246,9 @@ def test_biasnorm_backward_ragged_shapes(dev, rows, D):
 
 
 def _attn_ref(qkp, pos, H, qd, pd, amask, kpm):
-    T, B, _ = qkp.shape
-    q = qkp[..., :H * qd].reshape(T, B, H, qd).permute(2, 1, 0, 3)
-    k = qkp[..., H * qd:2 * H * qd].reshape(T, B, H, qd).permute(2, 1, 3, 0)
-    p = qkp[..., 2 * H * qd:].reshape(T, B, H, pd).permute(2, 1, 0, 3)
-    s = torch.matmul(q, k)
-    if pos is not None:
-        pe = pos.reshape(1, 2 * T - 1, H, pd).permute(2, 0, 3, 1)
-        ps = torch.matmul(p, pe)
-        idx = (T - 1) - torch.arange(T).unsqueeze(1) + torch.arange(T).unsqueeze(0)
-        s = s + ps[:, :, torch.arange(T).unsqueeze(1), idx]
-    if amask is not None:
-        s = s.masked_fill(amask, -1000)
-    if kpm is not None:
-        s = s.masked_fill(kpm.unsqueeze(1), -1000)
-    return s.softmax(dim=-1)
+    """The yardstick of tests/test_gpu_zip_attn_kernels.py (tests/zipattn_f64.py, pinned against the oracle's
+    attn_weights and its autograd by tests/test_zipattn_f64.py)."""
+    return ZR.attn_weights(qkp, pos, kpm, amask, H, qd, pd)[0]
 
 
 @pytest.mark.parametrize("T,B,H,qd,pd,dvs,use_dw0,use_am", [
