@@ -922,6 +922,55 @@ int s2t_ctc_prefix_beam_ngram(const S2tNgramLmDesc* lm, const float* logits, con
                               int start_ctx, void* workspace, long* tokens, long* out_len, float* score,
                               float* lm_score, void* stream);
 
+/* ---- The n-gram above fused into the one-workgroup RNN-T beam search (csrc/decode_search.h beam_walk's
+ * n-gram mode; csrc/decode_beam.hip, csrc/decode_stream.hip).  s2t_rnnt_beam_stateless's statement with
+ * the LM term of s2t_rnnt_beam_lstm_lm: a live beam also carries a context id and lm_sum; the cutoff_top_k
+ * classes of a beam are chosen as there (the LM does not enter the cut); the candidate of class c !=
+ * blank of a beam in context n takes (q, next) = score(n, c) of THE SCORING STATEMENT above, scores
+ * (beam score + lp) + lm_weight * q in fp32, in this order, sums lm_sum + q, and a kept beam takes next;
+ * a blank candidate carries no LM term and no look-up and keeps its parent's context and lm_sum.  The
+ * look-ups of a frame run a thread per candidate, at most beam_size * cutoff_top_k <= 256.  Ranking,
+ * selection, records, predictor states and lm rows are unchanged.  The empty hypothesis starts in
+ * start_ctx, so the first token is scored too; there is no end-of-sentence term.  ONE launch, a workgroup
+ * per utterance, no host synchronisation (it can be captured in a graph); the workspace is the plain
+ * entry's.  lm_score [B] = the best beam's lm_sum, so that score = (RNN-T path score) + lm_weight *
+ * lm_score up to the order of the adds; a zero-length utterance gives no tokens, score 0 and lm_score 0.
+ * With lm_weight = 0 tokens, frames, out_len and score are s2t_rnnt_beam_stateless's bit for bit.
+ * Refused (-1 / size 0, before any launch and without following a pointer): what s2t_rnnt_beam_stateless
+ * refuses, the descriptor's limits above, lm.V != V, start_ctx outside [0, num_ctx), lm_weight not
+ * finite, lm_score NULL. */
+long s2t_rnnt_beam_ngram_workspace_bytes(int B, int T, int V, int beam_size);
+int s2t_rnnt_beam_stateless_ngram(const S2tNgramLmDesc* lm, const float* am, const long* lengths,
+                                  const float* emb, const float* conv_w, const float* lin_w,
+                                  const float* lin_b, const float* pre_w, const float* pre_b, int B, int T,
+                                  int V, int E, int D, int ctx, int act, int blank, int beam_size,
+                                  int cutoff_top_k, float lm_weight, int start_ctx, void* workspace,
+                                  long* tokens, long* frames, long* out_len, float* score, float* lm_score,
+                                  void* stream);
+/* The search above fed its frames in pieces: s2t_rnnt_beam_stateless_chunk's contract word for word
+ * (idle rows keep state and outputs, stable_len, the max_tokens saturation and overflow, Tc in 1..256,
+ * reset of chosen rows only), with lm_score [B] beside score.  The frame body is the one-shot kernel's
+ * own, so for ANY cut tokens, frames, out_len, score and lm_score after a chunk are
+ * s2t_rnnt_beam_stateless_ngram's on the frames fed so far, bit for bit.
+ * state: s2t_rnnt_ngram_stream_state_bytes(B, V, ctx, beam_size, max_tokens) bytes, beam_size in 1..16 (0
+ * for what s2t_rnnt_stream_state_bytes refuses, and for beam_size 0: there is no greedy form).  A row is
+ * the plain beam row of s2t_rnnt_stream_state_bytes, unchanged, followed by ctx [beam_size] int32, the
+ * beams' context ids, and lm_sum [beam_size] fp32, padded to a multiple of 256.
+ * s2t_rnnt_ngram_stream_reset: s2t_rnnt_stream_reset, and the one beam of a reset row starts in start_ctx
+ * with lm_sum 0; -1 as well for start_ctx < 0 (reset sees no tables: a chunk call clamps the context ids
+ * it loads into [0, num_ctx)).  The chunk call refuses what s2t_rnnt_beam_stateless_chunk and, of the LM
+ * arguments, s2t_rnnt_beam_stateless_ngram refuse. */
+long s2t_rnnt_ngram_stream_state_bytes(int B, int V, int ctx, int beam_size, int max_tokens);
+int s2t_rnnt_ngram_stream_reset(void* state, const int* rows, int B, int V, int ctx, int beam_size,
+                                int max_tokens, int blank, int start_ctx, void* stream);
+int s2t_rnnt_beam_stateless_ngram_chunk(const S2tNgramLmDesc* lm, const float* am, const long* chunk_len,
+                                        const float* emb, const float* conv_w, const float* lin_w,
+                                        const float* lin_b, const float* pre_w, const float* pre_b, int B,
+                                        int Tc, int V, int E, int D, int ctx, int act, int blank,
+                                        int beam_size, int cutoff_top_k, float lm_weight, int max_tokens,
+                                        void* state, long* tokens, long* frames, long* out_len, float* score,
+                                        float* lm_score, long* stable_len, int* overflow, void* stream);
+
 /* ---- chunk-carried (streaming) CTC prefix beam search: the two searches above fed their frames in
  * pieces (csrc/decode_ctc.hip).  logits [B][Tc][V], Tc in 1..256; row b advances over the first n =
  * min(chunk_len[b], Tc) frames of the chunk and reads no later frame.  A frame is the one-shot entries'

@@ -21,6 +21,8 @@
 // After the last frame the best beam (position 0) is traced back through the records
 // (decode_records.h trace_best, which also holds the record, the ranking of B and the limits).
 // lm [beam_size][V] lives in LDS when it fits and in the workspace (L2 resident) when it does not.
+// s2t_rnnt_beam_stateless_ngram is the same walk in beam_walk's n-gram mode (decode_search.h): between A
+// and B a thread per candidate adds lm_weight x the back-off n-gram's look-up, C carries the context id.
 #include "common.h"
 #include "decode_search.h"
 
@@ -96,7 +98,76 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_kernel(BeamArgs a) {
                        a.frames + (long)b * a.T);
 }
 
+// ---- the same search fused with a back-off n-gram (ngram_lookup.h): beam_walk's n-gram mode.  A beam
+// also carries a context id and the unweighted sum of its look-ups; nothing runs between frames.
+struct BeamNgramArgs {
+  BeamArgs c;
+  NgramTables g;
+  float lm_weight;
+  int start_ctx;
+  float* lm_score;        // [B]
+};
+
+template <bool CACHE>
+__global__ __launch_bounds__(kThreads) void rnnt_beam_ngram_kernel(BeamNgramArgs a) {
+  extern __shared__ float sm[];
+  __shared__ BeamShared s;
+  __shared__ RnntNgramShared ng;
+
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int V = a.c.V, BS = a.c.beam;
+  float* e = sm;                                           // [kGroup][E]
+  float* h = e + kGroup * a.c.E;                           // [kGroup][D]
+  int* state = reinterpret_cast<int*>(h + kGroup * a.c.D); // [2][kMaxBeam][ctx], most recent last
+  float* lm = a.c.lm_in_lds ? reinterpret_cast<float*>(state + 2 * kMaxBeam * a.c.ctx)
+                            : a.c.lm_spill + (long)b * BS * V;
+  const int Tb = (int)clamped_len(a.c.lengths, b, a.c.T);
+  if (Tb == 0) {                                           // no frames: no tokens, score 0, lm_score 0
+    if (tid == 0) {
+      a.c.out_len[b] = 0;
+      a.c.score[b] = 0.f;
+      a.lm_score[b] = 0.f;
+    }
+    return;
+  }
+  const float* amb = a.c.am + (long)b * a.c.T * V;
+  int* rec = a.c.records + (long)b * a.c.T * BS;
+
+  // one beam: no tokens, score 0, ctx blanks, the LM's start context, no LM sum
+  for (int k = tid; k < a.c.ctx; k += kThreads) state[k] = a.c.blank;
+  if (tid == 0) {
+    s.score[0][0] = 0.f;
+    s.slot[0][0] = 0;
+    s.len[0][0] = 0;
+    s.emit[0] = 0;
+    ng.g = a.g;
+    ng.ctx[0][0] = a.start_ctx;
+    ng.lm_sum[0][0] = 0.f;
+  }
+  __syncthreads();
+  recompute_lm(a.c, s.emit, 1, state, s.slot[0], e, h, lm);
+  int nb = 1, cur = 0;
+  beam_walk<CACHE, kLmNgram>(a.c, s, amb, Tb, nb, cur, e, h, state, lm,
+                             [&](int t, int pos, int r) { rec[(long)t * BS + pos] = r; }, &ng, a.lm_weight);
+
+  const int n = s.len[cur][0];
+  if (tid == 0) {
+    a.c.out_len[b] = n;
+    a.c.score[b] = s.score[cur][0];
+    a.lm_score[b] = ng.lm_sum[cur][0];
+  }
+  trace_best<kThreads>(rec, Tb, BS, a.c.blank, n, s.trace, &s.nemit, a.c.tokens + (long)b * a.c.T,
+                       a.c.frames + (long)b * a.c.T);
+}
+
 size_t records_bytes(int B, int T, int beam) { return align256(sizeof(int) * (size_t)B * T * beam); }
+
+// what s2t_rnnt_beam_stateless refuses of its shape
+bool beam_shape_ok(int T, int V, int E, int D, int ctx, int act, int blank, int beam_size, int cutoff_top_k) {
+  return T > 0 && V > 0 && V <= 8192 && E > 0 && D > 0 && ctx >= 1 && ctx <= 64 && act >= 0 && act <= 1 &&
+         blank >= 0 && blank < V && beam_size >= 1 && beam_size <= kMaxBeam && cutoff_top_k >= 1 &&
+         (cutoff_top_k < V ? cutoff_top_k : V) <= kMaxBeam && beam_fixed_lds(E, D, ctx) <= kLdsBudget;
+}
 
 }  // namespace
 
@@ -112,12 +183,8 @@ extern "C" int s2t_rnnt_beam_stateless(const float* am, const long* lengths, con
                                        int cutoff_top_k, void* workspace, long* tokens, long* frames,
                                        long* out_len, float* score, void* stream) {
   if (B <= 0) return 0;
-  if (T <= 0 || V <= 0 || V > 8192 || E <= 0 || D <= 0 || ctx < 1 || ctx > 64 || act < 0 ||
-      act > 1 || blank < 0 || blank >= V || beam_size < 1 || beam_size > kMaxBeam ||
-      cutoff_top_k < 1 || (cutoff_top_k < V ? cutoff_top_k : V) > kMaxBeam || !workspace)
-    return -1;
+  if (!beam_shape_ok(T, V, E, D, ctx, act, blank, beam_size, cutoff_top_k) || !workspace) return -1;
   const size_t fixed = beam_fixed_lds(E, D, ctx);
-  if (fixed > kLdsBudget) return -1;
   const size_t lm_bytes = sizeof(float) * (size_t)beam_size * V;
   const int lm_in_lds = fixed + lm_bytes <= kLdsBudget;
   char* ws = static_cast<char*>(workspace);
@@ -130,6 +197,39 @@ extern "C" int s2t_rnnt_beam_stateless(const float* am, const long* lengths, con
     hipLaunchKernelGGL(rnnt_beam_kernel<true>, dim3(B), dim3(kThreads), smem, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(rnnt_beam_kernel<false>, dim3(B), dim3(kThreads), smem, (hipStream_t)stream, a);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" long s2t_rnnt_beam_ngram_workspace_bytes(int B, int T, int V, int beam_size) {
+  if (V > 8192 || beam_size > kMaxBeam) return 0;
+  return s2t_rnnt_beam_workspace_bytes(B, T, V, beam_size);
+}
+
+extern "C" int s2t_rnnt_beam_stateless_ngram(const S2tNgramLmDesc* lm, const float* am, const long* lengths,
+                                             const float* emb, const float* conv_w, const float* lin_w,
+                                             const float* lin_b, const float* pre_w, const float* pre_b, int B,
+                                             int T, int V, int E, int D, int ctx, int act, int blank,
+                                             int beam_size, int cutoff_top_k, float lm_weight, int start_ctx,
+                                             void* workspace, long* tokens, long* frames, long* out_len,
+                                             float* score, float* lm_score, void* stream) {
+  if (B <= 0) return 0;
+  if (!beam_shape_ok(T, V, E, D, ctx, act, blank, beam_size, cutoff_top_k) || !ngram_desc_ok(lm) || lm->V != V ||
+      start_ctx < 0 || start_ctx >= lm->num_ctx || !__builtin_isfinite(lm_weight) || !workspace || !lm_score)
+    return -1;
+  const size_t fixed = beam_fixed_lds(E, D, ctx);
+  const size_t lm_bytes = sizeof(float) * (size_t)beam_size * V;
+  const int lm_in_lds = fixed + lm_bytes <= kLdsBudget;
+  char* ws = static_cast<char*>(workspace);
+  BeamNgramArgs a{{am, lengths, emb, conv_w, lin_w, lin_b, pre_w, pre_b, T, V, E, D, ctx, act, blank, beam_size,
+                   cutoff_top_k, lm_in_lds, reinterpret_cast<int*>(ws),
+                   reinterpret_cast<float*>(ws + records_bytes(B, T, beam_size)), tokens, frames, out_len, score},
+                  ngram_tables(*lm), lm_weight, start_ctx, lm_score};
+  const size_t smem = fixed + (lm_in_lds ? lm_bytes : 0);
+  if (V <= 64 * kRegs)
+    hipLaunchKernelGGL(rnnt_beam_ngram_kernel<true>, dim3(B), dim3(kThreads), smem, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(rnnt_beam_ngram_kernel<false>, dim3(B), dim3(kThreads), smem, (hipStream_t)stream, a);
   S2T_CHECK_LAUNCH();
   return 0;
 }

@@ -6,12 +6,15 @@
 //                (256 threads): lm recompute after an emission, arg-max, emit or advance.
 //   beam_walk    phases A-D of s2t_rnnt_beam_stateless (see decode_beam.hip) over frames [0, Tb) of
 //                one row (8 waves); the (parent, class) record of every kept beam goes to a functor.
+//                Its LM mode kLmNgram adds the back-off n-gram term of ngram_lookup.h to the candidates
+//                (s2t_rnnt_beam_stateless_ngram and its chunk form); kLmNone is the search as it was.
 // Both take the search state by reference and leave it as the next frame needs it.  The limits,
 // the record and candidate ranking are decode_records.h's.
 #pragma once
 #include "common.h"
 #include "decode_common.h"
 #include "decode_records.h"
+#include "ngram_lookup.h"
 
 namespace s2t_dec {
 
@@ -115,6 +118,16 @@ struct BeamShared {
   int emit[kMaxBeam];              // beams whose lm is to be recomputed
   int nemit;
   int trace[kTraceFrames * kMaxBeam];
+};
+
+constexpr int kLmNone = 0, kLmNgram = 1;   // the LM modes of beam_walk
+
+struct RnntNgramShared {           // the n-gram mode's part of the beams and of the candidates
+  NgramTables g;                   // (in LDS, as in CtcNgramShared: ten scalar registers less across the frame)
+  int ctx[2][kMaxBeam];            // context id of each beam, double-buffered like score
+  float lm_sum[2][kMaxBeam];       // unweighted sum of the look-ups a beam was extended by
+  int cnext[kMaxCand];             // per candidate: the context its look-up returned (blank: the parent's)
+  float cq[kMaxCand];              // ... and the look-up's value (blank: 0)
 };
 
 // LDS of a beam workgroup besides BeamShared: e [kGroup][E], h [kGroup][D], state [2][kMaxBeam][ctx]
@@ -251,10 +264,16 @@ __device__ void recompute_lm(const A& a, const int* __restrict__ list, int n,
 // class)) is called by the lane of every kept beam.  On return nb and cur name the beams after the
 // last frame, best first.  CACHE: V <= 64 kRegs, the frame's am is held in registers and the next
 // frame's is fetched a frame ahead.  A: recompute_lm's fields and a.act, a.blank, a.beam, a.topk.
-template <bool CACHE, typename A, typename Rec>
+// LM = kLmNgram (ng, lm_weight given; ng->g and ng->ctx / lm_sum [cur] filled): between A and B a thread
+// per candidate of a class other than blank adds lm_weight * ngram_score(parent's context, class) to
+// the candidate's score, as (beam score + log-probability) + lm_weight * q in fp32, and C hands the
+// kept beams the look-up's context and lm_sum + q; a blank candidate keeps its parent's context and
+// sum.  The cut to top-k, the ranking, the records and D are the same code in both modes.
+template <bool CACHE, int LM = kLmNone, typename A, typename Rec>
 __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float* __restrict__ amb,
                                           int Tb, int& nb, int& cur, float* e, float* h, int* state,
-                                          float* lm, Rec rec) {
+                                          float* lm, Rec rec, RnntNgramShared* ng = nullptr,
+                                          float lm_weight = 0.f) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int V = a.V, K = min(a.topk, V), BS = a.beam;
   float am_cur[kRegs] = {}, am_next[kRegs] = {};
@@ -323,6 +342,20 @@ __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float
       }
     }
     __syncthreads();
+    if constexpr (LM == kLmNgram) {                        // ---- the LM term: a thread per candidate
+      for (int q = tid; q < nb * K; q += kThreads) {
+        const int cls = s.ccls[q], pctx = ng->ctx[cur][q / K];
+        const float sc = s.cscore[q];
+        NgramHit hit{0.f, pctx};                           // blank, or an empty round: no term, no look-up
+        if (cls != a.blank && sc != S2T_NEG_INF) {
+          hit = ngram_score(ng->g, pctx, cls);
+          s.cscore[q] = __fadd_rn(sc, __fmul_rn(lm_weight, hit.logp));
+        }
+        ng->cq[q] = hit.logp;
+        ng->cnext[q] = hit.next;
+      }
+      __syncthreads();
+    }
     // ---- B: rank the candidates, keep the beam_size best
     const int nc = nb * K, nnb = min(nc, BS), nxt = cur ^ 1;
     rank_candidates(s.cscore, nc, nnb, s.pick);
@@ -337,6 +370,10 @@ __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float
         cls = s.ccls[q];
         s.score[nxt][lane] = s.cscore[q];
         s.len[nxt][lane] = s.len[cur][parent] + (cls != a.blank ? 1 : 0);
+        if constexpr (LM == kLmNgram) {
+          ng->ctx[nxt][lane] = ng->cnext[q];
+          ng->lm_sum[nxt][lane] = ng->lm_sum[cur][parent] + ng->cq[q];
+        }
         rec(t, lane, pack_record(parent, cls));
         const int* so = state + (cur * kMaxBeam + parent) * a.ctx;
         int* sn = state + (nxt * kMaxBeam + lane) * a.ctx;

@@ -10,6 +10,8 @@
 //           | score [16] | len [16] | lm row of each beam [16] | predictor states [16][ctx]
 //           | lm [beam][V] | records [256][beam] | token histories [2][beam][max_tokens]
 //           | frame histories [2][beam][max_tokens]
+//   n-gram  the beam row, every offset unchanged | ctx [beam] int32 | lm_sum [beam] fp32
+//           (s2t_rnnt_ngram_stream_state_bytes; the beam kernel's kLmNgram instantiation)
 // The lm rows are PERSISTED, not recomputed on entry: a chunk then starts with beam V floats from
 // HBM instead of up to four passes over the predictor's weights (decode_search.h recompute_lm), and
 // when the rows do not fit the LDS the search simply works on them in place.  Only a reset row has
@@ -57,10 +59,20 @@ Layout layout(int V, int ctx, int beam, int max_tokens) {
   return l;
 }
 
+// The n-gram beam row (s2t_rnnt_ngram_stream_state_bytes) is the plain beam row, every offset as above,
+// followed by ctx [beam] int32, the beams' n-gram context ids, and lm_sum [beam] fp32.
+Layout ngram_layout(int V, int ctx, int beam, int max_tokens, long* o_ng) {
+  Layout l = layout(V, ctx, beam, max_tokens);
+  *o_ng = l.stride;
+  l.stride = (long)align256(l.stride + (sizeof(int) + sizeof(float)) * (size_t)beam);
+  return l;
+}
+
 // ------------------------------------------------------------------------------------ reset
+// o_ng != 0: an n-gram beam row, whose one beam starts in the context start_ctx with no LM sum
 __global__ __launch_bounds__(64) void rnnt_stream_reset_kernel(char* state, const int* __restrict__ rows,
                                                                long stride, long pstate, int beam,
-                                                               int ctx, int blank) {
+                                                               int ctx, int blank, long o_ng, int start_ctx) {
   const int b = blockIdx.x, tid = threadIdx.x;
   if (rows && rows[b] == 0) return;
   char* row = state + (long)b * stride;
@@ -73,6 +85,10 @@ __global__ __launch_bounds__(64) void rnnt_stream_reset_kernel(char* state, cons
       reinterpret_cast<float*>(row + kHdr)[0] = 0.f;       // its score, length, lm row
       reinterpret_cast<int*>(row + 2 * kHdr)[0] = 0;
       reinterpret_cast<int*>(row + 3 * kHdr)[0] = 0;
+      if (o_ng) {
+        reinterpret_cast<int*>(row + o_ng)[0] = start_ctx;
+        reinterpret_cast<float*>(row + o_ng)[beam] = 0.f;
+      }
     }
   }
   int* ps = reinterpret_cast<int*>(row + pstate);          // init state + the blank start token
@@ -157,11 +173,23 @@ struct BeamChunkArgs {
   int* overflow;          // [B]
 };
 
-template <bool CACHE>
-__global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamChunkArgs a) {
+struct BeamNgramChunkArgs : BeamChunkArgs {    // the n-gram mode's (decode_search.h beam_walk)
+  NgramTables g;
+  float lm_weight;
+  long o_ng;              // ctx [beam] int32 | lm_sum [beam] fp32 inside a row of state
+  float* lm_score;        // [B]
+};
+
+template <bool CACHE, int LM = kLmNone, typename Args = BeamChunkArgs>
+__global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(Args a) {
   extern __shared__ float sm[];
   __shared__ BeamShared s;
   __shared__ int s_anc[kMaxBeam], s_base[kMaxBeam];
+  RnntNgramShared* ng = nullptr;
+  if constexpr (LM == kLmNgram) {
+    __shared__ RnntNgramShared s_ng;
+    ng = &s_ng;
+  }
 
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int V = a.V, BS = a.beam, MT = a.max_tokens;
@@ -196,17 +224,34 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamChunkArgs
   if (a.lm_in_lds && lm_valid)
     for (int x = tid; x < BS * V; x += kThreads) lm[x] = g_lm[x];
   if (tid == 0) s.emit[0] = 0;
+  if constexpr (LM == kLmNgram) {
+    const int* g_ctx = reinterpret_cast<const int*>(row + a.o_ng);
+    if (tid < nb0) {                                       // (clamped: the look-up indexes with it)
+      ng->ctx[0][tid] = ngram_clamp(g_ctx[tid], a.g.num_ctx);
+      ng->lm_sum[0][tid] = reinterpret_cast<const float*>(g_ctx + BS)[tid];
+    }
+    if (tid == 0) ng->g = a.g;
+  }
   __syncthreads();
   if (!lm_valid) recompute_lm(a, s.emit, 1, state, s.slot[0], e, h, lm);   // (a reset row: one beam)
   int nb = nb0, cur = 0;
-  beam_walk<CACHE>(a, s, a.am + (long)b * a.Tc * V, Tb, nb, cur, e, h, state, lm,
-                   [&](int t, int pos, int r) { rec[t * BS + pos] = r; });
+  if constexpr (LM == kLmNgram)
+    beam_walk<CACHE, kLmNgram>(a, s, a.am + (long)b * a.Tc * V, Tb, nb, cur, e, h, state, lm,
+                               [&](int t, int pos, int r) { rec[t * BS + pos] = r; }, ng, a.lm_weight);
+  else
+    beam_walk<CACHE>(a, s, a.am + (long)b * a.Tc * V, Tb, nb, cur, e, h, state, lm,
+                     [&](int t, int pos, int r) { rec[t * BS + pos] = r; });
 
   // ---- the beams go back
   if (tid < nb) {
     g_score[tid] = s.score[cur][tid];
     g_len[tid] = s.len[cur][tid];
     g_slot[tid] = s.slot[cur][tid];
+    if constexpr (LM == kLmNgram) {
+      int* g_ctx = reinterpret_cast<int*>(row + a.o_ng);
+      g_ctx[tid] = ng->ctx[cur][tid];
+      reinterpret_cast<float*>(g_ctx + BS)[tid] = ng->lm_sum[cur][tid];
+    }
   }
   for (int x = tid; x < nb * a.ctx; x += kThreads) g_state[x] = state[cur * kMaxBeam * a.ctx + x];
   if (a.lm_in_lds)
@@ -281,6 +326,7 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamChunkArgs
       const int ovf = (ovf0 || longest > MT) ? 1 : 0;
       a.out_len[b] = m0;
       a.score[b] = s.score[cur][0];
+      if constexpr (LM == kLmNgram) a.lm_score[b] = ng->lm_sum[cur][0];
       a.stable_len[b] = stable;
       a.overflow[b] = ovf;
       hdr[0] = nb;
@@ -306,7 +352,7 @@ extern "C" int s2t_rnnt_stream_reset(void* state, const int* rows, int B, int V,
   if (!state || !shape_ok(V, ctx, beam_size, max_tokens) || blank < 0 || blank >= V) return -1;
   const Layout l = layout(V, ctx, beam_size, max_tokens);
   hipLaunchKernelGGL(rnnt_stream_reset_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream,
-                     static_cast<char*>(state), rows, l.stride, l.pstate, beam_size, ctx, blank);
+                     static_cast<char*>(state), rows, l.stride, l.pstate, beam_size, ctx, blank, 0L, 0);
   S2T_CHECK_LAUNCH();
   return 0;
 }
@@ -359,6 +405,61 @@ extern "C" int s2t_rnnt_beam_stateless_chunk(const float* am, const long* chunk_
     hipLaunchKernelGGL(rnnt_beam_chunk_kernel<true>, dim3(B), dim3(kThreads), smem, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(rnnt_beam_chunk_kernel<false>, dim3(B), dim3(kThreads), smem, (hipStream_t)stream, a);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- the beam search above fused with a back-off n-gram (decode_search.h beam_walk's n-gram mode)
+extern "C" long s2t_rnnt_ngram_stream_state_bytes(int B, int V, int ctx, int beam_size, int max_tokens) {
+  if (B <= 0 || beam_size < 1 || !shape_ok(V, ctx, beam_size, max_tokens)) return 0;
+  long o_ng;
+  return (long)B * ngram_layout(V, ctx, beam_size, max_tokens, &o_ng).stride;
+}
+
+extern "C" int s2t_rnnt_ngram_stream_reset(void* state, const int* rows, int B, int V, int ctx, int beam_size,
+                                           int max_tokens, int blank, int start_ctx, void* stream) {
+  if (B <= 0) return 0;
+  if (!state || beam_size < 1 || !shape_ok(V, ctx, beam_size, max_tokens) || blank < 0 || blank >= V || start_ctx < 0)
+    return -1;
+  long o_ng;
+  const Layout l = ngram_layout(V, ctx, beam_size, max_tokens, &o_ng);
+  hipLaunchKernelGGL(rnnt_stream_reset_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream,
+                     static_cast<char*>(state), rows, l.stride, l.pstate, beam_size, ctx, blank, o_ng, start_ctx);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int s2t_rnnt_beam_stateless_ngram_chunk(const S2tNgramLmDesc* lm, const float* am, const long* chunk_len,
+                                                   const float* emb, const float* conv_w, const float* lin_w,
+                                                   const float* lin_b, const float* pre_w, const float* pre_b,
+                                                   int B, int Tc, int V, int E, int D, int ctx, int act, int blank,
+                                                   int beam_size, int cutoff_top_k, float lm_weight,
+                                                   int max_tokens, void* state, long* tokens, long* frames,
+                                                   long* out_len, float* score, float* lm_score, long* stable_len,
+                                                   int* overflow, void* stream) {
+  if (B <= 0) return 0;
+  if (Tc <= 0 || Tc > kMaxChunk || E <= 0 || D <= 0 || act < 0 || act > 1 || blank < 0 ||
+      beam_size < 1 || !shape_ok(V, ctx, beam_size, max_tokens) || blank >= V || cutoff_top_k < 1 ||
+      (cutoff_top_k < V ? cutoff_top_k : V) > kMaxBeam || !state || !ngram_desc_ok(lm) || lm->V != V ||
+      !__builtin_isfinite(lm_weight) || !lm_score)
+    return -1;
+  const size_t fixed = beam_fixed_lds(E, D, ctx);
+  if (fixed > kLdsBudget) return -1;
+  const size_t lm_bytes = sizeof(float) * (size_t)beam_size * V;
+  const int lm_in_lds = fixed + lm_bytes <= kLdsBudget;
+  long o_ng;
+  const Layout l = ngram_layout(V, ctx, beam_size, max_tokens, &o_ng);
+  BeamNgramChunkArgs a{{am, chunk_len, emb, conv_w, lin_w, lin_b, pre_w, pre_b, Tc, V, E, D, ctx, act, blank,
+                        beam_size, cutoff_top_k, lm_in_lds, max_tokens, static_cast<char*>(state), l, tokens,
+                        frames, out_len, score, stable_len, overflow},
+                       ngram_tables(*lm), lm_weight, o_ng, lm_score};
+  const size_t smem = fixed + (lm_in_lds ? lm_bytes : 0);
+  if (V <= 64 * kRegs)
+    hipLaunchKernelGGL((rnnt_beam_chunk_kernel<true, kLmNgram, BeamNgramChunkArgs>), dim3(B), dim3(kThreads), smem,
+                       (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((rnnt_beam_chunk_kernel<false, kLmNgram, BeamNgramChunkArgs>), dim3(B), dim3(kThreads), smem,
+                       (hipStream_t)stream, a);
   S2T_CHECK_LAUNCH();
   return 0;
 }

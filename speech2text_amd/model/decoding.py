@@ -21,6 +21,9 @@ for shallow fusion (`lm=`, `lm_weight=`): with the LSTM predictor and with the s
 (s2t_rnnt_beam_lstm_lm, s2t_rnnt_beam_stateless_lm), everything else runs `_module_loop_lm`; the
 chunk-carried beam searches take the same LM (RnntLstmStreamingSearch with `lm=`,
 RnntStatelessLmStreamingSearch; s2t_rnnt_beam_lstm_lm_chunk, s2t_rnnt_beam_stateless_lm_chunk).
+An NgramLm is fused into the one-workgroup search of the stateless predictor instead, one launch, and
+into its chunk-carried form (rnnt_beam_ngram_tokens_from_am, RnntNgramStreamingSearch;
+s2t_rnnt_beam_stateless_ngram, s2t_rnnt_beam_stateless_ngram_chunk).
 CtcPrefixBeamDecoding is a lexicon-free CTC prefix beam search with equal prefixes merged and the same
 optional RNN-LM term, on the device for the whole batch (csrc/decode_ctc.hip: s2t_ctc_prefix_beam,
 s2t_ctc_prefix_beam_lm) and, in one launch again, a back-off n-gram over the model's classes
@@ -770,6 +773,55 @@ def rnnt_beam_tokens_from_am(am, lengths, predictor, joiner, beam_size=4, cutoff
     return tokens, frames, out_len, score
 
 
+def _stateless_weights(predictor, joiner, dev=None):
+    """The six parameter tensors of the one-workgroup searches (embedding, conv [E][ctx], linear w / b,
+    pre_proj w / b), fp32 and contiguous -> (list, E, D, ctx, act)."""
+    p = getattr(predictor, "predictor", predictor)
+    f32 = lambda t: t.detach().to(device=dev or t.device, dtype=torch.float32).contiguous()   # noqa: E731
+    w = [f32(p._embedding.weight), f32(p._conv.weight.reshape(p._embedding_dim, p._context_size)),
+         f32(p._output_linear.weight), f32(p._output_linear.bias),
+         f32(joiner._pre_proj.weight), f32(joiner._pre_proj.bias)]
+    return w, p._embedding_dim, p._output_dim, p._context_size, 0 if joiner._act_name == "relu" else 1
+
+
+def rnnt_beam_ngram_tokens_from_am(am, lengths, predictor, joiner, lm, lm_weight, beam_size=4, cutoff_top_k=4):
+    """rnnt_beam_tokens_from_am with back-off n-gram shallow fusion (lm: an NgramLm whose fp32 tables are
+    on am's device), still ONE launch: the candidate of class c != blank scores lm_weight * log p_lm(c |
+    the beam's context) more, looked up inside the frame body, and a kept beam carries the context the
+    look-up returned.  The search starts in the LM's own start context, so the first token is scored
+    too.  -> (tokens, frames, out_len, score, lm_score (B) fp32: the best beam's unweighted LM sum), or
+    None where the entry refuses.  HIP: decode_beam.hip, decode_search.h, ngram_lookup.h."""
+    if not am.is_cuda:
+        raise RuntimeError("the fused RNN-T beam search runs on the GPU only")
+    am = am.contiguous().float()
+    B, T, V = am.shape
+    dev = am.device
+    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+    tokens, frames, out_len, score = _beam_outputs(B, T, dev)
+    lm_score = torch.zeros((B,), dtype=torch.float32, device=dev)
+    out = (tokens, frames, out_len, score, lm_score)
+    if B == 0 or T == 0:
+        return out
+    if lm.device != dev:
+        raise RuntimeError(f"the n-gram tables are on {lm.device}, am on {dev}: NgramLm.to(device)")
+    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
+    n = N.lib().s2t_rnnt_beam_ngram_workspace_bytes(B, T, V, beam_size)
+    if n <= 0:
+        return None
+    lm_desc, lm_keep = lm.desc()
+    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+    w, E, D, ctx, act = _stateless_weights(predictor, joiner)
+    rc = N.lib().s2t_rnnt_beam_stateless_ngram(
+        lm_desc, N.fp(am), N.lp(lengths), *[N.fp(t) for t in w], B, T, V, E, D, ctx, act, 0, beam_size,
+        cutoff_top_k, float(lm_weight), int(lm.start_ctx), N.ptr(ws), N.lp(tokens), N.lp(frames), N.lp(out_len),
+        N.fp(score), N.fp(lm_score), N.stream())
+    del lm_keep
+    if rc == -1:
+        return None
+    N.check(rc, "s2t_rnnt_beam_stateless_ngram")
+    return out
+
+
 class RnntBeamDecoding(DecodingMethod):
     """Beam search of the RNN-T (reference :295-425): at most one symbol per frame per beam, the
     `cutoff_top_k` best classes of every beam are expanded, the `beam_size` best candidates
@@ -777,13 +829,17 @@ class RnntBeamDecoding(DecodingMethod):
     fixed: top-k by (log-probability descending, class ascending), candidates by (score
     descending, parent beam position ascending, rank in the parent's top-k ascending).
 
-    With `lm` (an RnnLm, or anything with init_states / score_step) the search is shallow-fused: the
-    candidate of class c != blank scores `lm_weight * log p_lm(c | the beam's tokens)` more, the cut
-    to `cutoff_top_k` classes is still the RNN-T's own, blank carries no LM term.  `lm_start_token`
-    None: the LM starts from zero state and a hypothesis' first token carries no LM term (how
-    RnnLm.score scores a sequence); a token id: the LM is first stepped on it.  The LSTM predictor and
-    the stateless predictor (with the project's Joiner and an RnnLm) run the fused device search
-    (csrc/decode_lstm.hip); everything else, and a shape the kernels refuse, `_module_loop_lm`.
+    With `lm` (an RnnLm, an NgramLm, or anything with init_states / score_step) the search is
+    shallow-fused: the candidate of class c != blank scores `lm_weight * log p_lm(c | the beam's tokens)`
+    more, the cut to `cutoff_top_k` classes is still the RNN-T's own, blank carries no LM term.
+    `lm_start_token` None: the LM starts from its initial state and, unless it has `start_scores`, a
+    hypothesis' first token carries no LM term (how RnnLm.score scores a sequence); an LM with
+    `start_scores` (NgramLm) scores the first token too, from its own start state; a token id: the LM
+    is first stepped on it.  The LSTM predictor and the stateless predictor (with the project's Joiner
+    and an RnnLm) run the fused device search (csrc/decode_lstm.hip); the stateless predictor with a
+    projection-free Joiner and an NgramLm (no `lm_start_token`) runs the one-launch search fused with
+    the n-gram (csrc/decode_beam.hip s2t_rnnt_beam_stateless_ngram), the tables following the inputs to
+    their device; everything else, and a shape the kernels refuse, `_module_loop_lm`.
     `beam_tokens` then returns a fifth tensor, the best beam's unweighted LM sum."""
 
     def __init__(self, tokenizer, predictor, joiner, beam_size=4, cutoff_top_k=4, lm=None, lm_weight=0.0,
@@ -853,6 +909,8 @@ class RnntBeamDecoding(DecodingMethod):
         if self._lm_start_token is not None:
             q, lm_state = lm.score_step(torch.full((1,), self._lm_start_token, dtype=torch.int64, device=dev),
                                         lm_state)
+        elif hasattr(lm, "start_scores"):                  # (an n-gram scores the first token too)
+            q = lm.start_scores(lm_state)
         beams = [((), (), pred_state, pred_out, lm_state, q)]   # (tokens, frames, state, pred_out, LM state, q (1,V))
         scores = lm_sums = None
         for t in range(hidden_states.shape[1]):
@@ -892,6 +950,8 @@ class RnntBeamDecoding(DecodingMethod):
             p = next(self._lm.parameters(), None)
             if p is not None and p.device != dev:
                 self._lm.to(dev)
+        elif _is_ngram(self._lm):
+            self._lm.to(dev)
 
     @torch.no_grad()
     def beam_tokens(self, hidden_states, inputs_length, fused=True):
@@ -945,6 +1005,13 @@ class RnntBeamDecoding(DecodingMethod):
                                                         self._lm_start_token)
             if out is not None:
                 return out
+        if fused and self._fusable() and _is_ngram(self._lm) and self._lm_start_token is None \
+                and hidden_states.is_cuda and self._lm.dtype == torch.float32:
+            am = self._joiner._enc_proj(hidden_states)                # (B,T,V), one GEMM
+            out = rnnt_beam_ngram_tokens_from_am(am, inputs_length, self._predictor, self._joiner, self._lm,
+                                                 self._lm_weight, self._beam_size, self._cutoff_top_k)
+            if out is not None:
+                return out
         B, T = hidden_states.shape[0], hidden_states.shape[1]
         tokens = torch.zeros((B, T), dtype=torch.int64)
         frames = torch.zeros((B, T), dtype=torch.int64)
@@ -980,8 +1047,9 @@ def _stream_lm_arguments(lm, lm_weight, lm_start_token, method):
     if method == "greedy":
         raise ValueError("the greedy searches take no language model: use method='beam' or lm=None")
     if _is_ngram(lm):
-        raise ValueError("the chunk-carried searches are not fused with an NgramLm: the n-gram search is the "
-                         "whole-utterance CtcPrefixBeamDecoding only (pass an RnnLm, or lm=None)")
+        raise ValueError("this chunk-carried search is not fused with an NgramLm: the chunk-carried n-gram search "
+                         "is RnntNgramStreamingSearch, the beam search of the stateless predictor with a "
+                         "projection-free Joiner (pass an RnnLm, or lm=None)")
     if not isinstance(lm, RnnLm):
         raise ValueError(f"the chunk-carried search is fused with an RnnLm only, got {type(lm).__name__} "
                          "(there is no module-loop fallback here)")
@@ -1296,13 +1364,78 @@ class RnntStatelessLmStreamingSearch(_ChunkCarriedSearch):
             N.lp(self.stable_len), N.ip(self.overflow), N.stream()), "s2t_rnnt_beam_stateless_lm_chunk")
 
 
+class RnntNgramStreamingSearch(RnntStreamingSearch):
+    """RnntStreamingSearch's beam search fused with a back-off n-gram (csrc/decode_stream.hip
+    s2t_rnnt_beam_stateless_ngram_chunk): the one-workgroup search of the stateless predictor and a
+    projection-free Joiner, a look-up per candidate inside the frame body, carried across chunks.
+    However the frames are cut, the result after a chunk is rnnt_beam_ngram_tokens_from_am on the frames
+    fed so far, bit for bit, `lm_score` included.
+
+    Same surface as RnntStreamingSearch with method="beam": `state`, `tokens`, `frames`, `out_len`,
+    `score`, `stable_len`, `overflow`, `reset(rows)` (a reset row restarts in the LM's start context),
+    `step(am_chunk, chunk_len)` returning the five beam views without a host synchronisation, plus
+    `lm_score` (B, fp32), the best beam's unweighted LM sum.  Beam only.  The tables are copied to the
+    search's device when they live elsewhere.  Other modules, an `lm` that is not an NgramLm with fp32
+    tables, a weight that is not finite or a shape the entry refuses are a ValueError at construction;
+    modules off the GPU a RuntimeError.  No module-loop fallback."""
+
+    def __init__(self, predictor, joiner, batch_size=1, beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None,
+                 lm=None, lm_weight=0.0):
+        if not _is_ngram(lm):
+            raise ValueError(f"RnntNgramStreamingSearch needs an NgramLm, got {type(lm).__name__}")
+        if lm.dtype != torch.float32:
+            raise ValueError("the device n-gram search needs fp32 tables")
+        if not math.isfinite(float(lm_weight)):
+            raise ValueError(f"lm_weight must be finite, got {lm_weight!r}")
+        self.lm_score = None
+        self._lm, self._lm_weight = lm, float(lm_weight)
+        super().__init__(predictor, joiner, batch_size, "beam", 0, beam_size, cutoff_top_k, max_tokens, device)
+
+    def _allocate(self, predictor, joiner, dev):
+        super()._allocate(predictor, joiner, dev)          # the plain search's checks and weights
+        n = N.lib().s2t_rnnt_ngram_stream_state_bytes(self.batch_size, self.V, self.ctx, self.beam_size,
+                                                      self.max_tokens)
+        if n <= 0 or self._lm.num_classes != self.V:
+            raise ValueError(f"the chunk-carried n-gram beam search does not take this shape: B {self.batch_size} "
+                             f"V {self.V} beam {self.beam_size} max_tokens {self.max_tokens}, LM V "
+                             f"{self._lm.num_classes} (limits: include/s2t_mi355.h)")
+        self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)   # the plain row + ctx and lm_sum per beam
+        if self._lm.device != self.state.device:           # a copy: the caller's LM stays where it is
+            import copy
+            self._lm = copy.copy(self._lm)
+            self._lm._cache = {}
+            self._lm.to(self.state.device)
+        self._lm_desc, self._lm_keep = self._lm.desc()
+        self.lm_score = torch.zeros((self.batch_size,), dtype=torch.float32, device=dev)
+
+    def _reset_state(self, mask):
+        N.check(N.lib().s2t_rnnt_ngram_stream_reset(N.ptr(self.state), N.ip(mask), self.batch_size, self.V, self.ctx,
+                                                    self.beam_size, self.max_tokens, 0, int(self._lm.start_ctx),
+                                                    N.stream()), "s2t_rnnt_ngram_stream_reset")
+
+    def _chunk(self, am_chunk, chunk_len, Tc):
+        N.check(N.lib().s2t_rnnt_beam_stateless_ngram_chunk(
+            self._lm_desc, N.fp(am_chunk), N.lp(chunk_len), *[N.fp(t) for t in self._w], self.batch_size, Tc,
+            self.V, self.E, self.D, self.ctx, self._act, 0, self.beam_size, self.cutoff_top_k, self._lm_weight,
+            self.max_tokens, N.ptr(self.state), N.lp(self.tokens), N.lp(self.frames), N.lp(self.out_len),
+            N.fp(self.score), N.fp(self.lm_score), N.lp(self.stable_len), N.ip(self.overflow), N.stream()),
+            "s2t_rnnt_beam_stateless_ngram_chunk")
+
+
 def rnnt_streaming_search(predictor, joiner, batch_size=1, method="greedy", max_token_step=5, beam_size=4,
                           cutoff_top_k=4, max_tokens=1024, device=None, lm=None, lm_weight=0.0,
                           lm_start_token=None, **kw):
     """The chunk-carried search that serves the pair: RnntLstmStreamingSearch for LstmPredictor +
     Joiner (kw: capturable), with or without an `lm`; for the stateless predictor
-    RnntStatelessLmStreamingSearch with an `lm` (joiner with or without output projection) and
-    RnntStreamingSearch without one (which raises for what it does not take)."""
+    RnntStatelessLmStreamingSearch with an RnnLm (joiner with or without output projection),
+    RnntNgramStreamingSearch with an NgramLm (beam search, projection-free joiner, no `lm_start_token`)
+    and RnntStreamingSearch without an `lm` (which raises for what it does not take).  An NgramLm with
+    the LSTM pair or with method="greedy" raises: those searches are not fused with an n-gram."""
+    if _is_ngram(lm) and method == "beam" and not _is_lstm_pair(predictor, joiner):
+        if lm_start_token is not None:
+            raise ValueError("an NgramLm starts in its own <s> context: lm_start_token must be None")
+        return RnntNgramStreamingSearch(predictor, joiner, batch_size, beam_size, cutoff_top_k, max_tokens, device,
+                                        lm=lm, lm_weight=lm_weight, **kw)
     if _is_lstm_pair(predictor, joiner):
         if lm is not None:
             kw.update(lm=lm, lm_weight=lm_weight, lm_start_token=lm_start_token)

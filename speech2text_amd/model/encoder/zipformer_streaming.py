@@ -298,7 +298,9 @@ class StreamingRecognizer:
     is an error: there is no module-loop fallback.  With `lm` (an RnnLm; beam only) the graph captures
     the chunk call fused with the LM (`lm_weight`, `lm_start_token` as RnntBeamDecoding's): the LSTM
     pair through RnntLstmStreamingSearch, the stateless predictor with either joiner through
-    RnntStatelessLmStreamingSearch; `search.lm_score` holds the best beams' unweighted LM sums."""
+    RnntStatelessLmStreamingSearch; `search.lm_score` holds the best beams' unweighted LM sums.  With an
+    NgramLm (beam only, no `lm_start_token`) the stateless predictor with a projection-free joiner runs
+    RnntNgramStreamingSearch, the one-workgroup chunk kernel with the look-up inside its frame body."""
 
     def __init__(self, encoder, predictor, joiner, tokenizer, cmvn=None, batch_size: int = 1,
                  method: str = "greedy", max_token_step: int = 5, beam_size: int = 4,
