@@ -41,6 +41,12 @@
 // s2t_rnnt_beam_stateless_lm_chunk): the same rounds through the same host functions, the LM's (h, c), q
 // and lm_sum carried in the caller's state buffer behind the predictor's.
 //
+// On the host every beam entry point is ONE function, beam_search: a predictor (LstmPredictor or
+// StatelessPredictor, which say how their workspace and state are carved, blanked, stepped and copied
+// home), with an LM or not, the whole utterance or a chunk.  It checks the shapes, fills BeamArgs by name
+// and enqueues the launches; stream_reset does the same for the three resets.  Buffers are handed out
+// by one Arena, which also answers the *_bytes queries.
+//
 // A row's arithmetic does not depend on the rows that share its launch: tiles sit at fixed row
 // positions, every (row, output) sum is taken per lane over k = lane, lane + 64, ... and folded by the
 // same butterfly, and rows beyond R read clamped addresses and are never stored.
@@ -261,59 +267,81 @@ __global__ __launch_bounds__(kThreads) void cell_kernel(CellArgs a) {
 }
 
 // ------------------------------------------------------------------ workspace
-struct Workspace {
-  float *h[2], *c[2], *lm[2];   // state [layers][R][H] twice, lm [R][V] twice
-  float *x, *raw, *lin, *dvec;  // LN(embedding) [R][E], raw gates [R][4H], linear(h) [R][D], its LN
+// A caller's buffer handed out array by array, each on a 256-byte boundary.  Without a base (the
+// *_bytes queries) it only adds the sizes up and hands out NULL.
+struct Arena {
+  char* base;
+  size_t bytes = 0;
+  explicit Arena(void* b) : base(static_cast<char*>(b)) {}
+  template <class T>
+  T* take(size_t n) {
+    const size_t at = bytes;
+    bytes += align256(sizeof(T) * n);
+    return base ? reinterpret_cast<T*>(base + at) : nullptr;
+  }
+};
+
+// What a search works on whatever its predictor: R = B * max(1, beam) rows.
+struct SearchArrays {
   float *z, *mid, *logit;       // joint: act(am + lm) [R][V], [R][inner], out-projection [R][V]
   float* cscore;                // beam: candidates [B][kMaxCand]
   float* score;                 // beam: [R]
   int *ccls, *blen, *nb, *rec;  // beam: candidate classes, tokens per beam [R], live beams [B], records [B][T][beam]
   int *emit, *token, *parent;   // [R]
-  int *t, *nts, *done;          // greedy: [R]
   int* counts;                  // [0], [1]: rows that emit, by round parity; [2]: R; [3]: rows still live
-  size_t bytes;
+};
+
+// joint: the caller runs the joint (a search); a predictor step on its own keeps one-element placeholders.
+// n_mid: the elements of `mid`, which the two predictors' workspaces have sized differently without an
+// out-projection (R or 1) and the size queries' answers keep.
+SearchArrays carve_search(Arena& m, int B, int T, int beam, int V, size_t n_mid, bool joint) {
+  const size_t R = (size_t)B * (beam > 0 ? beam : 1);
+  SearchArrays a;
+  a.z = m.take<float>(joint ? R * V : 1);
+  a.mid = m.take<float>(n_mid);
+  a.logit = m.take<float>(joint ? R * V : 1);
+  a.cscore = m.take<float>(joint ? (size_t)B * kMaxCand : 1);
+  a.score = m.take<float>(R);
+  a.ccls = m.take<int>(joint ? (size_t)B * kMaxCand : 1);
+  a.blen = m.take<int>(R);
+  a.nb = m.take<int>(B);
+  a.rec = m.take<int>(beam > 0 ? (size_t)B * T * beam : 1);
+  a.emit = m.take<int>(R);
+  a.token = m.take<int>(R);
+  a.parent = m.take<int>(R);
+  a.counts = m.take<int>(4);
+  return a;
+}
+
+struct StateBuf {
+  float *h, *c, *lm;            // [layers][R][H], [layers][R][H], [R][V]
+};
+
+struct Workspace {
+  StateBuf buf[2];              // state and lm twice
+  float *x, *raw, *lin, *dvec;  // LN(embedding) [R][E], raw gates [R][4H], linear(h) [R][D], its LN
+  SearchArrays s;
+  int *t, *nts, *done;          // greedy: [R]
 };
 
 // n_state: how many copies of (h, c, lm) the workspace holds -- two for a whole-utterance search; a
 // chunk call keeps the live copy in the caller's state buffer (beam: one here, greedy: none)
-Workspace carve(const S2tRnntLstmDesc& d, int B, int T, int beam, void* base, int n_state = 2) {
+Workspace carve(const S2tRnntLstmDesc& d, int B, int T, int beam, Arena& m, int n_state = 2) {
   const size_t R = (size_t)B * (beam > 0 ? beam : 1), L = d.num_layers;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* q = p + off;
-    off += align256(bytes);
-    return q;
-  };
-  auto f = [&](size_t n) { return reinterpret_cast<float*>(take(4 * n)); };
-  auto i = [&](size_t n) { return reinterpret_cast<int*>(take(4 * n)); };
   Workspace w;
   for (int s = 0; s < 2; ++s) {
-    w.h[s] = s < n_state ? f(L * R * d.H) : nullptr;
-    w.c[s] = s < n_state ? f(L * R * d.H) : nullptr;
-    w.lm[s] = s < n_state ? f(R * d.V) : nullptr;
+    w.buf[s].h = s < n_state ? m.take<float>(L * R * d.H) : nullptr;
+    w.buf[s].c = s < n_state ? m.take<float>(L * R * d.H) : nullptr;
+    w.buf[s].lm = s < n_state ? m.take<float>(R * d.V) : nullptr;
   }
-  w.x = f(R * d.E);
-  w.raw = f(R * 4 * d.H);
-  w.lin = f(R * d.D);
-  w.dvec = f(R * d.D);
-  w.z = f(R * d.V);
-  w.mid = f(R * (d.inner > 0 ? d.inner : 1));
-  w.logit = f(R * d.V);
-  w.cscore = f((size_t)B * kMaxCand);
-  w.score = f(R);
-  w.ccls = i((size_t)B * kMaxCand);
-  w.blen = i(R);
-  w.nb = i(B);
-  w.rec = i(beam > 0 ? (size_t)B * T * beam : 1);
-  w.emit = i(R);
-  w.token = i(R);
-  w.parent = i(R);
-  w.t = i(R);
-  w.nts = i(R);
-  w.done = i(R);
-  w.counts = i(4);
-  w.bytes = off;
+  w.x = m.take<float>(R * d.E);
+  w.raw = m.take<float>(R * 4 * d.H);
+  w.lin = m.take<float>(R * d.D);
+  w.dvec = m.take<float>(R * d.D);
+  w.s = carve_search(m, B, T, beam, d.V, R * (d.inner > 0 ? d.inner : 1), true);
+  w.t = m.take<int>(R);
+  w.nts = m.take<int>(R);
+  w.done = m.take<int>(R);
   return w;
 }
 
@@ -386,33 +414,24 @@ struct LmWorkspace {
   float *x, *raw, *logit;       // embedding rows [R][E], raw gates [R][4H], logits [R][V]
   float *cq, *lm_sum;           // beam: the candidates' q [B][kMaxCand], the rows' sums [R]
   int *tok, *counts;            // the start token [R]; the step on its own: its count
-  size_t bytes;
 };
 
 // n_state copies of (h, c, q): two for a search, none for the step on its own (the caller's buffers)
-LmWorkspace carve_lm(const S2tRnnLmDesc& d, int B, int beam, void* base, int n_state) {
+LmWorkspace carve_lm(const S2tRnnLmDesc& d, int B, int beam, Arena& m, int n_state) {
   const size_t R = (size_t)B * (beam > 0 ? beam : 1), L = d.num_layers;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto f = [&](size_t n) {
-    char* q = p + off;
-    off += align256(4 * n);
-    return reinterpret_cast<float*>(q);
-  };
   LmWorkspace w;
   for (int s = 0; s < 2; ++s) {
-    w.h[s] = s < n_state ? f(L * R * d.H) : nullptr;
-    w.c[s] = s < n_state ? f(L * R * d.H) : nullptr;
-    w.q[s] = s < n_state ? f(R * d.V) : nullptr;
+    w.h[s] = s < n_state ? m.take<float>(L * R * d.H) : nullptr;
+    w.c[s] = s < n_state ? m.take<float>(L * R * d.H) : nullptr;
+    w.q[s] = s < n_state ? m.take<float>(R * d.V) : nullptr;
   }
-  w.x = f(R * d.E);
-  w.raw = f(R * 4 * d.H);
-  w.logit = f(R * d.V);
-  w.cq = f(beam > 0 ? (size_t)B * kMaxCand : 1);
-  w.lm_sum = f(R);
-  w.tok = reinterpret_cast<int*>(f(R));
-  w.counts = reinterpret_cast<int*>(f(4));
-  w.bytes = off;
+  w.x = m.take<float>(R * d.E);
+  w.raw = m.take<float>(R * 4 * d.H);
+  w.logit = m.take<float>(R * d.V);
+  w.cq = m.take<float>(beam > 0 ? (size_t)B * kMaxCand : 1);
+  w.lm_sum = m.take<float>(R);
+  w.tok = m.take<int>(R);
+  w.counts = m.take<int>(4);
   return w;
 }
 
@@ -767,8 +786,10 @@ __global__ __launch_bounds__(64) void beam_trace_kernel(const long* lengths, int
                  frames + (long)b * T);
 }
 
-JointArgs joint_args(const S2tRnntLstmDesc& d, const float* am, int T, const Workspace& w) {
-  return JointArgs{am, T, d.V, d.inner, d.act, d.out1_w, d.out1_b, d.out2_w, d.out2_b, w.z, w.mid, w.logit};
+// Desc: S2tRnntLstmDesc or S2tRnntStatelessDesc (the joiner's fields carry the same names)
+template <class Desc>
+JointArgs joint_args(const Desc& d, const float* am, int T, const SearchArrays& s) {
+  return JointArgs{am, T, d.V, d.inner, d.act, d.out1_w, d.out1_b, d.out2_w, d.out2_b, s.z, s.mid, s.logit};
 }
 
 // The rounds of a greedy search on the state (h, c, lm), in place: a joint launch and a predictor
@@ -780,58 +801,17 @@ int greedy_rounds(const S2tRnntLstmDesc& d, int B, GreedyArgs g, float* h, float
     for (int q = 0; (q < kRoundBlock || !host_poll) && r < max_rounds; ++q, ++r) {
       g.parity = (int)(r & 1);
       hipLaunchKernelGGL(greedy_joint_kernel, dim3(B), dim3(kThreads), 0, st, g);
-      enqueue_pred_step(d, B, w.token, w.emit, nullptr, w.counts + g.parity, h, c, lm, h, c, lm, w, st);
+      enqueue_pred_step(d, B, w.s.token, w.s.emit, nullptr, w.s.counts + g.parity, h, c, lm, h, c, lm, w, st);
     }
     S2T_CHECK_LAUNCH();
     if (!host_poll) continue;
     int live = 0;                                          // the one host read of the block
-    hipError_t e = hipMemcpyAsync(&live, w.counts + 3, sizeof(int), hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(&live, w.s.counts + 3, sizeof(int), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return (int)e;
     if (live <= 0) break;
   }
   return 0;
-}
-
-struct StateBuf {
-  float *h, *c, *lm;    // [layers][R][H], [layers][R][H], [R][V]
-};
-
-// The T rounds of a beam search: frame t reads buf[t & 1] and leaves the survivors in buf[~t & 1].
-// With an LM (shallow fusion) its step follows the predictor's on the same emit / parent / token / count,
-// from its buffer cur to nxt.
-// pred_step(cur, nxt) enqueues the predictor's step on a.token / a.emit / a.parent / a.counts + cur from
-// its buffer cur to nxt; lm_rows are the two buffers' lm vectors.
-template <typename PredStep>
-void beam_rounds_over(BeamArgs a, float* const (&lm_rows)[2], PredStep pred_step, int T, hipStream_t st,
-                      const S2tRnnLmDesc* lm, const LmWorkspace* lw) {
-  const int R = a.B * a.beam;
-  for (int t = 0; t < T; ++t) {
-    const int cur = t & 1, nxt = cur ^ 1;
-    a.t = t;
-    a.parity = cur;
-    a.lm = lm_rows[cur];
-    if (lm) a.q = lw->q[cur];
-    hipLaunchKernelGGL(beam_expand_kernel, dim3(R), dim3(kThreads), 0, st, a);
-    hipLaunchKernelGGL(beam_select_kernel, dim3(a.B), dim3(kThreads), 0, st, a);
-    pred_step(cur, nxt);
-    if (lm)
-      enqueue_lm_step(*lm, R, a.token, a.emit, a.parent, a.counts + cur, lw->h[cur], lw->c[cur], lw->q[cur],
-                      lw->h[nxt], lw->c[nxt], lw->q[nxt], *lw, st);
-  }
-}
-
-void beam_rounds(const S2tRnntLstmDesc& d, BeamArgs a, const StateBuf (&buf)[2], const Workspace& w, int T,
-                 hipStream_t st, const S2tRnnLmDesc* lm = nullptr, const LmWorkspace* lw = nullptr) {
-  const int R = a.B * a.beam;
-  float* const lm_rows[2] = {buf[0].lm, buf[1].lm};
-  beam_rounds_over(
-      a, lm_rows,
-      [&](int cur, int nxt) {
-        enqueue_pred_step(d, R, w.token, w.emit, w.parent, w.counts + cur, buf[cur].h, buf[cur].c, buf[cur].lm,
-                          buf[nxt].h, buf[nxt].c, buf[nxt].lm, w, st);
-      },
-      T, st, lm, lw);
 }
 
 // ------------------------------------------------------------------ the stateless predictor in the row layout
@@ -880,50 +860,28 @@ __global__ __launch_bounds__(kThreads) void stateless_row_kernel(StatelessRowArg
   }
 }
 
+struct StatelessBuf {
+  int* ctx;                     // [R][ctx]
+  float* lm;                    // [R][V]
+};
+
 struct StatelessWorkspace {
-  int* ctx[2];                  // state [R][ctx] twice
-  float* lm[2];                 // lm [R][V] twice
+  StatelessBuf buf[2];          // state and lm twice
   float *x, *lin;               // the depthwise sums [R][E], linear(x) [R][D]
-  float *z, *mid, *logit;       // joint, as Workspace
-  float *cscore, *score;        // beam, as Workspace
-  int *ccls, *blen, *nb, *rec, *emit, *token, *parent, *counts;
-  size_t bytes;
+  SearchArrays s;
 };
 
 // n_state copies of (ctx, lm): two for a search, none for the step on its own (the caller's buffers)
-StatelessWorkspace carve_stateless(const S2tRnntStatelessDesc& d, int B, int T, int beam, void* base, int n_state) {
+StatelessWorkspace carve_stateless(const S2tRnntStatelessDesc& d, int B, int T, int beam, Arena& m, int n_state) {
   const size_t R = (size_t)B * (beam > 0 ? beam : 1);
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* q = p + off;
-    off += align256(bytes);
-    return q;
-  };
-  auto f = [&](size_t n) { return reinterpret_cast<float*>(take(4 * n)); };
-  auto i = [&](size_t n) { return reinterpret_cast<int*>(take(4 * n)); };
   StatelessWorkspace w;
   for (int s = 0; s < 2; ++s) {
-    w.ctx[s] = s < n_state ? i(R * d.ctx) : nullptr;
-    w.lm[s] = s < n_state ? f(R * d.V) : nullptr;
+    w.buf[s].ctx = s < n_state ? m.take<int>(R * d.ctx) : nullptr;
+    w.buf[s].lm = s < n_state ? m.take<float>(R * d.V) : nullptr;
   }
-  w.x = f(R * d.E);
-  w.lin = f(R * d.D);
-  const bool search = beam > 0;
-  w.z = f(search ? R * d.V : 1);
-  w.mid = f(search && d.inner > 0 ? R * d.inner : 1);
-  w.logit = f(search ? R * d.V : 1);
-  w.cscore = f(search ? (size_t)B * kMaxCand : 1);
-  w.score = f(R);
-  w.ccls = i(search ? (size_t)B * kMaxCand : 1);
-  w.blen = i(R);
-  w.nb = i(B);
-  w.rec = i(search ? (size_t)B * T * beam : 1);
-  w.emit = i(R);
-  w.token = i(R);
-  w.parent = i(R);
-  w.counts = i(4);
-  w.bytes = off;
+  w.x = m.take<float>(R * d.E);
+  w.lin = m.take<float>(R * d.D);
+  w.s = carve_search(m, B, T, beam, d.V, beam > 0 && d.inner > 0 ? R * d.inner : 1, beam > 0);
   return w;
 }
 
@@ -963,44 +921,32 @@ void enqueue_stateless_step(const S2tRnntStatelessDesc& d, int R, const int* tok
 constexpr int kStreamHdr = 4;      // ints per row: frames since reset, overflow, history buffer in use, stable_len
 
 struct StreamState {
-  float *h, *c, *lm;
+  StateBuf live;                   // (h, c, lm)
   float* score;                    // beam: [R]
   int *blen, *nb;                  // beam: tokens per beam [R] (not clamped), live beams [B]
   long* n;                         // greedy: symbols since the reset [B] (not clamped)
   int* hdr;                        // [B][kStreamHdr]
   int *htok, *hfrm;                // beam: [B][2][beam][max_tokens]
-  size_t bytes;
 };
 
-StreamState carve_state(const S2tRnntLstmDesc& d, int B, int beam, int max_tokens, void* base) {
+// (the order is the header's documented layout)
+StreamState carve_state(const S2tRnntLstmDesc& d, int B, int beam, int max_tokens, Arena& m) {
   const size_t R = (size_t)B * (beam > 0 ? beam : 1), L = d.num_layers;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* q = p + off;
-    off += align256(bytes);
-    return q;
-  };
   StreamState s{};
-  s.h = reinterpret_cast<float*>(take(4 * L * R * d.H));
-  s.c = reinterpret_cast<float*>(take(4 * L * R * d.H));
-  s.lm = reinterpret_cast<float*>(take(4 * R * d.V));
-  s.hdr = reinterpret_cast<int*>(take(4 * (size_t)B * kStreamHdr));
+  s.live.h = m.take<float>(L * R * d.H);
+  s.live.c = m.take<float>(L * R * d.H);
+  s.live.lm = m.take<float>(R * d.V);
+  s.hdr = m.take<int>((size_t)B * kStreamHdr);
   if (beam > 0) {
-    s.score = reinterpret_cast<float*>(take(4 * R));
-    s.blen = reinterpret_cast<int*>(take(4 * R));
-    s.nb = reinterpret_cast<int*>(take(4 * (size_t)B));
-    s.htok = reinterpret_cast<int*>(take(4 * 2 * R * max_tokens));
-    s.hfrm = reinterpret_cast<int*>(take(4 * 2 * R * max_tokens));
+    s.score = m.take<float>(R);
+    s.blen = m.take<int>(R);
+    s.nb = m.take<int>(B);
+    s.htok = m.take<int>(2 * R * max_tokens);
+    s.hfrm = m.take<int>(2 * R * max_tokens);
   } else {
-    s.n = reinterpret_cast<long*>(take(8 * (size_t)B));
+    s.n = m.take<long>(B);
   }
-  s.bytes = off;
   return s;
-}
-
-bool stream_ok(const S2tRnntLstmDesc* d, int beam, int max_tokens) {
-  return desc_ok(d) && beam >= 0 && beam <= kMaxBeam && max_tokens >= 1;
 }
 
 struct ResetArgs {
@@ -1083,18 +1029,6 @@ __global__ void beam_chunk_init_kernel(int* counts, int R) {
   if (threadIdx.x < 4) counts[threadIdx.x] = threadIdx.x == 2 ? R : 0;
 }
 
-__global__ __launch_bounds__(kThreads) void state_copy_kernel(const float* __restrict__ h_src,
-                                                              const float* __restrict__ c_src,
-                                                              const float* __restrict__ lm_src, float* h,
-                                                              float* c, float* lm, long n_state, long n_lm) {
-  const long step = (long)gridDim.x * kThreads;
-  for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n_state; i += step) {
-    h[i] = h_src[i];
-    c[i] = c_src[i];
-  }
-  for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n_lm; i += step) lm[i] = lm_src[i];
-}
-
 struct BeamEndArgs {
   const long* chunk_len;
   int Tc, beam, max_tokens;
@@ -1144,68 +1078,46 @@ __global__ __launch_bounds__(kThreads) void beam_chunk_end_kernel(BeamEndArgs a)
 
 // ------------------------------------------------------------------ chunk-carried search with the RNN-LM
 // The fused searches (s2t_rnnt_beam_lstm_lm, s2t_rnnt_beam_stateless_lm) fed their frames in pieces: the
-// rounds are beam_rounds_over with the LM, on carried buffers.  Behind the predictor's stream state the
+// rounds are beam_rounds with the LM, on carried buffers.  Behind the predictor's stream state the
 // caller's buffer holds the LM's live (h, c, q) and lm_sum; the workspace holds the second copy of (h, c,
 // q), and after an odd Tc ONE launch copies every survivor home, the predictor's and the LM's.
 struct LmStreamState {
   float *h, *c, *q;                // [layers][R][H] twice, [R][V]
   float* lm_sum;                   // [R]
-  size_t bytes;
 };
 
-LmStreamState carve_lm_state(const S2tRnnLmDesc& d, int B, int beam, void* base) {
+LmStreamState carve_lm_state(const S2tRnnLmDesc& d, int B, int beam, Arena& m) {
   const size_t R = (size_t)B * beam, L = d.num_layers;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto f = [&](size_t n) {
-    char* q = p + off;
-    off += align256(4 * n);
-    return reinterpret_cast<float*>(q);
-  };
   LmStreamState s{};
-  s.h = f(L * R * d.H);
-  s.c = f(L * R * d.H);
-  s.q = f(R * d.V);
-  s.lm_sum = f(R);
-  s.bytes = off;
+  s.h = m.take<float>(L * R * d.H);
+  s.c = m.take<float>(L * R * d.H);
+  s.q = m.take<float>(R * d.V);
+  s.lm_sum = m.take<float>(R);
   return s;
 }
 
 // the stateless predictor's stream state: StreamState with the context in place of (h, c)
 struct StatelessStreamState {
-  int* ctx;                        // [R][ctx]
-  float *lm, *score;               // [R][V], [R]
+  StatelessBuf live;               // (ctx, lm)
+  float* score;                    // [R]
   int *blen, *nb, *hdr;            // [R], [B], [B][kStreamHdr]
   int *htok, *hfrm;                // [B][2][beam][max_tokens]
-  size_t bytes;
 };
 
+// (the order is the header's documented layout)
 StatelessStreamState carve_stateless_state(const S2tRnntStatelessDesc& d, int B, int beam, int max_tokens,
-                                           void* base) {
+                                           Arena& m) {
   const size_t R = (size_t)B * beam;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* q = p + off;
-    off += align256(bytes);
-    return q;
-  };
   StatelessStreamState s{};
-  s.ctx = reinterpret_cast<int*>(take(4 * R * d.ctx));
-  s.lm = reinterpret_cast<float*>(take(4 * R * d.V));
-  s.hdr = reinterpret_cast<int*>(take(4 * (size_t)B * kStreamHdr));
-  s.score = reinterpret_cast<float*>(take(4 * R));
-  s.blen = reinterpret_cast<int*>(take(4 * R));
-  s.nb = reinterpret_cast<int*>(take(4 * (size_t)B));
-  s.htok = reinterpret_cast<int*>(take(4 * 2 * R * max_tokens));
-  s.hfrm = reinterpret_cast<int*>(take(4 * 2 * R * max_tokens));
-  s.bytes = off;
+  s.live.ctx = m.take<int>(R * d.ctx);
+  s.live.lm = m.take<float>(R * d.V);
+  s.hdr = m.take<int>((size_t)B * kStreamHdr);
+  s.score = m.take<float>(R);
+  s.blen = m.take<int>(R);
+  s.nb = m.take<int>(B);
+  s.htok = m.take<int>(2 * R * max_tokens);
+  s.hfrm = m.take<int>(2 * R * max_tokens);
   return s;
-}
-
-// pred_ok, V: the predictor descriptor's check and vocabulary
-bool lm_stream_ok(bool pred_ok, int V, const S2tRnnLmDesc* lm, int beam, int max_tokens) {
-  return pred_ok && lm_ok(lm) && lm->V == V && beam >= 1 && beam <= kMaxBeam && max_tokens >= 1;
 }
 
 // The LM workspace a chunk's rounds work on: buffer 0 is the state's (the live copy, frame 0 reads it),
@@ -1256,7 +1168,7 @@ struct CopyHomeArgs {
   long n[kCopyParts];              // 4-byte words (float or int); 0: unused
 };
 
-// state_copy_kernel for the fused searches: the predictor's survivors and the LM's in one launch
+// a chunk's copy-home: the predictor's survivors and the LM's in one launch
 __global__ __launch_bounds__(kThreads) void state_copy_parts_kernel(CopyHomeArgs a) {
   const long step = (long)gridDim.x * kThreads, i0 = (long)blockIdx.x * kThreads + threadIdx.x;
 #pragma unroll
@@ -1274,13 +1186,297 @@ void enqueue_copy_home(const CopyHomeArgs& c, hipStream_t st) {
   hipLaunchKernelGGL(state_copy_parts_kernel, dim3((int)(need < 1024 ? need : 1024)), dim3(kThreads), 0, st, c);
 }
 
+struct HomeList {
+  CopyHomeArgs c{};
+  int parts = 0;
+  void add(const void* src, void* dst, long n) {
+    c.src[parts] = src;
+    c.dst[parts] = dst;
+    c.n[parts++] = n;
+  }
+};
+
+// ------------------------------------------------------------------ the two predictors, as the beam search sees them
+// What beam_search and stream_reset below ask of a predictor: whether the descriptor is valid and its V;
+// the joint's arguments; its workspace (Work: two buffers `buf`, scratch, the search's arrays `s`) and its
+// stream state (State: the live buffer `live`, then score / blen / nb / hdr / htok / hfrm); how a buffer is
+// blanked for a whole-utterance search; its step from one buffer to another on the workspace's emit /
+// token; which arrays go home after an odd number of rounds; what the reset kernels are told.
+struct LstmPredictor {
+  using Work = Workspace;
+  using State = StreamState;
+  using Buf = StateBuf;
+  const S2tRnntLstmDesc* d;
+
+  bool ok() const { return desc_ok(d); }
+  int V() const { return d->V; }
+  JointArgs joint(const float* am, int T, const Work& w) const { return joint_args(*d, am, T, w.s); }
+  Work work(int B, int T, int beam, Arena& m, int n_state) const { return carve(*d, B, T, beam, m, n_state); }
+  State state(int B, int beam, int max_tokens, Arena& m) const { return carve_state(*d, B, beam, max_tokens, m); }
+  hipError_t blank(const Buf& b, int R, hipStream_t st) const {   // zero (h, c)
+    const size_t bytes = sizeof(float) * (size_t)d->num_layers * R * d->H;
+    const hipError_t e = hipMemsetAsync(b.h, 0, bytes, st);
+    return e == hipSuccess ? hipMemsetAsync(b.c, 0, bytes, st) : e;
+  }
+  // parent NULL: in place (src is dst)
+  void step(int R, const Work& w, const int* parent, const int* count, const Buf& src, const Buf& dst,
+            hipStream_t st) const {
+    enqueue_pred_step(*d, R, w.s.token, w.s.emit, parent, count, src.h, src.c, src.lm, dst.h, dst.c, dst.lm, w, st);
+  }
+  void home(HomeList& l, int R, const Buf& src, const Buf& dst) const {
+    const long n_state = (long)d->num_layers * R * d->H;
+    l.add(src.h, dst.h, n_state);
+    l.add(src.c, dst.c, n_state);
+    l.add(src.lm, dst.lm, (long)R * d->V);
+  }
+  void reset_args(const State& s, ResetArgs& a, LmResetArgs&) const {   // (h, c) to zero, greedy's counter
+    a.layers = d->num_layers;
+    a.H = d->H;
+    a.h = s.live.h;
+    a.c = s.live.c;
+    a.n = s.n;
+  }
+};
+
+struct StatelessPredictor {
+  using Work = StatelessWorkspace;
+  using State = StatelessStreamState;
+  using Buf = StatelessBuf;
+  const S2tRnntStatelessDesc* d;
+
+  bool ok() const { return stateless_ok(d); }
+  int V() const { return d->V; }
+  JointArgs joint(const float* am, int T, const Work& w) const { return joint_args(*d, am, T, w.s); }
+  Work work(int B, int T, int beam, Arena& m, int n_state) const {
+    return carve_stateless(*d, B, T, beam, m, n_state);
+  }
+  State state(int B, int beam, int max_tokens, Arena& m) const {
+    return carve_stateless_state(*d, B, beam, max_tokens, m);
+  }
+  hipError_t blank(const Buf& b, int R, hipStream_t st) const {   // a context of blanks
+    return hipMemsetAsync(b.ctx, 0, sizeof(int) * (size_t)R * d->ctx, st);
+  }
+  void step(int R, const Work& w, const int* parent, const int* count, const Buf& src, const Buf& dst,
+            hipStream_t st) const {
+    enqueue_stateless_step(*d, R, w.s.token, w.s.emit, parent, count, src.ctx, src.lm, dst.ctx, dst.lm, w, st);
+  }
+  void home(HomeList& l, int R, const Buf& src, const Buf& dst) const {
+    l.add(src.ctx, dst.ctx, (long)R * d->ctx);
+    l.add(src.lm, dst.lm, (long)R * d->V);
+  }
+  // (no LSTM layers: the predictor's state is the context, which the LM's reset blanks)
+  void reset_args(const State& s, ResetArgs&, LmResetArgs& la) const {
+    la.nctx = d->ctx;
+    la.ctx = s.live.ctx;
+  }
+};
+
+// ------------------------------------------------------------------ the beam search, whole or a chunk of it
+struct Fusion {                    // shallow fusion with an RNN-LM
+  const S2tRnnLmDesc* lm;
+  float weight;
+  int start_token;                 // the LM's first input, < 0: none (a chunk call: the reset has taken it)
+  float* lm_score;                 // [B]
+};
+
+struct Chunk {                     // a chunk call: the caller's state, and what it answers beside the search's outputs
+  void* state;
+  int max_tokens;
+  long* stable_len;
+  int* overflow;
+};
+
+bool beam_ok(int beam, int least) { return beam >= least && beam <= kMaxBeam; }
+bool chunk_ok(int Tc) { return Tc >= 1 && Tc <= kMaxChunk; }
+bool fusion_ok(const S2tRnnLmDesc* lm, int V) { return lm_ok(lm) && lm->V == V; }
+
+// The T rounds of a beam search: frame t reads buf[t & 1] and leaves the survivors in buf[~t & 1], by the
+// predictor's step on a.token / a.emit / a.parent / a.counts + cur.  With an LM (shallow fusion) its step
+// follows the predictor's on the same four, from its buffer cur to nxt.
+template <class P>
+void beam_rounds(const P& p, BeamArgs a, const typename P::Buf (&buf)[2], const typename P::Work& w,
+                 const S2tRnnLmDesc* lm, const LmWorkspace& lw, int T, hipStream_t st) {
+  const int R = a.B * a.beam;
+  for (int t = 0; t < T; ++t) {
+    const int cur = t & 1, nxt = cur ^ 1;
+    a.t = t;
+    a.parity = cur;
+    a.lm = buf[cur].lm;
+    if (lm) a.q = lw.q[cur];
+    hipLaunchKernelGGL(beam_expand_kernel, dim3(R), dim3(kThreads), 0, st, a);
+    hipLaunchKernelGGL(beam_select_kernel, dim3(a.B), dim3(kThreads), 0, st, a);
+    p.step(R, w, a.parent, a.counts + cur, buf[cur], buf[nxt], st);
+    if (lm)
+      enqueue_lm_step(*lm, R, a.token, a.emit, a.parent, a.counts + cur, lw.h[cur], lw.c[cur], lw.q[cur],
+                      lw.h[nxt], lw.c[nxt], lw.q[nxt], lw, st);
+  }
+}
+
+// Every lockstep beam entry point: predictor p, with an LM or not (f NULL), the whole utterance (ch NULL:
+// state in the workspace, blanked here, the best beam traced back at the end) or one chunk of it (the live
+// state is the caller's: frame 0 reads it, an odd T copies the survivors home, the records become histories).
+template <class P>
+int beam_search(const P& p, const Fusion* f, const Chunk* ch, const float* am, const long* lengths, int B, int T,
+                int beam, int topk, void* workspace, long* tokens, long* frames, long* out_len, float* score,
+                hipStream_t st) {
+  if (B <= 0) return 0;
+  if (!p.ok() || (f && !fusion_ok(f->lm, p.V())) || !beam_ok(beam, 1) || topk < 1 ||
+      (topk < p.V() ? topk : p.V()) > kMaxBeam || (f && f->start_token >= p.V()) ||
+      (f && !__builtin_isfinite(f->weight)) || (ch ? !chunk_ok(T) || ch->max_tokens < 1 || !ch->state : T <= 0) ||
+      !workspace)
+    return -1;
+  const S2tRnnLmDesc* lm = f ? f->lm : nullptr;
+  const int R = B * beam, n_state = ch ? 1 : 2;
+  Arena wm(workspace);
+  const typename P::Work w = p.work(B, T, beam, wm, n_state);
+  const SearchArrays& s = w.s;
+  LmWorkspace lw{};
+  if (f) lw = carve_lm(*lm, B, beam, wm, n_state);
+  typename P::State carried{};     // a chunk: the caller's state; buf[0] is its live copy
+  typename P::Buf buf[2] = {w.buf[0], w.buf[1]};
+  if (ch) {
+    Arena sm(ch->state);
+    carried = p.state(B, beam, ch->max_tokens, sm);
+    buf[1] = buf[0];
+    buf[0] = carried.live;
+    if (f) lw = live_lm(lw, carve_lm_state(*lm, B, beam, sm));
+    hipLaunchKernelGGL(beam_chunk_init_kernel, dim3(1), dim3(64), 0, st, s.counts, R);
+  } else {
+    hipError_t e = p.blank(buf[0], R, st);
+    if (f) {
+      const size_t lm_state = sizeof(float) * (size_t)lm->num_layers * R * lm->H;
+      if (e == hipSuccess) e = hipMemsetAsync(lw.h[0], 0, lm_state, st);
+      if (e == hipSuccess) e = hipMemsetAsync(lw.c[0], 0, lm_state, st);
+      if (e == hipSuccess) e = hipMemsetAsync(lw.q[0], 0, sizeof(float) * (size_t)R * p.V(), st);
+    }
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(beam_init_kernel, dim3(1), dim3(kThreads), 0, st, B, beam, s.score, s.blen, s.nb, s.emit,
+                       s.token, s.counts);
+    if (f)
+      hipLaunchKernelGGL(lm_start_kernel, dim3((R + kThreads - 1) / kThreads), dim3(kThreads), 0, st, R,
+                         f->start_token, lw.tok, lw.lm_sum);
+    p.step(R, w, nullptr, s.counts + 2, buf[0], buf[0], st);   // the first step: blank, from the blanked state
+    if (f && f->start_token >= 0)                          // the LM's first step, as the predictor's on blank
+      enqueue_lm_step(*lm, R, lw.tok, s.emit, nullptr, s.counts + 2, lw.h[0], lw.c[0], lw.q[0], lw.h[0], lw.c[0],
+                      lw.q[0], lw, st);
+  }
+  BeamArgs a{};                    // (t, parity, lm and q are the round's)
+  a.j = p.joint(am, T, w);
+  a.lengths = lengths;
+  a.B = B;
+  a.beam = beam;
+  a.topk = topk;
+  a.cscore = s.cscore;
+  a.ccls = s.ccls;
+  a.score = ch ? carried.score : s.score;
+  a.blen = ch ? carried.blen : s.blen;
+  a.nb = ch ? carried.nb : s.nb;
+  a.rec = s.rec;
+  a.emit = s.emit;
+  a.token = s.token;
+  a.parent = s.parent;
+  a.counts = s.counts;
+  if (f) {                         // else q stays NULL: no fusion
+    a.lm_weight = f->weight;
+    a.cq = lw.cq;
+    a.lm_sum = lw.lm_sum;
+  }
+  beam_rounds(p, a, buf, w, lm, lw, T, st);
+  const float* lm_sum = f ? lw.lm_sum : nullptr;
+  float* lm_score = f ? f->lm_score : nullptr;
+  if (ch) {
+    if (T & 1) {                                           // the live copies go home
+      HomeList l;
+      p.home(l, R, buf[1], buf[0]);
+      if (f) {
+        const long n_lstate = (long)lm->num_layers * R * lm->H;
+        l.add(lw.h[1], lw.h[0], n_lstate);
+        l.add(lw.c[1], lw.c[0], n_lstate);
+        l.add(lw.q[1], lw.q[0], (long)R * p.V());
+      }
+      enqueue_copy_home(l.c, st);
+    }
+    BeamEndArgs e{lengths, T, beam, ch->max_tokens, s.rec, carried.blen, carried.nb, carried.score, carried.hdr,
+                  carried.htok, carried.hfrm, tokens, frames, out_len, score, ch->stable_len, ch->overflow, lm_sum, lm_score};
+    hipLaunchKernelGGL(beam_chunk_end_kernel, dim3(B), dim3(kThreads), 0, st, e);
+  } else {
+    hipLaunchKernelGGL(beam_trace_kernel, dim3(B), dim3(64), 0, st, lengths, T, beam, s.rec, s.blen, s.score,
+                       tokens, frames, out_len, score, lm_sum, lm_score);
+  }
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+// Every stream reset: the rows the mask names become the empty hypothesis (with an LM: its state too), then
+// the one-shot call's own first step(s) with emit = the mask.
+template <class P>
+int stream_reset(const P& p, const Fusion* f, void* state, const int* rows, int B, int beam, int max_tokens,
+                 void* workspace, hipStream_t st) {
+  if (B <= 0) return 0;
+  if (!p.ok() || (f && !fusion_ok(f->lm, p.V())) || !beam_ok(beam, f ? 1 : 0) || max_tokens < 1 ||
+      (f && f->start_token >= p.V()) || !state || !workspace)
+    return -1;
+  const int BS = beam > 0 ? beam : 1, R = B * BS;
+  Arena sm(state), wm(workspace);
+  const typename P::State s = p.state(B, beam, max_tokens, sm);
+  const typename P::Work w = p.work(B, 1, beam, wm, beam > 0 ? 1 : 0);
+  LmStreamState ls{};
+  LmWorkspace lw{};
+  if (f) {
+    ls = carve_lm_state(*f->lm, B, beam, sm);
+    lw = carve_lm(*f->lm, B, beam, wm, 1);
+  }
+  // as for a predictor without LSTM layers or context; the predictor fills in its own
+  ResetArgs a{rows, beam, BS, 0, 0, nullptr, nullptr, s.score, s.blen, s.nb, s.hdr, nullptr, w.s.emit, w.s.token};
+  LmResetArgs la{rows, BS, f ? f->lm->num_layers : 0, f ? f->lm->H : 0, p.V(), 0, f ? f->start_token : -1,
+                 ls.h, ls.c, ls.q, ls.lm_sum, lw.tok, nullptr};
+  p.reset_args(s, a, la);
+  hipLaunchKernelGGL(stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, a);
+  if (f) hipLaunchKernelGGL(lm_stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, la);
+  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, st, w.s.emit, R, w.s.counts + 2);
+  p.step(R, w, nullptr, w.s.counts + 2, s.live, s.live, st);
+  if (f && f->start_token >= 0)                            // the LM's first step, as the predictor's on blank
+    enqueue_lm_step(*f->lm, R, lw.tok, w.s.emit, nullptr, w.s.counts + 2, ls.h, ls.c, ls.q, ls.h, ls.c, ls.q, lw,
+                    st);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------ sizes, on the host
+template <class Carve>
+long bytes_of(Carve carve) {
+  Arena m(nullptr);
+  carve(m);
+  return (long)m.bytes;
+}
+
+// a fused search's workspace: the predictor's, then the LM's
+template <class P>
+long fused_workspace_bytes(const P& p, const S2tRnnLmDesc* lm, int B, int T, int beam, int n_state) {
+  if (!p.ok() || !fusion_ok(lm, p.V()) || B <= 0 || T < 0 || !beam_ok(beam, 1)) return 0;
+  return bytes_of([&](Arena& m) {
+    p.work(B, T, beam, m, n_state);
+    carve_lm(*lm, B, beam, m, n_state);
+  });
+}
+
+// a fused search's stream state: the predictor's, then the LM's
+template <class P>
+long fused_state_bytes(const P& p, const S2tRnnLmDesc* lm, int B, int beam, int max_tokens) {
+  if (B <= 0 || !p.ok() || !fusion_ok(lm, p.V()) || !beam_ok(beam, 1) || max_tokens < 1) return 0;
+  return bytes_of([&](Arena& m) {
+    p.state(B, beam, max_tokens, m);
+    carve_lm_state(*lm, B, beam, m);
+  });
+}
+
 }  // namespace
 
 extern "C" {
 
 long s2t_rnnt_lstm_workspace_bytes(const S2tRnntLstmDesc* desc, int B, int T, int beam_size) {
-  if (!desc_ok(desc) || B <= 0 || T < 0 || beam_size < 0 || beam_size > kMaxBeam) return 0;
-  return (long)carve(*desc, B, T, beam_size, nullptr).bytes;
+  if (!desc_ok(desc) || B <= 0 || T < 0 || !beam_ok(beam_size, 0)) return 0;
+  return bytes_of([&](Arena& m) { carve(*desc, B, T, beam_size, m); });
 }
 
 int s2t_lstm_pred_step(const S2tRnntLstmDesc* desc, int R, const int* tokens, const int* emit,
@@ -1290,9 +1486,10 @@ int s2t_lstm_pred_step(const S2tRnntLstmDesc* desc, int R, const int* tokens, co
   if (!desc_ok(desc) || !workspace) return -1;
   const bool same = h_in == h_out;
   if (same != (c_in == c_out) || same != (lm_in == lm_out) || (same && parent)) return -1;
-  const Workspace w = carve(*desc, R, 0, 0, workspace);
-  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, emit, R, w.counts);
-  enqueue_pred_step(*desc, R, tokens, emit, parent, w.counts, h_in, c_in, lm_in, h_out, c_out, lm_out, w,
+  Arena m(workspace);
+  const Workspace w = carve(*desc, R, 0, 0, m);
+  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, emit, R, w.s.counts);
+  enqueue_pred_step(*desc, R, tokens, emit, parent, w.s.counts, h_in, c_in, lm_in, h_out, c_out, lm_out, w,
                     (hipStream_t)stream);
   S2T_CHECK_LAUNCH();
   return 0;
@@ -1303,54 +1500,32 @@ int s2t_rnnt_greedy_lstm(const S2tRnntLstmDesc* desc, const float* am, const lon
                          void* stream) {
   if (B <= 0) return 0;
   if (!desc_ok(desc) || T <= 0 || max_token_step < 0 || !workspace) return -1;
-  const S2tRnntLstmDesc& d = *desc;
+  const LstmPredictor p{desc};
   hipStream_t st = (hipStream_t)stream;
-  const Workspace w = carve(d, B, T, 0, workspace);
-  const size_t state = sizeof(float) * (size_t)d.num_layers * B * d.H;
-  hipError_t e = hipMemsetAsync(w.h[0], 0, state, st);
-  if (e == hipSuccess) e = hipMemsetAsync(w.c[0], 0, state, st);
+  Arena m(workspace);
+  const Workspace w = p.work(B, T, 0, m, 2);
+  const SearchArrays& s = w.s;
+  const StateBuf& b = w.buf[0];
+  const hipError_t e = p.blank(b, B, st);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(greedy_init_kernel, dim3(1), dim3(kThreads), 0, st, lengths, B, T, w.t, w.nts, w.done,
-                     w.emit, w.token, w.counts, out_len);
-  enqueue_pred_step(d, B, w.token, w.emit, nullptr, w.counts + 2, w.h[0], w.c[0], w.lm[0], w.h[0], w.c[0],
-                    w.lm[0], w, st);
-  GreedyArgs g{joint_args(d, am, T, w), lengths, w.lm[0], max_token_step, T * (max_token_step + 1), 0,
-               w.t, w.nts, w.done, w.emit, w.token, w.counts, tokens, out_len};
-  return greedy_rounds(d, B, g, w.h[0], w.c[0], w.lm[0], w, (long)T * (max_token_step + 2), 1, st);
+                     s.emit, s.token, s.counts, out_len);
+  p.step(B, w, nullptr, s.counts + 2, b, b, st);
+  GreedyArgs g{p.joint(am, T, w), lengths, b.lm, max_token_step, T * (max_token_step + 1), 0,
+               w.t, w.nts, w.done, s.emit, s.token, s.counts, tokens, out_len};
+  return greedy_rounds(*desc, B, g, b.h, b.c, b.lm, w, (long)T * (max_token_step + 2), 1, st);
 }
 
 int s2t_rnnt_beam_lstm(const S2tRnntLstmDesc* desc, const float* am, const long* lengths, int B,
                        int T, int beam_size, int cutoff_top_k, void* workspace, long* tokens,
                        long* frames, long* out_len, float* score, void* stream) {
-  if (B <= 0) return 0;
-  if (!desc_ok(desc) || T <= 0 || beam_size < 1 || beam_size > kMaxBeam || cutoff_top_k < 1 ||
-      (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam || !workspace)
-    return -1;
-  const S2tRnntLstmDesc& d = *desc;
-  hipStream_t st = (hipStream_t)stream;
-  const int R = B * beam_size;
-  const Workspace w = carve(d, B, T, beam_size, workspace);
-  const size_t state = sizeof(float) * (size_t)d.num_layers * R * d.H;
-  hipError_t e = hipMemsetAsync(w.h[0], 0, state, st);
-  if (e == hipSuccess) e = hipMemsetAsync(w.c[0], 0, state, st);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(beam_init_kernel, dim3(1), dim3(kThreads), 0, st, B, beam_size, w.score, w.blen, w.nb,
-                     w.emit, w.token, w.counts);
-  enqueue_pred_step(d, R, w.token, w.emit, nullptr, w.counts + 2, w.h[0], w.c[0], w.lm[0], w.h[0], w.c[0],
-                    w.lm[0], w, st);
-  BeamArgs a{joint_args(d, am, T, w), lengths, w.lm[0], 0, B, beam_size, cutoff_top_k, 0, w.cscore, w.score,
-             w.ccls, w.blen, w.nb, w.rec, w.emit, w.token, w.parent, w.counts, nullptr, 0.f, nullptr, nullptr};
-  const StateBuf buf[2] = {{w.h[0], w.c[0], w.lm[0]}, {w.h[1], w.c[1], w.lm[1]}};
-  beam_rounds(d, a, buf, w, T, st);
-  hipLaunchKernelGGL(beam_trace_kernel, dim3(B), dim3(64), 0, st, lengths, T, beam_size, w.rec, w.blen,
-                     w.score, tokens, frames, out_len, score, (const float*)nullptr, (float*)nullptr);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  return beam_search(LstmPredictor{desc}, nullptr, nullptr, am, lengths, B, T, beam_size, cutoff_top_k, workspace,
+                     tokens, frames, out_len, score, (hipStream_t)stream);
 }
 
 long s2t_rnn_lm_step_workspace_bytes(const S2tRnnLmDesc* lm, int R) {
   if (!lm_ok(lm) || R <= 0) return 0;
-  return (long)carve_lm(*lm, R, 0, nullptr, 0).bytes;
+  return bytes_of([&](Arena& m) { carve_lm(*lm, R, 0, m, 0); });
 }
 
 int s2t_rnn_lm_step(const S2tRnnLmDesc* lm, int R, const int* tokens, const int* emit, const int* parent,
@@ -1360,7 +1535,8 @@ int s2t_rnn_lm_step(const S2tRnnLmDesc* lm, int R, const int* tokens, const int*
   if (!lm_ok(lm) || !workspace) return -1;
   const bool same = h_in == h_out;
   if (same != (c_in == c_out) || same != (q_in == q_out) || (same && parent)) return -1;
-  const LmWorkspace w = carve_lm(*lm, R, 0, workspace, 0);
+  Arena m(workspace);
+  const LmWorkspace w = carve_lm(*lm, R, 0, m, 0);
   hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, emit, R, w.counts);
   enqueue_lm_step(*lm, R, tokens, emit, parent, w.counts, h_in, c_in, q_in, h_out, c_out, q_out, w,
                   (hipStream_t)stream);
@@ -1370,57 +1546,21 @@ int s2t_rnn_lm_step(const S2tRnnLmDesc* lm, int R, const int* tokens, const int*
 
 long s2t_rnnt_beam_lstm_lm_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B, int T,
                                            int beam_size) {
-  if (!desc_ok(desc) || !lm_ok(lm) || lm->V != desc->V || B <= 0 || T < 0 || beam_size < 1 ||
-      beam_size > kMaxBeam)
-    return 0;
-  return (long)(carve(*desc, B, T, beam_size, nullptr).bytes + carve_lm(*lm, B, beam_size, nullptr, 2).bytes);
+  return fused_workspace_bytes(LstmPredictor{desc}, lm, B, T, beam_size, 2);
 }
 
 int s2t_rnnt_beam_lstm_lm(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, const float* am,
                           const long* lengths, int B, int T, int beam_size, int cutoff_top_k, float lm_weight,
                           int lm_start_token, void* workspace, long* tokens, long* frames, long* out_len,
                           float* score, float* lm_score, void* stream) {
-  if (B <= 0) return 0;
-  if (!desc_ok(desc) || !lm_ok(lm) || lm->V != desc->V || T <= 0 || beam_size < 1 || beam_size > kMaxBeam ||
-      cutoff_top_k < 1 || (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam ||
-      lm_start_token >= desc->V || !__builtin_isfinite(lm_weight) || !workspace)
-    return -1;
-  const S2tRnntLstmDesc& d = *desc;
-  hipStream_t st = (hipStream_t)stream;
-  const int R = B * beam_size;
-  const Workspace w = carve(d, B, T, beam_size, workspace);
-  const LmWorkspace lw = carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 2);
-  const size_t state = sizeof(float) * (size_t)d.num_layers * R * d.H;
-  const size_t lm_state = sizeof(float) * (size_t)lm->num_layers * R * lm->H;
-  hipError_t e = hipMemsetAsync(w.h[0], 0, state, st);
-  if (e == hipSuccess) e = hipMemsetAsync(w.c[0], 0, state, st);
-  if (e == hipSuccess) e = hipMemsetAsync(lw.h[0], 0, lm_state, st);
-  if (e == hipSuccess) e = hipMemsetAsync(lw.c[0], 0, lm_state, st);
-  if (e == hipSuccess) e = hipMemsetAsync(lw.q[0], 0, sizeof(float) * (size_t)R * d.V, st);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(beam_init_kernel, dim3(1), dim3(kThreads), 0, st, B, beam_size, w.score, w.blen, w.nb,
-                     w.emit, w.token, w.counts);
-  hipLaunchKernelGGL(lm_start_kernel, dim3((R + kThreads - 1) / kThreads), dim3(kThreads), 0, st, R,
-                     lm_start_token, lw.tok, lw.lm_sum);
-  enqueue_pred_step(d, R, w.token, w.emit, nullptr, w.counts + 2, w.h[0], w.c[0], w.lm[0], w.h[0], w.c[0],
-                    w.lm[0], w, st);
-  if (lm_start_token >= 0)                                 // the LM's first step, as the predictor's on blank
-    enqueue_lm_step(*lm, R, lw.tok, w.emit, nullptr, w.counts + 2, lw.h[0], lw.c[0], lw.q[0], lw.h[0], lw.c[0],
-                    lw.q[0], lw, st);
-  BeamArgs a{joint_args(d, am, T, w), lengths, w.lm[0], 0, B, beam_size, cutoff_top_k, 0, w.cscore, w.score,
-             w.ccls, w.blen, w.nb, w.rec, w.emit, w.token, w.parent, w.counts, lw.q[0], lm_weight, lw.cq,
-             lw.lm_sum};
-  const StateBuf buf[2] = {{w.h[0], w.c[0], w.lm[0]}, {w.h[1], w.c[1], w.lm[1]}};
-  beam_rounds(d, a, buf, w, T, st, lm, &lw);
-  hipLaunchKernelGGL(beam_trace_kernel, dim3(B), dim3(64), 0, st, lengths, T, beam_size, w.rec, w.blen,
-                     w.score, tokens, frames, out_len, score, (const float*)lw.lm_sum, lm_score);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  const Fusion f{lm, lm_weight, lm_start_token, lm_score};
+  return beam_search(LstmPredictor{desc}, &f, nullptr, am, lengths, B, T, beam_size, cutoff_top_k, workspace,
+                     tokens, frames, out_len, score, (hipStream_t)stream);
 }
 
 long s2t_stateless_pred_step_workspace_bytes(const S2tRnntStatelessDesc* desc, int R) {
   if (!stateless_ok(desc) || R <= 0) return 0;
-  return (long)carve_stateless(*desc, R, 0, 0, nullptr, 0).bytes;
+  return bytes_of([&](Arena& m) { carve_stateless(*desc, R, 0, 0, m, 0); });
 }
 
 int s2t_stateless_pred_step(const S2tRnntStatelessDesc* desc, int R, const int* tokens, const int* emit,
@@ -1430,9 +1570,10 @@ int s2t_stateless_pred_step(const S2tRnntStatelessDesc* desc, int R, const int* 
   if (!stateless_ok(desc) || !workspace) return -1;
   const bool same = ctx_in == ctx_out;
   if (same != (lm_in == lm_out) || (same && parent)) return -1;
-  const StatelessWorkspace w = carve_stateless(*desc, R, 0, 0, workspace, 0);
-  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, emit, R, w.counts);
-  enqueue_stateless_step(*desc, R, tokens, emit, parent, w.counts, ctx_in, lm_in, ctx_out, lm_out, w,
+  Arena m(workspace);
+  const StatelessWorkspace w = carve_stateless(*desc, R, 0, 0, m, 0);
+  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, emit, R, w.s.counts);
+  enqueue_stateless_step(*desc, R, tokens, emit, parent, w.s.counts, ctx_in, lm_in, ctx_out, lm_out, w,
                          (hipStream_t)stream);
   S2T_CHECK_LAUNCH();
   return 0;
@@ -1440,103 +1581,52 @@ int s2t_stateless_pred_step(const S2tRnntStatelessDesc* desc, int R, const int* 
 
 long s2t_rnnt_beam_stateless_lm_workspace_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, int B,
                                                 int T, int beam_size) {
-  if (!stateless_ok(desc) || !lm_ok(lm) || lm->V != desc->V || B <= 0 || T < 0 || beam_size < 1 ||
-      beam_size > kMaxBeam)
-    return 0;
-  return (long)(carve_stateless(*desc, B, T, beam_size, nullptr, 2).bytes +
-                carve_lm(*lm, B, beam_size, nullptr, 2).bytes);
+  return fused_workspace_bytes(StatelessPredictor{desc}, lm, B, T, beam_size, 2);
 }
 
 int s2t_rnnt_beam_stateless_lm(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, const float* am,
                                const long* lengths, int B, int T, int beam_size, int cutoff_top_k,
                                float lm_weight, int lm_start_token, void* workspace, long* tokens,
                                long* frames, long* out_len, float* score, float* lm_score, void* stream) {
-  if (B <= 0) return 0;
-  if (!stateless_ok(desc) || !lm_ok(lm) || lm->V != desc->V || T <= 0 || beam_size < 1 ||
-      beam_size > kMaxBeam || cutoff_top_k < 1 || (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam ||
-      lm_start_token >= desc->V || !__builtin_isfinite(lm_weight) || !workspace)
-    return -1;
-  const S2tRnntStatelessDesc& d = *desc;
-  hipStream_t st = (hipStream_t)stream;
-  const int R = B * beam_size;
-  const StatelessWorkspace w = carve_stateless(d, B, T, beam_size, workspace, 2);
-  const LmWorkspace lw = carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 2);
-  const size_t lm_state = sizeof(float) * (size_t)lm->num_layers * R * lm->H;
-  hipError_t e = hipMemsetAsync(w.ctx[0], 0, sizeof(int) * (size_t)R * d.ctx, st);   // ctx blanks
-  if (e == hipSuccess) e = hipMemsetAsync(lw.h[0], 0, lm_state, st);
-  if (e == hipSuccess) e = hipMemsetAsync(lw.c[0], 0, lm_state, st);
-  if (e == hipSuccess) e = hipMemsetAsync(lw.q[0], 0, sizeof(float) * (size_t)R * d.V, st);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(beam_init_kernel, dim3(1), dim3(kThreads), 0, st, B, beam_size, w.score, w.blen, w.nb,
-                     w.emit, w.token, w.counts);
-  hipLaunchKernelGGL(lm_start_kernel, dim3((R + kThreads - 1) / kThreads), dim3(kThreads), 0, st, R,
-                     lm_start_token, lw.tok, lw.lm_sum);
-  enqueue_stateless_step(d, R, w.token, w.emit, nullptr, w.counts + 2, w.ctx[0], w.lm[0], w.ctx[0], w.lm[0], w,
-                         st);
-  if (lm_start_token >= 0)                                 // the LM's first step, as the predictor's on blank
-    enqueue_lm_step(*lm, R, lw.tok, w.emit, nullptr, w.counts + 2, lw.h[0], lw.c[0], lw.q[0], lw.h[0], lw.c[0],
-                    lw.q[0], lw, st);
-  BeamArgs a{JointArgs{am, T, d.V, d.inner, d.act, d.out1_w, d.out1_b, d.out2_w, d.out2_b, w.z, w.mid, w.logit},
-             lengths, w.lm[0], 0, B, beam_size, cutoff_top_k, 0, w.cscore, w.score, w.ccls, w.blen, w.nb, w.rec,
-             w.emit, w.token, w.parent, w.counts, lw.q[0], lm_weight, lw.cq, lw.lm_sum};
-  float* const lm_rows[2] = {w.lm[0], w.lm[1]};
-  beam_rounds_over(
-      a, lm_rows,
-      [&](int cur, int nxt) {
-        enqueue_stateless_step(d, R, w.token, w.emit, w.parent, w.counts + cur, w.ctx[cur], w.lm[cur], w.ctx[nxt],
-                               w.lm[nxt], w, st);
-      },
-      T, st, lm, &lw);
-  hipLaunchKernelGGL(beam_trace_kernel, dim3(B), dim3(64), 0, st, lengths, T, beam_size, w.rec, w.blen,
-                     w.score, tokens, frames, out_len, score, (const float*)lw.lm_sum, lm_score);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  const Fusion f{lm, lm_weight, lm_start_token, lm_score};
+  return beam_search(StatelessPredictor{desc}, &f, nullptr, am, lengths, B, T, beam_size, cutoff_top_k, workspace,
+                     tokens, frames, out_len, score, (hipStream_t)stream);
 }
 
 long s2t_rnnt_lstm_stream_state_bytes(const S2tRnntLstmDesc* desc, int B, int beam_size, int max_tokens) {
-  if (B <= 0 || !stream_ok(desc, beam_size, max_tokens)) return 0;
-  return (long)carve_state(*desc, B, beam_size, max_tokens, nullptr).bytes;
+  if (B <= 0 || !desc_ok(desc) || !beam_ok(beam_size, 0) || max_tokens < 1) return 0;
+  return bytes_of([&](Arena& m) { carve_state(*desc, B, beam_size, max_tokens, m); });
 }
 
 long s2t_rnnt_lstm_stream_workspace_bytes(const S2tRnntLstmDesc* desc, int B, int Tc, int beam_size) {
-  if (!desc_ok(desc) || B <= 0 || Tc < 1 || Tc > kMaxChunk || beam_size < 0 || beam_size > kMaxBeam) return 0;
-  return (long)carve(*desc, B, Tc, beam_size, nullptr, beam_size > 0 ? 1 : 0).bytes;
+  if (!desc_ok(desc) || B <= 0 || !chunk_ok(Tc) || !beam_ok(beam_size, 0)) return 0;
+  return bytes_of([&](Arena& m) { carve(*desc, B, Tc, beam_size, m, beam_size > 0 ? 1 : 0); });
 }
 
 int s2t_rnnt_lstm_stream_reset(const S2tRnntLstmDesc* desc, void* state, const int* rows, int B,
                                int beam_size, int max_tokens, void* workspace, void* stream) {
-  if (B <= 0) return 0;
-  if (!stream_ok(desc, beam_size, max_tokens) || !state || !workspace) return -1;
-  const S2tRnntLstmDesc& d = *desc;
-  hipStream_t st = (hipStream_t)stream;
-  const int BS = beam_size > 0 ? beam_size : 1, R = B * BS;
-  const StreamState s = carve_state(d, B, beam_size, max_tokens, state);
-  const Workspace w = carve(d, B, 1, beam_size, workspace, beam_size > 0 ? 1 : 0);
-  ResetArgs a{rows, beam_size, BS, d.num_layers, d.H, s.h, s.c, s.score, s.blen, s.nb, s.hdr, s.n, w.emit, w.token};
-  hipLaunchKernelGGL(stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, a);
-  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, st, w.emit, R, w.counts + 2);
-  enqueue_pred_step(d, R, w.token, w.emit, nullptr, w.counts + 2, s.h, s.c, s.lm, s.h, s.c, s.lm, w, st);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  return stream_reset(LstmPredictor{desc}, nullptr, state, rows, B, beam_size, max_tokens, workspace,
+                      (hipStream_t)stream);
 }
 
 int s2t_rnnt_greedy_lstm_chunk(const S2tRnntLstmDesc* desc, const float* am, const long* chunk_len, int B,
                                int Tc, int max_token_step, int max_tokens, int host_poll, void* state,
                                void* workspace, long* tokens, long* out_len, int* overflow, void* stream) {
   if (B <= 0) return 0;
-  if (!stream_ok(desc, 0, max_tokens) || Tc < 1 || Tc > kMaxChunk || max_token_step < 0 || !state || !workspace)
-    return -1;
+  if (!desc_ok(desc) || max_tokens < 1 || !chunk_ok(Tc) || max_token_step < 0 || !state || !workspace) return -1;
   const S2tRnntLstmDesc& d = *desc;
   hipStream_t st = (hipStream_t)stream;
-  const StreamState s = carve_state(d, B, 0, max_tokens, state);
-  const Workspace w = carve(d, B, Tc, 0, workspace, 0);
+  Arena sm(state), wm(workspace);
+  const StreamState s = carve_state(d, B, 0, max_tokens, sm);
+  const Workspace w = carve(d, B, Tc, 0, wm, 0);
   hipLaunchKernelGGL(greedy_chunk_init_kernel, dim3(1), dim3(kThreads), 0, st, chunk_len, B, w.t, w.nts, w.done,
-                     w.emit, w.token, w.counts);
+                     w.s.emit, w.s.token, w.s.counts);
   // the walk's own counter of symbols is the state's: it appends to the caller's tokens at the
   // stream's length and goes on counting past max_tokens
-  GreedyArgs g{joint_args(d, am, Tc, w), chunk_len, s.lm, max_token_step, max_tokens, 0,
-               w.t, w.nts, w.done, w.emit, w.token, w.counts, tokens, s.n};
-  const int rc = greedy_rounds(d, B, g, s.h, s.c, s.lm, w, (long)Tc * (max_token_step + 2), host_poll, st);
+  GreedyArgs g{joint_args(d, am, Tc, w.s), chunk_len, s.live.lm, max_token_step, max_tokens, 0,
+               w.t, w.nts, w.done, w.s.emit, w.s.token, w.s.counts, tokens, s.n};
+  const int rc = greedy_rounds(d, B, g, s.live.h, s.live.c, s.live.lm, w, (long)Tc * (max_token_step + 2), host_poll,
+                               st);
   if (rc != 0) return rc;
   hipLaunchKernelGGL(greedy_chunk_end_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
                      chunk_len, B, Tc, max_tokens, s.n, s.hdr, out_len, overflow);
@@ -1548,74 +1638,27 @@ int s2t_rnnt_beam_lstm_chunk(const S2tRnntLstmDesc* desc, const float* am, const
                              int Tc, int beam_size, int cutoff_top_k, int max_tokens, void* state,
                              void* workspace, long* tokens, long* frames, long* out_len, float* score,
                              long* stable_len, int* overflow, void* stream) {
-  if (B <= 0) return 0;
-  if (!stream_ok(desc, beam_size, max_tokens) || beam_size < 1 || Tc < 1 || Tc > kMaxChunk ||
-      cutoff_top_k < 1 || (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam || !state || !workspace)
-    return -1;
-  const S2tRnntLstmDesc& d = *desc;
-  hipStream_t st = (hipStream_t)stream;
-  const int R = B * beam_size;
-  const StreamState s = carve_state(d, B, beam_size, max_tokens, state);
-  const Workspace w = carve(d, B, Tc, beam_size, workspace, 1);
-  hipLaunchKernelGGL(beam_chunk_init_kernel, dim3(1), dim3(64), 0, st, w.counts, R);
-  BeamArgs a{joint_args(d, am, Tc, w), chunk_len, s.lm, 0, B, beam_size, cutoff_top_k, 0, w.cscore, s.score,
-             w.ccls, s.blen, s.nb, w.rec, w.emit, w.token, w.parent, w.counts, nullptr, 0.f, nullptr, nullptr};
-  const StateBuf buf[2] = {{s.h, s.c, s.lm}, {w.h[0], w.c[0], w.lm[0]}};
-  beam_rounds(d, a, buf, w, Tc, st);
-  if (Tc & 1) {                                            // the live copy goes home
-    const long n_state = (long)d.num_layers * R * d.H, n_lm = (long)R * d.V;
-    const long need = ((n_state > n_lm ? n_state : n_lm) + kThreads - 1) / kThreads;
-    const int blocks = (int)(need < 1024 ? need : 1024);
-    hipLaunchKernelGGL(state_copy_kernel, dim3(blocks), dim3(kThreads), 0, st, w.h[0], w.c[0], w.lm[0], s.h, s.c,
-                       s.lm, n_state, n_lm);
-  }
-  BeamEndArgs e{chunk_len, Tc, beam_size, max_tokens, w.rec, s.blen, s.nb, s.score, s.hdr, s.htok, s.hfrm,
-                tokens, frames, out_len, score, stable_len, overflow, nullptr, nullptr};
-  hipLaunchKernelGGL(beam_chunk_end_kernel, dim3(B), dim3(kThreads), 0, st, e);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  const Chunk ch{state, max_tokens, stable_len, overflow};
+  return beam_search(LstmPredictor{desc}, nullptr, &ch, am, chunk_len, B, Tc, beam_size, cutoff_top_k, workspace,
+                     tokens, frames, out_len, score, (hipStream_t)stream);
 }
 
 long s2t_rnnt_lstm_lm_stream_state_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B,
                                          int beam_size, int max_tokens) {
-  if (B <= 0 || !lm_stream_ok(desc_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens)) return 0;
-  return (long)(carve_state(*desc, B, beam_size, max_tokens, nullptr).bytes +
-                carve_lm_state(*lm, B, beam_size, nullptr).bytes);
+  return fused_state_bytes(LstmPredictor{desc}, lm, B, beam_size, max_tokens);
 }
 
 long s2t_rnnt_lstm_lm_stream_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B, int Tc,
                                              int beam_size) {
-  if (B <= 0 || Tc < 1 || Tc > kMaxChunk || !lm_stream_ok(desc_ok(desc), desc ? desc->V : 0, lm, beam_size, 1))
-    return 0;
-  return (long)(carve(*desc, B, Tc, beam_size, nullptr, 1).bytes + carve_lm(*lm, B, beam_size, nullptr, 1).bytes);
+  return chunk_ok(Tc) ? fused_workspace_bytes(LstmPredictor{desc}, lm, B, Tc, beam_size, 1) : 0;
 }
 
 int s2t_rnnt_lstm_lm_stream_reset(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int lm_start_token,
                                   void* state, const int* rows, int B, int beam_size, int max_tokens,
                                   void* workspace, void* stream) {
-  if (B <= 0) return 0;
-  if (!lm_stream_ok(desc_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens) || lm_start_token >= desc->V ||
-      !state || !workspace)
-    return -1;
-  const S2tRnntLstmDesc& d = *desc;
-  hipStream_t st = (hipStream_t)stream;
-  const int R = B * beam_size;
-  const StreamState s = carve_state(d, B, beam_size, max_tokens, state);
-  const LmStreamState ls = carve_lm_state(*lm, B, beam_size, static_cast<char*>(state) + s.bytes);
-  const Workspace w = carve(d, B, 1, beam_size, workspace, 1);
-  const LmWorkspace lw = carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 1);
-  ResetArgs a{rows, beam_size, beam_size, d.num_layers, d.H, s.h, s.c, s.score, s.blen, s.nb, s.hdr, s.n, w.emit,
-              w.token};
-  hipLaunchKernelGGL(stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, a);
-  LmResetArgs la{rows, beam_size, lm->num_layers, lm->H, d.V, 0, lm_start_token, ls.h, ls.c, ls.q, ls.lm_sum,
-                 lw.tok, nullptr};
-  hipLaunchKernelGGL(lm_stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, la);
-  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, st, w.emit, R, w.counts + 2);
-  enqueue_pred_step(d, R, w.token, w.emit, nullptr, w.counts + 2, s.h, s.c, s.lm, s.h, s.c, s.lm, w, st);
-  if (lm_start_token >= 0)                                 // the LM's first step, as the predictor's on blank
-    enqueue_lm_step(*lm, R, lw.tok, w.emit, nullptr, w.counts + 2, ls.h, ls.c, ls.q, ls.h, ls.c, ls.q, lw, st);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  const Fusion f{lm, 0.f, lm_start_token, nullptr};
+  return stream_reset(LstmPredictor{desc}, &f, state, rows, B, beam_size, max_tokens, workspace,
+                      (hipStream_t)stream);
 }
 
 int s2t_rnnt_beam_lstm_lm_chunk(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, const float* am,
@@ -1623,81 +1666,28 @@ int s2t_rnnt_beam_lstm_lm_chunk(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc*
                                 float lm_weight, int max_tokens, void* state, void* workspace, long* tokens,
                                 long* frames, long* out_len, float* score, float* lm_score, long* stable_len,
                                 int* overflow, void* stream) {
-  if (B <= 0) return 0;
-  if (!lm_stream_ok(desc_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens) || Tc < 1 || Tc > kMaxChunk ||
-      cutoff_top_k < 1 || (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam ||
-      !__builtin_isfinite(lm_weight) || !state || !workspace)
-    return -1;
-  const S2tRnntLstmDesc& d = *desc;
-  hipStream_t st = (hipStream_t)stream;
-  const int R = B * beam_size;
-  const StreamState s = carve_state(d, B, beam_size, max_tokens, state);
-  const LmStreamState ls = carve_lm_state(*lm, B, beam_size, static_cast<char*>(state) + s.bytes);
-  const Workspace w = carve(d, B, Tc, beam_size, workspace, 1);
-  const LmWorkspace lw = live_lm(carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 1), ls);
-  hipLaunchKernelGGL(beam_chunk_init_kernel, dim3(1), dim3(64), 0, st, w.counts, R);
-  BeamArgs a{joint_args(d, am, Tc, w), chunk_len, s.lm, 0, B, beam_size, cutoff_top_k, 0, w.cscore, s.score,
-             w.ccls, s.blen, s.nb, w.rec, w.emit, w.token, w.parent, w.counts, lw.q[0], lm_weight, lw.cq,
-             lw.lm_sum};
-  const StateBuf buf[2] = {{s.h, s.c, s.lm}, {w.h[0], w.c[0], w.lm[0]}};
-  beam_rounds(d, a, buf, w, Tc, st, lm, &lw);
-  if (Tc & 1) {                                            // the live copies go home
-    const long n_state = (long)d.num_layers * R * d.H, n_lm = (long)R * d.V;
-    const long n_lstate = (long)lm->num_layers * R * lm->H;
-    const CopyHomeArgs c{{w.h[0], w.c[0], w.lm[0], lw.h[1], lw.c[1], lw.q[1]},
-                         {s.h, s.c, s.lm, lw.h[0], lw.c[0], lw.q[0]},
-                         {n_state, n_state, n_lm, n_lstate, n_lstate, n_lm}};
-    enqueue_copy_home(c, st);
-  }
-  BeamEndArgs e{chunk_len, Tc, beam_size, max_tokens, w.rec, s.blen, s.nb, s.score, s.hdr, s.htok, s.hfrm,
-                tokens, frames, out_len, score, stable_len, overflow, lw.lm_sum, lm_score};
-  hipLaunchKernelGGL(beam_chunk_end_kernel, dim3(B), dim3(kThreads), 0, st, e);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  const Fusion f{lm, lm_weight, -1, lm_score};
+  const Chunk ch{state, max_tokens, stable_len, overflow};
+  return beam_search(LstmPredictor{desc}, &f, &ch, am, chunk_len, B, Tc, beam_size, cutoff_top_k, workspace, tokens,
+                     frames, out_len, score, (hipStream_t)stream);
 }
 
 long s2t_rnnt_stateless_lm_stream_state_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, int B,
                                               int beam_size, int max_tokens) {
-  if (B <= 0 || !lm_stream_ok(stateless_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens)) return 0;
-  return (long)(carve_stateless_state(*desc, B, beam_size, max_tokens, nullptr).bytes +
-                carve_lm_state(*lm, B, beam_size, nullptr).bytes);
+  return fused_state_bytes(StatelessPredictor{desc}, lm, B, beam_size, max_tokens);
 }
 
 long s2t_rnnt_stateless_lm_stream_workspace_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, int B,
                                                   int Tc, int beam_size) {
-  if (B <= 0 || Tc < 1 || Tc > kMaxChunk || !lm_stream_ok(stateless_ok(desc), desc ? desc->V : 0, lm, beam_size, 1))
-    return 0;
-  return (long)(carve_stateless(*desc, B, Tc, beam_size, nullptr, 1).bytes +
-                carve_lm(*lm, B, beam_size, nullptr, 1).bytes);
+  return chunk_ok(Tc) ? fused_workspace_bytes(StatelessPredictor{desc}, lm, B, Tc, beam_size, 1) : 0;
 }
 
 int s2t_rnnt_stateless_lm_stream_reset(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm,
                                        int lm_start_token, void* state, const int* rows, int B, int beam_size,
                                        int max_tokens, void* workspace, void* stream) {
-  if (B <= 0) return 0;
-  if (!lm_stream_ok(stateless_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens) ||
-      lm_start_token >= desc->V || !state || !workspace)
-    return -1;
-  const S2tRnntStatelessDesc& d = *desc;
-  hipStream_t st = (hipStream_t)stream;
-  const int R = B * beam_size;
-  const StatelessStreamState s = carve_stateless_state(d, B, beam_size, max_tokens, state);
-  const LmStreamState ls = carve_lm_state(*lm, B, beam_size, static_cast<char*>(state) + s.bytes);
-  const StatelessWorkspace w = carve_stateless(d, B, 1, beam_size, workspace, 1);
-  const LmWorkspace lw = carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 1);
-  // (no LSTM layers: the predictor's state is the context, which the LM's reset blanks)
-  ResetArgs a{rows, beam_size, beam_size, 0, 0, nullptr, nullptr, s.score, s.blen, s.nb, s.hdr, nullptr, w.emit,
-              w.token};
-  hipLaunchKernelGGL(stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, a);
-  LmResetArgs la{rows, beam_size, lm->num_layers, lm->H, d.V, d.ctx, lm_start_token, ls.h, ls.c, ls.q, ls.lm_sum,
-                 lw.tok, s.ctx};
-  hipLaunchKernelGGL(lm_stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, la);
-  hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, st, w.emit, R, w.counts + 2);
-  enqueue_stateless_step(d, R, w.token, w.emit, nullptr, w.counts + 2, s.ctx, s.lm, s.ctx, s.lm, w, st);
-  if (lm_start_token >= 0)                                 // the LM's first step, as the predictor's on blank
-    enqueue_lm_step(*lm, R, lw.tok, w.emit, nullptr, w.counts + 2, ls.h, ls.c, ls.q, ls.h, ls.c, ls.q, lw, st);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  const Fusion f{lm, 0.f, lm_start_token, nullptr};
+  return stream_reset(StatelessPredictor{desc}, &f, state, rows, B, beam_size, max_tokens, workspace,
+                      (hipStream_t)stream);
 }
 
 int s2t_rnnt_beam_stateless_lm_chunk(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, const float* am,
@@ -1705,43 +1695,11 @@ int s2t_rnnt_beam_stateless_lm_chunk(const S2tRnntStatelessDesc* desc, const S2t
                                      float lm_weight, int max_tokens, void* state, void* workspace,
                                      long* tokens, long* frames, long* out_len, float* score, float* lm_score,
                                      long* stable_len, int* overflow, void* stream) {
-  if (B <= 0) return 0;
-  if (!lm_stream_ok(stateless_ok(desc), desc ? desc->V : 0, lm, beam_size, max_tokens) || Tc < 1 ||
-      Tc > kMaxChunk || cutoff_top_k < 1 || (cutoff_top_k < desc->V ? cutoff_top_k : desc->V) > kMaxBeam ||
-      !__builtin_isfinite(lm_weight) || !state || !workspace)
-    return -1;
-  const S2tRnntStatelessDesc& d = *desc;
-  hipStream_t st = (hipStream_t)stream;
-  const int R = B * beam_size;
-  const StatelessStreamState s = carve_stateless_state(d, B, beam_size, max_tokens, state);
-  const LmStreamState ls = carve_lm_state(*lm, B, beam_size, static_cast<char*>(state) + s.bytes);
-  const StatelessWorkspace w = carve_stateless(d, B, Tc, beam_size, workspace, 1);
-  const LmWorkspace lw = live_lm(carve_lm(*lm, B, beam_size, static_cast<char*>(workspace) + w.bytes, 1), ls);
-  hipLaunchKernelGGL(beam_chunk_init_kernel, dim3(1), dim3(64), 0, st, w.counts, R);
-  BeamArgs a{JointArgs{am, Tc, d.V, d.inner, d.act, d.out1_w, d.out1_b, d.out2_w, d.out2_b, w.z, w.mid, w.logit},
-             chunk_len, s.lm, 0, B, beam_size, cutoff_top_k, 0, w.cscore, s.score, w.ccls, s.blen, s.nb, w.rec,
-             w.emit, w.token, w.parent, w.counts, lw.q[0], lm_weight, lw.cq, lw.lm_sum};
-  int* const ctx[2] = {s.ctx, w.ctx[0]};
-  float* const lm_rows[2] = {s.lm, w.lm[0]};
-  beam_rounds_over(
-      a, lm_rows,
-      [&](int cur, int nxt) {
-        enqueue_stateless_step(d, R, w.token, w.emit, w.parent, w.counts + cur, ctx[cur], lm_rows[cur], ctx[nxt],
-                               lm_rows[nxt], w, st);
-      },
-      Tc, st, lm, &lw);
-  if (Tc & 1) {                                            // the live copies go home
-    const long n_ctx = (long)R * d.ctx, n_lm = (long)R * d.V, n_lstate = (long)lm->num_layers * R * lm->H;
-    const CopyHomeArgs c{{w.ctx[0], w.lm[0], lw.h[1], lw.c[1], lw.q[1], nullptr},
-                         {s.ctx, s.lm, lw.h[0], lw.c[0], lw.q[0], nullptr},
-                         {n_ctx, n_lm, n_lstate, n_lstate, n_lm, 0}};
-    enqueue_copy_home(c, st);
-  }
-  BeamEndArgs e{chunk_len, Tc, beam_size, max_tokens, w.rec, s.blen, s.nb, s.score, s.hdr, s.htok, s.hfrm,
-                tokens, frames, out_len, score, stable_len, overflow, lw.lm_sum, lm_score};
-  hipLaunchKernelGGL(beam_chunk_end_kernel, dim3(B), dim3(kThreads), 0, st, e);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  const Fusion f{lm, lm_weight, -1, lm_score};
+  const Chunk ch{state, max_tokens, stable_len, overflow};
+  return beam_search(StatelessPredictor{desc}, &f, &ch, am, chunk_len, B, Tc, beam_size, cutoff_top_k, workspace,
+                     tokens, frames, out_len, score, (hipStream_t)stream);
 }
 
 }  // extern "C"
+

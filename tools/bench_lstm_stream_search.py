@@ -1,8 +1,9 @@
 """Time the chunk-carried RNN-T search with the LSTM predictor at the dimensions of
 the reference's LSTM YAMLs: E = H = 512, 3 layers, D 256, V 128, out-projection inner 256, relu;
-chunks of Tc = 16 encoder frames; B in {1, 16}.
+chunks of Tc = 16 encoder frames (--tc); B in {1, 16}.
 
-    python tools/bench_lstm_stream_search.py [--reps 40] [--chunks 8] [--blank 0] [--out FILE] [batch ...]
+    python tools/bench_lstm_stream_search.py [--reps 40] [--chunks 8] [--blank 0] [--tc 16] [--lib PATH]
+                                            [--label NAME] [--out FILE] [batch ...]
 
 Per batch size, medians over `reps` chunk calls after a warm-up on random am (streams running on,
 reset once per `chunks` calls outside the timed call):
@@ -10,9 +11,10 @@ reset once per `chunks` calls outside the timed call):
   host poll (blocks of 32 rounds, one read of the live counter each); beam 4 / top-k 4.
 Each figure is a host clock around one call that ends in a device synchronise -- what a caller
 waits for, the enqueue of the rounds included -- and next to it the device time between two events
-around the same call.  Each is set against the whole-utterance call on the same 16 * chunks frames,
+around the same call.  Each is set against the whole-utterance call on the same Tc * chunks frames,
 divided by chunks.  --blank lifts the blank logit behind the out-projection (fewer emissions: fewer
-predictor steps do work).  Prints one JSON line per batch size (and appends it to --out)."""
+predictor steps do work).  `--lib PATH` times another build of the library, `--label` names it in the
+row.  Prints one JSON line per batch size (and appends it to --out)."""
 import argparse
 import json
 import os
@@ -54,17 +56,23 @@ def main():
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--chunks", type=int, default=8)
     ap.add_argument("--blank", type=float, default=0.0)
+    ap.add_argument("--tc", type=int, default=16, help="frames per chunk")
+    ap.add_argument("--lib", default=None, help="another build of libs2t_mi355.so to time")
+    ap.add_argument("--label", default="tree")
     ap.add_argument("--out", default=None)
     ap.add_argument("batch", nargs="*", type=int)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: nothing to time")
+    from speech2text_amd import _native as N
+    if args.lib:
+        N.LIB_PATH = os.path.abspath(args.lib)
     from speech2text_amd.model.decoding import (RnntLstmStreamingSearch, rnnt_beam_lstm_tokens_from_am,
                                                 rnnt_greedy_lstm_tokens_from_am)
     from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
     from speech2text_amd.model.predictor.predictor import Predictor
     dev = torch.device("cuda:0")
-    V, D, E, H, L, inner, Tc, K = 128, 256, 512, 512, 3, 256, 16, args.chunks
+    V, D, E, H, L, inner, Tc, K = 128, 256, 512, 512, 3, 256, args.tc, args.chunks
     torch.manual_seed(0)
     pred = Predictor({"model": "Lstm", "config": {
         "num_symbols": V, "output_dim": D, "symbol_embedding_dim": E, "num_lstm_layers": L,
@@ -77,8 +85,8 @@ def main():
     pred.to(dev).eval()
     join.to(dev).eval()
     for B in args.batch or [1, 16]:
-        row = {"B": B, "V": V, "D": D, "E": E, "H": H, "layers": L, "inner": inner, "Tc": Tc, "chunks": K,
-               "reps": args.reps, "blank": args.blank}
+        row = {"label": args.label, "B": B, "V": V, "D": D, "E": E, "H": H, "layers": L, "inner": inner,
+               "Tc": Tc, "chunks": K, "reps": args.reps, "blank": args.blank}
         g = torch.Generator().manual_seed(B)
         am_all = (torch.randn(B, Tc * K, V, generator=g) * 3.0).to(dev)
         ams = [am_all[:, k * Tc:(k + 1) * Tc].contiguous() for k in range(K)]

@@ -3,12 +3,14 @@ against the un-fused device search (s2t_rnnt_beam_lstm) and against the module l
 (RnntBeamDecoding._module_loop_lm), on the same inputs.
 
     python tools/time_rnnt_lm_fusion.py [--frames 250] [--batch 16] [--runs 10] [--loop-runs 3]
+                                        [--lib PATH] [--label NAME]
 
 Synthetic weights at the dimensions of the reference's LSTM YAMLs (predictor E = H = 512, 3 layers,
 D 256, V 128, out-projection 256) and of rnn_lm.yaml (H 512, 3 layers), beam 4 / top-k 4, the blank
 bias bisected on the device so that the un-fused search emits about `--tokens` tokens per utterance.
 Device events around the warmed calls; the two device searches alternate call by call in one
-process; every figure is the median of its runs with the spread (min .. max) behind.  One JSON line.
+process; every figure is the median of its runs with the spread (min .. max) behind.  `--lib PATH`
+times another build of the library, `--label` names it in the row.  One JSON line.
 """
 import argparse
 import json
@@ -51,7 +53,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tokens", type=int, default=40)
     ap.add_argument("--lm-weight", type=float, default=0.3)
+    ap.add_argument("--lib", default=None, help="another build of libs2t_mi355.so to time")
+    ap.add_argument("--label", default="tree")
     args = ap.parse_args()
+    from speech2text_amd import _native as N
+    if args.lib:
+        N.LIB_PATH = os.path.abspath(args.lib)
     from speech2text_amd.model.decoding import (RnntBeamDecoding, rnnt_beam_lstm_lm_tokens_from_am,
                                                 rnnt_beam_lstm_tokens_from_am)
     from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
@@ -96,7 +103,7 @@ def main():
     loop()
     for _ in range(args.loop_runs):
         t_loop.append(_event_ms(loop)[0])
-    row = {"B": B, "T": T, "beam": 4, "top_k": 4, "lm_weight": args.lm_weight,
+    row = {"label": args.label, "B": B, "T": T, "beam": 4, "top_k": 4, "lm_weight": args.lm_weight,
            "tokens_per_utt_unfused": round(n, 1), "tokens_per_utt_fused": round(n_fused, 1),
            "fused_lm": _stats(t_fused), "unfused": _stats(t_plain), "module_loop_lm": _stats(t_loop)}
     row["fused_over_unfused"] = round(row["fused_lm"]["median_ms"] / row["unfused"]["median_ms"], 2)

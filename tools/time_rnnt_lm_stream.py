@@ -2,18 +2,20 @@
 dimensions of the reference's YAMLs: the LSTM predictor (E = H = 512, 3 layers, D 256, V 128,
 out-projection inner 256, relu) and the stateless predictor (E 512, D 256, ctx 5, V 128, no
 out-projection), each with the LM of rnn_lm.yaml (H 512, 3 layers, V 128); chunks of Tc = 16 encoder
-frames, beam 4 / top-k 4, B in {1, 16}.
+frames (--tc), beam 4 / top-k 4, B in {1, 16}.
 
-    python tools/time_rnnt_lm_stream.py [--reps 40] [--chunks 8] [--out FILE] [batch ...]
+    python tools/time_rnnt_lm_stream.py [--reps 40] [--chunks 8] [--tc 16] [--lib PATH] [--label NAME] [--out FILE]
+                                        [batch ...]
 
 Per family and batch size, medians over `reps` warmed chunk calls on random am (streams running on,
 reset once per `chunks` calls outside the timed call), and beside them
   (a) the same family's chunk call without an LM, where one exists (the LSTM family's
       s2t_rnnt_beam_lstm_chunk; the lockstep rounds over the stateless predictor exist with an LM only);
-  (b) the one-shot fused call on the same 16 * chunks frames, divided by chunks.
+  (b) the one-shot fused call on the same Tc * chunks frames, divided by chunks.
 Each figure is a host clock around one call that ends in a device synchronise -- what a caller waits
 for, the enqueue of the rounds included -- and next to it the device time between two events around the
 same call.  Nothing is asserted: the reading is whether carrying state costs anything over (b).
+`--lib PATH` times another build of the library, `--label` names it in the row.
 Prints one JSON line per family and batch size (and appends it to --out)."""
 import argparse
 import json
@@ -52,24 +54,30 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--chunks", type=int, default=8)
+    ap.add_argument("--tc", type=int, default=16, help="frames per chunk")
+    ap.add_argument("--lib", default=None, help="another build of libs2t_mi355.so to time")
+    ap.add_argument("--label", default="tree")
     ap.add_argument("--out", default=None)
     ap.add_argument("batch", nargs="*", type=int)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: nothing to time")
+    from speech2text_amd import _native as N
+    if args.lib:
+        N.LIB_PATH = os.path.abspath(args.lib)
     from speech2text_amd.model.decoding import (RnntLstmStreamingSearch, rnnt_beam_lstm_lm_tokens_from_am,
                                                 rnnt_beam_stateless_lm_tokens_from_am, rnnt_streaming_search)
     from speech2text_amd.model.lm.rnn_lm import RnnLm, RnnLmConfig
     dev = torch.device("cuda:0")
-    V, D, Tc, K, weight = 128, 256, 16, args.chunks, 0.3
+    V, D, Tc, K, weight = 128, 256, args.tc, args.chunks, 0.3
     pairs = _pairs(dev, V, D)
     torch.manual_seed(1)
     lm = RnnLm(config=RnnLmConfig(num_symbols=V, symbol_embedding_dim=512, num_rnn_layer=3)).to(dev).eval()
     one_shot = {"lstm": rnnt_beam_lstm_lm_tokens_from_am, "stateless": rnnt_beam_stateless_lm_tokens_from_am}
     for family, (pred, join) in pairs.items():
         for B in args.batch or [1, 16]:
-            row = {"family": family, "B": B, "V": V, "D": D, "Tc": Tc, "chunks": K, "beam": 4, "topk": 4,
-                   "lm": "H 512 x 3", "lm_weight": weight, "reps": args.reps}
+            row = {"label": args.label, "family": family, "B": B, "V": V, "D": D, "Tc": Tc, "chunks": K,
+                   "beam": 4, "topk": 4, "lm": "H 512 x 3", "lm_weight": weight, "reps": args.reps}
             g = torch.Generator().manual_seed(B)
             am_all = (torch.randn(B, Tc * K, V, generator=g) * 3.0).to(dev)
             ams = [am_all[:, k * Tc:(k + 1) * Tc].contiguous() for k in range(K)]

@@ -2,13 +2,15 @@
 against the module-by-module loop (what every decode ran before the device search existed, and
 still runs for shapes the kernels refuse), on the same inputs.
 
-    python tools/time_rnnt_lstm_decode.py [--frames 250] [--runs 10] [--warmup 2]
+    python tools/time_rnnt_lstm_decode.py [--frames 250] [--runs 10] [--warmup 2] [--lib PATH]
+                                          [--label NAME]
 
 Synthetic weights at the dimensions of the bench's C4 configuration (bench.c4_config: the LSTM
 predictor and the out-projection joiner), T = 250 frames per utterance, the blank bias calibrated
 on the device so that greedy emits about 40 tokens per utterance; B = 1 and B = 16; greedy with
 max_token_step 1 and beam 4 / top-k 4.  Every figure is the median of `runs` device-synchronised
-runs after `warmup`; one JSON line per (search, B) pair, then a table.
+runs after `warmup`; one JSON line per (search, B) pair, then a table.  `--lib PATH` times another build of
+the library, and `--label` names it in every row.
 """
 import argparse
 import json
@@ -48,7 +50,12 @@ def main():
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tokens", type=int, default=40, help="emitted tokens per utterance to calibrate to")
+    ap.add_argument("--lib", default=None, help="another build of libs2t_mi355.so to time")
+    ap.add_argument("--label", default="tree")
     args = ap.parse_args()
+    from speech2text_amd import _native as N
+    if args.lib:
+        N.LIB_PATH = os.path.abspath(args.lib)
     import bench
     from speech2text_amd.model.decoding import RnntBeamDecoding, RnntGreedyDecoding
     from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
@@ -92,8 +99,8 @@ def main():
             with torch.no_grad():
                 t_new = _median_ms(new, args.runs, args.warmup)
                 t_old = _median_ms(old, args.runs, max(1, args.warmup // 2))
-            row = {"search": name, "B": B, "T": T, "device_ms": round(t_new, 3), "module_loop_ms": round(t_old, 3),
-                   "ratio": round(t_old / t_new, 2), "runs": args.runs}
+            row = {"label": args.label, "search": name, "B": B, "T": T, "device_ms": round(t_new, 3),
+                   "module_loop_ms": round(t_old, 3), "ratio": round(t_old / t_new, 2), "runs": args.runs}
             rows.append(row)
             print(json.dumps(row), flush=True)
     print("\nsearch        B   device ms   module loop ms   module / device")

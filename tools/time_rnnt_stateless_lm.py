@@ -4,12 +4,14 @@ ran for this call before the fused search existed) and against the one-workgroup
 an LM (s2t_rnnt_beam_stateless), on the same inputs.
 
     python tools/time_rnnt_stateless_lm.py [--frames 250] [--batch 16] [--runs 10] [--loop-runs 3]
+                                           [--lib PATH] [--label NAME]
 
 Synthetic weights at the dimensions of zipformer_stateless_pruned_rnnt.yaml (V 128, embedding 512, output
 256, context 5, no out-projection) and of rnn_lm.yaml (H 512, 3 layers), beam 4 / top-k 4, the blank's
 lift bisected on the device so that the search without an LM emits about `--tokens` tokens per utterance.
 Device events around the warmed calls; the two device searches alternate call by call in one process;
-every figure is the median of its runs with the spread (min .. max) behind.  One JSON line.
+every figure is the median of its runs with the spread (min .. max) behind.  `--lib PATH` times another
+build of the library, `--label` names it in the row.  One JSON line.
 """
 import argparse
 import json
@@ -52,7 +54,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tokens", type=int, default=40)
     ap.add_argument("--lm-weight", type=float, default=0.3)
+    ap.add_argument("--lib", default=None, help="another build of libs2t_mi355.so to time")
+    ap.add_argument("--label", default="tree")
     args = ap.parse_args()
+    from speech2text_amd import _native as N
+    if args.lib:
+        N.LIB_PATH = os.path.abspath(args.lib)
     from speech2text_amd.model.decoding import (RnntBeamDecoding, rnnt_beam_stateless_lm_tokens_from_am,
                                                 rnnt_beam_tokens_from_am)
     from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
@@ -97,7 +104,7 @@ def main():
     loop()
     for _ in range(args.loop_runs):
         t_loop.append(_event_ms(loop)[0])
-    row = {"B": B, "T": T, "beam": 4, "top_k": 4, "lm_weight": args.lm_weight,
+    row = {"label": args.label, "B": B, "T": T, "beam": 4, "top_k": 4, "lm_weight": args.lm_weight,
            "tokens_per_utt_no_lm": round(n, 1), "tokens_per_utt_fused": round(n_fused, 1),
            "fused_lm": _stats(t_fused), "one_workgroup_no_lm": _stats(t_plain), "module_loop_lm": _stats(t_loop)}
     row["fused_over_no_lm"] = round(row["fused_lm"]["median_ms"] / row["one_workgroup_no_lm"]["median_ms"], 2)
