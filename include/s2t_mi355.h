@@ -1054,6 +1054,33 @@ int s2t_ctc_prefix_beam_lm_chunk(const S2tRnnLmDesc* lm, const float* logits, co
                                  int lm_start_token, int max_tokens, int max_nodes, void* state,
                                  void* workspace, long* tokens, long* out_len, float* score, float* lm_score,
                                  long* stable_len, int* overflow, void* stream);
+/* The n-gram search (s2t_ctc_prefix_beam_ngram) fed its frames in pieces: the chunk-carried block's
+ * contract above word for word -- EQUALITY, IDLE ROWS, the compaction, both OVERFLOW bits, the refusals --
+ * with s2t_ctc_prefix_beam_ngram as the one-shot partner: for ANY cut, while overflow[b] == 0,
+ * tokens[b][:out_len[b]], out_len, score and lm_score after a chunk are the one-shot entry's on the frames
+ * fed so far, bit for bit.  With lm_weight = 0 tokens, out_len, score, stable_len and overflow are
+ * s2t_ctc_prefix_beam_chunk's bit for bit.  ONE launch per call, a workgroup per utterance: the plain
+ * chunk kernel's shape in the frame body's n-gram mode (admission, the beam and its context ids, the
+ * frames, outputs and compaction); no workspace, no host synchronisation; it can be captured in a graph.
+ * state: s2t_ctc_ngram_stream_state_bytes(B, V, beam_size, max_nodes) bytes: the plain state of
+ * s2t_ctc_stream_state_bytes first, byte for byte in the same order (lm_sum is part of it), followed by
+ *   ctx     [R] int32    the live prefixes' context ids, in beam order
+ * 256-byte aligned like every other array.  A context id belongs to a beam position, not to a trie node:
+ * the compaction leaves it alone.
+ * s2t_ctc_ngram_stream_reset: s2t_ctc_stream_reset, and the one live prefix of a reset row starts in
+ * start_ctx with lm_sum 0; -1 as well for start_ctx < 0 (reset sees no tables: a chunk call clamps every
+ * context id it loads into [0, num_ctx)).
+ * The chunk call refuses (-1, before any launch and without following a device pointer) what
+ * s2t_ctc_prefix_beam_chunk refuses and, of the LM arguments, what s2t_ctc_prefix_beam_ngram refuses (the
+ * descriptor's limits, lm.V != V, lm_weight not finite), and a NULL lm_score. */
+long s2t_ctc_ngram_stream_state_bytes(int B, int V, int beam_size, int max_nodes);
+int s2t_ctc_ngram_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
+                               int start_ctx, void* stream);
+int s2t_ctc_prefix_beam_ngram_chunk(const S2tNgramLmDesc* lm, const float* logits, const long* chunk_len,
+                                    int B, int Tc, int V, int blank, int beam_size, int cutoff_top_k,
+                                    float lm_weight, int max_tokens, int max_nodes, void* state, long* tokens,
+                                    long* out_len, float* score, float* lm_score, long* stable_len,
+                                    int* overflow, void* stream);
 
 /* ---- chunk-carried (streaming) RNN-T search with the LSTM predictor: the two searches above fed
  * their frames in pieces (csrc/decode_lstm.hip).  A round's launches ARE the whole-utterance calls'
@@ -1178,6 +1205,56 @@ int s2t_rnnt_beam_stateless_lm_chunk(const S2tRnntStatelessDesc* desc, const S2t
                                      void* workspace, long* tokens, long* frames, long* out_len,
                                      float* score, float* lm_score, long* stable_len, int* overflow,
                                      void* stream);
+
+/* ---- The back-off n-gram (S2tNgramLmDesc, THE SCORING STATEMENT above) fused into the lockstep RNN-T beam
+ * search of the LSTM predictor, whole and chunk-carried (csrc/decode_lstm.hip): the siblings of the RNN-LM
+ * family (s2t_rnnt_beam_lstm_lm*, s2t_rnnt_lstm_lm_stream_*), with the n-gram's descriptor where those take
+ * the RNN LM's and start_ctx where those take lm_start_token.
+ * STATEMENT.  s2t_rnnt_beam_lstm's statement with the LM term of s2t_rnnt_beam_stateless_ngram: a live row
+ * also carries a context id and lm_sum; the cutoff_top_k classes of a row are chosen on the logits, as there
+ * (the LM does not enter the cut); the candidate of class c != blank of a row in context n takes (q, next) =
+ * score(n, c), scores (row score + lp) + lm_weight * q in fp32, in this order (an fp32 multiply, then an
+ * fp32 add, not contracted), sums lm_sum + q, and a kept row takes next; a blank candidate makes no
+ * look-up and keeps its parent's context and lm_sum.  The empty hypothesis starts in start_ctx, so the
+ * first token is scored too; there is no end-of-sentence term.  lm_score [B] = the best beam's lm_sum; a
+ * zero-length utterance gives no tokens, score 0 and lm_score 0.  With lm_weight = 0 tokens, frames, out_len
+ * and score are s2t_rnnt_beam_lstm's bit for bit.
+ * LAUNCHES.  A round stays expand, select, predictor step: the look-ups of a row's K candidates run on K
+ * threads of the expand launch after its top-k loop, select hands the kept rows their contexts and sums in
+ * place; no LM step is launched, and the two-buffer alternation and the copy home after an odd Tc concern
+ * the predictor's state only.  No host synchronisation; reset and chunk call can be captured in a graph.
+ * workspace: the plain search's (s2t_rnnt_lstm_workspace_bytes / s2t_rnnt_lstm_stream_workspace_bytes),
+ * then the candidates' q and next contexts [B][256] and, for the whole-utterance call, ctx and lm_sum [R].
+ * state (chunk-carried): the state of s2t_rnnt_lstm_stream_state_bytes (same layout), then ctx [R] int32,
+ * the rows' context ids, and lm_sum [R] fp32, R = B * beam_size, each 256-byte aligned.
+ * s2t_rnnt_lstm_ngram_stream_reset: s2t_rnnt_lstm_stream_reset, and every beam of a reset row starts in
+ * start_ctx with lm_sum 0; other rows keep every bit.  Reset follows no table: the chunk call clamps every
+ * context id it loads into [0, num_ctx).
+ * s2t_rnnt_beam_lstm_ngram_chunk: s2t_rnnt_beam_lstm_lm_chunk's contract word for word (idle rows keep
+ * state and outputs, stable_len, the max_tokens saturation and overflow, Tc in 1..256, reset of chosen rows
+ * only): for ANY cut, tokens, frames, out_len, score and lm_score after a chunk are
+ * s2t_rnnt_beam_lstm_ngram's on the frames fed so far, bit for bit.
+ * Refused (-1 / size 0, before any launch and without following a device pointer): what the RNN-LM siblings
+ * refuse, with the n-gram descriptor's limits in place of the RNN LM's: lm NULL or outside its limits,
+ * lm.V != desc.V, start_ctx outside [0, num_ctx) (reset: < 0), lm_weight not finite, lm_score NULL. */
+long s2t_rnnt_beam_lstm_ngram_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, int B,
+                                              int T, int beam_size);
+int s2t_rnnt_beam_lstm_ngram(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, const float* am,
+                             const long* lengths, int B, int T, int beam_size, int cutoff_top_k,
+                             float lm_weight, int start_ctx, void* workspace, long* tokens, long* frames,
+                             long* out_len, float* score, float* lm_score, void* stream);
+long s2t_rnnt_lstm_ngram_stream_state_bytes(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, int B,
+                                            int beam_size, int max_tokens);
+long s2t_rnnt_lstm_ngram_stream_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, int B,
+                                                int Tc, int beam_size);
+int s2t_rnnt_lstm_ngram_stream_reset(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, int start_ctx,
+                                     void* state, const int* rows, int B, int beam_size, int max_tokens,
+                                     void* workspace, void* stream);
+int s2t_rnnt_beam_lstm_ngram_chunk(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, const float* am,
+                                   const long* chunk_len, int B, int Tc, int beam_size, int cutoff_top_k,
+                                   float lm_weight, int max_tokens, void* state, void* workspace,
+                                   long* tokens, long* frames, long* out_len, float* score, float* lm_score,
+                                   long* stable_len, int* overflow, void* stream);
 
 /* ---- batched on-device augmentation + collate next to the fbank kernel
  * (dataset/frontend/data_augmentation.py:13-56 AddNoise, :59-118 MixFeats, :150-196 SpecAugment;

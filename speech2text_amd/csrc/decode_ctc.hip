@@ -20,6 +20,10 @@
 //                            the two above fed their frames in pieces: beam and trie in a caller-owned
 //                            state, the same frame body and round kernel, and at the end of every call
 //                            a compaction of the trie to what the live prefixes can still reach.
+//   s2t_ctc_prefix_beam_ngram_chunk
+//                            the n-gram form fed its frames in pieces: the plain chunk kernel's shape in
+//                            the frame body's n-gram mode, still ONE launch; the state gains the live
+//                            prefixes' context ids behind the plain layout.
 #include <hip/hip_runtime.h>
 
 #include "../../include/s2t_mi355.h"
@@ -31,8 +35,14 @@ namespace {
 using namespace s2t_dec;
 
 static_assert(S2T_RNNT_LSTM_MAX_BEAM == kMaxBeam, "the header's limit is the kernels'");
-static_assert(sizeof(float) * S2T_RNNT_LSTM_MAX_VOCAB + sizeof(CtcShared) <= 60 * 1024,
-              "a frame's logits are staged in LDS whole");
+struct CtcCompact {
+  int anc, depth;                  // the live nodes' lowest common ancestor and its absolute depth
+  int part[kCtcWaves];
+};
+
+static_assert(sizeof(float) * S2T_RNNT_LSTM_MAX_VOCAB + sizeof(CtcShared) + sizeof(CtcNgramShared) +
+                      sizeof(CtcCompact) <= 60 * 1024,
+              "a frame's logits are staged in LDS whole, beside the beam, the n-gram part and the compaction's");
 
 struct CtcArgs {
   const float* logits;    // [B][T][V]
@@ -252,10 +262,12 @@ struct CtcStream {
   int *depth, *ovf;                // [B] the committed depth; the overflow bits
   long* eff;                       // [B] frames the current call consumes (the LM family's rounds read it)
   float *h, *c, *q;                // the LM's live copy (LM family)
+  int* ctx;                        // [R] the live prefixes' context ids (n-gram family)
   size_t bytes;
 };
 
-CtcStream carve_ctc_stream(const S2tRnnLmDesc* lm, int B, int V, int beam, int max_nodes, void* base) {
+CtcStream carve_ctc_stream(const S2tRnnLmDesc* lm, int B, int V, int beam, int max_nodes, void* base,
+                           bool ngram = false) {
   const size_t R = (size_t)B * beam, M = (size_t)B * max_nodes;
   char* p = static_cast<char*>(base);
   size_t off = 0;
@@ -282,6 +294,7 @@ CtcStream carve_ctc_stream(const S2tRnnLmDesc* lm, int B, int V, int beam, int m
     s.c = f((size_t)lm->num_layers * R * lm->H);
     s.q = f(R * V);
   }
+  if (ngram) s.ctx = i(R);                                 // (behind the plain layout, which it leaves as it is)
   s.bytes = off;
   return s;
 }
@@ -323,11 +336,6 @@ struct CtcStreamArgs {
   int* overflow;
 };
 
-struct CtcCompact {
-  int anc, depth;                  // the live nodes' lowest common ancestor and its absolute depth
-  int part[kCtcWaves];
-};
-
 // frames row b consumes in this call: 0 for an idle row, an inert one, and one whose nodes do not fit
 // (which then becomes inert: bit 1)
 __device__ __forceinline__ int ctc_stream_admit(const CtcStreamArgs& a, int b) {
@@ -346,7 +354,8 @@ __device__ __forceinline__ int ctc_stream_admit(const CtcStreamArgs& a, int b) {
 
 // After the last frame of a call, beam in s: the outputs, then the compaction.  All kCtcThreads
 // threads call it.  Every walk is bounded by the node count: a corrupt state ends in a wrong answer.
-__device__ __forceinline__ void ctc_stream_close(CtcShared& s, CtcCompact& k, const CtcStreamArgs& a, int b) {
+__device__ __forceinline__ void ctc_stream_close(CtcShared& s, CtcCompact& k, const CtcStreamArgs& a, int b,
+                                                 const CtcNgramShared* ng = nullptr, int* ctx = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int M = a.c.max_nodes, nb = s.nb, nn = s.nnodes, BS = a.c.beam;
   CtcNode* nodes = a.c.nodes + (long)b * M;
@@ -437,6 +446,7 @@ __device__ __forceinline__ void ctc_stream_close(CtcShared& s, CtcCompact& k, co
     a.st.node[r] = nid < 0 ? 0 : nid;
     a.st.last[r] = s.last[tid];
     a.st.len[r] = s.len[tid];
+    if (ng) ctx[r] = ng->state[tid];                       // (a context id belongs to a beam position, not to a node)
   }
   if (tid == 0) {
     const int ovf = a.ovf[b] | (s.len[0] > a.max_tokens ? 1 : 0);
@@ -450,10 +460,12 @@ __device__ __forceinline__ void ctc_stream_close(CtcShared& s, CtcCompact& k, co
 }
 
 // grid B: rows[b] != 0 (NULL: every row) becomes the empty prefix; with an LM its state is zeroed and
-// the first LM step is asked for on row 0 of exactly those utterances
+// the first LM step is asked for on row 0 of exactly those utterances; with an n-gram (ctx) the one live
+// prefix starts in start_ctx
 __global__ __launch_bounds__(kCtcThreads) void ctc_stream_reset_kernel(CtcStreamArgs a, const int* rows,
                                                                        int lm_start_token, int layers, int H,
-                                                                       float* h, float* c, float* q) {
+                                                                       float* h, float* c, float* q, int* ctx,
+                                                                       int start_ctx) {
   const int b = blockIdx.x, tid = threadIdx.x, BS = a.c.beam, r = b * BS + tid;
   const long R = (long)gridDim.x * BS;
   const bool on = !rows || rows[b] != 0;
@@ -470,6 +482,7 @@ __global__ __launch_bounds__(kCtcThreads) void ctc_stream_reset_kernel(CtcStream
     a.st.node[r] = 0;
     a.st.last[r] = -1;
     a.st.len[r] = 0;
+    if (ctx) ctx[r] = start_ctx;
   }
   if (tid == 0) {
     a.st.nb[b] = 1;
@@ -505,6 +518,36 @@ __global__ __launch_bounds__(kCtcThreads) void ctc_prefix_chunk_kernel(CtcStream
     ctc_frame<kCtcPlain>(s, row, x + (long)t * a.c.V, a.c.V, K, a.c.beam, a.c.blank, nodes, a.c.max_nodes, 0.f,
                          nullptr, nullptr, nullptr, nullptr, 0);
   ctc_stream_close(s, k, a, b);
+}
+
+// the n-gram family: the same launch in the frame body's n-gram mode; the context ids are loaded with the
+// beam (clamped: the reset that wrote them saw no tables) and go home with it
+struct CtcNgramStreamArgs {
+  CtcStreamArgs s;
+  NgramTables g;
+  float lm_weight;
+  int* ctx;                        // [B][beam]
+};
+
+__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_ngram_chunk_kernel(CtcNgramStreamArgs a) {
+  extern __shared__ float row[];
+  __shared__ CtcShared s;
+  __shared__ CtcNgramShared ng;
+  __shared__ CtcCompact k;
+  const int b = blockIdx.x, tid = threadIdx.x, BS = a.s.c.beam;
+  const int n = ctc_stream_admit(a.s, b);
+  if (n == 0) return;
+  CtcNode* nodes = a.s.c.nodes + (long)b * a.s.c.max_nodes;
+  const float* x = a.s.c.logits + (long)b * a.s.c.T * a.s.c.V;
+  load_beam(s, a.s.st, b, BS);
+  if (tid < BS) ng.state[tid] = ngram_clamp(a.ctx[b * BS + tid], a.g.num_ctx);
+  if (tid == 0) ng.g = a.g;
+  __syncthreads();
+  const int K = min(a.s.c.topk, a.s.c.V);
+  for (int t = 0; t < n; ++t)
+    ctc_frame<kCtcNgram>(s, row, x + (long)t * a.s.c.V, a.s.c.V, K, BS, a.s.c.blank, nodes, a.s.c.max_nodes,
+                         a.lm_weight, nullptr, nullptr, nullptr, nullptr, 0, &ng);
+  ctc_stream_close(s, k, a.s, b, &ng, a.ctx);
 }
 
 // the LM family: what the rounds read as lengths, before them ...
@@ -654,7 +697,7 @@ int s2t_ctc_stream_reset(void* state, const int* rows, int B, int V, int beam_si
   const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
                                       nullptr, nullptr, nullptr, nullptr);
   hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows, -1, 0, 0,
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr);
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (int*)nullptr, 0);
   S2T_CHECK_LAUNCH();
   return 0;
 }
@@ -671,6 +714,43 @@ int s2t_ctc_prefix_beam_chunk(const float* logits, const long* chunk_len, int B,
   const CtcStreamArgs a = stream_args(s, logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_tokens,
                                       max_nodes, tokens, out_len, score, nullptr, stable_len, overflow);
   hipLaunchKernelGGL(ctc_prefix_chunk_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, (hipStream_t)stream, a);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+long s2t_ctc_ngram_stream_state_bytes(int B, int V, int beam_size, int max_nodes) {
+  if (B <= 0 || !ctc_stream_ok(V, beam_size, max_nodes)) return 0;
+  return (long)carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, nullptr, true).bytes;
+}
+
+int s2t_ctc_ngram_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
+                               int start_ctx, void* stream) {
+  if (B <= 0) return 0;
+  if (!ctc_stream_ok(V, beam_size, max_nodes) || start_ctx < 0 || !state) return -1;
+  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, true);
+  const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
+                                      nullptr, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows, -1, 0, 0,
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, s.ctx, start_ctx);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_ctc_prefix_beam_ngram_chunk(const S2tNgramLmDesc* lm, const float* logits, const long* chunk_len, int B,
+                                    int Tc, int V, int blank, int beam_size, int cutoff_top_k, float lm_weight,
+                                    int max_tokens, int max_nodes, void* state, long* tokens, long* out_len,
+                                    float* score, float* lm_score, long* stable_len, int* overflow, void* stream) {
+  if (B <= 0) return 0;
+  if (Tc < 1 || Tc > 256 || !ctc_ok(Tc, V, blank, beam_size, cutoff_top_k) || max_tokens < 1 ||
+      !ctc_stream_ok(V, beam_size, max_nodes) || !ngram_desc_ok(lm) || lm->V != V ||
+      !__builtin_isfinite(lm_weight) || !lm_score || !state)
+    return -1;
+  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, true);
+  const CtcNgramStreamArgs a{stream_args(s, logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_tokens,
+                                         max_nodes, tokens, out_len, score, lm_score, stable_len, overflow),
+                             ngram_tables(*lm), lm_weight, s.ctx};
+  hipLaunchKernelGGL(ctc_prefix_ngram_chunk_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V,
+                     (hipStream_t)stream, a);
   S2T_CHECK_LAUNCH();
   return 0;
 }
@@ -695,7 +775,7 @@ int s2t_ctc_lm_stream_reset(const S2tRnnLmDesc* lm, int lm_start_token, void* st
   const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
                                       nullptr, nullptr, nullptr, nullptr);
   hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows,
-                     lm_start_token, lm->num_layers, lm->H, s.h, s.c, s.q);
+                     lm_start_token, lm->num_layers, lm->H, s.h, s.c, s.q, (int*)nullptr, 0);
   if (lm_start_token >= 0) {                               // the one-shot entry's own first step, masked by rows
     const int rc = s2t_rnn_lm_step(lm, B * beam_size, s.st.token, s.st.emit, nullptr, s.h, s.c, s.q, s.h, s.c, s.q,
                                    w.step, stream);

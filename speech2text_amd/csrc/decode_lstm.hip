@@ -41,6 +41,12 @@
 // s2t_rnnt_beam_stateless_lm_chunk): the same rounds through the same host functions, the LM's (h, c), q
 // and lm_sum carried in the caller's state buffer behind the predictor's.
 //
+// Back-off n-gram shallow fusion (s2t_rnnt_beam_lstm_ngram, s2t_rnnt_beam_lstm_ngram_chunk): the LM's state
+// is one context id per row, so nothing rides the rounds: beam_expand_kernel and beam_select_kernel have a
+// compile-time n-gram mode in which the K candidates of a row take their look-ups (csrc/ngram_lookup.h) on K
+// threads after the top-k loop and a kept row takes the context its look-up returned.  A round stays
+// expand, select, predictor step; context ids and lm_sum are per-row arrays updated in place by select.
+//
 // On the host every beam entry point is ONE function, beam_search: a predictor (LstmPredictor or
 // StatelessPredictor, which say how their workspace and state are carved, blanked, stepped and copied
 // home), with an LM or not, the whole utterance or a chunk.  It checks the shapes, fills BeamArgs by name
@@ -50,9 +56,12 @@
 // A row's arithmetic does not depend on the rows that share its launch: tiles sit at fixed row
 // positions, every (row, output) sum is taken per lane over k = lane, lane + 64, ... and folded by the
 // same butterfly, and rows beyond R read clamped addresses and are never stored.
+#include <type_traits>
+
 #include "common.h"
 #include "decode_common.h"
 #include "decode_records.h"
+#include "ngram_lookup.h"
 #include "../../include/s2t_mi355.h"
 
 namespace {
@@ -684,9 +693,28 @@ __global__ void beam_init_kernel(int B, int beam, float* score, int* blen, int* 
 // grid B * beam: the cutoff_top_k best classes of a live beam by (logit descending, class ascending)
 // -- log-softmax is monotone, the order is taken on the logits -- as candidates (beam score +
 // log-probability, class)
-__global__ __launch_bounds__(kThreads) void beam_expand_kernel(BeamArgs a) {
+// n-gram mode: the tables, the rows' context ids [R] (updated in place by select) and the context a
+// candidate is in when it is kept [B][kMaxCand]; the weight, the candidates' q and the rows' sums are
+// BeamArgs' lm_weight, cq and lm_sum (q stays NULL: there are no LM rows)
+struct BeamNgram {
+  NgramTables g;
+  int *ctx, *cnext;
+};
+
+// The two beam kernels are instantiated on their argument struct: BeamArgs (no LM, or the RNN-LM's q
+// rows), or BeamNgramArgs, the compile-time n-gram mode.  The plain instantiations keep their kernel
+// arguments and their code.
+struct BeamNgramArgs : BeamArgs {
+  BeamNgram ng;
+};
+
+template <class Args>
+__global__ __launch_bounds__(kThreads) void beam_expand_kernel(Args a) {
+  constexpr bool NG = std::is_same_v<Args, BeamNgramArgs>;
   __shared__ Top s_top[kWaves];
   __shared__ float scratch[kWaves];
+  __shared__ float s_sc[NG ? kMaxBeam : 1];                // n-gram mode: the row's candidates before the LM term
+  __shared__ int s_cls[NG ? kMaxBeam : 1];
   const int row = blockIdx.x, b = row / a.beam, i = row - b * a.beam, tid = threadIdx.x;
   if (a.t >= clamped_len(a.lengths, b, a.j.T) || i >= a.nb[b]) return;
   const int V = a.j.V, K = min(a.topk, V);
@@ -716,18 +744,42 @@ __global__ __launch_bounds__(kThreads) void beam_expand_kernel(BeamArgs a) {
         sc = __fadd_rn(sc, __fmul_rn(a.lm_weight, qv));
         a.cq[b * kMaxCand + i * K + r] = qv;
       }
-      a.cscore[b * kMaxCand + i * K + r] = ok ? sc : S2T_NEG_INF;
-      a.ccls[b * kMaxCand + i * K + r] = ok ? pi : 0;
+      if constexpr (NG) {                                  // the LM term follows the loop, a thread per candidate
+        s_sc[r] = sc;
+        s_cls[r] = ok ? pi : -1;
+      } else {
+        a.cscore[b * kMaxCand + i * K + r] = ok ? sc : S2T_NEG_INF;
+        a.ccls[b * kMaxCand + i * K + r] = ok ? pi : 0;
+      }
+    }
+  }
+  if constexpr (NG) {
+    __syncthreads();
+    if (tid < K) {                                         // blank: no look-up, the parent's context
+      const int at = b * kMaxCand + i * K + tid;
+      const bool ok = s_cls[tid] >= 0;                     // (only a NaN input leaves a round empty)
+      const int cls = ok ? s_cls[tid] : 0;
+      const int ctx = ngram_clamp(a.ng.ctx[row], a.ng.g.num_ctx);
+      NgramHit h{0.f, ctx};
+      if (cls != 0) h = ngram_score(a.ng.g, ctx, cls);
+      a.cscore[at] = ok ? __fadd_rn(s_sc[tid], __fmul_rn(a.lm_weight, h.logp)) : S2T_NEG_INF;
+      a.ccls[at] = cls;
+      a.cq[at] = h.logp;
+      a.ng.cnext[at] = h.next;
     }
   }
 }
 
+
 // grid B: rank the candidates of an utterance (score descending, then parent position, then rank
 // in the parent's top-k: the candidate index), keep the beam_size best as the new beams, one
 // (parent, class) record each; the rows' parent / emit / token for the predictor step.
-__global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
+template <class Args>
+__global__ __launch_bounds__(kThreads) void beam_select_kernel(Args a) {
+  constexpr bool NG = std::is_same_v<Args, BeamNgramArgs>;
   __shared__ float s_cscore[kMaxCand], s_lmsum[kMaxBeam];
   __shared__ int s_ccls[kMaxCand], s_pick[kMaxBeam], s_len[kMaxBeam];
+  __shared__ int s_ctx[NG ? kMaxBeam : 1];                 // n-gram mode: the parents' context ids
   const int b = blockIdx.x, tid = threadIdx.x, BS = a.beam, row0 = b * BS;
   if (b == 0 && tid == 0) a.counts[a.parity ^ 1] = 0;
   if (a.t >= clamped_len(a.lengths, b, a.j.T)) {           // finished: the rows keep what they have
@@ -744,7 +796,8 @@ __global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
   }
   if (tid < nb) {                                          // the rows of an utterance read each other's
     s_len[tid] = a.blen[row0 + tid];
-    if (a.q) s_lmsum[tid] = a.lm_sum[row0 + tid];
+    if (NG || a.q) s_lmsum[tid] = a.lm_sum[row0 + tid];
+    if constexpr (NG) s_ctx[tid] = a.ng.ctx[row0 + tid];
   }
   __syncthreads();
   rank_candidates(s_cscore, nc, nnb, s_pick);
@@ -755,7 +808,8 @@ __global__ __launch_bounds__(kThreads) void beam_select_kernel(BeamArgs a) {
       const int q = s_pick[tid], parent = q / K, cls = s_ccls[q];
       a.score[row] = s_cscore[q];
       a.blen[row] = s_len[parent] + (cls != 0 ? 1 : 0);
-      if (a.q) a.lm_sum[row] = cls != 0 ? s_lmsum[parent] + a.cq[b * kMaxCand + q] : s_lmsum[parent];
+      if (NG || a.q) a.lm_sum[row] = cls != 0 ? s_lmsum[parent] + a.cq[b * kMaxCand + q] : s_lmsum[parent];
+      if constexpr (NG) a.ng.ctx[row] = cls != 0 ? a.ng.cnext[b * kMaxCand + q] : s_ctx[parent];
       a.rec[((long)b * a.j.T + a.t) * BS + tid] = pack_record(parent, cls);
       a.parent[row] = row0 + parent;
       a.emit[row] = cls != 0;
@@ -1272,12 +1326,58 @@ struct StatelessPredictor {
 };
 
 // ------------------------------------------------------------------ the beam search, whole or a chunk of it
-struct Fusion {                    // shallow fusion with an RNN-LM
+struct Fusion {                    // shallow fusion: with an RNN-LM (lm), or with a back-off n-gram (ngram)
   const S2tRnnLmDesc* lm;
   float weight;
   int start_token;                 // the LM's first input, < 0: none (a chunk call: the reset has taken it)
   float* lm_score;                 // [B]
+  const S2tNgramLmDesc* ngram = nullptr;
+  int start_ctx = 0;               // n-gram: the empty hypothesis' context (a chunk call: the reset has set it)
 };
+
+// What the n-gram adds to a search's buffers: in the workspace the candidates' q and next contexts, and for
+// a whole-utterance search the rows' context ids and sums; a chunk call keeps those two in the caller's
+// state, behind the predictor's.
+struct NgramWork {
+  float *cq, *lm_sum;              // [B][kMaxCand], [R]
+  int *cnext, *ctx;                // [B][kMaxCand], [R]
+};
+
+NgramWork carve_ngram(int B, int beam, Arena& m, bool rows) {
+  NgramWork w{};
+  w.cq = m.take<float>((size_t)B * kMaxCand);
+  w.cnext = m.take<int>((size_t)B * kMaxCand);
+  if (rows) {
+    w.ctx = m.take<int>((size_t)B * beam);
+    w.lm_sum = m.take<float>((size_t)B * beam);
+  }
+  return w;
+}
+
+struct NgramStreamState {
+  int* ctx;                        // [R]
+  float* lm_sum;                   // [R]
+};
+
+// (the order is the header's documented layout)
+NgramStreamState carve_ngram_state(int B, int beam, Arena& m) {
+  NgramStreamState s{};
+  s.ctx = m.take<int>((size_t)B * beam);
+  s.lm_sum = m.take<float>((size_t)B * beam);
+  return s;
+}
+
+// grid B, after stream_reset_kernel: the one live beam of a row the mask names starts in start_ctx with
+// lm_sum 0; the other rows keep every bit
+__global__ __launch_bounds__(64) void ngram_stream_reset_kernel(const int* rows, int BS, int start_ctx, int* ctx,
+                                                                float* lm_sum) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (rows && rows[b] == 0) return;
+  if (tid < BS) {
+    ctx[b * BS + tid] = start_ctx;
+    lm_sum[b * BS + tid] = 0.f;
+  }
+}
 
 struct Chunk {                     // a chunk call: the caller's state, and what it answers beside the search's outputs
   void* state;
@@ -1289,13 +1389,17 @@ struct Chunk {                     // a chunk call: the caller's state, and what
 bool beam_ok(int beam, int least) { return beam >= least && beam <= kMaxBeam; }
 bool chunk_ok(int Tc) { return Tc >= 1 && Tc <= kMaxChunk; }
 bool fusion_ok(const S2tRnnLmDesc* lm, int V) { return lm_ok(lm) && lm->V == V; }
+bool fusion_ok(const Fusion& f, int V) {
+  return f.ngram ? !f.lm && ngram_desc_ok(f.ngram) && f.ngram->V == V : fusion_ok(f.lm, V);
+}
 
 // The T rounds of a beam search: frame t reads buf[t & 1] and leaves the survivors in buf[~t & 1], by the
 // predictor's step on a.token / a.emit / a.parent / a.counts + cur.  With an LM (shallow fusion) its step
-// follows the predictor's on the same four, from its buffer cur to nxt.
+// follows the predictor's on the same four, from its buffer cur to nxt; with an n-gram (ng) the two
+// kernels run in their n-gram mode and nothing follows.
 template <class P>
 void beam_rounds(const P& p, BeamArgs a, const typename P::Buf (&buf)[2], const typename P::Work& w,
-                 const S2tRnnLmDesc* lm, const LmWorkspace& lw, int T, hipStream_t st) {
+                 const S2tRnnLmDesc* lm, const LmWorkspace& lw, const BeamNgram* ng, int T, hipStream_t st) {
   const int R = a.B * a.beam;
   for (int t = 0; t < T; ++t) {
     const int cur = t & 1, nxt = cur ^ 1;
@@ -1303,8 +1407,14 @@ void beam_rounds(const P& p, BeamArgs a, const typename P::Buf (&buf)[2], const 
     a.parity = cur;
     a.lm = buf[cur].lm;
     if (lm) a.q = lw.q[cur];
-    hipLaunchKernelGGL(beam_expand_kernel, dim3(R), dim3(kThreads), 0, st, a);
-    hipLaunchKernelGGL(beam_select_kernel, dim3(a.B), dim3(kThreads), 0, st, a);
+    if (ng) {                                              // (no LM step: a kept row took its context in select)
+      const BeamNgramArgs na{a, *ng};
+      hipLaunchKernelGGL(beam_expand_kernel<BeamNgramArgs>, dim3(R), dim3(kThreads), 0, st, na);
+      hipLaunchKernelGGL(beam_select_kernel<BeamNgramArgs>, dim3(a.B), dim3(kThreads), 0, st, na);
+    } else {
+      hipLaunchKernelGGL(beam_expand_kernel<BeamArgs>, dim3(R), dim3(kThreads), 0, st, a);
+      hipLaunchKernelGGL(beam_select_kernel<BeamArgs>, dim3(a.B), dim3(kThreads), 0, st, a);
+    }
     p.step(R, w, a.parent, a.counts + cur, buf[cur], buf[nxt], st);
     if (lm)
       enqueue_lm_step(*lm, R, a.token, a.emit, a.parent, a.counts + cur, lw.h[cur], lw.c[cur], lw.q[cur],
@@ -1320,18 +1430,22 @@ int beam_search(const P& p, const Fusion* f, const Chunk* ch, const float* am, c
                 int beam, int topk, void* workspace, long* tokens, long* frames, long* out_len, float* score,
                 hipStream_t st) {
   if (B <= 0) return 0;
-  if (!p.ok() || (f && !fusion_ok(f->lm, p.V())) || !beam_ok(beam, 1) || topk < 1 ||
+  if (!p.ok() || (f && !fusion_ok(*f, p.V())) || !beam_ok(beam, 1) || topk < 1 ||
       (topk < p.V() ? topk : p.V()) > kMaxBeam || (f && f->start_token >= p.V()) ||
       (f && !__builtin_isfinite(f->weight)) || (ch ? !chunk_ok(T) || ch->max_tokens < 1 || !ch->state : T <= 0) ||
       !workspace)
     return -1;
+  const S2tNgramLmDesc* ngram = f ? f->ngram : nullptr;
+  if (ngram && (!f->lm_score || (!ch && (f->start_ctx < 0 || f->start_ctx >= ngram->num_ctx)))) return -1;
   const S2tRnnLmDesc* lm = f ? f->lm : nullptr;
   const int R = B * beam, n_state = ch ? 1 : 2;
   Arena wm(workspace);
   const typename P::Work w = p.work(B, T, beam, wm, n_state);
   const SearchArrays& s = w.s;
   LmWorkspace lw{};
-  if (f) lw = carve_lm(*lm, B, beam, wm, n_state);
+  if (lm) lw = carve_lm(*lm, B, beam, wm, n_state);
+  NgramWork nw{};
+  if (ngram) nw = carve_ngram(B, beam, wm, !ch);
   typename P::State carried{};     // a chunk: the caller's state; buf[0] is its live copy
   typename P::Buf buf[2] = {w.buf[0], w.buf[1]};
   if (ch) {
@@ -1339,11 +1453,16 @@ int beam_search(const P& p, const Fusion* f, const Chunk* ch, const float* am, c
     carried = p.state(B, beam, ch->max_tokens, sm);
     buf[1] = buf[0];
     buf[0] = carried.live;
-    if (f) lw = live_lm(lw, carve_lm_state(*lm, B, beam, sm));
+    if (lm) lw = live_lm(lw, carve_lm_state(*lm, B, beam, sm));
+    if (ngram) {
+      const NgramStreamState ns = carve_ngram_state(B, beam, sm);
+      nw.ctx = ns.ctx;
+      nw.lm_sum = ns.lm_sum;
+    }
     hipLaunchKernelGGL(beam_chunk_init_kernel, dim3(1), dim3(64), 0, st, s.counts, R);
   } else {
     hipError_t e = p.blank(buf[0], R, st);
-    if (f) {
+    if (lm) {
       const size_t lm_state = sizeof(float) * (size_t)lm->num_layers * R * lm->H;
       if (e == hipSuccess) e = hipMemsetAsync(lw.h[0], 0, lm_state, st);
       if (e == hipSuccess) e = hipMemsetAsync(lw.c[0], 0, lm_state, st);
@@ -1352,11 +1471,14 @@ int beam_search(const P& p, const Fusion* f, const Chunk* ch, const float* am, c
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(beam_init_kernel, dim3(1), dim3(kThreads), 0, st, B, beam, s.score, s.blen, s.nb, s.emit,
                        s.token, s.counts);
-    if (f)
+    if (lm)
       hipLaunchKernelGGL(lm_start_kernel, dim3((R + kThreads - 1) / kThreads), dim3(kThreads), 0, st, R,
                          f->start_token, lw.tok, lw.lm_sum);
+    if (ngram)                                             // every row in start_ctx, lm_sum 0
+      hipLaunchKernelGGL(lm_start_kernel, dim3((R + kThreads - 1) / kThreads), dim3(kThreads), 0, st, R,
+                         f->start_ctx, nw.ctx, nw.lm_sum);
     p.step(R, w, nullptr, s.counts + 2, buf[0], buf[0], st);   // the first step: blank, from the blanked state
-    if (f && f->start_token >= 0)                          // the LM's first step, as the predictor's on blank
+    if (lm && f->start_token >= 0)                          // the LM's first step, as the predictor's on blank
       enqueue_lm_step(*lm, R, lw.tok, s.emit, nullptr, s.counts + 2, lw.h[0], lw.c[0], lw.q[0], lw.h[0], lw.c[0],
                       lw.q[0], lw, st);
   }
@@ -1376,19 +1498,21 @@ int beam_search(const P& p, const Fusion* f, const Chunk* ch, const float* am, c
   a.token = s.token;
   a.parent = s.parent;
   a.counts = s.counts;
-  if (f) {                         // else q stays NULL: no fusion
+  if (f) {                         // else q stays NULL: no fusion (an n-gram: q stays NULL too, no LM rows)
     a.lm_weight = f->weight;
-    a.cq = lw.cq;
-    a.lm_sum = lw.lm_sum;
+    a.cq = ngram ? nw.cq : lw.cq;
+    a.lm_sum = ngram ? nw.lm_sum : lw.lm_sum;
   }
-  beam_rounds(p, a, buf, w, lm, lw, T, st);
-  const float* lm_sum = f ? lw.lm_sum : nullptr;
+  BeamNgram bn{};
+  if (ngram) bn = BeamNgram{ngram_tables(*ngram), nw.ctx, nw.cnext};
+  beam_rounds(p, a, buf, w, lm, lw, ngram ? &bn : nullptr, T, st);
+  const float* lm_sum = f ? a.lm_sum : nullptr;
   float* lm_score = f ? f->lm_score : nullptr;
   if (ch) {
     if (T & 1) {                                           // the live copies go home
       HomeList l;
       p.home(l, R, buf[1], buf[0]);
-      if (f) {
+      if (lm) {
         const long n_lstate = (long)lm->num_layers * R * lm->H;
         l.add(lw.h[1], lw.h[0], n_lstate);
         l.add(lw.c[1], lw.c[0], n_lstate);
@@ -1413,30 +1537,35 @@ template <class P>
 int stream_reset(const P& p, const Fusion* f, void* state, const int* rows, int B, int beam, int max_tokens,
                  void* workspace, hipStream_t st) {
   if (B <= 0) return 0;
-  if (!p.ok() || (f && !fusion_ok(f->lm, p.V())) || !beam_ok(beam, f ? 1 : 0) || max_tokens < 1 ||
-      (f && f->start_token >= p.V()) || !state || !workspace)
+  if (!p.ok() || (f && !fusion_ok(*f, p.V())) || !beam_ok(beam, f ? 1 : 0) || max_tokens < 1 ||
+      (f && f->start_token >= p.V()) || (f && f->ngram && f->start_ctx < 0) || !state || !workspace)
     return -1;
+  const S2tRnnLmDesc* lm = f ? f->lm : nullptr;
   const int BS = beam > 0 ? beam : 1, R = B * BS;
   Arena sm(state), wm(workspace);
   const typename P::State s = p.state(B, beam, max_tokens, sm);
   const typename P::Work w = p.work(B, 1, beam, wm, beam > 0 ? 1 : 0);
   LmStreamState ls{};
   LmWorkspace lw{};
-  if (f) {
-    ls = carve_lm_state(*f->lm, B, beam, sm);
-    lw = carve_lm(*f->lm, B, beam, wm, 1);
+  if (lm) {
+    ls = carve_lm_state(*lm, B, beam, sm);
+    lw = carve_lm(*lm, B, beam, wm, 1);
   }
+  NgramStreamState ns{};
+  if (f && f->ngram) ns = carve_ngram_state(B, beam, sm);
   // as for a predictor without LSTM layers or context; the predictor fills in its own
   ResetArgs a{rows, beam, BS, 0, 0, nullptr, nullptr, s.score, s.blen, s.nb, s.hdr, nullptr, w.s.emit, w.s.token};
-  LmResetArgs la{rows, BS, f ? f->lm->num_layers : 0, f ? f->lm->H : 0, p.V(), 0, f ? f->start_token : -1,
+  LmResetArgs la{rows, BS, lm ? lm->num_layers : 0, lm ? lm->H : 0, p.V(), 0, lm ? f->start_token : -1,
                  ls.h, ls.c, ls.q, ls.lm_sum, lw.tok, nullptr};
   p.reset_args(s, a, la);
   hipLaunchKernelGGL(stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, a);
-  if (f) hipLaunchKernelGGL(lm_stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, la);
+  if (lm) hipLaunchKernelGGL(lm_stream_reset_kernel, dim3(B), dim3(kThreads), 0, st, la);
+  if (ns.ctx)
+    hipLaunchKernelGGL(ngram_stream_reset_kernel, dim3(B), dim3(64), 0, st, rows, BS, f->start_ctx, ns.ctx, ns.lm_sum);
   hipLaunchKernelGGL(count_kernel, dim3(1), dim3(kThreads), 0, st, w.s.emit, R, w.s.counts + 2);
   p.step(R, w, nullptr, w.s.counts + 2, s.live, s.live, st);
-  if (f && f->start_token >= 0)                            // the LM's first step, as the predictor's on blank
-    enqueue_lm_step(*f->lm, R, lw.tok, w.s.emit, nullptr, w.s.counts + 2, ls.h, ls.c, ls.q, ls.h, ls.c, ls.q, lw,
+  if (lm && f->start_token >= 0)                           // the LM's first step, as the predictor's on blank
+    enqueue_lm_step(*lm, R, lw.tok, w.s.emit, nullptr, w.s.counts + 2, ls.h, ls.c, ls.q, ls.h, ls.c, ls.q, lw,
                     st);
   S2T_CHECK_LAUNCH();
   return 0;
@@ -1452,22 +1581,35 @@ long bytes_of(Carve carve) {
 
 // a fused search's workspace: the predictor's, then the LM's
 template <class P>
-long fused_workspace_bytes(const P& p, const S2tRnnLmDesc* lm, int B, int T, int beam, int n_state) {
-  if (!p.ok() || !fusion_ok(lm, p.V()) || B <= 0 || T < 0 || !beam_ok(beam, 1)) return 0;
+long fused_workspace_bytes(const P& p, const Fusion& f, int B, int T, int beam, int n_state) {
+  if (!p.ok() || !fusion_ok(f, p.V()) || B <= 0 || T < 0 || !beam_ok(beam, 1)) return 0;
   return bytes_of([&](Arena& m) {
     p.work(B, T, beam, m, n_state);
-    carve_lm(*lm, B, beam, m, n_state);
+    if (f.ngram) carve_ngram(B, beam, m, n_state == 2);
+    else carve_lm(*f.lm, B, beam, m, n_state);
   });
 }
 
 // a fused search's stream state: the predictor's, then the LM's
 template <class P>
-long fused_state_bytes(const P& p, const S2tRnnLmDesc* lm, int B, int beam, int max_tokens) {
-  if (B <= 0 || !p.ok() || !fusion_ok(lm, p.V()) || !beam_ok(beam, 1) || max_tokens < 1) return 0;
+long fused_state_bytes(const P& p, const Fusion& f, int B, int beam, int max_tokens) {
+  if (B <= 0 || !p.ok() || !fusion_ok(f, p.V()) || !beam_ok(beam, 1) || max_tokens < 1) return 0;
   return bytes_of([&](Arena& m) {
     p.state(B, beam, max_tokens, m);
-    carve_lm_state(*lm, B, beam, m);
+    if (f.ngram) carve_ngram_state(B, beam, m);
+    else carve_lm_state(*f.lm, B, beam, m);
   });
+}
+
+Fusion rnn_fusion(const S2tRnnLmDesc* lm, float weight = 0.f, int start_token = -1, float* lm_score = nullptr) {
+  return Fusion{lm, weight, start_token, lm_score};
+}
+
+Fusion ngram_fusion(const S2tNgramLmDesc* lm, float weight = 0.f, int start_ctx = 0, float* lm_score = nullptr) {
+  Fusion f{nullptr, weight, -1, lm_score};
+  f.ngram = lm;
+  f.start_ctx = start_ctx;
+  return f;
 }
 
 }  // namespace
@@ -1546,7 +1688,7 @@ int s2t_rnn_lm_step(const S2tRnnLmDesc* lm, int R, const int* tokens, const int*
 
 long s2t_rnnt_beam_lstm_lm_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B, int T,
                                            int beam_size) {
-  return fused_workspace_bytes(LstmPredictor{desc}, lm, B, T, beam_size, 2);
+  return fused_workspace_bytes(LstmPredictor{desc}, rnn_fusion(lm), B, T, beam_size, 2);
 }
 
 int s2t_rnnt_beam_lstm_lm(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, const float* am,
@@ -1581,7 +1723,7 @@ int s2t_stateless_pred_step(const S2tRnntStatelessDesc* desc, int R, const int* 
 
 long s2t_rnnt_beam_stateless_lm_workspace_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, int B,
                                                 int T, int beam_size) {
-  return fused_workspace_bytes(StatelessPredictor{desc}, lm, B, T, beam_size, 2);
+  return fused_workspace_bytes(StatelessPredictor{desc}, rnn_fusion(lm), B, T, beam_size, 2);
 }
 
 int s2t_rnnt_beam_stateless_lm(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, const float* am,
@@ -1645,12 +1787,12 @@ int s2t_rnnt_beam_lstm_chunk(const S2tRnntLstmDesc* desc, const float* am, const
 
 long s2t_rnnt_lstm_lm_stream_state_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B,
                                          int beam_size, int max_tokens) {
-  return fused_state_bytes(LstmPredictor{desc}, lm, B, beam_size, max_tokens);
+  return fused_state_bytes(LstmPredictor{desc}, rnn_fusion(lm), B, beam_size, max_tokens);
 }
 
 long s2t_rnnt_lstm_lm_stream_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int B, int Tc,
                                              int beam_size) {
-  return chunk_ok(Tc) ? fused_workspace_bytes(LstmPredictor{desc}, lm, B, Tc, beam_size, 1) : 0;
+  return chunk_ok(Tc) ? fused_workspace_bytes(LstmPredictor{desc}, rnn_fusion(lm), B, Tc, beam_size, 1) : 0;
 }
 
 int s2t_rnnt_lstm_lm_stream_reset(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc* lm, int lm_start_token,
@@ -1672,14 +1814,58 @@ int s2t_rnnt_beam_lstm_lm_chunk(const S2tRnntLstmDesc* desc, const S2tRnnLmDesc*
                      frames, out_len, score, (hipStream_t)stream);
 }
 
+// ---- the LSTM predictor's beam search with a back-off n-gram: the RNN-LM family's siblings
+long s2t_rnnt_beam_lstm_ngram_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, int B, int T,
+                                              int beam_size) {
+  return fused_workspace_bytes(LstmPredictor{desc}, ngram_fusion(lm), B, T, beam_size, 2);
+}
+
+int s2t_rnnt_beam_lstm_ngram(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, const float* am,
+                             const long* lengths, int B, int T, int beam_size, int cutoff_top_k, float lm_weight,
+                             int start_ctx, void* workspace, long* tokens, long* frames, long* out_len,
+                             float* score, float* lm_score, void* stream) {
+  const Fusion f = ngram_fusion(lm, lm_weight, start_ctx, lm_score);
+  return beam_search(LstmPredictor{desc}, &f, nullptr, am, lengths, B, T, beam_size, cutoff_top_k, workspace,
+                     tokens, frames, out_len, score, (hipStream_t)stream);
+}
+
+long s2t_rnnt_lstm_ngram_stream_state_bytes(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, int B,
+                                            int beam_size, int max_tokens) {
+  return fused_state_bytes(LstmPredictor{desc}, ngram_fusion(lm), B, beam_size, max_tokens);
+}
+
+long s2t_rnnt_lstm_ngram_stream_workspace_bytes(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, int B,
+                                                int Tc, int beam_size) {
+  return chunk_ok(Tc) ? fused_workspace_bytes(LstmPredictor{desc}, ngram_fusion(lm), B, Tc, beam_size, 1) : 0;
+}
+
+int s2t_rnnt_lstm_ngram_stream_reset(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, int start_ctx,
+                                     void* state, const int* rows, int B, int beam_size, int max_tokens,
+                                     void* workspace, void* stream) {
+  const Fusion f = ngram_fusion(lm, 0.f, start_ctx, nullptr);
+  return stream_reset(LstmPredictor{desc}, &f, state, rows, B, beam_size, max_tokens, workspace,
+                      (hipStream_t)stream);
+}
+
+int s2t_rnnt_beam_lstm_ngram_chunk(const S2tRnntLstmDesc* desc, const S2tNgramLmDesc* lm, const float* am,
+                                   const long* chunk_len, int B, int Tc, int beam_size, int cutoff_top_k,
+                                   float lm_weight, int max_tokens, void* state, void* workspace, long* tokens,
+                                   long* frames, long* out_len, float* score, float* lm_score, long* stable_len,
+                                   int* overflow, void* stream) {
+  const Fusion f = ngram_fusion(lm, lm_weight, 0, lm_score);
+  const Chunk ch{state, max_tokens, stable_len, overflow};
+  return beam_search(LstmPredictor{desc}, &f, &ch, am, chunk_len, B, Tc, beam_size, cutoff_top_k, workspace, tokens,
+                     frames, out_len, score, (hipStream_t)stream);
+}
+
 long s2t_rnnt_stateless_lm_stream_state_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, int B,
                                               int beam_size, int max_tokens) {
-  return fused_state_bytes(StatelessPredictor{desc}, lm, B, beam_size, max_tokens);
+  return fused_state_bytes(StatelessPredictor{desc}, rnn_fusion(lm), B, beam_size, max_tokens);
 }
 
 long s2t_rnnt_stateless_lm_stream_workspace_bytes(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm, int B,
                                                   int Tc, int beam_size) {
-  return chunk_ok(Tc) ? fused_workspace_bytes(StatelessPredictor{desc}, lm, B, Tc, beam_size, 1) : 0;
+  return chunk_ok(Tc) ? fused_workspace_bytes(StatelessPredictor{desc}, rnn_fusion(lm), B, Tc, beam_size, 1) : 0;
 }
 
 int s2t_rnnt_stateless_lm_stream_reset(const S2tRnntStatelessDesc* desc, const S2tRnnLmDesc* lm,

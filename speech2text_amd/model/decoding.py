@@ -23,11 +23,14 @@ chunk-carried beam searches take the same LM (RnntLstmStreamingSearch with `lm=`
 RnntStatelessLmStreamingSearch; s2t_rnnt_beam_lstm_lm_chunk, s2t_rnnt_beam_stateless_lm_chunk).
 An NgramLm is fused into the one-workgroup search of the stateless predictor instead, one launch, and
 into its chunk-carried form (rnnt_beam_ngram_tokens_from_am, RnntNgramStreamingSearch;
-s2t_rnnt_beam_stateless_ngram, s2t_rnnt_beam_stateless_ngram_chunk).
+s2t_rnnt_beam_stateless_ngram, s2t_rnnt_beam_stateless_ngram_chunk), and into the lockstep beam search of the
+LSTM predictor, whose rounds then launch no LM step (rnnt_beam_lstm_ngram_tokens_from_am,
+RnntLstmNgramStreamingSearch; s2t_rnnt_beam_lstm_ngram, s2t_rnnt_beam_lstm_ngram_chunk).
 CtcPrefixBeamDecoding is a lexicon-free CTC prefix beam search with equal prefixes merged and the same
 optional RNN-LM term, on the device for the whole batch (csrc/decode_ctc.hip: s2t_ctc_prefix_beam,
 s2t_ctc_prefix_beam_lm) and, in one launch again, a back-off n-gram over the model's classes
-(model/lm/ngram_lm.py NgramLm, s2t_ctc_prefix_beam_ngram); CtcStreamingSearch carries the plain and the
+(model/lm/ngram_lm.py NgramLm, s2t_ctc_prefix_beam_ngram; chunk-carried: CtcNgramStreamingSearch,
+s2t_ctc_prefix_beam_ngram_chunk, built by ctc_streaming_search); CtcStreamingSearch carries the plain and the
 RNN-LM search across chunks with a trie that does not grow with the stream (s2t_ctc_prefix_beam_chunk,
 s2t_ctc_prefix_beam_lm_chunk).  The lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are
 not here."""
@@ -551,6 +554,43 @@ def rnnt_beam_lstm_lm_tokens_from_am(am, lengths, predictor, joiner, lm, lm_weig
     return out
 
 
+def rnnt_beam_lstm_ngram_tokens_from_am(am, lengths, predictor, joiner, lm, lm_weight, beam_size=4, cutoff_top_k=4):
+    """rnnt_beam_lstm_tokens_from_am with back-off n-gram shallow fusion (lm: an NgramLm whose fp32 tables
+    are on am's device): the lockstep rounds in their n-gram mode, a look-up per candidate inside the expand
+    launch and no LM step.  The search starts in the LM's own start context, so the first token is scored
+    too.  -> (tokens, frames, out_len, score, lm_score (B) fp32: the best beam's unweighted LM sum), or
+    None where the entry refuses.  HIP: decode_lstm.hip, ngram_lookup.h."""
+    if not am.is_cuda:
+        raise RuntimeError("the device RNN-T beam search runs on the GPU only")
+    am = am.contiguous().float()
+    B, T, V = am.shape
+    dev = am.device
+    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+    out = _beam_outputs(B, T, dev) + (torch.zeros((B,), dtype=torch.float32, device=dev),)
+    if B == 0 or T == 0:
+        return out
+    if lm.device != dev:
+        raise RuntimeError(f"the n-gram tables are on {lm.device}, am on {dev}: NgramLm.to(device)")
+    desc, keep = rnnt_lstm_desc(predictor, joiner)
+    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
+    if desc is None or lm.dtype != torch.float32:
+        return None
+    lm_desc, lm_keep = lm.desc()
+    n = N.lib().s2t_rnnt_beam_lstm_ngram_workspace_bytes(desc, lm_desc, B, T, beam_size)
+    if n <= 0:
+        return None
+    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+    tokens, frames, out_len, score, lm_score = out
+    rc = N.lib().s2t_rnnt_beam_lstm_ngram(desc, lm_desc, N.fp(am), N.lp(lengths), B, T, beam_size, cutoff_top_k,
+                                          float(lm_weight), int(lm.start_ctx), N.ptr(ws), N.lp(tokens),
+                                          N.lp(frames), N.lp(out_len), N.fp(score), N.fp(lm_score), N.stream())
+    del keep, lm_keep
+    if rc == -1:
+        return None
+    N.check(rc, "s2t_rnnt_beam_lstm_ngram")
+    return out
+
+
 def _is_stateless_pair(predictor, joiner):
     """The modules s2t_rnnt_beam_stateless_lm serves: StatelessPredictor + Joiner (any out-projection)."""
     from speech2text_amd.model.joiner.joiner import Joiner
@@ -997,6 +1037,13 @@ class RnntBeamDecoding(DecodingMethod):
                                                    self._lm_start_token)
             if out is not None:
                 return out
+        if fused and self._lstm_search() and _is_ngram(self._lm) and self._lm_start_token is None \
+                and hidden_states.is_cuda and self._lm.dtype == torch.float32:
+            am, lens = _am_per_utterance(self._joiner, hidden_states, inputs_length)
+            out = rnnt_beam_lstm_ngram_tokens_from_am(am, lens, self._predictor, self._joiner, self._lm,
+                                                      self._lm_weight, self._beam_size, self._cutoff_top_k)
+            if out is not None:
+                return out
         if fused and _is_stateless_pair(self._predictor, self._joiner) and isinstance(self._lm, RnnLm) \
                 and hidden_states.is_cuda:
             am, lens = _am_per_utterance(self._joiner, hidden_states, inputs_length)
@@ -1047,9 +1094,10 @@ def _stream_lm_arguments(lm, lm_weight, lm_start_token, method):
     if method == "greedy":
         raise ValueError("the greedy searches take no language model: use method='beam' or lm=None")
     if _is_ngram(lm):
-        raise ValueError("this chunk-carried search is not fused with an NgramLm: the chunk-carried n-gram search "
-                         "is RnntNgramStreamingSearch, the beam search of the stateless predictor with a "
-                         "projection-free Joiner (pass an RnnLm, or lm=None)")
+        raise ValueError("this chunk-carried search is not fused with an NgramLm: the chunk-carried n-gram searches "
+                         "are CtcNgramStreamingSearch (ctc_streaming_search), RnntLstmNgramStreamingSearch (the "
+                         "LSTM predictor) and RnntNgramStreamingSearch (the stateless predictor with a "
+                         "projection-free Joiner); pass an RnnLm, or lm=None")
     if not isinstance(lm, RnnLm):
         raise ValueError(f"the chunk-carried search is fused with an RnnLm only, got {type(lm).__name__} "
                          "(there is no module-loop fallback here)")
@@ -1300,6 +1348,72 @@ class RnntLstmStreamingSearch(_ChunkCarriedSearch):
             "s2t_rnnt_beam_lstm_chunk")
 
 
+class RnntLstmNgramStreamingSearch(RnntLstmStreamingSearch):
+    """RnntLstmStreamingSearch's beam search fused with a back-off n-gram (csrc/decode_lstm.hip
+    s2t_rnnt_beam_lstm_ngram_chunk): the lockstep rounds in their n-gram mode, carried across chunks; the
+    state buffer also holds a context id and lm_sum per beam, and no LM step is launched.  However the
+    frames are cut, the result after a chunk is rnnt_beam_lstm_ngram_tokens_from_am on the frames fed so
+    far, bit for bit, `lm_score` included.
+
+    Same surface as RnntLstmStreamingSearch with method="beam" and an LM: `step` returns the five beam
+    views, `lm_score` (B, fp32) is the best beam's unweighted LM sum, `reset(rows)` restarts those rows in
+    the LM's start context.  Beam only, no `lm_start_token`.  The tables are copied to the search's device
+    when they live elsewhere.  Other modules, an `lm` that is not an NgramLm with fp32 tables, a weight
+    that is not finite or a shape the entries refuse are a ValueError at construction; modules off the GPU
+    a RuntimeError.  No module-loop fallback."""
+
+    def __init__(self, predictor, joiner, batch_size=1, beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None,
+                 lm=None, lm_weight=0.0):
+        if not _is_ngram(lm):
+            raise ValueError(f"RnntLstmNgramStreamingSearch needs an NgramLm, got {type(lm).__name__}")
+        if lm.dtype != torch.float32:
+            raise ValueError("the device n-gram search needs fp32 tables")
+        if not math.isfinite(float(lm_weight)):
+            raise ValueError(f"lm_weight must be finite, got {lm_weight!r}")
+        self.capturable = True
+        self.lm_score = None
+        self._lm, self._lm_weight, self._lm_start = None, float(lm_weight), -1   # (_lm: the base class' RnnLm slot)
+        self._ngram = lm
+        _ChunkCarriedSearch.__init__(self, predictor, joiner, batch_size, "beam", 0, beam_size, cutoff_top_k,
+                                     max_tokens, device)
+
+    def _allocate(self, predictor, joiner, dev):
+        B, V = self.batch_size, self.V
+        self._desc, self._keep = rnnt_lstm_desc(predictor, joiner)
+        if self._ngram.device != torch.empty(0, device=dev).device:
+            import copy                                    # a copy: the caller's LM stays where it is
+            self._ngram = copy.copy(self._ngram)
+            self._ngram._cache = {}
+            self._ngram.to(dev)
+        lib = N.lib()
+        n = ws = 0
+        if self._desc is not None and B > 0 and self._ngram.num_classes == V:
+            self._lm_desc, self._lm_keep = self._ngram.desc()
+            n = lib.s2t_rnnt_lstm_ngram_stream_state_bytes(self._desc, self._lm_desc, B, self.beam_size,
+                                                           self.max_tokens)
+            ws = lib.s2t_rnnt_lstm_ngram_stream_workspace_bytes(self._desc, self._lm_desc, B, 256, self.beam_size)
+        ok = 1 <= min(self.cutoff_top_k, V) <= N.const("S2T_RNNT_LSTM_MAX_BEAM")
+        if n <= 0 or ws <= 0 or not ok:
+            raise ValueError(f"the chunk-carried LSTM n-gram beam search does not take this shape: B {B} V {V} beam "
+                             f"{self.beam_size} top-k {self.cutoff_top_k} max_tokens {self.max_tokens}, LM V "
+                             f"{self._ngram.num_classes} (limits: include/s2t_mi355.h)")
+        self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)   # the plain state, then ctx and lm_sum per beam
+        self._ws = torch.zeros((ws,), dtype=torch.uint8, device=dev)
+        self.lm_score = torch.zeros((B,), dtype=torch.float32, device=dev)
+
+    def _reset_state(self, mask):
+        N.check(N.lib().s2t_rnnt_lstm_ngram_stream_reset(
+            self._desc, self._lm_desc, int(self._ngram.start_ctx), N.ptr(self.state), N.ip(mask), self.batch_size,
+            self.beam_size, self.max_tokens, N.ptr(self._ws), N.stream()), "s2t_rnnt_lstm_ngram_stream_reset")
+
+    def _chunk(self, am_chunk, chunk_len, Tc):
+        N.check(N.lib().s2t_rnnt_beam_lstm_ngram_chunk(
+            self._desc, self._lm_desc, N.fp(am_chunk), N.lp(chunk_len), self.batch_size, Tc, self.beam_size,
+            self.cutoff_top_k, self._lm_weight, self.max_tokens, N.ptr(self.state), N.ptr(self._ws),
+            N.lp(self.tokens), N.lp(self.frames), N.lp(self.out_len), N.fp(self.score), N.fp(self.lm_score),
+            N.lp(self.stable_len), N.ip(self.overflow), N.stream()), "s2t_rnnt_beam_lstm_ngram_chunk")
+
+
 class RnntStatelessLmStreamingSearch(_ChunkCarriedSearch):
     """The chunk-carried beam search of StatelessPredictor + Joiner (with or without output projection)
     + RnnLm on the lockstep rounds of csrc/decode_lstm.hip (s2t_rnnt_beam_stateless_lm_chunk): however
@@ -1430,7 +1544,9 @@ def rnnt_streaming_search(predictor, joiner, batch_size=1, method="greedy", max_
     RnntStatelessLmStreamingSearch with an RnnLm (joiner with or without output projection),
     RnntNgramStreamingSearch with an NgramLm (beam search, projection-free joiner, no `lm_start_token`)
     and RnntStreamingSearch without an `lm` (which raises for what it does not take).  An NgramLm with
-    the LSTM pair or with method="greedy" raises: those searches are not fused with an n-gram."""
+    the LSTM pair raises here (existing callers are pinned to that): build RnntLstmNgramStreamingSearch
+    directly, as StreamingRecognizer and the tasks do; with method="greedy" it raises: the greedy searches
+    take no LM."""
     if _is_ngram(lm) and method == "beam" and not _is_lstm_pair(predictor, joiner):
         if lm_start_token is not None:
             raise ValueError("an NgramLm starts in its own <s> context: lm_start_token must be None")
@@ -1515,6 +1631,18 @@ class CtcStreamingSearch:
         host and copied over: not for a graph capture); or a device mask, an int32 tensor (B) on the
         search's device with 1 for the rows to reset, which is used as it is -- then, as with None,
         reset enqueues kernels only and can be captured."""
+        mask = self._reset_mask(rows)
+        self._reset_state(mask)
+        outs = [self.tokens, self.out_len, self.score, self.stable_len, self.overflow]
+        if self.lm_score is not None:
+            outs.append(self.lm_score)
+        for t in outs:
+            if mask is None:
+                t.zero_()
+            else:
+                t.masked_fill_(mask.bool().reshape(-1, *[1] * (t.dim() - 1)), 0)
+
+    def _reset_mask(self, rows):
         mask = None
         if isinstance(rows, torch.Tensor) and rows.is_cuda:
             if rows.dtype != torch.int32 or tuple(rows.shape) != (self.batch_size,):
@@ -1525,6 +1653,9 @@ class CtcStreamingSearch:
             mask = torch.zeros((self.batch_size,), dtype=torch.int32)
             mask[torch.as_tensor(rows, dtype=torch.int64)] = 1
             mask = mask.to(self.state.device)
+        return mask
+
+    def _reset_state(self, mask):
         B, V = self.batch_size, self.V
         if self._lm is not None:
             N.check(N.lib().s2t_ctc_lm_stream_reset(self._lm_desc, self._lm_start, N.ptr(self.state), N.ip(mask), B, V,
@@ -1533,14 +1664,6 @@ class CtcStreamingSearch:
         else:
             N.check(N.lib().s2t_ctc_stream_reset(N.ptr(self.state), N.ip(mask), B, V, self.beam_size, self.max_nodes,
                                                  N.stream()), "s2t_ctc_stream_reset")
-        outs = [self.tokens, self.out_len, self.score, self.stable_len, self.overflow]
-        if self.lm_score is not None:
-            outs.append(self.lm_score)
-        for t in outs:
-            if mask is None:
-                t.zero_()
-            else:
-                t.masked_fill_(mask.bool().reshape(-1, *[1] * (t.dim() - 1)), 0)
 
     def step(self, logits_chunk, chunk_len=None):
         """logits_chunk (B, Tc, V) fp32 on the device, raw or normalised, Tc <= 256; chunk_len (B) int64
@@ -1555,6 +1678,11 @@ class CtcStreamingSearch:
             chunk_len = self._full.get(Tc)
             if chunk_len is None:
                 chunk_len = self._full[Tc] = torch.full((B,), Tc, dtype=torch.int64, device=self.state.device)
+        self._chunk(logits_chunk, chunk_len, Tc)
+        return self.tokens, self.out_len, self.score, self.stable_len
+
+    def _chunk(self, logits_chunk, chunk_len, Tc):
+        B, V = self.batch_size, self.V
         if self._lm is not None:
             N.check(N.lib().s2t_ctc_prefix_beam_lm_chunk(
                 self._lm_desc, N.fp(logits_chunk), N.lp(chunk_len), B, Tc, V, self.blank, self.beam_size,
@@ -1568,7 +1696,88 @@ class CtcStreamingSearch:
                 self.max_tokens, self.max_nodes, N.ptr(self.state), N.lp(self.tokens), N.lp(self.out_len),
                 N.fp(self.score), N.lp(self.stable_len), N.ip(self.overflow), N.stream()),
                 "s2t_ctc_prefix_beam_chunk")
-        return self.tokens, self.out_len, self.score, self.stable_len
+
+
+class CtcNgramStreamingSearch(CtcStreamingSearch):
+    """CtcStreamingSearch's beam search fused with a back-off n-gram (csrc/decode_ctc.hip
+    s2t_ctc_prefix_beam_ngram_chunk): ctc_prefix_beam_ngram_tokens fed the frames' scores a chunk at a
+    time, still ONE launch per chunk, the look-up inside the frame body.  However the frames are cut,
+    the result after a chunk is ctc_prefix_beam_ngram_tokens' on the frames fed so far, bit for bit,
+    `lm_score` included, while `overflow` is 0.
+
+    Same attributes, `reset(rows)` (a reset row restarts in the LM's start context) and
+    `step(logits_chunk, chunk_len)` as CtcStreamingSearch with an LM.  Beam only; an NgramLm starts in its
+    own <s> context, so there is no `lm_start_token`.  The tables are copied to the search's device when
+    they live elsewhere.  An `lm` that is not an NgramLm with fp32 tables, a weight that is not finite or
+    a shape the entry refuses are a ValueError at construction.  No host-loop fallback."""
+
+    def __init__(self, num_classes, batch_size=1, beam_size=4, cutoff_top_k=4, max_tokens=1024, max_nodes=4096,
+                 blank=0, device=None, lm=None, lm_weight=0.0):
+        if not _is_ngram(lm):
+            raise ValueError(f"CtcNgramStreamingSearch needs an NgramLm, got {type(lm).__name__}")
+        if lm.dtype != torch.float32:
+            raise ValueError("the device n-gram search needs fp32 tables")
+        if not math.isfinite(float(lm_weight)):
+            raise ValueError(f"lm_weight must be finite, got {lm_weight!r}")
+        dev = torch.device("cuda") if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("the chunk-carried search runs on the GPU only: the device must be cuda")
+        self.method, self.batch_size, self.V = "beam", int(batch_size), int(num_classes)
+        self.beam_size, self.cutoff_top_k = int(beam_size), int(cutoff_top_k)
+        self.max_tokens, self.max_nodes, self.blank = int(max_tokens), int(max_nodes), int(blank)
+        self._lm_weight = float(lm_weight)
+        B, V = self.batch_size, self.V
+        ok = B > 0 and 0 <= self.blank < V and self.max_tokens >= 1 and self.cutoff_top_k >= 1 \
+            and min(self.cutoff_top_k, V) <= N.const("S2T_RNNT_LSTM_MAX_BEAM") and lm.num_classes == V
+        n = N.lib().s2t_ctc_ngram_stream_state_bytes(B, V, self.beam_size, self.max_nodes) if ok else 0
+        if n <= 0:
+            raise ValueError(f"the chunk-carried CTC n-gram beam search does not take this shape: B {B} V {V} blank "
+                             f"{self.blank} beam {self.beam_size} top-k {self.cutoff_top_k} max_tokens "
+                             f"{self.max_tokens} max_nodes {self.max_nodes}, LM V {lm.num_classes} "
+                             "(limits: include/s2t_mi355.h)")
+        self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)   # the plain state, then ctx per prefix
+        if lm.device != self.state.device:                 # a copy: the caller's LM stays where it is
+            import copy
+            lm = copy.copy(lm)
+            lm._cache = {}
+            lm.to(self.state.device)
+        self._lm = lm
+        self._lm_desc, self._lm_keep = lm.desc()
+        self._ws = None
+        self.tokens = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
+        self.out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
+        self.score = torch.zeros((B,), dtype=torch.float32, device=dev)
+        self.stable_len = torch.zeros((B,), dtype=torch.int64, device=dev)
+        self.overflow = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.lm_score = torch.zeros((B,), dtype=torch.float32, device=dev)
+        self._full = {}
+        self.reset()
+
+    def _reset_state(self, mask):
+        N.check(N.lib().s2t_ctc_ngram_stream_reset(N.ptr(self.state), N.ip(mask), self.batch_size, self.V,
+                                                   self.beam_size, self.max_nodes, int(self._lm.start_ctx),
+                                                   N.stream()), "s2t_ctc_ngram_stream_reset")
+
+    def _chunk(self, logits_chunk, chunk_len, Tc):
+        N.check(N.lib().s2t_ctc_prefix_beam_ngram_chunk(
+            self._lm_desc, N.fp(logits_chunk), N.lp(chunk_len), self.batch_size, Tc, self.V, self.blank,
+            self.beam_size, self.cutoff_top_k, self._lm_weight, self.max_tokens, self.max_nodes, N.ptr(self.state),
+            N.lp(self.tokens), N.lp(self.out_len), N.fp(self.score), N.fp(self.lm_score), N.lp(self.stable_len),
+            N.ip(self.overflow), N.stream()), "s2t_ctc_prefix_beam_ngram_chunk")
+
+
+def ctc_streaming_search(num_classes, batch_size=1, method="beam", beam_size=4, cutoff_top_k=4, max_tokens=1024,
+                         max_nodes=4096, blank=0, device=None, lm=None, lm_weight=0.0, lm_start_token=None):
+    """The chunk-carried CTC search that serves the LM: CtcNgramStreamingSearch for an NgramLm with the
+    beam method (no `lm_start_token`), CtcStreamingSearch for everything else (which raises for what it
+    does not take)."""
+    if _is_ngram(lm) and method == "beam":
+        if lm_start_token is not None:
+            raise ValueError("an NgramLm starts in its own <s> context: lm_start_token must be None")
+        return CtcNgramStreamingSearch(num_classes, batch_size, beam_size, cutoff_top_k, max_tokens, max_nodes,
+                                       blank, device, lm=lm, lm_weight=lm_weight)
+    return CtcStreamingSearch(num_classes, batch_size, method, beam_size, cutoff_top_k, max_tokens, max_nodes,
+                              blank, device, lm=lm, lm_weight=lm_weight, lm_start_token=lm_start_token)
 
 
 @unique

@@ -300,20 +300,28 @@ class StreamingRecognizer:
     pair through RnntLstmStreamingSearch, the stateless predictor with either joiner through
     RnntStatelessLmStreamingSearch; `search.lm_score` holds the best beams' unweighted LM sums.  With an
     NgramLm (beam only, no `lm_start_token`) the stateless predictor with a projection-free joiner runs
-    RnntNgramStreamingSearch, the one-workgroup chunk kernel with the look-up inside its frame body."""
+    RnntNgramStreamingSearch, the one-workgroup chunk kernel with the look-up inside its frame body, and
+    the LSTM pair RnntLstmNgramStreamingSearch, the lockstep rounds in their n-gram mode."""
 
     def __init__(self, encoder, predictor, joiner, tokenizer, cmvn=None, batch_size: int = 1,
                  method: str = "greedy", max_token_step: int = 5, beam_size: int = 4,
                  cutoff_top_k: int = 4, max_tokens: int = 1024, device=None, warmup: int = 2,
                  lm=None, lm_weight: float = 0.0, lm_start_token=None):
-        from speech2text_amd.model.decoding import rnnt_streaming_search
+        from speech2text_amd.model.decoding import (RnntLstmNgramStreamingSearch, _is_lstm_pair, _is_ngram,
+                                                    rnnt_streaming_search)
         model, device, lm = self._check_model(encoder, (predictor, joiner), tokenizer, batch_size, device, lm)
         if model._for_ctc:
             raise ValueError("StreamingRecognizer searches the encoder output: build the encoder with for_ctc=False")
         self.joiner = joiner
-        self.search = rnnt_streaming_search(predictor, joiner, batch_size, method, max_token_step,
-                                            beam_size, cutoff_top_k, max_tokens, device, lm=lm,
-                                            lm_weight=lm_weight, lm_start_token=lm_start_token)
+        if _is_ngram(lm) and method == "beam" and _is_lstm_pair(predictor, joiner):
+            if lm_start_token is not None:
+                raise ValueError("an NgramLm starts in its own <s> context: lm_start_token must be None")
+            self.search = RnntLstmNgramStreamingSearch(predictor, joiner, batch_size, beam_size, cutoff_top_k,
+                                                       max_tokens, device, lm=lm, lm_weight=lm_weight)
+        else:
+            self.search = rnnt_streaming_search(predictor, joiner, batch_size, method, max_token_step,
+                                                beam_size, cutoff_top_k, max_tokens, device, lm=lm,
+                                                lm_weight=lm_weight, lm_start_token=lm_start_token)
         self._capture(model, cmvn, device, warmup, lambda enc: joiner._enc_proj(enc).float().contiguous())
 
     def _check_model(self, encoder, heads, tokenizer, batch_size, device, lm):
@@ -455,15 +463,16 @@ class CtcStreamingRecognizer(StreamingRecognizer):
     Same surface: `reset`, `step`, `texts`, `stable_texts`, `num_output_frames`, `recognize`, the fixed
     buffers `x`, `chunk_len`, `states`, and `search` with its outputs.  `step` returns (tokens, out_len,
     score, stable_len, scores), scores (B, chunk//2, V) being what the search read.  method "beam" or
-    "greedy" (beam_size = cutoff_top_k = 1); with `lm` (an RnnLm; beam only) the chunk call is fused with
-    it (`lm_weight`, `lm_start_token` as CtcPrefixBeamDecoding's) and `search.lm_score` holds the best
-    prefixes' unweighted LM sums.  `max_nodes`: trie nodes per stream (CtcStreamingSearch)."""
+    "greedy" (beam_size = cutoff_top_k = 1); with `lm` (an RnnLm, or an NgramLm, which takes no
+    `lm_start_token`; beam only) the chunk call is fused with it (`lm_weight`, `lm_start_token` as
+    CtcPrefixBeamDecoding's; model/decoding.py ctc_streaming_search picks the search) and `search.lm_score`
+    holds the best prefixes' unweighted LM sums.  `max_nodes`: trie nodes per stream (CtcStreamingSearch)."""
 
     def __init__(self, encoder, tokenizer, head=None, cmvn=None, batch_size: int = 1, method: str = "beam",
                  beam_size: int = 4, cutoff_top_k: int = 4, max_tokens: int = 1024, max_nodes: int = 4096,
                  blank: int = 0, device=None, warmup: int = 2, lm=None, lm_weight: float = 0.0,
                  lm_start_token=None):
-        from speech2text_amd.model.decoding import CtcStreamingSearch
+        from speech2text_amd.model.decoding import ctc_streaming_search
         model, device, lm = self._check_model(encoder, (head,), tokenizer, batch_size, device, lm)
         if model._for_ctc == (head is not None):
             raise ValueError("CtcStreamingRecognizer searches CTC scores: build the encoder with for_ctc=True and "
@@ -475,7 +484,7 @@ class CtcStreamingRecognizer(StreamingRecognizer):
             num_classes = head._fc.out_features
             scores = lambda enc: head(enc, self.chunk_len)[0].float().contiguous()          # noqa: E731
         self.head = head
-        self.search = CtcStreamingSearch(num_classes, batch_size, method, beam_size, cutoff_top_k, max_tokens,
-                                         max_nodes, blank, device, lm=lm, lm_weight=lm_weight,
-                                         lm_start_token=lm_start_token)
+        self.search = ctc_streaming_search(num_classes, batch_size, method, beam_size, cutoff_top_k, max_tokens,
+                                           max_nodes, blank, device, lm=lm, lm_weight=lm_weight,
+                                           lm_start_token=lm_start_token)
         self._capture(model, cmvn, device, warmup, scores)

@@ -65,7 +65,9 @@ class CtcTask(TaskBase):
         "beam") comes from the `metric:` section's decode_method when not given (ctc_greedy_search /
         ctc_prefix_beam_search), beam_size and cutoff_top_k from there too, and with `metric.lm` and the
         beam method the search is shallow-fused with that LM (`metric.lm_weight`,
-        `metric.lm_start_token`), as the validation search is.  The task must be on the GPU and in eval
+        `metric.lm_start_token`), as the validation search is; an ARPA `metric.lm` is not taken by default
+        (a ValueError): pass lm=<NgramLm>, lm_weight= explicitly for the fused n-gram search
+        (CtcNgramStreamingSearch).  The task must be on the GPU and in eval
         mode; its head is the encoder's own projection (for_ctc, Identity decoder) or the Projector."""
         from speech2text_amd.model.decoder.decoder import Identity, Projector
         from speech2text_amd.model.encoder.zipformer_streaming import CtcStreamingRecognizer
@@ -88,8 +90,8 @@ class CtcTask(TaskBase):
             lm = self._metric_lm()
             from speech2text_amd.model.lm.ngram_lm import NgramLm
             if isinstance(lm, NgramLm):
-                raise ValueError("metric.lm names an ARPA n-gram: the chunk-carried CTC search is not fused with "
-                                 "it (pass lm=None or an RnnLm to stream without it)")
+                raise ValueError("metric.lm names an ARPA n-gram: pass it as lm=<NgramLm> (and lm_weight=) to "
+                                 "stream with CtcNgramStreamingSearch, or lm=None / an RnnLm to stream without it")
             if lm is not None:
                 kw["lm"] = lm
                 kw.setdefault("lm_weight", cfg.lm_weight)

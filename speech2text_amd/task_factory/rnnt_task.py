@@ -235,7 +235,8 @@ class PrunedRnntTask(BaseRnntTask):
         `metric.lm` and the beam method the search is shallow-fused with that LM (`metric.lm_weight`,
         `metric.lm_start_token`), as the validation search is; the stateless predictor then takes
         either joiner.  `metric.lm: {arpa:}` (an NgramLm) builds RnntNgramStreamingSearch for the stateless
-        predictor with a projection-free joiner and raises for the LSTM predictor."""
+        predictor with a projection-free joiner and RnntLstmNgramStreamingSearch for the LSTM predictor
+        (no `metric.lm_start_token` with either)."""
         from speech2text_amd.model.decoder.decoder import Identity
         from speech2text_amd.model.encoder.zipformer_streaming import StreamingRecognizer
         from speech2text_amd.model.utils import AsrMetricConfig
