@@ -578,12 +578,16 @@ int s2t_gemm_tn_grouped(int n, const S2tTnProblem* probs, void* stream);
 /* ---- BEST-RQ SSL heads: fused log-softmax + smoothed-target loss (model/loss/kl_divergence.py:
  * 36-76, model/loss/cross_entropy.py:38-69; call site task_factory/ssl_task.py:140-158).
  * logits [rows][K]; labels [rows]; target t_c = t_other (c != label) / t_label; row_loss[r] =
- * c0 - sum_c t_c log_softmax(scale x)_c and lse[r]; backward grad[r][c] = row_weight[r] * scale *
- * (softmax_c - t_c)  (row_weight = upstream gradient * mask / mask.sum()). */
+ * c0 - sum_c t_c log_softmax(scale x)_c; backward grad[r][c] = row_weight[r] * scale *
+ * (softmax_c - t_c)  (row_weight = upstream gradient * mask / mask.sum()).  stats
+ * [rows][S2T_NLL_STATS] is what the forward saves for the backward: the row maximum of scale x and
+ * the log of sum_c exp(scale x_c - maximum), kept apart so that an offset row loses nothing.  A
+ * label outside [0, K) matches no class: no label term in the loss, t_c = t_other in the gradient. */
+#define S2T_NLL_STATS 2
 int s2t_smoothed_nll_fwd(const float* logits, const long* labels, long rows, int K, float scale,
-                         float t_other, float t_label, float c0, float* row_loss, float* lse,
+                         float t_other, float t_label, float c0, float* row_loss, float* stats,
                          void* stream);
-int s2t_smoothed_nll_bwd(const float* logits, const long* labels, const float* lse,
+int s2t_smoothed_nll_bwd(const float* logits, const long* labels, const float* stats,
                          const float* row_weight, long rows, int K, float scale, float t_other,
                          float t_label, float* grad, void* stream);
 

@@ -1,4 +1,5 @@
-"""Oracle: kaldi-style fbank, numpy float32 restatement.
+"""Oracle: kaldi-style fbank, numpy float32 restatement (the window and the mel banks in torch
+float32, op for op as torchaudio builds them: tests/test_front_f64.py holds them to FbankTables bit for bit).
 
 Follows dataset/frontend/frontend.py:85-94 -> torchaudio.compliance.kaldi.fbank
 (torchaudio 0.13.1, not vendored) as stated op-by-op by the TorchScript archive
@@ -19,10 +20,11 @@ def mel_scale(f):
 
 
 def povey_window():
-    # hann_window(400, periodic=False) ** 0.85 in float32
-    n = np.arange(400, dtype=np.float64)
-    hann = (0.5 - 0.5 * np.cos(2.0 * math.pi * n / 399.0)).astype(np.float32)
-    return np.power(hann, np.float32(0.85)).astype(np.float32)
+    # torch.hann_window(400, periodic=False).pow(0.85), all of it in float32 as kaldi.fbank takes it:
+    # a Hann window rounded from float64 differs from that by up to 6e-5 (relative) near the edges,
+    # and the archive's outputs (tests/golden/fbank_script64.npz) sit closer to this one
+    import torch
+    return torch.hann_window(400, periodic=False, dtype=torch.float32).pow(0.85).numpy()
 
 
 def mel_banks(num_bins, sample_freq=16000.0, low_freq=20.0, high_freq=0.0, nfft=512):
@@ -34,17 +36,19 @@ def mel_banks(num_bins, sample_freq=16000.0, low_freq=20.0, high_freq=0.0, nfft=
     mel_low = mel_scale(low_freq)
     mel_high = mel_scale(high_freq)
     delta = (mel_high - mel_low) / (num_bins + 1)
-    b = np.arange(num_bins, dtype=np.float32)[:, None]
-    d32, l32 = np.float32(delta), np.float32(mel_low)
-    left = b * d32 + l32
-    center = (b + np.float32(1.0)) * d32 + l32
-    right = (b + np.float32(2.0)) * d32 + l32
-    freq = np.arange(nfft // 2, dtype=np.float32) * np.float32(fft_bin_width)
-    mel = (np.log(freq / np.float32(700.0) + np.float32(1.0)) * np.float32(1127.0))[None, :]
-    mel = mel.astype(np.float32)
+    # torchaudio's get_mel_banks, op for op in torch float32: the slopes divide by differences of mel
+    # values near 2800, so one rounding of the logarithm moves a weight by 1e-5, and numpy's float32
+    # log is not torch's.  The archive's outputs sit closer to this form than to a numpy one.
+    import torch
+    b = torch.arange(num_bins).unsqueeze(1)
+    left = mel_low + b * delta
+    center = mel_low + (b + 1.0) * delta
+    right = mel_low + (b + 2.0) * delta
+    freq = fft_bin_width * torch.arange(nfft // 2)
+    mel = (1127.0 * (1.0 + freq / 700.0).log()).unsqueeze(0)
     up = (mel - left) / (center - left)
     down = (right - mel) / (right - center)
-    w = np.maximum(np.float32(0.0), np.minimum(up, down)).astype(np.float32)
+    w = torch.max(torch.zeros(1), torch.min(up, down)).numpy()
     return np.pad(w, ((0, 0), (0, 1))).astype(np.float32)
 
 

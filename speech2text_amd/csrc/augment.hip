@@ -31,6 +31,10 @@ __global__ __launch_bounds__(256) void row_energy_kernel(const float* __restrict
 //   gain = src_e > 0 && noise_e > 0 ? src_e 10^(-snr/10) / noise_e : 1;  log(max(e^a + gain e^b, 1e-10))
 // mode 1 (AddNoise, PCM, D = 1): gain_db = min(rms_db(src) - rms_db(noise) - snr, max_gain);
 //   clip(a + b 10^(gain_db/20), -1, 1)
+//   Silence (an energy of exactly 0) adds nothing: a silent source has rms_db = -inf, so the gain is
+//   10^(-inf) = 0; a silent noise gives gain_db = +inf, which fminf holds at max_gain, times noise
+//   samples that are all 0; both silent gives -inf + inf = NaN, which fminf drops for max_gain as
+//   well.  In all three the output is the source, bit for bit (tests/front_cases.py mx1_silent).
 __global__ __launch_bounds__(256) void mix_kernel(const float* __restrict__ src, long sstride,
                                                   const long* __restrict__ slen,
                                                   const float* __restrict__ noise, long nstride,

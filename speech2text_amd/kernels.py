@@ -655,6 +655,9 @@ def make_boundary(target_lengths, frame_lengths, device):
 
 
 # =============================================================== BEST-RQ SSL heads
+NLL_STATS = N.const("S2T_NLL_STATS")     # floats per row the forward saves for the backward (csrc/ssl_loss.hip)
+
+
 class _SmoothedNll(torch.autograd.Function):
     """Per-row  C0 - sum_c t_c log_softmax(scale * logits)_c  (csrc/ssl_loss.hip)."""
 
@@ -665,23 +668,23 @@ class _SmoothedNll(torch.autograd.Function):
         rows, K = logits.shape
         labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
         row = torch.empty(rows, dtype=torch.float32, device=logits.device)
-        lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
+        stats = torch.empty((rows, NLL_STATS), dtype=torch.float32, device=logits.device)
         N.PROF[0] and N.profile_note("s2t_smoothed_nll_fwd", 4.0 * logits.numel())
         N.check(N.lib().s2t_smoothed_nll_fwd(N.fp(logits), N.lp(labels), rows, K, float(scale),
                                              float(t_other), float(t_label), float(c0),
-                                             N.fp(row), N.fp(lse), N.stream()), "smoothed_nll_fwd")
-        ctx.save_for_backward(logits, labels, lse)
+                                             N.fp(row), N.fp(stats), N.stream()), "smoothed_nll_fwd")
+        ctx.save_for_backward(logits, labels, stats)
         ctx.cfg = (float(scale), float(t_other), float(t_label))
         return row
 
     @staticmethod
     def backward(ctx, g):
-        logits, labels, lse = ctx.saved_tensors
+        logits, labels, stats = ctx.saved_tensors
         scale, t_other, t_label = ctx.cfg
         rows, K = logits.shape
         grad = torch.empty_like(logits)
         N.PROF[0] and N.profile_note("s2t_smoothed_nll_bwd", 8.0 * logits.numel())
-        N.check(N.lib().s2t_smoothed_nll_bwd(N.fp(logits), N.lp(labels), N.fp(lse),
+        N.check(N.lib().s2t_smoothed_nll_bwd(N.fp(logits), N.lp(labels), N.fp(stats),
                                              N.fp(g.contiguous().float()), rows, K, scale, t_other,
                                              t_label, N.fp(grad), N.stream()), "smoothed_nll_bwd")
         return grad, None, None, None, None, None

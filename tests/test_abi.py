@@ -83,6 +83,7 @@ def test_header_constants():
     assert zip_native.NDEC == len(zip_native.Call().dec) == int(found["S2T_ZL_NDEC"])
     assert zip_native.NWHITEN == int(found["S2T_ZL_NWHITEN"])
     assert kernels.CTC_MAX_LABELS == int(found["S2T_CTC_MAX_LABELS"])
+    assert kernels.NLL_STATS == int(found["S2T_NLL_STATS"]) == 2
 
 
 # ------------------------------------------------------------------ the plan rule
