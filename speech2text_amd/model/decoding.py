@@ -35,6 +35,8 @@ RNN-LM search across chunks with a trie that does not grow with the stream (s2t_
 s2t_ctc_prefix_beam_lm_chunk).  The lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are
 not here."""
 import abc
+import copy
+import ctypes
 import math
 from enum import Enum, unique
 from typing import List
@@ -52,6 +54,16 @@ class DecodingMethod(abc.ABC):
     def decode_batch(self, hidden_states: torch.Tensor, inputs_length: torch.Tensor) -> List[str]:
         return [self.decode(hidden_states[i:i + 1, :int(inputs_length[i]), :])
                 for i in range(hidden_states.shape[0])]
+
+
+class _BatchDecoding(DecodingMethod):
+    """A method whose decode_batch is the search: one utterance is a batch of one."""
+
+    @torch.no_grad()
+    def decode(self, hidden_states: torch.Tensor) -> str:
+        assert hidden_states.shape[0] == 1, "Support BatchSize = 1 only."
+        n = torch.tensor([hidden_states.shape[1]], dtype=torch.int64)
+        return self.decode_batch(hidden_states, n)[0]
 
 
 def batch_search(hidden_states: torch.Tensor, inputs_length: torch.Tensor,
@@ -93,7 +105,7 @@ def _to_texts(tokens, out_len, tokenizer):
     return [tokenizer.decode(tok[b, :n[b]]) for b in range(tok.shape[0])]
 
 
-class CtcGreedyDecoding(DecodingMethod):
+class CtcGreedyDecoding(_BatchDecoding):
     def __init__(self, tokenizer, dummy=-1) -> None:
         self._tokenizer = tokenizer
 
@@ -101,44 +113,102 @@ class CtcGreedyDecoding(DecodingMethod):
         assert hidden_states.shape[-1] == len(self._tokenizer.labels)
         return _to_texts(*ctc_greedy_tokens(hidden_states, inputs_length), self._tokenizer)
 
-    def decode(self, hidden_states: torch.Tensor) -> str:
-        assert hidden_states.shape[0] == 1, "Support BatchSize = 1 only."
-        n = torch.tensor([hidden_states.shape[1]], dtype=torch.int64)
-        return self.decode_batch(hidden_states, n)[0]
 
-
-def _ctc_prefix_arguments(logits, lengths):
-    if not logits.is_cuda:
-        raise RuntimeError("the device CTC prefix beam search runs on the GPU only")
-    logits = logits.contiguous().float()
-    B, T, _ = logits.shape
-    dev = logits.device
+def _whole_utterance(entry, what, scores, lengths, plan, frames=False, score=True, lm_score=False, per_frame=1):
+    """The one calling path of the whole-utterance device searches.  scores (B,T,V) must be on the device
+    (RuntimeError: the `what` runs on the GPU only), lengths (B) follow them.  The outputs are zeroed --
+    tokens (B, T * per_frame) int64, [frames (B,T) int64,] out_len (B) int64, [score (B) fp32,] [lm_score
+    (B) fp32] -- and are the answer for an empty batch.  Then `plan(scores, lengths)` states the search:
+    None where it refuses, else (workspace bytes, call, keep).  `call(tail)` makes the C call, `tail` being
+    the entry's last arguments: workspace, the outputs in the order above, stream.  `keep` is what the
+    call's pointers need alive (descriptors and the tensors behind them); it is held here until the call
+    has returned.  -> the outputs, or None for bytes <= 0 and for rc -1 (the caller runs its host loop);
+    any other rc raises."""
+    if not scores.is_cuda:
+        raise RuntimeError(f"the {what} runs on the GPU only")
+    scores = scores.contiguous().float()
+    B, T, _ = scores.shape
+    dev = scores.device
     lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
-    out = (torch.zeros((B, T), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev),
-           torch.zeros((B,), dtype=torch.float32, device=dev))
-    return logits, lengths, out
+    out = [torch.zeros((B, T * per_frame), dtype=torch.int64, device=dev)]
+    if frames:
+        out.append(torch.zeros((B, T), dtype=torch.int64, device=dev))
+    out.append(torch.zeros((B,), dtype=torch.int64, device=dev))
+    out += [torch.zeros((B,), dtype=torch.float32, device=dev) for has in (score, lm_score) if has]
+    out = tuple(out)
+    if B == 0 or T == 0:
+        return out
+    planned = plan(scores, lengths)
+    if planned is None or planned[0] <= 0:
+        return None
+    nbytes, call, keep = planned                           # (keep: a local until this function returns)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    rc = call([N.ptr(ws)] + [N.lp(t) if t.dtype is torch.int64 else N.fp(t) for t in out] + [N.stream()])
+    if rc == -1:
+        return None
+    N.check(rc, entry)
+    return out
+
+
+def _lm_start_arg(lm_start_token):
+    """lm_start_token as the C entries take it: -1 for None, else the token id; a negative id is a ValueError."""
+    start = -1 if lm_start_token is None else int(lm_start_token)
+    if lm_start_token is not None and start < 0:
+        raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
+    return start
+
+
+def _is_ngram(lm):
+    from speech2text_amd.model.lm.ngram_lm import NgramLm
+    return isinstance(lm, NgramLm)
+
+
+def _ngram_arguments(lm, lm_weight, name):
+    """The LM arguments of the device n-gram search `name`, checked -> (lm, lm_weight, -1: it starts in
+    its own <s> context and takes no start token)."""
+    if not _is_ngram(lm):
+        raise ValueError(f"{name} needs an NgramLm, got {type(lm).__name__}")
+    if lm.dtype != torch.float32:
+        raise ValueError("the device n-gram search needs fp32 tables")
+    if not math.isfinite(float(lm_weight)):
+        raise ValueError(f"lm_weight must be finite, got {lm_weight!r}")
+    return lm, float(lm_weight), -1
+
+
+def _ngram_on(lm, dev):
+    """lm itself where its tables are on `dev`, else a copy moved there: the caller's object stays where it is."""
+    dev = torch.empty(0, device=dev).device                # (with its index, as a tensor's device reads)
+    if lm.device == dev:
+        return lm
+    lm = copy.copy(lm)
+    lm._cache = {}
+    return lm.to(dev)
+
+
+def _ngram_beside(lm, scores, what):
+    if lm.device != scores.device:
+        raise RuntimeError(f"the n-gram tables are on {lm.device}, {what} on {scores.device}: NgramLm.to(device)")
+
+
+def _lm_follows(lm, dev):
+    """A decoding class' LM follows the inputs to their device on first use (the task does not own it)."""
+    if isinstance(lm, torch.nn.Module):
+        p = next(lm.parameters(), None)
+        if p is not None and p.device != dev:
+            lm.to(dev)
+    elif _is_ngram(lm):
+        lm.to(dev)
 
 
 def ctc_prefix_beam_tokens(logits, lengths, beam_size=4, cutoff_top_k=4, blank=0):
     """CTC prefix beam search with equal prefixes merged: (B,T,V) device logits (raw or normalised) ->
     (tokens (B,T) int64, out_len (B) int64, score (B) fp32: log-probability of the best prefix summed
     over its alignments), or None when the kernel does not take the shape.  HIP: decode_ctc.hip."""
-    logits, lengths, out = _ctc_prefix_arguments(logits, lengths)
-    B, T, V = logits.shape
-    if B == 0 or T == 0:
-        return out
-    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
-    n = N.lib().s2t_ctc_prefix_beam_workspace_bytes(B, T, V, beam_size)
-    if n <= 0:
-        return None
-    ws = torch.empty((n,), dtype=torch.uint8, device=logits.device)
-    tokens, out_len, score = out
-    rc = N.lib().s2t_ctc_prefix_beam(N.fp(logits), N.lp(lengths), B, T, V, int(blank), beam_size, cutoff_top_k,
-                                     N.ptr(ws), N.lp(tokens), N.lp(out_len), N.fp(score), N.stream())
-    if rc == -1:
-        return None
-    N.check(rc, "s2t_ctc_prefix_beam")
-    return out
+    def plan(x, n):
+        (B, T, V), beam, topk = x.shape, int(beam_size), int(cutoff_top_k)
+        return N.lib().s2t_ctc_prefix_beam_workspace_bytes(B, T, V, beam), lambda tail: N.lib().s2t_ctc_prefix_beam(
+            N.fp(x), N.lp(n), B, T, V, int(blank), beam, topk, *tail), None
+    return _whole_utterance("s2t_ctc_prefix_beam", "device CTC prefix beam search", logits, lengths, plan)
 
 
 def ctc_prefix_beam_lm_tokens(logits, lengths, lm, lm_weight, beam_size=4, cutoff_top_k=4, blank=0,
@@ -147,31 +217,17 @@ def ctc_prefix_beam_lm_tokens(logits, lengths, lm, lm_weight, beam_size=4, cutof
     lm_weight * (the LM's log-probability of their tokens).  lm_start_token as in
     rnnt_beam_lstm_lm_tokens_from_am.  -> (tokens, out_len, score (the acoustic part), lm_score (B) fp32:
     the best prefix' unweighted LM sum), or None when the kernels do not take the shape."""
-    logits, lengths, out = _ctc_prefix_arguments(logits, lengths)
-    B, T, V = logits.shape
-    out = out + (torch.zeros((B,), dtype=torch.float32, device=logits.device),)
-    if B == 0 or T == 0:
-        return out
-    start = -1 if lm_start_token is None else int(lm_start_token)
-    if lm_start_token is not None and start < 0:
-        raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
-    lm_desc, lm_keep = rnn_lm_desc(lm)
-    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
-    if lm_desc is None:
-        return None
-    n = N.lib().s2t_ctc_prefix_beam_lm_workspace_bytes(lm_desc, B, T, V, beam_size)
-    if n <= 0:
-        return None
-    ws = torch.empty((n,), dtype=torch.uint8, device=logits.device)
-    tokens, out_len, score, lm_score = out
-    rc = N.lib().s2t_ctc_prefix_beam_lm(lm_desc, N.fp(logits), N.lp(lengths), B, T, V, int(blank), beam_size,
-                                        cutoff_top_k, float(lm_weight), start, N.ptr(ws), N.lp(tokens),
-                                        N.lp(out_len), N.fp(score), N.fp(lm_score), N.stream())
-    del lm_keep
-    if rc == -1:
-        return None
-    N.check(rc, "s2t_ctc_prefix_beam_lm")
-    return out
+    def plan(x, n):
+        start = _lm_start_arg(lm_start_token)
+        lm_desc, keep = rnn_lm_desc(lm)
+        (B, T, V), beam, topk = x.shape, int(beam_size), int(cutoff_top_k)
+        if lm_desc is None:
+            return None
+        return N.lib().s2t_ctc_prefix_beam_lm_workspace_bytes(lm_desc, B, T, V, beam), \
+            lambda tail: N.lib().s2t_ctc_prefix_beam_lm(lm_desc, N.fp(x), N.lp(n), B, T, V, int(blank), beam, topk,
+                                                        float(lm_weight), start, *tail), keep
+    return _whole_utterance("s2t_ctc_prefix_beam_lm", "device CTC prefix beam search", logits, lengths, plan,
+                            lm_score=True)
 
 
 def ctc_prefix_beam_ngram_tokens(logits, lengths, lm, lm_weight, beam_size=4, cutoff_top_k=4, blank=0):
@@ -181,28 +237,17 @@ def ctc_prefix_beam_ngram_tokens(logits, lengths, lm, lm_weight, beam_size=4, cu
     own start context, so the first token is scored too.  -> (tokens, out_len, score (the acoustic
     part), lm_score (B) fp32: the best prefix' unweighted LM sum), or None where the entry refuses.
     HIP: decode_ctc.hip, ngram_lookup.h."""
-    logits, lengths, out = _ctc_prefix_arguments(logits, lengths)
-    B, T, V = logits.shape
-    out = out + (torch.zeros((B,), dtype=torch.float32, device=logits.device),)
-    if B == 0 or T == 0:
-        return out
-    if lm.device != logits.device:
-        raise RuntimeError(f"the n-gram tables are on {lm.device}, the logits on {logits.device}: NgramLm.to(device)")
-    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
-    n = N.lib().s2t_ctc_prefix_beam_ngram_workspace_bytes(B, T, V, beam_size)
-    if n <= 0:
-        return None
-    lm_desc, lm_keep = lm.desc()
-    ws = torch.empty((n,), dtype=torch.uint8, device=logits.device)
-    tokens, out_len, score, lm_score = out
-    rc = N.lib().s2t_ctc_prefix_beam_ngram(lm_desc, N.fp(logits), N.lp(lengths), B, T, V, int(blank), beam_size,
-                                           cutoff_top_k, float(lm_weight), int(lm.start_ctx), N.ptr(ws),
-                                           N.lp(tokens), N.lp(out_len), N.fp(score), N.fp(lm_score), N.stream())
-    del lm_keep
-    if rc == -1:
-        return None
-    N.check(rc, "s2t_ctc_prefix_beam_ngram")
-    return out
+    def plan(x, n):
+        _ngram_beside(lm, x, "the logits")
+        (B, T, V), beam, topk = x.shape, int(beam_size), int(cutoff_top_k)
+        nbytes = N.lib().s2t_ctc_prefix_beam_ngram_workspace_bytes(B, T, V, beam)
+        if nbytes <= 0:
+            return None
+        lm_desc, keep = lm.desc()
+        return nbytes, lambda tail: N.lib().s2t_ctc_prefix_beam_ngram(
+            lm_desc, N.fp(x), N.lp(n), B, T, V, int(blank), beam, topk, float(lm_weight), int(lm.start_ctx), *tail), keep
+    return _whole_utterance("s2t_ctc_prefix_beam_ngram", "device CTC prefix beam search", logits, lengths, plan,
+                            lm_score=True)
 
 
 def _logaddexp(a, b):
@@ -215,12 +260,7 @@ def _logaddexp(a, b):
     return hi + math.log1p(math.exp(lo - hi))
 
 
-def _is_ngram(lm):
-    from speech2text_amd.model.lm.ngram_lm import NgramLm
-    return isinstance(lm, NgramLm)
-
-
-class CtcPrefixBeamDecoding(DecodingMethod):
+class CtcPrefixBeamDecoding(_BatchDecoding):
     """Lexicon-free CTC prefix beam search (the reference's CTC beam decoder wraps a lexicon decoder of
     a library that is not here; this one searches the model's own classes).  A live prefix carries
     the log-probabilities of its alignments ending in blank and in a non-blank; per frame the
@@ -243,9 +283,7 @@ class CtcPrefixBeamDecoding(DecodingMethod):
         self._cutoff_top_k = int(cutoff_top_k)
         self._lm = lm
         self._lm_weight = float(lm_weight)
-        self._lm_start_token = None if lm_start_token is None else int(lm_start_token)
-        if self._lm_start_token is not None and self._lm_start_token < 0:
-            raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
+        self._lm_start_token = None if lm_start_token is None else _lm_start_arg(lm_start_token)
         if self._beam_size < 1 or self._cutoff_top_k < 1:
             raise ValueError(f"beam_size and cutoff_top_k must be at least 1, got {beam_size!r}, {cutoff_top_k!r}")
         if self._lm_start_token is not None and _is_ngram(lm):
@@ -340,12 +378,7 @@ class CtcPrefixBeamDecoding(DecodingMethod):
         with an LM its lm_score (B).  The fused device search where it applies (and `fused` is left
         on), else the host loop per utterance."""
         dev = hidden_states.device
-        if isinstance(self._lm, torch.nn.Module):
-            p = next(self._lm.parameters(), None)
-            if p is not None and p.device != dev:
-                self._lm.to(dev)
-        elif _is_ngram(self._lm):
-            self._lm.to(dev)
+        _lm_follows(self._lm, dev)
         if fused:
             out = self._fused(hidden_states, inputs_length)
             if out is not None:
@@ -368,12 +401,6 @@ class CtcPrefixBeamDecoding(DecodingMethod):
         out = self.beam_tokens(hidden_states, inputs_length)
         return _to_texts(out[0], out[1], self._tokenizer)
 
-    @torch.no_grad()
-    def decode(self, hidden_states: torch.Tensor) -> str:
-        assert hidden_states.shape[0] == 1, "Support BatchSize = 1 only."
-        n = torch.tensor([hidden_states.shape[1]], dtype=torch.int64)
-        return self.decode_batch(hidden_states, n)[0]
-
 
 def _is_lstm_pair(predictor, joiner):
     """The modules csrc/decode_lstm.hip serves: LstmPredictor + Joiner (any out-projection)."""
@@ -382,20 +409,24 @@ def _is_lstm_pair(predictor, joiner):
     return isinstance(getattr(predictor, "predictor", predictor), LstmPredictor) and isinstance(joiner, Joiner)
 
 
-def rnnt_lstm_desc(predictor, joiner):
-    """-> (S2tRnntLstmDesc of the two modules' fp32 device parameters, the tensors it points to:
-    keep them alive while the descriptor is in use)."""
-    import ctypes
-    p = getattr(predictor, "predictor", predictor)._predictor
-    keep = []
-
+def _kept_f32(keep, address=N.fp):
+    """-> a(t): the address of t detached, contiguous and fp32 (t itself where it is that already), which is
+    appended to `keep`; None stays None.  N.fp raises for a tensor off the device."""
     def a(t):
         if t is None:
             return None
         t = t.detach().contiguous().float()
         keep.append(t)
-        return N.fp(t)
+        return address(t)
+    return a
 
+
+def rnnt_lstm_desc(predictor, joiner):
+    """-> (S2tRnntLstmDesc of the two modules' fp32 device parameters, the tensors it points to:
+    keep them alive while the descriptor is in use)."""
+    p = getattr(predictor, "predictor", predictor)._predictor
+    keep = []
+    a = _kept_f32(keep)
     d = N.struct("S2tRnntLstmDesc")()
     layers = list(p.lstm_layers)
     if len(layers) > N.const("S2T_RNNT_LSTM_MAX_LAYERS") or p.embedding.num_embeddings < joiner._output_dim:
@@ -425,82 +456,45 @@ def rnnt_lstm_desc(predictor, joiner):
     return ctypes.byref(d), keep
 
 
-def _lstm_workspace(desc, B, T, beam, dev):
-    n = N.lib().s2t_rnnt_lstm_workspace_bytes(desc, B, T, beam) if desc is not None else 0
-    return None if n <= 0 else torch.empty((n,), dtype=torch.uint8, device=dev)
-
-
-def _beam_outputs(B, T, dev):
-    """Zeroed outputs of a whole-utterance beam search: tokens, frames (B,T), out_len (B) int64, score (B) fp32."""
-    return (torch.zeros((B, T), dtype=torch.int64, device=dev), torch.zeros((B, T), dtype=torch.int64, device=dev),
-            torch.zeros((B,), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.float32, device=dev))
+def _beam_in_range(beam):
+    return 1 <= beam <= N.const("S2T_RNNT_LSTM_MAX_BEAM")
 
 
 def rnnt_greedy_lstm_tokens_from_am(am, lengths, predictor, joiner, max_token_step=10):
     """Lockstep device greedy search on a given am = joiner._enc_proj(encoder_out), (B,T,V) fp32, LSTM
     predictor.  -> (tokens (B, T (max_token_step + 1)) int64, out_len (B) int64), or None when the
     kernels do not take the shape (the caller runs the module loop).  HIP: decode_lstm.hip."""
-    if not am.is_cuda:
-        raise RuntimeError("the device RNN-T greedy search runs on the GPU only")
-    am = am.contiguous().float()
-    B, T, V = am.shape
-    dev = am.device
-    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
-    tokens = torch.zeros((B, T * (int(max_token_step) + 1)), dtype=torch.int64, device=dev)
-    out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
-    if B == 0 or T == 0:
-        return tokens, out_len
-    desc, keep = rnnt_lstm_desc(predictor, joiner)
-    ws = _lstm_workspace(desc, B, T, 0, dev)
-    if ws is None or max_token_step < 0:
-        return None
-    rc = N.lib().s2t_rnnt_greedy_lstm(desc, N.fp(am), N.lp(lengths), B, T, int(max_token_step),
-                                      N.ptr(ws), N.lp(tokens), N.lp(out_len), N.stream())
-    if rc == -1:
-        return None
-    N.check(rc, "s2t_rnnt_greedy_lstm")
-    return tokens, out_len
+    def plan(am, n):
+        B, T, _ = am.shape
+        desc, keep = rnnt_lstm_desc(predictor, joiner)
+        nbytes = N.lib().s2t_rnnt_lstm_workspace_bytes(desc, B, T, 0) if desc is not None else 0
+        if nbytes <= 0 or max_token_step < 0:
+            return None
+        return nbytes, lambda tail: N.lib().s2t_rnnt_greedy_lstm(desc, N.fp(am), N.lp(n), B, T, int(max_token_step),
+                                                                 *tail), keep
+    return _whole_utterance("s2t_rnnt_greedy_lstm", "device RNN-T greedy search", am, lengths, plan, score=False,
+                            per_frame=int(max_token_step) + 1)
 
 
 def rnnt_beam_lstm_tokens_from_am(am, lengths, predictor, joiner, beam_size=4, cutoff_top_k=4):
     """rnnt_beam_tokens_from_am for the LSTM predictor (joiner with or without out-projection):
     same outputs, or None when the kernels do not take the shape.  HIP: decode_lstm.hip."""
-    if not am.is_cuda:
-        raise RuntimeError("the device RNN-T beam search runs on the GPU only")
-    am = am.contiguous().float()
-    B, T, V = am.shape
-    dev = am.device
-    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
-    tokens, frames, out_len, score = out = _beam_outputs(B, T, dev)
-    if B == 0 or T == 0:
-        return out
-    desc, keep = rnnt_lstm_desc(predictor, joiner)
-    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
-    if not 1 <= beam_size <= N.const("S2T_RNNT_LSTM_MAX_BEAM"):
-        return None
-    ws = _lstm_workspace(desc, B, T, beam_size, dev)
-    if ws is None:
-        return None
-    rc = N.lib().s2t_rnnt_beam_lstm(desc, N.fp(am), N.lp(lengths), B, T, beam_size, cutoff_top_k,
-                                    N.ptr(ws), N.lp(tokens), N.lp(frames), N.lp(out_len), N.fp(score),
-                                    N.stream())
-    if rc == -1:
-        return None
-    N.check(rc, "s2t_rnnt_beam_lstm")
-    return tokens, frames, out_len, score
+    def plan(am, n):
+        B, T, _ = am.shape
+        desc, keep = rnnt_lstm_desc(predictor, joiner)
+        beam, topk = int(beam_size), int(cutoff_top_k)
+        if desc is None or not _beam_in_range(beam):
+            return None
+        return N.lib().s2t_rnnt_lstm_workspace_bytes(desc, B, T, beam), lambda tail: N.lib().s2t_rnnt_beam_lstm(
+            desc, N.fp(am), N.lp(n), B, T, beam, topk, *tail), keep
+    return _whole_utterance("s2t_rnnt_beam_lstm", "device RNN-T beam search", am, lengths, plan, frames=True)
 
 
 def rnn_lm_desc(lm):
     """-> (S2tRnnLmDesc of an RnnLm's fp32 device parameters, the tensors it points to: keep them
     alive while the descriptor is in use).  A layer's two biases are summed once into a kept tensor."""
-    import ctypes
     keep = []
-
-    def a(t):
-        t = t.detach().contiguous().float()
-        keep.append(t)
-        return N.fp(t)
-
+    a = _kept_f32(keep)
     st = lm._rnn_layer
     if st.num_layers > N.const("S2T_RNNT_LSTM_MAX_LAYERS"):
         return None, keep
@@ -523,35 +517,19 @@ def rnnt_beam_lstm_lm_tokens_from_am(am, lengths, predictor, joiner, lm, lm_weig
     state and the first token carries no LM term (RnnLm.score's convention); a token: the LM is first
     stepped on it.  -> (tokens, frames, out_len, score, lm_score (B) fp32: the best beam's unweighted
     LM sum), or None when the kernels do not take the shape.  HIP: decode_lstm.hip."""
-    if not am.is_cuda:
-        raise RuntimeError("the device RNN-T beam search runs on the GPU only")
-    am = am.contiguous().float()
-    B, T, V = am.shape
-    dev = am.device
-    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
-    out = _beam_outputs(B, T, dev) + (torch.zeros((B,), dtype=torch.float32, device=dev),)
-    if B == 0 or T == 0:
-        return out
-    desc, keep = rnnt_lstm_desc(predictor, joiner)
-    lm_desc, lm_keep = rnn_lm_desc(lm)
-    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
-    start = -1 if lm_start_token is None else int(lm_start_token)
-    if lm_start_token is not None and start < 0:
-        raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
-    if desc is None or lm_desc is None or not 1 <= beam_size <= N.const("S2T_RNNT_LSTM_MAX_BEAM"):
-        return None
-    n = N.lib().s2t_rnnt_beam_lstm_lm_workspace_bytes(desc, lm_desc, B, T, beam_size)
-    if n <= 0:
-        return None
-    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
-    tokens, frames, out_len, score, lm_score = out
-    rc = N.lib().s2t_rnnt_beam_lstm_lm(desc, lm_desc, N.fp(am), N.lp(lengths), B, T, beam_size, cutoff_top_k,
-                                       float(lm_weight), start, N.ptr(ws), N.lp(tokens), N.lp(frames),
-                                       N.lp(out_len), N.fp(score), N.fp(lm_score), N.stream())
-    if rc == -1:
-        return None
-    N.check(rc, "s2t_rnnt_beam_lstm_lm")
-    return out
+    def plan(am, n):
+        B, T, _ = am.shape
+        desc, keep = rnnt_lstm_desc(predictor, joiner)
+        lm_desc, lm_keep = rnn_lm_desc(lm)
+        beam, topk = int(beam_size), int(cutoff_top_k)
+        start = _lm_start_arg(lm_start_token)
+        if desc is None or lm_desc is None or not _beam_in_range(beam):
+            return None
+        return N.lib().s2t_rnnt_beam_lstm_lm_workspace_bytes(desc, lm_desc, B, T, beam), \
+            lambda tail: N.lib().s2t_rnnt_beam_lstm_lm(desc, lm_desc, N.fp(am), N.lp(n), B, T, beam, topk,
+                                                       float(lm_weight), start, *tail), (keep, lm_keep)
+    return _whole_utterance("s2t_rnnt_beam_lstm_lm", "device RNN-T beam search", am, lengths, plan, frames=True,
+                            lm_score=True)
 
 
 def rnnt_beam_lstm_ngram_tokens_from_am(am, lengths, predictor, joiner, lm, lm_weight, beam_size=4, cutoff_top_k=4):
@@ -560,35 +538,19 @@ def rnnt_beam_lstm_ngram_tokens_from_am(am, lengths, predictor, joiner, lm, lm_w
     launch and no LM step.  The search starts in the LM's own start context, so the first token is scored
     too.  -> (tokens, frames, out_len, score, lm_score (B) fp32: the best beam's unweighted LM sum), or
     None where the entry refuses.  HIP: decode_lstm.hip, ngram_lookup.h."""
-    if not am.is_cuda:
-        raise RuntimeError("the device RNN-T beam search runs on the GPU only")
-    am = am.contiguous().float()
-    B, T, V = am.shape
-    dev = am.device
-    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
-    out = _beam_outputs(B, T, dev) + (torch.zeros((B,), dtype=torch.float32, device=dev),)
-    if B == 0 or T == 0:
-        return out
-    if lm.device != dev:
-        raise RuntimeError(f"the n-gram tables are on {lm.device}, am on {dev}: NgramLm.to(device)")
-    desc, keep = rnnt_lstm_desc(predictor, joiner)
-    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
-    if desc is None or lm.dtype != torch.float32:
-        return None
-    lm_desc, lm_keep = lm.desc()
-    n = N.lib().s2t_rnnt_beam_lstm_ngram_workspace_bytes(desc, lm_desc, B, T, beam_size)
-    if n <= 0:
-        return None
-    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
-    tokens, frames, out_len, score, lm_score = out
-    rc = N.lib().s2t_rnnt_beam_lstm_ngram(desc, lm_desc, N.fp(am), N.lp(lengths), B, T, beam_size, cutoff_top_k,
-                                          float(lm_weight), int(lm.start_ctx), N.ptr(ws), N.lp(tokens),
-                                          N.lp(frames), N.lp(out_len), N.fp(score), N.fp(lm_score), N.stream())
-    del keep, lm_keep
-    if rc == -1:
-        return None
-    N.check(rc, "s2t_rnnt_beam_lstm_ngram")
-    return out
+    def plan(am, n):
+        B, T, _ = am.shape
+        _ngram_beside(lm, am, "am")
+        desc, keep = rnnt_lstm_desc(predictor, joiner)
+        beam, topk = int(beam_size), int(cutoff_top_k)
+        if desc is None or lm.dtype != torch.float32:
+            return None
+        lm_desc, lm_keep = lm.desc()
+        return N.lib().s2t_rnnt_beam_lstm_ngram_workspace_bytes(desc, lm_desc, B, T, beam), \
+            lambda tail: N.lib().s2t_rnnt_beam_lstm_ngram(desc, lm_desc, N.fp(am), N.lp(n), B, T, beam, topk,
+                                                          float(lm_weight), int(lm.start_ctx), *tail), (keep, lm_keep)
+    return _whole_utterance("s2t_rnnt_beam_lstm_ngram", "device RNN-T beam search", am, lengths, plan, frames=True,
+                            lm_score=True)
 
 
 def _is_stateless_pair(predictor, joiner):
@@ -602,17 +564,11 @@ def rnnt_stateless_desc(predictor, joiner):
     """rnnt_lstm_desc for the stateless predictor -> (S2tRnntStatelessDesc of the two modules' fp32
     parameters, the tensors it points to: keep them alive while the descriptor is in use), or
     (None, []) for anything that is not StatelessPredictor + Joiner."""
-    import ctypes
     keep = []
     if not _is_stateless_pair(predictor, joiner):
         return None, keep
     p = getattr(predictor, "predictor", predictor)
-
-    def a(t):
-        t = t.detach().contiguous().float()
-        keep.append(t)
-        return t.data_ptr()
-
+    a = _kept_f32(keep, torch.Tensor.data_ptr)             # (host modules describe too: the searches check)
     if p._embedding.num_embeddings < joiner._output_dim:   # (every class must have an embedding row)
         return None, keep
     d = N.struct("S2tRnntStatelessDesc")()
@@ -635,37 +591,21 @@ def rnnt_beam_stateless_lm_tokens_from_am(am, lengths, predictor, joiner, lm, lm
     out-projection): the same lockstep rounds, LM step and outputs, the predictor step being one row
     kernel and two tiled products.  -> (tokens, frames, out_len, score, lm_score), or None when the
     kernels do not take the modules or the shape.  HIP: decode_lstm.hip."""
-    if not am.is_cuda:
-        raise RuntimeError("the device RNN-T beam search runs on the GPU only")
-    am = am.contiguous().float()
-    B, T, V = am.shape
-    dev = am.device
-    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
-    out = _beam_outputs(B, T, dev) + (torch.zeros((B,), dtype=torch.float32, device=dev),)
-    if B == 0 or T == 0:
-        return out
-    start = -1 if lm_start_token is None else int(lm_start_token)
-    if lm_start_token is not None and start < 0:
-        raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
-    desc, keep = rnnt_stateless_desc(predictor, joiner)
-    lm_desc, lm_keep = rnn_lm_desc(lm)
-    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
-    if desc is None or lm_desc is None or not 1 <= beam_size <= N.const("S2T_RNNT_LSTM_MAX_BEAM"):
-        return None
-    if any(not t.is_cuda for t in keep[:-1]):
-        raise RuntimeError("the device RNN-T beam search runs on the GPU only: the modules are not on it")
-    n = N.lib().s2t_rnnt_beam_stateless_lm_workspace_bytes(desc, lm_desc, B, T, beam_size)
-    if n <= 0:
-        return None
-    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
-    tokens, frames, out_len, score, lm_score = out
-    rc = N.lib().s2t_rnnt_beam_stateless_lm(desc, lm_desc, N.fp(am), N.lp(lengths), B, T, beam_size, cutoff_top_k,
-                                            float(lm_weight), start, N.ptr(ws), N.lp(tokens), N.lp(frames),
-                                            N.lp(out_len), N.fp(score), N.fp(lm_score), N.stream())
-    if rc == -1:
-        return None
-    N.check(rc, "s2t_rnnt_beam_stateless_lm")
-    return out
+    def plan(am, n):
+        B, T, _ = am.shape
+        start = _lm_start_arg(lm_start_token)
+        desc, keep = rnnt_stateless_desc(predictor, joiner)
+        lm_desc, lm_keep = rnn_lm_desc(lm)
+        beam, topk = int(beam_size), int(cutoff_top_k)
+        if desc is None or lm_desc is None or not _beam_in_range(beam):
+            return None
+        if any(not t.is_cuda for t in keep[:-1]):
+            raise RuntimeError("the device RNN-T beam search runs on the GPU only: the modules are not on it")
+        return N.lib().s2t_rnnt_beam_stateless_lm_workspace_bytes(desc, lm_desc, B, T, beam), \
+            lambda tail: N.lib().s2t_rnnt_beam_stateless_lm(desc, lm_desc, N.fp(am), N.lp(n), B, T, beam, topk,
+                                                            float(lm_weight), start, *tail), (keep, lm_keep)
+    return _whole_utterance("s2t_rnnt_beam_stateless_lm", "device RNN-T beam search", am, lengths, plan, frames=True,
+                            lm_score=True)
 
 
 def _am_per_utterance(joiner, hidden_states, inputs_length):
@@ -707,23 +647,17 @@ class RnntGreedyDecoding(DecodingMethod):
 
     def greedy_tokens(self, hidden_states, inputs_length):
         """(B,T,D) encoder output -> (tokens (B,max_out), out_len (B)); fused device search."""
-        p = getattr(self._predictor, "predictor", self._predictor)
-        j = self._joiner
-        am = j._enc_proj(hidden_states).contiguous().float()          # (B,T,V), one GEMM
+        am = self._joiner._enc_proj(hidden_states).contiguous().float()          # (B,T,V), one GEMM
         B, T, V = am.shape
         dev = am.device
-        lengths = inputs_length.to(device=dev, dtype=torch.int64).contiguous()
+        n = inputs_length.to(device=dev, dtype=torch.int64).contiguous()
         max_out = T * (self._max_token_step + 1)
         tokens = torch.zeros((B, max_out), dtype=torch.int64, device=dev)
         out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
-        conv_w = p._conv.weight.reshape(p._embedding_dim, p._context_size).contiguous()
+        w, E, D, ctx, act = _stateless_weights(self._predictor, self._joiner)
         N.check(N.lib().s2t_rnnt_greedy_stateless(
-            N.fp(am), N.lp(lengths), N.fp(p._embedding.weight.contiguous()), N.fp(conv_w),
-            N.fp(p._output_linear.weight.contiguous()), N.fp(p._output_linear.bias.contiguous()),
-            N.fp(j._pre_proj.weight.contiguous()), N.fp(j._pre_proj.bias.contiguous()), B, T, V,
-            p._embedding_dim, p._output_dim, p._context_size, 0 if j._act_name == "relu" else 1,
-            int(self._max_token_step), max_out, 0, N.lp(tokens), N.lp(out_len), N.stream()),
-            "s2t_rnnt_greedy_stateless")
+            N.fp(am), N.lp(n), *[N.fp(t) for t in w], B, T, V, E, D, ctx, act, int(self._max_token_step), max_out, 0,
+            N.lp(tokens), N.lp(out_len), N.stream()), "s2t_rnnt_greedy_stateless")
         return tokens, out_len
 
     def _lstm_search(self):
@@ -781,47 +715,37 @@ class RnntGreedyDecoding(DecodingMethod):
         return self._tokenizer.decode(torch.tensor(out, dtype=torch.int64))
 
 
+def _stateless_weights(predictor, joiner, dev=None):
+    """The six parameter tensors of the one-workgroup searches (embedding, conv [E][ctx], linear w / b,
+    pre_proj w / b), fp32 and contiguous, on `dev` (None: where they are) -> (list, E, D, ctx, act).  The
+    only place that gathers them: the whole-utterance greedy and beam searches and the chunk-carried ones
+    call it.  A module held in another dtype is cast here (the greedy and the plain beam search used to
+    raise for one)."""
+    p = getattr(predictor, "predictor", predictor)
+    # .to() and .contiguous() return the tensor itself for an fp32 contiguous parameter that is on `dev`:
+    # the kernels then get the module's own pointers and a call makes no copy (the reshaped conv weight is
+    # a view of the parameter's storage)
+    f32 = lambda t: t.detach().to(device=dev or t.device, dtype=torch.float32).contiguous()   # noqa: E731
+    w = [f32(p._embedding.weight), f32(p._conv.weight.reshape(p._embedding_dim, p._context_size)),
+         f32(p._output_linear.weight), f32(p._output_linear.bias),
+         f32(joiner._pre_proj.weight), f32(joiner._pre_proj.bias)]
+    return w, p._embedding_dim, p._output_dim, p._context_size, 0 if joiner._act_name == "relu" else 1
+
+
 def rnnt_beam_tokens_from_am(am, lengths, predictor, joiner, beam_size=4, cutoff_top_k=4):
     """Fused device beam search on a given am = joiner._enc_proj(encoder_out), (B,T,V) fp32.
     -> (tokens (B,T) int64, frames (B,T) int64, out_len (B) int64, score (B) fp32): the best
     beam's tokens, the frame at which each was emitted, their count and the beam's score.
     Returns None when the kernel does not take the shape (rc -1: the caller runs the module
     loop).  HIP: decode_beam.hip."""
-    if not am.is_cuda:
-        raise RuntimeError("the fused RNN-T beam search runs on the GPU only")
-    p = getattr(predictor, "predictor", predictor)
-    am = am.contiguous().float()
-    B, T, V = am.shape
-    dev = am.device
-    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
-    tokens, frames, out_len, score = out = _beam_outputs(B, T, dev)
-    if B == 0 or T == 0:
-        return out
-    ws = torch.empty((max(1, N.lib().s2t_rnnt_beam_workspace_bytes(B, T, V, int(beam_size))),),
-                     dtype=torch.uint8, device=dev)
-    conv_w = p._conv.weight.reshape(p._embedding_dim, p._context_size).contiguous()
-    rc = N.lib().s2t_rnnt_beam_stateless(
-        N.fp(am), N.lp(lengths), N.fp(p._embedding.weight.contiguous()), N.fp(conv_w),
-        N.fp(p._output_linear.weight.contiguous()), N.fp(p._output_linear.bias.contiguous()),
-        N.fp(joiner._pre_proj.weight.contiguous()), N.fp(joiner._pre_proj.bias.contiguous()),
-        B, T, V, p._embedding_dim, p._output_dim, p._context_size,
-        0 if joiner._act_name == "relu" else 1, 0, int(beam_size), int(cutoff_top_k),
-        N.ptr(ws), N.lp(tokens), N.lp(frames), N.lp(out_len), N.fp(score), N.stream())
-    if rc == -1:
-        return None
-    N.check(rc, "s2t_rnnt_beam_stateless")
-    return tokens, frames, out_len, score
-
-
-def _stateless_weights(predictor, joiner, dev=None):
-    """The six parameter tensors of the one-workgroup searches (embedding, conv [E][ctx], linear w / b,
-    pre_proj w / b), fp32 and contiguous -> (list, E, D, ctx, act)."""
-    p = getattr(predictor, "predictor", predictor)
-    f32 = lambda t: t.detach().to(device=dev or t.device, dtype=torch.float32).contiguous()   # noqa: E731
-    w = [f32(p._embedding.weight), f32(p._conv.weight.reshape(p._embedding_dim, p._context_size)),
-         f32(p._output_linear.weight), f32(p._output_linear.bias),
-         f32(joiner._pre_proj.weight), f32(joiner._pre_proj.bias)]
-    return w, p._embedding_dim, p._output_dim, p._context_size, 0 if joiner._act_name == "relu" else 1
+    def plan(am, n):
+        B, T, V = am.shape
+        nbytes = max(1, N.lib().s2t_rnnt_beam_workspace_bytes(B, T, V, int(beam_size)))   # (the entry refuses, not this)
+        w, E, D, ctx, act = _stateless_weights(predictor, joiner)
+        return nbytes, lambda tail: N.lib().s2t_rnnt_beam_stateless(
+            N.fp(am), N.lp(n), *[N.fp(t) for t in w], B, T, V, E, D, ctx, act, 0, int(beam_size), int(cutoff_top_k),
+            *tail), w
+    return _whole_utterance("s2t_rnnt_beam_stateless", "fused RNN-T beam search", am, lengths, plan, frames=True)
 
 
 def rnnt_beam_ngram_tokens_from_am(am, lengths, predictor, joiner, lm, lm_weight, beam_size=4, cutoff_top_k=4):
@@ -831,38 +755,23 @@ def rnnt_beam_ngram_tokens_from_am(am, lengths, predictor, joiner, lm, lm_weight
     look-up returned.  The search starts in the LM's own start context, so the first token is scored
     too.  -> (tokens, frames, out_len, score, lm_score (B) fp32: the best beam's unweighted LM sum), or
     None where the entry refuses.  HIP: decode_beam.hip, decode_search.h, ngram_lookup.h."""
-    if not am.is_cuda:
-        raise RuntimeError("the fused RNN-T beam search runs on the GPU only")
-    am = am.contiguous().float()
-    B, T, V = am.shape
-    dev = am.device
-    lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
-    tokens, frames, out_len, score = _beam_outputs(B, T, dev)
-    lm_score = torch.zeros((B,), dtype=torch.float32, device=dev)
-    out = (tokens, frames, out_len, score, lm_score)
-    if B == 0 or T == 0:
-        return out
-    if lm.device != dev:
-        raise RuntimeError(f"the n-gram tables are on {lm.device}, am on {dev}: NgramLm.to(device)")
-    beam_size, cutoff_top_k = int(beam_size), int(cutoff_top_k)
-    n = N.lib().s2t_rnnt_beam_ngram_workspace_bytes(B, T, V, beam_size)
-    if n <= 0:
-        return None
-    lm_desc, lm_keep = lm.desc()
-    ws = torch.empty((n,), dtype=torch.uint8, device=dev)
-    w, E, D, ctx, act = _stateless_weights(predictor, joiner)
-    rc = N.lib().s2t_rnnt_beam_stateless_ngram(
-        lm_desc, N.fp(am), N.lp(lengths), *[N.fp(t) for t in w], B, T, V, E, D, ctx, act, 0, beam_size,
-        cutoff_top_k, float(lm_weight), int(lm.start_ctx), N.ptr(ws), N.lp(tokens), N.lp(frames), N.lp(out_len),
-        N.fp(score), N.fp(lm_score), N.stream())
-    del lm_keep
-    if rc == -1:
-        return None
-    N.check(rc, "s2t_rnnt_beam_stateless_ngram")
-    return out
+    def plan(am, n):
+        B, T, V = am.shape
+        _ngram_beside(lm, am, "am")
+        beam, topk = int(beam_size), int(cutoff_top_k)
+        nbytes = N.lib().s2t_rnnt_beam_ngram_workspace_bytes(B, T, V, beam)
+        if nbytes <= 0:
+            return None
+        lm_desc, lm_keep = lm.desc()
+        w, E, D, ctx, act = _stateless_weights(predictor, joiner)
+        return nbytes, lambda tail: N.lib().s2t_rnnt_beam_stateless_ngram(
+            lm_desc, N.fp(am), N.lp(n), *[N.fp(t) for t in w], B, T, V, E, D, ctx, act, 0, beam, topk,
+            float(lm_weight), int(lm.start_ctx), *tail), (w, lm_keep)
+    return _whole_utterance("s2t_rnnt_beam_stateless_ngram", "fused RNN-T beam search", am, lengths, plan,
+                            frames=True, lm_score=True)
 
 
-class RnntBeamDecoding(DecodingMethod):
+class RnntBeamDecoding(_BatchDecoding):
     """Beam search of the RNN-T (reference :295-425): at most one symbol per frame per beam, the
     `cutoff_top_k` best classes of every beam are expanded, the `beam_size` best candidates
     survive, equal hypotheses are not merged.  The orders the reference leaves to its library are
@@ -891,9 +800,7 @@ class RnntBeamDecoding(DecodingMethod):
         self._cutoff_top_k = cutoff_top_k
         self._lm = lm
         self._lm_weight = float(lm_weight)
-        self._lm_start_token = None if lm_start_token is None else int(lm_start_token)
-        if self._lm_start_token is not None and self._lm_start_token < 0:
-            raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
+        self._lm_start_token = None if lm_start_token is None else _lm_start_arg(lm_start_token)
         assert hasattr(self._predictor, "streaming_step") and hasattr(self._joiner, "streaming_step"), \
             "Predictor and Joiner should impl streaming_step for decoding."
 
@@ -985,78 +892,43 @@ class RnntBeamDecoding(DecodingMethod):
         return list(beams[0][0]), list(beams[0][1]), float(scores[0]), float(lm_sums[0])
 
     def _lm_to(self, dev):
-        """The LM follows the inputs to their device on first use (the task does not own it)."""
-        if isinstance(self._lm, torch.nn.Module):
-            p = next(self._lm.parameters(), None)
-            if p is not None and p.device != dev:
-                self._lm.to(dev)
-        elif _is_ngram(self._lm):
-            self._lm.to(dev)
+        _lm_follows(self._lm, dev)
+
+    def _device_searches(self):
+        """The fused searches in the order they are tried: (serves these modules and this LM?, am formed for
+        the whole batch by one _enc_proj (else per utterance, the lockstep searches' am), the
+        whole-utterance function, its arguments after the modules).  A new search is a row here."""
+        from speech2text_amd.model.lm.rnn_lm import RnnLm
+        lm, lstm, sizes = self._lm, self._lstm_search(), (self._beam_size, self._cutoff_top_k)
+        if lm is None:
+            return [(self._fusable(), True, rnnt_beam_tokens_from_am, sizes),
+                    (lstm, False, rnnt_beam_lstm_tokens_from_am, sizes)]
+        rnn = isinstance(lm, RnnLm)
+        ngram = _is_ngram(lm) and self._lm_start_token is None and lm.dtype == torch.float32
+        fused_lm, started = (lm, self._lm_weight) + sizes, (self._lm_start_token,)
+        return [(lstm and rnn, False, rnnt_beam_lstm_lm_tokens_from_am, fused_lm + started),
+                (lstm and ngram, False, rnnt_beam_lstm_ngram_tokens_from_am, fused_lm),
+                (rnn and _is_stateless_pair(self._predictor, self._joiner), False,
+                 rnnt_beam_stateless_lm_tokens_from_am, fused_lm + started),
+                (ngram and self._fusable(), True, rnnt_beam_ngram_tokens_from_am, fused_lm)]
 
     @torch.no_grad()
     def beam_tokens(self, hidden_states, inputs_length, fused=True):
         """(B,T,D) encoder output -> (tokens (B,T), frames (B,T), out_len (B), score (B)) of the
         best beam per utterance, and with an LM its lm_score (B).  The fused device search where the
         modules allow it (and `fused` is left on), else the module loop per utterance."""
-        if self._lm is not None:
-            return self._beam_tokens_lm(hidden_states, inputs_length, fused)
-        if fused and self._fusable() and hidden_states.is_cuda:
-            am = self._joiner._enc_proj(hidden_states)                # (B,T,V), one GEMM
-            out = rnnt_beam_tokens_from_am(am, inputs_length, self._predictor, self._joiner,
-                                           self._beam_size, self._cutoff_top_k)
-            if out is not None:
-                return out
-        if fused and self._lstm_search() and hidden_states.is_cuda:
-            am, lens = _am_per_utterance(self._joiner, hidden_states, inputs_length)
-            out = rnnt_beam_lstm_tokens_from_am(am, lens, self._predictor, self._joiner,
-                                                self._beam_size, self._cutoff_top_k)
-            if out is not None:
-                return out
-        B, T = hidden_states.shape[0], hidden_states.shape[1]
-        tokens = torch.zeros((B, T), dtype=torch.int64)
-        frames = torch.zeros((B, T), dtype=torch.int64)
-        out_len = torch.zeros((B,), dtype=torch.int64)
-        score = torch.zeros((B,), dtype=torch.float32)
-        for b in range(B):
-            n = max(0, min(int(inputs_length[b]), T))
-            tok, frm, score[b] = self._module_loop(hidden_states[b:b + 1, :n, :])
-            out_len[b] = len(tok)
-            tokens[b, :len(tok)] = torch.tensor(tok, dtype=torch.int64)
-            frames[b, :len(frm)] = torch.tensor(frm, dtype=torch.int64)
-        dev = hidden_states.device
-        return tokens.to(dev), frames.to(dev), out_len.to(dev), score.to(dev)
-
-    def _beam_tokens_lm(self, hidden_states, inputs_length, fused):
-        from speech2text_amd.model.lm.rnn_lm import RnnLm
-        dev = hidden_states.device
-        self._lm_to(dev)
-        if fused and self._lstm_search() and isinstance(self._lm, RnnLm) and hidden_states.is_cuda:
-            am, lens = _am_per_utterance(self._joiner, hidden_states, inputs_length)
-            out = rnnt_beam_lstm_lm_tokens_from_am(am, lens, self._predictor, self._joiner, self._lm,
-                                                   self._lm_weight, self._beam_size, self._cutoff_top_k,
-                                                   self._lm_start_token)
-            if out is not None:
-                return out
-        if fused and self._lstm_search() and _is_ngram(self._lm) and self._lm_start_token is None \
-                and hidden_states.is_cuda and self._lm.dtype == torch.float32:
-            am, lens = _am_per_utterance(self._joiner, hidden_states, inputs_length)
-            out = rnnt_beam_lstm_ngram_tokens_from_am(am, lens, self._predictor, self._joiner, self._lm,
-                                                      self._lm_weight, self._beam_size, self._cutoff_top_k)
-            if out is not None:
-                return out
-        if fused and _is_stateless_pair(self._predictor, self._joiner) and isinstance(self._lm, RnnLm) \
-                and hidden_states.is_cuda:
-            am, lens = _am_per_utterance(self._joiner, hidden_states, inputs_length)
-            out = rnnt_beam_stateless_lm_tokens_from_am(am, lens, self._predictor, self._joiner, self._lm,
-                                                        self._lm_weight, self._beam_size, self._cutoff_top_k,
-                                                        self._lm_start_token)
-            if out is not None:
-                return out
-        if fused and self._fusable() and _is_ngram(self._lm) and self._lm_start_token is None \
-                and hidden_states.is_cuda and self._lm.dtype == torch.float32:
-            am = self._joiner._enc_proj(hidden_states)                # (B,T,V), one GEMM
-            out = rnnt_beam_ngram_tokens_from_am(am, inputs_length, self._predictor, self._joiner, self._lm,
-                                                 self._lm_weight, self._beam_size, self._cutoff_top_k)
+        dev, with_lm = hidden_states.device, self._lm is not None
+        if with_lm:
+            self._lm_to(dev)
+        searches = self._device_searches() if fused and hidden_states.is_cuda else []
+        for serves, whole_batch, search, args in searches:
+            if not serves:
+                continue
+            if whole_batch:
+                am, lens = self._joiner._enc_proj(hidden_states), inputs_length   # (B,T,V), one GEMM
+            else:
+                am, lens = _am_per_utterance(self._joiner, hidden_states, inputs_length)
+            out = search(am, lens, self._predictor, self._joiner, *args)
             if out is not None:
                 return out
         B, T = hidden_states.shape[0], hidden_states.shape[1]
@@ -1067,27 +939,30 @@ class RnntBeamDecoding(DecodingMethod):
         lm_score = torch.zeros((B,), dtype=torch.float32)
         for b in range(B):
             n = max(0, min(int(inputs_length[b]), T))
-            tok, frm, score[b], lm_score[b] = self._module_loop_lm(hidden_states[b:b + 1, :n, :])
+            if with_lm:
+                tok, frm, score[b], lm_score[b] = self._module_loop_lm(hidden_states[b:b + 1, :n, :])
+            else:
+                tok, frm, score[b] = self._module_loop(hidden_states[b:b + 1, :n, :])
             out_len[b] = len(tok)
             tokens[b, :len(tok)] = torch.tensor(tok, dtype=torch.int64)
             frames[b, :len(frm)] = torch.tensor(frm, dtype=torch.int64)
-        return tokens.to(dev), frames.to(dev), out_len.to(dev), score.to(dev), lm_score.to(dev)
+        out = (tokens.to(dev), frames.to(dev), out_len.to(dev), score.to(dev))
+        return out + (lm_score.to(dev),) if with_lm else out
 
     @torch.no_grad()
     def decode_batch(self, hidden_states, inputs_length):
         out = self.beam_tokens(hidden_states, inputs_length)
         return _to_texts(out[0], out[2], self._tokenizer)
 
-    @torch.no_grad()
-    def decode(self, hidden_states: torch.Tensor) -> str:
-        assert hidden_states.shape[0] == 1, "Support BatchSize = 1 only."
-        n = torch.tensor([hidden_states.shape[1]], dtype=torch.int64)
-        return self.decode_batch(hidden_states, n)[0]
+
+def _method_arg(method):
+    if method not in ("greedy", "beam"):
+        raise ValueError(f"method must be 'greedy' or 'beam', got {method!r}")
+    return method
 
 
 def _stream_lm_arguments(lm, lm_weight, lm_start_token, method):
     """The LM arguments of a chunk-carried search, checked -> (lm, lm_weight, the C start token)."""
-    import math
     if lm is None:
         return None, 0.0, -1
     from speech2text_amd.model.lm.rnn_lm import RnnLm
@@ -1101,61 +976,94 @@ def _stream_lm_arguments(lm, lm_weight, lm_start_token, method):
     if not isinstance(lm, RnnLm):
         raise ValueError(f"the chunk-carried search is fused with an RnnLm only, got {type(lm).__name__} "
                          "(there is no module-loop fallback here)")
-    start = -1 if lm_start_token is None else int(lm_start_token)
-    if lm_start_token is not None and start < 0:
-        raise ValueError(f"lm_start_token must be None or a token id, got {lm_start_token!r}")
+    start = _lm_start_arg(lm_start_token)
     if not math.isfinite(float(lm_weight)):
         raise ValueError(f"lm_weight must be finite, got {lm_weight!r}")
     return lm, float(lm_weight), start
 
 
 class _ChunkCarriedSearch:
-    """What the two chunk-carried searches share: the settings, the fixed output tensors, `reset`
-    and `step` around the library calls.  A subclass says which modules it takes (`_check_modules`),
-    which shapes, and where its state lives (`_allocate`), and makes the calls (`_reset_state`,
-    `_chunk`)."""
+    """What every chunk-carried search is, RNN-T or CTC: the settings, the fixed output tensors (`frames`
+    for RNN-T only, `lm_score` with an LM, else None), `reset` and `step` around the library calls.  A
+    subclass' __init__ hands its arguments to `_construct`; it says what it takes and which class count
+    follows (`_check_modules`), which shapes, and where its state and workspace live (`_allocate`: `state`,
+    `_ws` and its descriptors), and makes the calls (`_reset_state`, `_chunk`).  `_lm_arguments` checks the
+    LM (an RnnLm here; the n-gram classes override it) and `_views` is what `step` returns."""
 
-    def __init__(self, predictor, joiner, batch_size=1, method="greedy", max_token_step=5,
-                 beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None):
-        if method not in ("greedy", "beam"):
-            raise ValueError(f"method must be 'greedy' or 'beam', got {method!r}")
-        on_gpu = self._check_modules(predictor, joiner)
+    _input, _has_frames = "am", True                       # (the CTC classes: "logits", no frames)
+
+    def _construct(self, what, batch_size, method, beam_size, cutoff_top_k, max_tokens, device, lm=None,
+                   lm_weight=0.0, lm_start_token=None):
+        """what: the arguments of _check_modules and _allocate, (predictor, joiner) or (num_classes,)."""
+        self._lm, self._lm_weight, self._lm_start = self._lm_arguments(lm, lm_weight, lm_start_token, method)
+        self.method = _method_arg(method)
+        self.V, on_gpu = self._check_modules(*what)
         dev = torch.device("cuda") if device is None else torch.device(device)
         if dev.type != "cuda" or any(t.device.type != "cuda" for t in on_gpu):
-            raise RuntimeError("the chunk-carried search runs on the GPU only: modules and device must be cuda")
-        self.method, self.batch_size, self.max_tokens = method, int(batch_size), int(max_tokens)
-        self.max_token_step = int(max_token_step)
-        self.beam_size = int(beam_size) if method == "beam" else 0
-        self.cutoff_top_k = int(cutoff_top_k)
-        self.V = joiner._output_dim
-        self._allocate(predictor, joiner, dev)             # raises for a shape the kernels refuse
+            raise RuntimeError("the chunk-carried search runs on the GPU only: modules, LM and device must be cuda")
+        self.batch_size, self.max_tokens = int(batch_size), int(max_tokens)
+        self.beam_size, self.cutoff_top_k = int(beam_size), int(cutoff_top_k)
+        self._ws = None
+        self._allocate(*what, dev)                         # raises for a shape the kernels refuse
         B = self.batch_size
         self.tokens = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
-        self.frames = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
+        self.frames = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev) if self._has_frames else None
         self.out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
         self.score = torch.zeros((B,), dtype=torch.float32, device=dev)
         self.stable_len = torch.zeros((B,), dtype=torch.int64, device=dev)
         self.overflow = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.lm_score = None if self._lm is None else torch.zeros((B,), dtype=torch.float32, device=dev)
+        self._outputs = [t for t in (self.tokens, self.frames, self.out_len, self.score, self.stable_len,
+                                     self.overflow, self.lm_score) if t is not None]
+        self._step_views = self._views()
         self._full = {}                                    # Tc -> chunk_len of a whole chunk
         self.reset()
 
+    def _construct_rnnt(self, predictor, joiner, batch_size, method, max_token_step, beam_size, cutoff_top_k,
+                        max_tokens, device, lm=None, lm_weight=0.0, lm_start_token=None):
+        """_construct with the settings of an RNN-T search: `max_token_step`, and beam_size 0 for greedy."""
+        self.max_token_step = int(max_token_step)
+        self._construct((predictor, joiner), batch_size, method, beam_size if method == "beam" else 0, cutoff_top_k,
+                        max_tokens, device, lm, lm_weight, lm_start_token)
+
+    def _lm_arguments(self, lm, lm_weight, lm_start_token, method):
+        return _stream_lm_arguments(lm, lm_weight, lm_start_token, method)
+
+    def _lm_on_gpu(self):
+        """The LM's tensors that must be on the GPU already (an n-gram's tables are copied over instead)."""
+        return [] if self._lm is None or _is_ngram(self._lm) else [self._lm._embedding.weight]
+
+    def _views(self):
+        if self.method == "greedy":
+            return self.tokens, self.out_len
+        return self.tokens, self.frames, self.out_len, self.score, self.stable_len
+
     def reset(self, rows=None):
-        """Rows (indices, or None for all) become the empty hypothesis; their outputs read zero
-        until their next chunk.  The others are not touched."""
-        mask = None
-        if rows is not None:
-            mask = torch.zeros((self.batch_size,), dtype=torch.int32)
-            mask[torch.as_tensor(rows, dtype=torch.int64)] = 1
-            mask = mask.to(self.state.device)
+        """Rows become the empty hypothesis; their outputs read zero until their next chunk.  The others
+        are not touched.  rows: None for all; a list of row indices (the mask is then built on the host
+        and copied over: not for a graph capture); or a device mask, an int32 tensor (B) on the search's
+        device with 1 for the rows to reset, which is used as it is -- then, as with None, reset
+        enqueues kernels only and can be captured."""
+        mask = self._reset_mask(rows)
         self._reset_state(mask)
-        outs = [self.tokens, self.frames, self.out_len, self.score, self.stable_len, self.overflow]
-        if getattr(self, "lm_score", None) is not None:    # (the searches with a language model)
-            outs.append(self.lm_score)
-        for t in outs:
+        for t in self._outputs:
             if mask is None:
                 t.zero_()
             else:
                 t.masked_fill_(mask.bool().reshape(-1, *[1] * (t.dim() - 1)), 0)
+
+    def _reset_mask(self, rows):
+        mask = None
+        if isinstance(rows, torch.Tensor) and rows.is_cuda:
+            if rows.dtype != torch.int32 or tuple(rows.shape) != (self.batch_size,):
+                raise ValueError(f"a device mask is int32 of shape ({self.batch_size},), got {rows.dtype} "
+                                 f"{tuple(rows.shape)}")
+            mask = rows.contiguous()
+        elif rows is not None:
+            mask = torch.zeros((self.batch_size,), dtype=torch.int32)
+            mask[torch.as_tensor(rows, dtype=torch.int64)] = 1
+            mask = mask.to(self.state.device)
+        return mask
 
     def step(self, am_chunk, chunk_len=None):
         """am_chunk (B, Tc, V) fp32 on the device, Tc <= 256; chunk_len (B) int64 on the device
@@ -1164,16 +1072,14 @@ class _ChunkCarriedSearch:
         B, V = self.batch_size, self.V
         if am_chunk.dim() != 3 or am_chunk.shape[0] != B or am_chunk.shape[2] != V \
                 or not 1 <= am_chunk.shape[1] <= 256:
-            raise ValueError(f"expected am of shape ({B}, 1..256, {V}), got {tuple(am_chunk.shape)}")
+            raise ValueError(f"expected {self._input} of shape ({B}, 1..256, {V}), got {tuple(am_chunk.shape)}")
         Tc = am_chunk.shape[1]
         if chunk_len is None:
             chunk_len = self._full.get(Tc)
             if chunk_len is None:
                 chunk_len = self._full[Tc] = torch.full((B,), Tc, dtype=torch.int64, device=self.state.device)
         self._chunk(am_chunk, chunk_len, Tc)
-        if self.method == "greedy":
-            return self.tokens, self.out_len
-        return self.tokens, self.frames, self.out_len, self.score, self.stable_len
+        return self._step_views
 
 
 class RnntStreamingSearch(_ChunkCarriedSearch):
@@ -1187,6 +1093,11 @@ class RnntStreamingSearch(_ChunkCarriedSearch):
     be captured into a graph.  There is no module-loop fallback: a predictor / joiner pair or a
     shape the fused search does not take is an error at construction."""
 
+    def __init__(self, predictor, joiner, batch_size=1, method="greedy", max_token_step=5,
+                 beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None):
+        self._construct_rnnt(predictor, joiner, batch_size, method, max_token_step, beam_size, cutoff_top_k,
+                             max_tokens, device)
+
     def _check_modules(self, predictor, joiner):
         from speech2text_amd.model.joiner.joiner import Joiner
         from speech2text_amd.model.predictor.predictor import StatelessPredictor
@@ -1197,13 +1108,11 @@ class RnntStreamingSearch(_ChunkCarriedSearch):
                              "RnntLstmStreamingSearch; rnnt_streaming_search picks the class)")
         if not isinstance(joiner, Joiner) or joiner._use_out_project:
             raise ValueError("the chunk-carried search takes a Joiner without output projection")
-        return [p._embedding.weight]
+        return joiner._output_dim, [p._embedding.weight]
 
     def _allocate(self, predictor, joiner, dev):
         p = getattr(predictor, "predictor", predictor)
-        self.E, self.D, self.ctx = p._embedding_dim, p._output_dim, p._context_size
-        self._act = 0 if joiner._act_name == "relu" else 1
-        B, V, E, D, ctx = self.batch_size, self.V, self.E, self.D, self.ctx
+        B, V, E, D, ctx = self.batch_size, self.V, p._embedding_dim, p._output_dim, p._context_size
         n = N.lib().s2t_rnnt_stream_state_bytes(B, V, ctx, self.beam_size, self.max_tokens) if B > 0 else 0
         if self.method == "beam":
             ok = 1 <= self.beam_size <= 16 and 1 <= min(self.cutoff_top_k, V) <= 16 \
@@ -1214,10 +1123,7 @@ class RnntStreamingSearch(_ChunkCarriedSearch):
             raise ValueError(f"the chunk-carried {self.method} search does not take this shape: B {B} V {V} "
                              f"E {E} D {D} ctx {ctx} beam {self.beam_size} top-k {self.cutoff_top_k} "
                              f"max_tokens {self.max_tokens} (limits: include/s2t_mi355.h)")
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        self._w = [f32(p._embedding.weight), f32(p._conv.weight.reshape(E, ctx)),
-                   f32(p._output_linear.weight), f32(p._output_linear.bias),
-                   f32(joiner._pre_proj.weight), f32(joiner._pre_proj.bias)]
+        self._w, self.E, self.D, self.ctx, self._act = _stateless_weights(predictor, joiner, dev)
         self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
 
     def _reset_state(self, mask):
@@ -1272,18 +1178,15 @@ class RnntLstmStreamingSearch(_ChunkCarriedSearch):
                  beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None, capturable=True, lm=None,
                  lm_weight=0.0, lm_start_token=None):
         self.capturable = bool(capturable)
-        self.lm_score = None
-        self._lm, self._lm_weight, self._lm_start = _stream_lm_arguments(lm, lm_weight, lm_start_token, method)
-        super().__init__(predictor, joiner, batch_size, method, max_token_step, beam_size, cutoff_top_k,
-                         max_tokens, device)
+        self._construct_rnnt(predictor, joiner, batch_size, method, max_token_step, beam_size, cutoff_top_k,
+                             max_tokens, device, lm, lm_weight, lm_start_token)
 
     def _check_modules(self, predictor, joiner):
         if not _is_lstm_pair(predictor, joiner):
             raise ValueError("RnntLstmStreamingSearch takes LstmPredictor + Joiner, got "
                              f"{type(getattr(predictor, 'predictor', predictor)).__name__} + "
                              f"{type(joiner).__name__} (the stateless predictor: RnntStreamingSearch)")
-        return [joiner._pre_proj.weight, next(predictor.parameters())] + \
-            ([] if self._lm is None else [self._lm._embedding.weight])
+        return joiner._output_dim, [joiner._pre_proj.weight, next(predictor.parameters())] + self._lm_on_gpu()
 
     def _allocate(self, predictor, joiner, dev):
         B, V = self.batch_size, self.V
@@ -1301,8 +1204,7 @@ class RnntLstmStreamingSearch(_ChunkCarriedSearch):
             n = lib.s2t_rnnt_lstm_stream_state_bytes(self._desc, B, self.beam_size, self.max_tokens)
             ws = lib.s2t_rnnt_lstm_stream_workspace_bytes(self._desc, B, 256, self.beam_size)
         if self.method == "beam":
-            ok = 1 <= self.beam_size <= N.const("S2T_RNNT_LSTM_MAX_BEAM") and \
-                1 <= min(self.cutoff_top_k, V) <= N.const("S2T_RNNT_LSTM_MAX_BEAM")
+            ok = _beam_in_range(self.beam_size) and _beam_in_range(min(self.cutoff_top_k, V))
         else:
             ok = self.max_token_step >= 0
         if n <= 0 or ws <= 0 or not ok:
@@ -1313,8 +1215,6 @@ class RnntLstmStreamingSearch(_ChunkCarriedSearch):
                                 f"start token {self._lm_start}") + " (limits: include/s2t_mi355.h)")
         self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
         self._ws = torch.zeros((ws,), dtype=torch.uint8, device=dev)
-        if self._lm is not None:
-            self.lm_score = torch.zeros((B,), dtype=torch.float32, device=dev)
 
     def _reset_state(self, mask):
         if self._lm is not None:
@@ -1364,46 +1264,33 @@ class RnntLstmNgramStreamingSearch(RnntLstmStreamingSearch):
 
     def __init__(self, predictor, joiner, batch_size=1, beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None,
                  lm=None, lm_weight=0.0):
-        if not _is_ngram(lm):
-            raise ValueError(f"RnntLstmNgramStreamingSearch needs an NgramLm, got {type(lm).__name__}")
-        if lm.dtype != torch.float32:
-            raise ValueError("the device n-gram search needs fp32 tables")
-        if not math.isfinite(float(lm_weight)):
-            raise ValueError(f"lm_weight must be finite, got {lm_weight!r}")
-        self.capturable = True
-        self.lm_score = None
-        self._lm, self._lm_weight, self._lm_start = None, float(lm_weight), -1   # (_lm: the base class' RnnLm slot)
-        self._ngram = lm
-        _ChunkCarriedSearch.__init__(self, predictor, joiner, batch_size, "beam", 0, beam_size, cutoff_top_k,
-                                     max_tokens, device)
+        super().__init__(predictor, joiner, batch_size, "beam", 0, beam_size, cutoff_top_k, max_tokens, device,
+                         True, lm, lm_weight)
+
+    def _lm_arguments(self, lm, lm_weight, lm_start_token, method):
+        return _ngram_arguments(lm, lm_weight, "RnntLstmNgramStreamingSearch")
 
     def _allocate(self, predictor, joiner, dev):
         B, V = self.batch_size, self.V
         self._desc, self._keep = rnnt_lstm_desc(predictor, joiner)
-        if self._ngram.device != torch.empty(0, device=dev).device:
-            import copy                                    # a copy: the caller's LM stays where it is
-            self._ngram = copy.copy(self._ngram)
-            self._ngram._cache = {}
-            self._ngram.to(dev)
+        self._lm = _ngram_on(self._lm, dev)
         lib = N.lib()
         n = ws = 0
-        if self._desc is not None and B > 0 and self._ngram.num_classes == V:
-            self._lm_desc, self._lm_keep = self._ngram.desc()
+        if self._desc is not None and B > 0 and self._lm.num_classes == V:
+            self._lm_desc, self._lm_keep = self._lm.desc()
             n = lib.s2t_rnnt_lstm_ngram_stream_state_bytes(self._desc, self._lm_desc, B, self.beam_size,
                                                            self.max_tokens)
             ws = lib.s2t_rnnt_lstm_ngram_stream_workspace_bytes(self._desc, self._lm_desc, B, 256, self.beam_size)
-        ok = 1 <= min(self.cutoff_top_k, V) <= N.const("S2T_RNNT_LSTM_MAX_BEAM")
-        if n <= 0 or ws <= 0 or not ok:
+        if n <= 0 or ws <= 0 or not _beam_in_range(min(self.cutoff_top_k, V)):
             raise ValueError(f"the chunk-carried LSTM n-gram beam search does not take this shape: B {B} V {V} beam "
                              f"{self.beam_size} top-k {self.cutoff_top_k} max_tokens {self.max_tokens}, LM V "
-                             f"{self._ngram.num_classes} (limits: include/s2t_mi355.h)")
+                             f"{self._lm.num_classes} (limits: include/s2t_mi355.h)")
         self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)   # the plain state, then ctx and lm_sum per beam
         self._ws = torch.zeros((ws,), dtype=torch.uint8, device=dev)
-        self.lm_score = torch.zeros((B,), dtype=torch.float32, device=dev)
 
     def _reset_state(self, mask):
         N.check(N.lib().s2t_rnnt_lstm_ngram_stream_reset(
-            self._desc, self._lm_desc, int(self._ngram.start_ctx), N.ptr(self.state), N.ip(mask), self.batch_size,
+            self._desc, self._lm_desc, int(self._lm.start_ctx), N.ptr(self.state), N.ip(mask), self.batch_size,
             self.beam_size, self.max_tokens, N.ptr(self._ws), N.stream()), "s2t_rnnt_lstm_ngram_stream_reset")
 
     def _chunk(self, am_chunk, chunk_len, Tc):
@@ -1433,18 +1320,16 @@ class RnntStatelessLmStreamingSearch(_ChunkCarriedSearch):
                  cutoff_top_k=4, max_tokens=1024, device=None, lm=None, lm_weight=0.0, lm_start_token=None):
         if lm is None:
             raise ValueError("RnntStatelessLmStreamingSearch needs an lm (without one: RnntStreamingSearch)")
-        self.lm_score = None
-        self._lm, self._lm_weight, self._lm_start = _stream_lm_arguments(lm, lm_weight, lm_start_token, method)
-        super().__init__(predictor, joiner, batch_size, method, max_token_step, beam_size, cutoff_top_k,
-                         max_tokens, device)
+        self._construct_rnnt(predictor, joiner, batch_size, method, max_token_step, beam_size, cutoff_top_k,
+                             max_tokens, device, lm, lm_weight, lm_start_token)
 
     def _check_modules(self, predictor, joiner):
         if not _is_stateless_pair(predictor, joiner):
             raise ValueError("RnntStatelessLmStreamingSearch takes StatelessPredictor + Joiner, got "
                              f"{type(getattr(predictor, 'predictor', predictor)).__name__} + "
                              f"{type(joiner).__name__} (the LSTM predictor: RnntLstmStreamingSearch)")
-        return [joiner._pre_proj.weight, getattr(predictor, "predictor", predictor)._embedding.weight,
-                self._lm._embedding.weight]
+        return joiner._output_dim, [joiner._pre_proj.weight,
+                                    getattr(predictor, "predictor", predictor)._embedding.weight] + self._lm_on_gpu()
 
     def _allocate(self, predictor, joiner, dev):
         B, V = self.batch_size, self.V
@@ -1456,14 +1341,13 @@ class RnntStatelessLmStreamingSearch(_ChunkCarriedSearch):
             n = lib.s2t_rnnt_stateless_lm_stream_state_bytes(self._desc, self._lm_desc, B, self.beam_size,
                                                              self.max_tokens)
             ws = lib.s2t_rnnt_stateless_lm_stream_workspace_bytes(self._desc, self._lm_desc, B, 256, self.beam_size)
-        if n <= 0 or ws <= 0 or not 1 <= min(self.cutoff_top_k, V) <= N.const("S2T_RNNT_LSTM_MAX_BEAM"):
+        if n <= 0 or ws <= 0 or not _beam_in_range(min(self.cutoff_top_k, V)):
             raise ValueError(f"the chunk-carried stateless beam search with an LM does not take this shape: B {B} "
                              f"V {V} beam {self.beam_size} top-k {self.cutoff_top_k} max_tokens {self.max_tokens}, "
                              f"LM V {self._lm._num_symbols} start token {self._lm_start} "
                              "(limits: include/s2t_mi355.h)")
         self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
         self._ws = torch.zeros((ws,), dtype=torch.uint8, device=dev)
-        self.lm_score = torch.zeros((B,), dtype=torch.float32, device=dev)
 
     def _reset_state(self, mask):
         N.check(N.lib().s2t_rnnt_stateless_lm_stream_reset(
@@ -1495,15 +1379,11 @@ class RnntNgramStreamingSearch(RnntStreamingSearch):
 
     def __init__(self, predictor, joiner, batch_size=1, beam_size=4, cutoff_top_k=4, max_tokens=1024, device=None,
                  lm=None, lm_weight=0.0):
-        if not _is_ngram(lm):
-            raise ValueError(f"RnntNgramStreamingSearch needs an NgramLm, got {type(lm).__name__}")
-        if lm.dtype != torch.float32:
-            raise ValueError("the device n-gram search needs fp32 tables")
-        if not math.isfinite(float(lm_weight)):
-            raise ValueError(f"lm_weight must be finite, got {lm_weight!r}")
-        self.lm_score = None
-        self._lm, self._lm_weight = lm, float(lm_weight)
-        super().__init__(predictor, joiner, batch_size, "beam", 0, beam_size, cutoff_top_k, max_tokens, device)
+        self._construct_rnnt(predictor, joiner, batch_size, "beam", 0, beam_size, cutoff_top_k, max_tokens, device,
+                             lm, lm_weight)
+
+    def _lm_arguments(self, lm, lm_weight, lm_start_token, method):
+        return _ngram_arguments(lm, lm_weight, "RnntNgramStreamingSearch")
 
     def _allocate(self, predictor, joiner, dev):
         super()._allocate(predictor, joiner, dev)          # the plain search's checks and weights
@@ -1514,13 +1394,8 @@ class RnntNgramStreamingSearch(RnntStreamingSearch):
                              f"V {self.V} beam {self.beam_size} max_tokens {self.max_tokens}, LM V "
                              f"{self._lm.num_classes} (limits: include/s2t_mi355.h)")
         self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)   # the plain row + ctx and lm_sum per beam
-        if self._lm.device != self.state.device:           # a copy: the caller's LM stays where it is
-            import copy
-            self._lm = copy.copy(self._lm)
-            self._lm._cache = {}
-            self._lm.to(self.state.device)
+        self._lm = _ngram_on(self._lm, dev)
         self._lm_desc, self._lm_keep = self._lm.desc()
-        self.lm_score = torch.zeros((self.batch_size,), dtype=torch.float32, device=dev)
 
     def _reset_state(self, mask):
         N.check(N.lib().s2t_rnnt_ngram_stream_reset(N.ptr(self.state), N.ip(mask), self.batch_size, self.V, self.ctx,
@@ -1565,7 +1440,7 @@ def rnnt_streaming_search(predictor, joiner, batch_size=1, method="greedy", max_
                                cutoff_top_k, max_tokens, device, **kw)
 
 
-class CtcStreamingSearch:
+class CtcStreamingSearch(_ChunkCarriedSearch):
     """Chunk-carried CTC prefix beam search on the device (csrc/decode_ctc.hip s2t_ctc_prefix_beam_chunk,
     with an `lm` s2t_ctc_prefix_beam_lm_chunk): ctc_prefix_beam_tokens / ctc_prefix_beam_lm_tokens fed the
     frames' scores (B, Tc, V) a chunk at a time.  The frame body is the whole-utterance entries' own, so
@@ -1583,77 +1458,48 @@ class CtcStreamingSearch:
     and takes no LM.  A shape the entries refuse, an `lm` that is not an RnnLm, or greedy with an `lm` is
     a ValueError at construction: there is no host-loop fallback."""
 
+    _input, _has_frames = "logits", False
+
     def __init__(self, num_classes, batch_size=1, method="beam", beam_size=4, cutoff_top_k=4, max_tokens=1024,
                  max_nodes=4096, blank=0, device=None, lm=None, lm_weight=0.0, lm_start_token=None):
-        if method not in ("greedy", "beam"):
-            raise ValueError(f"method must be 'greedy' or 'beam', got {method!r}")
-        self._lm, self._lm_weight, self._lm_start = _stream_lm_arguments(lm, lm_weight, lm_start_token, method)
-        dev = torch.device("cuda") if device is None else torch.device(device)
-        if dev.type != "cuda" or (self._lm is not None and self._lm._embedding.weight.device.type != "cuda"):
-            raise RuntimeError("the chunk-carried search runs on the GPU only: the LM and device must be cuda")
-        self.method, self.batch_size, self.V = method, int(batch_size), int(num_classes)
-        self.beam_size = int(beam_size) if method == "beam" else 1
-        self.cutoff_top_k = int(cutoff_top_k) if method == "beam" else 1
-        self.max_tokens, self.max_nodes, self.blank = int(max_tokens), int(max_nodes), int(blank)
+        beam = _method_arg(method) == "beam"               # (here a method's error comes before an LM's)
+        self.max_nodes, self.blank = int(max_nodes), int(blank)
+        self._construct((num_classes,), batch_size, method, beam_size if beam else 1, cutoff_top_k if beam else 1,
+                        max_tokens, device, lm, lm_weight, lm_start_token)
+
+    def _check_modules(self, num_classes):
+        return int(num_classes), self._lm_on_gpu()
+
+    def _views(self):
+        return self.tokens, self.out_len, self.score, self.stable_len
+
+    def _refuse(self, what, lm_note):
+        """-> the ValueError for a shape the entries refuse; the entries say 0 bytes for what the kernels
+        do not take, `_shape_ok` is what they are not asked."""
+        return ValueError(f"the chunk-carried CTC {what} search does not take this shape: B {self.batch_size} V "
+                          f"{self.V} blank {self.blank} beam {self.beam_size} top-k {self.cutoff_top_k} max_tokens "
+                          f"{self.max_tokens} max_nodes {self.max_nodes}{lm_note} (limits: include/s2t_mi355.h)")
+
+    def _shape_ok(self):
+        return self.batch_size > 0 and 0 <= self.blank < self.V and self.max_tokens >= 1 \
+            and self.cutoff_top_k >= 1 and _beam_in_range(min(self.cutoff_top_k, self.V))
+
+    def _allocate(self, num_classes, dev):
         B, V, lib = self.batch_size, self.V, N.lib()
-        top = N.const("S2T_RNNT_LSTM_MAX_BEAM")
-        ok = B > 0 and 0 <= self.blank < V and self.max_tokens >= 1 and self.cutoff_top_k >= 1 \
-            and min(self.cutoff_top_k, V) <= top
         n, ws = 0, 1
         self._lm_desc = None
-        if ok and self._lm is not None:
+        if self._shape_ok() and self._lm is not None:
             self._lm_desc, self._lm_keep = rnn_lm_desc(self._lm)
             if self._lm_desc is not None and self._lm_start < V:
                 n = lib.s2t_ctc_lm_stream_state_bytes(self._lm_desc, B, V, self.beam_size, self.max_nodes)
                 ws = lib.s2t_ctc_prefix_beam_lm_chunk_workspace_bytes(self._lm_desc, B, V, self.beam_size)
-        elif ok:
+        elif self._shape_ok():
             n = lib.s2t_ctc_stream_state_bytes(B, V, self.beam_size, self.max_nodes)
         if n <= 0 or ws <= 0:
-            raise ValueError(f"the chunk-carried CTC {method} search does not take this shape: B {B} V {V} blank "
-                             f"{self.blank} beam {self.beam_size} top-k {self.cutoff_top_k} max_tokens "
-                             f"{self.max_tokens} max_nodes {self.max_nodes}"
-                             + ("" if self._lm is None else f", with an LM of V {self._lm._num_symbols} "
-                                f"start token {self._lm_start}") + " (limits: include/s2t_mi355.h)")
+            raise self._refuse(self.method, "" if self._lm is None else
+                               f", with an LM of V {self._lm._num_symbols} start token {self._lm_start}")
         self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)
         self._ws = None if self._lm is None else torch.zeros((ws,), dtype=torch.uint8, device=dev)
-        self.tokens = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
-        self.out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
-        self.score = torch.zeros((B,), dtype=torch.float32, device=dev)
-        self.stable_len = torch.zeros((B,), dtype=torch.int64, device=dev)
-        self.overflow = torch.zeros((B,), dtype=torch.int32, device=dev)
-        self.lm_score = None if self._lm is None else torch.zeros((B,), dtype=torch.float32, device=dev)
-        self._full = {}                                    # Tc -> chunk_len of a whole chunk
-        self.reset()
-
-    def reset(self, rows=None):
-        """Rows become the empty prefix; their outputs read zero until their next chunk.  The others
-        are not touched.  rows: None for all; a list of row indices (the mask is then built on the
-        host and copied over: not for a graph capture); or a device mask, an int32 tensor (B) on the
-        search's device with 1 for the rows to reset, which is used as it is -- then, as with None,
-        reset enqueues kernels only and can be captured."""
-        mask = self._reset_mask(rows)
-        self._reset_state(mask)
-        outs = [self.tokens, self.out_len, self.score, self.stable_len, self.overflow]
-        if self.lm_score is not None:
-            outs.append(self.lm_score)
-        for t in outs:
-            if mask is None:
-                t.zero_()
-            else:
-                t.masked_fill_(mask.bool().reshape(-1, *[1] * (t.dim() - 1)), 0)
-
-    def _reset_mask(self, rows):
-        mask = None
-        if isinstance(rows, torch.Tensor) and rows.is_cuda:
-            if rows.dtype != torch.int32 or tuple(rows.shape) != (self.batch_size,):
-                raise ValueError(f"a device mask is int32 of shape ({self.batch_size},), got {rows.dtype} "
-                                 f"{tuple(rows.shape)}")
-            mask = rows.contiguous()
-        elif rows is not None:
-            mask = torch.zeros((self.batch_size,), dtype=torch.int32)
-            mask[torch.as_tensor(rows, dtype=torch.int64)] = 1
-            mask = mask.to(self.state.device)
-        return mask
 
     def _reset_state(self, mask):
         B, V = self.batch_size, self.V
@@ -1669,17 +1515,7 @@ class CtcStreamingSearch:
         """logits_chunk (B, Tc, V) fp32 on the device, raw or normalised, Tc <= 256; chunk_len (B) int64
         on the device (None: Tc frames for every row; 0 leaves a row as it is).  -> (tokens, out_len,
         score, stable_len): views of the fixed output tensors."""
-        B, V = self.batch_size, self.V
-        if logits_chunk.dim() != 3 or logits_chunk.shape[0] != B or logits_chunk.shape[2] != V \
-                or not 1 <= logits_chunk.shape[1] <= 256:
-            raise ValueError(f"expected logits of shape ({B}, 1..256, {V}), got {tuple(logits_chunk.shape)}")
-        Tc = logits_chunk.shape[1]
-        if chunk_len is None:
-            chunk_len = self._full.get(Tc)
-            if chunk_len is None:
-                chunk_len = self._full[Tc] = torch.full((B,), Tc, dtype=torch.int64, device=self.state.device)
-        self._chunk(logits_chunk, chunk_len, Tc)
-        return self.tokens, self.out_len, self.score, self.stable_len
+        return super().step(logits_chunk, chunk_len)
 
     def _chunk(self, logits_chunk, chunk_len, Tc):
         B, V = self.batch_size, self.V
@@ -1713,45 +1549,21 @@ class CtcNgramStreamingSearch(CtcStreamingSearch):
 
     def __init__(self, num_classes, batch_size=1, beam_size=4, cutoff_top_k=4, max_tokens=1024, max_nodes=4096,
                  blank=0, device=None, lm=None, lm_weight=0.0):
-        if not _is_ngram(lm):
-            raise ValueError(f"CtcNgramStreamingSearch needs an NgramLm, got {type(lm).__name__}")
-        if lm.dtype != torch.float32:
-            raise ValueError("the device n-gram search needs fp32 tables")
-        if not math.isfinite(float(lm_weight)):
-            raise ValueError(f"lm_weight must be finite, got {lm_weight!r}")
-        dev = torch.device("cuda") if device is None else torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("the chunk-carried search runs on the GPU only: the device must be cuda")
-        self.method, self.batch_size, self.V = "beam", int(batch_size), int(num_classes)
-        self.beam_size, self.cutoff_top_k = int(beam_size), int(cutoff_top_k)
-        self.max_tokens, self.max_nodes, self.blank = int(max_tokens), int(max_nodes), int(blank)
-        self._lm_weight = float(lm_weight)
+        super().__init__(num_classes, batch_size, "beam", beam_size, cutoff_top_k, max_tokens, max_nodes, blank,
+                         device, lm, lm_weight)
+
+    def _lm_arguments(self, lm, lm_weight, lm_start_token, method):
+        return _ngram_arguments(lm, lm_weight, "CtcNgramStreamingSearch")
+
+    def _allocate(self, num_classes, dev):
         B, V = self.batch_size, self.V
-        ok = B > 0 and 0 <= self.blank < V and self.max_tokens >= 1 and self.cutoff_top_k >= 1 \
-            and min(self.cutoff_top_k, V) <= N.const("S2T_RNNT_LSTM_MAX_BEAM") and lm.num_classes == V
+        ok = self._shape_ok() and self._lm.num_classes == V
         n = N.lib().s2t_ctc_ngram_stream_state_bytes(B, V, self.beam_size, self.max_nodes) if ok else 0
         if n <= 0:
-            raise ValueError(f"the chunk-carried CTC n-gram beam search does not take this shape: B {B} V {V} blank "
-                             f"{self.blank} beam {self.beam_size} top-k {self.cutoff_top_k} max_tokens "
-                             f"{self.max_tokens} max_nodes {self.max_nodes}, LM V {lm.num_classes} "
-                             "(limits: include/s2t_mi355.h)")
+            raise self._refuse("n-gram beam", f", LM V {self._lm.num_classes}")
         self.state = torch.zeros((n,), dtype=torch.uint8, device=dev)   # the plain state, then ctx per prefix
-        if lm.device != self.state.device:                 # a copy: the caller's LM stays where it is
-            import copy
-            lm = copy.copy(lm)
-            lm._cache = {}
-            lm.to(self.state.device)
-        self._lm = lm
-        self._lm_desc, self._lm_keep = lm.desc()
-        self._ws = None
-        self.tokens = torch.zeros((B, self.max_tokens), dtype=torch.int64, device=dev)
-        self.out_len = torch.zeros((B,), dtype=torch.int64, device=dev)
-        self.score = torch.zeros((B,), dtype=torch.float32, device=dev)
-        self.stable_len = torch.zeros((B,), dtype=torch.int64, device=dev)
-        self.overflow = torch.zeros((B,), dtype=torch.int32, device=dev)
-        self.lm_score = torch.zeros((B,), dtype=torch.float32, device=dev)
-        self._full = {}
-        self.reset()
+        self._lm = _ngram_on(self._lm, dev)
+        self._lm_desc, self._lm_keep = self._lm.desc()
 
     def _reset_state(self, mask):
         N.check(N.lib().s2t_ctc_ngram_stream_reset(N.ptr(self.state), N.ip(mask), self.batch_size, self.V,

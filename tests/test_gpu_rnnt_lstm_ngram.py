@@ -402,7 +402,7 @@ def test_empty_batch_and_the_class_surface(dev):
         rnnt_streaming_search(p, j, method="beam", lm=lm, lm_weight=0.5, device=dev)
     cpu = NgramLm.from_arpa(C.text_of(name), num_classes=63)
     s = RnntLstmNgramStreamingSearch(p, j, 2, device=dev, lm=cpu, lm_weight=0.3)           # tables copied over
-    assert s._ngram.device.type == "cuda" and cpu.device.type == "cpu" and s.lm_score.shape == (2,)
+    assert s._lm.device.type == "cuda" and cpu.device.type == "cpu" and s.lm_score.shape == (2,)
     assert s.method == "beam" and len(s.step(am[:2, :3].contiguous())) == 5
     other = _lm(dev, C.text_of("n_v65_l2_t90"), 65)
     for kw in (dict(beam_size=17), dict(beam_size=0), dict(cutoff_top_k=0), dict(max_tokens=0),
