@@ -88,6 +88,7 @@ import torch
 
 import conf_f64 as CF
 from oracle import conformer as OC
+from yardstick import FLOOR, MARGIN, UNIT, _leaf, bound_of, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 EPS = 1e-5
 SMAX = 2 ** 62 - 1
@@ -284,10 +285,6 @@ def bn_mean_over_std(name):
 
 
 # ------------------------------------------------------------------ the yardstick on a case
-def _leaf(v, dt, grad=True):
-    return None if v is None else v.to(dt).clone().requires_grad_(grad)
-
-
 def _eval_ln(c, t, dt):
     out = {}
     for add in (False, True):
@@ -409,25 +406,12 @@ def reference(name):
     return evaluate(name, torch.float64)
 
 
-def rel_err(got, ref):
-    """max |got - ref| relative to max |ref|, the error measure of every bound in both files; of
-    lists: the largest over the items, each relative to its own reference."""
-    if isinstance(ref, (list, tuple)):
-        return max(rel_err(a, b) for a, b in zip(got, ref))
-    ref = ref.detach().double().cpu()
-    got = got.detach().double().cpu()
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    return float((got - ref).abs().max() / (ref.abs().max() + 1e-300))
-
-
 def fp32_figures(name):
     """{tensor: rel_err of the float32 CPU evaluation of the yardstick against float64}."""
     ref, f32 = reference(name), evaluate(name, torch.float32)
     return {k: rel_err(f32[k], ref[k]) for k in ref}
 
 
-FLOOR = 2e-5            # test_gpu_conformer_layer.py's bound on LayerNorm / attention gradients
-MARGIN = 8.0            # the project's margin on a float32 figure (tests/lstm_cases.py)
 BN_VAR_TENSORS = ("y", "dx", "dx_plus_ds", "dgamma", "rstd", "running_var")
 
 
@@ -441,7 +425,7 @@ def bound(name, tensor):
     fig = FP32_COST[name][tensor]
     if CASES[name]["group"] == "bn" and tensor in BN_VAR_TENSORS:
         fig = fig * bn_kappa(name)
-    return max(FLOOR, MARGIN * fig)
+    return bound_of(fig)
 
 
 # ------------------------------------------------------------------ measured cost of fp32
@@ -451,7 +435,6 @@ def bound(name, tensor):
 # float32 rounding (a tensor of one or four elements that happened to round well, or an exact
 # product with a mask of 0 / 1 / 2: 0.0) says nothing a host would repeat, and no figure below
 # FLOOR / MARGIN = 2.5e-6 reaches a bound.
-UNIT = 2.0 ** -24
 FP32_COST = {
     "ln_c4": dict(out=1.1e-7, dgamma=9.6e-8, dbeta=5.5e-8, dx=1.7e-7, mean=3.7e-8, rstd=4.2e-8,
                   out_add=2.1e-7, dgamma_add=6.3e-8, dbeta_add=5.5e-8, xsum=3.5e-8, dx_add=2.6e-7),

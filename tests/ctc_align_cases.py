@@ -28,15 +28,15 @@ restatement return the same ok, path and spans on every utterance of every case;
 least one tied decision on its best path.
 
 COST holds what float32 costs the RESTATEMENT (tests/ctc_align_f64.py in float32 on the CPU against
-float64) on exactly these inputs, in the sense of lstm_cases.rel_err over the feasible rows, the larger of
-score's and tok_logp's; the GPU bounds are max(FLOOR, MARGIN x figure), the rule of tests/lstm_cases.py.
+float64) on exactly these inputs, in the sense of yardstick.rel_err over the feasible rows, the larger of
+score's and tok_logp's; the GPU bounds are max(FLOOR, MARGIN x figure), the rule of tests/yardstick.py.
 """
 import functools
 
 import torch
 
 import ctc_align_f64 as A
-from lstm_cases import FLOOR, MARGIN, rel_err
+from yardstick import FLOOR, MARGIN, bound_of, clamp, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 KINDS = ("full", "tight", "less", "zero", "above", "short", "rand")
 
@@ -87,10 +87,6 @@ FORMS = {                                                  # what s2t_ctc_align_
 def need(targets):
     """The fewest frames a transcript can be aligned to: its labels and a blank between doubled ones."""
     return len(targets) + sum(a == b for a, b in zip(targets, targets[1:]))
-
-
-def clamp(n, T):
-    return max(0, min(int(n), T))
 
 
 @functools.lru_cache(maxsize=None)
@@ -211,7 +207,7 @@ def fp32_figure(name):
 
 def bound(name):
     """Allowed rel_err of the device's score and tok_logp in case `name`."""
-    return max(FLOOR, MARGIN * COST[name])
+    return bound_of(COST[name])
 
 
 # ------------------------------------------------------------------ measured cost of fp32

@@ -22,8 +22,8 @@ cases a prefix that had left the beam is kept again next to one of its own exten
 land on live prefixes.
 
 COST holds what float32 costs the RESTATEMENT (float32 on the CPU against float64) on exactly these
-inputs, in the sense of lstm_cases.rel_err, the larger of score's and lm_score's; the GPU bounds are
-max(2e-5, 8 x figure), the rule of tests/lstm_cases.py.
+inputs, in the sense of yardstick.rel_err, the larger of score's and lm_score's; the GPU bounds are
+max(2e-5, 8 x figure), the rule of tests/yardstick.py.
 """
 import functools
 
@@ -31,8 +31,8 @@ import numpy as np
 import torch
 
 import ctc_ngram_f64 as G
-from ctc_prefix_cases import clamp, lengths_of
-from lstm_cases import FLOOR, MARGIN, rel_err
+from ctc_prefix_cases import lengths_of
+from yardstick import FLOOR, MARGIN, bound_of, clamp, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 
 def _c(seed, V, T, B, beam, topk, scale, order, lens="full", norm=False, n_tokens=300, lm_seed=0, weight=0.5,
@@ -150,7 +150,7 @@ def fp32_figure(name):
 
 def bound(name):
     """Allowed rel_err of the device's score and lm_score in case `name`."""
-    return max(FLOOR, MARGIN * COST[name])
+    return bound_of(COST[name])
 
 
 # ------------------------------------------------------------------ the exhaustive cases

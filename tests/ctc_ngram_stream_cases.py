@@ -26,8 +26,8 @@ import torch
 
 import ctc_ngram_cases as G
 import ctc_ngram_stream_f64 as S
-from ctc_prefix_cases import clamp
 from ctc_stream_cases import CUTS, RAGGED  # noqa: F401  (CUTS: the tests parametrise over it)
+from yardstick import clamp
 
 CASES = G.CASES
 LM_CHANGES, REENTER = G.LM_CHANGES, G.REENTER

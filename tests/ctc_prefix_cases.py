@@ -18,8 +18,8 @@ that had left the beam is kept again next to one of its own extensions (what an 
 gets wrong); in LM_CHANGES cases the LM changes a hypothesis against lm_weight = 0.
 
 COST holds what float32 costs the RESTATEMENT (tests/ctc_prefix_f64.py in float32 on the CPU against
-float64) on exactly these inputs, in the sense of lstm_cases.rel_err, the larger of score's and
-lm_score's; the GPU bounds are max(2e-5, 8 x figure), the rule of tests/lstm_cases.py.
+float64) on exactly these inputs, in the sense of yardstick.rel_err, the larger of score's and
+lm_score's; the GPU bounds are max(2e-5, 8 x figure), the rule of tests/yardstick.py.
 """
 import functools
 
@@ -27,7 +27,7 @@ import torch
 
 import ctc_prefix_f64 as P
 import rnnt_lm_fusion_cases as L
-from lstm_cases import FLOOR, MARGIN, rel_err
+from yardstick import FLOOR, MARGIN, bound_of, clamp, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 
 def _c(seed, V, T, B, beam, topk, scale, lens="full", norm=False, lm=None, lm_seed=0, weight=0.0, start=None):
@@ -68,10 +68,6 @@ def lengths_of(c):
     if B > 2:
         lens[2] = T + 3
     return lens
-
-
-def clamp(n, T):
-    return max(0, min(int(n), T))
 
 
 def make(name):
@@ -121,7 +117,7 @@ def fp32_figure(name):
 
 def bound(name):
     """Allowed rel_err of the device's score and lm_score in case `name`."""
-    return max(FLOOR, MARGIN * COST[name])
+    return bound_of(COST[name])
 
 
 # ------------------------------------------------------------------ the exhaustive cases

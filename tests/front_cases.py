@@ -5,7 +5,7 @@ float32 costs the REFERENCE on exactly these inputs, per output tensor: tests/fr
 in float32 on the CPU against float64, and for the fbank oracle.fbank (float32) against the float64
 restatement under the fbank's own measure (front_f64.fbank_err).  The CPU file measures and checks
 the figures; the GPU file takes its bounds from them (bound(): max(2e-5, 8 x figure), FLOOR and
-MARGIN of tests/zip_cases.py), so a figure is never anything a kernel produced.  Error measure:
+MARGIN of tests/yardstick.py), so a figure is never anything a kernel produced.  Error measure:
 max |got - ref| / max |ref| per tensor; integer and copied outputs are compared exactly.
 
 Why each case is there (the launch code of the five sources names the numbers):
@@ -73,7 +73,7 @@ import numpy as np
 import torch
 
 import front_f64 as FF
-from zip_cases import FLOOR, MARGIN, UNIT, rel_err  # noqa: F401  (the project's convention, unchanged)
+from yardstick import FLOOR, MARGIN, UNIT, bound_of, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 CAP = 1024 * 256                      # elements one trip of an augment.hip stream covers
 
@@ -416,12 +416,12 @@ def fp32_figures(name):
 def bound(name, tensor):
     """Allowed error of device tensor `tensor` of case `name`: max(FLOOR, MARGIN x the float32 figure of
     the yardstick) = max(2e-5, 8 x figure).  No derived exception is needed."""
-    return max(FLOOR, MARGIN * FP32_COST[name][tensor])
+    return bound_of(FP32_COST[name][tensor])
 
 
 # ------------------------------------------------------------------ measured cost of fp32
 # fp32_figures(name), rounded up to two digits; tests/test_front_f64.py re-measures every one to a
-# factor 4 both ways after raising both to UNIT (zip_cases.UNIT, one float32 rounding).
+# factor 4 both ways after raising both to UNIT (yardstick.UNIT, one float32 rounding).
 FP32_COST = {
     "fb_ragged": dict(feat=4.2e-07),
     "fb_mf_below": dict(feat=3.9e-07),

@@ -150,6 +150,26 @@ FP32_COST = {                      # measured value, rounded up to two digits
 }
 
 
+# ------------------------------------------------------------------ shared by the loss kernels' GPU files
+def _kern():
+    from speech2text_amd import kernels
+    return kernels
+
+
+def _np(t):
+    return t.detach().cpu().double().numpy()
+
+
+G_ATOL, G_RTOL = 3e-5, 2e-3            # gradients under weights that sum to about one
+
+
+def _assert_grad(got, ref, atol=G_ATOL, rtol=G_RTOL, what=""):
+    got, ref = _np(got), _np(ref)
+    print(f"{what}: max abs dev {np.abs(got - ref).max():.3e} (atol {atol:.1e})")
+    np.testing.assert_allclose(got, ref, atol=atol, rtol=rtol)
+
+
 def bound(measured, floor):
-    """4x what fp32 costs the reference, never tighter than the small-case bound."""
+    """4x what fp32 costs the reference, never tighter than the small-case bound (the loss suite's own
+    rule, with a floor per quantity: not the one of tests/yardstick.py)."""
     return max(4.0 * measured, floor)

@@ -123,7 +123,8 @@ FP32_COST = {
 
 
 def bound(measured, floor):
-    """4x what fp32 costs the restatement, never tighter than the small-case bound."""
+    """4x what fp32 costs the restatement, never tighter than the small-case bound (the rule of
+    tests/loss_cases.py, not the one of tests/yardstick.py)."""
     return max(4.0 * measured, floor)
 
 

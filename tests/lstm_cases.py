@@ -25,6 +25,7 @@ import functools
 import torch
 
 import lstm_f64 as LF
+from yardstick import FLOOR, MARGIN, bound_of, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 EPS = 1e-3
 
@@ -121,12 +122,6 @@ def reference(name):
     return evaluate(make(name), torch.float64)
 
 
-def rel_err(got, ref):
-    """max |got - ref| relative to max |ref|, the error measure of every bound in both files."""
-    ref = ref.detach().double().cpu()
-    return float((got.detach().double().cpu() - ref).abs().max() / (ref.abs().max() + 1e-300))
-
-
 def fp32_figures(name):
     """(fwd, bwd): the largest rel_err over TENSORS_FWD / TENSORS_BWD of the float32 CPU
     evaluation of the reference against float64."""
@@ -136,14 +131,9 @@ def fp32_figures(name):
     return fwd, bwd
 
 
-FLOOR = 2e-5            # test_gpu_conformer_layer.py's bound on LayerNorm / attention gradients
-MARGIN = 8.0            # 2 x the loss suite's 4: the kernel's sigmoid / tanh use the hardware
-#                         exponential and reciprocal, each about an ulp looser than torch's CPU ones
-
-
 def bound(name, kind):
     """Allowed rel_err of a device tensor of `kind` ('fwd' / 'bwd') in case `name`."""
-    return max(FLOOR, MARGIN * FP32_COST[name][kind])
+    return bound_of(FP32_COST[name][kind])
 
 
 # ------------------------------------------------------------------ measured cost of fp32

@@ -6,7 +6,7 @@ scale.  The float64 reference is tests/rnn_lm_f64.lstm_ref; FP32_COST holds what
 REFERENCE -- torch.nn.LSTM in float32 on the CPU against that float64 -- on exactly these inputs
 (gx enters nn.LSTM through an identity weight_ih and zero biases, which is exact).  The CPU file
 measures and checks the figures; the GPU file derives its bounds from them (max(2e-5, 8 x figure),
-the rule of lstm_cases), so the figures measure the reference only, never the kernel.
+the rule of tests/yardstick.py), so the figures measure the reference only, never the kernel.
 
 Why each shape (csrc/lstm_step.hip: a workgroup owns HS = 16 hidden units and BT = 16 utterances,
 grid = ceil(H / 16) x ceil(B / 16); a wave walks K = H in chunks of 64 = four 16-wide sub-chunks on
@@ -38,6 +38,7 @@ import functools
 import torch
 
 import rnn_lm_f64 as RF
+from yardstick import FLOOR, MARGIN, bound_of, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 THRESHOLD = 1          # conf_kernels.LSTM_STEP_MIN_BATCH the cases were laid out for (the GPU file
 #                        asserts that they agree)
@@ -134,12 +135,6 @@ def reference(name):
     return evaluate(make(name), torch.float64)
 
 
-def rel_err(got, ref):
-    """max |got - ref| relative to max |ref|, the error measure of every bound in both files."""
-    ref = ref.detach().double().cpu()
-    return float((got.detach().double().cpu() - ref).abs().max() / (ref.abs().max() + 1e-300))
-
-
 def fp32_figures(name):
     """(fwd, bwd): the largest rel_err over TENSORS_FWD / TENSORS_BWD of torch.nn.LSTM in float32
     on the CPU against the float64 reference."""
@@ -148,14 +143,9 @@ def fp32_figures(name):
             max(rel_err(f32[k], ref[k]) for k in TENSORS_BWD))
 
 
-FLOOR = 2e-5            # lstm_cases.FLOOR
-MARGIN = 8.0            # lstm_cases.MARGIN: the kernel's sigmoid / tanh use the hardware exponential
-#                         and reciprocal, each about an ulp looser than torch's CPU ones
-
-
 def bound(name, kind):
     """Allowed rel_err of a device tensor of `kind` ('fwd' / 'bwd') in case `name`."""
-    return max(FLOOR, MARGIN * FP32_COST[name][kind])
+    return bound_of(FP32_COST[name][kind])
 
 
 # ------------------------------------------------------------------ measured cost of fp32

@@ -24,8 +24,8 @@ in float64 and the float32 CPU run of the restatement returns the same tokens an
 case with beam > 1 at least one utterance's fused tokens differ from the un-fused search's.
 
 LM_STEP_COST / FUSED_COST hold what float32 costs the RESTATEMENT (tests/rnnt_lm_fusion_f64.py in
-float32 on the CPU against float64) on exactly these inputs, in the sense of lstm_cases.rel_err; the
-GPU bounds are max(2e-5, 8 x figure), the rule of tests/lstm_cases.py.
+float32 on the CPU against float64) on exactly these inputs, in the sense of yardstick.rel_err; the
+GPU bounds are max(2e-5, 8 x figure), the rule of tests/yardstick.py.
 """
 import functools
 
@@ -34,7 +34,7 @@ import torch
 import rnnt_lm_fusion_f64 as F
 import rnnt_lstm_search_cases as C
 import rnnt_lstm_search_f64 as S
-from lstm_cases import rel_err  # noqa: F401
+from yardstick import rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 bound = C.bound
 
@@ -194,7 +194,7 @@ def stateless_reference():
 
 # ------------------------------------------------------------------ measured cost of fp32
 # The largest value seen with 1, 4, 8 and 16 host threads, rounded up to two digits, the value
-# itself behind (the rule of tests/lstm_cases.py).
+# itself behind (the rule of tests/yardstick.py).
 LM_STEP_COST = {
     "lm20": 1.5e-07,                    # 1.491e-07
     "lm48": 2.1e-07,                    # 2.049e-07

@@ -19,8 +19,8 @@ returns the same tokens and frames; in LM_CHANGES cases the n-gram changes a hyp
 lm_weight = 0; across the cases a look-up backs off 0, 1 and order - 1 times and reaches the dense root.
 
 COST holds what float32 costs the RESTATEMENT (float32 on the CPU against float64) on exactly these
-inputs, in the sense of lstm_cases.rel_err, the larger of score's and lm_score's; the GPU bounds are
-max(FLOOR, MARGIN x figure), the rule of tests/lstm_cases.py.
+inputs, in the sense of yardstick.rel_err, the larger of score's and lm_score's; the GPU bounds are
+max(FLOOR, MARGIN x figure), the rule of tests/yardstick.py.
 """
 import functools
 
@@ -31,8 +31,8 @@ import ctc_ngram_cases as N
 import ctc_ngram_f64 as G
 import rnnt_lstm_ngram_f64 as R
 import rnnt_lstm_search_cases as LC
-from lstm_cases import FLOOR, rel_err
-from lstm_cases import MARGIN as COST_MARGIN
+from yardstick import FLOOR, bound_of, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
+from yardstick import MARGIN as COST_MARGIN  # noqa: F401
 from rnnt_lm_stream_cases import PARTITIONS  # noqa: F401
 from rnnt_lstm_search_f64 import MARGIN  # noqa: F401  (the decision margin, 1e-3)
 from rnnt_lstm_stream_f64 import cuts_of as _cuts
@@ -184,7 +184,7 @@ def fp32_figure(name):
 
 def bound(name):
     """Allowed rel_err of the device's score and lm_score in case `name`."""
-    return max(FLOOR, COST_MARGIN * COST[name])
+    return bound_of(COST[name])
 
 
 # ------------------------------------------------------------------ the exhaustive cases

@@ -23,16 +23,16 @@ tokens (the seeds and scales were chosen on the CPU for that; tests/test_rnnt_ls
 asserts both).
 
 PRED_COST / BEAM_COST hold what float32 costs the RESTATEMENT (tests/rnnt_lstm_search_f64.py in
-float32 on the CPU against float64) on exactly these inputs, in the sense of lstm_cases.rel_err; the
+float32 on the CPU against float64) on exactly these inputs, in the sense of yardstick.rel_err; the
 CPU file checks the figures to a factor 4 and the GPU file derives its bounds from them by the rule
-of tests/lstm_cases.py: max(2e-5, 8 x figure).
+of tests/yardstick.py: max(2e-5, 8 x figure).
 """
 import functools
 
 import torch
 
 import rnnt_lstm_search_f64 as S
-from lstm_cases import FLOOR, MARGIN as COST_MARGIN, rel_err  # noqa: F401
+from yardstick import FLOOR, MARGIN as COST_MARGIN, bound_of, clamp, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 EPS_IN, EPS_LSTM, EPS_OUT = 1e-5, 1e-3, 1e-5
 
@@ -126,10 +126,6 @@ def make(name):
     return w, m["act"], am, lens
 
 
-def clamp(n, T):
-    return max(0, min(int(n), T))
-
-
 def evaluate(name, dtype):
     """The restatement on a case with the weights in `dtype` -> per utterance, greedy: (tokens,
     margin, forced); beam: (tokens, score, frames, margin)."""
@@ -203,12 +199,12 @@ def beam_fp32_figure(name):
 
 def bound(figure):
     """Allowed rel_err of a device tensor whose float32 cost in the restatement is `figure`."""
-    return max(FLOOR, COST_MARGIN * figure)
+    return bound_of(figure)
 
 
 # ------------------------------------------------------------------ measured cost of fp32
 # The largest value seen with 1, 4, 8 and 16 host threads, rounded up to two digits, the value
-# itself behind (the rule of tests/lstm_cases.py).
+# itself behind (the rule of tests/yardstick.py).
 PRED_COST = {
     "h20": 3.6e-07,                     # 3.550e-07
     "h48": 2.9e-07,                     # 2.821e-07

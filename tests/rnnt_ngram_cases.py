@@ -30,8 +30,8 @@ walks the same tokens and frames; in every case with beam > 1 the LM changes at 
 tokens against lm_weight = 0; per order the look-ups of the cases back off 0, 1, ..., order - 1 times.
 
 COST holds what float32 costs the RESTATEMENT (float32 on the CPU against float64) on exactly these
-inputs, in the sense of lstm_cases.rel_err, the larger of score's and lm_score's; the GPU bounds are
-max(2e-5, 8 x figure), the rule of tests/lstm_cases.py.
+inputs, in the sense of yardstick.rel_err, the larger of score's and lm_score's; the GPU bounds are
+max(2e-5, 8 x figure), the rule of tests/yardstick.py.
 """
 import functools
 
@@ -41,8 +41,8 @@ import torch
 import ctc_ngram_cases as N
 import ctc_ngram_f64 as G
 import rnnt_ngram_f64 as R
-from lstm_cases import FLOOR, rel_err
-from lstm_cases import MARGIN as COST_MARGIN
+from yardstick import FLOOR, bound_of, clamp, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
+from yardstick import MARGIN as COST_MARGIN  # noqa: F401
 from rnnt_lstm_search_f64 import MARGIN  # noqa: F401  (the decision margin, 1e-3)
 
 
@@ -65,10 +65,6 @@ CASES = {
 YAML = "g_yaml"
 LONG = "g_long_o3"
 LARGE = "g_v1000_o2_beam16"
-
-
-def clamp(n, T):
-    return max(0, min(int(n), T))
 
 
 def text_of(name):
@@ -154,7 +150,7 @@ def fp32_figure(name):
 
 def bound(name):
     """Allowed rel_err of the device's score and lm_score in case `name`."""
-    return max(FLOOR, COST_MARGIN * COST[name])
+    return bound_of(COST[name])
 
 
 def cuts_of(name, b, kind):

@@ -27,8 +27,8 @@ the same tokens and frames; in every case with beam > 1 the LM changes at least 
 against lm_weight = 0.
 
 STEP_COST / FUSED_COST hold what float32 costs the RESTATEMENT (tests/rnnt_stateless_lm_f64.py in float32
-on the CPU against float64) on exactly these inputs, in the sense of lstm_cases.rel_err; the GPU bounds
-are max(2e-5, 8 x figure), the rule of tests/lstm_cases.py.
+on the CPU against float64) on exactly these inputs, in the sense of yardstick.rel_err; the GPU bounds
+are max(2e-5, 8 x figure), the rule of tests/yardstick.py.
 """
 import functools
 
@@ -37,7 +37,7 @@ import torch
 import rnnt_lm_fusion_cases as L
 import rnnt_lstm_search_cases as C
 import rnnt_stateless_lm_f64 as SF
-from lstm_cases import rel_err  # noqa: F401
+from yardstick import rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 bound = C.bound
 clamp = C.clamp
@@ -153,7 +153,7 @@ def step_fp32_figure(name):
 
 # ------------------------------------------------------------------ measured cost of fp32
 # The largest value seen with 1, 4, 8 and 16 host threads, rounded up to two digits, the value
-# itself behind (the rule of tests/lstm_cases.py).
+# itself behind (the rule of tests/yardstick.py).
 STEP_COST = {                           # the lm rows after steps 1 and 5
     "s_b1_ctx1_beam1_k1": 1.5e-07,      # 1.471e-07
     "s_b17_ctx5_e65": 2.4e-07,          # 2.369e-07

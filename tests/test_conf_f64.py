@@ -10,7 +10,6 @@ The last part measures what float32 costs the REFERENCE on every case of tests/c
 figures recorded in conf_cases.FP32_COST are checked here (to the factor by which they move from
 host to host), so the GPU file's bounds (max(2e-5, 8 x figure)) cannot drift.
 """
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -18,18 +17,7 @@ import torch.nn.functional as F
 import conf_cases as CC
 import conf_f64 as CF
 from oracle import conformer as OC
-
-F64 = torch.float64
-TOL = dict(atol=1e-12, rtol=1e-12)
-
-
-def _rn(seed):
-    g = torch.Generator().manual_seed(seed)
-    return lambda *s: torch.randn(*s, generator=g, dtype=F64)
-
-
-def _same(a, b, what=""):
-    np.testing.assert_allclose(a.detach().numpy(), b.detach().numpy(), err_msg=what, **TOL)
+from yardstick import F64, _rn, _same
 
 
 # ------------------------------------------------------------------ LayerNorm

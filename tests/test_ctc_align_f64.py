@@ -12,6 +12,7 @@ import torch
 
 import ctc_align_cases as C
 import ctc_align_f64 as A
+from decode_support import _lib
 
 
 # ------------------------------------------------------------------ 1. the conditions
@@ -107,9 +108,6 @@ def test_best_path_is_the_best_of_all_paths_on_small_lattices():
 
 
 # ------------------------------------------------------------------ 3. the host side of the entry
-def _lib():
-    from speech2text_amd import _native as N
-    return N, N.lib()
 
 
 def test_workspace_size_and_form_are_pure_host_functions():

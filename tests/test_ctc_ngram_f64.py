@@ -15,11 +15,7 @@ import ctc_ngram_cases as C
 import ctc_ngram_f64 as G
 import ctc_prefix_f64 as P
 from rnnt_lstm_search_f64 import MARGIN
-
-
-class _Ids:
-    def decode(self, t):
-        return [int(x) for x in t]
+from yardstick import _Ids
 
 
 # ------------------------------------------------------------------ 1. the restatement itself

@@ -19,8 +19,8 @@ import ctc_ngram_f64 as NG
 import ctc_ngram_stream_cases as C
 import ctc_ngram_stream_f64 as S
 import ctc_stream_f64 as PS
-from lstm_cases import rel_err
 from rnnt_lstm_search_f64 import MARGIN
+from yardstick import rel_err
 
 
 # ------------------------------------------------------------------ 1. the restatement itself

@@ -16,11 +16,7 @@ import ctc_prefix_f64 as P
 import rnnt_lm_fusion_cases as L
 import rnnt_lm_fusion_f64 as F
 from rnnt_lstm_search_f64 import MARGIN
-
-
-class _Ids:
-    def decode(self, t):
-        return [int(x) for x in t]
+from yardstick import _Ids
 
 
 # ------------------------------------------------------------------ 1. the restatement itself

@@ -1,19 +1,12 @@
 """CPU, world_size 2 (gloo): the bucketed gradient reducer averages gradients like DDP,
 tolerates parameters that never get a gradient, and skips sync under no_sync()."""
 import os
-import socket
 
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from task_support import _free_port
 
 
 def _worker(rank, world, port, q, algo):

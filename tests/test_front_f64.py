@@ -26,16 +26,10 @@ from oracle import augment as OA
 from oracle import best_rq as OB
 from oracle import fbank as OF
 from oracle import heads as OH
+from yardstick import F64, TOL, _rn
 
-F64 = torch.float64
-TOL = dict(atol=1e-12, rtol=1e-12)
 GC = dict(eps=1e-6, atol=1e-7, rtol=1e-6)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _rn(seed):
-    g = torch.Generator().manual_seed(seed)
-    return lambda *s: torch.randn(*s, generator=g, dtype=F64)
 
 
 def _same(a, b, what=""):

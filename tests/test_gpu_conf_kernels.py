@@ -5,77 +5,43 @@ tests/conf_f64.py, at every dispatch edge (tests/conf_cases.py names why each sh
 
 Error = max |got - ref| / max |ref| per tensor; allowed = conf_cases.bound(case, tensor) =
 max(2e-5, 8 x the case's float32 figure of the YARDSTICK, asserted by tests/test_conf_f64.py).
-Every buffer a kernel writes is allocated with one guard row of a sentinel behind it, which must be
-intact afterwards (the LayerNorm partial sums and statistics, the BatchNorm save vectors, running
+Every buffer a kernel writes is a guarded buffer of tests/guarded.py holding the sentinel SENT, with a
+guard of at least one row of SENT behind it, which must be intact afterwards (the LayerNorm partial sums and statistics, the BatchNorm save vectors, running
 statistics and workspace included): an over-run shows here, without any sanitizer.
 """
+import functools
 import math
 
 import pytest
 import torch
 
 import conf_cases as CC
+import guarded
+from guarded import SENT, env, hold
 from oracle import conformer as OC
 
 pytestmark = pytest.mark.gpu
 
-SENT = -7777.25          # no kernel under test produces it
-
-
-class Guarded:
-    """A (rows, cols) float32 device buffer with one more row of SENT behind it."""
-
-    def __init__(self, dev, rows, cols, fill=SENT):
-        self.full = torch.full((rows + 1, cols), SENT, dtype=torch.float32, device=dev)
-        self.t = self.full[:rows]
-        if fill != SENT:
-            self.t.fill_(fill)
-
-    def intact(self, what):
-        assert bool((self.full[-1] == SENT).all()), f"{what}: the guard row behind the buffer was written"
-
-
-def _put(dev, src, cols=None):
-    """`src` copied into a guarded buffer (1-D tensors as one row unless `cols` is given)."""
-    s2 = src.reshape(-1, cols if cols else src.shape[-1])
-    g = Guarded(dev, s2.shape[0], s2.shape[1])
-    g.t.copy_(s2)
-    return g
-
-
-def _flat(dev, n, fill=SENT):
-    """A guarded buffer for a stream of n floats: rows of 4 (one float4), so that the guard starts
-    right behind the last element."""
-    return Guarded(dev, n // 4, 4, fill)
+Buf = functools.partial(guarded.Buf, fill=SENT)
 
 
 def _hold(name, got, ref=None):
-    """Every tensor of `got` within conf_cases.bound of the reference; all misses are reported."""
+    """guarded.hold on tensors that already have the reference's shapes: this file hands every tensor over
+    in the yardstick's own layout, so a reshape would hide a mistake of the test's."""
     ref = CC.reference(name) if ref is None else ref
-    assert set(got) == set(ref), (sorted(got), sorted(ref))
-    bad = []
     for k, v in got.items():
-        for w in (v if isinstance(v, list) else [v]):
-            assert bool(torch.isfinite(w).all()), f"{name} {k}: not finite"
-        err, tol = CC.rel_err(v, ref[k]), CC.bound(name, k)
-        print(f"{name} {k}: err {err:.3e} bound {tol:.3e}")
-        if not err <= tol:
-            bad.append(f"{name} {k}: err {err:.3e} > bound {tol:.3e}")
-    assert not bad, "; ".join(bad)
-
-
-def _env():
-    from speech2text_amd import _native as N
-    return N, N.lib(), N.stream()
+        if k in ref and not isinstance(v, list):
+            assert v.shape == ref[k].shape, (name, k, v.shape, ref[k].shape)
+    hold(CC, name, got, ref=ref)
 
 
 # ------------------------------------------------------------------ LayerNorm
 def _ln_forward(dev, x, y, gamma, beta):
     """-> (xsum | None, out, stats) in guarded buffers."""
-    N, lib, st = _env()
+    N, lib, st = env()
     R, C = x.shape
-    out, stats = Guarded(dev, R, C), Guarded(dev, R, 2)
-    xsum = Guarded(dev, R, C) if y is not None else None
+    out, stats = Buf(dev, (R, C)), Buf(dev, (R, 2))
+    xsum = Buf(dev, (R, C)) if y is not None else None
     N.check(lib.s2t_layernorm_fwd(N.fp(x), N.fp(y), 0.5, N.fp(gamma), N.fp(beta), R, C, CC.EPS,
                                   N.fp(xsum.t) if xsum else None, N.fp(out.t), N.fp(stats.t), st),
             "s2t_layernorm_fwd")
@@ -84,10 +50,10 @@ def _ln_forward(dev, x, y, gamma, beta):
 
 def _ln_backward(dev, x, stats, gamma, dy, resid):
     """-> (dx, partial) in guarded buffers; partial is (workgroups, 2C)."""
-    N, lib, st = _env()
+    N, lib, st = env()
     R, C = x.shape
     nwg = lib.s2t_layernorm_bwd_partial_floats(R, C) // (2 * C)
-    dx, partial = Guarded(dev, R, C), Guarded(dev, nwg, 2 * C)
+    dx, partial = Buf(dev, (R, C)), Buf(dev, (nwg, 2 * C))
     N.check(lib.s2t_layernorm_bwd(N.fp(x), N.fp(stats), N.fp(gamma), N.fp(dy), N.fp(resid), R, C,
                                   N.fp(dx.t), N.fp(partial.t), st), "s2t_layernorm_bwd")
     return dx, partial
@@ -107,7 +73,7 @@ def test_layernorm_forward_backward_vs_float64(dev, name):
         xsum, out, stats = _ln_forward(dev, t["x"], t["y"] if add else None, t["gamma"], t["beta"])
         xs = xsum.t if add else t["x"]
         dx, partial = _ln_backward(dev, xs, stats.t, t["gamma"], t["dy"], t["resid"] if add else None)
-        grads = Guarded(dev, 2, C, fill=0.0)
+        grads = Buf(dev, (2, C), src=torch.zeros(2, C))
         ck.ln_param_grad([(partial.t, R, grads.t[0], grads.t[1])], C)
         torch.cuda.synchronize()
         for g, what in ((out, "out"), (stats, "stats"), (dx, "dx"), (partial, "partial"), (grads, "dgamma / dbeta")):
@@ -135,7 +101,7 @@ def test_layernorm_fold_vs_float64(dev, name):
     c = CC.CASES[name]
     C, n = c["C"], len(c["rows"])
     items = CC.make(name)["items"]
-    dg, db = Guarded(dev, n, C), Guarded(dev, n, C)
+    dg, db = Buf(dev, (n, C)), Buf(dev, (n, C))
     keep, call = [], []
     for i, it in enumerate(items):
         d = {k: v.to(dev) for k, v in it.items()}
@@ -159,12 +125,12 @@ def test_layernorm_fold_vs_float64(dev, name):
 def test_silu_kernels_vs_float64(dev, name):
     """silu_fwd and silu_bwd (scale 0.5) through the ABI; the backward written over da (the form
     the layer executor uses) equals the out-of-place one bit for bit."""
-    N, lib, st = _env()
+    N, lib, st = env()
     from speech2text_amd import conf_kernels as ck
     n = CC.CASES[name]["n"]
     t = CC.make(name)
     h, da = t["h"].to(dev), t["da"].to(dev)
-    a, dh, inp = _flat(dev, n), _flat(dev, n), _flat(dev, n)
+    a, dh, inp = Buf(dev, n), Buf(dev, n), Buf(dev, n)
     inp.t.view(-1).copy_(da)
     N.check(lib.s2t_silu_fwd(N.fp(h), n, N.fp(a.t), st), "s2t_silu_fwd")
     N.check(lib.s2t_silu_bwd(N.fp(h), N.fp(da), n, 0.5, N.fp(dh.t), st), "s2t_silu_bwd")
@@ -186,11 +152,11 @@ def test_silu_kernels_vs_float64(dev, name):
 def test_dropout_streams_vs_float64(dev, name):
     """dropout_add without and with x, silu_drop_fwd, silu_drop_bwd (scale 0.5): the keep pattern is
     oracle.conformer.keep_scale's at every element, the values are the yardstick's under that mask."""
-    N, lib, st = _env()
+    N, lib, st = env()
     c = CC.CASES[name]
     n, p, seed = c["n"], c["p"], c["dseed"]
     t = {k: v.to(dev) for k, v in CC.make(name).items()}
-    mask, add, grad, fwd, bwd = (_flat(dev, n) for _ in range(5))
+    mask, add, grad, fwd, bwd = (Buf(dev, n) for _ in range(5))
     ones = torch.ones(n, device=dev)
     N.check(lib.s2t_dropout_add(None, N.fp(ones), n, 1.0, p, seed, N.fp(mask.t), st), "s2t_dropout_add")
     N.check(lib.s2t_dropout_add(N.fp(t["x"]), N.fp(t["y"]), n, 0.5, p, seed, N.fp(add.t), st), "s2t_dropout_add")
@@ -217,15 +183,15 @@ def test_batchnorm_silu_vs_float64(dev, name):
     """Training forward (save vectors, running statistics, batch counter), backward into pre-filled
     dgamma / dbeta, and the evaluation pass, through the ABI; then the module path
     (conf_kernels.bn_silu_fwd / batchnorm_silu) must give the same bits, its momentum included."""
-    N, lib, st = _env()
+    N, lib, st = env()
     from speech2text_amd import conf_kernels as ck
     c = CC.CASES[name]
     R, C = c["rows"], c["C"]
     t = CC.make(name)
     gamma, beta, ds = t["gamma"].to(dev), t["beta"].to(dev), t["ds"].to(dev)
-    rm, rv = _put(dev, t["rm0"]), _put(dev, t["rv0"])
+    rm, rv = Buf(dev, (1, C), t["rm0"]), Buf(dev, (1, C), t["rv0"])
     nbt = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = Guarded(dev, N.const("S2T_BN_PARTIALS") + 1, 2 * C)
+    ws = Buf(dev, (N.const("S2T_BN_PARTIALS") + 1, 2 * C))
     assert ws.t.numel() == lib.s2t_bn_workspace_floats(C)
     bn = torch.nn.BatchNorm1d(C, eps=CC.EPS, momentum=c["momentum"], track_running_stats=c["track"]).to(dev)
     with torch.no_grad():
@@ -234,7 +200,7 @@ def test_batchnorm_silu_vs_float64(dev, name):
             bn.running_mean.copy_(t["rm0"]); bn.running_var.copy_(t["rv0"])
     for i, x0 in enumerate(t["xs"]):
         x = x0.to(dev)
-        y, mean, rstd = Guarded(dev, R, C), Guarded(dev, 1, C), Guarded(dev, 1, C)
+        y, mean, rstd = Buf(dev, (R, C)), Buf(dev, (1, C)), Buf(dev, (1, C))
         mom = 1.0 / (i + 1) if c["momentum"] is None else c["momentum"]
         N.check(lib.s2t_bn_silu_fwd(N.fp(x), N.fp(gamma), N.fp(beta), CC.EPS, mom if c["track"] else 0.0,
                                     N.fp(rm.t) if c["track"] else None, N.fp(rv.t) if c["track"] else None,
@@ -242,7 +208,7 @@ def test_batchnorm_silu_vs_float64(dev, name):
                                     N.fp(rstd.t), N.fp(ws.t), st), "s2t_bn_silu_fwd")
         y2, mean2, rstd2 = ck.bn_silu_fwd(x, bn)
         assert torch.equal(y2, y.t) and torch.equal(mean2, mean.t[0]) and torch.equal(rstd2, rstd.t[0])
-    dx, grads = Guarded(dev, R, C), Guarded(dev, 2, C)
+    dx, grads = Buf(dev, (R, C)), Buf(dev, (2, C))
     grads.t[0].copy_(t["dg0"]); grads.t[1].copy_(t["db0"])
     N.check(lib.s2t_bn_silu_bwd(N.fp(x), N.fp(ds), N.fp(mean.t), N.fp(rstd.t), N.fp(gamma), N.fp(beta), R, C,
                                 N.fp(dx.t), N.fp(grads.t[0]), N.fp(grads.t[1]), N.fp(ws.t), st), "s2t_bn_silu_bwd")
@@ -260,7 +226,7 @@ def test_batchnorm_silu_vs_float64(dev, name):
         assert int(nbt) == c["batches"] and int(bn.num_batches_tracked) == c["batches"]
         assert torch.equal(bn.running_mean, rm.t[0]) and torch.equal(bn.running_var, rv.t[0])
         got["running_mean"], got["running_var"] = rm.t[0], rv.t[0]
-        ye = Guarded(dev, R, C)
+        ye = Buf(dev, (R, C))
         ers = torch.rsqrt(rv.t[0] + CC.EPS)
         N.check(lib.s2t_bn_silu_apply(N.fp(xe), N.fp(rm.t[0]), N.fp(ers), N.fp(gamma), N.fp(beta), R, C,
                                       N.fp(ye.t), st), "s2t_bn_silu_apply")
@@ -278,10 +244,10 @@ def test_batchnorm_silu_vs_float64(dev, name):
 def _mhsa_abi(dev, c, qkv_buf, ld, offs, lens, do_buf, ldo, seed):
     """s2t_mhsa_fwd + s2t_mhsa_bwd on a (T*B [+ guard], ld) buffer holding q, k, v at column offsets
     `offs` -> guarded (o, lse, delta, dqkv), o and dqkv with rows of ldo / ld floats."""
-    N, lib, st = _env()
+    N, lib, st = env()
     T, B, H, dh = c["T"], c["B"], c["H"], c["dh"]
-    o, dqkv = Guarded(dev, T * B, ldo), Guarded(dev, T * B, ld)
-    lse, delta = Guarded(dev, B * H, T), Guarded(dev, B * H, T)
+    o, dqkv = Buf(dev, (T * B, ldo)), Buf(dev, (T * B, ld))
+    lse, delta = Buf(dev, (B * H, T)), Buf(dev, (B * H, T))
     sc = 1.0 / math.sqrt(dh)
     N.check(lib.s2t_mhsa_fwd(N.fp(qkv_buf), ld, offs[0], offs[1], offs[2], N.lp(lens), T, B, H, dh, sc,
                              c["p"], seed, N.fp(o.t), ldo, N.fp(lse.t), st), "s2t_mhsa_fwd")
@@ -347,7 +313,7 @@ def test_mhsa_strided_and_permuted_layout(dev, name):
     T, B, D = c["T"], c["B"], c["H"] * c["dh"]
     o0, _, _, dqkv0 = _mhsa_abi(dev, c, qkv, 3 * D, (0, D, 2 * D), lens, do, D, seed)
     ld, ldo = 3 * D + 8, D + 4
-    buf, dob = Guarded(dev, T * B, ld), Guarded(dev, T * B, ldo)
+    buf, dob = Buf(dev, (T * B, ld)), Buf(dev, (T * B, ldo))
     voff, qoff, koff = 0, D, 2 * D
     buf.t[:, qoff:qoff + D] = qkv[:, :D]
     buf.t[:, koff:koff + D] = qkv[:, D:2 * D]

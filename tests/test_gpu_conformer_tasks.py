@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import conformer as OC
+from task_support import _base_cfg, _CONF, _pcm_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -38,35 +39,6 @@ def test_conformer_vs_oracle(dev):
                 ref = sd[n].grad.numpy()
                 # (a bias in front of BatchNorm has zero true gradient: pure rounding noise)
                 assert np.abs(p.grad.cpu().numpy() - ref).max() <= 1e-2 * np.abs(ref).max() + 3e-4, n
-
-
-def _base_cfg(feat_type="fbank"):
-    return {"dataset": {"feat_type": feat_type,
-                        "feat_config": {"num_mel_bins": 80, "frame_length": 25, "frame_shift": 10,
-                                        "dither": 0.0} if feat_type == "fbank" else
-                        {"num_mel_bins": 80, "snip_edges": True}},
-            "optim_setup": {"seperate_lr": {"apply": False},
-                            "optimizer": {"type": "ScaledAdam", "config": {"lr": 0.045, "clipping_scale": 2.0}},
-                            "lr_scheduler": {"type": "Eden", "config": {"lr_batches": 7000},
-                                             "step_config": {"interval": "step", "frequency": 1}}},
-            "trainer": {"accelerator": "gpu", "devices": 1, "strategy": "ddp", "precision": "32-true",
-                        "max_epochs": 1, "accumulate_grad_batches": 2, "gradient_clip_val": 5.0,
-                        "gradient_clip_algorithm": "norm"}}
-
-
-_CONF = {"model": "Conformer", "config": {"bn_cmvn": False, "feats_dim": 80, "subsampling_rate": 4,
-                                          "input_dim": 64, "num_heads": 4, "ffn_dim": 128,
-                                          "num_layers": 2, "depthwise_conv_kernel_size": 15,
-                                          "dropout": 0.1, "output_dim": 64}}
-
-
-def _pcm_batch(dev, B=3, sec=2.0, U=6, V=32):
-    g = torch.Generator().manual_seed(1)
-    n = int(sec * 16000)
-    return {"pcm": (torch.randn(B, n, generator=g) * 0.1).to(dev),
-            "pcm_length": torch.tensor([n, n - 3000, n - 8000][:B]).to(dev),
-            "label": torch.randint(1, V - 1, (B, U), generator=g).to(dev),
-            "label_length": torch.tensor([U, U - 1, U - 3][:B]).to(dev)}
 
 
 def _run(task_cls, cfg, batch, dev, steps=4):

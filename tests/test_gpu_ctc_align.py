@@ -12,6 +12,7 @@ import torch
 
 import ctc_align_cases as C
 import ctc_align_f64 as A
+from task_support import _ctc_cfg, _pcm_batch, _task
 
 pytestmark = pytest.mark.gpu
 
@@ -192,9 +193,6 @@ def test_aligner_runs_the_kernel_on_device_tensors_and_the_loop_beyond_its_limit
 
 # ------------------------------------------------------------------ 5. the task
 def test_ctc_task_align_tiles_the_frames_in_order(dev, golden_dir):
-    from test_gpu_conformer_tasks import _pcm_batch
-    from test_gpu_ctc_prefix_beam import _ctc_cfg
-    from test_gpu_validation import _task
     cfg, V = _ctc_cfg(golden_dir)
     task = _task("CTC", cfg, dev)
     batch = _pcm_batch(dev, B=2, sec=1.0, V=V)

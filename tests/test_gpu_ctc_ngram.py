@@ -17,13 +17,9 @@ import torch
 import ctc_ngram_cases as C
 import ctc_ngram_f64 as G
 import ctc_prefix_cases as PC
+from yardstick import _Ids
 
 pytestmark = pytest.mark.gpu
-
-
-class _Tok:
-    def decode(self, t):
-        return [int(x) for x in t]
 
 
 _CACHE, _LMS = {}, {}
@@ -276,7 +272,7 @@ def test_class_fused_path_is_the_module_loop(dev, name):
     from speech2text_amd.model.lm.ngram_lm import NgramLm
     c, x, lens, _ = _case(dev, name)
     lm = NgramLm.from_arpa(C.text_of(name), num_classes=c["V"])           # on the CPU: it follows the logits
-    dec = CtcPrefixBeamDecoding(_Tok(), beam_size=c["beam"], cutoff_top_k=c["topk"], lm=lm, lm_weight=c["weight"])
+    dec = CtcPrefixBeamDecoding(_Ids(), beam_size=c["beam"], cutoff_top_k=c["topk"], lm=lm, lm_weight=c["weight"])
     fused = dec.beam_tokens(x, lens)
     assert lm.device == x.device
     loop = dec.beam_tokens(x, lens, fused=False)
@@ -287,7 +283,7 @@ def test_class_fused_path_is_the_module_loop(dev, name):
     ref = C.reference(name)
     assert dec.decode_batch(x, lens) == [r.tokens for r in ref]
     assert dec.decode(x[:1, :C.clamp(lens[0], c["T"])]) == ref[0].tokens
-    cpu = CtcPrefixBeamDecoding(_Tok(), beam_size=c["beam"], cutoff_top_k=c["topk"], lm=C.model(name),
+    cpu = CtcPrefixBeamDecoding(_Ids(), beam_size=c["beam"], cutoff_top_k=c["topk"], lm=C.model(name),
                                 lm_weight=c["weight"])
     assert cpu.decode_batch(x[:2].cpu(), lens[:2].cpu()) == [r.tokens for r in ref[:2]]     # CPU tensors: the loop
     assert C.model(name).device.type == "cpu"
@@ -297,7 +293,7 @@ def test_refused_shapes_take_the_module_loop_and_streams_refuse_the_ngram(dev):
     from speech2text_amd.model.decoding import CtcPrefixBeamDecoding, CtcStreamingSearch
     name = "n_v11_o2_b17_beam4_k3"
     c, x, lens, lm = _case(dev, name)
-    dec = CtcPrefixBeamDecoding(_Tok(), beam_size=17, cutoff_top_k=c["topk"], lm=lm, lm_weight=c["weight"])
+    dec = CtcPrefixBeamDecoding(_Ids(), beam_size=17, cutoff_top_k=c["topk"], lm=lm, lm_weight=c["weight"])
     assert dec._fused(x[:2], lens[:2]) is None
     out = dec.beam_tokens(x[:2], lens[:2])
     assert len(out) == 4 and out[0].is_cuda
@@ -307,4 +303,4 @@ def test_refused_shapes_take_the_module_loop_and_streams_refuse_the_ngram(dev):
     with pytest.raises(ValueError, match="NgramLm"):
         CtcStreamingSearch(c["V"], lm=lm, lm_weight=0.5, device=dev)
     with pytest.raises(ValueError, match="lm_start_token"):
-        CtcPrefixBeamDecoding(_Tok(), lm=lm, lm_weight=0.5, lm_start_token=1)
+        CtcPrefixBeamDecoding(_Ids(), lm=lm, lm_weight=0.5, lm_start_token=1)

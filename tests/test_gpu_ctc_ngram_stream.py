@@ -20,23 +20,18 @@ import torch
 
 import ctc_ngram_cases as G
 import ctc_ngram_stream_cases as C
+from decode_support import _lm_module, _ngram_lm, _tiny_ctc_encoder, _tokenizer
+from task_support import _ctc_zipformer_cfg
 
 pytestmark = pytest.mark.gpu
 
-_CACHE, _LMS, _PREFIX = {}, {}, {}
-
-
-def _lm(dev, text, V):
-    from speech2text_amd.model.lm.ngram_lm import NgramLm
-    if text not in _LMS:
-        _LMS[text] = NgramLm.from_arpa(text, num_classes=V).to(dev)
-    return _LMS[text]
+_CACHE, _PREFIX = {}, {}
 
 
 def _case(dev, name):
     if name not in _CACHE:
         x, lens = G.make(name)
-        _CACHE[name] = (C.CASES[name], x.to(dev), lens.to(dev), _lm(dev, G.text_of(name), C.CASES[name]["V"]))
+        _CACHE[name] = (C.CASES[name], x.to(dev), lens.to(dev), _ngram_lm(dev, G.text_of(name), C.CASES[name]["V"]))
     return _CACHE[name]
 
 
@@ -346,7 +341,7 @@ def test_entries_refuse_before_any_launch(dev, change):
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import CtcNgramStreamingSearch
     lib = N.lib()
-    lm = _lm(dev, G.lm_text(_V, 3, 200, 2), _V)
+    lm = _ngram_lm(dev, G.lm_text(_V, 3, 200, 2), _V)
     s = CtcNgramStreamingSearch(_V, batch_size=2, beam_size=4, cutoff_top_k=4, max_tokens=8, max_nodes=64,
                                 device=dev, lm=lm, lm_weight=0.3)
     x = torch.randn(2, 4, _V, generator=torch.Generator().manual_seed(3)).to(dev)
@@ -389,9 +384,8 @@ def test_empty_batch_and_the_python_surface(dev):
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import CtcNgramStreamingSearch, CtcStreamingSearch, ctc_streaming_search
     from speech2text_amd.model.lm.ngram_lm import NgramLm
-    from test_gpu_rnnt_lm_fusion import _lm_module
     lib = N.lib()
-    lm = _lm(dev, G.lm_text(_V, 3, 200, 2), _V)
+    lm = _ngram_lm(dev, G.lm_text(_V, 3, 200, 2), _V)
     desc, keep = lm.desc()
     assert lib.s2t_ctc_ngram_stream_state_bytes(0, _V, 4, 64) == 0
     assert lib.s2t_ctc_ngram_stream_reset(None, None, 0, _V, 99, 0, -1, N.stream()) == 0
@@ -437,10 +431,8 @@ def test_empty_batch_and_the_python_surface(dev):
 def test_recognizer_with_an_ngram_equals_the_one_shot_entry_on_its_scores(dev, golden_dir):
     from speech2text_amd.model.decoding import CtcNgramStreamingSearch, ctc_prefix_beam_ngram_tokens
     from speech2text_amd.model.encoder.zipformer_streaming import CtcStreamingRecognizer
-    from test_gpu_ctc_stream import _tiny_ctc_encoder
-    from test_rnnt_beam import _tokenizer
     g, m, chunk, V = _tiny_ctc_encoder(golden_dir, dev)
-    lm = _lm(dev, G.lm_text(V, 3, 200, 2), V)
+    lm = _ngram_lm(dev, G.lm_text(V, 3, 200, 2), V)
     feats = torch.from_numpy(g["feats"]).to(dev)
     B, T, Tc = feats.shape[0], 2 * chunk + 13, chunk // 2
     rec = CtcStreamingRecognizer(m, _tokenizer(V), batch_size=B, device=dev, beam_size=4, cutoff_top_k=4,
@@ -471,7 +463,6 @@ def test_task_streaming_recognizer_takes_an_explicit_ngram(dev):
     """CtcTask.streaming_recognizer(lm=<NgramLm>, lm_weight=) builds the fused recogniser; `recognize` runs."""
     from speech2text_amd.build_task import TaskFactory
     from speech2text_amd.model.decoding import CtcNgramStreamingSearch
-    from test_gpu_ctc_stream import _ctc_zipformer_cfg
     V, chunk = 32, 8
     torch.manual_seed(0)
     task = TaskFactory.get("CTC")(copy.deepcopy(_ctc_zipformer_cfg(V, chunk))).to(dev)
@@ -479,7 +470,7 @@ def test_task_streaming_recognizer_takes_an_explicit_ngram(dev):
     with torch.no_grad():
         for p in task._decoder.parameters():
             p.mul_(6.0)
-    lm = _lm(dev, G.lm_text(V, 3, 200, 2), V)
+    lm = _ngram_lm(dev, G.lm_text(V, 3, 200, 2), V)
     rec = task.streaming_recognizer(batch_size=2, lm=lm, lm_weight=0.4)
     s = rec.search
     assert type(s) is CtcNgramStreamingSearch and (s.beam_size, s.cutoff_top_k, s._lm_weight) == (3, 2, 0.4)

@@ -9,23 +9,18 @@ reference's tokens.
 """
 import copy
 import math
-import os
 
 import pytest
 import torch
-import yaml
 
 import ctc_prefix_cases as C
 import ctc_prefix_f64 as P
 import rnnt_lm_fusion_cases as L
-from test_gpu_rnnt_lm_fusion import _lm_module
+from decode_support import _lm_module
+from task_support import _ctc_cfg, _pcm_batch, _refs, _task
+from yardstick import _Ids
 
 pytestmark = pytest.mark.gpu
-
-
-class _Tok:
-    def decode(self, t):
-        return [int(x) for x in t]
 
 
 _CACHE = {}
@@ -232,7 +227,7 @@ def test_class_fused_path_is_the_module_loop(dev, name):
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import CtcPrefixBeamDecoding
     c, x, lens, lm = _case(dev, name)
-    dec = CtcPrefixBeamDecoding(_Tok(), beam_size=c["beam"], cutoff_top_k=c["topk"], lm=lm, lm_weight=c["weight"],
+    dec = CtcPrefixBeamDecoding(_Ids(), beam_size=c["beam"], cutoff_top_k=c["topk"], lm=lm, lm_weight=c["weight"],
                                 lm_start_token=c["start"])
     fused = dec.beam_tokens(x, lens)
     assert N.lib().s2t_gemm_arith_set(3) == 0              # the module's products at fp32 level
@@ -257,7 +252,7 @@ def test_refused_shapes_and_foreign_lms_take_the_module_loop(dev):
     assert _plain(c, x, lens, beam_size=17) is None and _fused(c, x, lens, lm, beam_size=17) is None
     ref = C.reference(name)
     sd = {k: v.to(dev) for k, v in L.cast(C.make(name)[2], torch.float64).items()}
-    dec = CtcPrefixBeamDecoding(_Tok(), beam_size=c["beam"], cutoff_top_k=c["topk"], lm=F.PlainLm(sd),
+    dec = CtcPrefixBeamDecoding(_Ids(), beam_size=c["beam"], cutoff_top_k=c["topk"], lm=F.PlainLm(sd),
                                 lm_weight=c["weight"])
     assert dec._fused(x, lens) is None
     out = dec.beam_tokens(x.double(), lens)
@@ -267,21 +262,10 @@ def test_refused_shapes_and_foreign_lms_take_the_module_loop(dev):
 
 
 # ------------------------------------------------------------------ 5. validation_step
-def _ctc_cfg(golden_dir):
-    root = os.path.join(golden_dir, "reference_configs")
-    cfg = yaml.safe_load(open(os.path.join(root, "config", "training", "conformer_ctc.yaml")))
-    for k in ("spm_model", "spm_vocab"):
-        cfg["tokenizer"]["config"][k] = os.path.join(root, cfg["tokenizer"]["config"][k])
-    cfg["encoder"]["config"].update({"input_dim": 64, "ffn_dim": 128, "num_layers": 2, "output_dim": 64,
-                                     "depthwise_conv_kernel_size": 15})
-    cfg["decoder"]["config"]["input_dim"] = 64
-    return cfg, cfg["decoder"]["config"]["output_dim"]
 
 
 def test_validation_step_logs_the_restatements_wer(dev, golden_dir):
     from oracle import decoding as OD
-    from test_gpu_conformer_tasks import _pcm_batch
-    from test_gpu_validation import _refs, _task
     cfg, V = _ctc_cfg(golden_dir)
     cfg = copy.deepcopy(cfg)
     cfg["metric"] = {"decode_method": "ctc_prefix_beam_search", "beam_size": 3, "cutoff_top_k": 3, "lm_weight": 0.5,

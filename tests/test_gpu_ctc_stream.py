@@ -12,16 +12,15 @@ at and beyond chunk_len[b] are NaN in every call.
 """
 import copy
 import math
-import os
 
-import numpy as np
 import pytest
 import torch
 
 import ctc_prefix_cases as C
 import ctc_stream_cases as SC
 import rnnt_lm_fusion_cases as L
-from test_gpu_rnnt_lm_fusion import _lm_module
+from decode_support import _lm_module, _tiny_ctc_encoder, _tokenizer
+from task_support import _ctc_zipformer_cfg
 
 pytestmark = pytest.mark.gpu
 
@@ -402,19 +401,6 @@ def test_reset_takes_a_device_mask(dev, with_lm):
 
 
 # ------------------------------------------------------------------ 3. the recogniser and the task
-def _tiny_ctc_encoder(golden_dir, dev):
-    from speech2text_amd.model.encoder.zipformer import Zipformer2, Zipformer2Config
-    from test_gpu_zipformer import TINY
-    g = np.load(os.path.join(golden_dir, "zipformer_tiny_stream.npz"))
-    chunk, left = int(g["chunk"]), int(g["left"])
-    sd = {k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("sd.")}
-    V = sd["_ctc_projection.weight"].shape[0]
-    m = Zipformer2(Zipformer2Config(**TINY, chunk_size=(chunk,), left_context_frames=(left,), for_ctc=True,
-                                    num_tokens=V))
-    m.load_state_dict(sd, strict=True)
-    with torch.no_grad():                                  # tokens on some frames, blank on others
-        m._ctc_projection.weight.mul_(4.0)
-    return g, m.to(dev).eval(), chunk, V
 
 
 @pytest.mark.parametrize("method", ["beam", "greedy", "beam_lm"])
@@ -425,7 +411,6 @@ def test_recognizer_graph_equals_the_eager_composition(dev, golden_dir, method):
     from speech2text_amd.model.decoding import (CtcStreamingSearch, ctc_greedy_tokens, ctc_prefix_beam_lm_tokens,
                                                 ctc_prefix_beam_tokens)
     from speech2text_amd.model.encoder.zipformer_streaming import CtcStreamingRecognizer, StreamingRecognizer
-    from test_rnnt_beam import _tokenizer
     g, m, chunk, V = _tiny_ctc_encoder(golden_dir, dev)
     assert V == 13 and m._for_ctc
     feats = torch.from_numpy(g["feats"]).to(dev)
@@ -486,22 +471,6 @@ def test_recognizer_graph_equals_the_eager_composition(dev, golden_dir, method):
     m.train()
     with pytest.raises(RuntimeError):
         CtcStreamingRecognizer(m, _tokenizer(V), device=dev)
-
-
-def _ctc_zipformer_cfg(V, chunk):
-    from test_rnnt_beam import _pruned_cfg
-    cfg = _pruned_cfg(V)
-    for k in ("predictor", "joiner"):
-        cfg.pop(k)
-    cfg["task"]["type"] = "CTC"
-    cfg["encoder"]["config"].update({"chunk_size": [chunk], "left_context_frames": [16]})
-    cfg["decoder"] = {"model": "Projector", "config": {"input_dim": 64, "output_dim": V, "dropout_p": 0.1}}
-    cfg["loss"] = {"model": "CTC", "config": {"blank_label": 0, "reduction": "mean"}}
-    cfg["metric"] = {"decode_method": "ctc_prefix_beam_search", "beam_size": 3, "cutoff_top_k": 2, "lm_weight": 0.5,
-                     "lm_start_token": V - 1,
-                     "lm": {"config": {"num_symbols": V, "symbol_embedding_dim": 16, "num_rnn_layer": 1},
-                            "checkpoint": None}}
-    return cfg
 
 
 def test_task_streaming_recognizer(dev):

@@ -3,22 +3,15 @@ buffer, bucket hooks firing from the autograd thread, side HIP stream, scalar sy
 ScaledAdam -- and must stay bit-identical replicas that follow the same trajectory as a
 single process fed the averaged gradient."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from task_support import _free_port
+
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, q):

@@ -8,10 +8,12 @@ Error = max |got - ref| / max |ref| per tensor; allowed = front_cases.bound(case
 max(2e-5, 8 x the case's float32 figure of the YARDSTICK, asserted by tests/test_front_f64.py).  The
 fbank is measured per frame in the energy domain (front_f64.fbank_err).  Frame counts, labels,
 SpecAugment, pad_rows and every copied-through frame are compared exactly.  Every buffer a kernel
-writes is allocated full of NaN with a guard behind it, which must be intact afterwards; inputs carry
+writes is a guarded buffer of tests/guarded.py, full of NaN (int64 outputs: of ISENT) with a guard of the
+same behind it, which must be intact afterwards; inputs carry
 NaN wherever a kernel must not read; accumulators are pre-filled and must hold pre-fill + reference;
 a call the entry point must refuse returns -1 and leaves its outputs untouched.
 """
+import functools
 import math
 
 import numpy as np
@@ -20,73 +22,22 @@ import torch
 
 import front_cases as FC
 import front_f64 as FF
+from guarded import ISENT, Buf, env, hold
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-ISENT = -7                                  # no label or frame count is negative
 LOG_EPS = float(np.float32(math.log(FF.EPS)))
 LOG_EPS_ULP = 2.0 ** -20                    # one float32 ulp at 15.94
+IBuf = functools.partial(Buf, fill=ISENT, dtype=torch.int64)      # labels, frame counts
+_hold = functools.partial(hold, FC)
 RUNS = dict(test_fbank_vs_float64="fb", test_row_energy_vs_float64="re", test_mix_vs_float64="mx",
             test_specaug_exact="sa", test_pad_rows_exact="pr", test_smoothed_nll_vs_float64="nll",
             test_bestrq_labels_exact="rq", test_predictor_context_vs_float64="pc")
 
 
-class Buf:
-    """A float32 device buffer of `shape`, NaN-filled (or holding src), with a guard of NaN behind it."""
-
-    def __init__(self, dev, shape, src=None):
-        shape = tuple(shape) if isinstance(shape, (tuple, list, torch.Size)) else (shape,)
-        self.n = int(np.prod(shape))
-        self.full = torch.full((self.n + max(64, shape[-1]),), NAN, dtype=torch.float32, device=dev)
-        self.t = self.full[:self.n].view(shape)
-        if src is not None:
-            self.t.copy_(src.reshape(shape))
-
-    def intact(self, what):
-        assert bool(torch.isnan(self.full[self.n:]).all()), f"{what}: the guard behind the buffer was written"
-
-    def untouched(self, what):
-        assert bool(torch.isnan(self.full).all()), f"{what}: a refused call wrote its output"
-
-
-class IBuf:
-    """The same for int64 outputs (labels, frame counts), filled with ISENT."""
-
-    def __init__(self, dev, shape):
-        shape = tuple(shape) if isinstance(shape, (tuple, list)) else (shape,)
-        self.n = int(np.prod(shape))
-        self.full = torch.full((self.n + 64,), ISENT, dtype=torch.int64, device=dev)
-        self.t = self.full[:self.n].view(shape)
-
-    def intact(self, what):
-        assert bool((self.full[self.n:] == ISENT).all()), f"{what}: the guard behind the buffer was written"
-
-    def untouched(self, what):
-        assert bool((self.full == ISENT).all()), f"{what}: a refused call wrote its output"
-
-
-def _hold(name, got):
-    """Every tensor of `got` within front_cases.bound of the float64 reference; all misses are reported."""
-    ref, bad = FC.reference(name), []
-    assert set(got) == set(ref), (sorted(got), sorted(ref))
-    for k, v in got.items():
-        assert bool(torch.isfinite(v).all()), f"{name} {k}: not finite"
-        err, tol = FC.rel_err(v.reshape(ref[k].shape), ref[k]), FC.bound(name, k)
-        print(f"{name} {k}: err {err:.3e} bound {tol:.3e} ratio {err / tol:.3f}")
-        if not err <= tol:
-            bad.append(f"{name} {k}: err {err:.3e} > bound {tol:.3e}")
-    assert not bad, "; ".join(bad)
-
-
-def _env():
-    from speech2text_amd import _native as N
-    return N, N.lib(), N.stream()
-
-
 # ------------------------------------------------------------------ fbank
 def _fbank_call(dev, tab, pcm, lens, M, scale, mf, mean=None, istd=None):
-    N, lib, st = _env()
+    N, lib, st = env()
     B = pcm.shape[0]
     out, frames = Buf(dev, (B, mf, M)), IBuf(dev, B)
     N.check(lib.s2t_fbank_f32(N.fp(pcm), pcm.stride(0), N.lp(lens), B, N.fp(tab.window), N.fp(tab.twiddle),
@@ -151,7 +102,7 @@ def test_fbank_vs_float64(dev, name):
 
 def test_fbank_refuses_129_bins_and_1025_filter_weights(dev):
     from speech2text_amd.kernels import FbankTables
-    N, lib, st = _env()
+    N, lib, st = env()
     tab = FbankTables(80, device=dev)
     pcm, nsamp = torch.zeros(1, 800, device=dev), torch.tensor([800], device=dev)
     w = torch.zeros(1025, device=dev)
@@ -167,7 +118,7 @@ def test_fbank_refuses_129_bins_and_1025_filter_weights(dev):
 # ------------------------------------------------------------------ augmentation
 @pytest.mark.parametrize("name", FC.names("re"))
 def test_row_energy_vs_float64(dev, name):
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = FC.CASES[name], FC.make(name)
     x, lens = t["x"].to(dev), torch.tensor(t["lens"], device=dev)
     out = Buf(dev, len(t["lens"]))
@@ -183,7 +134,7 @@ def test_row_energy_vs_float64(dev, name):
 def test_mix_vs_float64(dev, name):
     """Rows of stride rows_max D + 5 (NaN in the pad of the source, which the output's pad must keep);
     noise rows past nlen are NaN; frames past slen, and utterances without noise, bit for bit."""
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = FC.CASES[name], FC.make(name)
     B, R, D, ss = len(c["slen"]), c["rows"], c["D"], t["sstride"]
     src = Buf(dev, (B, ss))
@@ -207,7 +158,7 @@ def test_mix_vs_float64(dev, name):
 
 @pytest.mark.parametrize("name", FC.names("sa"))
 def test_specaug_exact(dev, name):
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = FC.CASES[name], FC.make(name)
     feats = Buf(dev, (c["B"], c["T"], c["F"]), t["feats"])
     tspan = t["tspan"].to(dev) if c["nt"] else None
@@ -221,7 +172,7 @@ def test_specaug_exact(dev, name):
 
 @pytest.mark.parametrize("name", FC.names("pr"))
 def test_pad_rows_exact(dev, name):
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = FC.CASES[name], FC.make(name)
     B = len(c["rows"])
     packed, offs = t["packed"].to(dev), torch.tensor(t["offsets"], device=dev)
@@ -233,7 +184,7 @@ def test_pad_rows_exact(dev, name):
 
 
 def test_augment_entries_refuse_bad_settings(dev):
-    N, lib, st = _env()
+    N, lib, st = env()
     x, n = torch.zeros(1, 8, device=dev), torch.tensor([8], device=dev)
     f, z = torch.zeros(1, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
     out = Buf(dev, 8)
@@ -251,7 +202,7 @@ def test_augment_entries_refuse_bad_settings(dev):
 @pytest.mark.parametrize("name", FC.names("nll"))
 def test_smoothed_nll_vs_float64(dev, name):
     """Row losses and the gradient (through the saved row statistics of the forward)."""
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = FC.CASES[name], FC.make(name)
     R, K = c["rows"], c["K"]
     a, b, c0 = FF.nll_consts(K, c["eps"], c["kind"])
@@ -272,7 +223,7 @@ def test_smoothed_nll_vs_float64(dev, name):
 # ------------------------------------------------------------------ BEST-RQ
 @pytest.mark.parametrize("name", FC.names("rq"))
 def test_bestrq_labels_exact(dev, name):
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = FC.CASES[name], FC.make(name)
     feats, proj, cb = (t[k].to(dev) for k in ("feats", "proj", "codebooks"))
     labels = IBuf(dev, (c["ncb"], c["B"], t["T2"]))
@@ -284,7 +235,7 @@ def test_bestrq_labels_exact(dev, name):
 
 
 def test_bestrq_refuses_a_bad_width_and_too_many_labels(dev):
-    N, lib, st = _env()
+    N, lib, st = env()
     feats, proj, cb = torch.zeros(1, 11, 4, device=dev), torch.zeros(36, 128, device=dev), torch.zeros(1, 4, 128, device=dev)
     for D, T, T2 in ((3, 11, 2), (48, 11, 2), (128, 11, 2), (16, 11, 3), (16, 10, 2), (16, 6, 1)):
         labels = IBuf(dev, (1, 1, 3))
@@ -295,7 +246,7 @@ def test_bestrq_refuses_a_bad_width_and_too_many_labels(dev):
 
 # ------------------------------------------------------------------ predictor context
 def _pc_call(dev, name, want_emb=True, want_w=True):
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = FC.CASES[name], FC.make(name)
     B, L, K, D, V = (c[k] for k in ("B", "L", "K", "D", "V"))
     Lo = L - K + 1
@@ -328,7 +279,7 @@ def test_predictor_context_backward_with_one_gradient_absent(dev, name):
 
 
 def test_predictor_context_refuses_nine_taps_and_a_row_shorter_than_the_taps(dev):
-    N, lib, st = _env()
+    N, lib, st = env()
     tok, emb, g = torch.zeros(2, 12, dtype=torch.int32, device=dev), torch.zeros(5, 8, device=dev), torch.zeros(2, 12, 8, device=dev)
     w = torch.zeros(8, 9, device=dev)
     for K, L, V in ((9, 12, 5), (4, 3, 5), (0, 12, 5), (2, 12, 0)):

@@ -5,16 +5,12 @@ import numpy as np
 import pytest
 import torch
 
+from loss_cases import _kern
 from oracle import ctc as octc
 from oracle import fbank as ofbank
 from oracle import k2_rnnt as K
 
 pytestmark = pytest.mark.gpu
-
-
-def _kern():
-    from speech2text_amd import kernels
-    return kernels
 
 
 # ------------------------------------------------------------------ fbank

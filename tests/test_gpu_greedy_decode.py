@@ -18,6 +18,8 @@ import numpy as np
 import pytest
 import torch
 
+from decode_support import _Tok
+
 pytestmark = pytest.mark.gpu
 
 
@@ -220,14 +222,6 @@ def test_rnnt_greedy_kernel_exact(dev, name):
         assert tokens[b, :len(ids)].tolist() == ids, (name, b)
         assert (tokens[b, len(ids):] == 0).all()
     assert int(out_len[1]) == 0                       # length 0
-
-
-class _Tok:
-    """Token ids -> text, one word per id (the decoders only call decode)."""
-    labels = []
-
-    def decode(self, ids):
-        return " ".join(str(int(i)) for i in ids)
 
 
 def _modules(dev, w, V, E, D, ctx, act):

@@ -53,24 +53,15 @@ import torch
 
 import lattice_f64 as L
 import loss_cases as LC
+from loss_cases import G_ATOL, G_RTOL, _assert_grad, _kern, _np
 from oracle import ctc as octc
 from oracle import k2_rnnt as K
 
 pytestmark = pytest.mark.gpu
 
-G_ATOL, G_RTOL = 3e-5, 2e-3            # gradients under weights that sum to about one
 CTC_SUM_ATOL = 3e-3                    # CTC gradients under unit weights
 CTC_RTOL, RNNT_RTOL = 2e-5, 1e-4       # losses
 BIG = 3.0e4                            # "large finite" filler of padded frames
-
-
-def _kern():
-    from speech2text_amd import kernels
-    return kernels
-
-
-def _np(t):
-    return t.detach().cpu().double().numpy()
 
 
 # ================================================================== CTC
@@ -260,12 +251,6 @@ def _check_ranges(rg, S, R, gx, gy, bnd):
     assert (rg >= 0).all() and (rg <= S).all()
     assert (s0[:, 1:] - s0[:, :-1] < rg.shape[2]).all()
     assert torch.equal(rg, K.get_rnnt_prune_ranges(gx.cpu(), gy.cpu(), bnd.cpu(), R))
-
-
-def _assert_grad(got, ref, atol=G_ATOL, rtol=G_RTOL, what=""):
-    got, ref = _np(got), _np(ref)
-    print(f"{what}: max abs dev {np.abs(got - ref).max():.3e} (atol {atol:.1e})")
-    np.testing.assert_allclose(got, ref, atol=atol, rtol=rtol)
 
 
 def _simple_ranges_pruned(dev, am, lm, sym, tl, el, R, blank, act, w, check_ranges=True):

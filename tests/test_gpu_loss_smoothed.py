@@ -26,6 +26,7 @@ import lattice_f64 as L
 import lattice_smoothed_f64 as LS
 import loss_cases as LC
 import loss_smoothed_cases as SC
+from loss_cases import _kern, _np
 from oracle import k2_rnnt as K
 
 pytestmark = pytest.mark.gpu
@@ -34,15 +35,6 @@ G_ATOL, G_RTOL = 3e-5, 2e-3            # gradients under weights that sum to abo
 RNNT_RTOL = 1e-4                       # losses
 OCC_ATOL = 2e-4                        # raw occupation counts
 BIG = 3.0e4                            # "large finite" filler of padded frames
-
-
-def _kern():
-    from speech2text_amd import kernels
-    return kernels
-
-
-def _np(t):
-    return t.detach().cpu().double().numpy()
 
 
 def _run(dev, c, am=None, scales=True):

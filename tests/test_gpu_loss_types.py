@@ -31,28 +31,13 @@ import lattice_f64 as L
 import lattice_types_f64 as LT
 import loss_cases as LC
 import loss_types_cases as TC
+from loss_cases import _assert_grad, _kern, _np
 
 pytestmark = pytest.mark.gpu
 
-G_ATOL, G_RTOL = 3e-5, 2e-3            # gradients under weights that sum to about one
 RNNT_RTOL = 1e-4                       # losses
 MI_ATOL = 2e-4                         # raw occupation gradients
 NEW_TYPES = ("modified", "constrained")
-
-
-def _kern():
-    from speech2text_amd import kernels
-    return kernels
-
-
-def _np(t):
-    return t.detach().cpu().double().numpy()
-
-
-def _assert_grad(got, ref, atol=G_ATOL, rtol=G_RTOL, what=""):
-    got, ref = _np(got), _np(ref)
-    print(f"{what}: max abs dev {np.abs(got - ref).max():.3e} (atol {atol:.1e})")
-    np.testing.assert_allclose(got, ref, atol=atol, rtol=rtol)
 
 
 def _assert_loss(got, ref, what=""):

@@ -11,10 +11,12 @@ import numpy as np
 import pytest
 import torch
 
+import decode_support as DS
 import lattice_types_f64 as LT
 import rnnt_align_cases as C
 import rnnt_align_f64 as A
-from lstm_cases import FLOOR, MARGIN
+from task_support import _base_cfg, _CONF, _pcm_batch, _pruned_cfg, _task, _TOK, _V
+from yardstick import FLOOR, MARGIN
 
 pytestmark = pytest.mark.gpu
 
@@ -119,8 +121,7 @@ def _stateless_pair(dev, V, D, act="relu"):
 
 
 def _lstm_pair(dev, V, D):
-    from test_gpu_rnnt_lstm_stream import _lstm_pair as make
-    return make(dev, V, D, 31, 2.0)
+    return DS._lstm_pair(dev, V, D, 31, 2.0)
 
 
 def _batch(dev, V, D, B=3, T=12, S=5):
@@ -293,8 +294,6 @@ def _check_task_alignment(out, batch, lens, labels_of, one_per_frame):
 
 @pytest.mark.parametrize("rnnt_type", ["regular", "modified"])
 def test_pruned_rnnt_task_align(dev, rnnt_type):
-    from test_gpu_conformer_tasks import _pcm_batch
-    from test_gpu_validation import _V, _pruned_cfg, _task
     cfg = _pruned_cfg()
     cfg["loss"]["config"] = {**cfg["loss"].get("config", {}), "rnnt_type": rnnt_type, "delay_penalty": 0.01}
     task = _task("Pruned_Rnnt", cfg, dev)
@@ -309,8 +308,6 @@ def test_pruned_rnnt_task_align(dev, rnnt_type):
 
 
 def test_rnnt_task_align_materialises_the_out_projection_joiner(dev):
-    from test_gpu_conformer_tasks import _CONF, _base_cfg, _pcm_batch
-    from test_gpu_validation import _TOK, _V, _task
     cfg = _base_cfg()
     cfg.update({"task": {"type": "Rnnt"}, "tokenizer": _TOK, "encoder": _CONF,
                 "decoder": {"model": "Identity", "config": {"dummy": -1}},

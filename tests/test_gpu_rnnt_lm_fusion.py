@@ -18,24 +18,10 @@ import rnnt_lm_fusion_cases as L
 import rnnt_lm_fusion_f64 as F
 import rnnt_lstm_search_cases as C
 import rnnt_lstm_search_f64 as S
-import test_gpu_rnnt_lstm_search as G
+from decode_support import _beam_modules, _decoder, _lm_module, _lstm_build, _lstm_modules, _TINY, _Tok, _weights_of
+from task_support import _pcm_batch, _refs, _rnnt_cfg, _task
 
 pytestmark = pytest.mark.gpu
-
-_Tok = G._Tok
-
-
-def _lm_module(dev, sd=None, V=None, H=None, layers=None):
-    """The project's RnnLm on the device, holding the state dict `sd` when given."""
-    from speech2text_amd.model.lm.rnn_lm import RnnLm, RnnLmConfig
-    if sd is not None:
-        V, H = sd["_embedding.weight"].shape
-        layers = sum(1 for k in sd if "weight_hh_l" in k)
-    with torch.device(dev):
-        lm = RnnLm(RnnLmConfig(num_symbols=V, symbol_embedding_dim=H, num_rnn_layer=layers))
-    if sd is not None:
-        lm.load_state_dict(sd, strict=True)
-    return lm.to(dev).eval().requires_grad_(False)
 
 
 _CACHE = {}
@@ -46,16 +32,9 @@ def _case(dev, name):
     if name not in _CACHE:
         c = L.CASES[name]
         w, act, am, lens, sd = L.make(name)
-        p, j = G._modules(dev, w, C.CASES[c["base"]]["model"])
+        p, j = _lstm_modules(dev, w, C.CASES[c["base"]]["model"])
         _CACHE[name] = (c, p, j, _lm_module(dev, sd), am.to(dev), lens.to(dev), L.reference(name))
     return _CACHE[name]
-
-
-def _decoder(c, p, j, lm, **kw):
-    from speech2text_amd.model.decoding import RnntBeamDecoding
-    args = dict(beam_size=c["beam"], cutoff_top_k=c["topk"], lm=lm, lm_weight=c["weight"], lm_start_token=c["start"])
-    args.update(kw)
-    return RnntBeamDecoding(_Tok(), p, j, **args)
 
 
 def _fused(c, p, j, lm, am, lens, **kw):
@@ -208,7 +187,7 @@ def test_batch_invariance(dev):
 
 
 # ------------------------------------------------------------------ 6. limits
-_V = G._TINY["V"]
+_V = _TINY["V"]
 
 
 def _tiny_run(dev, p, j, lm, **kw):
@@ -221,7 +200,7 @@ def _tiny_run(dev, p, j, lm, **kw):
 
 @pytest.mark.parametrize("H,layers", [(1024, 1), (8, 8)])
 def test_limits_just_inside_are_taken(dev, H, layers):
-    p, j = G._build(dev, **G._TINY)
+    p, j = _lstm_build(dev, **_TINY)
     lm = _lm_module(dev, V=_V, H=H, layers=layers)
     for start in (None, _V - 1):
         _, _, out = _tiny_run(dev, p, j, lm, lm_start_token=start)
@@ -237,7 +216,7 @@ def test_limits_just_outside_return_minus_one(dev, change):
     pointers are never followed (the workspace here is 256 bytes) and no output is touched."""
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import rnn_lm_desc, rnnt_lstm_desc
-    p, j = G._build(dev, **G._TINY)
+    p, j = _lstm_build(dev, **_TINY)
     lm = _lm_module(dev, V=_V, H=8, layers=1)
     desc, keep = rnnt_lstm_desc(p, j)
     lm_desc, lm_keep = rnn_lm_desc(lm)
@@ -272,7 +251,7 @@ def test_refused_shapes_take_the_module_loop(dev):
     """An LM wider than the limit, a vocabulary that is not the joiner's, a beam above 16: the wrapper
     returns None and the class answers with _module_loop_lm."""
     from speech2text_amd.model.decoding import RnntBeamDecoding
-    p, j = G._build(dev, **G._TINY)
+    p, j = _lstm_build(dev, **_TINY)
     wide = _lm_module(dev, V=_V, H=1028, layers=1)
     am, lens, out = _tiny_run(dev, p, j, wide)
     assert out is None
@@ -294,14 +273,13 @@ def test_refused_shapes_take_the_module_loop(dev):
 
 # ------------------------------------------------------------------ 7. the stateless predictor
 def test_stateless_predictor_takes_the_module_loop(dev):
-    import test_rnnt_beam as TB
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import RnntBeamDecoding
     c, am, lens, sd = L.stateless_case()
     ref = L.stateless_reference()
     print("stateless: float64 margins", [r[4] for r in ref], "tokens", [r[0] for r in ref])
     assert min(r[4] for r in ref) >= S.MARGIN and sum(len(r[0]) for r in ref) > 0
-    pred, join = TB._modules(c, dev)
+    pred, join = _beam_modules(c, dev)
     join._enc_proj = torch.nn.Identity()
     lm = _lm_module(dev, sd)
     dec = RnntBeamDecoding(_Tok(), pred.eval(), join.eval(), beam_size=c["beam"], cutoff_top_k=c["topk"], lm=lm,
@@ -322,9 +300,6 @@ def test_stateless_predictor_takes_the_module_loop(dev):
 # ------------------------------------------------------------------ 8. validation_step
 def test_validation_step_logs_the_restatements_wer(dev):
     from oracle import decoding as OD
-    from test_gpu_conformer_tasks import _pcm_batch
-    from test_gpu_validation import _refs, _task
-    from test_rnnt_lm_fusion_f64 import _rnnt_cfg
     cfg, V = _rnnt_cfg()
     cfg = copy.deepcopy(cfg)
     cfg["metric"].update({"lm_weight": 0.3, "lm": {"config": {"num_symbols": V, "symbol_embedding_dim": 24,
@@ -347,7 +322,7 @@ def test_validation_step_logs_the_restatements_wer(dev):
     with torch.no_grad():
         feat, n = task.features(batch)
         enc, el = task._encoder(feat, n)
-    w = G._weights_of(task._predictor, task._joiner)
+    w = _weights_of(task._predictor, task._joiner)
     sd = {k: v.detach().double().cpu() for k, v in sess._lm.state_dict().items()}
     hyps, plain, margins = [], [], []
     for b in range(enc.shape[0]):

@@ -19,16 +19,12 @@ import torch
 
 import rnnt_lm_stream_cases as K
 import rnnt_lstm_stream_cases as SC
-import test_gpu_rnnt_lm_fusion as GF
-import test_gpu_rnnt_lstm_search as LS
-import test_gpu_rnnt_lstm_stream as LT
-import test_gpu_rnnt_stateless_lm as GS
-import test_gpu_rnnt_stream_search as SS
-import test_rnnt_beam as TB
+import decode_support as DS
+from task_support import _pruned_beam_cfg
 
 pytestmark = pytest.mark.gpu
 
-_plan = LT._plan
+_plan = DS._plan
 
 
 # ------------------------------------------------------------------------------------ helpers
@@ -38,10 +34,10 @@ def _case(dev, name):
     w, act, am, lens, sd = K.make(name)
     c = K.CASES[name]
     if K.is_lstm(name):
-        p, j = LS._modules(dev, w, SC.CASES[c["base"]]["model"])
+        p, j = DS._lstm_modules(dev, w, SC.CASES[c["base"]]["model"])
     else:
-        p, j = GS._modules(dev, w, c)
-    return p, j, GF._lm_module(dev, sd), am.to(dev), lens.to(dev)
+        p, j = DS._stateless_modules(dev, w, c)
+    return p, j, DS._lm_module(dev, sd), am.to(dev), lens.to(dev)
 
 
 def _lens(name):
@@ -79,17 +75,17 @@ def _stream(dev, name, B=None, max_tokens=None, **kw):
 
 
 def _same(got, lm_score, want, rows=None):
-    """SS._same_rows on tokens / frames / out_len / score, torch.equal on lm_score."""
-    SS._same_rows(got, want, rows)
+    """DS._same_rows on tokens / frames / out_len / score, torch.equal on lm_score."""
+    DS._same_rows(got, want, rows)
     rows = range(len(lm_score)) if rows is None else rows
     for b in rows:
         assert torch.equal(lm_score[b], want[4][b]), (b, float(lm_score[b]), float(want[4][b]))
 
 
 def _feed(search, am, plan, snap=None, off=None):
-    """SS._feed; the snapshots and the result carry lm_score as a sixth tensor."""
+    """DS._feed; the snapshots and the result carry lm_score as a sixth tensor."""
     wrap = None if snap is None else (lambda o, out: snap(o, out + [search.lm_score.cpu().clone()]))
-    got, off = SS._feed(search, am, plan, snap=wrap, off=off)
+    got, off = DS._feed(search, am, plan, snap=wrap, off=off)
     return got + [search.lm_score.cpu().clone()], off
 
 
@@ -116,7 +112,7 @@ def test_chunks_equal_the_one_shot_fused_search(dev, name, partition):
 def _run7(dev, name):
     """The 7-frame partition of a case with the outputs after every chunk."""
     snaps = []
-    _feed(_stream(dev, name), _case(dev, name)[3], SS._regular(_lens(name), 7),
+    _feed(_stream(dev, name), _case(dev, name)[3], DS._regular(_lens(name), 7),
           snap=lambda off, out: snaps.append((off, out)))
     return snaps
 
@@ -143,7 +139,7 @@ def test_long_chunks_cross_the_trace_blocks(dev, name):
     stable = []
     for step in (16, 1):
         search = _stream(dev, name)
-        got, off = _feed(search, am, SS._regular(_lens(name), step))
+        got, off = _feed(search, am, DS._regular(_lens(name), step))
         assert off.tolist() == _lens(name).tolist()
         _same(got, got[5], want)
         assert int(search.overflow.sum()) == 0
@@ -218,11 +214,11 @@ def test_rows_are_independent_and_reset_alone(dev, name, start):
     assert lb > 0 and int(want[2][0]) > 0 and int(want[2][3]) > 0
     am = torch.stack([am_c[0]] * 4)
     plain_search = _stream(dev, name, B=4, **kw)
-    plain, _ = _feed(plain_search, am, SS._regular([la] * 4, 16))
+    plain, _ = _feed(plain_search, am, DS._regular([la] * 4, 16))
     _same(plain, plain[5], [x[[0, 0, 0, 0]] for x in want])
 
     search = _stream(dev, name, B=4, **kw)
-    plan = SS._regular([la] * 4, 16)
+    plan = DS._regular([la] * 4, 16)
     half = len(plan) // 2
     _, off = _feed(search, am, plan[:half])
     assert int(search.out_len[2]) > 0 and float(search.lm_score[2]) != 0.0
@@ -237,7 +233,7 @@ def test_rows_are_independent_and_reset_alone(dev, name, start):
     am2[2] = am_c[3]
     off[2] = 0
     rest = [np.array([q[0], q[1], 0, q[3]]) for q in plan[half:]]
-    for k, cl in enumerate(SS._regular([lb], 16)):                     # B rides along from its frame 0
+    for k, cl in enumerate(DS._regular([lb], 16)):                     # B rides along from its frame 0
         if k < len(rest):
             rest[k][2] = cl[0]
         else:
@@ -263,7 +259,7 @@ def test_idle_call_changes_nothing(dev, name):
     am = _case(dev, name)[3]
     want = _one_shot(dev, name)
     search = _stream(dev, name)
-    plan = SS._regular(_lens(name), 7)
+    plan = DS._regular(_lens(name), 7)
     _, off = _feed(search, am, plan[:3])
     assert int(search.out_len.sum()) > 0 and float(search.lm_score.abs().sum()) > 0
     outs = (search.state, search.tokens, search.frames, search.out_len, search.score, search.lm_score,
@@ -290,7 +286,7 @@ def test_capacity(dev, name):
     assert len(rows) >= 2, (name, want[2].tolist())
     search = _stream(dev, name, B=len(rows), max_tokens=3)
     lens = _lens(name)[rows]
-    got, _ = _feed(search, am[rows].contiguous(), SS._regular(lens, 7))
+    got, _ = _feed(search, am[rows].contiguous(), DS._regular(lens, 7))
     assert got[2].tolist() == [3] * len(rows) and search.overflow.tolist() == [1] * len(rows)
     assert torch.equal(got[0], want[0][rows, :3]) and torch.equal(got[1], want[1][rows, :3])
     assert torch.equal(got[3], want[3][rows]) and torch.equal(got[5], want[4][rows])
@@ -299,7 +295,7 @@ def test_capacity(dev, name):
     torch.cuda.synchronize()
     assert search.overflow.tolist() == [0] * len(rows) and search.out_len.tolist() == [0] * len(rows)
     assert search.lm_score.tolist() == [0.0] * len(rows)
-    _feed(search, am[rows].contiguous(), SS._regular(lens, 1)[:1])
+    _feed(search, am[rows].contiguous(), DS._regular(lens, 1)[:1])
     assert search.overflow.tolist() == [0] * len(rows)                  # one frame: at most one token
 
 
@@ -331,9 +327,9 @@ def test_weight_zero_gives_the_bits_of_the_search_without_an_lm(dev, name):
     assert plain.lm_score is None
     fused = _stream(dev, name, lm_weight=0.0)
     a, b = [], []
-    plan = SS._regular(_lens(name), 7)
-    SS._feed(plain, am, plan, snap=lambda off, out: a.append(out + [plain.overflow.cpu().clone()]))
-    SS._feed(fused, am, plan, snap=lambda off, out: b.append(out + [fused.overflow.cpu().clone()]))
+    plan = DS._regular(_lens(name), 7)
+    DS._feed(plain, am, plan, snap=lambda off, out: a.append(out + [plain.overflow.cpu().clone()]))
+    DS._feed(fused, am, plan, snap=lambda off, out: b.append(out + [fused.overflow.cpu().clone()]))
     assert len(a) == len(b) == len(plan)
     for x, y in zip(a, b):
         for u, v in zip(x, y):                             # tokens, frames, out_len, score, stable_len, overflow
@@ -350,20 +346,20 @@ def test_refusals(dev, family):
     lib = N.lib()
     V, B, MT = 16, 2, 10
     if family == "lstm":
-        p, j = LS._build(dev, **LS._TINY)
+        p, j = DS._lstm_build(dev, **DS._TINY)
         desc, keep = rnnt_lstm_desc(p, j)
         bad, keep_bad = rnnt_lstm_desc(p, j)
         keep_bad[-1].H = 1028
     else:
-        p, j = GS._build(dev, V, 8, 8, 2, inner=8)
+        p, j = DS._stateless_build(dev, V, 8, 8, 2, inner=8)
         desc, keep = rnnt_stateless_desc(p, j)
         bad, keep_bad = rnnt_stateless_desc(p, j)
         keep_bad[-1].ctx = 65
-    lm = GF._lm_module(dev, V=V, H=8, layers=1)
+    lm = DS._lm_module(dev, V=V, H=8, layers=1)
     lmd, lm_keep = rnn_lm_desc(lm)
     bad_lm, bad_lm_keep = rnn_lm_desc(lm)
     bad_lm_keep[-1].H = 1028
-    other_v, other_keep = rnn_lm_desc(GF._lm_module(dev, V=V + 1, H=8, layers=1))
+    other_v, other_keep = rnn_lm_desc(DS._lm_module(dev, V=V + 1, H=8, layers=1))
     fam = family
     state_bytes = getattr(lib, f"s2t_rnnt_{fam}_lm_stream_state_bytes")
     ws_bytes = getattr(lib, f"s2t_rnnt_{fam}_lm_stream_workspace_bytes")
@@ -414,11 +410,11 @@ def test_refusals(dev, family):
 def test_classes_refuse_what_the_kernels_do_not_take(dev):
     from speech2text_amd.model.decoding import (RnntLstmStreamingSearch, RnntStatelessLmStreamingSearch,
                                                 RnntStreamingSearch, rnnt_streaming_search)
-    V = LS._TINY["V"]
-    p, j = LS._build(dev, **LS._TINY)
-    sp, sj = GS._build(dev, V, 8, 8, 2, inner=8)
-    sp0, sj0 = GS._build(dev, V, 8, 8, 2)
-    lm = GF._lm_module(dev, V=V, H=8, layers=1)
+    V = DS._TINY["V"]
+    p, j = DS._lstm_build(dev, **DS._TINY)
+    sp, sj = DS._stateless_build(dev, V, 8, 8, 2, inner=8)
+    sp0, sj0 = DS._stateless_build(dev, V, 8, 8, 2)
+    lm = DS._lm_module(dev, V=V, H=8, layers=1)
     a = rnnt_streaming_search(p, j, 2, "beam", device=dev, lm=lm, lm_weight=0.3)
     assert isinstance(a, RnntLstmStreamingSearch) and a.lm_score is not None and a.lm_score.shape == (2,)
     assert rnnt_streaming_search(p, j, 2, "beam", device=dev).lm_score is None
@@ -439,27 +435,27 @@ def test_classes_refuse_what_the_kernels_do_not_take(dev):
         with pytest.raises(ValueError):
             cls(*pair, 2, "beam", max_tokens=0, device=dev, lm=lm)
         with pytest.raises(ValueError):                                 # lm.V != V
-            cls(*pair, 2, "beam", device=dev, lm=GF._lm_module(dev, V=V + 1, H=8, layers=1))
+            cls(*pair, 2, "beam", device=dev, lm=DS._lm_module(dev, V=V + 1, H=8, layers=1))
         with pytest.raises(ValueError):                                 # H just outside the limit
-            cls(*pair, 2, "beam", device=dev, lm=GF._lm_module(dev, V=V, H=1028, layers=1))
+            cls(*pair, 2, "beam", device=dev, lm=DS._lm_module(dev, V=V, H=1028, layers=1))
         with pytest.raises(ValueError):                                 # layers just outside the limit
-            cls(*pair, 2, "beam", device=dev, lm=GF._lm_module(dev, V=V, H=8, layers=9))
+            cls(*pair, 2, "beam", device=dev, lm=DS._lm_module(dev, V=V, H=8, layers=9))
         with pytest.raises(ValueError):
             cls(*pair, 2, "beam", device=dev, lm=lm, lm_start_token=V)
         with pytest.raises(RuntimeError):                               # an LM off the GPU
-            cls(*pair, 2, "beam", device=dev, lm=GF._lm_module("cpu", V=V, H=8, layers=1))
+            cls(*pair, 2, "beam", device=dev, lm=DS._lm_module("cpu", V=V, H=8, layers=1))
         with pytest.raises(ValueError):
             cls(*pair, 2, "beam", device=dev, lm=lm).step(torch.zeros(2, 257, V, device=dev))
     with pytest.raises(ValueError):
-        RnntLstmStreamingSearch(*LS._build(dev, **dict(LS._TINY, H=1028)), 2, "beam", device=dev, lm=lm)
+        RnntLstmStreamingSearch(*DS._lstm_build(dev, **dict(DS._TINY, H=1028)), 2, "beam", device=dev, lm=lm)
     with pytest.raises(ValueError):
-        RnntStatelessLmStreamingSearch(*GS._build(dev, V, 8, 8, 65), 2, "beam", device=dev, lm=lm)
+        RnntStatelessLmStreamingSearch(*DS._stateless_build(dev, V, 8, 8, 65), 2, "beam", device=dev, lm=lm)
 
 
 # ------------------------------------------------------------------------------------ 11. recogniser
 def _peaky_lm(dev, V, seed):
     torch.manual_seed(seed)
-    lm = GF._lm_module(dev, V=V, H=16, layers=1)
+    lm = DS._lm_module(dev, V=V, H=16, layers=1)
     with torch.no_grad():
         lm._logits_layer.weight.mul_(16.0)
     return lm
@@ -467,7 +463,7 @@ def _peaky_lm(dev, V, seed):
 
 def _stateless_out_projection_pair(dev, V, D, seed, blank):
     """A stateless predictor and a joiner WITH output projection of fresh weights, times 3, blank lifted
-    behind the out-projection (LT._lstm_pair's construction)."""
+    behind the out-projection (DS._lstm_pair's construction)."""
     from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
     from speech2text_amd.model.predictor.predictor import Predictor
     torch.manual_seed(seed)
@@ -491,19 +487,19 @@ def test_recognizer_graph_equals_the_eager_composition(dev, golden_dir, family):
                                                 rnnt_beam_lstm_lm_tokens_from_am,
                                                 rnnt_beam_stateless_lm_tokens_from_am)
     from speech2text_amd.model.encoder.zipformer_streaming import StreamingRecognizer
-    g, m, chunk = SS._tiny_stream_encoder(golden_dir, dev)
+    g, m, chunk = DS._tiny_stream_encoder(golden_dir, dev)
     V, D = 24, max(m.encoder_dim)
     if family == "lstm":
-        pred, join = LT._lstm_pair(dev, V, D, 31, LT.RECOGNIZER_BLANK)
+        pred, join = DS._lstm_pair(dev, V, D, 31, DS.RECOGNIZER_BLANK)
         cls, one_shot = RnntLstmStreamingSearch, rnnt_beam_lstm_lm_tokens_from_am
     else:
-        pred, join = _stateless_out_projection_pair(dev, V, D, 31, LT.RECOGNIZER_BLANK)
+        pred, join = _stateless_out_projection_pair(dev, V, D, 31, DS.RECOGNIZER_BLANK)
         cls, one_shot = RnntStatelessLmStreamingSearch, rnnt_beam_stateless_lm_tokens_from_am
     lm = _peaky_lm(dev, V, 32)
     feats = torch.from_numpy(g["feats"]).to(dev)
     B, T, Tc = feats.shape[0], 2 * chunk + 13, chunk // 2
     kw = dict(method="beam", beam_size=4, cutoff_top_k=4, max_tokens=64, lm=lm, lm_weight=0.3, lm_start_token=V - 1)
-    rec = StreamingRecognizer(m, pred, join, TB._tokenizer(V), batch_size=B, device=dev, **kw)
+    rec = StreamingRecognizer(m, pred, join, DS._tokenizer(V), batch_size=B, device=dev, **kw)
     assert isinstance(rec.search, cls) and rec.search.lm_score is not None
     eager = cls(pred, join, B, device=dev, **kw)
     for rep in range(2):
@@ -557,7 +553,7 @@ def test_task_streaming_recognizer_hands_over_the_metric_lm(dev, tmp_path):
     from speech2text_amd.model.decoding import RnntLstmStreamingSearch
     from speech2text_amd.model.lm.rnn_lm import RnnLm, RnnLmConfig
     V, chunk = 32, 8
-    cfg = TB._pruned_cfg(V)
+    cfg = _pruned_beam_cfg(V)
     cfg["encoder"]["config"].update({"chunk_size": [chunk], "left_context_frames": [16]})
     cfg["predictor"] = {"model": "Lstm", "config": {
         "num_symbols": V, "output_dim": 64, "symbol_embedding_dim": 32, "num_lstm_layers": 2,

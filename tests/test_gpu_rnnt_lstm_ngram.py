@@ -18,23 +18,14 @@ import pytest
 import torch
 
 import rnnt_lstm_ngram_cases as C
-import test_gpu_rnnt_lstm_search as LS
+from decode_support import _lstm_build, _lstm_pair, _ngram_lm, RECOGNIZER_BLANK, _tiny_stream_encoder, _tokenizer
 
 pytestmark = pytest.mark.gpu
-
-_LMS = {}
-
-
-def _lm(dev, text, V):
-    from speech2text_amd.model.lm.ngram_lm import NgramLm
-    if text not in _LMS:
-        _LMS[text] = NgramLm.from_arpa(text, num_classes=V).to(dev)
-    return _LMS[text]
 
 
 def _modules(dev, w, m):
     """The project's LstmPredictor + Joiner holding the weights `w` of the model dict m."""
-    p, j = LS._build(dev, m["V"], m["E"], m["H"], m["D"], m["L"], m["ln"], m["inner"], m["act"])
+    p, j = _lstm_build(dev, m["V"], m["E"], m["H"], m["D"], m["L"], m["ln"], m["inner"], m["act"])
     q = p.predictor._predictor
     with torch.no_grad():
         for dst, src in ((q.embedding.weight, "emb"), (q.input_layer_norm.weight, "in_g"),
@@ -64,7 +55,7 @@ def _case(dev, name):
     c = C.CASES[name]
     w, _, am, lens = C.make(name)
     p, j = _modules(dev, w, c["m"])
-    return c, p, j, _lm(dev, C.text_of(name), c["m"]["V"]), am.to(dev), lens.to(dev)
+    return c, p, j, _ngram_lm(dev, C.text_of(name), c["m"]["V"]), am.to(dev), lens.to(dev)
 
 
 @functools.lru_cache(maxsize=None)
@@ -404,7 +395,7 @@ def test_empty_batch_and_the_class_surface(dev):
     s = RnntLstmNgramStreamingSearch(p, j, 2, device=dev, lm=cpu, lm_weight=0.3)           # tables copied over
     assert s._lm.device.type == "cuda" and cpu.device.type == "cpu" and s.lm_score.shape == (2,)
     assert s.method == "beam" and len(s.step(am[:2, :3].contiguous())) == 5
-    other = _lm(dev, C.text_of("n_v65_l2_t90"), 65)
+    other = _ngram_lm(dev, C.text_of("n_v65_l2_t90"), 65)
     for kw in (dict(beam_size=17), dict(beam_size=0), dict(cutoff_top_k=0), dict(max_tokens=0),
                dict(lm_weight=math.inf), dict(lm=None), dict(lm=other)):
         args = dict(beam_size=4, cutoff_top_k=4, max_tokens=8, device=dev, lm=lm, lm_weight=0.3)
@@ -433,23 +424,20 @@ def test_decoding_class_routes_the_lstm_pair_to_the_fused_entry(dev, name):
 
 
 def test_recognizer_for_the_lstm_pair_equals_the_one_shot_call(dev, golden_dir):
-    import test_gpu_rnnt_lstm_stream as LT
-    import test_gpu_rnnt_stream_search as SS
-    import test_rnnt_beam as TB
     from speech2text_amd.model.decoding import RnntLstmNgramStreamingSearch, rnnt_beam_lstm_ngram_tokens_from_am
     from speech2text_amd.model.encoder.zipformer_streaming import StreamingRecognizer
     import ctc_ngram_cases as CN
-    g, m, chunk = SS._tiny_stream_encoder(golden_dir, dev)
+    g, m, chunk = _tiny_stream_encoder(golden_dir, dev)
     V, D = 24, max(m.encoder_dim)
-    pred, join = LT._lstm_pair(dev, V, D, 31, LT.RECOGNIZER_BLANK)
-    lm = _lm(dev, CN.lm_text(V, 3, 200, 2), V)
+    pred, join = _lstm_pair(dev, V, D, 31, RECOGNIZER_BLANK)
+    lm = _ngram_lm(dev, CN.lm_text(V, 3, 200, 2), V)
     feats = torch.from_numpy(g["feats"]).to(dev)
     B, T, Tc = feats.shape[0], 2 * chunk + 13, chunk // 2
-    rec = StreamingRecognizer(m, pred, join, TB._tokenizer(V), batch_size=B, device=dev, method="beam", beam_size=4,
+    rec = StreamingRecognizer(m, pred, join, _tokenizer(V), batch_size=B, device=dev, method="beam", beam_size=4,
                               cutoff_top_k=4, max_tokens=64, lm=lm, lm_weight=0.4)
     assert type(rec.search) is RnntLstmNgramStreamingSearch
     with pytest.raises(ValueError, match="lm_start_token"):
-        StreamingRecognizer(m, pred, join, TB._tokenizer(V), batch_size=B, device=dev, method="beam", lm=lm,
+        StreamingRecognizer(m, pred, join, _tokenizer(V), batch_size=B, device=dev, method="beam", lm=lm,
                             lm_weight=0.4, lm_start_token=1)
     for rep in range(2):
         rec.reset()

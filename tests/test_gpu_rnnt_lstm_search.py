@@ -16,94 +16,10 @@ import torch
 
 import rnnt_lstm_search_cases as C
 import rnnt_lstm_search_f64 as S
+from decode_support import _lstm_build, _lstm_case, _lstm_modules, _TINY, _Tok, _weights_of
+from task_support import _base_cfg, _CONF, _pcm_batch, _refs, _task, _TOK, _V
 
 pytestmark = pytest.mark.gpu
-
-
-class _Tok:
-    """Token ids -> text, one word per id (the decoders only call decode)."""
-    labels = []
-
-    def decode(self, ids):
-        return " ".join(str(int(i)) for i in ids)
-
-
-def _build(dev, V, E, H, D, L, ln, inner, act):
-    from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
-    from speech2text_amd.model.predictor.predictor import Predictor
-    torch.manual_seed(V + H)
-    p = Predictor({"model": "Lstm", "config": {
-        "num_symbols": V, "output_dim": D, "symbol_embedding_dim": E, "num_lstm_layers": L,
-        "lstm_hidden_dim": H, "lstm_layer_norm": ln, "lstm_layer_norm_epsilon": C.EPS_LSTM, "lstm_dropout": 0.0}})
-    j = Joiner(JoinerConfig(input_dim=D, output_dim=V, inner_dim=inner or 8, activation=act,
-                            use_out_project=bool(inner)))
-    j._enc_proj = torch.nn.Identity()                     # the searches are handed am itself
-    return p.to(dev).eval(), j.to(dev).eval()
-
-
-def _modules(dev, w, model):
-    """The project's LstmPredictor + Joiner holding the weights `w` of MODELS[model]."""
-    m = C.MODELS[model]
-    p, j = _build(dev, m["V"], m["E"], m["H"], m["D"], m["L"], m["ln"], m["inner"], m["act"])
-    q = p.predictor._predictor
-    with torch.no_grad():
-        for dst, src in ((q.embedding.weight, "emb"), (q.input_layer_norm.weight, "in_g"),
-                         (q.input_layer_norm.bias, "in_b"), (q.linear.weight, "lin_w"),
-                         (q.linear.bias, "lin_b"), (q.output_layer_norm.weight, "out_g"),
-                         (q.output_layer_norm.bias, "out_b"), (j._pre_proj.weight, "pre_w"),
-                         (j._pre_proj.bias, "pre_b")):
-            dst.copy_(w[src])
-        for lstm, lw in zip(q.lstm_layers, w["layers"]):
-            lstm.x2g.weight.copy_(lw["x2g_w"])
-            lstm.p2g.weight.copy_(lw["wp"])
-            if m["ln"]:
-                for mod, a, b in ((lstm.g_norm, "gg", "gb"), (lstm.c_norm, "cg", "cb")):
-                    mod.weight.copy_(lw[a])
-                    mod.bias.copy_(lw[b])
-            else:
-                lstm.x2g.bias.copy_(lw["x2g_b"])
-        if m["inner"]:
-            for lin, a, b in ((j._out_projection[0], "o1_w", "o1_b"), (j._out_projection[1], "o2_w", "o2_b")):
-                lin.weight.copy_(w[a])
-                lin.bias.copy_(w[b])
-    assert q.input_layer_norm.eps == C.EPS_IN and q.output_layer_norm.eps == C.EPS_OUT
-    return p, j
-
-
-def _weights_of(p, j):
-    """The restatement's weights (float64, CPU) of a task's modules."""
-    q = p.predictor._predictor
-    t = lambda x: None if x is None else x.detach().double().cpu()      # noqa: E731
-    ln = isinstance(q.lstm_layers[0].g_norm, torch.nn.LayerNorm)
-    w = dict(emb=t(q.embedding.weight), in_g=t(q.input_layer_norm.weight), in_b=t(q.input_layer_norm.bias),
-             lin_w=t(q.linear.weight), lin_b=t(q.linear.bias), out_g=t(q.output_layer_norm.weight),
-             out_b=t(q.output_layer_norm.bias), pre_w=t(j._pre_proj.weight), pre_b=t(j._pre_proj.bias),
-             eps_in=q.input_layer_norm.eps, eps_out=q.output_layer_norm.eps,
-             eps_lstm=q.lstm_layers[0].g_norm.eps if ln else 0.0, layers=[])
-    for m in q.lstm_layers:
-        lw = dict(x2g_w=t(m.x2g.weight), wp=t(m.p2g.weight))
-        if ln:
-            lw.update(gg=t(m.g_norm.weight), gb=t(m.g_norm.bias), cg=t(m.c_norm.weight), cb=t(m.c_norm.bias))
-        else:
-            lw["x2g_b"] = t(m.x2g.bias)
-        w["layers"].append(lw)
-    if j._use_out_project:
-        w.update(o1_w=t(j._out_projection[0].weight), o1_b=t(j._out_projection[0].bias),
-                 o2_w=t(j._out_projection[1].weight), o2_b=t(j._out_projection[1].bias))
-    return w
-
-
-_CACHE = {}
-
-
-def _case(dev, name):
-    """(case, modules, am and lengths on the device, the float64 results), built once per case."""
-    if name not in _CACHE:
-        c = C.CASES[name]
-        w, act, am, lens = C.make(name)
-        p, j = _modules(dev, w, c["model"])
-        _CACHE[name] = (c, p, j, am.to(dev), lens.to(dev), C.reference(name))
-    return _CACHE[name]
 
 
 # ------------------------------------------------------------------ 1. the predictor step alone
@@ -112,7 +28,7 @@ def test_pred_step_chain(dev, model):
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import rnnt_lstm_desc
     m, R = C.MODELS[model], C.PRED_ROWS
-    p, j = _modules(dev, C.weights(model, 100), model)
+    p, j = _lstm_modules(dev, C.weights(model, 100), model)
     desc, keep = rnnt_lstm_desc(p, j)
     nbytes = N.lib().s2t_rnnt_lstm_workspace_bytes(desc, R, 0, 0)
     assert nbytes > 0
@@ -153,7 +69,7 @@ def test_pred_step_chain(dev, model):
 @pytest.mark.parametrize("name", list(C.GREEDY_CASES))
 def test_greedy_exact(dev, name):
     from speech2text_amd.model.decoding import RnntGreedyDecoding, rnnt_greedy_lstm_tokens_from_am
-    c, p, j, am, lens, ref = _case(dev, name)
+    c, p, j, am, lens, ref = _lstm_case(dev, name)
     max_out = c["T"] * (c["mts"] + 1)
     dec = RnntGreedyDecoding(_Tok(), p, j, max_token_step=c["mts"])
     assert dec._lstm_search() and not dec._fusable() and not dec._fused()
@@ -178,7 +94,7 @@ def test_greedy_exact(dev, name):
 def test_beam_exact(dev, name):
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import RnntBeamDecoding, rnnt_beam_lstm_tokens_from_am
-    c, p, j, am, lens, ref = _case(dev, name)
+    c, p, j, am, lens, ref = _lstm_case(dev, name)
     dec = RnntBeamDecoding(_Tok(), p, j, beam_size=c["beam"], cutoff_top_k=c["topk"])
     assert dec._lstm_search() and not dec._fusable()
     want = torch.tensor([r[1] for r in ref])
@@ -215,14 +131,14 @@ def test_beam_exact(dev, name):
 def test_batch_invariance(dev):
     """Utterance b alone, inside the first 17 and inside all 33: bit-identical tokens (and score)."""
     from speech2text_amd.model.decoding import rnnt_beam_lstm_tokens_from_am, rnnt_greedy_lstm_tokens_from_am
-    c, p, j, am, lens, _ = _case(dev, "g_h64_b33_mts0")
+    c, p, j, am, lens, _ = _lstm_case(dev, "g_h64_b33_mts0")
     runs = {n: rnnt_greedy_lstm_tokens_from_am(am[:n], lens[:n], p, j, c["mts"]) for n in (17, 33)}
     for b in (0, 2, 7, 15, 16):
         alone = rnnt_greedy_lstm_tokens_from_am(am[b:b + 1], lens[b:b + 1], p, j, c["mts"])
         for n, (tokens, out_len) in runs.items():
             assert torch.equal(alone[0][0], tokens[b]) and torch.equal(alone[1][0], out_len[b]), (b, n)
     assert torch.equal(runs[17][0], runs[33][0][:17])
-    c, p, j, am, lens, _ = _case(dev, "b_h64o_b33_beam4_k1")
+    c, p, j, am, lens, _ = _lstm_case(dev, "b_h64o_b33_beam4_k1")
     runs = {n: rnnt_beam_lstm_tokens_from_am(am[:n], lens[:n], p, j, c["beam"], 4) for n in (17, 33)}
     for b in (0, 2, 7, 15, 16):
         alone = rnnt_beam_lstm_tokens_from_am(am[b:b + 1], lens[b:b + 1], p, j, c["beam"], 4)
@@ -234,7 +150,6 @@ def test_batch_invariance(dev):
 
 
 # ------------------------------------------------------------------ 5. refusals
-_TINY = dict(V=16, E=8, H=8, D=8, L=1, ln=True, inner=0, act="relu")
 
 
 def _run_both(dev, p, j, V, beam=4, topk=4, T=2):
@@ -252,7 +167,7 @@ def test_limits_just_inside_are_taken(dev, change):
     change = dict(change)
     beam, topk = change.pop("beam", 4), change.pop("topk", 4)
     dims = dict(_TINY, **change)
-    p, j = _build(dev, **dims)
+    p, j = _lstm_build(dev, **dims)
     _, _, greedy, beams = _run_both(dev, p, j, dims["V"], beam, topk)
     assert greedy is not None and beams is not None
     assert 0 <= int(greedy[1][0]) <= 4 and 0 <= int(beams[2][0]) <= 2
@@ -267,7 +182,7 @@ def test_limits_just_outside_return_minus_one(dev, field, value):
     any launch -- the pointers are never followed (the workspace here is 256 bytes)."""
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import rnnt_lstm_desc
-    p, j = _build(dev, **_TINY)
+    p, j = _lstm_build(dev, **_TINY)
     desc, keep = rnnt_lstm_desc(p, j)
     setattr(keep[-1], field, value)
     lib = N.lib()
@@ -294,7 +209,7 @@ def test_refused_shapes_take_the_module_loop(dev):
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import (RnntBeamDecoding, RnntGreedyDecoding, rnnt_beam_lstm_tokens_from_am,
                                                 rnnt_lstm_desc)
-    c, p, j, am, lens, ref = _case(dev, "b_h20_beam1_k1")
+    c, p, j, am, lens, ref = _lstm_case(dev, "b_h20_beam1_k1")
     desc, keep = rnnt_lstm_desc(p, j)
     ws = torch.zeros(N.lib().s2t_rnnt_lstm_workspace_bytes(desc, 1, 2, 16), dtype=torch.uint8, device=dev)
     for beam, topk, rc in ((17, 4, -1), (0, 4, -1), (4, 17, -1), (4, 0, -1)):
@@ -308,7 +223,7 @@ def test_refused_shapes_take_the_module_loop(dev):
     wide = RnntBeamDecoding(_Tok(), p, j, beam_size=17, cutoff_top_k=1)       # (top-1: beam 1 in effect)
     texts = wide.decode_batch(am, lens)
     assert texts == [_Tok().decode(r[0]) for r in ref]
-    p2, j2 = _build(dev, **dict(_TINY, H=1028))
+    p2, j2 = _lstm_build(dev, **dict(_TINY, H=1028))
     am2, lens2, greedy, beams = _run_both(dev, p2, j2, 16)
     assert greedy is None and beams is None
     g = RnntGreedyDecoding(_Tok(), p2, j2, max_token_step=1)
@@ -323,8 +238,6 @@ def test_refused_shapes_take_the_module_loop(dev):
 # ------------------------------------------------------------------ 6. validation_step
 def test_validation_steps_log_the_restatements_wer(dev):
     from oracle import decoding as OD
-    from test_gpu_conformer_tasks import _CONF, _base_cfg, _pcm_batch
-    from test_gpu_validation import _TOK, _V, _refs, _task
     cfg = _base_cfg()
     cfg.update({"task": {"type": "CTC_Hybrid_Rnnt"}, "tokenizer": _TOK, "encoder": _CONF,
                 "decoder": {"model": "Projector", "config": {"input_dim": 64, "output_dim": _V, "dropout_p": 0.1}},

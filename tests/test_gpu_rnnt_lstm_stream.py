@@ -18,11 +18,13 @@ import pytest
 import torch
 
 import rnnt_lstm_search_cases as C
+import rnnt_lstm_search_f64 as S
 import rnnt_lstm_stream_cases as SC
 import rnnt_lstm_stream_f64 as F
-import test_gpu_rnnt_lstm_search as LS
-import test_gpu_rnnt_stream_search as SS
-import test_rnnt_beam as TB
+from decode_support import (_beam_modules, _feed, _fixture_free_config, _lstm_build, _lstm_case, _lstm_modules,
+                            _lstm_pair, _plan, RECOGNIZER_BLANK, _regular, _same_rows, _TINY,
+                            _tiny_stream_encoder, _tokenizer)
+from task_support import _pruned_beam_cfg
 
 pytestmark = pytest.mark.gpu
 
@@ -30,26 +32,6 @@ PARTITIONS = ("1", "7", "16", "irregular")
 
 
 # ------------------------------------------------------------------------------------ helpers
-def _irregular(lens, seed):
-    """SS._irregular (sizes 0..16 from a seeded generator, different per row, one call that idles
-    every row) for any batch, one row included."""
-    g = np.random.default_rng(seed)
-    rows = []
-    for n in np.asarray(lens).tolist():
-        sizes, left = [], n
-        while left > 0:
-            s = min(int(g.choice([0, 0, 1, 1, 2, 3, 5, 7, 11, 16])), left)
-            sizes.append(s)
-            left -= s
-        rows.append(sizes)
-    K = max(1, max(len(r) for r in rows))
-    plan = [np.array([r[k] if k < len(r) else 0 for r in rows], dtype=np.int64) for k in range(K)]
-    plan.insert(K // 2, np.zeros(len(rows), dtype=np.int64))
-    return plan
-
-
-def _plan(lens, name, seed=0):
-    return _irregular(lens, 100 + seed) if name == "irregular" else SS._regular(lens, int(name))
 
 
 _CACHE = {}
@@ -58,11 +40,11 @@ _CACHE = {}
 def _case(dev, name):
     """(case, modules, am and lengths on the device, the float64 results), built once per case."""
     if name in C.CASES:
-        return LS._case(dev, name)
+        return _lstm_case(dev, name)
     if name not in _CACHE:
         c = SC.CASES[name]
         w, act, am, lens = SC.make(name)
-        p, j = LS._modules(dev, w, c["model"])
+        p, j = _lstm_modules(dev, w, c["model"])
         _CACHE[name] = (c, p, j, am.to(dev), lens.to(dev), SC.reference(name))
     return _CACHE[name]
 
@@ -104,7 +86,7 @@ def test_greedy_chunks_equal_the_whole_utterance_walk(dev, name, partition, capt
     c, p, j, am, lens, ref = _case(dev, name)
     gt, gn = _one_shot(dev, name)
     search = _stream(dev, name, capturable=capturable)
-    got, off = SS._feed(search, am, _plan(_lens(name), partition, c["seed"]))
+    got, off = _feed(search, am, _plan(_lens(name), partition, c["seed"]))
     assert off.tolist() == _lens(name).tolist()
     assert torch.equal(got[1], gn)
     for b, r in enumerate(ref):
@@ -122,9 +104,9 @@ def test_beam_chunks_equal_the_whole_utterance_search(dev, name, partition):
     c, p, j, am, lens, ref = _case(dev, name)
     want = _one_shot(dev, name)
     search = _stream(dev, name)
-    got, off = SS._feed(search, am, _plan(_lens(name), partition, c["seed"]))
+    got, off = _feed(search, am, _plan(_lens(name), partition, c["seed"]))
     assert off.tolist() == _lens(name).tolist()
-    SS._same_rows(got, want)
+    _same_rows(got, want)
     for b, (tok, _, frm, _) in enumerate(ref):
         n = int(got[2][b])
         assert got[0][b, :n].tolist() == tok and got[1][b, :n].tolist() == frm, b
@@ -145,9 +127,9 @@ def test_long_chunks_cross_the_trace_blocks(dev, name):
     stable = []
     for step in (90, 70, 7):
         search = _stream(dev, name)
-        got, off = SS._feed(search, am, SS._regular(_lens(name), step))
+        got, off = _feed(search, am, _regular(_lens(name), step))
         assert off.tolist() == _lens(name).tolist()
-        SS._same_rows(got, want)
+        _same_rows(got, want)
         assert int(search.overflow.sum()) == 0
         stable.append(got[4].tolist())
     assert stable[0] == stable[1] == stable[2], stable
@@ -158,7 +140,7 @@ def test_long_chunks_cross_the_trace_blocks(dev, name):
 def _run7(dev, name):
     """The 7-frame partition of a case with the outputs after every chunk."""
     snaps = []
-    SS._feed(_stream(dev, name), _case(dev, name)[3], SS._regular(_lens(name), 7),
+    _feed(_stream(dev, name), _case(dev, name)[3], _regular(_lens(name), 7),
              snap=lambda off, out: snaps.append((off, out)))
     return snaps
 
@@ -169,7 +151,7 @@ def test_every_chunk_gives_the_prefix_answer(dev, name):
     c, p, j, am, _, _ = _case(dev, name)
     for off, out in _run7(dev, name):
         want = [x.cpu() for x in rnnt_beam_lstm_tokens_from_am(am, torch.as_tensor(off), p, j, c["beam"], c["topk"])]
-        SS._same_rows(out, want)
+        _same_rows(out, want)
 
 
 # ------------------------------------------------------------------------------------ 4. stable_len
@@ -178,7 +160,7 @@ def _stable_f64(name, b):
     c = SC.CASES[name]
     w, act, am, _ = SC.make(name)
     n = int(_lens(name)[b])
-    return F.beam_search_chunked(am[b, :n], F.cuts_of(n, "7"), LS.S.cast(w, torch.float64), act, c["beam"],
+    return F.beam_search_chunked(am[b, :n], F.cuts_of(n, "7"), S.cast(w, torch.float64), act, c["beam"],
                                  c["topk"])[4]
 
 
@@ -216,13 +198,13 @@ def test_rows_are_independent_and_reset_alone(dev):
     la, lb = int(_lens(name)[0]), int(_lens(name)[3])
     assert lb > 0 and int(want[2][0]) > 0 and int(want[2][3]) > 0
     am = torch.stack([am_c[0]] * 4)
-    plain, _ = SS._feed(_stream(dev, name, B=4), am, SS._regular([la] * 4, 16))
-    SS._same_rows(plain, [x[[0, 0, 0, 0]] for x in want])
+    plain, _ = _feed(_stream(dev, name, B=4), am, _regular([la] * 4, 16))
+    _same_rows(plain, [x[[0, 0, 0, 0]] for x in want])
 
     search = _stream(dev, name, B=4)
-    plan = SS._regular([la] * 4, 16)
+    plan = _regular([la] * 4, 16)
     half = len(plan) // 2
-    _, off = SS._feed(search, am, plan[:half])
+    _, off = _feed(search, am, plan[:half])
     assert int(search.out_len[2]) > 0
     search.reset([2])
     assert search.out_len.tolist()[2] == 0 and int(search.out_len[1]) > 0
@@ -230,16 +212,16 @@ def test_rows_are_independent_and_reset_alone(dev):
     am2[2] = am_c[3]
     off[2] = 0
     rest = [np.array([q[0], q[1], 0, q[3]]) for q in plan[half:]]
-    for k, cl in enumerate(SS._regular([lb], 16)):                     # B rides along from its frame 0
+    for k, cl in enumerate(_regular([lb], 16)):                     # B rides along from its frame 0
         if k < len(rest):
             rest[k][2] = cl[0]
         else:
             rest.append(np.array([0, 0, cl[0], 0]))
-    got, off = SS._feed(search, am2, rest, off=off)
+    got, off = _feed(search, am2, rest, off=off)
     assert off.tolist() == [la, la, lb, la]
     for x, y in zip(got, plain):
         assert torch.equal(x[[0, 1, 3]], y[[0, 1, 3]])
-    SS._same_rows([x[2:3] for x in got], [x[3:4] for x in want])
+    _same_rows([x[2:3] for x in got], [x[3:4] for x in want])
     assert got[0][2, :int(got[2][2])].tolist() == ref[3][0] and got[1][2, :int(got[2][2])].tolist() == ref[3][2]
 
 
@@ -249,8 +231,8 @@ def test_idle_call_changes_nothing(dev, name):
     c, p, j, am, _, _ = _case(dev, name)
     want = _one_shot(dev, name)
     search = _stream(dev, name)
-    plan = SS._regular(_lens(name), 7)
-    _, off = SS._feed(search, am, plan[:3])
+    plan = _regular(_lens(name), 7)
+    _, off = _feed(search, am, plan[:3])
     assert int(search.out_len.sum()) > 0
     outs = (search.state, search.tokens, search.frames, search.out_len, search.score, search.stable_len,
             search.overflow)
@@ -260,13 +242,13 @@ def test_idle_call_changes_nothing(dev, name):
         torch.cuda.synchronize()
         for x, y in zip(outs, before):
             assert torch.equal(x, y), Tc
-    got, off = SS._feed(search, am, plan[3:], off=off)
+    got, off = _feed(search, am, plan[3:], off=off)
     if c["beam"] is None:
         assert torch.equal(got[1], want[1])
         for b in range(c["B"]):
             assert torch.equal(got[0][b, :int(want[1][b])], want[0][b, :int(want[1][b])])
     else:
-        SS._same_rows(got, want)
+        _same_rows(got, want)
 
 
 # ------------------------------------------------------------------------------------ 7. capacity
@@ -282,7 +264,7 @@ def test_capacity(dev):
         assert len(rows) >= 2, (name, n_want.tolist())
         search = _stream(dev, name, B=len(rows), max_tokens=3)
         lens = _lens(name)[rows]
-        got, _ = SS._feed(search, am[rows].contiguous(), SS._regular(lens, 7))
+        got, _ = _feed(search, am[rows].contiguous(), _regular(lens, 7))
         n_got = got[1] if c["beam"] is None else got[2]
         assert n_got.tolist() == [3] * len(rows) and search.overflow.tolist() == [1] * len(rows)
         assert torch.equal(got[0], want[0][rows, :3])
@@ -293,7 +275,7 @@ def test_capacity(dev):
         search.reset()
         torch.cuda.synchronize()
         assert search.overflow.tolist() == [0] * len(rows) and search.out_len.tolist() == [0] * len(rows)
-        got, _ = SS._feed(search, am[rows].contiguous(), SS._regular(lens, 1)[:1])
+        got, _ = _feed(search, am[rows].contiguous(), _regular(lens, 1)[:1])
         assert search.overflow.tolist() == [0] * len(rows)              # one frame: at most two tokens
 
 
@@ -303,8 +285,8 @@ def test_refusals(dev):
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import rnnt_lstm_desc
     lib = N.lib()
-    V, B, MT = LS._TINY["V"], 2, 10
-    p, j = LS._build(dev, **LS._TINY)
+    V, B, MT = _TINY["V"], 2, 10
+    p, j = _lstm_build(dev, **_TINY)
     desc, keep = rnnt_lstm_desc(p, j)
     bad, keep_bad = rnnt_lstm_desc(p, j)
     keep_bad[-1].H = 1028
@@ -353,11 +335,11 @@ def test_refusals(dev):
 
 def test_class_refuses_what_the_kernels_do_not_take(dev):
     from speech2text_amd.model.decoding import RnntLstmStreamingSearch, RnntStreamingSearch, rnnt_streaming_search
-    p, j = LS._build(dev, **LS._TINY)
+    p, j = _lstm_build(dev, **_TINY)
     assert isinstance(rnnt_streaming_search(p, j, 2, "beam", device=dev), RnntLstmStreamingSearch)
     assert not rnnt_streaming_search(p, j, 2, "greedy", device=dev, capturable=False).capturable
-    s = TB._fixture_free_config(V=8, D=16, E=12, ctx=2, seed=9)
-    pred, join = TB._modules(s, dev)
+    s = _fixture_free_config(V=8, D=16, E=12, ctx=2, seed=9)
+    pred, join = _beam_modules(s, dev)
     assert isinstance(rnnt_streaming_search(pred, join, 2, "beam", device=dev), RnntStreamingSearch)
     with pytest.raises(ValueError):
         RnntLstmStreamingSearch(pred, join, 2, "greedy", device=dev)
@@ -368,38 +350,19 @@ def test_class_refuses_what_the_kernels_do_not_take(dev):
     with pytest.raises(ValueError):
         RnntLstmStreamingSearch(p, j, 2, "viterbi", device=dev)
     with pytest.raises(ValueError):
-        RnntLstmStreamingSearch(*LS._build(dev, **dict(LS._TINY, H=1028)), 2, "greedy", device=dev)
+        RnntLstmStreamingSearch(*_lstm_build(dev, **dict(_TINY, H=1028)), 2, "greedy", device=dev)
     with pytest.raises(ValueError):
         RnntLstmStreamingSearch(p, j, 2, "greedy", max_tokens=0, device=dev)
     with pytest.raises(RuntimeError):
-        RnntLstmStreamingSearch(*LS._build("cpu", **LS._TINY), 2, "greedy", device=dev)
+        RnntLstmStreamingSearch(*_lstm_build("cpu", **_TINY), 2, "greedy", device=dev)
     with pytest.raises(ValueError):
-        RnntLstmStreamingSearch(p, j, 2, "beam", device=dev).step(torch.zeros(2, 257, LS._TINY["V"], device=dev))
+        RnntLstmStreamingSearch(p, j, 2, "beam", device=dev).step(torch.zeros(2, 257, _TINY["V"], device=dev))
 
 
 # ------------------------------------------------------------------------------------ 9. recogniser
 # The tiny random encoder's output hardly moves from frame to frame, so on the fixture's audio a row
 # emits at nearly every node (lift <= 14) or only at its first (lift >= 17); 16 sits between for both
 # searches: greedy 2 and beam 22 tokens on the 48 frames.
-RECOGNIZER_BLANK = 16.0
-
-
-def _lstm_pair(dev, V, D, seed, blank):
-    """An LSTM predictor and a joiner WITH output projection of fresh weights, times 3 (away from
-    the near-ties of a fresh model), blank lifted behind the out-projection so that it wins on a
-    share of the nodes: tokens on some frames, not on all."""
-    from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
-    from speech2text_amd.model.predictor.predictor import Predictor
-    torch.manual_seed(seed)
-    pred = Predictor({"model": "Lstm", "config": {
-        "num_symbols": V, "output_dim": D, "symbol_embedding_dim": 16, "num_lstm_layers": 2,
-        "lstm_hidden_dim": 32, "lstm_layer_norm": True, "lstm_layer_norm_epsilon": 1e-3, "lstm_dropout": 0.0}})
-    join = Joiner(JoinerConfig(input_dim=D, output_dim=V, inner_dim=32, activation="relu", use_out_project=True))
-    with torch.no_grad():
-        for q in list(pred.parameters()) + list(join.parameters()):
-            q.mul_(3.0)
-        join._out_projection[1].bias[0] += blank
-    return pred.to(dev).eval(), join.to(dev).eval()
 
 
 @pytest.mark.parametrize("method", ["greedy", "beam"])
@@ -411,13 +374,13 @@ def test_recognizer_graph_equals_the_eager_composition(dev, golden_dir, method):
     from speech2text_amd.model.decoding import (RnntLstmStreamingSearch, rnnt_beam_lstm_tokens_from_am,
                                                 rnnt_greedy_lstm_tokens_from_am)
     from speech2text_amd.model.encoder.zipformer_streaming import StreamingRecognizer
-    g, m, chunk = SS._tiny_stream_encoder(golden_dir, dev)
+    g, m, chunk = _tiny_stream_encoder(golden_dir, dev)
     V, D = 24, max(m.encoder_dim)
     pred, join = _lstm_pair(dev, V, D, 31, RECOGNIZER_BLANK)
     feats = torch.from_numpy(g["feats"]).to(dev)
     B, T, Tc = feats.shape[0], 2 * chunk + 13, chunk // 2
     kw = dict(method=method, max_token_step=1, beam_size=4, cutoff_top_k=4, max_tokens=64)
-    rec = StreamingRecognizer(m, pred, join, TB._tokenizer(V), batch_size=B, device=dev, **kw)
+    rec = StreamingRecognizer(m, pred, join, _tokenizer(V), batch_size=B, device=dev, **kw)
     assert isinstance(rec.search, RnntLstmStreamingSearch) and rec.search.capturable
     eager = RnntLstmStreamingSearch(pred, join, B, device=dev, **kw)
     for rep in range(2):
@@ -446,7 +409,7 @@ def test_recognizer_graph_equals_the_eager_composition(dev, golden_dir, method):
         lens = torch.full((B,), 6 * Tc, dtype=torch.int64)
         if method == "beam":
             want = [x.cpu() for x in rnnt_beam_lstm_tokens_from_am(am_all, lens, pred, join, 4, 4)]
-            SS._same_rows([x.cpu() for x in rec.outputs], want)
+            _same_rows([x.cpu() for x in rec.outputs], want)
             assert bool((rec.search.stable_len <= rec.search.out_len).all())
         else:
             gt, gn = (x.cpu() for x in rnnt_greedy_lstm_tokens_from_am(am_all, lens, pred, join, 1))
@@ -459,7 +422,6 @@ def test_recognizer_graph_equals_the_eager_composition(dev, golden_dir, method):
         assert all(t.startswith(u) for t, u in zip(texts, rec.stable_texts()))
 
 
-
 # ------------------------------------------------------------------------------------ 10. task
 def test_task_streaming_recognizer_with_the_lstm_predictor(dev):
     """PrunedRnntTask.streaming_recognizer(batch_size=2) of a task with `predictor.model: Lstm`:
@@ -469,7 +431,7 @@ def test_task_streaming_recognizer_with_the_lstm_predictor(dev):
     from speech2text_amd.build_task import TaskFactory
     from speech2text_amd.model.decoding import RnntLstmStreamingSearch
     V, chunk = 32, 8
-    cfg = TB._pruned_cfg(V)
+    cfg = _pruned_beam_cfg(V)
     cfg["encoder"]["config"].update({"chunk_size": [chunk], "left_context_frames": [16]})
     cfg["predictor"] = {"model": "Lstm", "config": {
         "num_symbols": V, "output_dim": 64, "symbol_embedding_dim": 32, "num_lstm_layers": 2,

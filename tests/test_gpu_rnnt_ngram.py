@@ -18,32 +18,10 @@ import torch
 
 import rnnt_ngram_cases as C
 import rnnt_ngram_f64 as R
+from decode_support import _bad_desc, _fused, _ngram_case
+from task_support import _pcm_batch, _pruned_cfg, _task, _V
 
 pytestmark = pytest.mark.gpu
-
-_CACHE = {}
-
-
-def _lm_on(dev, name):
-    from speech2text_amd.model.lm.ngram_lm import NgramLm
-    return NgramLm.from_arpa(C.text_of(name), num_classes=C.CASES[name]["V"]).to(dev)
-
-
-def _case(dev, name):
-    """(case, predictor, joiner, NgramLm, am and lengths on the device, the float64 results), once per case."""
-    if name not in _CACHE:
-        c = C.CASES[name]
-        _, am, lens = C.make(name)
-        pred, join = C.modules(dev, name)
-        _CACHE[name] = (c, pred, join, _lm_on(dev, name), am.to(dev), lens.to(dev), C.reference(name))
-    return _CACHE[name]
-
-
-def _fused(c, p, j, lm, am, lens, **kw):
-    from speech2text_amd.model.decoding import rnnt_beam_ngram_tokens_from_am
-    args = dict(lm_weight=c["weight"], beam_size=c["beam"], cutoff_top_k=c["topk"])
-    args.update(kw)
-    return rnnt_beam_ngram_tokens_from_am(am, lens, p, j, lm, **args)
 
 
 def _column(rows, i):
@@ -62,7 +40,7 @@ def _same_path(out, ref, what, zeroed=True):
 # ------------------------------------------------------------------ 1. the fused search
 @pytest.mark.parametrize("name", list(C.CASES))
 def test_fused_search_exact(dev, name):
-    c, p, j, lm, am, lens, ref = _case(dev, name)
+    c, p, j, lm, am, lens, ref = _ngram_case(dev, name)
     out = _fused(c, p, j, lm, am, lens)
     assert out is not None and len(out) == 5
     assert out[0].shape == out[1].shape == am.shape[:2] and out[0].dtype == torch.int64
@@ -84,7 +62,7 @@ def test_fused_search_exact(dev, name):
 @pytest.mark.parametrize("name", list(C.CASES))
 def test_weight_zero_is_the_plain_entry(dev, name):
     from speech2text_amd.model.decoding import rnnt_beam_tokens_from_am
-    c, p, j, lm, am, lens, _ = _case(dev, name)
+    c, p, j, lm, am, lens, _ = _ngram_case(dev, name)
     plain = rnnt_beam_tokens_from_am(am, lens, p, j, c["beam"], c["topk"])
     out = _fused(c, p, j, lm, am, lens, lm_weight=0.0)
     assert plain is not None and out is not None and int(plain[2].sum()) > 0
@@ -101,7 +79,7 @@ def test_weight_zero_is_the_plain_entry(dev, name):
 def test_beam_one_walks_the_plain_path(dev):
     from speech2text_amd.model.decoding import rnnt_beam_tokens_from_am
     name = "g_v63_o1_beam1_k1"
-    c, p, j, lm, am, lens, _ = _case(dev, name)
+    c, p, j, lm, am, lens, _ = _ngram_case(dev, name)
     assert c["beam"] == c["topk"] == 1
     plain = rnnt_beam_tokens_from_am(am, lens, p, j, 1, 1)
     out = _fused(c, p, j, lm, am, lens)
@@ -117,7 +95,7 @@ def test_beam_one_walks_the_plain_path(dev):
 def _abi_arguments(dev, name):
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import _stateless_weights
-    c, p, j, lm, am, lens, _ = _case(dev, name)
+    c, p, j, lm, am, lens, _ = _ngram_case(dev, name)
     B, T, V = am.shape
     w, E, D, ctx, act = _stateless_weights(p, j)
     need = N.lib().s2t_rnnt_beam_ngram_workspace_bytes(B, T, V, c["beam"])
@@ -133,18 +111,6 @@ def _abi_arguments(dev, name):
                 tokens=N.lp(outs[0]), frames=N.lp(outs[1]), out_len=N.lp(outs[2]), score=N.fp(outs[3]),
                 lm_score=N.fp(outs[4]), stream=N.stream())
     return args, ws, outs, (w, lm)
-
-
-def _bad_desc(lm, **change):
-    from speech2text_amd import _native as N
-    d = N.struct("S2tNgramLmDesc")()
-    src = lm._cache["desc"]
-    for f, _ in d._fields_:
-        setattr(d, f, getattr(src, f))
-    for k, v in change.items():
-        setattr(d, k, v)
-    import ctypes
-    return ctypes.byref(d), d
 
 
 _REFUSED = [dict(lm=None), dict(desc=dict(ctx_begin=None)), dict(desc=dict(arc_next=None)), dict(desc=dict(V=64)),
@@ -184,7 +150,7 @@ def test_refusals_leave_everything_untouched(dev):
 
 
 def test_wrapper_refuses_tables_on_another_device(dev):
-    c, p, j, lm, am, lens, _ = _case(dev, "g_v11_o2_kV")
+    c, p, j, lm, am, lens, _ = _ngram_case(dev, "g_v11_o2_kV")
     with pytest.raises(RuntimeError, match="NgramLm.to"):
         _fused(c, p, j, C.model("g_v11_o2_kV"), am, lens)
     assert _fused(c, p, j, lm, am, lens, beam_size=17) is None
@@ -215,7 +181,7 @@ def _counted(monkeypatch):
 def test_class_takes_the_fused_entry_with_tables_from_the_cpu(dev, monkeypatch):
     from speech2text_amd.model.lm.ngram_lm import NgramLm
     name = "g_v65_o3_b17"
-    c, p, j, _, am, lens, ref = _case(dev, name)
+    c, p, j, _, am, lens, ref = _ngram_case(dev, name)
     lm = NgramLm.from_arpa(C.text_of(name), num_classes=c["V"])
     assert lm.device.type == "cpu"
     calls = _counted(monkeypatch)
@@ -243,7 +209,7 @@ def test_a_refused_shape_takes_the_module_loop(dev, monkeypatch):
     """beam 17: the entry refuses, the class answers with _module_loop_lm on the device, first token scored."""
     from speech2text_amd import _native as N
     name = "g_v520_o3"
-    c, p, j, lm, am, lens, _ = _case(dev, name)
+    c, p, j, lm, am, lens, _ = _ngram_case(dev, name)
     want = _loop_reference(name, 17)
     assert min(r.margin for r in want) >= C.MARGIN
     calls = _counted(monkeypatch)
@@ -260,7 +226,7 @@ def test_a_refused_shape_takes_the_module_loop(dev, monkeypatch):
 
 def test_an_out_projection_joiner_takes_the_module_loop(dev, monkeypatch):
     name = "g_v11_o2_kV"
-    c, _, _, lm, am, lens, _ = _case(dev, name)
+    c, _, _, lm, am, lens, _ = _ngram_case(dev, name)
     torch.manual_seed(3)
     p, j = C.build_modules(dev, c["V"], c["E"], c["D"], c["ctx"], c["act"], inner=16)
     calls = _counted(monkeypatch)
@@ -279,8 +245,6 @@ def test_task_with_an_arpa_section_decodes_through_the_fused_entry(dev, tmp_path
     import ctc_ngram_cases as CN
     from speech2text_amd.model.decoding import RnntBeamDecoding, rnnt_beam_ngram_tokens_from_am
     from speech2text_amd.model.lm.ngram_lm import NgramLm
-    from test_gpu_conformer_tasks import _pcm_batch
-    from test_gpu_validation import _V, _pruned_cfg, _task
     cfg = copy.deepcopy(_pruned_cfg())
     plain = _task("Pruned_Rnnt", copy.deepcopy(cfg), "cpu")
     est = NgramLm.estimate(CN.lm_sequences(_V, 200, 4), _V, order=3)

@@ -17,8 +17,9 @@ import torch
 
 import rnnt_ngram_cases as C
 import rnnt_ngram_f64 as R
-import test_gpu_rnnt_ngram as G
-import test_gpu_rnnt_stream_search as SS
+from decode_support import (_bad_desc, _beam_modules, _feed, _fixture_free_config, _fused, _lm_on, _ngram_case,
+                            _regular, _same_rows, _tiny_stream_encoder, _tokenizer)
+from task_support import _pruned_beam_cfg
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +28,7 @@ _OUT = ("tokens", "frames", "out_len", "score", "lm_score")
 
 def _search(dev, name, B=None, max_tokens=None, lm_weight=None, **kw):
     from speech2text_amd.model.decoding import RnntNgramStreamingSearch
-    c, p, j, lm, am, lens, _ = G._case(dev, name)
+    c, p, j, lm, am, lens, _ = _ngram_case(dev, name)
     return RnntNgramStreamingSearch(p, j, am.shape[0] if B is None else B, c["beam"], c["topk"],
                                     am.shape[1] if max_tokens is None else max_tokens, dev, lm=lm,
                                     lm_weight=c["weight"] if lm_weight is None else lm_weight, **kw)
@@ -61,7 +62,7 @@ def _ragged(lens, seed):
 
 def _plan(name, cut):
     lens = _lens(name)
-    return _ragged(lens, 11) if cut == "ragged" else SS._regular(lens, cut)
+    return _ragged(lens, 11) if cut == "ragged" else _regular(lens, cut)
 
 
 def _same(got, want, what):
@@ -76,9 +77,9 @@ def _same(got, want, what):
 
 
 def _one_shot(dev, name, fed=None, **kw):
-    c, p, j, lm, am, lens, _ = G._case(dev, name)
+    c, p, j, lm, am, lens, _ = _ngram_case(dev, name)
     n = lens if fed is None else torch.as_tensor(fed, dtype=torch.int64)
-    return [x.cpu() for x in G._fused(c, p, j, lm, am, n, **kw)]
+    return [x.cpu() for x in _fused(c, p, j, lm, am, n, **kw)]
 
 
 def _stable_reference(name, plan):
@@ -99,7 +100,7 @@ def _stable_reference(name, plan):
 @pytest.mark.parametrize("cut", [1, 4, 7, "ragged"], ids=str)
 @pytest.mark.parametrize("name", list(C.CASES))
 def test_chunks_equal_the_one_shot_search(dev, name, cut):
-    c, _, _, _, am, _, ref = G._case(dev, name)
+    c, _, _, _, am, _, ref = _ngram_case(dev, name)
     plan = _plan(name, cut)
     if cut == "ragged" and c["B"] > 1:
         assert any((p == 0).any() and (p > 0).any() for p in plan)
@@ -114,7 +115,7 @@ def test_chunks_equal_the_one_shot_search(dev, name, cut):
         if cut == 7:                                       # after every chunk: the one-shot entry on the prefix
             _same(_outputs(search), _one_shot(dev, name, fed=off), (name, k))
 
-    SS._feed(search, am, plan, snap=snap)
+    _feed(search, am, plan, snap=snap)
     assert seen[-1].tolist() == _lens(name).tolist()
     _same(_outputs(search), _one_shot(dev, name), (name, cut))
     got = _outputs(search)
@@ -128,13 +129,13 @@ def test_chunks_equal_the_one_shot_search(dev, name, cut):
 @pytest.mark.parametrize("name", ["g_v65_o3_b17", C.LARGE, "g_v520_o3"])
 def test_weight_zero_is_the_plain_chunk_search(dev, name):
     from speech2text_amd.model.decoding import RnntStreamingSearch
-    c, p, j, _, am, _, _ = G._case(dev, name)
+    c, p, j, _, am, _, _ = _ngram_case(dev, name)
     plan = _plan(name, "ragged")
     ng = _search(dev, name, lm_weight=0.0)
     plain = RnntStreamingSearch(p, j, am.shape[0], "beam", beam_size=c["beam"], cutoff_top_k=c["topk"],
                                 max_tokens=am.shape[1], device=dev)
-    SS._feed(ng, am, plan)
-    SS._feed(plain, am, plan)
+    _feed(ng, am, plan)
+    _feed(plain, am, plan)
     for k in ("tokens", "frames", "out_len", "score", "stable_len", "overflow"):
         assert torch.equal(getattr(ng, k), getattr(plain, k)), (name, k)
     assert int(ng.out_len.sum()) > 0 and float(ng.lm_score.abs().max()) > 0
@@ -144,9 +145,9 @@ def test_weight_zero_is_the_plain_chunk_search(dev, name):
 # ------------------------------------------------------------------ 3. idle rows, reset, capacity
 def test_idle_call_changes_nothing(dev):
     name = "g_v65_o3_b17"
-    _, _, _, _, am, _, _ = G._case(dev, name)
+    _, _, _, _, am, _, _ = _ngram_case(dev, name)
     search = _search(dev, name)
-    SS._feed(search, am, _plan(name, 1)[:3])
+    _feed(search, am, _plan(name, 1)[:3])
     assert int(search.out_len.sum()) > 0
     outs = (search.state, search.tokens, search.frames, search.out_len, search.score, search.lm_score,
             search.stable_len, search.overflow)
@@ -162,12 +163,12 @@ def test_one_row_resets_while_its_neighbours_go_on(dev, how):
     """Row 3 is reset after two frames and fed utterance 0 from its first frame; the others go on."""
     from speech2text_amd import _native as N
     name = "g_v65_o3_b17"
-    c, _, _, lm, am, _, _ = G._case(dev, name)
+    c, _, _, lm, am, _, _ = _ngram_case(dev, name)
     lens, want = _lens(name), _one_shot(dev, name)
     assert lens[3] >= 2 and lens[0] == c["T"]
     search = _search(dev, name)
-    plan = SS._regular(lens, 1)
-    _, off = SS._feed(search, am, plan[:2])
+    plan = _regular(lens, 1)
+    _, off = _feed(search, am, plan[:2])
     if how == "indices":
         search.reset([3])
     else:
@@ -184,7 +185,7 @@ def test_one_row_resets_while_its_neighbours_go_on(dev, how):
             rest[k][3] = 1
         else:
             rest.append(np.eye(1, c["B"], 3, dtype=np.int64)[0])
-    SS._feed(search, am2, rest, off=off)
+    _feed(search, am2, rest, off=off)
     got = _outputs(search)
     others = [b for b in range(c["B"]) if b != 3]
     _same([x[others] for x in got], [y[others] for y in want], how)
@@ -196,11 +197,11 @@ def test_capacity(dev):
     """max_tokens 3 on an utterance with more tokens: the first 3, out_len 3, overflow 1, and the search
     went on exactly: score and lm_score are the one-shot entry's, bit for bit."""
     name = C.LONG
-    _, _, _, _, am, _, _ = G._case(dev, name)
+    _, _, _, _, am, _, _ = _ngram_case(dev, name)
     want = _one_shot(dev, name)
     assert int(want[2].min()) > 3
     search = _search(dev, name, max_tokens=3)
-    SS._feed(search, am, _plan(name, 7))
+    _feed(search, am, _plan(name, 7))
     got = _outputs(search)
     assert got[2].tolist() == [3] and search.overflow.tolist() == [1]
     assert torch.equal(got[0], want[0][:, :3]) and torch.equal(got[1], want[1][:, :3])
@@ -216,7 +217,7 @@ def test_refusals_leave_state_and_outputs_untouched(dev):
     from speech2text_amd.model.decoding import _stateless_weights
     lib = N.lib()
     name = "g_v63_o5_beam16_k16"
-    c, p, j, lm, am, _, _ = G._case(dev, name)
+    c, p, j, lm, am, _, _ = _ngram_case(dev, name)
     B, T, V = am.shape
     MT = 10
     w, E, D, ctx, act = _stateless_weights(p, j)
@@ -255,7 +256,7 @@ def test_refusals_leave_state_and_outputs_untouched(dev):
         a, held = dict(args), None
         for k, v in change.items():
             if k == "desc":
-                a["lm"], held = G._bad_desc(lm, **v)
+                a["lm"], held = _bad_desc(lm, **v)
             else:
                 a[k] = v
         assert lib.s2t_rnnt_beam_stateless_ngram_chunk(*a.values()) == -1, change
@@ -277,14 +278,14 @@ def test_class_refuses_what_the_entry_does_not_take(dev):
     from speech2text_amd.model.decoding import RnntNgramStreamingSearch, rnnt_streaming_search
     from speech2text_amd.model.lm.ngram_lm import NgramLm
     name = "g_v11_o2_kV"
-    c, p, j, lm, _, _, _ = G._case(dev, name)
+    c, p, j, lm, _, _, _ = _ngram_case(dev, name)
     assert isinstance(rnnt_streaming_search(p, j, 2, "beam", beam_size=4, cutoff_top_k=4, max_tokens=8, device=dev,
                                             lm=lm, lm_weight=0.3), RnntNgramStreamingSearch)
     cpu = NgramLm.from_arpa(C.text_of(name), num_classes=c["V"])
     s = RnntNgramStreamingSearch(p, j, 2, device=dev, lm=cpu, lm_weight=0.3)               # tables copied over
     assert s._lm.device.type == "cuda" and cpu.device.type == "cpu" and s.lm_score.shape == (2,)
     for kw in (dict(beam_size=17), dict(beam_size=0), dict(cutoff_top_k=0), dict(max_tokens=0), dict(lm_weight=math.inf),
-               dict(lm=None), dict(lm=G._lm_on(dev, "g_v63_o1_beam1_k1"))):
+               dict(lm=None), dict(lm=_lm_on(dev, "g_v63_o1_beam1_k1"))):
         args = dict(beam_size=4, cutoff_top_k=4, max_tokens=8, device=dev, lm=lm, lm_weight=0.3)
         args.update(kw)
         with pytest.raises(ValueError):
@@ -302,20 +303,19 @@ def test_recognizer_graph_equals_the_eager_composition(dev, golden_dir):
     RnntNgramStreamingSearch.step issued eagerly over the fixture's 6 chunks, twice across reset(); the
     final result is the one-shot n-gram entry's on the concatenated am chunks."""
     import ctc_ngram_cases as CN
-    import test_rnnt_beam as TB
     from speech2text_amd.model.decoding import RnntNgramStreamingSearch, rnnt_beam_ngram_tokens_from_am
     from speech2text_amd.model.encoder.zipformer_streaming import StreamingRecognizer
     from speech2text_amd.model.lm.ngram_lm import NgramLm
-    g, m, chunk = SS._tiny_stream_encoder(golden_dir, dev)
+    g, m, chunk = _tiny_stream_encoder(golden_dir, dev)
     V, D = 24, max(m.encoder_dim)
-    s = TB._fixture_free_config(V=V, D=D, E=16, ctx=3, seed=31, scale=2.0)
+    s = _fixture_free_config(V=V, D=D, E=16, ctx=3, seed=31, scale=2.0)
     s["enc_b"][0] += 4.0
-    pred, join = TB._modules(s, dev)
+    pred, join = _beam_modules(s, dev)
     pred.eval(), join.eval()
     lm = NgramLm.estimate(CN.lm_sequences(V, 200, 4), V, order=3)
     feats = torch.from_numpy(g["feats"]).to(dev)
     B, T, Tc = feats.shape[0], 2 * chunk + 13, chunk // 2
-    rec = StreamingRecognizer(m, pred, join, TB._tokenizer(V), batch_size=B, device=dev, method="beam", beam_size=4,
+    rec = StreamingRecognizer(m, pred, join, _tokenizer(V), batch_size=B, device=dev, method="beam", beam_size=4,
                               cutoff_top_k=4, max_tokens=64, lm=lm, lm_weight=0.4)
     assert isinstance(rec.search, RnntNgramStreamingSearch) and lm.device.type == "cuda"
     eager = RnntNgramStreamingSearch(pred, join, B, 4, 4, 64, dev, lm=lm, lm_weight=0.4)
@@ -341,18 +341,17 @@ def test_recognizer_graph_equals_the_eager_composition(dev, golden_dir):
         lens = torch.full((B,), 6 * Tc, dtype=torch.int64)
         want = rnnt_beam_ngram_tokens_from_am(torch.cat(ams, dim=1), lens, pred, join, lm, 0.4, 4, 4)
         got = _outputs(rec.search)
-        SS._same_rows(got[:4], [x.cpu() for x in want[:4]])
+        _same_rows(got[:4], [x.cpu() for x in want[:4]])
         assert torch.equal(got[4], want[4].cpu()) and float(got[4].abs().max()) > 0
 
 
 def test_task_streaming_recognizer_builds_the_ngram_search(dev, tmp_path):
     import ctc_ngram_cases as CN
-    import test_rnnt_beam as TB
     from speech2text_amd.build_task import TaskFactory
     from speech2text_amd.model.decoding import RnntNgramStreamingSearch
     from speech2text_amd.model.lm.ngram_lm import NgramLm
     V, chunk = 32, 8
-    cfg = TB._pruned_cfg(V)
+    cfg = _pruned_beam_cfg(V)
     cfg["encoder"]["config"].update({"chunk_size": [chunk], "left_context_frames": [16]})
     torch.manual_seed(0)
     plain = TaskFactory.get("Pruned_Rnnt")(copy.deepcopy(cfg))

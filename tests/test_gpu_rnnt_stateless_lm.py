@@ -17,44 +17,10 @@ import torch
 import rnnt_lstm_search_f64 as S
 import rnnt_stateless_lm_cases as SC
 import rnnt_stateless_lm_f64 as SF
-import test_gpu_rnnt_lm_fusion as GF
+from decode_support import _decoder, _lm_module, _stateless_build, _stateless_modules, _Tok
+from task_support import _pcm_batch, _pruned_cfg, _refs, _task, _V
 
 pytestmark = pytest.mark.gpu
-
-_Tok = GF._Tok
-_lm_module = GF._lm_module
-
-
-def _build(dev, V, E, D, ctx, inner=0, act="relu"):
-    from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
-    from speech2text_amd.model.predictor.predictor import Predictor
-    pred = Predictor({"model": "Stateless", "config": {"num_symbols": V, "output_dim": D, "symbol_embedding_dim": E,
-                                                       "context_size": ctx}})
-    join = Joiner(JoinerConfig(input_dim=D, output_dim=V, inner_dim=max(inner, 1), activation=act, prune_range=5,
-                               use_out_project=inner > 0))
-    join._enc_proj = torch.nn.Identity()                   # the searches are handed am itself
-    return pred.to(dev).eval().requires_grad_(False), join.to(dev).eval().requires_grad_(False)
-
-
-def _modules(dev, p, c):
-    """The project's Predictor / Joiner on the device carrying the weights `p` of a case."""
-    pred, join = _build(dev, c["V"], c["E"], c["D"], c["ctx"], c["inner"], c["act"])
-    q = pred.predictor
-    with torch.no_grad():
-        q._embedding.weight.copy_(p["emb"])
-        q._conv.weight.copy_(p["conv_w"].reshape(c["E"], 1, c["ctx"]))
-        q._output_linear.weight.copy_(p["lin_w"])
-        q._output_linear.bias.copy_(p["lin_b"])
-        join._pre_proj.weight.copy_(p["pre_w"])
-        join._pre_proj.bias.copy_(p["pre_b"])
-        if c["inner"]:
-            o1, o2 = join._out_projection[0], join._out_projection[1]
-            o1.weight.copy_(p["o1_w"])
-            o1.bias.copy_(p["o1_b"])
-            o2.weight.copy_(p["o2_w"])
-            o2.bias.copy_(p["o2_b"])
-    return pred, join
-
 
 _CACHE = {}
 
@@ -64,16 +30,9 @@ def _case(dev, name):
     if name not in _CACHE:
         c = SC.CASES[name]
         p, am, lens, sd = SC.make(name)
-        pred, join = _modules(dev, p, c)
+        pred, join = _stateless_modules(dev, p, c)
         _CACHE[name] = (c, pred, join, _lm_module(dev, sd), am.to(dev), lens.to(dev), SC.reference(name))
     return _CACHE[name]
-
-
-def _decoder(c, p, j, lm, **kw):
-    from speech2text_amd.model.decoding import RnntBeamDecoding
-    args = dict(beam_size=c["beam"], cutoff_top_k=c["topk"], lm=lm, lm_weight=c["weight"], lm_start_token=c["start"])
-    args.update(kw)
-    return RnntBeamDecoding(_Tok(), p, j, **args)
 
 
 def _fused(c, p, j, lm, am, lens, **kw):
@@ -96,7 +55,7 @@ def test_pred_step_chain(dev, name):
     from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import rnnt_stateless_desc
     c, R = SC.CASES[name], SC.STEP_ROWS
-    pred, join = _modules(dev, SC.make(name, 100)[0], c)
+    pred, join = _stateless_modules(dev, SC.make(name, 100)[0], c)
     desc, keep = rnnt_stateless_desc(pred, join)
     nbytes = N.lib().s2t_stateless_pred_step_workspace_bytes(desc, R)
     assert nbytes > 0
@@ -271,7 +230,7 @@ def test_limits_just_inside_are_taken(dev, shape):
     shape = dict(shape)
     beam, topk = shape.pop("beam", 4), shape.pop("topk", 4)
     torch.manual_seed(5)
-    p, j = _build(dev, **shape)
+    p, j = _stateless_build(dev, **shape)
     lm = _lm_module(dev, V=shape["V"], H=8, layers=1)
     for start in (None, shape["V"] - 1):
         _, _, out = _tiny_run(dev, p, j, lm, shape["V"], beam, topk, lm_start_token=start)
@@ -289,7 +248,7 @@ def test_limits_just_outside_take_the_module_loop(dev, shape):
     shape = dict(shape)
     beam, lm_V, weight = shape.pop("beam", 2), shape.pop("lm_V", shape["V"]), shape.pop("weight", 0.3)
     torch.manual_seed(5)
-    p, j = _build(dev, **shape)
+    p, j = _stateless_build(dev, **shape)
     lm = _lm_module(dev, V=lm_V, H=8, layers=1)
     g = torch.Generator().manual_seed(3)
     am = torch.randn(1, 2, shape["V"], generator=g).to(dev)
@@ -331,8 +290,6 @@ def test_a_foreign_lm_takes_the_module_loop(dev):
 # ------------------------------------------------------------------ 8. validation_step
 def test_validation_step_logs_the_restatements_wer(dev):
     from oracle import decoding as OD
-    from test_gpu_conformer_tasks import _pcm_batch
-    from test_gpu_validation import _V, _pruned_cfg, _refs, _task
     cfg = copy.deepcopy(_pruned_cfg())
     cfg["metric"] = {"decode_method": "rnnt_beam_search", "beam_size": 3, "cutoff_top_k": 3, "lm_weight": 0.5,
                      "lm": {"config": {"num_symbols": _V, "symbol_embedding_dim": 24, "num_rnn_layer": 2},

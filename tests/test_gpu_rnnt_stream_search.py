@@ -8,7 +8,6 @@ concatenated am, bit for bit -- torch.equal, no tolerance.  `stable_len` is held
 chunked restatement (tests/rnnt_stream_restatement.py) on the utterances whose stored decision
 margin is at least 16 N, the project's decidability rule."""
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -16,17 +15,14 @@ import torch
 
 import rnnt_beam_restatement as R
 import rnnt_stream_restatement as S
-import test_rnnt_beam as TB
+from decode_support import (_beam_modules, _feed, _fixture, _fixture_free_config, _long_input, _regular,
+                            _same_rows, _search, _tiny_stream_encoder, _tokenizer)
+from task_support import _pruned_beam_cfg
 
 pytestmark = pytest.mark.gpu
 
 
 # ------------------------------------------------------------------------------------ helpers
-def _regular(lens, step):
-    """Every row in `step`-frame chunks: rows that ended idle (chunk_len 0) while longer ones go on."""
-    lens = np.asarray(lens, dtype=np.int64)
-    K = -(-int(lens.max()) // step)
-    return [np.clip(lens - k * step, 0, step) for k in range(K)]
 
 
 def _irregular(lens, seed):
@@ -49,57 +45,25 @@ def _irregular(lens, seed):
     return plan
 
 
-def _feed(search, am_dev, plan, snap=None, off=None):
-    """am_dev (B, T, V) on the device; plan: per call the frames each row takes.  Row b's chunk is
-    am[b, off[b] : off[b] + plan[k][b]] at the front of a (B, max(plan[k]), V) tensor."""
-    B, T, V = am_dev.shape
-    dev = am_dev.device
-    off = np.zeros(B, dtype=np.int64) if off is None else off
-    rows = torch.arange(B, device=dev).unsqueeze(1)
-    out = None
-    for cl in plan:
-        Tc = max(1, int(cl.max()))
-        idx = (torch.as_tensor(off, device=dev).unsqueeze(1) + torch.arange(Tc, device=dev)).clamp(max=T - 1)
-        out = search.step(am_dev[rows, idx].contiguous(), torch.as_tensor(cl, dtype=torch.int64).to(dev))
-        off += cl
-        if snap is not None:
-            snap(off.copy(), [x.cpu().clone() for x in out])
-    torch.cuda.synchronize()
-    return [x.cpu().clone() for x in out], off
-
-
 def _stream(c, dev, B, method="beam", beam=None, topk=None, max_tokens=None, mts=5, modules=None):
     from speech2text_amd.model.decoding import RnntStreamingSearch
-    pred, join = modules or TB._modules(c, dev)
+    pred, join = modules or _beam_modules(c, dev)
     return RnntStreamingSearch(pred, join, B, method, max_token_step=mts,
                                beam_size=c.get("beam", 1) if beam is None else beam,
                                cutoff_top_k=c.get("topk", 1) if topk is None else topk,
                                max_tokens=c["Tmax"] if max_tokens is None else max_tokens, device=dev)
 
 
-def _same_rows(got, want, rows=None):
-    """Stream outputs (tokens, frames, out_len, score[, stable_len]) against the whole-utterance
-    search's (tokens, frames, out_len, score): bit for bit on the valid part of every row."""
-    tokens, frames, out_len, score = got[:4]
-    rows = range(len(out_len)) if rows is None else rows
-    for b in rows:
-        n = int(want[2][b])
-        assert int(out_len[b]) == n, b
-        assert torch.equal(tokens[b, :n], want[0][b, :n]), b
-        assert torch.equal(frames[b, :n], want[1][b, :n]), b
-        assert torch.equal(score[b], want[3][b]), (b, float(score[b]), float(want[3][b]))
-
-
 @functools.lru_cache(maxsize=None)
 def _one_shot(golden_dir, dev, ci):
     """The whole-utterance search on a stored configuration: computed once, shared, left unchanged."""
-    c = TB._fixture(golden_dir)[ci]
-    return TB._search(c, c["am"], c["lengths"], dev)
+    c = _fixture(golden_dir)[ci]
+    return _search(c, c["am"], c["lengths"], dev)
 
 
 def _large_v():
     """Seed and shapes of test_rnnt_beam.test_large_vocabulary_keeps_lm_rows_in_the_workspace."""
-    s = TB._fixture_free_config(V=1024, D=32, E=24, ctx=3, seed=21, scale=3.0)
+    s = _fixture_free_config(V=1024, D=32, E=24, ctx=3, seed=21, scale=3.0)
     s.update(beam=16, topk=4, Tmax=24)
     g = torch.Generator().manual_seed(4)
     return s, torch.randn(4, 24, 1024, generator=g) * 2.0, np.array([24, 17, 5, 1], dtype=np.int64)
@@ -117,7 +81,7 @@ def _plan(lens, name, seed=0):
 def test_beam_chunks_equal_the_whole_utterance_search(dev, golden_dir, partition):
     """Every stored utterance, 8 rows per launch; configuration 4 (V 500, beam 16) keeps its lm rows
     outside the LDS, in place in the state buffer."""
-    fx = TB._fixture(golden_dir)
+    fx = _fixture(golden_dir)
     assert (fx[4]["V"], fx[4]["beam"]) == (500, 16)
     for ci, c in enumerate(fx):
         want = _one_shot(golden_dir, dev, ci)
@@ -136,7 +100,7 @@ def test_beam_chunks_equal_the_whole_utterance_search(dev, golden_dir, partition
 def test_large_vocabulary_chunks(dev, partition):
     """V = 1024 at beam 16: lm rows in the state buffer, classes re-read per selection round."""
     s, am, lens = _large_v()
-    want = TB._search(s, am, lens, dev)
+    want = _search(s, am, lens, dev)
     assert int(want[2].min()) > 0
     got, _ = _feed(_stream(s, dev, 4), am.to(dev), _plan(lens, partition, 9))
     _same_rows(got, want)
@@ -145,7 +109,7 @@ def test_large_vocabulary_chunks(dev, partition):
 @functools.lru_cache(maxsize=None)
 def _run7(golden_dir, dev, ci, beam=None, topk=None):
     """The 7-frame partition of a configuration with the outputs after every chunk."""
-    c = TB._fixture(golden_dir)[ci]
+    c = _fixture(golden_dir)[ci]
     snaps = []
     _feed(_stream(c, dev, 8, beam=beam, topk=topk), torch.from_numpy(c["am"]).to(dev),
           _regular(c["lengths"], 7), snap=lambda off, out: snaps.append((off, out)))
@@ -156,8 +120,8 @@ def test_every_chunk_gives_the_prefix_answer(dev, golden_dir):
     """After each chunk of the 7-frame partition the outputs are the whole-utterance search's on the
     frames fed so far: the answer after every chunk, not only the last."""
     from speech2text_amd.model.decoding import rnnt_beam_tokens_from_am
-    for ci, c in enumerate(TB._fixture(golden_dir)):
-        pred, join = TB._modules(c, dev)
+    for ci, c in enumerate(_fixture(golden_dir)):
+        pred, join = _beam_modules(c, dev)
         am = torch.from_numpy(c["am"]).to(dev)
         for off, out in _run7(golden_dir, dev, ci):
             want = [x.cpu() for x in rnnt_beam_tokens_from_am(am, torch.as_tensor(off), pred, join,
@@ -169,7 +133,7 @@ def test_stable_len(dev, golden_dir):
     """stable_len never decreases; tokens[:stable_len] is a prefix of every later result; with one
     beam it is out_len; on the utterances with the stored margin >= 16 N it is the chunked float64
     restatement's common-prefix length after every chunk (at least 3/4 of each configuration)."""
-    for ci, c in enumerate(TB._fixture(golden_dir)):
+    for ci, c in enumerate(_fixture(golden_dir)):
         snaps = _run7(golden_dir, dev, ci)
         params = {k: c[k] for k in R.PARAM_KEYS}
         decidable = [b for b in range(8) if c["margin"][b] >= 16 * c["N"]]
@@ -195,12 +159,12 @@ def test_rows_are_independent_and_reset_alone(dev, golden_dir):
     """Rows 0..3 run utterance A; row 2 is reset midway by the row mask and fed utterance B.  Rows
     0, 1, 3 are bit-identical to a run without the reset; row 2 is B's whole-utterance result with
     frames counted from its reset."""
-    c = TB._fixture(golden_dir)[1]
+    c = _fixture(golden_dir)[1]
     want = _one_shot(golden_dir, dev, 1)
     la, lb = int(c["lengths"][0]), int(c["lengths"][1])
     A, Bu = torch.from_numpy(c["am"][0]), torch.from_numpy(c["am"][1])
     am = torch.stack([A, A, A, A]).to(dev)
-    modules = TB._modules(c, dev)
+    modules = _beam_modules(c, dev)
     plain, _ = _feed(_stream(c, dev, 4, modules=modules), am, _regular([la] * 4, 16))
     _same_rows(plain, [x[[0, 0, 0, 0]] for x in want])
 
@@ -230,7 +194,7 @@ def test_rows_are_independent_and_reset_alone(dev, golden_dir):
 
 @pytest.mark.parametrize("method", ["greedy", "beam"])
 def test_idle_call_changes_nothing(dev, golden_dir, method):
-    c = TB._fixture(golden_dir)[2]
+    c = _fixture(golden_dir)[2]
     search = _stream(c, dev, 8, method)
     am = torch.from_numpy(c["am"]).to(dev)
     _feed(search, am, _regular(c["lengths"], 16)[:3])
@@ -247,7 +211,7 @@ def test_idle_call_changes_nothing(dev, golden_dir, method):
 def test_capacity(dev, golden_dir):
     """max_tokens = 3 on utterances with more than 3 tokens: the first 3 tokens, out_len 3, overflow
     1, and the search itself went on exactly -- the score is the whole-utterance score, bit for bit."""
-    c = TB._fixture(golden_dir)[1]
+    c = _fixture(golden_dir)[1]
     want = _one_shot(golden_dir, dev, 1)
     assert int(want[2].min()) > 3
     search = _stream(c, dev, 8, max_tokens=3)
@@ -312,8 +276,8 @@ def test_class_refuses_what_the_fused_search_does_not_take(dev):
     from speech2text_amd.model.decoding import RnntStreamingSearch
     from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
     from speech2text_amd.model.predictor.predictor import Predictor
-    s = TB._fixture_free_config(V=8, D=16, E=12, ctx=2, seed=9)
-    pred, join = TB._modules(s, dev)
+    s = _fixture_free_config(V=8, D=16, E=12, ctx=2, seed=9)
+    pred, join = _beam_modules(s, dev)
     RnntStreamingSearch(pred, join, 2, "beam", device=dev)
     with pytest.raises(ValueError):
         RnntStreamingSearch(pred, join, 2, "beam", beam_size=17, device=dev)
@@ -328,7 +292,7 @@ def test_class_refuses_what_the_fused_search_does_not_take(dev):
     with pytest.raises(ValueError):
         RnntStreamingSearch(lstm, join, 2, "greedy", device=dev)
     with pytest.raises(RuntimeError):
-        RnntStreamingSearch(*TB._modules(s, "cpu"), 2, "greedy", device=dev)
+        RnntStreamingSearch(*_beam_modules(s, "cpu"), 2, "greedy", device=dev)
     with pytest.raises(ValueError):
         RnntStreamingSearch(pred, join, 2, "beam", device=dev).step(torch.zeros(2, 257, 8, device=dev))
 
@@ -337,7 +301,7 @@ def test_class_refuses_what_the_fused_search_does_not_take(dev):
 def _greedy_one_shot(c, am, lens, dev, mts, max_out=None):
     """s2t_rnnt_greedy_stateless on a given am."""
     from speech2text_amd import _native as N
-    pred, join = TB._modules(c, dev)
+    pred, join = _beam_modules(c, dev)
     p = pred.predictor
     am = torch.as_tensor(am).to(dev).contiguous()
     B, T, V = am.shape
@@ -357,7 +321,7 @@ def _greedy_one_shot(c, am, lens, dev, mts, max_out=None):
 def _greedy_inputs(golden_dir):
     """The stored am, and the seeded input of test_rnnt_beam.test_degenerate_beam_equals_the_greedy_
     kernel: it emits on many frames, several symbols per frame right before a chunk boundary included."""
-    c = TB._fixture(golden_dir)[0]
+    c = _fixture(golden_dir)[0]
     g = torch.Generator().manual_seed(17)
     rand_am = torch.randn(64, 90, c["V"], generator=g) * 3.0
     rand_lens = torch.randint(1, 91, (64,), generator=g)
@@ -368,7 +332,7 @@ def _greedy_inputs(golden_dir):
 @pytest.mark.parametrize("mts", [0, 1, 5])
 def test_greedy_chunks_equal_the_whole_utterance_walk(dev, golden_dir, mts):
     c, inputs = _greedy_inputs(golden_dir)
-    modules = TB._modules(c, dev)
+    modules = _beam_modules(c, dev)
     for am, lens in inputs:
         B, T = am.shape[0], am.shape[1]
         gt, gn = _greedy_one_shot(c, am, lens, dev, mts)
@@ -389,7 +353,7 @@ def test_greedy_chunks_equal_the_whole_utterance_walk(dev, golden_dir, mts):
 def test_degenerate_beam_chunks_equal_greedy_chunks(dev, golden_dir):
     """beam_size = cutoff_top_k = 1, chunked, is the chunked greedy walk at max_token_step = 0."""
     c, inputs = _greedy_inputs(golden_dir)
-    modules = TB._modules(c, dev)
+    modules = _beam_modules(c, dev)
     for am, lens in inputs:
         B, T = am.shape[0], am.shape[1]
         plan = _irregular(lens, 5)
@@ -407,13 +371,13 @@ def test_long_chunks_cross_the_trace_blocks(dev, golden_dir):
     chunk per row, 70 + the rest, and 7-frame chunks equal the whole-utterance search bit for bit and
     end with the same stable_len.  Row 0 (90 frames: the blocks [26, 90) and [0, 26)) emits on both
     sides of both block edges; tests/test_rnnt_beam.py asserts the same of the float64 restatement."""
-    c = TB._fixture(golden_dir)[0]
-    am, lens = TB._long_input(c)
+    c = _fixture(golden_dir)[0]
+    am, lens = _long_input(c)
     assert int(lens[0]) == 90
-    want = TB._search(c, am, lens, dev, beam=4, topk=4)
+    want = _search(c, am, lens, dev, beam=4, topk=4)
     frames0 = want[1][0, :int(want[2][0])].tolist()
     assert min(frames0) < 26 and max(frames0) >= 64, frames0
-    modules = TB._modules(c, dev)
+    modules = _beam_modules(c, dev)
     stable = []
     for step in (90, 70, 7):
         search = _stream(c, dev, 8, beam=4, topk=4, max_tokens=90, modules=modules)
@@ -426,16 +390,6 @@ def test_long_chunks_cross_the_trace_blocks(dev, golden_dir):
 
 
 # ------------------------------------------------------------------------------------ recogniser
-def _tiny_stream_encoder(golden_dir, dev):
-    from speech2text_amd.model.encoder.zipformer import Zipformer2, Zipformer2Config
-    from test_gpu_zipformer import TINY
-    g = np.load(os.path.join(golden_dir, "zipformer_tiny_stream.npz"))
-    chunk, left = int(g["chunk"]), int(g["left"])
-    m = Zipformer2(Zipformer2Config(**TINY, chunk_size=(chunk,), left_context_frames=(left,), for_ctc=False))
-    sd = {k[3:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("sd.")}
-    missing, unexpected = m.load_state_dict(sd, strict=False)
-    assert not missing and all(k.startswith("_ctc_projection") for k in unexpected), (missing, unexpected)
-    return g, m.to(dev).eval(), chunk
 
 
 @pytest.mark.parametrize("method", ["greedy", "beam"])
@@ -448,14 +402,14 @@ def test_recognizer_graph_equals_the_eager_composition(dev, golden_dir, method):
     from speech2text_amd.model.encoder.zipformer_streaming import StreamingRecognizer
     g, m, chunk = _tiny_stream_encoder(golden_dir, dev)
     V, D = 24, max(m.encoder_dim)
-    s = TB._fixture_free_config(V=V, D=D, E=16, ctx=3, seed=31, scale=2.0)
+    s = _fixture_free_config(V=V, D=D, E=16, ctx=3, seed=31, scale=2.0)
     s["enc_b"][0] += 4.0                 # blank wins on a share of the frames: tokens on some, not on all
-    pred, join = TB._modules(s, dev)
+    pred, join = _beam_modules(s, dev)
     pred.eval(), join.eval()
     feats = torch.from_numpy(g["feats"]).to(dev)
     B, T, Tc = feats.shape[0], 2 * chunk + 13, chunk // 2
     kw = dict(method=method, max_token_step=1, beam_size=4, cutoff_top_k=4, max_tokens=64)
-    rec = StreamingRecognizer(m, pred, join, TB._tokenizer(V), batch_size=B, device=dev, **kw)
+    rec = StreamingRecognizer(m, pred, join, _tokenizer(V), batch_size=B, device=dev, **kw)
     eager = _stream(s, dev, B, method, beam=4, topk=4, max_tokens=64, mts=1, modules=(pred, join))
     for rep in range(2):
         st = m.get_init_states(B, dev)
@@ -500,15 +454,15 @@ def test_recognizer_graph_equals_the_eager_composition(dev, golden_dir, method):
 def test_recognizer_rejects_cpu_and_training(dev, golden_dir):
     from speech2text_amd.model.encoder.zipformer_streaming import StreamingRecognizer
     g, m, chunk = _tiny_stream_encoder(golden_dir, dev)
-    s = TB._fixture_free_config(V=24, D=max(m.encoder_dim), E=16, ctx=3, seed=31)
-    pred, join = TB._modules(s, dev)
+    s = _fixture_free_config(V=24, D=max(m.encoder_dim), E=16, ctx=3, seed=31)
+    pred, join = _beam_modules(s, dev)
     pred.eval(), join.eval()
     m.train()
     with pytest.raises(RuntimeError):
-        StreamingRecognizer(m, pred, join, TB._tokenizer(24), device=dev)
+        StreamingRecognizer(m, pred, join, _tokenizer(24), device=dev)
     m.eval()
     with pytest.raises(RuntimeError):
-        StreamingRecognizer(m.cpu(), pred, join, TB._tokenizer(24), device=dev)
+        StreamingRecognizer(m.cpu(), pred, join, _tokenizer(24), device=dev)
 
 
 def test_task_streaming_recognizer(dev):
@@ -518,7 +472,7 @@ def test_task_streaming_recognizer(dev):
     import math
     from speech2text_amd.build_task import TaskFactory
     V, chunk = 32, 8
-    cfg = TB._pruned_cfg(V)
+    cfg = _pruned_beam_cfg(V)
     cfg["encoder"]["config"].update({"chunk_size": [chunk], "left_context_frames": [16]})
     torch.manual_seed(0)
     task = TaskFactory.get("Pruned_Rnnt")(cfg).to(dev)

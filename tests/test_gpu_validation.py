@@ -9,25 +9,9 @@ import pytest
 import torch
 
 from oracle import decoding as OD
-from test_gpu_conformer_tasks import _CONF, _base_cfg, _pcm_batch
+from task_support import _base_cfg, _CONF, _pcm_batch, _pruned_cfg, _refs, _task, _TOK, _V
 
 pytestmark = pytest.mark.gpu
-
-_V = 32
-_TOK = {"type": "char", "config": {"labels": [chr(97 + i) for i in range(_V - 3)]}}
-
-
-def _task(name, cfg, dev):
-    from speech2text_amd.build_task import TaskFactory
-    torch.manual_seed(0)
-    task = TaskFactory.get(name)(cfg).to(dev)
-    task.eval()
-    return task
-
-
-def _refs(task, labels):
-    from speech2text_amd.model.decoding import reference_decoder
-    return reference_decoder(labels, task._tokenizer)
 
 
 def test_ctc_validation_step_vs_oracle(dev):
@@ -50,22 +34,6 @@ def test_ctc_validation_step_vs_oracle(dev):
     # training still works after a validation pass (no stale no_grad state, BatchNorm untouched)
     task.train()
     assert task.training_step(batch, 0).requires_grad
-
-
-def _pruned_cfg():
-    import bench
-    cfg = bench.c3_config(_V)
-    cfg["encoder"]["config"].update({"downsampling_factor": [1, 2], "num_encoder_layers": [1, 1],
-                                     "feedforward_dim": [96, 128], "encoder_dim": [48, 64],
-                                     "encoder_unmasked_dim": [32, 48], "num_heads": [4, 4],
-                                     "query_head_dim": 8, "value_head_dim": 4, "pos_dim": 16,
-                                     "cnn_module_kernel": [15, 7], "chunk_size": [-1],
-                                     "left_context_frames": [-1]})
-    cfg["predictor"]["config"].update({"output_dim": 64, "symbol_embedding_dim": 32})
-    cfg["joiner"].update({"input_dim": 64})
-    cfg["tokenizer"] = _TOK
-    cfg["metric"] = {"decode_method": "rnnt_greedy_search", "max_token_step": 1}
-    return cfg
 
 
 def test_pruned_rnnt_validation_step_vs_oracle(dev):

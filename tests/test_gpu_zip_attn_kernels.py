@@ -6,19 +6,22 @@ points) against the float64 yardstick tests/zipattn_f64.py, through the C ABI, a
 
 Error = max |got - ref| / max |ref| per tensor; allowed = zipattn_cases.bound(case, tensor) = max(2e-5, 8 x the
 case's float32 figure of the YARDSTICK, asserted by tests/test_zipattn_f64.py).  Every output and workspace
-starts as NaN with a NaN guard behind it and one word in front, and must come out finite with the guards
-intact; dpos starts NaN (the entry point clears it); accumulators start from N(0,1) and are compared as
+is a guarded buffer of tests/guarded.py: it starts as NaN with a NaN guard behind it and one word in front,
+and must come out finite with the guards intact; dpos starts NaN (the entry point clears it); accumulators start from N(0,1) and are compared as
 got - prefill.  A call the entry point must refuse returns its code and leaves its outputs NaN.
 """
+import functools
+
 import pytest
 import torch
 
 import zipattn_cases as ZA
-from test_gpu_zip_conv_kernels import Out, _p
+from guarded import NAN, Buf, env, hold, ptr
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
+_hold = functools.partial(hold, ZA, partial=True)
+
 COVER = dict(fw=ZA.names("fw"), fl=ZA.names("fl"), bw=ZA.names("bw"), ap=ZA.names("ap"), wm=ZA.names("wm"),
              wx=ZA.names("wx"), wd=ZA.names("wd"), wa=ZA.names("wa"), lp=ZA.names("lp"))
 # test -> (the COVER key it is parametrised over, the entry points it calls itself or through HELPERS)
@@ -38,11 +41,6 @@ HELPERS = dict(test_attention_weights_vs_float64=("_fw_run",), test_attention_pe
                test_whiten_metric_after_the_xtx_product=("_metric",))
 
 
-def _env():
-    from speech2text_amd import _native as N
-    return N.lib(), N.stream()
-
-
 def _in(dev, v, mis=False):
     """A float32 device copy of v; mis: its first element is 4 bytes past a multiple of 16."""
     if v is None:
@@ -59,35 +57,20 @@ def _u8(dev, m):
     return None if m is None else m.to(torch.uint8).to(dev).contiguous()
 
 
-def _hold(name, got):
-    """Every tensor of `got` within zipattn_cases.bound of the reference; all misses are reported."""
-    ref = ZA.reference(name)
-    bad = []
-    for k, v in got.items():
-        v = v.detach().cpu()
-        assert bool(torch.isfinite(v).all()), f"{name} {k}: not finite"
-        r = ref[k]
-        err, tol = ZA.rel_err(v.reshape(r.shape), r), ZA.bound(name, k)
-        print(f"{name} {k}: err {err:.3e} bound {tol:.3e} ratio {err / tol:.3f}")
-        if not err <= tol:
-            bad.append(f"{name} {k}: err {err:.3e} > bound {tol:.3e}")
-    assert not bad, "; ".join(bad)
-
-
 # ------------------------------------------------------------------ attention weights
 def _fw_run(dev, name, flag=None):
-    lib, st = _env()
+    _, lib, st = env()
     c, t = ZA.CASES[name], ZA.make(name)
     T, B, H, qd, pd = c["T"], c["B"], c["H"], c["qd"], c["pd"]
     qkp, pos = _in(dev, t["qkp"], "qkp" in c["mis"]), _in(dev, t["pos"], "pos" in c["mis"])
     if pd == 0:
         pos = torch.full((8,), NAN, dtype=torch.float32, device=dev)          # not NULL, and never read
     k8, a8 = _u8(dev, t["kpm"]), _u8(dev, t["amask"])
-    W = Out(dev, (H, B, T, T))
+    W = Buf(dev, (H, B, T, T))
     if flag is None:
-        rc = lib.s2t_relpos_attn_fwd(_p(qkp), _p(pos), _p(k8), _p(a8), T, B, H, qd, pd, _p(W), st)
+        rc = lib.s2t_relpos_attn_fwd(ptr(qkp), ptr(pos), ptr(k8), ptr(a8), T, B, H, qd, pd, ptr(W), st)
     else:
-        rc = lib.s2t_relpos_attn_fwd_flag(_p(qkp), _p(pos), _p(k8), _p(a8), T, B, H, qd, pd, _p(W), ZA.LIMIT, _p(flag), st)
+        rc = lib.s2t_relpos_attn_fwd_flag(ptr(qkp), ptr(pos), ptr(k8), ptr(a8), T, B, H, qd, pd, ptr(W), ZA.LIMIT, ptr(flag), st)
     torch.cuda.synchronize()
     return rc, W
 
@@ -116,7 +99,7 @@ def test_attention_weights_vs_float64(dev, name):
 def test_attention_penalty_flag(dev, name):
     """s2t_relpos_attn_fwd_flag: the flag is 1 exactly when a raw score of the float64 yardstick exceeds the
     limit (before masking, rows and keys past T not counted); W as the plain entry's."""
-    flag = Out(dev, 1, src=torch.zeros(1))
+    flag = Buf(dev, 1, src=torch.zeros(1))
     rc, W = _fw_run(dev, name, flag)
     assert rc == 0
     W.intact(f"{name} W")
@@ -128,7 +111,7 @@ def test_attention_penalty_flag(dev, name):
 
 
 def test_attention_penalty_flag_is_refused_outside_the_mfma_kernel(dev):
-    flag = Out(dev, 1, src=torch.zeros(1))
+    flag = Buf(dev, 1, src=torch.zeros(1))
     rc, W = _fw_run(dev, "fw_g_qd4", flag)
     assert rc == -3
     W.untouched("flag on the general kernel")
@@ -137,14 +120,14 @@ def test_attention_penalty_flag_is_refused_outside_the_mfma_kernel(dev):
 
 @pytest.mark.parametrize("bad", ZA.FW_REFUSALS, ids=lambda d: "_".join(f"{k}{v}" for k, v in d.items()))
 def test_attention_forward_refusals(dev, bad):
-    lib, st = _env()
+    _, lib, st = env()
     a = dict(T=8, B=2, H=2, qd=8, pd=4)
     a.update(bad)
     qkp, pos = torch.zeros(8, 2, 2 * 80, device=dev), torch.zeros(15, 16, device=dev)
-    W, flag = Out(dev, (2, 2, 8, 8)), Out(dev, 1)
-    head = (_p(qkp), _p(pos), None, None, a["T"], a["B"], a["H"], a["qd"], a["pd"], _p(W))
+    W, flag = Buf(dev, (2, 2, 8, 8)), Buf(dev, 1)
+    head = (ptr(qkp), ptr(pos), None, None, a["T"], a["B"], a["H"], a["qd"], a["pd"], ptr(W))
     assert lib.s2t_relpos_attn_fwd(*head, st) == -1
-    assert lib.s2t_relpos_attn_fwd_flag(*head, ZA.LIMIT, _p(flag), st) == -1
+    assert lib.s2t_relpos_attn_fwd_flag(*head, ZA.LIMIT, ptr(flag), st) == -1
     torch.cuda.synchronize()
     W.untouched(f"refused {bad}")
     flag.untouched(f"refused {bad}")
@@ -152,9 +135,9 @@ def test_attention_forward_refusals(dev, bad):
 
 # ------------------------------------------------------------------ attention backward
 def _bw_run(dev, name, dead_scale=1.0, bad=None):
-    """s2t_relpos_attn_bwd on the case (W and delta = the float64 ones rounded) -> (rc, {name: Out}).
+    """s2t_relpos_attn_bwd on the case (W and delta = the float64 ones rounded) -> (rc, {name: Buf}).
     dead_scale multiplies dW, dO and delta of the rows without a live key."""
-    lib, st = _env()
+    _, lib, st = env()
     c, t, ref = ZA.CASES[name], ZA.make(name), ZA.reference(name)
     T, B, H, qd, pd = c["T"], c["B"], c["H"], c["qd"], c["pd"]
     Dp = H * (2 * qd + pd)
@@ -176,12 +159,12 @@ def _bw_run(dev, name, dead_scale=1.0, bad=None):
             a[:, utts] *= dead_scale
     pairs += [(None, None, 0)] * (2 - len(pairs))
     given = int(c["given"])
-    o = dict(delta=Out(dev, (H, B, T), src=dl if given else None), dqkp=Out(dev, (T, B, Dp)))
+    o = dict(delta=Buf(dev, (H, B, T), src=dl if given else None), dqkp=Buf(dev, (T, B, Dp)))
     nws = lib.s2t_relpos_attn_bwd_workspace_floats(T, B, H, pd)
     nj = (T + 31) // 32
     assert nws == B * H * nj * (nj + 1) * 32 * pd
     if pos is not None and pd > 0:
-        o.update(dpos=Out(dev, (2 * T - 1, H * pd)), ws=Out(dev, nws))
+        o.update(dpos=Buf(dev, (2 * T - 1, H * pd)), ws=Buf(dev, nws))
     if bad == "cd33":
         pairs = [(pairs[0][0], pairs[0][1], 17), (pairs[0][0], pairs[0][1], 16)]
     if bad == "no_dw_no_delta":
@@ -192,9 +175,9 @@ def _bw_run(dev, name, dead_scale=1.0, bad=None):
         qd = 0
     if bad == "pd9":
         pd = 9
-    rc = lib.s2t_relpos_attn_bwd(_p(qkp), _p(pos), _p(k8), _p(a8), T, B, H, qd, pd, _p(W), _p(dW), _p(dW0),
-                                 _p(pairs[0][0]), _p(pairs[0][1]), pairs[0][2], _p(pairs[1][0]), _p(pairs[1][1]),
-                                 pairs[1][2], given, _p(o["delta"]), _p(o["dqkp"]), _p(o.get("dpos")), _p(o.get("ws")), st)
+    rc = lib.s2t_relpos_attn_bwd(ptr(qkp), ptr(pos), ptr(k8), ptr(a8), T, B, H, qd, pd, ptr(W), ptr(dW), ptr(dW0),
+                                 ptr(pairs[0][0]), ptr(pairs[0][1]), pairs[0][2], ptr(pairs[1][0]), ptr(pairs[1][1]),
+                                 pairs[1][2], given, ptr(o["delta"]), ptr(o["dqkp"]), ptr(o.get("dpos")), ptr(o.get("ws")), st)
     torch.cuda.synchronize()
     return rc, o
 
@@ -243,14 +226,14 @@ def test_attention_backward_refusals(dev, bad):
 @pytest.mark.parametrize("name", COVER["ap"])
 def test_attention_apply_vs_float64(dev, name):
     """s2t_attn_apply, transpose 0 and 1, in the form the case names."""
-    lib, st = _env()
+    _, lib, st = env()
     c, t = ZA.CASES[name], ZA.make(name)
     T, B, H, dv = c["T"], c["B"], c["H"], c["dv"]
     W, v = _in(dev, t["W"]), _in(dev, t["v"], c["mis"] == "v")
     got = {}
     for tr in (0, 1):
-        out = Out(dev, (T, B, H * dv), mis=c["mis"] == "out")
-        assert lib.s2t_attn_apply(_p(W), _p(v), T, B, H, dv, tr, _p(out), st) == 0
+        out = Buf(dev, (T, B, H * dv), mis=c["mis"] == "out")
+        assert lib.s2t_attn_apply(ptr(W), ptr(v), T, B, H, dv, tr, ptr(out), st) == 0
         torch.cuda.synchronize()
         out.intact(f"{name} transpose {tr}")
         got[f"out{tr}"] = out.t
@@ -260,7 +243,7 @@ def test_attention_apply_vs_float64(dev, name):
 @pytest.mark.parametrize("name", ZA.PERM_CASES)
 def test_attention_apply_of_a_permutation_is_exact(dev, name):
     """W = a permutation matrix per (h, b): out is the permuted v bit for bit, both ways."""
-    lib, st = _env()
+    _, lib, st = env()
     c, t = ZA.CASES[name], ZA.make(name)
     T, B, H, dv = c["T"], c["B"], c["H"], c["dv"]
     g = torch.Generator().manual_seed(c["seed"])
@@ -274,8 +257,8 @@ def test_attention_apply_of_a_permutation_is_exact(dev, name):
             ref1[perm[h, b], b, h] = v4[:, b, h]             # out1[perm(i)] = v[i]
     W, v = _in(dev, Wp), _in(dev, t["v"], c["mis"] == "v")
     for tr, ref in ((0, ref0), (1, ref1)):
-        out = Out(dev, (T, B, H * dv), mis=c["mis"] == "out")
-        assert lib.s2t_attn_apply(_p(W), _p(v), T, B, H, dv, tr, _p(out), st) == 0
+        out = Buf(dev, (T, B, H * dv), mis=c["mis"] == "out")
+        assert lib.s2t_attn_apply(ptr(W), ptr(v), T, B, H, dv, tr, ptr(out), st) == 0
         torch.cuda.synchronize()
         out.intact(f"{name} transpose {tr}")
         assert torch.equal(out.t.cpu(), ref.view(T, B, H * dv)), f"{name} transpose {tr}"
@@ -283,10 +266,10 @@ def test_attention_apply_of_a_permutation_is_exact(dev, name):
 
 @pytest.mark.parametrize("dv", [17, 0])
 def test_attention_apply_refusals(dev, dv):
-    lib, st = _env()
-    W, v, out = torch.zeros(2, 2, 8, 8, device=dev), torch.zeros(8, 2, 2 * 17, device=dev), Out(dev, (8, 2, 2 * 17))
+    _, lib, st = env()
+    W, v, out = torch.zeros(2, 2, 8, 8, device=dev), torch.zeros(8, 2, 2 * 17, device=dev), Buf(dev, (8, 2, 2 * 17))
     for tr in (0, 1):
-        assert lib.s2t_attn_apply(_p(W), _p(v), 8, 2, 2, dv, tr, _p(out), st) == -1
+        assert lib.s2t_attn_apply(ptr(W), ptr(v), 8, 2, 2, dv, tr, ptr(out), st) == -1
     torch.cuda.synchronize()
     out.untouched(f"refused dv {dv}")
 
@@ -297,11 +280,11 @@ STATS = ("cov", "mean", "md", "covsq", "denom", "metric")
 
 def _metric(dev, c, xtx, colsum, ws, host=True):
     """s2t_whiten_metric on NaN outputs -> {tensor: value}, the raw scal and host_metric."""
-    lib, st = _env()
+    _, lib, st = env()
     G, cg = c["G"], c["cg"]
     C = G * cg
-    cov, mean, scal, hm = Out(dev, (G, cg, cg)), Out(dev, C), Out(dev, 4), (Out(dev, 1) if host else None)
-    assert lib.s2t_whiten_metric(_p(xtx), _p(colsum), ZA.ROWS, G, cg, _p(cov), _p(mean), _p(scal), _p(hm), _p(ws), st) == 0
+    cov, mean, scal, hm = Buf(dev, (G, cg, cg)), Buf(dev, C), Buf(dev, 4), (Buf(dev, 1) if host else None)
+    assert lib.s2t_whiten_metric(ptr(xtx), ptr(colsum), ZA.ROWS, G, cg, ptr(cov), ptr(mean), ptr(scal), ptr(hm), ptr(ws), st) == 0
     torch.cuda.synchronize()
     for what, o in (("xtx", xtx), ("colsum", colsum), ("cov", cov), ("mean", mean), ("scal", scal), ("workspace", ws)):
         o.intact(what)
@@ -316,7 +299,7 @@ def _metric(dev, c, xtx, colsum, ws, host=True):
 
 
 def _metric_ws(dev, C):
-    ws = Out(dev, 4 + 2 * C)                                 # the partial-sum slots start NaN
+    ws = Buf(dev, 4 + 2 * C)                                 # the partial-sum slots start NaN
     ws.t[0] = 0.0                                            # the ticket: zeroed once when allocated
     return ws
 
@@ -332,7 +315,7 @@ def test_whiten_metric_vs_float64(dev, name):
     ws = _metric_ws(dev, C)
     res = []
     for src, host in ((tiles, True), (t["xtx"], False), (tiles, True)):
-        got = _metric(dev, c, Out(dev, (C, C), src=src), Out(dev, C, src=t["colsum"]), ws, host)
+        got = _metric(dev, c, Buf(dev, (C, C), src=src), Buf(dev, C, src=t["colsum"]), ws, host)
         _hold(name, got)
         res.append(got)
     for k in STATS:
@@ -341,13 +324,13 @@ def test_whiten_metric_vs_float64(dev, name):
 
 
 def test_whiten_metric_refusals(dev):
-    lib, st = _env()
+    _, lib, st = env()
     xtx, colsum, ws = torch.zeros(8, 8, device=dev), torch.zeros(8, device=dev), torch.zeros(20, device=dev)
-    cov, mean, scal = Out(dev, (1, 8, 8)), Out(dev, 8), Out(dev, 4)
-    call = lambda n, G, w: lib.s2t_whiten_metric(_p(xtx), _p(colsum), n, G, 8, _p(cov), _p(mean), _p(scal), None, w, st)  # noqa: E731
-    assert call(0, 1, _p(ws)) == -1 and call(10, 0, _p(ws)) == -1 and call(10, 1, None) == -1
-    x65, o65 = torch.zeros(8, 65, device=dev), Out(dev, (65, 65))
-    assert lib.s2t_gemm_xtx(_p(x65), 65, 8, 65, 65, _p(o65), 65, _p(colsum), st) == -2       # C % 4: no wx case at (1, 65)
+    cov, mean, scal = Buf(dev, (1, 8, 8)), Buf(dev, 8), Buf(dev, 4)
+    call = lambda n, G, w: lib.s2t_whiten_metric(ptr(xtx), ptr(colsum), n, G, 8, ptr(cov), ptr(mean), ptr(scal), None, w, st)  # noqa: E731
+    assert call(0, 1, ptr(ws)) == -1 and call(10, 0, ptr(ws)) == -1 and call(10, 1, None) == -1
+    x65, o65 = torch.zeros(8, 65, device=dev), Buf(dev, (65, 65))
+    assert lib.s2t_gemm_xtx(ptr(x65), 65, 8, 65, 65, ptr(o65), 65, ptr(colsum), st) == -2       # C % 4: no wx case at (1, 65)
     torch.cuda.synchronize()
     for o in (cov, mean, scal, o65):
         o.untouched("refused whiten_metric")
@@ -357,13 +340,13 @@ def test_whiten_metric_refusals(dev):
 def test_whiten_metric_after_the_xtx_product(dev, name):
     """s2t_gemm_xtx -> s2t_whiten_metric from x itself, against the reference's centred form; the product
     leaves everything outside its tiles alone."""
-    lib, st = _env()
+    _, lib, st = env()
     c, t = ZA.CASES[name], ZA.make(name)
     G, cg = c["G"], c["cg"]
     C = G * cg
     x = _in(dev, t["x"])
-    xtx, colsum = Out(dev, (C, C), src=torch.zeros(C, C)), Out(dev, C, src=torch.zeros(C))
-    assert lib.s2t_gemm_xtx(_p(x), C, ZA.ROWS, C, cg, _p(xtx), C, _p(colsum), st) == 0
+    xtx, colsum = Buf(dev, (C, C), src=torch.zeros(C, C)), Buf(dev, C, src=torch.zeros(C))
+    assert lib.s2t_gemm_xtx(ptr(x), C, ZA.ROWS, C, cg, ptr(xtx), C, ptr(colsum), st) == 0
     torch.cuda.synchronize()
     assert not bool(xtx.t.cpu()[~ZA.xtx_needed(G, cg)].any()), f"{name}: s2t_gemm_xtx wrote outside its tiles"
     _hold(name, _metric(dev, c, xtx, colsum, _metric_ws(dev, C)))
@@ -373,7 +356,7 @@ def test_whiten_metric_after_the_xtx_product(dev, name):
 def test_whiten_dcov_and_prep_vs_float64(dev, name):
     """s2t_whiten_dcov and s2t_whiten_prep: dcov from NaN, exactly zero off the block diagonal, symmetric bit
     for bit; sums[0..1] (all 128 slots for _prep) zeroed from NaN."""
-    lib, st = _env()
+    _, lib, st = env()
     c, t = ZA.CASES[name], ZA.make(name)
     G, cg = c["G"], c["cg"]
     C = G * cg
@@ -382,9 +365,9 @@ def test_whiten_dcov_and_prep_vs_float64(dev, name):
     same = i.unsqueeze(1) == i.unsqueeze(0)
     res = []
     for prep in (False, True):
-        dcov, bias, sums = Out(dev, (C, C)), Out(dev, C), Out(dev, 128 if prep else 2)
+        dcov, bias, sums = Buf(dev, (C, C)), Buf(dev, C), Buf(dev, 128 if prep else 2)
         fn = lib.s2t_whiten_prep if prep else lib.s2t_whiten_dcov
-        assert fn(_p(cov), _p(mean), _p(scal), G, cg, _p(dcov), _p(bias), _p(sums), st) == 0
+        assert fn(ptr(cov), ptr(mean), ptr(scal), G, cg, ptr(dcov), ptr(bias), ptr(sums), st) == 0
         torch.cuda.synchronize()
         for what, o in (("dcov", dcov), ("bias", bias), ("sums", sums)):
             o.intact(f"{name} {what}")
@@ -394,9 +377,9 @@ def test_whiten_dcov_and_prep_vs_float64(dev, name):
         assert not bool(sums.t.any()), f"{name}: sums not zeroed"
         res.append((dcov.t, bias.t))
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
-    dcov, bias = Out(dev, (C, C)), Out(dev, C)
-    assert lib.s2t_whiten_prep(_p(cov), _p(mean), _p(scal), G, cg, _p(dcov), _p(bias), None, st) == -1
-    assert lib.s2t_whiten_dcov(_p(cov), _p(mean), _p(scal), 0, cg, _p(dcov), _p(bias), None, st) == -1
+    dcov, bias = Buf(dev, (C, C)), Buf(dev, C)
+    assert lib.s2t_whiten_prep(ptr(cov), ptr(mean), ptr(scal), G, cg, ptr(dcov), ptr(bias), None, st) == -1
+    assert lib.s2t_whiten_dcov(ptr(cov), ptr(mean), ptr(scal), 0, cg, ptr(dcov), ptr(bias), None, st) == -1
     torch.cuda.synchronize()
     dcov.untouched(f"{name}: refused")
     bias.untouched(f"{name}: refused")
@@ -407,19 +390,19 @@ def test_whiten_dcov_and_prep_vs_float64(dev, name):
 def test_whiten_streams_vs_float64(dev, name):
     """s2t_sumsq64 into N(0,1) slots (the increment, summed over the 64 slots); s2t_whiten_combine64 on clean
     slots; s2t_whiten_apply (its own sums pass) and s2t_whiten_combine on those sums."""
-    lib, st = _env()
+    _, lib, st = env()
     c, t = ZA.CASES[name], ZA.make(name)
     n, gs = c["n"], ZA.GRAD_SCALE
     g, pg = _in(dev, t["g"]), _in(dev, t["pg"])
-    pre = Out(dev, 128, src=t["pre64"])
-    clean = Out(dev, 128, src=torch.zeros(128))
+    pre = Buf(dev, 128, src=t["pre64"])
+    clean = Buf(dev, 128, src=torch.zeros(128))
     for s in (pre, clean):
-        assert lib.s2t_sumsq64(_p(g), n, _p(s), st) == 0
-        assert lib.s2t_sumsq64(_p(pg), n, s.t[64:].data_ptr(), st) == 0
-    o64, oa, oc, sums = Out(dev, n), Out(dev, n), Out(dev, n), Out(dev, 2, src=torch.zeros(2))
-    assert lib.s2t_whiten_combine64(_p(g), _p(pg), n, gs, _p(clean), _p(o64), st) == 0
-    assert lib.s2t_whiten_apply(_p(g), _p(pg), n, gs, _p(sums), _p(oa), st) == 0
-    assert lib.s2t_whiten_combine(_p(g), _p(pg), n, gs, _p(sums), _p(oc), st) == 0
+        assert lib.s2t_sumsq64(ptr(g), n, ptr(s), st) == 0
+        assert lib.s2t_sumsq64(ptr(pg), n, s.t[64:].data_ptr(), st) == 0
+    o64, oa, oc, sums = Buf(dev, n), Buf(dev, n), Buf(dev, n), Buf(dev, 2, src=torch.zeros(2))
+    assert lib.s2t_whiten_combine64(ptr(g), ptr(pg), n, gs, ptr(clean), ptr(o64), st) == 0
+    assert lib.s2t_whiten_apply(ptr(g), ptr(pg), n, gs, ptr(sums), ptr(oa), st) == 0
+    assert lib.s2t_whiten_combine(ptr(g), ptr(pg), n, gs, ptr(sums), ptr(oc), st) == 0
     torch.cuda.synchronize()
     for what, o in (("sums64", pre), ("sums64 (clean)", clean), ("combine64", o64), ("apply", oa), ("combine", oc), ("sums", sums)):
         o.intact(f"{name} {what}")
@@ -435,20 +418,20 @@ def test_whiten_streams_vs_float64(dev, name):
 
 
 def test_whiten_streams_refuse_misaligned_operands(dev):
-    lib, st = _env()
+    _, lib, st = env()
     n = 64
     al, mis = _in(dev, torch.ones(n)), _in(dev, torch.ones(n), True)
-    sums, s64 = Out(dev, 2, src=torch.zeros(2)), Out(dev, 128, src=torch.zeros(128))
-    for g, pg, out in ((mis, al, Out(dev, n)), (al, mis, Out(dev, n)), (al, al, Out(dev, n, mis=True))):
-        assert lib.s2t_whiten_apply(_p(g), _p(pg), n, 0.05, _p(sums), _p(out), st) == -1
-        assert lib.s2t_whiten_combine(_p(g), _p(pg), n, 0.05, _p(sums), _p(out), st) == -1
-        assert lib.s2t_whiten_combine64(_p(g), _p(pg), n, 0.05, _p(s64), _p(out), st) == -1
+    sums, s64 = Buf(dev, 2, src=torch.zeros(2)), Buf(dev, 128, src=torch.zeros(128))
+    for g, pg, out in ((mis, al, Buf(dev, n)), (al, mis, Buf(dev, n)), (al, al, Buf(dev, n, mis=True))):
+        assert lib.s2t_whiten_apply(ptr(g), ptr(pg), n, 0.05, ptr(sums), ptr(out), st) == -1
+        assert lib.s2t_whiten_combine(ptr(g), ptr(pg), n, 0.05, ptr(sums), ptr(out), st) == -1
+        assert lib.s2t_whiten_combine64(ptr(g), ptr(pg), n, 0.05, ptr(s64), ptr(out), st) == -1
         torch.cuda.synchronize()
         out.untouched("misaligned operand")
-    out = Out(dev, n)
-    assert lib.s2t_whiten_combine(_p(al), _p(al), n, 0.05, None, _p(out), st) == -1
-    assert lib.s2t_whiten_combine64(_p(al), _p(al), n, 0.05, None, _p(out), st) == -1
-    assert lib.s2t_sumsq64(_p(mis), n, _p(s64), st) == -1
+    out = Buf(dev, n)
+    assert lib.s2t_whiten_combine(ptr(al), ptr(al), n, 0.05, None, ptr(out), st) == -1
+    assert lib.s2t_whiten_combine64(ptr(al), ptr(al), n, 0.05, None, ptr(out), st) == -1
+    assert lib.s2t_sumsq64(ptr(mis), n, ptr(s64), st) == -1
     torch.cuda.synchronize()
     out.untouched("NULL sums")
     assert not bool(sums.t.any()) and not bool(s64.t.any())
@@ -456,10 +439,10 @@ def test_whiten_streams_refuse_misaligned_operands(dev):
 
 @pytest.mark.parametrize("name", COVER["lp"])
 def test_limit_param_grad_is_bit_exact(dev, name):
-    lib, st = _env()
+    _, lib, st = env()
     c, t = ZA.CASES[name], ZA.make(name)
-    x, g, out = _in(dev, t["x"]), _in(dev, t["g"]), Out(dev, c["n"])
-    assert lib.s2t_limit_param_grad(_p(x), _p(g), c["lo"], c["hi"], c["n"], _p(out), st) == 0
+    x, g, out = _in(dev, t["x"]), _in(dev, t["g"]), Buf(dev, c["n"])
+    assert lib.s2t_limit_param_grad(ptr(x), ptr(g), c["lo"], c["hi"], c["n"], ptr(out), st) == 0
     torch.cuda.synchronize()
     out.intact(name)
     ref = ZA.reference(name)["out"].float()

@@ -589,28 +589,6 @@ def N_lib():
     return _native.lib()
 
 
-def _balancer_ref64(x, g, min_mean, max_mean, min_rms, max_rms, grad_scale, swoosh):
-    """reference model/layer/scaling.py:741-789 in closed form (as zk.balancer_backward's torch path), fp64.
-    Right on live channels only: where a variance is at the 1e-20 clamp it multiplies by 1 / (std var)
-    what autograd sees as a constant.  tests/test_zip_f64.py pins the autograd restatement
-    (tests/zip_f64.py balancer_bwd_ref, the yardstick below) to it on live channels."""
-    x, g = x.double(), g.double()
-    if swoosh is not None:
-        g = g * (torch.sigmoid(x - (4.0 if swoosh else 1.0)) - 0.08)
-    n = x.shape[0]
-    mean = x.mean(0, keepdim=True)
-    uvar = (x * x).mean(0, keepdim=True)
-    var = (uvar - mean * mean).clamp(min=1.0e-20)
-    std, rms = var.sqrt(), uvar.clamp(min=1.0e-20).sqrt()
-    m = mean / std
-    s_m = torch.sign(m - m.clamp(min=min_mean, max=max_mean))
-    s_r = -torch.sign((rms.clamp(min=min_rms, max=max_rms) / rms).log())
-    a = s_m / n * (1.0 / std + mean * mean / (std * var))
-    b = -s_m / n * mean / (std * var) + s_r / n / (rms * rms)
-    lg_rms = (a * a + 2 * a * b * mean + b * b * uvar).clamp(min=0).sqrt().clamp(min=1.0e-20)
-    return g + g.abs() * (a + b * x) * (grad_scale / lg_rms)
-
-
 @pytest.mark.parametrize("rows,C", [(31680, 192), (15872, 576), (7936, 960), (3968, 1024), (1000, 100), (37, 256),
                                     (5000, 260), (300001, 8), (50001, 32), (4097, 16), (333, 4)])
 @pytest.mark.parametrize("swoosh", [None, True])

@@ -6,78 +6,30 @@ tests/zip_f64.py, at every dispatch edge (tests/zip_cases.py names why each shap
 
 Error = max |got - ref| / max |ref| per tensor; allowed = zip_cases.bound(case, tensor) =
 max(2e-5, 8 x the case's float32 figure of the YARDSTICK, asserted by tests/test_zip_f64.py).
-Every buffer a kernel writes is allocated with a guard of a sentinel behind it, which must be intact
-afterwards; accumulators are pre-filled and must hold pre-fill + reference; a call the entry point
+Every buffer a kernel writes is a guarded buffer of tests/guarded.py holding the sentinel SENT, with a
+guard of SENT behind it (and one word in front where it is misaligned), which must be intact afterwards; accumulators are pre-filled and must hold pre-fill + reference; a call the entry point
 must refuse returns -1 and leaves its outputs at the sentinel.
 """
 import ctypes
+import functools
 
 import pytest
 import torch
 
+import guarded
 import zip_cases as ZC
 import zip_f64 as ZF
+from guarded import SENT, env, hold
 
 pytestmark = pytest.mark.gpu
 
-SENT = -7777.25          # no kernel under test produces it
-
-
-class Buf:
-    """A float32 device buffer of `shape` with a guard of SENT behind it; mis: its first element is 4
-    bytes past a multiple of 16.  src: initial contents; else fill (the sentinel by default)."""
-
-    def __init__(self, dev, shape, src=None, mis=False, fill=SENT):
-        shape = tuple(shape) if isinstance(shape, (tuple, list, torch.Size)) else (shape,)
-        n = 1
-        for s in shape:
-            n *= s
-        self.n, self.off = n, (1 if mis else 0)
-        self.full = torch.full((self.off + n + max(64, shape[-1]),), SENT, dtype=torch.float32, device=dev)
-        self.t = self.full[self.off:self.off + n].view(shape)
-        assert self.t.data_ptr() % 16 == (4 if mis else 0)
-        if src is not None:
-            self.t.copy_(src.reshape(shape))
-        elif fill != SENT:
-            self.t.fill_(fill)
-
-    def intact(self, what):
-        assert bool((self.full[self.off + self.n:] == SENT).all()), f"{what}: the guard behind the buffer was written"
-        assert bool((self.full[:self.off] == SENT).all()), f"{what}: the word in front of the buffer was written"
-
-    def untouched(self, what):
-        assert bool((self.full == SENT).all()), f"{what}: a refused call wrote its output"
+Buf = functools.partial(guarded.Buf, fill=SENT)
+_hold = functools.partial(hold, ZC)
 
 
 def _intact(name, **bufs):
     for k, b in bufs.items():
         b.intact(f"{name} {k}")
-
-
-def _hold(name, got, alias=None, partial=False):
-    """Every tensor of `got` within zip_cases.bound of the reference (alias: got key -> the reference
-    tensor it must equal); all misses are reported."""
-    ref, alias = ZC.reference(name), alias or {}
-    if not partial:
-        assert {alias.get(k, k) for k in got} == set(ref), (sorted(got), sorted(ref))
-    bad = []
-    for k, v in got.items():
-        rk = alias.get(k, k)
-        for w in (v if isinstance(v, list) else [v]):
-            assert bool(torch.isfinite(w).all()), f"{name} {k}: not finite"
-        r = ref[rk]
-        if not isinstance(r, list):
-            v = v.reshape(r.shape)
-        err, tol = ZC.rel_err(v, r), ZC.bound(name, rk)
-        print(f"{name} {k}: err {err:.3e} bound {tol:.3e}")
-        if not err <= tol:
-            bad.append(f"{name} {k}: err {err:.3e} > bound {tol:.3e}")
-    assert not bad, "; ".join(bad)
-
-
-def _env():
-    from speech2text_amd import _native as N
-    return N, N.lib(), N.stream()
 
 
 def _dev(dev, t, *keys):
@@ -87,7 +39,7 @@ def _dev(dev, t, *keys):
 # ------------------------------------------------------------------ Swoosh
 @pytest.mark.parametrize("name", ZC.names("sw"))
 def test_swoosh_kernels_vs_float64(dev, name):
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = ZC.CASES[name], ZC.make(name)
     n = c["n"]
     off, cst = ZF.SWOOSH[c["is_l"]]
@@ -118,7 +70,7 @@ def test_swoosh_wrappers_on_a_view_off_the_alignment_rule(dev):
 def test_biasnorm_kernels_vs_float64(dev, name):
     """Forward (y and the per-row scales) and backward into pre-filled dbias / dls; the _tb cases
     through s2t_biasnorm_fwd_tb / _bwd_tb."""
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = ZC.CASES[name], ZC.make(name)
     R, D = c["rows"], c["D"]
     x, bias, ls, g = _dev(dev, t, "x", "bias", "ls", "g")
@@ -150,7 +102,7 @@ def test_biasnorm_kernels_vs_float64(dev, name):
 
 
 def test_biasnorm_backward_refuses_a_row_longer_than_1024(dev):
-    N, lib, st = _env()
+    N, lib, st = env()
     R, D = 3, 1028
     x, bias, g = torch.randn(R, D, device=dev), torch.zeros(D, device=dev), torch.randn(R, D, device=dev)
     scales = torch.ones(R, device=dev)
@@ -169,7 +121,7 @@ def test_biasnorm_backward_refuses_a_row_longer_than_1024(dev):
 def test_norm_bypass_kernels_vs_float64(dev, name):
     """s2t_norm_bypass_fwd and _bwd: out, the scales, dx, d_orig and the three pre-filled parameter
     gradients, each against float64."""
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = ZC.CASES[name], ZC.make(name)
     R, B, D, mis = c["rows"], c["B"], c["D"], c["mis"]
     bias, ls, bscale, fm = _dev(dev, t, "bias", "ls", "bscale", "fm")
@@ -192,7 +144,7 @@ def test_norm_bypass_kernels_vs_float64(dev, name):
 
 
 def test_norm_bypass_refuses_a_row_longer_than_1024_and_an_empty_batch(dev):
-    N, lib, st = _env()
+    N, lib, st = env()
     R = 3
     for D, B, fwd_too in ((1028, 1, False), (64, 0, True)):
         x, orig, g = (torch.randn(R, D, device=dev) for _ in range(3))
@@ -239,12 +191,12 @@ def test_balancer_kernels_vs_float64(dev, name):
     """s2t_balancer_bwd (statistics + update in one call, alternating accumulators) and the pair
     s2t_balancer_stats + s2t_balancer_apply, each against the autograd restatement: the output and the
     update alone.  Dead channels (variance or E[x^2] at the 1e-20 clamp) included."""
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = ZC.CASES[name], ZC.make(name)
     R, C = c["rows"], c["C"]
     x, g, out, out2, (ldx, ldg, ldo) = _bal_operands(dev, c, t)
-    ws, stats = Buf(dev, lib.s2t_balancer_bwd_workspace_floats(), fill=0.0), Buf(dev, 2048, fill=0.0)
-    assert ws.n == 4096
+    assert lib.s2t_balancer_bwd_workspace_floats() == 4096
+    ws, stats = Buf(dev, 4096, torch.zeros(4096)), Buf(dev, 2048, torch.zeros(2048))
     N.check(lib.s2t_balancer_bwd(N.fp(x.t), ldx, N.fp(g.t), ldg, R, C, *ZC.BAL_CFG, N.fp(out.t), ldo, N.fp(ws.t), 0,
                                  _act_off(c), st), "s2t_balancer_bwd")
     N.check(lib.s2t_balancer_stats(N.fp(x.t), ldx, R, C, N.fp(stats.t), st), "s2t_balancer_stats")
@@ -270,8 +222,8 @@ def test_balancer_bwd_leaves_the_other_accumulator_clean_after_a_wider_user(dev)
     """Two successive s2t_balancer_bwd calls on alternating parity, the first with C = 1024 and the
     second with C = 64: the second must clear the WHOLE accumulator the first one used (2048 floats),
     and a third call on that accumulator is right again."""
-    N, lib, st = _env()
-    ws = Buf(dev, 4096, fill=0.0)
+    N, lib, st = env()
+    ws = Buf(dev, 4096, torch.zeros(4096))
     for parity, name in ((0, "bal_c1024"), (1, "bal_c64"), (0, "bal_c64")):
         c, t = ZC.CASES[name], ZC.make(name)
         R, C = c["rows"], c["C"]
@@ -286,7 +238,7 @@ def test_balancer_bwd_leaves_the_other_accumulator_clean_after_a_wider_user(dev)
 
 
 def test_balancer_refuses_more_than_1024_channels(dev):
-    N, lib, st = _env()
+    N, lib, st = env()
     R, C = 3, 1025
     x, g = torch.randn(R, C, device=dev), torch.randn(R, C, device=dev)
     out, ws = Buf(dev, (R, C)), Buf(dev, 4096)
@@ -303,7 +255,7 @@ def test_balancer_refuses_more_than_1024_channels(dev):
 def test_bypass_kernels_vs_float64(dev, name):
     """s2t_bypass_fwd / _fwd_mask (refused when C % 4 != 0), s2t_bypass_bwd / _bwd_mask / _bwd_acc into
     a pre-filled d_scale."""
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = ZC.CASES[name], ZC.make(name)
     R, C, B = c["rows"], c["C"], c["B"]
     orig, src, scale, g, fm, acc_in = _dev(dev, t, "orig", "src", "scale", "g", "fm", "acc_in")
@@ -343,7 +295,7 @@ def test_bypass_kernels_vs_float64(dev, name):
 def test_downsample_kernels_vs_float64(dev, name):
     """s2t_downsample_fwd / _fwd_bt and s2t_downsample_bwd / _bwd_bt (dw pre-filled): time-major and
     batch-major output and gradient give the same values."""
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = ZC.CASES[name], ZC.make(name)
     ds, T, B, C, mis = c["ds"], c["T"], c["B"], c["C"], c["mis"]
     dT = (T + ds - 1) // ds
@@ -367,7 +319,7 @@ def test_downsample_kernels_vs_float64(dev, name):
 
 
 def test_downsample_refuses_a_factor_above_8(dev):
-    N, lib, st = _env()
+    N, lib, st = env()
     T, B, C, ds = 10, 2, 8, 9
     src, g, w = torch.randn(T, B, C, device=dev), torch.randn(2, B, C, device=dev), torch.ones(ds, device=dev) / ds
     out, dsrc, dw = Buf(dev, (2, B, C)), Buf(dev, (T, B, C)), Buf(dev, ds)
@@ -385,7 +337,7 @@ def test_downsample_refuses_a_factor_above_8(dev):
 def test_upsample_bypass_kernels_vs_float64(dev, name):
     """s2t_bypass_up_fwd (refused when C % 4 != 0; its float4 stream has no scalar form, so the
     misaligned case runs the backward only) and s2t_bypass_up_bwd into a pre-filled d_scale."""
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = ZC.CASES[name], ZC.make(name)
     up, T, B, C, mis = c["up"], c["T"], c["B"], c["C"], c["mis"]
     Ts = (T + up - 1) // up
@@ -415,7 +367,7 @@ def test_upsample_bypass_kernels_vs_float64(dev, name):
 def test_nonlin_gate_and_out_kernels_vs_float64(dev, name):
     """s2t_nonlin_gate_fwd / _out_fwd / _out_bwd / _gate_bwd on u = [s | x | y]; du is written in
     thirds: [ds | dx] by the gate's backward, [dy] by the out's, and neither touches the other's."""
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = ZC.CASES[name], ZC.make(name)
     T, B, C = c["T"], c["B"], c["C"]
     u, z, g, dxs = _dev(dev, t, "u", "z", "g", "dxs")
@@ -437,7 +389,7 @@ def test_nonlin_gate_and_out_kernels_vs_float64(dev, name):
 
 # ------------------------------------------------------------------ attention row constants
 def _delta_call(dev, c, t, delta):
-    N, lib, st = _env()
+    N, lib, st = env()
     keep = [t["W"].to(dev), None if t["dW0"] is None else t["dW0"].to(dev)]
     args = []
     for p, dv in zip(t["pairs"], (c["dv1"], c["dv2"])):
@@ -493,7 +445,7 @@ def _commit_items(dev, N, items, limits):
 def test_param_grad_commit_vs_float64(dev, name):
     """grad += d (after limit_param_value's sign flip where asked) for up to 8 parameters in one
     launch; d is exactly zero afterwards, x is not written."""
-    N, lib, st = _env()
+    N, lib, st = env()
     c, t = ZC.CASES[name], ZC.make(name)
     arr, bufs = _commit_items(dev, N, t["items"], c["limit"])
     N.check(lib.s2t_param_grad_commit_n(len(bufs), ctypes.cast(arr, ctypes.c_void_p), st), "s2t_param_grad_commit_n")
@@ -506,7 +458,7 @@ def test_param_grad_commit_vs_float64(dev, name):
 
 
 def test_param_grad_commit_refuses_nine_items_and_does_nothing_for_none(dev):
-    N, lib, st = _env()
+    N, lib, st = env()
     g = torch.Generator().manual_seed(2)
     items = [dict(x=torch.randn(5, generator=g), d=torch.randn(5, generator=g), grad=torch.randn(5, generator=g))
              for _ in range(9)]
@@ -521,7 +473,7 @@ def test_param_grad_commit_refuses_nine_items_and_does_nothing_for_none(dev):
 # ------------------------------------------------------------------ add
 @pytest.mark.parametrize("name", ZC.names("add"))
 def test_add_kernel_vs_float64(dev, name):
-    N, lib, st = _env()
+    N, lib, st = env()
     n = ZC.CASES[name]["n"]
     t = ZC.make(name)
     a, b = _dev(dev, t, "a", "b")
@@ -535,7 +487,7 @@ def test_add_kernel_vs_float64(dev, name):
 
 
 def test_add_refuses_an_operand_off_16_bytes(dev):
-    N, lib, st = _env()
+    N, lib, st = env()
     a, b, out = Buf(dev, 8, mis=True), Buf(dev, 8), Buf(dev, 8)
     for args in ((a, b, out), (b, a, out), (b, b, a)):
         assert lib.s2t_add_f32(*(N.fp(v.t) for v in args), 8, st) == -1

@@ -8,13 +8,10 @@ import pytest
 import torch
 
 from oracle import zipformer as Z
+from decode_support import TINY
 
 pytestmark = pytest.mark.gpu
 
-TINY = dict(feature_dim=80, downsampling_factor=(1, 2, 4), num_encoder_layers=(1, 1, 1),
-            feedforward_dim=(64, 96, 96), encoder_dim=(32, 48, 48), encoder_unmasked_dim=(24, 32, 32),
-            num_heads=(4, 4, 4), query_head_dim=(8,), value_head_dim=(4,), pos_head_dim=(4,),
-            pos_dim=16, cnn_module_kernel=(7, 5, 5), causal=True)
 MID = dict(feature_dim=80, downsampling_factor=(1, 2, 4), num_encoder_layers=(2, 1, 1),
            feedforward_dim=(128, 192, 192), encoder_dim=(64, 96, 96), encoder_unmasked_dim=(48, 64, 64),
            num_heads=(4, 4, 8), query_head_dim=(16,), value_head_dim=(8,), pos_head_dim=(4,),

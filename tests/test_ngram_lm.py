@@ -12,6 +12,7 @@ import torch
 import ctc_ngram_cases as C
 import ctc_ngram_f64 as G
 from speech2text_amd.model.lm.ngram_lm import BOS, NgramLm
+from task_support import _base_cfg, _CONF, _TOK, _V
 
 # order 3, pieces as words; `d` and the blank have no unigram; `c` is a context without a back-off column,
 # `<unk>` has a back-off and nothing after it; three entries predict </s>
@@ -272,8 +273,6 @@ def test_classes_refuse_what_is_not_fused():
 
 # ------------------------------------------------------------------ 5. the YAML section
 def _ctc_cfg():
-    from test_gpu_conformer_tasks import _CONF, _base_cfg
-    from test_gpu_validation import _TOK, _V
     cfg = _base_cfg()
     cfg.update({"task": {"type": "CTC"}, "tokenizer": _TOK, "encoder": _CONF,
                 "decoder": {"model": "Projector", "config": {"input_dim": 64, "output_dim": _V, "dropout_p": 0.1}},

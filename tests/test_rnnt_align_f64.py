@@ -14,6 +14,7 @@ import torch
 import lattice_types_f64 as LT
 import rnnt_align_cases as C
 import rnnt_align_f64 as A
+from decode_support import _lib
 
 
 # ------------------------------------------------------------------ 1. the conditions
@@ -124,9 +125,6 @@ def test_best_path_is_the_best_of_all_paths_on_small_lattices(rnnt_type):
 
 
 # ------------------------------------------------------------------ 3. the host side of the entry
-def _lib():
-    from speech2text_amd import _native as N
-    return N, N.lib()
 
 
 def _ty(name):

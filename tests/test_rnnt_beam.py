@@ -7,27 +7,18 @@ reference class's tokens on utterances where it agrees with the float64 restatem
 (tests/rnnt_beam_restatement.py) and every decision of the search has a margin of at least 16 N,
 N = the reference's own fp32 score noise of the configuration.  Bounds: tokens and frames exact;
 score within 4 N."""
-import functools
 
 import numpy as np
 import pytest
 import torch
 
 import rnnt_beam_restatement as R
-
-
-@functools.lru_cache(maxsize=None)
-def _fixture(golden_dir):
-    return R.load_fixture(golden_dir)
+from decode_support import _beam_modules, _fixture, _fixture_free_config, _long_input, _search, _tokenizer
+from task_support import _pcm_batch, _pruned_beam_cfg
 
 
 def _params(c):
     return {k: c[k] for k in R.PARAM_KEYS}
-
-
-def _tokenizer(V):
-    from speech2text_amd.dataset.utils import TokenizerSetup
-    return TokenizerSetup({"type": "char", "config": {"labels": [chr(97 + i) for i in range(V - 3)]}})
 
 
 class _PlainPredictor:
@@ -121,16 +112,6 @@ def test_factory_and_metric_config():
         AsrMetric(_tokenizer(40), AsrMetricConfig(decode_method="ctc_lexicon_beam_search"))
 
 
-def _long_input(c):
-    """Rows 0-7 of the seeded 64 x 90 input of test_degenerate_beam_equals_the_greedy_kernel (row 0 has
-    90 frames): longer than one 64-frame block of the staged trace-back (csrc/decode_records.h)."""
-    g = torch.Generator().manual_seed(17)
-    am = torch.randn(64, 90, c["V"], generator=g) * 3.0
-    lens = torch.randint(1, 91, (64,), generator=g)
-    lens[0] = 90
-    return am[:8].contiguous(), lens[:8].numpy()
-
-
 def test_long_input_emits_on_both_sides_of_the_trace_blocks(golden_dir):
     """What tests/test_gpu_rnnt_stream_search.py::test_long_chunks_cross_the_trace_blocks relies on, by
     the float64 restatement: at beam 4 / top-k 4 the best beam of row 0 (90 frames: blocks [26, 90)
@@ -142,15 +123,6 @@ def test_long_input_emits_on_both_sides_of_the_trace_blocks(golden_dir):
     assert min(frames) < 26 and max(frames) >= 64, frames
 
 
-def _fixture_free_config(V=40, D=48, E=32, ctx=3, act="relu", seed=5, scale=1.0):
-    g = np.random.default_rng(seed)
-    c = {"V": V, "D": D, "E": E, "ctx": ctx, "act": act}
-    for k, shape in (("emb", (V, E)), ("conv_w", (E, ctx)), ("lin_w", (D, E)), ("lin_b", (D,)),
-                     ("pre_w", (V, D)), ("pre_b", (V,)), ("enc_w", (V, D)), ("enc_b", (V,))):
-        c[k] = (g.standard_normal(shape) * scale / np.sqrt(shape[-1])).astype(np.float32)
-    return c
-
-
 def test_workspace_size_is_a_pure_host_function():
     from speech2text_amd import _native as N
     lib = N.lib()
@@ -160,39 +132,6 @@ def test_workspace_size_is_a_pure_host_function():
 
 
 # ---------------------------------------------------------------------------------------- GPU
-
-def _modules(c, dev):
-    """Product Predictor / Joiner carrying a configuration's weights."""
-    from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
-    from speech2text_amd.model.predictor.predictor import Predictor
-    pred = Predictor({"model": "Stateless", "config": {
-        "num_symbols": c["V"], "output_dim": c["D"], "symbol_embedding_dim": c["E"],
-        "context_size": c["ctx"]}})
-    join = Joiner(JoinerConfig(input_dim=c["D"], output_dim=c["V"], activation=c["act"],
-                               prune_range=5, use_out_project=False))
-    p = pred.predictor
-    with torch.no_grad():
-        p._embedding.weight.copy_(torch.from_numpy(c["emb"]))
-        p._conv.weight.copy_(torch.from_numpy(c["conv_w"]).reshape(c["E"], 1, c["ctx"]))
-        p._output_linear.weight.copy_(torch.from_numpy(c["lin_w"]))
-        p._output_linear.bias.copy_(torch.from_numpy(c["lin_b"]))
-        join._pre_proj.weight.copy_(torch.from_numpy(c["pre_w"]))
-        join._pre_proj.bias.copy_(torch.from_numpy(c["pre_b"]))
-        if "enc_w" in c:
-            join._enc_proj.weight.copy_(torch.from_numpy(c["enc_w"]))
-            join._enc_proj.bias.copy_(torch.from_numpy(c["enc_b"]))
-    return pred.to(dev), join.to(dev)
-
-
-def _search(c, am, lens, dev, beam=None, topk=None):
-    from speech2text_amd.model.decoding import rnnt_beam_tokens_from_am
-    pred, join = _modules(c, dev)
-    out = rnnt_beam_tokens_from_am(torch.as_tensor(am).to(dev), torch.as_tensor(lens), pred, join,
-                                   c["beam"] if beam is None else beam,
-                                   c["topk"] if topk is None else topk)
-    assert out is not None, "the fused search refused a shape it must take"
-    torch.cuda.synchronize()
-    return [x.cpu() for x in out]
 
 
 @pytest.mark.gpu
@@ -214,7 +153,7 @@ def test_fused_search_is_exact_on_every_stored_utterance(dev, golden_dir):
 def _greedy_from_am(c, am, lens, dev):
     """s2t_rnnt_greedy_stateless on a given am with max_token_step = 0 (one symbol per frame)."""
     from speech2text_amd import _native as N
-    pred, join = _modules(c, dev)
+    pred, join = _beam_modules(c, dev)
     p = pred.predictor
     am = torch.as_tensor(am).to(dev).contiguous()
     B, T, V = am.shape
@@ -267,7 +206,7 @@ def test_through_the_class(dev, golden_dir):
     from speech2text_amd.model.decoding import RnntBeamDecoding, batch_search
     c = _fixture(golden_dir)[1]
     assert (c["V"], c["act"], c["ctx"]) == (40, "relu", 5)
-    pred, join = _modules(c, dev)
+    pred, join = _beam_modules(c, dev)
     tok = _tokenizer(40)
     sess = RnntBeamDecoding(tok, pred, join, beam_size=c["beam"], cutoff_top_k=c["topk"])
     assert sess._fusable()
@@ -325,7 +264,7 @@ def test_ragged_and_edge_cases(dev, golden_dir):
             assert above[0][b, :n].tolist() == tok_b and above[1][b, :n].tolist() == frames_b
             assert abs(float(above[3][b]) - score_b) <= 1e-4
 
-    pred, join = _modules(s, dev)
+    pred, join = _beam_modules(s, dev)
     p = pred.predictor
     amd = am.to(dev).contiguous()
     ld = torch.as_tensor(lens).to(dev)
@@ -371,7 +310,7 @@ def test_module_loop_on_the_device_gives_the_fused_tokens(dev, golden_dir):
     from speech2text_amd.model.decoding import RnntBeamDecoding
     c = _fixture(golden_dir)[3]
     assert (c["V"], c["ctx"], c["beam"], c["topk"]) == (40, 2, 8, 3)
-    pred, join = _modules(c, dev)
+    pred, join = _beam_modules(c, dev)
     sess = RnntBeamDecoding(_tokenizer(40), pred, join, beam_size=8, cutoff_top_k=3)
     enc, lens = torch.from_numpy(c["enc"]).to(dev), torch.from_numpy(c["lengths"])
     with torch.no_grad():
@@ -390,33 +329,15 @@ def test_module_loop_on_the_device_gives_the_fused_tokens(dev, golden_dir):
             assert loop[1][b, :n].tolist() == fused[1][b, :n].tolist(), b
 
 
-def _pruned_cfg(V):
-    """A tiny Pruned_Rnnt task (the construction of tests/test_gpu_validation.py::_pruned_cfg)."""
-    import bench
-    cfg = bench.c3_config(V)
-    cfg["encoder"]["config"].update({"downsampling_factor": [1, 2], "num_encoder_layers": [1, 1],
-                                     "feedforward_dim": [96, 128], "encoder_dim": [48, 64],
-                                     "encoder_unmasked_dim": [32, 48], "num_heads": [4, 4],
-                                     "query_head_dim": 8, "value_head_dim": 4, "pos_dim": 16,
-                                     "cnn_module_kernel": [15, 7], "chunk_size": [-1],
-                                     "left_context_frames": [-1]})
-    cfg["predictor"]["config"].update({"output_dim": 64, "symbol_embedding_dim": 32})
-    cfg["joiner"].update({"input_dim": 64})
-    cfg["tokenizer"] = {"type": "char", "config": {"labels": [chr(97 + i) for i in range(V - 3)]}}
-    cfg["metric"] = {"decode_method": "rnnt_beam_search", "beam_size": 3, "cutoff_top_k": 2}
-    return cfg
-
-
 @pytest.mark.gpu
 def test_validation_step_reports_beam_wer(dev):
     """Check 6: AsrMetric with rnnt_beam_search inside a task's validation_step."""
     from speech2text_amd.build_task import TaskFactory
     from speech2text_amd.model.decoding import RnntBeamDecoding, reference_decoder
     from speech2text_amd.model.utils import word_error_rate
-    from test_gpu_conformer_tasks import _pcm_batch
     V = 32
     torch.manual_seed(0)
-    task = TaskFactory.get("Pruned_Rnnt")(_pruned_cfg(V)).to(dev)
+    task = TaskFactory.get("Pruned_Rnnt")(_pruned_beam_cfg(V)).to(dev)
     task.eval()
     with torch.no_grad():
         for p in list(task._predictor.parameters()) + list(task._joiner.parameters()):

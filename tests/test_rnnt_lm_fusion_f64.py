@@ -18,11 +18,8 @@ import rnnt_lm_fusion_cases as L
 import rnnt_lm_fusion_f64 as F
 import rnnt_lstm_search_cases as C
 import rnnt_lstm_search_f64 as S
-
-
-class _Ids:
-    def decode(self, t):
-        return [int(x) for x in t]
+from yardstick import _Ids
+from task_support import _rnnt_cfg
 
 
 # ------------------------------------------------------------------ 1. lm_weight 0 is the un-fused search
@@ -158,21 +155,6 @@ def test_without_an_lm_the_class_is_what_it_was():
 
 
 # ------------------------------------------------------------------ 5. the task does not own the LM
-def _rnnt_cfg():
-    from test_gpu_conformer_tasks import _CONF, _base_cfg
-    from test_gpu_validation import _TOK, _V
-    cfg = _base_cfg()
-    cfg.update({"task": {"type": "Rnnt"}, "tokenizer": _TOK, "encoder": _CONF,
-                "decoder": {"model": "Identity", "config": {"dummy": -1}},
-                "predictor": {"model": "Lstm", "config": {"num_symbols": _V, "output_dim": 64,
-                                                          "symbol_embedding_dim": 32, "num_lstm_layers": 2,
-                                                          "lstm_hidden_dim": 48, "lstm_layer_norm": True,
-                                                          "lstm_layer_norm_epsilon": 1e-3, "lstm_dropout": 0.1}},
-                "joiner": {"input_dim": 64, "output_dim": _V, "inner_dim": 48, "activation": "tanh",
-                           "prune_range": -1},
-                "metric": {"decode_method": "rnnt_beam_search", "beam_size": 3, "cutoff_top_k": 3},
-                "loss": {"model": "Rnnt", "config": {"blank_label": 0, "reduction": "mean"}}})
-    return cfg, _V
 
 
 def test_task_with_metric_lm_has_the_same_state_and_parameters(tmp_path):

@@ -17,11 +17,7 @@ import torch
 
 import rnnt_lstm_search_cases as C
 import rnnt_lstm_search_f64 as S
-
-
-class _Ids:
-    def decode(self, t):
-        return [int(x) for x in t]
+from yardstick import _Ids
 
 
 def _fixture(golden_dir):

@@ -22,11 +22,7 @@ import rnnt_lm_fusion_f64 as F
 import rnnt_lstm_search_f64 as S
 import rnnt_stateless_lm_cases as SC
 import rnnt_stateless_lm_f64 as SF
-
-
-class _Ids:
-    def decode(self, t):
-        return [int(x) for x in t]
+from yardstick import _Ids
 
 
 class _PlainStateless:

@@ -1,15 +1,10 @@
 """CPU: the host side of the chunk-carried RNN-T search (csrc/decode_stream.hip) -- the size of its
 state buffer -- and the test's own yardstick: the chunked float64 restatement
 (tests/rnnt_stream_restatement.py) against the whole-utterance one on every stored utterance."""
-import functools
 
 import rnnt_beam_restatement as R
 import rnnt_stream_restatement as S
-
-
-@functools.lru_cache(maxsize=None)
-def _fixture(golden_dir):
-    return R.load_fixture(golden_dir)
+from decode_support import _fixture
 
 
 def test_state_size_is_a_pure_host_function():

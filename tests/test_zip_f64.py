@@ -4,8 +4,8 @@ The restatements are pinned in float64 at 1e-12 before any kernel is compared wi
 oracle.zipformer where the oracle states the operation (swoosh_l / swoosh_r, bias_norm, bypass,
 simple_downsample, simple_upsample, _LimitParam, _Balancer), against plain torch autograd or an
 index-by-index loop where it does not; torch.autograd.gradcheck on the differentiable ones.  The
-Balancer's restatement (autograd through the loss) equals the closed form of
-tests/test_gpu_zip_ops.py on live channels and differs from it on a constant one, where the closed
+Balancer's restatement (autograd through the loss) equals the closed form
+zip_f64.balancer_bwd_closed_form on live channels and differs from it on a constant one, where the closed
 form divides by the clamped variance.
 
 The last part measures what float32 costs the REFERENCE on every case of tests/zip_cases.py: the
@@ -19,26 +19,9 @@ import torch
 import zip_cases as ZC
 import zip_f64 as ZF
 from oracle import zipformer as OZ
+from yardstick import F64, _grads, _rn, _same
 
-F64 = torch.float64
-TOL = dict(atol=1e-12, rtol=1e-12)
 GC = dict(eps=1e-6, atol=1e-7, rtol=1e-6)
-
-
-def _rn(seed):
-    g = torch.Generator().manual_seed(seed)
-    return lambda *s: torch.randn(*s, generator=g, dtype=F64)
-
-
-def _same(a, b, what=""):
-    np.testing.assert_allclose(a.detach().numpy(), b.detach().numpy(), err_msg=what, **TOL)
-
-
-def _grads(out, g, *leaves):
-    for v in leaves:
-        v.grad = None
-    (out * g).sum().backward(retain_graph=True)
-    return [v.grad.clone() for v in leaves]
 
 
 # ------------------------------------------------------------------ Swoosh
@@ -221,7 +204,6 @@ def _bal_x(rn, rows, C):
 
 @pytest.mark.parametrize("swoosh", [None, True, False])
 def test_balancer_ref_equals_the_oracle_and_the_closed_form_on_live_channels(monkeypatch, swoosh):
-    from test_gpu_zip_ops import _balancer_ref64
     rn = _rn(9)
     x, g = _bal_x(rn, 50, 24), rn(50, 24)
     out = ZF.balancer_bwd_ref(x, g, *ZC.BAL_CFG, swoosh=swoosh)
@@ -234,7 +216,7 @@ def test_balancer_ref_equals_the_oracle_and_the_closed_form_on_live_channels(mon
     assert xo.grad.dtype == F64
     _same(out, xo.grad)
     assert float((out - ge).abs().max()) > 1e-3 * float(out.abs().max())        # the update is really there
-    cf = _balancer_ref64(x, g, *ZC.BAL_CFG, swoosh if swoosh is None else bool(swoosh))
+    cf = ZF.balancer_bwd_closed_form(x, g, *ZC.BAL_CFG, swoosh if swoosh is None else bool(swoosh))
     if swoosh is not False:           # (the closed form of that file knows SwooshL only)
         np.testing.assert_allclose(out.numpy(), cf.numpy(), atol=1e-12 * float(out.abs().max()), rtol=1e-9)
     # channels on both sides of every clamp
@@ -250,13 +232,12 @@ def test_balancer_ref_and_the_closed_form_differ_on_a_constant_channel():
     (derivative zero), so the loss gradient is s_m / (n std) and the update is +-grad_scale |g|.  The
     closed form multiplies by 1 / (std var) = 1e30 and cancels it again in float64 rounding noise.
     An all-zero channel gets no update from either."""
-    from test_gpu_zip_ops import _balancer_ref64
     rn = _rn(10)
     x, g = _bal_x(rn, 64, 6), rn(64, 6)
     x[:, 1] = 0.75
     x[:, 2] = 0.0
     out = ZF.balancer_bwd_ref(x, g, *ZC.BAL_CFG)
-    cf = _balancer_ref64(x, g, *ZC.BAL_CFG, None)
+    cf = ZF.balancer_bwd_closed_form(x, g, *ZC.BAL_CFG, None)
     _same(out[:, 1], g[:, 1] + ZC.BAL_CFG[4] * g[:, 1].abs())       # mean / std = +inf side: s_m = +1
     _same(out[:, 2], g[:, 2])
     live = [0, 3, 4, 5]

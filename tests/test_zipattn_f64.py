@@ -22,20 +22,10 @@ import torch
 import zipattn_cases as ZA
 import zipattn_f64 as ZR
 from oracle import zipformer as OZ
+from yardstick import F64, _rn, _same
 
-F64 = torch.float64
-TOL = dict(atol=1e-12, rtol=1e-12)
 GC = dict(eps=1e-6, atol=1e-7, rtol=1e-6)
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "speech2text_amd", "csrc")
-
-
-def _rn(seed):
-    g = torch.Generator().manual_seed(seed)
-    return lambda *s: torch.randn(*s, generator=g, dtype=F64)
-
-
-def _same(a, b, what=""):
-    np.testing.assert_allclose(a.detach().numpy(), b.detach().numpy(), err_msg=what, **TOL)
 
 
 def _masks(T, B, am, kp):

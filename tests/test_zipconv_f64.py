@@ -12,7 +12,6 @@ host, so the GPU file's bounds cannot drift), checks that the float32 and float6
 for bit on the exactly representable inputs, that the launch arithmetic of the weight gradient gives
 the path each case names, and that the GPU file runs every case.
 """
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -20,26 +19,9 @@ import torch.nn.functional as F
 import zipconv_cases as ZC
 import zipconv_f64 as ZR
 from oracle import zipformer as OZ
+from yardstick import F64, _grads, _rn, _same
 
-F64 = torch.float64
-TOL = dict(atol=1e-12, rtol=1e-12)
 GC = dict(eps=1e-6, atol=1e-7, rtol=1e-6)
-
-
-def _rn(seed):
-    g = torch.Generator().manual_seed(seed)
-    return lambda *s: torch.randn(*s, generator=g, dtype=F64)
-
-
-def _same(a, b, what=""):
-    np.testing.assert_allclose(a.detach().numpy(), b.detach().numpy(), err_msg=what, **TOL)
-
-
-def _grads(out, g, *leaves):
-    for v in leaves:
-        v.grad = None
-    (out * g).sum().backward(retain_graph=True)
-    return [v.grad.clone() for v in leaves]
 
 
 # ------------------------------------------------------------------ conv module

@@ -127,6 +127,7 @@ import math
 import torch
 
 import zip_f64 as ZF
+from yardstick import FLOOR, MARGIN, UNIT, _leaf, bound_of, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 SAT = (0.0, -0.0, 20.0, -20.0, 87.0, -87.0, 88.5, -88.5, 100.0, -100.0, 1e4, -1e4)
 STREAM_CAP = 4096 * 256            # float4 elements one trip of a swoosh / add / bypass stream covers
@@ -365,10 +366,6 @@ def bal_kappa(name):
 
 
 # ------------------------------------------------------------------ the yardstick on a case
-def _leaf(v, dt, grad=True):
-    return None if v is None else v.to(dt).clone().requires_grad_(grad)
-
-
 def _eval_sw(c, t, dt):
     x = _leaf(t["x"], dt)
     y = ZF.swoosh_ref(x, c["is_l"])
@@ -478,25 +475,10 @@ def reference(name):
     return evaluate(name, torch.float64)
 
 
-def rel_err(got, ref):
-    """max |got - ref| relative to max |ref|, the error measure of every bound in both files; of
-    lists: the largest over the items, each relative to its own reference."""
-    if isinstance(ref, (list, tuple)):
-        return max(rel_err(a, b) for a, b in zip(got, ref))
-    ref = ref.detach().double().cpu()
-    got = got.detach().double().cpu()
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    return float((got - ref).abs().max() / (ref.abs().max() + 1e-300))
-
-
 def fp32_figures(name):
     """{tensor: rel_err of the float32 CPU evaluation of the yardstick against float64}."""
     ref, f32 = reference(name), evaluate(name, torch.float32)
     return {k: rel_err(f32[k], ref[k]) for k in ref}
-
-
-FLOOR = 2e-5            # the project's figure (tests/conf_cases.py, test_gpu_conformer_layer.py)
-MARGIN = 8.0            # the project's margin on a float32 figure (tests/lstm_cases.py)
 
 
 def bound(name, tensor):
@@ -508,7 +490,7 @@ def bound(name, tensor):
     fig = FP32_COST[name][tensor]
     if CASES[name]["group"] == "bal":
         fig = fig * bal_kappa(name)
-    return max(FLOOR, MARGIN * fig)
+    return bound_of(fig)
 
 
 # ------------------------------------------------------------------ measured cost of fp32
@@ -516,7 +498,6 @@ def bound(name, tensor):
 # the host's summation order and vector maths; tests/test_zip_f64.py checks it to a factor 4 both
 # ways after raising both to UNIT, as tests/test_conf_f64.py does: a figure below one float32 rounding
 # says nothing a host would repeat, and no figure below FLOOR / MARGIN = 2.5e-6 reaches a bound.
-UNIT = 2.0 ** -24
 FP32_COST = {
     "sw_n4": dict(y=1.7e-8, d=1.3e-7),
     "sw_n3": dict(y=5.9e-8, d=4.0e-7),

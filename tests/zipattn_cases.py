@@ -56,8 +56,8 @@ import functools
 
 import torch
 
-import zip_cases as ZC
 import zipattn_f64 as ZR
+from yardstick import FLOOR, MARGIN, UNIT, bound_of, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 
 F64 = torch.float64
 LIMIT = 25.0
@@ -438,10 +438,6 @@ def flag_expected(name):
     return bool((reference(name)["_raw"].abs() > LIMIT).any())
 
 
-rel_err = ZC.rel_err
-FLOOR, MARGIN, UNIT = ZC.FLOOR, ZC.MARGIN, ZC.UNIT
-
-
 def fp32_figures(name):
     """{tensor: rel_err of the float32 CPU evaluation of the yardstick against float64}."""
     ref, f32 = reference(name), evaluate(name, torch.float32)
@@ -455,7 +451,7 @@ def bound(name, tensor):
     same expression on the kernel's own inputs, so its float32 figure carries the amplification already
     (wm_off5, kappa = 26: figure 1.8e-6 for cov against 3e-7 ... 5e-7 at kappa <= 7.3), and against the
     centred form the composed cases stay below the 2e-5 floor even at kappa = 26 (wx_off5)."""
-    return max(FLOOR, MARGIN * FP32_COST[name][tensor])
+    return bound_of(FP32_COST[name][tensor])
 
 
 # ------------------------------------------------------------------ measured cost of fp32

@@ -57,6 +57,7 @@ import functools
 import torch
 
 import zip_cases as ZC
+from yardstick import FLOOR, MARGIN, UNIT, bound_of, rel_err  # noqa: F401  (the rule of tests/yardstick.py)
 import zipconv_f64 as ZR
 
 SAT10 = tuple(v for v in ZC.SAT if abs(v) < 1e4)
@@ -350,8 +351,6 @@ EXACT_TENSORS = ("y", "du", "dwc", "dbc", "dwk", "dbk", "y0", "y1", "dx")     # 
 # cases whose float32 and float64 references differ on the exact inputs (test_zipconv_f64.py): none
 EXACT_DROPPED = ()
 
-rel_err = ZC.rel_err
-
 
 def fp32_figures(name):
     """{tensor: rel_err of the float32 CPU evaluation of the yardstick against float64}."""
@@ -359,12 +358,9 @@ def fp32_figures(name):
     return {k: rel_err(f32[k], ref[k]) for k in ref}
 
 
-FLOOR, MARGIN, UNIT = ZC.FLOOR, ZC.MARGIN, ZC.UNIT
-
-
 def bound(name, tensor):
     """Allowed rel_err of device tensor `tensor` of case `name`: max(2e-5, 8 x the float32 figure)."""
-    return max(FLOOR, MARGIN * FP32_COST[name][tensor])
+    return bound_of(FP32_COST[name][tensor])
 
 
 # ------------------------------------------------------------------ measured cost of fp32
