@@ -30,6 +30,53 @@ int s2t_fbank_f32(const float* pcm, long pcm_stride, const long* num_samples, in
                   float scale_in, const float* cmvn_mean, const float* cmvn_istd, float* out,
                   int max_frames, long* out_frames, void* stream);
 
+/* ---- the fbank carried across chunks (csrc/fbank_stream.hip, csrc/fbank_kernel.h): audio arrives in arbitrary cuts, the frames
+ * leave as the one-shot kernel would have computed them.  pcm [batch][pcm_stride] holds each row's NEW
+ * samples, chunk_samples [batch] how many (clamped to 0..pcm_stride), flush [batch] != 0 ends the row;
+ * tables, eps, scale_in and the optional fused CMVN as s2t_fbank_f32; out [batch][max_new_frames]
+ * [num_mel], new_frames [batch] (may be NULL).  THE STATEMENT, for row b: the stream so far is the
+ * concatenation of every chunk fed since the row's reset, N samples in total; one_shot is
+ * s2t_fbank_f32 on those N samples; frames(N) = N >= 400 ? 1 + (N - 400) / 160 : 0.
+ *   Frames leave in pairs: pair p (frames 2p and 2p+1) is emitted by the first call after which
+ *   N >= 320 p + 560, all newly completed pairs in frame order.  The kernel packs frames 2p and 2p+1
+ *   into one complex FFT and a frame's fp32 result depends on its partner at rounding level, so the
+ *   pairing is by ABSOLUTE frame index, whatever the cuts.
+ *   Flush: with flush[b] != 0 the call also emits the one remaining complete frame, if frames(N) is
+ *   odd, packed with the partner the one-shot kernel stages for it: the samples that exist, then
+ *   zeros.  After a flush the row is ended: until its reset it accepts no samples (chunk_samples[b] is
+ *   read as 0), emits nothing, and its state keeps every bit.
+ *   The invariant: the frames a row has emitted up to any call, in order, equal the corresponding rows
+ *   of one_shot's output on the N samples the stream holds in the end, bit for bit -- with and
+ *   without the fused CMVN, for any scale_in, however the samples were cut, calls of 0 samples
+ *   included; after the flush their number is one_shot's out_frames.
+ *   Output rows: new_frames[b] = the frames this call emitted for row b; rows of out at or past it
+ *   hold the one-shot kernel's padding (0, CMVN'd when CMVN is fused); every element of out is written.
+ * State, caller-owned, two buffers:
+ *   carry  [batch][S2T_FBANK_CARRY_MAX] fp32   the RAW samples (scale_in is applied where the one-shot
+ *          kernel applies it, at staging) from the start of the first un-emitted pair: pair P is
+ *          un-emitted exactly when N < 320 P + 560, so at most 559 samples, N - 160 * emitted of them;
+ *   counts [batch][S2T_FBANK_STATE_LONGS] int64   N, the frames emitted, the ended flag, 0.
+ *   A row is reset by zeroing its counts (its carry need not be cleared: none of it is live).
+ * A call of n >= 1 samples emits at most 2 * ((n - 1) / 320 + 1) + 1 frames, one of 0 samples at most
+ * 1 (the flush): s2t_fbank_chunk_max_frames(n), a pure host function.  max_new_frames must be at least
+ * s2t_fbank_chunk_max_frames(pcm_stride), so that no emitted frame is ever without a row; the grid is
+ * sized from max_new_frames, 32 frames to a workgroup.
+ * Two launches on `stream`: the frame kernel reads carry and counts in every workgroup and writes
+ * neither; a second launch of one workgroup per row then moves the new tail into carry (through
+ * registers: the ranges overlap) and writes counts.  Stream order is what keeps a workgroup from
+ * overwriting what another still reads.  No host synchronisation, no memset: capturable.
+ * Return 0; -1 before any launch for pcm_stride < 0, max_new_frames below the bound, carry or counts
+ * NULL, and what s2t_fbank_f32 refuses; batch <= 0 returns 0. */
+#define S2T_FBANK_CARRY_MAX 559
+#define S2T_FBANK_STATE_LONGS 4
+int s2t_fbank_chunk_max_frames(long chunk_samples);
+int s2t_fbank_chunk_f32(const float* pcm, long pcm_stride, const long* chunk_samples, const int* flush,
+                        int batch, float* carry, long* counts, const float* window400,
+                        const float* twiddle512, const int* mel_off, const int* mel_k0,
+                        const float* mel_w, int nnz, int num_mel, float eps, float scale_in,
+                        const float* cmvn_mean, const float* cmvn_istd, float* out, int max_new_frames,
+                        long* new_frames, void* stream);
+
 /* ---- CTC: model/loss/ctc_loss.py:35-41 (log_softmax + nn.CTCLoss).
  * logits [B][T][V] batch-major; targets [B][tgt_stride]; loss_per_utt [B] (nll,
  * or 0 where infinite and zero_infinity); grad_logits [B][T][V] =

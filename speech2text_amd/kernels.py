@@ -92,6 +92,87 @@ def fbank_batch(pcm, num_samples, tables, cmvn_mean=None, cmvn_istd=None, scale_
     return out, frames
 
 
+FBANK_CARRY_MAX = N.const("S2T_FBANK_CARRY_MAX")
+
+
+def fbank_frames(num_samples):
+    """Frames the one-shot fbank gives num_samples samples (snip_edges, 400 at hop 160)."""
+    return 1 + (num_samples - 400) // 160 if num_samples >= 400 else 0
+
+
+def fbank_chunk_max_frames(chunk_samples):
+    """The most frames one fbank_chunk call of chunk_samples new samples can emit: the pairs the
+    samples can complete, and the flush's lone frame (s2t_fbank_chunk_max_frames, in integers)."""
+    return 2 * ((chunk_samples - 1) // 320 + 1) + 1 if chunk_samples >= 1 else 1
+
+
+def fbank_frames_after(total_samples, ended):
+    """Frames a stream of total_samples samples has emitted: every complete PAIR (pair p leaves once
+    total_samples >= 320 p + 560); after the flush (`ended`) the one-shot count."""
+    if total_samples < 0:
+        raise ValueError(f"total_samples must be >= 0, got {total_samples}")
+    if ended:
+        return fbank_frames(total_samples)
+    return 2 * ((total_samples - 560) // 320 + 1) if total_samples >= 560 else 0
+
+
+class FbankStreamState:
+    """The caller-owned state of fbank_chunk (include/s2t_mi355.h s2t_fbank_chunk_f32): `carry`
+    (B, 559) the raw samples of the first un-emitted frame pair onwards, `counts` (B, 4) int64 the
+    samples seen, the frames emitted and the ended flag.  A row whose counts are zero is a new stream."""
+
+    def __init__(self, batch_size, device):
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        self.batch_size = batch_size
+        self.carry = torch.zeros((batch_size, FBANK_CARRY_MAX), dtype=torch.float32, device=device)
+        self.counts = torch.zeros((batch_size, N.const("S2T_FBANK_STATE_LONGS")), dtype=torch.int64,
+                                  device=device)
+
+    def reset(self, rows=None):
+        """Rows (indices, or None for all) start a new stream."""
+        if rows is None:
+            self.counts.zero_()
+        else:
+            self.counts.index_fill_(0, torch.as_tensor(rows, dtype=torch.int64).to(self.counts.device), 0)
+
+
+def fbank_chunk(pcm, chunk_samples, flush, state, tables, cmvn_mean=None, cmvn_istd=None, scale_in=1.0,
+                max_new_frames=None, out=None, new_frames=None):
+    """The fbank carried across chunks: pcm (B, n) f32 the NEW samples, chunk_samples (B,) i64 how
+    many per row, flush (B,) i32 (!= 0 ends the row), state a FbankStreamState -> feats (B,
+    max_new_frames, M), new_frames (B,).  The frames a row emits over its calls are fbank_batch's on
+    the whole audio, bit for bit, however it was cut; they leave in pairs, the flush adds the lone
+    last frame.  `out` / `new_frames`: fixed buffers to write instead of fresh ones."""
+    _dev_check(pcm, chunk_samples, flush)
+    B, n = pcm.shape
+    if B != state.batch_size:
+        raise ValueError(f"pcm has {B} rows, the state {state.batch_size}")
+    if max_new_frames is None:
+        max_new_frames = fbank_chunk_max_frames(n) if out is None else out.shape[1]
+    if max_new_frames < fbank_chunk_max_frames(n):
+        raise ValueError(f"a call of {n} samples can emit {fbank_chunk_max_frames(n)} frames: "
+                         f"max_new_frames = {max_new_frames} is too small")
+    if out is None:
+        out = torch.empty((B, max_new_frames, tables.num_mel), dtype=torch.float32, device=pcm.device)
+    elif tuple(out.shape) != (B, max_new_frames, tables.num_mel):
+        raise ValueError(f"out must be {(B, max_new_frames, tables.num_mel)}, got {tuple(out.shape)}")
+    if new_frames is None:
+        new_frames = torch.empty((B,), dtype=torch.int64, device=pcm.device)
+    if n == 0:                       # (a zero-width tensor has no row stride to speak of)
+        pcm = pcm.new_zeros((B, 1))
+    N.PROF[0] and N.profile_note("s2t_fbank_chunk_f32", 4.0 * (pcm.numel() + out.numel()))
+    rc = N.lib().s2t_fbank_chunk_f32(N.fp(pcm), n, N.lp(chunk_samples), N.ip(flush), B,
+                                     N.fp(state.carry), N.lp(state.counts), N.fp(tables.window),
+                                     N.fp(tables.twiddle), N.ip(tables.mel_off), N.ip(tables.mel_k0),
+                                     N.fp(tables.mel_w), tables.nnz, tables.num_mel,
+                                     1.1920928955078125e-07, float(scale_in), N.fp(cmvn_mean),
+                                     N.fp(cmvn_istd), N.fp(out), max_new_frames, N.lp(new_frames),
+                                     N.stream())
+    N.check(rc, "s2t_fbank_chunk_f32")
+    return out, new_frames
+
+
 # =============================================================== CTC
 class _CtcLoss(torch.autograd.Function):
     @staticmethod

@@ -70,6 +70,18 @@ class TaskBase(nn.Module):
         feats, frames = self._frontend.forward_batch(pcm, n, mean, istd)
         return feats, frames
 
+    def audio_streaming_recognizer(self, batch_size=1, max_chunk_samples=5120, **kw):
+        """An AudioStreamingRecognizer (model/encoder/zipformer_audio_streaming.py): audio in arbitrary
+        cuts of at most max_chunk_samples samples in, text out, over this task's own frontend and its
+        `streaming_recognizer(batch_size, **kw)` (the CTC and RNN-T tasks have one)."""
+        from speech2text_amd.model.encoder.zipformer_audio_streaming import AudioStreamingRecognizer
+        if not hasattr(self, "streaming_recognizer"):
+            raise NotImplementedError(f"{type(self).__name__} has no streaming_recognizer to put audio in front of")
+        if self._frontend is None:
+            raise RuntimeError("audio_streaming_recognizer needs the YAML's `dataset:` feat_type / feat_config")
+        return AudioStreamingRecognizer(self.streaming_recognizer(batch_size=batch_size, **kw),
+                                        self._frontend, max_chunk_samples=max_chunk_samples)
+
     def _asr_metric(self, predictor=None, joiner=None):
         """AsrMetric of the YAML's `metric:` section (reference ctc_task.py:56-57,
         rnnt_task.py:65-69), or None when the config carries no tokenizer / metric."""
