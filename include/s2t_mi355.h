@@ -1133,6 +1133,96 @@ int s2t_ctc_prefix_beam_ngram_chunk(const S2tNgramLmDesc* lm, const float* logit
                                     long* out_len, float* score, float* lm_score, long* stable_len,
                                     int* overflow, void* stream);
 
+/* ---- Hotword (contextual) biasing of the CTC prefix beam search (csrc/ngram_lookup.h, csrc/ngram.hip,
+ * csrc/decode_ctc.h, csrc/decode_ctc.hip; the host side is model/lm/context_graph.py).  The caller's
+ * phrases (token-id lists) are compiled to an Aho-Corasick automaton in the n-gram's table form: a state
+ * is the longest suffix of a hypothesis that begins a phrase.  On a whole history h:
+ *   match(h)      the longest suffix of h that is a prefix (proper or whole) of some phrase
+ *   bias_sum(h) = context_score * len(match(h)) + sum over k in 1..len(h), over every phrase p that h[:k]
+ *                 ends with, of bonus(p)          (the first term is a loan, paid back when the match is lost)
+ *   final_bias(h) = bias_sum(h) without the first term
+ * Tables: ctx_begin [num_ctx + 1], ctx_fail [num_ctx] (the longest proper suffix of the state that is a
+ * state), ctx_backoff [num_ctx] = context_score * (depth(fail[n]) - depth(n)), ctx_final [num_ctx] =
+ * -context_score * depth(n), arc_token / arc_score / arc_next [num_arcs]; arc_score = context_score + the
+ * bonuses of every phrase ending at the arc's target.  State 0 is the root and is dense: exactly V arcs,
+ * arc c is class c (score 0 and next 0 for a class no phrase starts with).  The arcs of every other state
+ * are sorted by token, without duplicates.  The host validates the tables (ContextGraph).
+ * THE BIAS STATEMENT, bias(state, c) -> (score, next):  acc = 0.f, n = state.  While n != 0: binary-search c
+ * among the arcs of n; found at arc a: return (acc + arc_score[a], arc_next[a]); else acc += ctx_backoff[n],
+ * n = ctx_fail[n].  At the root return (acc + arc_score[c], arc_next[c]).  fp32 adds in exactly this
+ * order; the loop is bounded by max_depth + 1 whatever the tables hold (then the root answers), and every
+ * index taken from a table is clamped into its array.  It is THE SCORING STATEMENT's device function,
+ * handed these tables.
+ * Limits (else -1 / size 0, before any launch and without following a device pointer): graph and each of
+ * its seven pointers not NULL; 1 <= V <= S2T_RNNT_LSTM_MAX_VOCAB; max_depth in 0..S2T_CONTEXT_MAX_DEPTH;
+ * num_ctx >= 1; num_arcs >= V. */
+#define S2T_CONTEXT_MAX_DEPTH 64
+typedef struct S2tContextGraphDesc {
+  int V, max_depth, num_ctx, num_arcs;
+  const int *ctx_begin, *ctx_fail;
+  const float *ctx_backoff, *ctx_final;
+  const int* arc_token;
+  const float* arc_score;
+  const int* arc_next;
+} S2tContextGraphDesc;
+/* The statement for R independent rows in one launch: (score[r], next[r]) = bias(state[r], token[r]); a
+ * state outside [0, num_ctx) or a token outside [0, V) is clamped into it.  R <= 0 returns 0. */
+int s2t_context_score(const S2tContextGraphDesc* graph, int R, const int* state, const int* token,
+                      float* score, int* next, void* stream);
+/* s2t_ctc_prefix_beam / s2t_ctc_prefix_beam_ngram with the bias term, still ONE launch and the plain
+ * entry's workspace.  A live prefix also carries a graph state and bias_sum; the empty prefix starts in
+ * the root with bias_sum 0.  An extension that does not land on a live prefix runs the look-up (after the
+ * n-gram's, in the same thread), has bias_sum(p) + hit and, when kept, takes the `next` it returned; a
+ * candidate that lands on a live prefix keeps that prefix' sum and state.  Candidates rank by
+ *   (logaddexp(pb, pnb) + lm_weight * lm_sum) + bias_weight * bias_sum      (fp32, in this order; no LM: no
+ * LM term).  FINALISATION: when an entry writes its outputs, the reported hypothesis is the live prefix
+ * with the largest (logaddexp(pb, pnb) + lm_weight * lm_sum) + bias_weight * (bias_sum + ctx_final[state]),
+ * ties to the lower beam position: an utterance that ends mid-phrase keeps nothing for the unfinished
+ * part.  bias_score [B] is that prefix' bias_sum + ctx_final[state]; score and lm_score are that prefix'
+ * own.  The finalisation touches the outputs only.  A zero-length utterance: no tokens, all scores 0.
+ * With bias_weight = 0, and with a graph of no phrases at any weight, tokens, out_len, score and lm_score
+ * are the plain / n-gram entry's bit for bit.
+ * Refused (-1): what the partner entry refuses, the graph's limits above, graph.V != V, bias_weight not
+ * finite, bias_score NULL. */
+int s2t_ctc_prefix_beam_bias(const S2tContextGraphDesc* graph, const float* logits, const long* lengths,
+                             int B, int T, int V, int blank, int beam_size, int cutoff_top_k,
+                             float bias_weight, void* workspace, long* tokens, long* out_len, float* score,
+                             float* bias_score, void* stream);
+int s2t_ctc_prefix_beam_ngram_bias(const S2tNgramLmDesc* lm, const S2tContextGraphDesc* graph,
+                                   const float* logits, const long* lengths, int B, int T, int V, int blank,
+                                   int beam_size, int cutoff_top_k, float lm_weight, int start_ctx,
+                                   float bias_weight, void* workspace, long* tokens, long* out_len,
+                                   float* score, float* lm_score, float* bias_score, void* stream);
+/* The two entries above fed their frames in pieces: s2t_ctc_prefix_beam_chunk's /
+ * s2t_ctc_prefix_beam_ngram_chunk's contract word for word, ONE launch per call, with the entries above as
+ * the one-shot partners: for ANY cut, while overflow[b] == 0, a chunk call's outputs are the one-shot
+ * entry's on the frames fed so far bit for bit, bias_score included (the finalisation enters no state:
+ * the carried beam, its order, its states and the compaction are what they would be without it).
+ * Overflow bit 0 is set when the reported prefix or the one at beam position 0 is longer than max_tokens.
+ * state: the plain (s2t_ctc_stream_state_bytes) or n-gram (s2t_ctc_ngram_stream_state_bytes) layout
+ * first, byte for byte, followed by
+ *   bstate  [R] int32    the live prefixes' graph states, in beam order
+ *   bsum    [R] fp32     their bias_sum
+ * 256-byte aligned like every other array.  The resets are their partners'; a reset row starts in the
+ * root with bias_sum 0.  The graph must not change between the chunks of a live stream. */
+long s2t_ctc_bias_stream_state_bytes(int B, int V, int beam_size, int max_nodes);
+int s2t_ctc_bias_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
+                              void* stream);
+int s2t_ctc_prefix_beam_bias_chunk(const S2tContextGraphDesc* graph, const float* logits,
+                                   const long* chunk_len, int B, int Tc, int V, int blank, int beam_size,
+                                   int cutoff_top_k, float bias_weight, int max_tokens, int max_nodes,
+                                   void* state, long* tokens, long* out_len, float* score, float* bias_score,
+                                   long* stable_len, int* overflow, void* stream);
+long s2t_ctc_ngram_bias_stream_state_bytes(int B, int V, int beam_size, int max_nodes);
+int s2t_ctc_ngram_bias_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
+                                    int start_ctx, void* stream);
+int s2t_ctc_prefix_beam_ngram_bias_chunk(const S2tNgramLmDesc* lm, const S2tContextGraphDesc* graph,
+                                         const float* logits, const long* chunk_len, int B, int Tc, int V,
+                                         int blank, int beam_size, int cutoff_top_k, float lm_weight,
+                                         float bias_weight, int max_tokens, int max_nodes, void* state,
+                                         long* tokens, long* out_len, float* score, float* lm_score,
+                                         float* bias_score, long* stable_len, int* overflow, void* stream);
+
 /* ---- chunk-carried (streaming) RNN-T search with the LSTM predictor: the two searches above fed
  * their frames in pieces (csrc/decode_lstm.hip).  A round's launches ARE the whole-utterance calls'
  * (one text, the same arguments), and a row's arithmetic does not depend on the rows that share its

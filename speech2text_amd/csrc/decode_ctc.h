@@ -22,6 +22,15 @@
 // and records the `next` it returns beside clm, and a kept prefix that was not live takes that next:
 // nothing has to run between frames).  The n-gram mode's extra LDS is a struct of its own, so the
 // other modes' kernels keep the LDS and the arithmetic they had.
+//
+// Beside the LM mode stands a compile-time bias switch (hotwords: THE BIAS STATEMENT of
+// include/s2t_mi355.h).  A live prefix then also carries a graph state and bias_sum, in a struct of their
+// own (CtcBiasShared); the slot thread that runs the n-gram's look-up runs the graph's after it, through
+// the same device function; the ranking total gains bias_weight * bias_sum as its last add.  Every LDS
+// write of the bias part stands next to the n-gram part's write of the same kind (the candidates'
+// before the barrier that ends the slot phase, the beam's after the barrier that follows the picks'
+// reads), so the body needs no barrier it did not have.  With the switch off the body's text is what
+// it was.
 #pragma once
 #include "common.h"
 #include "decode_common.h"
@@ -62,6 +71,15 @@ struct CtcNgramShared {            // the n-gram mode's part of the beam and of 
   int cnext[kCtcSlots];            // the context a candidate is in when it is kept
 };
 
+struct CtcBiasShared {             // the bias switch's part of the beam and of the candidates
+  NgramTables g;                   // the graph in the look-up's table form (order = max_depth + 1)
+  const float* final;              // ctx_final [num_ctx]
+  int state[kMaxBeam];             // a live prefix' graph state ...
+  float sum[kMaxBeam];             // ... and its bias_sum
+  int cnext[kCtcSlots];            // the state a candidate is in when it is kept ...
+  float csum[kCtcSlots];           // ... and its bias_sum
+};
+
 // the empty prefix: pb = 0, pnb = -inf, the root node
 __device__ __forceinline__ void ctc_start(CtcShared& s, CtcNode* nodes) {
   if (threadIdx.x == 0) {
@@ -81,12 +99,13 @@ __device__ __forceinline__ void ctc_start(CtcShared& s, CtcNode* nodes) {
 // prefixes (beam order); emit / parent / token [beam] receive what s2t_rnn_lm_step needs, parent as a
 // row of the whole batch (row0 + position).  kCtcNgram: ng holds the tables and the context ids (else
 // NULL).  All kCtcThreads threads call it; it begins and ends with the beam in s (and ng) consistent
-// for every thread.
-template <int MODE>
+// for every thread.  BIAS: bs holds the graph, the states and the sums (else NULL).
+template <int MODE, bool BIAS = false>
 __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float* __restrict__ x, int V, int K,
                                           int BS, int blank, CtcNode* nodes, int max_nodes, float lm_weight,
                                           const float* __restrict__ q, int* emit, int* parent, int* token,
-                                          int row0, CtcNgramShared* ng = nullptr) {
+                                          int row0, CtcNgramShared* ng = nullptr, CtcBiasShared* bs = nullptr,
+                                          float bias_weight = 0.f) {
   constexpr bool LM = MODE != kCtcPlain;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nb = s.nb, K1 = K + 1, nc = nb * K1;
@@ -135,6 +154,12 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
     float cpb = S2T_NEG_INF, cpnb = S2T_NEG_INF, clm = s.lm_sum[i];
     int cnode = s.node[i], key = kCtcNoKey, cnext = 0;
     if (MODE == kCtcNgram) cnext = ng->state[i];
+    float cbsum = 0.f;
+    int cbnext = 0;
+    if (BIAS) {
+      cbsum = bs->sum[i];
+      cbnext = bs->state[i];
+    }
     if (j == 0) {
       for (int r = 0; r < K; ++r) {
         const int c = s.cls[r];
@@ -168,6 +193,11 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
             clm += h.logp;
             cnext = h.next;
           }
+          if (BIAS) {
+            const NgramHit h = ngram_score(bs->g, cbnext, c);
+            cbsum += h.logp;
+            cbnext = h.next;
+          }
         }
         cnode = id;
       }
@@ -178,7 +208,13 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
     s.cnode[xs] = cnode;
     s.ckey[xs] = key;
     if (MODE == kCtcNgram) ng->cnext[xs] = cnext;
-    s.ctot[xs] = LM ? cpnb + lm_weight * clm : cpnb;       // (an extension: pb = -inf; staying: below)
+    float ctot = LM ? cpnb + lm_weight * clm : cpnb;       // (an extension: pb = -inf; staying: below)
+    if (BIAS) {
+      bs->cnext[xs] = cbnext;
+      bs->csum[xs] = cbsum;
+      ctot = ctot + bias_weight * cbsum;
+    }
+    s.ctot[xs] = ctot;
   }
   __syncthreads();
   if (tid < nb) {                                          // the staying candidates take what landed on them
@@ -187,7 +223,9 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
     const float tot = log_add_precise(s.cpb[xs], pnb);
     s.cpnb[xs] = pnb;
     s.ckey[xs] = min(s.ckey[xs], s.ext_key[tid]);
-    s.ctot[xs] = LM ? tot + lm_weight * s.clm[xs] : tot;
+    float ctot = LM ? tot + lm_weight * s.clm[xs] : tot;
+    if (BIAS) ctot = ctot + bias_weight * bs->csum[xs];
+    s.ctot[xs] = ctot;
   }
   __syncthreads();
   // ---- rank by counting: total descending, then key ascending
@@ -207,8 +245,8 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
   // ---- the new beam
   const int xs = tid < BS ? s.pick[tid] : -1;
   const bool kept = xs >= 0;
-  float npb = 0.f, npnb = 0.f, nlm = 0.f;
-  int nnode = 0, nlast = 0, nlen = 0, npar = 0, src = tid, ext = 0, nstate = 0;
+  float npb = 0.f, npnb = 0.f, nlm = 0.f, nbsum = 0.f;
+  int nnode = 0, nlast = 0, nlen = 0, npar = 0, src = tid, ext = 0, nstate = 0, nbstate = 0;
   if (kept) {
     src = xs / K1;
     const int j = xs - src * K1;
@@ -221,6 +259,10 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
     nlen = s.len[src] + ext;
     npar = s.node[src];
     if (MODE == kCtcNgram) nstate = ng->cnext[xs];
+    if (BIAS) {
+      nbstate = bs->cnext[xs];
+      nbsum = bs->csum[xs];
+    }
   }
   __syncthreads();
   if (s.pick[0] < 0) {                                     // no candidate at all (NaN input): the beam stays
@@ -240,6 +282,10 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
     s.len[tid] = nlen;
     s.par_node[tid] = npar;
     if (MODE == kCtcNgram) ng->state[tid] = nstate;
+    if (BIAS) {
+      bs->state[tid] = nbstate;
+      bs->sum[tid] = nbsum;
+    }
   }
   if (MODE == kCtcRnn && tid < BS) {                       // a prefix that was not live steps the LM
     emit[tid] = kept && ext;
@@ -269,22 +315,46 @@ __device__ __forceinline__ void ctc_frame(CtcShared& s, float* row, const float*
 // max_tokens positions: a longer prefix keeps its first max_tokens tokens and out_len saturates there
 // (the whole-utterance entries pass T: a prefix has at most a token a frame).  The walk ends at the
 // root, whatever its depth (a chunk-carried trie's root is the committed prefix), after at most
-// max_hops nodes.
+// max_hops nodes.  pos: the beam position reported (the bias entries' finalisation picks it).
 __device__ __forceinline__ void ctc_finish(const CtcShared& s, const CtcNode* nodes, long* __restrict__ tokens,
                                            long* out_len, float* score, float* lm_score, int max_tokens,
-                                           int max_hops) {
+                                           int max_hops, int pos = 0) {
   if (threadIdx.x == 0) {
-    const int n = s.len[0];
+    const int n = s.len[pos];
     *out_len = min(n, max_tokens);
-    *score = log_add_precise(s.pb[0], s.pnb[0]);
-    if (lm_score) *lm_score = s.lm_sum[0];
-    int id = s.node[0];
+    *score = log_add_precise(s.pb[pos], s.pnb[pos]);
+    if (lm_score) *lm_score = s.lm_sum[pos];
+    int id = s.node[pos];
     for (int p = n - 1, hop = 0; p >= 0 && id > 0 && hop < max_hops; --p, ++hop) {
       const CtcNode nd = nodes[id];
       if (p < max_tokens) tokens[p] = nd.token;
       id = nd.parent;
     }
   }
+}
+
+// The bias entries' finalisation: the live prefix with the largest (logaddexp(pb, pnb) + lm_weight *
+// lm_sum) + bias_weight * (bias_sum + ctx_final[state]), ties to the lower position; *bias_score is its
+// bias_sum + ctx_final[state].  It reads the beam and writes an output: nothing of it is carried.
+// Thread 0 calls it, after the barrier that ends a frame (or the load of the beam).
+template <bool LM>
+__device__ __forceinline__ int ctc_bias_pick(const CtcShared& s, const CtcBiasShared& bs, float lm_weight,
+                                             float bias_weight, float* bias_score) {
+  int pos = 0;
+  float best = 0.f, best_bias = 0.f;
+  for (int i = 0; i < s.nb; ++i) {
+    float tot = log_add_precise(s.pb[i], s.pnb[i]);
+    if (LM) tot = tot + lm_weight * s.lm_sum[i];
+    const float fb = bs.sum[i] + bs.final[ngram_clamp(bs.state[i], bs.g.num_ctx)];
+    tot = tot + bias_weight * fb;
+    if (i == 0 || tot > best) {
+      pos = i;
+      best = tot;
+      best_bias = fb;
+    }
+  }
+  *bias_score = best_bias;
+  return pos;
 }
 
 }  // namespace s2t_dec

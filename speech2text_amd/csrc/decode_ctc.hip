@@ -20,6 +20,11 @@
 //                            the two above fed their frames in pieces: beam and trie in a caller-owned
 //                            state, the same frame body and round kernel, and at the end of every call
 //                            a compaction of the trie to what the live prefixes can still reach.
+//   s2t_ctc_prefix_beam_bias, s2t_ctc_prefix_beam_ngram_bias, and their _chunk partners
+//                            the plain and n-gram launches with the frame body's bias switch on: a live
+//                            prefix also carries a hotword-graph state and bias_sum (two more arrays behind
+//                            the state's layout), and the outputs report the live prefix that is best
+//                            once every unfinished match has been paid back (the finalisation).
 //   s2t_ctc_prefix_beam_ngram_chunk
 //                            the n-gram form fed its frames in pieces: the plain chunk kernel's shape in
 //                            the frame body's n-gram mode, still ONE launch; the state gains the live
@@ -41,8 +46,9 @@ struct CtcCompact {
 };
 
 static_assert(sizeof(float) * S2T_RNNT_LSTM_MAX_VOCAB + sizeof(CtcShared) + sizeof(CtcNgramShared) +
-                      sizeof(CtcCompact) <= 60 * 1024,
-              "a frame's logits are staged in LDS whole, beside the beam, the n-gram part and the compaction's");
+                      sizeof(CtcBiasShared) + sizeof(CtcCompact) <= 60 * 1024,
+              "a frame's logits are staged in LDS whole, beside the beam, the n-gram part, the bias part and the "
+              "compaction's");
 
 struct CtcArgs {
   const float* logits;    // [B][T][V]
@@ -99,6 +105,73 @@ __global__ __launch_bounds__(kCtcThreads) void ctc_prefix_ngram_kernel(CtcNgramA
                          a.lm_weight, nullptr, nullptr, nullptr, nullptr, 0, &ng);
   ctc_finish(s, nodes, a.c.tokens + (long)b * a.c.T, a.c.out_len + b, a.c.score + b, a.lm_score + b, a.c.T,
              a.c.max_nodes);
+}
+
+// ------------------------------------------------------------------ the bias forms: one launch
+struct CtcBiasArgs {
+  CtcNgramArgs n;         // (g, lm_weight, start_ctx, lm_score: the n-gram form only)
+  NgramTables graph;
+  const float* ctx_final;
+  float bias_weight;
+  float* bias_score;      // [B]
+};
+
+// the graph and the empty prefix' bias part: the root, nothing lent
+__device__ __forceinline__ void ctc_bias_start(CtcBiasShared& bs, const NgramTables& graph, const float* ctx_final) {
+  if (threadIdx.x == 0) {
+    bs.g = graph;
+    bs.final = ctx_final;
+    bs.state[0] = 0;
+    bs.sum[0] = 0.f;
+  }
+}
+
+__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_bias_kernel(CtcBiasArgs a) {
+  extern __shared__ float row[];
+  __shared__ CtcShared s;
+  __shared__ CtcBiasShared bs;
+  const CtcArgs& c = a.n.c;
+  const int b = blockIdx.x;
+  const int Tb = (int)clamped_len(c.lengths, b, c.T);
+  CtcNode* nodes = c.nodes + (long)b * c.max_nodes;
+  const float* x = c.logits + (long)b * c.T * c.V;
+  ctc_start(s, nodes);
+  ctc_bias_start(bs, a.graph, a.ctx_final);
+  __syncthreads();
+  const int K = min(c.topk, c.V);
+  for (int t = 0; t < Tb; ++t)
+    ctc_frame<kCtcPlain, true>(s, row, x + (long)t * c.V, c.V, K, c.beam, c.blank, nodes, c.max_nodes, 0.f, nullptr,
+                               nullptr, nullptr, nullptr, 0, nullptr, &bs, a.bias_weight);
+  int pos = 0;
+  if (threadIdx.x == 0) pos = ctc_bias_pick<false>(s, bs, 0.f, a.bias_weight, a.bias_score + b);
+  ctc_finish(s, nodes, c.tokens + (long)b * c.T, c.out_len + b, c.score + b, nullptr, c.T, c.max_nodes, pos);
+}
+
+__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_ngram_bias_kernel(CtcBiasArgs a) {
+  extern __shared__ float row[];
+  __shared__ CtcShared s;
+  __shared__ CtcNgramShared ng;
+  __shared__ CtcBiasShared bs;
+  const CtcArgs& c = a.n.c;
+  const int b = blockIdx.x;
+  const int Tb = (int)clamped_len(c.lengths, b, c.T);
+  CtcNode* nodes = c.nodes + (long)b * c.max_nodes;
+  const float* x = c.logits + (long)b * c.T * c.V;
+  ctc_start(s, nodes);
+  if (threadIdx.x == 0) {
+    ng.g = a.n.g;
+    ng.state[0] = a.n.start_ctx;
+  }
+  ctc_bias_start(bs, a.graph, a.ctx_final);
+  __syncthreads();
+  const int K = min(c.topk, c.V);
+  for (int t = 0; t < Tb; ++t)
+    ctc_frame<kCtcNgram, true>(s, row, x + (long)t * c.V, c.V, K, c.beam, c.blank, nodes, c.max_nodes, a.n.lm_weight,
+                               nullptr, nullptr, nullptr, nullptr, 0, &ng, &bs, a.bias_weight);
+  int pos = 0;
+  if (threadIdx.x == 0) pos = ctc_bias_pick<true>(s, bs, a.n.lm_weight, a.bias_weight, a.bias_score + b);
+  ctc_finish(s, nodes, c.tokens + (long)b * c.T, c.out_len + b, c.score + b, a.n.lm_score + b, c.T, c.max_nodes,
+             pos);
 }
 
 // ------------------------------------------------------------------ the lockstep form
@@ -263,11 +336,13 @@ struct CtcStream {
   long* eff;                       // [B] frames the current call consumes (the LM family's rounds read it)
   float *h, *c, *q;                // the LM's live copy (LM family)
   int* ctx;                        // [R] the live prefixes' context ids (n-gram family)
+  int* bstate;                     // [R] the live prefixes' graph states and bias sums (bias families)
+  float* bsum;
   size_t bytes;
 };
 
 CtcStream carve_ctc_stream(const S2tRnnLmDesc* lm, int B, int V, int beam, int max_nodes, void* base,
-                           bool ngram = false) {
+                           bool ngram = false, bool bias = false) {
   const size_t R = (size_t)B * beam, M = (size_t)B * max_nodes;
   char* p = static_cast<char*>(base);
   size_t off = 0;
@@ -295,6 +370,10 @@ CtcStream carve_ctc_stream(const S2tRnnLmDesc* lm, int B, int V, int beam, int m
     s.q = f(R * V);
   }
   if (ngram) s.ctx = i(R);                                 // (behind the plain layout, which it leaves as it is)
+  if (bias) {                                              // (behind either, likewise)
+    s.bstate = i(R);
+    s.bsum = f(R);
+  }
   s.bytes = off;
   return s;
 }
@@ -354,8 +433,17 @@ __device__ __forceinline__ int ctc_stream_admit(const CtcStreamArgs& a, int b) {
 
 // After the last frame of a call, beam in s: the outputs, then the compaction.  All kCtcThreads
 // threads call it.  Every walk is bounded by the node count: a corrupt state ends in a wrong answer.
+// pos: the beam position the outputs report (the bias families' finalisation; it enters nothing else).
+struct CtcBiasHome {               // where the bias part of the beam goes home
+  const CtcBiasShared* bs;
+  int* bstate;
+  float* bsum;
+};
+
 __device__ __forceinline__ void ctc_stream_close(CtcShared& s, CtcCompact& k, const CtcStreamArgs& a, int b,
-                                                 const CtcNgramShared* ng = nullptr, int* ctx = nullptr) {
+                                                 const CtcNgramShared* ng = nullptr, int* ctx = nullptr,
+                                                 CtcBiasHome bh = CtcBiasHome{nullptr, nullptr, nullptr},
+                                                 int pos = 0) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int M = a.c.max_nodes, nb = s.nb, nn = s.nnodes, BS = a.c.beam;
   CtcNode* nodes = a.c.nodes + (long)b * M;
@@ -364,7 +452,7 @@ __device__ __forceinline__ void ctc_stream_close(CtcShared& s, CtcCompact& k, co
   const int root_depth = a.depth[b];
   // ---- the best prefix: positions from the committed depth up (below it earlier calls wrote them)
   ctc_finish(s, nodes, a.c.tokens + (long)b * a.max_tokens, a.c.out_len + b, a.c.score + b,
-             a.lm_score ? a.lm_score + b : nullptr, a.max_tokens, nn);
+             a.lm_score ? a.lm_score + b : nullptr, a.max_tokens, nn, pos);
   for (int id = tid; id < nn; id += kCtcThreads) map[id] = -1;
   // ---- the lowest common ancestor: a lane per live node, levelled to the shallowest, then up together
   if (wave == 0) {
@@ -447,9 +535,13 @@ __device__ __forceinline__ void ctc_stream_close(CtcShared& s, CtcCompact& k, co
     a.st.last[r] = s.last[tid];
     a.st.len[r] = s.len[tid];
     if (ng) ctx[r] = ng->state[tid];                       // (a context id belongs to a beam position, not to a node)
+    if (bh.bs) {
+      bh.bstate[r] = bh.bs->state[tid];
+      bh.bsum[r] = bh.bs->sum[tid];
+    }
   }
   if (tid == 0) {
-    const int ovf = a.ovf[b] | (s.len[0] > a.max_tokens ? 1 : 0);
+    const int ovf = a.ovf[b] | (s.len[0] > a.max_tokens || s.len[pos] > a.max_tokens ? 1 : 0);
     a.st.nb[b] = nb;
     a.st.nnodes[b] = kept;
     a.depth[b] = k.depth;
@@ -461,11 +553,12 @@ __device__ __forceinline__ void ctc_stream_close(CtcShared& s, CtcCompact& k, co
 
 // grid B: rows[b] != 0 (NULL: every row) becomes the empty prefix; with an LM its state is zeroed and
 // the first LM step is asked for on row 0 of exactly those utterances; with an n-gram (ctx) the one live
-// prefix starts in start_ctx
+// prefix starts in start_ctx; with a graph (bstate) in its root with nothing lent
 __global__ __launch_bounds__(kCtcThreads) void ctc_stream_reset_kernel(CtcStreamArgs a, const int* rows,
                                                                        int lm_start_token, int layers, int H,
                                                                        float* h, float* c, float* q, int* ctx,
-                                                                       int start_ctx) {
+                                                                       int start_ctx, int* bstate = nullptr,
+                                                                       float* bsum = nullptr) {
   const int b = blockIdx.x, tid = threadIdx.x, BS = a.c.beam, r = b * BS + tid;
   const long R = (long)gridDim.x * BS;
   const bool on = !rows || rows[b] != 0;
@@ -483,6 +576,10 @@ __global__ __launch_bounds__(kCtcThreads) void ctc_stream_reset_kernel(CtcStream
     a.st.last[r] = -1;
     a.st.len[r] = 0;
     if (ctx) ctx[r] = start_ctx;
+    if (bstate) {
+      bstate[r] = 0;
+      bsum[r] = 0.f;
+    }
   }
   if (tid == 0) {
     a.st.nb[b] = 1;
@@ -548,6 +645,80 @@ __global__ __launch_bounds__(kCtcThreads) void ctc_prefix_ngram_chunk_kernel(Ctc
     ctc_frame<kCtcNgram>(s, row, x + (long)t * a.s.c.V, a.s.c.V, K, BS, a.s.c.blank, nodes, a.s.c.max_nodes,
                          a.lm_weight, nullptr, nullptr, nullptr, nullptr, 0, &ng);
   ctc_stream_close(s, k, a.s, b, &ng, a.ctx);
+}
+
+// the bias families: the two launches above with the frame body's bias switch on; the graph states and sums
+// are loaded with the beam (clamped, like the context ids) and go home with it.  pos is thread 0's: it
+// alone writes outputs.
+struct CtcBiasStreamArgs {
+  CtcNgramStreamArgs n;            // (g, lm_weight, ctx: the n-gram family only)
+  NgramTables graph;
+  const float* ctx_final;
+  float bias_weight;
+  int* bstate;                     // [B][beam]
+  float* bsum;                     // [B][beam]
+  float* bias_score;               // [B]
+};
+
+__device__ __forceinline__ void ctc_bias_load(CtcBiasShared& bs, const CtcBiasStreamArgs& a, int b, int BS) {
+  const int tid = threadIdx.x;
+  if (tid < BS) {
+    bs.state[tid] = ngram_clamp(a.bstate[b * BS + tid], a.graph.num_ctx);
+    bs.sum[tid] = a.bsum[b * BS + tid];
+  }
+  if (tid == 0) {
+    bs.g = a.graph;
+    bs.final = a.ctx_final;
+  }
+}
+
+__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_bias_chunk_kernel(CtcBiasStreamArgs a) {
+  extern __shared__ float row[];
+  __shared__ CtcShared s;
+  __shared__ CtcBiasShared bs;
+  __shared__ CtcCompact k;
+  const CtcStreamArgs& sa = a.n.s;
+  const int b = blockIdx.x, BS = sa.c.beam;
+  const int n = ctc_stream_admit(sa, b);
+  if (n == 0) return;
+  CtcNode* nodes = sa.c.nodes + (long)b * sa.c.max_nodes;
+  const float* x = sa.c.logits + (long)b * sa.c.T * sa.c.V;
+  load_beam(s, sa.st, b, BS);
+  ctc_bias_load(bs, a, b, BS);
+  __syncthreads();
+  const int K = min(sa.c.topk, sa.c.V);
+  for (int t = 0; t < n; ++t)
+    ctc_frame<kCtcPlain, true>(s, row, x + (long)t * sa.c.V, sa.c.V, K, BS, sa.c.blank, nodes, sa.c.max_nodes, 0.f,
+                               nullptr, nullptr, nullptr, nullptr, 0, nullptr, &bs, a.bias_weight);
+  int pos = 0;
+  if (threadIdx.x == 0) pos = ctc_bias_pick<false>(s, bs, 0.f, a.bias_weight, a.bias_score + b);
+  ctc_stream_close(s, k, sa, b, nullptr, nullptr, CtcBiasHome{&bs, a.bstate, a.bsum}, pos);
+}
+
+__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_ngram_bias_chunk_kernel(CtcBiasStreamArgs a) {
+  extern __shared__ float row[];
+  __shared__ CtcShared s;
+  __shared__ CtcNgramShared ng;
+  __shared__ CtcBiasShared bs;
+  __shared__ CtcCompact k;
+  const CtcStreamArgs& sa = a.n.s;
+  const int b = blockIdx.x, tid = threadIdx.x, BS = sa.c.beam;
+  const int n = ctc_stream_admit(sa, b);
+  if (n == 0) return;
+  CtcNode* nodes = sa.c.nodes + (long)b * sa.c.max_nodes;
+  const float* x = sa.c.logits + (long)b * sa.c.T * sa.c.V;
+  load_beam(s, sa.st, b, BS);
+  if (tid < BS) ng.state[tid] = ngram_clamp(a.n.ctx[b * BS + tid], a.n.g.num_ctx);
+  if (tid == 0) ng.g = a.n.g;
+  ctc_bias_load(bs, a, b, BS);
+  __syncthreads();
+  const int K = min(sa.c.topk, sa.c.V);
+  for (int t = 0; t < n; ++t)
+    ctc_frame<kCtcNgram, true>(s, row, x + (long)t * sa.c.V, sa.c.V, K, BS, sa.c.blank, nodes, sa.c.max_nodes,
+                               a.n.lm_weight, nullptr, nullptr, nullptr, nullptr, 0, &ng, &bs, a.bias_weight);
+  int pos = 0;
+  if (tid == 0) pos = ctc_bias_pick<true>(s, bs, a.n.lm_weight, a.bias_weight, a.bias_score + b);
+  ctc_stream_close(s, k, sa, b, &ng, a.n.ctx, CtcBiasHome{&bs, a.bstate, a.bsum}, pos);
 }
 
 // the LM family: what the rounds read as lengths, before them ...
@@ -632,6 +803,43 @@ int s2t_ctc_prefix_beam_ngram(const S2tNgramLmDesc* lm, const float* logits, con
                   static_cast<CtcNode*>(workspace), tokens, out_len, score},
                  ngram_tables(*lm), lm_weight, start_ctx, lm_score};
   hipLaunchKernelGGL(ctc_prefix_ngram_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, (hipStream_t)stream, a);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_ctc_prefix_beam_bias(const S2tContextGraphDesc* graph, const float* logits, const long* lengths, int B,
+                             int T, int V, int blank, int beam_size, int cutoff_top_k, float bias_weight,
+                             void* workspace, long* tokens, long* out_len, float* score, float* bias_score,
+                             void* stream) {
+  if (B <= 0) return 0;
+  if (T <= 0 || !ctc_ok(T, V, blank, beam_size, cutoff_top_k) || !context_desc_ok(graph) || graph->V != V ||
+      !__builtin_isfinite(bias_weight) || !bias_score || !workspace)
+    return -1;
+  CtcBiasArgs a{{{logits, lengths, T, V, blank, beam_size, cutoff_top_k, max_nodes_of(T, beam_size),
+                  static_cast<CtcNode*>(workspace), tokens, out_len, score},
+                 NgramTables{}, 0.f, 0, nullptr},
+                context_tables(*graph), graph->ctx_final, bias_weight, bias_score};
+  hipLaunchKernelGGL(ctc_prefix_bias_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, (hipStream_t)stream, a);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_ctc_prefix_beam_ngram_bias(const S2tNgramLmDesc* lm, const S2tContextGraphDesc* graph, const float* logits,
+                                   const long* lengths, int B, int T, int V, int blank, int beam_size,
+                                   int cutoff_top_k, float lm_weight, int start_ctx, float bias_weight,
+                                   void* workspace, long* tokens, long* out_len, float* score, float* lm_score,
+                                   float* bias_score, void* stream) {
+  if (B <= 0) return 0;
+  if (T <= 0 || !ctc_ok(T, V, blank, beam_size, cutoff_top_k) || !ngram_desc_ok(lm) || lm->V != V || start_ctx < 0 ||
+      start_ctx >= lm->num_ctx || !__builtin_isfinite(lm_weight) || !context_desc_ok(graph) || graph->V != V ||
+      !__builtin_isfinite(bias_weight) || !lm_score || !bias_score || !workspace)
+    return -1;
+  CtcBiasArgs a{{{logits, lengths, T, V, blank, beam_size, cutoff_top_k, max_nodes_of(T, beam_size),
+                  static_cast<CtcNode*>(workspace), tokens, out_len, score},
+                 ngram_tables(*lm), lm_weight, start_ctx, lm_score},
+                context_tables(*graph), graph->ctx_final, bias_weight, bias_score};
+  hipLaunchKernelGGL(ctc_prefix_ngram_bias_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V,
+                     (hipStream_t)stream, a);
   S2T_CHECK_LAUNCH();
   return 0;
 }
@@ -750,6 +958,86 @@ int s2t_ctc_prefix_beam_ngram_chunk(const S2tNgramLmDesc* lm, const float* logit
                                          max_nodes, tokens, out_len, score, lm_score, stable_len, overflow),
                              ngram_tables(*lm), lm_weight, s.ctx};
   hipLaunchKernelGGL(ctc_prefix_ngram_chunk_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V,
+                     (hipStream_t)stream, a);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+long s2t_ctc_bias_stream_state_bytes(int B, int V, int beam_size, int max_nodes) {
+  if (B <= 0 || !ctc_stream_ok(V, beam_size, max_nodes)) return 0;
+  return (long)carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, nullptr, false, true).bytes;
+}
+
+long s2t_ctc_ngram_bias_stream_state_bytes(int B, int V, int beam_size, int max_nodes) {
+  if (B <= 0 || !ctc_stream_ok(V, beam_size, max_nodes)) return 0;
+  return (long)carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, nullptr, true, true).bytes;
+}
+
+int s2t_ctc_bias_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
+                              void* stream) {
+  if (B <= 0) return 0;
+  if (!ctc_stream_ok(V, beam_size, max_nodes) || !state) return -1;
+  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, false, true);
+  const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
+                                      nullptr, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows, -1, 0, 0,
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (int*)nullptr, 0, s.bstate, s.bsum);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_ctc_ngram_bias_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
+                                    int start_ctx, void* stream) {
+  if (B <= 0) return 0;
+  if (!ctc_stream_ok(V, beam_size, max_nodes) || start_ctx < 0 || !state) return -1;
+  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, true, true);
+  const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
+                                      nullptr, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows, -1, 0, 0,
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, s.ctx, start_ctx, s.bstate, s.bsum);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_ctc_prefix_beam_bias_chunk(const S2tContextGraphDesc* graph, const float* logits, const long* chunk_len,
+                                   int B, int Tc, int V, int blank, int beam_size, int cutoff_top_k,
+                                   float bias_weight, int max_tokens, int max_nodes, void* state, long* tokens,
+                                   long* out_len, float* score, float* bias_score, long* stable_len, int* overflow,
+                                   void* stream) {
+  if (B <= 0) return 0;
+  if (Tc < 1 || Tc > 256 || !ctc_ok(Tc, V, blank, beam_size, cutoff_top_k) || max_tokens < 1 ||
+      !ctc_stream_ok(V, beam_size, max_nodes) || !context_desc_ok(graph) || graph->V != V ||
+      !__builtin_isfinite(bias_weight) || !bias_score || !state)
+    return -1;
+  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, false, true);
+  const CtcBiasStreamArgs a{{stream_args(s, logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_tokens,
+                                         max_nodes, tokens, out_len, score, nullptr, stable_len, overflow),
+                             NgramTables{}, 0.f, nullptr},
+                            context_tables(*graph), graph->ctx_final, bias_weight, s.bstate, s.bsum, bias_score};
+  hipLaunchKernelGGL(ctc_prefix_bias_chunk_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V,
+                     (hipStream_t)stream, a);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+int s2t_ctc_prefix_beam_ngram_bias_chunk(const S2tNgramLmDesc* lm, const S2tContextGraphDesc* graph,
+                                         const float* logits, const long* chunk_len, int B, int Tc, int V, int blank,
+                                         int beam_size, int cutoff_top_k, float lm_weight, float bias_weight,
+                                         int max_tokens, int max_nodes, void* state, long* tokens, long* out_len,
+                                         float* score, float* lm_score, float* bias_score, long* stable_len,
+                                         int* overflow, void* stream) {
+  if (B <= 0) return 0;
+  if (Tc < 1 || Tc > 256 || !ctc_ok(Tc, V, blank, beam_size, cutoff_top_k) || max_tokens < 1 ||
+      !ctc_stream_ok(V, beam_size, max_nodes) || !ngram_desc_ok(lm) || lm->V != V ||
+      !__builtin_isfinite(lm_weight) || !lm_score || !context_desc_ok(graph) || graph->V != V ||
+      !__builtin_isfinite(bias_weight) || !bias_score || !state)
+    return -1;
+  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, true, true);
+  const CtcBiasStreamArgs a{{stream_args(s, logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_tokens,
+                                         max_nodes, tokens, out_len, score, lm_score, stable_len, overflow),
+                             ngram_tables(*lm), lm_weight, s.ctx},
+                            context_tables(*graph), graph->ctx_final, bias_weight, s.bstate, s.bsum, bias_score};
+  hipLaunchKernelGGL(ctc_prefix_ngram_bias_chunk_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V,
                      (hipStream_t)stream, a);
   S2T_CHECK_LAUNCH();
   return 0;

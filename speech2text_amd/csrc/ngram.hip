@@ -2,6 +2,7 @@
 // include/s2t_mi355.h) for R independent rows in one launch, for gfx950.  It is the device side of
 // NgramLm.score_step and what lets the look-up be held to the host's fp32 evaluation on its own; the
 // CTC prefix beam search runs the same device function inside its frame body (csrc/decode_ctc.h).
+// s2t_context_score is the same kernel on a hotword graph's tables (THE BIAS STATEMENT of the header).
 #include <hip/hip_runtime.h>
 
 #include "../../include/s2t_mi355.h"
@@ -34,6 +35,17 @@ int s2t_ngram_score(const S2tNgramLmDesc* lm, int R, const int* ctx, const int* 
   if (!ngram_desc_ok(lm) || !ctx || !token || !logp || !next) return -1;
   hipLaunchKernelGGL(ngram_score_kernel, dim3((R + kNgramThreads - 1) / kNgramThreads), dim3(kNgramThreads), 0,
                      (hipStream_t)stream, ngram_tables(*lm), R, ctx, token, logp, next);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+// THE BIAS STATEMENT of a hotword graph: the same kernel handed the graph's tables
+int s2t_context_score(const S2tContextGraphDesc* graph, int R, const int* state, const int* token, float* score,
+                      int* next, void* stream) {
+  if (R <= 0) return 0;
+  if (!context_desc_ok(graph) || !state || !token || !score || !next) return -1;
+  hipLaunchKernelGGL(ngram_score_kernel, dim3((R + kNgramThreads - 1) / kNgramThreads), dim3(kNgramThreads), 0,
+                     (hipStream_t)stream, context_tables(*graph), R, state, token, score, next);
   S2T_CHECK_LAUNCH();
   return 0;
 }

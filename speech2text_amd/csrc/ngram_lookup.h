@@ -63,4 +63,19 @@ inline NgramTables ngram_tables(const S2tNgramLmDesc& d) {
                      d.arc_logp, d.arc_next};
 }
 
+// A hotword graph (S2tContextGraphDesc, THE BIAS STATEMENT) is the same kind of table: ngram_score reads
+// its hop bound from the tables it is handed, so the graph rides the same device function with order =
+// max_depth + 1 (a state of depth d fails at most d times) and arc_logp = arc_score.  Its limits have a
+// host check of their own.
+inline bool context_desc_ok(const S2tContextGraphDesc* d) {
+  return d && d->V >= 1 && d->V <= S2T_RNNT_LSTM_MAX_VOCAB && d->max_depth >= 0 &&
+         d->max_depth <= S2T_CONTEXT_MAX_DEPTH && d->num_ctx >= 1 && d->num_arcs >= d->V && d->ctx_begin &&
+         d->ctx_fail && d->ctx_backoff && d->ctx_final && d->arc_token && d->arc_score && d->arc_next;
+}
+
+inline NgramTables context_tables(const S2tContextGraphDesc& d) {
+  return NgramTables{d.V, d.max_depth + 1, d.num_ctx, d.num_arcs, d.ctx_begin, d.ctx_fail, d.ctx_backoff,
+                     d.arc_token, d.arc_score, d.arc_next};
+}
+
 }  // namespace s2t_dec

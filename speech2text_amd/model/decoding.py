@@ -32,7 +32,10 @@ s2t_ctc_prefix_beam_lm) and, in one launch again, a back-off n-gram over the mod
 (model/lm/ngram_lm.py NgramLm, s2t_ctc_prefix_beam_ngram; chunk-carried: CtcNgramStreamingSearch,
 s2t_ctc_prefix_beam_ngram_chunk, built by ctc_streaming_search); CtcStreamingSearch carries the plain and the
 RNN-LM search across chunks with a trie that does not grow with the stream (s2t_ctc_prefix_beam_chunk,
-s2t_ctc_prefix_beam_lm_chunk).  The lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are
+s2t_ctc_prefix_beam_lm_chunk).  The plain and the n-gram search also take hotwords, a ContextGraph of phrases
+to boost: that surface is model/ctc_bias.py (this module's public names and signatures are pinned), which sets
+the `_context` that CtcPrefixBeamDecoding's host loop and dispatch read.
+The lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are
 not here."""
 import abc
 import copy
@@ -114,11 +117,12 @@ class CtcGreedyDecoding(_BatchDecoding):
         return _to_texts(*ctc_greedy_tokens(hidden_states, inputs_length), self._tokenizer)
 
 
-def _whole_utterance(entry, what, scores, lengths, plan, frames=False, score=True, lm_score=False, per_frame=1):
+def _whole_utterance(entry, what, scores, lengths, plan, frames=False, score=True, lm_score=False, per_frame=1,
+                     bias_score=False):
     """The one calling path of the whole-utterance device searches.  scores (B,T,V) must be on the device
     (RuntimeError: the `what` runs on the GPU only), lengths (B) follow them.  The outputs are zeroed --
     tokens (B, T * per_frame) int64, [frames (B,T) int64,] out_len (B) int64, [score (B) fp32,] [lm_score
-    (B) fp32] -- and are the answer for an empty batch.  Then `plan(scores, lengths)` states the search:
+    (B) fp32,] [bias_score (B) fp32] -- and are the answer for an empty batch.  Then `plan(scores, lengths)` states the search:
     None where it refuses, else (workspace bytes, call, keep).  `call(tail)` makes the C call, `tail` being
     the entry's last arguments: workspace, the outputs in the order above, stream.  `keep` is what the
     call's pointers need alive (descriptors and the tensors behind them); it is held here until the call
@@ -134,7 +138,7 @@ def _whole_utterance(entry, what, scores, lengths, plan, frames=False, score=Tru
     if frames:
         out.append(torch.zeros((B, T), dtype=torch.int64, device=dev))
     out.append(torch.zeros((B,), dtype=torch.int64, device=dev))
-    out += [torch.zeros((B,), dtype=torch.float32, device=dev) for has in (score, lm_score) if has]
+    out += [torch.zeros((B,), dtype=torch.float32, device=dev) for has in (score, lm_score, bias_score) if has]
     out = tuple(out)
     if B == 0 or T == 0:
         return out
@@ -275,7 +279,13 @@ class CtcPrefixBeamDecoding(_BatchDecoding):
     one launch, its tables following the logits to their device); CPU tensors, shapes the kernels
     refuse and foreign LMs run `_module_loop`.
     `beam_tokens` returns (tokens, out_len, score) and with an LM a fourth tensor, the best prefix'
-    unweighted LM sum."""
+    unweighted LM sum.
+
+    The subclass CtcBiasPrefixBeamDecoding (model/ctc_bias.py) gives the search a context (a ContextGraph:
+    hotwords): prefixes then rank with `context_weight` times their bias_sum added and the reported prefix is
+    the best one once every unfinished match has been paid back (the bias statement and the finalisation:
+    model/lm/context_graph.py, include/s2t_mi355.h); `beam_tokens` then returns one more tensor at the end, the
+    reported prefix' bias_score.  The search itself, host loop and dispatch, is this class' either way."""
 
     def __init__(self, tokenizer, beam_size=4, cutoff_top_k=4, lm=None, lm_weight=0.0, lm_start_token=None) -> None:
         self._tokenizer = tokenizer
@@ -288,9 +298,11 @@ class CtcPrefixBeamDecoding(_BatchDecoding):
             raise ValueError(f"beam_size and cutoff_top_k must be at least 1, got {beam_size!r}, {cutoff_top_k!r}")
         if self._lm_start_token is not None and _is_ngram(lm):
             raise ValueError("an NgramLm starts in its own <s> context: lm_start_token must be None")
+        self._context, self._context_weight = None, 0.0    # (hotwords: CtcBiasPrefixBeamDecoding sets them)
 
     def _module_loop(self, hidden_states, blank=0):
-        """(1,T,V) -> (tokens, score, lm_score) of the best prefix: the same search on the host.  The
+        """(1,T,V) -> (tokens, score, lm_score) of the best prefix, with a context (tokens, score, lm_score,
+        bias_score) of the reported one: the same search on the host.  The
         log-softmax, the top-k and the LM run in torch on the inputs' device (in their dtype, fp32 at
         least); the per-prefix recursion runs on Python floats keyed by token tuples."""
         x = hidden_states[0]
@@ -299,6 +311,8 @@ class CtcPrefixBeamDecoding(_BatchDecoding):
         dev = x.device
         k = min(self._cutoff_top_k, V)
         lm, weight = self._lm, self._lm_weight
+        graph, bias_weight = self._context, self._context_weight
+        bias = {(): (0, 0.0)}                              # live prefix -> (graph state, bias_sum)
         info = {}                                          # live prefix -> (q as a list, LM state, lm_sum)
         if lm is not None:
             state, q = lm.init_states(1), [0.0] * V
@@ -339,12 +353,23 @@ class CtcPrefixBeamDecoding(_BatchDecoding):
                 lm_sum = 0.0
                 if lm is not None:
                     lm_sum = info[tokens][2] if tokens in live else info[tokens[:-1]][2] + info[tokens[:-1]][0][tokens[-1]]
-                ranked.append((-(_logaddexp(pb, pnb) + weight * lm_sum), key, tokens, pb, pnb, lm_sum))
+                total = _logaddexp(pb, pnb) + weight * lm_sum
+                bias_of = None
+                if graph is not None:
+                    if tokens in live:
+                        bias_of = bias[tokens]
+                    else:
+                        state, bias_sum = bias[tokens[:-1]]
+                        hit, nxt = graph._row(state)
+                        bias_of = (int(nxt[tokens[-1]]), bias_sum + float(hit[tokens[-1]]))
+                    total = total + bias_weight * bias_of[1]
+                ranked.append((-total, key, tokens, pb, pnb, lm_sum, bias_of))
             ranked.sort(key=lambda e: e[:2])
             ranked = ranked[:self._beam_size]
+            bias = {e[2]: e[6] for e in ranked}
             if lm is not None:
                 new_info = {}
-                for _, _, tokens, _, _, lm_sum in ranked:
+                for _, _, tokens, _, _, lm_sum, _ in ranked:
                     if tokens in live:
                         new_info[tokens] = info[tokens]
                     else:
@@ -353,6 +378,13 @@ class CtcPrefixBeamDecoding(_BatchDecoding):
                         new_info[tokens] = (qt[0].double().tolist(), state, lm_sum)
                 info = new_info
             beam = [(e[2], e[3], e[4]) for e in ranked]
+        if graph is not None:                              # the finalisation: the loan of an unfinished match goes back
+            final = graph.final_scores(torch.tensor([bias[p][0] for p, _, _ in beam])).double().tolist()
+            totals = [(_logaddexp(pb, pnb) + weight * (info[p][2] if lm is not None else 0.0))
+                      + bias_weight * (bias[p][1] + f) for (p, pb, pnb), f in zip(beam, final)]
+            pos = max(range(len(beam)), key=lambda i: (totals[i], -i))
+            p, pb, pnb = beam[pos]
+            return list(p), _logaddexp(pb, pnb), (info[p][2] if lm is not None else 0.0), bias[p][1] + final[pos]
         p, pb, pnb = beam[0]
         return list(p), _logaddexp(pb, pnb), (info[p][2] if lm is not None else 0.0)
 
@@ -360,6 +392,13 @@ class CtcPrefixBeamDecoding(_BatchDecoding):
         from speech2text_amd.model.lm.rnn_lm import RnnLm
         if not hidden_states.is_cuda:
             return None
+        if self._context is not None:
+            if self._context.dtype != torch.float32 or not (self._lm is None or (
+                    _is_ngram(self._lm) and self._lm.dtype == torch.float32)):
+                return None
+            from speech2text_amd.model.ctc_bias import ctc_prefix_beam_bias_tokens
+            return ctc_prefix_beam_bias_tokens(hidden_states, inputs_length, self._context, self._context_weight,
+                                               self._lm, self._lm_weight, self._beam_size, self._cutoff_top_k)
         if self._lm is None:
             return ctc_prefix_beam_tokens(hidden_states, inputs_length, self._beam_size, self._cutoff_top_k)
         if _is_ngram(self._lm):
@@ -379,6 +418,8 @@ class CtcPrefixBeamDecoding(_BatchDecoding):
         on), else the host loop per utterance."""
         dev = hidden_states.device
         _lm_follows(self._lm, dev)
+        if self._context is not None:
+            self._context.to(dev)
         if fused:
             out = self._fused(hidden_states, inputs_length)
             if out is not None:
@@ -388,13 +429,18 @@ class CtcPrefixBeamDecoding(_BatchDecoding):
         out_len = torch.zeros((B,), dtype=torch.int64)
         score = torch.zeros((B,), dtype=torch.float32)
         lm_score = torch.zeros((B,), dtype=torch.float32)
+        bias_score = torch.zeros((B,), dtype=torch.float32)
         for b in range(B):
             n = max(0, min(int(inputs_length[b]), T))
-            tok, score[b], lm_score[b] = self._module_loop(hidden_states[b:b + 1, :n, :])
+            res = self._module_loop(hidden_states[b:b + 1, :n, :])
+            tok, score[b], lm_score[b] = res[:3]
+            if self._context is not None:
+                bias_score[b] = res[3]
             out_len[b] = len(tok)
             tokens[b, :len(tok)] = torch.tensor(tok, dtype=torch.int64)
         out = (tokens.to(dev), out_len.to(dev), score.to(dev))
-        return out + (lm_score.to(dev),) if self._lm is not None else out
+        out = out + (lm_score.to(dev),) if self._lm is not None else out
+        return out + (bias_score.to(dev),) if self._context is not None else out
 
     @torch.no_grad()
     def decode_batch(self, hidden_states, inputs_length):

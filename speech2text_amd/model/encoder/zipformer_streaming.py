@@ -465,14 +465,17 @@ class CtcStreamingRecognizer(StreamingRecognizer):
     score, stable_len, scores), scores (B, chunk//2, V) being what the search read.  method "beam" or
     "greedy" (beam_size = cutoff_top_k = 1); with `lm` (an RnnLm, or an NgramLm, which takes no
     `lm_start_token`; beam only) the chunk call is fused with it (`lm_weight`, `lm_start_token` as
-    CtcPrefixBeamDecoding's; model/decoding.py ctc_streaming_search picks the search) and `search.lm_score`
-    holds the best prefixes' unweighted LM sums.  `max_nodes`: trie nodes per stream (CtcStreamingSearch)."""
+    CtcPrefixBeamDecoding's; model/decoding.py ctc_streaming_search picks the search, through
+    model/ctc_bias.py ctc_bias_streaming_search) and `search.lm_score`
+    holds the best prefixes' unweighted LM sums.  With `context` (a ContextGraph: hotwords; beam only, no LM
+    or an NgramLm) the captured chunk call is CtcBiasStreamingSearch's and `search.bias_score` holds the
+    reported prefixes' bias scores.  `max_nodes`: trie nodes per stream (CtcStreamingSearch)."""
 
     def __init__(self, encoder, tokenizer, head=None, cmvn=None, batch_size: int = 1, method: str = "beam",
                  beam_size: int = 4, cutoff_top_k: int = 4, max_tokens: int = 1024, max_nodes: int = 4096,
                  blank: int = 0, device=None, warmup: int = 2, lm=None, lm_weight: float = 0.0,
-                 lm_start_token=None):
-        from speech2text_amd.model.decoding import ctc_streaming_search
+                 lm_start_token=None, context=None, context_weight: float = 1.0):
+        from speech2text_amd.model.ctc_bias import ctc_bias_streaming_search
         model, device, lm = self._check_model(encoder, (head,), tokenizer, batch_size, device, lm)
         if model._for_ctc == (head is not None):
             raise ValueError("CtcStreamingRecognizer searches CTC scores: build the encoder with for_ctc=True and "
@@ -484,7 +487,8 @@ class CtcStreamingRecognizer(StreamingRecognizer):
             num_classes = head._fc.out_features
             scores = lambda enc: head(enc, self.chunk_len)[0].float().contiguous()          # noqa: E731
         self.head = head
-        self.search = ctc_streaming_search(num_classes, batch_size, method, beam_size, cutoff_top_k, max_tokens,
-                                           max_nodes, blank, device, lm=lm, lm_weight=lm_weight,
-                                           lm_start_token=lm_start_token)
+        self.search = ctc_bias_streaming_search(num_classes, batch_size, method, beam_size, cutoff_top_k, max_tokens,
+                                                max_nodes, blank, device, lm=lm, lm_weight=lm_weight,
+                                                lm_start_token=lm_start_token, context=context,
+                                                context_weight=context_weight)
         self._capture(model, cmvn, device, warmup, scores)

@@ -44,7 +44,7 @@ class AsrMetricConfig:
     "ctc_prefix_beam_search" (also a name of this project: the reference's CTC beam decoder needs a
     lexicon decoder of a library) scores a CTC head with CtcPrefixBeamDecoding(beam_size,
     cutoff_top_k), lexicon-free and with equal prefixes merged; it takes the same `lm`, lm_weight and
-    lm_start_token."""
+    lm_start_token, and AsrMetric's `context` / `context_weight` (hotwords: the `metric.hotwords` key)."""
     decode_method: str = "ctc_greedy_search"
     max_token_step: int = 5
     beam_size: int = 4
@@ -54,8 +54,12 @@ class AsrMetricConfig:
 
 
 class AsrMetric(object):
-    def __init__(self, tokenizer, config: AsrMetricConfig, predictor=None, joiner=None, lm=None):
+    def __init__(self, tokenizer, config: AsrMetricConfig, predictor=None, joiner=None, lm=None, context=None,
+                 context_weight=1.0):
         self._tokenizer = tokenizer
+        if context is not None and config.decode_method != "ctc_prefix_beam_search":
+            raise ValueError("hotwords bias the CTC prefix beam search: metric.decode_method must be "
+                             "ctc_prefix_beam_search")
         self._lm = lm                  # held here, not by the task: no parameter of the task
         if config.decode_method == "ctc_greedy_search":
             self._decode_sess = CtcGreedyDecoding(tokenizer=tokenizer)
@@ -70,10 +74,12 @@ class AsrMetric(object):
                                                  lm_weight=config.lm_weight,
                                                  lm_start_token=config.lm_start_token)
         elif config.decode_method == "ctc_prefix_beam_search":
-            self._decode_sess = CtcPrefixBeamDecoding(tokenizer=tokenizer, beam_size=config.beam_size,
-                                                      cutoff_top_k=config.cutoff_top_k, lm=lm,
-                                                      lm_weight=config.lm_weight,
-                                                      lm_start_token=config.lm_start_token)
+            from speech2text_amd.model.ctc_bias import CtcBiasPrefixBeamDecoding
+            search = CtcPrefixBeamDecoding if context is None else CtcBiasPrefixBeamDecoding
+            bias = {} if context is None else dict(context=context, context_weight=context_weight)
+            self._decode_sess = search(tokenizer=tokenizer, beam_size=config.beam_size,
+                                       cutoff_top_k=config.cutoff_top_k, lm=lm, lm_weight=config.lm_weight,
+                                       lm_start_token=config.lm_start_token, **bias)
         else:
             raise NotImplementedError(config.decode_method)
 

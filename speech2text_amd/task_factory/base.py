@@ -36,6 +36,12 @@ class TaskBase(nn.Module):
             # n-gram over the tokenizer's pieces (CTC prefix beam search); the rest is AsrMetricConfig's
             self._metric_config = dict(self._metric_config)
             self._metric_lm_config = self._metric_config.pop("lm")
+        self._metric_hotwords_config = None
+        if self._metric_config is not None and "hotwords" in self._metric_config:
+            # metric: {hotwords: {phrases: [...] | file: <one phrase a line>, context_score:, context_weight:}}:
+            # the phrases the CTC prefix beam search is biased towards (model/lm/context_graph.py)
+            self._metric_config = dict(self._metric_config)
+            self._metric_hotwords_config = self._metric_config.pop("hotwords")
         self._metric = None
         if "feat_type" in self._dataset_config:
             self._frontend = self._get_frontend(copy.deepcopy(config["dataset"]))
@@ -89,7 +95,28 @@ class TaskBase(nn.Module):
             return None
         from speech2text_amd.model.utils import AsrMetric, AsrMetricConfig
         return AsrMetric(tokenizer=self._tokenizer, config=AsrMetricConfig(**self._metric_config),
-                         predictor=predictor, joiner=joiner, lm=self._metric_lm())
+                         predictor=predictor, joiner=joiner, lm=self._metric_lm(), **self._metric_context())
+
+    def _metric_context(self):
+        """The hotword arguments of `metric.hotwords` -> {} without the key, else {context: the ContextGraph
+        of the phrases (`phrases:` a list, or `file:` with one phrase a line) encoded with the task's
+        tokenizer, context_weight:}.  Like the LM it is handed to the metric object or the recogniser,
+        never held by the task."""
+        cfg = self._metric_hotwords_config
+        if not cfg:
+            return {}
+        if self._tokenizer is None:
+            raise RuntimeError("metric.hotwords needs the YAML's `tokenizer:` section: the phrases are encoded with it")
+        if (cfg.get("phrases") is None) == (cfg.get("file") is None):
+            raise ValueError("metric.hotwords names either `phrases:` (a list) or `file:` (one phrase a line)")
+        phrases = cfg.get("phrases")
+        if phrases is None:
+            with open(cfg["file"], encoding="utf-8") as fh:
+                phrases = [line.strip() for line in fh if line.strip()]
+        from speech2text_amd.model.lm.context_graph import ContextGraph
+        graph = ContextGraph.from_texts(list(phrases), self._tokenizer,
+                                        context_score=float(cfg.get("context_score", 1.0)))
+        return dict(context=graph, context_weight=float(cfg.get("context_weight", 1.0)))
 
     def _metric_lm(self):
         """The frozen RnnLm of `metric.lm`, or None: built from `lm.config`, loaded from the `_nnlm.*`

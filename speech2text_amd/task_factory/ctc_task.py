@@ -67,7 +67,8 @@ class CtcTask(TaskBase):
         beam method the search is shallow-fused with that LM (`metric.lm_weight`,
         `metric.lm_start_token`), as the validation search is; an ARPA `metric.lm` is not taken by default
         (a ValueError): pass lm=<NgramLm>, lm_weight= explicitly for the fused n-gram search
-        (CtcNgramStreamingSearch).  The task must be on the GPU and in eval
+        (CtcNgramStreamingSearch).  With `metric.hotwords` and the beam method the search is biased with
+        those phrases (CtcBiasStreamingSearch; context=, context_weight= override).  The task must be on the GPU and in eval
         mode; its head is the encoder's own projection (for_ctc, Identity decoder) or the Projector."""
         from speech2text_amd.model.decoder.decoder import Identity, Projector
         from speech2text_amd.model.encoder.zipformer_streaming import CtcStreamingRecognizer
@@ -96,5 +97,8 @@ class CtcTask(TaskBase):
                 kw["lm"] = lm
                 kw.setdefault("lm_weight", cfg.lm_weight)
                 kw.setdefault("lm_start_token", cfg.lm_start_token)
+        if method == "beam" and "context" not in kw:       # the hotwords the validation search is biased with
+            for k, v in self._metric_context().items():
+                kw.setdefault(k, v)
         return CtcStreamingRecognizer(self._encoder, self._tokenizer, head=head, cmvn=self._global_cmvn,
                                       batch_size=batch_size, method=method, **kw)
