@@ -1,34 +1,26 @@
-// CTC prefix beam search, lexicon-free, with equal prefixes merged exactly and optional RNN-LM
-// shallow fusion, for gfx950.  (The reference's CTC beam decoder wraps a lexicon decoder of a library;
-// this is the textbook prefix search over the model's own classes.)  The per-frame body, the trie that
-// gives a token sequence one node id for ever and the candidate slots are csrc/decode_ctc.h.
+// CTC prefix beam search, lexicon-free, with equal prefixes merged exactly, for gfx950.  (The reference's
+// CTC beam decoder wraps a lexicon decoder of a library; this is the textbook prefix search over the
+// model's own classes.)  The per-frame body, the trie that gives a token sequence one node id for ever
+// and the candidate slots are csrc/decode_ctc.h.  Around that body this file states each thing once:
 //
-//   s2t_ctc_prefix_beam      ONE launch per batch, one workgroup (4 waves) per utterance walking its
-//                            frames on the device; the beam lives in LDS, the trie in the workspace.
-//   s2t_ctc_prefix_beam_lm   lockstep rounds over the batch, exactly T of them and no host
-//                            synchronisation: per round one search kernel (the same frame body; it
-//                            gathers the q[c] it needs from the live prefixes' LM rows and writes emit /
-//                            parent / token), then s2t_rnn_lm_step on B * beam_size rows through two
-//                            alternating state buffers.  The beam lives in the workspace between
-//                            rounds.  A row past its length passes its state through.
-//   s2t_ctc_prefix_beam_ngram
-//                            the plain entry's one launch with a back-off n-gram LM: the frame body's
-//                            n-gram mode scores an extension by the look-up of csrc/ngram_lookup.h and a
-//                            kept prefix takes the context that look-up returned, so nothing runs
-//                            between frames.  The beam gains one int per prefix, in LDS.
-//   s2t_ctc_prefix_beam_chunk, s2t_ctc_prefix_beam_lm_chunk
-//                            the two above fed their frames in pieces: beam and trie in a caller-owned
-//                            state, the same frame body and round kernel, and at the end of every call
-//                            a compaction of the trie to what the live prefixes can still reach.
-//   s2t_ctc_prefix_beam_bias, s2t_ctc_prefix_beam_ngram_bias, and their _chunk partners
-//                            the plain and n-gram launches with the frame body's bias switch on: a live
-//                            prefix also carries a hotword-graph state and bias_sum (two more arrays behind
-//                            the state's layout), and the outputs report the live prefix that is best
-//                            once every unfinished match has been paid back (the finalisation).
-//   s2t_ctc_prefix_beam_ngram_chunk
-//                            the n-gram form fed its frames in pieces: the plain chunk kernel's shape in
-//                            the frame body's n-gram mode, still ONE launch; the state gains the live
-//                            prefixes' context ids behind the plain layout.
+//   ctc_search_kernel<MODE, BIAS, CHUNK>
+//                  the ONE-launch searches: a workgroup (4 waves) per utterance walks its frames on the
+//                  device, the beam in LDS, the trie in the workspace or the caller's state.  MODE: plain
+//                  or back-off n-gram; BIAS: the hotword graph; CHUNK: the beam is loaded from a
+//                  caller-owned state and goes home through ctc_stream_close (outputs, then the trie's
+//                  compaction) instead of starting empty and ending in ctc_finish.  Eight instantiations
+//                  behind s2t_ctc_prefix_beam[_ngram][_bias][_chunk]; one that has no n-gram, graph or
+//                  state has no LDS, load or store of theirs.  All take one CtcSearchArgs.
+//   ctc_search     the host path of those eight entries: the refusals, the argument struct filled by
+//                  name, the instantiation, the launch.  An entry only describes its call (CtcSearch).
+//   ctc_reset      likewise for the five s2t_ctc_*_stream_reset entries and ctc_stream_reset_kernel.
+//   ctc_lm_rounds  the RNN-LM family (s2t_ctc_prefix_beam_lm, _lm_chunk): lockstep rounds over the batch
+//                  and no host synchronisation; per round ctc_prefix_round_kernel (the same frame body; it
+//                  gathers the q[c] it needs from the live prefixes' LM rows and writes emit / parent /
+//                  token), then s2t_rnn_lm_step on B * beam_size rows from one copy of the LM's state
+//                  into the other, then the flip.  A row past its length passes its state through.
+//   carve_*        every workspace and state layout, handed out by the Arena of decode_records.h, which
+//                  also answers the *_bytes queries.
 #include <hip/hip_runtime.h>
 
 #include "../../include/s2t_mi355.h"
@@ -59,120 +51,6 @@ struct CtcArgs {
   long* out_len;          // [B]
   float* score;           // [B]
 };
-
-__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_kernel(CtcArgs a) {
-  extern __shared__ float row[];
-  __shared__ CtcShared s;
-  const int b = blockIdx.x;
-  const int Tb = (int)clamped_len(a.lengths, b, a.T);
-  CtcNode* nodes = a.nodes + (long)b * a.max_nodes;
-  const float* x = a.logits + (long)b * a.T * a.V;
-  ctc_start(s, nodes);
-  __syncthreads();
-  const int K = min(a.topk, a.V);
-  for (int t = 0; t < Tb; ++t)
-    ctc_frame<kCtcPlain>(s, row, x + (long)t * a.V, a.V, K, a.beam, a.blank, nodes, a.max_nodes, 0.f, nullptr,
-                         nullptr, nullptr, nullptr, 0);
-  ctc_finish(s, nodes, a.tokens + (long)b * a.T, a.out_len + b, a.score + b, nullptr, a.T, a.max_nodes);
-}
-
-// ------------------------------------------------------------------ the n-gram form: one launch
-struct CtcNgramArgs {
-  CtcArgs c;
-  NgramTables g;
-  float lm_weight;
-  int start_ctx;
-  float* lm_score;        // [B]
-};
-
-__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_ngram_kernel(CtcNgramArgs a) {
-  extern __shared__ float row[];
-  __shared__ CtcShared s;
-  __shared__ CtcNgramShared ng;
-  const int b = blockIdx.x;
-  const int Tb = (int)clamped_len(a.c.lengths, b, a.c.T);
-  CtcNode* nodes = a.c.nodes + (long)b * a.c.max_nodes;
-  const float* x = a.c.logits + (long)b * a.c.T * a.c.V;
-  ctc_start(s, nodes);
-  if (threadIdx.x == 0) {
-    ng.g = a.g;
-    ng.state[0] = a.start_ctx;
-  }
-  __syncthreads();
-  const int K = min(a.c.topk, a.c.V);
-  for (int t = 0; t < Tb; ++t)
-    ctc_frame<kCtcNgram>(s, row, x + (long)t * a.c.V, a.c.V, K, a.c.beam, a.c.blank, nodes, a.c.max_nodes,
-                         a.lm_weight, nullptr, nullptr, nullptr, nullptr, 0, &ng);
-  ctc_finish(s, nodes, a.c.tokens + (long)b * a.c.T, a.c.out_len + b, a.c.score + b, a.lm_score + b, a.c.T,
-             a.c.max_nodes);
-}
-
-// ------------------------------------------------------------------ the bias forms: one launch
-struct CtcBiasArgs {
-  CtcNgramArgs n;         // (g, lm_weight, start_ctx, lm_score: the n-gram form only)
-  NgramTables graph;
-  const float* ctx_final;
-  float bias_weight;
-  float* bias_score;      // [B]
-};
-
-// the graph and the empty prefix' bias part: the root, nothing lent
-__device__ __forceinline__ void ctc_bias_start(CtcBiasShared& bs, const NgramTables& graph, const float* ctx_final) {
-  if (threadIdx.x == 0) {
-    bs.g = graph;
-    bs.final = ctx_final;
-    bs.state[0] = 0;
-    bs.sum[0] = 0.f;
-  }
-}
-
-__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_bias_kernel(CtcBiasArgs a) {
-  extern __shared__ float row[];
-  __shared__ CtcShared s;
-  __shared__ CtcBiasShared bs;
-  const CtcArgs& c = a.n.c;
-  const int b = blockIdx.x;
-  const int Tb = (int)clamped_len(c.lengths, b, c.T);
-  CtcNode* nodes = c.nodes + (long)b * c.max_nodes;
-  const float* x = c.logits + (long)b * c.T * c.V;
-  ctc_start(s, nodes);
-  ctc_bias_start(bs, a.graph, a.ctx_final);
-  __syncthreads();
-  const int K = min(c.topk, c.V);
-  for (int t = 0; t < Tb; ++t)
-    ctc_frame<kCtcPlain, true>(s, row, x + (long)t * c.V, c.V, K, c.beam, c.blank, nodes, c.max_nodes, 0.f, nullptr,
-                               nullptr, nullptr, nullptr, 0, nullptr, &bs, a.bias_weight);
-  int pos = 0;
-  if (threadIdx.x == 0) pos = ctc_bias_pick<false>(s, bs, 0.f, a.bias_weight, a.bias_score + b);
-  ctc_finish(s, nodes, c.tokens + (long)b * c.T, c.out_len + b, c.score + b, nullptr, c.T, c.max_nodes, pos);
-}
-
-__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_ngram_bias_kernel(CtcBiasArgs a) {
-  extern __shared__ float row[];
-  __shared__ CtcShared s;
-  __shared__ CtcNgramShared ng;
-  __shared__ CtcBiasShared bs;
-  const CtcArgs& c = a.n.c;
-  const int b = blockIdx.x;
-  const int Tb = (int)clamped_len(c.lengths, b, c.T);
-  CtcNode* nodes = c.nodes + (long)b * c.max_nodes;
-  const float* x = c.logits + (long)b * c.T * c.V;
-  ctc_start(s, nodes);
-  if (threadIdx.x == 0) {
-    ng.g = a.n.g;
-    ng.state[0] = a.n.start_ctx;
-  }
-  ctc_bias_start(bs, a.graph, a.ctx_final);
-  __syncthreads();
-  const int K = min(c.topk, c.V);
-  for (int t = 0; t < Tb; ++t)
-    ctc_frame<kCtcNgram, true>(s, row, x + (long)t * c.V, c.V, K, c.beam, c.blank, nodes, c.max_nodes, a.n.lm_weight,
-                               nullptr, nullptr, nullptr, nullptr, 0, &ng, &bs, a.bias_weight);
-  int pos = 0;
-  if (threadIdx.x == 0) pos = ctc_bias_pick<true>(s, bs, a.n.lm_weight, a.bias_weight, a.bias_score + b);
-  ctc_finish(s, nodes, c.tokens + (long)b * c.T, c.out_len + b, c.score + b, a.n.lm_score + b, c.T, c.max_nodes,
-             pos);
-}
 
 // ------------------------------------------------------------------ the lockstep form
 struct CtcState {                  // the beams between rounds, R = B * beam rows
@@ -287,35 +165,30 @@ size_t nodes_bytes(int B, int T, int beam) {
   return align256(sizeof(CtcNode) * (size_t)B * max_nodes_of(T, beam));
 }
 
+struct CtcLmCopies {               // the two copies of the LM's state the rounds alternate between
+  float *h[2], *c[2], *q[2];
+  void* step;                      // s2t_rnn_lm_step's scratch
+};
+
 struct CtcLmWorkspace {
   CtcNode* nodes;
   CtcState st;
-  float *h[2], *c[2], *q[2];
-  void* step;
-  size_t bytes;
+  CtcLmCopies lm;
 };
 
-CtcLmWorkspace carve_ctc_lm(const S2tRnnLmDesc& d, int B, int T, int beam, void* base) {
+CtcLmWorkspace carve_ctc_lm(const S2tRnnLmDesc& d, int B, int T, int beam, Arena& m) {
   const size_t R = (size_t)B * beam, L = d.num_layers;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    char* q = p + off;
-    off += align256(n);
-    return q;
-  };
-  auto f = [&](size_t n) { return reinterpret_cast<float*>(take(4 * n)); };
-  auto i = [&](size_t n) { return reinterpret_cast<int*>(take(4 * n)); };
+  auto f = [&](size_t n) { return m.take<float>(n); };
+  auto i = [&](size_t n) { return m.take<int>(n); };
   CtcLmWorkspace w;
-  w.nodes = reinterpret_cast<CtcNode*>(take(nodes_bytes(B, T, beam)));
+  w.nodes = m.take<CtcNode>((size_t)B * max_nodes_of(T, beam));
   w.st = CtcState{f(R), f(R), f(R), i(R), i(R), i(R), i(B), i(B), i(R), i(R), i(R)};
   for (int s = 0; s < 2; ++s) {
-    w.h[s] = f(L * R * d.H);
-    w.c[s] = f(L * R * d.H);
-    w.q[s] = f(R * d.V);
+    w.lm.h[s] = f(L * R * d.H);
+    w.lm.c[s] = f(L * R * d.H);
+    w.lm.q[s] = f(R * d.V);
   }
-  w.step = take((size_t)s2t_rnn_lm_step_workspace_bytes(&d, (int)R));
-  w.bytes = off;
+  w.lm.step = m.take<char>((size_t)s2t_rnn_lm_step_workspace_bytes(&d, (int)R));
   return w;
 }
 
@@ -338,29 +211,21 @@ struct CtcStream {
   int* ctx;                        // [R] the live prefixes' context ids (n-gram family)
   int* bstate;                     // [R] the live prefixes' graph states and bias sums (bias families)
   float* bsum;
-  size_t bytes;
 };
 
-CtcStream carve_ctc_stream(const S2tRnnLmDesc* lm, int B, int V, int beam, int max_nodes, void* base,
+CtcStream carve_ctc_stream(const S2tRnnLmDesc* lm, int B, int V, int beam, int max_nodes, Arena& m,
                            bool ngram = false, bool bias = false) {
   const size_t R = (size_t)B * beam, M = (size_t)B * max_nodes;
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t n) {
-    char* q = p + off;
-    off += align256(n);
-    return q;
-  };
-  auto f = [&](size_t n) { return reinterpret_cast<float*>(take(4 * n)); };
-  auto i = [&](size_t n) { return reinterpret_cast<int*>(take(4 * n)); };
+  auto f = [&](size_t n) { return m.take<float>(n); };
+  auto i = [&](size_t n) { return m.take<int>(n); };
   CtcStream s{};
-  s.nodes = reinterpret_cast<CtcNode*>(take(sizeof(CtcNode) * M));
-  s.stage = reinterpret_cast<CtcNode*>(take(sizeof(CtcNode) * M));
+  s.nodes = m.take<CtcNode>(M);
+  s.stage = m.take<CtcNode>(M);
   s.map = i(M);
   s.st = CtcState{f(R), f(R), f(R), i(R), i(R), i(R), i(B), i(B), nullptr, nullptr, nullptr};
   s.depth = i(B);
   s.ovf = i(B);
-  s.eff = reinterpret_cast<long*>(take(sizeof(long) * (size_t)B));
+  s.eff = m.take<long>(B);
   if (lm) {
     s.st.emit = i(R);
     s.st.parent = i(R);
@@ -374,32 +239,21 @@ CtcStream carve_ctc_stream(const S2tRnnLmDesc* lm, int B, int V, int beam, int m
     s.bstate = i(R);
     s.bsum = f(R);
   }
-  s.bytes = off;
   return s;
 }
 
 struct CtcLmStreamWorkspace {      // the second copy of the LM's state, the LM step's scratch
   float *h, *c, *q;
   void* step;
-  size_t bytes;
 };
 
-CtcLmStreamWorkspace carve_ctc_lm_stream_ws(const S2tRnnLmDesc& d, int B, int beam, void* base) {
+CtcLmStreamWorkspace carve_ctc_lm_stream_ws(const S2tRnnLmDesc& d, int B, int beam, Arena& m) {
   const size_t R = (size_t)B * beam;
-  char* p = static_cast<char*>(base);
   CtcLmStreamWorkspace w;
-  size_t off = 0;
-  auto f = [&](size_t n) {
-    char* q = p + off;
-    off += align256(4 * n);
-    return reinterpret_cast<float*>(q);
-  };
-  w.h = f((size_t)d.num_layers * R * d.H);
-  w.c = f((size_t)d.num_layers * R * d.H);
-  w.q = f(R * d.V);
-  w.step = p + off;
-  off += align256((size_t)s2t_rnn_lm_step_workspace_bytes(&d, (int)R));
-  w.bytes = off;
+  w.h = m.take<float>((size_t)d.num_layers * R * d.H);
+  w.c = m.take<float>((size_t)d.num_layers * R * d.H);
+  w.q = m.take<float>(R * d.V);
+  w.step = m.take<char>((size_t)s2t_rnn_lm_step_workspace_bytes(&d, (int)R));
   return w;
 }
 
@@ -551,116 +405,88 @@ __device__ __forceinline__ void ctc_stream_close(CtcShared& s, CtcCompact& k, co
   }
 }
 
-// grid B: rows[b] != 0 (NULL: every row) becomes the empty prefix; with an LM its state is zeroed and
-// the first LM step is asked for on row 0 of exactly those utterances; with an n-gram (ctx) the one live
-// prefix starts in start_ctx; with a graph (bstate) in its root with nothing lent
-__global__ __launch_bounds__(kCtcThreads) void ctc_stream_reset_kernel(CtcStreamArgs a, const int* rows,
-                                                                       int lm_start_token, int layers, int H,
-                                                                       float* h, float* c, float* q, int* ctx,
-                                                                       int start_ctx, int* bstate = nullptr,
-                                                                       float* bsum = nullptr) {
-  const int b = blockIdx.x, tid = threadIdx.x, BS = a.c.beam, r = b * BS + tid;
+// grid B: rows[b] != 0 (NULL: every row) becomes the empty prefix; with an LM (s.h) its state is zeroed and
+// the first LM step is asked for on row 0 of exactly those utterances; with an n-gram (s.ctx) the one live
+// prefix starts in start_ctx; with a graph (s.bstate) in its root with nothing lent
+struct CtcResetArgs {
+  CtcStream s;                     // the state's arrays
+  const int* rows;                 // [B] or NULL
+  int V, beam, max_nodes;
+  int lm_start_token, layers, H;   // (-1, 0, 0 without an LM)
+  int start_ctx;
+};
+
+__global__ __launch_bounds__(kCtcThreads) void ctc_stream_reset_kernel(CtcResetArgs a) {
+  const int b = blockIdx.x, tid = threadIdx.x, BS = a.beam, r = b * BS + tid;
   const long R = (long)gridDim.x * BS;
-  const bool on = !rows || rows[b] != 0;
-  if (a.st.emit && tid < BS) {
-    a.st.emit[r] = on && tid == 0;
-    a.st.parent[r] = r;
-    a.st.token[r] = lm_start_token < 0 ? 0 : lm_start_token;
+  const CtcState& st = a.s.st;
+  const bool on = !a.rows || a.rows[b] != 0;
+  if (st.emit && tid < BS) {
+    st.emit[r] = on && tid == 0;
+    st.parent[r] = r;
+    st.token[r] = a.lm_start_token < 0 ? 0 : a.lm_start_token;
   }
   if (!on) return;
   if (tid < BS) {
-    a.st.pb[r] = tid == 0 ? 0.f : S2T_NEG_INF;
-    a.st.pnb[r] = S2T_NEG_INF;
-    a.st.lm_sum[r] = 0.f;
-    a.st.node[r] = 0;
-    a.st.last[r] = -1;
-    a.st.len[r] = 0;
-    if (ctx) ctx[r] = start_ctx;
-    if (bstate) {
-      bstate[r] = 0;
-      bsum[r] = 0.f;
+    st.pb[r] = tid == 0 ? 0.f : S2T_NEG_INF;
+    st.pnb[r] = S2T_NEG_INF;
+    st.lm_sum[r] = 0.f;
+    st.node[r] = 0;
+    st.last[r] = -1;
+    st.len[r] = 0;
+    if (a.s.ctx) a.s.ctx[r] = a.start_ctx;
+    if (a.s.bstate) {
+      a.s.bstate[r] = 0;
+      a.s.bsum[r] = 0.f;
     }
   }
   if (tid == 0) {
-    a.st.nb[b] = 1;
-    a.st.nnodes[b] = 1;
-    a.depth[b] = 0;
-    a.ovf[b] = 0;
-    a.eff[b] = 0;
-    a.c.nodes[(long)b * a.c.max_nodes] = CtcNode{-1, -1, -1, -1};
+    st.nb[b] = 1;
+    st.nnodes[b] = 1;
+    a.s.depth[b] = 0;
+    a.s.ovf[b] = 0;
+    a.s.eff[b] = 0;
+    a.s.nodes[(long)b * a.max_nodes] = CtcNode{-1, -1, -1, -1};
   }
-  if (!h) return;
-  for (int l = 0; l < layers; ++l)
-    for (int x = tid; x < BS * H; x += kCtcThreads) {
-      h[(l * R + (long)b * BS) * H + x] = 0.f;
-      c[(l * R + (long)b * BS) * H + x] = 0.f;
+  if (!a.s.h) return;
+  for (int l = 0; l < a.layers; ++l)
+    for (int x = tid; x < BS * a.H; x += kCtcThreads) {
+      a.s.h[(l * R + (long)b * BS) * a.H + x] = 0.f;
+      a.s.c[(l * R + (long)b * BS) * a.H + x] = 0.f;
     }
-  for (long x = tid; x < (long)BS * a.c.V; x += kCtcThreads) q[(long)b * BS * a.c.V + x] = 0.f;
+  for (long x = tid; x < (long)BS * a.V; x += kCtcThreads) a.s.q[(long)b * BS * a.V + x] = 0.f;
 }
 
-// the plain family: ONE launch, a workgroup per utterance, like ctc_prefix_kernel
-__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_chunk_kernel(CtcStreamArgs a) {
-  extern __shared__ float row[];
-  __shared__ CtcShared s;
-  __shared__ CtcCompact k;
-  const int b = blockIdx.x;
-  const int n = ctc_stream_admit(a, b);
-  if (n == 0) return;
-  CtcNode* nodes = a.c.nodes + (long)b * a.c.max_nodes;
-  const float* x = a.c.logits + (long)b * a.c.T * a.c.V;
-  load_beam(s, a.st, b, a.c.beam);
-  __syncthreads();
-  const int K = min(a.c.topk, a.c.V);
-  for (int t = 0; t < n; ++t)
-    ctc_frame<kCtcPlain>(s, row, x + (long)t * a.c.V, a.c.V, K, a.c.beam, a.c.blank, nodes, a.c.max_nodes, 0.f,
-                         nullptr, nullptr, nullptr, nullptr, 0);
-  ctc_stream_close(s, k, a, b);
-}
-
-// the n-gram family: the same launch in the frame body's n-gram mode; the context ids are loaded with the
-// beam (clamped: the reset that wrote them saw no tables) and go home with it
-struct CtcNgramStreamArgs {
-  CtcStreamArgs s;
+// ------------------------------------------------------------------ the one-launch searches
+// One struct for the eight instantiations; a part is read only by the instantiations that have it.
+struct CtcSearchArgs {
+  CtcStreamArgs s;                 // whole utterance: s.c and s.lm_score alone (c.lengths, c.T: the utterance's)
+  // MODE == kCtcNgram
   NgramTables g;
   float lm_weight;
-  int* ctx;                        // [B][beam]
-};
-
-__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_ngram_chunk_kernel(CtcNgramStreamArgs a) {
-  extern __shared__ float row[];
-  __shared__ CtcShared s;
-  __shared__ CtcNgramShared ng;
-  __shared__ CtcCompact k;
-  const int b = blockIdx.x, tid = threadIdx.x, BS = a.s.c.beam;
-  const int n = ctc_stream_admit(a.s, b);
-  if (n == 0) return;
-  CtcNode* nodes = a.s.c.nodes + (long)b * a.s.c.max_nodes;
-  const float* x = a.s.c.logits + (long)b * a.s.c.T * a.s.c.V;
-  load_beam(s, a.s.st, b, BS);
-  if (tid < BS) ng.state[tid] = ngram_clamp(a.ctx[b * BS + tid], a.g.num_ctx);
-  if (tid == 0) ng.g = a.g;
-  __syncthreads();
-  const int K = min(a.s.c.topk, a.s.c.V);
-  for (int t = 0; t < n; ++t)
-    ctc_frame<kCtcNgram>(s, row, x + (long)t * a.s.c.V, a.s.c.V, K, BS, a.s.c.blank, nodes, a.s.c.max_nodes,
-                         a.lm_weight, nullptr, nullptr, nullptr, nullptr, 0, &ng);
-  ctc_stream_close(s, k, a.s, b, &ng, a.ctx);
-}
-
-// the bias families: the two launches above with the frame body's bias switch on; the graph states and sums
-// are loaded with the beam (clamped, like the context ids) and go home with it.  pos is thread 0's: it
-// alone writes outputs.
-struct CtcBiasStreamArgs {
-  CtcNgramStreamArgs n;            // (g, lm_weight, ctx: the n-gram family only)
+  int start_ctx;                   // whole utterance: the empty prefix' context
+  int* ctx;                        // chunk: [B][beam] the live prefixes' contexts, in the state
+  // BIAS
   NgramTables graph;
   const float* ctx_final;
   float bias_weight;
-  int* bstate;                     // [B][beam]
-  float* bsum;                     // [B][beam]
+  int* bstate;                     // chunk: [B][beam] the live prefixes' graph states and sums, in the state
+  float* bsum;
   float* bias_score;               // [B]
 };
 
-__device__ __forceinline__ void ctc_bias_load(CtcBiasShared& bs, const CtcBiasStreamArgs& a, int b, int BS) {
+// the graph and the empty prefix' bias part: the root, nothing lent
+__device__ __forceinline__ void ctc_bias_start(CtcBiasShared& bs, const NgramTables& graph, const float* ctx_final) {
+  if (threadIdx.x == 0) {
+    bs.g = graph;
+    bs.final = ctx_final;
+    bs.state[0] = 0;
+    bs.sum[0] = 0.f;
+  }
+}
+
+// the graph states and sums are loaded with the beam (clamped: the reset that wrote them saw no tables)
+__device__ __forceinline__ void ctc_bias_load(CtcBiasShared& bs, const CtcSearchArgs& a, int b, int BS) {
   const int tid = threadIdx.x;
   if (tid < BS) {
     bs.state[tid] = ngram_clamp(a.bstate[b * BS + tid], a.graph.num_ctx);
@@ -672,54 +498,77 @@ __device__ __forceinline__ void ctc_bias_load(CtcBiasShared& bs, const CtcBiasSt
   }
 }
 
-__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_bias_chunk_kernel(CtcBiasStreamArgs a) {
+// ONE launch, a workgroup per utterance.  The n-gram part, the bias part and the compaction's are LDS objects
+// of the branches that use them: an instantiation without one reserves nothing for it.  The context ids,
+// graph states and sums of a chunk call are loaded with the beam and go home with it; the bias
+// instantiations report the position their finalisation picks (thread 0's: it alone writes outputs).
+template <int MODE, bool BIAS, bool CHUNK>
+__global__ __launch_bounds__(kCtcThreads) void ctc_search_kernel(CtcSearchArgs a) {
+  constexpr bool NGRAM = MODE == kCtcNgram;
   extern __shared__ float row[];
   __shared__ CtcShared s;
-  __shared__ CtcBiasShared bs;
-  __shared__ CtcCompact k;
-  const CtcStreamArgs& sa = a.n.s;
-  const int b = blockIdx.x, BS = sa.c.beam;
-  const int n = ctc_stream_admit(sa, b);
-  if (n == 0) return;
-  CtcNode* nodes = sa.c.nodes + (long)b * sa.c.max_nodes;
-  const float* x = sa.c.logits + (long)b * sa.c.T * sa.c.V;
-  load_beam(s, sa.st, b, BS);
-  ctc_bias_load(bs, a, b, BS);
+  CtcNgramShared* ng = nullptr;
+  CtcBiasShared* bs = nullptr;
+  if constexpr (NGRAM) {
+    __shared__ CtcNgramShared ngram_part;
+    ng = &ngram_part;
+  }
+  if constexpr (BIAS) {
+    __shared__ CtcBiasShared bias_part;
+    bs = &bias_part;
+  }
+  const CtcArgs& c = a.s.c;
+  const int b = blockIdx.x, tid = threadIdx.x, BS = c.beam;
+  int n;
+  if constexpr (CHUNK) {
+    n = ctc_stream_admit(a.s, b);
+    if (n == 0) return;
+  } else {
+    n = (int)clamped_len(c.lengths, b, c.T);
+  }
+  CtcNode* nodes = c.nodes + (long)b * c.max_nodes;
+  const float* x = c.logits + (long)b * c.T * c.V;
+  if constexpr (CHUNK) load_beam(s, a.s.st, b, BS);
+  else ctc_start(s, nodes);
+  if constexpr (NGRAM && CHUNK) {
+    if (tid < BS) ng->state[tid] = ngram_clamp(a.ctx[b * BS + tid], a.g.num_ctx);
+    if (tid == 0) ng->g = a.g;
+  }
+  if constexpr (NGRAM && !CHUNK) {
+    if (tid == 0) {
+      ng->g = a.g;
+      ng->state[0] = a.start_ctx;
+    }
+  }
+  if constexpr (BIAS && CHUNK) ctc_bias_load(*bs, a, b, BS);
+  if constexpr (BIAS && !CHUNK) ctc_bias_start(*bs, a.graph, a.ctx_final);
   __syncthreads();
-  const int K = min(sa.c.topk, sa.c.V);
+  const float lm_weight = NGRAM ? a.lm_weight : 0.f, bias_weight = BIAS ? a.bias_weight : 0.f;
+  const int K = min(c.topk, c.V);
   for (int t = 0; t < n; ++t)
-    ctc_frame<kCtcPlain, true>(s, row, x + (long)t * sa.c.V, sa.c.V, K, BS, sa.c.blank, nodes, sa.c.max_nodes, 0.f,
-                               nullptr, nullptr, nullptr, nullptr, 0, nullptr, &bs, a.bias_weight);
+    ctc_frame<MODE, BIAS>(s, row, x + (long)t * c.V, c.V, K, BS, c.blank, nodes, c.max_nodes, lm_weight, nullptr,
+                          nullptr, nullptr, nullptr, 0, ng, bs, bias_weight);
   int pos = 0;
-  if (threadIdx.x == 0) pos = ctc_bias_pick<false>(s, bs, 0.f, a.bias_weight, a.bias_score + b);
-  ctc_stream_close(s, k, sa, b, nullptr, nullptr, CtcBiasHome{&bs, a.bstate, a.bsum}, pos);
+  if constexpr (BIAS) {
+    if (tid == 0) pos = ctc_bias_pick<NGRAM>(s, *bs, lm_weight, bias_weight, a.bias_score + b);
+  }
+  if constexpr (CHUNK) {
+    __shared__ CtcCompact k;
+    CtcBiasHome home{nullptr, nullptr, nullptr};
+    if constexpr (BIAS) home = CtcBiasHome{bs, a.bstate, a.bsum};
+    ctc_stream_close(s, k, a.s, b, ng, NGRAM ? a.ctx : nullptr, home, pos);
+  } else {
+    ctc_finish(s, nodes, c.tokens + (long)b * c.T, c.out_len + b, c.score + b, NGRAM ? a.s.lm_score + b : nullptr,
+               c.T, c.max_nodes, pos);
+  }
 }
 
-__global__ __launch_bounds__(kCtcThreads) void ctc_prefix_ngram_bias_chunk_kernel(CtcBiasStreamArgs a) {
-  extern __shared__ float row[];
-  __shared__ CtcShared s;
-  __shared__ CtcNgramShared ng;
-  __shared__ CtcBiasShared bs;
-  __shared__ CtcCompact k;
-  const CtcStreamArgs& sa = a.n.s;
-  const int b = blockIdx.x, tid = threadIdx.x, BS = sa.c.beam;
-  const int n = ctc_stream_admit(sa, b);
-  if (n == 0) return;
-  CtcNode* nodes = sa.c.nodes + (long)b * sa.c.max_nodes;
-  const float* x = sa.c.logits + (long)b * sa.c.T * sa.c.V;
-  load_beam(s, sa.st, b, BS);
-  if (tid < BS) ng.state[tid] = ngram_clamp(a.n.ctx[b * BS + tid], a.n.g.num_ctx);
-  if (tid == 0) ng.g = a.n.g;
-  ctc_bias_load(bs, a, b, BS);
-  __syncthreads();
-  const int K = min(sa.c.topk, sa.c.V);
-  for (int t = 0; t < n; ++t)
-    ctc_frame<kCtcNgram, true>(s, row, x + (long)t * sa.c.V, sa.c.V, K, BS, sa.c.blank, nodes, sa.c.max_nodes,
-                               a.n.lm_weight, nullptr, nullptr, nullptr, nullptr, 0, &ng, &bs, a.bias_weight);
-  int pos = 0;
-  if (tid == 0) pos = ctc_bias_pick<true>(s, bs, a.n.lm_weight, a.bias_weight, a.bias_score + b);
-  ctc_stream_close(s, k, sa, b, &ng, a.n.ctx, CtcBiasHome{&bs, a.bstate, a.bsum}, pos);
-}
+using CtcSearchKernel = void (*)(CtcSearchArgs);
+const CtcSearchKernel kCtcSearchKernels[2][2][2] = {   // [CHUNK][n-gram][BIAS]
+    {{ctc_search_kernel<kCtcPlain, false, false>, ctc_search_kernel<kCtcPlain, true, false>},
+     {ctc_search_kernel<kCtcNgram, false, false>, ctc_search_kernel<kCtcNgram, true, false>}},
+    {{ctc_search_kernel<kCtcPlain, false, true>, ctc_search_kernel<kCtcPlain, true, true>},
+     {ctc_search_kernel<kCtcNgram, false, true>, ctc_search_kernel<kCtcNgram, true, true>}}};
 
 // the LM family: what the rounds read as lengths, before them ...
 __global__ __launch_bounds__(64) void ctc_stream_begin_kernel(CtcStreamArgs a) {
@@ -758,12 +607,198 @@ bool ctc_stream_ok(int V, int beam_size, int max_nodes) {
          max_nodes <= S2T_CTC_STREAM_MAX_NODES;
 }
 
-CtcStreamArgs stream_args(const CtcStream& s, const float* logits, const long* chunk_len, int Tc, int V, int blank,
-                          int beam_size, int cutoff_top_k, int max_tokens, int max_nodes, long* tokens,
-                          long* out_len, float* score, float* lm_score, long* stable_len, int* overflow) {
-  return CtcStreamArgs{{logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_nodes, s.nodes, tokens, out_len,
-                        score},
-                       s.st, s.stage, s.map, s.depth, s.ovf, s.eff, max_tokens, lm_score, stable_len, overflow};
+// the state's arrays a chunk call works on
+void stream_part(CtcStreamArgs& a, const CtcStream& s) {
+  a.c.nodes = s.nodes;
+  a.st = s.st;
+  a.stage = s.stage;
+  a.map = s.map;
+  a.depth = s.depth;
+  a.ovf = s.ovf;
+  a.eff = s.eff;
+}
+
+long stream_state_bytes(const S2tRnnLmDesc* lm, int B, int V, int beam, int max_nodes, bool ngram, bool bias) {
+  if (B <= 0 || !ctc_stream_ok(V, beam, max_nodes)) return 0;
+  return bytes_of([&](Arena& m) { carve_ctc_stream(lm, B, V, beam, max_nodes, m, ngram, bias); });
+}
+
+// ------------------------------------------------------------------ one host path for the one-launch searches
+struct CtcSearch {                 // what an extern "C" search entry asks for
+  const float* logits;
+  const long* lengths;             // chunk: chunk_len
+  int B, T, V, blank, beam, topk;  // chunk: T is Tc
+  void* memory;                    // the workspace; chunk: the state
+  long *tokens, *out_len;
+  float* score;
+  void* stream;
+  bool chunk = false;
+  int max_tokens = 0, max_nodes = 0;
+  long* stable_len = nullptr;
+  int* overflow = nullptr;
+  bool ngram = false;
+  const S2tNgramLmDesc* lm = nullptr;
+  float lm_weight = 0.f;
+  int start_ctx = 0;               // whole utterance only: a stream's is its reset's
+  float* lm_score = nullptr;
+  bool lm_score_may_be_null = false;   // s2t_ctc_prefix_beam_ngram alone has never refused a NULL lm_score
+  bool bias = false;
+  const S2tContextGraphDesc* graph = nullptr;
+  float bias_weight = 0.f;
+  float* bias_score = nullptr;
+};
+
+// the arguments every search entry has, in the order of its prototype
+CtcSearch ctc_call(const float* logits, const long* lengths, int B, int T, int V, int blank, int beam, int topk,
+                   void* memory, long* tokens, long* out_len, float* score, void* stream) {
+  CtcSearch q;
+  q.logits = logits, q.lengths = lengths;
+  q.B = B, q.T = T, q.V = V, q.blank = blank, q.beam = beam, q.topk = topk;
+  q.memory = memory, q.tokens = tokens, q.out_len = out_len, q.score = score, q.stream = stream;
+  return q;
+}
+
+void chunk_part(CtcSearch& q, int max_tokens, int max_nodes, long* stable_len, int* overflow) {
+  q.chunk = true;
+  q.max_tokens = max_tokens, q.max_nodes = max_nodes, q.stable_len = stable_len, q.overflow = overflow;
+}
+
+void ngram_part(CtcSearch& q, const S2tNgramLmDesc* lm, float lm_weight, float* lm_score) {
+  q.ngram = true;
+  q.lm = lm, q.lm_weight = lm_weight, q.lm_score = lm_score;
+}
+
+void bias_part(CtcSearch& q, const S2tContextGraphDesc* graph, float bias_weight, float* bias_score) {
+  q.bias = true;
+  q.graph = graph, q.bias_weight = bias_weight, q.bias_score = bias_score;
+}
+
+int ctc_search(const CtcSearch& q) {
+  if (q.B <= 0) return 0;
+  bool ok = q.T >= 1 && ctc_ok(q.T, q.V, q.blank, q.beam, q.topk) && q.memory;
+  if (q.chunk) ok = ok && q.T <= 256 && q.max_tokens >= 1 && ctc_stream_ok(q.V, q.beam, q.max_nodes);
+  if (q.ngram) {
+    ok = ok && ngram_desc_ok(q.lm) && q.lm->V == q.V && __builtin_isfinite(q.lm_weight) &&
+         (q.lm_score || q.lm_score_may_be_null);
+    if (!q.chunk) ok = ok && q.start_ctx >= 0 && q.start_ctx < q.lm->num_ctx;
+  }
+  if (q.bias)
+    ok = ok && context_desc_ok(q.graph) && q.graph->V == q.V && __builtin_isfinite(q.bias_weight) && q.bias_score;
+  if (!ok) return -1;
+  CtcSearchArgs a{};
+  CtcArgs& c = a.s.c;
+  c.logits = q.logits;
+  c.lengths = q.lengths;
+  c.T = q.T;
+  c.V = q.V;
+  c.blank = q.blank;
+  c.beam = q.beam;
+  c.topk = q.topk;
+  c.tokens = q.tokens;
+  c.out_len = q.out_len;
+  c.score = q.score;
+  a.s.lm_score = q.lm_score;
+  if (q.chunk) {
+    Arena m(q.memory);
+    const CtcStream s = carve_ctc_stream(nullptr, q.B, q.V, q.beam, q.max_nodes, m, q.ngram, q.bias);
+    stream_part(a.s, s);
+    c.max_nodes = q.max_nodes;
+    a.s.max_tokens = q.max_tokens;
+    a.s.stable_len = q.stable_len;
+    a.s.overflow = q.overflow;
+    a.ctx = s.ctx;
+    a.bstate = s.bstate;
+    a.bsum = s.bsum;
+  } else {
+    c.nodes = static_cast<CtcNode*>(q.memory);
+    c.max_nodes = max_nodes_of(q.T, q.beam);
+  }
+  if (q.ngram) {
+    a.g = ngram_tables(*q.lm);
+    a.lm_weight = q.lm_weight;
+    a.start_ctx = q.start_ctx;
+  }
+  if (q.bias) {
+    a.graph = context_tables(*q.graph);
+    a.ctx_final = q.graph->ctx_final;
+    a.bias_weight = q.bias_weight;
+    a.bias_score = q.bias_score;
+  }
+  hipLaunchKernelGGL(kCtcSearchKernels[q.chunk][q.ngram][q.bias], dim3(q.B), dim3(kCtcThreads), sizeof(float) * q.V,
+                     (hipStream_t)q.stream, a);
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------ one host path for the resets
+struct CtcReset {                  // what an extern "C" reset entry asks for
+  void* state;
+  const int* rows;
+  int B, V, beam, max_nodes;
+  void* stream;
+  bool ngram = false, bias = false, rnn = false;
+  int start_ctx = 0;
+  const S2tRnnLmDesc* lm = nullptr;   // rnn: the LM, its start token, the chunk entry's workspace
+  int lm_start_token = -1;
+  void* workspace = nullptr;
+};
+
+CtcReset reset_call(void* state, const int* rows, int B, int V, int beam, int max_nodes, void* stream) {
+  CtcReset q;
+  q.state = state, q.rows = rows, q.B = B, q.V = V, q.beam = beam, q.max_nodes = max_nodes, q.stream = stream;
+  return q;
+}
+
+int ctc_reset(const CtcReset& q) {
+  if (q.B <= 0) return 0;
+  bool ok = ctc_stream_ok(q.V, q.beam, q.max_nodes) && q.state && q.start_ctx >= 0;
+  if (q.rnn) ok = ok && lm_desc_ok(q.lm, q.V) && q.lm_start_token < q.V && q.workspace;
+  if (!ok) return -1;
+  Arena m(q.state);
+  CtcResetArgs a{};
+  a.s = carve_ctc_stream(q.lm, q.B, q.V, q.beam, q.max_nodes, m, q.ngram, q.bias);
+  a.rows = q.rows;
+  a.V = q.V;
+  a.beam = q.beam;
+  a.max_nodes = q.max_nodes;
+  a.lm_start_token = q.lm_start_token;
+  a.layers = q.rnn ? q.lm->num_layers : 0;
+  a.H = q.rnn ? q.lm->H : 0;
+  a.start_ctx = q.start_ctx;
+  hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(q.B), dim3(kCtcThreads), 0, (hipStream_t)q.stream, a);
+  if (q.rnn && q.lm_start_token >= 0) {                    // the one-shot entry's own first step, masked by rows
+    Arena wm(q.workspace);
+    const CtcLmStreamWorkspace w = carve_ctc_lm_stream_ws(*q.lm, q.B, q.beam, wm);
+    const int rc = s2t_rnn_lm_step(q.lm, q.B * q.beam, a.s.st.token, a.s.st.emit, nullptr, a.s.h, a.s.c, a.s.q, a.s.h,
+                                   a.s.c, a.s.q, w.step, q.stream);
+    if (rc != 0) return rc;
+  }
+  S2T_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------ the LM family's rounds
+// Frames 0 .. T - 1 in lockstep over the batch: the round kernel reads the q rows of the live copy, then
+// s2t_rnn_lm_step takes the state from it into the other copy, then the two flip.  step_after_last: the
+// step also follows the last frame (a chunk call: the next chunk's frame 0 reads it; a whole utterance:
+// nothing does).  *live: the copy the state is in afterwards.
+int ctc_lm_rounds(const S2tRnnLmDesc* lm, CtcLmArgs& a, int B, int T, const CtcLmCopies& w, bool step_after_last,
+                  void* stream, int* live) {
+  const int R = B * a.c.beam;
+  int cur = 0;
+  for (int t = 0; t < T; ++t) {
+    a.t = t;
+    a.q = w.q[cur];
+    hipLaunchKernelGGL(ctc_prefix_round_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * a.c.V,
+                       (hipStream_t)stream, a);
+    if (t + 1 == T && !step_after_last) break;
+    const int rc = s2t_rnn_lm_step(lm, R, a.st.token, a.st.emit, a.st.parent, w.h[cur], w.c[cur], w.q[cur],
+                                   w.h[cur ^ 1], w.c[cur ^ 1], w.q[cur ^ 1], w.step, stream);
+    if (rc != 0) return rc;
+    cur ^= 1;
+  }
+  *live = cur;
+  return 0;
 }
 
 }  // namespace
@@ -775,53 +810,37 @@ long s2t_ctc_prefix_beam_workspace_bytes(int B, int T, int V, int beam_size) {
   return (long)nodes_bytes(B, T, beam_size);
 }
 
+long s2t_ctc_prefix_beam_ngram_workspace_bytes(int B, int T, int V, int beam_size) {
+  return s2t_ctc_prefix_beam_workspace_bytes(B, T, V, beam_size);
+}
+
 int s2t_ctc_prefix_beam(const float* logits, const long* lengths, int B, int T, int V, int blank,
                         int beam_size, int cutoff_top_k, void* workspace, long* tokens, long* out_len,
                         float* score, void* stream) {
-  if (B <= 0) return 0;
-  if (T <= 0 || !ctc_ok(T, V, blank, beam_size, cutoff_top_k) || !workspace) return -1;
-  CtcArgs a{logits, lengths, T, V, blank, beam_size, cutoff_top_k, max_nodes_of(T, beam_size),
-            static_cast<CtcNode*>(workspace), tokens, out_len, score};
-  hipLaunchKernelGGL(ctc_prefix_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, (hipStream_t)stream, a);
-  S2T_CHECK_LAUNCH();
-  return 0;
-}
-
-long s2t_ctc_prefix_beam_ngram_workspace_bytes(int B, int T, int V, int beam_size) {
-  return s2t_ctc_prefix_beam_workspace_bytes(B, T, V, beam_size);
+  return ctc_search(ctc_call(logits, lengths, B, T, V, blank, beam_size, cutoff_top_k, workspace, tokens, out_len,
+                             score, stream));
 }
 
 int s2t_ctc_prefix_beam_ngram(const S2tNgramLmDesc* lm, const float* logits, const long* lengths, int B, int T,
                               int V, int blank, int beam_size, int cutoff_top_k, float lm_weight, int start_ctx,
                               void* workspace, long* tokens, long* out_len, float* score, float* lm_score,
                               void* stream) {
-  if (B <= 0) return 0;
-  if (T <= 0 || !ctc_ok(T, V, blank, beam_size, cutoff_top_k) || !ngram_desc_ok(lm) || lm->V != V || start_ctx < 0 ||
-      start_ctx >= lm->num_ctx || !__builtin_isfinite(lm_weight) || !workspace)
-    return -1;
-  CtcNgramArgs a{{logits, lengths, T, V, blank, beam_size, cutoff_top_k, max_nodes_of(T, beam_size),
-                  static_cast<CtcNode*>(workspace), tokens, out_len, score},
-                 ngram_tables(*lm), lm_weight, start_ctx, lm_score};
-  hipLaunchKernelGGL(ctc_prefix_ngram_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, (hipStream_t)stream, a);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  CtcSearch q = ctc_call(logits, lengths, B, T, V, blank, beam_size, cutoff_top_k, workspace, tokens, out_len, score,
+                         stream);
+  ngram_part(q, lm, lm_weight, lm_score);
+  q.start_ctx = start_ctx;
+  q.lm_score_may_be_null = true;
+  return ctc_search(q);
 }
 
 int s2t_ctc_prefix_beam_bias(const S2tContextGraphDesc* graph, const float* logits, const long* lengths, int B,
                              int T, int V, int blank, int beam_size, int cutoff_top_k, float bias_weight,
                              void* workspace, long* tokens, long* out_len, float* score, float* bias_score,
                              void* stream) {
-  if (B <= 0) return 0;
-  if (T <= 0 || !ctc_ok(T, V, blank, beam_size, cutoff_top_k) || !context_desc_ok(graph) || graph->V != V ||
-      !__builtin_isfinite(bias_weight) || !bias_score || !workspace)
-    return -1;
-  CtcBiasArgs a{{{logits, lengths, T, V, blank, beam_size, cutoff_top_k, max_nodes_of(T, beam_size),
-                  static_cast<CtcNode*>(workspace), tokens, out_len, score},
-                 NgramTables{}, 0.f, 0, nullptr},
-                context_tables(*graph), graph->ctx_final, bias_weight, bias_score};
-  hipLaunchKernelGGL(ctc_prefix_bias_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, (hipStream_t)stream, a);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  CtcSearch q = ctc_call(logits, lengths, B, T, V, blank, beam_size, cutoff_top_k, workspace, tokens, out_len, score,
+                         stream);
+  bias_part(q, graph, bias_weight, bias_score);
+  return ctc_search(q);
 }
 
 int s2t_ctc_prefix_beam_ngram_bias(const S2tNgramLmDesc* lm, const S2tContextGraphDesc* graph, const float* logits,
@@ -829,26 +848,19 @@ int s2t_ctc_prefix_beam_ngram_bias(const S2tNgramLmDesc* lm, const S2tContextGra
                                    int cutoff_top_k, float lm_weight, int start_ctx, float bias_weight,
                                    void* workspace, long* tokens, long* out_len, float* score, float* lm_score,
                                    float* bias_score, void* stream) {
-  if (B <= 0) return 0;
-  if (T <= 0 || !ctc_ok(T, V, blank, beam_size, cutoff_top_k) || !ngram_desc_ok(lm) || lm->V != V || start_ctx < 0 ||
-      start_ctx >= lm->num_ctx || !__builtin_isfinite(lm_weight) || !context_desc_ok(graph) || graph->V != V ||
-      !__builtin_isfinite(bias_weight) || !lm_score || !bias_score || !workspace)
-    return -1;
-  CtcBiasArgs a{{{logits, lengths, T, V, blank, beam_size, cutoff_top_k, max_nodes_of(T, beam_size),
-                  static_cast<CtcNode*>(workspace), tokens, out_len, score},
-                 ngram_tables(*lm), lm_weight, start_ctx, lm_score},
-                context_tables(*graph), graph->ctx_final, bias_weight, bias_score};
-  hipLaunchKernelGGL(ctc_prefix_ngram_bias_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V,
-                     (hipStream_t)stream, a);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  CtcSearch q = ctc_call(logits, lengths, B, T, V, blank, beam_size, cutoff_top_k, workspace, tokens, out_len, score,
+                         stream);
+  ngram_part(q, lm, lm_weight, lm_score);
+  q.start_ctx = start_ctx;
+  bias_part(q, graph, bias_weight, bias_score);
+  return ctc_search(q);
 }
 
 long s2t_ctc_prefix_beam_lm_workspace_bytes(const S2tRnnLmDesc* lm, int B, int T, int V, int beam_size) {
   if (B <= 0 || T < 0 || V < 1 || V > S2T_RNNT_LSTM_MAX_VOCAB || beam_size < 1 || beam_size > kMaxBeam ||
       !lm_desc_ok(lm, V))
     return 0;
-  return (long)carve_ctc_lm(*lm, B, T, beam_size, nullptr).bytes;
+  return bytes_of([&](Arena& m) { carve_ctc_lm(*lm, B, T, beam_size, m); });
 }
 
 int s2t_ctc_prefix_beam_lm(const S2tRnnLmDesc* lm, const float* logits, const long* lengths, int B, int T,
@@ -861,32 +873,25 @@ int s2t_ctc_prefix_beam_lm(const S2tRnnLmDesc* lm, const float* logits, const lo
     return -1;
   hipStream_t st = (hipStream_t)stream;
   const int R = B * beam_size;
-  const CtcLmWorkspace w = carve_ctc_lm(*lm, B, T, beam_size, workspace);
+  Arena m(workspace);
+  const CtcLmWorkspace w = carve_ctc_lm(*lm, B, T, beam_size, m);
   const size_t lm_state = sizeof(float) * (size_t)lm->num_layers * R * lm->H;
-  hipError_t e = hipMemsetAsync(w.h[0], 0, lm_state, st);
-  if (e == hipSuccess) e = hipMemsetAsync(w.c[0], 0, lm_state, st);
-  if (e == hipSuccess) e = hipMemsetAsync(w.q[0], 0, sizeof(float) * (size_t)R * V, st);
+  hipError_t e = hipMemsetAsync(w.lm.h[0], 0, lm_state, st);
+  if (e == hipSuccess) e = hipMemsetAsync(w.lm.c[0], 0, lm_state, st);
+  if (e == hipSuccess) e = hipMemsetAsync(w.lm.q[0], 0, sizeof(float) * (size_t)R * V, st);
   if (e != hipSuccess) return (int)e;
   CtcLmArgs a{{logits, lengths, T, V, blank, beam_size, cutoff_top_k, max_nodes_of(T, beam_size), w.nodes, tokens,
                out_len, score},
-              w.st, w.q[0], lm_weight, 0, lm_start_token, lm_score};
+              w.st, w.lm.q[0], lm_weight, 0, lm_start_token, lm_score};
   hipLaunchKernelGGL(ctc_lm_init_kernel, dim3(B), dim3(64), 0, st, a);
   if (lm_start_token >= 0) {                               // the LM's first step, on the start token
-    const int rc = s2t_rnn_lm_step(lm, R, w.st.token, w.st.emit, nullptr, w.h[0], w.c[0], w.q[0], w.h[0], w.c[0],
-                                   w.q[0], w.step, stream);
+    const int rc = s2t_rnn_lm_step(lm, R, w.st.token, w.st.emit, nullptr, w.lm.h[0], w.lm.c[0], w.lm.q[0], w.lm.h[0],
+                                   w.lm.c[0], w.lm.q[0], w.lm.step, stream);
     if (rc != 0) return rc;
   }
-  int cur = 0;
-  for (int t = 0; t < T; ++t) {
-    a.t = t;
-    a.q = w.q[cur];
-    hipLaunchKernelGGL(ctc_prefix_round_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, st, a);
-    if (t + 1 == T) break;                                 // (nothing reads the LM after the last frame)
-    const int rc = s2t_rnn_lm_step(lm, R, w.st.token, w.st.emit, w.st.parent, w.h[cur], w.c[cur], w.q[cur],
-                                   w.h[cur ^ 1], w.c[cur ^ 1], w.q[cur ^ 1], w.step, stream);
-    if (rc != 0) return rc;
-    cur ^= 1;
-  }
+  int live;
+  const int rc = ctc_lm_rounds(lm, a, B, T, w.lm, false, stream, &live);
+  if (rc != 0) return rc;
   hipLaunchKernelGGL(ctc_lm_finish_kernel, dim3(B), dim3(64), 0, st, a);
   S2T_CHECK_LAUNCH();
   return 0;
@@ -894,109 +899,86 @@ int s2t_ctc_prefix_beam_lm(const S2tRnnLmDesc* lm, const float* logits, const lo
 
 // ------------------------------------------------------------------ the chunk-carried entries
 long s2t_ctc_stream_state_bytes(int B, int V, int beam_size, int max_nodes) {
-  if (B <= 0 || !ctc_stream_ok(V, beam_size, max_nodes)) return 0;
-  return (long)carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, nullptr).bytes;
+  return stream_state_bytes(nullptr, B, V, beam_size, max_nodes, false, false);
+}
+
+long s2t_ctc_ngram_stream_state_bytes(int B, int V, int beam_size, int max_nodes) {
+  return stream_state_bytes(nullptr, B, V, beam_size, max_nodes, true, false);
+}
+
+long s2t_ctc_bias_stream_state_bytes(int B, int V, int beam_size, int max_nodes) {
+  return stream_state_bytes(nullptr, B, V, beam_size, max_nodes, false, true);
+}
+
+long s2t_ctc_ngram_bias_stream_state_bytes(int B, int V, int beam_size, int max_nodes) {
+  return stream_state_bytes(nullptr, B, V, beam_size, max_nodes, true, true);
+}
+
+long s2t_ctc_lm_stream_state_bytes(const S2tRnnLmDesc* lm, int B, int V, int beam_size, int max_nodes) {
+  return lm_desc_ok(lm, V) ? stream_state_bytes(lm, B, V, beam_size, max_nodes, false, false) : 0;
+}
+
+long s2t_ctc_prefix_beam_lm_chunk_workspace_bytes(const S2tRnnLmDesc* lm, int B, int V, int beam_size) {
+  if (B <= 0 || !ctc_stream_ok(V, beam_size, 1) || !lm_desc_ok(lm, V)) return 0;
+  return bytes_of([&](Arena& m) { carve_ctc_lm_stream_ws(*lm, B, beam_size, m); });
 }
 
 int s2t_ctc_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes, void* stream) {
-  if (B <= 0) return 0;
-  if (!ctc_stream_ok(V, beam_size, max_nodes) || !state) return -1;
-  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state);
-  const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
-                                      nullptr, nullptr, nullptr, nullptr);
-  hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows, -1, 0, 0,
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (int*)nullptr, 0);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  return ctc_reset(reset_call(state, rows, B, V, beam_size, max_nodes, stream));
+}
+
+int s2t_ctc_ngram_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
+                               int start_ctx, void* stream) {
+  CtcReset q = reset_call(state, rows, B, V, beam_size, max_nodes, stream);
+  q.ngram = true;
+  q.start_ctx = start_ctx;
+  return ctc_reset(q);
+}
+
+int s2t_ctc_bias_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
+                              void* stream) {
+  CtcReset q = reset_call(state, rows, B, V, beam_size, max_nodes, stream);
+  q.bias = true;
+  return ctc_reset(q);
+}
+
+int s2t_ctc_ngram_bias_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
+                                    int start_ctx, void* stream) {
+  CtcReset q = reset_call(state, rows, B, V, beam_size, max_nodes, stream);
+  q.ngram = q.bias = true;
+  q.start_ctx = start_ctx;
+  return ctc_reset(q);
+}
+
+int s2t_ctc_lm_stream_reset(const S2tRnnLmDesc* lm, int lm_start_token, void* state, const int* rows, int B, int V,
+                            int beam_size, int max_nodes, void* workspace, void* stream) {
+  CtcReset q = reset_call(state, rows, B, V, beam_size, max_nodes, stream);
+  q.rnn = true;
+  q.lm = lm;
+  q.lm_start_token = lm_start_token;
+  q.workspace = workspace;
+  return ctc_reset(q);
 }
 
 int s2t_ctc_prefix_beam_chunk(const float* logits, const long* chunk_len, int B, int Tc, int V, int blank,
                               int beam_size, int cutoff_top_k, int max_tokens, int max_nodes, void* state,
                               long* tokens, long* out_len, float* score, long* stable_len, int* overflow,
                               void* stream) {
-  if (B <= 0) return 0;
-  if (Tc < 1 || Tc > 256 || !ctc_ok(Tc, V, blank, beam_size, cutoff_top_k) || max_tokens < 1 ||
-      !ctc_stream_ok(V, beam_size, max_nodes) || !state)
-    return -1;
-  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state);
-  const CtcStreamArgs a = stream_args(s, logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_tokens,
-                                      max_nodes, tokens, out_len, score, nullptr, stable_len, overflow);
-  hipLaunchKernelGGL(ctc_prefix_chunk_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, (hipStream_t)stream, a);
-  S2T_CHECK_LAUNCH();
-  return 0;
-}
-
-long s2t_ctc_ngram_stream_state_bytes(int B, int V, int beam_size, int max_nodes) {
-  if (B <= 0 || !ctc_stream_ok(V, beam_size, max_nodes)) return 0;
-  return (long)carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, nullptr, true).bytes;
-}
-
-int s2t_ctc_ngram_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
-                               int start_ctx, void* stream) {
-  if (B <= 0) return 0;
-  if (!ctc_stream_ok(V, beam_size, max_nodes) || start_ctx < 0 || !state) return -1;
-  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, true);
-  const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
-                                      nullptr, nullptr, nullptr, nullptr);
-  hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows, -1, 0, 0,
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr, s.ctx, start_ctx);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  CtcSearch q = ctc_call(logits, chunk_len, B, Tc, V, blank, beam_size, cutoff_top_k, state, tokens, out_len, score,
+                         stream);
+  chunk_part(q, max_tokens, max_nodes, stable_len, overflow);
+  return ctc_search(q);
 }
 
 int s2t_ctc_prefix_beam_ngram_chunk(const S2tNgramLmDesc* lm, const float* logits, const long* chunk_len, int B,
                                     int Tc, int V, int blank, int beam_size, int cutoff_top_k, float lm_weight,
                                     int max_tokens, int max_nodes, void* state, long* tokens, long* out_len,
                                     float* score, float* lm_score, long* stable_len, int* overflow, void* stream) {
-  if (B <= 0) return 0;
-  if (Tc < 1 || Tc > 256 || !ctc_ok(Tc, V, blank, beam_size, cutoff_top_k) || max_tokens < 1 ||
-      !ctc_stream_ok(V, beam_size, max_nodes) || !ngram_desc_ok(lm) || lm->V != V ||
-      !__builtin_isfinite(lm_weight) || !lm_score || !state)
-    return -1;
-  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, true);
-  const CtcNgramStreamArgs a{stream_args(s, logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_tokens,
-                                         max_nodes, tokens, out_len, score, lm_score, stable_len, overflow),
-                             ngram_tables(*lm), lm_weight, s.ctx};
-  hipLaunchKernelGGL(ctc_prefix_ngram_chunk_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V,
-                     (hipStream_t)stream, a);
-  S2T_CHECK_LAUNCH();
-  return 0;
-}
-
-long s2t_ctc_bias_stream_state_bytes(int B, int V, int beam_size, int max_nodes) {
-  if (B <= 0 || !ctc_stream_ok(V, beam_size, max_nodes)) return 0;
-  return (long)carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, nullptr, false, true).bytes;
-}
-
-long s2t_ctc_ngram_bias_stream_state_bytes(int B, int V, int beam_size, int max_nodes) {
-  if (B <= 0 || !ctc_stream_ok(V, beam_size, max_nodes)) return 0;
-  return (long)carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, nullptr, true, true).bytes;
-}
-
-int s2t_ctc_bias_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
-                              void* stream) {
-  if (B <= 0) return 0;
-  if (!ctc_stream_ok(V, beam_size, max_nodes) || !state) return -1;
-  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, false, true);
-  const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
-                                      nullptr, nullptr, nullptr, nullptr);
-  hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows, -1, 0, 0,
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (int*)nullptr, 0, s.bstate, s.bsum);
-  S2T_CHECK_LAUNCH();
-  return 0;
-}
-
-int s2t_ctc_ngram_bias_stream_reset(void* state, const int* rows, int B, int V, int beam_size, int max_nodes,
-                                    int start_ctx, void* stream) {
-  if (B <= 0) return 0;
-  if (!ctc_stream_ok(V, beam_size, max_nodes) || start_ctx < 0 || !state) return -1;
-  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, true, true);
-  const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
-                                      nullptr, nullptr, nullptr, nullptr);
-  hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows, -1, 0, 0,
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr, s.ctx, start_ctx, s.bstate, s.bsum);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  CtcSearch q = ctc_call(logits, chunk_len, B, Tc, V, blank, beam_size, cutoff_top_k, state, tokens, out_len, score,
+                         stream);
+  chunk_part(q, max_tokens, max_nodes, stable_len, overflow);
+  ngram_part(q, lm, lm_weight, lm_score);
+  return ctc_search(q);
 }
 
 int s2t_ctc_prefix_beam_bias_chunk(const S2tContextGraphDesc* graph, const float* logits, const long* chunk_len,
@@ -1004,20 +986,11 @@ int s2t_ctc_prefix_beam_bias_chunk(const S2tContextGraphDesc* graph, const float
                                    float bias_weight, int max_tokens, int max_nodes, void* state, long* tokens,
                                    long* out_len, float* score, float* bias_score, long* stable_len, int* overflow,
                                    void* stream) {
-  if (B <= 0) return 0;
-  if (Tc < 1 || Tc > 256 || !ctc_ok(Tc, V, blank, beam_size, cutoff_top_k) || max_tokens < 1 ||
-      !ctc_stream_ok(V, beam_size, max_nodes) || !context_desc_ok(graph) || graph->V != V ||
-      !__builtin_isfinite(bias_weight) || !bias_score || !state)
-    return -1;
-  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, false, true);
-  const CtcBiasStreamArgs a{{stream_args(s, logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_tokens,
-                                         max_nodes, tokens, out_len, score, nullptr, stable_len, overflow),
-                             NgramTables{}, 0.f, nullptr},
-                            context_tables(*graph), graph->ctx_final, bias_weight, s.bstate, s.bsum, bias_score};
-  hipLaunchKernelGGL(ctc_prefix_bias_chunk_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V,
-                     (hipStream_t)stream, a);
-  S2T_CHECK_LAUNCH();
-  return 0;
+  CtcSearch q = ctc_call(logits, chunk_len, B, Tc, V, blank, beam_size, cutoff_top_k, state, tokens, out_len, score,
+                         stream);
+  chunk_part(q, max_tokens, max_nodes, stable_len, overflow);
+  bias_part(q, graph, bias_weight, bias_score);
+  return ctc_search(q);
 }
 
 int s2t_ctc_prefix_beam_ngram_bias_chunk(const S2tNgramLmDesc* lm, const S2tContextGraphDesc* graph,
@@ -1026,51 +999,12 @@ int s2t_ctc_prefix_beam_ngram_bias_chunk(const S2tNgramLmDesc* lm, const S2tCont
                                          int max_tokens, int max_nodes, void* state, long* tokens, long* out_len,
                                          float* score, float* lm_score, float* bias_score, long* stable_len,
                                          int* overflow, void* stream) {
-  if (B <= 0) return 0;
-  if (Tc < 1 || Tc > 256 || !ctc_ok(Tc, V, blank, beam_size, cutoff_top_k) || max_tokens < 1 ||
-      !ctc_stream_ok(V, beam_size, max_nodes) || !ngram_desc_ok(lm) || lm->V != V ||
-      !__builtin_isfinite(lm_weight) || !lm_score || !context_desc_ok(graph) || graph->V != V ||
-      !__builtin_isfinite(bias_weight) || !bias_score || !state)
-    return -1;
-  const CtcStream s = carve_ctc_stream(nullptr, B, V, beam_size, max_nodes, state, true, true);
-  const CtcBiasStreamArgs a{{stream_args(s, logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_tokens,
-                                         max_nodes, tokens, out_len, score, lm_score, stable_len, overflow),
-                             ngram_tables(*lm), lm_weight, s.ctx},
-                            context_tables(*graph), graph->ctx_final, bias_weight, s.bstate, s.bsum, bias_score};
-  hipLaunchKernelGGL(ctc_prefix_ngram_bias_chunk_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V,
-                     (hipStream_t)stream, a);
-  S2T_CHECK_LAUNCH();
-  return 0;
-}
-
-long s2t_ctc_lm_stream_state_bytes(const S2tRnnLmDesc* lm, int B, int V, int beam_size, int max_nodes) {
-  if (B <= 0 || !ctc_stream_ok(V, beam_size, max_nodes) || !lm_desc_ok(lm, V)) return 0;
-  return (long)carve_ctc_stream(lm, B, V, beam_size, max_nodes, nullptr).bytes;
-}
-
-long s2t_ctc_prefix_beam_lm_chunk_workspace_bytes(const S2tRnnLmDesc* lm, int B, int V, int beam_size) {
-  if (B <= 0 || !ctc_stream_ok(V, beam_size, 1) || !lm_desc_ok(lm, V)) return 0;
-  return (long)carve_ctc_lm_stream_ws(*lm, B, beam_size, nullptr).bytes;
-}
-
-int s2t_ctc_lm_stream_reset(const S2tRnnLmDesc* lm, int lm_start_token, void* state, const int* rows, int B, int V,
-                            int beam_size, int max_nodes, void* workspace, void* stream) {
-  if (B <= 0) return 0;
-  if (!ctc_stream_ok(V, beam_size, max_nodes) || !lm_desc_ok(lm, V) || lm_start_token >= V || !state || !workspace)
-    return -1;
-  const CtcStream s = carve_ctc_stream(lm, B, V, beam_size, max_nodes, state);
-  const CtcLmStreamWorkspace w = carve_ctc_lm_stream_ws(*lm, B, beam_size, workspace);
-  const CtcStreamArgs a = stream_args(s, nullptr, nullptr, 0, V, 0, beam_size, 1, 1, max_nodes, nullptr, nullptr,
-                                      nullptr, nullptr, nullptr, nullptr);
-  hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3(B), dim3(kCtcThreads), 0, (hipStream_t)stream, a, rows,
-                     lm_start_token, lm->num_layers, lm->H, s.h, s.c, s.q, (int*)nullptr, 0);
-  if (lm_start_token >= 0) {                               // the one-shot entry's own first step, masked by rows
-    const int rc = s2t_rnn_lm_step(lm, B * beam_size, s.st.token, s.st.emit, nullptr, s.h, s.c, s.q, s.h, s.c, s.q,
-                                   w.step, stream);
-    if (rc != 0) return rc;
-  }
-  S2T_CHECK_LAUNCH();
-  return 0;
+  CtcSearch q = ctc_call(logits, chunk_len, B, Tc, V, blank, beam_size, cutoff_top_k, state, tokens, out_len, score,
+                         stream);
+  chunk_part(q, max_tokens, max_nodes, stable_len, overflow);
+  ngram_part(q, lm, lm_weight, lm_score);
+  bias_part(q, graph, bias_weight, bias_score);
+  return ctc_search(q);
 }
 
 int s2t_ctc_prefix_beam_lm_chunk(const S2tRnnLmDesc* lm, const float* logits, const long* chunk_len, int B, int Tc,
@@ -1085,25 +1019,24 @@ int s2t_ctc_prefix_beam_lm_chunk(const S2tRnnLmDesc* lm, const float* logits, co
     return -1;
   hipStream_t st = (hipStream_t)stream;
   const int R = B * beam_size;
-  const CtcStream s = carve_ctc_stream(lm, B, V, beam_size, max_nodes, state);
-  const CtcLmStreamWorkspace w = carve_ctc_lm_stream_ws(*lm, B, beam_size, workspace);
-  const CtcStreamArgs sa = stream_args(s, logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_tokens,
-                                       max_nodes, tokens, out_len, score, lm_score, stable_len, overflow);
+  Arena sm(state), wm(workspace);
+  const CtcStream s = carve_ctc_stream(lm, B, V, beam_size, max_nodes, sm);
+  const CtcLmStreamWorkspace w = carve_ctc_lm_stream_ws(*lm, B, beam_size, wm);
+  CtcStreamArgs sa{};
+  sa.c = CtcArgs{logits, chunk_len, Tc, V, blank, beam_size, cutoff_top_k, max_nodes, s.nodes, tokens, out_len, score};
+  stream_part(sa, s);
+  sa.max_tokens = max_tokens;
+  sa.lm_score = lm_score;
+  sa.stable_len = stable_len;
+  sa.overflow = overflow;
   hipLaunchKernelGGL(ctc_stream_begin_kernel, dim3(B), dim3(64), 0, st, sa);
   CtcLmArgs a{sa.c, s.st, s.q, lm_weight, 0, lm_start_token, lm_score};
   a.c.lengths = s.eff;                                     // the rounds walk the frames this call consumes
-  float *h[2] = {s.h, w.h}, *c[2] = {s.c, w.c}, *q[2] = {s.q, w.q};
-  int cur = 0;
-  for (int t = 0; t < Tc; ++t) {
-    a.t = t;
-    a.q = q[cur];
-    hipLaunchKernelGGL(ctc_prefix_round_kernel, dim3(B), dim3(kCtcThreads), sizeof(float) * V, st, a);
-    const int rc = s2t_rnn_lm_step(lm, R, s.st.token, s.st.emit, s.st.parent, h[cur], c[cur], q[cur], h[cur ^ 1],
-                                   c[cur ^ 1], q[cur ^ 1], w.step, stream);   // (also after the last frame: the
-    if (rc != 0) return rc;                                                   // next chunk's frame 0 reads it)
-    cur ^= 1;
-  }
-  if (cur) {
+  const CtcLmCopies copies{{s.h, w.h}, {s.c, w.c}, {s.q, w.q}, w.step};
+  int live;
+  const int rc = ctc_lm_rounds(lm, a, B, Tc, copies, true, stream, &live);
+  if (rc != 0) return rc;
+  if (live) {                                              // (an odd Tc: the survivors' LM state is in the workspace)
     const long ns = (long)lm->num_layers * R * lm->H, nq = (long)R * V;
     const CtcCopyHomeArgs cp{{w.h, w.c, w.q}, {s.h, s.c, s.q}, {ns, ns, nq}};
     const long most = ns > nq ? ns : nq, need = (most + kCtcThreads - 1) / kCtcThreads;
@@ -1113,5 +1046,6 @@ int s2t_ctc_prefix_beam_lm_chunk(const S2tRnnLmDesc* lm, const float* logits, co
   S2T_CHECK_LAUNCH();
   return 0;
 }
+
 
 }  // extern "C"

@@ -275,21 +275,7 @@ __global__ __launch_bounds__(kThreads) void cell_kernel(CellArgs a) {
   }
 }
 
-// ------------------------------------------------------------------ workspace
-// A caller's buffer handed out array by array, each on a 256-byte boundary.  Without a base (the
-// *_bytes queries) it only adds the sizes up and hands out NULL.
-struct Arena {
-  char* base;
-  size_t bytes = 0;
-  explicit Arena(void* b) : base(static_cast<char*>(b)) {}
-  template <class T>
-  T* take(size_t n) {
-    const size_t at = bytes;
-    bytes += align256(sizeof(T) * n);
-    return base ? reinterpret_cast<T*>(base + at) : nullptr;
-  }
-};
-
+// ------------------------------------------------------------------ workspace (Arena: decode_records.h)
 // What a search works on whatever its predictor: R = B * max(1, beam) rows.
 struct SearchArrays {
   float *z, *mid, *logit;       // joint: act(am + lm) [R][V], [R][inner], out-projection [R][V]
@@ -1571,14 +1557,7 @@ int stream_reset(const P& p, const Fusion* f, void* state, const int* rows, int 
   return 0;
 }
 
-// ------------------------------------------------------------------ sizes, on the host
-template <class Carve>
-long bytes_of(Carve carve) {
-  Arena m(nullptr);
-  carve(m);
-  return (long)m.bytes;
-}
-
+// ------------------------------------------------------------------ sizes, on the host (bytes_of: decode_records.h)
 // a fused search's workspace: the predictor's, then the LM's
 template <class P>
 long fused_workspace_bytes(const P& p, const Fusion& f, int B, int T, int beam, int n_state) {

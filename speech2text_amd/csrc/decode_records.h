@@ -2,7 +2,8 @@
 // (decode_search.h, decode_beam.hip, decode_stream.hip) and the lockstep LSTM ones (decode_lstm.hip):
 // the limits, the (parent, class) record, candidate ranking, the trace-back of the best beam, and a
 // chunk's records turned into histories and outputs.  THREADS is a template parameter: the two
-// families launch 512 and 256 (or 64) threads.
+// families launch 512 and 256 (or 64) threads.  Also the Arena that hands out the workspaces and states
+// of decode_lstm.hip and decode_ctc.hip and answers their size queries.
 #pragma once
 #include "common.h"
 
@@ -14,6 +15,28 @@ constexpr int kTraceFrames = 64;   // frames of records staged in LDS per trace-
 constexpr int kMaxChunk = 256;     // frames per chunk call
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// A caller's buffer handed out array by array, each on a 256-byte boundary.  Without a base (the
+// *_bytes queries) it only adds the sizes up and hands out NULL.
+struct Arena {
+  char* base;
+  size_t bytes = 0;
+  explicit Arena(void* b) : base(static_cast<char*>(b)) {}
+  template <class T>
+  T* take(size_t n) {
+    const size_t at = bytes;
+    bytes += align256(sizeof(T) * n);
+    return base ? reinterpret_cast<T*>(base + at) : nullptr;
+  }
+};
+
+// the size a layout takes: its carve function run on an Arena without a base
+template <class Carve>
+long bytes_of(Carve carve) {
+  Arena m(nullptr);
+  carve(m);
+  return (long)m.bytes;
+}
 
 // frames of row b, held to [0, T]
 __host__ __device__ __forceinline__ long clamped_len(const long* lengths, int b, int T) {

@@ -25,6 +25,53 @@ def test_ctc_workspace_size_is_pure_host_function():
     assert lib.s2t_ctc_workspace_floats(2, 10, 3) == 2 * 10 + 3 * 2 * 10 * 7 + 2   # lse + lp,alpha,beta + nll
 
 
+def test_ctc_search_size_queries_are_pure_host_functions():
+    """Every size query of the CTC prefix beam search at two shapes: the bytes the layouts took before one
+    arena handed them out (literals of the library built from that commit: trie nodes of 16 bytes, every
+    array rounded up to 256 bytes).  An LM desc with only V, E, H and num_layers filled is enough: no query
+    reads a weight.  One refused shape per query answers 0."""
+    lib = _native.lib()
+    Lm = _native.parse_abi(open(_native.HEADER_PATH).read())[1]["S2tRnnLmDesc"]
+
+    def lm(V, E, H, layers):
+        d = Lm()
+        d.V, d.E, d.H, d.num_layers = V, E, H, layers
+        return ctypes.byref(d)
+
+    B, T, V, beam, nodes, d = 2, 30, 50, 4, 100, lm(50, 16, 32, 2)
+    assert lib.s2t_ctc_prefix_beam_workspace_bytes(B, T, V, beam) == 4096
+    assert lib.s2t_ctc_prefix_beam_ngram_workspace_bytes(B, T, V, beam) == 4096
+    assert lib.s2t_ctc_prefix_beam_lm_workspace_bytes(d, B, T, V, beam) == 26112
+    assert lib.s2t_ctc_stream_state_bytes(B, V, beam, nodes) == 10496
+    assert lib.s2t_ctc_ngram_stream_state_bytes(B, V, beam, nodes) == 10752     # + the context ids
+    assert lib.s2t_ctc_bias_stream_state_bytes(B, V, beam, nodes) == 11008      # + the graph states and sums
+    assert lib.s2t_ctc_ngram_bias_stream_state_bytes(B, V, beam, nodes) == 11264
+    assert lib.s2t_ctc_lm_stream_state_bytes(d, B, V, beam, nodes) == 17152
+    assert lib.s2t_ctc_prefix_beam_lm_chunk_workspace_bytes(d, B, V, beam) == 13312
+
+    B, T, V, beam, nodes, d = 1, 1, 7, 1, 1, lm(7, 8, 4, 1)
+    assert lib.s2t_ctc_prefix_beam_workspace_bytes(B, T, V, beam) == 256
+    assert lib.s2t_ctc_prefix_beam_ngram_workspace_bytes(B, T, V, beam) == 256
+    assert lib.s2t_ctc_prefix_beam_lm_workspace_bytes(d, B, T, V, beam) == 6400
+    assert lib.s2t_ctc_stream_state_bytes(B, V, beam, nodes) == 3584
+    assert lib.s2t_ctc_ngram_stream_state_bytes(B, V, beam, nodes) == 3840
+    assert lib.s2t_ctc_bias_stream_state_bytes(B, V, beam, nodes) == 4096
+    assert lib.s2t_ctc_ngram_bias_stream_state_bytes(B, V, beam, nodes) == 4352
+    assert lib.s2t_ctc_lm_stream_state_bytes(d, B, V, beam, nodes) == 5120
+    assert lib.s2t_ctc_prefix_beam_lm_chunk_workspace_bytes(d, B, V, beam) == 2560
+
+    beam_max, nodes_max = _native.const("S2T_RNNT_LSTM_MAX_BEAM"), _native.const("S2T_CTC_STREAM_MAX_NODES")
+    assert lib.s2t_ctc_prefix_beam_workspace_bytes(0, 30, 50, 4) == 0                   # no batch
+    assert lib.s2t_ctc_prefix_beam_ngram_workspace_bytes(2, -1, 50, 4) == 0             # T < 0
+    assert lib.s2t_ctc_prefix_beam_lm_workspace_bytes(lm(49, 16, 32, 2), 2, 30, 50, 4) == 0   # the LM's V is not V
+    assert lib.s2t_ctc_stream_state_bytes(2, 50, beam_max + 1, 100) == 0
+    assert lib.s2t_ctc_ngram_stream_state_bytes(2, 50, 4, 0) == 0                       # no node for the root
+    assert lib.s2t_ctc_bias_stream_state_bytes(2, 50, 4, nodes_max + 1) == 0
+    assert lib.s2t_ctc_ngram_bias_stream_state_bytes(2, 0, 4, 100) == 0
+    assert lib.s2t_ctc_lm_stream_state_bytes(lm(50, 16, 30, 2), 2, 50, 4, 100) == 0     # H is no multiple of 4
+    assert lib.s2t_ctc_prefix_beam_lm_chunk_workspace_bytes(None, 2, 50, 4) == 0
+
+
 # ------------------------------------------------------------------ structs and constants from the header
 def _c_name(field):
     """The header's name of a parsed field (a Python keyword got a trailing underscore)."""

@@ -2,7 +2,7 @@
 s2t_ctc_prefix_beam_ngram_bias and their _chunk partners) next to the entries it extends, and show that
 those entries did not pay for it.
 
-    python tools/time_ctc_bias.py [--runs 20] [--loop-runs 1] [--parent-lib PATH] [--out FILE]
+    python tools/time_ctc_bias.py [--runs 20] [--loop-runs 1] [--parent-lib PATH] [--label NAME] [--out FILE]
 
 Inputs: tools/bench_ctc_ngram.py's (16 x 250 frames of log-probability rows at V 128, the blank bias bisected
 so that the plain search emits about 40 tokens an utterance, beam 4 / top-k 4, the order-3 n-gram of its
@@ -15,11 +15,18 @@ its runs with the spread (min .. max) behind.
   2. chunk        a 16-frame chunk call of the four streaming searches (CtcStreamingSearch,
                   CtcNgramStreamingSearch, CtcBiasStreamingSearch without and with the n-gram), each on a
                   stream of its own that is reset every 32 calls.
-  3. vs_parent    with --parent-lib (another build of libs2t_mi355.so, the parent commit's): s2t_ctc_prefix_beam,
-                  _ngram, _chunk and _ngram_chunk of both libraries through plain ctypes handles on the same
-                  buffers, alternating, and `bits_equal`: their outputs compared with torch.equal on every
-                  case of tests/ctc_prefix_cases.PLAIN_CASES and tests/ctc_ngram_cases.CASES (whole utterances,
-                  and fed in 7-frame chunks).
+  3. vs_parent    with --parent-lib (another build of libs2t_mi355.so, the parent commit's): the twelve search
+                  entries (s2t_ctc_prefix_beam, _ngram, _bias, _ngram_bias, _lm and their _chunk partners, each
+                  with its matching reset) of this build, of the parent's and of the parent's loaded a second
+                  time from a byte copy under another name, through plain ctypes handles on the same inputs
+                  (the whole-utterance entries also on the same workspace and outputs, a stream on a state
+                  of its own), alternating, the three libraries' order within a figure rotating run by run
+                  (no library is always the first after another figure's kernel).  Parent against parent is
+                  the noise: `speed_limit_ms` is the larger parent median plus the two parents' difference,
+                  `speed_missed` the figures of this build above it.  `bits_equal`: both builds' outputs compared byte for byte on every case of
+                  tests/ctc_prefix_cases.PLAIN_CASES, tests/ctc_ngram_cases.CASES and
+                  tests/ctc_bias_cases.CASES, every entry on every case, whole utterances and fed in 7-frame
+                  chunks, the chunk entries' caller-owned state buffers included after every chunk.
 
 One JSON line, appended to `--out` (default profiles/ctc_bias.jsonl).  Nothing is gated.
 """
@@ -27,8 +34,10 @@ import argparse
 import ctypes
 import json
 import os
+import shutil
 import statistics
 import sys
+import tempfile
 
 import torch
 
@@ -61,16 +70,21 @@ def _stats(ms):
             "runs": len(ms)}
 
 
-def _alternate(calls, runs, warmup=3):
-    """{name: fn} -> {name: stats}, the calls alternating call by call."""
+def _alternate(calls, runs, warmup=3, group=1):
+    """{name: fn} -> {name: stats}, the calls alternating call by call.  group: the calls are groups of that
+    many in a row (one figure of several libraries), and run r walks every group from its member r % group
+    on, so that each member follows each neighbour equally often."""
+    names = list(calls)
     for _ in range(warmup):
         for fn in calls.values():
             fn()
     torch.cuda.synchronize()
     times = {k: [] for k in calls}
-    for _ in range(runs):
-        for k, fn in calls.items():
-            times[k].append(_event_ms(fn)[0])
+    for r in range(runs):
+        for g0 in range(0, len(names), group):
+            for i in range(group):
+                k = names[g0 + (r + i) % group]
+                times[k].append(_event_ms(calls[k])[0])
     return {k: _stats(v) for k, v in times.items()}
 
 
@@ -89,102 +103,176 @@ def phrases_of(text, n, seed):
     return out
 
 
-class _Raw:
-    """The four existing CTC entries of the library at `path` through a ctypes handle of its own."""
+class _Kind:
+    """What a search runs with, and so which of the six families its entries are: nothing, a back-off n-gram
+    (lm, weight), a hotword graph (graph, bias_weight), both, or an RNN-LM (rnn: RnnLm, weight, start token)."""
 
-    NAMES = ("s2t_ctc_prefix_beam_workspace_bytes", "s2t_ctc_prefix_beam", "s2t_ctc_prefix_beam_ngram",
-             "s2t_ctc_stream_state_bytes", "s2t_ctc_stream_reset", "s2t_ctc_prefix_beam_chunk",
-             "s2t_ctc_ngram_stream_state_bytes", "s2t_ctc_ngram_stream_reset", "s2t_ctc_prefix_beam_ngram_chunk")
+    def __init__(self, lm=None, weight=0.0, graph=None, bias_weight=1.0, rnn=None, start=-1):
+        from speech2text_amd.model.decoding import rnn_lm_desc
+        parts = ["lm"] if rnn is not None else ["ngram"] * (lm is not None) + ["bias"] * (graph is not None)
+        self.family = "".join(p + "_" for p in parts)        # as in s2t_ctc_<family>stream_reset
+        self.suffix = "".join("_" + p for p in parts)        # as in s2t_ctc_prefix_beam<suffix>[_chunk]
+        self.rnn, self.lm_scored, self.biased = None, lm is not None or rnn is not None, graph is not None
+        # the descriptors in front, then what the whole-utterance, the chunk and the reset entry take of it
+        self.descs, self.keep, self.whole, self.chunk, self.reset = (), [], (), (), ()
+        if rnn is not None:
+            self.rnn, keep = rnn_lm_desc(rnn)
+            self.descs, self.whole, self.chunk = (self.rnn,), (weight, start), (weight, start)
+            self.keep.append(keep)
+        if lm is not None:
+            desc, keep = lm.desc()
+            ctx = int(lm.start_ctx)
+            self.descs, self.whole, self.chunk, self.reset = (desc,), (weight, ctx), (weight,), (ctx,)
+            self.keep.append(keep)
+        if graph is not None:
+            desc, keep = graph.desc()
+            self.descs, self.whole, self.chunk = self.descs + (desc,), self.whole + (bias_weight,), \
+                self.chunk + (bias_weight,)
+            self.keep.append(keep)
+
+
+class _Raw:
+    """The CTC prefix beam search entries of the library at `path` through a ctypes handle of its own."""
 
     def __init__(self, path, N):
-        self.N, lib, protos = N, ctypes.CDLL(path), N.parse_header()
-        for name in self.NAMES:
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = protos[name]
-            setattr(self, name[4:], fn)
+        self.N, lib = N, ctypes.CDLL(path)
+        for name, proto in N.parse_header().items():
+            if name.startswith("s2t_ctc_"):
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = proto
+                setattr(self, name[4:], fn)
 
-    def outputs(self, x, max_tokens=None):
-        B, T, dev = x.shape[0], max_tokens or x.shape[1], x.device
-        return dict(tokens=torch.zeros((B, T), dtype=torch.int64, device=dev),
-                    out_len=torch.zeros((B,), dtype=torch.int64, device=dev),
-                    score=torch.zeros((B,), device=dev), lm_score=torch.zeros((B,), device=dev),
-                    stable=torch.zeros((B,), dtype=torch.int64, device=dev),
-                    ovf=torch.zeros((B,), dtype=torch.int32, device=dev))
+    def outputs(self, x, k, max_tokens=None):
+        """-> (the outputs' tensors, their pointers in the entries' order up to the scores)."""
+        B, T, dev, N = x.shape[0], max_tokens or x.shape[1], x.device, self.N
+        o = dict(tokens=torch.zeros((B, T), dtype=torch.int64, device=dev),
+                 out_len=torch.zeros((B,), dtype=torch.int64, device=dev),
+                 score=torch.zeros((B,), device=dev), lm_score=torch.zeros((B,), device=dev),
+                 bias_score=torch.zeros((B,), device=dev),
+                 stable=torch.zeros((B,), dtype=torch.int64, device=dev),
+                 ovf=torch.zeros((B,), dtype=torch.int32, device=dev))
+        ptrs = (N.lp(o["tokens"]), N.lp(o["out_len"]), N.fp(o["score"])) + \
+            ((N.fp(o["lm_score"]),) if k.lm_scored else ()) + ((N.fp(o["bias_score"]),) if k.biased else ())
+        return o, ptrs
 
-    def one_shot(self, x, lens, beam, topk, lm=None, weight=0.0):
-        """-> (call, outputs): the plain entry, or with lm the n-gram entry."""
+    def one_shot(self, x, lens, beam, topk, k, buffers=None):
+        """-> (call, outputs, buffers) of the whole-utterance entry of k's family; buffers: another library's,
+        so that both work on the same workspace and outputs (a timing; never where outputs are compared)."""
         N, (B, T, V) = self.N, x.shape
-        o = self.outputs(x)
-        ws = torch.empty((self.ctc_prefix_beam_workspace_bytes(B, T, V, beam),), dtype=torch.uint8, device=x.device)
-        desc, keep = lm.desc() if lm is not None else (None, None)
+        if buffers is None:
+            nbytes = self.ctc_prefix_beam_workspace_bytes(B, T, V, beam) if k.rnn is None else \
+                self.ctc_prefix_beam_lm_workspace_bytes(k.rnn, B, T, V, beam)
+            buffers = self.outputs(x, k) + (torch.empty((nbytes,), dtype=torch.uint8, device=x.device),)
+        o, ptrs, ws = buffers
+        fn, name = getattr(self, "ctc_prefix_beam" + k.suffix), "s2t_ctc_prefix_beam" + k.suffix
+        args = k.descs + (N.fp(x), N.lp(lens), B, T, V, 0, beam, topk) + k.whole + (N.ptr(ws),) + ptrs
 
         def call():
-            if lm is None:
-                rc = self.ctc_prefix_beam(N.fp(x), N.lp(lens), B, T, V, 0, beam, topk, N.ptr(ws), N.lp(o["tokens"]),
-                                          N.lp(o["out_len"]), N.fp(o["score"]), N.stream())
-            else:
-                rc = self.ctc_prefix_beam_ngram(desc, N.fp(x), N.lp(lens), B, T, V, 0, beam, topk, weight,
-                                                int(lm.start_ctx), N.ptr(ws), N.lp(o["tokens"]), N.lp(o["out_len"]),
-                                                N.fp(o["score"]), N.fp(o["lm_score"]), N.stream())
-            N.check(rc, "one-shot entry")
-            return keep
-        return call, o
+            N.check(fn(*args, N.stream()), name)
+            return ws
+        return call, o, buffers
 
-    def stream(self, x, beam, topk, max_tokens, max_nodes, lm=None, weight=0.0):
-        """-> (reset, chunk(chunk, chunk_len), outputs, state) of the plain or n-gram chunk entries."""
+    def stream(self, x, beam, topk, max_tokens, max_nodes, k):
+        """-> (reset, chunk(chunk, chunk_len), outputs, state) of the chunk entries of k's family.  The state
+        (and the LM family's workspace) starts as one byte pattern, so that what no kernel writes, the
+        padding behind every array, is the same in two libraries' buffers."""
         N, (B, _, V) = self.N, x.shape
-        o = self.outputs(x, max_tokens)
-        size = self.ctc_stream_state_bytes if lm is None else self.ctc_ngram_stream_state_bytes
-        state = torch.zeros((size(B, V, beam, max_nodes),), dtype=torch.uint8, device=x.device)
-        desc, keep = lm.desc() if lm is not None else (None, None)
+        o, ptrs = self.outputs(x, k, max_tokens)
+        head = () if k.rnn is None else (k.rnn,)
+        size = getattr(self, "ctc_" + k.family + "stream_state_bytes")(*head, B, V, beam, max_nodes)
+        state = torch.full((size,), 0xA5, dtype=torch.uint8, device=x.device)
+        ws = None if k.rnn is None else torch.full((self.ctc_prefix_beam_lm_chunk_workspace_bytes(k.rnn, B, V, beam),),
+                                                   0xA5, dtype=torch.uint8, device=x.device)
+        reset_fn = getattr(self, "ctc_" + k.family + "stream_reset")
+        chunk_fn = getattr(self, f"ctc_prefix_beam{k.suffix}_chunk")
+        shape = (N.ptr(state), None, B, V, beam, max_nodes)
+        reset_args = shape + k.reset if k.rnn is None else (k.rnn, k.whole[1]) + shape + (N.ptr(ws),)
+        mem = (max_tokens, max_nodes, N.ptr(state)) + (() if ws is None else (N.ptr(ws),))
+        tail = mem + ptrs + (N.lp(o["stable"]), N.ip(o["ovf"]))
 
         def reset():
-            if lm is None:
-                rc = self.ctc_stream_reset(N.ptr(state), None, B, V, beam, max_nodes, N.stream())
-            else:
-                rc = self.ctc_ngram_stream_reset(N.ptr(state), None, B, V, beam, max_nodes, int(lm.start_ctx),
-                                                 N.stream())
-            N.check(rc, "stream reset")
+            N.check(reset_fn(*reset_args, N.stream()), f"s2t_ctc_{k.family}stream_reset")
 
         def chunk(ch, cl):
-            tail = (max_tokens, max_nodes, N.ptr(state), N.lp(o["tokens"]), N.lp(o["out_len"]), N.fp(o["score"]))
-            if lm is None:
-                rc = self.ctc_prefix_beam_chunk(N.fp(ch), N.lp(cl), B, ch.shape[1], V, 0, beam, topk, *tail,
-                                                N.lp(o["stable"]), N.ip(o["ovf"]), N.stream())
-            else:
-                rc = self.ctc_prefix_beam_ngram_chunk(desc, N.fp(ch), N.lp(cl), B, ch.shape[1], V, 0, beam, topk,
-                                                      weight, *tail, N.fp(o["lm_score"]), N.lp(o["stable"]),
-                                                      N.ip(o["ovf"]), N.stream())
-            N.check(rc, "chunk entry")
-            return keep
+            rc = chunk_fn(*k.descs, N.fp(ch), N.lp(cl), B, ch.shape[1], V, 0, beam, topk, *k.chunk, *tail, N.stream())
+            N.check(rc, f"s2t_ctc_prefix_beam{k.suffix}_chunk")
+            return ws
         return reset, chunk, o, state
 
 
-def _bits_equal(tree, parent, dev):
-    """Both libraries on every plain and n-gram test case, one-shot and in 7-frame chunks -> (cases, equal)."""
+FAMILIES = ("plain", "ngram", "bias", "ngram_bias", "lm")
+
+
+def _kinds(V, dev, lm, weight, graph, bias_weight, start=-1):
+    """{family: _Kind} on V classes: the n-gram and the graph given, and a seeded RNN-LM of one layer."""
+    from speech2text_amd.model.lm.rnn_lm import RnnLm, RnnLmConfig
+    torch.manual_seed(1000 + V)
+    rnn = RnnLm(config=RnnLmConfig(num_symbols=V, symbol_embedding_dim=16, num_rnn_layer=1)).to(dev).eval()
+    return {"plain": _Kind(), "ngram": _Kind(lm=lm, weight=weight), "bias": _Kind(graph=graph, bias_weight=bias_weight),
+            "ngram_bias": _Kind(lm=lm, weight=weight, graph=graph, bias_weight=bias_weight),
+            "lm": _Kind(rnn=rnn, weight=weight, start=start)}
+
+
+def _cases(dev):
+    """Every plain, n-gram and bias test case as (name, settings, logits, lengths, n-gram, graph): what a case
+    does not bring (the plain cases an n-gram and a graph, the n-gram cases a graph, the bias cases without an
+    LM an n-gram) is estimated on, or cut from, tests/ctc_ngram_cases.py's seeded token text at the case's V."""
+    import ctc_bias_cases as BC
     import ctc_ngram_cases as NC
     import ctc_prefix_cases as PC
+    from speech2text_amd.model.lm.context_graph import ContextGraph
     from speech2text_amd.model.lm.ngram_lm import NgramLm
-    jobs = [(PC.CASES[n], PC.make(n)[:2], None) for n in PC.PLAIN_CASES]
-    jobs += [(NC.CASES[n], NC.make(n), NgramLm.from_arpa(NC.text_of(n), num_classes=NC.CASES[n]["V"]).to(dev))
-             for n in NC.CASES]
-    equal = True
-    for c, (x, lens), lm in jobs:
-        x, lens = x.to(dev), lens.to(dev)
-        T, w = x.shape[1], c.get("weight", 0.0)
-        outs = []
-        for lib in (tree, parent):
-            call, o = lib.one_shot(x, lens, c["beam"], c["topk"], lm, w)
-            call()
-            reset, chunk, so, state = lib.stream(x, c["beam"], c["topk"], T, 1 + c["beam"] * T, lm, w)
-            reset()
+
+    def stand_in_lm(V):
+        return NgramLm.estimate(NC.lm_sequences(V, 120, 1), V, order=2)
+
+    def stand_in_graph(V):
+        return ContextGraph(phrases_of(NC.lm_sequences(V, 120, 1), 3, 5), V, context_score=1.0)
+
+    out = []
+    for n in PC.PLAIN_CASES:
+        c = PC.CASES[n]
+        out.append((n, c, *PC.make(n)[:2], stand_in_lm(c["V"]), stand_in_graph(c["V"])))
+    for n, c in NC.CASES.items():
+        out.append((n, c, *NC.make(n), NgramLm.from_arpa(NC.text_of(n), num_classes=c["V"]), stand_in_graph(c["V"])))
+    for n, c in BC.CASES.items():
+        out.append((n, c, *BC.make(n), BC.model_of(n) if c["order"] else stand_in_lm(c["V"]), BC.graph_of(n)))
+    return [(n, c, x.to(dev), lens.to(dev), lm.to(dev), graph.to(dev)) for n, c, x, lens, lm, graph in out]
+
+
+def _same(xs, ys):
+    """Whether the tensors of xs are those of ys byte for byte."""
+    return all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(xs, ys))
+
+
+def _bits_equal(tree, parent, dev):
+    """Both libraries' twelve search entries on every case, whole and in 7-frame chunks, the chunk entries'
+    state buffers compared byte for byte after every chunk -> (cases, equal, [what differed])."""
+    cases, differ = _cases(dev), []
+    for i, (name, c, x, lens, lm, graph) in enumerate(cases):
+        T, V = x.shape[1], x.shape[2]
+        kinds = _kinds(V, dev, lm, c.get("weight") or 0.5, graph, c.get("bias_weight", 1.0), V - 1 if i % 2 else -1)
+        for fam, k in kinds.items():
+            whole = [lib.one_shot(x, lens, c["beam"], c["topk"], k) for lib in (tree, parent)]
+            for call, _, _ in whole:
+                call()
+            torch.cuda.synchronize()
+            if not _same(whole[0][1].values(), whole[1][1].values()):
+                differ.append(f"{name}:{fam}")
+            streams = [lib.stream(x, c["beam"], c["topk"], T, 1 + c["beam"] * T, k) for lib in (tree, parent)]
+            for reset, _, _, _ in streams:
+                reset()
             for t0 in range(0, T, 7):
                 ch = x[:, t0:t0 + 7].contiguous()
-                chunk(ch, (lens.clamp(max=T) - t0).clamp(0, ch.shape[1]))
-            torch.cuda.synchronize()
-            outs.append(list(o.values()) + list(so.values()) + [state])
-        equal = equal and all(torch.equal(a, b) for a, b in zip(*outs))
-    return len(jobs), equal
+                cl = (lens.clamp(max=T) - t0).clamp(0, ch.shape[1])
+                for _, chunk, _, _ in streams:
+                    chunk(ch, cl)
+                torch.cuda.synchronize()
+                (_, _, oa, sa), (_, _, ob, sb) = streams
+                if not _same([sa, *oa.values()], [sb, *ob.values()]):
+                    differ.append(f"{name}:{fam}_chunk@{t0}")
+                    break
+    return len(cases), not differ, differ
 
 
 def main():
@@ -192,6 +280,7 @@ def main():
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--loop-runs", type=int, default=1)
     ap.add_argument("--parent-lib", default=None, help="another build of libs2t_mi355.so: the parent commit's")
+    ap.add_argument("--label", default=None, help="kept in the JSON line")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ctc_bias.jsonl"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -277,15 +366,20 @@ def main():
     row["chunk_bias_over_plain"] = round(cm["bias"] / cm["plain"], 3)
     row["chunk_ngram_bias_over_ngram"] = round(cm["ngram_bias"] / cm["ngram"], 3)
 
-    # ---- 3. the existing entries against the parent commit's library
+    # ---- 3. every search entry against the parent commit's library, and that library against a copy of itself
     if args.parent_lib:
-        libs = {"tree": _Raw(N.LIB_PATH, N), "parent": _Raw(os.path.abspath(args.parent_lib), N)}
+        with tempfile.TemporaryDirectory() as tmp:
+            again = shutil.copy(os.path.abspath(args.parent_lib), os.path.join(tmp, "libs2t_parent_again.so"))
+            libs = {"tree": _Raw(N.LIB_PATH, N), "parent": _Raw(os.path.abspath(args.parent_lib), N),
+                    "parent_again": _Raw(again, N)}
+        kinds = _kinds(V, dev, ngram, lm_w, graph, bias_w)
         calls, keep = {}, []
         full = torch.full((B,), CHUNK, dtype=torch.int64, device=dev)
-        for who, lib in libs.items():
-            for what, lm in (("plain", None), ("ngram", ngram)):
-                calls[f"{what}_{who}"], o = lib.one_shot(x, lens, BEAM, TOPK, lm, lm_w)
-                reset, chunk, so, state = lib.stream(x, BEAM, TOPK, 1024, 4096, lm, lm_w)
+        for fam in FAMILIES:
+            steps, shared = {}, None
+            for who, lib in libs.items():
+                calls[f"{fam}_{who}"], o, shared = lib.one_shot(x, lens, BEAM, TOPK, kinds[fam], shared)
+                reset, chunk, so, state = lib.stream(x, BEAM, TOPK, 1024, 4096, kinds[fam])
                 keep.append((o, so, state))
                 n = [0]
 
@@ -294,12 +388,19 @@ def main():
                         reset()
                     chunk(pieces[n[0] % len(pieces)], full)
                     n[0] += 1
-                calls[f"{what}_chunk_{who}"] = step
-        row["vs_parent"] = _alternate(calls, 4 * args.runs)
+                steps[f"{fam}_chunk_{who}"] = step
+            calls.update(steps)
+        row["vs_parent"] = _alternate(calls, 4 * args.runs, group=len(libs))
         pm = {k: v["median_ms"] for k, v in row["vs_parent"].items()}
-        row["tree_over_parent"] = {k: round(pm[f"{k}_tree"] / pm[f"{k}_parent"], 4)
-                                   for k in ("plain", "ngram", "plain_chunk", "ngram_chunk")}
-        row["bits_equal_cases"], row["bits_equal"] = _bits_equal(libs["tree"], libs["parent"], dev)
+        figures = [f + c for f in FAMILIES for c in ("", "_chunk")]
+        row["tree_over_parent"] = {k: round(pm[f"{k}_tree"] / pm[f"{k}_parent"], 4) for k in figures}
+        # the rule: the tree's median is at most the larger parent median plus the two parents' difference
+        row["speed_limit_ms"] = {k: round(max(pm[f"{k}_parent"], pm[f"{k}_parent_again"])
+                                          + abs(pm[f"{k}_parent"] - pm[f"{k}_parent_again"]), 4) for k in figures}
+        row["speed_missed"] = [k for k in figures if pm[f"{k}_tree"] > row["speed_limit_ms"][k]]
+        row["bits_equal_cases"], row["bits_equal"], row["bits_differ"] = _bits_equal(libs["tree"], libs["parent"], dev)
+    if args.label:
+        row["label"] = args.label
     line = json.dumps(row)
     print(line, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
