@@ -10,7 +10,7 @@
 //             Linears when there are any) and the row's decision -- greedy: arg-max, first index on
 //             ties, and the reference's bookkeeping; beam: log-softmax, the cutoff_top_k best classes,
 //             then (a workgroup per utterance) candidate ranking, selection and trace-back records
-//             in the orders of csrc/decode_beam.hip, by the functions both share
+//             in the orders of csrc/decode_rnnt.hip, by the functions both share
 //             (csrc/decode_records.h).  Rows that emitted are counted on the device.
 //   predictor for the rows that emitted: LN(embedding[token]); per layer the raw gates
 //             x . x2g^T (+ bias) + h . p2g^T as (16 rows x 16 gate rows) tiles -- a weight matrix is
@@ -25,7 +25,7 @@
 // The same rounds also run a chunk at a time on caller-owned state (s2t_rnnt_*_lstm_chunk, at the
 // end of this file): the whole-utterance calls and the chunk calls enqueue them through the same
 // host functions.  A beam chunk's records become histories and outputs by decode_records.h
-// chunk_histories, the scheme csrc/decode_stream.hip keeps written out.
+// chunk_histories, the scheme csrc/decode_rnnt.hip keeps written out.
 //
 // RNN-LM shallow fusion (s2t_rnnt_beam_lstm_lm): a second recurrent model rides the beam rounds.  Every
 // row also carries the LM's (h, c), q = log_softmax(logits(h_last)) [V] and the sum of the q it was
@@ -1084,7 +1084,7 @@ struct BeamEndArgs {
 };
 
 // grid B: the chunk's records become the beams' new histories and the row's outputs
-// (decode_records.h chunk_histories, the scheme of csrc/decode_stream.hip).  The two history
+// (decode_records.h chunk_histories, the scheme of csrc/decode_rnnt.hip).  The two history
 // buffers swap roles per chunk (the index is the row's, on the device).
 __global__ __launch_bounds__(kThreads) void beam_chunk_end_kernel(BeamEndArgs a) {
   __shared__ int s_trace[kTraceFrames * kMaxBeam], s_anc[kMaxBeam], s_base[kMaxBeam], s_len[kMaxBeam];

@@ -1,5 +1,5 @@
 // What the RNN-T beam searches keep besides a predictor, once for the stateless kernels
-// (decode_search.h, decode_beam.hip, decode_stream.hip) and the lockstep LSTM ones (decode_lstm.hip):
+// (decode_search.h, decode_rnnt.hip) and the lockstep LSTM ones (decode_lstm.hip):
 // the limits, the (parent, class) record, candidate ranking, the trace-back of the best beam, and a
 // chunk's records turned into histories and outputs.  THREADS is a template parameter: the two
 // families launch 512 and 256 (or 64) threads.  Also the Arena that hands out the workspaces and states
@@ -117,7 +117,7 @@ struct ChunkHistoryArgs {
 // the way; a wave per beam then copies the ancestor's old history in front of them.  Then the best
 // beam's (position 0) tokens and frames, and the prefix all live beams share.  All threads call it,
 // with the indices the kernel holds; ONE thread then calls done(out_len, stable_len, overflow), where
-// the caller writes its own header and scalar outputs.  (decode_stream.hip keeps this text written
+// the caller writes its own header and scalar outputs.  (decode_rnnt.hip keeps this text written
 // out: the call cost its 512-thread kernel, which runs at the limit of its scalar registers, time.)
 template <int THREADS, typename Done>
 __device__ __forceinline__ void chunk_histories(int tid, int lane, int wave, const ChunkHistoryArgs& a,

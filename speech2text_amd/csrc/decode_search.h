@@ -1,15 +1,17 @@
 // The walks of the two stateless-predictor RNN-T searches as device functions, so that the
-// whole-utterance kernels (csrc/decode.hip, csrc/decode_beam.hip) and the chunk-carried kernels
-// (csrc/decode_stream.hip) instantiate ONE body each: a search fed its frames in pieces then makes
-// the arithmetic of the search fed them at once, in the same order, and gives the same bits.
+// whole-utterance kernels (csrc/decode.hip, csrc/decode_rnnt.hip) and the chunk-carried kernels
+// (csrc/decode_rnnt.hip) instantiate ONE body each: a
+// search fed its frames in pieces then makes the arithmetic of the search fed them at once, in the
+// same order, and gives the same bits.
 //   greedy_walk  the lattice walk of s2t_rnnt_greedy_stateless over frames [0, Tb) of one row
 //                (256 threads): lm recompute after an emission, arg-max, emit or advance.
-//   beam_walk    phases A-D of s2t_rnnt_beam_stateless (see decode_beam.hip) over frames [0, Tb) of
+//   beam_walk    phases A-D of s2t_rnnt_beam_stateless (see decode_rnnt.hip) over frames [0, Tb) of
 //                one row (8 waves); the (parent, class) record of every kept beam goes to a functor.
 //                Its LM mode kLmNgram adds the back-off n-gram term of ngram_lookup.h to the candidates
 //                (s2t_rnnt_beam_stateless_ngram and its chunk form); kLmNone is the search as it was.
-// Both take the search state by reference and leave it as the next frame needs it.  The limits,
-// the record and candidate ranking are decode_records.h's.
+// Both take the search state by reference and leave it as the next frame needs it, and read the
+// predictor from the two parts of StatelessWeights, the one place that names its fields.  The limits, the record and
+// candidate ranking are decode_records.h's.
 #pragma once
 #include "common.h"
 #include "decode_common.h"
@@ -18,8 +20,49 @@
 
 namespace s2t_dec {
 
+// The stateless predictor and the joiner's activation: the one place that names these fields.  In two parts,
+// because the kernels' argument blocks have always kept them apart (a search's T sits between the pointers and
+// the dimensions, and moving it moves the compiler's scalar loads and, at these kernels' register limits, their
+// schedule); the walks read both parts where they lie, the host holds them as one.
+struct StatelessPointers {
+  const float* emb;                // [num_symbols][E]
+  const float* conv_w;             // [E][ctx]   depthwise, no bias
+  const float* lin_w;              // [D][E]
+  const float* lin_b;              // [D]
+  const float* pre_w;              // [V][D]
+  const float* pre_b;              // [V]
+};
+struct StatelessDims {
+  int V, E, D, ctx, act;
+};
+struct StatelessWeights : StatelessPointers, StatelessDims {};
+
+// the predictor's arguments every search entry has, in the order of its prototype
+inline StatelessWeights stateless_weights(const float* emb, const float* conv_w, const float* lin_w,
+                                          const float* lin_b, const float* pre_w, const float* pre_b, int V, int E,
+                                          int D, int ctx, int act) {
+  StatelessWeights w;
+  w.emb = emb, w.conv_w = conv_w, w.lin_w = lin_w, w.lin_b = lin_b, w.pre_w = pre_w, w.pre_b = pre_b;
+  w.V = V, w.E = E, w.D = D, w.ctx = ctx, w.act = act;
+  return w;
+}
+
+inline bool dims_ok(const StatelessDims& d) {              // (V's upper limit is the caller's)
+  return d.V > 0 && d.E > 0 && d.D > 0 && d.ctx >= 1 && d.ctx <= 64 && d.act >= 0 && d.act <= 1;
+}
+
 // ------------------------------------------------------------------------------------ greedy
 constexpr int kGreedyThreads = 256;
+
+// LDS of a greedy workgroup: e [E], h [D], lm [V], state [ctx]
+inline size_t greedy_lds(const StatelessDims& d) {
+  return sizeof(float) * ((size_t)d.E + d.D + d.V) + sizeof(int) * d.ctx;
+}
+
+// what both greedy entries refuse of their shape (the chunk entry refuses more: decode_rnnt.hip)
+inline bool greedy_ok(int T, const StatelessDims& d, int max_out) {
+  return T > 0 && dims_ok(d) && max_out > 0 && greedy_lds(d) <= 60 * 1024;
+}
 
 // y[r] = w[r] . x + b[r], one wave per row, x in LDS
 __device__ __forceinline__ void gemv_rows(const float* __restrict__ w, const float* __restrict__ bias,
@@ -40,37 +83,35 @@ struct GreedyShared {
   int tok;
 };
 
-// Frames [0, Tb) of amb [Tb][V] from (state, lm, need_lm, n): a.emb .. a.pre_b, a.V, a.E, a.D, a.ctx,
-// a.act, a.max_token_step, a.blank are read from the argument struct; tokens_row holds max_out
-// tokens.  Returns true when the output filled up and the walk stopped inside a frame (the
+// Frames [0, Tb) of amb [Tb][V] from (state, lm, need_lm, n); tokens_row holds max_out tokens.
+// Returns true when the output filled up and the walk stopped inside a frame (the
 // whole-utterance kernel ends there; a stream is inert from there on).  Every frame advance
 // leaves need_lm false and the symbols-on-this-frame counter at 0, so neither is part of what a
 // chunk hands to the next: a walk that starts at a frame boundary starts them as this does.
-template <typename A>
-__device__ __forceinline__ bool greedy_walk(const A& a, GreedyShared& s, const float* __restrict__ amb,
-                                            long Tb, int* state, float* e, float* hvec, float* lm,
-                                            bool& need_lm, long& n, long* __restrict__ tokens_row,
-                                            int max_out) {
+__device__ __forceinline__ bool greedy_walk(const StatelessPointers& p, const StatelessDims& d, int max_token_step, int blank,
+                                            GreedyShared& s, const float* __restrict__ amb, long Tb,
+                                            int* state, float* e, float* hvec, float* lm, bool& need_lm,
+                                            long& n, long* __restrict__ tokens_row, int max_out) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int t = 0, nts = 0;
   while (t < Tb) {
     if (need_lm) {
-      for (int c = tid; c < a.E; c += kGreedyThreads) {
+      for (int c = tid; c < d.E; c += kGreedyThreads) {
         float acc = 0.f;
-        for (int k = 0; k < a.ctx; ++k) acc = fmaf(a.conv_w[c * a.ctx + k], a.emb[(long)state[k] * a.E + c], acc);
+        for (int k = 0; k < d.ctx; ++k) acc = fmaf(p.conv_w[c * d.ctx + k], p.emb[(long)state[k] * d.E + c], acc);
         e[c] = acc;
       }
       __syncthreads();
-      gemv_rows(a.lin_w, a.lin_b, e, a.D, a.E, hvec);
+      gemv_rows(p.lin_w, p.lin_b, e, d.D, d.E, hvec);
       __syncthreads();
-      gemv_rows(a.pre_w, a.pre_b, hvec, a.V, a.D, lm);
+      gemv_rows(p.pre_w, p.pre_b, hvec, d.V, d.D, lm);
       __syncthreads();
       need_lm = false;
     }
-    Top best{S2T_NEG_INF, a.V};
-    for (int c = tid; c < a.V; c += kGreedyThreads) {
-      float v = amb[(long)t * a.V + c] + lm[c];
-      v = a.act == 0 ? fmaxf(v, 0.f) : tanhf(v);
+    Top best{S2T_NEG_INF, d.V};
+    for (int c = tid; c < d.V; c += kGreedyThreads) {
+      float v = amb[(long)t * d.V + c] + lm[c];
+      v = d.act == 0 ? fmaxf(v, 0.f) : tanhf(v);
       best = better(best, Top{v, c});
     }
     best = wave_top(best);
@@ -79,7 +120,7 @@ __device__ __forceinline__ bool greedy_walk(const A& a, GreedyShared& s, const f
     if (tid == 0) s.tok = better(better(s.red[0], s.red[1]), better(s.red[2], s.red[3])).i;
     __syncthreads();
     const int tok = s.tok;
-    if (tok == a.blank || nts > a.max_token_step) {
+    if (tok == blank || nts > max_token_step) {
       ++t;
       nts = 0;
     } else {
@@ -88,8 +129,8 @@ __device__ __forceinline__ bool greedy_walk(const A& a, GreedyShared& s, const f
       ++n;
       __syncthreads();
       if (tid == 0) {
-        for (int k = 0; k + 1 < a.ctx; ++k) state[k] = state[k + 1];
-        state[a.ctx - 1] = tok;
+        for (int k = 0; k + 1 < d.ctx; ++k) state[k] = state[k + 1];
+        state[d.ctx - 1] = tok;
       }
       need_lm = true;
       if (n >= max_out) return true;                 // output buffer full (uniform exit)
@@ -224,37 +265,35 @@ __device__ __forceinline__ void gemv_group(const float* __restrict__ w, const fl
 }
 
 // lm rows of the beams list[0..n) from their predictor states; per beam the arithmetic (and its
-// order) of the greedy kernel's gemv_rows.  Ends with a barrier.  A: a.emb .. a.pre_b, a.V, a.E,
-// a.D, a.ctx.
-template <typename A>
-__device__ void recompute_lm(const A& a, const int* __restrict__ list, int n,
+// order) of the greedy kernel's gemv_rows.  Ends with a barrier.
+__device__ inline void recompute_lm(const StatelessPointers& p, const StatelessDims& d, const int* __restrict__ list, int n,
                              const int* __restrict__ state, const int* __restrict__ slot,
                              float* __restrict__ e, float* __restrict__ h, float* lm) {
   const int tid = threadIdx.x;
   for (int g0 = 0; g0 < n; g0 += kGroup) {
     const int ng = min(kGroup, n - g0);
-    for (int x = tid; x < ng * a.E; x += kThreads) {
-      const int g = x / a.E, c = x - g * a.E;
-      const int* st = state + list[g0 + g] * a.ctx;
+    for (int x = tid; x < ng * d.E; x += kThreads) {
+      const int g = x / d.E, c = x - g * d.E;
+      const int* st = state + list[g0 + g] * d.ctx;
       float acc = 0.f;
-      for (int k0 = 0; k0 < a.ctx; k0 += kCols) {          // (loads first, clamped, as in gemv_group)
+      for (int k0 = 0; k0 < d.ctx; k0 += kCols) {          // (loads first, clamped, as in gemv_group)
         float cw[kCols], ev[kCols];
 #pragma unroll
         for (int q = 0; q < kCols; ++q) {
-          const int k = min(k0 + q, a.ctx - 1);
-          cw[q] = a.conv_w[c * a.ctx + k];
-          ev[q] = a.emb[(long)st[k] * a.E + c];
+          const int k = min(k0 + q, d.ctx - 1);
+          cw[q] = p.conv_w[c * d.ctx + k];
+          ev[q] = p.emb[(long)st[k] * d.E + c];
         }
 #pragma unroll
-        for (int q = 0; q < kCols; ++q) acc = k0 + q < a.ctx ? fmaf(cw[q], ev[q], acc) : acc;
+        for (int q = 0; q < kCols; ++q) acc = k0 + q < d.ctx ? fmaf(cw[q], ev[q], acc) : acc;
       }
-      e[g * a.E + c] = acc;
+      e[g * d.E + c] = acc;
     }
     __syncthreads();
-    gemv_group(a.lin_w, a.lin_b, e, a.D, a.E, ng, [&](int g, int r, float y) { h[g * a.D + r] = y; });
+    gemv_group(p.lin_w, p.lin_b, e, d.D, d.E, ng, [&](int g, int r, float y) { h[g * d.D + r] = y; });
     __syncthreads();
-    gemv_group(a.pre_w, a.pre_b, h, a.V, a.D, ng,
-               [&](int g, int r, float y) { lm[(long)slot[list[g0 + g]] * a.V + r] = y; });
+    gemv_group(p.pre_w, p.pre_b, h, d.V, d.D, ng,
+               [&](int g, int r, float y) { lm[(long)slot[list[g0 + g]] * d.V + r] = y; });
     __syncthreads();
   }
 }
@@ -263,19 +302,19 @@ __device__ void recompute_lm(const A& a, const int* __restrict__ list, int n,
 // [cur], state [cur], their lm rows): phases A-D per frame.  rec(t, position, pack_record(parent,
 // class)) is called by the lane of every kept beam.  On return nb and cur name the beams after the
 // last frame, best first.  CACHE: V <= 64 kRegs, the frame's am is held in registers and the next
-// frame's is fetched a frame ahead.  A: recompute_lm's fields and a.act, a.blank, a.beam, a.topk.
+// frame's is fetched a frame ahead.  c: the search's blank, beam and topk (decode_rnnt.hip BeamHead).
 // LM = kLmNgram (ng, lm_weight given; ng->g and ng->ctx / lm_sum [cur] filled): between A and B a thread
 // per candidate of a class other than blank adds lm_weight * ngram_score(parent's context, class) to
 // the candidate's score, as (beam score + log-probability) + lm_weight * q in fp32, and C hands the
 // kept beams the look-up's context and lm_sum + q; a blank candidate keeps its parent's context and
 // sum.  The cut to top-k, the ranking, the records and D are the same code in both modes.
-template <bool CACHE, int LM = kLmNone, typename A, typename Rec>
-__device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float* __restrict__ amb,
-                                          int Tb, int& nb, int& cur, float* e, float* h, int* state,
-                                          float* lm, Rec rec, RnntNgramShared* ng = nullptr,
-                                          float lm_weight = 0.f) {
+template <bool CACHE, int LM = kLmNone, typename C, typename Rec>
+__device__ __forceinline__ void beam_walk(const StatelessPointers& p, const StatelessDims& d, const C& c, BeamShared& s,
+                                          const float* __restrict__ amb, int Tb, int& nb, int& cur, float* e,
+                                          float* h, int* state, float* lm, Rec rec,
+                                          RnntNgramShared* ng = nullptr, float lm_weight = 0.f) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int V = a.V, K = min(a.topk, V), BS = a.beam;
+  const int V = d.V, K = min(c.topk, V), BS = c.beam;
   float am_cur[kRegs] = {}, am_next[kRegs] = {};
   if (CACHE) {
 #pragma unroll
@@ -300,7 +339,7 @@ __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float
 #pragma unroll
         for (int j = 0; j < kRegs; ++j) {
           const int c = lane + 64 * j;
-          zr[j] = c < V ? activate(am_cur[j] + lmi[min(c, V - 1)], a.act) : S2T_NEG_INF;
+          zr[j] = c < V ? activate(am_cur[j] + lmi[min(c, V - 1)], d.act) : S2T_NEG_INF;
         }
       }
       float pv = 0.f, lse = 0.f, zmax = 0.f;
@@ -315,7 +354,7 @@ __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float
           }
         } else {
           for (int c = lane; c < V; c += 64) {
-            const float z = activate(amt[c] + lmi[c], a.act);
+            const float z = activate(amt[c] + lmi[c], d.act);
             if (r == 0 || after(z, c, pv, pi)) best = better(best, Top{z, c});
           }
         }
@@ -330,14 +369,14 @@ __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float
             for (int j = 0; j < kRegs; ++j)
               if (lane + 64 * j < V) sum += expf(zr[j] - zmax);
           } else {
-            for (int c = lane; c < V; c += 64) sum += expf(activate(amt[c] + lmi[c], a.act) - zmax);
+            for (int c = lane; c < V; c += 64) sum += expf(activate(amt[c] + lmi[c], d.act) - zmax);
           }
           lse = logf(wave_sum(sum));
         }
         if (lane == 0) {
           const bool ok = pi < V;                          // (only a NaN input leaves a round empty)
           s.cscore[i * K + r] = ok ? base + ((pv - zmax) - lse) : S2T_NEG_INF;
-          s.ccls[i * K + r] = ok ? pi : a.blank;
+          s.ccls[i * K + r] = ok ? pi : c.blank;
         }
       }
     }
@@ -347,7 +386,7 @@ __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float
         const int cls = s.ccls[q], pctx = ng->ctx[cur][q / K];
         const float sc = s.cscore[q];
         NgramHit hit{0.f, pctx};                           // blank, or an empty round: no term, no look-up
-        if (cls != a.blank && sc != S2T_NEG_INF) {
+        if (cls != c.blank && sc != S2T_NEG_INF) {
           hit = ngram_score(ng->g, pctx, cls);
           s.cscore[q] = __fadd_rn(sc, __fmul_rn(lm_weight, hit.logp));
         }
@@ -363,28 +402,28 @@ __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float
     // ---- C: the new beams (wave 0, a lane per beam)
     if (wave == 0) {
       const bool live = lane < nnb;
-      int parent = 0, cls = a.blank;
+      int parent = 0, cls = c.blank;
       if (live) {
         const int q = s.pick[lane];
         parent = q / K;
         cls = s.ccls[q];
         s.score[nxt][lane] = s.cscore[q];
-        s.len[nxt][lane] = s.len[cur][parent] + (cls != a.blank ? 1 : 0);
+        s.len[nxt][lane] = s.len[cur][parent] + (cls != c.blank ? 1 : 0);
         if constexpr (LM == kLmNgram) {
           ng->ctx[nxt][lane] = ng->cnext[q];
           ng->lm_sum[nxt][lane] = ng->lm_sum[cur][parent] + ng->cq[q];
         }
         rec(t, lane, pack_record(parent, cls));
-        const int* so = state + (cur * kMaxBeam + parent) * a.ctx;
-        int* sn = state + (nxt * kMaxBeam + lane) * a.ctx;
-        if (cls == a.blank) {
-          for (int k = 0; k < a.ctx; ++k) sn[k] = so[k];
+        const int* so = state + (cur * kMaxBeam + parent) * d.ctx;
+        int* sn = state + (nxt * kMaxBeam + lane) * d.ctx;
+        if (cls == c.blank) {
+          for (int k = 0; k < d.ctx; ++k) sn[k] = so[k];
         } else {
-          for (int k = 0; k + 1 < a.ctx; ++k) sn[k] = so[k + 1];
-          sn[a.ctx - 1] = cls;
+          for (int k = 0; k + 1 < d.ctx; ++k) sn[k] = so[k + 1];
+          sn[d.ctx - 1] = cls;
         }
       }
-      const bool emits = live && cls != a.blank;
+      const bool emits = live && cls != c.blank;
       // lm rows: a blank child keeps its parent's row (a parent has at most one); the emitting
       // beams take the rows that are left, in beam order
       unsigned used = (live && !emits) ? 1u << s.slot[cur][parent] : 0u;
@@ -410,7 +449,7 @@ __device__ __forceinline__ void beam_walk(const A& a, BeamShared& s, const float
     __syncthreads();
     // ---- D: lm of the beams that emitted (at most one symbol per frame per beam)
     const int ne = s.nemit;
-    if (ne > 0) recompute_lm(a, s.emit, ne, state + nxt * kMaxBeam * a.ctx, s.slot[nxt], e, h, lm);
+    if (ne > 0) recompute_lm(p, d, s.emit, ne, state + nxt * kMaxBeam * d.ctx, s.slot[nxt], e, h, lm);
     nb = nnb;
     cur = nxt;
     if (CACHE) {

@@ -7,12 +7,12 @@ The reference decodes one utterance at a time with Python loops over frames (and
 predictor / joiner module calls per lattice move, per beam for the beam search).  Here
 `batch_search` hands the WHOLE batch to one HIP launch: per-frame argmax + repeat/blank collapse
 for CTC (csrc/decode.hip); for RNN-T with the stateless predictor and a projection-free joiner the
-whole greedy lattice walk (csrc/decode.hip) and the whole beam search (csrc/decode_beam.hip) run
+whole greedy lattice walk (csrc/decode.hip) and the whole beam search (csrc/decode_rnnt.hip) run
 on the device, one workgroup per utterance.  With the LSTM predictor (joiner with or without
 output projection: every LSTM YAML of the reference) both searches run on the device in lockstep
 over the batch (csrc/decode_lstm.hip): per round one lattice move of every live row, a predictor
 step for the rows that emitted, no host synchronisation per move.  Both families are also carried
-across chunks of a stream (RnntStreamingSearch, csrc/decode_stream.hip; RnntLstmStreamingSearch,
+across chunks of a stream (RnntStreamingSearch, csrc/decode_rnnt.hip; RnntLstmStreamingSearch,
 csrc/decode_lstm.hip; rnnt_streaming_search picks the class).  Other predictor / joiner
 combinations (the stateless predictor with an out-projection joiner, foreign classes, shapes a
 kernel refuses) keep the module-by-module loop.  RnntBeamDecoding takes an RNN language model
@@ -783,7 +783,7 @@ def rnnt_beam_tokens_from_am(am, lengths, predictor, joiner, beam_size=4, cutoff
     -> (tokens (B,T) int64, frames (B,T) int64, out_len (B) int64, score (B) fp32): the best
     beam's tokens, the frame at which each was emitted, their count and the beam's score.
     Returns None when the kernel does not take the shape (rc -1: the caller runs the module
-    loop).  HIP: decode_beam.hip."""
+    loop).  HIP: decode_rnnt.hip."""
     def plan(am, n):
         B, T, V = am.shape
         nbytes = max(1, N.lib().s2t_rnnt_beam_workspace_bytes(B, T, V, int(beam_size)))   # (the entry refuses, not this)
@@ -800,7 +800,7 @@ def rnnt_beam_ngram_tokens_from_am(am, lengths, predictor, joiner, lm, lm_weight
     the beam's context) more, looked up inside the frame body, and a kept beam carries the context the
     look-up returned.  The search starts in the LM's own start context, so the first token is scored
     too.  -> (tokens, frames, out_len, score, lm_score (B) fp32: the best beam's unweighted LM sum), or
-    None where the entry refuses.  HIP: decode_beam.hip, decode_search.h, ngram_lookup.h."""
+    None where the entry refuses.  HIP: decode_rnnt.hip, decode_search.h, ngram_lookup.h."""
     def plan(am, n):
         B, T, V = am.shape
         _ngram_beside(lm, am, "am")
@@ -833,7 +833,7 @@ class RnntBeamDecoding(_BatchDecoding):
     is first stepped on it.  The LSTM predictor and the stateless predictor (with the project's Joiner
     and an RnnLm) run the fused device search (csrc/decode_lstm.hip); the stateless predictor with a
     projection-free Joiner and an NgramLm (no `lm_start_token`) runs the one-launch search fused with
-    the n-gram (csrc/decode_beam.hip s2t_rnnt_beam_stateless_ngram), the tables following the inputs to
+    the n-gram (csrc/decode_rnnt.hip s2t_rnnt_beam_stateless_ngram), the tables following the inputs to
     their device; everything else, and a shape the kernels refuse, `_module_loop_lm`.
     `beam_tokens` then returns a fifth tensor, the best beam's unweighted LM sum."""
 
@@ -1129,7 +1129,7 @@ class _ChunkCarriedSearch:
 
 
 class RnntStreamingSearch(_ChunkCarriedSearch):
-    """Chunk-carried RNN-T search on the device (csrc/decode_stream.hip): the fused greedy / beam
+    """Chunk-carried RNN-T search on the device (csrc/decode_rnnt.hip): the fused greedy / beam
     search of the stateless predictor and a projection-free joiner, fed `am = joiner._enc_proj(
     encoder_out)` a chunk at a time.  However the frames are cut, the result after a chunk is the
     whole-utterance search's on the frames fed so far, bit for bit (the kernels share their walk).
@@ -1409,7 +1409,7 @@ class RnntStatelessLmStreamingSearch(_ChunkCarriedSearch):
 
 
 class RnntNgramStreamingSearch(RnntStreamingSearch):
-    """RnntStreamingSearch's beam search fused with a back-off n-gram (csrc/decode_stream.hip
+    """RnntStreamingSearch's beam search fused with a back-off n-gram (csrc/decode_rnnt.hip
     s2t_rnnt_beam_stateless_ngram_chunk): the one-workgroup search of the stateless predictor and a
     projection-free Joiner, a look-up per candidate inside the frame body, carried across chunks.
     However the frames are cut, the result after a chunk is rnnt_beam_ngram_tokens_from_am on the frames

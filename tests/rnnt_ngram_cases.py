@@ -1,7 +1,7 @@
 """Seeded cases shared by tests/test_rnnt_ngram_f64.py (CPU), tests/test_gpu_rnnt_ngram.py and
 tests/test_gpu_rnnt_ngram_stream.py (GPU): the one-workgroup RNN-T beam search of the stateless predictor
-fused with a back-off n-gram (csrc/decode_beam.hip s2t_rnnt_beam_stateless_ngram and its chunk-carried
-form in csrc/decode_stream.hip).
+fused with a back-off n-gram (csrc/decode_rnnt.hip s2t_rnnt_beam_stateless_ngram and its chunk-carried
+form).
 
 Test infrastructure (not a test file).  A case is an ARPA text, predictor / joiner weights and am.  The
 text is tests/ctc_ngram_cases.py's lm_text: an order-`order` model estimated on `n_tokens` seeded tokens

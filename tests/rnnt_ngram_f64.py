@@ -1,5 +1,5 @@
 """Plain restatement of the RNN-T beam search of the stateless predictor with back-off n-gram shallow
-fusion (csrc/decode_beam.hip s2t_rnnt_beam_stateless_ngram, csrc/decode_stream.hip
+fusion (csrc/decode_rnnt.hip s2t_rnnt_beam_stateless_ngram and
 s2t_rnnt_beam_stateless_ngram_chunk), keyed by Python token tuples, over a dict-based n-gram: the
 yardstick of tests/test_rnnt_ngram_f64.py, tests/test_gpu_rnnt_ngram.py and
 tests/test_gpu_rnnt_ngram_stream.py.

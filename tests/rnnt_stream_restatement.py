@@ -3,7 +3,7 @@ in chunks: `beam_search_chunk` takes the beam list a previous call returned and 
 chunk, and returns the new list.  Frames are counted from the start of the stream.  The per-frame
 body is beam_search's, statement for statement; tests/test_rnnt_stream_host.py pins the two to each
 other on every stored utterance for several partitions.  Test infrastructure: the answer the
-chunk-carried device search (csrc/decode_stream.hip) is held to for `stable_len`."""
+chunk-carried device search (csrc/decode_rnnt.hip) is held to for `stable_len`."""
 import numpy as np
 
 from rnnt_beam_restatement import PARAM_KEYS, lm_vector, log_softmax

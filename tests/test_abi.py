@@ -72,6 +72,38 @@ def test_ctc_search_size_queries_are_pure_host_functions():
     assert lib.s2t_ctc_prefix_beam_lm_chunk_workspace_bytes(None, 2, 50, 4) == 0
 
 
+def test_rnnt_search_size_queries_are_pure_host_functions():
+    """The four size queries of the one-launch stateless RNN-T searches (csrc/decode_rnnt.hip) at two shapes:
+    literals of the library built from the commit before the queries got one size function, their refusals'
+    zeros, and the one place the two workspace queries have always disagreed: the plain one does not refuse a
+    V or a beam past the search's limits."""
+    lib = _native.lib()
+    B, T, V, ctx, beam, max_tokens = 2, 30, 50, 2, 4, 16
+    assert lib.s2t_rnnt_beam_workspace_bytes(B, T, V, beam) == 2816
+    assert lib.s2t_rnnt_beam_ngram_workspace_bytes(B, T, V, beam) == 2816
+    assert lib.s2t_rnnt_stream_state_bytes(B, V, ctx, beam, max_tokens) == 13312
+    assert lib.s2t_rnnt_stream_state_bytes(B, V, ctx, 0, max_tokens) == 512              # greedy rows
+    assert lib.s2t_rnnt_ngram_stream_state_bytes(B, V, ctx, beam, max_tokens) == 13824   # + contexts and LM sums
+
+    B, T, V, ctx, beam, max_tokens = 3, 50, 500, 5, 16, 1024
+    assert lib.s2t_rnnt_beam_workspace_bytes(B, T, V, beam) == 105728
+    assert lib.s2t_rnnt_beam_ngram_workspace_bytes(B, T, V, beam) == 105728
+    assert lib.s2t_rnnt_stream_state_bytes(B, V, ctx, beam, max_tokens) == 933888
+    assert lib.s2t_rnnt_stream_state_bytes(B, V, ctx, 0, max_tokens) == 6144
+    assert lib.s2t_rnnt_ngram_stream_state_bytes(B, V, ctx, beam, max_tokens) == 934656
+
+    for q in (lib.s2t_rnnt_beam_workspace_bytes, lib.s2t_rnnt_beam_ngram_workspace_bytes):
+        assert [q(0, 30, 50, 4), q(2, 0, 50, 4), q(2, 30, 0, 4), q(2, 30, 50, 0)] == [0, 0, 0, 0]
+    assert lib.s2t_rnnt_beam_workspace_bytes(2, 30, 8193, 4) == 263424                   # (not refused)
+    assert lib.s2t_rnnt_beam_ngram_workspace_bytes(2, 30, 8193, 4) == 0
+    assert lib.s2t_rnnt_beam_workspace_bytes(2, 30, 50, 17) == 11008                     # (not refused)
+    assert lib.s2t_rnnt_beam_ngram_workspace_bytes(2, 30, 50, 17) == 0
+    for q in (lib.s2t_rnnt_stream_state_bytes, lib.s2t_rnnt_ngram_stream_state_bytes):
+        assert [q(0, 50, 2, 4, 16), q(2, 0, 2, 4, 16), q(2, 8193, 2, 4, 16), q(2, 50, 0, 4, 16), q(2, 50, 65, 4, 16),
+                q(2, 50, 2, -1, 16), q(2, 50, 2, 17, 16), q(2, 50, 2, 4, 0)] == [0] * 8
+    assert lib.s2t_rnnt_ngram_stream_state_bytes(2, 50, 2, 0, 16) == 0                   # an n-gram row is a beam row
+
+
 # ------------------------------------------------------------------ structs and constants from the header
 def _c_name(field):
     """The header's name of a parsed field (a Python keyword got a trailing underscore)."""

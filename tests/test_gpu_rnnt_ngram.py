@@ -1,5 +1,5 @@
 """GPU: the one-launch RNN-T beam search of the stateless predictor fused with a back-off n-gram
-(csrc/decode_beam.hip s2t_rnnt_beam_stateless_ngram; the frame body is csrc/decode_search.h beam_walk's
+(csrc/decode_rnnt.hip s2t_rnnt_beam_stateless_ngram; the frame body is csrc/decode_search.h beam_walk's
 n-gram mode, the look-up csrc/ngram_lookup.h) against the float64 restatement of tests/rnnt_ngram_f64.py
 on the seeded cases of tests/rnnt_ngram_cases.py.
 

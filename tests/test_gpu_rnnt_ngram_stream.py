@@ -1,4 +1,4 @@
-"""GPU: the chunk-carried RNN-T beam search fused with a back-off n-gram (csrc/decode_stream.hip
+"""GPU: the chunk-carried RNN-T beam search fused with a back-off n-gram (csrc/decode_rnnt.hip
 s2t_rnnt_beam_stateless_ngram_chunk, model/decoding.py RnntNgramStreamingSearch), the StreamingRecognizer
 graph around it and the RNN-T task's streaming_recognizer with an `lm: {arpa:}` section.
 

@@ -1,4 +1,4 @@
-"""GPU: the chunk-carried RNN-T search (csrc/decode_stream.hip, model/decoding.py
+"""GPU: the chunk-carried RNN-T search (csrc/decode_rnnt.hip, model/decoding.py
 RnntStreamingSearch), the StreamingRecognizer graph around it and PrunedRnntTask.streaming_recognizer.
 
 The yardstick is exact: however [0, L) is cut into chunks, tokens, frames, out_len and score are

@@ -1,5 +1,5 @@
 """RNN-T beam search (reference model/decoding.py:295-435): the fused device search
-(csrc/decode_beam.hip, s2t_rnnt_beam_stateless), RnntBeamDecoding with its module loop,
+(csrc/decode_rnnt.hip, s2t_rnnt_beam_stateless), RnntBeamDecoding with its module loop,
 DecodingFactory and the `rnnt_beam_search` metric.
 
 The answers come from tests/golden/rnnt_beam_ref*.npz (tools/gen_golden.py::gen_rnnt_beam): the

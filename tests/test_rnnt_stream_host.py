@@ -1,4 +1,4 @@
-"""CPU: the host side of the chunk-carried RNN-T search (csrc/decode_stream.hip) -- the size of its
+"""CPU: the host side of the chunk-carried RNN-T search (csrc/decode_rnnt.hip) -- the size of its
 state buffer -- and the test's own yardstick: the chunked float64 restatement
 (tests/rnnt_stream_restatement.py) against the whole-utterance one on every stored utterance."""
 

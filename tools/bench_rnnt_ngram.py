@@ -1,4 +1,4 @@
-"""Time the one-launch RNN-T beam search fused with a back-off n-gram (csrc/decode_beam.hip
+"""Time the one-launch RNN-T beam search fused with a back-off n-gram (csrc/decode_rnnt.hip
 s2t_rnnt_beam_stateless_ngram) next to the plain one-workgroup entry (s2t_rnnt_beam_stateless, one launch),
 the lockstep search with RNN-LM shallow fusion (s2t_rnnt_beam_stateless_lm; the LM at rnn_lm.yaml's
 dimensions) and the n-gram host loop (RnntBeamDecoding._module_loop_lm, once), on the same inputs and in one

@@ -15,7 +15,8 @@ its runs with the spread (min .. max) behind.
   2. chunk        a 16-frame chunk call of the four streaming searches (CtcStreamingSearch,
                   CtcNgramStreamingSearch, CtcBiasStreamingSearch without and with the n-gram), each on a
                   stream of its own that is reset every 32 calls.
-  3. vs_parent    with --parent-lib (another build of libs2t_mi355.so, the parent commit's): the twelve search
+  3. vs_parent    (the machinery is tools/vs_parent.py's)
+                  with --parent-lib (another build of libs2t_mi355.so, the parent commit's): the twelve search
                   entries (s2t_ctc_prefix_beam, _ngram, _bias, _ngram_bias, _lm and their _chunk partners, each
                   with its matching reset) of this build, of the parent's and of the parent's loaded a second
                   time from a byte copy under another name, through plain ctypes handles on the same inputs
@@ -34,10 +35,7 @@ import argparse
 import ctypes
 import json
 import os
-import shutil
-import statistics
 import sys
-import tempfile
 
 import torch
 
@@ -45,6 +43,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from vs_parent import alternate as _alternate, event_ms as _event_ms, same as _same  # noqa: E402
+from vs_parent import speed_rule, stats as _stats, three_libraries  # noqa: E402
 
 BEAM, TOPK, CHUNK = 4, 4, 16
 
@@ -54,38 +55,6 @@ class _Tok:
 
     def decode(self, ids):
         return " ".join(str(int(i)) for i in ids)
-
-
-def _event_ms(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    out = fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1), out
-
-
-def _stats(ms):
-    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4),
-            "runs": len(ms)}
-
-
-def _alternate(calls, runs, warmup=3, group=1):
-    """{name: fn} -> {name: stats}, the calls alternating call by call.  group: the calls are groups of that
-    many in a row (one figure of several libraries), and run r walks every group from its member r % group
-    on, so that each member follows each neighbour equally often."""
-    names = list(calls)
-    for _ in range(warmup):
-        for fn in calls.values():
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in calls}
-    for r in range(runs):
-        for g0 in range(0, len(names), group):
-            for i in range(group):
-                k = names[g0 + (r + i) % group]
-                times[k].append(_event_ms(calls[k])[0])
-    return {k: _stats(v) for k, v in times.items()}
 
 
 def phrases_of(text, n, seed):
@@ -240,11 +209,6 @@ def _cases(dev):
     return [(n, c, x.to(dev), lens.to(dev), lm.to(dev), graph.to(dev)) for n, c, x, lens, lm, graph in out]
 
 
-def _same(xs, ys):
-    """Whether the tensors of xs are those of ys byte for byte."""
-    return all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(xs, ys))
-
-
 def _bits_equal(tree, parent, dev):
     """Both libraries' twelve search entries on every case, whole and in 7-frame chunks, the chunk entries'
     state buffers compared byte for byte after every chunk -> (cases, equal, [what differed])."""
@@ -368,10 +332,7 @@ def main():
 
     # ---- 3. every search entry against the parent commit's library, and that library against a copy of itself
     if args.parent_lib:
-        with tempfile.TemporaryDirectory() as tmp:
-            again = shutil.copy(os.path.abspath(args.parent_lib), os.path.join(tmp, "libs2t_parent_again.so"))
-            libs = {"tree": _Raw(N.LIB_PATH, N), "parent": _Raw(os.path.abspath(args.parent_lib), N),
-                    "parent_again": _Raw(again, N)}
+        libs = three_libraries(N.LIB_PATH, args.parent_lib, lambda path: _Raw(path, N))
         kinds = _kinds(V, dev, ngram, lm_w, graph, bias_w)
         calls, keep = {}, []
         full = torch.full((B,), CHUNK, dtype=torch.int64, device=dev)
@@ -391,13 +352,8 @@ def main():
                 steps[f"{fam}_chunk_{who}"] = step
             calls.update(steps)
         row["vs_parent"] = _alternate(calls, 4 * args.runs, group=len(libs))
-        pm = {k: v["median_ms"] for k, v in row["vs_parent"].items()}
-        figures = [f + c for f in FAMILIES for c in ("", "_chunk")]
-        row["tree_over_parent"] = {k: round(pm[f"{k}_tree"] / pm[f"{k}_parent"], 4) for k in figures}
         # the rule: the tree's median is at most the larger parent median plus the two parents' difference
-        row["speed_limit_ms"] = {k: round(max(pm[f"{k}_parent"], pm[f"{k}_parent_again"])
-                                          + abs(pm[f"{k}_parent"] - pm[f"{k}_parent_again"]), 4) for k in figures}
-        row["speed_missed"] = [k for k in figures if pm[f"{k}_tree"] > row["speed_limit_ms"][k]]
+        speed_rule(row, [f + c for f in FAMILIES for c in ("", "_chunk")])
         row["bits_equal_cases"], row["bits_equal"], row["bits_differ"] = _bits_equal(libs["tree"], libs["parent"], dev)
     if args.label:
         row["label"] = args.label
