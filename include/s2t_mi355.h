@@ -424,21 +424,20 @@ int s2t_linear_wgrad(const float* g, long ldg, const float* a, long lda, int R, 
  * with a plain GEMM; s2t_whiten_apply writes out = g + pg * grad_scale * |g| / (|pg| + 1e-20). */
 int s2t_whiten_metric(float* xtx, float* colsum, long n, int G, int cg, float* cov, float* mean,
                       float* scal, float* host_metric, float* workspace, void* stream);
-/* The round-6 form of the backward: s2t_whiten_prep = s2t_whiten_dcov's dcov / bias, and sums64 = the
+/* The fused form of the backward (shapes the pre-split-weight kernel takes): s2t_whiten_prep = s2t_whiten_dcov's dcov / bias, and sums64 = the
  * [2][64] partial-sum slots of the two norms zeroed -- everything that depends on x only, so it runs in
  * FORWARD on the statistics' stream, followed there by s2t_x3p_split of dcov into a per-site piece
  * buffer.  Backward is then s2t_gemm_x3p_sq (pg = x dcov + bias from dcov's pieces, with ||g||^2 and
  * ||pg||^2 taken in its epilogue: the norms are those of the pg actually computed, as the reference
  * takes them) and s2t_whiten_combine64 (out = g + pg * grad_scale ||g|| / (||pg|| + 1e-20)).
- * Late round 6: pg does not depend on the gradient either -- s2t_gemm_x3p_sq with other == NULL (only
- * ||pg||^2 is taken) runs in FORWARD after the split, on the statistics' stream; backward's chain is
- * s2t_sumsq64 (||g||^2 into row 0 of the same slots) + s2t_whiten_combine64. */
+ * s2t_gemm_x3p_sq: `other` (= g) and `sums` are required (-1).  Where the pre-split kernel refuses the
+ * shape: s2t_whiten_dcov + s2t_gemm_f32_sq + s2t_whiten_combine (sums[2]); where that product's 16-byte
+ * rules refuse as well: a plain product + s2t_whiten_apply, which takes the two norms in a pass of its own. */
 int s2t_whiten_prep(const float* cov, const float* mean, const float* scal, int G, int cg, float* dcov,
                     float* bias, float* sums64, void* stream);
 int s2t_gemm_x3p_sq(const float* A, long lda, const unsigned short* Bp, int N, int K, float* C, long ldc,
                     int M, const float* bias, const float* other, long ld_other, float* sums, int tile,
                     void* stream);
-int s2t_sumsq64(const float* g, long numel, float* sums64, void* stream);
 int s2t_whiten_combine64(const float* g, const float* pg, long numel, float grad_scale,
                          const float* sums64, float* out, void* stream);
 int s2t_whiten_dcov(const float* cov, const float* mean, const float* scal, int G, int cg,
@@ -1671,9 +1670,7 @@ int s2t_predictor_ctx_bwd(const int* tokens, const float* emb, const float* w, c
  *   16-byte aligned (else -2).  tile = 0 (from the shape) | 11 | 12 | 21 | 22: block tile
  *   (64 tm) x (64 tn); + 100 w: w persistent workgroups per CU;
  *   2000 + tm tn: the form that moves the weight pieces global -> LDS directly, + 200 (two-piece
- *   arithmetic only): 32-deep barrier intervals; 3000 + tm tn (22 | 21 | 12), + 200 (22 | 12): the
- *   same form on 8-wave workgroups, block tile (128 tm) x (64 tn), two-piece arithmetic, no Balancer
- *   epilogue (measured, not in the default plan: DESIGN 3i).  -2: a tile code the current
+ *   arithmetic only): 32-deep barrier intervals.  Any other code: -1.  -2: a tile code the current
  *   arithmetic has not. */
 /* ---- the arithmetic of every bf16 matrix-core GEMM of the library (s2t_gemm_x3p*, the weight-gradient /
  * NT / NN / batched kernels of csrc/gemm.hip): pieces per fp32 operand.
@@ -1908,13 +1905,10 @@ typedef struct S2tZipLayerCall {
   int nwh;
   void* lt_ws;
   long lt_ws_bytes;
-  int x3p_tile;                    /* tile code of the Whiten penalty product (s2t_gemm_x3p_sq; 0: from the shape) */
   float x3p_margin;                /* s2t_zl_plan_choose's margin */
-  int whiten_x3p;                  /* Whiten backward: 2 = dcov + its pieces in forward, product on the pre-split-weight kernel (round 6); 0 = the NN kernel, three launches */
-  int conv_w_side, stats_side, wgrad_side;   /* conv parameter gradients / Whiten statistics / weight gradients on the side stream */
-  int whiten_sq;                   /* Whiten's norms in the x dcov product's epilogue (s2t_gemm_f32_sq) */
-  int bal_fwd_side;                /* firing Balancers' column statistics taken in forward on the side stream (round 6) */
-  int whiten_fwd_pg;               /* Whiten's penalty product x dcov taken in forward on the statistics' stream (round 6) */
+  int use_side;                    /* the caller passes a side stream to fwd / bwd: Whiten and firing Balancers' statistics,
+                                      conv parameter gradients and weight gradients run there (the sizing pass has no
+                                      streams and sizes by this) */
 } S2tZipLayerCall;
 long s2t_zip_layer_state_bytes(void);
 long s2t_zip_layer_ws_floats(const S2tZipLayerDesc* desc, const S2tZipLayerCall* call, int backward);

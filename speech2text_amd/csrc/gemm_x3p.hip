@@ -654,14 +654,12 @@ __device__ __forceinline__ unsigned x3p_lds_addr(const void* p) {
 // (1 | 2): with two pieces a 16-deep stage holds only 12 MFMAs per wave (2 x 2 tile) between two
 // barriers; KS = 2 stages 32 k at a time -- the same 24 MFMAs per barrier as the three-piece form,
 // half the barriers, waits and address arithmetic per product.
-// WM: waves along M (2: the 4-wave workgroup, block tile 64 TM x 64 TN; 4: an 8-wave workgroup, block
-// tile 128 TM x 64 TN -- every wave keeps its 32 TM x 32 TN, a weight stage is shared by twice the
-// rows: 0.75 of the global -> LDS bytes per product at TM = TN = 2)
-template <int TM, int TN, int WPC, bool MAP = false, int NP = 3, int KS = 1, bool BAL = false, int WM = 2>
-__global__ __launch_bounds__(128 * WM, WPC * WM / 2) void x3p_dma_kernel(X3P g) {   // (HIP: waves per SIMD)
-  constexpr int NT = 128 * WM, NWV = 2 * WM;        // threads, waves
-  constexpr int BM = 32 * WM * TM, BN = 64 * TN;
-  constexpr int A_SUB = WM * TM * NP * 1024, B_SUB = 2 * TN * NP * 1024;   // one 16-deep sub-stage
+// Workgroup = 4 waves (2 x 2), block tile 64 TM x 64 TN.
+template <int TM, int TN, int WPC, bool MAP = false, int NP = 3, int KS = 1, bool BAL = false>
+__global__ __launch_bounds__(256, WPC) void x3p_dma_kernel(X3P g) {   // (HIP: waves per SIMD)
+  constexpr int NT = 256, NWV = 4;                  // threads, waves
+  constexpr int BM = 64 * TM, BN = 64 * TN;
+  constexpr int A_SUB = 2 * TM * NP * 1024, B_SUB = 2 * TN * NP * 1024;   // one 16-deep sub-stage
   constexpr int A_ST = KS * A_SUB, B_ST = KS * B_SUB, ST = A_ST + B_ST;
   constexpr int NAU = (2 * BM * KS + NT - 1) / NT;  // A units (8 k of one row) per thread and stage
   constexpr int NRUN = 2 * TN * KS * NP;            // B: 1 KB runs (one wave-instruction each) per stage
@@ -917,16 +915,6 @@ void launch_x3p_dma(X3P& g, hipStream_t st) {
     X3P_LAUNCH((x3p_dma_kernel<TM, TN, WPC, false, NP, KS>), grid, 256, 0);
 }
 
-// the 8-wave workgroup (WM = 4): block tile 128 TM x 64 TN, 512 threads
-template <int TM, int TN, int WPC, int NP, int KS>
-void launch_x3p_dma8(X3P& g, hipStream_t st) {
-  g.tiles_m = (g.M + 128 * TM - 1) / (128 * TM);
-  g.tiles_n = (g.N + 64 * TN - 1) / (64 * TN);
-  const int total = g.tiles_m * g.tiles_n;
-  const int grid = std::min(((total + 7) / 8) * 8, 256 * WPC);
-  X3P_LAUNCH((x3p_dma_kernel<TM, TN, WPC, false, NP, KS, false, 4>), grid, 512, 0);
-}
-
 template <int TM, int TN, int WPC, int NP = 3, int KS = 1>
 void launch_x3p_map(X3P& g, hipStream_t st) {
   g.tiles_m = (g.M + 64 * TM - 1) / (64 * TM);
@@ -1063,19 +1051,15 @@ int s2t_gemm_x3p(const float* A, long lda, const unsigned short* Bp, int N, int 
   // tile = 100 wgs + (10 tm + tn): the register-staged form, wgs = persistent workgroups per CU (0 =
   // default); 2000 + 100 ks + tm tn: the LDS-DMA form at its own occupancy, ks = 2: 32-deep barrier
   // intervals (two-piece arithmetic only)
-  // 3000 + 100 ks + tm tn: the LDS-DMA form with 8-wave workgroups (block tile 128 tm x 64 tn; two-piece
-  // arithmetic, no Balancer epilogue)
   const int arith = s2t_gemm_arith();
-  if (tile < 0 || (tile >= 1000 && tile < 2000) || tile >= 4000) return -1;
-  const bool w8 = tile / 1000 == 3;
-  int dma = tile / 1000 == 2 || w8;
+  if (tile < 0 || (tile >= 1000 && tile < 2000) || tile >= 3000) return -1;
+  int dma = tile / 1000 == 2;
   const int wgs = (tile / 100) % 10;
   tile %= 100;
   if ((tile != 0 && tile != 11 && tile != 12 && tile != 21 && tile != 22) || wgs > 8 ||
-      (dma && (tile == 0 || wgs > 2)) || (w8 && (tile == 11 || (wgs != 0 && wgs != 2) || (wgs == 2 && tile == 21))))
+      (dma && (tile == 0 || wgs > 2)))
     return -1;
   if (dma && wgs == 2 && arith != 2) return -2;      // (the plan's candidate list follows the arithmetic)
-  if (w8 && (arith != 2 || g_bal.stats)) return -2;
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if ((K & 7) || (N & 3) || (lda & 3) || (ldc & 3) || !al16(A) || !al16(Bp) || !al16(C) ||
       (bias && !al16(bias)) || (resid && (!al16(resid) || (ldr & 3))) ||
@@ -1107,7 +1091,7 @@ int s2t_gemm_x3p(const float* A, long lda, const unsigned short* Bp, int N, int 
     if (act_src) { g.op[k] = act_src; g.ldop[k] = ld_act; g.role[k++] = 1; }
     if (resid) { g.op[k] = resid; g.ldop[k] = ldr; g.role[k++] = 2; }
     if (resid_b) { g.op[k] = resid_b; g.ldop[k] = ldrb; g.role[k++] = 3; }
-    if (g_sq.sums && g_sq.other) {       // the companion matrix: read for its squares only (role 4)
+    if (g_sq.sums) {                     // the companion matrix: read for its squares only (role 4)
       if (k > 1) return -2;
       g.op[k] = g_sq.other; g.ldop[k] = g_sq.ld; g.role[k++] = 4;
     }
@@ -1137,17 +1121,6 @@ int s2t_gemm_x3p(const float* A, long lda, const unsigned short* Bp, int N, int 
       g_samp.flops += 2.0 * (double)M * N * K;
       ++g_samp.launches;
     }
-  }
-  if (w8) {
-    switch (100 * wgs + tile) {
-      case 22: launch_x3p_dma8<2, 2, 2, 2, 1>(g, st); break;
-      case 21: launch_x3p_dma8<2, 1, 2, 2, 1>(g, st); break;
-      case 12: launch_x3p_dma8<1, 2, 2, 2, 1>(g, st); break;
-      case 222: launch_x3p_dma8<2, 2, 1, 2, 2>(g, st); break;
-      default: launch_x3p_dma8<1, 2, 2, 2, 2>(g, st); break;     // 212
-    }
-    S2T_CHECK_LAUNCH();
-    return 0;
   }
   if (dma && g.bal_stats && arith != 2) dma = 0;    // (three pieces: the Balancer epilogue lives in the register-staged form)
   if (dma && arith == 2 && wgs == 2) {              // 32-deep intervals: 64 / 48 / 48 / 32 KB of LDS
@@ -1353,10 +1326,8 @@ int s2t_balancer_coef(float* bal_stats, int N, long rows, float min_mean, float 
 int s2t_gemm_x3p_sq(const float* A, long lda, const unsigned short* Bp, int N, int K, float* C, long ldc,
                     int M, const float* bias, const float* other, long ld_other, float* sums, int tile,
                     void* stream) {
-  if (!sums) return -1;
-  // other == NULL: only C's squares are taken (sums row 1) -- the form Whiten's forward uses: x dcov does not
-  // depend on the gradient, so it runs where the statistics run; backward adds ||g||^2 with s2t_sumsq64
-  if (other && ((reinterpret_cast<uintptr_t>(other) & 15) || (ld_other & 3) || (long)M * ld_other * 4 >= 0x7FFFFF00L))
+  if (!sums || !other) return -1;
+  if ((reinterpret_cast<uintptr_t>(other) & 15) || (ld_other & 3) || (long)M * ld_other * 4 >= 0x7FFFFF00L)
     return -2;
   g_sq.sums = sums;
   g_sq.other = other;

@@ -99,10 +99,9 @@ struct WStat {
   float *cov, *mean, *scal, *host;
   hipEvent_t ev;
   int G, cg;
-  // round-6 form (whiten_x3p == 2): written in forward on the statistics' stream; sums = [2][64] slots
+  // fused form (pieces != NULL): written in forward on the statistics' stream; sums = [2][64] slots
   float *dcov, *bias, *sums;
   unsigned short* pieces;
-  float* pg;                 // x dcov + bias, taken in forward as well (whiten_fwd_pg), or NULL
 };
 struct FfS { float *h, *a, *y; WStat st; };
 struct SaS { float *v, *o, *y; WStat st; int dv; };
@@ -187,6 +186,8 @@ int fail(int rc, const char* what) {
   } while (0)
 
 inline bool dec(const Ctx& c, int i) { return c.c.dec[i] != 0; }
+// launches that may leave the main chain go to the side stream (the dry run has no streams: see bal_stats_fwd)
+inline bool on_side(const Ctx& c) { return c.c.use_side && c.side; }
 
 // arithmetic class of the Whiten penalty product: statistics (3) on the three-launch form, data
 // gradient (1) on the pre-split-weight kernel (zip_kernels._WHITEN_PG_CLS / _WHITEN_PG2_CLS)
@@ -368,7 +369,7 @@ int whiten_stats(Ctx& c, WStat& s, const float* x, long ldx, long R, int C, int 
   // stream (they depend on x only): backward's chain is the penalty product on the pre-split-weight kernel
   // with the two norms in its epilogue, and the combining pass
   const S2tZlWhScratch* sc0 = wh_scratch(c, C);
-  const bool fused = c.c.whiten_x3p == 2 && C >= 16 && (C & 7) == 0 && s.cg <= 1024 &&
+  const bool fused = C >= 16 && (C & 7) == 0 && s.cg <= 1024 &&
                      R >= 4 && R * C * 4 < 0x7FFFFF00L && R * ldx * 4 < 0x7FFFFF00L && sc0 && sc0->tab;
   s.pieces = nullptr;
   if (fused) {
@@ -377,9 +378,6 @@ int whiten_stats(Ctx& c, WStat& s, const float* x, long ldx, long R, int C, int 
     s.sums = c.ar.alloc(128);
     s.pieces = reinterpret_cast<unsigned short*>(c.ar.alloc((s2t_x3p_plane_elems(C, C) + 1) / 2));
   }
-  // the penalty product itself depends on x only: on the statistics' stream too (backward then adds
-  // ||g||^2 and combines: the product was 35 us per firing Whiten on the data-gradient chain)
-  s.pg = (fused && c.c.whiten_fwd_pg) ? c.ar.alloc(R * C) : nullptr;
   if (c.dry) return 0;
   const S2tZlWhScratch* sc = wh_scratch(c, C);
   if (!sc) return fail(-1, "whiten_stats: no scratch for this channel count");
@@ -388,9 +386,9 @@ int whiten_stats(Ctx& c, WStat& s, const float* x, long ldx, long R, int C, int 
   s.host = pinned_slot();
   s.ev = ring_event();
   if (!s.host || !s.ev) return fail(-1, "whiten_stats: pinned slot / event");
-  const bool on_side = c.c.stats_side && c.side;
-  auto launch = [&c, &s, sc, x, ldx, R, C, groups, on_side]() -> int {
-    hipStream_t q = on_side ? c.side : c.st;
+  const bool side = on_side(c);
+  auto launch = [&c, &s, sc, x, ldx, R, C, groups, side]() -> int {
+    hipStream_t q = side ? c.side : c.st;
     float* xtx = sc->acc;
     float* colsum = sc->acc + (long)C * C;
     RUN(s2t_gemm_xtx(x, ldx, (int)R, C, s.cg, xtx, C, colsum, (void*)q));
@@ -398,20 +396,13 @@ int whiten_stats(Ctx& c, WStat& s, const float* x, long ldx, long R, int C, int 
     if (s.pieces) {
       RUN(s2t_whiten_prep(s.cov, s.mean, s.scal, s.G, s.cg, s.dcov, s.bias, s.sums, (void*)q));
       RUN(s2t_x3p_split(s.dcov, sc->tab, 1, sc->blocks, s.pieces, (void*)q));
-      if (s.pg) {
-        const S2tGemmClass cls(WHITEN_PG2_CLS);
-        const bool two = s2t_gemm_arith_of(WHITEN_PG2_CLS) == 2;
-        const int tile = c.c.x3p_tile ? c.c.x3p_tile : ((C & 127) == 0 ? (two ? 2212 : 312) : (two ? 2221 : 321));
-        const int rc = s2t_gemm_x3p_sq(x, ldx, s.pieces, C, C, s.pg, C, (int)R, s.bias, nullptr, 0, s.sums, tile, (void*)q);
-        if (rc != 0) return fail(rc, "s2t_gemm_x3p_sq(whiten, forward)");
-      }
     }
     // (backward waits for this event on the host before it reads the metric: everything above is then
     //  complete, whichever stream it ran on)
     HIPRUN(hipEventRecord(s.ev, q));
     return 0;
   };
-  return on_side ? side_run(c, launch) : launch();
+  return side ? side_run(c, launch) : launch();
 }
 
 // zip_kernels.whiten_backward: g (R,C) dense -> *out (g itself when the penalty is inactive)
@@ -426,15 +417,6 @@ int whiten_bwd(Ctx& c, int site, const S2tZlWh& w, WStat& s, const float* x, lon
   c.s.wh_active[site] = active ? 1 : 0;
   *out = g;
   if (!active) return 0;
-  if (s.pieces && s.pg && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
-    // pg and ||pg||^2 were taken in forward (the host wait on s.ev above covers them): ||g||^2, then combine
-    float* o = c.ar.alloc(R * C);
-    if (c.dry) return 0;
-    RUN(s2t_sumsq64(g, R * C, s.sums, (void*)c.st));
-    RUN(s2t_whiten_combine64(g, s.pg, R * C, w.grad_scale, s.sums, o, (void*)c.st));
-    *out = o;
-    return 0;
-  }
   if (s.pieces && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
     // (the prep launches were issued on the side stream in forward: the main stream joined it at the
     //  end of that pass, long before this call)
@@ -448,7 +430,7 @@ int whiten_bwd(Ctx& c, int site, const S2tZlWh& w, WStat& s, const float* x, lon
     // block tile by the output width (the plan table has no bucket for these C x C products): 128-wide
     // column tiles where C is a multiple of 128, 64-wide otherwise; the 32-deep LDS-DMA form with two pieces
     const bool two = s2t_gemm_arith_of(WHITEN_PG2_CLS) == 2;
-    const int tile = c.c.x3p_tile ? c.c.x3p_tile : ((C & 127) == 0 ? (two ? 2212 : 312) : (two ? 2221 : 321));
+    const int tile = (C & 127) == 0 ? (two ? 2212 : 312) : (two ? 2221 : 321);
     const int rc = s2t_gemm_x3p_sq(x, ldx, s.pieces, C, C, pg, C, (int)R, s.bias, g, C, s.sums, tile,
                                    (void*)c.st);
     if (rc != 0) return fail(rc, "s2t_gemm_x3p_sq(whiten)");      // (the shape rules were checked in forward)
@@ -463,20 +445,12 @@ int whiten_bwd(Ctx& c, int site, const S2tZlWh& w, WStat& s, const float* x, lon
   float* o = c.ar.alloc(R * C);
   if (c.dry) return 0;
   RUN(s2t_whiten_dcov(s.cov, s.mean, s.scal, s.G, s.cg, dcov, bias, sums, (void*)c.st));
-  // the penalty's product x dcov: class S (statistics)
+  // the penalty's product x dcov: class S (statistics); the two norms of (g, pg) from its own epilogue.
+  // No separate-pass form behind a refusal: x, ldx, C and R passed whiten_stats' check in forward, dcov / bias /
+  // pg / o sit on the arena's 256-byte granules, and a g off 16 bytes is refused by s2t_whiten_apply as well
   const S2tGemmClass cls(WHITEN_PG_CLS);
-  if (c.c.whiten_sq) {               // the two norms of (g, pg) from the product's own epilogue
-    const int rc = s2t_gemm_f32_sq(1, x, ldx, dcov, C, pg, C, (int)R, C, C, bias, g, C, sums, (void*)c.st);
-    if (rc == 0) {
-      RUN(s2t_whiten_combine(g, pg, R * C, w.grad_scale, sums, o, (void*)c.st));
-      *out = o;
-      return 0;
-    }
-    if (rc != -2) return fail(rc, "s2t_gemm_f32_sq(whiten)");
-  }
-  RUN(s2t_gemm_f32(1, x, ldx, dcov, C, pg, C, (int)R, C, C, bias, nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, 0,
-                   (void*)c.st));
-  RUN(s2t_whiten_apply(g, pg, R * C, w.grad_scale, sums, o, (void*)c.st));
+  RUN(s2t_gemm_f32_sq(1, x, ldx, dcov, C, pg, C, (int)R, C, C, bias, g, C, sums, (void*)c.st));
+  RUN(s2t_whiten_combine(g, pg, R * C, w.grad_scale, sums, o, (void*)c.st));
   *out = o;
   return 0;
 }
@@ -524,7 +498,7 @@ int copy2d(Ctx& c, float* dst, long ldd, const float* src, long lds, int cols, l
 int bal_stats_fwd(Ctx& c, int site, const float* x, long ldx, long R, int C, int n = 2048,
                   const S2tZlBal* coef = nullptr) {
   c.s.bst[site] = nullptr;
-  if (!c.c.bal_fwd_side || (!c.dry && !c.side) || C > 1024) return 0;   // (the dry run has no streams: it sizes for the side form)
+  if (!c.c.use_side || (!c.dry && !c.side) || C > 1024) return 0;   // (the dry run has no streams: it sizes for the side form)
   float* st = c.ar.alloc(n);
   c.s.bst[site] = st;
   if (c.dry) return 0;
@@ -845,7 +819,7 @@ int conv_bwd(Ctx& c, int i, int d0, const float* x_in, const float* g, const flo
   float* du = c.ar.alloc(R * 2 * D);
   const long wsn = s2t_zipconv_bwd_workspace_floats(T, B, D, m.K);
   float* ws = c.ar.alloc(wsn);
-  if (c.c.conv_w_side && c.side) {
+  if (on_side(c)) {
     RUN(s2t_zipconv_bwd_data(sv.u, 2 * D, D, c.c.k8, T, B, D, m.K, sv.chunk, m.wc, m.wk, m.bk, m.scale, dy, du,
                              (void*)c.st));
     if (!c.dry)
@@ -1019,7 +993,7 @@ int layer_bwd(Ctx& c, int phase) {
     TRY(lt_matmul(c, 1, dqkp, Dp, R, d.attn_in, e, c.c.gx));
   }
   if (!c.dry && s.nprob > 0) {
-    if (c.c.wgrad_side && c.side) {
+    if (on_side(c)) {
       TRY(side_run(c, [&c, &s]() -> int {
         RUN(s2t_gemm_tn_grouped(s.nprob, s.probs, (void*)c.side));
         return 0;

@@ -372,12 +372,12 @@ class WhitenStats:
                                           ctypes.c_void_p(self.host.data_ptr()), N.fp(ws),
                                           side if side is not None else N.stream()),
                 "s2t_whiten_metric")
-        # The round-6 form of the backward (csrc/zip_layer.hip whiten_stats / whiten_bwd,
-        # include/s2t_mi355.h s2t_whiten_prep): d metric / d cov, its bias row and dcov's bf16 pieces
-        # depend on x only -- taken now, on the statistics' stream
+        # The fused form of the backward (csrc/zip_layer.hip whiten_stats / whiten_bwd,
+        # include/s2t_mi355.h s2t_whiten_prep), where the pre-split-weight kernel takes the shape:
+        # d metric / d cov, its bias row and dcov's bf16 pieces depend on x only -- taken now, on the
+        # statistics' stream
         self.pieces = None
-        self.pg = None
-        ent = planes.adhoc_entry(C, C, 1, dev) if (_WHITEN_X3P == 2 and _tn_ok(xf) and C % 8 == 0
+        ent = planes.adhoc_entry(C, C, 1, dev) if (_tn_ok(xf) and C % 8 == 0
                                                     and cg <= 1024 and n >= 4
                                                     and n * max(C, xf.stride(0)) * 4 < 0x7FFFFF00) else None
         if ent is not None:
@@ -392,25 +392,12 @@ class WhitenStats:
             N.PROF[0] and N.profile_note("s2t_x3p_split", 4.0 * C * C + 2.0 * self.pieces.numel())
             N.check(N.lib().s2t_x3p_split(self.dcov.data_ptr(), ent[0].data_ptr(), 1, ent[2],
                                           self.pieces.data_ptr(), q), "s2t_x3p_split")
-            if _WHITEN_FWD_PG:
-                # the penalty product x dcov + bias depends on x only as well: here, with ||pg||^2 from its
-                # epilogue (csrc/zip_layer.hip whiten_stats makes the same calls); backward adds ||g||^2
-                self.pg = torch.empty((n, C), dtype=torch.float32, device=dev)
-                N.PROF[0] and N.profile_note("s2t_gemm_x3p_sq", 4.0 * (xf.numel() + self.pg.numel()) + 6.0 * C * C,
-                                             2.0 * n * C * C)
-                two = gemm_arith(_WHITEN_PG2_CLS) == 2
-                tile = X3P["tile"] or ((2212 if two else 312) if C % 128 == 0 else (2221 if two else 321))
-                with gemm_class(_WHITEN_PG2_CLS):
-                    rc = N.lib().s2t_gemm_x3p_sq(N.raw(xf, torch.float32), xf.stride(0),
-                                                 ctypes.c_void_p(self.pieces.data_ptr()), C, C, N.fp(self.pg), C, n,
-                                                 N.fp(self.bias), None, 0, N.fp(self.sums), tile, q)
-                N.check(rc, "s2t_gemm_x3p_sq(forward)")
         if side is not None:
             # the side stream may still be reading x / writing the statistics when this object (or
             # a float() temporary of x) dies -- e.g. a forward under train() with no backward: the
             # caching allocator must not hand the memory to main-stream work before the join
             _Side.keep.append((xf, self.cov, self.mean, self.scal) +
-                              ((self.dcov, self.bias, self.sums, self.pieces, self.pg) if self.pieces is not None else ()))
+                              ((self.dcov, self.bias, self.sums, self.pieces) if self.pieces is not None else ()))
         self.event = torch.cuda.Event()
         if side is not None:
             self.event.record(N._launch_stream((side,)))
@@ -423,21 +410,6 @@ class WhitenStats:
         return float(self.host[0])
 
 
-# (round 5: off -- the NN kernel that takes the two norms in its epilogue (below) beats the bf16x3
-# product + a separate norm pass also for the 31 680-row activations: 37.61 against 37.72 ms/step)
-# (round 6: 2 = dcov and its pieces taken in forward on the statistics' stream, backward = the penalty
-# product on the pre-split-weight kernel with the two norms in its epilogue + the combining pass; 0 = the
-# three-launch form on the NN kernel -- also what shapes outside the pre-split kernel's rules take)
-_WHITEN_X3P = 2
-# the norms of (g, x dcov) taken in the product's epilogue (s2t_gemm_f32_sq) instead of by a pass over both
-_WHITEN_SQ = True
-# the penalty product x dcov itself in forward, on the statistics' stream (late round 6; parity-tested).  OFF:
-# measured 33.49 / 33.46 / 33.12 against 32.78 / 32.79 / 32.63 ms per step with the product in backward -- a
-# GEMM with a 48-64 KB / 130-200 register footprint on the side stream costs forward's own GEMMs more than
-# the 25 us per firing Whiten it takes off backward's chain
-_WHITEN_FWD_PG = False
-
-
 _WHITEN_PG_CLS = 3    # class of the penalty product, three-launch form (csrc/zip_layer.hip whiten_bwd): statistics
 _WHITEN_PG2_CLS = 1   # ... on the pre-split-weight kernel (round-6 form): data gradient
 
@@ -445,45 +417,39 @@ _WHITEN_PG2_CLS = 1   # ... on the pre-split-weight kernel (round-6 form): data 
 def whiten_backward(x, g, stats, limit, grad_scale):
     """Closed form of reference scaling.py:949-1028.  Returns (grad, penalty_was_active).
     d metric/d x = 2 (x - mean) dcov  (the centring's own Jacobian vanishes because the centred
-    columns sum to zero), i.e. ONE GEMM with a bias row; the norm ratio and the final axpy are
-    two more launches."""
+    columns sum to zero), i.e. ONE GEMM with a bias row, the norm ratio and the final axpy.
+    Three forms, by the shape (the same rules as csrc/zip_layer.hip whiten_bwd): fused -- dcov's
+    pieces were taken in forward, the product on the pre-split-weight kernel with the two norms in
+    its epilogue, and the combining pass; sq -- where that kernel refuses the shape: dcov, the NN
+    kernel with the norms in its epilogue, the combining pass; pass -- where the NN kernel's 16-byte
+    rules refuse as well: the library's product and a norm pass of its own before the update."""
     if not (stats.metric() >= limit):
         return g, False
     shp = x.shape
     C = shp[-1]
     G, cg = stats.num_groups, stats.cg
     dev = x.device
-    if getattr(stats, "pieces", None) is not None:
-        xf = x.reshape(-1, C)
-        g2 = g.contiguous().float()
-        if stats.pg is not None and g2.data_ptr() % 16 == 0:
-            # the product and ||pg||^2 were taken in forward (stats.metric() waited for their stream)
-            out = torch.empty_like(g2)
-            N.PROF[0] and N.profile_note("s2t_sumsq64", 4.0 * g2.numel())
-            N.check(N.lib().s2t_sumsq64(N.fp(g2), g2.numel(), N.fp(stats.sums), N.stream()), "s2t_sumsq64")
-            N.PROF[0] and N.profile_note("s2t_whiten_combine64", 12.0 * g2.numel())
-            N.check(N.lib().s2t_whiten_combine64(N.fp(g2), N.fp(stats.pg), g2.numel(), float(grad_scale),
-                                                 N.fp(stats.sums), N.fp(out), N.stream()), "s2t_whiten_combine64")
-            return out.view(shp), True
-        if xf.dtype is torch.float32 and xf.stride(1) == 1 and g2.data_ptr() % 16 == 0:
-            out = torch.empty_like(g2)
-            pg = torch.empty_like(g2)
-            N.PROF[0] and N.profile_note("s2t_gemm_x3p_sq", 4.0 * (xf.numel() + 2 * g2.numel()) + 6.0 * C * C,
-                                         2.0 * xf.shape[0] * C * C)
-            # (class and block tile as csrc/zip_layer.hip whiten_bwd: a data-gradient-like product, two
-            #  pieces by default; 128-wide column tiles where C is a multiple of 128, 64-wide otherwise)
-            two = gemm_arith(_WHITEN_PG2_CLS) == 2
-            tile = X3P["tile"] or ((2212 if two else 312) if C % 128 == 0 else (2221 if two else 321))
-            with gemm_class(_WHITEN_PG2_CLS):
-                rc = N.lib().s2t_gemm_x3p_sq(N.raw(xf, torch.float32), xf.stride(0),
-                                             ctypes.c_void_p(stats.pieces.data_ptr()), C, C, N.fp(pg), C,
-                                             xf.shape[0], N.fp(stats.bias), N.fp(g2), C, N.fp(stats.sums),
-                                             tile, N.stream())
-            N.check(rc, "s2t_gemm_x3p_sq")
-            N.PROF[0] and N.profile_note("s2t_whiten_combine64", 12.0 * g2.numel())
-            N.check(N.lib().s2t_whiten_combine64(N.fp(g2), N.fp(pg), g2.numel(), float(grad_scale),
-                                                 N.fp(stats.sums), N.fp(out), N.stream()), "s2t_whiten_combine64")
-            return out.view(shp), True
+    xf = x.reshape(-1, C)
+    g2 = g.contiguous().float()
+    if stats.pieces is not None and xf.dtype is torch.float32 and xf.stride(1) == 1 and g2.data_ptr() % 16 == 0:
+        out = torch.empty_like(g2)
+        pg = torch.empty_like(g2)
+        N.PROF[0] and N.profile_note("s2t_gemm_x3p_sq", 4.0 * (xf.numel() + 2 * g2.numel()) + 6.0 * C * C,
+                                     2.0 * xf.shape[0] * C * C)
+        # (class and block tile as csrc/zip_layer.hip whiten_bwd: a data-gradient-like product, two
+        #  pieces by default; 128-wide column tiles where C is a multiple of 128, 64-wide otherwise)
+        two = gemm_arith(_WHITEN_PG2_CLS) == 2
+        tile = (2212 if two else 312) if C % 128 == 0 else (2221 if two else 321)
+        with gemm_class(_WHITEN_PG2_CLS):
+            rc = N.lib().s2t_gemm_x3p_sq(N.raw(xf, torch.float32), xf.stride(0),
+                                         ctypes.c_void_p(stats.pieces.data_ptr()), C, C, N.fp(pg), C,
+                                         xf.shape[0], N.fp(stats.bias), N.fp(g2), C, N.fp(stats.sums),
+                                         tile, N.stream())
+        N.check(rc, "s2t_gemm_x3p_sq")
+        N.PROF[0] and N.profile_note("s2t_whiten_combine64", 12.0 * g2.numel())
+        N.check(N.lib().s2t_whiten_combine64(N.fp(g2), N.fp(pg), g2.numel(), float(grad_scale),
+                                             N.fp(stats.sums), N.fp(out), N.stream()), "s2t_whiten_combine64")
+        return out.view(shp), True
     dcov = torch.empty((C, C), dtype=torch.float32, device=dev)
     bias = torch.empty((C,), dtype=torch.float32, device=dev)
     sums = torch.empty((2,), dtype=torch.float32, device=dev)
@@ -491,44 +457,32 @@ def whiten_backward(x, g, stats, limit, grad_scale):
     N.check(N.lib().s2t_whiten_dcov(N.fp(stats.cov), N.fp(stats.mean), N.fp(stats.scal), G, cg,
                                     N.fp(dcov), N.fp(bias), N.fp(sums), N.stream()),
             "s2t_whiten_dcov")
-    xf = x.reshape(-1, C)
     if xf.dtype != torch.float32:
         xf = xf.float()
-    pg = None
-    g2 = g.contiguous().float()
     if g2.data_ptr() % 16:
         g2 = g2.clone()
     out = torch.empty_like(g2)
-    with gemm_class(_WHITEN_PG_CLS):               # (the penalty's product x dcov: a statistic)
-        return _whiten_penalty(xf, g2, dcov, bias, sums, pg, out, C, shp, grad_scale, dev)
-
-
-def _whiten_penalty(xf, g2, dcov, bias, sums, pg, out, C, shp, grad_scale, dev):
-    if pg is None:
-        # (our NN kernel with the bias in its epilogue: the same calls csrc/zip_layer.hip makes);
-        # first the form that takes the two norms of (g, pg) while pg leaves the accumulators
+    rc = -2
+    if xf.stride(1) == 1:
+        # (our NN kernel with the bias in its epilogue, taking the two norms of (g, pg) while pg leaves
+        #  the accumulators: the same calls csrc/zip_layer.hip makes; the penalty's product is a statistic)
         pg = torch.empty((xf.shape[0], C), dtype=torch.float32, device=dev)
-        if _WHITEN_SQ and xf.stride(1) == 1:
-            N.PROF[0] and N.profile_note("s2t_gemm_f32_sq", 4.0 * (xf.numel() + 2 * pg.numel() + C * C),
-                                         2.0 * xf.shape[0] * C * C)
+        N.PROF[0] and N.profile_note("s2t_gemm_f32_sq", 4.0 * (xf.numel() + 2 * pg.numel() + C * C),
+                                     2.0 * xf.shape[0] * C * C)
+        with gemm_class(_WHITEN_PG_CLS):
             rc = N.lib().s2t_gemm_f32_sq(1, N.raw(xf, torch.float32), xf.stride(0), N.fp(dcov), C, N.fp(pg), C,
                                          xf.shape[0], C, C, N.fp(bias), N.fp(g2.view(-1, C)), C, N.fp(sums),
                                          N.stream())
-            if rc == 0:
-                N.PROF[0] and N.profile_note("s2t_whiten_combine", 12.0 * g2.numel())
-                N.check(N.lib().s2t_whiten_combine(N.fp(g2), N.fp(pg), g2.numel(), float(grad_scale),
-                                                   N.fp(sums), N.fp(out), N.stream()), "s2t_whiten_combine")
-                return out.view(shp), True
-            if rc != -2:
-                N.check(rc, "s2t_gemm_f32_sq(whiten)")
-        N.PROF[0] and N.profile_note("s2t_gemm_f32", 4.0 * (xf.numel() + pg.numel() + C * C), 2.0 * xf.shape[0] * C * C)
-        rc = N.lib().s2t_gemm_f32(1, N.raw(xf, torch.float32), xf.stride(0), N.fp(dcov), C, N.fp(pg), C,
-                                  xf.shape[0], C, C, N.fp(bias), None, 0, None, 0, 0, 0, 0, None, 0,
-                                  N.stream()) if xf.stride(1) == 1 else -2
-        if rc == -2:
-            pg = torch.addmm(bias, xf, dcov)
-        else:
-            N.check(rc, "s2t_gemm_f32(whiten)")
+    if rc == 0:
+        N.PROF[0] and N.profile_note("s2t_whiten_combine", 12.0 * g2.numel())
+        N.check(N.lib().s2t_whiten_combine(N.fp(g2), N.fp(pg), g2.numel(), float(grad_scale),
+                                           N.fp(sums), N.fp(out), N.stream()), "s2t_whiten_combine")
+        return out.view(shp), True
+    if rc != -2:
+        N.check(rc, "s2t_gemm_f32_sq(whiten)")
+    # (what s2t_gemm_f32_sq refuses, s2t_gemm_f32 refuses too: its rules are a subset, and dcov, bias,
+    #  pg and g2 above are 16-byte aligned with rows of C floats)
+    pg = torch.addmm(bias, xf, dcov)
     N.PROF[0] and N.profile_note("s2t_whiten_apply", 12.0 * g2.numel())
     N.check(N.lib().s2t_whiten_apply(N.fp(g2), N.fp(pg), g2.numel(), float(grad_scale), N.fp(sums),
                                      N.fp(out), N.stream()), "s2t_whiten_apply")
@@ -1430,7 +1384,7 @@ def _rows(t):
 
 
 _ACTK = {None: 0, "swoosh_l": 1, "swoosh_r": 2, "add": 3}
-X3P = {"calls": 0, "tile": 0, "margin": 0.97}
+X3P = {"calls": 0, "margin": 0.97}
 
 
 def _vp(t):
@@ -1484,14 +1438,14 @@ def _x3p_launch(mode, x2, w2, bias, resid2, act_src, act_kind, act2, tile, resid
                 "s2t_balancer_stats")
         rc = N.lib().s2t_gemm_x3p_bal(_vp(x2), x2.stride(0), ctypes.c_void_p(pp), cols, inner, _vp(out), cols, R,
                                       _vp(resid2), 0 if resid2 is None else resid2.stride(0), _vp(act_src),
-                                      act_src.stride(0), _ACTK[act_kind], tile or X3P["tile"], _vp(stats),
+                                      act_src.stride(0), _ACTK[act_kind], tile, _vp(stats),
                                       bal[0], bal[1], bal[2], bal[3], bal[4], N.stream())
     else:
         rc = N.lib().s2t_gemm_x3p(_vp(x2), x2.stride(0), ctypes.c_void_p(pp), cols, inner, _vp(out), cols, R,
                                   _vp(bias), _vp(resid2), 0 if resid2 is None else resid2.stride(0),
                                   _vp(act_src), 0 if act_src is None else act_src.stride(0),
                                   _ACTK[act_kind], _vp(out2), cols, _ACTK[act2], _vp(resid_b),
-                                  0 if resid_b is None else resid_b.stride(0), tile or X3P["tile"],
+                                  0 if resid_b is None else resid_b.stride(0), tile,
                                   N.stream())
     if rc == -2:
         return None

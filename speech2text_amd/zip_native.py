@@ -274,15 +274,8 @@ def _fill_call(L, T, B, D, chunk_size, x0, pos2, a8, k8, fm, dec, dev):
     c.nwh = len(cs)
     ws = zk._lt_workspace(dev)
     c.lt_ws, c.lt_ws_bytes = ws.data_ptr(), ws.numel()
-    c.x3p_tile, c.x3p_margin = int(zk.X3P["tile"]), float(zk.X3P["margin"])
-    c.whiten_x3p = int(zk._WHITEN_X3P)
-    side = zk._Side.enabled
-    c.conv_w_side = int(side)
-    c.stats_side = int(side)
-    c.wgrad_side = int(side)
-    c.whiten_sq = int(zk._WHITEN_SQ)
-    c.bal_fwd_side = int(side)       # Balancer column statistics in forward, side stream
-    c.whiten_fwd_pg = int(zk._WHITEN_FWD_PG)
+    c.x3p_margin = float(zk.X3P["margin"])
+    c.use_side = int(zk._Side.enabled)
     return c
 
 
@@ -334,8 +327,7 @@ class _NativeLayerFn(torch.autograd.Function):
                                        N.stream(), _side_handle())
         if rc != 0:
             _err(rc, "s2t_zip_layer_fwd")
-        if call.bal_fwd_side or (call.stats_side and (d.k_wh or d.ff1[1] or d.na[1] or d.na[2] or d.sa1 or d.cv1[2]
-                                                      or d.ff2[1] or d.sa2 or d.cv2[2] or d.ff3[1] or d.wh_out)):
+        if call.use_side:
             # the side stream may still be reading the workspace / the output when this object dies
             # without a backward pass (a forward under train()): keep them until the join
             zk._Side.keep.append((wsf, x11, x0))

@@ -33,8 +33,7 @@ RUNS = dict(
     test_whiten_metric_vs_float64=("wm", ("s2t_whiten_metric",)),
     test_whiten_metric_after_the_xtx_product=("wx", ("s2t_whiten_metric",)),
     test_whiten_dcov_and_prep_vs_float64=("wd", ("s2t_whiten_dcov", "s2t_whiten_prep")),
-    test_whiten_streams_vs_float64=("wa", ("s2t_sumsq64", "s2t_whiten_combine64", "s2t_whiten_apply",
-                                           "s2t_whiten_combine")),
+    test_whiten_streams_vs_float64=("wa", ("s2t_whiten_combine64", "s2t_whiten_apply", "s2t_whiten_combine")),
     test_limit_param_grad_is_bit_exact=("lp", ("s2t_limit_param_grad",)))
 HELPERS = dict(test_attention_weights_vs_float64=("_fw_run",), test_attention_penalty_flag=("_fw_run",),
                test_attention_backward_vs_float64=("_bw_run",), test_whiten_metric_vs_float64=("_metric",),
@@ -388,26 +387,24 @@ def test_whiten_dcov_and_prep_vs_float64(dev, name):
 # ------------------------------------------------------------------ Whiten streams, limit_param_grad
 @pytest.mark.parametrize("name", COVER["wa"])
 def test_whiten_streams_vs_float64(dev, name):
-    """s2t_sumsq64 into N(0,1) slots (the increment, summed over the 64 slots); s2t_whiten_combine64 on clean
-    slots; s2t_whiten_apply (its own sums pass) and s2t_whiten_combine on those sums."""
+    """s2t_whiten_combine64 on the yardstick's two sums (as float32, in one slot of each row of the [2][64]
+    slots, the others zero); s2t_whiten_apply (its own sums pass) and s2t_whiten_combine on those sums."""
     _, lib, st = env()
     c, t = ZA.CASES[name], ZA.make(name)
     n, gs = c["n"], ZA.GRAD_SCALE
     g, pg = _in(dev, t["g"]), _in(dev, t["pg"])
-    pre = Buf(dev, 128, src=t["pre64"])
-    clean = Buf(dev, 128, src=torch.zeros(128))
-    for s in (pre, clean):
-        assert lib.s2t_sumsq64(ptr(g), n, ptr(s), st) == 0
-        assert lib.s2t_sumsq64(ptr(pg), n, s.t[64:].data_ptr(), st) == 0
+    ref = ZA.reference(name)
+    s64 = torch.zeros(128)
+    s64[5], s64[64 + 41] = float(ref["ssg"]), float(ref["sspg"])
+    clean = Buf(dev, 128, src=s64)
     o64, oa, oc, sums = Buf(dev, n), Buf(dev, n), Buf(dev, n), Buf(dev, 2, src=torch.zeros(2))
     assert lib.s2t_whiten_combine64(ptr(g), ptr(pg), n, gs, ptr(clean), ptr(o64), st) == 0
     assert lib.s2t_whiten_apply(ptr(g), ptr(pg), n, gs, ptr(sums), ptr(oa), st) == 0
     assert lib.s2t_whiten_combine(ptr(g), ptr(pg), n, gs, ptr(sums), ptr(oc), st) == 0
     torch.cuda.synchronize()
-    for what, o in (("sums64", pre), ("sums64 (clean)", clean), ("combine64", o64), ("apply", oa), ("combine", oc), ("sums", sums)):
+    for what, o in (("sums64", clean), ("combine64", o64), ("apply", oa), ("combine", oc), ("sums", sums)):
         o.intact(f"{name} {what}")
-    inc = (pre.t.double().cpu() - t["pre64"].double()).view(2, 64).sum(1)
-    _hold(name, dict(ssg=inc[0:1], sspg=inc[1:2]))
+    assert torch.equal(clean.t.cpu(), s64), f"{name}: combine64 wrote to its sums"
     _hold(name, dict(ssg=sums.t[0:1], sspg=sums.t[1:2], out=oa.t))
     _hold(name, dict(out=o64.t))
     assert torch.equal(oa.t, oc.t), f"{name}: combine differs from apply on the same sums"
@@ -431,7 +428,6 @@ def test_whiten_streams_refuse_misaligned_operands(dev):
     out = Buf(dev, n)
     assert lib.s2t_whiten_combine(ptr(al), ptr(al), n, 0.05, None, ptr(out), st) == -1
     assert lib.s2t_whiten_combine64(ptr(al), ptr(al), n, 0.05, None, ptr(out), st) == -1
-    assert lib.s2t_sumsq64(ptr(mis), n, ptr(s64), st) == -1
     torch.cuda.synchronize()
     out.untouched("NULL sums")
     assert not bool(sums.t.any()) and not bool(s64.t.any())

@@ -502,26 +502,27 @@ def test_downsample_and_upsampled_bypass_vs_torch(dev, T, B, C, ds):
     torch.testing.assert_close(s_g.grad.cpu().double(), s_r.grad, atol=1e-3, rtol=1e-4)
 
 
-@pytest.mark.parametrize("R,C,G", [(700, 192, 1), (1000, 128, 4), (333, 96, 2), (2000, 512, 1),
-                                   (500, 256, 8), (260, 64, 1)])
-@pytest.mark.parametrize("form", ["fwdpg", "fused", "sq", "pass"])
+_WHITEN_COMBINER = {"fused": "s2t_whiten_combine64", "sq": "s2t_whiten_combine", "pass": "s2t_whiten_apply"}
+
+
+@pytest.mark.parametrize("form,R,C,G", [("fused", 700, 192, 1), ("fused", 1000, 128, 4), ("fused", 333, 96, 2),
+                                        ("fused", 2000, 512, 1), ("fused", 500, 256, 8), ("fused", 260, 64, 1),
+                                        ("sq", 333, 100, 2), ("sq", 260, 12, 1),
+                                        ("pass", 300, 66, 2), ("pass", 260, 65, 1)])
 def test_whiten_backward_vs_oracle(dev, monkeypatch, R, C, G, form):
     """Whiten (scaling.py:949-1095): x^T x comes from the symmetric TN GEMM (only the 64x64 tiles on /
     above the diagonal with same-group pairs; cg = 48 straddles tiles), the metric kernel mirrors
-    them; the backward term against the oracle's autograd-in-backward statement.  form: "fwdpg" (built
-    late in round 6, measured slower in the step, off by default) = the penalty product x dcov taken in FORWARD too, with ||pg||^2 from its epilogue; backward =
-    s2t_sumsq64 (||g||^2) + s2t_whiten_combine64; "fused" = dcov
-    and its bf16 pieces taken in forward, backward = the penalty product on the pre-split-weight kernel
-    with the two norms in its epilogue + the combining pass (s2t_whiten_prep / s2t_gemm_x3p_sq /
-    s2t_whiten_combine64: the default);
-    "sq" = the norms of (g, x dcov) from the NN product's epilogue (s2t_gemm_f32_sq); "pass" = from a
-    pass over both tensors."""
+    them; the backward term against the oracle's autograd-in-backward statement.  The shape selects
+    the form, and the test states which one ran from the launches it sees: "fused" (C % 8 == 0,
+    C >= 16) = dcov and its bf16 pieces taken in forward, backward = the penalty product on the
+    pre-split-weight kernel with the two norms in its epilogue + the combining pass (s2t_whiten_prep /
+    s2t_gemm_x3p_sq / s2t_whiten_combine64); "sq" (that kernel refuses; C % 4 == 0) = the norms of
+    (g, x dcov) from the NN product's epilogue (s2t_gemm_f32_sq, s2t_whiten_combine); "pass"
+    (C % 4 != 0: the 16-byte rules refuse too, and the statistics take the unaligned path) = the
+    library's product and the norms from a pass over both tensors (s2t_whiten_apply)."""
     import random
-    from speech2text_amd import zip_kernels as zkm
+    from speech2text_amd import _native as Nt
     from speech2text_amd.model.layer.scaling import Whiten
-    monkeypatch.setattr(zkm, "_WHITEN_X3P", 2 if form in ("fused", "fwdpg") else 0)
-    monkeypatch.setattr(zkm, "_WHITEN_FWD_PG", form == "fwdpg")
-    monkeypatch.setattr(zkm, "_WHITEN_SQ", form == "sq")
     fused0 = int(N_lib().s2t_gemm_x3p_calls())
     torch.manual_seed(R + C)
     x = torch.randn(R, C) @ (torch.eye(C) + 0.3 * torch.randn(C, C))      # correlated channels
@@ -535,14 +536,20 @@ def test_whiten_backward_vs_oracle(dev, monkeypatch, R, C, G, form):
     for _ in range(2):                       # twice: the shared accumulator must come back clean
         xg = x.to(dev).requires_grad_(True)
         y = m(xg)
-        (y * w.to(dev)).sum().backward()
+        loss = (y * w.to(dev)).sum()
+        Nt.profile_begin("*")
+        try:
+            loss.backward()
+        finally:
+            seen = Nt.profile_end()
+        assert [k for k in _WHITEN_COMBINER.values() if k in seen] == [_WHITEN_COMBINER[form]], sorted(seen)
         assert torch.equal(y.detach().cpu(), x)
         d = (xg.grad.cpu() - w).numpy()                                    # the shaping term only
         r = (xc.grad - w).numpy()
         assert np.abs(r).max() > 0, "metric below the limit: the test would be vacuous"
         np.testing.assert_allclose(d, r, atol=2e-3 * np.abs(r).max(), rtol=2e-3)
-    # the fused form really ran (C % 8 == 0 everywhere here): one s2t_gemm_x3p launch per backward
-    assert int(N_lib().s2t_gemm_x3p_calls()) - fused0 == (2 if form in ("fused", "fwdpg") else 0)
+    # the fused form is one s2t_gemm_x3p launch per backward; the other two make none
+    assert int(N_lib().s2t_gemm_x3p_calls()) - fused0 == (2 if form == "fused" else 0)
 
 
 def test_whiten_backward_rank_one_input_stays_finite(dev, monkeypatch):
