@@ -1222,6 +1222,73 @@ int s2t_ctc_prefix_beam_ngram_bias_chunk(const S2tNgramLmDesc* lm, const S2tCont
                                          long* tokens, long* out_len, float* score, float* lm_score,
                                          float* bias_score, long* stable_len, int* overflow, void* stream);
 
+/* ---- Hotword biasing of the one-workgroup RNN-T beam search (csrc/decode_search.h beam_walk's bias mode;
+ * csrc/decode_rnnt.hip).  s2t_rnnt_beam_stateless / s2t_rnnt_beam_stateless_ngram with the bias term of the
+ * block above (its bias_sum, final_bias, tables and THE BIAS STATEMENT, not restated here), still ONE launch
+ * and the partner's workspace (s2t_rnnt_beam_workspace_bytes / s2t_rnnt_beam_ngram_workspace_bytes).  A live
+ * beam also carries a graph state and an unweighted bias_sum; the fresh beam starts in the root with 0.  The
+ * candidate of class c != blank whose round is not empty takes (d, next) = bias(parent's state, c), looked up
+ * by the thread that ran the n-gram's look-up, after it, and scores
+ *   ((beam score + lp) + lm_weight * q) + bias_weight * d        (fp32, in this order; no LM: no LM term);
+ * a kept beam takes next and bias_sum + d.  A blank candidate and an empty round run no look-up and keep the
+ * parent's state and sum.  The cut to cutoff_top_k, the ranking, the records and the predictor are the
+ * partner's; equal hypotheses are not merged, so no candidate lands on a live beam.
+ * FINALISATION: when an entry writes its outputs it reports the live beam with the largest
+ * score + bias_weight * ctx_final[state] (fp32), ties to the lower position.  score [B] is that value,
+ * bias_score [B] that beam's bias_sum + ctx_final[state], lm_score [B] that beam's own lm_sum, tokens, frames
+ * and out_len that beam's.  It touches the outputs only.  A zero-length utterance: no tokens, all scores 0.
+ * With bias_weight = 0, and with a graph of no phrases at any weight, tokens, frames, out_len, score and
+ * lm_score are the partner entry's bit for bit.
+ * Refused (-1, before any launch and without following a device pointer): what the partner entry refuses, the
+ * graph's limits above, graph.V != V, bias_weight not finite, bias_score NULL. */
+int s2t_rnnt_beam_stateless_bias(const S2tContextGraphDesc* graph, const float* am, const long* lengths,
+                                 const float* emb, const float* conv_w, const float* lin_w, const float* lin_b,
+                                 const float* pre_w, const float* pre_b, int B, int T, int V, int E, int D,
+                                 int ctx, int act, int blank, int beam_size, int cutoff_top_k, float bias_weight,
+                                 void* workspace, long* tokens, long* frames, long* out_len, float* score,
+                                 float* bias_score, void* stream);
+int s2t_rnnt_beam_stateless_ngram_bias(const S2tNgramLmDesc* lm, const S2tContextGraphDesc* graph,
+                                       const float* am, const long* lengths, const float* emb,
+                                       const float* conv_w, const float* lin_w, const float* lin_b,
+                                       const float* pre_w, const float* pre_b, int B, int T, int V, int E, int D,
+                                       int ctx, int act, int blank, int beam_size, int cutoff_top_k,
+                                       float lm_weight, int start_ctx, float bias_weight, void* workspace,
+                                       long* tokens, long* frames, long* out_len, float* score, float* lm_score,
+                                       float* bias_score, void* stream);
+/* The two entries above fed their frames in pieces: s2t_rnnt_beam_stateless_chunk's /
+ * s2t_rnnt_beam_stateless_ngram_chunk's contract word for word, ONE launch per call.  Nothing of the
+ * finalisation is stored: stable_len, overflow, the header, the histories and the carried beams with their order
+ * are what the partner computes, so for ANY cut, while overflow[b] == 0, a chunk call's outputs are the
+ * one-shot entry's on the frames fed so far bit for bit, bias_score included.
+ * state: the plain (s2t_rnnt_stream_state_bytes) or n-gram (s2t_rnnt_ngram_stream_state_bytes) beam row
+ * first, byte for byte, followed, 256-byte aligned, by bstate [beam_size] int32, the beams' graph states, and
+ * bsum [beam_size] fp32, padded to a multiple of 256; size 0 for what the partner's query refuses and for
+ * beam_size 0 (there is no greedy form).  The resets are their partners', -1 as well for beam_size 0; a reset
+ * row starts in the root with bias_sum 0.  A chunk call clamps the graph states it loads into [0, num_ctx).
+ * The graph must not change between the chunks of a live stream. */
+long s2t_rnnt_bias_stream_state_bytes(int B, int V, int ctx, int beam_size, int max_tokens);
+int s2t_rnnt_bias_stream_reset(void* state, const int* rows, int B, int V, int ctx, int beam_size,
+                               int max_tokens, int blank, void* stream);
+int s2t_rnnt_beam_stateless_bias_chunk(const S2tContextGraphDesc* graph, const float* am, const long* chunk_len,
+                                       const float* emb, const float* conv_w, const float* lin_w,
+                                       const float* lin_b, const float* pre_w, const float* pre_b, int B, int Tc,
+                                       int V, int E, int D, int ctx, int act, int blank, int beam_size,
+                                       int cutoff_top_k, float bias_weight, int max_tokens, void* state,
+                                       long* tokens, long* frames, long* out_len, float* score, float* bias_score,
+                                       long* stable_len, int* overflow, void* stream);
+long s2t_rnnt_ngram_bias_stream_state_bytes(int B, int V, int ctx, int beam_size, int max_tokens);
+int s2t_rnnt_ngram_bias_stream_reset(void* state, const int* rows, int B, int V, int ctx, int beam_size,
+                                     int max_tokens, int blank, int start_ctx, void* stream);
+int s2t_rnnt_beam_stateless_ngram_bias_chunk(const S2tNgramLmDesc* lm, const S2tContextGraphDesc* graph,
+                                             const float* am, const long* chunk_len, const float* emb,
+                                             const float* conv_w, const float* lin_w, const float* lin_b,
+                                             const float* pre_w, const float* pre_b, int B, int Tc, int V, int E,
+                                             int D, int ctx, int act, int blank, int beam_size, int cutoff_top_k,
+                                             float lm_weight, float bias_weight, int max_tokens, void* state,
+                                             long* tokens, long* frames, long* out_len, float* score,
+                                             float* lm_score, float* bias_score, long* stable_len, int* overflow,
+                                             void* stream);
+
 /* ---- chunk-carried (streaming) RNN-T search with the LSTM predictor: the two searches above fed
  * their frames in pieces (csrc/decode_lstm.hip).  A round's launches ARE the whole-utterance calls'
  * (one text, the same arguments), and a row's arithmetic does not depend on the rows that share its

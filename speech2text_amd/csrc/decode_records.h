@@ -71,13 +71,14 @@ __device__ __forceinline__ void rank_candidates(const float* cscore, int nc, int
 // The best beam is position 0 after the last frame: its n tokens and the frames they were emitted
 // at, from the records rec [Tb][beam].  They are staged in blocks of kTraceFrames through trace (LDS,
 // kTraceFrames * kMaxBeam ints); thread 0 walks them and hands the count of tokens still to be found
-// to every thread through *left_slot (LDS): the walk ends at the block of the first token.
+// to every thread through *left_slot (LDS): the walk ends at the block of the first token.  pos0: the
+// position the walk starts at, for a search that reports another beam (the hotword finalisation).
 template <int THREADS>
 __device__ __forceinline__ void trace_best(const int* __restrict__ rec, int Tb, int beam, int blank, int n,
                                            int* trace, int* left_slot, long* __restrict__ tokens,
-                                           long* __restrict__ frames) {
+                                           long* __restrict__ frames, int pos0 = 0) {
   const int tid = threadIdx.x;
-  int pos = 0, left = n;                                   // tokens still to be found
+  int pos = pos0, left = n;                                // tokens still to be found
   for (int tend = Tb; tend > 0 && left > 0; tend -= kTraceFrames) {
     const int t0 = max(0, tend - kTraceFrames);
     for (int x = tid; x < (tend - t0) * beam; x += THREADS) trace[x] = rec[(long)t0 * beam + x];

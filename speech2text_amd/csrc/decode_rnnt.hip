@@ -21,6 +21,10 @@
 // carries the context id and the unweighted sum of the look-ups.  lm [beam_size][V] lives in LDS when it fits
 // and in the workspace / the state row (L2 resident) when not.  Whole utterance: after the last frame the best
 // beam (position 0) is traced back through the records (decode_records.h trace_best).
+// In the hotword mode (BIAS; without an LM or with the n-gram) the same thread adds bias_weight x the context
+// graph's look-up behind the LM term, C carries the graph state and the unweighted sum, and when an entry writes
+// its outputs it reports the live beam that is best once the loan of an unfinished match is taken back
+// (decode_search.h bias_pick): outputs only, nothing of the pick is stored or carried.
 //
 // Chunk-carried: the same walks fed their frames in pieces, so for any cut of [0, L) into chunks the result
 // is the whole-utterance search's on the concatenated am, bit for bit; what is added is what is carried.
@@ -31,6 +35,7 @@
 //           | lm [beam][V] | records [256][beam] | token histories [2][beam][max_tokens]
 //           | frame histories [2][beam][max_tokens]
 //   n-gram  the beam row, every offset unchanged | ctx [beam] int32 | lm_sum [beam] fp32
+//   bias    the beam or the n-gram row, byte for byte | bstate [beam] int32 | bsum [beam] fp32
 // The lm rows are PERSISTED, not recomputed on entry: a chunk then starts with beam V floats from
 // HBM instead of up to four passes over the predictor's weights, and when the rows do not fit the LDS the
 // search works on them in place.  Only a reset row has no lm yet (reset takes no weights): its first chunk
@@ -68,8 +73,9 @@ bool row_ok(int V, int ctx, int beam, int max_tokens) {
 }
 
 // o_ng given: the n-gram beam row, which is the plain beam row, every offset unchanged, followed by ctx [beam]
-// int32, the beams' n-gram context ids, and lm_sum [beam] fp32
-Layout layout(int V, int ctx, int beam, int max_tokens, long* o_ng = nullptr) {
+// int32, the beams' n-gram context ids, and lm_sum [beam] fp32.  o_bias given: that row (plain or n-gram),
+// byte for byte, followed by bstate [beam] int32, the beams' hotword graph states, and bsum [beam] fp32
+Layout layout(int V, int ctx, int beam, int max_tokens, long* o_ng = nullptr, long* o_bias = nullptr) {
   Layout l{};
   if (beam == 0) {                 // greedy
     l.pstate = 16;
@@ -87,24 +93,32 @@ Layout layout(int V, int ctx, int beam, int max_tokens, long* o_ng = nullptr) {
     *o_ng = l.stride;
     l.stride = (long)align256(l.stride + (sizeof(int) + sizeof(float)) * (size_t)beam);
   }
+  if (o_bias) {
+    *o_bias = l.stride;
+    l.stride = (long)align256(l.stride + (sizeof(int) + sizeof(float)) * (size_t)beam);
+  }
   return l;
 }
 
-// B rows of state: behind s2t_rnnt_stream_state_bytes and s2t_rnnt_ngram_stream_state_bytes
-long state_bytes(int B, int V, int ctx, int beam, int max_tokens, bool ngram) {
-  if (B <= 0 || !row_ok(V, ctx, beam, max_tokens) || (ngram && beam < 1)) return 0;
-  long o_ng;
-  return (long)B * layout(V, ctx, beam, max_tokens, ngram ? &o_ng : nullptr).stride;
+// B rows of state: behind the four s2t_rnnt_*stream_state_bytes
+long state_bytes(int B, int V, int ctx, int beam, int max_tokens, bool ngram, bool bias = false) {
+  if (B <= 0 || !row_ok(V, ctx, beam, max_tokens) || ((ngram || bias) && beam < 1)) return 0;
+  long o_ng, o_bias;
+  return (long)B * layout(V, ctx, beam, max_tokens, ngram ? &o_ng : nullptr, bias ? &o_bias : nullptr).stride;
 }
 
 // the whole-utterance beam search's workspace: records [B][T][beam] | lm_spill [B][beam][V]
 size_t records_bytes(int B, int T, int beam) { return align256(sizeof(int) * (size_t)B * T * beam); }
 
 // ------------------------------------------------------------------------------------ reset
-// o_ng != 0: an n-gram beam row, whose one beam starts in the context start_ctx with no LM sum
+// o_ng != 0: an n-gram beam row, whose one beam starts in the context start_ctx with no LM sum.  One text for
+// both kernels: without a tail the plain / n-gram reset with the arguments it has always had, with o_bias as
+// its tail the reset of a hotword row (beam >= 1), whose one beam also starts in the graph's root with bias_sum 0.
+template <typename... Tail>
 __global__ __launch_bounds__(64) void rnnt_stream_reset_kernel(char* state, const int* __restrict__ rows,
                                                                long stride, long pstate, int beam,
-                                                               int ctx, int blank, long o_ng, int start_ctx) {
+                                                               int ctx, int blank, long o_ng, int start_ctx,
+                                                               Tail... o_bias) {
   const int b = blockIdx.x, tid = threadIdx.x;
   if (rows && rows[b] == 0) return;
   char* row = state + (long)b * stride;
@@ -121,23 +135,33 @@ __global__ __launch_bounds__(64) void rnnt_stream_reset_kernel(char* state, cons
         reinterpret_cast<int*>(row + o_ng)[0] = start_ctx;
         reinterpret_cast<float*>(row + o_ng)[beam] = 0.f;
       }
+      if constexpr (sizeof...(Tail) == 1) {
+        const long at = (o_bias, ...);
+        reinterpret_cast<int*>(row + at)[0] = 0;
+        reinterpret_cast<float*>(row + at)[beam] = 0.f;
+      }
     }
   }
   int* ps = reinterpret_cast<int*>(row + pstate);          // init state + the blank start token
   if (tid < ctx) ps[tid] = blank;
 }
 
-// Both resets.  ngram: an n-gram row, which is a beam row; its start_ctx is tested from below alone, because a
-// reset sees no tables (the chunk kernel clamps what it loads).
+// All four resets.  ngram: an n-gram row, which is a beam row; its start_ctx is tested from below alone, because a
+// reset sees no tables (the chunk kernel clamps what it loads).  bias: a hotword row, which is a beam row too.
 int rnnt_reset(void* state, const int* rows, int B, int V, int ctx, int beam, int max_tokens, int blank, bool ngram,
-               int start_ctx, void* stream) {
+               int start_ctx, void* stream, bool bias = false) {
   if (B <= 0) return 0;
-  if (!state || !row_ok(V, ctx, beam, max_tokens) || blank < 0 || blank >= V || (ngram && (beam < 1 || start_ctx < 0)))
+  if (!state || !row_ok(V, ctx, beam, max_tokens) || blank < 0 || blank >= V ||
+      (ngram && (beam < 1 || start_ctx < 0)) || (bias && beam < 1))
     return -1;
-  long o_ng = 0;
-  const Layout l = layout(V, ctx, beam, max_tokens, ngram ? &o_ng : nullptr);
-  hipLaunchKernelGGL(rnnt_stream_reset_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, static_cast<char*>(state),
-                     rows, l.stride, l.pstate, beam, ctx, blank, o_ng, start_ctx);
+  long o_ng = 0, o_bias = 0;
+  const Layout l = layout(V, ctx, beam, max_tokens, ngram ? &o_ng : nullptr, bias ? &o_bias : nullptr);
+  if (bias)
+    hipLaunchKernelGGL(rnnt_stream_reset_kernel<long>, dim3(B), dim3(64), 0, (hipStream_t)stream,
+                       static_cast<char*>(state), rows, l.stride, l.pstate, beam, ctx, blank, o_ng, start_ctx, o_bias);
+  else
+    hipLaunchKernelGGL(rnnt_stream_reset_kernel<>, dim3(B), dim3(64), 0, (hipStream_t)stream, static_cast<char*>(state),
+                       rows, l.stride, l.pstate, beam, ctx, blank, o_ng, start_ctx);
   S2T_CHECK_LAUNCH();
   return 0;
 }
@@ -243,22 +267,39 @@ struct BeamNgramChunkPart {
   float* lm_score;        // [B]
 };
 
-template <int LM, bool CHUNK>
+struct BeamBiasPart {              // the hotword mode's (decode_search.h beam_walk), behind every other part
+  NgramTables graph;
+  const float* ctx_final; // [num_ctx]
+  float bias_weight;
+  float* bias_score;      // [B]
+};
+struct BeamBiasChunkPart {
+  long o_bias;            // bstate [beam] int32 | bsum [beam] fp32 inside a row of state
+};
+
+template <int LM, bool CHUNK, bool BIAS = false>
 struct BeamArgs : BeamHead,
                   std::conditional_t<CHUNK, BeamChunkPart, BeamWholePart>,
                   BeamOutputs,
                   std::conditional_t<CHUNK, BeamChunkOutputs, NoPart<0>>,
                   std::conditional_t<LM == kLmNgram, std::conditional_t<CHUNK, BeamNgramChunkPart, BeamNgramWholePart>,
-                                     NoPart<1>> {};
+                                     NoPart<1>>,
+                  std::conditional_t<BIAS, BeamBiasPart, NoPart<2>>,
+                  std::conditional_t<BIAS && CHUNK, BeamBiasChunkPart, NoPart<3>> {};
 
-template <bool CACHE, int LM>
-__global__ __launch_bounds__(kThreads) void rnnt_beam_kernel(BeamArgs<LM, false> a) {
+template <bool CACHE, int LM, bool BIAS = false>
+__global__ __launch_bounds__(kThreads) void rnnt_beam_kernel(BeamArgs<LM, false, BIAS> a) {
   extern __shared__ float sm[];
   __shared__ BeamShared s;
   RnntNgramShared* ng = nullptr;
   if constexpr (LM == kLmNgram) {
     __shared__ RnntNgramShared s_ng;
     ng = &s_ng;
+  }
+  RnntBiasShared* bs = nullptr;
+  if constexpr (BIAS) {
+    __shared__ RnntBiasShared s_bias;
+    bs = &s_bias;
   }
 
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -275,6 +316,7 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_kernel(BeamArgs<LM, false>
       a.out_len[b] = 0;
       a.score[b] = 0.f;
       if constexpr (LM == kLmNgram) a.lm_score[b] = 0.f;
+      if constexpr (BIAS) a.bias_score[b] = 0.f;
     }
     return;
   }
@@ -293,6 +335,12 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_kernel(BeamArgs<LM, false>
       ng->ctx[0][0] = a.start_ctx;
       ng->lm_sum[0][0] = 0.f;
     }
+    if constexpr (BIAS) {                                  // the graph's root, no bias sum
+      bs->g = a.graph;
+      bs->final = a.ctx_final;
+      bs->bstate[0][0] = 0;
+      bs->bsum[0][0] = 0.f;
+    }
   }
   __syncthreads();
   recompute_lm(a.p, a.d, s.emit, 1, state, s.slot[0], e, h, lm);
@@ -300,10 +348,29 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_kernel(BeamArgs<LM, false>
   float lm_weight = 0.f;
   if constexpr (LM == kLmNgram) lm_weight = a.lm_weight;
   // phases A-D per frame: shared with the chunk-carried kernel (decode_search.h)
-  beam_walk<CACHE, LM>(a.p, a.d, a, s, amb, Tb, nb, cur, e, h, state, lm,
-                       [&](int t, int pos, int r) { rec[(long)t * BS + pos] = r; }, ng, lm_weight);
+  if constexpr (BIAS)
+    beam_walk<CACHE, LM, true>(a.p, a.d, a, s, amb, Tb, nb, cur, e, h, state, lm,
+                               [&](int t, int pos, int r) { rec[(long)t * BS + pos] = r; }, ng, lm_weight, bs,
+                               a.bias_weight);
+  else
+    beam_walk<CACHE, LM>(a.p, a.d, a, s, amb, Tb, nb, cur, e, h, state, lm,
+                         [&](int t, int pos, int r) { rec[(long)t * BS + pos] = r; }, ng, lm_weight);
 
   // ---- the best beam is position 0: trace its (parent, class) records back
+  if constexpr (BIAS) {            // ... the finalisation's pick with hotwords: outputs only, nothing is stored
+    float top;
+    const int pos = bias_pick(*bs, s.score[cur], cur, nb, a.bias_weight, &top);
+    const int n = s.len[cur][pos];
+    if (tid == 0) {
+      a.out_len[b] = n;
+      a.score[b] = top;
+      if constexpr (LM == kLmNgram) a.lm_score[b] = ng->lm_sum[cur][pos];
+      a.bias_score[b] = bs->bsum[cur][pos] + bs->final[bs->bstate[cur][pos]];
+    }
+    trace_best<kThreads>(rec, Tb, BS, a.blank, n, s.trace, &s.nemit, a.tokens + (long)b * a.T,
+                         a.frames + (long)b * a.T, pos);
+    return;
+  }
   const int n = s.len[cur][0];
   if (tid == 0) {
     a.out_len[b] = n;
@@ -317,8 +384,8 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_kernel(BeamArgs<LM, false>
 // The chunk-carried form: it loads the carried beams where the kernel above starts one, and ends as the file
 // header says.  A text of its own: folded into the kernel above behind `if constexpr`, in every order of
 // statements tried, its instantiations lost the unrolled copies of lm and two registers.
-template <bool CACHE, int LM>
-__global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamArgs<LM, true> a) {
+template <bool CACHE, int LM, bool BIAS = false>
+__global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamArgs<LM, true, BIAS> a) {
   extern __shared__ float sm[];
   __shared__ BeamShared s;
   __shared__ int s_anc[kMaxBeam], s_base[kMaxBeam];
@@ -326,6 +393,11 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamArgs<LM, 
   if constexpr (LM == kLmNgram) {
     __shared__ RnntNgramShared s_ng;
     ng = &s_ng;
+  }
+  RnntBiasShared* bs = nullptr;
+  if constexpr (BIAS) {
+    __shared__ RnntBiasShared s_bias;
+    bs = &s_bias;
   }
 
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -369,10 +441,27 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamArgs<LM, 
     }
     if (tid == 0) ng->g = a.g;
   }
+  if constexpr (BIAS) {
+    const int* g_bstate = reinterpret_cast<const int*>(row + a.o_bias);
+    if (tid < nb0) {                                       // (clamped: the look-up and ctx_final index with it)
+      bs->bstate[0][tid] = ngram_clamp(g_bstate[tid], a.graph.num_ctx);
+      bs->bsum[0][tid] = reinterpret_cast<const float*>(g_bstate + BS)[tid];
+    }
+    if (tid == 0) {
+      bs->g = a.graph;
+      bs->final = a.ctx_final;
+    }
+  }
   __syncthreads();
   if (!lm_valid) recompute_lm(a.p, a.d, s.emit, 1, state, s.slot[0], e, h, lm);   // (a reset row: one beam)
   int nb = nb0, cur = 0;
-  if constexpr (LM == kLmNgram)
+  if constexpr (BIAS) {
+    float lm_weight = 0.f;
+    if constexpr (LM == kLmNgram) lm_weight = a.lm_weight;
+    beam_walk<CACHE, LM, true>(a.p, a.d, a, s, a.am + (long)b * a.T * V, Tb, nb, cur, e, h, state, lm,
+                               [&](int t, int pos, int r) { rec[t * BS + pos] = r; }, ng, lm_weight, bs,
+                               a.bias_weight);
+  } else if constexpr (LM == kLmNgram)
     beam_walk<CACHE, kLmNgram>(a.p, a.d, a, s, a.am + (long)b * a.T * V, Tb, nb, cur, e, h, state, lm,
                                [&](int t, int pos, int r) { rec[t * BS + pos] = r; }, ng, a.lm_weight);
   else
@@ -388,6 +477,11 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamArgs<LM, 
       int* g_ctx = reinterpret_cast<int*>(row + a.o_ng);
       g_ctx[tid] = ng->ctx[cur][tid];
       reinterpret_cast<float*>(g_ctx + BS)[tid] = ng->lm_sum[cur][tid];
+    }
+    if constexpr (BIAS) {
+      int* g_bstate = reinterpret_cast<int*>(row + a.o_bias);
+      g_bstate[tid] = bs->bstate[cur][tid];
+      reinterpret_cast<float*>(g_bstate + BS)[tid] = bs->bsum[cur][tid];
     }
   }
   for (int x = tid; x < nb * a.d.ctx; x += kThreads) g_state[x] = state[cur * kMaxBeam * a.d.ctx + x];
@@ -437,9 +531,20 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamArgs<LM, 
 
   // ---- outputs: the best beam (position 0), and the prefix all live beams share
   const int n0 = s.len[cur][0], m0 = min(n0, MT);
-  for (int p = tid; p < m0; p += kThreads) {
-    a.tokens[(long)b * MT + p] = ntok[p];
-    a.frames[(long)b * MT + p] = nfrm[p];
+  int rpos = 0, rlen = m0;         // with hotwords the finalisation's pick is reported: outputs only, the
+  float rtop = 0.f;                // header, stable_len, overflow and what is carried stay position 0's
+  if constexpr (BIAS) {
+    rpos = bias_pick(*bs, s.score[cur], cur, nb, a.bias_weight, &rtop);
+    rlen = min(s.len[cur][rpos], MT);
+    for (int p = tid; p < rlen; p += kThreads) {
+      a.tokens[(long)b * MT + p] = ntok[(long)rpos * MT + p];
+      a.frames[(long)b * MT + p] = nfrm[(long)rpos * MT + p];
+    }
+  } else {
+    for (int p = tid; p < m0; p += kThreads) {
+      a.tokens[(long)b * MT + p] = ntok[p];
+      a.frames[(long)b * MT + p] = nfrm[p];
+    }
   }
   if (wave == 0) {
     int shortest = m0, longest = n0;
@@ -461,9 +566,16 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamArgs<LM, 
     for (int o = 32; o > 0; o >>= 1) stable = min(stable, __shfl_xor(stable, o, 64));
     if (lane == 0) {
       const int ovf = (ovf0 || longest > MT) ? 1 : 0;
-      a.out_len[b] = m0;
-      a.score[b] = s.score[cur][0];
-      if constexpr (LM == kLmNgram) a.lm_score[b] = ng->lm_sum[cur][0];
+      if constexpr (BIAS) {
+        a.out_len[b] = rlen;
+        a.score[b] = rtop;
+        if constexpr (LM == kLmNgram) a.lm_score[b] = ng->lm_sum[cur][rpos];
+        a.bias_score[b] = bs->bsum[cur][rpos] + bs->final[bs->bstate[cur][rpos]];
+      } else {
+        a.out_len[b] = m0;
+        a.score[b] = s.score[cur][0];
+        if constexpr (LM == kLmNgram) a.lm_score[b] = ng->lm_sum[cur][0];
+      }
       a.stable_len[b] = stable;
       a.overflow[b] = ovf;
       hdr[0] = nb;
@@ -476,11 +588,11 @@ __global__ __launch_bounds__(kThreads) void rnnt_beam_chunk_kernel(BeamArgs<LM, 
   }
 }
 
-// One host path for the four beam entries: an entry fills the arguments it was handed, this states the refusals,
+// One host path for the eight beam entries: an entry fills the arguments it was handed, this states the refusals,
 // the LDS rule and the choice of instantiation.  memory: the workspace; chunk: the state.
-template <int LM, bool CHUNK>
-int rnnt_beam_search(BeamArgs<LM, CHUNK>& a, const StatelessWeights& w, int B, void* memory,
-                     const S2tNgramLmDesc* lm, void* stream) {
+template <int LM, bool CHUNK, bool BIAS>
+int rnnt_beam_search(BeamArgs<LM, CHUNK, BIAS>& a, const StatelessWeights& w, int B, void* memory,
+                     const S2tNgramLmDesc* lm, void* stream, const S2tContextGraphDesc* graph = nullptr) {
   if (B <= 0) return 0;
   bool ok = a.T > 0 && dims_ok(w) && w.V <= kMaxV && a.blank >= 0 && a.blank < w.V && a.beam >= 1 &&
             a.beam <= kMaxBeam && a.topk >= 1 && (a.topk < w.V ? a.topk : w.V) <= kMaxBeam &&
@@ -490,6 +602,8 @@ int rnnt_beam_search(BeamArgs<LM, CHUNK>& a, const StatelessWeights& w, int B, v
     ok = ok && ngram_desc_ok(lm) && lm->V == w.V && __builtin_isfinite(a.lm_weight) && a.lm_score;
     if constexpr (!CHUNK) ok = ok && a.start_ctx >= 0 && a.start_ctx < lm->num_ctx;
   }
+  if constexpr (BIAS)
+    ok = ok && context_desc_ok(graph) && graph->V == w.V && __builtin_isfinite(a.bias_weight) && a.bias_score;
   if (!ok) return -1;
   a.p = w, a.d = w;
   const size_t fixed = beam_fixed_lds(w.E, w.D, w.ctx), lm_bytes = sizeof(float) * (size_t)a.beam * w.V;
@@ -499,9 +613,14 @@ int rnnt_beam_search(BeamArgs<LM, CHUNK>& a, const StatelessWeights& w, int B, v
     a.g = ngram_tables(*lm);
     if constexpr (CHUNK) o_ng = &a.o_ng;
   }
+  long* o_bias = nullptr;
+  if constexpr (BIAS) {
+    a.graph = context_tables(*graph), a.ctx_final = graph->ctx_final;
+    if constexpr (CHUNK) o_bias = &a.o_bias;
+  }
   if constexpr (CHUNK) {
     a.state = static_cast<char*>(memory);
-    a.l = layout(w.V, w.ctx, a.beam, a.max_tokens, o_ng);
+    a.l = layout(w.V, w.ctx, a.beam, a.max_tokens, o_ng, o_bias);
   } else {
     a.records = static_cast<int*>(memory);
     a.lm_spill = reinterpret_cast<float*>(static_cast<char*>(memory) + records_bytes(B, a.T, a.beam));
@@ -510,11 +629,11 @@ int rnnt_beam_search(BeamArgs<LM, CHUNK>& a, const StatelessWeights& w, int B, v
   const size_t smem = fixed + (a.lm_in_lds ? lm_bytes : 0);
   const bool cache = w.V <= 64 * kRegs;
   if constexpr (CHUNK)
-    hipLaunchKernelGGL((cache ? rnnt_beam_chunk_kernel<true, LM> : rnnt_beam_chunk_kernel<false, LM>), dim3(B),
-                       dim3(kThreads), smem, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((cache ? rnnt_beam_chunk_kernel<true, LM, BIAS> : rnnt_beam_chunk_kernel<false, LM, BIAS>),
+                       dim3(B), dim3(kThreads), smem, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL((cache ? rnnt_beam_kernel<true, LM> : rnnt_beam_kernel<false, LM>), dim3(B), dim3(kThreads),
-                       smem, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((cache ? rnnt_beam_kernel<true, LM, BIAS> : rnnt_beam_kernel<false, LM, BIAS>), dim3(B),
+                       dim3(kThreads), smem, (hipStream_t)stream, a);
   S2T_CHECK_LAUNCH();
   return 0;
 }
@@ -557,6 +676,24 @@ extern "C" int s2t_rnnt_stream_reset(void* state, const int* rows, int B, int V,
 extern "C" int s2t_rnnt_ngram_stream_reset(void* state, const int* rows, int B, int V, int ctx, int beam_size,
                                            int max_tokens, int blank, int start_ctx, void* stream) {
   return rnnt_reset(state, rows, B, V, ctx, beam_size, max_tokens, blank, true, start_ctx, stream);
+}
+
+extern "C" long s2t_rnnt_bias_stream_state_bytes(int B, int V, int ctx, int beam_size, int max_tokens) {
+  return state_bytes(B, V, ctx, beam_size, max_tokens, false, true);
+}
+
+extern "C" long s2t_rnnt_ngram_bias_stream_state_bytes(int B, int V, int ctx, int beam_size, int max_tokens) {
+  return state_bytes(B, V, ctx, beam_size, max_tokens, true, true);
+}
+
+extern "C" int s2t_rnnt_bias_stream_reset(void* state, const int* rows, int B, int V, int ctx, int beam_size,
+                                          int max_tokens, int blank, void* stream) {
+  return rnnt_reset(state, rows, B, V, ctx, beam_size, max_tokens, blank, false, 0, stream, true);
+}
+
+extern "C" int s2t_rnnt_ngram_bias_stream_reset(void* state, const int* rows, int B, int V, int ctx, int beam_size,
+                                                int max_tokens, int blank, int start_ctx, void* stream) {
+  return rnnt_reset(state, rows, B, V, ctx, beam_size, max_tokens, blank, true, start_ctx, stream, true);
 }
 
 // ------------------------------------------------------------------------------------ the searches
@@ -634,4 +771,70 @@ extern "C" int s2t_rnnt_beam_stateless_ngram_chunk(const S2tNgramLmDesc* lm, con
   a.lm_weight = lm_weight, a.lm_score = lm_score;
   return rnnt_beam_search(a, stateless_weights(emb, conv_w, lin_w, lin_b, pre_w, pre_b, V, E, D, ctx, act), B,
                           state, lm, stream);
+}
+
+// ------------------------------------------------------------------------------------ with hotwords
+extern "C" int s2t_rnnt_beam_stateless_bias(const S2tContextGraphDesc* graph, const float* am, const long* lengths,
+                                            const float* emb, const float* conv_w, const float* lin_w,
+                                            const float* lin_b, const float* pre_w, const float* pre_b, int B, int T,
+                                            int V, int E, int D, int ctx, int act, int blank, int beam_size,
+                                            int cutoff_top_k, float bias_weight, void* workspace, long* tokens,
+                                            long* frames, long* out_len, float* score, float* bias_score,
+                                            void* stream) {
+  BeamArgs<kLmNone, false, true> a{};
+  beam_head(a, am, lengths, T, blank, beam_size, cutoff_top_k, tokens, frames, out_len, score);
+  a.bias_weight = bias_weight, a.bias_score = bias_score;
+  return rnnt_beam_search(a, stateless_weights(emb, conv_w, lin_w, lin_b, pre_w, pre_b, V, E, D, ctx, act), B,
+                          workspace, nullptr, stream, graph);
+}
+
+extern "C" int s2t_rnnt_beam_stateless_ngram_bias(const S2tNgramLmDesc* lm, const S2tContextGraphDesc* graph,
+                                                  const float* am, const long* lengths, const float* emb,
+                                                  const float* conv_w, const float* lin_w, const float* lin_b,
+                                                  const float* pre_w, const float* pre_b, int B, int T, int V, int E,
+                                                  int D, int ctx, int act, int blank, int beam_size, int cutoff_top_k,
+                                                  float lm_weight, int start_ctx, float bias_weight, void* workspace,
+                                                  long* tokens, long* frames, long* out_len, float* score,
+                                                  float* lm_score, float* bias_score, void* stream) {
+  BeamArgs<kLmNgram, false, true> a{};
+  beam_head(a, am, lengths, T, blank, beam_size, cutoff_top_k, tokens, frames, out_len, score);
+  a.lm_weight = lm_weight, a.start_ctx = start_ctx, a.lm_score = lm_score;
+  a.bias_weight = bias_weight, a.bias_score = bias_score;
+  return rnnt_beam_search(a, stateless_weights(emb, conv_w, lin_w, lin_b, pre_w, pre_b, V, E, D, ctx, act), B,
+                          workspace, lm, stream, graph);
+}
+
+extern "C" int s2t_rnnt_beam_stateless_bias_chunk(const S2tContextGraphDesc* graph, const float* am,
+                                                  const long* chunk_len, const float* emb, const float* conv_w,
+                                                  const float* lin_w, const float* lin_b, const float* pre_w,
+                                                  const float* pre_b, int B, int Tc, int V, int E, int D, int ctx,
+                                                  int act, int blank, int beam_size, int cutoff_top_k,
+                                                  float bias_weight, int max_tokens, void* state, long* tokens,
+                                                  long* frames, long* out_len, float* score, float* bias_score,
+                                                  long* stable_len, int* overflow, void* stream) {
+  BeamArgs<kLmNone, true, true> a{};
+  beam_head(a, am, chunk_len, Tc, blank, beam_size, cutoff_top_k, tokens, frames, out_len, score);
+  a.max_tokens = max_tokens, a.stable_len = stable_len, a.overflow = overflow;
+  a.bias_weight = bias_weight, a.bias_score = bias_score;
+  return rnnt_beam_search(a, stateless_weights(emb, conv_w, lin_w, lin_b, pre_w, pre_b, V, E, D, ctx, act), B,
+                          state, nullptr, stream, graph);
+}
+
+extern "C" int s2t_rnnt_beam_stateless_ngram_bias_chunk(const S2tNgramLmDesc* lm, const S2tContextGraphDesc* graph,
+                                                        const float* am, const long* chunk_len, const float* emb,
+                                                        const float* conv_w, const float* lin_w, const float* lin_b,
+                                                        const float* pre_w, const float* pre_b, int B, int Tc, int V,
+                                                        int E, int D, int ctx, int act, int blank, int beam_size,
+                                                        int cutoff_top_k, float lm_weight, float bias_weight,
+                                                        int max_tokens, void* state, long* tokens, long* frames,
+                                                        long* out_len, float* score, float* lm_score,
+                                                        float* bias_score, long* stable_len, int* overflow,
+                                                        void* stream) {
+  BeamArgs<kLmNgram, true, true> a{};
+  beam_head(a, am, chunk_len, Tc, blank, beam_size, cutoff_top_k, tokens, frames, out_len, score);
+  a.max_tokens = max_tokens, a.stable_len = stable_len, a.overflow = overflow;
+  a.lm_weight = lm_weight, a.lm_score = lm_score;
+  a.bias_weight = bias_weight, a.bias_score = bias_score;
+  return rnnt_beam_search(a, stateless_weights(emb, conv_w, lin_w, lin_b, pre_w, pre_b, V, E, D, ctx, act), B,
+                          state, lm, stream, graph);
 }

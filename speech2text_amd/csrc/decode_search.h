@@ -9,6 +9,8 @@
 //                one row (8 waves); the (parent, class) record of every kept beam goes to a functor.
 //                Its LM mode kLmNgram adds the back-off n-gram term of ngram_lookup.h to the candidates
 //                (s2t_rnnt_beam_stateless_ngram and its chunk form); kLmNone is the search as it was.
+//                Its switch BIAS adds the hotword graph's term behind that, in either LM mode
+//                (s2t_rnnt_beam_stateless_bias, s2t_rnnt_beam_stateless_ngram_bias and their chunk forms).
 // Both take the search state by reference and leave it as the next frame needs it, and read the
 // predictor from the two parts of StatelessWeights, the one place that names its fields.  The limits, the record and
 // candidate ranking are decode_records.h's.
@@ -171,6 +173,48 @@ struct RnntNgramShared {           // the n-gram mode's part of the beams and of
   float cq[kMaxCand];              // ... and the look-up's value (blank: 0)
 };
 
+struct RnntBiasShared {            // the hotword mode's part of the beams and of the candidates
+  NgramTables g;                   // the graph in the n-gram's table form (ngram_lookup.h context_tables)
+  const float* final;              // ctx_final [num_ctx]
+  int bstate[2][kMaxBeam];         // graph state of each beam, double-buffered like score
+  float bsum[2][kMaxBeam];         // unweighted sum of the look-ups a beam was extended by (bias_sum)
+  int cnext[kMaxCand];             // per candidate: the state its look-up returned (blank: the parent's)
+  float cd[kMaxCand];              // ... and the look-up's value (blank: 0)
+};
+
+// The bias term of candidate q of the beam at `parent`, by the thread that ran the n-gram's look-up for it
+// (after that): look = a class other than blank in a round that is not empty.  The candidate's score takes
+// bias_weight * d as one more fp32 add behind what it holds.
+__device__ __forceinline__ void bias_candidate(RnntBiasShared& bs, float* cscore, int cur, int q, int parent, int cls,
+                                               bool look, float bias_weight) {
+  const int pst = bs.bstate[cur][parent];
+  NgramHit hit{0.f, pst};                                  // blank, or an empty round: no term, no look-up
+  if (look) {
+    hit = ngram_score(bs.g, pst, cls);
+    cscore[q] = __fadd_rn(cscore[q], __fmul_rn(bias_weight, hit.logp));
+  }
+  bs.cd[q] = hit.logp;
+  bs.cnext[q] = hit.next;
+}
+
+// The finalisation's pick among the nb live beams of buffer cur: the largest score + bias_weight *
+// ctx_final[bstate], ties to the lower position; *top is that value.  Every thread may call it (LDS and
+// table reads only); nothing of it is stored in the beams.
+__device__ __forceinline__ int bias_pick(const RnntBiasShared& bs, const float* score, int cur, int nb,
+                                         float bias_weight, float* top) {
+  int pos = 0;
+  float best = 0.f;
+  for (int i = 0; i < nb; ++i) {
+    const float v = __fadd_rn(score[i], __fmul_rn(bias_weight, bs.final[bs.bstate[cur][i]]));
+    if (i == 0 || v > best) {
+      best = v;
+      pos = i;
+    }
+  }
+  *top = best;
+  return pos;
+}
+
 // LDS of a beam workgroup besides BeamShared: e [kGroup][E], h [kGroup][D], state [2][kMaxBeam][ctx]
 // (most recent token last), then lm [beam][V] when it fits next to them.
 __host__ __device__ inline size_t beam_fixed_lds(int E, int D, int ctx) {
@@ -308,11 +352,17 @@ __device__ inline void recompute_lm(const StatelessPointers& p, const StatelessD
 // the candidate's score, as (beam score + log-probability) + lm_weight * q in fp32, and C hands the
 // kept beams the look-up's context and lm_sum + q; a blank candidate keeps its parent's context and
 // sum.  The cut to top-k, the ranking, the records and D are the same code in both modes.
-template <bool CACHE, int LM = kLmNone, typename C, typename Rec>
+// BIAS (bs, bias_weight given; bs->g, bs->final and bs->bstate / bsum [cur] filled): the same thread then adds
+// bias_weight * d, (d, next) = the graph's look-up from the parent's state, behind the LM term, and C hands
+// the kept beams next and bsum + d; blank keeps the parent's.  Without an LM the candidate phase and its
+// barrier exist for the bias alone; with the n-gram every bias LDS write stands beside the n-gram's write of
+// the same kind, under the barriers that were there.
+template <bool CACHE, int LM = kLmNone, bool BIAS = false, typename C, typename Rec>
 __device__ __forceinline__ void beam_walk(const StatelessPointers& p, const StatelessDims& d, const C& c, BeamShared& s,
                                           const float* __restrict__ amb, int Tb, int& nb, int& cur, float* e,
                                           float* h, int* state, float* lm, Rec rec,
-                                          RnntNgramShared* ng = nullptr, float lm_weight = 0.f) {
+                                          RnntNgramShared* ng = nullptr, float lm_weight = 0.f,
+                                          RnntBiasShared* bs = nullptr, float bias_weight = 0.f) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int V = d.V, K = min(c.topk, V), BS = c.beam;
   float am_cur[kRegs] = {}, am_next[kRegs] = {};
@@ -392,6 +442,15 @@ __device__ __forceinline__ void beam_walk(const StatelessPointers& p, const Stat
         }
         ng->cq[q] = hit.logp;
         ng->cnext[q] = hit.next;
+        if constexpr (BIAS)
+          bias_candidate(*bs, s.cscore, cur, q, q / K, cls, cls != c.blank && sc != S2T_NEG_INF, bias_weight);
+      }
+      __syncthreads();
+    } else if constexpr (BIAS) {                           // ---- the bias term alone: a thread per candidate
+      for (int q = tid; q < nb * K; q += kThreads) {
+        const int cls = s.ccls[q];
+        bias_candidate(*bs, s.cscore, cur, q, q / K, cls, cls != c.blank && s.cscore[q] != S2T_NEG_INF,
+                       bias_weight);
       }
       __syncthreads();
     }
@@ -412,6 +471,10 @@ __device__ __forceinline__ void beam_walk(const StatelessPointers& p, const Stat
         if constexpr (LM == kLmNgram) {
           ng->ctx[nxt][lane] = ng->cnext[q];
           ng->lm_sum[nxt][lane] = ng->lm_sum[cur][parent] + ng->cq[q];
+        }
+        if constexpr (BIAS) {
+          bs->bstate[nxt][lane] = bs->cnext[q];
+          bs->bsum[nxt][lane] = bs->bsum[cur][parent] + bs->cd[q];
         }
         rec(t, lane, pack_record(parent, cls));
         const int* so = state + (cur * kMaxBeam + parent) * d.ctx;

@@ -35,6 +35,8 @@ RNN-LM search across chunks with a trie that does not grow with the stream (s2t_
 s2t_ctc_prefix_beam_lm_chunk).  The plain and the n-gram search also take hotwords, a ContextGraph of phrases
 to boost: that surface is model/ctc_bias.py (this module's public names and signatures are pinned), which sets
 the `_context` that CtcPrefixBeamDecoding's host loop and dispatch read.
+The one-launch RNN-T beam search of the stateless predictor takes hotwords the same way, without an LM or with
+the n-gram: model/rnnt_bias.py, which sets the `_context` that RnntBeamDecoding's host loops and dispatch read.
 The lexicon CTC beam decoder (it wraps flashlight) and the CIF decoder are
 not here."""
 import abc
@@ -847,6 +849,7 @@ class RnntBeamDecoding(_BatchDecoding):
         self._lm = lm
         self._lm_weight = float(lm_weight)
         self._lm_start_token = None if lm_start_token is None else _lm_start_arg(lm_start_token)
+        self._context, self._context_weight = None, 0.0    # (hotwords: RnntBiasBeamDecoding sets them)
         assert hasattr(self._predictor, "streaming_step") and hasattr(self._joiner, "streaming_step"), \
             "Predictor and Joiner should impl streaming_step for decoding."
 
@@ -864,7 +867,10 @@ class RnntBeamDecoding(_BatchDecoding):
     def _module_loop(self, hidden_states):
         """(1,T,D) -> (tokens, frames, score) of the best beam: the reference's loop (:350-425)
         against init_state / streaming_step only, in plain torch on whatever device the inputs
-        live.  Scores are accumulated in fp32 on that device (beam score + log-probability)."""
+        live.  Scores are accumulated in fp32 on that device (beam score + log-probability).  With a
+        context (RnntBiasBeamDecoding): `_module_loop_lm` without the LM term, and its five results."""
+        if self._context is not None:
+            return self._module_loop_lm(hidden_states)
         dev = hidden_states.device
         blk = torch.zeros((1, 1), dtype=torch.int64, device=dev)
         pred_out, pred_state = self._predictor.streaming_step(blk, self._predictor.init_state())
@@ -893,13 +899,23 @@ class RnntBeamDecoding(_BatchDecoding):
         """_module_loop with the LM term -> (tokens, frames, score, lm_score) of the best beam, over
         predictor.streaming_step, joiner.streaming_step and lm.score_step.  Scores are accumulated
         on the inputs' device in fp32 (fp64 where the modules compute in it) as (beam score +
-        log-probability) + lm_weight * q, the order of the device search."""
+        log-probability) + lm_weight * q, the order of the device search.
+        With a context (a ContextGraph, through init_states / start_scores / score_step / final_scores; the LM
+        may then be None): a candidate of class c != blank scores bias_weight * d more, behind the LM term,
+        d = the graph's look-up from the beam's state; the reported beam is the one with the largest score +
+        bias_weight * final_scores(state), ties to the lower position -> (tokens, frames, that value, lm_score,
+        bias_score = the beam's sum of d + final_scores(state))."""
         dev = hidden_states.device
         lm, weight = self._lm, self._lm_weight
+        graph, bias_weight = self._context, self._context_weight
         blk = torch.zeros((1, 1), dtype=torch.int64, device=dev)
         pred_out, pred_state = self._predictor.streaming_step(blk, self._predictor.init_state())
-        lm_state, q = lm.init_states(1), None              # q None: all zeros (no start token)
-        if self._lm_start_token is not None:
+        lm_state, q = (lm.init_states(1), None) if lm is not None else (None, None)   # q None: all zeros
+        bstates = graph.init_states(1).to(dev) if graph is not None else None
+        bias_sums = None
+        if lm is None:
+            pass
+        elif self._lm_start_token is not None:
             q, lm_state = lm.score_step(torch.full((1,), self._lm_start_token, dtype=torch.int64, device=dev),
                                         lm_state)
         elif hasattr(lm, "start_scores"):                  # (an n-gram scores the first token too)
@@ -912,27 +928,51 @@ class RnntBeamDecoding(_BatchDecoding):
             log_probs = log_probs.to(torch.promote_types(log_probs.dtype, torch.float32))
             if scores is None:
                 scores, lm_sums = log_probs.new_zeros(1), log_probs.new_zeros(1)
+                bias_sums = log_probs.new_zeros(1)
             k = min(int(self._cutoff_top_k), log_probs.shape[-1])
             vals, cls = torch.sort(log_probs, dim=-1, descending=True, stable=True)
             vals, cls = vals[:, :k], cls[:, :k]
             qs = torch.cat([torch.zeros_like(log_probs[:1]) if b[5] is None else b[5].to(log_probs.dtype)
                             for b in beams], dim=0)
             qv = torch.where(cls != 0, qs.gather(1, cls), torch.zeros_like(vals))   # blank: no LM term
-            cand = ((scores.unsqueeze(1) + vals) + weight * qv).flatten()   # index = parent * k + rank
+            cand = scores.unsqueeze(1) + vals                      # index = parent * k + rank
+            if lm is not None:
+                cand = cand + weight * qv
+            if graph is not None:
+                ds = graph.start_scores(bstates).to(device=dev, dtype=log_probs.dtype)
+                dv = torch.where(cls != 0, ds.gather(1, cls), torch.zeros_like(vals))   # blank: no bias term
+                cand = cand + bias_weight * dv
+                cand_bias = (bias_sums.unsqueeze(1) + dv).flatten()
+            cand = cand.flatten()
             cand_lm = (lm_sums.unsqueeze(1) + qv).flatten()
             scores, pick = torch.sort(cand, descending=True, stable=True)
             scores, pick = scores[:self._beam_size], pick[:self._beam_size]
             lm_sums = cand_lm[pick]
-            new_beams = []
+            new_beams, new_bstates = [], []
             for p, c in zip(pick.tolist(), cls.flatten()[pick].tolist()):
                 tokens, frames, state, out, lm_state, q = beams[p // k]
+                bstate = bstates[p // k:p // k + 1] if graph is not None else None
                 if c != 0:
                     tok = torch.full((1, 1), c, dtype=torch.int64, device=dev)
                     out, state = self._predictor.streaming_step(tok, state)
-                    q, lm_state = lm.score_step(tok.reshape(1), lm_state)
+                    if lm is not None:
+                        q, lm_state = lm.score_step(tok.reshape(1), lm_state)
+                    if graph is not None:
+                        bstate = graph.score_step(tok.reshape(1), bstate)[1].to(dev)
                     tokens, frames = tokens + (c,), frames + (t,)
                 new_beams.append((tokens, frames, state, out, lm_state, q))
+                new_bstates.append(bstate)
             beams = new_beams
+            if graph is not None:
+                bias_sums, bstates = cand_bias[pick], torch.cat(new_bstates)
+        if graph is not None:
+            if scores is None:
+                return [], [], 0.0, 0.0, 0.0
+            fin = graph.final_scores(bstates).to(device=dev, dtype=scores.dtype)
+            total = scores + bias_weight * fin
+            pos = int(torch.sort(total, descending=True, stable=True)[1][0])
+            return (list(beams[pos][0]), list(beams[pos][1]), float(total[pos]), float(lm_sums[pos]),
+                    float(bias_sums[pos] + fin[pos]))
         if scores is None:
             return [], [], 0.0, 0.0
         return list(beams[0][0]), list(beams[0][1]), float(scores[0]), float(lm_sums[0])
@@ -946,6 +986,12 @@ class RnntBeamDecoding(_BatchDecoding):
         whole-utterance function, its arguments after the modules).  A new search is a row here."""
         from speech2text_amd.model.lm.rnn_lm import RnnLm
         lm, lstm, sizes = self._lm, self._lstm_search(), (self._beam_size, self._cutoff_top_k)
+        if self._context is not None:                      # hotwords: the one-workgroup search alone
+            from speech2text_amd.model.rnnt_bias import rnnt_beam_bias_tokens_from_am
+            serves = self._fusable() and self._context.dtype == torch.float32 and (lm is None or (
+                _is_ngram(lm) and self._lm_start_token is None and lm.dtype == torch.float32))
+            return [(serves, True, rnnt_beam_bias_tokens_from_am,
+                     (self._context, self._context_weight, lm, self._lm_weight) + sizes)]
         if lm is None:
             return [(self._fusable(), True, rnnt_beam_tokens_from_am, sizes),
                     (lstm, False, rnnt_beam_lstm_tokens_from_am, sizes)]
@@ -963,9 +1009,11 @@ class RnntBeamDecoding(_BatchDecoding):
         """(B,T,D) encoder output -> (tokens (B,T), frames (B,T), out_len (B), score (B)) of the
         best beam per utterance, and with an LM its lm_score (B).  The fused device search where the
         modules allow it (and `fused` is left on), else the module loop per utterance."""
-        dev, with_lm = hidden_states.device, self._lm is not None
+        dev, with_lm, with_bias = hidden_states.device, self._lm is not None, self._context is not None
         if with_lm:
             self._lm_to(dev)
+        if with_bias:
+            self._context.to(dev)
         searches = self._device_searches() if fused and hidden_states.is_cuda else []
         for serves, whole_batch, search, args in searches:
             if not serves:
@@ -983,9 +1031,12 @@ class RnntBeamDecoding(_BatchDecoding):
         out_len = torch.zeros((B,), dtype=torch.int64)
         score = torch.zeros((B,), dtype=torch.float32)
         lm_score = torch.zeros((B,), dtype=torch.float32)
+        bias_score = torch.zeros((B,), dtype=torch.float32)
         for b in range(B):
             n = max(0, min(int(inputs_length[b]), T))
-            if with_lm:
+            if with_bias:
+                tok, frm, score[b], lm_score[b], bias_score[b] = self._module_loop_lm(hidden_states[b:b + 1, :n, :])
+            elif with_lm:
                 tok, frm, score[b], lm_score[b] = self._module_loop_lm(hidden_states[b:b + 1, :n, :])
             else:
                 tok, frm, score[b] = self._module_loop(hidden_states[b:b + 1, :n, :])
@@ -993,7 +1044,8 @@ class RnntBeamDecoding(_BatchDecoding):
             tokens[b, :len(tok)] = torch.tensor(tok, dtype=torch.int64)
             frames[b, :len(frm)] = torch.tensor(frm, dtype=torch.int64)
         out = (tokens.to(dev), frames.to(dev), out_len.to(dev), score.to(dev))
-        return out + (lm_score.to(dev),) if with_lm else out
+        out = out + (lm_score.to(dev),) if with_lm else out
+        return out + (bias_score.to(dev),) if with_bias else out
 
     @torch.no_grad()
     def decode_batch(self, hidden_states, inputs_length):

@@ -44,7 +44,8 @@ class AsrMetricConfig:
     "ctc_prefix_beam_search" (also a name of this project: the reference's CTC beam decoder needs a
     lexicon decoder of a library) scores a CTC head with CtcPrefixBeamDecoding(beam_size,
     cutoff_top_k), lexicon-free and with equal prefixes merged; it takes the same `lm`, lm_weight and
-    lm_start_token, and AsrMetric's `context` / `context_weight` (hotwords: the `metric.hotwords` key)."""
+    lm_start_token.  Both beam methods take AsrMetric's `context` / `context_weight` (hotwords: the
+    `metric.hotwords` key; CtcBiasPrefixBeamDecoding / RnntBiasBeamDecoding); the greedy methods raise for one."""
     decode_method: str = "ctc_greedy_search"
     max_token_step: int = 5
     beam_size: int = 4
@@ -57,9 +58,9 @@ class AsrMetric(object):
     def __init__(self, tokenizer, config: AsrMetricConfig, predictor=None, joiner=None, lm=None, context=None,
                  context_weight=1.0):
         self._tokenizer = tokenizer
-        if context is not None and config.decode_method != "ctc_prefix_beam_search":
-            raise ValueError("hotwords bias the CTC prefix beam search: metric.decode_method must be "
-                             "ctc_prefix_beam_search")
+        if context is not None and config.decode_method not in ("ctc_prefix_beam_search", "rnnt_beam_search"):
+            raise ValueError("hotwords bias the beam searches: metric.decode_method must be ctc_prefix_beam_search or "
+                             "rnnt_beam_search")
         self._lm = lm                  # held here, not by the task: no parameter of the task
         if config.decode_method == "ctc_greedy_search":
             self._decode_sess = CtcGreedyDecoding(tokenizer=tokenizer)
@@ -68,11 +69,14 @@ class AsrMetric(object):
                                                    joiner=joiner,
                                                    max_token_step=config.max_token_step)
         elif config.decode_method == "rnnt_beam_search":
-            self._decode_sess = RnntBeamDecoding(tokenizer=tokenizer, predictor=predictor,
-                                                 joiner=joiner, beam_size=config.beam_size,
-                                                 cutoff_top_k=config.cutoff_top_k, lm=lm,
-                                                 lm_weight=config.lm_weight,
-                                                 lm_start_token=config.lm_start_token)
+            from speech2text_amd.model.rnnt_bias import RnntBiasBeamDecoding
+            search = RnntBeamDecoding if context is None else RnntBiasBeamDecoding
+            bias = {} if context is None else dict(context=context, context_weight=context_weight)
+            self._decode_sess = search(tokenizer=tokenizer, predictor=predictor,
+                                       joiner=joiner, beam_size=config.beam_size,
+                                       cutoff_top_k=config.cutoff_top_k, lm=lm,
+                                       lm_weight=config.lm_weight,
+                                       lm_start_token=config.lm_start_token, **bias)
         elif config.decode_method == "ctc_prefix_beam_search":
             from speech2text_amd.model.ctc_bias import CtcBiasPrefixBeamDecoding
             search = CtcPrefixBeamDecoding if context is None else CtcBiasPrefixBeamDecoding

@@ -58,7 +58,7 @@ class _Raw:
     def __init__(self, path, N):
         self.N, lib = N, ctypes.CDLL(path)
         for name, proto in N.parse_header().items():
-            if name.startswith("s2t_rnnt_"):
+            if name.startswith("s2t_rnnt_") and hasattr(lib, name):   # (the parent's library lacks newer entries)
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = proto
                 setattr(self, name[4:], fn)
@@ -194,24 +194,16 @@ def _bits_equal(tree, parent, dev):
     return len(cases), not differ, differ
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--runs", type=int, default=20)
-    ap.add_argument("--parent-lib", required=True, help="another build of libs2t_mi355.so: the parent commit's")
-    ap.add_argument("--label", default=None, help="kept in the JSON line")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rnnt_stateless.jsonl"))
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("time_rnnt_stateless.py measures on the GPU; there is none here")
+def bench_inputs(dev):
+    """tools/bench_rnnt_ngram.py's inputs -> (predictor, joiner, their _Predictor, am (16, 250, 128) with the blank's
+    lift bisected so that the plain beam search emits about 40 tokens an utterance, lengths, the order-3 NgramLm)."""
     from bench_ctc_ngram import token_text
-    from speech2text_amd import _native as N
     from speech2text_amd.model.decoding import _stateless_weights, rnnt_beam_tokens_from_am
     from speech2text_amd.model.joiner.joiner import Joiner, JoinerConfig
     from speech2text_amd.model.lm.ngram_lm import NgramLm
     from speech2text_amd.model.predictor.predictor import Predictor
-    dev = torch.device("cuda:0")
-    V, B, T, lm_w = 128, 16, 250, 0.3
-    torch.manual_seed(0)                                   # tools/bench_rnnt_ngram.py's inputs
+    V, B, T = 128, 16, 250
+    torch.manual_seed(0)
     pred = Predictor({"model": "Stateless", "config": {"num_symbols": V, "output_dim": 256, "symbol_embedding_dim": 512,
                                                        "context_size": 5}})
     join = Joiner(JoinerConfig(input_dim=256, output_dim=V, activation="relu", prune_range=5, use_out_project=False))
@@ -231,7 +223,22 @@ def main():
         n = float(rnnt_beam_tokens_from_am(am, lens, pred, join, BEAM, TOPK)[2].float().mean())
         lo, hi = (mid, hi) if n > 40 else (lo, mid)
     w, _, _, _, act = _stateless_weights(pred, join)
-    p = _Predictor(w, act, dev)
+    return pred, join, _Predictor(w, act, dev), am, lens, ngram
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=20)
+    ap.add_argument("--parent-lib", required=True, help="another build of libs2t_mi355.so: the parent commit's")
+    ap.add_argument("--label", default=None, help="kept in the JSON line")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rnnt_stateless.jsonl"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("time_rnnt_stateless.py measures on the GPU; there is none here")
+    from speech2text_amd import _native as N
+    dev = torch.device("cuda:0")
+    V, B, T, lm_w = 128, 16, 250, 0.3
+    _, _, p, am, lens, ngram = bench_inputs(dev)
     desc, keep = ngram.desc()
     lm = (desc, int(ngram.start_ctx))
 
